@@ -10,12 +10,15 @@ samples (image+text pairs)/s; image-only and text-only rates and the kNN scan ar
 Multi-GPU: encode = replicas only (no collective; weak scaling: every rank encodes its own batches).
 kNN = row-sharded index, one all-gather of per-shard top-k + merge (RCCL), also weak (fixed rows per GPU).
 
-The line is only printed when every parity gate holds; otherwise the process exits non-zero (fail closed):
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, `--dump-outputs` if given, the line.  Every
+row of the timed batch must be finite and unit-norm, and no launch may have overflowed the fp16 residual stream.  `--full` adds
+everything else (per-kernel timings, image-only / text-only rates, text A/B, host-buffer leg, CPU baselines, kNN, pipeline, IVF)
+and its gates; the line is only printed when every gate of the run holds, otherwise the process exits non-zero (fail closed):
   * encode: all 256 image and text rows of the timed batch against the fp32 CPU oracle (cosine >= 1 - 1e-3);
   * kNN:    planted neighbours are the top hit at full scale, exact id lists against the numpy oracle on the first 1 M
             rows, id sets against a chunked torch fp32 matmul + topk over the whole index.
 
-    python bench.py [--gpus N --steps K --warmup W]          # N>1: launched by torch.distributed.run
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]   # N>1: launched by torch.distributed.run
 """
 import argparse
 import json
@@ -155,6 +158,23 @@ def headline_numbers(line):
     return h, [ln[:330] for ln in out[:12]]
 
 
+DUMP_BYTES_PER_ARRAY = 16 << 20  # four arrays: at most 64 MB in all
+
+
+def dump_outputs(folder, tensors):
+    """Each tensor as folder/<name>.npy in float32.  An array above DUMP_BYTES_PER_ARRAY keeps a fixed, seeded sample of its rows
+    (sorted row indices from default_rng(0); the default batch of 256 x 768 is written whole)."""
+    import numpy as np
+
+    os.makedirs(folder, exist_ok=True)
+    for name, t in tensors.items():
+        a = t.float().cpu().numpy()
+        if a.nbytes > DUMP_BYTES_PER_ARRAY:
+            keep = np.sort(np.random.default_rng(0).choice(len(a), DUMP_BYTES_PER_ARRAY // a[0].nbytes, replace=False))
+            a = a[keep]
+        np.save(os.path.join(folder, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def pipeline_leg(model, value, device, shards_n=8, per_shard=2048, workers=16, log=lambda m: None):
     """BASELINE configs[3]'s single-GPU share: synthetic tar shards in /dev/shm (seeded, untimed) ->
     `worker()` -> WebdatasetReader (decode processes) -> pipelined Runner -> ClipMapper (asynchronous tickets of the C ABI) ->
@@ -278,8 +298,16 @@ def main():
     ap.add_argument("--ivf-rows", type=int, default=125_000_000)
     ap.add_argument("--no-pipeline", dest="pipeline", action="store_false", help="skip BASELINE config 4's single-GPU share (tar shards -> "
                     "worker() -> reader -> pipelined Runner -> writer, pre-decoded uint8 and JPEG members; embedded as `pipeline`, ~30 s)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline encode figure: per-kernel timings, image-only / "
+                    "text-only rates, the ragged / rectangular text A/B, the host-buffer leg, parity against the CPU oracle and the CPU "
+                    "baselines, kNN, pipeline and IVF legs (a few minutes); the --no-* switches above select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the embeddings of the last timed step as DIR/<name>.npy "
+                    "(float32; inputs and weights are seeded, so two builds can be compared output for output)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.profile_run:
+        args.full = True  # the counter passes count the steps of the full run's legs
         args.no_parity, args.no_ab, args.knn_extra, args.ivf, args.cpu_seconds, args.host_path = True, True, False, False, 0.0, False
         args.pipeline = False
     refuse_debug_environment()
@@ -323,8 +351,8 @@ def main():
     arch = ARCHS[args.model]
     B = args.batch
     single = world == 1 and rank == 0
-    want_parity = single and not args.no_parity
-    want_cpu = single and args.cpu_seconds > 0
+    want_parity = single and args.full and not args.no_parity
+    want_cpu = single and args.full and args.cpu_seconds > 0
     failures = []
 
     # ---- weights: random init of the named architecture (no checkpoints exist offline).  At N=1 the SAME blob is loaded
@@ -374,23 +402,29 @@ def main():
     dt = max_over_ranks(time.perf_counter() - t0)
     enc.profile(0)
     value = world * args.steps * B / dt
+    if args.dump_outputs and rank == 0:
+        # what the timed path handed back in its last step: fp16 embeddings (what ClipMapper returns) and their f32 copies
+        dump_outputs(args.dump_outputs, {"image_embeddings": out_i, "text_embeddings": out_t,
+                                         "image_embeddings_f32": o32_i, "text_embeddings_f32": o32_t})
 
-    # per-kernel live timing (hipEvents on the launch stream).  GEMM: recorded inside the timed region above.
+    # per-kernel live timing (hipEvents on the launch stream).  GEMM: recorded inside the timed region above; the other kinds
+    # take extra steps of their own (--full)
     kinds = {"gemm": 0, "attention": 1, "layernorm": 2, "other": 3}
     prof = {}
     n, ms, fl = enc.profile_get(0)
     prof["gemm"] = {"launches": n, "ms": round(ms, 3), "tflops": (fl / (ms * 1e-3) / 1e12) if ms > 0 and fl > 0 else None, "steps": args.steps}
-    enc.profile(PROF_REST)
-    extra_steps = max(2, args.steps // 2)
-    for _ in range(extra_steps):
-        step()
-    barrier()
-    enc.profile(0)
-    for name, kind in kinds.items():
-        if name == "gemm":
-            continue
-        n, ms, fl = enc.profile_get(kind)
-        prof[name] = {"launches": n, "ms": round(ms, 3), "tflops": (fl / (ms * 1e-3) / 1e12) if ms > 0 and fl > 0 else None, "steps": extra_steps}
+    if args.full:
+        enc.profile(PROF_REST)
+        extra_steps = max(2, args.steps // 2)
+        for _ in range(extra_steps):
+            step()
+        barrier()
+        enc.profile(0)
+        for name, kind in kinds.items():
+            if name == "gemm":
+                continue
+            n, ms, fl = enc.profile_get(kind)
+            prof[name] = {"launches": n, "ms": round(ms, 3), "tflops": (fl / (ms * 1e-3) / 1e12) if ms > 0 and fl > 0 else None, "steps": extra_steps}
     g = prof["gemm"]
     gemm_tflops = g["tflops"] or 0.0
     # the committed counter passes were taken on the default workload only
@@ -406,21 +440,22 @@ def main():
                 "traffic": traffic, "traffic_unit": traffic_unit, "traffic_run": "separate --pmc pass" if traffic else None,
                 "traffic_source": "profiles/traffic.json: rocprofv3 --pmc FETCH_SIZE (x2 on gfx950) + WRITE_SIZE passes of this command (tools/gpu_round.sh); counters cannot be read inside the timed run" if traffic else None}
 
-    # image-only / text-only rates (untimed extras)
+    # image-only / text-only rates (untimed extras, --full)
     extras = {}
-    for key, kw in (("images_per_s", dict(img=True, txt=False)), ("texts_per_s", dict(img=False, txt=True))):
-        barrier()
-        t1 = time.perf_counter()
-        for _ in range(max(2, args.steps // 2)):
-            step(**kw)
-        barrier()
-        extras[key] = round(world * max(2, args.steps // 2) * B / max_over_ranks(time.perf_counter() - t1), 1)
+    if args.full:
+        for key, kw in (("images_per_s", dict(img=True, txt=False)), ("texts_per_s", dict(img=False, txt=True))):
+            barrier()
+            t1 = time.perf_counter()
+            for _ in range(max(2, args.steps // 2)):
+                step(**kw)
+            barrier()
+            extras[key] = round(world * max(2, args.steps // 2) * B / max_over_ranks(time.perf_counter() - t1), 1)
     # the headline depends on the caption lengths (the text tower runs on the rows up to each caption's EOT only): print the length
     # distribution and, in the same process, the figure with every row computed (CLIPX_OPT_RAGGED_TEXT = 0)
     tok_len = (ids_host.argmax(axis=1) + 1).astype(np.int64)
     extras["text_rows"] = {"tokens_incl_sot_eot": {"min": int(tok_len.min()), "mean": round(float(tok_len.mean()), 2), "max": int(tok_len.max())},
                            "rows_run": int(tok_len.sum()), "rows_rectangular": int(B * arch.ctx_len)}
-    if enc.get_option(enc.OPT_RAGGED_TEXT) == 1 and not args.no_ab:
+    if enc.get_option(enc.OPT_RAGGED_TEXT) == 1 and args.full and not args.no_ab:
         # same-process A/B, both legs timed the same way (no per-launch events: the headline region above carries two hipEvents per
         # GEMM launch for `roofline`, which costs ~0.5 % -- its `value` is the conservative one)
         ab = {}
@@ -441,7 +476,7 @@ def main():
         extras["value_ragged_text_same_timing"] = round(world * args.steps * B / ab["ragged"], 1)
     enc.check_range(stream)  # CLIPX_E_RANGE: no launch of this run may have overflowed the fp16 residual stream
 
-    if args.host_path:
+    if args.host_path and args.full:
         # What ClipMapper.__call__ includes and `value` does not ("device-only AND including H2D/D2H"): the same batches from
         # pinned HOST buffers -- f32 NCHW pixels + int32 tokens in, fp16 rows out on the host -- through the asynchronous tickets
         # (clipx_encode_*_async / clipx_wait: upload, both towers, download; two steps in flight so that a step's copies overlap its
@@ -475,15 +510,24 @@ def main():
 
     # FLOPs that RUN per step (counters of the launches: GEMMs + attention), not the model formula: the last block's out-proj / MLP
     # (and, in the image tower, all but the first query block of its attention) are computed on the pooled rows only
-    a = prof["attention"]
-    run_tflop = gemm_tflops * g["ms"] / max(args.steps, 1) / 1e3 + ((a["tflops"] or 0.0) * a["ms"] / max(a["steps"], 1) / 1e3)
-    model_tflop = B * (gf_img + gf_txt) / 1e3
-    e2e_tflops = run_tflop / (dt / args.steps)
-    extras["end_to_end_tflops_per_gpu"] = round(e2e_tflops, 1)
-    extras["end_to_end_frac_of_mfma_peak"] = round(e2e_tflops / BF16_PEAK_TFLOPS, 4)
-    extras["tflop_per_step"] = {"run": round(run_tflop, 3), "full_model_formula": round(model_tflop, 3),
-                                "note": "the embedding reads one row per sample of the last block: its out-proj / MLP run on those rows only (bit-identical; CLIPX_FULL_LAST_BLOCK=1 runs every row)"}
-    extras["kernel_ms_per_step"] = {k: round(v["ms"] / v["steps"], 3) for k, v in prof.items()}
+    if args.full:
+        a = prof["attention"]
+        run_tflop = gemm_tflops * g["ms"] / max(args.steps, 1) / 1e3 + ((a["tflops"] or 0.0) * a["ms"] / max(a["steps"], 1) / 1e3)
+        model_tflop = B * (gf_img + gf_txt) / 1e3
+        e2e_tflops = run_tflop / (dt / args.steps)
+        extras["end_to_end_tflops_per_gpu"] = round(e2e_tflops, 1)
+        extras["end_to_end_frac_of_mfma_peak"] = round(e2e_tflops / BF16_PEAK_TFLOPS, 4)
+        extras["tflop_per_step"] = {"run": round(run_tflop, 3), "full_model_formula": round(model_tflop, 3),
+                                    "note": "the embedding reads one row per sample of the last block: its out-proj / MLP run on those rows only (bit-identical; CLIPX_FULL_LAST_BLOCK=1 runs every row)"}
+        extras["kernel_ms_per_step"] = {k: round(v["ms"] / v["steps"], 3) for k, v in prof.items()}
+
+    # every row of the timed batch must be finite and unit-norm (non-finite activations make the chip clock higher and the run "faster")
+    gi = out_i.float().cpu().numpy().astype(np.float64)
+    gt = out_t.float().cpu().numpy().astype(np.float64)
+    for name, g_ in (("image", gi), ("text", gt)):
+        nrm = np.linalg.norm(g_, axis=-1)
+        if not (np.isfinite(g_).all() and np.abs(nrm - 1).max() < 2e-3):
+            failures.append(f"encode sanity: {name} embeddings not finite / not unit norm (max |norm - 1| {np.abs(nrm - 1).max()})")
 
     # ---- parity gate on the benchmark's own weights and inputs, ALL rows of the timed batch (oracle = checker), and
     # the CPU baseline: the same pass of the oracle (transformers.CLIPModel fp32 = the reference's hf_clip backend +
@@ -492,15 +536,8 @@ def main():
     if want_parity:
         from oracle.clip_oracle import mapper_semantics
 
-        gi = out_i.float().cpu().numpy().astype(np.float64)
-        gt = out_t.float().cpu().numpy().astype(np.float64)
-        # every row of the timed batch must be finite and unit-norm (non-finite activations make the chip clock higher and
-        # the run "faster"); `--parity-rows` of them, spread over the batch, go through the oracle (~0.37 s per pair on this
-        # box's 32 threads: 64 rows keep the CPU leg near 25 s; --parity-rows 256 checks them all)
-        for name, g in (("image", gi), ("text", gt)):
-            nrm = np.linalg.norm(g, axis=-1)
-            if not (np.isfinite(g).all() and np.abs(nrm - 1).max() < 2e-3):
-                failures.append(f"encode sanity: {name} embeddings not finite / not unit norm (max |norm - 1| {np.abs(nrm - 1).max()})")
+        # `--parity-rows` rows, spread over the batch, go through the oracle (~0.37 s per pair on 32 threads: 64 rows keep the
+        # CPU leg near 25 s; --parity-rows 256 checks them all)
         from oracle.clip_oracle import NORTH_STAR_BAR, TIGHT_BAR, CENTRED_BAR, parity_report
 
         cb = 8
@@ -558,7 +595,7 @@ def main():
     rows = args.knn_rows
     if rows < 0:
         rows = 125_000_000 if world == 8 else 100_000_000
-    if rows > 0:
+    if rows > 0 and args.full:
         from clip_retrieval_amd.distributed import ShardedIndex
         from clip_retrieval_amd.knn import synth_rows_device
 
@@ -775,14 +812,14 @@ def main():
 
     # ---- BASELINE config 4's single-GPU share: the reference's whole loop around the hot path, wall to wall
     pipeline = None
-    if args.pipeline and single:
+    if args.pipeline and single and args.full:
         pipeline = pipeline_leg(args.model, value, local_rank, log=lambda m: sys.stderr.write(m + "\n"))
         if not (pipeline["u8"]["outputs_ok"] and pipeline["jpeg"]["outputs_ok"]):
             failures.append(f"pipeline leg: written files / shapes / dtypes / row counts are not the writer's: {pipeline}")
 
     # ---- BASELINE config 5 (opt-in: minutes): one GPU's IVF-Flat shard at its stated size, built on the device, served
     ivf = None
-    if args.ivf and single:
+    if args.ivf and single and args.full:
         import importlib.util
 
         enc.close()

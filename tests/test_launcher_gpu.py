@@ -41,7 +41,7 @@ def test_bench_under_the_launcher_at_world_size_1():
     "nccl", the planted queries are broadcast, the timings go through the MAX all-reduce, and -- CLIPX_FORCE_GATHER=1 -- every kNN
     batch goes through all_gather_into_tensor + the merge kernel.  The line must parse, carry the contract's keys and pass its own
     parity gates (a failed gate prints no line)."""
-    r = _launch(["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--knn-rows", "2200000", "--knn-scans", "2", "--knn-batches", "1,64,256",
+    r = _launch(["bench.py", "--full", "--gpus", "1", "--steps", "2", "--warmup", "1", "--knn-rows", "2200000", "--knn-scans", "2", "--knn-batches", "1,64,256",
                  "--no-ivf", "--no-knn-extra", "--no-pipeline", "--parity-rows", "8", "--cpu-seconds", "0", "--no-host-path"],
                 {"CLIPX_FORCE_GATHER": "1"})
     assert r.returncode == 0, r.stderr[-3000:]

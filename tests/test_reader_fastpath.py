@@ -12,7 +12,8 @@ from PIL import Image
 from clip_retrieval_amd import reader as R
 from clip_retrieval_amd.runner import Sampler
 
-REF_TARS = "/root/reference/tests/test_clip_inference/test_tars"
+# the reference's own test shards (tests/test_clip_inference/test_tars), committed as fixtures
+REF_TARS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_clip_inference", "test_tars")
 
 
 def _jpeg(seed, h=40, w=56):
@@ -158,7 +159,6 @@ def test_decode_processes_return_pixels_through_the_arena(tmp_path):
         assert np.array_equal(a, w) and np.array_equal(b, w)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_TARS), reason="reference fixtures are only present in the build container")
 def test_reference_tars_through_both_paths():
     tars = sorted(os.path.join(REF_TARS, f) for f in os.listdir(REF_TARS) if f.endswith(".tar"))
     for t in tars:

@@ -1,10 +1,11 @@
 """The reader pinned to the only reference-held golden VECTORS on the encode path:
-/root/reference/tests/test_clip_inference/test_tensors/{0..3}.pkl are the reference reader's own `image_tensor` batches for
+the reference's tests/test_clip_inference/test_tensors/{0..3}.pkl are its reader's own `image_tensor` batches for
 test_tars/image1.tar + image2.tar (batch size 2, two loader workers; written by the reference's author, consumed by its
 test_mapper.py:31-36).  They need no weights.  CPU: `WebdatasetReader` must yield the same keys, the same batch order and
 composition, and BIT-IDENTICAL tensors (torchvision's arithmetic: x / 255, then (x - mean) / std).  The reference folder does not
-travel to the GPU box, so a fixture DERIVED FROM THE PICKLES ALONE (tests/golden/make_golden_reader_tensors.py: the uint8 crops
-recovered from the tensors + the sha256 of every tensor) is committed; the GPU test holds the device-side normalisation to it."""
+travel with the repository, so a fixture DERIVED FROM THE PICKLES ALONE (tests/golden/make_golden_reader_tensors.py: the uint8 crops
+recovered from the tensors + the sha256 of every tensor) is committed, beside the two tars themselves
+(tests/golden/reference_clip_inference/test_tars); the GPU test holds the device-side normalisation to it."""
 import hashlib
 import os
 import sys
@@ -14,7 +15,7 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
-REF_T = "/root/reference/tests/test_clip_inference"
+REF_T = os.path.join(HERE, "golden", "reference_clip_inference")  # the reference's test_tars, committed as fixtures
 GOLD = os.path.join(HERE, "golden", "reference_reader_tensors.npz")
 
 
@@ -31,20 +32,13 @@ def _normalise(u8):
 
 def test_fixture_reproduces_the_reference_tensors_it_was_made_from():
     """torchvision's arithmetic on the committed uint8 crops gives tensors whose sha256 are the reference pickles' (so the 0.8 MB
-    fixture stands for the 4.2 MB of reference tensors, bit for bit) -- and, when the reference is present, against the pickles."""
+    fixture stands for the 4.2 MB of reference tensors, bit for bit)."""
     names, crops, sizes, shas = _fixture()
     assert sizes == [2, 2, 2, 1] and len(names) == 7 and crops.shape == (7, 224, 224, 3)
     o = 0
     for n, sha in zip(sizes, shas):
         assert hashlib.sha256(_normalise(crops[o:o + n]).tobytes()).digest() == bytes(sha)
         o += n
-    if os.path.isdir(REF_T):
-        from make_golden_reader_tensors import load_reference_batches
-
-        o = 0
-        for (fn, t), n in zip(load_reference_batches(), sizes):
-            assert fn == names[o:o + n] and t.tobytes() == _normalise(crops[o:o + n]).tobytes()
-            o += n
 
 
 def test_restricted_unpickler_refuses_other_globals():
@@ -57,7 +51,6 @@ def test_restricted_unpickler_refuses_other_globals():
         RestrictedUnpickler(io.BytesIO(pickle.dumps(os.getcwd))).load()
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_T), reason="the reference's test_tars are only in the build container")
 @pytest.mark.parametrize("use_processes", [True, False])
 def test_webdataset_reader_yields_the_reference_batches_bit_for_bit(use_processes):
     """tests/test_clip_inference/test_reader.py:9-61's WebdatasetReader call on image1.tar + image2.tar: keys, batch order and
@@ -90,7 +83,6 @@ def test_webdataset_reader_yields_the_reference_batches_bit_for_bit(use_processe
     assert got == [["123_456", "208_495"], ["321_421", "389_535"], ["416_264", "456_123"], ["524_316"]]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_T), reason="the reference's test_tars are only in the build container")
 def test_reference_reader_test_batch_shapes_over_four_tars():
     """The reference's own assertion (test_reader.py:58-61): 4 tars, 2 output partitions, 2 loader workers, batch 2 ->
     [[2, 2, 2], [2, 2, 1]]."""

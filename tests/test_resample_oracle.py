@@ -10,7 +10,8 @@ from PIL import Image
 from clip_retrieval_amd import reader
 from oracle import resample_oracle as ro
 
-REF_IMAGES = "/root/reference/tests/test_clip_inference/test_images"
+# the reference's own test images (tests/test_clip_inference/test_images), committed as fixtures
+REF_IMAGES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_clip_inference", "test_images")
 
 
 def _synthetic(h, w, seed):
@@ -56,7 +57,6 @@ def test_geometry_is_torchvision():
     assert ro.clip_geometry(100, 333, 224) == (745, 224, 260, 0)  # int(round(260.5)) = 260: round half to even, like torchvision
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_IMAGES), reason="reference fixtures are only present in the build container")
 def test_oracle_equals_pillow_on_reference_images():
     names = sorted(f for f in os.listdir(REF_IMAGES) if f.lower().endswith((".jpg", ".jpeg", ".png")))
     assert names

@@ -14,10 +14,10 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_FIX = "/root/reference/tests/test_clip_inference"
+# the reference's own reader fixtures (tests/test_clip_inference/test_images, test_tars), committed as fixtures
+REF_FIX = os.path.join(ROOT, "tests", "golden", "reference_clip_inference")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_FIX), reason="the reference checkout (build container only) holds these fixtures")
 def test_readers_on_the_reference_fixture_files():
     """The reference's own reader test (tests/test_clip_inference/test_reader.py:18-61) on the reference's own files:
     test_images (7 JPEGs) -> [[2, 2], [2, 1]], test_tars (4 tars, 11 samples) -> [[2, 2, 2], [2, 2, 1]] for 2 partitions of

@@ -79,6 +79,19 @@ SIGNATURES = {
     "knnx_ivfb_assign_device": (C.c_int, [_P, _P, C.c_int64, _P]),
     "knnx_ivfb_list_sizes": (C.c_int, [_P, _P, C.c_int]),
     "knnx_ivf_add_assigned_device": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P]),
+    "knnx_ivfpq_set_quantizer": (C.c_int, [_P, C.c_int, _P]),
+    "knnx_ivfpq_add_codes": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P]),
+    "knnx_ivfpq_m": (C.c_int, [_P]),
+    "knnx_ivfpq_get_codes": (C.c_int, [_P, _P, _P, _P]),
+    "knnx_ivfpq_get_codebooks": (C.c_int, [_P, _P]),
+    "knnx_pqb_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
+    "knnx_pqb_destroy": (None, [_P]),
+    "knnx_pqb_set_sample": (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int]),
+    "knnx_pqb_set_sample_device": (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int]),
+    "knnx_pqb_seed_from_sample": (C.c_int, [_P, _P, _P, C.c_int64]),
+    "knnx_pqb_set_codebooks": (C.c_int, [_P, _P]),
+    "knnx_pqb_get_codebooks": (C.c_int, [_P, _P]),
+    "knnx_pqb_lloyd": (C.c_int, [_P, _P, _P]),
     "knnx_synth_rows_device": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_uint64, C.c_int, C.c_int64, _P]),
     "knnx_mlp_create": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "knnx_mlp_forward": (C.c_int, [_P, _P, C.c_int, _P]),

@@ -72,6 +72,8 @@ hipError_t launch_ivf_worklist_from_scores(const float* scores, int nq, int npro
                                            const unsigned* ntile, const unsigned* size, unsigned* off, uint4* work, unsigned* nwork,
                                            hipStream_t st, unsigned work_stride = 0);
 hipError_t launch_ivf_union_tiles(const unsigned* masks, int nblk, int nlist, const unsigned* ntile, unsigned* out, hipStream_t st);
+// the nprobe best lists of every query from a score dump [nq, nlist] -> bit q % 32 of masks[q / 32][l] (masks cleared first)
+hipError_t launch_ivf_select_mark(const float* scores, int nq, int nprobe, int nlist, unsigned* masks, hipStream_t st);
 hipError_t launch_ivf_relayout(const _Float16* src, _Float16* dst, int d, int nlist, const int64_t* src0, const unsigned* tile0,
                                const unsigned* ntile, const unsigned* size, const int64_t* ids, int64_t id_lo, int64_t n_ids,
                                int64_t* idmap, uint32_t* inv, hipStream_t st);
@@ -159,5 +161,31 @@ hipError_t launch_rq8_scan(const int8_t* X8, int64_t N, int d, int nq, int plane
                            unsigned* cnt, unsigned cap, float* hit_s, uint32_t* hit_r, unsigned* lost, int grid, int tstep, hipStream_t st);
 hipError_t launch_i8_proof(int nq, int k, const float* D, const float* thr_lb, const unsigned* cnt, unsigned cap, const unsigned* lost,
                            unsigned* need, unsigned* gate, unsigned long long* stats, hipStream_t st);
+
+// ---- IVF-PQ (knn_pq_kernels.hip): faiss IndexIVFPQ(IndexFlatIP(d), d, nlist, M, 8), inner product, by_residual
+constexpr int PQ_MAX_K = 64;  // k of the ADC scan's candidate queues
+bool pq_supported(int d, int M);  // M in {16, 32, 64, 128}, M | d, d / M <= 64
+// codes[row * M + m] = argmin_j ||r_m - cb[m][j]||^2, r = f32(X[i]) - f32(cent[lists[i]]); row = tile0[lists[i]] * 32 + pos[i] (tile0 == null:
+// row = i); idmap != null: also idmap[row] = id (ids[i], or id0 + i) and inv[id - id_lo] = row
+hipError_t launch_pq_encode(const _Float16* X, int64_t n, int d, int M, const int32_t* lists, const _Float16* cent, const float* cb,
+                            const unsigned* tile0, const int32_t* pos, const int64_t* ids, int64_t id0, int64_t id_lo, int64_t n_ids,
+                            uint8_t* codes, int64_t* idmap, uint32_t* inv, hipStream_t st);
+// one Lloyd update of the codebooks from the sample: order [M][n] (members of each (m, j), ascending row), off [M][257]
+hipError_t launch_pq_update(const _Float16* X, int d, int M, const int32_t* lists, const _Float16* cent, const int32_t* order,
+                            const int32_t* off, int64_t n, float* cb, hipStream_t st);
+hipError_t launch_pq_seed(const _Float16* X, int d, int M, const int32_t* lists, const _Float16* cent, const int32_t* mj, const int64_t* rows,
+                          int64_t n, float* cb, hipStream_t st);
+hipError_t launch_pq_lut(const float* q, int nq, int d, int M, const float* cb, float* lut, hipStream_t st);
+hipError_t launch_pq_probe(const unsigned* masks, const float* scores, int nq, int nlist, int np, unsigned* pcnt, int* probe, float* pscore,
+                           hipStream_t st);
+size_t pq_scan_smem_bytes(int M);
+hipError_t launch_pq_adc_scan(const uint8_t* codes, int M, const float* lut, const int* probe, const float* pscore, const unsigned* pcnt,
+                              int np, int nsplit, const unsigned* tile0, const unsigned* size, const int64_t* idmap, int k, int nq,
+                              float* part_s, uint32_t* part_i, int* part_n, hipStream_t st);
+hipError_t launch_pq_decode(const uint8_t* codes, int d, int M, const float* cb, const _Float16* cent, const unsigned* tile0, int nlist,
+                            int64_t id_lo, int64_t n_ids, const uint32_t* inv, const int64_t* ids, int64_t n, float* out, hipStream_t st);
+hipError_t launch_pq_scatter_codes(const uint8_t* src, int64_t n, int M, const int32_t* lists, const int32_t* pos, const int64_t* ids,
+                                   const unsigned* tile0, int64_t id_lo, int64_t n_ids, uint8_t* codes, int64_t* idmap, uint32_t* inv,
+                                   hipStream_t st);
 
 }  // namespace knnx

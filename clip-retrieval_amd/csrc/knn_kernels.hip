@@ -1374,6 +1374,13 @@ hipError_t launch_ivf_worklist_from_scores(const float* scores, int nq, int npro
   return hipGetLastError();
 }
 
+hipError_t launch_ivf_select_mark(const float* scores, int nq, int nprobe, int nlist, unsigned* masks, hipStream_t st) {
+  hipError_t e = hipMemsetAsync(masks, 0, (size_t)((nq + 31) / 32) * nlist * sizeof(unsigned), st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(ivf_select_mark_kernel, dim3(nq), dim3(1024), 0, st, scores, nlist, nprobe, masks);
+  return hipGetLastError();
+}
+
 hipError_t launch_ivf_worklist(const int64_t* Ic, int nq, int nprobe, int nlist, unsigned* masks, const unsigned* tile0,
                                const unsigned* ntile, const unsigned* size, unsigned* off, uint4* work, unsigned* nwork,
                                hipStream_t st, unsigned work_stride) {

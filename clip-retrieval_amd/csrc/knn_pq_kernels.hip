@@ -1,0 +1,427 @@
+// knn_pq_kernels.hip -- gfx950 kernels of the IVF-PQ index (faiss IndexIVFPQ(IndexFlatIP(d), d, nlist, M, 8), inner product,
+// by_residual): encoding, codebook training, the per-query lookup tables, the ADC list scan with top-k, decoding.
+//
+// Data layout in HBM
+//   codes    u8 [capacity][M]: the list-sorted, tile-padded arena of IVF-Flat with M code bytes per row instead of 2 d
+//   cb       f32 [M][256][ds], ds = d / M: sub-quantiser m, centroid j, component t
+//   lut      f32 [nq][M][256]: LUT[q][m][j] = <q_m, cb[m][j]> (fp32, t in order)
+// A row's residual is r = f32(x_f16) - f32(c_list); its code byte m is argmin_j ||r_m - cb[m][j]||^2 (ties -> smaller j); its
+// score for a query is <q, c_list> + sum_m LUT[m][code_m] (the sum in m order, then added to the coarse score).
+//
+// ADC scan: one workgroup per (query, share of its probed lists), 4 waves.  The query's lookup table (M KiB) is loaded into the
+// LDS once; every lane scores one row per step (M / 16 16-byte code loads, M LDS lookups).  Each WAVE keeps its own candidate
+// queue in the LDS (k + 64 entries, appended through a ballot, pruned to the exact top k by a rank count when full), so the row
+// loop has no workgroup barrier; at the end the four queues are ranked together and the workgroup's top k goes to the partial
+// lists that knn_merge_kernel (launch_merge_u32 with the id map) merges.
+
+#include <hip/hip_runtime.h>
+#include <float.h>
+#include <math.h>
+#include <stdint.h>
+#include <algorithm>
+#include "knn_kernels.h"
+
+namespace knnx {
+
+constexpr int PQ_WQ = PQ_MAX_K + 64;  // entries of one wave's candidate queue
+
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// strict total order of results: score descending, then id ascending
+__device__ __forceinline__ bool pq_better(float sa, long long ia, float sb, long long ib) {
+  return (sa > sb) || (sa == sb && ia < ib);
+}
+
+// ---------------------------------------------------------------------------------------------
+// encode: one row per thread.  Source rows are fp16 with a list id each; the residual is formed in registers.  The workgroup
+// stages sub-quantiser m's 256 centroids in the LDS (every lane reads the same address: broadcast), each lane keeps its
+// residual sub-vector in registers and walks the 256 centroids.  Destination: arena row tile0[list] * 32 + pos[i] (tile0 == null:
+// row i of a plain [n][M] array); idmap / inv written when idmap != null.
+// ---------------------------------------------------------------------------------------------
+template <int DS>
+__global__ __launch_bounds__(256) void pq_encode_kernel(const _Float16* __restrict__ X, int64_t n, int d, int M,
+                                                       const int32_t* __restrict__ lists, const _Float16* __restrict__ cent,
+                                                       const float* __restrict__ cb, const unsigned* __restrict__ tile0,
+                                                       const int32_t* __restrict__ pos, const int64_t* __restrict__ ids, int64_t id0,
+                                                       int64_t id_lo, int64_t n_ids, uint8_t* __restrict__ codes,
+                                                       int64_t* __restrict__ idmap, uint32_t* __restrict__ inv) {
+  extern __shared__ float pq_sc[];  // [256][DS]
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool live = i < n;
+  const int32_t l = live ? lists[i] : 0;
+  const _Float16* xr = X + (size_t)(live ? i : 0) * d;
+  const _Float16* cr = cent + (size_t)l * d;
+  const size_t drow = live ? (tile0 ? (size_t)tile0[l] * 32 + (size_t)pos[i] : (size_t)i) : 0;
+  for (int m = 0; m < M; ++m) {
+    __syncthreads();
+    const float* src = cb + (size_t)m * 256 * DS;
+    for (int e = threadIdx.x; e < 256 * DS; e += 256) pq_sc[e] = src[e];
+    __syncthreads();
+    if (live) {
+      float r[DS];
+#pragma unroll
+      for (int t = 0; t < DS; ++t) r[t] = (float)xr[m * DS + t] - (float)cr[m * DS + t];
+      float best = INFINITY;
+      int bj = 0;
+      for (int j = 0; j < 256; ++j) {
+        float s = 0.f;
+#pragma unroll
+        for (int t = 0; t < DS; ++t) {
+          const float df = r[t] - pq_sc[j * DS + t];
+          s = fmaf(df, df, s);
+        }
+        if (s < best) { best = s; bj = j; }
+      }
+      codes[drow * M + m] = (uint8_t)bj;
+    }
+  }
+  if (live && idmap) {
+    const int64_t id = ids ? ids[i] : id0 + i;
+    idmap[drow] = id;
+    if (id >= id_lo && id - id_lo < n_ids) inv[id - id_lo] = (uint32_t)drow;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// PQ Lloyd update: one 64-thread workgroup per (m, j); lane t sums component t of the residual sub-vectors of the cluster's
+// members in order[] order (ascending sample row: a fixed summation order) and writes the mean.  Empty clusters keep their centroid.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void pq_update_kernel(const _Float16* __restrict__ X, int d, int M, const int32_t* __restrict__ lists,
+                                                      const _Float16* __restrict__ cent, const int32_t* __restrict__ order,
+                                                      const int32_t* __restrict__ off, int64_t n, float* __restrict__ cb) {
+  const int ds = d / M;
+  const int m = blockIdx.x / 256, j = blockIdx.x % 256, t = threadIdx.x;
+  const int a = off[m * 257 + j], b = off[m * 257 + j + 1];
+  if (b <= a || t >= ds) return;
+  const int32_t* ord = order + (size_t)m * n;
+  const int c = m * ds + t;
+  float s = 0.f;
+  for (int e = a; e < b; ++e) {
+    const int64_t r = ord[e];
+    s += (float)X[(size_t)r * d + c] - (float)cent[(size_t)lists[r] * d + c];
+  }
+  cb[((size_t)m * 256 + j) * ds + t] = s / (float)(b - a);
+}
+
+// codebook entry mj[i] = m * 256 + j := residual sub-vector m of sample row rows[i] (seeding, re-seeding of empty clusters)
+__global__ __launch_bounds__(64) void pq_seed_kernel(const _Float16* __restrict__ X, int d, int M, const int32_t* __restrict__ lists,
+                                                    const _Float16* __restrict__ cent, const int32_t* __restrict__ mj,
+                                                    const int64_t* __restrict__ rows, float* __restrict__ cb) {
+  const int ds = d / M, i = blockIdx.x, t = threadIdx.x;
+  if (t >= ds) return;
+  const int m = mj[i] / 256;
+  const int64_t r = rows[i];
+  const int c = m * ds + t;
+  cb[(size_t)mj[i] * ds + t] = (float)X[(size_t)r * d + c] - (float)cent[(size_t)lists[r] * d + c];
+}
+
+// ---------------------------------------------------------------------------------------------
+// lookup tables: workgroup (q, m), thread j: LUT[q][m][j] = sum_t q[m ds + t] * cb[m][j][t] (fp32, t in order)
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void pq_lut_kernel(const float* __restrict__ q, int d, int M, const float* __restrict__ cb,
+                                                    float* __restrict__ lut) {
+  __shared__ float sq[64];
+  const int qi = blockIdx.x, m = blockIdx.y, j = threadIdx.x, ds = d / M;
+  if (j < ds) sq[j] = q[(size_t)qi * d + m * ds + j];
+  __syncthreads();
+  const float* c = cb + ((size_t)m * 256 + j) * ds;
+  float s = 0.f;
+  for (int t = 0; t < ds; ++t) s = fmaf(sq[t], c[t], s);
+  lut[((size_t)qi * M + m) * 256 + j] = s;
+}
+
+// ---------------------------------------------------------------------------------------------
+// probe lists: the masks of ivf_select_mark_kernel ([nblk][nlist], bit q % 32 of block q / 32) -> per query the ids of its
+// probed lists and their coarse scores (any order: the scan's result does not depend on it)
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void pq_probe_kernel(const unsigned* __restrict__ masks, const float* __restrict__ scores, int nq,
+                                                      int nlist, int np, unsigned* __restrict__ pcnt, int* __restrict__ probe,
+                                                      float* __restrict__ pscore) {
+  const int l = blockIdx.x * 256 + threadIdx.x;
+  const int b = blockIdx.y;
+  if (l >= nlist) return;
+  unsigned mk = masks[(size_t)b * nlist + l];
+  while (mk) {
+    const int bit = __ffs(mk) - 1;
+    mk &= mk - 1;
+    const int qi = b * 32 + bit;
+    if (qi >= nq) continue;
+    const unsigned p = atomicAdd(&pcnt[qi], 1u);
+    if (p < (unsigned)np) {
+      probe[(size_t)qi * np + p] = l;
+      pscore[(size_t)qi * np + p] = scores[(size_t)qi * nlist + l];
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// ADC list scan with top-k (see the head of the file).  grid (nsplit, nq); workgroup (s, q) scans probes s, s + nsplit, ... of
+// query q and writes partial list s * nq + q (<= k entries, arena rows) of part_s / part_i / part_n.
+// ---------------------------------------------------------------------------------------------
+// wave-local prune: the queue (n <= PQ_WQ entries) -> its top min(n, k) in rank order; returns the new count; thr = the k-th score
+__device__ __forceinline__ int pq_wave_prune(float* qs, uint32_t* qr, long long* qi, int n, int k, int lane, float& thr) {
+  float s0 = 0.f, s1 = 0.f;
+  uint32_t r0 = 0, r1 = 0;
+  long long i0 = 0, i1 = 0;
+  const bool v0 = lane < n, v1 = lane + 64 < n;
+  int k0 = 0, k1 = 0;  // ranks
+  if (v0) { s0 = qs[lane]; r0 = qr[lane]; i0 = qi[lane]; }
+  if (v1) { s1 = qs[lane + 64]; r1 = qr[lane + 64]; i1 = qi[lane + 64]; }
+  for (int j = 0; j < n; ++j) {
+    const float sj = qs[j];
+    const long long ij = qi[j];
+    k0 += pq_better(sj, ij, s0, i0) ? 1 : 0;
+    k1 += pq_better(sj, ij, s1, i1) ? 1 : 0;
+  }
+  wave_sync();
+  if (v0 && k0 < k) { qs[k0] = s0; qr[k0] = r0; qi[k0] = i0; }
+  if (v1 && k1 < k) { qs[k1] = s1; qr[k1] = r1; qi[k1] = i1; }
+  wave_sync();
+  if (n >= k) thr = qs[k - 1];
+  return n < k ? n : k;
+}
+
+template <int M>
+__global__ __launch_bounds__(256) void pq_adc_scan_kernel(const uint8_t* __restrict__ codes, const float* __restrict__ lut,
+                                                         const int* __restrict__ probe, const float* __restrict__ pscore,
+                                                         const unsigned* __restrict__ pcnt, int np, int nsplit,
+                                                         const unsigned* __restrict__ tile0, const unsigned* __restrict__ size,
+                                                         const int64_t* __restrict__ idmap, int k, int nq, float* __restrict__ part_s,
+                                                         uint32_t* __restrict__ part_i, int* __restrict__ part_n) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char pq_smem[];
+  float* s_lut = reinterpret_cast<float*>(pq_smem);                  // [M * 256]
+  long long* c_id = reinterpret_cast<long long*>(s_lut + M * 256);  // [4][PQ_WQ]
+  float* c_s = reinterpret_cast<float*>(c_id + 4 * PQ_WQ);           // [4][PQ_WQ]
+  uint32_t* c_r = reinterpret_cast<uint32_t*>(c_s + 4 * PQ_WQ);      // [4][PQ_WQ]
+  __shared__ int w_cnt[4];
+  const int s = blockIdx.x, q = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const float4* lq = reinterpret_cast<const float4*>(lut + (size_t)q * M * 256);
+  for (int e = tid; e < M * 64; e += 256) reinterpret_cast<float4*>(s_lut)[e] = lq[e];
+  __syncthreads();
+  float* qs = c_s + w * PQ_WQ;
+  uint32_t* qr = c_r + w * PQ_WQ;
+  long long* qi = c_id + w * PQ_WQ;
+  int cnt = 0;
+  float thr = -INFINITY;
+  const int npq = min((int)pcnt[q], np);
+  for (int p = s; p < npq; p += nsplit) {
+    const int l = probe[(size_t)q * np + p];
+    const float cs = pscore[(size_t)q * np + p];
+    const size_t r0 = (size_t)tile0[l] * 32;
+    const unsigned sz = size[l];
+    for (unsigned base = (unsigned)w * 64; base < sz; base += 256) {
+      if (cnt > PQ_WQ - 64) cnt = pq_wave_prune(qs, qr, qi, cnt, k, lane, thr);
+      const unsigned i = base + lane;
+      float sc = -INFINITY;
+      bool ok = false;
+      size_t row = 0;
+      if (i < sz) {
+        row = r0 + i;
+        const uint4* cp = reinterpret_cast<const uint4*>(codes + row * M);
+        uint4 cw[M / 16];
+#pragma unroll
+        for (int v = 0; v < M / 16; ++v) cw[v] = cp[v];
+        float acc = 0.f;
+#pragma unroll
+        for (int v = 0; v < M / 16; ++v) {
+          const unsigned ww[4] = {cw[v].x, cw[v].y, cw[v].z, cw[v].w};
+#pragma unroll
+          for (int b = 0; b < 16; ++b) acc += s_lut[(v * 16 + b) * 256 + ((ww[b >> 2] >> (8 * (b & 3))) & 255u)];
+        }
+        sc = cs + acc;
+        ok = sc >= thr;
+      }
+      const unsigned long long bal = __ballot(ok);
+      if (ok) {
+        const int at = cnt + (int)__popcll(bal & ((1ull << lane) - 1ull));
+        qs[at] = sc;
+        qr[at] = (uint32_t)row;
+        qi[at] = (long long)idmap[row];
+      }
+      cnt += (int)__popcll(bal);
+      wave_sync();
+    }
+  }
+  cnt = pq_wave_prune(qs, qr, qi, cnt, k, lane, thr);
+  if (lane == 0) w_cnt[w] = cnt;
+  __syncthreads();
+  // the four queues (each <= k sorted entries) ranked together: thread (w, lane) holds entry `lane` of queue w
+  const bool mine = lane < w_cnt[w];
+  const float se = mine ? qs[lane] : 0.f;
+  const long long ie = mine ? qi[lane] : 0;
+  int rank = 0;
+  if (mine) {
+    for (int v = 0; v < 4; ++v)
+      for (int j = 0; j < w_cnt[v]; ++j) rank += pq_better(c_s[v * PQ_WQ + j], c_id[v * PQ_WQ + j], se, ie) ? 1 : 0;
+  }
+  const size_t slot = (size_t)s * nq + q;
+  if (mine && rank < k) {
+    part_s[slot * k + rank] = se;
+    part_i[slot * k + rank] = qr[lane];
+  }
+  if (tid == 0) {
+    const int tot = w_cnt[0] + w_cnt[1] + w_cnt[2] + w_cnt[3];
+    part_n[slot] = tot < k ? tot : k;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// decode-gather (reconstruct, the coalescer's R): out[i] = f32(c_list) + concat_m cb[m][code_m] of id ids[i]; a bad id -> 0xFF
+// bytes.  The list of an arena row is the last list whose first tile is <= the row's tile (binary search over tile0).
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void pq_decode_kernel(const uint8_t* __restrict__ codes, int d, int M, const float* __restrict__ cb,
+                                                       const _Float16* __restrict__ cent, const unsigned* __restrict__ tile0, int nlist,
+                                                       int64_t id_lo, int64_t n_ids, const uint32_t* __restrict__ inv,
+                                                       const int64_t* __restrict__ ids, int64_t n, float* __restrict__ out) {
+  const int64_t i = blockIdx.x;
+  if (i >= n) return;
+  const int64_t id = ids[i];
+  const bool ok = id >= id_lo && id - id_lo < n_ids;
+  float* o = out + (size_t)i * d;
+  if (!ok) {
+    for (int c = threadIdx.x; c < d; c += 256) o[c] = __int_as_float(-1);
+    return;
+  }
+  const size_t row = inv[id - id_lo];
+  const unsigned t = (unsigned)(row / 32);
+  int lo = 0, hi = nlist;  // first l with tile0[l] > t
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (tile0[mid] <= t) lo = mid + 1; else hi = mid;
+  }
+  const int l = lo > 0 ? lo - 1 : 0;
+  const int ds = d / M;
+  for (int c = threadIdx.x; c < d; c += 256) {
+    const int m = c / ds;
+    const unsigned code = codes[row * M + m];
+    o[c] = (float)cent[(size_t)l * d + c] + cb[((size_t)m * 256 + code) * ds + (c - m * ds)];
+  }
+}
+
+// precomputed codes into their arena slots (knnx_ivfpq_add_codes: an index loaded from its saved codes); one thread per row
+__global__ __launch_bounds__(256) void pq_scatter_codes_kernel(const uint8_t* __restrict__ src, int64_t n, int M, const int32_t* __restrict__ lists,
+                                                              const int32_t* __restrict__ pos, const int64_t* __restrict__ ids,
+                                                              const unsigned* __restrict__ tile0, int64_t id_lo, int64_t n_ids,
+                                                              uint8_t* __restrict__ codes, int64_t* __restrict__ idmap, uint32_t* __restrict__ inv) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const size_t drow = (size_t)tile0[lists[i]] * 32 + (size_t)pos[i];
+  const uint4* s = reinterpret_cast<const uint4*>(src + (size_t)i * M);
+  uint4* o = reinterpret_cast<uint4*>(codes + drow * M);
+  for (int v = 0; v < M / 16; ++v) o[v] = s[v];
+  const int64_t id = ids[i];
+  idmap[drow] = id;
+  if (id >= id_lo && id - id_lo < n_ids) inv[id - id_lo] = (uint32_t)drow;
+}
+
+// ---------------------------------------------------------------------------------------------
+// host-side launchers (declared in knn_kernels.h)
+// ---------------------------------------------------------------------------------------------
+bool pq_supported(int d, int M) {
+  return (M == 16 || M == 32 || M == 64 || M == 128) && d % 256 == 0 && d > 0 && d <= 1024 && d % M == 0 && d / M <= 64;
+}
+
+template <int DS>
+static hipError_t launch_encode_ds(const _Float16* X, int64_t n, int d, int M, const int32_t* lists, const _Float16* cent, const float* cb,
+                                   const unsigned* tile0, const int32_t* pos, const int64_t* ids, int64_t id0, int64_t id_lo, int64_t n_ids,
+                                   uint8_t* codes, int64_t* idmap, uint32_t* inv, hipStream_t st) {
+  auto kern = pq_encode_kernel<DS>;
+  const int smem = 256 * DS * (int)sizeof(float);
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kern, dim3((unsigned)((n + 255) / 256)), dim3(256), smem, st, X, n, d, M, lists, cent, cb, tile0, pos, ids, id0, id_lo,
+                     n_ids, codes, idmap, inv);
+  return hipGetLastError();
+}
+
+hipError_t launch_pq_encode(const _Float16* X, int64_t n, int d, int M, const int32_t* lists, const _Float16* cent, const float* cb,
+                            const unsigned* tile0, const int32_t* pos, const int64_t* ids, int64_t id0, int64_t id_lo, int64_t n_ids,
+                            uint8_t* codes, int64_t* idmap, uint32_t* inv, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  if (!pq_supported(d, M)) return hipErrorInvalidValue;
+#define PQ_ENC(DS) \
+  case DS: return launch_encode_ds<DS>(X, n, d, M, lists, cent, cb, tile0, pos, ids, id0, id_lo, n_ids, codes, idmap, inv, st);
+  switch (d / M) {
+    PQ_ENC(2) PQ_ENC(4) PQ_ENC(6) PQ_ENC(8) PQ_ENC(12) PQ_ENC(16) PQ_ENC(24) PQ_ENC(32) PQ_ENC(48) PQ_ENC(64)
+    default: return hipErrorInvalidValue;
+  }
+#undef PQ_ENC
+}
+
+hipError_t launch_pq_update(const _Float16* X, int d, int M, const int32_t* lists, const _Float16* cent, const int32_t* order,
+                            const int32_t* off, int64_t n, float* cb, hipStream_t st) {
+  if (!pq_supported(d, M)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(pq_update_kernel, dim3((unsigned)(M * 256)), dim3(64), 0, st, X, d, M, lists, cent, order, off, n, cb);
+  return hipGetLastError();
+}
+
+hipError_t launch_pq_seed(const _Float16* X, int d, int M, const int32_t* lists, const _Float16* cent, const int32_t* mj, const int64_t* rows,
+                          int64_t n, float* cb, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  if (!pq_supported(d, M)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(pq_seed_kernel, dim3((unsigned)n), dim3(64), 0, st, X, d, M, lists, cent, mj, rows, cb);
+  return hipGetLastError();
+}
+
+hipError_t launch_pq_lut(const float* q, int nq, int d, int M, const float* cb, float* lut, hipStream_t st) {
+  if (nq <= 0) return hipSuccess;
+  if (!pq_supported(d, M)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(pq_lut_kernel, dim3((unsigned)nq, (unsigned)M), dim3(256), 0, st, q, d, M, cb, lut);
+  return hipGetLastError();
+}
+
+hipError_t launch_pq_probe(const unsigned* masks, const float* scores, int nq, int nlist, int np, unsigned* pcnt, int* probe, float* pscore,
+                           hipStream_t st) {
+  hipError_t e = hipMemsetAsync(pcnt, 0, (size_t)nq * sizeof(unsigned), st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(pq_probe_kernel, dim3((unsigned)((nlist + 255) / 256), (unsigned)((nq + 31) / 32)), dim3(256), 0, st, masks, scores, nq,
+                     nlist, np, pcnt, probe, pscore);
+  return hipGetLastError();
+}
+
+size_t pq_scan_smem_bytes(int M) { return (size_t)M * 256 * 4 + (size_t)4 * PQ_WQ * (8 + 4 + 4); }
+
+hipError_t launch_pq_adc_scan(const uint8_t* codes, int M, const float* lut, const int* probe, const float* pscore, const unsigned* pcnt,
+                              int np, int nsplit, const unsigned* tile0, const unsigned* size, const int64_t* idmap, int k, int nq,
+                              float* part_s, uint32_t* part_i, int* part_n, hipStream_t st) {
+  if (k < 1 || k > PQ_MAX_K || nq <= 0 || nsplit <= 0) return hipErrorInvalidValue;
+  const size_t smem = pq_scan_smem_bytes(M);
+  if (smem + 64 > (size_t)KNN_LDS_BYTES) return hipErrorInvalidValue;
+#define PQ_SCAN(MM)                                                                                                               \
+  case MM: {                                                                                                                      \
+    auto kern = pq_adc_scan_kernel<MM>;                                                                                           \
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
+    if (e != hipSuccess) return e;                                                                                                \
+    hipLaunchKernelGGL(kern, dim3((unsigned)nsplit, (unsigned)nq), dim3(256), smem, st, codes, lut, probe, pscore, pcnt, np, nsplit, \
+                       tile0, size, idmap, k, nq, part_s, part_i, part_n);                                                        \
+    return hipGetLastError();                                                                                                     \
+  }
+  switch (M) {
+    PQ_SCAN(16) PQ_SCAN(32) PQ_SCAN(64) PQ_SCAN(128)
+    default: return hipErrorInvalidValue;
+  }
+#undef PQ_SCAN
+}
+
+hipError_t launch_pq_decode(const uint8_t* codes, int d, int M, const float* cb, const _Float16* cent, const unsigned* tile0, int nlist,
+                            int64_t id_lo, int64_t n_ids, const uint32_t* inv, const int64_t* ids, int64_t n, float* out, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  if (!pq_supported(d, M)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(pq_decode_kernel, dim3((unsigned)n), dim3(256), 0, st, codes, d, M, cb, cent, tile0, nlist, id_lo, n_ids, inv, ids, n, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_pq_scatter_codes(const uint8_t* src, int64_t n, int M, const int32_t* lists, const int32_t* pos, const int64_t* ids,
+                                   const unsigned* tile0, int64_t id_lo, int64_t n_ids, uint8_t* codes, int64_t* idmap, uint32_t* inv,
+                                   hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(pq_scatter_codes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, n, M, lists, pos, ids, tile0, id_lo,
+                     n_ids, codes, idmap, inv);
+  return hipGetLastError();
+}
+
+}  // namespace knnx

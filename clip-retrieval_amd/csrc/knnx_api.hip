@@ -122,6 +122,27 @@ struct knnx_index {
   std::vector<uint32_t> ivfb_size, ivfb_fill, ivfb_tile0;
   std::vector<uint64_t> ivfb_taken;  // one bit per padded arena row
 
+  // IVF-PQ (knnx_ivfpq_set_quantizer before knnx_ivf_begin; csrc/knn_pq_kernels.hip): the arena holds M code bytes per row, list-sorted
+  // and tile-padded like the IVF-Flat rows (`rows` stays null); the coarse quantiser is the IVF one
+  int pq_m = 0;
+  float* pq_cb = nullptr;                       // [M][256][d / M]
+  uint8_t* pq_codes = nullptr;                  // [capacity][M]
+  _Float16* pq_bcent = nullptr;                 // centroids during the build (knnx_ivf_begin .. knnx_ivf_end)
+  std::vector<unsigned> pq_tile0_h, pq_size_h;  // host copy of the layout (knnx_ivfpq_get_codes)
+  // one search pass of up to 256 queries, allocated on first use
+  _Float16* pq_qfrag = nullptr;
+  int* pq_thr = nullptr;         // [2][256] thresholds reset by the query prep (the coarse dump does not use them)
+  float* pq_scores = nullptr;    // [256][nlist] coarse scores
+  unsigned* pq_masks = nullptr;  // [8][nlist]
+  unsigned* pq_pcnt = nullptr;   // [256]
+  int* pq_probe = nullptr;       // [256][pq_np_cap] probed lists
+  float* pq_pscore = nullptr;    // [256][pq_np_cap] their coarse scores
+  int pq_np_cap = 0;
+  float* pq_lut = nullptr;       // [256][M][256]
+  float* pq_part_s = nullptr;    // [PQ_SLOTS][64] per-workgroup top-k of the ADC scan
+  uint32_t* pq_part_i = nullptr;
+  int* pq_part_n = nullptr;      // [PQ_SLOTS]
+
   // int8 first stage of the flat scans (knn_rq_kernels.hip): allocated and built on first use, rebuilt after the rows change
   int i8_ok = 1;                  // KNNX_I8=0 disables; cleared for good when its memory cannot be had
   bool i8_valid = false;          // rows8 / colscale / ab describe the current rows
@@ -412,6 +433,20 @@ extern "C" void knnx_destroy(knnx_index* ix) {
   hipFree(ix->ivfb_ids);
   hipFree(ix->ivfb_lists);
   hipFree(ix->ivfb_pos);
+  hipFree(ix->pq_cb);
+  hipFree(ix->pq_codes);
+  hipFree(ix->pq_bcent);
+  hipFree(ix->pq_qfrag);
+  hipFree(ix->pq_thr);
+  hipFree(ix->pq_scores);
+  hipFree(ix->pq_masks);
+  hipFree(ix->pq_pcnt);
+  hipFree(ix->pq_probe);
+  hipFree(ix->pq_pscore);
+  hipFree(ix->pq_lut);
+  hipFree(ix->pq_part_s);
+  hipFree(ix->pq_part_i);
+  hipFree(ix->pq_part_n);
   if (ix->pin) hipHostFree(ix->pin);
   for (int i = 0; i < 9; ++i)
     if (ix->scratch[i]) hipFree(ix->scratch[i]);
@@ -431,6 +466,7 @@ extern "C" int knnx_dim(const knnx_index* ix) { return ix ? ix->d : 0; }
 extern "C" int knnx_reset(knnx_index* ix) {
   if (!ix) return fail(KNNX_E_ARG, "index is null");
   std::lock_guard<std::mutex> lk(ix->mu);
+  if (ix->pq_m) return fail(KNNX_E_STATE, "reset of an IVF-PQ index is not supported (destroy it instead)");
   if (ix->ivf_nlist || ix->ivfb_nlist) return fail(KNNX_E_STATE, "reset of an IVF index is not supported (destroy it instead)");
   if (set_dev(ix)) return KNNX_E_HIP;
   HIPCHK(hipStreamSynchronize(ix->stream));
@@ -481,6 +517,7 @@ extern "C" int knnx_reserve(knnx_index* ix, int64_t n_rows) {
   if (!ix || n_rows < 0) return fail(KNNX_E_ARG, "bad reserve");
   std::lock_guard<std::mutex> lk(ix->mu);
   if (set_dev(ix)) return KNNX_E_HIP;
+  if (ix->pq_m) return fail(KNNX_E_STATE, "reserve on an IVF-PQ index (its arena is sized by knnx_ivf_begin)");
   return grow(ix, n_rows);
 }
 
@@ -490,6 +527,7 @@ static int add_common(knnx_index* ix, const void* rows, int64_t n, bool is_f32) 
   std::lock_guard<std::mutex> lk(ix->mu);
   if (set_dev(ix)) return KNNX_E_HIP;
   if (ix->borrowed) return fail(KNNX_E_STATE, "add() on an index that borrows device rows");
+  if (ix->pq_m) return fail(KNNX_E_STATE, "add() on an IVF-PQ index (rows are encoded by knnx_ivf_begin / knnx_ivf_add_assigned / knnx_ivf_end)");
   if (ix->ivf_nlist) return fail(KNNX_E_STATE, "add() after knnx_ivf_set_lists (rebuild the index instead)");
   if (ix->ntotal + n > ix->capacity) {
     int64_t want = std::max<int64_t>(ix->ntotal + n, ix->capacity + ix->capacity / 2);
@@ -533,6 +571,7 @@ extern "C" int knnx_add_f32(knnx_index* ix, const float* rows, int64_t n) { retu
 extern "C" int knnx_attach_device_f16(knnx_index* ix, const void* dev_rows, int64_t n) {
   if (!ix || !dev_rows || n < 0) return fail(KNNX_E_ARG, "bad attach arguments");
   std::lock_guard<std::mutex> lk(ix->mu);
+  if (ix->pq_m) return fail(KNNX_E_STATE, "attach on an IVF-PQ index");
   if (ix->rows && !ix->borrowed) return fail(KNNX_E_STATE, "index already owns rows");
   if (n > (int64_t)0xffffffffll) return fail(KNNX_E_UNSUPPORTED, "more than 2^32 rows per device");
   ix->rows = (_Float16*)dev_rows;
@@ -552,6 +591,7 @@ extern "C" int knnx_synth_fill(knnx_index* ix, int64_t n, uint64_t seed) {
   if (!ix || n < 0) return fail(KNNX_E_ARG, "bad synth arguments");
   std::lock_guard<std::mutex> lk(ix->mu);
   if (set_dev(ix)) return KNNX_E_HIP;
+  if (ix->pq_m) return fail(KNNX_E_STATE, "synth_fill on an IVF-PQ index");
   if (!ix->borrowed) {
     int r = grow(ix, n);
     if (r) return r;
@@ -1234,7 +1274,87 @@ static int scan_topk_i8(knnx_index* ix, const float* q_dev, int nq, int k, float
 }
 
 // how many of `remaining` queries the next scan step takes (the same choice scan_step makes)
+// ---------------------------------------------------------------------------------------------
+// IVF-PQ pass of 1 .. 256 queries already in HBM (csrc/knn_pq_kernels.hip): the coarse quantiser of the multi-block IVF pass
+// (one score dump over the centroids + the radix select of ivf_select_mark_kernel: the nprobe largest <q, c>, ties to the lower
+// list id), the probed lists of every query, its lookup table, the ADC list scan, the merge of the per-workgroup lists.
+// ---------------------------------------------------------------------------------------------
+constexpr int PQ_PASS = IVFM_BLK * KNN_NQ;    // queries of one pass
+constexpr int PQ_TARGET_WG = 1024;            // ADC workgroups a pass aims for (a query's lists are split over ceil(1024 / nq))
+constexpr int PQ_MAX_SPLIT = 128;             // ... at most (the merge holds split x k scores of a query in the LDS)
+constexpr int PQ_SLOTS = PQ_TARGET_WG + PQ_PASS;  // >= nq * split
+
+static int pq_alloc(knnx_index* ix, int np) {
+  const size_t nl = (size_t)ix->ivf_nlist;
+  if (!ix->pq_qfrag) HIPCHK(hipMalloc(&ix->pq_qfrag, (size_t)IVFM_BLK * ix->d * 128));
+  if (!ix->pq_thr) HIPCHK(hipMalloc(&ix->pq_thr, 2 * PQ_PASS * sizeof(int)));
+  if (!ix->pq_scores) HIPCHK(hipMalloc(&ix->pq_scores, PQ_PASS * nl * sizeof(float)));
+  if (!ix->pq_masks) HIPCHK(hipMalloc(&ix->pq_masks, IVFM_BLK * nl * sizeof(unsigned)));
+  if (!ix->pq_pcnt) HIPCHK(hipMalloc(&ix->pq_pcnt, PQ_PASS * sizeof(unsigned)));
+  if (!ix->pq_lut) HIPCHK(hipMalloc(&ix->pq_lut, (size_t)PQ_PASS * ix->pq_m * 256 * sizeof(float)));
+  if (!ix->pq_part_s) HIPCHK(hipMalloc(&ix->pq_part_s, (size_t)PQ_SLOTS * KNNX_MAX_K_FAST * sizeof(float)));
+  if (!ix->pq_part_i) HIPCHK(hipMalloc(&ix->pq_part_i, (size_t)PQ_SLOTS * KNNX_MAX_K_FAST * sizeof(uint32_t)));
+  if (!ix->pq_part_n) HIPCHK(hipMalloc(&ix->pq_part_n, PQ_SLOTS * sizeof(int)));
+  if (np > ix->pq_np_cap) {
+    hipFree(ix->pq_probe);
+    hipFree(ix->pq_pscore);
+    ix->pq_probe = nullptr;
+    ix->pq_pscore = nullptr;
+    ix->pq_np_cap = 0;
+    HIPCHK(hipMalloc(&ix->pq_probe, (size_t)PQ_PASS * np * sizeof(int)));
+    HIPCHK(hipMalloc(&ix->pq_pscore, (size_t)PQ_PASS * np * sizeof(float)));
+    ix->pq_np_cap = np;
+  }
+  return 0;
+}
+
+static int scan_topk_pq(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out, int64_t* I_out, hipStream_t st) {
+  if (nq < 1 || nq > PQ_PASS || k < 1 || k > KNNX_MAX_K_FAST || !ix->cent || !ix->ivf_nlist)
+    return fail(KNNX_E_STATE, "internal: IVF-PQ pass misuse");
+  const int np = std::min(ix->ivf_nprobe, ix->ivf_nlist);
+  int r = pq_alloc(ix, np);
+  if (r) return r;
+  knnx_index* c = ix->cent;
+  const int nblk = (nq + KNN_NQ - 1) / KNN_NQ;
+  HIPCHK(launch_prep_blocks(q_dev, nq, ix->d, ix->pq_qfrag, ix->pq_thr, ix->pq_thr + PQ_PASS, st));
+  ScanArgs ca{};
+  ca.X = c->rows;
+  ca.N = c->ntotal;
+  ca.d = c->d;
+  ca.qfrag = ix->pq_qfrag;
+  ca.nq = nq;
+  ca.grid = std::max(1, ix->n_cu / nblk) * nblk;
+  ca.thr_g = ix->pq_thr;
+  ca.nblk = nblk;
+  ca.k = 1;
+  ca.cap = 2;
+  ca.mode = 2;
+  ca.range_cap = (unsigned)ix->ivf_nlist;
+  ca.range_s = ix->pq_scores;
+  HIPCHK(launch_scan(ca, st));
+  HIPCHK(launch_ivf_select_mark(ix->pq_scores, nq, np, ix->ivf_nlist, ix->pq_masks, st));
+  HIPCHK(launch_pq_probe(ix->pq_masks, ix->pq_scores, nq, ix->ivf_nlist, np, ix->pq_pcnt, ix->pq_probe, ix->pq_pscore, st));
+  HIPCHK(launch_pq_lut(q_dev, nq, ix->d, ix->pq_m, ix->pq_cb, ix->pq_lut, st));
+  const int nsplit = std::max(1, std::min(std::min(np, PQ_MAX_SPLIT), (PQ_TARGET_WG + nq - 1) / nq));
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (ix->prof) {
+    HIPCHK(hipEventCreate(&e0));
+    HIPCHK(hipEventCreate(&e1));
+    HIPCHK(hipEventRecord(e0, st));
+  }
+  HIPCHK(launch_pq_adc_scan(ix->pq_codes, ix->pq_m, ix->pq_lut, ix->pq_probe, ix->pq_pscore, ix->pq_pcnt, np, nsplit, ix->ivf_tile0, ix->ivf_size,
+                            ix->ivf_idmap, k, nq, ix->pq_part_s, ix->pq_part_i, ix->pq_part_n, st));
+  if (ix->prof) {
+    HIPCHK(hipEventRecord(e1, st));
+    ix->prof_events.emplace_back(e0, e1);
+  }
+  HIPCHK(launch_merge_u32(ix->pq_part_s, ix->pq_part_i, ix->pq_part_n, nsplit, nq, k, nq, k, ix->id_base, ix->ivf_idmap, D_out, I_out,
+                          nullptr, st));
+  return 0;
+}
+
 static int step_queries(knnx_index* ix, int remaining, int k) {
+  if (ix->pq_m) return std::min(PQ_PASS, remaining);
   if (ivfm_usable(ix, remaining, k)) return std::min(IVFM_BLK * KNN_NQ, remaining);
   // (two planes: 128 queries per int8 pass -- a batch of more goes to the fp16 register-stationary pass, 36 ms for 256 against 2 x 19.6)
   if (i8_usable(ix, remaining, k) && !(ix->i8_planes == 2 && remaining > 128 && rq_usable(ix, remaining, k)))
@@ -1248,6 +1368,12 @@ static int step_queries(knnx_index* ix, int remaining, int k) {
 static int scan_step(knnx_index* ix, const float* q_dev, int remaining, int k, float* D_out, int64_t* I_out, hipStream_t st,
                      int* taken) {
   int nq, r;
+  if (ix->pq_m) {  // IVF-PQ: its own pass, dispatched beside the fp16 scans
+    nq = std::min(PQ_PASS, remaining);
+    r = scan_topk_pq(ix, q_dev, nq, k, D_out, I_out, st);
+    *taken = nq;
+    return r;
+  }
   if (ivfm_usable(ix, remaining, k) && ivfm_alloc(ix) == 0) {
     nq = std::min(IVFM_BLK * KNN_NQ, remaining);
     r = scan_topk_ivf_multi(ix, q_dev, nq, k, D_out, I_out, st);
@@ -1447,8 +1573,10 @@ static int co_run_batch_locked(knnx_index* ix, std::vector<CoReq*>& b) {
     memcpy(ix->pin, ix->co_Ibuf.data(), (size_t)nrow * sizeof(int64_t));
     HIPCHK(hipMemcpyAsync(ids_dev, ix->pin, (size_t)nrow * sizeof(int64_t), hipMemcpyHostToDevice, st));
     HIPCHK(hipStreamSynchronize(st));  // the pinned buffer is reused below
-    hipError_t e = ix->ivf_nlist ? launch_gather_inv(ix->rows, d, ix->id_base, ix->ntotal, ix->ivf_inv, ids_dev, nrow, rows_dev, st)
-                                 : launch_gather(ix->rows, ix->ntotal, d, ix->id_base, ids_dev, nrow, rows_dev, st);
+    hipError_t e = ix->pq_m ? launch_pq_decode(ix->pq_codes, d, ix->pq_m, ix->pq_cb, ix->cent ? ix->cent->rows : nullptr, ix->ivf_tile0,
+                                               ix->ivf_nlist, ix->id_base, ix->ntotal, ix->ivf_inv, ids_dev, nrow, rows_dev, st)
+                   : ix->ivf_nlist ? launch_gather_inv(ix->rows, d, ix->id_base, ix->ntotal, ix->ivf_inv, ids_dev, nrow, rows_dev, st)
+                                   : launch_gather(ix->rows, ix->ntotal, d, ix->id_base, ids_dev, nrow, rows_dev, st);
     if (e != hipSuccess) return fail(KNNX_E_HIP, std::string("coalesced gather: ") + hipGetErrorString(e));
     if (any_dd) {
       if ((r = ensure_scratch(ix, 6, (size_t)m * CO_PAIR_CAP * sizeof(int32_t), (void**)&pairs_dev))) return r;
@@ -1573,6 +1701,7 @@ extern "C" int knnx_search_dedup(knnx_index* ix, const float* q, int k, float* D
 extern "C" int knnx_search(knnx_index* ix, const float* q, int n, int k, float* D, int64_t* I, float* R) {
   if (!ix || (n > 0 && (!q || !D || !I)) || n < 0 || k <= 0) return fail(KNNX_E_ARG, "bad search arguments");
   if (k > KNNX_MAX_K) return fail(KNNX_E_UNSUPPORTED, "k > 131072 is not implemented");
+  if (ix->pq_m && k > KNNX_MAX_K_FAST) return fail(KNNX_E_UNSUPPORTED, "k > 64 is not supported on an IVF-PQ index");
   if (n == 0) return KNNX_OK;
   if (n == 1 && k <= KNNX_MAX_K_FAST && ix->coalesce) {  // concurrent single-query callers share one scan
     CoReq me{q, k, D, I, R, false, 0.f, nullptr, 0, nullptr};
@@ -1609,8 +1738,10 @@ extern "C" int knnx_reconstruct(knnx_index* ix, const int64_t* ids, int64_t n, f
     memcpy(ids_pin, ids + o, (size_t)m * sizeof(int64_t));
     e = hipMemcpyAsync(ids_dev, ids_pin, (size_t)m * sizeof(int64_t), hipMemcpyHostToDevice, ix->stream);
     if (e == hipSuccess)
-      e = ix->ivf_nlist ? launch_gather_inv(ix->rows, ix->d, ix->id_base, ix->ntotal, ix->ivf_inv, ids_dev, m, out_dev, ix->stream)
-                        : launch_gather(ix->rows, ix->ntotal, ix->d, ix->id_base, ids_dev, m, out_dev, ix->stream);
+      e = ix->pq_m ? launch_pq_decode(ix->pq_codes, ix->d, ix->pq_m, ix->pq_cb, ix->cent ? ix->cent->rows : nullptr, ix->ivf_tile0, ix->ivf_nlist,
+                                      ix->id_base, ix->ntotal, ix->ivf_inv, ids_dev, m, out_dev, ix->stream)
+          : ix->ivf_nlist ? launch_gather_inv(ix->rows, ix->d, ix->id_base, ix->ntotal, ix->ivf_inv, ids_dev, m, out_dev, ix->stream)
+                          : launch_gather(ix->rows, ix->ntotal, ix->d, ix->id_base, ids_dev, m, out_dev, ix->stream);
     if (e == hipSuccess)
       e = hipMemcpyAsync(out_pin, out_dev, (size_t)m * ix->d * sizeof(float), hipMemcpyDeviceToHost, ix->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ix->stream);
@@ -1814,6 +1945,7 @@ extern "C" int knnx_range_search(knnx_index* ix, const float* q, int n, float th
                                  int64_t* I) {
   if (!ix || !lims || (n > 0 && !q) || n < 0) return fail(KNNX_E_ARG, "bad range_search arguments");
   if ((D == nullptr) != (I == nullptr)) return fail(KNNX_E_ARG, "D and I must both be null or both be set");
+  if (ix->pq_m) return fail(KNNX_E_UNSUPPORTED, "range_search is not supported on an IVF-PQ index");
   std::lock_guard<std::mutex> lk(ix->mu);
   if (set_dev(ix)) return KNNX_E_HIP;
   const bool fill = D != nullptr;
@@ -1849,6 +1981,7 @@ extern "C" int knnx_range_search(knnx_index* ix, const float* q, int n, float th
 extern "C" int knnx_range_search_once(knnx_index* ix, const float* q, int n, float thresh, int64_t* lims, float* D, int64_t* I,
                                       int64_t capacity) {
   if (!ix || !lims || (n > 0 && !q) || n < 0 || capacity < 0 || (capacity > 0 && (!D || !I))) return fail(KNNX_E_ARG, "bad range_search_once arguments");
+  if (ix->pq_m) return fail(KNNX_E_UNSUPPORTED, "range_search is not supported on an IVF-PQ index");
   std::lock_guard<std::mutex> lk(ix->mu);
   if (set_dev(ix)) return KNNX_E_HIP;
   int64_t run = 0;
@@ -2061,6 +2194,7 @@ extern "C" int knnx_ivf_set_lists(knnx_index* ix, int nlist, const uint16_t* cen
   std::lock_guard<std::mutex> lk(ix->mu);
   if (set_dev(ix)) return KNNX_E_HIP;
   if (ix->borrowed) return fail(KNNX_E_STATE, "IVF needs an index that owns its rows");
+  if (ix->pq_m) return fail(KNNX_E_STATE, "an IVF-PQ index is built through knnx_ivf_begin / knnx_ivf_add_assigned / knnx_ivf_end");
   if (ix->ivf_nlist) return fail(KNNX_E_STATE, "lists are already set");
   std::vector<int64_t> src0(nlist);
   std::vector<unsigned> tile0(nlist), ntile(nlist), size(nlist);
@@ -2432,9 +2566,18 @@ extern "C" int knnx_ivf_begin(knnx_index* ix, int nlist, const uint16_t* centroi
   if (ix->rows) hipFree(ix->rows);
   ix->rows = nullptr;
   ix->capacity = 0;
-  HIPCHK(hipMalloc(&ix->rows, (size_t)prow * ix->d * sizeof(_Float16)));
-  ix->capacity = prow;
-  hipError_t e = hipMemsetAsync(ix->rows, 0, (size_t)prow * ix->d * sizeof(_Float16), ix->stream);  // pad rows are zero
+  hipError_t e;
+  if (ix->pq_m) {  // IVF-PQ: M code bytes per arena row, and the centroids on the device for the encoder
+    HIPCHK(hipMalloc(&ix->pq_codes, (size_t)prow * ix->pq_m));
+    ix->capacity = prow;
+    e = hipMemsetAsync(ix->pq_codes, 0, (size_t)prow * ix->pq_m, ix->stream);
+    if (e == hipSuccess) e = hipMalloc(&ix->pq_bcent, (size_t)nlist * ix->d * sizeof(_Float16));
+    if (e == hipSuccess) e = hipMemcpyAsync(ix->pq_bcent, centroids_f16, (size_t)nlist * ix->d * sizeof(_Float16), hipMemcpyHostToDevice, ix->stream);
+  } else {
+    HIPCHK(hipMalloc(&ix->rows, (size_t)prow * ix->d * sizeof(_Float16)));
+    ix->capacity = prow;
+    e = hipMemsetAsync(ix->rows, 0, (size_t)prow * ix->d * sizeof(_Float16), ix->stream);  // pad rows are zero
+  }
   if (e == hipSuccess) e = hipMalloc(&ix->ivf_tile0, nlist * sizeof(unsigned));
   if (e == hipSuccess) e = hipMalloc(&ix->ivf_ntile, nlist * sizeof(unsigned));
   if (e == hipSuccess) e = hipMalloc(&ix->ivf_size, nlist * sizeof(unsigned));
@@ -2518,10 +2661,16 @@ extern "C" int knnx_ivf_add_assigned(knnx_index* ix, const uint16_t* rows_f16, i
     HIPCHK(hipMemcpyAsync(ix->ivfb_ids, p_ids, (size_t)m * 8, hipMemcpyHostToDevice, ix->stream));
     HIPCHK(hipMemcpyAsync(ix->ivfb_lists, p_lists, (size_t)m * 4, hipMemcpyHostToDevice, ix->stream));
     HIPCHK(hipMemcpyAsync(ix->ivfb_pos, p_pos, (size_t)m * 4, hipMemcpyHostToDevice, ix->stream));
-    HIPCHK(launch_ivf_scatter((const _Float16*)ix->ivfb_rows, m, ix->d, (const int32_t*)ix->ivfb_lists, (const int32_t*)ix->ivfb_pos,
-                              (const int64_t*)ix->ivfb_ids, 0, ix->ivf_tile0, ix->id_base, ix->ivfb_total, ix->rows, ix->ivf_idmap,
-                              ix->ivf_inv, ix->stream));
-    HIPCHK(launch_maxnorm((const _Float16*)ix->ivfb_rows, m, ix->d, ix->maxnorm, ix->stream));
+    if (ix->pq_m) {  // IVF-PQ: the rows are encoded into their slots, not copied
+      HIPCHK(launch_pq_encode((const _Float16*)ix->ivfb_rows, m, ix->d, ix->pq_m, (const int32_t*)ix->ivfb_lists, ix->pq_bcent, ix->pq_cb,
+                              ix->ivf_tile0, (const int32_t*)ix->ivfb_pos, (const int64_t*)ix->ivfb_ids, 0, ix->id_base, ix->ivfb_total,
+                              ix->pq_codes, ix->ivf_idmap, ix->ivf_inv, ix->stream));
+    } else {
+      HIPCHK(launch_ivf_scatter((const _Float16*)ix->ivfb_rows, m, ix->d, (const int32_t*)ix->ivfb_lists, (const int32_t*)ix->ivfb_pos,
+                                (const int64_t*)ix->ivfb_ids, 0, ix->ivf_tile0, ix->id_base, ix->ivfb_total, ix->rows, ix->ivf_idmap,
+                                ix->ivf_inv, ix->stream));
+      HIPCHK(launch_maxnorm((const _Float16*)ix->ivfb_rows, m, ix->d, ix->maxnorm, ix->stream));
+    }
     HIPCHK(hipStreamSynchronize(ix->stream));
   }
   ix->ivfb_added += n;
@@ -2574,9 +2723,14 @@ extern "C" int knnx_ivf_add_assigned_device(knnx_index* ix, const void* rows_dev
     }
     HIPCHK(hipMemcpyAsync(ix->ivfb_pos, h_pos, (size_t)m * 4, hipMemcpyHostToDevice, ix->stream));
     const _Float16* src = (const _Float16*)rows_dev + (size_t)o * ix->d;
-    HIPCHK(launch_ivf_scatter(src, m, ix->d, lists_dev + o, (const int32_t*)ix->ivfb_pos, nullptr, id0 + o, ix->ivf_tile0, ix->id_base,
-                              ix->ivfb_total, ix->rows, ix->ivf_idmap, ix->ivf_inv, ix->stream));
-    HIPCHK(launch_maxnorm(src, m, ix->d, ix->maxnorm, ix->stream));
+    if (ix->pq_m) {
+      HIPCHK(launch_pq_encode(src, m, ix->d, ix->pq_m, lists_dev + o, ix->pq_bcent, ix->pq_cb, ix->ivf_tile0, (const int32_t*)ix->ivfb_pos,
+                              nullptr, id0 + o, ix->id_base, ix->ivfb_total, ix->pq_codes, ix->ivf_idmap, ix->ivf_inv, ix->stream));
+    } else {
+      HIPCHK(launch_ivf_scatter(src, m, ix->d, lists_dev + o, (const int32_t*)ix->ivfb_pos, nullptr, id0 + o, ix->ivf_tile0, ix->id_base,
+                                ix->ivfb_total, ix->rows, ix->ivf_idmap, ix->ivf_inv, ix->stream));
+      HIPCHK(launch_maxnorm(src, m, ix->d, ix->maxnorm, ix->stream));
+    }
     HIPCHK(hipStreamSynchronize(ix->stream));
   }
   ix->ivfb_added += n;
@@ -2594,6 +2748,12 @@ extern "C" int knnx_ivf_end(knnx_index* ix) {
     nlist = ix->ivfb_nlist;
     for (int l = 0; l < nlist; ++l)
       if (ix->ivfb_fill[l] != ix->ivfb_size[l]) return fail(KNNX_E_STATE, "a list received fewer rows than its announced size");
+    if (ix->pq_m) {
+      ix->pq_tile0_h.assign(ix->ivfb_tile0.begin(), ix->ivfb_tile0.end());
+      ix->pq_size_h.assign(ix->ivfb_size.begin(), ix->ivfb_size.end());
+      hipFree(ix->pq_bcent);
+      ix->pq_bcent = nullptr;
+    }
     std::vector<uint32_t>().swap(ix->ivfb_size);
     std::vector<uint32_t>().swap(ix->ivfb_fill);
     std::vector<uint32_t>().swap(ix->ivfb_tile0);
@@ -2723,5 +2883,273 @@ extern "C" int knnx_profile_get(knnx_index* ix, int64_t* scan_launches, double* 
   ix->prof_events.clear();
   if (scan_launches) *scan_launches = n;
   if (scan_ms) *scan_ms = ms;
+  return KNNX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// IVF-PQ (faiss IndexIVFPQ(IndexFlatIP(d), d, nlist, M, 8), METRIC_INNER_PRODUCT, by_residual): the index type autofaiss picks
+// for large corpora (the reference's notebook builds OPQ256_768,IVF16384_HNSW32,PQ256x8).  The quantizer is set on an empty
+// index; the IVF build protocol then ENCODES rows into the list-sorted arena; searches go through scan_topk_pq.
+// ---------------------------------------------------------------------------------------------
+extern "C" int knnx_ivfpq_set_quantizer(knnx_index* ix, int M, const float* codebooks) {
+  if (!ix || !codebooks) return fail(KNNX_E_ARG, "bad ivfpq_set_quantizer arguments");
+  if (!pq_supported(ix->d, M)) return fail(KNNX_E_ARG, "IVF-PQ needs M in {16, 32, 64, 128} dividing d (8-bit codes)");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  if (set_dev(ix)) return KNNX_E_HIP;
+  if (ix->borrowed || ix->ntotal != 0 || ix->ivf_nlist || ix->ivfb_nlist || ix->pq_m)
+    return fail(KNNX_E_STATE, "the PQ quantizer is set once, on an empty index, before knnx_ivf_begin");
+  const size_t bytes = (size_t)256 * ix->d * sizeof(float);
+  HIPCHK(hipMalloc(&ix->pq_cb, bytes));
+  HIPCHK(hipMemcpy(ix->pq_cb, codebooks, bytes, hipMemcpyHostToDevice));
+  ix->pq_m = M;
+  return KNNX_OK;
+}
+
+extern "C" int knnx_ivfpq_m(const knnx_index* ix) { return ix ? ix->pq_m : 0; }
+
+extern "C" int knnx_ivfpq_get_codebooks(knnx_index* ix, float* codebooks) {
+  if (!ix || !codebooks) return fail(KNNX_E_ARG, "bad ivfpq_get_codebooks arguments");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  if (!ix->pq_m) return fail(KNNX_E_STATE, "not an IVF-PQ index");
+  if (set_dev(ix)) return KNNX_E_HIP;
+  HIPCHK(hipMemcpy(codebooks, ix->pq_cb, (size_t)256 * ix->d * sizeof(float), hipMemcpyDeviceToHost));
+  return KNNX_OK;
+}
+
+// every row of a built index in arena order: ids [ntotal], lists [ntotal], codes [ntotal][M]
+extern "C" int knnx_ivfpq_get_codes(knnx_index* ix, int64_t* ids, int32_t* lists, uint8_t* codes) {
+  if (!ix || !ids || !lists || !codes) return fail(KNNX_E_ARG, "bad ivfpq_get_codes arguments");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  if (!ix->pq_m || !ix->ivf_nlist) return fail(KNNX_E_STATE, "not a built IVF-PQ index (knnx_ivf_end first)");
+  if (set_dev(ix)) return KNNX_E_HIP;
+  HIPCHK(hipStreamSynchronize(ix->stream));
+  const int M = ix->pq_m;
+  std::vector<int64_t> idmap((size_t)ix->capacity);
+  std::vector<uint8_t> all((size_t)ix->capacity * M);
+  HIPCHK(hipMemcpy(idmap.data(), ix->ivf_idmap, idmap.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(all.data(), ix->pq_codes, all.size(), hipMemcpyDeviceToHost));
+  int64_t o = 0;
+  for (int l = 0; l < ix->ivf_nlist; ++l) {
+    const size_t r0 = (size_t)ix->pq_tile0_h[l] * 32;
+    for (unsigned i = 0; i < ix->pq_size_h[l]; ++i, ++o) {
+      ids[o] = idmap[r0 + i];
+      lists[o] = l;
+      memcpy(codes + (size_t)o * M, all.data() + (r0 + i) * M, M);
+    }
+  }
+  return o == ix->ntotal ? KNNX_OK : fail(KNNX_E_STATE, "internal: IVF-PQ layout does not add up to ntotal");
+}
+
+// precomputed codes [n][M] (host) into an index between knnx_ivf_begin and knnx_ivf_end: the same (list, position) rules as
+// knnx_ivf_add_assigned; no encoding (an index loaded from its saved codes)
+extern "C" int knnx_ivfpq_add_codes(knnx_index* ix, const uint8_t* codes, int64_t n, const int64_t* ids, const int32_t* lists,
+                                    const int32_t* pos) {
+  if (!ix || (n > 0 && (!codes || !ids || !lists || !pos)) || n < 0) return fail(KNNX_E_ARG, "bad ivfpq_add_codes arguments");
+  if (n == 0) return KNNX_OK;
+  std::lock_guard<std::mutex> lk(ix->mu);
+  if (set_dev(ix)) return KNNX_E_HIP;
+  if (!ix->pq_m || !ix->ivfb_nlist) return fail(KNNX_E_STATE, "set the PQ quantizer and call knnx_ivf_begin first");
+  if (ix->ivfb_added + n > ix->ivfb_total) return fail(KNNX_E_ARG, "more rows than the list sizes announced");
+  for (int64_t i = 0; i < n; ++i)
+    if (ids[i] < ix->id_base || ids[i] - ix->id_base >= ix->ivfb_total) return fail(KNNX_E_ARG, "ids must lie in [id_base, id_base + total rows)");
+  for (int64_t i = 0; i < n; ++i)
+    if (!ivfb_claim(ix, lists[i], pos[i])) {
+      for (int64_t j = 0; j < i; ++j) {
+        const size_t slot = (size_t)ix->ivfb_tile0[lists[j]] * 32 + (size_t)pos[j];
+        ix->ivfb_taken[slot >> 6] &= ~(1ull << (slot & 63));
+        ix->ivfb_fill[lists[j]]--;
+      }
+      return KNNX_E_ARG;
+    }
+  const int M = ix->pq_m;
+  // (ivfb_rows holds IVFB_CHUNK x d x 2 >= IVFB_CHUNK x M bytes)
+  for (int64_t o = 0; o < n; o += IVFB_CHUNK) {
+    const int64_t m = std::min(IVFB_CHUNK, n - o);
+    HIPCHK(hipMemcpy(ix->ivfb_rows, codes + (size_t)o * M, (size_t)m * M, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ix->ivfb_ids, ids + o, (size_t)m * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ix->ivfb_lists, lists + o, (size_t)m * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ix->ivfb_pos, pos + o, (size_t)m * 4, hipMemcpyHostToDevice));
+    HIPCHK(launch_pq_scatter_codes((const uint8_t*)ix->ivfb_rows, m, M, (const int32_t*)ix->ivfb_lists, (const int32_t*)ix->ivfb_pos,
+                                   (const int64_t*)ix->ivfb_ids, ix->ivf_tile0, ix->id_base, ix->ivfb_total, ix->pq_codes, ix->ivf_idmap,
+                                   ix->ivf_inv, ix->stream));
+    HIPCHK(hipStreamSynchronize(ix->stream));
+  }
+  ix->ivfb_added += n;
+  return KNNX_OK;
+}
+
+// ---- codebook training (faiss ProductQuantizer::train on the residuals of a sample; one L2 k-means of 256 per sub-quantiser) ----
+struct knnx_pq_builder {
+  int device = 0, d = 0, M = 0, nlist = 0;
+  hipStream_t stream = nullptr;
+  float* cb = nullptr;           // [M][256][d / M]
+  _Float16* X = nullptr;         // sample rows [n][d] (owned unless borrowed)
+  bool borrowed = false;
+  int32_t* lists = nullptr;      // [n] their lists
+  _Float16* cent = nullptr;      // [nlist][d]
+  uint8_t* codes = nullptr;      // [n][M]
+  int32_t* order = nullptr;      // [M][n]
+  int32_t* off = nullptr;        // [M][257]
+  int64_t n = 0;
+  std::vector<uint8_t> h_codes;
+  std::vector<int32_t> h_order, h_off;
+};
+
+static void pqb_free_sample(knnx_pq_builder* b) {
+  if (!b->borrowed) (void)hipFree(b->X);
+  (void)hipFree(b->lists);
+  (void)hipFree(b->cent);
+  (void)hipFree(b->codes);
+  (void)hipFree(b->order);
+  (void)hipFree(b->off);
+  b->X = nullptr;
+  b->lists = nullptr;
+  b->cent = nullptr;
+  b->codes = nullptr;
+  b->order = nullptr;
+  b->off = nullptr;
+  b->borrowed = false;
+  b->n = 0;
+}
+
+extern "C" void knnx_pqb_destroy(knnx_pq_builder* b) {
+  if (!b) return;
+  (void)hipSetDevice(b->device);
+  if (b->stream) (void)hipStreamSynchronize(b->stream);
+  pqb_free_sample(b);
+  (void)hipFree(b->cb);
+  if (b->stream) (void)hipStreamDestroy(b->stream);
+  delete b;
+}
+
+extern "C" int knnx_pqb_create(int device, int d, int M, knnx_pq_builder** out) {
+  if (!out) return fail(KNNX_E_ARG, "out is null");
+  *out = nullptr;
+  if (!pq_supported(d, M)) return fail(KNNX_E_ARG, "IVF-PQ needs M in {16, 32, 64, 128} dividing d (8-bit codes)");
+  HIPCHK(hipSetDevice(device));
+  knnx_pq_builder* b = new knnx_pq_builder();
+  b->device = device;
+  b->d = d;
+  b->M = M;
+  hipError_t e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
+  if (e == hipSuccess) e = hipMalloc(&b->cb, (size_t)256 * d * sizeof(float));
+  if (e == hipSuccess) e = hipMemset(b->cb, 0, (size_t)256 * d * sizeof(float));
+  if (e != hipSuccess) {
+    knnx_pqb_destroy(b);
+    return fail(e == hipErrorOutOfMemory ? KNNX_E_NOMEM : KNNX_E_HIP, std::string("pqb_create: ") + hipGetErrorString(e));
+  }
+  *out = b;
+  return KNNX_OK;
+}
+
+// the part of set_sample shared by the host and the device variant: lists (host copy h_lists, validated), centroids, scratch
+static int pqb_sample_common(knnx_pq_builder* b, int64_t n, const int32_t* h_lists, const uint16_t* centroids_f16, int nlist) {
+  for (int64_t i = 0; i < n; ++i)
+    if (h_lists[i] < 0 || h_lists[i] >= nlist) return fail(KNNX_E_ARG, "a sample row's list id is outside [0, nlist)");
+  b->nlist = nlist;
+  b->n = n;
+  HIPCHK(hipMalloc(&b->lists, (size_t)n * sizeof(int32_t)));
+  HIPCHK(hipMemcpy(b->lists, h_lists, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIPCHK(hipMalloc(&b->cent, (size_t)nlist * b->d * sizeof(_Float16)));
+  HIPCHK(hipMemcpy(b->cent, centroids_f16, (size_t)nlist * b->d * sizeof(_Float16), hipMemcpyHostToDevice));
+  HIPCHK(hipMalloc(&b->codes, (size_t)n * b->M));
+  HIPCHK(hipMalloc(&b->order, (size_t)n * b->M * sizeof(int32_t)));
+  HIPCHK(hipMalloc(&b->off, (size_t)b->M * 257 * sizeof(int32_t)));
+  return KNNX_OK;
+}
+
+extern "C" int knnx_pqb_set_sample(knnx_pq_builder* b, const uint16_t* rows_f16, const int32_t* lists, int64_t n, const uint16_t* centroids_f16,
+                                   int nlist) {
+  if (!b || !rows_f16 || !lists || !centroids_f16 || n <= 0 || n > INT32_MAX || nlist <= 0) return fail(KNNX_E_ARG, "bad pqb_set_sample arguments");
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  pqb_free_sample(b);
+  HIPCHK(hipMalloc(&b->X, (size_t)n * b->d * sizeof(_Float16)));
+  HIPCHK(hipMemcpy(b->X, rows_f16, (size_t)n * b->d * sizeof(_Float16), hipMemcpyHostToDevice));
+  return pqb_sample_common(b, n, lists, centroids_f16, nlist);
+}
+
+// rows_dev: fp16 [n][d] borrowed (kept alive by the caller until the training is over); lists_dev: int32 [n] (copied)
+extern "C" int knnx_pqb_set_sample_device(knnx_pq_builder* b, const void* rows_dev_f16, const int32_t* lists_dev, int64_t n,
+                                          const uint16_t* centroids_f16, int nlist) {
+  if (!b || !rows_dev_f16 || !lists_dev || !centroids_f16 || n <= 0 || n > INT32_MAX || nlist <= 0)
+    return fail(KNNX_E_ARG, "bad pqb_set_sample_device arguments");
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  pqb_free_sample(b);
+  std::vector<int32_t> h((size_t)n);
+  HIPCHK(hipMemcpy(h.data(), lists_dev, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  b->X = (_Float16*)rows_dev_f16;
+  b->borrowed = true;
+  return pqb_sample_common(b, n, h.data(), centroids_f16, nlist);
+}
+
+// codebook entries mj[i] (= m * 256 + j) := residual sub-vector m of sample row sample_rows[i]
+extern "C" int knnx_pqb_seed_from_sample(knnx_pq_builder* b, const int32_t* mj, const int64_t* sample_rows, int64_t n) {
+  if (!b || (n > 0 && (!mj || !sample_rows)) || n < 0 || !b->X) return fail(KNNX_E_ARG, "bad pqb_seed_from_sample arguments (set a sample first)");
+  if (n == 0) return KNNX_OK;
+  for (int64_t i = 0; i < n; ++i)
+    if (mj[i] < 0 || mj[i] >= b->M * 256 || sample_rows[i] < 0 || sample_rows[i] >= b->n) return fail(KNNX_E_ARG, "codebook entry / sample row out of range");
+  HIPCHK(hipSetDevice(b->device));
+  int32_t* mj_dev = nullptr;
+  int64_t* r_dev = nullptr;
+  HIPCHK(hipMalloc(&mj_dev, (size_t)n * sizeof(int32_t)));
+  hipError_t e = hipMalloc(&r_dev, (size_t)n * sizeof(int64_t));
+  if (e == hipSuccess) e = hipMemcpy(mj_dev, mj, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(r_dev, sample_rows, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = launch_pq_seed(b->X, b->d, b->M, b->lists, b->cent, mj_dev, r_dev, n, b->cb, b->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+  (void)hipFree(mj_dev);
+  (void)hipFree(r_dev);
+  if (e != hipSuccess) return fail(KNNX_E_HIP, std::string("pqb_seed_from_sample: ") + hipGetErrorString(e));
+  return KNNX_OK;
+}
+
+extern "C" int knnx_pqb_set_codebooks(knnx_pq_builder* b, const float* codebooks) {
+  if (!b || !codebooks) return fail(KNNX_E_ARG, "bad pqb_set_codebooks arguments");
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  HIPCHK(hipMemcpy(b->cb, codebooks, (size_t)256 * b->d * sizeof(float), hipMemcpyHostToDevice));
+  return KNNX_OK;
+}
+
+extern "C" int knnx_pqb_get_codebooks(knnx_pq_builder* b, float* codebooks) {
+  if (!b || !codebooks) return fail(KNNX_E_ARG, "bad pqb_get_codebooks arguments");
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  HIPCHK(hipMemcpy(codebooks, b->cb, (size_t)256 * b->d * sizeof(float), hipMemcpyDeviceToHost));
+  return KNNX_OK;
+}
+
+// One Lloyd iteration of the M k-means: encode the sample (argmin per sub-quantiser, ties -> smaller j) -> codes to the host ->
+// counting sort per sub-quantiser (members ascending by sample row: the fixed summation order) -> mean update; an empty
+// cluster keeps its centroid (the caller re-seeds it).  codes_out [n][M] (this iteration's assignment) and sizes_out [M][256]
+// (host) may be null.
+extern "C" int knnx_pqb_lloyd(knnx_pq_builder* b, uint8_t* codes_out, int64_t* sizes_out) {
+  if (!b || !b->X) return fail(KNNX_E_ARG, "bad pqb_lloyd arguments (set a sample first)");
+  HIPCHK(hipSetDevice(b->device));
+  const int64_t n = b->n;
+  const int M = b->M;
+  b->h_codes.resize((size_t)n * M);
+  b->h_order.resize((size_t)n * M);
+  b->h_off.assign((size_t)M * 257, 0);
+  HIPCHK(launch_pq_encode(b->X, n, b->d, M, b->lists, b->cent, b->cb, nullptr, nullptr, nullptr, 0, 0, 0, b->codes, nullptr, nullptr, b->stream));
+  HIPCHK(hipMemcpyAsync(b->h_codes.data(), b->codes, (size_t)n * M, hipMemcpyDeviceToHost, b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  for (int m = 0; m < M; ++m) {
+    int32_t* off = b->h_off.data() + (size_t)m * 257;
+    for (int64_t i = 0; i < n; ++i) off[b->h_codes[(size_t)i * M + m] + 1]++;
+    if (sizes_out)
+      for (int j = 0; j < 256; ++j) sizes_out[(size_t)m * 256 + j] = off[j + 1];
+    for (int j = 0; j < 256; ++j) off[j + 1] += off[j];
+    std::vector<int32_t> cur(off, off + 256);
+    int32_t* ord = b->h_order.data() + (size_t)m * n;
+    for (int64_t i = 0; i < n; ++i) ord[cur[b->h_codes[(size_t)i * M + m]]++] = (int32_t)i;
+  }
+  if (codes_out) memcpy(codes_out, b->h_codes.data(), (size_t)n * M);
+  HIPCHK(hipMemcpyAsync(b->order, b->h_order.data(), (size_t)n * M * sizeof(int32_t), hipMemcpyHostToDevice, b->stream));
+  HIPCHK(hipMemcpyAsync(b->off, b->h_off.data(), (size_t)M * 257 * sizeof(int32_t), hipMemcpyHostToDevice, b->stream));
+  HIPCHK(launch_pq_update(b->X, b->d, M, b->lists, b->cent, b->order, b->off, n, b->cb, b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
   return KNNX_OK;
 }

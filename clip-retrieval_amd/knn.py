@@ -218,6 +218,37 @@ class Mi355xIndex(_FaissShaped):
         check(self._lib, self._lib.knnx_ivf_last_scan_union_tiles(self._h, C.byref(t)), "knnx")
         return int(t.value)
 
+    # ------------------------------------------------------------------ IVF-PQ
+    def set_pq_quantizer(self, M, codebooks):
+        """Make this EMPTY index an IVF-PQ one (faiss IndexIVFPQ(IndexFlatIP(d), d, nlist, M, 8)): codebooks f32 [M, 256, d_padded / M].
+        The rows then go in through knnx_ivf_begin / add_assigned / end (build_ivfpq_index*), which encode them."""
+        cb = np.ascontiguousarray(codebooks, dtype=np.float32)
+        if cb.size != 256 * self._dpad:
+            raise AssertionError(f"codebooks must hold M x 256 x d_padded / M = {256 * self._dpad} floats, got {cb.shape}")
+        check(self._lib, self._lib.knnx_ivfpq_set_quantizer(self._h, int(M), cb.ctypes.data), "knnx")
+
+    @property
+    def pq_m(self):
+        """Bytes of code per row of an IVF-PQ index (0: another index type)."""
+        return int(self._lib.knnx_ivfpq_m(self._h)) if self._h else 0
+
+    def pq_codebooks(self):
+        """f32 [M, 256, d_padded / M]."""
+        M = self.pq_m
+        out = np.empty((M, 256, self._dpad // max(M, 1)), dtype=np.float32)
+        check(self._lib, self._lib.knnx_ivfpq_get_codebooks(self._h, out.ctypes.data), "knnx")
+        return out
+
+    def pq_codes(self):
+        """(codes u8 [ntotal, M], lists int32 [ntotal]) in id order: row i belongs to id id_base + i."""
+        n, M = self.ntotal, self.pq_m
+        ids = np.empty(n, dtype=np.int64)
+        lists = np.empty(n, dtype=np.int32)
+        codes = np.empty((n, M), dtype=np.uint8)
+        check(self._lib, self._lib.knnx_ivfpq_get_codes(self._h, ids.ctypes.data, lists.ctypes.data, codes.ctypes.data), "knnx")
+        order = np.argsort(ids, kind="stable")
+        return np.ascontiguousarray(codes[order]), np.ascontiguousarray(lists[order])
+
     # ------------------------------------------------------------------ searching
     def _search_raw(self, q, k, want_r):
         n = q.shape[0]
@@ -486,6 +517,8 @@ def load_index(path, device=0, row_range=None, enable_faiss_memory_mapping=False
     (`ShardedMi355xIndex`, the KnnService case).  `enable_faiss_memory_mapping` is accepted for call compatibility:
     rows are always resident in HBM; the files themselves are read through np.load(mmap_mode="r").
     """
+    if os.path.isfile(os.path.join(path, IVFPQ_MANIFEST)):  # a saved IVF-PQ index: self-contained, no embeddings needed
+        return _load_ivfpq_index(path, device=device, row_range=row_range, devices=devices)
     if os.path.isfile(os.path.join(path, IVF_MANIFEST)):  # a built IVF-Flat index saved by save_index(): no k-means, no assignment
         return _load_ivf_index(path, device=device, row_range=row_range, devices=devices)
     src = FolderRows(path)
@@ -959,6 +992,8 @@ def save_index(index, folder, embeddings_folder=None):
     `load_index(folder)` in the place of clip_back.py:589-596."""
     import json  # pylint: disable=import-outside-toplevel
 
+    if getattr(index, "pq_m", 0):
+        return _save_ivfpq_index(index, folder)
     lists, cent = getattr(index, "ivf_lists", None), getattr(index, "ivf_centroids", None)
     src = getattr(index, "ivf_source", None)
     if lists is None or cent is None:
@@ -1026,3 +1061,337 @@ def _load_ivf_index(folder, device=0, row_range=None, devices=None, embeddings_f
     if not slo <= lo <= hi <= shi:
         raise ValueError(f"row_range {row_range} is outside the saved shard's rows [{slo}, {shi})")
     return _scatter_into_ivf(src, lo, hi, cent, np.asarray(lists[lo - slo:hi - slo]), man["nprobe"], device, chunk)
+
+
+# ------------------------------------------------------------------------------------------------------------
+# IVF-PQ (faiss IndexIVFPQ(IndexFlatIP(d), d, nlist, M, 8), METRIC_INNER_PRODUCT, by_residual): what autofaiss builds for large
+# corpora (clip_index.py:12-66; the reference notebook's OPQ256_768,IVF16384_HNSW32,PQ256x8 without OPQ / HNSW).  The coarse
+# quantiser is the IVF-Flat one; every row is kept as M code bytes (csrc/knn_pq_kernels.hip), so 1 B x 768 fits one GPU.
+# ------------------------------------------------------------------------------------------------------------
+PQ_SAMPLE_ROWS = 256 * 256  # rows of the codebook training sample (faiss: 256 x ksub)
+IVFPQ_MANIFEST = "ivf_pq_manifest.json"
+IVFPQ_FORMAT = "clip-retrieval_amd ivf-pq v1"
+
+
+def _f16_padded(x, dpad):
+    x = np.asarray(x)
+    if x.dtype != np.float16:
+        x = x.astype(np.float16)
+    if x.shape[1] != dpad:
+        out = np.zeros((x.shape[0], dpad), dtype=np.float16)
+        out[:, : x.shape[1]] = x
+        x = out
+    return np.ascontiguousarray(x)
+
+
+class PqBuilder:
+    """Codebook training on one GPU (knnx_pqb_* of include/knnx.h): the sample rows, their lists and the coarse centroids stay
+    resident; lloyd() = one iteration of the M L2 k-means (device assignment, host counting sort, fixed-order device mean)."""
+
+    def __init__(self, d, M, device=0):
+        self._lib = load_library()
+        self.d, self.M, self.device = int(d), int(M), int(device)
+        self._dpad = (self.d + 255) // 256 * 256
+        h = C.c_void_p()
+        check(self._lib, self._lib.knnx_pqb_create(self.device, self._dpad, self.M, C.byref(h)), "knnx")
+        self._h = h
+        self.n_sample = 0
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._lib.knnx_pqb_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pylint: disable=broad-except
+            pass
+
+    def set_sample(self, x_f16, lists, centroids):
+        x = _f16_padded(x_f16, self._dpad)
+        ls = np.ascontiguousarray(lists, dtype=np.int32)
+        c = _f16_padded(centroids, self._dpad)
+        assert ls.shape[0] == x.shape[0]
+        self.n_sample = x.shape[0]
+        check(self._lib, self._lib.knnx_pqb_set_sample(self._h, x.ctypes.data, ls.ctypes.data, x.shape[0], c.ctypes.data, c.shape[0]), "knnx")
+
+    def set_sample_device(self, rows_ptr, lists_ptr, n, centroids):
+        """Borrow n fp16 device rows [n, d_padded] with their int32 device list ids (the caller keeps the rows alive)."""
+        c = _f16_padded(centroids, self._dpad)
+        self.n_sample = int(n)
+        check(self._lib, self._lib.knnx_pqb_set_sample_device(self._h, C.c_void_p(rows_ptr), C.c_void_p(lists_ptr), int(n), c.ctypes.data,
+                                                              c.shape[0]), "knnx")
+
+    def seed_from_sample(self, mj, sample_rows):
+        """codebook entry mj[i] (= m * 256 + j) := residual sub-vector m of sample row sample_rows[i]."""
+        a = np.ascontiguousarray(mj, dtype=np.int32)
+        r = np.ascontiguousarray(sample_rows, dtype=np.int64)
+        assert a.shape == r.shape
+        check(self._lib, self._lib.knnx_pqb_seed_from_sample(self._h, a.ctypes.data, r.ctypes.data, a.size), "knnx")
+
+    def set_codebooks(self, cb):
+        cb = np.ascontiguousarray(cb, dtype=np.float32)
+        assert cb.size == 256 * self._dpad
+        check(self._lib, self._lib.knnx_pqb_set_codebooks(self._h, cb.ctypes.data), "knnx")
+
+    def codebooks(self):
+        out = np.empty((self.M, 256, self._dpad // self.M), dtype=np.float32)
+        check(self._lib, self._lib.knnx_pqb_get_codebooks(self._h, out.ctypes.data), "knnx")
+        return out
+
+    def lloyd(self, want_codes=False):
+        """One iteration; returns (cluster sizes int64 [M, 256], the iteration's codes u8 [n, M] or None)."""
+        sizes = np.empty((self.M, 256), dtype=np.int64)
+        codes = np.empty((self.n_sample, self.M), dtype=np.uint8) if want_codes else None
+        check(self._lib, self._lib.knnx_pqb_lloyd(self._h, codes.ctypes.data if want_codes else None, sizes.ctypes.data), "knnx")
+        return sizes, codes
+
+
+def train_pq_codebooks(builder, niter=10, seed=0):
+    """M independent L2 k-means of 256 over the builder's resident residual sample: initial codewords are residual sub-vectors of
+    distinct random sample rows (per sub-quantiser), then `niter` Lloyd iterations; between iterations an empty cluster is re-seeded
+    on a random sample row (a host step, as in the IVF-Flat trainer).  Returns the codebooks f32 [M, 256, d_padded / M]."""
+    rng = np.random.default_rng(seed)
+    n, M = builder.n_sample, builder.M
+    if n < 256:
+        raise ValueError(f"PQ training needs at least 256 sample rows, got {n}")
+    rows = np.concatenate([np.sort(rng.choice(n, 256, replace=False)) for _ in range(M)])
+    builder.seed_from_sample(np.arange(M * 256), rows)
+    for it in range(niter):
+        sizes, _ = builder.lloyd()
+        empty = np.flatnonzero(sizes.reshape(-1) == 0)
+        if empty.size and it < niter - 1:
+            builder.seed_from_sample(empty, rng.choice(n, empty.size))
+    return builder.codebooks()
+
+
+def train_ivfpq(x_f16, nlist, M, niter=8, pq_niter=10, seed=0, device=0, sample_rows=PQ_SAMPLE_ROWS, centroids=None,
+                max_points_per_centroid=256):
+    """faiss IndexIVFPQ.train order: the coarse centroids first (the spherical k-means of train_ivf_centroids; `centroids=` skips it),
+    then the M sub-quantisers on the residuals of a sample of <= sample_rows rows against their lists.  Returns (centroids fp16
+    [nlist, d], codebooks f32 [M, 256, d_padded / M])."""
+    x_f16 = np.asarray(x_f16)
+    n, d = x_f16.shape
+    if centroids is None:
+        centroids = train_ivf_centroids(x_f16, nlist, niter=niter, seed=seed, device=device, max_points_per_centroid=max_points_per_centroid)
+    centroids = np.asarray(centroids).astype(np.float16)
+    rng = np.random.default_rng(seed + 1)
+    take = min(n, int(sample_rows))
+    sample = np.asarray(x_f16[np.sort(rng.choice(n, take, replace=False))] if take < n else x_f16, dtype=np.float16)
+    ib = IvfBuilder(d, centroids.shape[0], device)
+    ib.set_centroids(centroids)
+    lists = ib.assign(sample)
+    ib.close()
+    b = PqBuilder(d, M, device)
+    b.set_sample(sample, lists, centroids)
+    cb = train_pq_codebooks(b, niter=pq_niter, seed=seed)
+    b.close()
+    return centroids, cb
+
+
+def _ivfpq_begin(d, nlist, M, centroids, codebooks, sizes, device, id_base):
+    index = Mi355xIndex(d, device=device, id_base=id_base)
+    index.set_pq_quantizer(M, codebooks)
+    cpad = np.ascontiguousarray(index._pad(np.asarray(centroids, dtype=np.float16)))  # pylint: disable=protected-access
+    check(index._lib, index._lib.knnx_ivf_begin(index._h, nlist, cpad.ctypes.data, np.ascontiguousarray(sizes, dtype=np.int64).ctypes.data), "knnx")  # pylint: disable=protected-access
+    return index
+
+
+def _ivfpq_end(index, nlist, nprobe, centroids, id_base, n):
+    check(index._lib, index._lib.knnx_ivf_end(index._h), "knnx")  # pylint: disable=protected-access
+    index.nprobe = min(int(nprobe), nlist)
+    index.ivf_centroids, index.ivf_row_range = np.asarray(centroids, dtype=np.float16), (int(id_base), int(id_base) + int(n))
+    return index
+
+
+def _ivfpq_encode_chunks(chunks, n, d, nlist, M, centroids, codebooks, lists, nprobe, device, id_base):
+    """Rows (an iterator of (offset, fp16 rows)) -> IVF-PQ index: every row is encoded into the next free slot of its list."""
+    sizes = np.bincount(lists, minlength=nlist).astype(np.int64)
+    if sizes.shape[0] != nlist:
+        raise ValueError("a list id is outside [0, nlist)")
+    index = _ivfpq_begin(d, nlist, M, centroids, codebooks, sizes, device, id_base)
+    lib = index._lib  # pylint: disable=protected-access
+    cursor = np.zeros(nlist, dtype=np.int64)
+    for o, x in chunks:
+        rows = np.ascontiguousarray(index._pad(np.asarray(x, dtype=np.float16)))  # pylint: disable=protected-access
+        ls = np.ascontiguousarray(lists[o:o + rows.shape[0]], dtype=np.int32)
+        pos = _positions_in_lists(ls, cursor)
+        ids = np.arange(o, o + rows.shape[0], dtype=np.int64) + id_base
+        check(lib, lib.knnx_ivf_add_assigned(index._h, rows.ctypes.data, rows.shape[0], ids.ctypes.data, ls.ctypes.data, pos.ctypes.data), "knnx")  # pylint: disable=protected-access
+    index = _ivfpq_end(index, nlist, nprobe, centroids, id_base, n)
+    index.ivf_lists = lists
+    return index
+
+
+def build_ivfpq_index(x_f16, nlist, M, nprobe=16, niter=8, pq_niter=10, seed=0, device=0, id_base=0, centroids=None, codebooks=None,
+                      chunk=1 << 20):
+    """fp16 rows [N, d] -> HBM-resident IVF-PQ index (ids = id_base + row number).  Trains (train_ivfpq) unless both `centroids` and
+    `codebooks` are given; lists by the MFMA assignment kernel; codes by the device encoder."""
+    n, d = x_f16.shape
+    if centroids is None or codebooks is None:
+        centroids, codebooks = train_ivfpq(x_f16, nlist, M, niter=niter, pq_niter=pq_niter, seed=seed, device=device, centroids=centroids)
+    centroids = np.asarray(centroids).astype(np.float16)
+    b = IvfBuilder(d, nlist, device)
+    b.set_centroids(centroids)
+    lists = np.empty(n, dtype=np.int32)
+    for o in range(0, n, chunk):
+        lists[o:o + chunk] = b.assign(x_f16[o:o + chunk])
+    b.close()
+    return _ivfpq_encode_chunks(((o, x_f16[o:o + chunk]) for o in range(0, n, chunk)), n, d, nlist, M, centroids, codebooks, lists, nprobe,
+                                device, id_base)
+
+
+def build_ivfpq_index_from_folder(path, nlist, M, nprobe=16, niter=8, pq_niter=10, seed=0, device=0, centroids=None, codebooks=None,
+                                  max_points_per_centroid=256, chunk=1 << 20):
+    """`clip inference` output folder (img_emb_*.npy) -> IVF-PQ index, streaming the partitions: training on a strided sample of the
+    whole folder, then one assignment pass and one encoding pass.  The result can be save_index()ed (self-contained)."""
+    src = path if isinstance(path, FolderRows) else FolderRows(path)
+    if centroids is None or codebooks is None:
+        take = min(src.n, max(int(nlist) * int(max_points_per_centroid), PQ_SAMPLE_ROWS))
+        idx = np.unique(np.linspace(0, src.n - 1, take).astype(np.int64))
+        centroids, codebooks = train_ivfpq(src.take(idx), nlist, M, niter=niter, pq_niter=pq_niter, seed=seed, device=device,
+                                           centroids=centroids, max_points_per_centroid=max_points_per_centroid)
+    centroids = np.asarray(centroids).astype(np.float16)
+    b = IvfBuilder(src.d, nlist, device)
+    b.set_centroids(centroids)
+    lists = np.empty(src.n, dtype=np.int32)
+    for o, x in src.chunks(0, src.n, chunk):
+        lists[o:o + x.shape[0]] = b.assign(x)
+    b.close()
+    return _ivfpq_encode_chunks(src.chunks(0, src.n, chunk), src.n, src.d, nlist, M, centroids, codebooks, lists, nprobe, device, 0)
+
+
+def build_ivfpq_index_device(fill_rows, n, d, nlist, M, nprobe=16, niter=8, pq_niter=10, seed=0, device=0, id_base=0, centroids=None,
+                             codebooks=None, chunk=1 << 20, alloc=None, points_per_centroid=64, pq_sample_rows=PQ_SAMPLE_ROWS):
+    """IVF-PQ index over n rows PRODUCED ON THE GPU (`fill_rows(dst_ptr, row0, count, stride)` as in build_ivf_index_device): the
+    fp16 corpus never exists whole -- training samples, then per chunk one assignment pass and one encoding pass; the index keeps
+    M bytes per row.  Returns (index, stats dict)."""
+    import time
+
+    assert d % 256 == 0, "device builds take padded rows (d % 256 == 0)"
+    lib = load_library()
+    if alloc is None:
+        def alloc(nbytes):
+            import torch
+
+            t = torch.empty(int(nbytes), dtype=torch.uint8, device=f"cuda:{device}")
+            return t.data_ptr(), t
+    t0 = time.perf_counter()
+    b = IvfBuilder(d, nlist, device)
+    if centroids is None:
+        n_sample = int(min(n, nlist * points_per_centroid))
+        sample_ptr, sample_keep = alloc(n_sample * d * 2)
+        fill_rows(sample_ptr, 0, n_sample, max(1, n // n_sample))
+        train_ivf_centroids_device(b, sample_ptr, n_sample, niter=niter, seed=seed)
+        centroids = np.ascontiguousarray(b.centroids())
+        del sample_keep
+    centroids = np.asarray(centroids).astype(np.float16)
+    b.set_centroids(centroids)
+    if codebooks is None:
+        n_ps = int(min(n, pq_sample_rows))
+        ps_ptr, ps_keep = alloc(n_ps * d * 2)
+        pl_ptr, pl_keep = alloc(n_ps * 4)
+        fill_rows(ps_ptr, 0, n_ps, max(1, n // n_ps))
+        b.assign_device(ps_ptr, n_ps, pl_ptr)
+        pb = PqBuilder(d, M, device)
+        pb.set_sample_device(ps_ptr, pl_ptr, n_ps, centroids)
+        codebooks = train_pq_codebooks(pb, niter=pq_niter, seed=seed)
+        pb.close()
+        del ps_keep, pl_keep
+    _release_cached_device_memory()
+    t1 = time.perf_counter()
+    lists_ptr, lists_keep = alloc(n * 4)
+    rows_ptr, rows_keep = alloc(min(chunk, n) * d * 2)
+    b.list_sizes(reset=True)
+    for o in range(0, n, chunk):
+        m = min(chunk, n - o)
+        fill_rows(rows_ptr, o, m, 1)
+        b.assign_device(rows_ptr, m, lists_ptr + 4 * o)
+    sizes = b.list_sizes()
+    b.close()
+    t2 = time.perf_counter()
+    index = _ivfpq_begin(d, nlist, M, centroids, codebooks, sizes, device, id_base)
+    for o in range(0, n, chunk):
+        m = min(chunk, n - o)
+        fill_rows(rows_ptr, o, m, 1)
+        check(lib, lib.knnx_ivf_add_assigned_device(index._h, C.c_void_p(rows_ptr), m, id_base + o, C.c_void_p(lists_ptr + 4 * o)), "knnx")  # pylint: disable=protected-access
+    index = _ivfpq_end(index, nlist, nprobe, centroids, id_base, n)
+    del rows_keep, lists_keep
+    _release_cached_device_memory()
+    t3 = time.perf_counter()
+    stats = {"train_s": t1 - t0, "assign_s": t2 - t1, "encode_s": t3 - t2, "list_sizes": sizes, "bytes_per_row": M + 12}
+    return index, stats
+
+
+def _save_ivfpq_index(index, folder):
+    """The self-contained IVF-PQ folder: ivf_pq_centroids.npy (fp16 [nlist, d]), ivf_pq_codebooks.npy (f32 [M, 256, d_padded / M]),
+    ivf_pq_codes.npy (u8 [n, M] in id order), ivf_pq_lists.npy (int32 [n]) and ivf_pq_manifest.json (written last)."""
+    import json  # pylint: disable=import-outside-toplevel
+
+    cent = getattr(index, "ivf_centroids", None)
+    if cent is None:
+        raise ValueError("save_index takes an IVF-PQ index built by build_ivfpq_index* / load_index")
+    codes, lists = index.pq_codes()
+    lo, hi = getattr(index, "ivf_row_range", (0, codes.shape[0]))
+    os.makedirs(folder, exist_ok=True)
+    np.save(os.path.join(folder, "ivf_pq_centroids.npy"), np.asarray(cent, dtype=np.float16))
+    np.save(os.path.join(folder, "ivf_pq_codebooks.npy"), index.pq_codebooks())
+    np.save(os.path.join(folder, "ivf_pq_codes.npy"), codes)
+    np.save(os.path.join(folder, "ivf_pq_lists.npy"), lists)
+    man = {"format": IVFPQ_FORMAT, "d": int(index.d), "nlist": int(cent.shape[0]), "M": int(index.pq_m), "nprobe": int(index.nprobe),
+           "row_range": [int(lo), int(hi)]}
+    tmp = os.path.join(folder, IVFPQ_MANIFEST + ".part")
+    with open(tmp, "w", encoding="utf-8") as f:
+        json.dump(man, f, indent=1)
+    os.replace(tmp, os.path.join(folder, IVFPQ_MANIFEST))
+    return man
+
+
+def _ivfpq_from_codes(codes, lists, lo, cent, cb, M, nprobe, device, chunk=1 << 20):
+    nlist, d = cent.shape
+    n = codes.shape[0]
+    sizes = np.bincount(lists, minlength=nlist).astype(np.int64)
+    index = _ivfpq_begin(d, nlist, M, cent, cb, sizes, device, lo)
+    lib = index._lib  # pylint: disable=protected-access
+    cursor = np.zeros(nlist, dtype=np.int64)
+    for o in range(0, n, chunk):
+        c = np.ascontiguousarray(codes[o:o + chunk], dtype=np.uint8)
+        ls = np.ascontiguousarray(lists[o:o + chunk], dtype=np.int32)
+        pos = _positions_in_lists(ls, cursor)
+        ids = np.arange(lo + o, lo + o + c.shape[0], dtype=np.int64)
+        check(lib, lib.knnx_ivfpq_add_codes(index._h, c.ctypes.data, c.shape[0], ids.ctypes.data, ls.ctypes.data, pos.ctypes.data), "knnx")  # pylint: disable=protected-access
+    index = _ivfpq_end(index, nlist, nprobe, cent, lo, n)
+    index.ivf_lists = np.asarray(lists, dtype=np.int32)
+    return index
+
+
+def _load_ivfpq_index(folder, device=0, row_range=None, devices=None):
+    import json  # pylint: disable=import-outside-toplevel
+
+    with open(os.path.join(folder, IVFPQ_MANIFEST), encoding="utf-8") as f:
+        man = json.load(f)
+    if man.get("format") != IVFPQ_FORMAT:
+        raise ValueError(f"{folder}: unknown index format {man.get('format')!r}")
+    cent = np.load(os.path.join(folder, "ivf_pq_centroids.npy"))
+    cb = np.load(os.path.join(folder, "ivf_pq_codebooks.npy"))
+    codes = np.load(os.path.join(folder, "ivf_pq_codes.npy"), mmap_mode="r")
+    lists = np.load(os.path.join(folder, "ivf_pq_lists.npy"), mmap_mode="r")
+    slo, shi = man["row_range"]
+    M = int(man["M"])
+    if cent.shape != (man["nlist"], man["d"]) or codes.shape != (shi - slo, M) or lists.shape[0] != shi - slo:
+        raise ValueError(f"{folder}: the IVF-PQ files disagree with the manifest")
+    if devices is not None:
+        if row_range is not None:
+            raise ValueError("row_range and devices are mutually exclusive")
+        G = len(devices)
+        cuts = [slo + (shi - slo) * g // G for g in range(G + 1)]
+        shards = [_ivfpq_from_codes(codes[cuts[g] - slo:cuts[g + 1] - slo], np.asarray(lists[cuts[g] - slo:cuts[g + 1] - slo]), cuts[g], cent, cb,
+                                    M, man["nprobe"], devices[g]) for g in range(G)]
+        sharded = ShardedMi355xIndex.from_shards(shards, cuts[:-1])
+        sharded.nprobe = man["nprobe"]
+        return sharded
+    lo, hi = (slo, shi) if row_range is None else (int(row_range[0]), int(row_range[1]))
+    if not slo <= lo <= hi <= shi:
+        raise ValueError(f"row_range {row_range} is outside the saved shard's rows [{slo}, {shi})")
+    return _ivfpq_from_codes(codes[lo - slo:hi - slo], np.asarray(lists[lo - slo:hi - slo]), lo, cent, cb, M, man["nprobe"], device)

@@ -148,6 +148,40 @@ int knnx_ivfb_assign_device(knnx_ivf_builder* b, const void* rows_dev_f16, int64
 int knnx_ivfb_list_sizes(knnx_ivf_builder* b, int64_t* sizes_out, int reset);
 int knnx_ivf_add_assigned_device(knnx_index* ix, const void* rows_dev_f16, int64_t n, int64_t id0, const int32_t* lists_dev);
 
+/* ---- IVF-PQ: faiss IndexIVFPQ(IndexFlatIP(d), d, nlist, M, 8), METRIC_INNER_PRODUCT, by_residual = true ----------------------
+ * (the index type autofaiss builds for large corpora -- clip_index.py:12-66; the reference notebook's OPQ256_768,IVF16384_HNSW32,PQ256x8
+ * without the rotation and the HNSW coarse quantiser).  M in {16, 32, 64, 128} dividing d, 256 centroids per sub-quantiser; other M:
+ * KNNX_E_ARG.  Codebooks: f32 [M][256][d / M].  Row x of list l: residual r = f32(x_f16) - f32(c_l), code byte m =
+ * argmin_j ||r_m - C[m][j]||^2 in fp32 (ties -> smaller j).  Score = <q, c_l> + sum over m (in order) of LUT[m][code_m], LUT[m][j] =
+ * <q_m, C[m][j]> in fp32; the coarse quantiser and its probe rule are those of IVF-Flat.  Results as knnx_search; reconstruct /
+ * the R of search returns the decoded vector f32(c_l) + concat_m C[m][code_m].
+ * Build: knnx_ivfpq_set_quantizer on an empty index, then knnx_ivf_begin / knnx_ivf_add_assigned[_device] / knnx_ivf_end ENCODE
+ * the rows (same list / position rules), or knnx_ivfpq_add_codes loads precomputed codes in their place.  The arena holds M bytes
+ * per row.  k > 64 and range_search answer KNNX_E_UNSUPPORTED; add / attach / synth_fill / reset / reserve / knnx_ivf_set_lists
+ * answer KNNX_E_STATE.  At most 2^32 - 1 padded rows per device. */
+int knnx_ivfpq_set_quantizer(knnx_index* ix, int M, const float* codebooks);
+int knnx_ivfpq_add_codes(knnx_index* ix, const uint8_t* codes, int64_t n, const int64_t* ids, const int32_t* lists, const int32_t* pos);
+int knnx_ivfpq_m(const knnx_index* ix); /* 0: not an IVF-PQ index */
+/* every row of a built index, in arena order (list by list): ids [ntotal], lists [ntotal], codes [ntotal][M] (host) */
+int knnx_ivfpq_get_codes(knnx_index* ix, int64_t* ids, int32_t* lists, uint8_t* codes);
+int knnx_ivfpq_get_codebooks(knnx_index* ix, float* codebooks);
+/* Codebook training on the device (faiss trains the M sub-quantisers on the residuals of a sample; default 256 x 256 rows):
+ * the builder keeps the sample rows (fp16 [n][d]) with their list ids and the coarse centroids resident.  knnx_pqb_lloyd = one
+ * iteration of all M L2 k-means: assignment (the encode kernel), counting sort on the host, fixed-order mean update; an empty
+ * cluster keeps its codeword (codes_out [n][M], sizes_out [M][256] or NULL).  knnx_pqb_seed_from_sample: entry mj[i] = m * 256 + j
+ * := residual sub-vector m of sample row sample_rows[i] (initial codebooks, re-seeding).  _set_sample_device borrows the rows. */
+typedef struct knnx_pq_builder knnx_pq_builder;
+int knnx_pqb_create(int device, int d, int M, knnx_pq_builder** out);
+void knnx_pqb_destroy(knnx_pq_builder* b);
+int knnx_pqb_set_sample(knnx_pq_builder* b, const uint16_t* rows_f16, const int32_t* lists, int64_t n, const uint16_t* centroids_f16,
+                        int nlist);
+int knnx_pqb_set_sample_device(knnx_pq_builder* b, const void* rows_dev_f16, const int32_t* lists_dev, int64_t n,
+                               const uint16_t* centroids_f16, int nlist);
+int knnx_pqb_seed_from_sample(knnx_pq_builder* b, const int32_t* mj, const int64_t* sample_rows, int64_t n);
+int knnx_pqb_set_codebooks(knnx_pq_builder* b, const float* codebooks);
+int knnx_pqb_get_codebooks(knnx_pq_builder* b, float* codebooks);
+int knnx_pqb_lloyd(knnx_pq_builder* b, uint8_t* codes_out, int64_t* sizes_out);
+
 /* Merge P per-shard results ([P, n, k] each, already global ids) into the top-k [n, k];
  * the step after the RCCL all-gather of a row-sharded index.  Device buffers.  k <= 64: any order within a list;
  * k > 64: every list sorted as knnx_search returns it (score descending, -1 padding at the tail), P <= 64. */

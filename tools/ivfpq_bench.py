@@ -1,0 +1,131 @@
+"""IVF-PQ benchmark on one MI355X: build (train / assign / encode) over the synthetic mixture corpus generated on the device
+(knnx_synth_rows_device kind 1, BASELINE config 5), HBM bytes per row, QPS at B x nprobe, the ADC scan's kernel time against the
+byte model, recall@40 against the exact top-40 streamed over the same corpus, and an IVF-Flat A/B in the same process (--flat-ab,
+at a size where both fit).  Prints ONE JSON line.
+
+  python tools/ivfpq_bench.py                                   # config 5's shard: 125 M x 1024, nlist 65 536, M = 64
+  python tools/ivfpq_bench.py --rows 1000000000 --d 768         # the headline index on one GPU
+  python tools/ivfpq_bench.py --rows 16000000 --nlist 16384 --flat-ab
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=125_000_000)
+    ap.add_argument("--d", type=int, default=1024)
+    ap.add_argument("--nlist", type=int, default=65536)
+    ap.add_argument("--M", type=int, default=64)
+    ap.add_argument("--clusters", type=int, default=4096)
+    ap.add_argument("--seed", type=int, default=5)
+    ap.add_argument("--batches", default="1,32,256")
+    ap.add_argument("--nprobes", default="16,64,256")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--recall-queries", type=int, default=64)
+    ap.add_argument("--flat-ab", action="store_true")
+    a = ap.parse_args()
+
+    import torch
+
+    from clip_retrieval_amd.knn import Mi355xIndex, build_ivf_index_device, build_ivfpq_index_device, synth_rows_device
+
+    n, d = a.rows, a.d
+
+    def fill_rows(dst, row0, count, stride):
+        synth_rows_device(dst, row0, count, d, a.seed, kind=1, n_clusters=a.clusters, row_stride=stride)
+
+    free0 = torch.cuda.mem_get_info()[0]
+    index, st = build_ivfpq_index_device(fill_rows, n, d, a.nlist, a.M, nprobe=16, niter=6, pq_niter=8, seed=0)
+    torch.cuda.synchronize()
+    used = free0 - torch.cuda.mem_get_info()[0]
+    out = {"rows": n, "d": d, "nlist": a.nlist, "M": a.M, "train_s": round(st["train_s"], 2), "assign_s": round(st["assign_s"], 2),
+           "encode_s": round(st["encode_s"], 2), "bytes_per_row_model": a.M + 12, "hbm_bytes_index": int(used),
+           "hbm_bytes_per_row": round(used / n, 2)}
+
+    # queries: corpus rows (a different seed region) perturbed -- the mixture's own distribution
+    rng = np.random.default_rng(1)
+    qrows = torch.empty((256, d), dtype=torch.float16, device="cuda")
+    synth_rows_device(qrows.data_ptr(), n + 12345, 256, d, a.seed, kind=1, n_clusters=a.clusters)
+    q = qrows.float().cpu().numpy()
+    q += 0.05 * rng.standard_normal(q.shape).astype(np.float32) / np.sqrt(d)
+    q /= np.linalg.norm(q, axis=1, keepdims=True)
+    q = np.ascontiguousarray(q, dtype=np.float32)
+    qd = torch.from_numpy(q).cuda()
+    Dd = torch.empty((256, 64), dtype=torch.float32, device="cuda")
+    Id = torch.empty((256, 64), dtype=torch.int64, device="cuda")
+
+    def timed(ix, B, k=40):
+        ix.search_device(qd.data_ptr(), B, k, Dd.data_ptr(), Id.data_ptr())
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            ix.search_device(qd.data_ptr(), B, k, Dd.data_ptr(), Id.data_ptr())
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+        return float(np.median(ts))
+
+    grid = {}
+    for npb in [int(v) for v in a.nprobes.split(",")]:
+        index.nprobe = npb
+        for B in [int(v) for v in a.batches.split(",")]:
+            t = timed(index, B)
+            index.profile(True)
+            index.search_device(qd.data_ptr(), B, 40, Dd.data_ptr(), Id.data_ptr())
+            torch.cuda.synchronize()
+            _, scan_ms = index.profile_get()
+            index.profile(False)
+            code_bytes = B * npb * (n / a.nlist) * a.M  # byte model: every probed list's codes once per query
+            grid[f"B{B}_np{npb}"] = {"ms": round(t * 1e3, 3), "qps": round(B / t, 1), "adc_scan_ms": round(scan_ms, 3),
+                                     "code_bytes_model": int(code_bytes), "code_TBps_model": round(code_bytes / (scan_ms * 1e-3) / 1e12, 2) if scan_ms else None}
+    out["search"] = grid
+
+    # recall@40 at nprobe 64 against the exact top-40, streamed over the corpus in chunks (flat scans of device-generated rows)
+    nr, k = a.recall_queries, 40
+    index.nprobe = 64
+    _, I_pq = index.search(q[:nr], k)
+    chunk = 1 << 23
+    buf = torch.empty((min(chunk, n), d), dtype=torch.float16, device="cuda")
+    best_D = np.full((nr, k), -np.inf, np.float32)
+    best_I = np.full((nr, k), -1, np.int64)
+    for o in range(0, n, chunk):
+        m = min(chunk, n - o)
+        synth_rows_device(buf.data_ptr(), o, m, d, a.seed, kind=1, n_clusters=a.clusters)
+        torch.cuda.synchronize()
+        f = Mi355xIndex(d, id_base=o)
+        f.attach_device_rows(buf.data_ptr(), m)
+        D, I = f.search(q[:nr], k)
+        f.close()
+        allD, allI = np.concatenate([best_D, D], 1), np.concatenate([best_I, I], 1)
+        sel = np.argsort(-allD, axis=1, kind="stable")[:, :k]
+        best_D, best_I = np.take_along_axis(allD, sel, 1), np.take_along_axis(allI, sel, 1)
+    del buf
+    out["recall40_np64"] = round(float(np.mean([len(set(x) & set(y)) / k for x, y in zip(I_pq, best_I)])), 4)
+
+    if a.flat_ab:
+        index.close()
+        torch.cuda.empty_cache()
+        flat, _ = build_ivf_index_device(fill_rows, n, d, a.nlist, nprobe=64, seed=0)  # same k-means seed: the same coarse centroids
+        flat.nprobe = 64
+        _, I_f = flat.search(q[:nr], k)
+        ab = {"recall40_np64": round(float(np.mean([len(set(x) & set(y)) / k for x, y in zip(I_f, best_I)])), 4)}
+        for B in (1, 256):
+            t = timed(flat, B)
+            ab[f"B{B}_np64_ms"] = round(t * 1e3, 3)
+        out["ivf_flat_ab"] = ab
+        flat.close()
+    else:
+        index.close()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

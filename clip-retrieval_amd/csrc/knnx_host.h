@@ -1,0 +1,548 @@
+// knnx_host.h -- shared by the HOST translation units of the search half (knnx_api / knnx_range / knnx_ivf / knnx_ivfpq /
+// knnx_sharded .hip): the error helpers, the owners of device memory, pinned memory, streams and events, the index object
+// with its state grouped by the scan that uses it, and the handful of functions one file calls in another.  The kernel
+// files include knn_kernels.h only.
+//
+// Allocation rule: every group has ONE alloc() that leaves the whole group allocated or leaves it EMPTY and returns the
+// hipError_t; the caller turns that into its error code or its fallback.  Nothing is freed by hand: a group is emptied by
+// assigning a fresh one, the index by `delete`.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <float.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+#include <algorithm>
+#include <condition_variable>
+#include <deque>
+#include <mutex>
+#include <string>
+#include <type_traits>
+#include <utility>
+#include <vector>
+
+#include "../../include/knnx.h"
+#include "knn_kernels.h"
+
+using namespace knnx;  // (the launchers and constants of knn_kernels.h)
+
+#pragma GCC visibility push(hidden)  // nothing below is part of the library's ABI
+
+inline thread_local std::string g_err;  // knnx_last_error()
+inline int fail(int code, const std::string& msg) {
+  g_err = msg;
+  return code;
+}
+#define HIPCHK(expr)                                                                              \
+  do {                                                                                            \
+    hipError_t _e = (expr);                                                                       \
+    if (_e != hipSuccess)                                                                         \
+      return fail(_e == hipErrorOutOfMemory ? KNNX_E_NOMEM : KNNX_E_HIP,                         \
+                  std::string(#expr) + ": " + hipGetErrorString(_e));                             \
+  } while (0)
+
+// ---- owners -------------------------------------------------------------------------------------
+// One device allocation of n T (bytes for T = void).  Move-only; converts to T* so that it is passed to launchers and
+// copies like the pointer it holds.  borrow() points it at memory somebody else owns (attached rows, a device-resident
+// training sample): reset() and the destructor then leave that memory alone.
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  bool borrowed = false;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), borrowed(o.borrowed) { o.p = nullptr, o.borrowed = false; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) {
+      reset();
+      std::swap(p, o.p);
+      std::swap(borrowed, o.borrowed);
+    }
+    return *this;
+  }
+  ~DevBuf() { reset(); }
+  hipError_t alloc(size_t n) {
+    reset();
+    hipError_t e = hipMalloc((void**)&p, n * sizeof(std::conditional_t<std::is_void<T>::value, char, T>));
+    if (e != hipSuccess) p = nullptr;
+    return e;
+  }
+  void borrow(const void* q) {
+    reset();
+    p = (T*)q;
+    borrowed = true;
+  }
+  void reset() {
+    if (p && !borrowed) (void)hipFree(p);
+    p = nullptr;
+    borrowed = false;
+  }
+  operator T*() const { return p; }
+};
+// `e` carries the first failure of a chain of allocations; the ones after it are skipped
+template <class T>
+inline void dev_alloc(hipError_t& e, DevBuf<T>& b, size_t n) {
+  if (e == hipSuccess) e = b.alloc(n);
+}
+
+// grow-only pinned staging buffer
+struct PinBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+  PinBuf() = default;
+  PinBuf(const PinBuf&) = delete;
+  PinBuf& operator=(const PinBuf&) = delete;
+  ~PinBuf() { reset(); }
+  hipError_t ensure(size_t want) {
+    if (bytes >= want) return hipSuccess;
+    reset();
+    hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
+    if (e != hipSuccess) p = nullptr;
+    else bytes = want;
+    return e;
+  }
+  void reset() {
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    bytes = 0;
+  }
+  operator void*() const { return p; }
+};
+
+struct Stream {
+  hipStream_t s = nullptr;
+  Stream() = default;
+  Stream(const Stream&) = delete;
+  Stream& operator=(const Stream&) = delete;
+  Stream(Stream&& o) noexcept : s(o.s) { o.s = nullptr; }
+  Stream& operator=(Stream&& o) noexcept {
+    std::swap(s, o.s);
+    return *this;
+  }
+  ~Stream() {
+    if (s) (void)hipStreamDestroy(s);
+  }
+  hipError_t create() { return hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+  operator hipStream_t() const { return s; }
+};
+
+struct Event {
+  hipEvent_t e = nullptr;
+  Event() = default;
+  Event(const Event&) = delete;
+  Event& operator=(const Event&) = delete;
+  Event(Event&& o) noexcept : e(o.e) { o.e = nullptr; }
+  Event& operator=(Event&& o) noexcept {
+    std::swap(e, o.e);
+    return *this;
+  }
+  ~Event() {
+    if (e) (void)hipEventDestroy(e);
+  }
+  hipError_t create(unsigned flags = hipEventDefault) { return hipEventCreateWithFlags(&e, flags); }
+  operator hipEvent_t() const { return e; }
+};
+
+// ---- the index: state grouped by the scan that uses it --------------------------------------------
+constexpr int IVFM_BLK = 8;                       // 32-query blocks of one multi-block IVF pass (knnx_ivf.hip)
+constexpr int PQ_PASS = IVFM_BLK * KNN_NQ;        // queries of one IVF-PQ pass (knnx_ivfpq.hip)
+constexpr int PQ_TARGET_WG = 1024;                // ADC workgroups a pass aims for (a query's lists are split over ceil(1024 / nq))
+constexpr int PQ_MAX_SPLIT = 128;                 // ... at most (the merge holds split x k scores of a query in the LDS)
+constexpr int PQ_SLOTS = PQ_TARGET_WG + PQ_PASS;  // >= nq * split
+constexpr int64_t IVFB_CHUNK = (int64_t)1 << 20;  // rows per streamed chunk of the IVF builds
+
+// per-scan scratch of the exact 32-query scan, created with the index (sized for KNN_NQ_MAX queries, grid = n_cu workgroups,
+// k <= KNNX_MAX_K_FAST)
+struct FlatScratch {
+  DevBuf<_Float16> qfrag;
+  DevBuf<float> q_dev;  // [KNN_RQ_MAX, d]
+  DevBuf<int> thr_g;
+  DevBuf<float> part_s;
+  DevBuf<uint32_t> part_i;
+  DevBuf<int> part_n;
+  DevBuf<float> D_dev;    // [KNN_RQ_MAX, KNNX_MAX_K_FAST]
+  DevBuf<int64_t> I_dev;  // [KNN_RQ_MAX, KNNX_MAX_K_FAST]
+  DevBuf<unsigned> range_cnt;  // [KNN_NQ] hit counters of a range scan
+  DevBuf<int> maxnorm;    // largest row norm (order-encoded)
+  DevBuf<unsigned long long> stats;  // device counters: [0] queries served by a proof-based path, [1] proofs that failed
+  hipError_t alloc(int d, size_t G) {
+    hipError_t e = hipSuccess;
+    dev_alloc(e, qfrag, (size_t)d * 64);
+    dev_alloc(e, q_dev, (size_t)KNN_RQ_MAX * d);
+    dev_alloc(e, thr_g, KNN_NQ_MAX);
+    dev_alloc(e, part_s, G * KNN_NQ_MAX * KNNX_MAX_K_FAST);
+    dev_alloc(e, part_i, G * KNN_NQ_MAX * KNNX_MAX_K_FAST);
+    dev_alloc(e, part_n, G * KNN_NQ_MAX);
+    dev_alloc(e, D_dev, (size_t)KNN_RQ_MAX * KNNX_MAX_K_FAST);
+    dev_alloc(e, I_dev, (size_t)KNN_RQ_MAX * KNNX_MAX_K_FAST);
+    dev_alloc(e, range_cnt, KNN_NQ);
+    dev_alloc(e, maxnorm, 1);
+    if (e == hipSuccess) e = hipMemset(maxnorm, 0, sizeof(int));  // order-encoded +0.0f
+    dev_alloc(e, stats, 2);
+    if (e == hipSuccess) e = hipMemset(stats, 0, 2 * sizeof(unsigned long long));
+    if (e != hipSuccess) *this = FlatScratch();
+    return e;
+  }
+};
+
+// wide scan (64 queries per pass): candidates, fallback results, proof flags; created with the index.
+// Unproven queries of the proof-based scans (wide / RQ / int8) get the exact 32-query scan of their group.  On the device-buffer
+// entry point that scan is launched for every group, gated on the device (no host round trip); the host-buffer entry points
+// (search_fast_locked) read the gates back with the results instead and launch it only for a group that needs it -- 4 gated
+// no-op kernels per group, 32 per 256-query batch, ~0.16 ms of launch slots (profiles/r06r_knn_b256_timeline.log).
+struct WideScratch {
+  DevBuf<int64_t> cand;   // [64, 64]
+  DevBuf<float> approx;   // [64, 64]
+  DevBuf<unsigned> need;  // [64]
+  DevBuf<unsigned> gate;  // [2]
+  DevBuf<float> Dfb;      // [32, 64]
+  DevBuf<int64_t> Ifb;
+  hipError_t alloc() {
+    hipError_t e = hipSuccess;
+    dev_alloc(e, cand, (size_t)KNN_NQ_MAX * KNN_WIDE_KW);
+    dev_alloc(e, approx, (size_t)KNN_NQ_MAX * KNN_WIDE_KW);
+    dev_alloc(e, need, KNN_NQ_MAX);
+    dev_alloc(e, gate, 2);
+    dev_alloc(e, Dfb, (size_t)KNN_NQ * KNNX_MAX_K_FAST);
+    dev_alloc(e, Ifb, (size_t)KNN_NQ * KNNX_MAX_K_FAST);
+    if (e != hipSuccess) *this = WideScratch();
+    return e;
+  }
+};
+
+// RQ scan (register-stationary queries, up to 256 per pass; knn_rq_kernels.hip): allocated on first use
+struct RqScratch {
+  DevBuf<_Float16> qfrag;  // [8 blocks][d/16][64][8]
+  DevBuf<float> thr;       // [256]
+  DevBuf<unsigned> cnt, lost, need, gate;  // [256] x3, [8]
+  DevBuf<int> cntc;        // [256]
+  DevBuf<float> hit_s;     // [256, KNN_RQ_CAP]
+  DevBuf<uint32_t> hit_r;
+  DevBuf<float> samp;      // [256, 64] sample scores
+  DevBuf<int64_t> samp_i;
+  DevBuf<_Float16> m_qfrag;  // fragment images of the sample scans of one batch, side by side (blocks of one launch)
+  DevBuf<int> m_thr;       // [256] their global thresholds
+  hipError_t alloc(int d) {
+    if (qfrag) return hipSuccess;
+    const size_t Q = KNN_RQ_MAX;
+    hipError_t e = hipSuccess;
+    dev_alloc(e, qfrag, (size_t)(Q / 32) * (d / 16) * 64 * 8);
+    dev_alloc(e, thr, Q);
+    dev_alloc(e, cnt, Q);
+    dev_alloc(e, lost, Q);
+    dev_alloc(e, need, Q);
+    dev_alloc(e, gate, 8);
+    dev_alloc(e, cntc, Q);
+    dev_alloc(e, hit_s, Q * KNN_RQ_CAP);
+    dev_alloc(e, hit_r, Q * KNN_RQ_CAP);
+    dev_alloc(e, samp, Q * KNN_WIDE_KW);
+    dev_alloc(e, samp_i, Q * KNN_WIDE_KW);
+    dev_alloc(e, m_qfrag, (Q / KNN_NQ) * (size_t)d * 64);
+    dev_alloc(e, m_thr, Q);
+    if (e != hipSuccess) *this = RqScratch();
+    return e;
+  }
+};
+
+// int8 first stage of the flat scans (knn_rq_kernels.hip): the copy of the rows, allocated and built on first use, rebuilt after
+// the rows change.  The image may be PARTIAL (KNNX_I8_MAX_BYTES, or what fits next to the fp16 rows): the other rows are scanned in fp16.
+struct I8Copy {
+  bool valid = false;          // rows / i8q.colscale / i8q.ab describe the current rows
+  int64_t cap_rows = 0;
+  int64_t nrows = 0;           // rows [0, nrows) are quantised with the current column scales (add() appends: only the new rows are done)
+  int64_t scale_rows = 0;      // rows the column scales were taken over (a full rebuild once the index has doubled since)
+  int planes = 1;              // int8 planes of a query: 2 when the column scales differ widely (decided at every full build)
+  I8Dom dom;                   // dominant columns of the index (knn_kernels.h), decided with the planes
+  DevBuf<int8_t> rows;         // tile-ordered image of rows [0, nrows) (knn_i8_quant_kernel): cap_rows / 32 tiles of 32 d bytes
+  unsigned long long served = 0;       // queries answered through the int8 path (knnx_i8_active reports it)
+  unsigned long long rest_served = 0;  // queries whose pass ran over an int8 part AND an fp16 rest
+  // give the image back (it is an accelerator, not data: see malloc_or_reclaim)
+  void release() {
+    rows.reset();
+    cap_rows = 0;
+    nrows = 0;
+    valid = false;
+  }
+};
+// column statistics of the int8 copy and the query scratch of its pass: allocated on first use
+struct I8Scratch {
+  DevBuf<float> colscale;      // [d]
+  DevBuf<int> colmax, ab;      // [d] (encoded), [2] (encoded A, B)
+  DevBuf<int8_t> qdom;         // [2][256][4] the queries' 14-bit digits at the dominant positions (knn_i8_prep_kernel)
+  DevBuf<int8_t> qfrag;        // [16 blocks][d / 64][64][16]
+  DevBuf<int> thr;             // [256]
+  DevBuf<float> lb;            // [256]
+  DevBuf<float> hit_s;         // [256, KNN_I8_CAP]
+  DevBuf<uint32_t> hit_r;
+  hipError_t alloc(int d) {
+    if (colscale) return hipSuccess;
+    const size_t Q = KNN_RQ_MAX;
+    hipError_t e = hipSuccess;
+    dev_alloc(e, colscale, d);
+    dev_alloc(e, colmax, d);
+    dev_alloc(e, ab, 2);
+    dev_alloc(e, qfrag, 2 * Q * d);
+    dev_alloc(e, qdom, 2 * Q * 4);
+    dev_alloc(e, thr, Q);
+    dev_alloc(e, lb, Q);
+    dev_alloc(e, hit_s, Q * KNN_I8_CAP);
+    dev_alloc(e, hit_r, Q * KNN_I8_CAP);
+    if (e != hipSuccess) *this = I8Scratch();
+    return e;
+  }
+};
+
+// IVF layout (ivf_layout_alloc, knnx_ivf.hip): rows -- or PQ codes -- live list-sorted and tile-padded in the arena; see knn_kernels.hip
+struct IvfLayout {
+  DevBuf<unsigned> tile0, ntile, size;  // [nlist] first tile, tiles, rows of a list
+  DevBuf<int64_t> idmap;   // padded arena row -> id (-1 on pad rows)
+  DevBuf<uint32_t> inv;    // id - id_base -> padded arena row
+};
+// single-block IVF scan (ivf_build_worklist): the work list of <= 32 queries; allocated with the layout
+struct IvfScratch {
+  DevBuf<unsigned> masks, off, nwork;  // [nlist] query mask of a list; off: unused since the atomic work list; [1] tiles in `work`
+  DevBuf<uint4> work;      // [tiles of the arena]
+  DevBuf<int64_t> Ic;      // [KNN_NQ, KNNX_MAX_K_FAST] coarse result
+  DevBuf<float> Dc;
+  DevBuf<float> scores;    // [KNN_NQ, nlist] coarse scores (nprobe > 64 only; allocated on first use)
+};
+// multi-block pass (scan_topk_ivf_multi): up to IVFM_BLK blocks of 32 queries in ONE coarse scan + ONE list scan; allocated on
+// first use
+struct IvfMultiScratch {
+  DevBuf<_Float16> qfrag;      // [IVFM_BLK][d * 64] fragment images
+  DevBuf<int> thr_c, thr_f;    // [32 IVFM_BLK] thresholds of the coarse / the list scan
+  DevBuf<unsigned> nwork;      // 16 counters (8: union tiles) + masks [IVFM_BLK][nlist] behind them: one memset clears both
+                               // (knn_kernels.hip launch_ivf_worklist*)
+  unsigned* masks = nullptr;   // = nwork + 16 (not an allocation of its own)
+  DevBuf<unsigned> off;        // unused since the atomic work list
+  DevBuf<uint4> work;          // [IVFM_BLK][stride]
+  unsigned stride = 0;
+  DevBuf<float> scores;        // [32 IVFM_BLK, nlist] coarse scores of one pass
+  hipError_t alloc(int d, size_t nl, int64_t capacity) {
+    if (qfrag) return hipSuccess;
+    const size_t tiles = (size_t)std::max<int64_t>(capacity / 32, 1);
+    hipError_t e = hipSuccess;
+    dev_alloc(e, qfrag, (size_t)IVFM_BLK * d * 64);
+    dev_alloc(e, thr_c, (size_t)IVFM_BLK * 32);
+    dev_alloc(e, thr_f, (size_t)IVFM_BLK * 32);
+    dev_alloc(e, nwork, (size_t)IVFM_BLK * nl + 16);
+    dev_alloc(e, off, (size_t)IVFM_BLK * nl);
+    dev_alloc(e, work, (size_t)IVFM_BLK * tiles);
+    dev_alloc(e, scores, (size_t)IVFM_BLK * 32 * nl);
+    if (e != hipSuccess) {
+      *this = IvfMultiScratch();
+      return e;
+    }
+    masks = nwork + 16;
+    stride = (unsigned)tiles;
+    return e;
+  }
+};
+
+// streaming build (knnx_ivf_begin .. knnx_ivf_end)
+struct IvfBuild {
+  int nlist = 0;
+  int64_t total = 0, added = 0;
+  std::vector<uint16_t> cent;
+  // device staging of one chunk
+  DevBuf<_Float16> rows;  // [IVFB_CHUNK, d] (knnx_ivfpq_add_codes stages its code bytes here: M <= 2 d)
+  DevBuf<int64_t> ids;
+  DevBuf<int32_t> lists, pos;
+  // host mirror of the layout, so that every (list, position) a caller hands over is checked before it is scattered
+  // (a position past its list, or used twice, would silently overwrite a neighbouring list's rows)
+  std::vector<uint32_t> size, fill, tile0;
+  std::vector<uint64_t> taken;  // one bit per padded arena row
+};
+
+// IVF-PQ (knnx_ivfpq_set_quantizer before knnx_ivf_begin; knn_pq_kernels.hip): the arena holds M code bytes per row, list-sorted
+// and tile-padded like the IVF-Flat rows (`rows` stays null); the coarse quantiser is the IVF one
+struct PqData {
+  int m = 0;
+  DevBuf<float> cb;                      // [M][256][d / M]
+  DevBuf<uint8_t> codes;                 // [capacity][M]
+  DevBuf<_Float16> bcent;                // centroids during the build (knnx_ivf_begin .. knnx_ivf_end)
+  std::vector<unsigned> tile0_h, size_h; // host copy of the layout (knnx_ivfpq_get_codes)
+};
+// one IVF-PQ search pass of up to PQ_PASS queries, allocated on first use
+struct PqScratch {
+  DevBuf<_Float16> qfrag;
+  DevBuf<int> thr;          // [2][256] thresholds reset by the query prep (the coarse dump does not use them)
+  DevBuf<float> scores;     // [256][nlist] coarse scores
+  DevBuf<unsigned> masks;   // [8][nlist]
+  DevBuf<unsigned> pcnt;    // [256]
+  DevBuf<int> probe;        // [256][np_cap] probed lists
+  DevBuf<float> pscore;     // [256][np_cap] their coarse scores
+  int np_cap = 0;
+  DevBuf<float> lut;        // [256][M][256]
+  DevBuf<float> part_s;     // [PQ_SLOTS][64] per-workgroup top-k of the ADC scan
+  DevBuf<uint32_t> part_i;
+  DevBuf<int> part_n;       // [PQ_SLOTS]
+  // (a larger nprobe than any before regrows probe / pscore only)
+  hipError_t alloc(int d, size_t nl, int m, int np) {
+    if (qfrag && np <= np_cap) return hipSuccess;
+    hipError_t e = hipSuccess;
+    if (!qfrag) {
+      dev_alloc(e, qfrag, (size_t)IVFM_BLK * d * 64);
+      dev_alloc(e, thr, 2 * PQ_PASS);
+      dev_alloc(e, scores, PQ_PASS * nl);
+      dev_alloc(e, masks, IVFM_BLK * nl);
+      dev_alloc(e, pcnt, PQ_PASS);
+      dev_alloc(e, lut, (size_t)PQ_PASS * m * 256);
+      dev_alloc(e, part_s, (size_t)PQ_SLOTS * KNNX_MAX_K_FAST);
+      dev_alloc(e, part_i, (size_t)PQ_SLOTS * KNNX_MAX_K_FAST);
+      dev_alloc(e, part_n, PQ_SLOTS);
+    }
+    dev_alloc(e, probe, (size_t)PQ_PASS * np);
+    dev_alloc(e, pscore, (size_t)PQ_PASS * np);
+    if (e != hipSuccess) *this = PqScratch();
+    else np_cap = np;
+    return e;
+  }
+};
+
+// hit pools of the range scans, grown on demand (knnx_range.hip: range_pool_alloc)
+struct RangePools {
+  DevBuf<float> s;
+  DevBuf<uint32_t> i;
+  size_t pool = 0;  // entries in s / i, shared by the queries of one scan
+};
+
+// scan timing (knnx_profile_enable / knnx_profile_get): an event pair around every main scan launch while `on`
+struct Profile {
+  bool on = false;
+  std::vector<std::pair<Event, Event>> events;  // recorded pairs, collected by knnx_profile_get
+  std::pair<Event, Event> open;                 // between begin() and end()
+  // begin() before the launch, end() after it; both do nothing unless `timed`
+  hipError_t begin(bool timed, hipStream_t st) {
+    if (!timed) return hipSuccess;
+    open = std::pair<Event, Event>();
+    hipError_t e = open.first.create();
+    if (e == hipSuccess) e = open.second.create();
+    if (e == hipSuccess) e = hipEventRecord(open.first, st);
+    return e;
+  }
+  hipError_t end(bool timed, hipStream_t st) {
+    if (!timed) return hipSuccess;
+    hipError_t e = hipEventRecord(open.second, st);
+    if (e == hipSuccess) events.push_back(std::move(open));
+    return e;
+  }
+};
+
+// Request coalescer ("knnx_search is re-entrant; internally a batching queue"): concurrent single-query callers
+// (the werkzeug request threads of clip_back.py:1018) queue here; one of them -- the leader -- serves everything that queued
+// while the GPU was busy, up to one scan's worth with the same k, in ONE pass over HBM, then hands the lead on.
+struct Coalescer {
+  bool on = true;
+  std::mutex mu;
+  std::condition_variable cv;
+  std::deque<struct CoReq*> q;
+  bool leader = false;
+  int64_t batches = 0, queries = 0, largest = 0;
+  std::vector<float> qbuf, Dbuf;
+  std::vector<int64_t> Ibuf;
+};
+
+struct knnx_index {
+  int device = 0;
+  int d = 0;
+  int n_cu = 256;
+  int64_t ntotal = 0;
+  int64_t capacity = 0;
+  int64_t id_base = 0;
+  Stream stream;           // (first: destroyed after everything that may still be queued on it has been freed)
+  DevBuf<_Float16> rows;   // [capacity, d]; borrowed after knnx_attach_device_f16
+  std::mutex mu;
+
+  // switches, read from the environment once (knnx_create)
+  int nt_loads = 0;        // KNNX_NT=1
+  int wide_ok = 1;         // KNNX_WIDE=0 disables
+  int rq_ok = 1;           // KNNX_RQ=0 disables
+  int64_t rq_min_rows = KNN_RQ_MIN_ROWS;  // KNNX_RQ_MIN_ROWS overrides (tests run the RQ path on small indexes)
+  int rq_sample_grid = 0;  // workgroups of the threshold-sample scans (0: chosen from the sample size; KNNX_RQ_SAMPLE_GRID overrides)
+  int i8_env_ok = 1;       // KNNX_I8=0 disables
+  int i8_ok = 1;           // = i8_env_ok until the copy's memory cannot be had (knnx_reset tries again)
+  int i8_planes_env = 0;   // KNNX_I8_PLANES=1|2 forces the choice (and switches the dominant-column form off)
+  int i8_dom_off = 0;      // KNNX_I8_DOM=0: never use the dominant-column form (two planes instead)
+  int64_t i8_budget = 0;   // KNNX_I8_MAX_BYTES: cap on the int8 image (0: none)
+  int ivfm_ok = 1;         // KNNX_IVF_MULTI=0, or an allocation failed: the 32-queries-per-pass IVF path
+
+  FlatScratch flat;
+  WideScratch wide;
+  RqScratch rq;
+  I8Copy i8;
+  I8Scratch i8q;
+  RangePools range;
+  Profile prof;
+  Coalescer co;
+
+  // pinned staging for host<->device hand-over
+  PinBuf pin;
+  // device scratch of reconstruct / range_fetch, kept between calls (hipMalloc + hipFree per request cost more than a
+  // small search: hipFree synchronises the device); grown on demand, released with the index.  Used under mu only.
+  struct Slot {
+    DevBuf<void> p;
+    size_t bytes = 0;
+  } scratch[9];
+
+  // IVF-Flat / IVF-PQ state
+  int ivf_nlist = 0, ivf_nprobe = 1;
+  knnx_index* cent = nullptr;  // coarse quantiser: a flat index over the fp16 centroids
+  IvfLayout ivf;
+  IvfScratch ivf1;
+  IvfMultiScratch ivfm;
+  int ivfm_last_blk = 0;          // blocks of the most recent IVF scan (0: the single-block path) -- knnx_ivf_last_scan_tiles
+  bool ivfm_union_valid = false;  // the most recent pass also counted the union of its lists (profiling was on)
+  IvfBuild ivfb;
+  PqData pq;
+  PqScratch pqs;
+
+  // a proof-based scan that skipped its fallback (see WideScratch) says so here: 1 = rq.need / rq.gate, 2 = wide.need / wide.gate
+  bool defer_fb = false;
+  int defer_kind = 0, defer_nq = 0;
+
+  // scratch hand-over between streams: the per-handle scratch above is shared by every call, so each launch sequence
+  // first waits for the event the previous sequence recorded, whichever stream that ran on
+  Event ev_scratch;
+  bool ev_valid = false;
+};
+
+// ---- what one host file calls in another ---------------------------------------------------------
+// knnx_api.hip
+int set_dev(const knnx_index* ix);
+int ensure_pin(knnx_index* ix, size_t bytes);
+int ensure_scratch(knnx_index* ix, int slot, size_t bytes, void** out);
+int scratch_acquire(knnx_index* ix, hipStream_t st);
+int scratch_release(knnx_index* ix, hipStream_t st);
+int scan_cap(int d, int k);
+int scan_topk(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out, int64_t* I_out, hipStream_t st,
+              const unsigned* gate = nullptr);
+int search_fast_locked(knnx_index* ix, const float* q, int n, int k, float* D, int64_t* I);
+// knnx_range.hip
+int search_large_k_locked(knnx_index* ix, const float* q, int n, int k, float* D, int64_t* I);
+// knnx_ivf.hip
+int ivf_build_worklist(knnx_index* ix, const float* q_dev, int nq, hipStream_t st, const unsigned* gate);
+bool ivfm_usable(const knnx_index* ix, int nq, int k);
+int ivfm_alloc(knnx_index* ix);
+int scan_topk_ivf_multi(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out, int64_t* I_out, hipStream_t st);
+bool ivfb_claim_all(knnx_index* ix, const int32_t* lists, const int32_t* pos, int64_t n);
+// knnx_ivfpq.hip
+int scan_topk_pq(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out, int64_t* I_out, hipStream_t st);
+
+// the int8 copy is an accelerator, not data: whoever needs device memory and cannot get it takes the copy's back and tries once more
+// (the lazily built copy must not starve the range pools / large-k scratch that fitted before it existed)
+template <class T>
+inline hipError_t malloc_or_reclaim(knnx_index* ix, DevBuf<T>& b, size_t n) {
+  hipError_t e = b.alloc(n);
+  if (e != hipSuccess && ix->i8.rows) {
+    (void)hipGetLastError();
+    ix->i8.release();
+    ix->i8_ok = 0;  // it did not fit next to what the index needs: do not rebuild it on the next search
+    e = b.alloc(n);
+  }
+  return e;
+}
+
+#pragma GCC visibility pop

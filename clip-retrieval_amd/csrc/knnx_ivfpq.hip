@@ -1,0 +1,289 @@
+// knnx_ivfpq.hip -- IVF-PQ on the host side: the search pass, the quantiser and code entry points, codebook training
+// (knnx_pqb_*) (see knnx_host.h; kernels in knn_pq_kernels.hip).
+
+#include "knnx_host.h"
+
+// ---------------------------------------------------------------------------------------------
+// IVF-PQ pass of 1 .. 256 queries already in HBM (csrc/knn_pq_kernels.hip): the coarse quantiser of the multi-block IVF pass
+// (one score dump over the centroids + the radix select of ivf_select_mark_kernel: the nprobe largest <q, c>, ties to the lower
+// list id), the probed lists of every query, its lookup table, the ADC list scan, the merge of the per-workgroup lists.
+// ---------------------------------------------------------------------------------------------
+int scan_topk_pq(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out, int64_t* I_out, hipStream_t st) {
+  if (nq < 1 || nq > PQ_PASS || k < 1 || k > KNNX_MAX_K_FAST || !ix->cent || !ix->ivf_nlist)
+    return fail(KNNX_E_STATE, "internal: IVF-PQ pass misuse");
+  const int np = std::min(ix->ivf_nprobe, ix->ivf_nlist);
+  HIPCHK(ix->pqs.alloc(ix->d, (size_t)ix->ivf_nlist, ix->pq.m, np));
+  knnx_index* c = ix->cent;
+  const int nblk = (nq + KNN_NQ - 1) / KNN_NQ;
+  HIPCHK(launch_prep_blocks(q_dev, nq, ix->d, ix->pqs.qfrag, ix->pqs.thr, ix->pqs.thr + PQ_PASS, st));
+  ScanArgs ca{};
+  ca.X = c->rows;
+  ca.N = c->ntotal;
+  ca.d = c->d;
+  ca.qfrag = ix->pqs.qfrag;
+  ca.nq = nq;
+  ca.grid = std::max(1, ix->n_cu / nblk) * nblk;
+  ca.thr_g = ix->pqs.thr;
+  ca.nblk = nblk;
+  ca.k = 1;
+  ca.cap = 2;
+  ca.mode = 2;
+  ca.range_cap = (unsigned)ix->ivf_nlist;
+  ca.range_s = ix->pqs.scores;
+  HIPCHK(launch_scan(ca, st));
+  HIPCHK(launch_ivf_select_mark(ix->pqs.scores, nq, np, ix->ivf_nlist, ix->pqs.masks, st));
+  HIPCHK(launch_pq_probe(ix->pqs.masks, ix->pqs.scores, nq, ix->ivf_nlist, np, ix->pqs.pcnt, ix->pqs.probe, ix->pqs.pscore, st));
+  HIPCHK(launch_pq_lut(q_dev, nq, ix->d, ix->pq.m, ix->pq.cb, ix->pqs.lut, st));
+  const int nsplit = std::max(1, std::min(std::min(np, PQ_MAX_SPLIT), (PQ_TARGET_WG + nq - 1) / nq));
+  HIPCHK(ix->prof.begin(ix->prof.on, st));
+  HIPCHK(launch_pq_adc_scan(ix->pq.codes, ix->pq.m, ix->pqs.lut, ix->pqs.probe, ix->pqs.pscore, ix->pqs.pcnt, np, nsplit, ix->ivf.tile0, ix->ivf.size,
+                            ix->ivf.idmap, k, nq, ix->pqs.part_s, ix->pqs.part_i, ix->pqs.part_n, st));
+  HIPCHK(ix->prof.end(ix->prof.on, st));
+  HIPCHK(launch_merge_u32(ix->pqs.part_s, ix->pqs.part_i, ix->pqs.part_n, nsplit, nq, k, nq, k, ix->id_base, ix->ivf.idmap, D_out, I_out,
+                          nullptr, st));
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// IVF-PQ (faiss IndexIVFPQ(IndexFlatIP(d), d, nlist, M, 8), METRIC_INNER_PRODUCT, by_residual): the index type autofaiss picks
+// for large corpora (the reference's notebook builds OPQ256_768,IVF16384_HNSW32,PQ256x8).  The quantizer is set on an empty
+// index; the IVF build protocol then ENCODES rows into the list-sorted arena; searches go through scan_topk_pq.
+// ---------------------------------------------------------------------------------------------
+extern "C" int knnx_ivfpq_set_quantizer(knnx_index* ix, int M, const float* codebooks) {
+  if (!ix || !codebooks) return fail(KNNX_E_ARG, "bad ivfpq_set_quantizer arguments");
+  if (!pq_supported(ix->d, M)) return fail(KNNX_E_ARG, "IVF-PQ needs M in {16, 32, 64, 128} dividing d (8-bit codes)");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  if (set_dev(ix)) return KNNX_E_HIP;
+  if (ix->rows.borrowed || ix->ntotal != 0 || ix->ivf_nlist || ix->ivfb.nlist || ix->pq.m)
+    return fail(KNNX_E_STATE, "the PQ quantizer is set once, on an empty index, before knnx_ivf_begin");
+  const size_t bytes = (size_t)256 * ix->d * sizeof(float);
+  HIPCHK(ix->pq.cb.alloc((size_t)256 * ix->d));
+  HIPCHK(hipMemcpy(ix->pq.cb, codebooks, bytes, hipMemcpyHostToDevice));
+  ix->pq.m = M;
+  return KNNX_OK;
+}
+
+extern "C" int knnx_ivfpq_m(const knnx_index* ix) { return ix ? ix->pq.m : 0; }
+
+extern "C" int knnx_ivfpq_get_codebooks(knnx_index* ix, float* codebooks) {
+  if (!ix || !codebooks) return fail(KNNX_E_ARG, "bad ivfpq_get_codebooks arguments");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  if (!ix->pq.m) return fail(KNNX_E_STATE, "not an IVF-PQ index");
+  if (set_dev(ix)) return KNNX_E_HIP;
+  HIPCHK(hipMemcpy(codebooks, ix->pq.cb, (size_t)256 * ix->d * sizeof(float), hipMemcpyDeviceToHost));
+  return KNNX_OK;
+}
+
+// every row of a built index in arena order: ids [ntotal], lists [ntotal], codes [ntotal][M]
+extern "C" int knnx_ivfpq_get_codes(knnx_index* ix, int64_t* ids, int32_t* lists, uint8_t* codes) {
+  if (!ix || !ids || !lists || !codes) return fail(KNNX_E_ARG, "bad ivfpq_get_codes arguments");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  if (!ix->pq.m || !ix->ivf_nlist) return fail(KNNX_E_STATE, "not a built IVF-PQ index (knnx_ivf_end first)");
+  if (set_dev(ix)) return KNNX_E_HIP;
+  HIPCHK(hipStreamSynchronize(ix->stream));
+  const int M = ix->pq.m;
+  std::vector<int64_t> idmap((size_t)ix->capacity);
+  std::vector<uint8_t> all((size_t)ix->capacity * M);
+  HIPCHK(hipMemcpy(idmap.data(), ix->ivf.idmap, idmap.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(all.data(), ix->pq.codes, all.size(), hipMemcpyDeviceToHost));
+  int64_t o = 0;
+  for (int l = 0; l < ix->ivf_nlist; ++l) {
+    const size_t r0 = (size_t)ix->pq.tile0_h[l] * 32;
+    for (unsigned i = 0; i < ix->pq.size_h[l]; ++i, ++o) {
+      ids[o] = idmap[r0 + i];
+      lists[o] = l;
+      memcpy(codes + (size_t)o * M, all.data() + (r0 + i) * M, M);
+    }
+  }
+  return o == ix->ntotal ? KNNX_OK : fail(KNNX_E_STATE, "internal: IVF-PQ layout does not add up to ntotal");
+}
+
+// precomputed codes [n][M] (host) into an index between knnx_ivf_begin and knnx_ivf_end: the same (list, position) rules as
+// knnx_ivf_add_assigned; no encoding (an index loaded from its saved codes)
+extern "C" int knnx_ivfpq_add_codes(knnx_index* ix, const uint8_t* codes, int64_t n, const int64_t* ids, const int32_t* lists,
+                                    const int32_t* pos) {
+  if (!ix || (n > 0 && (!codes || !ids || !lists || !pos)) || n < 0) return fail(KNNX_E_ARG, "bad ivfpq_add_codes arguments");
+  if (n == 0) return KNNX_OK;
+  std::lock_guard<std::mutex> lk(ix->mu);
+  if (set_dev(ix)) return KNNX_E_HIP;
+  if (!ix->pq.m || !ix->ivfb.nlist) return fail(KNNX_E_STATE, "set the PQ quantizer and call knnx_ivf_begin first");
+  if (ix->ivfb.added + n > ix->ivfb.total) return fail(KNNX_E_ARG, "more rows than the list sizes announced");
+  for (int64_t i = 0; i < n; ++i)
+    if (ids[i] < ix->id_base || ids[i] - ix->id_base >= ix->ivfb.total) return fail(KNNX_E_ARG, "ids must lie in [id_base, id_base + total rows)");
+  if (!ivfb_claim_all(ix, lists, pos, n)) return KNNX_E_ARG;
+  const int M = ix->pq.m;
+  // (ivfb_rows holds IVFB_CHUNK x d x 2 >= IVFB_CHUNK x M bytes)
+  for (int64_t o = 0; o < n; o += IVFB_CHUNK) {
+    const int64_t m = std::min(IVFB_CHUNK, n - o);
+    HIPCHK(hipMemcpy(ix->ivfb.rows, codes + (size_t)o * M, (size_t)m * M, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ix->ivfb.ids, ids + o, (size_t)m * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ix->ivfb.lists, lists + o, (size_t)m * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ix->ivfb.pos, pos + o, (size_t)m * 4, hipMemcpyHostToDevice));
+    HIPCHK(launch_pq_scatter_codes((const uint8_t*)ix->ivfb.rows.p, m, M, ix->ivfb.lists, ix->ivfb.pos,
+                                   ix->ivfb.ids, ix->ivf.tile0, ix->id_base, ix->ivfb.total, ix->pq.codes, ix->ivf.idmap,
+                                   ix->ivf.inv, ix->stream));
+    HIPCHK(hipStreamSynchronize(ix->stream));
+  }
+  ix->ivfb.added += n;
+  return KNNX_OK;
+}
+
+// ---- codebook training (faiss ProductQuantizer::train on the residuals of a sample; one L2 k-means of 256 per sub-quantiser) ----
+struct knnx_pq_builder {
+  int device = 0, d = 0, M = 0;
+  Stream stream;
+  DevBuf<float> cb;  // [M][256][d / M]
+  // the sample (knnx_pqb_set_sample*): one group, replaced as a whole
+  struct Sample {
+    int nlist = 0;
+    int64_t n = 0;
+    DevBuf<_Float16> X;      // rows [n][d]; borrowed after knnx_pqb_set_sample_device
+    DevBuf<int32_t> lists;   // [n] their lists
+    DevBuf<_Float16> cent;   // [nlist][d]
+    DevBuf<uint8_t> codes;   // [n][M]
+    DevBuf<int32_t> order;   // [M][n]
+    DevBuf<int32_t> off;     // [M][257]
+  } s;
+  std::vector<uint8_t> h_codes;
+  std::vector<int32_t> h_order, h_off;
+};
+
+extern "C" void knnx_pqb_destroy(knnx_pq_builder* b) {
+  if (!b) return;
+  (void)hipSetDevice(b->device);
+  if (b->stream) (void)hipStreamSynchronize(b->stream);
+  delete b;
+}
+
+extern "C" int knnx_pqb_create(int device, int d, int M, knnx_pq_builder** out) {
+  if (!out) return fail(KNNX_E_ARG, "out is null");
+  *out = nullptr;
+  if (!pq_supported(d, M)) return fail(KNNX_E_ARG, "IVF-PQ needs M in {16, 32, 64, 128} dividing d (8-bit codes)");
+  HIPCHK(hipSetDevice(device));
+  knnx_pq_builder* b = new knnx_pq_builder();
+  b->device = device;
+  b->d = d;
+  b->M = M;
+  hipError_t e = b->stream.create();
+  dev_alloc(e, b->cb, (size_t)256 * d);
+  if (e == hipSuccess) e = hipMemset(b->cb, 0, (size_t)256 * d * sizeof(float));
+  if (e != hipSuccess) {
+    knnx_pqb_destroy(b);
+    return fail(e == hipErrorOutOfMemory ? KNNX_E_NOMEM : KNNX_E_HIP, std::string("pqb_create: ") + hipGetErrorString(e));
+  }
+  *out = b;
+  return KNNX_OK;
+}
+
+// the part of set_sample shared by the host and the device variant: lists (host copy h_lists, validated), centroids, scratch
+static int pqb_sample_common(knnx_pq_builder* b, int64_t n, const int32_t* h_lists, const uint16_t* centroids_f16, int nlist) {
+  for (int64_t i = 0; i < n; ++i)
+    if (h_lists[i] < 0 || h_lists[i] >= nlist) return fail(KNNX_E_ARG, "a sample row's list id is outside [0, nlist)");
+  knnx_pq_builder::Sample& s = b->s;
+  s.nlist = nlist;
+  s.n = n;
+  hipError_t e = hipSuccess;
+  dev_alloc(e, s.lists, (size_t)n);
+  dev_alloc(e, s.cent, (size_t)nlist * b->d);
+  dev_alloc(e, s.codes, (size_t)n * b->M);
+  dev_alloc(e, s.order, (size_t)n * b->M);
+  dev_alloc(e, s.off, (size_t)b->M * 257);
+  if (e == hipSuccess) e = hipMemcpy(s.lists, h_lists, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(s.cent, centroids_f16, (size_t)nlist * b->d * sizeof(_Float16), hipMemcpyHostToDevice);
+  if (e != hipSuccess) b->s = knnx_pq_builder::Sample();
+  HIPCHK(e);
+  return KNNX_OK;
+}
+
+extern "C" int knnx_pqb_set_sample(knnx_pq_builder* b, const uint16_t* rows_f16, const int32_t* lists, int64_t n, const uint16_t* centroids_f16,
+                                   int nlist) {
+  if (!b || !rows_f16 || !lists || !centroids_f16 || n <= 0 || n > INT32_MAX || nlist <= 0) return fail(KNNX_E_ARG, "bad pqb_set_sample arguments");
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  b->s = knnx_pq_builder::Sample();
+  HIPCHK(b->s.X.alloc((size_t)n * b->d));
+  HIPCHK(hipMemcpy(b->s.X, rows_f16, (size_t)n * b->d * sizeof(_Float16), hipMemcpyHostToDevice));
+  return pqb_sample_common(b, n, lists, centroids_f16, nlist);
+}
+
+// rows_dev: fp16 [n][d] borrowed (kept alive by the caller until the training is over); lists_dev: int32 [n] (copied)
+extern "C" int knnx_pqb_set_sample_device(knnx_pq_builder* b, const void* rows_dev_f16, const int32_t* lists_dev, int64_t n,
+                                          const uint16_t* centroids_f16, int nlist) {
+  if (!b || !rows_dev_f16 || !lists_dev || !centroids_f16 || n <= 0 || n > INT32_MAX || nlist <= 0)
+    return fail(KNNX_E_ARG, "bad pqb_set_sample_device arguments");
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  b->s = knnx_pq_builder::Sample();
+  std::vector<int32_t> h((size_t)n);
+  HIPCHK(hipMemcpy(h.data(), lists_dev, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  b->s.X.borrow(rows_dev_f16);
+  return pqb_sample_common(b, n, h.data(), centroids_f16, nlist);
+}
+
+// codebook entries mj[i] (= m * 256 + j) := residual sub-vector m of sample row sample_rows[i]
+extern "C" int knnx_pqb_seed_from_sample(knnx_pq_builder* b, const int32_t* mj, const int64_t* sample_rows, int64_t n) {
+  if (!b || (n > 0 && (!mj || !sample_rows)) || n < 0 || !b->s.X) return fail(KNNX_E_ARG, "bad pqb_seed_from_sample arguments (set a sample first)");
+  if (n == 0) return KNNX_OK;
+  for (int64_t i = 0; i < n; ++i)
+    if (mj[i] < 0 || mj[i] >= b->M * 256 || sample_rows[i] < 0 || sample_rows[i] >= b->s.n) return fail(KNNX_E_ARG, "codebook entry / sample row out of range");
+  HIPCHK(hipSetDevice(b->device));
+  DevBuf<int32_t> mj_dev;
+  DevBuf<int64_t> r_dev;
+  HIPCHK(mj_dev.alloc((size_t)n));
+  hipError_t e = r_dev.alloc((size_t)n);
+  if (e == hipSuccess) e = hipMemcpy(mj_dev, mj, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(r_dev, sample_rows, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = launch_pq_seed(b->s.X, b->d, b->M, b->s.lists, b->s.cent, mj_dev, r_dev, n, b->cb, b->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+  if (e != hipSuccess) return fail(KNNX_E_HIP, std::string("pqb_seed_from_sample: ") + hipGetErrorString(e));
+  return KNNX_OK;
+}
+
+extern "C" int knnx_pqb_set_codebooks(knnx_pq_builder* b, const float* codebooks) {
+  if (!b || !codebooks) return fail(KNNX_E_ARG, "bad pqb_set_codebooks arguments");
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  HIPCHK(hipMemcpy(b->cb, codebooks, (size_t)256 * b->d * sizeof(float), hipMemcpyHostToDevice));
+  return KNNX_OK;
+}
+
+extern "C" int knnx_pqb_get_codebooks(knnx_pq_builder* b, float* codebooks) {
+  if (!b || !codebooks) return fail(KNNX_E_ARG, "bad pqb_get_codebooks arguments");
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  HIPCHK(hipMemcpy(codebooks, b->cb, (size_t)256 * b->d * sizeof(float), hipMemcpyDeviceToHost));
+  return KNNX_OK;
+}
+
+// One Lloyd iteration of the M k-means: encode the sample (argmin per sub-quantiser, ties -> smaller j) -> codes to the host ->
+// counting sort per sub-quantiser (members ascending by sample row: the fixed summation order) -> mean update; an empty
+// cluster keeps its centroid (the caller re-seeds it).  codes_out [n][M] (this iteration's assignment) and sizes_out [M][256]
+// (host) may be null.
+extern "C" int knnx_pqb_lloyd(knnx_pq_builder* b, uint8_t* codes_out, int64_t* sizes_out) {
+  if (!b || !b->s.X) return fail(KNNX_E_ARG, "bad pqb_lloyd arguments (set a sample first)");
+  HIPCHK(hipSetDevice(b->device));
+  const int64_t n = b->s.n;
+  const int M = b->M;
+  b->h_codes.resize((size_t)n * M);
+  b->h_order.resize((size_t)n * M);
+  b->h_off.assign((size_t)M * 257, 0);
+  HIPCHK(launch_pq_encode(b->s.X, n, b->d, M, b->s.lists, b->s.cent, b->cb, nullptr, nullptr, nullptr, 0, 0, 0, b->s.codes, nullptr, nullptr, b->stream));
+  HIPCHK(hipMemcpyAsync(b->h_codes.data(), b->s.codes, (size_t)n * M, hipMemcpyDeviceToHost, b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  for (int m = 0; m < M; ++m) {
+    int32_t* off = b->h_off.data() + (size_t)m * 257;
+    for (int64_t i = 0; i < n; ++i) off[b->h_codes[(size_t)i * M + m] + 1]++;
+    if (sizes_out)
+      for (int j = 0; j < 256; ++j) sizes_out[(size_t)m * 256 + j] = off[j + 1];
+    for (int j = 0; j < 256; ++j) off[j + 1] += off[j];
+    std::vector<int32_t> cur(off, off + 256);
+    int32_t* ord = b->h_order.data() + (size_t)m * n;
+    for (int64_t i = 0; i < n; ++i) ord[cur[b->h_codes[(size_t)i * M + m]]++] = (int32_t)i;
+  }
+  if (codes_out) memcpy(codes_out, b->h_codes.data(), (size_t)n * M);
+  HIPCHK(hipMemcpyAsync(b->s.order, b->h_order.data(), (size_t)n * M * sizeof(int32_t), hipMemcpyHostToDevice, b->stream));
+  HIPCHK(hipMemcpyAsync(b->s.off, b->h_off.data(), (size_t)M * 257 * sizeof(int32_t), hipMemcpyHostToDevice, b->stream));
+  HIPCHK(launch_pq_update(b->s.X, b->d, M, b->s.lists, b->s.cent, b->s.order, b->s.off, n, b->cb, b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  return KNNX_OK;
+}

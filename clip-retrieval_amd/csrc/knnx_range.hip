@@ -1,0 +1,425 @@
+// knnx_range.hip -- range scans and the large-k search built on them (host side; see knnx_host.h).
+
+#include "knnx_host.h"
+
+// range scan of <= KNN_NQ queries; leaves per-query counts in `counts` and the hits on the device
+// (query i's hits at range_s/range_i[i*cap .. i*cap+counts[i]), cap = range_pool / nq)
+static const size_t RANGE_POOL_MAX = (size_t)1 << 29;  // 512 Mi hits = 4 GiB of scratch
+constexpr int64_t RANGE_BATCH_MAX_ROWS = 1 << 16;  // range_scan_batched: indexes up to this many rows (a scan is launch-bound there)
+
+// the hit pools with `want` entries each, or none (the int8 copy is reclaimed first when they do not fit)
+static int range_pool_alloc(knnx_index* ix, size_t want) {
+  ix->range = RangePools();
+  hipError_t e = malloc_or_reclaim(ix, ix->range.s, want);
+  if (e == hipSuccess) e = malloc_or_reclaim(ix, ix->range.i, want);
+  if (e != hipSuccess) ix->range = RangePools();
+  HIPCHK(e);
+  ix->range.pool = want;
+  return 0;
+}
+
+static int range_scan(knnx_index* ix, const float* q_host, int nq, float thr, std::vector<unsigned>& counts,
+                      unsigned* cap_out) {
+  hipStream_t st = ix->stream;
+  int r = ensure_pin(ix, (size_t)KNN_NQ * ix->d * sizeof(float));
+  if (r) return r;
+  if (scratch_acquire(ix, st)) return KNNX_E_HIP;
+  memcpy(ix->pin.p, q_host, (size_t)nq * ix->d * sizeof(float));
+  HIPCHK(hipMemcpyAsync(ix->flat.q_dev, ix->pin.p, (size_t)nq * ix->d * sizeof(float), hipMemcpyHostToDevice, st));
+  for (;;) {
+    if (ix->range.pool == 0 && (r = range_pool_alloc(ix, (size_t)1 << 21))) return r;
+    const unsigned cap = (unsigned)std::min<size_t>(ix->range.pool / (size_t)nq, 0xffffffffu);
+    if (ix->ivf_nlist) {  // IVF: the range is taken over the rows of the nprobe best lists of each query (faiss IndexIVF semantics)
+      r = ivf_build_worklist(ix, ix->flat.q_dev, nq, st, nullptr);
+      if (r) return r;
+    }
+    HIPCHK(launch_prep(ix->flat.q_dev, nq, ix->d, ix->flat.qfrag, ix->flat.thr_g, ix->flat.range_cnt, 0, nullptr, st));
+    ScanArgs a{};
+    a.X = ix->rows;
+    a.N = ix->ivf_nlist ? ix->capacity : ix->ntotal;
+    a.work = ix->ivf_nlist ? ix->ivf1.work : nullptr;
+    a.nwork = ix->ivf1.nwork;
+    a.d = ix->d;
+    a.qfrag = ix->flat.qfrag;
+    a.nq = nq;
+    a.k = 1;
+    a.cap = 2;
+    a.grid = ix->n_cu;
+    a.mode = 1;
+    a.thr_g = ix->flat.thr_g;
+    a.range_thr = thr;
+    a.range_cnt = ix->flat.range_cnt;
+    a.range_cap = cap;
+    a.range_s = ix->range.s;
+    a.range_i = ix->range.i;
+    HIPCHK(launch_scan(a, st));
+    counts.assign(KNN_NQ, 0u);
+    HIPCHK(hipMemcpyAsync(counts.data(), ix->flat.range_cnt, KNN_NQ * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    unsigned mx = 0;
+    for (int i = 0; i < nq; ++i) mx = std::max(mx, counts[i]);
+    if (mx <= cap) {
+      *cap_out = cap;
+      return 0;
+    }
+    // overflow: regrow and rescan (the counts are exact even when the buffers overflowed)
+    size_t want = ix->range.pool;
+    while (want / (size_t)nq < (size_t)mx) want <<= 1;
+    if (want > RANGE_POOL_MAX) return fail(KNNX_E_NOMEM, "range_search result exceeds the 512 Mi-hit scratch limit");
+    if ((r = range_pool_alloc(ix, want))) return r;
+  }
+}
+
+// Many queries against a SMALL flat index (the per-request dedup of clip_back.py:290-294: the k result vectors against themselves,
+// k up to 3 000): all 32-query groups are launched back to back, every group with its own counters and its own slice of the hit
+// pool, and the host synchronises ONCE for the counts -- the one-group-at-a-time loop costs two synchronisations per group
+// (94 groups at k = 3 000: 10 ms of a 45 ms request, profiles/r03h_request.log).  counts [n]; *cnt_dev_out = the device counters
+// (scratch slot 4) for range_fetch.
+static int range_scan_batched(knnx_index* ix, const float* q_host, int n, float thr, std::vector<unsigned>& counts, unsigned* cap_out,
+                              unsigned** cnt_dev_out) {
+  hipStream_t st = ix->stream;
+  const int ngroups = (n + KNN_NQ - 1) / KNN_NQ;
+  const size_t nr = (size_t)ngroups * KNN_NQ;
+  float* q_all = nullptr;
+  unsigned* cnt_all = nullptr;
+  int r = ensure_scratch(ix, 3, nr * ix->d * sizeof(float), (void**)&q_all);
+  if (!r) r = ensure_scratch(ix, 4, nr * sizeof(unsigned), (void**)&cnt_all);
+  if (r) return r;
+  if (scratch_acquire(ix, st)) return KNNX_E_HIP;
+  HIPCHK(hipMemcpyAsync(q_all, q_host, (size_t)n * ix->d * sizeof(float), hipMemcpyHostToDevice, st));
+  for (;;) {
+    if (ix->range.pool == 0 && (r = range_pool_alloc(ix, (size_t)1 << 21))) return r;
+    const unsigned cap = (unsigned)std::min<size_t>(ix->range.pool / nr, 0xffffffffu);
+    unsigned mx = 0;
+    if (cap > 0) {
+      for (int g = 0; g < ngroups; ++g) {
+        const int q0 = g * KNN_NQ, nq = std::min(KNN_NQ, n - q0);
+        HIPCHK(launch_prep(q_all + (size_t)q0 * ix->d, nq, ix->d, ix->flat.qfrag, ix->flat.thr_g, cnt_all + q0, 0, nullptr, st));
+        ScanArgs a{};
+        a.X = ix->rows;
+        a.N = ix->ntotal;
+        a.d = ix->d;
+        a.qfrag = ix->flat.qfrag;
+        a.nq = nq;
+        a.k = 1;
+        a.cap = 2;
+        a.grid = ix->n_cu;
+        a.mode = 1;
+        a.thr_g = ix->flat.thr_g;
+        a.range_thr = thr;
+        a.range_cnt = cnt_all + q0;
+        a.range_cap = cap;
+        a.range_s = ix->range.s + (size_t)q0 * cap;
+        a.range_i = ix->range.i + (size_t)q0 * cap;
+        HIPCHK(launch_scan(a, st));
+      }
+      counts.assign(nr, 0u);
+      HIPCHK(hipMemcpyAsync(counts.data(), cnt_all, nr * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      for (int i = 0; i < n; ++i) mx = std::max(mx, counts[i]);
+      if (mx <= cap) {
+        *cap_out = cap;
+        *cnt_dev_out = cnt_all;
+        return 0;
+      }
+    } else {
+      mx = 1;
+    }
+    // overflow: regrow and rescan (the counts are exact even when the buffers overflowed)
+    size_t want = ix->range.pool;
+    while (want / nr < (size_t)mx) want <<= 1;
+    if (want > RANGE_POOL_MAX) return fail(KNNX_E_NOMEM, "range_search result exceeds the 512 Mi-hit scratch limit");
+    if ((r = range_pool_alloc(ix, want))) return r;
+  }
+}
+
+// copy the hits of the last range_scan to the host, ids ascending inside each query
+static int range_fetch(knnx_index* ix, int nq, const std::vector<unsigned>& counts, unsigned cap, float* D,
+                       int64_t* I, const unsigned* cnt_dev = nullptr) {
+  if (!cnt_dev) cnt_dev = ix->flat.range_cnt;
+  std::vector<int64_t> loc(nq + 1);
+  loc[0] = 0;
+  for (int i = 0; i < nq; ++i) loc[i + 1] = loc[i] + counts[i];
+  if (loc[nq] == 0) return 0;
+  int64_t* lims_dev = nullptr;
+  float* D_dev = nullptr;
+  int64_t* I_dev = nullptr;
+  int rr = ensure_scratch(ix, 0, (nq + 1) * sizeof(int64_t), (void**)&lims_dev);
+  if (!rr) rr = ensure_scratch(ix, 1, (size_t)loc[nq] * sizeof(float), (void**)&D_dev);
+  if (!rr) rr = ensure_scratch(ix, 2, (size_t)loc[nq] * sizeof(int64_t), (void**)&I_dev);
+  if (rr) return rr;
+  hipError_t e = hipMemcpyAsync(lims_dev, loc.data(), (nq + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ix->stream);
+  if (e == hipSuccess)
+    e = launch_range_sort(ix->range.s, ix->range.i, cnt_dev, cap, lims_dev, ix->id_base,
+                          ix->ivf_nlist ? ix->ivf.idmap : nullptr, nq, D_dev, I_dev, ix->stream);
+  // hit lists too long for rank-by-counting: radix sort by id, one query at a time
+  unsigned longest = 0;
+  for (int i = 0; i < nq; ++i) longest = std::max(longest, counts[i] > RANGE_SORT_SMALL ? counts[i] : 0u);
+  if (e == hipSuccess && longest) {
+    DevBuf<uint32_t> k0, k1;
+    DevBuf<float> v0, v1;
+    DevBuf<unsigned> hist;
+    dev_alloc(e, k0, longest);
+    dev_alloc(e, k1, longest);
+    dev_alloc(e, v0, longest);
+    dev_alloc(e, v1, longest);
+    dev_alloc(e, hist, (size_t)16 * ((longest + 2047) / 2048));
+    int key_bits = 1;
+    while (key_bits < 32 && ((int64_t)1 << key_bits) < std::max<int64_t>(ix->ntotal, 2)) ++key_bits;
+    for (int i = 0; i < nq && e == hipSuccess; ++i)
+      if (counts[i] > RANGE_SORT_SMALL)
+        e = launch_range_sort_long(ix->range.s + (size_t)i * cap, ix->range.i + (size_t)i * cap, counts[i], ix->id_base,
+                                   ix->ivf_nlist ? ix->ivf.idmap : nullptr, key_bits, k0, k1, v0, v1, hist, D_dev + loc[i],
+                                   I_dev + loc[i], ix->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ix->stream);
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(D, D_dev, (size_t)loc[nq] * sizeof(float), hipMemcpyDeviceToHost, ix->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(I, I_dev, (size_t)loc[nq] * sizeof(int64_t), hipMemcpyDeviceToHost, ix->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ix->stream);
+  if (e != hipSuccess) return fail(KNNX_E_HIP, std::string("range fetch: ") + hipGetErrorString(e));
+  return 0;
+}
+
+extern "C" int knnx_range_search(knnx_index* ix, const float* q, int n, float thresh, int64_t* lims, float* D,
+                                 int64_t* I) {
+  if (!ix || !lims || (n > 0 && !q) || n < 0) return fail(KNNX_E_ARG, "bad range_search arguments");
+  if ((D == nullptr) != (I == nullptr)) return fail(KNNX_E_ARG, "D and I must both be null or both be set");
+  if (ix->pq.m) return fail(KNNX_E_UNSUPPORTED, "range_search is not supported on an IVF-PQ index");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  if (set_dev(ix)) return KNNX_E_HIP;
+  const bool fill = D != nullptr;
+  int64_t run = 0;
+  std::vector<unsigned> counts;
+  if (!fill) lims[0] = 0;
+  for (int o = 0; o < n; o += KNN_NQ) {
+    const int nq = std::min(KNN_NQ, n - o);
+    unsigned cap = 0;
+    int r = range_scan(ix, q + (size_t)o * ix->d, nq, thresh, counts, &cap);
+    if (r) return r;
+    if (!fill) {
+      for (int i = 0; i < nq; ++i) {
+        run += counts[i];
+        lims[o + i + 1] = run;
+      }
+      continue;
+    }
+    // filling: the caller passes the lims of the counting call; verify them as we go
+    for (int i = 0; i < nq; ++i)
+      if (lims[o + i + 1] - lims[o + i] != (int64_t)counts[i])
+        return fail(KNNX_E_STATE, "lims do not match this query/threshold (index changed between the two calls?)");
+    r = range_fetch(ix, nq, counts, cap, D + lims[o], I + lims[o]);
+    if (r) return r;
+  }
+  return KNNX_OK;
+}
+
+// range_search in ONE pass when the caller's buffers are large enough: lims [n + 1] is always filled; D / I (capacity entries)
+// receive the hits if lims[n] <= capacity (return KNNX_OK), otherwise nothing is written to them and the return value is 1 --
+// the caller then allocates lims[n] entries and uses knnx_range_search's filling call.  Saves the counting scan of the two-call
+// protocol for callers with a good guess (the per-request dedup of clip_back.py:290-294: ~k hits for k result vectors).
+extern "C" int knnx_range_search_once(knnx_index* ix, const float* q, int n, float thresh, int64_t* lims, float* D, int64_t* I,
+                                      int64_t capacity) {
+  if (!ix || !lims || (n > 0 && !q) || n < 0 || capacity < 0 || (capacity > 0 && (!D || !I))) return fail(KNNX_E_ARG, "bad range_search_once arguments");
+  if (ix->pq.m) return fail(KNNX_E_UNSUPPORTED, "range_search is not supported on an IVF-PQ index");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  if (set_dev(ix)) return KNNX_E_HIP;
+  int64_t run = 0;
+  bool fits = true;
+  std::vector<unsigned> counts;
+  lims[0] = 0;
+  if (!ix->ivf_nlist && n > KNN_NQ && ix->ntotal <= RANGE_BATCH_MAX_ROWS) {  // small flat index, many queries: one synchronisation
+    unsigned cap = 0;
+    unsigned* cnt_dev = nullptr;
+    int r = range_scan_batched(ix, q, n, thresh, counts, &cap, &cnt_dev);
+    if (r) return r;
+    for (int i = 0; i < n; ++i) {
+      run += counts[i];
+      lims[i + 1] = run;
+    }
+    if (run > capacity) return 1;
+    counts.resize(n);
+    return range_fetch(ix, n, counts, cap, D, I, cnt_dev);
+  }
+  for (int o = 0; o < n; o += KNN_NQ) {
+    const int nq = std::min(KNN_NQ, n - o);
+    unsigned cap = 0;
+    int r = range_scan(ix, q + (size_t)o * ix->d, nq, thresh, counts, &cap);
+    if (r) return r;
+    const int64_t first = run;
+    for (int i = 0; i < nq; ++i) {
+      run += counts[i];
+      lims[o + i + 1] = run;
+    }
+    if (run > capacity) fits = false;
+    if (fits) {
+      r = range_fetch(ix, nq, counts, cap, D + first, I + first);
+      if (r) return r;
+    }
+  }
+  return fits ? KNNX_OK : 1;
+}
+
+// k > 64 (the front-end's num_result_ids = 3000, clip_back.py:358 asks for up to 1e5): one range scan with a threshold that
+// lets >= k rows through, the hits ranked on the host (k log k, tiny next to a scan).  Exact: every row scoring above the
+// threshold is a hit, so cnt >= k hits contain the top k.  The threshold:
+//   * flat index with N >= 128 k rows: the j-th best EXACT score of a strided sample (every S-th 32-row tile, the 32-query scan
+//     with tstride = S: 1 / S of the bytes), S and j <= 48 chosen so that j S ~ 1.5 k rows are expected above it.  The count
+//     above the j-th best of a 1 / S sample is ~ S Gamma(j) whatever the score distribution (the argument of the RQ scan's
+//     thresholds, knn_kernels.h), so cnt < k has a probability of a few per cent; then the 64-th sample score is tried
+//     (~ S * 64 hits) before the descent below takes over.  Cost: ~1.01 scans instead of the 2 - 6 of round 2 -- and instead of
+//     the 10.9 s measured at 100 M rows in round 3 (profiles/r03b_request.log), where a query with one very close neighbour
+//     (top - s64 = 0.8) made the first descent step jump below zero and 50 M rows had to be fetched and sorted;
+//   * otherwise (small or IVF index): descent from the top-64 scores.  The first step extrapolates the LOCAL score density
+//     (32 rows lie between the 32nd and the 64th score), doubling while cnt < k; when a step overshoots by more than 16 x the
+//     threshold is bisected back (at most 4 times) before the hits are fetched.
+// Caller holds ix->mu.
+static int sample_scores_locked(knnx_index* ix, const float* qq, int tstride, float* d64) {
+  hipStream_t st = ix->stream;
+  int r = ensure_pin(ix, (size_t)ix->d * sizeof(float) + KNNX_MAX_K_FAST * sizeof(float));
+  if (r) return r;
+  if (scratch_acquire(ix, st)) return KNNX_E_HIP;
+  memcpy(ix->pin.p, qq, (size_t)ix->d * sizeof(float));
+  HIPCHK(hipMemcpyAsync(ix->flat.q_dev, ix->pin.p, (size_t)ix->d * sizeof(float), hipMemcpyHostToDevice, st));
+  HIPCHK(launch_prep(ix->flat.q_dev, 1, ix->d, ix->flat.qfrag, ix->flat.thr_g, nullptr, 0, nullptr, st));
+  ScanArgs a{};
+  a.X = ix->rows;
+  a.N = ix->ntotal;
+  a.d = ix->d;
+  a.qfrag = ix->flat.qfrag;
+  a.nq = 1;
+  a.k = KNNX_MAX_K_FAST;
+  a.cap = scan_cap(ix->d, KNNX_MAX_K_FAST);
+  a.grid = ix->n_cu;
+  a.mode = 0;
+  a.tstride = tstride;
+  a.thr_g = ix->flat.thr_g;
+  a.part_s = ix->flat.part_s;
+  a.part_i = ix->flat.part_i;
+  a.part_n = ix->flat.part_n;
+  if (a.cap < 0) return fail(KNNX_E_UNSUPPORTED, "k too large for the LDS queues at this d");
+  HIPCHK(launch_scan(a, st));
+  HIPCHK(launch_merge_u32(ix->flat.part_s, ix->flat.part_i, ix->flat.part_n, ix->n_cu, KNN_NQ, KNNX_MAX_K_FAST, 1, KNNX_MAX_K_FAST, 0, nullptr, ix->flat.D_dev,
+                          ix->flat.I_dev, nullptr, st));
+  float* out = (float*)((char*)ix->pin.p + (size_t)ix->d * sizeof(float));
+  HIPCHK(hipMemcpyAsync(out, ix->flat.D_dev, KNNX_MAX_K_FAST * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  memcpy(d64, out, KNNX_MAX_K_FAST * sizeof(float));
+  if (scratch_release(ix, st)) return KNNX_E_HIP;
+  return 0;
+}
+
+int search_large_k_locked(knnx_index* ix, const float* q, int n, int k, float* D, int64_t* I) {
+  std::vector<float> d64((size_t)KNNX_MAX_K_FAST);
+  std::vector<int64_t> i64((size_t)KNNX_MAX_K_FAST);
+  const int64_t N = ix->ntotal;
+  const int64_t want = std::min<int64_t>(k, N);
+  for (int qi = 0; qi < n; ++qi) {
+    const float* qq = q + (size_t)qi * ix->d;
+    float* Dq = D + (size_t)qi * k;
+    int64_t* Iq = I + (size_t)qi * k;
+    std::vector<std::pair<float, int64_t>> hits;
+    std::vector<unsigned> counts;
+    unsigned cap = 0;
+    int r;
+    bool done = false;
+    auto fetch = [&](int64_t cnt) -> int {
+      std::vector<float> hd((size_t)cnt);
+      std::vector<int64_t> hi((size_t)cnt);
+      int rr = range_fetch(ix, 1, counts, cap, hd.data(), hi.data());
+      if (rr) return rr;
+      hits.reserve((size_t)cnt);
+      for (int64_t j = 0; j < cnt; ++j) hits.emplace_back(hd[j], hi[j]);
+      return 0;
+    };
+    float thr_hi = FLT_MAX;  // a threshold known to let fewer than k rows through (descent / bisection bracket)
+    if (!ix->ivf_nlist && N >= (int64_t)128 * k) {
+      // ---- sampled threshold: S tiles apart, j-th best sample score, j S ~ 1.5 k
+      const int S = (int)std::max<int64_t>(2, (3 * (int64_t)k / 2 + 47) / 48);
+      const int j = (int)std::min<int64_t>(48, std::max<int64_t>(8, (3 * (int64_t)k / 2 + S - 1) / S));
+      r = sample_scores_locked(ix, qq, S, d64.data());
+      if (r) return r;
+      for (int attempt = 0; attempt < 2 && !done; ++attempt) {
+        const float sj = d64[attempt == 0 ? j - 1 : KNNX_MAX_K_FAST - 1];
+        if (!(sj > -FLT_MAX)) break;  // fewer sample rows than that
+        const float thr = nextafterf(sj, -FLT_MAX);  // the range is strict (>): keep the sample row itself
+        r = range_scan(ix, qq, 1, thr, counts, &cap);
+        if (r) return r;
+        if ((int64_t)counts[0] >= want) {
+          if ((r = fetch(counts[0]))) return r;
+          done = true;
+        } else {
+          thr_hi = thr;
+        }
+      }
+    }
+    if (!done) {
+      r = search_fast_locked(ix, qq, 1, KNNX_MAX_K_FAST, d64.data(), i64.data());
+      if (r) return r;
+      int have = 0;
+      while (have < KNNX_MAX_K_FAST && i64[have] >= 0) ++have;
+      if (have < KNNX_MAX_K_FAST) {  // the whole index (or all probed lists) is smaller than 64 rows
+        for (int j = 0; j < have; ++j) hits.emplace_back(d64[j], i64[j]);
+      } else {
+        const float s32 = d64[KNNX_MAX_K_FAST / 2 - 1], s64 = d64[KNNX_MAX_K_FAST - 1];
+        // local density: 32 rows within s32 - s64; k - 64 more rows are ~ (k - 64) / 32 such gaps away (fewer: the density grows)
+        float step = std::max((s32 - s64) * std::min(64.f, (float)(k - KNNX_MAX_K_FAST) / 32.f) * 0.5f, 1e-4f * std::max(1.f, fabsf(s64)));
+        float thr = std::min(s64 - step, thr_hi < FLT_MAX ? nextafterf(thr_hi, -FLT_MAX) : FLT_MAX);
+        float lo_ok = -FLT_MAX;  // lowest threshold tried so far (lets >= k rows through once found)
+        int64_t prev_cnt = -1;
+        int stalled = 0, bisections = 0;
+        thr_hi = std::min(thr_hi, s64);
+        for (int it = 0;; ++it) {
+          r = range_scan(ix, qq, 1, thr, counts, &cap);
+          if (r) return r;
+          const int64_t cnt = counts[0];
+          // an IVF index only reaches the rows of the probed lists: when three ever larger steps add nothing, take what there
+          // is.  Flat indexes never take this shortcut: cnt >= min(k, N) is reached after O(log) doublings.
+          stalled = (ix->ivf_nlist && cnt == prev_cnt) ? stalled + 1 : 0;
+          prev_cnt = cnt;
+          if (cnt < want && thr > -FLT_MAX && stalled < 3 && it < 60) {
+            thr_hi = thr;
+            step *= 2.f;
+            thr = (thr - step > -FLT_MAX) ? thr - step : -FLT_MAX;
+            continue;
+          }
+          if (cnt < want && thr > -FLT_MAX) {  // stalled (IVF) or out of patience: everything the scan can reach
+            thr = -FLT_MAX;
+            stalled = 0;
+            continue;
+          }
+          // enough rows.  Far too many (an overshooting step)?  Bisect back towards the last threshold that had too few.
+          if (cnt > 16 * want && cnt > 65536 && bisections < 4 && thr_hi < FLT_MAX && thr > -FLT_MAX) {
+            lo_ok = thr;
+            thr = 0.5f * (thr + thr_hi);
+            ++bisections;
+            // (a middle that has too few rows raises thr_hi above and steps down again, towards lo_ok)
+            step = 0.5f * (thr - lo_ok);
+            continue;
+          }
+          if ((r = fetch(cnt))) return r;
+          break;
+        }
+      }
+    }
+    // rank the hits: score descending, ties by ascending id.  Only the first k are reported, so only they are sorted (a range
+    // scan hands back 1.5 .. 16 x k hits: O(hits) selection + k log k, 10 ms at k = 100 000 instead of a full sort)
+    auto better = [](const std::pair<float, int64_t>& a, const std::pair<float, int64_t>& b) {
+      return a.first > b.first || (a.first == b.first && a.second < b.second);
+    };
+    if ((int64_t)hits.size() > (int64_t)k) {
+      std::nth_element(hits.begin(), hits.begin() + k, hits.end(), better);
+      hits.resize((size_t)k);
+    }
+    std::sort(hits.begin(), hits.end(), better);
+    for (int j = 0; j < k; ++j) {
+      if (j < (int)hits.size()) {
+        Dq[j] = hits[j].first;
+        Iq[j] = hits[j].second;
+      } else {
+        Dq[j] = -FLT_MAX;
+        Iq[j] = -1;
+      }
+    }
+  }
+  return KNNX_OK;
+}

@@ -22,21 +22,10 @@
 //   * reconstruct: ids are routed to the owning shard by row range.
 // Built on the public entry points of include/knnx.h only.  No CPU arithmetic: the host routes ids and pointers.
 
-#include <hip/hip_runtime.h>
 #include <dlfcn.h>
-#include <float.h>
 #include <stdlib.h>
-#include <stdint.h>
-#include <string.h>
-#include <algorithm>
-#include <mutex>
-#include <string>
-#include <vector>
 
-#include "../../include/knnx.h"
-#include "knn_kernels.h"
-
-extern "C" int knnx_set_error(int code, const char* msg);  // knnx_api.hip: sets the thread-local message, returns code
+#include "knnx_host.h"  // the error helpers and the owning types only: the index is used through include/knnx.h
 
 namespace {
 
@@ -77,14 +66,14 @@ struct Shard {
   knnx_index* ix = nullptr;
   int device = 0;
   int64_t lo = 0, hi = 0;      // global row range (hi fixed by reserve(); rows present = knnx_ntotal)
-  hipStream_t st = nullptr;
-  hipEvent_t ev = nullptr;
-  float* q = nullptr;          // [cap_q, d]
-  float* D = nullptr;          // [cap_q, 64]
-  int64_t* I = nullptr;
+  Stream st;
+  Event ev;
+  DevBuf<float> q;             // [cap_q, d]
+  DevBuf<float> D;             // [cap_q, 64]
+  DevBuf<int64_t> I;
   void* comm = nullptr;        // RCCL communicator of this device (rank = shard index), or null
-  float* agD = nullptr;        // RCCL: all P lists as this device receives them, [P, cap_q, 64]
-  int64_t* agI = nullptr;
+  DevBuf<float> agD;           // RCCL: all P lists as this device receives them, [P, cap_q, 64]
+  DevBuf<int64_t> agI;
 };
 
 }  // namespace
@@ -96,22 +85,15 @@ struct knnx_shards {
   bool reserved = false;
   int cap_q = 1024;            // queries per exchange round
   // on devices[0]
-  hipStream_t st0 = nullptr;
-  float* gD = nullptr;         // [P, cap_q, 64]
-  int64_t* gI = nullptr;
-  float* mD = nullptr;         // [cap_q, 64]
-  int64_t* mI = nullptr;
-  void* pin = nullptr;         // pinned: queries | D | I
+  Stream st0;
+  DevBuf<float> gD;            // [P, cap_q, 64]
+  DevBuf<int64_t> gI;
+  DevBuf<float> mD;            // [cap_q, 64]
+  DevBuf<int64_t> mI;
+  PinBuf pin;                  // pinned: queries | D | I
   size_t pin_q = 0, pin_d = 0;
   bool use_rccl = false;       // the per-shard top-k lists travel by one grouped ncclAllGather instead of peer copies
 };
-
-#define SHIP(expr)                                                                                                  \
-  do {                                                                                                              \
-    hipError_t _e = (expr);                                                                                         \
-    if (_e != hipSuccess)                                                                                           \
-      return knnx_set_error(_e == hipErrorOutOfMemory ? KNNX_E_NOMEM : KNNX_E_HIP, (std::string(#expr) + ": " + hipGetErrorString(_e)).c_str()); \
-  } while (0)
 
 // give the RCCL exchange up: communicators destroyed, receive buffers freed, the peer-copy form from now on
 static void shards_drop_rccl(knnx_shards* s) {
@@ -119,11 +101,9 @@ static void shards_drop_rccl(knnx_shards* s) {
   for (auto& h : s->sh) {
     (void)hipSetDevice(h.device);
     if (h.comm && rccl().ok) (void)rccl().CommDestroy(h.comm);
-    if (h.agD) (void)hipFree(h.agD);
-    if (h.agI) (void)hipFree(h.agI);
     h.comm = nullptr;
-    h.agD = nullptr;
-    h.agI = nullptr;
+    h.agD.reset();
+    h.agI.reset();
   }
   if (!s->sh.empty()) (void)hipSetDevice(s->sh[0].device);
 }
@@ -132,12 +112,12 @@ static int shards_finish_setup(knnx_shards* s) {
   const int P = (int)s->sh.size();
   for (int g = 0; g < P; ++g) {
     Shard& h = s->sh[g];
-    SHIP(hipSetDevice(h.device));
-    SHIP(hipStreamCreateWithFlags(&h.st, hipStreamNonBlocking));
-    SHIP(hipEventCreateWithFlags(&h.ev, hipEventDisableTiming));
-    SHIP(hipMalloc(&h.q, (size_t)s->cap_q * s->d * sizeof(float)));
-    SHIP(hipMalloc(&h.D, (size_t)s->cap_q * KNNX_MAX_K_FAST * sizeof(float)));
-    SHIP(hipMalloc(&h.I, (size_t)s->cap_q * KNNX_MAX_K_FAST * sizeof(int64_t)));
+    HIPCHK(hipSetDevice(h.device));
+    HIPCHK(h.st.create());
+    HIPCHK(h.ev.create(hipEventDisableTiming));
+    HIPCHK(h.q.alloc((size_t)s->cap_q * s->d));
+    HIPCHK(h.D.alloc((size_t)s->cap_q * KNNX_MAX_K_FAST));
+    HIPCHK(h.I.alloc((size_t)s->cap_q * KNNX_MAX_K_FAST));
     for (int o = 0; o < P; ++o) {  // peer access both ways where the topology offers it; the copies work without it
       if (s->sh[o].device == h.device) continue;
       int can = 0;
@@ -147,15 +127,15 @@ static int shards_finish_setup(knnx_shards* s) {
       }
     }
   }
-  SHIP(hipSetDevice(s->sh[0].device));
-  SHIP(hipStreamCreateWithFlags(&s->st0, hipStreamNonBlocking));
-  SHIP(hipMalloc(&s->gD, (size_t)P * s->cap_q * KNNX_MAX_K_FAST * sizeof(float)));
-  SHIP(hipMalloc(&s->gI, (size_t)P * s->cap_q * KNNX_MAX_K_FAST * sizeof(int64_t)));
-  SHIP(hipMalloc(&s->mD, (size_t)s->cap_q * KNNX_MAX_K_FAST * sizeof(float)));
-  SHIP(hipMalloc(&s->mI, (size_t)s->cap_q * KNNX_MAX_K_FAST * sizeof(int64_t)));
+  HIPCHK(hipSetDevice(s->sh[0].device));
+  HIPCHK(s->st0.create());
+  HIPCHK(s->gD.alloc((size_t)P * s->cap_q * KNNX_MAX_K_FAST));
+  HIPCHK(s->gI.alloc((size_t)P * s->cap_q * KNNX_MAX_K_FAST));
+  HIPCHK(s->mD.alloc((size_t)s->cap_q * KNNX_MAX_K_FAST));
+  HIPCHK(s->mI.alloc((size_t)s->cap_q * KNNX_MAX_K_FAST));
   s->pin_q = (size_t)s->cap_q * s->d * sizeof(float);
   s->pin_d = (size_t)s->cap_q * KNNX_MAX_K_FAST * sizeof(float);
-  SHIP(hipHostMalloc(&s->pin, s->pin_q + s->pin_d + (size_t)s->cap_q * KNNX_MAX_K_FAST * sizeof(int64_t), hipHostMallocDefault));
+  HIPCHK(s->pin.ensure(s->pin_q + s->pin_d + (size_t)s->cap_q * KNNX_MAX_K_FAST * sizeof(int64_t)));
   // ---- RCCL exchange: every shard on its own device (a communicator cannot hold one GPU twice).  OPT-IN (KNNX_SHARDS_RCCL=1) until it
   // has run on a box with more than one GPU: the peer-copy form is the default, and a failing exchange falls back to it.
   const char* env = getenv("KNNX_SHARDS_RCCL");
@@ -173,8 +153,8 @@ static int shards_finish_setup(knnx_shards* s) {
       for (int g = 0; g < P && mem; ++g) {
         Shard& h = s->sh[g];
         mem = hipSetDevice(h.device) == hipSuccess &&
-              hipMalloc(&h.agD, (size_t)P * s->cap_q * KNNX_MAX_K_FAST * sizeof(float)) == hipSuccess &&
-              hipMalloc(&h.agI, (size_t)P * s->cap_q * KNNX_MAX_K_FAST * sizeof(int64_t)) == hipSuccess;
+              h.agD.alloc((size_t)P * s->cap_q * KNNX_MAX_K_FAST) == hipSuccess &&
+              h.agI.alloc((size_t)P * s->cap_q * KNNX_MAX_K_FAST) == hipSuccess;
       }
       s->use_rccl = mem;
       if (!mem) {
@@ -188,7 +168,7 @@ static int shards_finish_setup(knnx_shards* s) {
 }
 
 extern "C" int knnx_shards_create(int n_shards, const int* devices, int d, int metric, knnx_shards** out) {
-  if (!out || !devices || n_shards <= 0 || n_shards > 64) return knnx_set_error(KNNX_E_ARG, "bad shards_create arguments");
+  if (!out || !devices || n_shards <= 0 || n_shards > 64) return fail(KNNX_E_ARG, "bad shards_create arguments");
   *out = nullptr;
   knnx_shards* s = new knnx_shards();
   s->d = d;
@@ -212,11 +192,11 @@ extern "C" int knnx_shards_create(int n_shards, const int* devices, int d, int m
 
 extern "C" int knnx_shards_adopt(int n_shards, knnx_index* const* shards, const int* devices, const int64_t* row_lo,
                                  knnx_shards** out) {
-  if (!out || !shards || !devices || !row_lo || n_shards <= 0 || n_shards > 64) return knnx_set_error(KNNX_E_ARG, "bad shards_adopt arguments");
+  if (!out || !shards || !devices || !row_lo || n_shards <= 0 || n_shards > 64) return fail(KNNX_E_ARG, "bad shards_adopt arguments");
   *out = nullptr;
   const int d = knnx_dim(shards[0]);
   for (int g = 0; g < n_shards; ++g)
-    if (!shards[g] || knnx_dim(shards[g]) != d) return knnx_set_error(KNNX_E_ARG, "shards disagree on the dimension");
+    if (!shards[g] || knnx_dim(shards[g]) != d) return fail(KNNX_E_ARG, "shards disagree on the dimension");
   knnx_shards* s = new knnx_shards();
   s->d = d;
   s->sh.resize(n_shards);
@@ -242,24 +222,12 @@ extern "C" void knnx_shards_destroy(knnx_shards* s) {
   for (auto& h : s->sh) {
     (void)hipSetDevice(h.device);
     if (h.st) (void)hipStreamSynchronize(h.st);
-    if (h.q) (void)hipFree(h.q);
-    if (h.D) (void)hipFree(h.D);
-    if (h.I) (void)hipFree(h.I);
     if (h.comm && rccl().ok) (void)rccl().CommDestroy(h.comm);
-    if (h.agD) (void)hipFree(h.agD);
-    if (h.agI) (void)hipFree(h.agI);
-    if (h.ev) (void)hipEventDestroy(h.ev);
-    if (h.st) (void)hipStreamDestroy(h.st);
     if (h.ix) knnx_destroy(h.ix);
+    h = Shard();  // (its buffers, event and stream go while its device is current)
   }
   if (!s->sh.empty()) (void)hipSetDevice(s->sh[0].device);
   if (s->st0) (void)hipStreamSynchronize(s->st0);
-  if (s->gD) (void)hipFree(s->gD);
-  if (s->gI) (void)hipFree(s->gI);
-  if (s->mD) (void)hipFree(s->mD);
-  if (s->mI) (void)hipFree(s->mI);
-  if (s->pin) (void)hipHostFree(s->pin);
-  if (s->st0) (void)hipStreamDestroy(s->st0);
   delete s;
 }
 
@@ -274,9 +242,9 @@ extern "C" int64_t knnx_shards_ntotal(const knnx_shards* s) {
 }
 
 extern "C" int knnx_shards_reserve(knnx_shards* s, int64_t total_rows) {
-  if (!s || total_rows < 0) return knnx_set_error(KNNX_E_ARG, "bad shards_reserve arguments");
+  if (!s || total_rows < 0) return fail(KNNX_E_ARG, "bad shards_reserve arguments");
   std::lock_guard<std::mutex> lk(s->mu);
-  if (s->reserved) return knnx_set_error(KNNX_E_STATE, "row ranges are already fixed");
+  if (s->reserved) return fail(KNNX_E_STATE, "row ranges are already fixed");
   const int P = (int)s->sh.size();
   for (int g = 0; g < P; ++g) {
     Shard& h = s->sh[g];
@@ -291,9 +259,9 @@ extern "C" int knnx_shards_reserve(knnx_shards* s, int64_t total_rows) {
 }
 
 static int shards_add(knnx_shards* s, const void* rows, int64_t n, bool f32) {
-  if (!s || (n > 0 && !rows) || n < 0) return knnx_set_error(KNNX_E_ARG, "bad shards_add arguments");
+  if (!s || (n > 0 && !rows) || n < 0) return fail(KNNX_E_ARG, "bad shards_add arguments");
   std::lock_guard<std::mutex> lk(s->mu);
-  if (!s->reserved) return knnx_set_error(KNNX_E_STATE, "call knnx_shards_reserve(total_rows) before add: it fixes the row range of every shard");
+  if (!s->reserved) return fail(KNNX_E_STATE, "call knnx_shards_reserve(total_rows) before add: it fixes the row range of every shard");
   const size_t esz = (f32 ? 4 : 2) * (size_t)s->d;
   int64_t done = 0;
   for (auto& h : s->sh) {
@@ -306,14 +274,14 @@ static int shards_add(knnx_shards* s, const void* rows, int64_t n, bool f32) {
     if (r) return r;
     done += m;
   }
-  if (done != n) return knnx_set_error(KNNX_E_NOMEM, "more rows added than knnx_shards_reserve announced");
+  if (done != n) return fail(KNNX_E_NOMEM, "more rows added than knnx_shards_reserve announced");
   return KNNX_OK;
 }
 extern "C" int knnx_shards_add_f16(knnx_shards* s, const uint16_t* rows, int64_t n) { return shards_add(s, rows, n, false); }
 extern "C" int knnx_shards_add_f32(knnx_shards* s, const float* rows, int64_t n) { return shards_add(s, rows, n, true); }
 
 extern "C" int knnx_shards_synth_fill(knnx_shards* s, int64_t rows_per_shard, uint64_t seed) {
-  if (!s || rows_per_shard < 0) return knnx_set_error(KNNX_E_ARG, "bad shards_synth_fill arguments");
+  if (!s || rows_per_shard < 0) return fail(KNNX_E_ARG, "bad shards_synth_fill arguments");
   std::lock_guard<std::mutex> lk(s->mu);
   int64_t lo = 0;
   for (size_t g = 0; g < s->sh.size(); ++g) {
@@ -332,14 +300,14 @@ extern "C" int knnx_shards_synth_fill(knnx_shards* s, int64_t rows_per_shard, ui
 // k <= 64: scans on every device concurrently, peer copies to devices[0], merge there
 static int shards_search_fast(knnx_shards* s, const float* q, int n, int k, float* D, int64_t* I) {
   const int P = (int)s->sh.size(), d = s->d;
-  char* pin = (char*)s->pin;
+  char* pin = (char*)s->pin.p;
   for (int o = 0; o < n; o += s->cap_q) {
     const int nb = std::min(s->cap_q, n - o);
     memcpy(pin, q + (size_t)o * d, (size_t)nb * d * sizeof(float));
     for (int g = 0; g < P; ++g) {
       Shard& h = s->sh[g];
-      SHIP(hipSetDevice(h.device));
-      SHIP(hipMemcpyAsync(h.q, pin, (size_t)nb * d * sizeof(float), hipMemcpyHostToDevice, h.st));
+      HIPCHK(hipSetDevice(h.device));
+      HIPCHK(hipMemcpyAsync(h.q, pin, (size_t)nb * d * sizeof(float), hipMemcpyHostToDevice, h.st));
       int r = knnx_search_device(h.ix, h.q, nb, k, h.D, h.I, h.st);
       if (r) return r;
     }
@@ -359,9 +327,9 @@ static int shards_search_fast(knnx_shards* s, const float* q, int n, int k, floa
       const int rc2 = rccl().GroupEnd();
       if (rc == 0) rc = rc2;
       if (rc == 0) {
-        SHIP(hipSetDevice(s->sh[0].device));
-        SHIP(hipEventRecord(s->sh[0].ev, s->sh[0].st));
-        SHIP(hipStreamWaitEvent(s->st0, s->sh[0].ev, 0));
+        HIPCHK(hipSetDevice(s->sh[0].device));
+        HIPCHK(hipEventRecord(s->sh[0].ev, s->sh[0].st));
+        HIPCHK(hipStreamWaitEvent(s->st0, s->sh[0].ev, 0));
         partD = s->sh[0].agD;
         partI = s->sh[0].agI;
         gathered = true;
@@ -380,24 +348,24 @@ static int shards_search_fast(knnx_shards* s, const float* q, int n, int k, floa
       for (int g = 0; g < P; ++g) {
         Shard& h = s->sh[g];
         const size_t cnt = (size_t)nb * k;
-        SHIP(hipSetDevice(h.device));
+        HIPCHK(hipSetDevice(h.device));
         if (h.device == s->sh[0].device) {
-          SHIP(hipMemcpyAsync(s->gD + (size_t)g * cnt, h.D, cnt * sizeof(float), hipMemcpyDeviceToDevice, h.st));
-          SHIP(hipMemcpyAsync(s->gI + (size_t)g * cnt, h.I, cnt * sizeof(int64_t), hipMemcpyDeviceToDevice, h.st));
+          HIPCHK(hipMemcpyAsync(s->gD + (size_t)g * cnt, h.D, cnt * sizeof(float), hipMemcpyDeviceToDevice, h.st));
+          HIPCHK(hipMemcpyAsync(s->gI + (size_t)g * cnt, h.I, cnt * sizeof(int64_t), hipMemcpyDeviceToDevice, h.st));
         } else {
-          SHIP(hipMemcpyPeerAsync(s->gD + (size_t)g * cnt, s->sh[0].device, h.D, h.device, cnt * sizeof(float), h.st));
-          SHIP(hipMemcpyPeerAsync(s->gI + (size_t)g * cnt, s->sh[0].device, h.I, h.device, cnt * sizeof(int64_t), h.st));
+          HIPCHK(hipMemcpyPeerAsync(s->gD + (size_t)g * cnt, s->sh[0].device, h.D, h.device, cnt * sizeof(float), h.st));
+          HIPCHK(hipMemcpyPeerAsync(s->gI + (size_t)g * cnt, s->sh[0].device, h.I, h.device, cnt * sizeof(int64_t), h.st));
         }
-        SHIP(hipEventRecord(h.ev, h.st));
+        HIPCHK(hipEventRecord(h.ev, h.st));
       }
-      SHIP(hipSetDevice(s->sh[0].device));
-      for (int g = 0; g < P; ++g) SHIP(hipStreamWaitEvent(s->st0, s->sh[g].ev, 0));
+      HIPCHK(hipSetDevice(s->sh[0].device));
+      for (int g = 0; g < P; ++g) HIPCHK(hipStreamWaitEvent(s->st0, s->sh[g].ev, 0));
     }
     int r = knnx_merge_topk_device(s->sh[0].device, partD, partI, P, nb, k, s->mD, s->mI, s->st0);
     if (r) return r;
-    SHIP(hipMemcpyAsync(pin + s->pin_q, s->mD, (size_t)nb * k * sizeof(float), hipMemcpyDeviceToHost, s->st0));
-    SHIP(hipMemcpyAsync(pin + s->pin_q + s->pin_d, s->mI, (size_t)nb * k * sizeof(int64_t), hipMemcpyDeviceToHost, s->st0));
-    SHIP(hipStreamSynchronize(s->st0));
+    HIPCHK(hipMemcpyAsync(pin + s->pin_q, s->mD, (size_t)nb * k * sizeof(float), hipMemcpyDeviceToHost, s->st0));
+    HIPCHK(hipMemcpyAsync(pin + s->pin_q + s->pin_d, s->mI, (size_t)nb * k * sizeof(int64_t), hipMemcpyDeviceToHost, s->st0));
+    HIPCHK(hipStreamSynchronize(s->st0));
     memcpy(D + (size_t)o * k, pin + s->pin_q, (size_t)nb * k * sizeof(float));
     memcpy(I + (size_t)o * k, pin + s->pin_q + s->pin_d, (size_t)nb * k * sizeof(int64_t));
   }
@@ -415,29 +383,25 @@ static int shards_search_large(knnx_shards* s, const float* q, int n, int k, flo
     int r = knnx_search(s->sh[g].ix, q, n, k, hD.data() + g * cnt, hI.data() + g * cnt, nullptr);
     if (r) return r;
   }
-  SHIP(hipSetDevice(s->sh[0].device));
-  float *dD = nullptr, *oD = nullptr;
-  int64_t *dI = nullptr, *oI = nullptr;
-  SHIP(hipMalloc(&dD, P * cnt * sizeof(float)));
-  hipError_t e = hipMalloc(&dI, P * cnt * sizeof(int64_t));
-  if (e == hipSuccess) e = hipMalloc(&oD, cnt * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&oI, cnt * sizeof(int64_t));
+  HIPCHK(hipSetDevice(s->sh[0].device));
+  DevBuf<float> dD, oD;
+  DevBuf<int64_t> dI, oI;
+  HIPCHK(dD.alloc(P * cnt));
+  hipError_t e = dI.alloc(P * cnt);
+  dev_alloc(e, oD, cnt);
+  dev_alloc(e, oI, cnt);
   if (e == hipSuccess) e = hipMemcpyAsync(dD, hD.data(), P * cnt * sizeof(float), hipMemcpyHostToDevice, s->st0);
   if (e == hipSuccess) e = hipMemcpyAsync(dI, hI.data(), P * cnt * sizeof(int64_t), hipMemcpyHostToDevice, s->st0);
   if (e == hipSuccess) e = knnx::launch_merge_sorted(dD, dI, P, n, k, oD, oI, s->st0);
   if (e == hipSuccess) e = hipMemcpyAsync(D, oD, cnt * sizeof(float), hipMemcpyDeviceToHost, s->st0);
   if (e == hipSuccess) e = hipMemcpyAsync(I, oI, cnt * sizeof(int64_t), hipMemcpyDeviceToHost, s->st0);
   if (e == hipSuccess) e = hipStreamSynchronize(s->st0);
-  (void)hipFree(dD);
-  if (dI) (void)hipFree(dI);
-  if (oD) (void)hipFree(oD);
-  if (oI) (void)hipFree(oI);
-  if (e != hipSuccess) return knnx_set_error(KNNX_E_HIP, (std::string("sharded large-k merge: ") + hipGetErrorString(e)).c_str());
+  if (e != hipSuccess) return fail(KNNX_E_HIP, std::string("sharded large-k merge: ") + hipGetErrorString(e));
   return KNNX_OK;
 }
 
 extern "C" int knnx_shards_reconstruct(knnx_shards* s, const int64_t* ids, int64_t n, float* out) {
-  if (!s || (n > 0 && (!ids || !out)) || n < 0) return knnx_set_error(KNNX_E_ARG, "bad shards_reconstruct arguments");
+  if (!s || (n > 0 && (!ids || !out)) || n < 0) return fail(KNNX_E_ARG, "bad shards_reconstruct arguments");
   const int d = s->d;
   std::vector<int64_t> sub;
   std::vector<int64_t> pos;
@@ -465,8 +429,8 @@ extern "C" int knnx_shards_reconstruct(knnx_shards* s, const int64_t* ids, int64
 }
 
 extern "C" int knnx_shards_search(knnx_shards* s, const float* q, int n, int k, float* D, int64_t* I, float* R) {
-  if (!s || (n > 0 && (!q || !D || !I)) || n < 0 || k <= 0) return knnx_set_error(KNNX_E_ARG, "bad shards_search arguments");
-  if (k > KNNX_MAX_K) return knnx_set_error(KNNX_E_UNSUPPORTED, "k > 131072 is not implemented");
+  if (!s || (n > 0 && (!q || !D || !I)) || n < 0 || k <= 0) return fail(KNNX_E_ARG, "bad shards_search arguments");
+  if (k > KNNX_MAX_K) return fail(KNNX_E_UNSUPPORTED, "k > 131072 is not implemented");
   if (n == 0) return KNNX_OK;
   {
     std::lock_guard<std::mutex> lk(s->mu);
@@ -480,8 +444,8 @@ extern "C" int knnx_shards_search(knnx_shards* s, const float* q, int n, int k, 
 // range_search over the shards: shard order = ascending id order, so concatenating the per-shard hit lists of a query
 // keeps the "ids ascending inside each query" contract.  Same two-call protocol as knnx_range_search.
 extern "C" int knnx_shards_range_search(knnx_shards* s, const float* q, int n, float thresh, int64_t* lims, float* D, int64_t* I) {
-  if (!s || !lims || (n > 0 && !q) || n < 0) return knnx_set_error(KNNX_E_ARG, "bad shards_range_search arguments");
-  if ((D == nullptr) != (I == nullptr)) return knnx_set_error(KNNX_E_ARG, "D and I must both be null or both be set");
+  if (!s || !lims || (n > 0 && !q) || n < 0) return fail(KNNX_E_ARG, "bad shards_range_search arguments");
+  if ((D == nullptr) != (I == nullptr)) return fail(KNNX_E_ARG, "D and I must both be null or both be set");
   std::lock_guard<std::mutex> lk(s->mu);
   const int P = (int)s->sh.size();
   std::vector<std::vector<int64_t>> sl(P, std::vector<int64_t>((size_t)n + 1, 0));
@@ -510,7 +474,7 @@ extern "C" int knnx_shards_range_search(knnx_shards* s, const float* q, int n, f
     if (r) return r;
     for (int i = 0; i < n; ++i) {
       const int64_t c = sl[g][i + 1] - sl[g][i];
-      if (lims[i] + fill[i] + c > lims[i + 1]) return knnx_set_error(KNNX_E_STATE, "lims do not match this query/threshold");
+      if (lims[i] + fill[i] + c > lims[i + 1]) return fail(KNNX_E_STATE, "lims do not match this query/threshold");
       memcpy(D + lims[i] + fill[i], sd.data() + sl[g][i], (size_t)c * sizeof(float));
       memcpy(I + lims[i] + fill[i], si.data() + sl[g][i], (size_t)c * sizeof(int64_t));
       fill[i] += c;

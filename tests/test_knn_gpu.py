@@ -509,7 +509,7 @@ def test_ivf_flat_parity(n, d, nlist, nprobe):
     ix = build_ivf_index(x, nlist, nprobe=nprobe, centroids=cent)
     assert ix.ntotal == n and ix.nlist == nlist
     o = IVFFlatOracle(d, cent, ix.ivf_lists, x)
-    # more than 32 queries = ONE multi-block pass of up to 256 (round 6: knnx_api.hip scan_topk_ivf_multi); 300 = a pass of 256 + one of 44
+    # more than 32 queries = ONE multi-block pass of up to 256 (round 6: knnx_ivf.hip scan_topk_ivf_multi); 300 = a pass of 256 + one of 44
     for nq, k in [(1, 40), (7, 10), (32, 64), (45, 40), (64, 40), (200, 20), (256, 40), (300, 64)]:
         q = _queries(nq, d, seed=k + nq, x=x)
         D, I = ix.search(q, k)

@@ -84,6 +84,10 @@ SIGNATURES = {
     "knnx_ivfpq_m": (C.c_int, [_P]),
     "knnx_ivfpq_get_codes": (C.c_int, [_P, _P, _P, _P]),
     "knnx_ivfpq_get_codebooks": (C.c_int, [_P, _P]),
+    "knnx_ivfpq_set_rotation": (C.c_int, [_P, _P]),
+    "knnx_ivfpq_get_rotation": (C.c_int, [_P, _P]),
+    "knnx_rotate_f16_device": (C.c_int, [C.c_int, _P, _P, C.c_int64, C.c_int, _P, _P]),
+    "knnx_xty_device": (C.c_int, [C.c_int, _P, _P, C.c_int64, C.c_int, _P, _P]),
     "knnx_pqb_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "knnx_pqb_destroy": (None, [_P]),
     "knnx_pqb_set_sample": (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int]),

@@ -319,8 +319,182 @@ __global__ __launch_bounds__(256) void pq_scatter_codes_kernel(const uint8_t* __
 }
 
 // ---------------------------------------------------------------------------------------------
+// OPQ rotation A (f32 [d][d] row-major, y = A x) in front of the index: the small kernels around it.  (The row rotation of the build
+// is the MFMA kernel knn_rotate_kernel of knn_rq_kernels.hip.)
+// ---------------------------------------------------------------------------------------------
+// A -> W fp16 [2 d][d], the streamed operand of knn_rotate_kernel: rows 32 p .. 32 p + 31 of A become tile 2 p (2048 x the part fp16
+// cannot hold) and tile 2 p + 1 (fp16(A))
+__global__ __launch_bounds__(256) void rot_split_kernel(const float* __restrict__ A, int d, _Float16* __restrict__ W) {
+  const int j = blockIdx.x;
+  const size_t lo_row = (size_t)(j >> 5) * 64 + (j & 31), hi_row = lo_row + 32;
+  for (int c = threadIdx.x; c < d; c += 256) {
+    const float a = A[(size_t)j * d + c];
+    const _Float16 hi = (_Float16)a;
+    W[hi_row * d + c] = hi;
+    W[lo_row * d + c] = (_Float16)((a - (float)hi) * KNN_LO_SCALE);
+  }
+}
+
+// queries: out[i][j] = <A[j], q[i]> for nq <= 256 queries.  Workgroup g owns ROT_QJ rows of A (staged in the LDS once per launch: A is
+// read once however many queries there are) and its 4 waves walk the queries; lane l sums columns l, l + 64, ... in ascending order
+// (fmaf), then the 64 partial sums meet in a butterfly: a fixed order, so a query's rotation does not depend on its batch.
+constexpr int ROT_QJ = 4;
+template <int D>
+__global__ __launch_bounds__(256) void rot_query_kernel(const float* __restrict__ A, const float* __restrict__ q, int nq,
+                                                       float* __restrict__ out) {
+  __shared__ float sa[ROT_QJ][D];
+  const int j0 = blockIdx.x * ROT_QJ, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  for (int e = tid; e < ROT_QJ * D; e += 256) sa[e / D][e % D] = A[(size_t)j0 * D + e];
+  __syncthreads();
+  for (int i = w; i < nq; i += 4) {
+    float qv[D / 64];
+#pragma unroll
+    for (int s = 0; s < D / 64; ++s) qv[s] = q[(size_t)i * D + lane + 64 * s];
+    float acc[ROT_QJ];
+#pragma unroll
+    for (int r = 0; r < ROT_QJ; ++r) {
+      float a = 0.f;
+#pragma unroll
+      for (int s = 0; s < D / 64; ++s) a = fmaf(sa[r][lane + 64 * s], qv[s], a);
+      acc[r] = a;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1)
+#pragma unroll
+      for (int r = 0; r < ROT_QJ; ++r) acc[r] += __shfl_xor(acc[r], o);
+    if (lane == 0) {
+#pragma unroll
+      for (int r = 0; r < ROT_QJ; ++r) out[(size_t)i * D + j0 + r] = acc[r];
+    }
+  }
+}
+
+// back to the original space (reconstruct, the R of a search): out[i] = A^T dec[i], out[i][c] = sum_j A[j][c] dec[i][j] in fp32, j
+// ascending (fmaf).  A workgroup takes ROT_BR decoded rows into the LDS, thread c owns columns c, c + 256, ... of all of them: a row of A
+// is read once per ROT_BR output rows, coalesced.  dec rows of a bad id are 0xFF bytes (pq_decode_kernel) and stay 0xFF bytes.
+constexpr int ROT_BR = 8;
+template <int D>
+__global__ __launch_bounds__(256) void rot_back_kernel(const float* __restrict__ A, const float* __restrict__ dec, int64_t n,
+                                                      float* __restrict__ out) {
+  __shared__ float sy[ROT_BR][D];
+  __shared__ int bad[ROT_BR];
+  const int64_t i0 = (int64_t)blockIdx.x * ROT_BR;
+  const int tid = threadIdx.x;
+  for (int e = tid; e < ROT_BR * D; e += 256) {
+    const int64_t i = i0 + e / D;
+    sy[e / D][e % D] = i < n ? dec[(size_t)i * D + e % D] : 0.f;
+  }
+  __syncthreads();
+  if (tid < ROT_BR) bad[tid] = __float_as_int(sy[tid][0]) == -1 && __float_as_int(sy[tid][D - 1]) == -1;
+  __syncthreads();
+  constexpr int NC = D / 256;
+  float acc[ROT_BR][NC];
+#pragma unroll
+  for (int r = 0; r < ROT_BR; ++r)
+#pragma unroll
+    for (int u = 0; u < NC; ++u) acc[r][u] = 0.f;
+  for (int j = 0; j < D; ++j) {
+    float a[NC];
+#pragma unroll
+    for (int u = 0; u < NC; ++u) a[u] = A[(size_t)j * D + tid + 256 * u];
+#pragma unroll
+    for (int r = 0; r < ROT_BR; ++r) {
+      const float y = sy[r][j];
+#pragma unroll
+      for (int u = 0; u < NC; ++u) acc[r][u] = fmaf(a[u], y, acc[r][u]);
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < ROT_BR; ++r) {
+    if (i0 + r >= n) break;
+#pragma unroll
+    for (int u = 0; u < NC; ++u) out[(size_t)(i0 + r) * D + tid + 256 * u] = bad[r] ? __int_as_float(-1) : acc[r][u];
+  }
+}
+
+// OPQ training: G = X^T Y (f32 [d][d]) for fp16 rows X [n][d] and f32 rows Y [n][d] -- the matrix whose SVD gives the Procrustes
+// step.  Workgroup (bx, by) owns the 64 x 64 block G[64 by ..][64 bx ..], thread (ty, tx) a 4 x 4 piece of it; the n rows go through
+// the LDS 16 at a time and every element is ONE fmaf chain over the rows in ascending order: two runs give the same bits.
+__global__ __launch_bounds__(256) void xty_kernel(const _Float16* __restrict__ X, const float* __restrict__ Y, int64_t n, int d,
+                                                 float* __restrict__ G) {
+  __shared__ float sx[16][64], sy[16][64];
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+  const int c0 = blockIdx.x * 64, r0 = blockIdx.y * 64;
+  float acc[4][4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[a][b] = 0.f;
+  for (int64_t i0 = 0; i0 < n; i0 += 16) {
+    __syncthreads();
+    for (int e = tid; e < 16 * 64; e += 256) {
+      const int64_t i = i0 + e / 64;
+      sx[e / 64][e % 64] = i < n ? (float)X[(size_t)i * d + r0 + e % 64] : 0.f;
+      sy[e / 64][e % 64] = i < n ? Y[(size_t)i * d + c0 + e % 64] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      float xv[4], yv[4];
+#pragma unroll
+      for (int a = 0; a < 4; ++a) xv[a] = sx[k][4 * ty + a];
+#pragma unroll
+      for (int b = 0; b < 4; ++b) yv[b] = sy[k][4 * tx + b];
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) acc[a][b] = fmaf(xv[a], yv[b], acc[a][b]);
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) G[(size_t)(r0 + 4 * ty + a) * d + c0 + 4 * tx + b] = acc[a][b];
+}
+
+// ---------------------------------------------------------------------------------------------
 // host-side launchers (declared in knn_kernels.h)
 // ---------------------------------------------------------------------------------------------
+static bool rot_supported(int d) { return d == 256 || d == 512 || d == 768 || d == 1024; }
+
+hipError_t launch_rot_split(const float* A, int d, _Float16* W, hipStream_t st) {
+  if (!rot_supported(d)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(rot_split_kernel, dim3((unsigned)d), dim3(256), 0, st, A, d, W);
+  return hipGetLastError();
+}
+
+#define ROT_BY_D(CALL)          \
+  switch (d) {                  \
+    case 256: CALL(256); break; \
+    case 512: CALL(512); break; \
+    case 768: CALL(768); break; \
+    case 1024: CALL(1024); break; \
+    default: return hipErrorInvalidValue; \
+  }
+
+hipError_t launch_rot_queries(const float* A, int d, const float* q, int nq, float* out, hipStream_t st) {
+  if (nq <= 0) return hipSuccess;
+#define ROT_Q(DD) hipLaunchKernelGGL(rot_query_kernel<DD>, dim3((unsigned)(DD / ROT_QJ)), dim3(256), 0, st, A, q, nq, out)
+  ROT_BY_D(ROT_Q)
+#undef ROT_Q
+  return hipGetLastError();
+}
+
+hipError_t launch_rot_back(const float* A, int d, const float* dec, int64_t n, float* out, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+#define ROT_B(DD) hipLaunchKernelGGL(rot_back_kernel<DD>, dim3((unsigned)((n + ROT_BR - 1) / ROT_BR)), dim3(256), 0, st, A, dec, n, out)
+  ROT_BY_D(ROT_B)
+#undef ROT_B
+  return hipGetLastError();
+}
+#undef ROT_BY_D
+
+hipError_t launch_xty(const _Float16* X, const float* Y, int64_t n, int d, float* G, hipStream_t st) {
+  if (n <= 0 || !rot_supported(d)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(xty_kernel, dim3((unsigned)(d / 64), (unsigned)(d / 64)), dim3(256), 0, st, X, Y, n, d, G);
+  return hipGetLastError();
+}
+
 bool pq_supported(int d, int M) {
   return (M == 16 || M == 32 || M == 64 || M == 128) && d % 256 == 0 && d > 0 && d <= 1024 && d % M == 0 && d / M <= 64;
 }

@@ -1188,6 +1188,113 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void knn_assign_kernel(const _Floa
     if (hb == 0 && pidx[b] < n) out[pidx[b]] = brow[b];
   }
 }
+
+// ---------------------------------------------------------------------------------------------
+// OPQ row rotation (the transform in front of IVF-PQ: faiss OPQMatrix, d_out = d_in): Y[i] = fp16(A X[i]), 2 n d^2 x 2 flops.
+// The assignment kernel with another epilogue: a workgroup keeps its NW x 32 points stationary and streams the rows of A through
+// the LDS ring; the score of (point i, row j of A) IS y_ij, and every score is stored instead of the arg-max.  fp16 A would be
+// orthonormal to 1e-3 only, so A travels as W = fp16 [2 d][d], 32-row tiles in pairs: tile 2 p = 2048 x (A - hi) rows 32 p .. 32 p + 31
+// (the "lo" part, scaled like the scans' query split), tile 2 p + 1 = hi = fp16(A) of the same rows.  The lo tile is multiplied first,
+// its fp32 sums are scaled by 2^-11 (exact) and the hi tile accumulates on top: one fp32 accumulator, one rounding to fp16.
+// A lane ends a pair with 4 consecutive columns of each of its points' rows per 16-row half: 8-byte stores, which the NEXT tile
+// issues behind its barrier -- vmcnt counts stores and the DMA pieces in issue order, so the wait at the top of a tile (all but the
+// newest DMA pieces) then covers stores that have had a whole tile to retire instead of ones issued a moment ago.
+// ---------------------------------------------------------------------------------------------
+typedef _Float16 half4 __attribute__((ext_vector_type(4)));
+template <int KS, int NW, int NSLOT>
+__global__ __launch_bounds__(NW * 64, NW / 4) void knn_rotate_kernel(const _Float16* __restrict__ W, const _Float16* __restrict__ P,
+                                                                     int64_t n, _Float16* __restrict__ Y) {
+  constexpr int D = KS * 16;
+  constexpr int TILE_BYTES = KS * 1024;
+  constexpr int DPW = KS / NW;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  constexpr int NQB = RQ_NQB(1), NSL = RQ_NSL(KS), QBS = KNNX_MFMA16 ? 16 : 32;
+  constexpr int NSC = KNNX_MFMA16 ? 8 : 16, NG = NSC / 4;
+  const int qcol = lane & (QBS - 1), hb = lane / QBS;
+  const _Float16* X = W;  // the streamed operand (RQ_TILE below)
+  constexpr int64_t N = 2 * D;
+
+  int64_t pidx[NQB];
+  half8 Q[NQB][NSL];
+#pragma unroll
+  for (int b = 0; b < NQB; ++b) {
+    pidx[b] = (int64_t)blockIdx.x * (NW * 32) + w * 32 + b * QBS + qcol;
+    const int64_t prow = pidx[b] < n ? pidx[b] : n - 1;
+    const half8* src = reinterpret_cast<const half8*>(P + (size_t)prow * D) + hb;
+#pragma unroll
+    for (int s = 0; s < NSL; ++s) Q[b][s] = src[(KNNX_MFMA16 ? 4 : 2) * s];
+  }
+#pragma unroll
+  for (int b = 0; b < NQB; ++b)
+#pragma unroll
+    for (int s = 0; s < NSL; ++s) asm volatile("" : "+v"(Q[b][s]));  // all landed before the DMA ring starts (see the scan)
+
+  constexpr int64_t ntile = N / 32;  // = KS, no ragged tile (d % 256 == 0)
+  constexpr int64_t last = ntile - 1;
+  const RqLaneOff lane_off = rq_lane_offsets(lane, D, 31);
+  const unsigned lds_base = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem);
+
+#pragma unroll
+  for (int i = 0; i < NSLOT - 1; ++i) rq_issue_all<NW, DPW>(RQ_TILE((int64_t)i, i));
+
+  rq_acc_t acc[NQB];
+  half4 pend[NQB][NG];  // the finished pair's outputs, stored by the next tile
+  int slot = 0;
+  for (int64_t t = 0; t < ntile; ++t) {
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DPW * (NSLOT - 2)) : "memory");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+    const RqTile refill = RQ_TILE(t + (NSLOT - 1), slot == 0 ? NSLOT - 1 : slot - 1);
+    if ((t & 1) == 0) {
+      if (t > 0) {
+        const int col0 = (int)(t >> 1) * 32 - 32 + 4 * hb;
+#pragma unroll
+        for (int b = 0; b < NQB; ++b)
+#pragma unroll
+          for (int g = 0; g < NG; ++g)
+            if (pidx[b] < n) *reinterpret_cast<half4*>(Y + (size_t)pidx[b] * D + col0 + RQ_ROWOFF(4 * g)) = pend[b][g];
+      }
+#if KNNX_MFMA16
+#pragma unroll
+      for (int b = 0; b < NQB; ++b) acc[b][0] = acc[b][1] = float4v{0.f, 0.f, 0.f, 0.f};
+#else
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[0][r] = 0.f;
+#endif
+    } else {
+#pragma unroll
+      for (int b = 0; b < NQB; ++b)
+#pragma unroll
+        for (int r = 0; r < NSC; ++r) RQ_SCORE(b, r) *= KNN_LO_INV;
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    const unsigned xa = lds_base + slot * TILE_BYTES + lane * 16;
+    i32x4 A[4];
+    rq_dsread<0>(A[0], xa);
+    rq_dsread<1024>(A[1], xa);
+    rq_dsread<2048>(A[2], xa);
+    __builtin_amdgcn_sched_barrier(0);
+    rq_ksteps<KS, 1, NW, DPW, 0>(xa, A, acc, Q, refill);
+    if (t & 1) {
+#pragma unroll
+      for (int b = 0; b < NQB; ++b)
+#pragma unroll
+        for (int g = 0; g < NG; ++g)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) pend[b][g][e] = (_Float16)RQ_SCORE(b, 4 * g + e);
+    }
+    slot = slot + 1 == NSLOT ? 0 : slot + 1;
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // tail reloads still in flight
+  const int col0 = (int)(ntile >> 1) * 32 - 32 + 4 * hb;
+#pragma unroll
+  for (int b = 0; b < NQB; ++b)
+#pragma unroll
+    for (int g = 0; g < NG; ++g)
+      if (pidx[b] < n) *reinterpret_cast<half4*>(Y + (size_t)pidx[b] * D + col0 + RQ_ROWOFF(4 * g)) = pend[b][g];
+}
 #undef RQ_SCORE
 #undef RQ_ROWOFF
 
@@ -1210,6 +1317,29 @@ hipError_t launch_assign(const _Float16* C, int64_t nlist, int d, const _Float16
     case 512: return launch_assign_cfg<32, 8, 3>(C, nlist, P, n, out, st);
     case 768: return launch_assign_cfg<48, 8, 3>(C, nlist, P, n, out, st);
     case 1024: return launch_assign_cfg<64, 4, 2>(C, nlist, P, n, out, st);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+template <int KS, int NW, int NSLOT>
+static hipError_t launch_rotate_cfg(const _Float16* W, const _Float16* P, int64_t n, _Float16* Y, hipStream_t st) {
+  const size_t smem = (size_t)NSLOT * KS * 1024;
+  auto kern = knn_rotate_kernel<KS, NW, NSLOT>;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  if (e != hipSuccess) return e;
+  const int64_t per = NW * 32;
+  hipLaunchKernelGGL(kern, dim3((unsigned)((n + per - 1) / per)), dim3(NW * 64), smem, st, W, P, n, Y);
+  return hipGetLastError();
+}
+
+// Y[i] = fp16(A P[i]) for n fp16 rows; W = the hi / lo tile image of A (launch_rot_split); Y must not overlap P
+hipError_t launch_rotate_f16(const _Float16* W, int d, const _Float16* P, int64_t n, _Float16* Y, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  switch (d) {
+    case 256: return launch_rotate_cfg<16, 8, 3>(W, P, n, Y, st);
+    case 512: return launch_rotate_cfg<32, 8, 3>(W, P, n, Y, st);
+    case 768: return launch_rotate_cfg<48, 8, 3>(W, P, n, Y, st);
+    case 1024: return launch_rotate_cfg<64, 4, 2>(W, P, n, Y, st);
     default: return hipErrorInvalidValue;
   }
 }

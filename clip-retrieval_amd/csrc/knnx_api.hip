@@ -861,8 +861,8 @@ static int co_run_batch_locked(knnx_index* ix, std::vector<CoReq*>& b) {
     memcpy(ix->pin.p, ix->co.Ibuf.data(), (size_t)nrow * sizeof(int64_t));
     HIPCHK(hipMemcpyAsync(ids_dev, ix->pin.p, (size_t)nrow * sizeof(int64_t), hipMemcpyHostToDevice, st));
     HIPCHK(hipStreamSynchronize(st));  // the pinned buffer is reused below
-    hipError_t e = ix->pq.m ? launch_pq_decode(ix->pq.codes, d, ix->pq.m, ix->pq.cb, ix->cent ? ix->cent->rows : nullptr, ix->ivf.tile0,
-                                               ix->ivf_nlist, ix->id_base, ix->ntotal, ix->ivf.inv, ids_dev, nrow, rows_dev, st)
+    if (ix->pq.m && (r = pq_decode_rows(ix, ids_dev, nrow, rows_dev, st))) return r;
+    hipError_t e = ix->pq.m ? hipSuccess
                    : ix->ivf_nlist ? launch_gather_inv(ix->rows, d, ix->id_base, ix->ntotal, ix->ivf.inv, ids_dev, nrow, rows_dev, st)
                                    : launch_gather(ix->rows, ix->ntotal, d, ix->id_base, ids_dev, nrow, rows_dev, st);
     if (e != hipSuccess) return fail(KNNX_E_HIP, std::string("coalesced gather: ") + hipGetErrorString(e));
@@ -1025,9 +1025,9 @@ extern "C" int knnx_reconstruct(knnx_index* ix, const int64_t* ids, int64_t n, f
     const int64_t m = std::min(chunk, n - o);
     memcpy(ids_pin, ids + o, (size_t)m * sizeof(int64_t));
     e = hipMemcpyAsync(ids_dev, ids_pin, (size_t)m * sizeof(int64_t), hipMemcpyHostToDevice, ix->stream);
+    if (e == hipSuccess && ix->pq.m && (r = pq_decode_rows(ix, ids_dev, m, out_dev, ix->stream))) return r;
     if (e == hipSuccess)
-      e = ix->pq.m ? launch_pq_decode(ix->pq.codes, ix->d, ix->pq.m, ix->pq.cb, ix->cent ? ix->cent->rows : nullptr, ix->ivf.tile0, ix->ivf_nlist,
-                                      ix->id_base, ix->ntotal, ix->ivf.inv, ids_dev, m, out_dev, ix->stream)
+      e = ix->pq.m ? hipSuccess
           : ix->ivf_nlist ? launch_gather_inv(ix->rows, ix->d, ix->id_base, ix->ntotal, ix->ivf.inv, ids_dev, m, out_dev, ix->stream)
                           : launch_gather(ix->rows, ix->ntotal, ix->d, ix->id_base, ids_dev, m, out_dev, ix->stream);
     if (e == hipSuccess)

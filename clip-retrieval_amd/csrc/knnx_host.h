@@ -348,6 +348,7 @@ struct IvfBuild {
   std::vector<uint16_t> cent;
   // device staging of one chunk
   DevBuf<_Float16> rows;  // [IVFB_CHUNK, d] (knnx_ivfpq_add_codes stages its code bytes here: M <= 2 d)
+  DevBuf<_Float16> rot;   // [IVFB_CHUNK, d] the chunk rotated, what the encoder reads (IVF-PQ with a rotation only)
   DevBuf<int64_t> ids;
   DevBuf<int32_t> lists, pos;
   // host mirror of the layout, so that every (list, position) a caller hands over is checked before it is scattered
@@ -364,6 +365,10 @@ struct PqData {
   DevBuf<uint8_t> codes;                 // [capacity][M]
   DevBuf<_Float16> bcent;                // centroids during the build (knnx_ivf_begin .. knnx_ivf_end)
   std::vector<unsigned> tile0_h, size_h; // host copy of the layout (knnx_ivfpq_get_codes)
+  // OPQ rotation (knnx_ivfpq_set_rotation; empty: none): y = A x in front of everything above
+  std::vector<float> rot_h;              // A, f32 [d][d] (knnx_ivfpq_get_rotation, knnx_shards_adopt)
+  DevBuf<float> rot;                     // the same on the device (queries, back-rotation)
+  DevBuf<_Float16> rot_w;                // [2 d][d] hi / lo tile image (row rotation of the build; released by knnx_ivf_end)
 };
 // one IVF-PQ search pass of up to PQ_PASS queries, allocated on first use
 struct PqScratch {
@@ -379,6 +384,7 @@ struct PqScratch {
   DevBuf<float> part_s;     // [PQ_SLOTS][64] per-workgroup top-k of the ADC scan
   DevBuf<uint32_t> part_i;
   DevBuf<int> part_n;       // [PQ_SLOTS]
+  DevBuf<float> qrot;       // [256][d] the rotated queries (allocated by scan_topk_pq when the index has a rotation)
   // (a larger nprobe than any before regrows probe / pscore only)
   hipError_t alloc(int d, size_t nl, int m, int np) {
     if (qfrag && np <= np_cap) return hipSuccess;
@@ -530,6 +536,8 @@ int scan_topk_ivf_multi(knnx_index* ix, const float* q_dev, int nq, int k, float
 bool ivfb_claim_all(knnx_index* ix, const int32_t* lists, const int32_t* pos, int64_t n);
 // knnx_ivfpq.hip
 int scan_topk_pq(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out, int64_t* I_out, hipStream_t st);
+// decoded rows of n ids (device) -> out f32 [n][d] in the ORIGINAL space (back-rotated when the index has a rotation; scratch slot 5)
+int pq_decode_rows(knnx_index* ix, const int64_t* ids_dev, int64_t n, float* out_dev, hipStream_t st);
 
 // the int8 copy is an accelerator, not data: whoever needs device memory and cannot get it takes the copy's back and tries once more
 // (the lazily built copy must not starve the range pools / large-k scratch that fitted before it existed)

@@ -473,6 +473,7 @@ extern "C" int knnx_ivf_begin(knnx_index* ix, int nlist, const uint16_t* centroi
   }
   if (e == hipSuccess) e = hipMemsetAsync(ix->ivf.idmap, 0xFF, (size_t)prow * sizeof(int64_t), ix->stream);  // -1 on pad rows
   dev_alloc(e, B.rows, (size_t)IVFB_CHUNK * ix->d);
+  if (ix->pq.rot) dev_alloc(e, B.rot, (size_t)IVFB_CHUNK * ix->d);
   dev_alloc(e, B.ids, (size_t)IVFB_CHUNK);
   dev_alloc(e, B.lists, (size_t)IVFB_CHUNK);
   dev_alloc(e, B.pos, (size_t)IVFB_CHUNK);
@@ -555,8 +556,9 @@ extern "C" int knnx_ivf_add_assigned(knnx_index* ix, const uint16_t* rows_f16, i
     HIPCHK(hipMemcpyAsync(ix->ivfb.ids, p_ids, (size_t)m * 8, hipMemcpyHostToDevice, ix->stream));
     HIPCHK(hipMemcpyAsync(ix->ivfb.lists, p_lists, (size_t)m * 4, hipMemcpyHostToDevice, ix->stream));
     HIPCHK(hipMemcpyAsync(ix->ivfb.pos, p_pos, (size_t)m * 4, hipMemcpyHostToDevice, ix->stream));
-    if (ix->pq.m) {  // IVF-PQ: the rows are encoded into their slots, not copied
-      HIPCHK(launch_pq_encode(ix->ivfb.rows, m, ix->d, ix->pq.m, ix->ivfb.lists, ix->pq.bcent, ix->pq.cb,
+    if (ix->pq.m) {  // IVF-PQ: the rows are encoded into their slots, not copied (OPQ: rotated first)
+      if (ix->pq.rot) HIPCHK(launch_rotate_f16(ix->pq.rot_w, ix->d, ix->ivfb.rows, m, ix->ivfb.rot, ix->stream));
+      HIPCHK(launch_pq_encode(ix->pq.rot ? ix->ivfb.rot.p : ix->ivfb.rows.p, m, ix->d, ix->pq.m, ix->ivfb.lists, ix->pq.bcent, ix->pq.cb,
                               ix->ivf.tile0, ix->ivfb.pos, ix->ivfb.ids, 0, ix->id_base, ix->ivfb.total,
                               ix->pq.codes, ix->ivf.idmap, ix->ivf.inv, ix->stream));
     } else {
@@ -618,7 +620,8 @@ extern "C" int knnx_ivf_add_assigned_device(knnx_index* ix, const void* rows_dev
     HIPCHK(hipMemcpyAsync(ix->ivfb.pos, h_pos, (size_t)m * 4, hipMemcpyHostToDevice, ix->stream));
     const _Float16* src = (const _Float16*)rows_dev + (size_t)o * ix->d;
     if (ix->pq.m) {
-      HIPCHK(launch_pq_encode(src, m, ix->d, ix->pq.m, lists_dev + o, ix->pq.bcent, ix->pq.cb, ix->ivf.tile0, ix->ivfb.pos,
+      if (ix->pq.rot) HIPCHK(launch_rotate_f16(ix->pq.rot_w, ix->d, src, m, ix->ivfb.rot, ix->stream));
+      HIPCHK(launch_pq_encode(ix->pq.rot ? ix->ivfb.rot.p : src, m, ix->d, ix->pq.m, lists_dev + o, ix->pq.bcent, ix->pq.cb, ix->ivf.tile0, ix->ivfb.pos,
                               nullptr, id0 + o, ix->id_base, ix->ivfb.total, ix->pq.codes, ix->ivf.idmap, ix->ivf.inv, ix->stream));
     } else {
       HIPCHK(launch_ivf_scatter(src, m, ix->d, lists_dev + o, ix->ivfb.pos, nullptr, id0 + o, ix->ivf.tile0, ix->id_base,
@@ -646,12 +649,13 @@ extern "C" int knnx_ivf_end(knnx_index* ix) {
       ix->pq.tile0_h.assign(ix->ivfb.tile0.begin(), ix->ivfb.tile0.end());
       ix->pq.size_h.assign(ix->ivfb.size.begin(), ix->ivfb.size.end());
       ix->pq.bcent.reset();
+      ix->pq.rot_w.reset();
     }
     std::vector<uint32_t>().swap(ix->ivfb.size);
     std::vector<uint32_t>().swap(ix->ivfb.fill);
     std::vector<uint32_t>().swap(ix->ivfb.tile0);
     std::vector<uint64_t>().swap(ix->ivfb.taken);
-    ix->ivfb.rows.reset(), ix->ivfb.ids.reset(), ix->ivfb.lists.reset(), ix->ivfb.pos.reset();
+    ix->ivfb.rows.reset(), ix->ivfb.rot.reset(), ix->ivfb.ids.reset(), ix->ivfb.lists.reset(), ix->ivfb.pos.reset();
   }
   int r = knnx_create(ix->device, ix->d, KNNX_METRIC_INNER_PRODUCT, &ix->cent);
   if (r) return r;

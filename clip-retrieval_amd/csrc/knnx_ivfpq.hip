@@ -15,6 +15,11 @@ int scan_topk_pq(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out
   HIPCHK(ix->pqs.alloc(ix->d, (size_t)ix->ivf_nlist, ix->pq.m, np));
   knnx_index* c = ix->cent;
   const int nblk = (nq + KNN_NQ - 1) / KNN_NQ;
+  if (ix->pq.rot) {  // OPQ: everything below sees q' = A q
+    if (!ix->pqs.qrot) HIPCHK(ix->pqs.qrot.alloc((size_t)PQ_PASS * ix->d));
+    HIPCHK(launch_rot_queries(ix->pq.rot, ix->d, q_dev, nq, ix->pqs.qrot, st));
+    q_dev = ix->pqs.qrot;
+  }
   HIPCHK(launch_prep_blocks(q_dev, nq, ix->d, ix->pqs.qfrag, ix->pqs.thr, ix->pqs.thr + PQ_PASS, st));
   ScanArgs ca{};
   ca.X = c->rows;
@@ -64,6 +69,97 @@ extern "C" int knnx_ivfpq_set_quantizer(knnx_index* ix, int M, const float* code
 }
 
 extern "C" int knnx_ivfpq_m(const knnx_index* ix) { return ix ? ix->pq.m : 0; }
+
+// ---- OPQ rotation (faiss IndexPreTransform(OPQMatrix(d, M), IndexIVFPQ), d_out = d_in) --------------------------------------------
+// A f32 [d][d] row-major, y = A x.  Orthonormal or refused: max |A A^T - I| <= 1e-3, checked in float64 on the host (d^3 <= 1e9
+// multiply-adds, once per index).
+extern "C" int knnx_ivfpq_set_rotation(knnx_index* ix, const float* A) {
+  if (!ix || !A) return fail(KNNX_E_ARG, "bad ivfpq_set_rotation arguments");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  if (set_dev(ix)) return KNNX_E_HIP;
+  if (!ix->pq.m || ix->ntotal != 0 || ix->ivf_nlist || ix->ivfb.nlist)
+    return fail(KNNX_E_STATE, "the rotation is set on an IVF-PQ index after knnx_ivfpq_set_quantizer and before knnx_ivf_begin");
+  const int d = ix->d;
+  double worst = 0.0;
+  for (int i = 0; i < d; ++i)
+    for (int j = i; j < d; ++j) {
+      const float *a = A + (size_t)i * d, *b = A + (size_t)j * d;
+      double s = 0.0;
+      for (int c = 0; c < d; ++c) s += (double)a[c] * (double)b[c];
+      const double e = fabs(s - (i == j ? 1.0 : 0.0));
+      if (!(e <= worst)) worst = e;  // (a NaN lands here too)
+    }
+  if (!(worst <= 1e-3)) return fail(KNNX_E_ARG, "the rotation is not orthonormal (max |A A^T - I| > 1e-3)");
+  hipError_t e = hipSuccess;
+  dev_alloc(e, ix->pq.rot, (size_t)d * d);
+  dev_alloc(e, ix->pq.rot_w, (size_t)2 * d * d);
+  if (e == hipSuccess) e = hipMemcpy(ix->pq.rot, A, (size_t)d * d * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = launch_rot_split(ix->pq.rot, d, ix->pq.rot_w, ix->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ix->stream);
+  if (e != hipSuccess) {
+    ix->pq.rot.reset();
+    ix->pq.rot_w.reset();
+    ix->pq.rot_h.clear();
+    HIPCHK(e);
+  }
+  ix->pq.rot_h.assign(A, A + (size_t)d * d);
+  return KNNX_OK;
+}
+
+// 0 and the matrix, or 1 (A untouched) when the index has no rotation
+extern "C" int knnx_ivfpq_get_rotation(knnx_index* ix, float* A) {
+  if (!ix || !A) return fail(KNNX_E_ARG, "bad ivfpq_get_rotation arguments");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  if (ix->pq.rot_h.empty()) return 1;
+  memcpy(A, ix->pq.rot_h.data(), ix->pq.rot_h.size() * sizeof(float));
+  return KNNX_OK;
+}
+
+// The stand-alone row rotation: out[i] = fp16(A rows[i]) for n fp16 rows in HBM (the OPQ trainer, the device-streamed build's
+// assignment pass).  A: host f32 [d][d] (not checked for orthonormality: the trainer's iterates are what they are); out must not
+// overlap rows.  Synchronous.
+extern "C" int knnx_rotate_f16_device(int device, const float* A_host, const void* rows_dev_f16, int64_t n, int d, void* out_dev_f16,
+                                      void* stream) {
+  if (!A_host || (n > 0 && (!rows_dev_f16 || !out_dev_f16)) || n < 0) return fail(KNNX_E_ARG, "bad rotate_f16_device arguments");
+  if (d != 256 && d != 512 && d != 768 && d != 1024) return fail(KNNX_E_ARG, "the rotation takes d in {256, 512, 768, 1024}");
+  if (n == 0) return KNNX_OK;
+  HIPCHK(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  DevBuf<float> A;
+  DevBuf<_Float16> W;
+  HIPCHK(A.alloc((size_t)d * d));
+  HIPCHK(W.alloc((size_t)2 * d * d));
+  HIPCHK(hipMemcpyAsync(A, A_host, (size_t)d * d * sizeof(float), hipMemcpyHostToDevice, st));
+  HIPCHK(launch_rot_split(A, d, W, st));
+  for (int64_t o = 0; o < n; o += IVFB_CHUNK)
+    HIPCHK(launch_rotate_f16(W, d, (const _Float16*)rows_dev_f16 + (size_t)o * d, std::min(IVFB_CHUNK, n - o),
+                             (_Float16*)out_dev_f16 + (size_t)o * d, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return KNNX_OK;
+}
+
+// G = X^T Y (f32 [d][d], device) for fp16 rows X and f32 rows Y [n][d] in HBM: the d x d product of an OPQ iteration, every element
+// one fp32 sum over the rows in ascending order.  Synchronous.
+extern "C" int knnx_xty_device(int device, const void* x_dev_f16, const float* y_dev_f32, int64_t n, int d, float* g_dev, void* stream) {
+  if (!x_dev_f16 || !y_dev_f32 || !g_dev || n <= 0) return fail(KNNX_E_ARG, "bad xty_device arguments");
+  if (d != 256 && d != 512 && d != 768 && d != 1024) return fail(KNNX_E_ARG, "xty takes d in {256, 512, 768, 1024}");
+  HIPCHK(hipSetDevice(device));
+  HIPCHK(launch_xty((const _Float16*)x_dev_f16, y_dev_f32, n, d, g_dev, (hipStream_t)stream));
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  return KNNX_OK;
+}
+
+int pq_decode_rows(knnx_index* ix, const int64_t* ids_dev, int64_t n, float* out_dev, hipStream_t st) {
+  float* dec = out_dev;
+  if (ix->pq.rot) {
+    int r = ensure_scratch(ix, 5, (size_t)n * ix->d * sizeof(float), (void**)&dec);
+    if (r) return r;
+  }
+  HIPCHK(launch_pq_decode(ix->pq.codes, ix->d, ix->pq.m, ix->pq.cb, ix->cent ? ix->cent->rows : nullptr, ix->ivf.tile0, ix->ivf_nlist,
+                          ix->id_base, ix->ntotal, ix->ivf.inv, ids_dev, n, dec, st));
+  if (ix->pq.rot) HIPCHK(launch_rot_back(ix->pq.rot, ix->d, dec, n, out_dev, st));
+  return KNNX_OK;
+}
 
 extern "C" int knnx_ivfpq_get_codebooks(knnx_index* ix, float* codebooks) {
   if (!ix || !codebooks) return fail(KNNX_E_ARG, "bad ivfpq_get_codebooks arguments");

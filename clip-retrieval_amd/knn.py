@@ -239,6 +239,25 @@ class Mi355xIndex(_FaissShaped):
         check(self._lib, self._lib.knnx_ivfpq_get_codebooks(self._h, out.ctypes.data), "knnx")
         return out
 
+    def set_pq_rotation(self, A):
+        """OPQ rotation in front of this IVF-PQ index (faiss IndexPreTransform(OPQMatrix(d, M), IndexIVFPQ)): A f32 [d, d], y = A x,
+        orthonormal (max |A A^T - I| <= 1e-3) or refused.  After set_pq_quantizer, before the rows go in.  Callers keep passing and
+        receiving UN-ROTATED vectors: the index rotates rows and queries itself and reconstructs into the original space."""
+        A = np.asarray(A, dtype=np.float32)
+        if A.shape != (self.d, self.d):
+            raise AssertionError(f"the rotation must be [{self.d}, {self.d}], got {A.shape}")
+        Ap = _pad_rotation(A, self._dpad)
+        check(self._lib, self._lib.knnx_ivfpq_set_rotation(self._h, Ap.ctypes.data), "knnx")
+
+    def pq_rotation(self):
+        """The OPQ rotation f32 [d, d], or None when the index has none."""
+        out = np.empty((self._dpad, self._dpad), dtype=np.float32)
+        rc = self._lib.knnx_ivfpq_get_rotation(self._h, out.ctypes.data)
+        if rc == 1:
+            return None
+        check(self._lib, rc, "knnx")
+        return np.ascontiguousarray(out[: self.d, : self.d])
+
     def pq_codes(self):
         """(codes u8 [ntotal, M], lists int32 [ntotal]) in id order: row i belongs to id id_base + i."""
         n, M = self.ntotal, self.pq_m
@@ -386,7 +405,8 @@ class ShardedMi355xIndex(_FaissShaped):
 
     @classmethod
     def from_shards(cls, shards, row_lo, coalesce=True):
-        """Adopt per-device `Mi355xIndex` objects (flat or IVF-Flat; shard g built with id_base = row_lo[g])."""
+        """Adopt per-device `Mi355xIndex` objects (flat, IVF-Flat or IVF-PQ -- all with the same rotation or none; shard g built with
+        id_base = row_lo[g])."""
         return cls(shards[0].d, [sh.device for sh in shards], coalesce=coalesce, _adopt=(shards, row_lo))
 
     def close(self):
@@ -1065,11 +1085,12 @@ def _load_ivf_index(folder, device=0, row_range=None, devices=None, embeddings_f
 
 # ------------------------------------------------------------------------------------------------------------
 # IVF-PQ (faiss IndexIVFPQ(IndexFlatIP(d), d, nlist, M, 8), METRIC_INNER_PRODUCT, by_residual): what autofaiss builds for large
-# corpora (clip_index.py:12-66; the reference notebook's OPQ256_768,IVF16384_HNSW32,PQ256x8 without OPQ / HNSW).  The coarse
+# corpora (clip_index.py:12-66; the reference notebook's OPQ256_768,IVF16384_HNSW32,PQ256x8 without HNSW; OPQ: train_opq below).  The coarse
 # quantiser is the IVF-Flat one; every row is kept as M code bytes (csrc/knn_pq_kernels.hip), so 1 B x 768 fits one GPU.
 # ------------------------------------------------------------------------------------------------------------
 PQ_SAMPLE_ROWS = 256 * 256  # rows of the codebook training sample (faiss: 256 x ksub)
 IVFPQ_MANIFEST = "ivf_pq_manifest.json"
+IVFPQ_ROTATION = "ivf_pq_rotation.npy"
 IVFPQ_FORMAT = "clip-retrieval_amd ivf-pq v1"
 
 
@@ -1166,13 +1187,144 @@ def train_pq_codebooks(builder, niter=10, seed=0):
     return builder.codebooks()
 
 
-def train_ivfpq(x_f16, nlist, M, niter=8, pq_niter=10, seed=0, device=0, sample_rows=PQ_SAMPLE_ROWS, centroids=None,
-                max_points_per_centroid=256):
-    """faiss IndexIVFPQ.train order: the coarse centroids first (the spherical k-means of train_ivf_centroids; `centroids=` skips it),
-    then the M sub-quantisers on the residuals of a sample of <= sample_rows rows against their lists.  Returns (centroids fp16
-    [nlist, d], codebooks f32 [M, 256, d_padded / M])."""
+# ------------------------------------------------------------------------------------------------------------
+# OPQ: the learned rotation in front of IVF-PQ (faiss OPQMatrix, d_out = d_in; what autofaiss puts in front of every IVF-PQ index,
+# clip_index.py:12-66).  The device does the arithmetic over rows (rotation: the MFMA kernel knn_rotate_kernel; PQ Lloyd: PqBuilder;
+# X^T Y: xty_kernel); the host takes the SVD of one d x d matrix per iteration.
+# ------------------------------------------------------------------------------------------------------------
+OPQ_SAMPLE_ROWS = 65536
+
+
+def _pad_rotation(A, dpad):
+    """[d, d] -> [dpad, dpad]: the zero pad columns of the rows map onto themselves."""
+    A = np.asarray(A, dtype=np.float32)
+    d = A.shape[0]
+    if d == dpad:
+        return np.ascontiguousarray(A)
+    out = np.eye(dpad, dtype=np.float32)
+    out[:d, :d] = A
+    return out
+
+
+def rotate_rows_device(A, rows_ptr, n, out_ptr, device=0, stream=None):
+    """out[i] = fp16(A rows[i]) for n fp16 device rows [n, d_padded] (include/knnx.h: knnx_rotate_f16_device); A f32 [d_padded,
+    d_padded]; out must not overlap rows.  Synchronous."""
+    A = np.ascontiguousarray(A, dtype=np.float32)
+    check(load_library(), load_library().knnx_rotate_f16_device(int(device), A.ctypes.data, C.c_void_p(int(rows_ptr)), int(n), A.shape[0],
+                                                                C.c_void_p(int(out_ptr)), C.c_void_p(stream) if stream else None), "knnx")
+
+
+def rotate_rows(A, x_f16, device=0, chunk=1 << 20):
+    """Host rows fp16 [n, d] -> fp16 [n, d] rotated on the device, chunk by chunk (the assignment pass of the host builds, tests)."""
+    import torch  # pylint: disable=import-outside-toplevel
+
     x_f16 = np.asarray(x_f16)
     n, d = x_f16.shape
+    dpad = (d + 255) // 256 * 256
+    Ap = _pad_rotation(A, dpad)
+    out = np.empty((n, d), dtype=np.float16)
+    for o in range(0, n, chunk):
+        xt = torch.from_numpy(_f16_padded(x_f16[o:o + chunk], dpad)).to(f"cuda:{device}")
+        yt = torch.empty_like(xt)
+        torch.cuda.synchronize(device)
+        rotate_rows_device(Ap, xt.data_ptr(), xt.shape[0], yt.data_ptr(), device)
+        out[o:o + chunk] = yt.cpu().numpy()[:, :d]
+    return out
+
+
+def opq_procrustes(G):
+    """The orthonormal A (y = A x) that minimises sum_i ||A x_i - y_i||^2, from G = X^T Y = sum_i x_i y_i^T: with G = U S V^T, A = V U^T
+    (faiss OPQMatrix::train takes the same SVD).  float64 on the host; G is d x d, d <= 1024."""
+    U, _, Vt = np.linalg.svd(np.asarray(G, dtype=np.float64))
+    return np.ascontiguousarray((U @ Vt).T.astype(np.float32))
+
+
+def opq_initial_rotation(d, seed):
+    """The seeded random orthonormal start: Q of the QR of a Gaussian matrix, columns signed so that R's diagonal is positive."""
+    g = np.random.default_rng(seed).standard_normal((d, d))
+    Q, R = np.linalg.qr(g)
+    return np.ascontiguousarray((Q * np.sign(np.diag(R))[None, :]).astype(np.float32))
+
+
+def train_opq_device(x_ptr, n, d, M, niter=8, pq_niter=4, seed=0, device=0):
+    """faiss' non-parametric OPQ over n fp16 rows [n, d] ALREADY IN HBM (d % 256 == 0): from a seeded random orthonormal matrix, per
+    iteration rotate the sample, train the M codebooks on the rotated rows (PqBuilder: one list with a zero centroid, so the
+    "residual" is the row), decode, G = X^T decoded on the device, A = the Procrustes solution of its SVD.  Every device step sums in
+    a fixed order: one seed, one matrix.  Returns A f32 [d, d]."""
+    import torch  # pylint: disable=import-outside-toplevel
+
+    assert d % 256 == 0, "device rows are padded (d % 256 == 0)"
+    lib = load_library()
+    dev = f"cuda:{device}"
+    A = opq_initial_rotation(d, seed)
+    y = torch.empty((n, d), dtype=torch.float16, device=dev)
+    zeros = torch.zeros(n, dtype=torch.int32, device=dev)
+    G = torch.empty((d, d), dtype=torch.float32, device=dev)
+    cent0 = np.zeros((1, d), dtype=np.float16)
+    m_idx = torch.arange(M, device=dev)[None, :]
+    for it in range(niter):
+        torch.cuda.synchronize(device)
+        rotate_rows_device(A, x_ptr, n, y.data_ptr(), device)
+        pb = PqBuilder(d, M, device)
+        pb.set_sample_device(y.data_ptr(), zeros.data_ptr(), n, cent0)
+        cb = train_pq_codebooks(pb, niter=pq_niter, seed=seed + it)
+        _, codes = pb.lloyd(want_codes=True)  # (the assignment of this call is against `cb`; the update behind it is not used)
+        pb.close()
+        dec = torch.from_numpy(cb).to(dev)[m_idx, torch.from_numpy(codes).to(dev).long()].reshape(n, d).contiguous()
+        torch.cuda.synchronize(device)
+        check(lib, lib.knnx_xty_device(int(device), C.c_void_p(int(x_ptr)), C.c_void_p(dec.data_ptr()), int(n), int(d), C.c_void_p(G.data_ptr()),
+                                       None), "knnx")
+        A = opq_procrustes(G.cpu().numpy())
+        del dec
+    return A
+
+
+def train_opq(x_f16, M, niter=8, pq_niter=4, seed=0, device=0, sample_rows=OPQ_SAMPLE_ROWS):
+    """OPQ rotation for host rows fp16 [n, d] (a seeded sample of <= sample_rows of them): A f32 [d, d], orthonormal, y = A x.  See
+    train_opq_device."""
+    import torch  # pylint: disable=import-outside-toplevel
+
+    x_f16 = np.asarray(x_f16)
+    n, d = x_f16.shape
+    take = min(n, int(sample_rows))
+    sample = x_f16[np.sort(np.random.default_rng(seed + 2).choice(n, take, replace=False))] if take < n else x_f16
+    dpad = (d + 255) // 256 * 256
+    xt = torch.from_numpy(_f16_padded(sample, dpad)).to(f"cuda:{device}")
+    if dpad == d:
+        return train_opq_device(xt.data_ptr(), take, d, M, niter=niter, pq_niter=pq_niter, seed=seed, device=device)
+    # padded rows: the zero columns carry no variance, G is singular there and the SVD's choice on that block is arbitrary -- the
+    # rotation is learned for a d_padded-wide problem and must be square in d, so such widths are refused rather than guessed
+    raise ValueError(f"train_opq needs d % 256 == 0 (got {d}): pass rotation= for other widths")
+
+
+def _resolve_rotation(x_sample, M, opq, rotation, seed, device):
+    """opq / rotation arguments of the builders -> (A f32 [d, d] or None, seconds spent training it)."""
+    import time  # pylint: disable=import-outside-toplevel
+
+    if rotation is not None:
+        return np.ascontiguousarray(rotation, dtype=np.float32), 0.0
+    if not opq:
+        return None, 0.0
+    t = time.perf_counter()
+    A = train_opq(x_sample, M, seed=seed, device=device)
+    return A, time.perf_counter() - t
+
+
+def train_ivfpq(x_f16, nlist, M, niter=8, pq_niter=10, seed=0, device=0, sample_rows=PQ_SAMPLE_ROWS, centroids=None,
+                max_points_per_centroid=256, opq=False, rotation=None):
+    """faiss IndexIVFPQ.train order: the coarse centroids first (the spherical k-means of train_ivf_centroids; `centroids=` skips it),
+    then the M sub-quantisers on the residuals of a sample of <= sample_rows rows against their lists.  Returns (centroids fp16
+    [nlist, d], codebooks f32 [M, 256, d_padded / M]).
+    opq=True / rotation=A (f32 [d, d]): the order of faiss' IndexPreTransform.train -- the OPQ rotation first, on the raw rows
+    (train_opq), then everything above on the ROTATED rows; returns (centroids, codebooks, A), both in the rotated space (`centroids=`
+    are then centroids of the rotated space)."""
+    x_f16 = np.asarray(x_f16)
+    n, d = x_f16.shape
+    A, _ = _resolve_rotation(x_f16, M, opq, rotation, seed, device)
+    if A is not None:
+        c, cb = train_ivfpq(rotate_rows(A, x_f16, device), nlist, M, niter=niter, pq_niter=pq_niter, seed=seed, device=device,
+                            sample_rows=sample_rows, centroids=centroids, max_points_per_centroid=max_points_per_centroid)
+        return c, cb, A
     if centroids is None:
         centroids = train_ivf_centroids(x_f16, nlist, niter=niter, seed=seed, device=device, max_points_per_centroid=max_points_per_centroid)
     centroids = np.asarray(centroids).astype(np.float16)
@@ -1190,9 +1342,11 @@ def train_ivfpq(x_f16, nlist, M, niter=8, pq_niter=10, seed=0, device=0, sample_
     return centroids, cb
 
 
-def _ivfpq_begin(d, nlist, M, centroids, codebooks, sizes, device, id_base):
+def _ivfpq_begin(d, nlist, M, centroids, codebooks, sizes, device, id_base, rotation=None):
     index = Mi355xIndex(d, device=device, id_base=id_base)
     index.set_pq_quantizer(M, codebooks)
+    if rotation is not None:
+        index.set_pq_rotation(rotation)
     cpad = np.ascontiguousarray(index._pad(np.asarray(centroids, dtype=np.float16)))  # pylint: disable=protected-access
     check(index._lib, index._lib.knnx_ivf_begin(index._h, nlist, cpad.ctypes.data, np.ascontiguousarray(sizes, dtype=np.int64).ctypes.data), "knnx")  # pylint: disable=protected-access
     return index
@@ -1205,12 +1359,13 @@ def _ivfpq_end(index, nlist, nprobe, centroids, id_base, n):
     return index
 
 
-def _ivfpq_encode_chunks(chunks, n, d, nlist, M, centroids, codebooks, lists, nprobe, device, id_base):
-    """Rows (an iterator of (offset, fp16 rows)) -> IVF-PQ index: every row is encoded into the next free slot of its list."""
+def _ivfpq_encode_chunks(chunks, n, d, nlist, M, centroids, codebooks, lists, nprobe, device, id_base, rotation=None):
+    """Rows (an iterator of (offset, fp16 rows)) -> IVF-PQ index: every row is encoded into the next free slot of its list.  With a
+    rotation the rows are the UN-ROTATED ones (the index rotates each chunk) and `lists` are those of the rotated rows."""
     sizes = np.bincount(lists, minlength=nlist).astype(np.int64)
     if sizes.shape[0] != nlist:
         raise ValueError("a list id is outside [0, nlist)")
-    index = _ivfpq_begin(d, nlist, M, centroids, codebooks, sizes, device, id_base)
+    index = _ivfpq_begin(d, nlist, M, centroids, codebooks, sizes, device, id_base, rotation)
     lib = index._lib  # pylint: disable=protected-access
     cursor = np.zeros(nlist, dtype=np.int64)
     for o, x in chunks:
@@ -1224,49 +1379,75 @@ def _ivfpq_encode_chunks(chunks, n, d, nlist, M, centroids, codebooks, lists, np
     return index
 
 
-def build_ivfpq_index(x_f16, nlist, M, nprobe=16, niter=8, pq_niter=10, seed=0, device=0, id_base=0, centroids=None, codebooks=None,
-                      chunk=1 << 20):
-    """fp16 rows [N, d] -> HBM-resident IVF-PQ index (ids = id_base + row number).  Trains (train_ivfpq) unless both `centroids` and
-    `codebooks` are given; lists by the MFMA assignment kernel; codes by the device encoder."""
-    n, d = x_f16.shape
-    if centroids is None or codebooks is None:
-        centroids, codebooks = train_ivfpq(x_f16, nlist, M, niter=niter, pq_niter=pq_niter, seed=seed, device=device, centroids=centroids)
-    centroids = np.asarray(centroids).astype(np.float16)
+def _assign_chunks(chunks, n, d, nlist, centroids, device, A):
+    """List of every row (rotated by A first when there is one) -> (lists int32 [n], seconds spent rotating)."""
+    import time  # pylint: disable=import-outside-toplevel
+
     b = IvfBuilder(d, nlist, device)
     b.set_centroids(centroids)
     lists = np.empty(n, dtype=np.int32)
-    for o in range(0, n, chunk):
-        lists[o:o + chunk] = b.assign(x_f16[o:o + chunk])
+    rotate_s = 0.0
+    for o, x in chunks:
+        if A is not None:
+            t = time.perf_counter()
+            x = rotate_rows(A, x, device)
+            rotate_s += time.perf_counter() - t
+        lists[o:o + x.shape[0]] = b.assign(x)
     b.close()
-    return _ivfpq_encode_chunks(((o, x_f16[o:o + chunk]) for o in range(0, n, chunk)), n, d, nlist, M, centroids, codebooks, lists, nprobe,
-                                device, id_base)
+    return lists, rotate_s
+
+
+def build_ivfpq_index(x_f16, nlist, M, nprobe=16, niter=8, pq_niter=10, seed=0, device=0, id_base=0, centroids=None, codebooks=None,
+                      chunk=1 << 20, opq=False, rotation=None):
+    """fp16 rows [N, d] -> HBM-resident IVF-PQ index (ids = id_base + row number).  Trains (train_ivfpq) unless both `centroids` and
+    `codebooks` are given; lists by the MFMA assignment kernel; codes by the device encoder.
+    opq=True trains an OPQ rotation first (train_opq), rotation=A uses that one; centroids / codebooks, given or trained, are those of
+    the rotated space.  The index keeps the rotation: it is searched with, and reconstructs, un-rotated vectors."""
+    n, d = x_f16.shape
+    A, _ = _resolve_rotation(x_f16, M, opq, rotation, seed, device)
+    if centroids is None or codebooks is None:
+        centroids, codebooks = train_ivfpq(x_f16, nlist, M, niter=niter, pq_niter=pq_niter, seed=seed, device=device, centroids=centroids,
+                                           rotation=A)[:2]
+    centroids = np.asarray(centroids).astype(np.float16)
+    lists, rotate_s = _assign_chunks(((o, x_f16[o:o + chunk]) for o in range(0, n, chunk)), n, d, nlist, centroids, device, A)
+    index = _ivfpq_encode_chunks(((o, x_f16[o:o + chunk]) for o in range(0, n, chunk)), n, d, nlist, M, centroids, codebooks, lists, nprobe,
+                                 device, id_base, A)
+    index.rotate_s = rotate_s
+    return index
 
 
 def build_ivfpq_index_from_folder(path, nlist, M, nprobe=16, niter=8, pq_niter=10, seed=0, device=0, centroids=None, codebooks=None,
-                                  max_points_per_centroid=256, chunk=1 << 20):
+                                  max_points_per_centroid=256, chunk=1 << 20, opq=False, rotation=None):
     """`clip inference` output folder (img_emb_*.npy) -> IVF-PQ index, streaming the partitions: training on a strided sample of the
-    whole folder, then one assignment pass and one encoding pass.  The result can be save_index()ed (self-contained)."""
+    whole folder, then one assignment pass and one encoding pass.  The result can be save_index()ed (self-contained).  opq / rotation
+    as in build_ivfpq_index (the rotation is trained on the same strided sample)."""
     src = path if isinstance(path, FolderRows) else FolderRows(path)
-    if centroids is None or codebooks is None:
+    A = None if rotation is None else np.ascontiguousarray(rotation, dtype=np.float32)
+    if centroids is None or codebooks is None or (opq and A is None):
         take = min(src.n, max(int(nlist) * int(max_points_per_centroid), PQ_SAMPLE_ROWS))
         idx = np.unique(np.linspace(0, src.n - 1, take).astype(np.int64))
-        centroids, codebooks = train_ivfpq(src.take(idx), nlist, M, niter=niter, pq_niter=pq_niter, seed=seed, device=device,
-                                           centroids=centroids, max_points_per_centroid=max_points_per_centroid)
+        sample = src.take(idx)
+        A, _ = _resolve_rotation(sample, M, opq, A, seed, device)
+        if centroids is None or codebooks is None:
+            centroids, codebooks = train_ivfpq(sample, nlist, M, niter=niter, pq_niter=pq_niter, seed=seed, device=device,
+                                               centroids=centroids, max_points_per_centroid=max_points_per_centroid, rotation=A)[:2]
     centroids = np.asarray(centroids).astype(np.float16)
-    b = IvfBuilder(src.d, nlist, device)
-    b.set_centroids(centroids)
-    lists = np.empty(src.n, dtype=np.int32)
-    for o, x in src.chunks(0, src.n, chunk):
-        lists[o:o + x.shape[0]] = b.assign(x)
-    b.close()
-    return _ivfpq_encode_chunks(src.chunks(0, src.n, chunk), src.n, src.d, nlist, M, centroids, codebooks, lists, nprobe, device, 0)
+    lists, rotate_s = _assign_chunks(src.chunks(0, src.n, chunk), src.n, src.d, nlist, centroids, device, A)
+    index = _ivfpq_encode_chunks(src.chunks(0, src.n, chunk), src.n, src.d, nlist, M, centroids, codebooks, lists, nprobe, device, 0, A)
+    index.rotate_s = rotate_s
+    return index
 
 
 def build_ivfpq_index_device(fill_rows, n, d, nlist, M, nprobe=16, niter=8, pq_niter=10, seed=0, device=0, id_base=0, centroids=None,
-                             codebooks=None, chunk=1 << 20, alloc=None, points_per_centroid=64, pq_sample_rows=PQ_SAMPLE_ROWS):
+                             codebooks=None, chunk=1 << 20, alloc=None, points_per_centroid=64, pq_sample_rows=PQ_SAMPLE_ROWS, opq=False,
+                             rotation=None, opq_sample_rows=OPQ_SAMPLE_ROWS):
     """IVF-PQ index over n rows PRODUCED ON THE GPU (`fill_rows(dst_ptr, row0, count, stride)` as in build_ivf_index_device): the
     fp16 corpus never exists whole -- training samples, then per chunk one assignment pass and one encoding pass; the index keeps
-    M bytes per row.  Returns (index, stats dict)."""
+    M bytes per row.  Returns (index, stats dict).
+    opq=True / rotation=A: the rotation is trained on a strided sample of raw rows (train_opq_device), every training sample and every
+    chunk of the assignment pass is rotated into a second buffer of its size before it is used, and the encoding pass hands the index
+    un-rotated chunks (it rotates them itself).  stats["rotate_s"]: the rotations of the assignment pass (those of the encoding pass
+    are part of encode_s), stats["opq_s"]: training the rotation (part of train_s)."""
     import time
 
     assert d % 256 == 0, "device builds take padded rows (d % 256 == 0)"
@@ -1278,14 +1459,33 @@ def build_ivfpq_index_device(fill_rows, n, d, nlist, M, nprobe=16, niter=8, pq_n
             t = torch.empty(int(nbytes), dtype=torch.uint8, device=f"cuda:{device}")
             return t.data_ptr(), t
     t0 = time.perf_counter()
+    A = None if rotation is None else _pad_rotation(rotation, d)
+    opq_s = rotate_s = 0.0
+    if A is None and opq:
+        n_os = int(min(n, opq_sample_rows))
+        os_ptr, os_keep = alloc(n_os * d * 2)
+        fill_rows(os_ptr, 0, n_os, max(1, n // n_os))
+        A = train_opq_device(os_ptr, n_os, d, M, seed=seed, device=device)
+        del os_keep
+        _release_cached_device_memory()
+        opq_s = time.perf_counter() - t0
+
+    def rotated(ptr, count):  # -> (pointer to the rotated rows, their owner): a second buffer, or the rows themselves without a rotation
+        if A is None:
+            return ptr, None
+        rp, rk = alloc(count * d * 2)
+        rotate_rows_device(A, ptr, count, rp, device)
+        return rp, rk
+
     b = IvfBuilder(d, nlist, device)
     if centroids is None:
         n_sample = int(min(n, nlist * points_per_centroid))
         sample_ptr, sample_keep = alloc(n_sample * d * 2)
         fill_rows(sample_ptr, 0, n_sample, max(1, n // n_sample))
+        sample_ptr, sample_rot_keep = rotated(sample_ptr, n_sample)
         train_ivf_centroids_device(b, sample_ptr, n_sample, niter=niter, seed=seed)
         centroids = np.ascontiguousarray(b.centroids())
-        del sample_keep
+        del sample_keep, sample_rot_keep
     centroids = np.asarray(centroids).astype(np.float16)
     b.set_centroids(centroids)
     if codebooks is None:
@@ -1293,25 +1493,32 @@ def build_ivfpq_index_device(fill_rows, n, d, nlist, M, nprobe=16, niter=8, pq_n
         ps_ptr, ps_keep = alloc(n_ps * d * 2)
         pl_ptr, pl_keep = alloc(n_ps * 4)
         fill_rows(ps_ptr, 0, n_ps, max(1, n // n_ps))
+        ps_ptr, ps_rot_keep = rotated(ps_ptr, n_ps)
         b.assign_device(ps_ptr, n_ps, pl_ptr)
         pb = PqBuilder(d, M, device)
         pb.set_sample_device(ps_ptr, pl_ptr, n_ps, centroids)
         codebooks = train_pq_codebooks(pb, niter=pq_niter, seed=seed)
         pb.close()
-        del ps_keep, pl_keep
+        del ps_keep, ps_rot_keep, pl_keep
     _release_cached_device_memory()
     t1 = time.perf_counter()
     lists_ptr, lists_keep = alloc(n * 4)
     rows_ptr, rows_keep = alloc(min(chunk, n) * d * 2)
+    rot_ptr, rot_keep = alloc(min(chunk, n) * d * 2) if A is not None else (rows_ptr, None)
     b.list_sizes(reset=True)
     for o in range(0, n, chunk):
         m = min(chunk, n - o)
         fill_rows(rows_ptr, o, m, 1)
-        b.assign_device(rows_ptr, m, lists_ptr + 4 * o)
+        if A is not None:
+            tr = time.perf_counter()
+            rotate_rows_device(A, rows_ptr, m, rot_ptr, device)
+            rotate_s += time.perf_counter() - tr
+        b.assign_device(rot_ptr, m, lists_ptr + 4 * o)
     sizes = b.list_sizes()
     b.close()
+    del rot_keep
     t2 = time.perf_counter()
-    index = _ivfpq_begin(d, nlist, M, centroids, codebooks, sizes, device, id_base)
+    index = _ivfpq_begin(d, nlist, M, centroids, codebooks, sizes, device, id_base, A)
     for o in range(0, n, chunk):
         m = min(chunk, n - o)
         fill_rows(rows_ptr, o, m, 1)
@@ -1320,13 +1527,15 @@ def build_ivfpq_index_device(fill_rows, n, d, nlist, M, nprobe=16, niter=8, pq_n
     del rows_keep, lists_keep
     _release_cached_device_memory()
     t3 = time.perf_counter()
-    stats = {"train_s": t1 - t0, "assign_s": t2 - t1, "encode_s": t3 - t2, "list_sizes": sizes, "bytes_per_row": M + 12}
+    stats = {"train_s": t1 - t0, "assign_s": t2 - t1, "encode_s": t3 - t2, "list_sizes": sizes, "bytes_per_row": M + 12,
+             "rotate_s": rotate_s, "opq_s": opq_s}
     return index, stats
 
 
 def _save_ivfpq_index(index, folder):
     """The self-contained IVF-PQ folder: ivf_pq_centroids.npy (fp16 [nlist, d]), ivf_pq_codebooks.npy (f32 [M, 256, d_padded / M]),
-    ivf_pq_codes.npy (u8 [n, M] in id order), ivf_pq_lists.npy (int32 [n]) and ivf_pq_manifest.json (written last)."""
+    ivf_pq_codes.npy (u8 [n, M] in id order), ivf_pq_lists.npy (int32 [n]) and ivf_pq_manifest.json (written last); an index with an
+    OPQ rotation adds ivf_pq_rotation.npy (f32 [d, d]) and "opq": true in the manifest."""
     import json  # pylint: disable=import-outside-toplevel
 
     cent = getattr(index, "ivf_centroids", None)
@@ -1341,6 +1550,10 @@ def _save_ivfpq_index(index, folder):
     np.save(os.path.join(folder, "ivf_pq_lists.npy"), lists)
     man = {"format": IVFPQ_FORMAT, "d": int(index.d), "nlist": int(cent.shape[0]), "M": int(index.pq_m), "nprobe": int(index.nprobe),
            "row_range": [int(lo), int(hi)]}
+    rot = index.pq_rotation()
+    if rot is not None:  # (only then: a folder of an index without a rotation is what it always was)
+        np.save(os.path.join(folder, IVFPQ_ROTATION), rot)
+        man["opq"] = True
     tmp = os.path.join(folder, IVFPQ_MANIFEST + ".part")
     with open(tmp, "w", encoding="utf-8") as f:
         json.dump(man, f, indent=1)
@@ -1348,11 +1561,28 @@ def _save_ivfpq_index(index, folder):
     return man
 
 
-def _ivfpq_from_codes(codes, lists, lo, cent, cb, M, nprobe, device, chunk=1 << 20):
+def read_ivfpq_rotation(folder, man):
+    """The rotation a saved IVF-PQ folder carries: None for a manifest without "opq" (every folder written before the rotation
+    existed), f32 [d, d] otherwise.  The flag and the file go together: either one without the other is refused."""
+    path = os.path.join(folder, IVFPQ_ROTATION)
+    if not man.get("opq", False):
+        if os.path.exists(path):
+            raise ValueError(f"{folder}: {IVFPQ_ROTATION} is present but the manifest does not say \"opq\": true")
+        return None
+    if not os.path.isfile(path):
+        raise ValueError(f"{folder}: the manifest says \"opq\": true but {IVFPQ_ROTATION} is missing")
+    rot = np.load(path)
+    d = int(man["d"])
+    if rot.shape != (d, d) or rot.dtype != np.float32:
+        raise ValueError(f"{folder}: {IVFPQ_ROTATION} must be float32 [{d}, {d}], got {rot.dtype} {rot.shape}")
+    return rot
+
+
+def _ivfpq_from_codes(codes, lists, lo, cent, cb, M, nprobe, device, chunk=1 << 20, rotation=None):
     nlist, d = cent.shape
     n = codes.shape[0]
     sizes = np.bincount(lists, minlength=nlist).astype(np.int64)
-    index = _ivfpq_begin(d, nlist, M, cent, cb, sizes, device, lo)
+    index = _ivfpq_begin(d, nlist, M, cent, cb, sizes, device, lo, rotation)
     lib = index._lib  # pylint: disable=protected-access
     cursor = np.zeros(nlist, dtype=np.int64)
     for o in range(0, n, chunk):
@@ -1377,6 +1607,7 @@ def _load_ivfpq_index(folder, device=0, row_range=None, devices=None):
     cb = np.load(os.path.join(folder, "ivf_pq_codebooks.npy"))
     codes = np.load(os.path.join(folder, "ivf_pq_codes.npy"), mmap_mode="r")
     lists = np.load(os.path.join(folder, "ivf_pq_lists.npy"), mmap_mode="r")
+    rot = read_ivfpq_rotation(folder, man)
     slo, shi = man["row_range"]
     M = int(man["M"])
     if cent.shape != (man["nlist"], man["d"]) or codes.shape != (shi - slo, M) or lists.shape[0] != shi - slo:
@@ -1387,11 +1618,11 @@ def _load_ivfpq_index(folder, device=0, row_range=None, devices=None):
         G = len(devices)
         cuts = [slo + (shi - slo) * g // G for g in range(G + 1)]
         shards = [_ivfpq_from_codes(codes[cuts[g] - slo:cuts[g + 1] - slo], np.asarray(lists[cuts[g] - slo:cuts[g + 1] - slo]), cuts[g], cent, cb,
-                                    M, man["nprobe"], devices[g]) for g in range(G)]
+                                    M, man["nprobe"], devices[g], rotation=rot) for g in range(G)]
         sharded = ShardedMi355xIndex.from_shards(shards, cuts[:-1])
         sharded.nprobe = man["nprobe"]
         return sharded
     lo, hi = (slo, shi) if row_range is None else (int(row_range[0]), int(row_range[1]))
     if not slo <= lo <= hi <= shi:
         raise ValueError(f"row_range {row_range} is outside the saved shard's rows [{slo}, {shi})")
-    return _ivfpq_from_codes(codes[lo - slo:hi - slo], np.asarray(lists[lo - slo:hi - slo]), lo, cent, cb, M, man["nprobe"], device)
+    return _ivfpq_from_codes(codes[lo - slo:hi - slo], np.asarray(lists[lo - slo:hi - slo]), lo, cent, cb, M, man["nprobe"], device, rotation=rot)

@@ -150,7 +150,7 @@ int knnx_ivf_add_assigned_device(knnx_index* ix, const void* rows_dev_f16, int64
 
 /* ---- IVF-PQ: faiss IndexIVFPQ(IndexFlatIP(d), d, nlist, M, 8), METRIC_INNER_PRODUCT, by_residual = true ----------------------
  * (the index type autofaiss builds for large corpora -- clip_index.py:12-66; the reference notebook's OPQ256_768,IVF16384_HNSW32,PQ256x8
- * without the rotation and the HNSW coarse quantiser).  M in {16, 32, 64, 128} dividing d, 256 centroids per sub-quantiser; other M:
+ * without the HNSW coarse quantiser; the OPQ rotation is the block below).  M in {16, 32, 64, 128} dividing d, 256 centroids per sub-quantiser; other M:
  * KNNX_E_ARG.  Codebooks: f32 [M][256][d / M].  Row x of list l: residual r = f32(x_f16) - f32(c_l), code byte m =
  * argmin_j ||r_m - C[m][j]||^2 in fp32 (ties -> smaller j).  Score = <q, c_l> + sum over m (in order) of LUT[m][code_m], LUT[m][j] =
  * <q_m, C[m][j]> in fp32; the coarse quantiser and its probe rule are those of IVF-Flat.  Results as knnx_search; reconstruct /
@@ -165,6 +165,35 @@ int knnx_ivfpq_m(const knnx_index* ix); /* 0: not an IVF-PQ index */
 /* every row of a built index, in arena order (list by list): ids [ntotal], lists [ntotal], codes [ntotal][M] (host) */
 int knnx_ivfpq_get_codes(knnx_index* ix, int64_t* ids, int32_t* lists, uint8_t* codes);
 int knnx_ivfpq_get_codebooks(knnx_index* ix, float* codebooks);
+/* ---- OPQ rotation in front of IVF-PQ: faiss IndexPreTransform(OPQMatrix(d, M), IndexIVFPQ(...)), d_out = d_in = d ------------------
+ * (what autofaiss puts in front of every IVF-PQ index it builds, and what ivf_metadata_ordering.py:23-24 applies to a query before it
+ * asks the coarse quantiser).  A: f32 [d][d] row-major, y = A x, owned by the index.  Everything of the block above -- centroids, lists,
+ * residuals, codebooks, codes, LUT, the ADC scan -- lives in the rotated space; an index without a rotation is exactly that block.
+ *   rows      a row entering the build is x_f16; what is encoded is y = fp16(A f32(x_f16)): A = hi + lo / 2048 with hi = fp16(A), lo =
+ *             fp16(2048 (A - hi)); per component one fp32 accumulator takes the lo products, 32 columns per MFMA step in ascending
+ *             order, is scaled by 2^-11, takes the hi products in the same order and is rounded to fp16 once (a zero sum is +0).  From
+ *             there on y is "the row" of the definition above.  The list ids handed to knnx_ivf_add_assigned[_device] are those of the
+ *             ROTATED rows (knnx_rotate_f16_device, then the assignment); the rows handed over are UN-ROTATED, the index rotates each
+ *             chunk itself before it encodes.  knnx_ivfpq_add_codes is unchanged: codes are already in the rotated space.
+ *   queries   q' = A q in fp32, once per query at the head of the pass: lane l of 64 sums columns l, l + 64, ... in ascending order with
+ *             fmaf, the 64 partial sums are added pairwise (a butterfly over lane distance 32, 16, .. 1).  Coarse scores, probe set
+ *             and LUT come from q'.  A is orthonormal, so the scores still estimate <q, x>.
+ *   decoding  reconstruct, the R of search / search_dedup and the vectors the dedup links are computed from are in the ORIGINAL space:
+ *             A^T (f32(c_l) + concat_m C[m][code_m]), fp32, component c = sum over j ascending of A[j][c] * decoded[j] with fmaf
+ *             (faiss IndexPreTransform::reconstruct -> reverse_transform; clip_back.py:290-325, 362-378 expects un-rotated rows).
+ * knnx_ivfpq_set_rotation: on an IVF-PQ index after knnx_ivfpq_set_quantizer and before knnx_ivf_begin, KNNX_E_STATE otherwise and on
+ * any index that is not IVF-PQ; a matrix with max |A A^T - I| > 1e-3 is refused (KNNX_E_ARG): scores of another metric would be silent.
+ * knnx_ivfpq_get_rotation: 0 and the matrix, or 1 and A untouched when the index has none.  knnx_shards_adopt takes IVF-PQ shards that
+ * all carry the same rotation (bit for bit) or none, and refuses a mix. */
+int knnx_ivfpq_set_rotation(knnx_index* ix, const float* A);
+int knnx_ivfpq_get_rotation(knnx_index* ix, float* A);
+/* The row rotation on its own (the MFMA kernel of the build): out_dev[i] = fp16(A rows_dev[i]) as defined above, n fp16 rows in HBM,
+ * d in {256, 512, 768, 1024}; A_host f32 [d][d] is NOT checked for orthonormality; out_dev must not overlap rows_dev; rows past n are
+ * not written.  knnx_xty_device: G = X^T Y (device f32 [d][d]) for fp16 rows X and f32 rows Y [n][d] in HBM, every element one fp32
+ * fmaf chain over the rows in ascending order -- the product whose SVD is the Procrustes step of OPQ training.  `stream`: hipStream_t
+ * or NULL; both synchronous. */
+int knnx_rotate_f16_device(int device, const float* A_host, const void* rows_dev_f16, int64_t n, int d, void* out_dev_f16, void* stream);
+int knnx_xty_device(int device, const void* x_dev_f16, const float* y_dev_f32, int64_t n, int d, float* g_dev, void* stream);
 /* Codebook training on the device (faiss trains the M sub-quantisers on the residuals of a sample; default 256 x 256 rows):
  * the builder keeps the sample rows (fp16 [n][d]) with their list ids and the coarse centroids resident.  knnx_pqb_lloyd = one
  * iteration of all M L2 k-means: assignment (the encode kernel), counting sort on the host, fixed-order mean update; an empty
@@ -197,8 +226,8 @@ int knnx_merge_topk_device(int device, const float* D_parts, const int64_t* I_pa
  * knnx_merge_topk_device.  Same result contract as knnx_search.  Thread-safe (calls are serialised). */
 typedef struct knnx_shards knnx_shards;
 int knnx_shards_create(int n_shards, const int* devices, int d, int metric, knnx_shards** out);
-/* Take ownership of per-device indexes built elsewhere (flat or IVF-Flat with replicated centroids; shard g must have
- * been given id_base = row_lo[g]).  On success the shards are destroyed with the handle. */
+/* Take ownership of per-device indexes built elsewhere (flat, IVF-Flat or IVF-PQ with replicated centroids -- and, IVF-PQ, the same
+ * rotation or none; shard g must have been given id_base = row_lo[g]).  On success the shards are destroyed with the handle. */
 int knnx_shards_adopt(int n_shards, knnx_index* const* shards, const int* devices, const int64_t* row_lo, knnx_shards** out);
 void knnx_shards_destroy(knnx_shards* s);
 /* Fix the row range of every shard (shard g = rows [g*T/G, (g+1)*T/G)) and size its arena; required before add. */

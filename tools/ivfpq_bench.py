@@ -6,6 +6,8 @@ at a size where both fit).  Prints ONE JSON line.
   python tools/ivfpq_bench.py                                   # config 5's shard: 125 M x 1024, nlist 65 536, M = 64
   python tools/ivfpq_bench.py --rows 1000000000 --d 768         # the headline index on one GPU
   python tools/ivfpq_bench.py --rows 16000000 --nlist 16384 --flat-ab
+  python tools/ivfpq_bench.py --opq                             # + the same index behind an OPQ rotation: rotate_s, recall, times
+  python tools/ivfpq_bench.py --opq --kind 2                    # ... on the dominant-column corpus (knnx_synth_rows_device kind 2)
 """
 import argparse
 import json
@@ -31,6 +33,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--recall-queries", type=int, default=64)
     ap.add_argument("--flat-ab", action="store_true")
+    ap.add_argument("--opq", action="store_true", help="also build the index behind a trained OPQ rotation and compare: same corpus, queries, process")
+    ap.add_argument("--kind", type=int, default=1, choices=(1, 2), help="corpus: 1 = the mixture of config 5, 2 = isotropic with three dominant columns")
     a = ap.parse_args()
 
     import torch
@@ -40,7 +44,11 @@ def main():
     n, d = a.rows, a.d
 
     def fill_rows(dst, row0, count, stride):
-        synth_rows_device(dst, row0, count, d, a.seed, kind=1, n_clusters=a.clusters, row_stride=stride)
+        if a.kind == 1:
+            synth_rows_device(dst, row0, count, d, a.seed, kind=1, n_clusters=a.clusters, row_stride=stride)
+            return
+        # kind 2 is generated with stride 1 only; its rows are i.i.d., so a contiguous block is as good a sample as a strided one
+        synth_rows_device(dst, row0, count, d, a.seed, kind=2)
 
     free0 = torch.cuda.mem_get_info()[0]
     index, st = build_ivfpq_index_device(fill_rows, n, d, a.nlist, a.M, nprobe=16, niter=6, pq_niter=8, seed=0)
@@ -53,7 +61,7 @@ def main():
     # queries: corpus rows (a different seed region) perturbed -- the mixture's own distribution
     rng = np.random.default_rng(1)
     qrows = torch.empty((256, d), dtype=torch.float16, device="cuda")
-    synth_rows_device(qrows.data_ptr(), n + 12345, 256, d, a.seed, kind=1, n_clusters=a.clusters)
+    synth_rows_device(qrows.data_ptr(), n + 12345, 256, d, a.seed, kind=a.kind, n_clusters=a.clusters if a.kind == 1 else 0)
     q = qrows.float().cpu().numpy()
     q += 0.05 * rng.standard_normal(q.shape).astype(np.float32) / np.sqrt(d)
     q /= np.linalg.norm(q, axis=1, keepdims=True)
@@ -98,7 +106,7 @@ def main():
     best_I = np.full((nr, k), -1, np.int64)
     for o in range(0, n, chunk):
         m = min(chunk, n - o)
-        synth_rows_device(buf.data_ptr(), o, m, d, a.seed, kind=1, n_clusters=a.clusters)
+        synth_rows_device(buf.data_ptr(), o, m, d, a.seed, kind=a.kind, n_clusters=a.clusters if a.kind == 1 else 0)
         torch.cuda.synchronize()
         f = Mi355xIndex(d, id_base=o)
         f.attach_device_rows(buf.data_ptr(), m)
@@ -109,6 +117,26 @@ def main():
         best_D, best_I = np.take_along_axis(allD, sel, 1), np.take_along_axis(allI, sel, 1)
     del buf
     out["recall40_np64"] = round(float(np.mean([len(set(x) & set(y)) / k for x, y in zip(I_pq, best_I)])), 4)
+
+    if a.opq:
+        # the same index behind a trained rotation, in the same process; the two are timed alternately (box-to-box spread is ~5 %)
+        rot, so = build_ivfpq_index_device(fill_rows, n, d, a.nlist, a.M, nprobe=64, niter=6, pq_niter=8, seed=0, opq=True)
+        torch.cuda.synchronize()
+        index.nprobe = rot.nprobe = 64
+        _, I_rot = rot.search(q[:nr], k)
+        cmp_ = {"opq_s": round(so["opq_s"], 2), "train_s": round(so["train_s"], 2), "assign_s": round(so["assign_s"], 2),
+                "rotate_s": round(so["rotate_s"], 2), "encode_s": round(so["encode_s"], 2),
+                "recall40_np64": round(float(np.mean([len(set(x) & set(y)) / k for x, y in zip(I_rot, best_I)])), 4),
+                "recall40_np64_plain": out["recall40_np64"]}
+        for B in [int(v) for v in a.batches.split(",")]:
+            tp, tr = [], []
+            for _ in range(3):
+                tp.append(timed(index, B))
+                tr.append(timed(rot, B))
+            cmp_[f"B{B}_np64_ms_plain"] = round(float(np.median(tp)) * 1e3, 4)
+            cmp_[f"B{B}_np64_ms"] = round(float(np.median(tr)) * 1e3, 4)
+        out["opq"] = cmp_
+        rot.close()
 
     if a.flat_ab:
         index.close()

@@ -184,6 +184,19 @@ hipError_t launch_pq_adc_scan(const uint8_t* codes, int M, const float* lut, con
                               float* part_s, uint32_t* part_i, int* part_n, hipStream_t st);
 hipError_t launch_pq_decode(const uint8_t* codes, int d, int M, const float* cb, const _Float16* cent, const unsigned* tile0, int nlist,
                             int64_t id_lo, int64_t n_ids, const uint32_t* inv, const int64_t* ids, int64_t n, float* out, hipStream_t st);
+// Refine (faiss IndexRefineFlat(IndexIVFPQ)): kc = k x k_factor candidates by ADC score, re-scored from the fp16 rows.
+constexpr int PQ_REFINE_MAX = 512;   // largest kc
+constexpr int PQ_SEL_MAX = 16384;    // entries (shares x kc) the cross-share selection sorts in the LDS: 128 KiB
+// the ADC scan for 64 < kc <= PQ_REFINE_MAX: partial list s * nq + q of part_s / part_r / part_n holds <= kc (score, arena row) entries
+hipError_t launch_pq_cand_scan(const uint8_t* codes, int M, const float* lut, const int* probe, const float* pscore, const unsigned* pcnt,
+                               int np, int nsplit, const unsigned* tile0, const unsigned* size, const int64_t* idmap, int kc, int nq,
+                               float* part_s, uint32_t* part_r, int* part_n, hipStream_t st);
+// ... and the ids of the best kc of every query's nsplit lists (nsplit * kc <= PQ_SEL_MAX) -> cand [nq][kc], -1 padded, any order
+hipError_t launch_pq_cand_select(const float* part_s, const uint32_t* part_r, const int* part_n, int nsplit, int nq, int kc,
+                                 const int64_t* idmap, int64_t* cand, hipStream_t st);
+// es[q][c] = <f32(X[inv[cand[q][c] - id_lo]]), q> (fixed summation order: knnx.h), then D / I = the top k of them, padded
+hipError_t launch_pq_refine(const _Float16* X, int d, const float* q, int nq, int64_t id_lo, int64_t n_ids, const uint32_t* inv,
+                            const int64_t* cand, int kc, int k, float* es, float* D, int64_t* I, hipStream_t st);
 // OPQ rotation in front of IVF-PQ (A f32 [d][d], y = A x; d in {256, 512, 768, 1024}).  launch_rot_split: A -> W fp16 [2 d][d], the
 // hi / lo tile image launch_rotate_f16 (knn_rq_kernels.hip, MFMA) streams: Y[i] = fp16(A P[i]), Y and P distinct.  launch_rot_queries:
 // out[i] = A q[i] in fp32 (nq <= 256 per launch is what it is sized for; any nq works).  launch_rot_back: out[i] = A^T dec[i] in fp32

@@ -270,6 +270,246 @@ __global__ __launch_bounds__(256) void pq_adc_scan_kernel(const uint8_t* __restr
 }
 
 // ---------------------------------------------------------------------------------------------
+// Refine (faiss IndexRefineFlat(IndexIVFPQ)): the kc = k x k_factor best rows by ADC score are re-scored exactly from the resident
+// fp16 rows.  For kc <= PQ_MAX_K the candidates come from pq_adc_scan_kernel + knn_merge_kernel above; for 64 < kc <= PQ_REFINE_MAX
+// from the three kernels below.  Same scores (same LUT, same summation order), same total order (score descending, id ascending).
+//
+// Candidate scan: grid and shares as pq_adc_scan_kernel, but ONE queue per workgroup of PQ_CQ (score, arena row) entries -- the id
+// is read from idmap only where two scores tie.  Every step the four waves score 256 rows of the current list (uniform trip
+// count: a list is walked by the whole workgroup), append what passes the threshold behind a per-wave count exchanged through the
+// LDS (one barrier per step; the counts alternate between two sets so that a fast wave cannot overwrite what a slow one still
+// reads), and when fewer than 256 slots are free the queue is pruned: bitonic sort of all PQ_CQ slots, O(n log^2 n), keep kc,
+// threshold = the kc-th score.  With kc = 512 a prune frees 1280 slots.
+// LDS budget (dynamic, 16-byte carves): LUT M KiB + queue PQ_CQ x 8 B = 16 KiB + 32 B of counts
+//   M = 16: 32 KiB + 32 B   M = 32: 48 KiB + 32 B   M = 64: 80 KiB + 32 B   M = 128: 144 KiB + 32 B   (of 160 KiB)
+// ---------------------------------------------------------------------------------------------
+constexpr int PQ_CQ = 2048;             // slots of the workgroup's candidate queue
+constexpr unsigned PQ_NOROW = ~0u;      // arena row of an empty queue slot (score -inf)
+static_assert(PQ_CQ >= PQ_REFINE_MAX + 256 && (PQ_CQ & (PQ_CQ - 1)) == 0, "the queue holds kc entries and one step, and is sorted as a power of two");
+static_assert((size_t)128 * 1024 + (size_t)PQ_CQ * 8 + 32 + 64 <= (size_t)KNN_LDS_BYTES, "M = 128: LUT + queue + counts exceed the LDS");
+static_assert((size_t)PQ_SEL_MAX * 8 + 64 <= (size_t)KNN_LDS_BYTES, "the selection holds a query's partial lists in the LDS");
+
+// a before b in the result order; rows index idmap (PQ_NOROW: an empty slot, after everything else)
+__device__ __forceinline__ bool pq_row_better(float sa, uint32_t ra, float sb, uint32_t rb, const int64_t* __restrict__ idmap) {
+  if (sa != sb) return sa > sb;
+  if (ra == rb || ra == PQ_NOROW) return false;
+  if (rb == PQ_NOROW) return true;
+  return idmap[ra] < idmap[rb];
+}
+
+// bitonic sort of n (a power of two) LDS entries into result order, by all threads of the workgroup; barriers inside, so every
+// thread calls it with the same n.  Entries written before the call must be followed by a barrier by the caller.
+__device__ __forceinline__ void pq_bitonic(float* s, uint32_t* r, int n, const int64_t* __restrict__ idmap, int tid, int nthr) {
+  for (int kk = 2; kk <= n; kk <<= 1)
+    for (int j = kk >> 1; j > 0; j >>= 1) {
+      for (int p = tid; p < (n >> 1); p += nthr) {
+        const int i = ((p & ~(j - 1)) << 1) | (p & (j - 1));  // the lower index of pair p
+        const int l = i | j;
+        const float si = s[i], sl = s[l];
+        const uint32_t ri = r[i], rl = r[l];
+        const bool fwd = (i & kk) == 0;
+        const bool sw = fwd ? pq_row_better(sl, rl, si, ri, idmap) : pq_row_better(si, ri, sl, rl, idmap);
+        if (sw) { s[i] = sl; r[i] = rl; s[l] = si; r[l] = ri; }
+      }
+      __syncthreads();
+    }
+}
+
+template <int M>
+__global__ __launch_bounds__(256) void pq_cand_scan_kernel(const uint8_t* __restrict__ codes, const float* __restrict__ lut,
+                                                          const int* __restrict__ probe, const float* __restrict__ pscore,
+                                                          const unsigned* __restrict__ pcnt, int np, int nsplit,
+                                                          const unsigned* __restrict__ tile0, const unsigned* __restrict__ size,
+                                                          const int64_t* __restrict__ idmap, int kc, int nq, float* __restrict__ part_s,
+                                                          uint32_t* __restrict__ part_r, int* __restrict__ part_n) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char pq_smem[];
+  float* s_lut = reinterpret_cast<float*>(pq_smem);              // [M * 256]
+  float* q_s = s_lut + M * 256;                                  // [PQ_CQ]
+  uint32_t* q_r = reinterpret_cast<uint32_t*>(q_s + PQ_CQ);      // [PQ_CQ]
+  int* s_wc = reinterpret_cast<int*>(q_r + PQ_CQ);               // [2][4]
+  const int s = blockIdx.x, q = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const float4* lq = reinterpret_cast<const float4*>(lut + (size_t)q * M * 256);
+  for (int e = tid; e < M * 64; e += 256) reinterpret_cast<float4*>(s_lut)[e] = lq[e];
+  __syncthreads();
+  int cnt = 0, par = 0;  // the same in every thread
+  float thr = -INFINITY;
+  // queue [0, cnt) -> its best min(cnt, kc) in result order
+  auto prune = [&]() {
+    __syncthreads();
+    for (int e = cnt + tid; e < PQ_CQ; e += 256) { q_s[e] = -INFINITY; q_r[e] = PQ_NOROW; }
+    __syncthreads();
+    pq_bitonic(q_s, q_r, PQ_CQ, idmap, tid, 256);
+    if (cnt >= kc) { cnt = kc; thr = q_s[kc - 1]; }
+  };
+  const int npq = min((int)pcnt[q], np);
+  for (int p = s; p < npq; p += nsplit) {
+    const int l = probe[(size_t)q * np + p];
+    const float cs = pscore[(size_t)q * np + p];
+    const size_t r0 = (size_t)tile0[l] * 32;
+    const unsigned sz = size[l];
+    for (unsigned base = 0; base < sz; base += 256) {
+      if (cnt > PQ_CQ - 256) prune();
+      const unsigned i = base + (unsigned)tid;
+      float sc = -INFINITY;
+      bool ok = false;
+      size_t row = 0;
+      if (i < sz) {
+        row = r0 + i;
+        const uint4* cp = reinterpret_cast<const uint4*>(codes + row * M);
+        uint4 cw[M / 16];
+#pragma unroll
+        for (int v = 0; v < M / 16; ++v) cw[v] = cp[v];
+        float acc = 0.f;
+#pragma unroll
+        for (int v = 0; v < M / 16; ++v) {
+          const unsigned ww[4] = {cw[v].x, cw[v].y, cw[v].z, cw[v].w};
+#pragma unroll
+          for (int b = 0; b < 16; ++b) acc += s_lut[(v * 16 + b) * 256 + ((ww[b >> 2] >> (8 * (b & 3))) & 255u)];
+        }
+        sc = cs + acc;
+        ok = sc >= thr;
+      }
+      const unsigned long long bal = __ballot(ok);
+      if (lane == 0) s_wc[par * 4 + w] = (int)__popcll(bal);
+      __syncthreads();
+      const int c0 = s_wc[par * 4], c1 = s_wc[par * 4 + 1], c2 = s_wc[par * 4 + 2], c3 = s_wc[par * 4 + 3];
+      if (ok) {
+        const int at = cnt + (w > 0 ? c0 : 0) + (w > 1 ? c1 : 0) + (w > 2 ? c2 : 0) + (int)__popcll(bal & ((1ull << lane) - 1ull));
+        q_s[at] = sc;
+        q_r[at] = (uint32_t)row;
+      }
+      cnt += c0 + c1 + c2 + c3;
+      par ^= 1;
+    }
+  }
+  prune();
+  const int keep = min(cnt, kc);
+  const size_t slot = (size_t)s * nq + q;
+  for (int e = tid; e < keep; e += 256) {
+    part_s[slot * kc + e] = q_s[e];
+    part_r[slot * kc + e] = q_r[e];
+  }
+  if (tid == 0) part_n[slot] = keep;
+}
+
+// selection across a query's shares: one workgroup per query holds its nsplit partial lists (<= PQ_SEL_MAX entries, padded to the
+// power of two n2) in the LDS, sorts them and writes the ids of the best kc (-1 behind the last one); grid nq, 1024 threads
+__global__ __launch_bounds__(1024) void pq_cand_select_kernel(const float* __restrict__ part_s, const uint32_t* __restrict__ part_r,
+                                                             const int* __restrict__ part_n, int nsplit, int nq, int kc, int n2,
+                                                             const int64_t* __restrict__ idmap, int64_t* __restrict__ cand) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char pq_smem[];
+  float* s_s = reinterpret_cast<float*>(pq_smem);            // [n2]
+  uint32_t* s_r = reinterpret_cast<uint32_t*>(s_s + n2);     // [n2]
+  const int q = blockIdx.x, tid = threadIdx.x;
+  for (int e = tid; e < n2; e += 1024) {
+    const int sh = e / kc, j = e - sh * kc;
+    float sv = -INFINITY;
+    uint32_t rv = PQ_NOROW;
+    if (sh < nsplit) {
+      const size_t slot = (size_t)sh * nq + q;
+      if (j < part_n[slot]) { sv = part_s[slot * kc + j]; rv = part_r[slot * kc + j]; }
+    }
+    s_s[e] = sv;
+    s_r[e] = rv;
+  }
+  __syncthreads();
+  pq_bitonic(s_s, s_r, n2, idmap, tid, 1024);
+  for (int e = tid; e < kc; e += 1024) {
+    const uint32_t rv = e < n2 ? s_r[e] : PQ_NOROW;
+    cand[(size_t)q * kc + e] = rv == PQ_NOROW ? -1 : idmap[rv];
+  }
+}
+
+// exact scores of the candidates: grid (ceil(kc / PQ_RS_WG), nq), 4 waves, one candidate row per wave pass.  The row (d x 2 bytes of
+// the refine store, found through inv) is read with one 16-byte load per lane and pass -- lane l of pass p holds columns
+// 8 (64 p + l) .. + 7 -- against the ORIGINAL fp32 query held in registers.
+// Summation order (knnx.h): every lane one fmaf chain from 0.f over its passes in ascending order and, inside a pass, its 8
+// columns in ascending order; then the 64 lane sums meet in the xor butterfly 32, 16, 8, 4, 2, 1 (rot_query_kernel's).  Nothing in
+// it depends on the batch, the shares of the ADC pass or the candidate's position.
+constexpr int PQ_RS_WG = 16;  // candidates of one workgroup (4 per wave): kc = 512 of ONE query are 32 workgroups
+template <int D>
+__global__ __launch_bounds__(256) void pq_rescore_kernel(const _Float16* __restrict__ X, const float* __restrict__ q, int64_t id_lo,
+                                                        int64_t n_ids, const uint32_t* __restrict__ inv, const int64_t* __restrict__ cand,
+                                                        int kc, float* __restrict__ es) {
+  constexpr int NP = (D / 8 + 63) / 64;  // passes
+  const int qi = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  float qv[NP][8];
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    const int g = p * 64 + lane;
+    if (g < D / 8) {
+      const float4* qp = reinterpret_cast<const float4*>(q + (size_t)qi * D + (size_t)g * 8);
+      const float4 a = qp[0], b = qp[1];
+      qv[p][0] = a.x; qv[p][1] = a.y; qv[p][2] = a.z; qv[p][3] = a.w;
+      qv[p][4] = b.x; qv[p][5] = b.y; qv[p][6] = b.z; qv[p][7] = b.w;
+    } else {
+#pragma unroll
+      for (int t = 0; t < 8; ++t) qv[p][t] = 0.f;
+    }
+  }
+  for (int c = blockIdx.x * PQ_RS_WG + w; c < min(kc, (int)(blockIdx.x + 1) * PQ_RS_WG); c += 4) {
+    const int64_t id = cand[(size_t)qi * kc + c];
+    float sc = -FLT_MAX;
+    if (id >= id_lo && id - id_lo < n_ids) {  // (wave-uniform)
+      const _Float16* xr = X + (size_t)inv[id - id_lo] * D;
+      float acc = 0.f;
+#pragma unroll
+      for (int p = 0; p < NP; ++p) {
+        const int g = p * 64 + lane;
+        if (g < D / 8) {
+          const uint4 v = *reinterpret_cast<const uint4*>(xr + (size_t)g * 8);
+          const unsigned ww[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+          for (int t = 0; t < 8; ++t) {
+            const unsigned short h = (unsigned short)(ww[t >> 1] >> (16 * (t & 1)));
+            _Float16 xh;
+            __builtin_memcpy(&xh, &h, 2);
+            acc = fmaf((float)xh, qv[p][t], acc);
+          }
+        }
+      }
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o);
+      sc = acc;
+    }
+    if (lane == 0) es[(size_t)qi * kc + c] = sc;
+  }
+}
+
+// top-k of a query's kc <= PQ_REFINE_MAX exact scores by rank counting (score descending, id ascending; candidates with id < 0
+// do not count), padded with -FLT_MAX / -1; grid nq, 256 threads
+__global__ __launch_bounds__(256) void pq_refine_topk_kernel(const float* __restrict__ es, const int64_t* __restrict__ cand, int kc, int k,
+                                                            float* __restrict__ D, int64_t* __restrict__ I) {
+  __shared__ __attribute__((aligned(16))) long long s_i[PQ_REFINE_MAX];
+  __shared__ __attribute__((aligned(16))) float s_s[PQ_REFINE_MAX];
+  __shared__ int s_n;
+  const int q = blockIdx.x, tid = threadIdx.x;
+  if (tid == 0) s_n = 0;
+  for (int e = tid; e < kc; e += 256) {
+    s_i[e] = cand[(size_t)q * kc + e];
+    s_s[e] = es[(size_t)q * kc + e];
+  }
+  __syncthreads();
+  for (int e = tid; e < kc; e += 256) {
+    const long long ie = s_i[e];
+    if (ie < 0) continue;
+    const float se = s_s[e];
+    int rank = 0;
+    for (int j = 0; j < kc; ++j) rank += (s_i[j] >= 0 && pq_better(s_s[j], s_i[j], se, ie)) ? 1 : 0;
+    if (rank < k) {
+      D[(size_t)q * k + rank] = se;
+      I[(size_t)q * k + rank] = ie;
+    }
+    atomicAdd(&s_n, 1);
+  }
+  __syncthreads();
+  for (int e = min(s_n, k) + tid; e < k; e += 256) {
+    D[(size_t)q * k + e] = -FLT_MAX;
+    I[(size_t)q * k + e] = -1;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // decode-gather (reconstruct, the coalescer's R): out[i] = f32(c_list) + concat_m cb[m][code_m] of id ids[i]; a bad id -> 0xFF
 // bytes.  The list of an arena row is the last list whose first tile is <= the row's tile (binary search over tile0).
 // ---------------------------------------------------------------------------------------------
@@ -579,6 +819,64 @@ hipError_t launch_pq_adc_scan(const uint8_t* codes, int M, const float* lut, con
     default: return hipErrorInvalidValue;
   }
 #undef PQ_SCAN
+}
+
+// refine: the candidate scan for 64 < kc <= PQ_REFINE_MAX; part_s / part_r hold nsplit * nq lists of kc entries
+hipError_t launch_pq_cand_scan(const uint8_t* codes, int M, const float* lut, const int* probe, const float* pscore, const unsigned* pcnt,
+                               int np, int nsplit, const unsigned* tile0, const unsigned* size, const int64_t* idmap, int kc, int nq,
+                               float* part_s, uint32_t* part_r, int* part_n, hipStream_t st) {
+  if (kc < 1 || kc > PQ_REFINE_MAX || nq <= 0 || nsplit <= 0) return hipErrorInvalidValue;
+  const size_t smem = (size_t)M * 1024 + (size_t)PQ_CQ * 8 + 32;
+  if (smem + 64 > (size_t)KNN_LDS_BYTES) return hipErrorInvalidValue;
+#define PQ_CSCAN(MM)                                                                                                              \
+  case MM: {                                                                                                                      \
+    auto kern = pq_cand_scan_kernel<MM>;                                                                                          \
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
+    if (e != hipSuccess) return e;                                                                                                \
+    hipLaunchKernelGGL(kern, dim3((unsigned)nsplit, (unsigned)nq), dim3(256), smem, st, codes, lut, probe, pscore, pcnt, np, nsplit, \
+                       tile0, size, idmap, kc, nq, part_s, part_r, part_n);                                                       \
+    return hipGetLastError();                                                                                                     \
+  }
+  switch (M) {
+    PQ_CSCAN(16) PQ_CSCAN(32) PQ_CSCAN(64) PQ_CSCAN(128)
+    default: return hipErrorInvalidValue;
+  }
+#undef PQ_CSCAN
+}
+
+// refine: the ids of the best kc of a query's nsplit partial lists -> cand [nq][kc] (-1 padded); nsplit * kc <= PQ_SEL_MAX
+hipError_t launch_pq_cand_select(const float* part_s, const uint32_t* part_r, const int* part_n, int nsplit, int nq, int kc,
+                                 const int64_t* idmap, int64_t* cand, hipStream_t st) {
+  if (nq <= 0 || nsplit <= 0 || kc < 1 || (size_t)nsplit * kc > (size_t)PQ_SEL_MAX) return hipErrorInvalidValue;
+  int n2 = 2;
+  while (n2 < nsplit * kc) n2 <<= 1;
+  const size_t smem = (size_t)n2 * 8;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pq_cand_select_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)smem);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(pq_cand_select_kernel, dim3((unsigned)nq), dim3(1024), smem, st, part_s, part_r, part_n, nsplit, nq, kc, n2, idmap, cand);
+  return hipGetLastError();
+}
+
+// refine: exact scores of cand [nq][kc] from the fp16 rows X (arena order, through inv) against q f32 [nq][d], then the top k of them
+hipError_t launch_pq_refine(const _Float16* X, int d, const float* q, int nq, int64_t id_lo, int64_t n_ids, const uint32_t* inv,
+                            const int64_t* cand, int kc, int k, float* es, float* D, int64_t* I, hipStream_t st) {
+  if (nq <= 0) return hipSuccess;
+  if (kc < 1 || kc > PQ_REFINE_MAX || k < 1 || k > kc) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((kc + PQ_RS_WG - 1) / PQ_RS_WG), (unsigned)nq);
+#define PQ_RS(DD) hipLaunchKernelGGL(pq_rescore_kernel<DD>, grid, dim3(256), 0, st, X, q, id_lo, n_ids, inv, cand, kc, es)
+  switch (d) {
+    case 256: PQ_RS(256); break;
+    case 512: PQ_RS(512); break;
+    case 768: PQ_RS(768); break;
+    case 1024: PQ_RS(1024); break;
+    default: return hipErrorInvalidValue;
+  }
+#undef PQ_RS
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(pq_refine_topk_kernel, dim3((unsigned)nq), dim3(256), 0, st, es, cand, kc, k, D, I);
+  return hipGetLastError();
 }
 
 hipError_t launch_pq_decode(const uint8_t* codes, int d, int M, const float* cb, const _Float16* cent, const unsigned* tile0, int nlist,

@@ -369,6 +369,10 @@ struct PqData {
   std::vector<float> rot_h;              // A, f32 [d][d] (knnx_ivfpq_get_rotation, knnx_shards_adopt)
   DevBuf<float> rot;                     // the same on the device (queries, back-rotation)
   DevBuf<_Float16> rot_w;                // [2 d][d] hi / lo tile image (row rotation of the build; released by knnx_ivf_end)
+  // refine store (knnx_ivfpq_set_refine): the fp16 rows as they entered the build, un-rotated, in the arena order of the codes.
+  // They live in knnx_index::rows ([capacity][d], allocated by knnx_ivf_begin); ivf.idmap / ivf.inv serve codes and rows alike.
+  bool refine = false;
+  int k_factor = 1;                      // candidates per result of a refine search (knnx_ivfpq_set_k_factor)
 };
 // one IVF-PQ search pass of up to PQ_PASS queries, allocated on first use
 struct PqScratch {
@@ -385,6 +389,24 @@ struct PqScratch {
   DevBuf<uint32_t> part_i;
   DevBuf<int> part_n;       // [PQ_SLOTS]
   DevBuf<float> qrot;       // [256][d] the rotated queries (allocated by scan_topk_pq when the index has a rotation)
+  // refine (allocated by the first refine search): candidates of one pass and their exact scores, the partial lists of the candidate
+  // scan for kc > 64, the ADC scores the merge writes next to the candidate ids for kc <= 64
+  DevBuf<int64_t> rcand;    // [256][PQ_REFINE_MAX]
+  DevBuf<float> rscore;     // [256][PQ_REFINE_MAX]
+  DevBuf<float> rpart_s;    // [PQ_SLOTS][PQ_REFINE_MAX]
+  DevBuf<uint32_t> rpart_r;
+  DevBuf<float> rdc;        // [256][64]
+  hipError_t alloc_refine() {
+    if (rcand) return hipSuccess;
+    hipError_t e = hipSuccess;
+    dev_alloc(e, rcand, (size_t)PQ_PASS * PQ_REFINE_MAX);
+    dev_alloc(e, rscore, (size_t)PQ_PASS * PQ_REFINE_MAX);
+    dev_alloc(e, rpart_s, (size_t)PQ_SLOTS * PQ_REFINE_MAX);
+    dev_alloc(e, rpart_r, (size_t)PQ_SLOTS * PQ_REFINE_MAX);
+    dev_alloc(e, rdc, (size_t)PQ_PASS * KNNX_MAX_K_FAST);
+    if (e != hipSuccess) rcand.reset(), rscore.reset(), rpart_s.reset(), rpart_r.reset(), rdc.reset();
+    return e;
+  }
   // (a larger nprobe than any before regrows probe / pscore only)
   hipError_t alloc(int d, size_t nl, int m, int np) {
     if (qfrag && np <= np_cap) return hipSuccess;
@@ -536,7 +558,8 @@ int scan_topk_ivf_multi(knnx_index* ix, const float* q_dev, int nq, int k, float
 bool ivfb_claim_all(knnx_index* ix, const int32_t* lists, const int32_t* pos, int64_t n);
 // knnx_ivfpq.hip
 int scan_topk_pq(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out, int64_t* I_out, hipStream_t st);
-// decoded rows of n ids (device) -> out f32 [n][d] in the ORIGINAL space (back-rotated when the index has a rotation; scratch slot 5)
+// decoded rows of n ids (device) -> out f32 [n][d] in the ORIGINAL space (back-rotated when the index has a rotation; scratch slot 5);
+// on an index with a refine store: the stored rows themselves
 int pq_decode_rows(knnx_index* ix, const int64_t* ids_dev, int64_t n, float* out_dev, hipStream_t st);
 
 // the int8 copy is an accelerator, not data: whoever needs device memory and cannot get it takes the copy's back and tries once more

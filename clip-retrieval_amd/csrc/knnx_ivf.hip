@@ -467,6 +467,10 @@ extern "C" int knnx_ivf_begin(knnx_index* ix, int nlist, const uint16_t* centroi
     if (e == hipSuccess) e = hipMemsetAsync(ix->pq.codes, 0, (size_t)prow * ix->pq.m, ix->stream);
     dev_alloc(e, ix->pq.bcent, (size_t)nlist * ix->d);
     if (e == hipSuccess) e = hipMemcpyAsync(ix->pq.bcent, centroids_f16, (size_t)nlist * ix->d * sizeof(_Float16), hipMemcpyHostToDevice, ix->stream);
+    if (ix->pq.refine) {  // the row arena next to the code arena (pad rows are zero)
+      if (e == hipSuccess) e = malloc_or_reclaim(ix, ix->rows, (size_t)prow * ix->d);
+      if (e == hipSuccess) e = hipMemsetAsync(ix->rows, 0, (size_t)prow * ix->d * sizeof(_Float16), ix->stream);
+    }
   } else {
     dev_alloc(e, ix->rows, (size_t)prow * ix->d);
     if (e == hipSuccess) e = hipMemsetAsync(ix->rows, 0, (size_t)prow * ix->d * sizeof(_Float16), ix->stream);  // pad rows are zero
@@ -556,7 +560,10 @@ extern "C" int knnx_ivf_add_assigned(knnx_index* ix, const uint16_t* rows_f16, i
     HIPCHK(hipMemcpyAsync(ix->ivfb.ids, p_ids, (size_t)m * 8, hipMemcpyHostToDevice, ix->stream));
     HIPCHK(hipMemcpyAsync(ix->ivfb.lists, p_lists, (size_t)m * 4, hipMemcpyHostToDevice, ix->stream));
     HIPCHK(hipMemcpyAsync(ix->ivfb.pos, p_pos, (size_t)m * 4, hipMemcpyHostToDevice, ix->stream));
-    if (ix->pq.m) {  // IVF-PQ: the rows are encoded into their slots, not copied (OPQ: rotated first)
+    if (ix->pq.m) {  // IVF-PQ: the rows are encoded into their slots, not copied (OPQ: rotated first); a refine store also keeps them
+      if (ix->pq.refine)
+        HIPCHK(launch_ivf_scatter(ix->ivfb.rows, m, ix->d, ix->ivfb.lists, ix->ivfb.pos, ix->ivfb.ids, 0, ix->ivf.tile0, ix->id_base,
+                                  ix->ivfb.total, ix->rows, ix->ivf.idmap, ix->ivf.inv, ix->stream));
       if (ix->pq.rot) HIPCHK(launch_rotate_f16(ix->pq.rot_w, ix->d, ix->ivfb.rows, m, ix->ivfb.rot, ix->stream));
       HIPCHK(launch_pq_encode(ix->pq.rot ? ix->ivfb.rot.p : ix->ivfb.rows.p, m, ix->d, ix->pq.m, ix->ivfb.lists, ix->pq.bcent, ix->pq.cb,
                               ix->ivf.tile0, ix->ivfb.pos, ix->ivfb.ids, 0, ix->id_base, ix->ivfb.total,
@@ -620,6 +627,9 @@ extern "C" int knnx_ivf_add_assigned_device(knnx_index* ix, const void* rows_dev
     HIPCHK(hipMemcpyAsync(ix->ivfb.pos, h_pos, (size_t)m * 4, hipMemcpyHostToDevice, ix->stream));
     const _Float16* src = (const _Float16*)rows_dev + (size_t)o * ix->d;
     if (ix->pq.m) {
+      if (ix->pq.refine)
+        HIPCHK(launch_ivf_scatter(src, m, ix->d, lists_dev + o, ix->ivfb.pos, nullptr, id0 + o, ix->ivf.tile0, ix->id_base, ix->ivfb.total,
+                                  ix->rows, ix->ivf.idmap, ix->ivf.inv, ix->stream));
       if (ix->pq.rot) HIPCHK(launch_rotate_f16(ix->pq.rot_w, ix->d, src, m, ix->ivfb.rot, ix->stream));
       HIPCHK(launch_pq_encode(ix->pq.rot ? ix->ivfb.rot.p : src, m, ix->d, ix->pq.m, lists_dev + o, ix->pq.bcent, ix->pq.cb, ix->ivf.tile0, ix->ivfb.pos,
                               nullptr, id0 + o, ix->id_base, ix->ivfb.total, ix->pq.codes, ix->ivf.idmap, ix->ivf.inv, ix->stream));

@@ -8,11 +8,22 @@
 // (one score dump over the centroids + the radix select of ivf_select_mark_kernel: the nprobe largest <q, c>, ties to the lower
 // list id), the probed lists of every query, its lookup table, the ADC list scan, the merge of the per-workgroup lists.
 // ---------------------------------------------------------------------------------------------
+//
+// Refine store (knnx_ivfpq_set_refine): the ADC stage keeps kc = k x k_factor candidates instead of k -- for kc <= 64 the scan and
+// merge above, for more the workgroup-queue scan and the LDS selection (pq_cand_scan_kernel, pq_cand_select_kernel) with the
+// shares capped so that shares x kc <= PQ_SEL_MAX -- and the candidates are re-scored from the fp16 rows with the ORIGINAL query
+// (pq_rescore_kernel) and ranked (pq_refine_topk_kernel).
 int scan_topk_pq(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out, int64_t* I_out, hipStream_t st) {
   if (nq < 1 || nq > PQ_PASS || k < 1 || k > KNNX_MAX_K_FAST || !ix->cent || !ix->ivf_nlist)
     return fail(KNNX_E_STATE, "internal: IVF-PQ pass misuse");
+  const int kc = ix->pq.refine ? k * ix->pq.k_factor : k;
+  if (kc > PQ_REFINE_MAX)
+    return fail(KNNX_E_ARG, "k x k_factor = " + std::to_string(k) + " x " + std::to_string(ix->pq.k_factor) + " exceeds " +
+                                std::to_string(PQ_REFINE_MAX) + " candidates per query");
+  const float* q_orig = q_dev;
   const int np = std::min(ix->ivf_nprobe, ix->ivf_nlist);
   HIPCHK(ix->pqs.alloc(ix->d, (size_t)ix->ivf_nlist, ix->pq.m, np));
+  if (ix->pq.refine) HIPCHK(ix->pqs.alloc_refine());
   knnx_index* c = ix->cent;
   const int nblk = (nq + KNN_NQ - 1) / KNN_NQ;
   if (ix->pq.rot) {  // OPQ: everything below sees q' = A q
@@ -39,7 +50,24 @@ int scan_topk_pq(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out
   HIPCHK(launch_ivf_select_mark(ix->pqs.scores, nq, np, ix->ivf_nlist, ix->pqs.masks, st));
   HIPCHK(launch_pq_probe(ix->pqs.masks, ix->pqs.scores, nq, ix->ivf_nlist, np, ix->pqs.pcnt, ix->pqs.probe, ix->pqs.pscore, st));
   HIPCHK(launch_pq_lut(q_dev, nq, ix->d, ix->pq.m, ix->pq.cb, ix->pqs.lut, st));
-  const int nsplit = std::max(1, std::min(std::min(np, PQ_MAX_SPLIT), (PQ_TARGET_WG + nq - 1) / nq));
+  int nsplit = std::max(1, std::min(std::min(np, PQ_MAX_SPLIT), (PQ_TARGET_WG + nq - 1) / nq));
+  if (ix->pq.refine) {
+    PqScratch& S = ix->pqs;
+    HIPCHK(ix->prof.begin(ix->prof.on, st));
+    if (kc <= PQ_MAX_K) {
+      HIPCHK(launch_pq_adc_scan(ix->pq.codes, ix->pq.m, S.lut, S.probe, S.pscore, S.pcnt, np, nsplit, ix->ivf.tile0, ix->ivf.size, ix->ivf.idmap,
+                                kc, nq, S.part_s, S.part_i, S.part_n, st));
+      HIPCHK(launch_merge_u32(S.part_s, S.part_i, S.part_n, nsplit, nq, kc, nq, kc, ix->id_base, ix->ivf.idmap, S.rdc, S.rcand, nullptr, st));
+    } else {
+      nsplit = std::max(1, std::min(nsplit, PQ_SEL_MAX / kc));
+      HIPCHK(launch_pq_cand_scan(ix->pq.codes, ix->pq.m, S.lut, S.probe, S.pscore, S.pcnt, np, nsplit, ix->ivf.tile0, ix->ivf.size,
+                                 ix->ivf.idmap, kc, nq, S.rpart_s, S.rpart_r, S.part_n, st));
+      HIPCHK(launch_pq_cand_select(S.rpart_s, S.rpart_r, S.part_n, nsplit, nq, kc, ix->ivf.idmap, S.rcand, st));
+    }
+    HIPCHK(launch_pq_refine(ix->rows, ix->d, q_orig, nq, ix->id_base, ix->ntotal, ix->ivf.inv, S.rcand, kc, k, S.rscore, D_out, I_out, st));
+    HIPCHK(ix->prof.end(ix->prof.on, st));
+    return 0;
+  }
   HIPCHK(ix->prof.begin(ix->prof.on, st));
   HIPCHK(launch_pq_adc_scan(ix->pq.codes, ix->pq.m, ix->pqs.lut, ix->pqs.probe, ix->pqs.pscore, ix->pqs.pcnt, np, nsplit, ix->ivf.tile0, ix->ivf.size,
                             ix->ivf.idmap, k, nq, ix->pqs.part_s, ix->pqs.part_i, ix->pqs.part_n, st));
@@ -69,6 +97,37 @@ extern "C" int knnx_ivfpq_set_quantizer(knnx_index* ix, int M, const float* code
 }
 
 extern "C" int knnx_ivfpq_m(const knnx_index* ix) { return ix ? ix->pq.m : 0; }
+
+// ---- refine store (faiss IndexRefineFlat(IndexIVFPQ)): the index keeps the fp16 rows next to the codes --------------------------
+extern "C" int knnx_ivfpq_set_refine(knnx_index* ix, int on) {
+  if (!ix) return fail(KNNX_E_ARG, "index is null");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  if (!ix->pq.m || ix->ntotal != 0 || ix->ivf_nlist || ix->ivfb.nlist)
+    return fail(KNNX_E_STATE, "the refine store is chosen on an IVF-PQ index after knnx_ivfpq_set_quantizer and before knnx_ivf_begin");
+  ix->pq.refine = on != 0;
+  return KNNX_OK;
+}
+extern "C" int knnx_ivfpq_refine(const knnx_index* ix) { return ix && ix->pq.refine ? 1 : 0; }
+
+extern "C" int knnx_ivfpq_set_k_factor(knnx_index* ix, int k_factor) {
+  if (!ix) return fail(KNNX_E_ARG, "index is null");
+  if (k_factor < 1 || k_factor > PQ_REFINE_MAX) return fail(KNNX_E_ARG, "k_factor must lie in 1 .. " + std::to_string(PQ_REFINE_MAX));
+  std::lock_guard<std::mutex> lk(ix->mu);
+  if (!ix->pq.m) return fail(KNNX_E_STATE, "not an IVF-PQ index");
+  ix->pq.k_factor = k_factor;
+  return KNNX_OK;
+}
+extern "C" int knnx_ivfpq_k_factor(const knnx_index* ix) { return ix ? ix->pq.k_factor : 0; }
+
+// bytes of the code arena and of the row arena (0 without a refine store) of an IVF-PQ index
+extern "C" int knnx_ivfpq_arena_bytes(knnx_index* ix, int64_t* code_bytes, int64_t* row_bytes) {
+  if (!ix || !code_bytes || !row_bytes) return fail(KNNX_E_ARG, "bad ivfpq_arena_bytes arguments");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  if (!ix->pq.m) return fail(KNNX_E_STATE, "not an IVF-PQ index");
+  *code_bytes = ix->pq.codes ? ix->capacity * (int64_t)ix->pq.m : 0;
+  *row_bytes = ix->pq.refine && ix->rows ? ix->capacity * (int64_t)ix->d * 2 : 0;
+  return KNNX_OK;
+}
 
 // ---- OPQ rotation (faiss IndexPreTransform(OPQMatrix(d, M), IndexIVFPQ), d_out = d_in) --------------------------------------------
 // A f32 [d][d] row-major, y = A x.  Orthonormal or refused: max |A A^T - I| <= 1e-3, checked in float64 on the host (d^3 <= 1e9
@@ -150,6 +209,10 @@ extern "C" int knnx_xty_device(int device, const void* x_dev_f16, const float* y
 }
 
 int pq_decode_rows(knnx_index* ix, const int64_t* ids_dev, int64_t n, float* out_dev, hipStream_t st) {
+  if (ix->pq.refine) {  // the stored rows, no decode and no back-rotation (faiss IndexRefine::reconstruct)
+    HIPCHK(launch_gather_inv(ix->rows, ix->d, ix->id_base, ix->ntotal, ix->ivf.inv, ids_dev, n, out_dev, st));
+    return KNNX_OK;
+  }
   float* dec = out_dev;
   if (ix->pq.rot) {
     int r = ensure_scratch(ix, 5, (size_t)n * ix->d * sizeof(float), (void**)&dec);
@@ -203,6 +266,7 @@ extern "C" int knnx_ivfpq_add_codes(knnx_index* ix, const uint8_t* codes, int64_
   std::lock_guard<std::mutex> lk(ix->mu);
   if (set_dev(ix)) return KNNX_E_HIP;
   if (!ix->pq.m || !ix->ivfb.nlist) return fail(KNNX_E_STATE, "set the PQ quantizer and call knnx_ivf_begin first");
+  if (ix->pq.refine) return fail(KNNX_E_STATE, "an index with a refine store takes rows (knnx_ivf_add_assigned), not codes: it has no rows to store");
   if (ix->ivfb.added + n > ix->ivfb.total) return fail(KNNX_E_ARG, "more rows than the list sizes announced");
   for (int64_t i = 0; i < n; ++i)
     if (ids[i] < ix->id_base || ids[i] - ix->id_base >= ix->ivfb.total) return fail(KNNX_E_ARG, "ids must lie in [id_base, id_base + total rows)");

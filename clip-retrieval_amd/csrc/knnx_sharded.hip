@@ -202,6 +202,10 @@ extern "C" int knnx_shards_adopt(int n_shards, knnx_index* const* shards, const 
     if (shards[g]->pq.rot_h.size() != shards[0]->pq.rot_h.size() ||
         memcmp(shards[g]->pq.rot_h.data(), shards[0]->pq.rot_h.data(), shards[0]->pq.rot_h.size() * sizeof(float)) != 0)
       return fail(KNNX_E_ARG, "IVF-PQ shards carry different rotations");
+  // ... and every shard refines its own candidates or none does: the merge ranks exact scores or ADC scores, never a mix
+  for (int g = 1; g < n_shards; ++g)
+    if (shards[g]->pq.refine != shards[0]->pq.refine)
+      return fail(KNNX_E_ARG, "IVF-PQ shards with and without a refine store cannot be mixed");
   knnx_shards* s = new knnx_shards();
   s->d = d;
   s->sh.resize(n_shards);

@@ -258,6 +258,32 @@ class Mi355xIndex(_FaissShaped):
         check(self._lib, rc, "knnx")
         return np.ascontiguousarray(out[: self.d, : self.d])
 
+    def set_pq_refine(self, on=True):
+        """Refine store (faiss IndexRefineFlat(IndexIVFPQ)): the index keeps the fp16 rows next to the codes (2 d bytes more per row) and
+        re-scores the k x k_factor best rows by ADC score exactly; reconstruct and the R of a search return the stored rows.  After
+        set_pq_quantizer, before the rows go in (include/knnx.h: knnx_ivfpq_set_refine)."""
+        check(self._lib, self._lib.knnx_ivfpq_set_refine(self._h, 1 if on else 0), "knnx")
+
+    @property
+    def pq_refine(self):
+        """True when this IVF-PQ index has a refine store."""
+        return bool(self._lib.knnx_ivfpq_refine(self._h)) if self._h else False
+
+    @property
+    def k_factor(self):
+        """Candidates per result of a refine search (faiss IndexRefine.k_factor; 1 .. 512, k x k_factor <= 512)."""
+        return int(self._lib.knnx_ivfpq_k_factor(self._h))
+
+    @k_factor.setter
+    def k_factor(self, v):
+        check(self._lib, self._lib.knnx_ivfpq_set_k_factor(self._h, int(v)), "knnx")
+
+    def pq_arena_bytes(self):
+        """(bytes of the code arena, bytes of the row arena -- 0 without a refine store) of an IVF-PQ index."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        check(self._lib, self._lib.knnx_ivfpq_arena_bytes(self._h, C.byref(a), C.byref(b)), "knnx")
+        return int(a.value), int(b.value)
+
     def pq_codes(self):
         """(codes u8 [ntotal, M], lists int32 [ntotal]) in id order: row i belongs to id id_base + i."""
         n, M = self.ntotal, self.pq_m
@@ -444,6 +470,21 @@ class ShardedMi355xIndex(_FaissShaped):
         self._nprobe = int(v)
 
     @property
+    def pq_refine(self):
+        """True when the shards are IVF-PQ indexes with a refine store (all of them or none: knnx_shards_adopt)."""
+        return bool(self._lib.knnx_ivfpq_refine(C.c_void_p(self._lib.knnx_shards_get(self._h, 0)))) if self.nshards else False
+
+    @property
+    def k_factor(self):
+        """Candidates per result of a refine search, as carried by the first shard (Mi355xIndex.k_factor)."""
+        return int(self._lib.knnx_ivfpq_k_factor(C.c_void_p(self._lib.knnx_shards_get(self._h, 0)))) if self.nshards else 1
+
+    @k_factor.setter
+    def k_factor(self, v):
+        for g in range(self.nshards):
+            check(self._lib, self._lib.knnx_ivfpq_set_k_factor(C.c_void_p(self._lib.knnx_shards_get(self._h, g)), int(v)), "knnx")
+
+    @property
     def nshards(self):
         return int(self._lib.knnx_shards_count(self._h))
 
@@ -526,7 +567,7 @@ def embedding_files(folder):
     return files
 
 
-def load_index(path, device=0, row_range=None, enable_faiss_memory_mapping=False, devices=None):  # pylint: disable=unused-argument
+def load_index(path, device=0, row_range=None, enable_faiss_memory_mapping=False, devices=None, embeddings_folder=None):  # pylint: disable=unused-argument
     """Build an HBM-resident flat index from a folder of fp16 `.npy` partitions -- or, when `path` is a folder written by
     `save_index()` (it holds ivf_manifest.json), re-create that IVF-Flat index without training or assigning anything.
 
@@ -537,8 +578,8 @@ def load_index(path, device=0, row_range=None, enable_faiss_memory_mapping=False
     (`ShardedMi355xIndex`, the KnnService case).  `enable_faiss_memory_mapping` is accepted for call compatibility:
     rows are always resident in HBM; the files themselves are read through np.load(mmap_mode="r").
     """
-    if os.path.isfile(os.path.join(path, IVFPQ_MANIFEST)):  # a saved IVF-PQ index: self-contained, no embeddings needed
-        return _load_ivfpq_index(path, device=device, row_range=row_range, devices=devices)
+    if os.path.isfile(os.path.join(path, IVFPQ_MANIFEST)):  # a saved IVF-PQ index: self-contained unless it has a refine store
+        return _load_ivfpq_index(path, device=device, row_range=row_range, devices=devices, embeddings_folder=embeddings_folder)
     if os.path.isfile(os.path.join(path, IVF_MANIFEST)):  # a built IVF-Flat index saved by save_index(): no k-means, no assignment
         return _load_ivf_index(path, device=device, row_range=row_range, devices=devices)
     src = FolderRows(path)
@@ -1013,7 +1054,7 @@ def save_index(index, folder, embeddings_folder=None):
     import json  # pylint: disable=import-outside-toplevel
 
     if getattr(index, "pq_m", 0):
-        return _save_ivfpq_index(index, folder)
+        return _save_ivfpq_index(index, folder, embeddings_folder)
     lists, cent = getattr(index, "ivf_lists", None), getattr(index, "ivf_centroids", None)
     src = getattr(index, "ivf_source", None)
     if lists is None or cent is None:
@@ -1342,11 +1383,14 @@ def train_ivfpq(x_f16, nlist, M, niter=8, pq_niter=10, seed=0, device=0, sample_
     return centroids, cb
 
 
-def _ivfpq_begin(d, nlist, M, centroids, codebooks, sizes, device, id_base, rotation=None):
+def _ivfpq_begin(d, nlist, M, centroids, codebooks, sizes, device, id_base, rotation=None, refine=False, k_factor=1):
     index = Mi355xIndex(d, device=device, id_base=id_base)
     index.set_pq_quantizer(M, codebooks)
     if rotation is not None:
         index.set_pq_rotation(rotation)
+    if refine:
+        index.set_pq_refine()
+    index.k_factor = k_factor
     cpad = np.ascontiguousarray(index._pad(np.asarray(centroids, dtype=np.float16)))  # pylint: disable=protected-access
     check(index._lib, index._lib.knnx_ivf_begin(index._h, nlist, cpad.ctypes.data, np.ascontiguousarray(sizes, dtype=np.int64).ctypes.data), "knnx")  # pylint: disable=protected-access
     return index
@@ -1359,13 +1403,14 @@ def _ivfpq_end(index, nlist, nprobe, centroids, id_base, n):
     return index
 
 
-def _ivfpq_encode_chunks(chunks, n, d, nlist, M, centroids, codebooks, lists, nprobe, device, id_base, rotation=None):
+def _ivfpq_encode_chunks(chunks, n, d, nlist, M, centroids, codebooks, lists, nprobe, device, id_base, rotation=None, refine=False,
+                         k_factor=1):
     """Rows (an iterator of (offset, fp16 rows)) -> IVF-PQ index: every row is encoded into the next free slot of its list.  With a
     rotation the rows are the UN-ROTATED ones (the index rotates each chunk) and `lists` are those of the rotated rows."""
     sizes = np.bincount(lists, minlength=nlist).astype(np.int64)
     if sizes.shape[0] != nlist:
         raise ValueError("a list id is outside [0, nlist)")
-    index = _ivfpq_begin(d, nlist, M, centroids, codebooks, sizes, device, id_base, rotation)
+    index = _ivfpq_begin(d, nlist, M, centroids, codebooks, sizes, device, id_base, rotation, refine, k_factor)
     lib = index._lib  # pylint: disable=protected-access
     cursor = np.zeros(nlist, dtype=np.int64)
     for o, x in chunks:
@@ -1398,11 +1443,12 @@ def _assign_chunks(chunks, n, d, nlist, centroids, device, A):
 
 
 def build_ivfpq_index(x_f16, nlist, M, nprobe=16, niter=8, pq_niter=10, seed=0, device=0, id_base=0, centroids=None, codebooks=None,
-                      chunk=1 << 20, opq=False, rotation=None):
+                      chunk=1 << 20, opq=False, rotation=None, refine=False, k_factor=1):
     """fp16 rows [N, d] -> HBM-resident IVF-PQ index (ids = id_base + row number).  Trains (train_ivfpq) unless both `centroids` and
     `codebooks` are given; lists by the MFMA assignment kernel; codes by the device encoder.
     opq=True trains an OPQ rotation first (train_opq), rotation=A uses that one; centroids / codebooks, given or trained, are those of
-    the rotated space.  The index keeps the rotation: it is searched with, and reconstructs, un-rotated vectors."""
+    the rotated space.  The index keeps the rotation: it is searched with, and reconstructs, un-rotated vectors.
+    refine=True keeps the fp16 rows next to the codes (Mi355xIndex.set_pq_refine) and re-scores k x k_factor candidates exactly."""
     n, d = x_f16.shape
     A, _ = _resolve_rotation(x_f16, M, opq, rotation, seed, device)
     if centroids is None or codebooks is None:
@@ -1411,16 +1457,17 @@ def build_ivfpq_index(x_f16, nlist, M, nprobe=16, niter=8, pq_niter=10, seed=0, 
     centroids = np.asarray(centroids).astype(np.float16)
     lists, rotate_s = _assign_chunks(((o, x_f16[o:o + chunk]) for o in range(0, n, chunk)), n, d, nlist, centroids, device, A)
     index = _ivfpq_encode_chunks(((o, x_f16[o:o + chunk]) for o in range(0, n, chunk)), n, d, nlist, M, centroids, codebooks, lists, nprobe,
-                                 device, id_base, A)
+                                 device, id_base, A, refine, k_factor)
     index.rotate_s = rotate_s
     return index
 
 
 def build_ivfpq_index_from_folder(path, nlist, M, nprobe=16, niter=8, pq_niter=10, seed=0, device=0, centroids=None, codebooks=None,
-                                  max_points_per_centroid=256, chunk=1 << 20, opq=False, rotation=None):
+                                  max_points_per_centroid=256, chunk=1 << 20, opq=False, rotation=None, refine=False, k_factor=1):
     """`clip inference` output folder (img_emb_*.npy) -> IVF-PQ index, streaming the partitions: training on a strided sample of the
     whole folder, then one assignment pass and one encoding pass.  The result can be save_index()ed (self-contained).  opq / rotation
-    as in build_ivfpq_index (the rotation is trained on the same strided sample)."""
+    as in build_ivfpq_index (the rotation is trained on the same strided sample).  refine / k_factor as in build_ivfpq_index; a saved
+    refine index is loaded from its folder PLUS these embeddings (save_index(index, folder, embeddings_folder=...))."""
     src = path if isinstance(path, FolderRows) else FolderRows(path)
     A = None if rotation is None else np.ascontiguousarray(rotation, dtype=np.float32)
     if centroids is None or codebooks is None or (opq and A is None):
@@ -1433,21 +1480,25 @@ def build_ivfpq_index_from_folder(path, nlist, M, nprobe=16, niter=8, pq_niter=1
                                                centroids=centroids, max_points_per_centroid=max_points_per_centroid, rotation=A)[:2]
     centroids = np.asarray(centroids).astype(np.float16)
     lists, rotate_s = _assign_chunks(src.chunks(0, src.n, chunk), src.n, src.d, nlist, centroids, device, A)
-    index = _ivfpq_encode_chunks(src.chunks(0, src.n, chunk), src.n, src.d, nlist, M, centroids, codebooks, lists, nprobe, device, 0, A)
+    index = _ivfpq_encode_chunks(src.chunks(0, src.n, chunk), src.n, src.d, nlist, M, centroids, codebooks, lists, nprobe, device, 0, A,
+                                 refine, k_factor)
     index.rotate_s = rotate_s
+    index.embeddings_folder = src.folder if hasattr(src, "folder") else None
     return index
 
 
 def build_ivfpq_index_device(fill_rows, n, d, nlist, M, nprobe=16, niter=8, pq_niter=10, seed=0, device=0, id_base=0, centroids=None,
                              codebooks=None, chunk=1 << 20, alloc=None, points_per_centroid=64, pq_sample_rows=PQ_SAMPLE_ROWS, opq=False,
-                             rotation=None, opq_sample_rows=OPQ_SAMPLE_ROWS):
+                             rotation=None, opq_sample_rows=OPQ_SAMPLE_ROWS, refine=False, k_factor=1):
     """IVF-PQ index over n rows PRODUCED ON THE GPU (`fill_rows(dst_ptr, row0, count, stride)` as in build_ivf_index_device): the
     fp16 corpus never exists whole -- training samples, then per chunk one assignment pass and one encoding pass; the index keeps
     M bytes per row.  Returns (index, stats dict).
     opq=True / rotation=A: the rotation is trained on a strided sample of raw rows (train_opq_device), every training sample and every
     chunk of the assignment pass is rotated into a second buffer of its size before it is used, and the encoding pass hands the index
     un-rotated chunks (it rotates them itself).  stats["rotate_s"]: the rotations of the assignment pass (those of the encoding pass
-    are part of encode_s), stats["opq_s"]: training the rotation (part of train_s)."""
+    are part of encode_s), stats["opq_s"]: training the rotation (part of train_s).
+    refine / k_factor as in build_ivfpq_index: the index stores each generated chunk as it encodes it (the chunk is handed over once
+    and never held a second time); stats["code_arena_bytes"] / stats["row_arena_bytes"]: what the index keeps in HBM."""
     import time
 
     assert d % 256 == 0, "device builds take padded rows (d % 256 == 0)"
@@ -1518,7 +1569,7 @@ def build_ivfpq_index_device(fill_rows, n, d, nlist, M, nprobe=16, niter=8, pq_n
     b.close()
     del rot_keep
     t2 = time.perf_counter()
-    index = _ivfpq_begin(d, nlist, M, centroids, codebooks, sizes, device, id_base, A)
+    index = _ivfpq_begin(d, nlist, M, centroids, codebooks, sizes, device, id_base, A, refine, k_factor)
     for o in range(0, n, chunk):
         m = min(chunk, n - o)
         fill_rows(rows_ptr, o, m, 1)
@@ -1527,20 +1578,29 @@ def build_ivfpq_index_device(fill_rows, n, d, nlist, M, nprobe=16, niter=8, pq_n
     del rows_keep, lists_keep
     _release_cached_device_memory()
     t3 = time.perf_counter()
-    stats = {"train_s": t1 - t0, "assign_s": t2 - t1, "encode_s": t3 - t2, "list_sizes": sizes, "bytes_per_row": M + 12,
-             "rotate_s": rotate_s, "opq_s": opq_s}
+    code_bytes, row_bytes = index.pq_arena_bytes()
+    stats = {"train_s": t1 - t0, "assign_s": t2 - t1, "encode_s": t3 - t2, "list_sizes": sizes, "bytes_per_row": M + 12 + (2 * d if refine else 0),
+             "rotate_s": rotate_s, "opq_s": opq_s, "code_arena_bytes": code_bytes, "row_arena_bytes": row_bytes}
     return index, stats
 
 
-def _save_ivfpq_index(index, folder):
+def _save_ivfpq_index(index, folder, embeddings_folder=None):
     """The self-contained IVF-PQ folder: ivf_pq_centroids.npy (fp16 [nlist, d]), ivf_pq_codebooks.npy (f32 [M, 256, d_padded / M]),
     ivf_pq_codes.npy (u8 [n, M] in id order), ivf_pq_lists.npy (int32 [n]) and ivf_pq_manifest.json (written last); an index with an
-    OPQ rotation adds ivf_pq_rotation.npy (f32 [d, d]) and "opq": true in the manifest."""
+    OPQ rotation adds ivf_pq_rotation.npy (f32 [d, d]) and "opq": true in the manifest.  An index with a refine store adds "refine": true,
+    "k_factor" and the embeddings folder (as save_index does for IVF-Flat) to the manifest: the rows are not written a second time, the
+    folder is loaded together with the embeddings."""
     import json  # pylint: disable=import-outside-toplevel
 
     cent = getattr(index, "ivf_centroids", None)
     if cent is None:
         raise ValueError("save_index takes an IVF-PQ index built by build_ivfpq_index* / load_index")
+    src = None
+    if index.pq_refine:
+        src = embeddings_folder or getattr(index, "embeddings_folder", None)
+        if src is None:
+            raise ValueError("this IVF-PQ index has a refine store: name the embeddings folder its rows can be re-read from")
+        src = src if isinstance(src, FolderRows) else FolderRows(src)
     codes, lists = index.pq_codes()
     lo, hi = getattr(index, "ivf_row_range", (0, codes.shape[0]))
     os.makedirs(folder, exist_ok=True)
@@ -1554,6 +1614,11 @@ def _save_ivfpq_index(index, folder):
     if rot is not None:  # (only then: a folder of an index without a rotation is what it always was)
         np.save(os.path.join(folder, IVFPQ_ROTATION), rot)
         man["opq"] = True
+    if src is not None:
+        if src.n < hi or src.d != index.d:
+            raise ValueError(f"{src.folder}: {src.n} rows of width {src.d} cannot hold rows [{lo}, {hi}) of width {index.d}")
+        man.update({"refine": True, "k_factor": int(index.k_factor), "embeddings": src.manifest(),
+                    "embeddings_relative": os.path.relpath(os.path.abspath(src.folder), os.path.abspath(folder))})
     tmp = os.path.join(folder, IVFPQ_MANIFEST + ".part")
     with open(tmp, "w", encoding="utf-8") as f:
         json.dump(man, f, indent=1)
@@ -1578,6 +1643,51 @@ def read_ivfpq_rotation(folder, man):
     return rot
 
 
+def read_ivfpq_refine(folder, man, embeddings_folder=None):
+    """The refine rules of a saved IVF-PQ manifest: (False, 1, None) for a manifest without "refine" (every folder written before the
+    refine store existed, and every plain index since: self-contained), else (True, k_factor, FolderRows of the embeddings).  The
+    embeddings are looked for at `embeddings_folder`, or at the recorded relative path, then at the absolute one; the flag without
+    reachable embeddings, or embeddings whose files changed, are refused.  Touches no device."""
+    if not man.get("refine", False):
+        if "k_factor" in man:
+            raise ValueError(f"{folder}: the manifest carries \"k_factor\" but does not say \"refine\": true")
+        return False, 1, None
+    kf = man.get("k_factor", 1)
+    if not isinstance(kf, int) or isinstance(kf, bool) or not 1 <= kf <= 512:
+        raise ValueError(f"{folder}: \"k_factor\" must be an integer in 1 .. 512, got {kf!r}")
+    emb = man.get("embeddings")
+    if not isinstance(emb, dict) or "files" not in emb:
+        raise ValueError(f"{folder}: the manifest says \"refine\": true but names no embeddings")
+    cands = [embeddings_folder] if embeddings_folder else [os.path.normpath(os.path.join(folder, man.get("embeddings_relative", "."))),
+                                                            emb.get("folder")]
+    src = None
+    for c in cands:
+        if c and os.path.isdir(c) and glob.glob(os.path.join(c, "*.npy")) and not os.path.isfile(os.path.join(c, IVFPQ_MANIFEST)):
+            src = FolderRows(c)
+            break
+    if src is None:
+        raise FileNotFoundError(f"{folder}: this IVF-PQ index has a refine store (\"refine\": true) and needs the embeddings it was built "
+                                f"from; they are not at {cands} (pass embeddings_folder=)")
+    if src.manifest()["files"] != emb["files"] or src.d != man["d"]:
+        raise ValueError(f"{src.folder}: the embedding files changed since the index was built (names / row counts / dimension)")
+    return True, kf, src
+
+
+def _ivfpq_refine_from_rows(src, codes, lists, lo, cent, cb, M, nprobe, device, k_factor, chunk=1 << 20, rotation=None):
+    """A saved refine index: rows [lo, lo + n) of the embeddings are stored AND re-encoded with the saved centroids, codebooks,
+    rotation and lists; the codes that come out must be the saved ones."""
+    n = codes.shape[0]
+    index = _ivfpq_encode_chunks(((o - lo, x) for o, x in src.chunks(lo, lo + n, chunk)), n, src.d, cent.shape[0], M, cent, cb,
+                                 np.asarray(lists, dtype=np.int32), nprobe, device, lo, rotation, True, k_factor)
+    got = index.pq_codes()[0]
+    if not np.array_equal(got, np.asarray(codes)):
+        bad = int((got != np.asarray(codes)).any(axis=1).sum())
+        index.close()
+        raise ValueError(f"{bad} of {n} rows of {src.folder} do not encode to the saved ivf_pq_codes.npy: the embeddings or the codes changed")
+    index.embeddings_folder = src.folder
+    return index
+
+
 def _ivfpq_from_codes(codes, lists, lo, cent, cb, M, nprobe, device, chunk=1 << 20, rotation=None):
     nlist, d = cent.shape
     n = codes.shape[0]
@@ -1596,7 +1706,7 @@ def _ivfpq_from_codes(codes, lists, lo, cent, cb, M, nprobe, device, chunk=1 << 
     return index
 
 
-def _load_ivfpq_index(folder, device=0, row_range=None, devices=None):
+def _load_ivfpq_index(folder, device=0, row_range=None, devices=None, embeddings_folder=None):
     import json  # pylint: disable=import-outside-toplevel
 
     with open(os.path.join(folder, IVFPQ_MANIFEST), encoding="utf-8") as f:
@@ -1608,8 +1718,15 @@ def _load_ivfpq_index(folder, device=0, row_range=None, devices=None):
     codes = np.load(os.path.join(folder, "ivf_pq_codes.npy"), mmap_mode="r")
     lists = np.load(os.path.join(folder, "ivf_pq_lists.npy"), mmap_mode="r")
     rot = read_ivfpq_rotation(folder, man)
+    refine, kf, src = read_ivfpq_refine(folder, man, embeddings_folder)
     slo, shi = man["row_range"]
     M = int(man["M"])
+
+    def make(c, ls, lo_, dev):
+        if refine:
+            return _ivfpq_refine_from_rows(src, c, ls, lo_, cent, cb, M, man["nprobe"], dev, kf, rotation=rot)
+        return _ivfpq_from_codes(c, ls, lo_, cent, cb, M, man["nprobe"], dev, rotation=rot)
+
     if cent.shape != (man["nlist"], man["d"]) or codes.shape != (shi - slo, M) or lists.shape[0] != shi - slo:
         raise ValueError(f"{folder}: the IVF-PQ files disagree with the manifest")
     if devices is not None:
@@ -1617,12 +1734,12 @@ def _load_ivfpq_index(folder, device=0, row_range=None, devices=None):
             raise ValueError("row_range and devices are mutually exclusive")
         G = len(devices)
         cuts = [slo + (shi - slo) * g // G for g in range(G + 1)]
-        shards = [_ivfpq_from_codes(codes[cuts[g] - slo:cuts[g + 1] - slo], np.asarray(lists[cuts[g] - slo:cuts[g + 1] - slo]), cuts[g], cent, cb,
-                                    M, man["nprobe"], devices[g], rotation=rot) for g in range(G)]
+        shards = [make(codes[cuts[g] - slo:cuts[g + 1] - slo], np.asarray(lists[cuts[g] - slo:cuts[g + 1] - slo]), cuts[g], devices[g])
+                  for g in range(G)]
         sharded = ShardedMi355xIndex.from_shards(shards, cuts[:-1])
         sharded.nprobe = man["nprobe"]
         return sharded
     lo, hi = (slo, shi) if row_range is None else (int(row_range[0]), int(row_range[1]))
     if not slo <= lo <= hi <= shi:
         raise ValueError(f"row_range {row_range} is outside the saved shard's rows [{slo}, {shi})")
-    return _ivfpq_from_codes(codes[lo - slo:hi - slo], np.asarray(lists[lo - slo:hi - slo]), lo, cent, cb, M, man["nprobe"], device, rotation=rot)
+    return make(codes[lo - slo:hi - slo], np.asarray(lists[lo - slo:hi - slo]), lo, device)

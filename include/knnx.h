@@ -187,6 +187,34 @@ int knnx_ivfpq_get_codebooks(knnx_index* ix, float* codebooks);
  * all carry the same rotation (bit for bit) or none, and refuses a mix. */
 int knnx_ivfpq_set_rotation(knnx_index* ix, const float* A);
 int knnx_ivfpq_get_rotation(knnx_index* ix, float* A);
+/* ---- Refine store on IVF-PQ: faiss IndexRefineFlat(IndexIVFPQ(...)) ("...,PQ64,RFlat"), with or without the OPQ rotation ------------
+ * The index keeps, next to the codes, the fp16 rows exactly as they entered the build (original, UN-ROTATED space), in the
+ * list-sorted, tile-padded arena order of the codes: tiles x 32 x d x 2 bytes more HBM (memory rule: M + 2 d bytes per padded row;
+ * the id map and its inverse serve codes and rows alike).
+ *   search    k <= 64, kc = k x k_factor.  1. Candidates: the top kc rows of the probed lists by (ADC score descending, id ascending) --
+ *             what knnx_search would return for k = kc; coarse quantiser, probe rule, LUT and summation order are those of the block
+ *             above; all rows of the probed lists when they hold fewer than kc.  2. Re-score: s = <f32(x_f16), q> in fp32 with the
+ *             ORIGINAL query and the stored row (with a rotation q' = A q feeds the candidate stage only).  Summation order: lane l of
+ *             64 owns columns 8 (64 p + l) .. 8 (64 p + l) + 7 for p = 0, 1 (while below d) and runs ONE fmaf chain from 0 over them in
+ *             ascending order; the 64 lane sums are added pairwise in a butterfly over lane distance 32, 16, .. 1.  It depends on
+ *             nothing else: a query gets the same D bits alone, in a batch of 256 and through the coalescer.  3. Result: the top k of
+ *             the candidates by (exact score descending, id ascending), padded with -1 / -FLT_MAX.
+ *   rows      reconstruct, the R of search / search_dedup and the vectors the dedup links are computed from are the STORED rows,
+ *             f32(x_f16) bit for bit: no decode, no back-rotation (faiss IndexRefine::reconstruct).
+ * knnx_ivfpq_set_refine: after knnx_ivfpq_set_quantizer and before knnx_ivf_begin (either order with knnx_ivfpq_set_rotation);
+ * KNNX_E_STATE otherwise and on any index that is not IVF-PQ.  knnx_ivf_begin then allocates the row arena next to the code arena
+ * (after giving back what an index gives back for its own data; KNNX_E_NOMEM leaves the index empty), knnx_ivf_add_assigned[_device]
+ * store the un-rotated chunk AND encode it; knnx_ivfpq_add_codes answers KNNX_E_STATE (it has no rows to store).
+ * knnx_ivfpq_set_k_factor: 1 .. 512, default 1 (faiss' default: the plain index's ids with exact scores); any time, any IVF-PQ index
+ * (without a refine store it has no effect).  A search with k x k_factor > 512 answers KNNX_E_ARG and names both numbers.  k > 64 and
+ * range_search stay KNNX_E_UNSUPPORTED.  knnx_shards_adopt takes IVF-PQ shards that all have a refine store or all have none and refuses
+ * a mix; each shard refines its own candidates and the merge ranks the exact scores.  An index without a refine store is exactly the
+ * two blocks above.  knnx_ivfpq_arena_bytes: bytes of the code arena and of the row arena (0 without a refine store). */
+int knnx_ivfpq_set_refine(knnx_index* ix, int on);
+int knnx_ivfpq_refine(const knnx_index* ix); /* 1: the index has (or will be built with) a refine store */
+int knnx_ivfpq_set_k_factor(knnx_index* ix, int k_factor);
+int knnx_ivfpq_k_factor(const knnx_index* ix);
+int knnx_ivfpq_arena_bytes(knnx_index* ix, int64_t* code_bytes, int64_t* row_bytes);
 /* The row rotation on its own (the MFMA kernel of the build): out_dev[i] = fp16(A rows_dev[i]) as defined above, n fp16 rows in HBM,
  * d in {256, 512, 768, 1024}; A_host f32 [d][d] is NOT checked for orthonormality; out_dev must not overlap rows_dev; rows past n are
  * not written.  knnx_xty_device: G = X^T Y (device f32 [d][d]) for fp16 rows X and f32 rows Y [n][d] in HBM, every element one fp32

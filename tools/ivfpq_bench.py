@@ -8,6 +8,9 @@ at a size where both fit).  Prints ONE JSON line.
   python tools/ivfpq_bench.py --rows 16000000 --nlist 16384 --flat-ab
   python tools/ivfpq_bench.py --opq                             # + the same index behind an OPQ rotation: rotate_s, recall, times
   python tools/ivfpq_bench.py --opq --kind 2                    # ... on the dominant-column corpus (knnx_synth_rows_device kind 2)
+  python tools/ivfpq_bench.py --rows 16000000 --nlist 16384 --nprobes 64 --refine [--k-factor 1,4,8]
+                                                                # + the same index with a refine store and IVF-Flat on the same rows, all three
+                                                                # resident, timed alternately; recall@40 of each
 """
 import argparse
 import json
@@ -34,6 +37,9 @@ def main():
     ap.add_argument("--recall-queries", type=int, default=64)
     ap.add_argument("--flat-ab", action="store_true")
     ap.add_argument("--opq", action="store_true", help="also build the index behind a trained OPQ rotation and compare: same corpus, queries, process")
+    ap.add_argument("--refine", action="store_true", help="also build the index with a refine store (same centroids and codebooks) and IVF-Flat "
+                    "on the same rows; all three stay resident and are timed alternately at nprobe 64, k = 40")
+    ap.add_argument("--k-factor", default="1,4,8", help="k_factor values of --refine")
     ap.add_argument("--kind", type=int, default=1, choices=(1, 2), help="corpus: 1 = the mixture of config 5, 2 = isotropic with three dominant columns")
     a = ap.parse_args()
 
@@ -137,6 +143,43 @@ def main():
             cmp_[f"B{B}_np64_ms"] = round(float(np.median(tr)) * 1e3, 4)
         out["opq"] = cmp_
         rot.close()
+
+    if a.refine:
+        # the same centroids and codebooks (so the candidates are the plain index's), the fp16 rows next to the codes; IVF-Flat with the
+        # same k-means seed on the same rows.  One process, the indexes timed alternately, three rounds, the median of the rounds' medians.
+        torch.cuda.synchronize()
+        free1 = torch.cuda.mem_get_info()[0]
+        ref, sr = build_ivfpq_index_device(fill_rows, n, d, a.nlist, a.M, nprobe=64, seed=0, centroids=index.ivf_centroids,
+                                           codebooks=index.pq_codebooks(), refine=True)
+        torch.cuda.synchronize()
+        used_ref = free1 - torch.cuda.mem_get_info()[0]
+        flat, sf = build_ivf_index_device(fill_rows, n, d, a.nlist, nprobe=64, seed=0)
+        index.nprobe = ref.nprobe = flat.nprobe = 64
+        kfs = [int(v) for v in a.k_factor.split(",")]
+
+        def rec(I):
+            return round(float(np.mean([len(set(x) & set(y)) / k for x, y in zip(I, best_I)])), 4)
+
+        r = {"assign_s": round(sr["assign_s"], 2), "encode_s": round(sr["encode_s"], 2), "code_arena_bytes": sr["code_arena_bytes"],
+             "row_arena_bytes": sr["row_arena_bytes"], "hbm_bytes_index": int(used_ref), "hbm_bytes_plain": int(used),
+             "flat_build_s": round(sum(v for kk, v in sf.items() if kk.endswith("_s")), 2) if isinstance(sf, dict) else None,
+             "recall40_plain": rec(index.search(q[:nr], k)[1]), "recall40_ivf_flat": rec(flat.search(q[:nr], k)[1])}
+        for kf in kfs:
+            ref.k_factor = kf
+            r[f"recall40_kf{kf}"] = rec(ref.search(q[:nr], k)[1])
+        for B in [int(v) for v in a.batches.split(",")]:
+            ts = {"plain": [], "ivf_flat": [], **{f"kf{kf}": [] for kf in kfs}}
+            for _ in range(3):
+                ts["plain"].append(timed(index, B))
+                for kf in kfs:
+                    ref.k_factor = kf
+                    ts[f"kf{kf}"].append(timed(ref, B))
+                ts["ivf_flat"].append(timed(flat, B))
+            for name, v in ts.items():
+                r[f"B{B}_np64_ms_{name}"] = round(float(np.median(v)) * 1e3, 4)
+        out["refine"] = r
+        ref.close()
+        flat.close()
 
     if a.flat_ab:
         index.close()

@@ -90,6 +90,9 @@ SIGNATURES = {
     "knnx_ivfpq_refine": (C.c_int, [_P]),
     "knnx_ivfpq_set_k_factor": (C.c_int, [_P, C.c_int]),
     "knnx_ivfpq_k_factor": (C.c_int, [_P]),
+    "knnx_ivfpq_set_threshold_scan": (C.c_int, [_P, C.c_int]),
+    "knnx_ivfpq_threshold_scan": (C.c_int, [_P]),
+    "knnx_ivfpq_threshold_stats": (C.c_int, [_P, _P, _P, _P, _P]),
     "knnx_ivfpq_arena_bytes": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "knnx_rotate_f16_device": (C.c_int, [C.c_int, _P, _P, C.c_int64, C.c_int, _P, _P]),
     "knnx_xty_device": (C.c_int, [C.c_int, _P, _P, C.c_int64, C.c_int, _P, _P]),

@@ -197,6 +197,15 @@ hipError_t launch_pq_cand_select(const float* part_s, const uint32_t* part_r, co
 // es[q][c] = <f32(X[inv[cand[q][c] - id_lo]]), q> (fixed summation order: knnx.h), then D / I = the top k of them, padded
 hipError_t launch_pq_refine(const _Float16* X, int d, const float* q, int nq, int64_t id_lo, int64_t n_ids, const uint32_t* inv,
                             const int64_t* cand, int kc, int k, float* es, float* D, int64_t* I, hipStream_t st);
+// the exact scores alone for any kc (the large-k refine search): es [nq][kc], -FLT_MAX where cand holds no id of the index
+hipError_t launch_pq_rescore(const _Float16* X, int d, const float* q, int nq, int64_t id_lo, int64_t n_ids, const uint32_t* inv,
+                             const int64_t* cand, int kc, float* es, hipStream_t st);
+// Threshold mode of the ADC scan (pq_range_scan_kernel): every row of the probed lists with score > thr[q] (strict; +INFINITY: the
+// query is skipped) is appended to hit_s / hit_r [q * cap ..] as (score, arena row); cnt[q] (cleared by the launcher) counts the hits
+// exactly even when more than cap of them exist.  Scores are those of launch_pq_adc_scan, bit for bit.
+hipError_t launch_pq_range_scan(const uint8_t* codes, int M, const float* lut, const int* probe, const float* pscore, const unsigned* pcnt,
+                                int np, int nsplit, const unsigned* tile0, const unsigned* size, const float* thr, unsigned* cnt,
+                                unsigned cap, float* hit_s, uint32_t* hit_r, int nq, hipStream_t st);
 // OPQ rotation in front of IVF-PQ (A f32 [d][d], y = A x; d in {256, 512, 768, 1024}).  launch_rot_split: A -> W fp16 [2 d][d], the
 // hi / lo tile image launch_rotate_f16 (knn_rq_kernels.hip, MFMA) streams: Y[i] = fp16(A P[i]), Y and P distinct.  launch_rot_queries:
 // out[i] = A q[i] in fp32 (nq <= 256 per launch is what it is sized for; any nq works).  launch_rot_back: out[i] = A^T dec[i] in fp32

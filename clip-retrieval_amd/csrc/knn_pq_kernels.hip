@@ -270,6 +270,79 @@ __global__ __launch_bounds__(256) void pq_adc_scan_kernel(const uint8_t* __restr
 }
 
 // ---------------------------------------------------------------------------------------------
+// Threshold mode of the ADC scan (range_search and k > 64 on an index with the threshold-scan switch on).  Grid, shares, LUT staging
+// and the scoring of a row are those of pq_adc_scan_kernel -- the same fp32 values, acc summed in m order, then cs + acc -- but there
+// are no candidate queues: a row is a hit when its score is > thr[q] (strict), and hits go to query q's slice of the range pools
+// (hit_s / hit_r [q * cap ..], score and ARENA ROW; the ids are resolved by the range sort through idmap).  Appends are aggregated per
+// wave: one ballot, ONE atomicAdd of the popcount by lane 0, the base broadcast, every hit lane writes at base + its prefix when that
+// is below cap.  With thr = -FLT_MAX every scored row is a hit on one counter per query, which a per-lane atomic would serialise.
+// cnt[q] stays exact when the slice overflows (the host regrows the pools and scans again).  A query whose threshold is +INFINITY is
+// finished: its workgroups return before they touch the LUT.  LDS: the LUT only, M KiB; no barrier in the row loop.
+// ---------------------------------------------------------------------------------------------
+static_assert((size_t)128 * 1024 + 64 <= (size_t)KNN_LDS_BYTES, "M = 128: the LUT of the threshold scan exceeds the LDS");
+
+template <int M>
+__global__ __launch_bounds__(256) void pq_range_scan_kernel(const uint8_t* __restrict__ codes, const float* __restrict__ lut,
+                                                           const int* __restrict__ probe, const float* __restrict__ pscore,
+                                                           const unsigned* __restrict__ pcnt, int np, int nsplit,
+                                                           const unsigned* __restrict__ tile0, const unsigned* __restrict__ size,
+                                                           const float* __restrict__ thr, unsigned* __restrict__ cnt, unsigned cap,
+                                                           float* __restrict__ hit_s, uint32_t* __restrict__ hit_r) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char pq_smem[];
+  float* s_lut = reinterpret_cast<float*>(pq_smem);  // [M * 256]
+  const int s = blockIdx.x, q = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const float th = thr[q];
+  if (th == INFINITY) return;  // (the whole workgroup: q is its query)
+  const float4* lq = reinterpret_cast<const float4*>(lut + (size_t)q * M * 256);
+  for (int e = tid; e < M * 64; e += 256) reinterpret_cast<float4*>(s_lut)[e] = lq[e];
+  __syncthreads();
+  float* hs = hit_s + (size_t)q * cap;
+  uint32_t* hr = hit_r + (size_t)q * cap;
+  const int npq = min((int)pcnt[q], np);
+  for (int p = s; p < npq; p += nsplit) {
+    const int l = probe[(size_t)q * np + p];
+    const float cs = pscore[(size_t)q * np + p];
+    const size_t r0 = (size_t)tile0[l] * 32;
+    const unsigned sz = size[l];
+    for (unsigned base = (unsigned)w * 64; base < sz; base += 256) {
+      const unsigned i = base + lane;
+      float sc = -INFINITY;
+      bool ok = false;
+      size_t row = 0;
+      if (i < sz) {
+        row = r0 + i;
+        const uint4* cp = reinterpret_cast<const uint4*>(codes + row * M);
+        uint4 cw[M / 16];
+#pragma unroll
+        for (int v = 0; v < M / 16; ++v) cw[v] = cp[v];
+        float acc = 0.f;
+#pragma unroll
+        for (int v = 0; v < M / 16; ++v) {
+          const unsigned ww[4] = {cw[v].x, cw[v].y, cw[v].z, cw[v].w};
+#pragma unroll
+          for (int b = 0; b < 16; ++b) acc += s_lut[(v * 16 + b) * 256 + ((ww[b >> 2] >> (8 * (b & 3))) & 255u)];
+        }
+        sc = cs + acc;
+        ok = sc > th;
+      }
+      const unsigned long long bal = __ballot(ok);
+      if (bal) {  // (wave-uniform)
+        unsigned at0 = 0;
+        if (lane == 0) at0 = atomicAdd(&cnt[q], (unsigned)__popcll(bal));
+        at0 = (unsigned)__shfl((int)at0, 0);
+        if (ok) {
+          const size_t at = (size_t)at0 + (size_t)__popcll(bal & ((1ull << lane) - 1ull));
+          if (at < (size_t)cap) {
+            hs[at] = sc;
+            hr[at] = (uint32_t)row;
+          }
+        }
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Refine (faiss IndexRefineFlat(IndexIVFPQ)): the kc = k x k_factor best rows by ADC score are re-scored exactly from the resident
 // fp16 rows.  For kc <= PQ_MAX_K the candidates come from pq_adc_scan_kernel + knn_merge_kernel above; for 64 < kc <= PQ_REFINE_MAX
 // from the three kernels below.  Same scores (same LUT, same summation order), same total order (score descending, id ascending).
@@ -821,6 +894,32 @@ hipError_t launch_pq_adc_scan(const uint8_t* codes, int M, const float* lut, con
 #undef PQ_SCAN
 }
 
+// threshold scan of nq queries over the probe lists / LUTs of their pass: thr [nq], cnt [nq] (cleared here), hits to hit_s / hit_r
+// [nq][cap]
+hipError_t launch_pq_range_scan(const uint8_t* codes, int M, const float* lut, const int* probe, const float* pscore, const unsigned* pcnt,
+                                int np, int nsplit, const unsigned* tile0, const unsigned* size, const float* thr, unsigned* cnt,
+                                unsigned cap, float* hit_s, uint32_t* hit_r, int nq, hipStream_t st) {
+  if (nq <= 0 || nsplit <= 0 || np <= 0 || !thr || !cnt || (cap > 0 && (!hit_s || !hit_r))) return hipErrorInvalidValue;
+  const size_t smem = (size_t)M * 256 * 4;
+  if (smem + 64 > (size_t)KNN_LDS_BYTES) return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(cnt, 0, (size_t)nq * sizeof(unsigned), st);
+  if (e != hipSuccess) return e;
+#define PQ_RSCAN(MM)                                                                                                              \
+  case MM: {                                                                                                                      \
+    auto kern = pq_range_scan_kernel<MM>;                                                                                         \
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);           \
+    if (e != hipSuccess) return e;                                                                                                \
+    hipLaunchKernelGGL(kern, dim3((unsigned)nsplit, (unsigned)nq), dim3(256), smem, st, codes, lut, probe, pscore, pcnt, np, nsplit, \
+                       tile0, size, thr, cnt, cap, hit_s, hit_r);                                                                 \
+    return hipGetLastError();                                                                                                     \
+  }
+  switch (M) {
+    PQ_RSCAN(16) PQ_RSCAN(32) PQ_RSCAN(64) PQ_RSCAN(128)
+    default: return hipErrorInvalidValue;
+  }
+#undef PQ_RSCAN
+}
+
 // refine: the candidate scan for 64 < kc <= PQ_REFINE_MAX; part_s / part_r hold nsplit * nq lists of kc entries
 hipError_t launch_pq_cand_scan(const uint8_t* codes, int M, const float* lut, const int* probe, const float* pscore, const unsigned* pcnt,
                                int np, int nsplit, const unsigned* tile0, const unsigned* size, const int64_t* idmap, int kc, int nq,
@@ -863,6 +962,17 @@ hipError_t launch_pq_refine(const _Float16* X, int d, const float* q, int nq, in
                             const int64_t* cand, int kc, int k, float* es, float* D, int64_t* I, hipStream_t st) {
   if (nq <= 0) return hipSuccess;
   if (kc < 1 || kc > PQ_REFINE_MAX || k < 1 || k > kc) return hipErrorInvalidValue;
+  hipError_t e = launch_pq_rescore(X, d, q, nq, id_lo, n_ids, inv, cand, kc, es, st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(pq_refine_topk_kernel, dim3((unsigned)nq), dim3(256), 0, st, es, cand, kc, k, D, I);
+  return hipGetLastError();
+}
+
+// the exact scores alone, any kc >= 1 (the large-k refine search ranks them on the host): es [nq][kc], -FLT_MAX where cand is no id
+hipError_t launch_pq_rescore(const _Float16* X, int d, const float* q, int nq, int64_t id_lo, int64_t n_ids, const uint32_t* inv,
+                             const int64_t* cand, int kc, float* es, hipStream_t st) {
+  if (nq <= 0) return hipSuccess;
+  if (kc < 1 || nq > 65535) return hipErrorInvalidValue;
   const dim3 grid((unsigned)((kc + PQ_RS_WG - 1) / PQ_RS_WG), (unsigned)nq);
 #define PQ_RS(DD) hipLaunchKernelGGL(pq_rescore_kernel<DD>, grid, dim3(256), 0, st, X, q, id_lo, n_ids, inv, cand, kc, es)
   switch (d) {
@@ -873,9 +983,6 @@ hipError_t launch_pq_refine(const _Float16* X, int d, const float* q, int nq, in
     default: return hipErrorInvalidValue;
   }
 #undef PQ_RS
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(pq_refine_topk_kernel, dim3((unsigned)nq), dim3(256), 0, st, es, cand, kc, k, D, I);
   return hipGetLastError();
 }
 

@@ -989,7 +989,10 @@ extern "C" int knnx_search_dedup(knnx_index* ix, const float* q, int k, float* D
 extern "C" int knnx_search(knnx_index* ix, const float* q, int n, int k, float* D, int64_t* I, float* R) {
   if (!ix || (n > 0 && (!q || !D || !I)) || n < 0 || k <= 0) return fail(KNNX_E_ARG, "bad search arguments");
   if (k > KNNX_MAX_K) return fail(KNNX_E_UNSUPPORTED, "k > 131072 is not implemented");
-  if (ix->pq.m && k > KNNX_MAX_K_FAST) return fail(KNNX_E_UNSUPPORTED, "k > 64 is not supported on an IVF-PQ index");
+  if (ix->pq.m && k > KNNX_MAX_K_FAST) {  // served through the threshold mode of the ADC scan where the index has it switched on
+    std::lock_guard<std::mutex> lk(ix->mu);
+    if (!ix->pq.threshold_scan) return fail(KNNX_E_UNSUPPORTED, "k > 64 is not supported on an IVF-PQ index");
+  }
   if (n == 0) return KNNX_OK;
   if (n == 1 && k <= KNNX_MAX_K_FAST && ix->co.on) {  // concurrent single-query callers share one scan
     CoReq me{q, k, D, I, R, false, 0.f, nullptr, 0, nullptr};
@@ -998,7 +1001,10 @@ extern "C" int knnx_search(knnx_index* ix, const float* q, int n, int k, float* 
   {
     std::lock_guard<std::mutex> lk(ix->mu);
     if (set_dev(ix)) return KNNX_E_HIP;
-    int r = (k <= KNNX_MAX_K_FAST) ? search_fast_locked(ix, q, n, k, D, I) : search_large_k_locked(ix, q, n, k, D, I);
+    int r = (k <= KNNX_MAX_K_FAST) ? search_fast_locked(ix, q, n, k, D, I)
+            : ix->pq.m               ? (ix->pq.threshold_scan ? search_large_k_pq_locked(ix, q, n, k, D, I)
+                                                              : fail(KNNX_E_UNSUPPORTED, "k > 64 is not supported on an IVF-PQ index"))
+                                     : search_large_k_locked(ix, q, n, k, D, I);
     if (r) return r;
   }
   if (R) return knnx_reconstruct(ix, I, (int64_t)n * k, R);

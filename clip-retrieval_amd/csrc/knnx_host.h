@@ -373,6 +373,9 @@ struct PqData {
   // They live in knnx_index::rows ([capacity][d], allocated by knnx_ivf_begin); ivf.idmap / ivf.inv serve codes and rows alike.
   bool refine = false;
   int k_factor = 1;                      // candidates per result of a refine search (knnx_ivfpq_set_k_factor)
+  // threshold mode of the ADC scan (knnx_ivfpq_set_threshold_scan): k > 64 and range_search are served; off: they are refused
+  bool threshold_scan = false;
+  int64_t thr_queries = 0, thr_scans = 0, thr_query_scans = 0, thr_hits = 0;  // knnx_ivfpq_threshold_stats
 };
 // one IVF-PQ search pass of up to PQ_PASS queries, allocated on first use
 struct PqScratch {
@@ -396,6 +399,19 @@ struct PqScratch {
   DevBuf<float> rpart_s;    // [PQ_SLOTS][PQ_REFINE_MAX]
   DevBuf<uint32_t> rpart_r;
   DevBuf<float> rdc;        // [256][64]
+  // threshold passes (allocated by the first one): the per-query thresholds and hit counters of one scan, the counters of a fetch
+  DevBuf<float> tthr;       // [256]
+  DevBuf<unsigned> tcnt;    // [256]
+  DevBuf<unsigned> tfetch;  // [256] tcnt with the queries that are not fetched set to 0 (range_fetch reads its counts on the device)
+  hipError_t alloc_threshold() {
+    if (tthr) return hipSuccess;
+    hipError_t e = hipSuccess;
+    dev_alloc(e, tthr, PQ_PASS);
+    dev_alloc(e, tcnt, PQ_PASS);
+    dev_alloc(e, tfetch, PQ_PASS);
+    if (e != hipSuccess) tthr.reset(), tcnt.reset(), tfetch.reset();
+    return e;
+  }
   hipError_t alloc_refine() {
     if (rcand) return hipSuccess;
     hipError_t e = hipSuccess;
@@ -550,6 +566,7 @@ int scan_topk(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out, i
 int search_fast_locked(knnx_index* ix, const float* q, int n, int k, float* D, int64_t* I);
 // knnx_range.hip
 int search_large_k_locked(knnx_index* ix, const float* q, int n, int k, float* D, int64_t* I);
+int search_large_k_pq_locked(knnx_index* ix, const float* q, int n, int k, float* D, int64_t* I);
 // knnx_ivf.hip
 int ivf_build_worklist(knnx_index* ix, const float* q_dev, int nq, hipStream_t st, const unsigned* gate);
 bool ivfm_usable(const knnx_index* ix, int nq, int k);
@@ -558,6 +575,11 @@ int scan_topk_ivf_multi(knnx_index* ix, const float* q_dev, int nq, int k, float
 bool ivfb_claim_all(knnx_index* ix, const int32_t* lists, const int32_t* pos, int64_t n);
 // knnx_ivfpq.hip
 int scan_topk_pq(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out, int64_t* I_out, hipStream_t st);
+// threshold passes (one front half, then any number of threshold scans over its probe lists and lookup tables)
+int pq_front(knnx_index* ix, const float* q_dev, int nq, hipStream_t st, const float** q_used, int* np_out);
+int pq_pass_top64(knnx_index* ix, int nq, int np, float* D64, hipStream_t st);
+int pq_pass_probed_rows(knnx_index* ix, int nq, int np, std::vector<int64_t>& total, hipStream_t st);
+int pq_pass_threshold_scan(knnx_index* ix, int nq, int np, const float* thr_h, unsigned cap, std::vector<unsigned>& counts, hipStream_t st);
 // decoded rows of n ids (device) -> out f32 [n][d] in the ORIGINAL space (back-rotated when the index has a rotation; scratch slot 5);
 // on an index with a refine store: the stored rows themselves
 int pq_decode_rows(knnx_index* ix, const int64_t* ids_dev, int64_t n, float* out_dev, hipStream_t st);

@@ -9,21 +9,12 @@
 // list id), the probed lists of every query, its lookup table, the ADC list scan, the merge of the per-workgroup lists.
 // ---------------------------------------------------------------------------------------------
 //
-// Refine store (knnx_ivfpq_set_refine): the ADC stage keeps kc = k x k_factor candidates instead of k -- for kc <= 64 the scan and
-// merge above, for more the workgroup-queue scan and the LDS selection (pq_cand_scan_kernel, pq_cand_select_kernel) with the
-// shares capped so that shares x kc <= PQ_SEL_MAX -- and the candidates are re-scored from the fp16 rows with the ORIGINAL query
-// (pq_rescore_kernel) and ranked (pq_refine_topk_kernel).
-int scan_topk_pq(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out, int64_t* I_out, hipStream_t st) {
-  if (nq < 1 || nq > PQ_PASS || k < 1 || k > KNNX_MAX_K_FAST || !ix->cent || !ix->ivf_nlist)
-    return fail(KNNX_E_STATE, "internal: IVF-PQ pass misuse");
-  const int kc = ix->pq.refine ? k * ix->pq.k_factor : k;
-  if (kc > PQ_REFINE_MAX)
-    return fail(KNNX_E_ARG, "k x k_factor = " + std::to_string(k) + " x " + std::to_string(ix->pq.k_factor) + " exceeds " +
-                                std::to_string(PQ_REFINE_MAX) + " candidates per query");
-  const float* q_orig = q_dev;
+// The front half of a pass, shared by the top-k pass and the threshold passes: rotation, query prep, coarse dump, select / mark,
+// probe lists and lookup tables.  Leaves probe / pscore / pcnt / lut of the nq queries in ix->pqs; *q_used = the queries the ADC
+// stage scores (the rotated ones behind an OPQ rotation), *np_out = lists probed per query.
+int pq_front(knnx_index* ix, const float* q_dev, int nq, hipStream_t st, const float** q_used, int* np_out) {
   const int np = std::min(ix->ivf_nprobe, ix->ivf_nlist);
   HIPCHK(ix->pqs.alloc(ix->d, (size_t)ix->ivf_nlist, ix->pq.m, np));
-  if (ix->pq.refine) HIPCHK(ix->pqs.alloc_refine());
   knnx_index* c = ix->cent;
   const int nblk = (nq + KNN_NQ - 1) / KNN_NQ;
   if (ix->pq.rot) {  // OPQ: everything below sees q' = A q
@@ -50,7 +41,31 @@ int scan_topk_pq(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out
   HIPCHK(launch_ivf_select_mark(ix->pqs.scores, nq, np, ix->ivf_nlist, ix->pqs.masks, st));
   HIPCHK(launch_pq_probe(ix->pqs.masks, ix->pqs.scores, nq, ix->ivf_nlist, np, ix->pqs.pcnt, ix->pqs.probe, ix->pqs.pscore, st));
   HIPCHK(launch_pq_lut(q_dev, nq, ix->d, ix->pq.m, ix->pq.cb, ix->pqs.lut, st));
-  int nsplit = std::max(1, std::min(std::min(np, PQ_MAX_SPLIT), (PQ_TARGET_WG + nq - 1) / nq));
+  *q_used = q_dev;
+  *np_out = np;
+  return 0;
+}
+
+// shares a query's probed lists are split into (workgroups per query of the ADC scans)
+static int pq_nsplit(int np, int nq) { return std::max(1, std::min(std::min(np, PQ_MAX_SPLIT), (PQ_TARGET_WG + nq - 1) / nq)); }
+
+// Refine store (knnx_ivfpq_set_refine): the ADC stage keeps kc = k x k_factor candidates instead of k -- for kc <= 64 the scan and
+// merge above, for more the workgroup-queue scan and the LDS selection (pq_cand_scan_kernel, pq_cand_select_kernel) with the
+// shares capped so that shares x kc <= PQ_SEL_MAX -- and the candidates are re-scored from the fp16 rows with the ORIGINAL query
+// (pq_rescore_kernel) and ranked (pq_refine_topk_kernel).
+int scan_topk_pq(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out, int64_t* I_out, hipStream_t st) {
+  if (nq < 1 || nq > PQ_PASS || k < 1 || k > KNNX_MAX_K_FAST || !ix->cent || !ix->ivf_nlist)
+    return fail(KNNX_E_STATE, "internal: IVF-PQ pass misuse");
+  const int kc = ix->pq.refine ? k * ix->pq.k_factor : k;
+  if (kc > PQ_REFINE_MAX)
+    return fail(KNNX_E_ARG, "k x k_factor = " + std::to_string(k) + " x " + std::to_string(ix->pq.k_factor) + " exceeds " +
+                                std::to_string(PQ_REFINE_MAX) + " candidates per query");
+  const float* q_orig = q_dev;
+  int np = 0;
+  int r = pq_front(ix, q_orig, nq, st, &q_dev, &np);
+  if (r) return r;
+  if (ix->pq.refine) HIPCHK(ix->pqs.alloc_refine());
+  int nsplit = pq_nsplit(np, nq);
   if (ix->pq.refine) {
     PqScratch& S = ix->pqs;
     HIPCHK(ix->prof.begin(ix->prof.on, st));
@@ -75,6 +90,80 @@ int scan_topk_pq(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out
   HIPCHK(launch_merge_u32(ix->pqs.part_s, ix->pqs.part_i, ix->pqs.part_n, nsplit, nq, k, nq, k, ix->id_base, ix->ivf.idmap, D_out, I_out,
                           nullptr, st));
   return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Threshold passes (the switch knnx_ivfpq_set_threshold_scan; knnx_range.hip drives them): after pq_front, any number of
+// pq_range_scan_kernel launches over the same probe lists and lookup tables with new per-query thresholds.
+// ---------------------------------------------------------------------------------------------
+// the plain ADC top-64 scores of the pass whose front half is in ix->pqs (no refine stage) -> D64 host [nq][64], -FLT_MAX padded.
+// Synchronises.
+int pq_pass_top64(knnx_index* ix, int nq, int np, float* D64, hipStream_t st) {
+  PqScratch& S = ix->pqs;
+  const int nsplit = pq_nsplit(np, nq), k = KNNX_MAX_K_FAST;
+  HIPCHK(launch_pq_adc_scan(ix->pq.codes, ix->pq.m, S.lut, S.probe, S.pscore, S.pcnt, np, nsplit, ix->ivf.tile0, ix->ivf.size, ix->ivf.idmap, k,
+                            nq, S.part_s, S.part_i, S.part_n, st));
+  HIPCHK(launch_merge_u32(S.part_s, S.part_i, S.part_n, nsplit, nq, k, nq, k, ix->id_base, ix->ivf.idmap, ix->flat.D_dev, ix->flat.I_dev,
+                          nullptr, st));
+  HIPCHK(hipMemcpyAsync(D64, ix->flat.D_dev, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return 0;
+}
+
+// rows in the probed lists of every query of the pass -> total [nq].  Synchronises.
+int pq_pass_probed_rows(knnx_index* ix, int nq, int np, std::vector<int64_t>& total, hipStream_t st) {
+  std::vector<unsigned> pc((size_t)nq);
+  std::vector<int> pr((size_t)nq * np);
+  HIPCHK(hipMemcpyAsync(pc.data(), ix->pqs.pcnt, pc.size() * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(pr.data(), ix->pqs.probe, pr.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  total.assign((size_t)nq, 0);
+  for (int q = 0; q < nq; ++q)
+    for (int p = 0; p < std::min<int>((int)pc[q], np); ++p) {
+      const int l = pr[(size_t)q * np + p];
+      if (l < 0 || l >= ix->ivf_nlist || (size_t)l >= ix->pq.size_h.size()) return fail(KNNX_E_STATE, "internal: probe list out of range");
+      total[q] += ix->pq.size_h[l];
+    }
+  return 0;
+}
+
+// one threshold scan of the pass: thr_h [nq] (host; +INFINITY skips a query) -> counts [nq] (exact), hits in ix->range at q * cap.
+// Synchronises.
+int pq_pass_threshold_scan(knnx_index* ix, int nq, int np, const float* thr_h, unsigned cap, std::vector<unsigned>& counts, hipStream_t st) {
+  PqScratch& S = ix->pqs;
+  HIPCHK(S.alloc_threshold());
+  HIPCHK(hipMemcpyAsync(S.tthr, thr_h, (size_t)nq * sizeof(float), hipMemcpyHostToDevice, st));
+  HIPCHK(ix->prof.begin(ix->prof.on, st));
+  HIPCHK(launch_pq_range_scan(ix->pq.codes, ix->pq.m, S.lut, S.probe, S.pscore, S.pcnt, np, pq_nsplit(np, nq), ix->ivf.tile0, ix->ivf.size,
+                              S.tthr, S.tcnt, cap, ix->range.s, ix->range.i, nq, st));
+  HIPCHK(ix->prof.end(ix->prof.on, st));
+  counts.assign((size_t)nq, 0u);
+  HIPCHK(hipMemcpyAsync(counts.data(), S.tcnt, (size_t)nq * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  ++ix->pq.thr_scans;
+  return 0;
+}
+
+extern "C" int knnx_ivfpq_set_threshold_scan(knnx_index* ix, int on) {
+  if (!ix) return fail(KNNX_E_ARG, "index is null");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  if (!ix->pq.m) return fail(KNNX_E_STATE, "not an IVF-PQ index");
+  ix->pq.threshold_scan = on != 0;
+  return KNNX_OK;
+}
+extern "C" int knnx_ivfpq_threshold_scan(const knnx_index* ix) { return ix && ix->pq.m && ix->pq.threshold_scan ? 1 : 0; }
+
+// counters of the threshold passes since the index was created: queries served with k > 64, threshold scans launched (one launch
+// serves a whole group), scans summed over the queries that took part in them, hits fetched to the host
+extern "C" int knnx_ivfpq_threshold_stats(knnx_index* ix, int64_t* queries, int64_t* launches, int64_t* query_scans, int64_t* hits) {
+  if (!ix) return fail(KNNX_E_ARG, "index is null");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  if (!ix->pq.m) return fail(KNNX_E_STATE, "not an IVF-PQ index");
+  if (queries) *queries = ix->pq.thr_queries;
+  if (launches) *launches = ix->pq.thr_scans;
+  if (query_scans) *query_scans = ix->pq.thr_query_scans;
+  if (hits) *hits = ix->pq.thr_hits;
+  return KNNX_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

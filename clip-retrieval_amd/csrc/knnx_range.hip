@@ -1,6 +1,7 @@
 // knnx_range.hip -- range scans and the large-k search built on them (host side; see knnx_host.h).
 
 #include "knnx_host.h"
+#include "knnx_descent.h"
 
 // range scan of <= KNN_NQ queries; leaves per-query counts in `counts` and the hits on the device
 // (query i's hits at range_s/range_i[i*cap .. i*cap+counts[i]), cap = range_pool / nq)
@@ -180,21 +181,70 @@ static int range_fetch(knnx_index* ix, int nq, const std::vector<unsigned>& coun
   return 0;
 }
 
+// ---- IVF-PQ with the threshold-scan switch on (knnx_ivfpq_set_threshold_scan): the ADC scan in threshold mode feeds the same pools ----
+// stage a group of <= PQ_PASS queries and run the front half of their pass (knnx_ivfpq.hip: pq_front)
+static int pq_pass_begin(knnx_index* ix, const float* q_host, int nq, int* np) {
+  hipStream_t st = ix->stream;
+  int r = ensure_pin(ix, (size_t)PQ_PASS * ix->d * sizeof(float));
+  if (r) return r;
+  if (scratch_acquire(ix, st)) return KNNX_E_HIP;
+  memcpy(ix->pin.p, q_host, (size_t)nq * ix->d * sizeof(float));
+  HIPCHK(hipMemcpyAsync(ix->flat.q_dev, ix->pin.p, (size_t)nq * ix->d * sizeof(float), hipMemcpyHostToDevice, st));
+  const float* used = nullptr;
+  return pq_front(ix, ix->flat.q_dev, nq, st, &used, np);
+}
+
+// range scan of <= PQ_PASS queries of an IVF-PQ index: the rows of the probed lists whose ADC score is > thr.  Counts and hits as
+// range_scan leaves them, the device counters in ix->pqs.tcnt.
+static int range_scan_pq(knnx_index* ix, const float* q_host, int nq, float thr, std::vector<unsigned>& counts, unsigned* cap_out) {
+  int np = 0;
+  int r = pq_pass_begin(ix, q_host, nq, &np);
+  if (r) return r;
+  const std::vector<float> th((size_t)nq, thr);
+  for (;;) {
+    if (ix->range.pool == 0 && (r = range_pool_alloc(ix, (size_t)1 << 21))) return r;
+    const unsigned cap = (unsigned)std::min<size_t>(ix->range.pool / (size_t)nq, 0xffffffffu);
+    if ((r = pq_pass_threshold_scan(ix, nq, np, th.data(), cap, counts, ix->stream))) return r;
+    unsigned mx = 0;
+    for (int i = 0; i < nq; ++i) mx = std::max(mx, counts[i]);
+    if (mx <= cap) {
+      *cap_out = cap;
+      return 0;
+    }
+    // overflow: regrow and rescan over the same front half (the counts are exact even when the slices overflowed)
+    size_t want = ix->range.pool;
+    while (want / (size_t)nq < (size_t)mx) want <<= 1;
+    if (want > RANGE_POOL_MAX) return fail(KNNX_E_NOMEM, "range_search result exceeds the 512 Mi-hit scratch limit");
+    if ((r = range_pool_alloc(ix, want))) return r;
+  }
+}
+
+// what an IVF-PQ index answers to a range_search it does not serve (0: it serves it, or is no IVF-PQ index).  Caller holds ix->mu.
+static int pq_range_refusal(const knnx_index* ix) {
+  if (!ix->pq.m) return 0;
+  if (!ix->pq.threshold_scan) return fail(KNNX_E_UNSUPPORTED, "range_search is not supported on an IVF-PQ index");
+  if (ix->pq.refine)
+    return fail(KNNX_E_UNSUPPORTED, "range_search is not supported on an IVF-PQ index with a refine store (it would need the exact score of every probed row)");
+  return 0;
+}
+
 extern "C" int knnx_range_search(knnx_index* ix, const float* q, int n, float thresh, int64_t* lims, float* D,
                                  int64_t* I) {
   if (!ix || !lims || (n > 0 && !q) || n < 0) return fail(KNNX_E_ARG, "bad range_search arguments");
   if ((D == nullptr) != (I == nullptr)) return fail(KNNX_E_ARG, "D and I must both be null or both be set");
-  if (ix->pq.m) return fail(KNNX_E_UNSUPPORTED, "range_search is not supported on an IVF-PQ index");
   std::lock_guard<std::mutex> lk(ix->mu);
+  if (pq_range_refusal(ix)) return KNNX_E_UNSUPPORTED;
   if (set_dev(ix)) return KNNX_E_HIP;
   const bool fill = D != nullptr;
+  const bool pq = ix->pq.m != 0;
+  const int step = pq ? PQ_PASS : KNN_NQ;
   int64_t run = 0;
   std::vector<unsigned> counts;
   if (!fill) lims[0] = 0;
-  for (int o = 0; o < n; o += KNN_NQ) {
-    const int nq = std::min(KNN_NQ, n - o);
+  for (int o = 0; o < n; o += step) {
+    const int nq = std::min(step, n - o);
     unsigned cap = 0;
-    int r = range_scan(ix, q + (size_t)o * ix->d, nq, thresh, counts, &cap);
+    int r = pq ? range_scan_pq(ix, q + (size_t)o * ix->d, nq, thresh, counts, &cap) : range_scan(ix, q + (size_t)o * ix->d, nq, thresh, counts, &cap);
     if (r) return r;
     if (!fill) {
       for (int i = 0; i < nq; ++i) {
@@ -207,7 +257,7 @@ extern "C" int knnx_range_search(knnx_index* ix, const float* q, int n, float th
     for (int i = 0; i < nq; ++i)
       if (lims[o + i + 1] - lims[o + i] != (int64_t)counts[i])
         return fail(KNNX_E_STATE, "lims do not match this query/threshold (index changed between the two calls?)");
-    r = range_fetch(ix, nq, counts, cap, D + lims[o], I + lims[o]);
+    r = range_fetch(ix, nq, counts, cap, D + lims[o], I + lims[o], pq ? ix->pqs.tcnt.p : nullptr);
     if (r) return r;
   }
   return KNNX_OK;
@@ -220,9 +270,11 @@ extern "C" int knnx_range_search(knnx_index* ix, const float* q, int n, float th
 extern "C" int knnx_range_search_once(knnx_index* ix, const float* q, int n, float thresh, int64_t* lims, float* D, int64_t* I,
                                       int64_t capacity) {
   if (!ix || !lims || (n > 0 && !q) || n < 0 || capacity < 0 || (capacity > 0 && (!D || !I))) return fail(KNNX_E_ARG, "bad range_search_once arguments");
-  if (ix->pq.m) return fail(KNNX_E_UNSUPPORTED, "range_search is not supported on an IVF-PQ index");
   std::lock_guard<std::mutex> lk(ix->mu);
+  if (pq_range_refusal(ix)) return KNNX_E_UNSUPPORTED;
   if (set_dev(ix)) return KNNX_E_HIP;
+  const bool pq = ix->pq.m != 0;
+  const int step = pq ? PQ_PASS : KNN_NQ;
   int64_t run = 0;
   bool fits = true;
   std::vector<unsigned> counts;
@@ -240,10 +292,10 @@ extern "C" int knnx_range_search_once(knnx_index* ix, const float* q, int n, flo
     counts.resize(n);
     return range_fetch(ix, n, counts, cap, D, I, cnt_dev);
   }
-  for (int o = 0; o < n; o += KNN_NQ) {
-    const int nq = std::min(KNN_NQ, n - o);
+  for (int o = 0; o < n; o += step) {
+    const int nq = std::min(step, n - o);
     unsigned cap = 0;
-    int r = range_scan(ix, q + (size_t)o * ix->d, nq, thresh, counts, &cap);
+    int r = pq ? range_scan_pq(ix, q + (size_t)o * ix->d, nq, thresh, counts, &cap) : range_scan(ix, q + (size_t)o * ix->d, nq, thresh, counts, &cap);
     if (r) return r;
     const int64_t first = run;
     for (int i = 0; i < nq; ++i) {
@@ -252,7 +304,7 @@ extern "C" int knnx_range_search_once(knnx_index* ix, const float* q, int n, flo
     }
     if (run > capacity) fits = false;
     if (fits) {
-      r = range_fetch(ix, nq, counts, cap, D + first, I + first);
+      r = range_fetch(ix, nq, counts, cap, D + first, I + first, pq ? ix->pqs.tcnt.p : nullptr);
       if (r) return r;
     }
   }
@@ -420,6 +472,142 @@ int search_large_k_locked(knnx_index* ix, const float* q, int n, int k, float* D
         Iq[j] = -1;
       }
     }
+  }
+  return KNNX_OK;
+}
+
+// k > 64 on an IVF-PQ index with the threshold-scan switch on.  A group of queries (up to PQ_PASS; fewer when group x 16 kc hits would
+// not fit the pools) runs the front half of the pass ONCE; the k = 64 ADC pass gives every query its 32nd and 64th score; then all
+// queries descend together (knnx_descent.h), one threshold scan and one synchronisation per step for the whole group, a finished
+// query riding along with thr = +INFINITY.  A query whose probed lists hold <= 2 kc rows takes them all in the first scan.  The hits
+// (score, id) are ranked on the host: (ADC score descending, id ascending), the first kc = k (k x k_factor with a refine store) kept;
+// with a refine store these candidates are re-scored from the stored rows (pq_rescore_kernel) and ranked again by (exact score
+// descending, id ascending).  Caller holds ix->mu.
+int search_large_k_pq_locked(knnx_index* ix, const float* q, int n, int k, float* D, int64_t* I) {
+  typedef std::pair<float, int64_t> Hit;
+  const bool refine = ix->pq.refine;
+  const int64_t kc = refine ? (int64_t)k * ix->pq.k_factor : (int64_t)k;
+  if (kc > KNNX_MAX_K)
+    return fail(KNNX_E_ARG, "k x k_factor = " + std::to_string(k) + " x " + std::to_string(ix->pq.k_factor) + " exceeds " +
+                                std::to_string(KNNX_MAX_K) + " candidates per query");
+  hipStream_t st = ix->stream;
+  const int K64 = KNNX_MAX_K_FAST;
+  const int gmax = (int)std::max<size_t>(1, std::min<size_t>((size_t)PQ_PASS, RANGE_POOL_MAX / ((size_t)16 * (size_t)kc)));
+  auto better = [](const Hit& a, const Hit& b) { return a.first > b.first || (a.first == b.first && a.second < b.second); };
+  std::vector<float> d64, thr, hd, es;
+  std::vector<int64_t> total, hi, cand;
+  std::vector<unsigned> counts, sel;
+  for (int o = 0; o < n;) {
+    const int gq = std::min(gmax, n - o);
+    int np = 0;
+    int r = pq_pass_begin(ix, q + (size_t)o * ix->d, gq, &np);
+    if (r) return r;
+    d64.resize((size_t)gq * K64);
+    if ((r = pq_pass_top64(ix, gq, np, d64.data(), st))) return r;
+    if ((r = pq_pass_probed_rows(ix, gq, np, total, st))) return r;
+    std::vector<PqDescent> ds((size_t)gq);
+    std::vector<int> state((size_t)gq, 0);  // 0: descending, 1: its threshold is final, the hits did not fit yet, 2: fetched
+    std::vector<std::vector<Hit>> hits((size_t)gq);
+    for (int i = 0; i < gq; ++i) ds[i].start(d64[(size_t)i * K64 + K64 / 2 - 1], d64[(size_t)i * K64 + K64 - 1], kc, total[i]);
+    thr.assign((size_t)gq, 0.f);
+    for (int left = gq; left > 0;) {
+      if (ix->range.pool == 0 && (r = range_pool_alloc(ix, (size_t)1 << 21))) return r;
+      const unsigned cap = (unsigned)std::min<size_t>(ix->range.pool / (size_t)gq, 0xffffffffu);
+      for (int i = 0; i < gq; ++i) thr[i] = state[i] == 2 ? INFINITY : ds[i].thr;
+      if ((r = pq_pass_threshold_scan(ix, gq, np, thr.data(), cap, counts, st))) return r;
+      sel.assign((size_t)gq, 0u);
+      unsigned grow = 0;
+      int64_t nsel = 0;
+      for (int i = 0; i < gq; ++i) {
+        if (state[i] == 2) continue;
+        ++ix->pq.thr_query_scans;
+        if (state[i] == 0) {
+          if (ds[i].next((int64_t)counts[i]) == PqDescent::SCAN) continue;
+          state[i] = 1;
+        }
+        if (counts[i] <= cap) {
+          sel[i] = counts[i];
+          nsel += counts[i];
+        } else {
+          grow = std::max(grow, counts[i]);
+        }
+      }
+      if (nsel > 0) {
+        HIPCHK(hipMemcpyAsync(ix->pqs.tfetch, sel.data(), (size_t)gq * sizeof(unsigned), hipMemcpyHostToDevice, st));
+        hd.resize((size_t)nsel);
+        hi.resize((size_t)nsel);
+        if ((r = range_fetch(ix, gq, sel, cap, hd.data(), hi.data(), ix->pqs.tfetch))) return r;
+        ix->pq.thr_hits += nsel;
+      }
+      int64_t at = 0;
+      for (int i = 0; i < gq; ++i) {
+        if (state[i] != 1 || counts[i] > cap) continue;
+        std::vector<Hit>& h = hits[i];
+        h.resize((size_t)sel[i]);
+        for (unsigned j = 0; j < sel[i]; ++j) h[j] = Hit(hd[(size_t)at + j], hi[(size_t)at + j]);
+        at += sel[i];
+        if ((int64_t)h.size() > kc) {
+          std::nth_element(h.begin(), h.begin() + kc, h.end(), better);
+          h.resize((size_t)kc);
+        }
+        std::sort(h.begin(), h.end(), better);
+        state[i] = 2;
+        --left;
+      }
+      if (grow) {  // a final threshold whose hits overflowed its slice: regrow, scan it again
+        size_t want = ix->range.pool;
+        while (want / (size_t)gq < (size_t)grow) want <<= 1;
+        if (want > RANGE_POOL_MAX) return fail(KNNX_E_NOMEM, "large-k search result exceeds the 512 Mi-hit scratch limit");
+        if ((r = range_pool_alloc(ix, want))) return r;
+      }
+    }
+    ix->pq.thr_queries += gq;
+    if (!refine) {
+      for (int i = 0; i < gq; ++i) {
+        float* Dq = D + (size_t)(o + i) * k;
+        int64_t* Iq = I + (size_t)(o + i) * k;
+        const std::vector<Hit>& h = hits[i];
+        for (int j = 0; j < k; ++j) {
+          Dq[j] = j < (int)h.size() ? h[j].first : -FLT_MAX;
+          Iq[j] = j < (int)h.size() ? h[j].second : -1;
+        }
+      }
+    } else {
+      // the kc candidates of every query, re-scored against the ORIGINAL query (still in flat.q_dev), a few queries per launch
+      const int qc = (int)std::max<int64_t>(1, std::min<int64_t>(gq, ((int64_t)1 << 22) / kc));
+      int64_t* cand_dev = nullptr;
+      float* es_dev = nullptr;
+      if ((r = ensure_scratch(ix, 3, (size_t)qc * kc * sizeof(int64_t), (void**)&cand_dev))) return r;
+      if ((r = ensure_scratch(ix, 4, (size_t)qc * kc * sizeof(float), (void**)&es_dev))) return r;
+      for (int c0 = 0; c0 < gq; c0 += qc) {
+        const int m = std::min(qc, gq - c0);
+        cand.assign((size_t)m * kc, -1);
+        for (int i = 0; i < m; ++i)
+          for (size_t j = 0; j < hits[c0 + i].size(); ++j) cand[(size_t)i * kc + j] = hits[c0 + i][j].second;
+        es.resize((size_t)m * kc);
+        HIPCHK(hipMemcpyAsync(cand_dev, cand.data(), cand.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        HIPCHK(launch_pq_rescore(ix->rows, ix->d, ix->flat.q_dev + (size_t)c0 * ix->d, m, ix->id_base, ix->ntotal, ix->ivf.inv, cand_dev, (int)kc,
+                                 es_dev, st));
+        HIPCHK(hipMemcpyAsync(es.data(), es_dev, es.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (int i = 0; i < m; ++i) {
+          std::vector<Hit>& h = hits[c0 + i];
+          for (size_t j = 0; j < h.size(); ++j) h[j].first = es[(size_t)i * kc + j];
+          if ((int64_t)h.size() > (int64_t)k) {
+            std::nth_element(h.begin(), h.begin() + k, h.end(), better);
+            h.resize((size_t)k);
+          }
+          std::sort(h.begin(), h.end(), better);
+          float* Dq = D + (size_t)(o + c0 + i) * k;
+          int64_t* Iq = I + (size_t)(o + c0 + i) * k;
+          for (int j = 0; j < k; ++j) {
+            Dq[j] = j < (int)h.size() ? h[j].first : -FLT_MAX;
+            Iq[j] = j < (int)h.size() ? h[j].second : -1;
+          }
+        }
+      }
+    }
+    o += gq;
   }
   return KNNX_OK;
 }

@@ -278,6 +278,24 @@ class Mi355xIndex(_FaissShaped):
     def k_factor(self, v):
         check(self._lib, self._lib.knnx_ivfpq_set_k_factor(self._h, int(v)), "knnx")
 
+    @property
+    def pq_threshold_scan(self):
+        """The threshold mode of the ADC scan (include/knnx.h: knnx_ivfpq_set_threshold_scan): with it on, an IVF-PQ index serves
+        k > 64 (up to 131 072) and range_search; off -- the default -- it refuses both as it always has.  False on an index that is
+        not IVF-PQ; setting it there is an error."""
+        return bool(self._lib.knnx_ivfpq_threshold_scan(self._h)) if self._h else False
+
+    @pq_threshold_scan.setter
+    def pq_threshold_scan(self, on):
+        check(self._lib, self._lib.knnx_ivfpq_set_threshold_scan(self._h, 1 if on else 0), "knnx")
+
+    def pq_threshold_stats(self):
+        """(queries served with k > 64, threshold-scan launches, scans summed over the queries that took part, hits fetched) since the
+        index was created (include/knnx.h: knnx_ivfpq_threshold_stats)."""
+        v = [C.c_int64(0) for _ in range(4)]
+        check(self._lib, self._lib.knnx_ivfpq_threshold_stats(self._h, *[C.byref(x) for x in v]), "knnx")
+        return tuple(int(x.value) for x in v)
+
     def pq_arena_bytes(self):
         """(bytes of the code arena, bytes of the row arena -- 0 without a refine store) of an IVF-PQ index."""
         a, b = C.c_int64(0), C.c_int64(0)
@@ -483,6 +501,16 @@ class ShardedMi355xIndex(_FaissShaped):
     def k_factor(self, v):
         for g in range(self.nshards):
             check(self._lib, self._lib.knnx_ivfpq_set_k_factor(C.c_void_p(self._lib.knnx_shards_get(self._h, g)), int(v)), "knnx")
+
+    @property
+    def pq_threshold_scan(self):
+        """The threshold-scan switch as carried by the first shard (Mi355xIndex.pq_threshold_scan); the setter sets every shard."""
+        return bool(self._lib.knnx_ivfpq_threshold_scan(C.c_void_p(self._lib.knnx_shards_get(self._h, 0)))) if self.nshards else False
+
+    @pq_threshold_scan.setter
+    def pq_threshold_scan(self, on):
+        for g in range(self.nshards):
+            check(self._lib, self._lib.knnx_ivfpq_set_threshold_scan(C.c_void_p(self._lib.knnx_shards_get(self._h, g)), 1 if on else 0), "knnx")
 
     @property
     def nshards(self):
@@ -1383,7 +1411,7 @@ def train_ivfpq(x_f16, nlist, M, niter=8, pq_niter=10, seed=0, device=0, sample_
     return centroids, cb
 
 
-def _ivfpq_begin(d, nlist, M, centroids, codebooks, sizes, device, id_base, rotation=None, refine=False, k_factor=1):
+def _ivfpq_begin(d, nlist, M, centroids, codebooks, sizes, device, id_base, rotation=None, refine=False, k_factor=1, threshold_scan=False):
     index = Mi355xIndex(d, device=device, id_base=id_base)
     index.set_pq_quantizer(M, codebooks)
     if rotation is not None:
@@ -1391,6 +1419,8 @@ def _ivfpq_begin(d, nlist, M, centroids, codebooks, sizes, device, id_base, rota
     if refine:
         index.set_pq_refine()
     index.k_factor = k_factor
+    if threshold_scan:  # (off is the state of a new index: nothing is called for it)
+        index.pq_threshold_scan = True
     cpad = np.ascontiguousarray(index._pad(np.asarray(centroids, dtype=np.float16)))  # pylint: disable=protected-access
     check(index._lib, index._lib.knnx_ivf_begin(index._h, nlist, cpad.ctypes.data, np.ascontiguousarray(sizes, dtype=np.int64).ctypes.data), "knnx")  # pylint: disable=protected-access
     return index
@@ -1404,13 +1434,13 @@ def _ivfpq_end(index, nlist, nprobe, centroids, id_base, n):
 
 
 def _ivfpq_encode_chunks(chunks, n, d, nlist, M, centroids, codebooks, lists, nprobe, device, id_base, rotation=None, refine=False,
-                         k_factor=1):
+                         k_factor=1, threshold_scan=False):
     """Rows (an iterator of (offset, fp16 rows)) -> IVF-PQ index: every row is encoded into the next free slot of its list.  With a
     rotation the rows are the UN-ROTATED ones (the index rotates each chunk) and `lists` are those of the rotated rows."""
     sizes = np.bincount(lists, minlength=nlist).astype(np.int64)
     if sizes.shape[0] != nlist:
         raise ValueError("a list id is outside [0, nlist)")
-    index = _ivfpq_begin(d, nlist, M, centroids, codebooks, sizes, device, id_base, rotation, refine, k_factor)
+    index = _ivfpq_begin(d, nlist, M, centroids, codebooks, sizes, device, id_base, rotation, refine, k_factor, threshold_scan)
     lib = index._lib  # pylint: disable=protected-access
     cursor = np.zeros(nlist, dtype=np.int64)
     for o, x in chunks:
@@ -1443,12 +1473,13 @@ def _assign_chunks(chunks, n, d, nlist, centroids, device, A):
 
 
 def build_ivfpq_index(x_f16, nlist, M, nprobe=16, niter=8, pq_niter=10, seed=0, device=0, id_base=0, centroids=None, codebooks=None,
-                      chunk=1 << 20, opq=False, rotation=None, refine=False, k_factor=1):
+                      chunk=1 << 20, opq=False, rotation=None, refine=False, k_factor=1, threshold_scan=False):
     """fp16 rows [N, d] -> HBM-resident IVF-PQ index (ids = id_base + row number).  Trains (train_ivfpq) unless both `centroids` and
     `codebooks` are given; lists by the MFMA assignment kernel; codes by the device encoder.
     opq=True trains an OPQ rotation first (train_opq), rotation=A uses that one; centroids / codebooks, given or trained, are those of
     the rotated space.  The index keeps the rotation: it is searched with, and reconstructs, un-rotated vectors.
-    refine=True keeps the fp16 rows next to the codes (Mi355xIndex.set_pq_refine) and re-scores k x k_factor candidates exactly."""
+    refine=True keeps the fp16 rows next to the codes (Mi355xIndex.set_pq_refine) and re-scores k x k_factor candidates exactly.
+    threshold_scan=True switches on k > 64 and range_search (Mi355xIndex.pq_threshold_scan; off by default)."""
     n, d = x_f16.shape
     A, _ = _resolve_rotation(x_f16, M, opq, rotation, seed, device)
     if centroids is None or codebooks is None:
@@ -1457,17 +1488,19 @@ def build_ivfpq_index(x_f16, nlist, M, nprobe=16, niter=8, pq_niter=10, seed=0, 
     centroids = np.asarray(centroids).astype(np.float16)
     lists, rotate_s = _assign_chunks(((o, x_f16[o:o + chunk]) for o in range(0, n, chunk)), n, d, nlist, centroids, device, A)
     index = _ivfpq_encode_chunks(((o, x_f16[o:o + chunk]) for o in range(0, n, chunk)), n, d, nlist, M, centroids, codebooks, lists, nprobe,
-                                 device, id_base, A, refine, k_factor)
+                                 device, id_base, A, refine, k_factor, threshold_scan)
     index.rotate_s = rotate_s
     return index
 
 
 def build_ivfpq_index_from_folder(path, nlist, M, nprobe=16, niter=8, pq_niter=10, seed=0, device=0, centroids=None, codebooks=None,
-                                  max_points_per_centroid=256, chunk=1 << 20, opq=False, rotation=None, refine=False, k_factor=1):
+                                  max_points_per_centroid=256, chunk=1 << 20, opq=False, rotation=None, refine=False, k_factor=1,
+                                  threshold_scan=False):
     """`clip inference` output folder (img_emb_*.npy) -> IVF-PQ index, streaming the partitions: training on a strided sample of the
     whole folder, then one assignment pass and one encoding pass.  The result can be save_index()ed (self-contained).  opq / rotation
     as in build_ivfpq_index (the rotation is trained on the same strided sample).  refine / k_factor as in build_ivfpq_index; a saved
-    refine index is loaded from its folder PLUS these embeddings (save_index(index, folder, embeddings_folder=...))."""
+    refine index is loaded from its folder PLUS these embeddings (save_index(index, folder, embeddings_folder=...)).  threshold_scan as
+    in build_ivfpq_index; save_index records it."""
     src = path if isinstance(path, FolderRows) else FolderRows(path)
     A = None if rotation is None else np.ascontiguousarray(rotation, dtype=np.float32)
     if centroids is None or codebooks is None or (opq and A is None):
@@ -1481,7 +1514,7 @@ def build_ivfpq_index_from_folder(path, nlist, M, nprobe=16, niter=8, pq_niter=1
     centroids = np.asarray(centroids).astype(np.float16)
     lists, rotate_s = _assign_chunks(src.chunks(0, src.n, chunk), src.n, src.d, nlist, centroids, device, A)
     index = _ivfpq_encode_chunks(src.chunks(0, src.n, chunk), src.n, src.d, nlist, M, centroids, codebooks, lists, nprobe, device, 0, A,
-                                 refine, k_factor)
+                                 refine, k_factor, threshold_scan)
     index.rotate_s = rotate_s
     index.embeddings_folder = src.folder if hasattr(src, "folder") else None
     return index
@@ -1489,7 +1522,7 @@ def build_ivfpq_index_from_folder(path, nlist, M, nprobe=16, niter=8, pq_niter=1
 
 def build_ivfpq_index_device(fill_rows, n, d, nlist, M, nprobe=16, niter=8, pq_niter=10, seed=0, device=0, id_base=0, centroids=None,
                              codebooks=None, chunk=1 << 20, alloc=None, points_per_centroid=64, pq_sample_rows=PQ_SAMPLE_ROWS, opq=False,
-                             rotation=None, opq_sample_rows=OPQ_SAMPLE_ROWS, refine=False, k_factor=1):
+                             rotation=None, opq_sample_rows=OPQ_SAMPLE_ROWS, refine=False, k_factor=1, threshold_scan=False):
     """IVF-PQ index over n rows PRODUCED ON THE GPU (`fill_rows(dst_ptr, row0, count, stride)` as in build_ivf_index_device): the
     fp16 corpus never exists whole -- training samples, then per chunk one assignment pass and one encoding pass; the index keeps
     M bytes per row.  Returns (index, stats dict).
@@ -1569,7 +1602,7 @@ def build_ivfpq_index_device(fill_rows, n, d, nlist, M, nprobe=16, niter=8, pq_n
     b.close()
     del rot_keep
     t2 = time.perf_counter()
-    index = _ivfpq_begin(d, nlist, M, centroids, codebooks, sizes, device, id_base, A, refine, k_factor)
+    index = _ivfpq_begin(d, nlist, M, centroids, codebooks, sizes, device, id_base, A, refine, k_factor, threshold_scan)
     for o in range(0, n, chunk):
         m = min(chunk, n - o)
         fill_rows(rows_ptr, o, m, 1)
@@ -1589,7 +1622,8 @@ def _save_ivfpq_index(index, folder, embeddings_folder=None):
     ivf_pq_codes.npy (u8 [n, M] in id order), ivf_pq_lists.npy (int32 [n]) and ivf_pq_manifest.json (written last); an index with an
     OPQ rotation adds ivf_pq_rotation.npy (f32 [d, d]) and "opq": true in the manifest.  An index with a refine store adds "refine": true,
     "k_factor" and the embeddings folder (as save_index does for IVF-Flat) to the manifest: the rows are not written a second time, the
-    folder is loaded together with the embeddings."""
+    folder is loaded together with the embeddings.  An index with the threshold scan switched on adds "threshold_scan": true (only
+    then: every other folder is what it always was)."""
     import json  # pylint: disable=import-outside-toplevel
 
     cent = getattr(index, "ivf_centroids", None)
@@ -1619,11 +1653,26 @@ def _save_ivfpq_index(index, folder, embeddings_folder=None):
             raise ValueError(f"{src.folder}: {src.n} rows of width {src.d} cannot hold rows [{lo}, {hi}) of width {index.d}")
         man.update({"refine": True, "k_factor": int(index.k_factor), "embeddings": src.manifest(),
                     "embeddings_relative": os.path.relpath(os.path.abspath(src.folder), os.path.abspath(folder))})
+    man.update(ivfpq_threshold_scan_entry(index.pq_threshold_scan))
     tmp = os.path.join(folder, IVFPQ_MANIFEST + ".part")
     with open(tmp, "w", encoding="utf-8") as f:
         json.dump(man, f, indent=1)
     os.replace(tmp, os.path.join(folder, IVFPQ_MANIFEST))
     return man
+
+
+def ivfpq_threshold_scan_entry(on):
+    """What a saved IVF-PQ manifest says about the threshold-scan switch: {"threshold_scan": true} when it is on, nothing otherwise."""
+    return {"threshold_scan": True} if on else {}
+
+
+def read_ivfpq_threshold_scan(folder, man):
+    """The threshold-scan switch of a saved IVF-PQ manifest: False for a manifest without the key (every folder written before the
+    switch existed, and every index saved with it off), else the boolean it carries; anything but a boolean is refused."""
+    v = man.get("threshold_scan", False)
+    if not isinstance(v, bool):
+        raise ValueError(f"{folder}: \"threshold_scan\" must be true or false, got {v!r}")
+    return v
 
 
 def read_ivfpq_rotation(folder, man):
@@ -1719,13 +1768,18 @@ def _load_ivfpq_index(folder, device=0, row_range=None, devices=None, embeddings
     lists = np.load(os.path.join(folder, "ivf_pq_lists.npy"), mmap_mode="r")
     rot = read_ivfpq_rotation(folder, man)
     refine, kf, src = read_ivfpq_refine(folder, man, embeddings_folder)
+    thr_scan = read_ivfpq_threshold_scan(folder, man)
     slo, shi = man["row_range"]
     M = int(man["M"])
 
     def make(c, ls, lo_, dev):
         if refine:
-            return _ivfpq_refine_from_rows(src, c, ls, lo_, cent, cb, M, man["nprobe"], dev, kf, rotation=rot)
-        return _ivfpq_from_codes(c, ls, lo_, cent, cb, M, man["nprobe"], dev, rotation=rot)
+            ix = _ivfpq_refine_from_rows(src, c, ls, lo_, cent, cb, M, man["nprobe"], dev, kf, rotation=rot)
+        else:
+            ix = _ivfpq_from_codes(c, ls, lo_, cent, cb, M, man["nprobe"], dev, rotation=rot)
+        if thr_scan:
+            ix.pq_threshold_scan = True
+        return ix
 
     if cent.shape != (man["nlist"], man["d"]) or codes.shape != (shi - slo, M) or lists.shape[0] != shi - slo:
         raise ValueError(f"{folder}: the IVF-PQ files disagree with the manifest")

@@ -334,7 +334,11 @@ class KnnHotPath:
     def knn_search(self, query, modality, num_result_ids, clip_resource, deduplicate, use_safety_model, use_violence_detector):
         """(distances, indices): the index's answer cut at the first -1, minus the post filter's picks, each id once, best
         first.  (metadata_is_ordered_by_ivf needs faiss' IVF id mapping: serve with reorder_metadata_by_ivf_index=False, as the
-        LAION-5B recipes do, docs/laion5B_back.md:22.)"""
+        LAION-5B recipes do, docs/laion5B_back.md:22.)
+        An IVF-PQ index serves num_result_ids <= 64 as it stands; the Python default of 100, the front end's 3 000 and the >= 100 000
+        requests of the probe-widening branch below need its threshold scan switched on (Mi355xIndex.pq_threshold_scan, or
+        threshold_scan=True at build time; saved with the index) -- without it the index answers them with KNNX_E_UNSUPPORTED, which
+        is raised, never papered over.  No branch of this function depends on the switch."""
         if getattr(clip_resource, "metadata_is_ordered_by_ivf", False):
             raise NotImplementedError("metadata_is_ordered_by_ivf needs faiss' IVF id mapping; serve with reorder_metadata_by_ivf_index=False")
         index = clip_resource.image_index if modality == "image" else clip_resource.text_index

@@ -157,7 +157,7 @@ int knnx_ivf_add_assigned_device(knnx_index* ix, const void* rows_dev_f16, int64
  * the R of search returns the decoded vector f32(c_l) + concat_m C[m][code_m].
  * Build: knnx_ivfpq_set_quantizer on an empty index, then knnx_ivf_begin / knnx_ivf_add_assigned[_device] / knnx_ivf_end ENCODE
  * the rows (same list / position rules), or knnx_ivfpq_add_codes loads precomputed codes in their place.  The arena holds M bytes
- * per row.  k > 64 and range_search answer KNNX_E_UNSUPPORTED; add / attach / synth_fill / reset / reserve / knnx_ivf_set_lists
+ * per row.  k > 64 and range_search answer KNNX_E_UNSUPPORTED (unless switched on: knnx_ivfpq_set_threshold_scan below); add / attach / synth_fill / reset / reserve / knnx_ivf_set_lists
  * answer KNNX_E_STATE.  At most 2^32 - 1 padded rows per device. */
 int knnx_ivfpq_set_quantizer(knnx_index* ix, int M, const float* codebooks);
 int knnx_ivfpq_add_codes(knnx_index* ix, const uint8_t* codes, int64_t n, const int64_t* ids, const int32_t* lists, const int32_t* pos);
@@ -207,7 +207,7 @@ int knnx_ivfpq_get_rotation(knnx_index* ix, float* A);
  * store the un-rotated chunk AND encode it; knnx_ivfpq_add_codes answers KNNX_E_STATE (it has no rows to store).
  * knnx_ivfpq_set_k_factor: 1 .. 512, default 1 (faiss' default: the plain index's ids with exact scores); any time, any IVF-PQ index
  * (without a refine store it has no effect).  A search with k x k_factor > 512 answers KNNX_E_ARG and names both numbers.  k > 64 and
- * range_search stay KNNX_E_UNSUPPORTED.  knnx_shards_adopt takes IVF-PQ shards that all have a refine store or all have none and refuses
+ * range_search stay KNNX_E_UNSUPPORTED unless the threshold scan is switched on (next block).  knnx_shards_adopt takes IVF-PQ shards that all have a refine store or all have none and refuses
  * a mix; each shard refines its own candidates and the merge ranks the exact scores.  An index without a refine store is exactly the
  * two blocks above.  knnx_ivfpq_arena_bytes: bytes of the code arena and of the row arena (0 without a refine store). */
 int knnx_ivfpq_set_refine(knnx_index* ix, int on);
@@ -215,6 +215,30 @@ int knnx_ivfpq_refine(const knnx_index* ix); /* 1: the index has (or will be bui
 int knnx_ivfpq_set_k_factor(knnx_index* ix, int k_factor);
 int knnx_ivfpq_k_factor(const knnx_index* ix);
 int knnx_ivfpq_arena_bytes(knnx_index* ix, int64_t* code_bytes, int64_t* row_bytes);
+/* ---- Threshold scan on IVF-PQ: k > 64 and range_search (clip_back.py:356-369 asks for up to 1e5 results; clip_filter.py:52) ---------
+ * A switch per index, OFF by default: an index nobody switched on is exactly the three blocks above, refusals included.
+ * knnx_ivfpq_set_threshold_scan: any IVF-PQ index, any time (like knnx_ivfpq_set_k_factor); KNNX_E_STATE on an index that is not IVF-PQ.
+ * knnx_ivfpq_threshold_scan: 0 / 1; 0 on a non-PQ or null index.  With the switch ON:
+ *   search    64 < k <= 131072: the top k rows of the probed lists by (ADC score descending, id ascending), padded with -1 / -FLT_MAX
+ *             -- the contract of the IVF-PQ block for k <= 64, extended.  The scores are the SAME fp32 values (same LUT, cs + (sum over m
+ *             in order)), so the first 64 results of a k > 64 search equal the k = 64 search bit for bit, D and I, and a query gets the
+ *             same answer alone and in a batch.  R comes from knnx_reconstruct: decoded and back-rotated rows, or the stored rows of a
+ *             refine store.  How: the ADC scan in threshold mode (every row scoring > t is a hit) with t walked down from the query's
+ *             64th score until at least k rows pass; the hits are ranked on the host.
+ *   range     knnx_range_search / knnx_range_search_once on an index WITHOUT a refine store: all rows of the probed lists whose ADC score
+ *             is > thresh (strict), ids ascending inside each query; two-call protocol, _once contract and KNNX_E_STATE on mismatching
+ *             lims as for IVF-Flat.  Behind a rotation the scores are those of q' = A q.  On an index WITH a refine store it stays
+ *             KNNX_E_UNSUPPORTED (the message says "refine store"): it would need the exact score of every probed row.
+ *   refine    k > 64: kc = k x k_factor candidates by (ADC score, id) as above, re-scored as the refine block defines (same summation
+ *             order), the top k by (exact score descending, id ascending) returned.  kc > 131072 answers KNNX_E_ARG and names both
+ *             numbers.  k <= 64 keeps the refine block's path and its k x k_factor <= 512 rule.
+ * knnx_search_device, knnx_search_dedup and the coalescer stay at k <= 64; builds and knnx_ivfpq_add_codes are unchanged.  Shards: every
+ * shard answers for itself (a shard with the switch off gives its own refusal).  knnx_ivfpq_threshold_stats: counters since the index
+ * was created -- queries served with k > 64, threshold-scan launches (one serves a whole group of queries), scans summed over the
+ * queries that took part in them, hits fetched to the host; any pointer may be null. */
+int knnx_ivfpq_set_threshold_scan(knnx_index* ix, int on);
+int knnx_ivfpq_threshold_scan(const knnx_index* ix);   /* 0 / 1; 0 on a non-PQ or null index */
+int knnx_ivfpq_threshold_stats(knnx_index* ix, int64_t* queries, int64_t* launches, int64_t* query_scans, int64_t* hits);
 /* The row rotation on its own (the MFMA kernel of the build): out_dev[i] = fp16(A rows_dev[i]) as defined above, n fp16 rows in HBM,
  * d in {256, 512, 768, 1024}; A_host f32 [d][d] is NOT checked for orthonormality; out_dev must not overlap rows_dev; rows past n are
  * not written.  knnx_xty_device: G = X^T Y (device f32 [d][d]) for fp16 rows X and f32 rows Y [n][d] in HBM, every element one fp32

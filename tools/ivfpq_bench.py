@@ -11,6 +11,9 @@ at a size where both fit).  Prints ONE JSON line.
   python tools/ivfpq_bench.py --rows 16000000 --nlist 16384 --nprobes 64 --refine [--k-factor 1,4,8]
                                                                 # + the same index with a refine store and IVF-Flat on the same rows, all three
                                                                 # resident, timed alternately; recall@40 of each
+  python tools/ivfpq_bench.py --rows 16000000 --nlist 16384 --nprobes 64 --refine --large-k 100,3000
+                                                                # + one query at nprobe 64 for every k on those three indexes (threshold scan
+                                                                # switched on), timed alternately; threshold scans and hits fetched per query
 """
 import argparse
 import json
@@ -40,6 +43,8 @@ def main():
     ap.add_argument("--refine", action="store_true", help="also build the index with a refine store (same centroids and codebooks) and IVF-Flat "
                     "on the same rows; all three stay resident and are timed alternately at nprobe 64, k = 40")
     ap.add_argument("--k-factor", default="1,4,8", help="k_factor values of --refine")
+    ap.add_argument("--large-k", default="", help="with --refine: k values above 64 (e.g. 100,3000) timed at B = 1, nprobe 64 on the plain index, "
+                    "the refine index (the first --k-factor) and IVF-Flat -- the yardstick -- alternately")
     ap.add_argument("--kind", type=int, default=1, choices=(1, 2), help="corpus: 1 = the mixture of config 5, 2 = isotropic with three dominant columns")
     a = ap.parse_args()
 
@@ -178,6 +183,38 @@ def main():
             for name, v in ts.items():
                 r[f"B{B}_np64_ms_{name}"] = round(float(np.median(v)) * 1e3, 4)
         out["refine"] = r
+        if a.large_k:
+            # k > 64 through the threshold scan (Mi355xIndex.pq_threshold_scan): host-buffer searches of ONE query, the three indexes
+            # alternately, three rounds of --reps, the median of the rounds' medians.  IVF-Flat's time for the same k is the yardstick.
+            index.pq_threshold_scan = ref.pq_threshold_scan = True
+            ref.k_factor = kfs[0]
+
+            def timed_host(ix, kk):
+                ix.search(q[:1], kk)
+                ts = []
+                for _ in range(a.reps):
+                    t0 = time.perf_counter()
+                    ix.search(q[:1], kk)
+                    ts.append(time.perf_counter() - t0)
+                return float(np.median(ts))
+
+            lk = {"k_factor": kfs[0]}
+            for kk in [64] + [int(v) for v in a.large_k.split(",")]:
+                ts = {"plain": [], "refine": [], "ivf_flat": []}
+                s0, s1 = index.pq_threshold_stats(), ref.pq_threshold_stats()
+                for _ in range(3):
+                    ts["plain"].append(timed_host(index, kk))
+                    if kk > 64 or kk * kfs[0] <= 512:
+                        ts["refine"].append(timed_host(ref, kk))
+                    ts["ivf_flat"].append(timed_host(flat, kk))
+                e = {f"ms_{name}": round(float(np.median(v)) * 1e3, 4) for name, v in ts.items() if v}
+                for name, ix, before in (("plain", index, s0), ("refine", ref, s1)):
+                    nq, _, qs, hits = (x - y for x, y in zip(ix.pq_threshold_stats(), before))
+                    if nq:
+                        e[f"scans_per_query_{name}"] = round(qs / nq, 2)
+                        e[f"hits_per_query_{name}"] = round(hits / nq, 1)
+                lk[f"k{kk}"] = e
+            out["large_k"] = lk
         ref.close()
         flat.close()
 

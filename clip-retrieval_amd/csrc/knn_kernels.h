@@ -164,7 +164,7 @@ hipError_t launch_i8_proof(int nq, int k, const float* D, const float* thr_lb, c
 
 // ---- IVF-PQ (knn_pq_kernels.hip): faiss IndexIVFPQ(IndexFlatIP(d), d, nlist, M, 8), inner product, by_residual
 constexpr int PQ_MAX_K = 64;  // k of the ADC scan's candidate queues
-bool pq_supported(int d, int M);  // M in {16, 32, 64, 128}, M | d, d / M <= 64
+bool pq_supported(int d, int M);  // M in {16, 32, 64, 128}, M | d, d / M <= 64; or M = 256 with d in {512, 768, 1024}
 // codes[row * M + m] = argmin_j ||r_m - cb[m][j]||^2, r = f32(X[i]) - f32(cent[lists[i]]); row = tile0[lists[i]] * 32 + pos[i] (tile0 == null:
 // row = i); idmap != null: also idmap[row] = id (ids[i], or id0 + i) and inv[id - id_lo] = row
 hipError_t launch_pq_encode(const _Float16* X, int64_t n, int d, int M, const int32_t* lists, const _Float16* cent, const float* cb,
@@ -206,6 +206,26 @@ hipError_t launch_pq_rescore(const _Float16* X, int d, const float* q, int nq, i
 hipError_t launch_pq_range_scan(const uint8_t* codes, int M, const float* lut, const int* probe, const float* pscore, const unsigned* pcnt,
                                 int np, int nsplit, const unsigned* tile0, const unsigned* size, const float* thr, unsigned* cnt,
                                 unsigned cap, float* hit_s, uint32_t* hit_r, int nq, hipStream_t st);
+// M = 256: the ADC stage in two halves of m (knn_pq_kernels.hip, above pq_probe_offsets_kernel).  poff [nq][np]: launch_pq_probe_offsets
+// after launch_pq_probe.  The others serve queries q0 .. q0 + g - 1 of the pass's nq: launch_pq_adc_lower fills their slabs (half: g x
+// slab floats; thr null or the thresholds of a threshold scan), the *_upper launchers are launch_pq_adc_scan / _cand_scan / _range_scan
+// continued from those sums (launch_pq_range_upper does NOT clear cnt).
+hipError_t launch_pq_probe_offsets(const int* probe, const unsigned* pcnt, int np, const unsigned* size, unsigned* poff, int nq, hipStream_t st);
+hipError_t launch_pq_adc_lower(const uint8_t* codes, const float* lut, const int* probe, const unsigned* pcnt, int np, int nsplit,
+                               const unsigned* tile0, const unsigned* size, const unsigned* poff, const float* thr, size_t slab, int q0, int g,
+                               float* half, hipStream_t st);
+hipError_t launch_pq_adc_upper(const uint8_t* codes, const float* lut, const int* probe, const float* pscore, const unsigned* pcnt, int np,
+                               int nsplit, const unsigned* tile0, const unsigned* size, const int64_t* idmap, int k, int nq, float* part_s,
+                               uint32_t* part_i, int* part_n, const float* half, const unsigned* poff, size_t slab, int q0, int g,
+                               hipStream_t st);
+hipError_t launch_pq_cand_upper(const uint8_t* codes, const float* lut, const int* probe, const float* pscore, const unsigned* pcnt, int np,
+                                int nsplit, const unsigned* tile0, const unsigned* size, const int64_t* idmap, int kc, int nq, float* part_s,
+                                uint32_t* part_r, int* part_n, const float* half, const unsigned* poff, size_t slab, int q0, int g,
+                                hipStream_t st);
+hipError_t launch_pq_range_upper(const uint8_t* codes, const float* lut, const int* probe, const float* pscore, const unsigned* pcnt, int np,
+                                 int nsplit, const unsigned* tile0, const unsigned* size, const float* thr, unsigned* cnt, unsigned cap,
+                                 float* hit_s, uint32_t* hit_r, const float* half, const unsigned* poff, size_t slab, int q0, int g,
+                                 hipStream_t st);
 // OPQ rotation in front of IVF-PQ (A f32 [d][d], y = A x; d in {256, 512, 768, 1024}).  launch_rot_split: A -> W fp16 [2 d][d], the
 // hi / lo tile image launch_rotate_f16 (knn_rq_kernels.hip, MFMA) streams: Y[i] = fp16(A P[i]), Y and P distinct.  launch_rot_queries:
 // out[i] = A q[i] in fp32 (nq <= 256 per launch is what it is sized for; any nq works).  launch_rot_back: out[i] = A^T dec[i] in fp32

@@ -159,6 +159,84 @@ __global__ __launch_bounds__(256) void pq_probe_kernel(const unsigned* __restric
 }
 
 // ---------------------------------------------------------------------------------------------
+// M = 256 (PQ256x8): the query's lookup table is 256 KiB and does not fit the LDS, so the ADC stage runs in two halves of m over the
+// same shares.  The lower half (pq_adc_lower_kernel) scores every probed row over tables 0 .. 127 and stores the fp32 partial sum; the
+// upper half is the UP mode of the three scans below, which starts from that sum and continues over tables 128 .. 255.  A 4-byte store
+// and load is exact, so the score is cs + (ONE fp32 chain over m = 0 .. 255 from 0.f), as for every other M.
+//
+// Partial sums: query q of a sub-group that starts at q0 owns the slab part[(q - q0) * slab ..]; inside it, probe p of the query
+// starts at poff[q][p] = the rows of the query's probes before p (pq_probe_offsets_kernel), and row i of the list sits at + i.  slab is
+// the sum of the np largest list sizes of the index (knnx_pq_plan.h), so a query's probed lists always fit.
+// ---------------------------------------------------------------------------------------------
+// exclusive prefix of size[probe[q][p]] over p < min(pcnt[q], np), in probe-list order; one workgroup per query, np of any size
+__global__ __launch_bounds__(256) void pq_probe_offsets_kernel(const int* __restrict__ probe, const unsigned* __restrict__ pcnt, int np,
+                                                              const unsigned* __restrict__ size, unsigned* __restrict__ poff) {
+  __shared__ unsigned sc[256];
+  const int q = blockIdx.x, tid = threadIdx.x;
+  const int npq = min((int)pcnt[q], np);
+  unsigned carry = 0;  // rows before this chunk of 256 probes (the same in every thread)
+  for (int p0 = 0; p0 < npq; p0 += 256) {
+    const int p = p0 + tid;
+    const unsigned mine = p < npq ? size[probe[(size_t)q * np + p]] : 0u;
+    sc[tid] = mine;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {  // inclusive scan of the chunk
+      const unsigned add = tid >= o ? sc[tid - o] : 0u;
+      __syncthreads();
+      sc[tid] += add;
+      __syncthreads();
+    }
+    if (p < npq) poff[(size_t)q * np + p] = carry + sc[tid] - mine;
+    carry += sc[255];
+    __syncthreads();
+  }
+}
+
+// lower half: grid (nsplit, g), the shares of pq_adc_scan_kernel (any nsplit: a row's slot does not depend on the share that scores
+// it).  Tables 0 .. 127 of query q0 + blockIdx.y in the LDS (128 KiB); every lane one row per step: eight 16-byte code loads, 128 LDS
+// lookups, one 4-byte store.  No queue, no barrier in the row loop, no id map.  thr (null: none) is the threshold array of a threshold
+// scan: a query at +INFINITY is finished and its workgroups return at once, like those of the upper half.
+static_assert((size_t)128 * 1024 + 64 <= (size_t)KNN_LDS_BYTES, "M = 256: a half-table exceeds the LDS");
+__global__ __launch_bounds__(256) void pq_adc_lower_kernel(const uint8_t* __restrict__ codes, const float* __restrict__ lut,
+                                                          const int* __restrict__ probe, const unsigned* __restrict__ pcnt, int np,
+                                                          int nsplit, const unsigned* __restrict__ tile0,
+                                                          const unsigned* __restrict__ size, const unsigned* __restrict__ poff,
+                                                          const float* __restrict__ thr, size_t slab, int q0, float* __restrict__ part) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char pq_smem[];
+  float* s_lut = reinterpret_cast<float*>(pq_smem);  // [128 * 256]
+  const int s = blockIdx.x, q = (int)blockIdx.y + q0, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  if (thr && thr[q] == INFINITY) return;  // (the whole workgroup: q is its query)
+  const float4* lq = reinterpret_cast<const float4*>(lut + (size_t)q * 256 * 256);
+  for (int e = tid; e < 128 * 64; e += 256) reinterpret_cast<float4*>(s_lut)[e] = lq[e];
+  __syncthreads();
+  float* slab_q = part + (size_t)blockIdx.y * slab;
+  const int npq = min((int)pcnt[q], np);
+  for (int p = s; p < npq; p += nsplit) {
+    const int l = probe[(size_t)q * np + p];
+    const size_t r0 = (size_t)tile0[l] * 32;
+    const unsigned sz = size[l];
+    const size_t off = poff[(size_t)q * np + p];
+    for (unsigned base = (unsigned)w * 64; base < sz; base += 256) {
+      const unsigned i = base + lane;
+      if (i < sz && off + i < slab) {  // (off + sz <= slab by the definition of slab; checked all the same: this is a store)
+        const uint4* cp = reinterpret_cast<const uint4*>(codes + (r0 + i) * 256);
+        uint4 cw[8];
+#pragma unroll
+        for (int v = 0; v < 8; ++v) cw[v] = cp[v];
+        float acc = 0.f;
+#pragma unroll
+        for (int v = 0; v < 8; ++v) {
+          const unsigned ww[4] = {cw[v].x, cw[v].y, cw[v].z, cw[v].w};
+#pragma unroll
+          for (int b = 0; b < 16; ++b) acc += s_lut[(v * 16 + b) * 256 + ((ww[b >> 2] >> (8 * (b & 3))) & 255u)];
+        }
+        slab_q[off + i] = acc;
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // ADC list scan with top-k (see the head of the file).  grid (nsplit, nq); workgroup (s, q) scans probes s, s + nsplit, ... of
 // query q and writes partial list s * nq + q (<= k entries, arena rows) of part_s / part_i / part_n.
 // ---------------------------------------------------------------------------------------------
@@ -185,21 +263,28 @@ __device__ __forceinline__ int pq_wave_prune(float* qs, uint32_t* qr, long long*
   return n < k ? n : k;
 }
 
-template <int M>
-__global__ __launch_bounds__(256) void pq_adc_scan_kernel(const uint8_t* __restrict__ codes, const float* __restrict__ lut,
-                                                         const int* __restrict__ probe, const float* __restrict__ pscore,
-                                                         const unsigned* __restrict__ pcnt, int np, int nsplit,
-                                                         const unsigned* __restrict__ tile0, const unsigned* __restrict__ size,
-                                                         const int64_t* __restrict__ idmap, int k, int nq, float* __restrict__ part_s,
-                                                         uint32_t* __restrict__ part_i, int* __restrict__ part_n) {
+// The three scans below are written once as a body with a mode: UP = false is the whole scan of an index with M <= 128 code bytes per
+// row (acc from 0.f over tables 0 .. M - 1).  UP = true is the UPPER HALF of the M = 256 scan (see pq_adc_lower_kernel): M = 128 tables
+// are staged, tables 128 .. 255 of the query's 256, the row's code bytes 128 .. 255 are read, and acc starts from the fp32 partial sum
+// the lower half stored for the row -- part[(q - q0) * slab + poff[q][p] + i] -- so that the score is the one ascending chain over
+// m = 0 .. 255.  The workgroup's query is q0 + blockIdx.y (a sub-group of the pass); everything else is indexed by q as before.
+template <int M, bool UP>
+__device__ __forceinline__ void pq_adc_scan_body(const uint8_t* __restrict__ codes, const float* __restrict__ lut,
+                                                 const int* __restrict__ probe, const float* __restrict__ pscore,
+                                                 const unsigned* __restrict__ pcnt, int np, int nsplit,
+                                                 const unsigned* __restrict__ tile0, const unsigned* __restrict__ size,
+                                                 const int64_t* __restrict__ idmap, int k, int nq, float* __restrict__ part_s,
+                                                 uint32_t* __restrict__ part_i, int* __restrict__ part_n, const float* __restrict__ half,
+                                                 const unsigned* __restrict__ poff, size_t slab, int q0) {
+  constexpr int ROW = UP ? 256 : M, BYTE0 = UP ? 128 : 0;  // bytes of an arena row, the first one this scan reads
   extern __shared__ __attribute__((aligned(16))) unsigned char pq_smem[];
   float* s_lut = reinterpret_cast<float*>(pq_smem);                  // [M * 256]
   long long* c_id = reinterpret_cast<long long*>(s_lut + M * 256);  // [4][PQ_WQ]
   float* c_s = reinterpret_cast<float*>(c_id + 4 * PQ_WQ);           // [4][PQ_WQ]
   uint32_t* c_r = reinterpret_cast<uint32_t*>(c_s + 4 * PQ_WQ);      // [4][PQ_WQ]
   __shared__ int w_cnt[4];
-  const int s = blockIdx.x, q = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const float4* lq = reinterpret_cast<const float4*>(lut + (size_t)q * M * 256);
+  const int s = blockIdx.x, q = (int)blockIdx.y + (UP ? q0 : 0), tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const float4* lq = reinterpret_cast<const float4*>(lut + ((size_t)q * ROW + BYTE0) * 256);
   for (int e = tid; e < M * 64; e += 256) reinterpret_cast<float4*>(s_lut)[e] = lq[e];
   __syncthreads();
   float* qs = c_s + w * PQ_WQ;
@@ -213,6 +298,7 @@ __global__ __launch_bounds__(256) void pq_adc_scan_kernel(const uint8_t* __restr
     const float cs = pscore[(size_t)q * np + p];
     const size_t r0 = (size_t)tile0[l] * 32;
     const unsigned sz = size[l];
+    const float* hp = UP ? half + (size_t)blockIdx.y * slab + poff[(size_t)q * np + p] : nullptr;  // the list's partial sums
     for (unsigned base = (unsigned)w * 64; base < sz; base += 256) {
       if (cnt > PQ_WQ - 64) cnt = pq_wave_prune(qs, qr, qi, cnt, k, lane, thr);
       const unsigned i = base + lane;
@@ -221,11 +307,11 @@ __global__ __launch_bounds__(256) void pq_adc_scan_kernel(const uint8_t* __restr
       size_t row = 0;
       if (i < sz) {
         row = r0 + i;
-        const uint4* cp = reinterpret_cast<const uint4*>(codes + row * M);
+        const uint4* cp = reinterpret_cast<const uint4*>(codes + row * ROW + BYTE0);
         uint4 cw[M / 16];
 #pragma unroll
         for (int v = 0; v < M / 16; ++v) cw[v] = cp[v];
-        float acc = 0.f;
+        float acc = UP ? hp[i] : 0.f;
 #pragma unroll
         for (int v = 0; v < M / 16; ++v) {
           const unsigned ww[4] = {cw[v].x, cw[v].y, cw[v].z, cw[v].w};
@@ -269,6 +355,31 @@ __global__ __launch_bounds__(256) void pq_adc_scan_kernel(const uint8_t* __restr
   }
 }
 
+template <int M>
+__global__ __launch_bounds__(256) void pq_adc_scan_kernel(const uint8_t* __restrict__ codes, const float* __restrict__ lut,
+                                                         const int* __restrict__ probe, const float* __restrict__ pscore,
+                                                         const unsigned* __restrict__ pcnt, int np, int nsplit,
+                                                         const unsigned* __restrict__ tile0, const unsigned* __restrict__ size,
+                                                         const int64_t* __restrict__ idmap, int k, int nq, float* __restrict__ part_s,
+                                                         uint32_t* __restrict__ part_i, int* __restrict__ part_n) {
+  pq_adc_scan_body<M, false>(codes, lut, probe, pscore, pcnt, np, nsplit, tile0, size, idmap, k, nq, part_s, part_i, part_n, nullptr, nullptr, 0,
+                             0);
+}
+
+// upper half of the M = 256 scan; grid (nsplit, g): queries q0 .. q0 + g - 1 of the pass's nq.  LDS as M = 128: 136 KiB
+static_assert((size_t)128 * 1024 + (size_t)4 * PQ_WQ * 16 + 64 <= (size_t)KNN_LDS_BYTES, "M = 256: a half-table + the queues exceed the LDS");
+__global__ __launch_bounds__(256) void pq_adc_upper_kernel(const uint8_t* __restrict__ codes, const float* __restrict__ lut,
+                                                          const int* __restrict__ probe, const float* __restrict__ pscore,
+                                                          const unsigned* __restrict__ pcnt, int np, int nsplit,
+                                                          const unsigned* __restrict__ tile0, const unsigned* __restrict__ size,
+                                                          const int64_t* __restrict__ idmap, int k, int nq, float* __restrict__ part_s,
+                                                          uint32_t* __restrict__ part_i, int* __restrict__ part_n,
+                                                          const float* __restrict__ half, const unsigned* __restrict__ poff, size_t slab,
+                                                          int q0) {
+  pq_adc_scan_body<128, true>(codes, lut, probe, pscore, pcnt, np, nsplit, tile0, size, idmap, k, nq, part_s, part_i, part_n, half, poff, slab,
+                              q0);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Threshold mode of the ADC scan (range_search and k > 64 on an index with the threshold-scan switch on).  Grid, shares, LUT staging
 // and the scoring of a row are those of pq_adc_scan_kernel -- the same fp32 values, acc summed in m order, then cs + acc -- but there
@@ -281,19 +392,21 @@ __global__ __launch_bounds__(256) void pq_adc_scan_kernel(const uint8_t* __restr
 // ---------------------------------------------------------------------------------------------
 static_assert((size_t)128 * 1024 + 64 <= (size_t)KNN_LDS_BYTES, "M = 128: the LUT of the threshold scan exceeds the LDS");
 
-template <int M>
-__global__ __launch_bounds__(256) void pq_range_scan_kernel(const uint8_t* __restrict__ codes, const float* __restrict__ lut,
-                                                           const int* __restrict__ probe, const float* __restrict__ pscore,
-                                                           const unsigned* __restrict__ pcnt, int np, int nsplit,
-                                                           const unsigned* __restrict__ tile0, const unsigned* __restrict__ size,
-                                                           const float* __restrict__ thr, unsigned* __restrict__ cnt, unsigned cap,
-                                                           float* __restrict__ hit_s, uint32_t* __restrict__ hit_r) {
+template <int M, bool UP>
+__device__ __forceinline__ void pq_range_scan_body(const uint8_t* __restrict__ codes, const float* __restrict__ lut,
+                                                   const int* __restrict__ probe, const float* __restrict__ pscore,
+                                                   const unsigned* __restrict__ pcnt, int np, int nsplit,
+                                                   const unsigned* __restrict__ tile0, const unsigned* __restrict__ size,
+                                                   const float* __restrict__ thr, unsigned* __restrict__ cnt, unsigned cap,
+                                                   float* __restrict__ hit_s, uint32_t* __restrict__ hit_r, const float* __restrict__ half,
+                                                   const unsigned* __restrict__ poff, size_t slab, int q0) {
+  constexpr int ROW = UP ? 256 : M, BYTE0 = UP ? 128 : 0;  // bytes of an arena row, the first one this scan reads
   extern __shared__ __attribute__((aligned(16))) unsigned char pq_smem[];
   float* s_lut = reinterpret_cast<float*>(pq_smem);  // [M * 256]
-  const int s = blockIdx.x, q = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int s = blockIdx.x, q = (int)blockIdx.y + (UP ? q0 : 0), tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const float th = thr[q];
   if (th == INFINITY) return;  // (the whole workgroup: q is its query)
-  const float4* lq = reinterpret_cast<const float4*>(lut + (size_t)q * M * 256);
+  const float4* lq = reinterpret_cast<const float4*>(lut + ((size_t)q * ROW + BYTE0) * 256);
   for (int e = tid; e < M * 64; e += 256) reinterpret_cast<float4*>(s_lut)[e] = lq[e];
   __syncthreads();
   float* hs = hit_s + (size_t)q * cap;
@@ -304,6 +417,7 @@ __global__ __launch_bounds__(256) void pq_range_scan_kernel(const uint8_t* __res
     const float cs = pscore[(size_t)q * np + p];
     const size_t r0 = (size_t)tile0[l] * 32;
     const unsigned sz = size[l];
+    const float* hp = UP ? half + (size_t)blockIdx.y * slab + poff[(size_t)q * np + p] : nullptr;  // the list's partial sums
     for (unsigned base = (unsigned)w * 64; base < sz; base += 256) {
       const unsigned i = base + lane;
       float sc = -INFINITY;
@@ -311,11 +425,11 @@ __global__ __launch_bounds__(256) void pq_range_scan_kernel(const uint8_t* __res
       size_t row = 0;
       if (i < sz) {
         row = r0 + i;
-        const uint4* cp = reinterpret_cast<const uint4*>(codes + row * M);
+        const uint4* cp = reinterpret_cast<const uint4*>(codes + row * ROW + BYTE0);
         uint4 cw[M / 16];
 #pragma unroll
         for (int v = 0; v < M / 16; ++v) cw[v] = cp[v];
-        float acc = 0.f;
+        float acc = UP ? hp[i] : 0.f;
 #pragma unroll
         for (int v = 0; v < M / 16; ++v) {
           const unsigned ww[4] = {cw[v].x, cw[v].y, cw[v].z, cw[v].w};
@@ -340,6 +454,28 @@ __global__ __launch_bounds__(256) void pq_range_scan_kernel(const uint8_t* __res
       }
     }
   }
+}
+
+template <int M>
+__global__ __launch_bounds__(256) void pq_range_scan_kernel(const uint8_t* __restrict__ codes, const float* __restrict__ lut,
+                                                           const int* __restrict__ probe, const float* __restrict__ pscore,
+                                                           const unsigned* __restrict__ pcnt, int np, int nsplit,
+                                                           const unsigned* __restrict__ tile0, const unsigned* __restrict__ size,
+                                                           const float* __restrict__ thr, unsigned* __restrict__ cnt, unsigned cap,
+                                                           float* __restrict__ hit_s, uint32_t* __restrict__ hit_r) {
+  pq_range_scan_body<M, false>(codes, lut, probe, pscore, pcnt, np, nsplit, tile0, size, thr, cnt, cap, hit_s, hit_r, nullptr, nullptr, 0, 0);
+}
+
+// upper half of the M = 256 threshold scan; grid (nsplit, g).  LDS as M = 128: 128 KiB
+__global__ __launch_bounds__(256) void pq_range_upper_kernel(const uint8_t* __restrict__ codes, const float* __restrict__ lut,
+                                                            const int* __restrict__ probe, const float* __restrict__ pscore,
+                                                            const unsigned* __restrict__ pcnt, int np, int nsplit,
+                                                            const unsigned* __restrict__ tile0, const unsigned* __restrict__ size,
+                                                            const float* __restrict__ thr, unsigned* __restrict__ cnt, unsigned cap,
+                                                            float* __restrict__ hit_s, uint32_t* __restrict__ hit_r,
+                                                            const float* __restrict__ half, const unsigned* __restrict__ poff, size_t slab,
+                                                            int q0) {
+  pq_range_scan_body<128, true>(codes, lut, probe, pscore, pcnt, np, nsplit, tile0, size, thr, cnt, cap, hit_s, hit_r, half, poff, slab, q0);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -388,20 +524,22 @@ __device__ __forceinline__ void pq_bitonic(float* s, uint32_t* r, int n, const i
     }
 }
 
-template <int M>
-__global__ __launch_bounds__(256) void pq_cand_scan_kernel(const uint8_t* __restrict__ codes, const float* __restrict__ lut,
-                                                          const int* __restrict__ probe, const float* __restrict__ pscore,
-                                                          const unsigned* __restrict__ pcnt, int np, int nsplit,
-                                                          const unsigned* __restrict__ tile0, const unsigned* __restrict__ size,
-                                                          const int64_t* __restrict__ idmap, int kc, int nq, float* __restrict__ part_s,
-                                                          uint32_t* __restrict__ part_r, int* __restrict__ part_n) {
+template <int M, bool UP>
+__device__ __forceinline__ void pq_cand_scan_body(const uint8_t* __restrict__ codes, const float* __restrict__ lut,
+                                                  const int* __restrict__ probe, const float* __restrict__ pscore,
+                                                  const unsigned* __restrict__ pcnt, int np, int nsplit,
+                                                  const unsigned* __restrict__ tile0, const unsigned* __restrict__ size,
+                                                  const int64_t* __restrict__ idmap, int kc, int nq, float* __restrict__ part_s,
+                                                  uint32_t* __restrict__ part_r, int* __restrict__ part_n, const float* __restrict__ half,
+                                                  const unsigned* __restrict__ poff, size_t slab, int q0) {
+  constexpr int ROW = UP ? 256 : M, BYTE0 = UP ? 128 : 0;  // bytes of an arena row, the first one this scan reads
   extern __shared__ __attribute__((aligned(16))) unsigned char pq_smem[];
   float* s_lut = reinterpret_cast<float*>(pq_smem);              // [M * 256]
   float* q_s = s_lut + M * 256;                                  // [PQ_CQ]
   uint32_t* q_r = reinterpret_cast<uint32_t*>(q_s + PQ_CQ);      // [PQ_CQ]
   int* s_wc = reinterpret_cast<int*>(q_r + PQ_CQ);               // [2][4]
-  const int s = blockIdx.x, q = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const float4* lq = reinterpret_cast<const float4*>(lut + (size_t)q * M * 256);
+  const int s = blockIdx.x, q = (int)blockIdx.y + (UP ? q0 : 0), tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const float4* lq = reinterpret_cast<const float4*>(lut + ((size_t)q * ROW + BYTE0) * 256);
   for (int e = tid; e < M * 64; e += 256) reinterpret_cast<float4*>(s_lut)[e] = lq[e];
   __syncthreads();
   int cnt = 0, par = 0;  // the same in every thread
@@ -420,6 +558,7 @@ __global__ __launch_bounds__(256) void pq_cand_scan_kernel(const uint8_t* __rest
     const float cs = pscore[(size_t)q * np + p];
     const size_t r0 = (size_t)tile0[l] * 32;
     const unsigned sz = size[l];
+    const float* hp = UP ? half + (size_t)blockIdx.y * slab + poff[(size_t)q * np + p] : nullptr;  // the list's partial sums
     for (unsigned base = 0; base < sz; base += 256) {
       if (cnt > PQ_CQ - 256) prune();
       const unsigned i = base + (unsigned)tid;
@@ -428,11 +567,11 @@ __global__ __launch_bounds__(256) void pq_cand_scan_kernel(const uint8_t* __rest
       size_t row = 0;
       if (i < sz) {
         row = r0 + i;
-        const uint4* cp = reinterpret_cast<const uint4*>(codes + row * M);
+        const uint4* cp = reinterpret_cast<const uint4*>(codes + row * ROW + BYTE0);
         uint4 cw[M / 16];
 #pragma unroll
         for (int v = 0; v < M / 16; ++v) cw[v] = cp[v];
-        float acc = 0.f;
+        float acc = UP ? hp[i] : 0.f;
 #pragma unroll
         for (int v = 0; v < M / 16; ++v) {
           const unsigned ww[4] = {cw[v].x, cw[v].y, cw[v].z, cw[v].w};
@@ -463,6 +602,30 @@ __global__ __launch_bounds__(256) void pq_cand_scan_kernel(const uint8_t* __rest
     part_r[slot * kc + e] = q_r[e];
   }
   if (tid == 0) part_n[slot] = keep;
+}
+
+template <int M>
+__global__ __launch_bounds__(256) void pq_cand_scan_kernel(const uint8_t* __restrict__ codes, const float* __restrict__ lut,
+                                                          const int* __restrict__ probe, const float* __restrict__ pscore,
+                                                          const unsigned* __restrict__ pcnt, int np, int nsplit,
+                                                          const unsigned* __restrict__ tile0, const unsigned* __restrict__ size,
+                                                          const int64_t* __restrict__ idmap, int kc, int nq, float* __restrict__ part_s,
+                                                          uint32_t* __restrict__ part_r, int* __restrict__ part_n) {
+  pq_cand_scan_body<M, false>(codes, lut, probe, pscore, pcnt, np, nsplit, tile0, size, idmap, kc, nq, part_s, part_r, part_n, nullptr, nullptr,
+                              0, 0);
+}
+
+// upper half of the M = 256 candidate scan; grid (nsplit, g).  LDS as M = 128: 144 KiB + 32 B
+__global__ __launch_bounds__(256) void pq_cand_upper_kernel(const uint8_t* __restrict__ codes, const float* __restrict__ lut,
+                                                           const int* __restrict__ probe, const float* __restrict__ pscore,
+                                                           const unsigned* __restrict__ pcnt, int np, int nsplit,
+                                                           const unsigned* __restrict__ tile0, const unsigned* __restrict__ size,
+                                                           const int64_t* __restrict__ idmap, int kc, int nq, float* __restrict__ part_s,
+                                                           uint32_t* __restrict__ part_r, int* __restrict__ part_n,
+                                                           const float* __restrict__ half, const unsigned* __restrict__ poff, size_t slab,
+                                                           int q0) {
+  pq_cand_scan_body<128, true>(codes, lut, probe, pscore, pcnt, np, nsplit, tile0, size, idmap, kc, nq, part_s, part_r, part_n, half, poff, slab,
+                               q0);
 }
 
 // selection across a query's shares: one workgroup per query holds its nsplit partial lists (<= PQ_SEL_MAX entries, padded to the
@@ -809,6 +972,7 @@ hipError_t launch_xty(const _Float16* X, const float* Y, int64_t n, int d, float
 }
 
 bool pq_supported(int d, int M) {
+  if (M == 256) return d == 512 || d == 768 || d == 1024;  // the two-half scan; d / M = 2, 3, 4
   return (M == 16 || M == 32 || M == 64 || M == 128) && d % 256 == 0 && d > 0 && d <= 1024 && d % M == 0 && d / M <= 64;
 }
 
@@ -833,7 +997,7 @@ hipError_t launch_pq_encode(const _Float16* X, int64_t n, int d, int M, const in
 #define PQ_ENC(DS) \
   case DS: return launch_encode_ds<DS>(X, n, d, M, lists, cent, cb, tile0, pos, ids, id0, id_lo, n_ids, codes, idmap, inv, st);
   switch (d / M) {
-    PQ_ENC(2) PQ_ENC(4) PQ_ENC(6) PQ_ENC(8) PQ_ENC(12) PQ_ENC(16) PQ_ENC(24) PQ_ENC(32) PQ_ENC(48) PQ_ENC(64)
+    PQ_ENC(2) PQ_ENC(3) PQ_ENC(4) PQ_ENC(6) PQ_ENC(8) PQ_ENC(12) PQ_ENC(16) PQ_ENC(24) PQ_ENC(32) PQ_ENC(48) PQ_ENC(64)
     default: return hipErrorInvalidValue;
   }
 #undef PQ_ENC
@@ -941,6 +1105,58 @@ hipError_t launch_pq_cand_scan(const uint8_t* codes, int M, const float* lut, co
     default: return hipErrorInvalidValue;
   }
 #undef PQ_CSCAN
+}
+
+// ---- M = 256: the two halves (queries q0 .. q0 + g - 1 of a pass of nq; half = their partial-sum slabs, g x slab floats) ----
+hipError_t launch_pq_probe_offsets(const int* probe, const unsigned* pcnt, int np, const unsigned* size, unsigned* poff, int nq, hipStream_t st) {
+  if (nq <= 0 || np <= 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(pq_probe_offsets_kernel, dim3((unsigned)nq), dim3(256), 0, st, probe, pcnt, np, size, poff);
+  return hipGetLastError();
+}
+
+// sets the dynamic LDS size of a kernel and launches it on grid (nsplit, g)
+template <class K, class... A>
+static hipError_t pq_launch_half(K kern, size_t smem, int nsplit, int g, hipStream_t st, A... args) {
+  if (g <= 0 || nsplit <= 0 || smem + 64 > (size_t)KNN_LDS_BYTES) return hipErrorInvalidValue;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kern, dim3((unsigned)nsplit, (unsigned)g), dim3(256), smem, st, args...);
+  return hipGetLastError();
+}
+
+hipError_t launch_pq_adc_lower(const uint8_t* codes, const float* lut, const int* probe, const unsigned* pcnt, int np, int nsplit,
+                               const unsigned* tile0, const unsigned* size, const unsigned* poff, const float* thr, size_t slab, int q0, int g,
+                               float* half, hipStream_t st) {
+  return pq_launch_half(pq_adc_lower_kernel, (size_t)128 * 1024, nsplit, g, st, codes, lut, probe, pcnt, np, nsplit, tile0, size, poff, thr,
+                        slab, q0, half);
+}
+
+hipError_t launch_pq_adc_upper(const uint8_t* codes, const float* lut, const int* probe, const float* pscore, const unsigned* pcnt, int np,
+                               int nsplit, const unsigned* tile0, const unsigned* size, const int64_t* idmap, int k, int nq, float* part_s,
+                               uint32_t* part_i, int* part_n, const float* half, const unsigned* poff, size_t slab, int q0, int g,
+                               hipStream_t st) {
+  if (k < 1 || k > PQ_MAX_K || q0 < 0 || q0 + g > nq) return hipErrorInvalidValue;
+  return pq_launch_half(pq_adc_upper_kernel, pq_scan_smem_bytes(128), nsplit, g, st, codes, lut, probe, pscore, pcnt, np, nsplit, tile0, size,
+                        idmap, k, nq, part_s, part_i, part_n, half, poff, slab, q0);
+}
+
+hipError_t launch_pq_cand_upper(const uint8_t* codes, const float* lut, const int* probe, const float* pscore, const unsigned* pcnt, int np,
+                                int nsplit, const unsigned* tile0, const unsigned* size, const int64_t* idmap, int kc, int nq, float* part_s,
+                                uint32_t* part_r, int* part_n, const float* half, const unsigned* poff, size_t slab, int q0, int g,
+                                hipStream_t st) {
+  if (kc < 1 || kc > PQ_REFINE_MAX || q0 < 0 || q0 + g > nq) return hipErrorInvalidValue;
+  return pq_launch_half(pq_cand_upper_kernel, (size_t)128 * 1024 + (size_t)PQ_CQ * 8 + 32, nsplit, g, st, codes, lut, probe, pscore, pcnt, np,
+                        nsplit, tile0, size, idmap, kc, nq, part_s, part_r, part_n, half, poff, slab, q0);
+}
+
+// (cnt is NOT cleared here: the caller clears the pass's counters once, before the first sub-group)
+hipError_t launch_pq_range_upper(const uint8_t* codes, const float* lut, const int* probe, const float* pscore, const unsigned* pcnt, int np,
+                                 int nsplit, const unsigned* tile0, const unsigned* size, const float* thr, unsigned* cnt, unsigned cap,
+                                 float* hit_s, uint32_t* hit_r, const float* half, const unsigned* poff, size_t slab, int q0, int g,
+                                 hipStream_t st) {
+  if (np <= 0 || !thr || !cnt || (cap > 0 && (!hit_s || !hit_r)) || q0 < 0) return hipErrorInvalidValue;
+  return pq_launch_half(pq_range_upper_kernel, (size_t)128 * 1024, nsplit, g, st, codes, lut, probe, pscore, pcnt, np, nsplit, tile0, size, thr,
+                        cnt, cap, hit_s, hit_r, half, poff, slab, q0);
 }
 
 // refine: the ids of the best kc of a query's nsplit partial lists -> cand [nq][kc] (-1 padded); nsplit * kc <= PQ_SEL_MAX

@@ -376,6 +376,11 @@ struct PqData {
   // threshold mode of the ADC scan (knnx_ivfpq_set_threshold_scan): k > 64 and range_search are served; off: they are refused
   bool threshold_scan = false;
   int64_t thr_queries = 0, thr_scans = 0, thr_query_scans = 0, thr_hits = 0;  // knnx_ivfpq_threshold_stats
+  // M = 256 (the two-half ADC scan, knnx_pq_plan.h): the budget of the partial-sum buffer (KNNX_PQ_PARTIAL_MAX_BYTES, read by
+  // knnx_ivfpq_set_quantizer) and the slab width S of slab_np probed lists (host arithmetic on size_h, no device round trip: by the
+  // first pass after the index is finished, and again by the first pass after nprobe changed; slab_np = 0: not computed)
+  uint64_t partial_budget = 0, slab = 0;
+  int slab_np = 0;
 };
 // one IVF-PQ search pass of up to PQ_PASS queries, allocated on first use
 struct PqScratch {
@@ -403,6 +408,13 @@ struct PqScratch {
   DevBuf<float> tthr;       // [256]
   DevBuf<unsigned> tcnt;    // [256]
   DevBuf<unsigned> tfetch;  // [256] tcnt with the queries that are not fetched set to 0 (range_fetch reads its counts on the device)
+  // M = 256 only (the two-half ADC scan): the row offset of every probe in its query's slab, written by pq_front; the partial sums
+  // of the sub-group being scored, allocated on first use (knnx_ivfpq.hip: pq_half_buffer).  half_nq = n > 0: the buffer holds the
+  // sums of all n queries of the pass whose front half is in here (one sub-group) -- cleared by pq_front, so they never outlive it.
+  DevBuf<unsigned> poff;    // [256][np_cap]
+  DevBuf<float> half;       // [g][S]
+  uint64_t half_cap = 0;    // floats in half
+  int half_nq = 0;
   hipError_t alloc_threshold() {
     if (tthr) return hipSuccess;
     hipError_t e = hipSuccess;
@@ -440,6 +452,7 @@ struct PqScratch {
     }
     dev_alloc(e, probe, (size_t)PQ_PASS * np);
     dev_alloc(e, pscore, (size_t)PQ_PASS * np);
+    if (m == 256) dev_alloc(e, poff, (size_t)PQ_PASS * np);
     if (e != hipSuccess) *this = PqScratch();
     else np_cap = np;
     return e;

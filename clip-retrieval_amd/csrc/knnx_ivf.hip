@@ -658,6 +658,7 @@ extern "C" int knnx_ivf_end(knnx_index* ix) {
     if (ix->pq.m) {
       ix->pq.tile0_h.assign(ix->ivfb.tile0.begin(), ix->ivfb.tile0.end());
       ix->pq.size_h.assign(ix->ivfb.size.begin(), ix->ivfb.size.end());
+      ix->pq.slab_np = 0;  // (M = 256: the slab width is recomputed from these sizes)
       ix->pq.bcent.reset();
       ix->pq.rot_w.reset();
     }

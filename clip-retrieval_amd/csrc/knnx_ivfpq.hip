@@ -2,6 +2,7 @@
 // (knnx_pqb_*) (see knnx_host.h; kernels in knn_pq_kernels.hip).
 
 #include "knnx_host.h"
+#include "knnx_pq_plan.h"
 
 // ---------------------------------------------------------------------------------------------
 // IVF-PQ pass of 1 .. 256 queries already in HBM (csrc/knn_pq_kernels.hip): the coarse quantiser of the multi-block IVF pass
@@ -40,6 +41,10 @@ int pq_front(knnx_index* ix, const float* q_dev, int nq, hipStream_t st, const f
   HIPCHK(launch_scan(ca, st));
   HIPCHK(launch_ivf_select_mark(ix->pqs.scores, nq, np, ix->ivf_nlist, ix->pqs.masks, st));
   HIPCHK(launch_pq_probe(ix->pqs.masks, ix->pqs.scores, nq, ix->ivf_nlist, np, ix->pqs.pcnt, ix->pqs.probe, ix->pqs.pscore, st));
+  if (ix->pq.m == 256) {  // the two-half scan: where every probe's rows start in its query's slab of partial sums
+    HIPCHK(launch_pq_probe_offsets(ix->pqs.probe, ix->pqs.pcnt, np, ix->ivf.size, ix->pqs.poff, nq, st));
+    ix->pqs.half_nq = 0;  // the sums of an earlier front half are not these queries'
+  }
   HIPCHK(launch_pq_lut(q_dev, nq, ix->d, ix->pq.m, ix->pq.cb, ix->pqs.lut, st));
   *q_used = q_dev;
   *np_out = np;
@@ -48,6 +53,97 @@ int pq_front(knnx_index* ix, const float* q_dev, int nq, hipStream_t st, const f
 
 // shares a query's probed lists are split into (workgroups per query of the ADC scans)
 static int pq_nsplit(int np, int nq) { return std::max(1, std::min(std::min(np, PQ_MAX_SPLIT), (PQ_TARGET_WG + nq - 1) / nq)); }
+
+// ---------------------------------------------------------------------------------------------
+// M = 256: the ADC stage in two halves of m (knn_pq_kernels.hip; sizes: knnx_pq_plan.h).  What the stage is asked for:
+// ---------------------------------------------------------------------------------------------
+struct PqStage {
+  enum Kind { TOPK, CAND, RANGE } kind = TOPK;
+  int k = 0;                   // TOPK: k <= 64; CAND: kc
+  float* part_s = nullptr;     // TOPK / CAND: the partial lists of the nsplit x nq workgroups
+  uint32_t* part_i = nullptr;
+  const float* thr = nullptr;  // RANGE: thresholds [nq], counters [nq] (cleared here), pool slices of cap hits
+  unsigned* cnt = nullptr;
+  unsigned cap = 0;
+  float* hit_s = nullptr;
+  uint32_t* hit_r = nullptr;
+};
+
+// S of the index at np probed lists (host arithmetic; cached until nprobe changes or the index is rebuilt)
+static uint64_t pq_slab(knnx_index* ix, int np) {
+  if (ix->pq.slab_np != np) {
+    ix->pq.slab = pq_plan_slab(ix->pq.size_h.data(), (int64_t)ix->pq.size_h.size(), np);
+    ix->pq.slab_np = np;
+  }
+  return ix->pq.slab;
+}
+
+// the buffer of plan.floats() partial sums (at least one), grown on demand
+static int pq_half_buffer(knnx_index* ix, const PqPlan& plan) {
+  PqScratch& S = ix->pqs;
+  const uint64_t need = std::max<uint64_t>(plan.floats(), 1);
+  if (S.half && S.half_cap >= need) return 0;
+  S.half.reset();
+  S.half_cap = 0;
+  S.half_nq = 0;
+  if (need > (uint64_t)SIZE_MAX / 4 || malloc_or_reclaim(ix, S.half, (size_t)need) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(KNNX_E_NOMEM, "IVF-PQ with M = 256: no device memory for " + std::to_string(need * 4) + " bytes of partial sums (" +
+                                  std::to_string(plan.g) + " queries x " + std::to_string(plan.slab) +
+                                  " probed rows x 4; KNNX_PQ_PARTIAL_MAX_BYTES lowers it)");
+  }
+  S.half_cap = need;
+  return 0;
+}
+
+// The stage over the nq queries of the pass whose front half is in ix->pqs: per sub-group of the plan the lower-half kernel, then the
+// upper half of the scan asked for.  A pass that is ONE sub-group keeps its partial sums for the later stages of the same front half
+// (the k = 64 pass and every threshold scan of a descent read the same sums); pq_front forgets them.
+static int pq_two_half_stage(knnx_index* ix, int nq, int np, int nsplit, const PqStage& a, hipStream_t st) {
+  PqScratch& S = ix->pqs;
+  const PqPlan plan(pq_slab(ix, np), nq, ix->pq.partial_budget);
+  int r = pq_half_buffer(ix, plan);
+  if (r) return r;
+  if (a.kind == PqStage::RANGE) HIPCHK(hipMemsetAsync(a.cnt, 0, (size_t)nq * sizeof(unsigned), st));
+  const bool whole = plan.groups() == 1;
+  for (int i = 0; i < plan.groups(); ++i) {
+    const int q0 = plan.first(i), g = plan.count(i);
+    if (!(whole && S.half_nq == nq)) {
+      // (with kept sums a query may have finished since they were made: only a scan that makes its own may skip the finished ones)
+      HIPCHK(launch_pq_adc_lower(ix->pq.codes, S.lut, S.probe, S.pcnt, np, pq_nsplit(np, g), ix->ivf.tile0, ix->ivf.size, S.poff,
+                                 whole ? nullptr : a.thr, (size_t)plan.slab, q0, g, S.half, st));
+      S.half_nq = whole ? nq : 0;
+    }
+    switch (a.kind) {
+      case PqStage::TOPK:
+        HIPCHK(launch_pq_adc_upper(ix->pq.codes, S.lut, S.probe, S.pscore, S.pcnt, np, nsplit, ix->ivf.tile0, ix->ivf.size, ix->ivf.idmap, a.k,
+                                   nq, a.part_s, a.part_i, S.part_n, S.half, S.poff, (size_t)plan.slab, q0, g, st));
+        break;
+      case PqStage::CAND:
+        HIPCHK(launch_pq_cand_upper(ix->pq.codes, S.lut, S.probe, S.pscore, S.pcnt, np, nsplit, ix->ivf.tile0, ix->ivf.size, ix->ivf.idmap, a.k,
+                                    nq, a.part_s, a.part_i, S.part_n, S.half, S.poff, (size_t)plan.slab, q0, g, st));
+        break;
+      case PqStage::RANGE:
+        HIPCHK(launch_pq_range_upper(ix->pq.codes, S.lut, S.probe, S.pscore, S.pcnt, np, nsplit, ix->ivf.tile0, ix->ivf.size, a.thr, a.cnt,
+                                     a.cap, a.hit_s, a.hit_r, S.half, S.poff, (size_t)plan.slab, q0, g, st));
+        break;
+    }
+  }
+  return 0;
+}
+
+// the ADC top-k scan of the pass (k <= 64) into the partial lists part_s / part_i / S.part_n: one launch, or the two halves at M = 256
+static int pq_stage_topk(knnx_index* ix, int nq, int np, int nsplit, int k, float* part_s, uint32_t* part_i, hipStream_t st) {
+  PqScratch& S = ix->pqs;
+  if (ix->pq.m == 256) {
+    PqStage a;
+    a.kind = PqStage::TOPK, a.k = k, a.part_s = part_s, a.part_i = part_i;
+    return pq_two_half_stage(ix, nq, np, nsplit, a, st);
+  }
+  HIPCHK(launch_pq_adc_scan(ix->pq.codes, ix->pq.m, S.lut, S.probe, S.pscore, S.pcnt, np, nsplit, ix->ivf.tile0, ix->ivf.size, ix->ivf.idmap, k, nq,
+                            part_s, part_i, S.part_n, st));
+  return 0;
+}
 
 // Refine store (knnx_ivfpq_set_refine): the ADC stage keeps kc = k x k_factor candidates instead of k -- for kc <= 64 the scan and
 // merge above, for more the workgroup-queue scan and the LDS selection (pq_cand_scan_kernel, pq_cand_select_kernel) with the
@@ -70,13 +166,18 @@ int scan_topk_pq(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out
     PqScratch& S = ix->pqs;
     HIPCHK(ix->prof.begin(ix->prof.on, st));
     if (kc <= PQ_MAX_K) {
-      HIPCHK(launch_pq_adc_scan(ix->pq.codes, ix->pq.m, S.lut, S.probe, S.pscore, S.pcnt, np, nsplit, ix->ivf.tile0, ix->ivf.size, ix->ivf.idmap,
-                                kc, nq, S.part_s, S.part_i, S.part_n, st));
+      if ((r = pq_stage_topk(ix, nq, np, nsplit, kc, S.part_s, S.part_i, st))) return r;
       HIPCHK(launch_merge_u32(S.part_s, S.part_i, S.part_n, nsplit, nq, kc, nq, kc, ix->id_base, ix->ivf.idmap, S.rdc, S.rcand, nullptr, st));
     } else {
       nsplit = std::max(1, std::min(nsplit, PQ_SEL_MAX / kc));
-      HIPCHK(launch_pq_cand_scan(ix->pq.codes, ix->pq.m, S.lut, S.probe, S.pscore, S.pcnt, np, nsplit, ix->ivf.tile0, ix->ivf.size,
-                                 ix->ivf.idmap, kc, nq, S.rpart_s, S.rpart_r, S.part_n, st));
+      if (ix->pq.m == 256) {
+        PqStage a;
+        a.kind = PqStage::CAND, a.k = kc, a.part_s = S.rpart_s, a.part_i = S.rpart_r;
+        if ((r = pq_two_half_stage(ix, nq, np, nsplit, a, st))) return r;
+      } else {
+        HIPCHK(launch_pq_cand_scan(ix->pq.codes, ix->pq.m, S.lut, S.probe, S.pscore, S.pcnt, np, nsplit, ix->ivf.tile0, ix->ivf.size,
+                                   ix->ivf.idmap, kc, nq, S.rpart_s, S.rpart_r, S.part_n, st));
+      }
       HIPCHK(launch_pq_cand_select(S.rpart_s, S.rpart_r, S.part_n, nsplit, nq, kc, ix->ivf.idmap, S.rcand, st));
     }
     HIPCHK(launch_pq_refine(ix->rows, ix->d, q_orig, nq, ix->id_base, ix->ntotal, ix->ivf.inv, S.rcand, kc, k, S.rscore, D_out, I_out, st));
@@ -84,8 +185,7 @@ int scan_topk_pq(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out
     return 0;
   }
   HIPCHK(ix->prof.begin(ix->prof.on, st));
-  HIPCHK(launch_pq_adc_scan(ix->pq.codes, ix->pq.m, ix->pqs.lut, ix->pqs.probe, ix->pqs.pscore, ix->pqs.pcnt, np, nsplit, ix->ivf.tile0, ix->ivf.size,
-                            ix->ivf.idmap, k, nq, ix->pqs.part_s, ix->pqs.part_i, ix->pqs.part_n, st));
+  if ((r = pq_stage_topk(ix, nq, np, nsplit, k, ix->pqs.part_s, ix->pqs.part_i, st))) return r;
   HIPCHK(ix->prof.end(ix->prof.on, st));
   HIPCHK(launch_merge_u32(ix->pqs.part_s, ix->pqs.part_i, ix->pqs.part_n, nsplit, nq, k, nq, k, ix->id_base, ix->ivf.idmap, D_out, I_out,
                           nullptr, st));
@@ -101,8 +201,8 @@ int scan_topk_pq(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out
 int pq_pass_top64(knnx_index* ix, int nq, int np, float* D64, hipStream_t st) {
   PqScratch& S = ix->pqs;
   const int nsplit = pq_nsplit(np, nq), k = KNNX_MAX_K_FAST;
-  HIPCHK(launch_pq_adc_scan(ix->pq.codes, ix->pq.m, S.lut, S.probe, S.pscore, S.pcnt, np, nsplit, ix->ivf.tile0, ix->ivf.size, ix->ivf.idmap, k,
-                            nq, S.part_s, S.part_i, S.part_n, st));
+  int r = pq_stage_topk(ix, nq, np, nsplit, k, S.part_s, S.part_i, st);
+  if (r) return r;
   HIPCHK(launch_merge_u32(S.part_s, S.part_i, S.part_n, nsplit, nq, k, nq, k, ix->id_base, ix->ivf.idmap, ix->flat.D_dev, ix->flat.I_dev,
                           nullptr, st));
   HIPCHK(hipMemcpyAsync(D64, ix->flat.D_dev, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
@@ -134,8 +234,15 @@ int pq_pass_threshold_scan(knnx_index* ix, int nq, int np, const float* thr_h, u
   HIPCHK(S.alloc_threshold());
   HIPCHK(hipMemcpyAsync(S.tthr, thr_h, (size_t)nq * sizeof(float), hipMemcpyHostToDevice, st));
   HIPCHK(ix->prof.begin(ix->prof.on, st));
-  HIPCHK(launch_pq_range_scan(ix->pq.codes, ix->pq.m, S.lut, S.probe, S.pscore, S.pcnt, np, pq_nsplit(np, nq), ix->ivf.tile0, ix->ivf.size,
-                              S.tthr, S.tcnt, cap, ix->range.s, ix->range.i, nq, st));
+  if (ix->pq.m == 256) {
+    PqStage a;
+    a.kind = PqStage::RANGE, a.thr = S.tthr, a.cnt = S.tcnt, a.cap = cap, a.hit_s = ix->range.s, a.hit_r = ix->range.i;
+    int r = pq_two_half_stage(ix, nq, np, pq_nsplit(np, nq), a, st);
+    if (r) return r;
+  } else {
+    HIPCHK(launch_pq_range_scan(ix->pq.codes, ix->pq.m, S.lut, S.probe, S.pscore, S.pcnt, np, pq_nsplit(np, nq), ix->ivf.tile0, ix->ivf.size,
+                                S.tthr, S.tcnt, cap, ix->range.s, ix->range.i, nq, st));
+  }
   HIPCHK(ix->prof.end(ix->prof.on, st));
   counts.assign((size_t)nq, 0u);
   HIPCHK(hipMemcpyAsync(counts.data(), S.tcnt, (size_t)nq * sizeof(unsigned), hipMemcpyDeviceToHost, st));
@@ -171,9 +278,11 @@ extern "C" int knnx_ivfpq_threshold_stats(knnx_index* ix, int64_t* queries, int6
 // for large corpora (the reference's notebook builds OPQ256_768,IVF16384_HNSW32,PQ256x8).  The quantizer is set on an empty
 // index; the IVF build protocol then ENCODES rows into the list-sorted arena; searches go through scan_topk_pq.
 // ---------------------------------------------------------------------------------------------
+static const char* const PQ_M_RULE = "IVF-PQ needs M in {16, 32, 64, 128} dividing d (8-bit codes), or M = 256 with d >= 512";
+
 extern "C" int knnx_ivfpq_set_quantizer(knnx_index* ix, int M, const float* codebooks) {
   if (!ix || !codebooks) return fail(KNNX_E_ARG, "bad ivfpq_set_quantizer arguments");
-  if (!pq_supported(ix->d, M)) return fail(KNNX_E_ARG, "IVF-PQ needs M in {16, 32, 64, 128} dividing d (8-bit codes)");
+  if (!pq_supported(ix->d, M)) return fail(KNNX_E_ARG, PQ_M_RULE);
   std::lock_guard<std::mutex> lk(ix->mu);
   if (set_dev(ix)) return KNNX_E_HIP;
   if (ix->rows.borrowed || ix->ntotal != 0 || ix->ivf_nlist || ix->ivfb.nlist || ix->pq.m)
@@ -182,6 +291,11 @@ extern "C" int knnx_ivfpq_set_quantizer(knnx_index* ix, int M, const float* code
   HIPCHK(ix->pq.cb.alloc((size_t)256 * ix->d));
   HIPCHK(hipMemcpy(ix->pq.cb, codebooks, bytes, hipMemcpyHostToDevice));
   ix->pq.m = M;
+  if (M == 256) {  // the budget of the two-half scan's partial sums, read once like the switches of knnx_create
+    const char* v = getenv("KNNX_PQ_PARTIAL_MAX_BYTES");
+    const long long b = (v && v[0]) ? atoll(v) : 0;
+    ix->pq.partial_budget = b > 0 ? (uint64_t)b : PQ_PARTIAL_DEFAULT_BYTES;
+  }
   return KNNX_OK;
 }
 
@@ -407,7 +521,7 @@ extern "C" void knnx_pqb_destroy(knnx_pq_builder* b) {
 extern "C" int knnx_pqb_create(int device, int d, int M, knnx_pq_builder** out) {
   if (!out) return fail(KNNX_E_ARG, "out is null");
   *out = nullptr;
-  if (!pq_supported(d, M)) return fail(KNNX_E_ARG, "IVF-PQ needs M in {16, 32, 64, 128} dividing d (8-bit codes)");
+  if (!pq_supported(d, M)) return fail(KNNX_E_ARG, PQ_M_RULE);
   HIPCHK(hipSetDevice(device));
   knnx_pq_builder* b = new knnx_pq_builder();
   b->device = device;

@@ -221,6 +221,8 @@ class Mi355xIndex(_FaissShaped):
     # ------------------------------------------------------------------ IVF-PQ
     def set_pq_quantizer(self, M, codebooks):
         """Make this EMPTY index an IVF-PQ one (faiss IndexIVFPQ(IndexFlatIP(d), d, nlist, M, 8)): codebooks f32 [M, 256, d_padded / M].
+        M in {16, 32, 64, 128} dividing d_padded, or M = 256 (PQ256x8) with d_padded in {512, 768, 1024}; M = 256 scores in two halves of
+        m through a scratch buffer of partial sums capped by KNNX_PQ_PARTIAL_MAX_BYTES (include/knnx.h).
         The rows then go in through knnx_ivf_begin / add_assigned / end (build_ivfpq_index*), which encode them."""
         cb = np.ascontiguousarray(codebooks, dtype=np.float32)
         if cb.size != 256 * self._dpad:

@@ -150,14 +150,24 @@ int knnx_ivf_add_assigned_device(knnx_index* ix, const void* rows_dev_f16, int64
 
 /* ---- IVF-PQ: faiss IndexIVFPQ(IndexFlatIP(d), d, nlist, M, 8), METRIC_INNER_PRODUCT, by_residual = true ----------------------
  * (the index type autofaiss builds for large corpora -- clip_index.py:12-66; the reference notebook's OPQ256_768,IVF16384_HNSW32,PQ256x8
- * without the HNSW coarse quantiser; the OPQ rotation is the block below).  M in {16, 32, 64, 128} dividing d, 256 centroids per sub-quantiser; other M:
+ * without the HNSW coarse quantiser; the OPQ rotation is the block below).  M in {16, 32, 64, 128} dividing d, or M = 256 with d in
+ * {512, 768, 1024} (d / M = 2, 3, 4; PQ256x8); 256 centroids per sub-quantiser; other M, and M = 256 at d = 256:
  * KNNX_E_ARG.  Codebooks: f32 [M][256][d / M].  Row x of list l: residual r = f32(x_f16) - f32(c_l), code byte m =
  * argmin_j ||r_m - C[m][j]||^2 in fp32 (ties -> smaller j).  Score = <q, c_l> + sum over m (in order) of LUT[m][code_m], LUT[m][j] =
  * <q_m, C[m][j]> in fp32; the coarse quantiser and its probe rule are those of IVF-Flat.  Results as knnx_search; reconstruct /
  * the R of search returns the decoded vector f32(c_l) + concat_m C[m][code_m].
  * Build: knnx_ivfpq_set_quantizer on an empty index, then knnx_ivf_begin / knnx_ivf_add_assigned[_device] / knnx_ivf_end ENCODE
  * the rows (same list / position rules), or knnx_ivfpq_add_codes loads precomputed codes in their place.  The arena holds M bytes
- * per row.  k > 64 and range_search answer KNNX_E_UNSUPPORTED (unless switched on: knnx_ivfpq_set_threshold_scan below); add / attach / synth_fill / reset / reserve / knnx_ivf_set_lists
+ * per row (M + 12 with the id maps: 268 at M = 256 against 2 d + 12 for fp16 rows).
+ * M = 256: the query's lookup table (256 KiB) does not fit the LDS, so the ADC stage runs in two halves of m: a first kernel stores,
+ * for every row of the probed lists, the fp32 sum over m = 0 .. 127; the scan proper starts from that stored value and continues over
+ * m = 128 .. 255.  A 4-byte store and load is exact, so the score is still cs + (ONE fp32 sum over m = 0 .. 255 in ascending order
+ * from 0.f), and everything defined on the scores -- k <= 64, the refine store, the threshold scan, the rotation, the other entry
+ * points -- holds at M = 256 word for word.  Memory rule: the partial sums take g x S x 4 bytes of scratch, S = the sum of the nprobe
+ * largest list sizes of the index, g = the queries scored at once (<= 256); when 256 x S x 4 exceeds KNNX_PQ_PARTIAL_MAX_BYTES (read
+ * from the environment by knnx_ivfpq_set_quantizer; default 1 GiB, a guess nobody has measured) a pass scores its queries in consecutive
+ * sub-groups of g = max(1, budget / (S x 4)); results do not depend on g.  A buffer that cannot be had: KNNX_E_NOMEM naming the bytes.
+ * An index with M <= 128 allocates and launches nothing of this.  k > 64 and range_search answer KNNX_E_UNSUPPORTED (unless switched on: knnx_ivfpq_set_threshold_scan below); add / attach / synth_fill / reset / reserve / knnx_ivf_set_lists
  * answer KNNX_E_STATE.  At most 2^32 - 1 padded rows per device. */
 int knnx_ivfpq_set_quantizer(knnx_index* ix, int M, const float* codebooks);
 int knnx_ivfpq_add_codes(knnx_index* ix, const uint8_t* codes, int64_t n, const int64_t* ids, const int32_t* lists, const int32_t* pos);

@@ -6,6 +6,9 @@ at a size where both fit).  Prints ONE JSON line.
   python tools/ivfpq_bench.py                                   # config 5's shard: 125 M x 1024, nlist 65 536, M = 64
   python tools/ivfpq_bench.py --rows 1000000000 --d 768         # the headline index on one GPU
   python tools/ivfpq_bench.py --rows 16000000 --nlist 16384 --flat-ab
+  python tools/ivfpq_bench.py --rows 16000000 --d 768 --nlist 16384 --M 256 --nprobes 16,64
+                                                                # PQ256x8 (the two-half ADC scan; yardstick: the same line with --M 128);
+                                                                # also prints the partial-sum slab and the sub-groups of a 256-query pass
   python tools/ivfpq_bench.py --opq                             # + the same index behind an OPQ rotation: rotate_s, recall, times
   python tools/ivfpq_bench.py --opq --kind 2                    # ... on the dominant-column corpus (knnx_synth_rows_device kind 2)
   python tools/ivfpq_bench.py --rows 16000000 --nlist 16384 --nprobes 64 --refine [--k-factor 1,4,8]
@@ -106,6 +109,16 @@ def main():
             grid[f"B{B}_np{npb}"] = {"ms": round(t * 1e3, 3), "qps": round(B / t, 1), "adc_scan_ms": round(scan_ms, 3),
                                      "code_bytes_model": int(code_bytes), "code_TBps_model": round(code_bytes / (scan_ms * 1e-3) / 1e12, 2) if scan_ms else None}
     out["search"] = grid
+    if a.M == 256:
+        # the two-half ADC scan's partial sums (csrc/knnx_pq_plan.h): slab = the nprobe largest lists, and whether the budget cut a
+        # 256-query pass into sub-groups
+        budget = int(os.environ.get("KNNX_PQ_PARTIAL_MAX_BYTES") or 0) or 1 << 30
+        sizes = np.sort(np.asarray(st["list_sizes"], dtype=np.int64))[::-1]
+        out["partial_sums"] = {"budget_bytes": budget}
+        for npb in [int(v) for v in a.nprobes.split(",")]:
+            slab = int(sizes[:npb].sum())
+            g = min(256, max(1, budget // max(slab * 4, 1)))
+            out["partial_sums"][f"np{npb}"] = {"slab_rows": slab, "bytes_B256": min(g, 256) * slab * 4, "sub_groups_B256": -(-256 // g)}
 
     # recall@40 at nprobe 64 against the exact top-40, streamed over the corpus in chunks (flat scans of device-generated rows)
     nr, k = a.recall_queries, 40

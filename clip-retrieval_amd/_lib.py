@@ -86,6 +86,8 @@ SIGNATURES = {
     "knnx_ivfpq_get_codebooks": (C.c_int, [_P, _P]),
     "knnx_ivfpq_set_rotation": (C.c_int, [_P, _P]),
     "knnx_ivfpq_get_rotation": (C.c_int, [_P, _P]),
+    "knnx_ivfpq_set_out_dim": (C.c_int, [_P, C.c_int]),
+    "knnx_ivfpq_out_dim": (C.c_int, [_P]),
     "knnx_ivfpq_set_refine": (C.c_int, [_P, C.c_int]),
     "knnx_ivfpq_refine": (C.c_int, [_P]),
     "knnx_ivfpq_set_k_factor": (C.c_int, [_P, C.c_int]),
@@ -95,6 +97,7 @@ SIGNATURES = {
     "knnx_ivfpq_threshold_stats": (C.c_int, [_P, _P, _P, _P, _P]),
     "knnx_ivfpq_arena_bytes": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "knnx_rotate_f16_device": (C.c_int, [C.c_int, _P, _P, C.c_int64, C.c_int, _P, _P]),
+    "knnx_rotate_rect_f16_device": (C.c_int, [C.c_int, _P, _P, C.c_int64, C.c_int, C.c_int, _P, _P]),
     "knnx_xty_device": (C.c_int, [C.c_int, _P, _P, C.c_int64, C.c_int, _P, _P]),
     "knnx_pqb_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "knnx_pqb_destroy": (None, [_P]),

@@ -226,14 +226,15 @@ hipError_t launch_pq_range_upper(const uint8_t* codes, const float* lut, const i
                                  int nsplit, const unsigned* tile0, const unsigned* size, const float* thr, unsigned* cnt, unsigned cap,
                                  float* hit_s, uint32_t* hit_r, const float* half, const unsigned* poff, size_t slab, int q0, int g,
                                  hipStream_t st);
-// OPQ rotation in front of IVF-PQ (A f32 [d][d], y = A x; d in {256, 512, 768, 1024}).  launch_rot_split: A -> W fp16 [2 d][d], the
-// hi / lo tile image launch_rotate_f16 (knn_rq_kernels.hip, MFMA) streams: Y[i] = fp16(A P[i]), Y and P distinct.  launch_rot_queries:
-// out[i] = A q[i] in fp32 (nq <= 256 per launch is what it is sized for; any nq works).  launch_rot_back: out[i] = A^T dec[i] in fp32
+// OPQ rotation in front of IVF-PQ (A f32 [d_out][d], y = A x; d <= d_out, both in {256, 512, 768, 1024}; d_out = d: the square
+// rotation).  launch_rot_split: A -> W fp16 [2 d_out][d], the hi / lo tile image launch_rotate_f16 (knn_rq_kernels.hip, MFMA) streams:
+// Y[i] = fp16(A P[i]) (P rows d wide, Y rows d_out wide), Y and P distinct.  launch_rot_queries: out[i] = A q[i] in fp32, d_out wide
+// (nq <= 256 per launch is what it is sized for; any nq works).  launch_rot_back: out[i] = A^T dec[i] in fp32, dec d_out wide, out d wide
 // (rows of 0xFF bytes stay 0xFF bytes; out and dec distinct).  launch_xty: G = X^T Y, f32 [d][d], fixed summation order.
-hipError_t launch_rot_split(const float* A, int d, _Float16* W, hipStream_t st);
-hipError_t launch_rotate_f16(const _Float16* W, int d, const _Float16* P, int64_t n, _Float16* Y, hipStream_t st);
-hipError_t launch_rot_queries(const float* A, int d, const float* q, int nq, float* out, hipStream_t st);
-hipError_t launch_rot_back(const float* A, int d, const float* dec, int64_t n, float* out, hipStream_t st);
+hipError_t launch_rot_split(const float* A, int d, int d_out, _Float16* W, hipStream_t st);
+hipError_t launch_rotate_f16(const _Float16* W, int d, int d_out, const _Float16* P, int64_t n, _Float16* Y, hipStream_t st);
+hipError_t launch_rot_queries(const float* A, int d, int d_out, const float* q, int nq, float* out, hipStream_t st);
+hipError_t launch_rot_back(const float* A, int d, int d_out, const float* dec, int64_t n, float* out, hipStream_t st);
 hipError_t launch_xty(const _Float16* X, const float* Y, int64_t n, int d, float* G, hipStream_t st);
 hipError_t launch_pq_scatter_codes(const uint8_t* src, int64_t n, int M, const int32_t* lists, const int32_t* pos, const int64_t* ids,
                                    const unsigned* tile0, int64_t id_lo, int64_t n_ids, uint8_t* codes, int64_t* idmap, uint32_t* inv,

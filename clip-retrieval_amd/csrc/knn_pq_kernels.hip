@@ -798,8 +798,8 @@ __global__ __launch_bounds__(256) void pq_scatter_codes_kernel(const uint8_t* __
 // OPQ rotation A (f32 [d][d] row-major, y = A x) in front of the index: the small kernels around it.  (The row rotation of the build
 // is the MFMA kernel knn_rotate_kernel of knn_rq_kernels.hip.)
 // ---------------------------------------------------------------------------------------------
-// A -> W fp16 [2 d][d], the streamed operand of knn_rotate_kernel: rows 32 p .. 32 p + 31 of A become tile 2 p (2048 x the part fp16
-// cannot hold) and tile 2 p + 1 (fp16(A))
+// A [d_out][d] -> W fp16 [2 d_out][d], the streamed operand of knn_rotate_kernel: rows 32 p .. 32 p + 31 of A become tile 2 p (2048 x
+// the part fp16 cannot hold) and tile 2 p + 1 (fp16(A)).  One workgroup per row of A (grid = d_out), d = the row length.
 __global__ __launch_bounds__(256) void rot_split_kernel(const float* __restrict__ A, int d, _Float16* __restrict__ W) {
   const int j = blockIdx.x;
   const size_t lo_row = (size_t)(j >> 5) * 64 + (j & 31), hi_row = lo_row + 32;
@@ -811,11 +811,12 @@ __global__ __launch_bounds__(256) void rot_split_kernel(const float* __restrict_
   }
 }
 
-// queries: out[i][j] = <A[j], q[i]> for nq <= 256 queries.  Workgroup g owns ROT_QJ rows of A (staged in the LDS once per launch: A is
-// read once however many queries there are) and its 4 waves walk the queries; lane l sums columns l, l + 64, ... in ascending order
-// (fmaf), then the 64 partial sums meet in a butterfly: a fixed order, so a query's rotation does not depend on its batch.
+// queries: out[i][j] = <A[j], q[i]> for nq <= 256 queries, A f32 [DO][D], q rows D wide, out rows DO wide.  Workgroup g owns ROT_QJ
+// rows of A (staged in the LDS once per launch: A is read once however many queries there are) and its 4 waves walk the queries; lane
+// l sums columns l, l + 64, ... in ascending order (fmaf), then the 64 partial sums meet in a butterfly: a fixed order, so a query's
+// rotation does not depend on its batch.
 constexpr int ROT_QJ = 4;
-template <int D>
+template <int D, int DO>
 __global__ __launch_bounds__(256) void rot_query_kernel(const float* __restrict__ A, const float* __restrict__ q, int nq,
                                                        float* __restrict__ out) {
   __shared__ float sa[ROT_QJ][D];
@@ -840,28 +841,29 @@ __global__ __launch_bounds__(256) void rot_query_kernel(const float* __restrict_
       for (int r = 0; r < ROT_QJ; ++r) acc[r] += __shfl_xor(acc[r], o);
     if (lane == 0) {
 #pragma unroll
-      for (int r = 0; r < ROT_QJ; ++r) out[(size_t)i * D + j0 + r] = acc[r];
+      for (int r = 0; r < ROT_QJ; ++r) out[(size_t)i * DO + j0 + r] = acc[r];
     }
   }
 }
 
 // back to the original space (reconstruct, the R of a search): out[i] = A^T dec[i], out[i][c] = sum_j A[j][c] dec[i][j] in fp32, j
-// ascending (fmaf).  A workgroup takes ROT_BR decoded rows into the LDS, thread c owns columns c, c + 256, ... of all of them: a row of A
-// is read once per ROT_BR output rows, coalesced.  dec rows of a bad id are 0xFF bytes (pq_decode_kernel) and stay 0xFF bytes.
+// ascending over the DO rows of A (fmaf); dec rows are DO wide, out rows D wide.  A workgroup takes ROT_BR decoded rows into the LDS,
+// thread c owns columns c, c + 256, ... of all of them: a row of A is read once per ROT_BR output rows, coalesced.  dec rows of a bad id
+// are 0xFF bytes (pq_decode_kernel) and stay 0xFF bytes.
 constexpr int ROT_BR = 8;
-template <int D>
+template <int D, int DO>
 __global__ __launch_bounds__(256) void rot_back_kernel(const float* __restrict__ A, const float* __restrict__ dec, int64_t n,
                                                       float* __restrict__ out) {
-  __shared__ float sy[ROT_BR][D];
+  __shared__ float sy[ROT_BR][DO];
   __shared__ int bad[ROT_BR];
   const int64_t i0 = (int64_t)blockIdx.x * ROT_BR;
   const int tid = threadIdx.x;
-  for (int e = tid; e < ROT_BR * D; e += 256) {
-    const int64_t i = i0 + e / D;
-    sy[e / D][e % D] = i < n ? dec[(size_t)i * D + e % D] : 0.f;
+  for (int e = tid; e < ROT_BR * DO; e += 256) {
+    const int64_t i = i0 + e / DO;
+    sy[e / DO][e % DO] = i < n ? dec[(size_t)i * DO + e % DO] : 0.f;
   }
   __syncthreads();
-  if (tid < ROT_BR) bad[tid] = __float_as_int(sy[tid][0]) == -1 && __float_as_int(sy[tid][D - 1]) == -1;
+  if (tid < ROT_BR) bad[tid] = __float_as_int(sy[tid][0]) == -1 && __float_as_int(sy[tid][DO - 1]) == -1;
   __syncthreads();
   constexpr int NC = D / 256;
   float acc[ROT_BR][NC];
@@ -869,7 +871,7 @@ __global__ __launch_bounds__(256) void rot_back_kernel(const float* __restrict__
   for (int r = 0; r < ROT_BR; ++r)
 #pragma unroll
     for (int u = 0; u < NC; ++u) acc[r][u] = 0.f;
-  for (int j = 0; j < D; ++j) {
+  for (int j = 0; j < DO; ++j) {
     float a[NC];
 #pragma unroll
     for (int u = 0; u < NC; ++u) a[u] = A[(size_t)j * D + tid + 256 * u];
@@ -933,37 +935,38 @@ __global__ __launch_bounds__(256) void xty_kernel(const _Float16* __restrict__ X
 // ---------------------------------------------------------------------------------------------
 static bool rot_supported(int d) { return d == 256 || d == 512 || d == 768 || d == 1024; }
 
-hipError_t launch_rot_split(const float* A, int d, _Float16* W, hipStream_t st) {
-  if (!rot_supported(d)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(rot_split_kernel, dim3((unsigned)d), dim3(256), 0, st, A, d, W);
+hipError_t launch_rot_split(const float* A, int d, int d_out, _Float16* W, hipStream_t st) {
+  if (!rot_supported(d) || !rot_supported(d_out) || d_out < d) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(rot_split_kernel, dim3((unsigned)d_out), dim3(256), 0, st, A, d, W);
   return hipGetLastError();
 }
 
-#define ROT_BY_D(CALL)          \
-  switch (d) {                  \
-    case 256: CALL(256); break; \
-    case 512: CALL(512); break; \
-    case 768: CALL(768); break; \
-    case 1024: CALL(1024); break; \
-    default: return hipErrorInvalidValue; \
-  }
+// the ten (d, d_out) pairs: d_out = d and the six rectangular ones, d < d_out
+#define ROT_PAIR(CALL, DI, DOUT) \
+  if (d == DI && d_out == DOUT) { CALL(DI, DOUT); } else
+#define ROT_BY_D(CALL)                                                                                                   \
+  ROT_PAIR(CALL, 256, 256) ROT_PAIR(CALL, 512, 512) ROT_PAIR(CALL, 768, 768) ROT_PAIR(CALL, 1024, 1024)                  \
+  ROT_PAIR(CALL, 256, 512) ROT_PAIR(CALL, 256, 768) ROT_PAIR(CALL, 256, 1024) ROT_PAIR(CALL, 512, 768)                   \
+  ROT_PAIR(CALL, 512, 1024) ROT_PAIR(CALL, 768, 1024) return hipErrorInvalidValue;
 
-hipError_t launch_rot_queries(const float* A, int d, const float* q, int nq, float* out, hipStream_t st) {
+hipError_t launch_rot_queries(const float* A, int d, int d_out, const float* q, int nq, float* out, hipStream_t st) {
   if (nq <= 0) return hipSuccess;
-#define ROT_Q(DD) hipLaunchKernelGGL(rot_query_kernel<DD>, dim3((unsigned)(DD / ROT_QJ)), dim3(256), 0, st, A, q, nq, out)
+#define ROT_Q(DI, DOUT) hipLaunchKernelGGL((rot_query_kernel<DI, DOUT>), dim3((unsigned)(DOUT / ROT_QJ)), dim3(256), 0, st, A, q, nq, out)
   ROT_BY_D(ROT_Q)
 #undef ROT_Q
   return hipGetLastError();
 }
 
-hipError_t launch_rot_back(const float* A, int d, const float* dec, int64_t n, float* out, hipStream_t st) {
+hipError_t launch_rot_back(const float* A, int d, int d_out, const float* dec, int64_t n, float* out, hipStream_t st) {
   if (n <= 0) return hipSuccess;
-#define ROT_B(DD) hipLaunchKernelGGL(rot_back_kernel<DD>, dim3((unsigned)((n + ROT_BR - 1) / ROT_BR)), dim3(256), 0, st, A, dec, n, out)
+#define ROT_B(DI, DOUT) \
+  hipLaunchKernelGGL((rot_back_kernel<DI, DOUT>), dim3((unsigned)((n + ROT_BR - 1) / ROT_BR)), dim3(256), 0, st, A, dec, n, out)
   ROT_BY_D(ROT_B)
 #undef ROT_B
   return hipGetLastError();
 }
 #undef ROT_BY_D
+#undef ROT_PAIR
 
 hipError_t launch_xty(const _Float16* X, const float* Y, int64_t n, int d, float* G, hipStream_t st) {
   if (n <= 0 || !rot_supported(d)) return hipErrorInvalidValue;

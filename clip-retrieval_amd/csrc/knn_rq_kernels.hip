@@ -1201,10 +1201,12 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void knn_assign_kernel(const _Floa
 // newest DMA pieces) then covers stores that have had a whole tile to retire instead of ones issued a moment ago.
 // ---------------------------------------------------------------------------------------------
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-template <int KS, int NW, int NSLOT>
+// d_out > d_in (A f32 [d_out][d_in], orthonormal columns): the stationary points stay d_in = 16 KS wide, W has 2 d_out rows of d_in
+// columns (KO = d_out / 16 tiles), the output rows are d_out wide.  KO = KS is the square kernel, instruction for instruction.
+template <int KS, int KO, int NW, int NSLOT>
 __global__ __launch_bounds__(NW * 64, NW / 4) void knn_rotate_kernel(const _Float16* __restrict__ W, const _Float16* __restrict__ P,
                                                                      int64_t n, _Float16* __restrict__ Y) {
-  constexpr int D = KS * 16;
+  constexpr int D = KS * 16, DO = KO * 16;
   constexpr int TILE_BYTES = KS * 1024;
   constexpr int DPW = KS / NW;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1214,7 +1216,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void knn_rotate_kernel(const _Floa
   constexpr int NSC = KNNX_MFMA16 ? 8 : 16, NG = NSC / 4;
   const int qcol = lane & (QBS - 1), hb = lane / QBS;
   const _Float16* X = W;  // the streamed operand (RQ_TILE below)
-  constexpr int64_t N = 2 * D;
+  constexpr int64_t N = 2 * DO;
 
   int64_t pidx[NQB];
   half8 Q[NQB][NSL];
@@ -1231,7 +1233,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void knn_rotate_kernel(const _Floa
 #pragma unroll
     for (int s = 0; s < NSL; ++s) asm volatile("" : "+v"(Q[b][s]));  // all landed before the DMA ring starts (see the scan)
 
-  constexpr int64_t ntile = N / 32;  // = KS, no ragged tile (d % 256 == 0)
+  constexpr int64_t ntile = N / 32;  // = KO, no ragged tile (d_out % 256 == 0)
   constexpr int64_t last = ntile - 1;
   const RqLaneOff lane_off = rq_lane_offsets(lane, D, 31);
   const unsigned lds_base = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem);
@@ -1254,7 +1256,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void knn_rotate_kernel(const _Floa
         for (int b = 0; b < NQB; ++b)
 #pragma unroll
           for (int g = 0; g < NG; ++g)
-            if (pidx[b] < n) *reinterpret_cast<half4*>(Y + (size_t)pidx[b] * D + col0 + RQ_ROWOFF(4 * g)) = pend[b][g];
+            if (pidx[b] < n) *reinterpret_cast<half4*>(Y + (size_t)pidx[b] * DO + col0 + RQ_ROWOFF(4 * g)) = pend[b][g];
       }
 #if KNNX_MFMA16
 #pragma unroll
@@ -1293,7 +1295,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void knn_rotate_kernel(const _Floa
   for (int b = 0; b < NQB; ++b)
 #pragma unroll
     for (int g = 0; g < NG; ++g)
-      if (pidx[b] < n) *reinterpret_cast<half4*>(Y + (size_t)pidx[b] * D + col0 + RQ_ROWOFF(4 * g)) = pend[b][g];
+      if (pidx[b] < n) *reinterpret_cast<half4*>(Y + (size_t)pidx[b] * DO + col0 + RQ_ROWOFF(4 * g)) = pend[b][g];
 }
 #undef RQ_SCORE
 #undef RQ_ROWOFF
@@ -1321,10 +1323,10 @@ hipError_t launch_assign(const _Float16* C, int64_t nlist, int d, const _Float16
   }
 }
 
-template <int KS, int NW, int NSLOT>
+template <int KS, int KO, int NW, int NSLOT>
 static hipError_t launch_rotate_cfg(const _Float16* W, const _Float16* P, int64_t n, _Float16* Y, hipStream_t st) {
   const size_t smem = (size_t)NSLOT * KS * 1024;
-  auto kern = knn_rotate_kernel<KS, NW, NSLOT>;
+  auto kern = knn_rotate_kernel<KS, KO, NW, NSLOT>;
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   if (e != hipSuccess) return e;
   const int64_t per = NW * 32;
@@ -1332,14 +1334,25 @@ static hipError_t launch_rotate_cfg(const _Float16* W, const _Float16* P, int64_
   return hipGetLastError();
 }
 
-// Y[i] = fp16(A P[i]) for n fp16 rows; W = the hi / lo tile image of A (launch_rot_split); Y must not overlap P
-hipError_t launch_rotate_f16(const _Float16* W, int d, const _Float16* P, int64_t n, _Float16* Y, hipStream_t st) {
+// the widths of a rotation: d_in, d_out in {256, 512, 768, 1024}, d_in <= d_out (csrc/knnx_rot_shape.h states the rule for callers)
+template <int KS, int NW, int NSLOT>
+static hipError_t launch_rotate_out(int d_out, const _Float16* W, const _Float16* P, int64_t n, _Float16* Y, hipStream_t st) {
+  if (d_out == KS * 16) return launch_rotate_cfg<KS, KS, NW, NSLOT>(W, P, n, Y, st);
+  if constexpr (KS < 32) if (d_out == 512) return launch_rotate_cfg<KS, 32, NW, NSLOT>(W, P, n, Y, st);
+  if constexpr (KS < 48) if (d_out == 768) return launch_rotate_cfg<KS, 48, NW, NSLOT>(W, P, n, Y, st);
+  if constexpr (KS < 64) if (d_out == 1024) return launch_rotate_cfg<KS, 64, NW, NSLOT>(W, P, n, Y, st);
+  return hipErrorInvalidValue;
+}
+
+// Y[i] = fp16(A P[i]) for n fp16 rows of d columns, Y rows d_out wide; W = the hi / lo tile image of A [d_out][d] (launch_rot_split);
+// Y must not overlap P.  The configurations follow d (the stationary operand), whatever d_out is.
+hipError_t launch_rotate_f16(const _Float16* W, int d, int d_out, const _Float16* P, int64_t n, _Float16* Y, hipStream_t st) {
   if (n <= 0) return hipSuccess;
   switch (d) {
-    case 256: return launch_rotate_cfg<16, 8, 3>(W, P, n, Y, st);
-    case 512: return launch_rotate_cfg<32, 8, 3>(W, P, n, Y, st);
-    case 768: return launch_rotate_cfg<48, 8, 3>(W, P, n, Y, st);
-    case 1024: return launch_rotate_cfg<64, 4, 2>(W, P, n, Y, st);
+    case 256: return launch_rotate_out<16, 8, 3>(d_out, W, P, n, Y, st);
+    case 512: return launch_rotate_out<32, 8, 3>(d_out, W, P, n, Y, st);
+    case 768: return launch_rotate_out<48, 8, 3>(d_out, W, P, n, Y, st);
+    case 1024: return launch_rotate_out<64, 4, 2>(d_out, W, P, n, Y, st);
     default: return hipErrorInvalidValue;
   }
 }

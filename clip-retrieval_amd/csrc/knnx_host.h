@@ -348,7 +348,7 @@ struct IvfBuild {
   std::vector<uint16_t> cent;
   // device staging of one chunk
   DevBuf<_Float16> rows;  // [IVFB_CHUNK, d] (knnx_ivfpq_add_codes stages its code bytes here: M <= 2 d)
-  DevBuf<_Float16> rot;   // [IVFB_CHUNK, d] the chunk rotated, what the encoder reads (IVF-PQ with a rotation only)
+  DevBuf<_Float16> rot;   // [IVFB_CHUNK, d_out] the chunk rotated, what the encoder reads (IVF-PQ with a rotation only)
   DevBuf<int64_t> ids;
   DevBuf<int32_t> lists, pos;
   // host mirror of the layout, so that every (list, position) a caller hands over is checked before it is scattered
@@ -361,14 +361,18 @@ struct IvfBuild {
 // and tile-padded like the IVF-Flat rows (`rows` stays null); the coarse quantiser is the IVF one
 struct PqData {
   int m = 0;
-  DevBuf<float> cb;                      // [M][256][d / M]
+  // the quantiser width d_out (knnx_ivfpq_set_out_dim; 0: none was given, the index has ONE width d).  With it the index has two:
+  // knnx_index::d is what the user sees (queries, rows entering the build, the refine store, reconstruct), dq is where the centroids,
+  // residuals, codebooks, lookup tables and codes live; the rotation A [dq][d] leads from one to the other.  Read it through pq_dq().
+  int dq = 0;
+  DevBuf<float> cb;                      // [M][256][d_out / M]
   DevBuf<uint8_t> codes;                 // [capacity][M]
   DevBuf<_Float16> bcent;                // centroids during the build (knnx_ivf_begin .. knnx_ivf_end)
   std::vector<unsigned> tile0_h, size_h; // host copy of the layout (knnx_ivfpq_get_codes)
   // OPQ rotation (knnx_ivfpq_set_rotation; empty: none): y = A x in front of everything above
-  std::vector<float> rot_h;              // A, f32 [d][d] (knnx_ivfpq_get_rotation, knnx_shards_adopt)
+  std::vector<float> rot_h;              // A, f32 [d_out][d] (knnx_ivfpq_get_rotation, knnx_shards_adopt)
   DevBuf<float> rot;                     // the same on the device (queries, back-rotation)
-  DevBuf<_Float16> rot_w;                // [2 d][d] hi / lo tile image (row rotation of the build; released by knnx_ivf_end)
+  DevBuf<_Float16> rot_w;                // [2 d_out][d] hi / lo tile image (row rotation of the build; released by knnx_ivf_end)
   // refine store (knnx_ivfpq_set_refine): the fp16 rows as they entered the build, un-rotated, in the arena order of the codes.
   // They live in knnx_index::rows ([capacity][d], allocated by knnx_ivf_begin); ivf.idmap / ivf.inv serve codes and rows alike.
   bool refine = false;
@@ -396,7 +400,7 @@ struct PqScratch {
   DevBuf<float> part_s;     // [PQ_SLOTS][64] per-workgroup top-k of the ADC scan
   DevBuf<uint32_t> part_i;
   DevBuf<int> part_n;       // [PQ_SLOTS]
-  DevBuf<float> qrot;       // [256][d] the rotated queries (allocated by scan_topk_pq when the index has a rotation)
+  DevBuf<float> qrot;       // [256][d_out] the rotated queries (allocated by scan_topk_pq when the index has a rotation)
   // refine (allocated by the first refine search): candidates of one pass and their exact scores, the partial lists of the candidate
   // scan for kc > 64, the ADC scores the merge writes next to the candidate ids for kc <= 64
   DevBuf<int64_t> rcand;    // [256][PQ_REFINE_MAX]
@@ -565,6 +569,9 @@ struct knnx_index {
   Event ev_scratch;
   bool ev_valid = false;
 };
+
+// the width of the quantiser space of an IVF-PQ index: d unless knnx_ivfpq_set_out_dim gave another
+inline int pq_dq(const knnx_index* ix) { return ix->pq.dq ? ix->pq.dq : ix->d; }
 
 // ---- what one host file calls in another ---------------------------------------------------------
 // knnx_api.hip

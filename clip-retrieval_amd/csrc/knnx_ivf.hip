@@ -453,6 +453,12 @@ extern "C" int knnx_ivf_begin(knnx_index* ix, int nlist, const uint16_t* centroi
   std::lock_guard<std::mutex> lk(ix->mu);
   if (set_dev(ix)) return KNNX_E_HIP;
   if (ix->rows.borrowed || ix->ntotal != 0 || ix->ivf_nlist || ix->ivfb.nlist) return fail(KNNX_E_STATE, "ivf_begin needs an empty index that owns its rows");
+  // the centroids, and with them the encoder, live in the quantiser space: dq = d unless the index was given a d_out
+  const int dq = ix->pq.m ? pq_dq(ix) : ix->d;
+  if (dq != ix->d && !ix->pq.rot)
+    return fail(KNNX_E_STATE, "an index with d_out = " + std::to_string(dq) + " != d = " + std::to_string(ix->d) +
+                                  " needs its rotation [d_out][d] before knnx_ivf_begin (knnx_ivfpq_set_rotation): nothing else leads "
+                                  "from the rows to the quantiser space");
   TileLayout t;
   int r = ivf_tile_layout(nlist, list_sizes, t);
   if (r) return r;
@@ -465,8 +471,8 @@ extern "C" int knnx_ivf_begin(knnx_index* ix, int nlist, const uint16_t* centroi
   if (ix->pq.m) {  // IVF-PQ: M code bytes per arena row, and the centroids on the device for the encoder
     dev_alloc(e, ix->pq.codes, (size_t)prow * ix->pq.m);
     if (e == hipSuccess) e = hipMemsetAsync(ix->pq.codes, 0, (size_t)prow * ix->pq.m, ix->stream);
-    dev_alloc(e, ix->pq.bcent, (size_t)nlist * ix->d);
-    if (e == hipSuccess) e = hipMemcpyAsync(ix->pq.bcent, centroids_f16, (size_t)nlist * ix->d * sizeof(_Float16), hipMemcpyHostToDevice, ix->stream);
+    dev_alloc(e, ix->pq.bcent, (size_t)nlist * dq);
+    if (e == hipSuccess) e = hipMemcpyAsync(ix->pq.bcent, centroids_f16, (size_t)nlist * dq * sizeof(_Float16), hipMemcpyHostToDevice, ix->stream);
     if (ix->pq.refine) {  // the row arena next to the code arena (pad rows are zero)
       if (e == hipSuccess) e = malloc_or_reclaim(ix, ix->rows, (size_t)prow * ix->d);
       if (e == hipSuccess) e = hipMemsetAsync(ix->rows, 0, (size_t)prow * ix->d * sizeof(_Float16), ix->stream);
@@ -477,7 +483,7 @@ extern "C" int knnx_ivf_begin(knnx_index* ix, int nlist, const uint16_t* centroi
   }
   if (e == hipSuccess) e = hipMemsetAsync(ix->ivf.idmap, 0xFF, (size_t)prow * sizeof(int64_t), ix->stream);  // -1 on pad rows
   dev_alloc(e, B.rows, (size_t)IVFB_CHUNK * ix->d);
-  if (ix->pq.rot) dev_alloc(e, B.rot, (size_t)IVFB_CHUNK * ix->d);
+  if (ix->pq.rot) dev_alloc(e, B.rot, (size_t)IVFB_CHUNK * dq);
   dev_alloc(e, B.ids, (size_t)IVFB_CHUNK);
   dev_alloc(e, B.lists, (size_t)IVFB_CHUNK);
   dev_alloc(e, B.pos, (size_t)IVFB_CHUNK);
@@ -493,7 +499,7 @@ extern "C" int knnx_ivf_begin(knnx_index* ix, int nlist, const uint16_t* centroi
     return fail(e == hipErrorOutOfMemory ? KNNX_E_NOMEM : KNNX_E_HIP, std::string("ivf_begin: ") + hipGetErrorString(e));
   }
   ix->capacity = prow;
-  ix->ivfb.cent.assign(centroids_f16, centroids_f16 + (size_t)nlist * ix->d);
+  ix->ivfb.cent.assign(centroids_f16, centroids_f16 + (size_t)nlist * dq);
   ix->ivfb.size.assign(t.size.begin(), t.size.end());
   ix->ivfb.tile0.assign(t.tile0.begin(), t.tile0.end());
   ix->ivfb.fill.assign(nlist, 0u);
@@ -564,8 +570,8 @@ extern "C" int knnx_ivf_add_assigned(knnx_index* ix, const uint16_t* rows_f16, i
       if (ix->pq.refine)
         HIPCHK(launch_ivf_scatter(ix->ivfb.rows, m, ix->d, ix->ivfb.lists, ix->ivfb.pos, ix->ivfb.ids, 0, ix->ivf.tile0, ix->id_base,
                                   ix->ivfb.total, ix->rows, ix->ivf.idmap, ix->ivf.inv, ix->stream));
-      if (ix->pq.rot) HIPCHK(launch_rotate_f16(ix->pq.rot_w, ix->d, ix->ivfb.rows, m, ix->ivfb.rot, ix->stream));
-      HIPCHK(launch_pq_encode(ix->pq.rot ? ix->ivfb.rot.p : ix->ivfb.rows.p, m, ix->d, ix->pq.m, ix->ivfb.lists, ix->pq.bcent, ix->pq.cb,
+      if (ix->pq.rot) HIPCHK(launch_rotate_f16(ix->pq.rot_w, ix->d, pq_dq(ix), ix->ivfb.rows, m, ix->ivfb.rot, ix->stream));
+      HIPCHK(launch_pq_encode(ix->pq.rot ? ix->ivfb.rot.p : ix->ivfb.rows.p, m, pq_dq(ix), ix->pq.m, ix->ivfb.lists, ix->pq.bcent, ix->pq.cb,
                               ix->ivf.tile0, ix->ivfb.pos, ix->ivfb.ids, 0, ix->id_base, ix->ivfb.total,
                               ix->pq.codes, ix->ivf.idmap, ix->ivf.inv, ix->stream));
     } else {
@@ -630,8 +636,8 @@ extern "C" int knnx_ivf_add_assigned_device(knnx_index* ix, const void* rows_dev
       if (ix->pq.refine)
         HIPCHK(launch_ivf_scatter(src, m, ix->d, lists_dev + o, ix->ivfb.pos, nullptr, id0 + o, ix->ivf.tile0, ix->id_base, ix->ivfb.total,
                                   ix->rows, ix->ivf.idmap, ix->ivf.inv, ix->stream));
-      if (ix->pq.rot) HIPCHK(launch_rotate_f16(ix->pq.rot_w, ix->d, src, m, ix->ivfb.rot, ix->stream));
-      HIPCHK(launch_pq_encode(ix->pq.rot ? ix->ivfb.rot.p : src, m, ix->d, ix->pq.m, lists_dev + o, ix->pq.bcent, ix->pq.cb, ix->ivf.tile0, ix->ivfb.pos,
+      if (ix->pq.rot) HIPCHK(launch_rotate_f16(ix->pq.rot_w, ix->d, pq_dq(ix), src, m, ix->ivfb.rot, ix->stream));
+      HIPCHK(launch_pq_encode(ix->pq.rot ? ix->ivfb.rot.p : src, m, pq_dq(ix), ix->pq.m, lists_dev + o, ix->pq.bcent, ix->pq.cb, ix->ivf.tile0, ix->ivfb.pos,
                               nullptr, id0 + o, ix->id_base, ix->ivfb.total, ix->pq.codes, ix->ivf.idmap, ix->ivf.inv, ix->stream));
     } else {
       HIPCHK(launch_ivf_scatter(src, m, ix->d, lists_dev + o, ix->ivfb.pos, nullptr, id0 + o, ix->ivf.tile0, ix->id_base,
@@ -668,7 +674,8 @@ extern "C" int knnx_ivf_end(knnx_index* ix) {
     std::vector<uint64_t>().swap(ix->ivfb.taken);
     ix->ivfb.rows.reset(), ix->ivfb.rot.reset(), ix->ivfb.ids.reset(), ix->ivfb.lists.reset(), ix->ivfb.pos.reset();
   }
-  int r = knnx_create(ix->device, ix->d, KNNX_METRIC_INNER_PRODUCT, &ix->cent);
+  // (the coarse quantiser is a flat index in the quantiser space; ix->pq is settled by now, so the width is read without the lock)
+  int r = knnx_create(ix->device, ix->pq.m ? pq_dq(ix) : ix->d, KNNX_METRIC_INNER_PRODUCT, &ix->cent);
   if (r) return r;
   r = knnx_add_f16(ix->cent, ix->ivfb.cent.data(), nlist);
   if (r) return r;

@@ -3,6 +3,7 @@
 
 #include "knnx_host.h"
 #include "knnx_pq_plan.h"
+#include "knnx_rot_shape.h"
 
 // ---------------------------------------------------------------------------------------------
 // IVF-PQ pass of 1 .. 256 queries already in HBM (csrc/knn_pq_kernels.hip): the coarse quantiser of the multi-block IVF pass
@@ -15,15 +16,16 @@
 // stage scores (the rotated ones behind an OPQ rotation), *np_out = lists probed per query.
 int pq_front(knnx_index* ix, const float* q_dev, int nq, hipStream_t st, const float** q_used, int* np_out) {
   const int np = std::min(ix->ivf_nprobe, ix->ivf_nlist);
-  HIPCHK(ix->pqs.alloc(ix->d, (size_t)ix->ivf_nlist, ix->pq.m, np));
+  const int dq = pq_dq(ix);  // everything behind the rotation is dq wide (= d unless the index was given a d_out)
+  HIPCHK(ix->pqs.alloc(dq, (size_t)ix->ivf_nlist, ix->pq.m, np));
   knnx_index* c = ix->cent;
   const int nblk = (nq + KNN_NQ - 1) / KNN_NQ;
   if (ix->pq.rot) {  // OPQ: everything below sees q' = A q
-    if (!ix->pqs.qrot) HIPCHK(ix->pqs.qrot.alloc((size_t)PQ_PASS * ix->d));
-    HIPCHK(launch_rot_queries(ix->pq.rot, ix->d, q_dev, nq, ix->pqs.qrot, st));
+    if (!ix->pqs.qrot) HIPCHK(ix->pqs.qrot.alloc((size_t)PQ_PASS * dq));
+    HIPCHK(launch_rot_queries(ix->pq.rot, ix->d, dq, q_dev, nq, ix->pqs.qrot, st));
     q_dev = ix->pqs.qrot;
   }
-  HIPCHK(launch_prep_blocks(q_dev, nq, ix->d, ix->pqs.qfrag, ix->pqs.thr, ix->pqs.thr + PQ_PASS, st));
+  HIPCHK(launch_prep_blocks(q_dev, nq, dq, ix->pqs.qfrag, ix->pqs.thr, ix->pqs.thr + PQ_PASS, st));
   ScanArgs ca{};
   ca.X = c->rows;
   ca.N = c->ntotal;
@@ -45,7 +47,7 @@ int pq_front(knnx_index* ix, const float* q_dev, int nq, hipStream_t st, const f
     HIPCHK(launch_pq_probe_offsets(ix->pqs.probe, ix->pqs.pcnt, np, ix->ivf.size, ix->pqs.poff, nq, st));
     ix->pqs.half_nq = 0;  // the sums of an earlier front half are not these queries'
   }
-  HIPCHK(launch_pq_lut(q_dev, nq, ix->d, ix->pq.m, ix->pq.cb, ix->pqs.lut, st));
+  HIPCHK(launch_pq_lut(q_dev, nq, dq, ix->pq.m, ix->pq.cb, ix->pqs.lut, st));
   *q_used = q_dev;
   *np_out = np;
   return 0;
@@ -282,13 +284,14 @@ static const char* const PQ_M_RULE = "IVF-PQ needs M in {16, 32, 64, 128} dividi
 
 extern "C" int knnx_ivfpq_set_quantizer(knnx_index* ix, int M, const float* codebooks) {
   if (!ix || !codebooks) return fail(KNNX_E_ARG, "bad ivfpq_set_quantizer arguments");
-  if (!pq_supported(ix->d, M)) return fail(KNNX_E_ARG, PQ_M_RULE);
+  const int dq = pq_dq(ix);  // (the rule speaks of the quantiser width: d_out where knnx_ivfpq_set_out_dim gave one)
+  if (!pq_supported(dq, M)) return fail(KNNX_E_ARG, PQ_M_RULE);
   std::lock_guard<std::mutex> lk(ix->mu);
   if (set_dev(ix)) return KNNX_E_HIP;
   if (ix->rows.borrowed || ix->ntotal != 0 || ix->ivf_nlist || ix->ivfb.nlist || ix->pq.m)
     return fail(KNNX_E_STATE, "the PQ quantizer is set once, on an empty index, before knnx_ivf_begin");
-  const size_t bytes = (size_t)256 * ix->d * sizeof(float);
-  HIPCHK(ix->pq.cb.alloc((size_t)256 * ix->d));
+  const size_t bytes = (size_t)256 * dq * sizeof(float);
+  HIPCHK(ix->pq.cb.alloc((size_t)256 * dq));
   HIPCHK(hipMemcpy(ix->pq.cb, codebooks, bytes, hipMemcpyHostToDevice));
   ix->pq.m = M;
   if (M == 256) {  // the budget of the two-half scan's partial sums, read once like the switches of knnx_create
@@ -300,6 +303,20 @@ extern "C" int knnx_ivfpq_set_quantizer(knnx_index* ix, int M, const float* code
 }
 
 extern "C" int knnx_ivfpq_m(const knnx_index* ix) { return ix ? ix->pq.m : 0; }
+
+// ---- the quantiser width (faiss OPQMatrix(d_in, M, d_out) with d_out > d_in): chosen before the quantizer, which is d_out wide ------
+extern "C" int knnx_ivfpq_set_out_dim(knnx_index* ix, int d_out) {
+  if (!ix) return fail(KNNX_E_ARG, "index is null");
+  if (d_out != ix->d && !rot_shape_supported(ix->d, d_out))
+    return fail(KNNX_E_ARG, "d_out = " + std::to_string(d_out) + " on an index of d = " + std::to_string(ix->d) +
+                                ": both widths must be multiples of 256 with 256 <= d <= d_out <= 1024");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  if (ix->pq.m || ix->rows.borrowed || ix->ntotal != 0 || ix->ivf_nlist || ix->ivfb.nlist)
+    return fail(KNNX_E_STATE, "d_out is chosen on an empty index, before knnx_ivfpq_set_quantizer");
+  ix->pq.dq = d_out == ix->d ? 0 : d_out;
+  return KNNX_OK;
+}
+extern "C" int knnx_ivfpq_out_dim(const knnx_index* ix) { return ix && ix->pq.m ? pq_dq(ix) : 0; }
 
 // ---- refine store (faiss IndexRefineFlat(IndexIVFPQ)): the index keeps the fp16 rows next to the codes --------------------------
 extern "C" int knnx_ivfpq_set_refine(knnx_index* ix, int on) {
@@ -332,31 +349,30 @@ extern "C" int knnx_ivfpq_arena_bytes(knnx_index* ix, int64_t* code_bytes, int64
   return KNNX_OK;
 }
 
-// ---- OPQ rotation (faiss IndexPreTransform(OPQMatrix(d, M), IndexIVFPQ), d_out = d_in) --------------------------------------------
-// A f32 [d][d] row-major, y = A x.  Orthonormal or refused: max |A A^T - I| <= 1e-3, checked in float64 on the host (d^3 <= 1e9
-// multiply-adds, once per index).
+// ---- OPQ rotation (faiss IndexPreTransform(OPQMatrix(d, M, d_out), IndexIVFPQ)) --------------------------------------------------
+// A f32 [d_out][d] row-major, y = A x.  Orthonormal or refused, checked in float64 on the host (csrc/knnx_rot_shape.h; at most 1e9
+// multiply-adds, once per index): the square matrix by its rows, max |A A^T - I| <= 1e-3; the rectangular one (d_out > d) by its
+// columns, max |A^T A - I_d| <= 1e-3 -- its rows cannot be orthonormal, its columns are what keeps <A q, A x> = <q, x>.
 extern "C" int knnx_ivfpq_set_rotation(knnx_index* ix, const float* A) {
   if (!ix || !A) return fail(KNNX_E_ARG, "bad ivfpq_set_rotation arguments");
   std::lock_guard<std::mutex> lk(ix->mu);
   if (set_dev(ix)) return KNNX_E_HIP;
   if (!ix->pq.m || ix->ntotal != 0 || ix->ivf_nlist || ix->ivfb.nlist)
     return fail(KNNX_E_STATE, "the rotation is set on an IVF-PQ index after knnx_ivfpq_set_quantizer and before knnx_ivf_begin");
-  const int d = ix->d;
-  double worst = 0.0;
-  for (int i = 0; i < d; ++i)
-    for (int j = i; j < d; ++j) {
-      const float *a = A + (size_t)i * d, *b = A + (size_t)j * d;
-      double s = 0.0;
-      for (int c = 0; c < d; ++c) s += (double)a[c] * (double)b[c];
-      const double e = fabs(s - (i == j ? 1.0 : 0.0));
-      if (!(e <= worst)) worst = e;  // (a NaN lands here too)
-    }
-  if (!(worst <= 1e-3)) return fail(KNNX_E_ARG, "the rotation is not orthonormal (max |A A^T - I| > 1e-3)");
+  const int d = ix->d, dq = pq_dq(ix);
+  if (dq == d) {
+    if (!(rot_row_gram_error(A, d, d) <= 1e-3)) return fail(KNNX_E_ARG, "the rotation is not orthonormal (max |A A^T - I| > 1e-3)");
+  } else {
+    std::vector<double> G((size_t)d * d);
+    if (!(rot_col_gram_error(A, dq, d, G.data()) <= 1e-3))
+      return fail(KNNX_E_ARG, "the rotation [" + std::to_string(dq) + "][" + std::to_string(d) +
+                                  "] does not have orthonormal columns (max |A^T A - I| > 1e-3)");
+  }
   hipError_t e = hipSuccess;
-  dev_alloc(e, ix->pq.rot, (size_t)d * d);
-  dev_alloc(e, ix->pq.rot_w, (size_t)2 * d * d);
-  if (e == hipSuccess) e = hipMemcpy(ix->pq.rot, A, (size_t)d * d * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = launch_rot_split(ix->pq.rot, d, ix->pq.rot_w, ix->stream);
+  dev_alloc(e, ix->pq.rot, (size_t)dq * d);
+  dev_alloc(e, ix->pq.rot_w, (size_t)2 * dq * d);
+  if (e == hipSuccess) e = hipMemcpy(ix->pq.rot, A, (size_t)dq * d * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = launch_rot_split(ix->pq.rot, d, dq, ix->pq.rot_w, ix->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ix->stream);
   if (e != hipSuccess) {
     ix->pq.rot.reset();
@@ -364,11 +380,11 @@ extern "C" int knnx_ivfpq_set_rotation(knnx_index* ix, const float* A) {
     ix->pq.rot_h.clear();
     HIPCHK(e);
   }
-  ix->pq.rot_h.assign(A, A + (size_t)d * d);
+  ix->pq.rot_h.assign(A, A + (size_t)dq * d);
   return KNNX_OK;
 }
 
-// 0 and the matrix, or 1 (A untouched) when the index has no rotation
+// 0 and the matrix [d_out][d], or 1 (A untouched) when the index has no rotation
 extern "C" int knnx_ivfpq_get_rotation(knnx_index* ix, float* A) {
   if (!ix || !A) return fail(KNNX_E_ARG, "bad ivfpq_get_rotation arguments");
   std::lock_guard<std::mutex> lk(ix->mu);
@@ -378,26 +394,41 @@ extern "C" int knnx_ivfpq_get_rotation(knnx_index* ix, float* A) {
 }
 
 // The stand-alone row rotation: out[i] = fp16(A rows[i]) for n fp16 rows in HBM (the OPQ trainer, the device-streamed build's
-// assignment pass).  A: host f32 [d][d] (not checked for orthonormality: the trainer's iterates are what they are); out must not
-// overlap rows.  Synchronous.
+// assignment pass).  A: host f32 [d_out][d_in] (not checked for orthonormality: the trainer's iterates are what they are); rows are
+// d_in wide, out rows d_out wide; out must not overlap rows.  Synchronous.
+static int rotate_rows_device(int device, const float* A_host, const void* rows_dev_f16, int64_t n, int d, int dq, void* out_dev_f16,
+                              void* stream) {
+  HIPCHK(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  DevBuf<float> A;
+  DevBuf<_Float16> W;
+  HIPCHK(A.alloc((size_t)dq * d));
+  HIPCHK(W.alloc((size_t)2 * dq * d));
+  HIPCHK(hipMemcpyAsync(A, A_host, (size_t)dq * d * sizeof(float), hipMemcpyHostToDevice, st));
+  HIPCHK(launch_rot_split(A, d, dq, W, st));
+  for (int64_t o = 0; o < n; o += IVFB_CHUNK)
+    HIPCHK(launch_rotate_f16(W, d, dq, (const _Float16*)rows_dev_f16 + (size_t)o * d, std::min(IVFB_CHUNK, n - o),
+                             (_Float16*)out_dev_f16 + (size_t)o * dq, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return KNNX_OK;
+}
+
 extern "C" int knnx_rotate_f16_device(int device, const float* A_host, const void* rows_dev_f16, int64_t n, int d, void* out_dev_f16,
                                       void* stream) {
   if (!A_host || (n > 0 && (!rows_dev_f16 || !out_dev_f16)) || n < 0) return fail(KNNX_E_ARG, "bad rotate_f16_device arguments");
   if (d != 256 && d != 512 && d != 768 && d != 1024) return fail(KNNX_E_ARG, "the rotation takes d in {256, 512, 768, 1024}");
   if (n == 0) return KNNX_OK;
-  HIPCHK(hipSetDevice(device));
-  hipStream_t st = (hipStream_t)stream;
-  DevBuf<float> A;
-  DevBuf<_Float16> W;
-  HIPCHK(A.alloc((size_t)d * d));
-  HIPCHK(W.alloc((size_t)2 * d * d));
-  HIPCHK(hipMemcpyAsync(A, A_host, (size_t)d * d * sizeof(float), hipMemcpyHostToDevice, st));
-  HIPCHK(launch_rot_split(A, d, W, st));
-  for (int64_t o = 0; o < n; o += IVFB_CHUNK)
-    HIPCHK(launch_rotate_f16(W, d, (const _Float16*)rows_dev_f16 + (size_t)o * d, std::min(IVFB_CHUNK, n - o),
-                             (_Float16*)out_dev_f16 + (size_t)o * d, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return KNNX_OK;
+  return rotate_rows_device(device, A_host, rows_dev_f16, n, d, d, out_dev_f16, stream);
+}
+
+extern "C" int knnx_rotate_rect_f16_device(int device, const float* A_host, const void* rows_dev_f16, int64_t n, int d_in, int d_out,
+                                           void* out_dev_f16, void* stream) {
+  if (!A_host || (n > 0 && (!rows_dev_f16 || !out_dev_f16)) || n < 0) return fail(KNNX_E_ARG, "bad rotate_rect_f16_device arguments");
+  if (!rot_shape_supported(d_in, d_out))
+    return fail(KNNX_E_ARG, "the rotation takes d_in <= d_out, both in {256, 512, 768, 1024} (got d_in = " + std::to_string(d_in) +
+                                ", d_out = " + std::to_string(d_out) + ")");
+  if (n == 0) return KNNX_OK;
+  return rotate_rows_device(device, A_host, rows_dev_f16, n, d_in, d_out, out_dev_f16, stream);
 }
 
 // G = X^T Y (f32 [d][d], device) for fp16 rows X and f32 rows Y [n][d] in HBM: the d x d product of an OPQ iteration, every element
@@ -416,14 +447,15 @@ int pq_decode_rows(knnx_index* ix, const int64_t* ids_dev, int64_t n, float* out
     HIPCHK(launch_gather_inv(ix->rows, ix->d, ix->id_base, ix->ntotal, ix->ivf.inv, ids_dev, n, out_dev, st));
     return KNNX_OK;
   }
+  const int dq = pq_dq(ix);  // the decode is dq wide; A^T brings it back to d (without a rotation dq = d: knnx_ivf_begin saw to it)
   float* dec = out_dev;
   if (ix->pq.rot) {
-    int r = ensure_scratch(ix, 5, (size_t)n * ix->d * sizeof(float), (void**)&dec);
+    int r = ensure_scratch(ix, 5, (size_t)n * dq * sizeof(float), (void**)&dec);
     if (r) return r;
   }
-  HIPCHK(launch_pq_decode(ix->pq.codes, ix->d, ix->pq.m, ix->pq.cb, ix->cent ? ix->cent->rows : nullptr, ix->ivf.tile0, ix->ivf_nlist,
+  HIPCHK(launch_pq_decode(ix->pq.codes, dq, ix->pq.m, ix->pq.cb, ix->cent ? ix->cent->rows : nullptr, ix->ivf.tile0, ix->ivf_nlist,
                           ix->id_base, ix->ntotal, ix->ivf.inv, ids_dev, n, dec, st));
-  if (ix->pq.rot) HIPCHK(launch_rot_back(ix->pq.rot, ix->d, dec, n, out_dev, st));
+  if (ix->pq.rot) HIPCHK(launch_rot_back(ix->pq.rot, ix->d, dq, dec, n, out_dev, st));
   return KNNX_OK;
 }
 
@@ -432,7 +464,7 @@ extern "C" int knnx_ivfpq_get_codebooks(knnx_index* ix, float* codebooks) {
   std::lock_guard<std::mutex> lk(ix->mu);
   if (!ix->pq.m) return fail(KNNX_E_STATE, "not an IVF-PQ index");
   if (set_dev(ix)) return KNNX_E_HIP;
-  HIPCHK(hipMemcpy(codebooks, ix->pq.cb, (size_t)256 * ix->d * sizeof(float), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(codebooks, ix->pq.cb, (size_t)256 * pq_dq(ix) * sizeof(float), hipMemcpyDeviceToHost));
   return KNNX_OK;
 }
 

@@ -197,7 +197,11 @@ extern "C" int knnx_shards_adopt(int n_shards, knnx_index* const* shards, const 
   const int d = knnx_dim(shards[0]);
   for (int g = 0; g < n_shards; ++g)
     if (!shards[g] || knnx_dim(shards[g]) != d) return fail(KNNX_E_ARG, "shards disagree on the dimension");
-  // IVF-PQ shards answer in one space only if they carry the same rotation (bit for bit), or none
+  // IVF-PQ shards answer in one space only if they quantise the same width behind the same rotation (bit for bit), or none
+  for (int g = 1; g < n_shards; ++g)
+    if (pq_dq(shards[g]) != pq_dq(shards[0]))
+      return fail(KNNX_E_ARG, "IVF-PQ shards disagree on the quantiser width: d_out = " + std::to_string(pq_dq(shards[0])) + " and " +
+                                  std::to_string(pq_dq(shards[g])) + " (d = " + std::to_string(d) + ")");
   for (int g = 1; g < n_shards; ++g)
     if (shards[g]->pq.rot_h.size() != shards[0]->pq.rot_h.size() ||
         memcmp(shards[g]->pq.rot_h.data(), shards[0]->pq.rot_h.data(), shards[0]->pq.rot_h.size() * sizeof(float)) != 0)

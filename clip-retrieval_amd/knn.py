@@ -225,9 +225,29 @@ class Mi355xIndex(_FaissShaped):
         m through a scratch buffer of partial sums capped by KNNX_PQ_PARTIAL_MAX_BYTES (include/knnx.h).
         The rows then go in through knnx_ivf_begin / add_assigned / end (build_ivfpq_index*), which encode them."""
         cb = np.ascontiguousarray(codebooks, dtype=np.float32)
-        if cb.size != 256 * self._dpad:
-            raise AssertionError(f"codebooks must hold M x 256 x d_padded / M = {256 * self._dpad} floats, got {cb.shape}")
+        dq = self._pq_width()  # (d_padded, or the d_out of set_pq_out_dim)
+        if cb.size != 256 * dq:
+            raise AssertionError(f"codebooks must hold M x 256 x d_padded / M = {256 * dq} floats, got {cb.shape}")
         check(self._lib, self._lib.knnx_ivfpq_set_quantizer(self._h, int(M), cb.ctypes.data), "knnx")
+
+    def set_pq_out_dim(self, d_out):
+        """Give this EMPTY index a quantiser space wider than its rows (faiss OPQMatrix(d, M, d_out), "OPQ256_768" on 512-d rows):
+        before set_pq_quantizer, which then takes codebooks [M, 256, d_out / M]; the rotation is [d_out, d] and mandatory.  Both widths
+        multiples of 256, 256 <= d < d_out <= 1024; d_out == d changes nothing (include/knnx.h: knnx_ivfpq_set_out_dim)."""
+        d_out = int(d_out)
+        if d_out != self.d and self.d % 256 != 0:
+            raise ValueError(f"d_out = {d_out} != d needs d % 256 == 0 (got d = {self.d})")
+        check(self._lib, self._lib.knnx_ivfpq_set_out_dim(self._h, d_out), "knnx")
+        self._pq_dout = d_out if d_out != self.d else 0
+
+    def _pq_width(self):
+        """Width of the quantiser space as the library sees it: d_padded unless set_pq_out_dim gave a d_out."""
+        return getattr(self, "_pq_dout", 0) or self._dpad
+
+    @property
+    def pq_out_dim(self):
+        """Width of the quantiser space of an IVF-PQ index: d unless set_pq_out_dim gave another."""
+        return getattr(self, "_pq_dout", 0) or self.d
 
     @property
     def pq_m(self):
@@ -237,28 +257,29 @@ class Mi355xIndex(_FaissShaped):
     def pq_codebooks(self):
         """f32 [M, 256, d_padded / M]."""
         M = self.pq_m
-        out = np.empty((M, 256, self._dpad // max(M, 1)), dtype=np.float32)
+        out = np.empty((M, 256, self._pq_width() // max(M, 1)), dtype=np.float32)
         check(self._lib, self._lib.knnx_ivfpq_get_codebooks(self._h, out.ctypes.data), "knnx")
         return out
 
     def set_pq_rotation(self, A):
         """OPQ rotation in front of this IVF-PQ index (faiss IndexPreTransform(OPQMatrix(d, M), IndexIVFPQ)): A f32 [d, d], y = A x,
         orthonormal (max |A A^T - I| <= 1e-3) or refused.  After set_pq_quantizer, before the rows go in.  Callers keep passing and
-        receiving UN-ROTATED vectors: the index rotates rows and queries itself and reconstructs into the original space."""
+        receiving UN-ROTATED vectors: the index rotates rows and queries itself and reconstructs into the original space.
+        After set_pq_out_dim(d_out): A f32 [d_out, d] with orthonormal columns (max |A^T A - I| <= 1e-3)."""
         A = np.asarray(A, dtype=np.float32)
-        if A.shape != (self.d, self.d):
-            raise AssertionError(f"the rotation must be [{self.d}, {self.d}], got {A.shape}")
-        Ap = _pad_rotation(A, self._dpad)
+        if A.shape != (self.pq_out_dim, self.d):
+            raise AssertionError(f"the rotation must be [{self.pq_out_dim}, {self.d}], got {A.shape}")
+        Ap = np.ascontiguousarray(A) if self.pq_out_dim != self.d else _pad_rotation(A, self._dpad)
         check(self._lib, self._lib.knnx_ivfpq_set_rotation(self._h, Ap.ctypes.data), "knnx")
 
     def pq_rotation(self):
-        """The OPQ rotation f32 [d, d], or None when the index has none."""
-        out = np.empty((self._dpad, self._dpad), dtype=np.float32)
+        """The OPQ rotation f32 [d, d] ([d_out, d] after set_pq_out_dim), or None when the index has none."""
+        out = np.empty((self._pq_width(), self._dpad), dtype=np.float32)
         rc = self._lib.knnx_ivfpq_get_rotation(self._h, out.ctypes.data)
         if rc == 1:
             return None
         check(self._lib, rc, "knnx")
-        return np.ascontiguousarray(out[: self.d, : self.d])
+        return np.ascontiguousarray(out[: self.pq_out_dim, : self.d])
 
     def set_pq_refine(self, on=True):
         """Refine store (faiss IndexRefineFlat(IndexIVFPQ)): the index keeps the fp16 rows next to the codes (2 d bytes more per row) and
@@ -1279,18 +1300,38 @@ def _pad_rotation(A, dpad):
 
 def rotate_rows_device(A, rows_ptr, n, out_ptr, device=0, stream=None):
     """out[i] = fp16(A rows[i]) for n fp16 device rows [n, d_padded] (include/knnx.h: knnx_rotate_f16_device); A f32 [d_padded,
-    d_padded]; out must not overlap rows.  Synchronous."""
+    d_padded]; out must not overlap rows.  Synchronous.  A f32 [d_out, d_in] with d_out > d_in (knnx_rotate_rect_f16_device): rows
+    [n, d_in] -> out [n, d_out]."""
     A = np.ascontiguousarray(A, dtype=np.float32)
-    check(load_library(), load_library().knnx_rotate_f16_device(int(device), A.ctypes.data, C.c_void_p(int(rows_ptr)), int(n), A.shape[0],
-                                                                C.c_void_p(int(out_ptr)), C.c_void_p(stream) if stream else None), "knnx")
+    lib = load_library()
+    st = C.c_void_p(stream) if stream else None
+    if A.shape[0] != A.shape[1]:
+        check(lib, lib.knnx_rotate_rect_f16_device(int(device), A.ctypes.data, C.c_void_p(int(rows_ptr)), int(n), A.shape[1], A.shape[0],
+                                                   C.c_void_p(int(out_ptr)), st), "knnx")
+        return
+    check(lib, lib.knnx_rotate_f16_device(int(device), A.ctypes.data, C.c_void_p(int(rows_ptr)), int(n), A.shape[0], C.c_void_p(int(out_ptr)),
+                                          st), "knnx")
 
 
 def rotate_rows(A, x_f16, device=0, chunk=1 << 20):
-    """Host rows fp16 [n, d] -> fp16 [n, d] rotated on the device, chunk by chunk (the assignment pass of the host builds, tests)."""
+    """Host rows fp16 [n, d] -> fp16 [n, d] rotated on the device, chunk by chunk (the assignment pass of the host builds, tests).
+    A f32 [d_out, d] with d_out > d (d % 256 == 0): -> fp16 [n, d_out]."""
     import torch  # pylint: disable=import-outside-toplevel
 
     x_f16 = np.asarray(x_f16)
     n, d = x_f16.shape
+    A = np.asarray(A, dtype=np.float32)
+    if A.shape[0] != A.shape[1]:
+        if A.shape[1] != d or d % 256 != 0:
+            raise ValueError(f"a rotation {A.shape} takes rows of width {A.shape[1]} with d % 256 == 0, got rows of width {d}")
+        out = np.empty((n, A.shape[0]), dtype=np.float16)
+        for o in range(0, n, chunk):
+            xt = torch.from_numpy(np.array(x_f16[o:o + chunk], dtype=np.float16)).to(f"cuda:{device}")  # (a copy: the source may be read-only)
+            yt = torch.empty((xt.shape[0], A.shape[0]), dtype=torch.float16, device=xt.device)
+            torch.cuda.synchronize(device)
+            rotate_rows_device(A, xt.data_ptr(), xt.shape[0], yt.data_ptr(), device)
+            out[o:o + chunk] = yt.cpu().numpy()
+        return out
     dpad = (d + 255) // 256 * 256
     Ap = _pad_rotation(A, dpad)
     out = np.empty((n, d), dtype=np.float16)
@@ -1350,15 +1391,40 @@ def train_opq_device(x_ptr, n, d, M, niter=8, pq_niter=4, seed=0, device=0):
     return A
 
 
-def train_opq(x_f16, M, niter=8, pq_niter=4, seed=0, device=0, sample_rows=OPQ_SAMPLE_ROWS):
+def opq_embedding(d, d_out):
+    """The zero-embedding E f32 [d_out, d] (E x = x followed by d_out - d zeros): rotating rows by it pads them on the device, exactly."""
+    E = np.zeros((d_out, d), dtype=np.float32)
+    E[np.arange(d), np.arange(d)] = 1.0
+    return E
+
+
+def _check_opq_dim(d, d_out):
+    if d % 256 != 0 or d_out % 256 != 0 or not 256 <= d < d_out <= 1024:
+        raise ValueError(f"an OPQ rotation with d_out != d needs both widths multiples of 256 and 256 <= d < d_out <= 1024 "
+                         f"(got d = {d}, d_out = {d_out})")
+
+
+def train_opq(x_f16, M, niter=8, pq_niter=4, seed=0, device=0, sample_rows=OPQ_SAMPLE_ROWS, d_out=None):
     """OPQ rotation for host rows fp16 [n, d] (a seeded sample of <= sample_rows of them): A f32 [d, d], orthonormal, y = A x.  See
-    train_opq_device."""
+    train_opq_device.  d_out > d (faiss OPQMatrix(d, M, d_out)): A f32 [d_out, d] with orthonormal columns -- faiss' recipe: the sample
+    zero-padded to d_out, the square trainer at d_out, the first d columns of its matrix."""
     import torch  # pylint: disable=import-outside-toplevel
 
     x_f16 = np.asarray(x_f16)
     n, d = x_f16.shape
     take = min(n, int(sample_rows))
     sample = x_f16[np.sort(np.random.default_rng(seed + 2).choice(n, take, replace=False))] if take < n else x_f16
+    if d_out is not None and int(d_out) != d:
+        d_out = int(d_out)
+        _check_opq_dim(d, d_out)
+        xt = torch.from_numpy(_f16_padded(sample, d_out)).to(f"cuda:{device}")
+        A = train_opq_device(xt.data_ptr(), take, d_out, M, niter=niter, pq_niter=pq_niter, seed=seed, device=device)
+        # The comment below about arbitrary SVD blocks does not reach the columns kept here.  The padded rows are zero in columns
+        # d .., so G = X^T Y has zero ROWS d ..: G = [G1; 0] with G1 [d, d_out].  The Procrustes matrix A = (U V^T)^T then has
+        # A[:, :d] = the transposed polar factor of G1, which is unique as soon as G1 has rank d (a sample that spans its d columns);
+        # everything the SVD is free to choose -- the completion of that factor to a square matrix -- sits in columns d .. of A, which
+        # only ever multiply the zero pad and are dropped.  Orthonormal columns of a square orthonormal matrix stay orthonormal.
+        return np.ascontiguousarray(A[:, :d])
     dpad = (d + 255) // 256 * 256
     xt = torch.from_numpy(_f16_padded(sample, dpad)).to(f"cuda:{device}")
     if dpad == d:
@@ -1368,30 +1434,44 @@ def train_opq(x_f16, M, niter=8, pq_niter=4, seed=0, device=0, sample_rows=OPQ_S
     raise ValueError(f"train_opq needs d % 256 == 0 (got {d}): pass rotation= for other widths")
 
 
-def _resolve_rotation(x_sample, M, opq, rotation, seed, device):
-    """opq / rotation arguments of the builders -> (A f32 [d, d] or None, seconds spent training it)."""
+def _resolve_rotation(x_sample, M, opq, rotation, seed, device, opq_dim=None):
+    """opq / rotation / opq_dim arguments of the builders -> (A f32 [d, d] -- [opq_dim, d] with an opq_dim != d -- or None, seconds
+    spent training it).  A given rotation says its own d_out (its row count); an opq_dim next to it must agree."""
     import time  # pylint: disable=import-outside-toplevel
 
     if rotation is not None:
-        return np.ascontiguousarray(rotation, dtype=np.float32), 0.0
+        A = np.ascontiguousarray(rotation, dtype=np.float32)
+        if opq_dim is not None and A.shape[0] != int(opq_dim):
+            raise ValueError(f"rotation {A.shape} does not have opq_dim = {opq_dim} rows")
+        if A.ndim != 2 or (A.shape[0] != A.shape[1] and A.shape[1] % 256 != 0):
+            raise ValueError(f"a rotation with d_out != d needs d % 256 == 0, got {A.shape}")
+        return A, 0.0
     if not opq:
+        if opq_dim is not None:
+            raise ValueError("opq_dim needs opq=True or rotation=")
         return None, 0.0
     t = time.perf_counter()
-    A = train_opq(x_sample, M, seed=seed, device=device)
+    A = train_opq(x_sample, M, seed=seed, device=device, d_out=opq_dim)
     return A, time.perf_counter() - t
 
 
+def _rotation_out_dim(A, d):
+    """Width of the space behind the rotation: its row count when it is rectangular, else d."""
+    return int(A.shape[0]) if A is not None and A.shape[0] != A.shape[1] else int(d)
+
+
 def train_ivfpq(x_f16, nlist, M, niter=8, pq_niter=10, seed=0, device=0, sample_rows=PQ_SAMPLE_ROWS, centroids=None,
-                max_points_per_centroid=256, opq=False, rotation=None):
+                max_points_per_centroid=256, opq=False, rotation=None, opq_dim=None):
     """faiss IndexIVFPQ.train order: the coarse centroids first (the spherical k-means of train_ivf_centroids; `centroids=` skips it),
     then the M sub-quantisers on the residuals of a sample of <= sample_rows rows against their lists.  Returns (centroids fp16
     [nlist, d], codebooks f32 [M, 256, d_padded / M]).
     opq=True / rotation=A (f32 [d, d]): the order of faiss' IndexPreTransform.train -- the OPQ rotation first, on the raw rows
     (train_opq), then everything above on the ROTATED rows; returns (centroids, codebooks, A), both in the rotated space (`centroids=`
-    are then centroids of the rotated space)."""
+    are then centroids of the rotated space).  opq_dim=d_out (or a rotation [d_out, d]): the rotated space is d_out wide -- centroids
+    fp16 [nlist, d_out], codebooks f32 [M, 256, d_out / M]."""
     x_f16 = np.asarray(x_f16)
     n, d = x_f16.shape
-    A, _ = _resolve_rotation(x_f16, M, opq, rotation, seed, device)
+    A, _ = _resolve_rotation(x_f16, M, opq, rotation, seed, device, opq_dim)
     if A is not None:
         c, cb = train_ivfpq(rotate_rows(A, x_f16, device), nlist, M, niter=niter, pq_niter=pq_niter, seed=seed, device=device,
                             sample_rows=sample_rows, centroids=centroids, max_points_per_centroid=max_points_per_centroid)
@@ -1413,8 +1493,62 @@ def train_ivfpq(x_f16, nlist, M, niter=8, pq_niter=10, seed=0, device=0, sample_
     return centroids, cb
 
 
+def ivfpq_params_from_index_key(key, d):
+    """A faiss index-factory string of the family autofaiss builds -- `OPQ{M}_{d_out},IVF{nlist}[_HNSW32],PQ{M}x8[,RFlat]`, the OPQ
+    part optional -- for rows of width d -> the keyword arguments of build_ivfpq_index*: {"nlist", "M", "opq", "opq_dim", "refine"}
+    (opq_dim is None when d_out == d).  The _HNSW32 suffix is accepted and ignored: the coarse quantiser here is flat.  Whatever
+    cannot be served raises ValueError naming the part.  It parses; it does not choose an index."""
+    import re  # pylint: disable=import-outside-toplevel
+
+    d = int(d)
+    parts = [p.strip() for p in str(key).split(",")]
+    out = {"nlist": None, "M": None, "opq": False, "opq_dim": None, "refine": False}
+    opq_m = None
+    i = 0
+    m = re.fullmatch(r"OPQ(\d+)(?:_(\d+))?", parts[i]) if parts else None
+    if m:
+        opq_m, d_out = int(m.group(1)), int(m.group(2)) if m.group(2) else d
+        if d_out != d:
+            try:
+                _check_opq_dim(d, d_out)
+            except ValueError as e:
+                raise ValueError(f"index key part {parts[i]!r}: {e}") from None
+            out["opq_dim"] = d_out
+        out["opq"] = True
+        i += 1
+    m = re.fullmatch(r"IVF(\d+)(_HNSW\d+)?", parts[i]) if i < len(parts) else None
+    if not m or int(m.group(1)) < 1:
+        raise ValueError(f"index key part {parts[i] if i < len(parts) else ''!r}: expected IVF{{nlist}} or IVF{{nlist}}_HNSW32")
+    out["nlist"] = int(m.group(1))
+    i += 1
+    m = re.fullmatch(r"PQ(\d+)(?:x(\d+))?", parts[i]) if i < len(parts) else None
+    if not m:
+        raise ValueError(f"index key part {parts[i] if i < len(parts) else ''!r}: expected PQ{{M}}x8")
+    M, bits = int(m.group(1)), int(m.group(2)) if m.group(2) else 8
+    if bits != 8:
+        raise ValueError(f"index key part {parts[i]!r}: only 8-bit codes are served")
+    dq = out["opq_dim"] or (d + 255) // 256 * 256
+    ok = dq in (512, 768, 1024) if M == 256 else (M in (16, 32, 64, 128) and dq <= 1024 and dq % M == 0 and dq // M <= 64)
+    if not ok:
+        raise ValueError(f"index key part {parts[i]!r}: M = {M} does not fit a quantiser width of {dq} (M in 16, 32, 64, 128 dividing it, "
+                         f"or M = 256 at 512, 768, 1024)")
+    if opq_m is not None and opq_m != M:
+        raise ValueError(f"index key part {parts[0]!r}: the OPQ block count {opq_m} differs from the PQ's M = {M}")
+    out["M"] = M
+    i += 1
+    if i < len(parts) and parts[i] == "RFlat":
+        out["refine"] = True
+        i += 1
+    if i < len(parts):
+        raise ValueError(f"index key part {parts[i]!r}: not served (OPQ, IVF, PQ and RFlat parts only)")
+    return out
+
+
 def _ivfpq_begin(d, nlist, M, centroids, codebooks, sizes, device, id_base, rotation=None, refine=False, k_factor=1, threshold_scan=False):
     index = Mi355xIndex(d, device=device, id_base=id_base)
+    dq = _rotation_out_dim(rotation, d)
+    if dq != d:  # (a rectangular rotation says the quantiser width; every other index makes exactly the calls it always made)
+        index.set_pq_out_dim(dq)
     index.set_pq_quantizer(M, codebooks)
     if rotation is not None:
         index.set_pq_rotation(rotation)
@@ -1424,6 +1558,8 @@ def _ivfpq_begin(d, nlist, M, centroids, codebooks, sizes, device, id_base, rota
     if threshold_scan:  # (off is the state of a new index: nothing is called for it)
         index.pq_threshold_scan = True
     cpad = np.ascontiguousarray(index._pad(np.asarray(centroids, dtype=np.float16)))  # pylint: disable=protected-access
+    if dq != d and cpad.shape != (nlist, dq):
+        raise ValueError(f"centroids must be [{nlist}, {dq}] behind a rotation {rotation.shape}, got {cpad.shape}")
     check(index._lib, index._lib.knnx_ivf_begin(index._h, nlist, cpad.ctypes.data, np.ascontiguousarray(sizes, dtype=np.int64).ctypes.data), "knnx")  # pylint: disable=protected-access
     return index
 
@@ -1460,7 +1596,7 @@ def _assign_chunks(chunks, n, d, nlist, centroids, device, A):
     """List of every row (rotated by A first when there is one) -> (lists int32 [n], seconds spent rotating)."""
     import time  # pylint: disable=import-outside-toplevel
 
-    b = IvfBuilder(d, nlist, device)
+    b = IvfBuilder(_rotation_out_dim(A, d), nlist, device)
     b.set_centroids(centroids)
     lists = np.empty(n, dtype=np.int32)
     rotate_s = 0.0
@@ -1475,15 +1611,17 @@ def _assign_chunks(chunks, n, d, nlist, centroids, device, A):
 
 
 def build_ivfpq_index(x_f16, nlist, M, nprobe=16, niter=8, pq_niter=10, seed=0, device=0, id_base=0, centroids=None, codebooks=None,
-                      chunk=1 << 20, opq=False, rotation=None, refine=False, k_factor=1, threshold_scan=False):
+                      chunk=1 << 20, opq=False, rotation=None, refine=False, k_factor=1, threshold_scan=False, opq_dim=None):
     """fp16 rows [N, d] -> HBM-resident IVF-PQ index (ids = id_base + row number).  Trains (train_ivfpq) unless both `centroids` and
     `codebooks` are given; lists by the MFMA assignment kernel; codes by the device encoder.
     opq=True trains an OPQ rotation first (train_opq), rotation=A uses that one; centroids / codebooks, given or trained, are those of
     the rotated space.  The index keeps the rotation: it is searched with, and reconstructs, un-rotated vectors.
     refine=True keeps the fp16 rows next to the codes (Mi355xIndex.set_pq_refine) and re-scores k x k_factor candidates exactly.
-    threshold_scan=True switches on k > 64 and range_search (Mi355xIndex.pq_threshold_scan; off by default)."""
+    threshold_scan=True switches on k > 64 and range_search (Mi355xIndex.pq_threshold_scan; off by default).
+    opq_dim=d_out with opq=True, or a rotation [d_out, d]: the rotation leads into a WIDER space (faiss OPQ{M}_{d_out}; d and d_out
+    multiples of 256, d < d_out <= 1024) where centroids, codebooks and codes live; queries, reconstruct and the refine store stay d wide."""
     n, d = x_f16.shape
-    A, _ = _resolve_rotation(x_f16, M, opq, rotation, seed, device)
+    A, _ = _resolve_rotation(x_f16, M, opq, rotation, seed, device, opq_dim)
     if centroids is None or codebooks is None:
         centroids, codebooks = train_ivfpq(x_f16, nlist, M, niter=niter, pq_niter=pq_niter, seed=seed, device=device, centroids=centroids,
                                            rotation=A)[:2]
@@ -1497,19 +1635,21 @@ def build_ivfpq_index(x_f16, nlist, M, nprobe=16, niter=8, pq_niter=10, seed=0, 
 
 def build_ivfpq_index_from_folder(path, nlist, M, nprobe=16, niter=8, pq_niter=10, seed=0, device=0, centroids=None, codebooks=None,
                                   max_points_per_centroid=256, chunk=1 << 20, opq=False, rotation=None, refine=False, k_factor=1,
-                                  threshold_scan=False):
+                                  threshold_scan=False, opq_dim=None):
     """`clip inference` output folder (img_emb_*.npy) -> IVF-PQ index, streaming the partitions: training on a strided sample of the
     whole folder, then one assignment pass and one encoding pass.  The result can be save_index()ed (self-contained).  opq / rotation
     as in build_ivfpq_index (the rotation is trained on the same strided sample).  refine / k_factor as in build_ivfpq_index; a saved
     refine index is loaded from its folder PLUS these embeddings (save_index(index, folder, embeddings_folder=...)).  threshold_scan as
-    in build_ivfpq_index; save_index records it."""
+    in build_ivfpq_index; save_index records it.  opq_dim as in build_ivfpq_index."""
     src = path if isinstance(path, FolderRows) else FolderRows(path)
-    A = None if rotation is None else np.ascontiguousarray(rotation, dtype=np.float32)
+    A = None if rotation is None else _resolve_rotation(None, M, opq, rotation, seed, device, opq_dim)[0]
+    if opq_dim is not None and A is None and not opq:
+        raise ValueError("opq_dim needs opq=True or rotation=")
     if centroids is None or codebooks is None or (opq and A is None):
         take = min(src.n, max(int(nlist) * int(max_points_per_centroid), PQ_SAMPLE_ROWS))
         idx = np.unique(np.linspace(0, src.n - 1, take).astype(np.int64))
         sample = src.take(idx)
-        A, _ = _resolve_rotation(sample, M, opq, A, seed, device)
+        A, _ = _resolve_rotation(sample, M, opq, A, seed, device, opq_dim)
         if centroids is None or codebooks is None:
             centroids, codebooks = train_ivfpq(sample, nlist, M, niter=niter, pq_niter=pq_niter, seed=seed, device=device,
                                                centroids=centroids, max_points_per_centroid=max_points_per_centroid, rotation=A)[:2]
@@ -1524,7 +1664,7 @@ def build_ivfpq_index_from_folder(path, nlist, M, nprobe=16, niter=8, pq_niter=1
 
 def build_ivfpq_index_device(fill_rows, n, d, nlist, M, nprobe=16, niter=8, pq_niter=10, seed=0, device=0, id_base=0, centroids=None,
                              codebooks=None, chunk=1 << 20, alloc=None, points_per_centroid=64, pq_sample_rows=PQ_SAMPLE_ROWS, opq=False,
-                             rotation=None, opq_sample_rows=OPQ_SAMPLE_ROWS, refine=False, k_factor=1, threshold_scan=False):
+                             rotation=None, opq_sample_rows=OPQ_SAMPLE_ROWS, refine=False, k_factor=1, threshold_scan=False, opq_dim=None):
     """IVF-PQ index over n rows PRODUCED ON THE GPU (`fill_rows(dst_ptr, row0, count, stride)` as in build_ivf_index_device): the
     fp16 corpus never exists whole -- training samples, then per chunk one assignment pass and one encoding pass; the index keeps
     M bytes per row.  Returns (index, stats dict).
@@ -1533,7 +1673,9 @@ def build_ivfpq_index_device(fill_rows, n, d, nlist, M, nprobe=16, niter=8, pq_n
     un-rotated chunks (it rotates them itself).  stats["rotate_s"]: the rotations of the assignment pass (those of the encoding pass
     are part of encode_s), stats["opq_s"]: training the rotation (part of train_s).
     refine / k_factor as in build_ivfpq_index: the index stores each generated chunk as it encodes it (the chunk is handed over once
-    and never held a second time); stats["code_arena_bytes"] / stats["row_arena_bytes"]: what the index keeps in HBM."""
+    and never held a second time); stats["code_arena_bytes"] / stats["row_arena_bytes"]: what the index keeps in HBM.
+    opq_dim=d_out / a rotation [d_out, d]: as in build_ivfpq_index; a chunk is still held once per width -- the generated rows d wide,
+    their rotation d_out wide."""
     import time
 
     assert d % 256 == 0, "device builds take padded rows (d % 256 == 0)"
@@ -1545,25 +1687,37 @@ def build_ivfpq_index_device(fill_rows, n, d, nlist, M, nprobe=16, niter=8, pq_n
             t = torch.empty(int(nbytes), dtype=torch.uint8, device=f"cuda:{device}")
             return t.data_ptr(), t
     t0 = time.perf_counter()
-    A = None if rotation is None else _pad_rotation(rotation, d)
+    A = None if rotation is None else _resolve_rotation(None, M, opq, rotation, seed, device, opq_dim)[0]
+    if A is not None and A.shape[0] == A.shape[1]:
+        A = _pad_rotation(A, d)
+    if opq_dim is not None and A is None and not opq:
+        raise ValueError("opq_dim needs opq=True or rotation=")
     opq_s = rotate_s = 0.0
     if A is None and opq:
         n_os = int(min(n, opq_sample_rows))
         os_ptr, os_keep = alloc(n_os * d * 2)
         fill_rows(os_ptr, 0, n_os, max(1, n // n_os))
-        A = train_opq_device(os_ptr, n_os, d, M, seed=seed, device=device)
+        if opq_dim is not None and int(opq_dim) != d:  # faiss' recipe (train_opq): the sample zero-padded to d_out, the first d columns kept
+            _check_opq_dim(d, int(opq_dim))
+            pad_ptr, pad_keep = alloc(n_os * int(opq_dim) * 2)
+            rotate_rows_device(opq_embedding(d, int(opq_dim)), os_ptr, n_os, pad_ptr, device)
+            A = np.ascontiguousarray(train_opq_device(pad_ptr, n_os, int(opq_dim), M, seed=seed, device=device)[:, :d])
+            del pad_keep
+        else:
+            A = train_opq_device(os_ptr, n_os, d, M, seed=seed, device=device)
         del os_keep
         _release_cached_device_memory()
         opq_s = time.perf_counter() - t0
+    dq = _rotation_out_dim(A, d)  # the width behind the rotation: training samples, centroids, codebooks, the rotated chunk
 
     def rotated(ptr, count):  # -> (pointer to the rotated rows, their owner): a second buffer, or the rows themselves without a rotation
         if A is None:
             return ptr, None
-        rp, rk = alloc(count * d * 2)
+        rp, rk = alloc(count * dq * 2)
         rotate_rows_device(A, ptr, count, rp, device)
         return rp, rk
 
-    b = IvfBuilder(d, nlist, device)
+    b = IvfBuilder(dq, nlist, device)
     if centroids is None:
         n_sample = int(min(n, nlist * points_per_centroid))
         sample_ptr, sample_keep = alloc(n_sample * d * 2)
@@ -1581,7 +1735,7 @@ def build_ivfpq_index_device(fill_rows, n, d, nlist, M, nprobe=16, niter=8, pq_n
         fill_rows(ps_ptr, 0, n_ps, max(1, n // n_ps))
         ps_ptr, ps_rot_keep = rotated(ps_ptr, n_ps)
         b.assign_device(ps_ptr, n_ps, pl_ptr)
-        pb = PqBuilder(d, M, device)
+        pb = PqBuilder(dq, M, device)
         pb.set_sample_device(ps_ptr, pl_ptr, n_ps, centroids)
         codebooks = train_pq_codebooks(pb, niter=pq_niter, seed=seed)
         pb.close()
@@ -1590,7 +1744,7 @@ def build_ivfpq_index_device(fill_rows, n, d, nlist, M, nprobe=16, niter=8, pq_n
     t1 = time.perf_counter()
     lists_ptr, lists_keep = alloc(n * 4)
     rows_ptr, rows_keep = alloc(min(chunk, n) * d * 2)
-    rot_ptr, rot_keep = alloc(min(chunk, n) * d * 2) if A is not None else (rows_ptr, None)
+    rot_ptr, rot_keep = alloc(min(chunk, n) * dq * 2) if A is not None else (rows_ptr, None)
     b.list_sizes(reset=True)
     for o in range(0, n, chunk):
         m = min(chunk, n - o)
@@ -1622,7 +1776,8 @@ def build_ivfpq_index_device(fill_rows, n, d, nlist, M, nprobe=16, niter=8, pq_n
 def _save_ivfpq_index(index, folder, embeddings_folder=None):
     """The self-contained IVF-PQ folder: ivf_pq_centroids.npy (fp16 [nlist, d]), ivf_pq_codebooks.npy (f32 [M, 256, d_padded / M]),
     ivf_pq_codes.npy (u8 [n, M] in id order), ivf_pq_lists.npy (int32 [n]) and ivf_pq_manifest.json (written last); an index with an
-    OPQ rotation adds ivf_pq_rotation.npy (f32 [d, d]) and "opq": true in the manifest.  An index with a refine store adds "refine": true,
+    OPQ rotation adds ivf_pq_rotation.npy (f32 [d, d]) and "opq": true in the manifest; one whose quantiser space is wider than its
+    rows also "d_out" (only then), and its rotation file is f32 [d_out, d], its centroids [nlist, d_out].  An index with a refine store adds "refine": true,
     "k_factor" and the embeddings folder (as save_index does for IVF-Flat) to the manifest: the rows are not written a second time, the
     folder is loaded together with the embeddings.  An index with the threshold scan switched on adds "threshold_scan": true (only
     then: every other folder is what it always was)."""
@@ -1650,6 +1805,7 @@ def _save_ivfpq_index(index, folder, embeddings_folder=None):
     if rot is not None:  # (only then: a folder of an index without a rotation is what it always was)
         np.save(os.path.join(folder, IVFPQ_ROTATION), rot)
         man["opq"] = True
+    man.update(ivfpq_out_dim_entry(index.d, index.pq_out_dim))
     if src is not None:
         if src.n < hi or src.d != index.d:
             raise ValueError(f"{src.folder}: {src.n} rows of width {src.d} cannot hold rows [{lo}, {hi}) of width {index.d}")
@@ -1677,20 +1833,45 @@ def read_ivfpq_threshold_scan(folder, man):
     return v
 
 
+def ivfpq_out_dim_entry(d, d_out):
+    """What a saved IVF-PQ manifest says about the quantiser width: {"d_out": d_out} when it differs from d, nothing otherwise."""
+    return {"d_out": int(d_out)} if int(d_out) != int(d) else {}
+
+
+def read_ivfpq_out_dim(folder, man):
+    """The quantiser width of a saved IVF-PQ manifest: d for a manifest without "d_out" (every folder written before the key
+    existed, and every index whose two widths agree), else the integer it carries -- which must obey the width rule and come with
+    "opq": true, since only a rotation leads from d to d_out."""
+    d = int(man["d"])
+    if "d_out" not in man:
+        return d
+    v = man["d_out"]
+    if not isinstance(v, int) or isinstance(v, bool) or v % 256 != 0 or d % 256 != 0 or not 256 <= d < v <= 1024:
+        raise ValueError(f"{folder}: \"d_out\" must be a multiple of 256 with 256 <= d < d_out <= 1024 and d % 256 == 0, got d = {d}, "
+                         f"d_out = {v!r}")
+    if not man.get("opq", False):
+        raise ValueError(f"{folder}: the manifest carries \"d_out\": {v} but does not say \"opq\": true (the rotation is what leads there)")
+    return v
+
+
 def read_ivfpq_rotation(folder, man):
     """The rotation a saved IVF-PQ folder carries: None for a manifest without "opq" (every folder written before the rotation
-    existed), f32 [d, d] otherwise.  The flag and the file go together: either one without the other is refused."""
+    existed), f32 [d, d] otherwise.  The flag and the file go together: either one without the other is refused.  A manifest with
+    "d_out" carries f32 [d_out, d]; that shape is accepted only with the key, and the key only with that shape."""
     path = os.path.join(folder, IVFPQ_ROTATION)
     if not man.get("opq", False):
         if os.path.exists(path):
             raise ValueError(f"{folder}: {IVFPQ_ROTATION} is present but the manifest does not say \"opq\": true")
+        if "d_out" in man:
+            read_ivfpq_out_dim(folder, man)  # (raises: the key without the flag)
         return None
     if not os.path.isfile(path):
         raise ValueError(f"{folder}: the manifest says \"opq\": true but {IVFPQ_ROTATION} is missing")
     rot = np.load(path)
     d = int(man["d"])
-    if rot.shape != (d, d) or rot.dtype != np.float32:
-        raise ValueError(f"{folder}: {IVFPQ_ROTATION} must be float32 [{d}, {d}], got {rot.dtype} {rot.shape}")
+    dq = read_ivfpq_out_dim(folder, man)
+    if rot.shape != (dq, d) or rot.dtype != np.float32:
+        raise ValueError(f"{folder}: {IVFPQ_ROTATION} must be float32 [{dq}, {d}], got {rot.dtype} {rot.shape}")
     return rot
 
 
@@ -1741,6 +1922,8 @@ def _ivfpq_refine_from_rows(src, codes, lists, lo, cent, cb, M, nprobe, device, 
 
 def _ivfpq_from_codes(codes, lists, lo, cent, cb, M, nprobe, device, chunk=1 << 20, rotation=None):
     nlist, d = cent.shape
+    if rotation is not None:  # (behind a rectangular rotation the centroids are d_out wide; the index is as wide as the rotation's input)
+        d = rotation.shape[1]
     n = codes.shape[0]
     sizes = np.bincount(lists, minlength=nlist).astype(np.int64)
     index = _ivfpq_begin(d, nlist, M, cent, cb, sizes, device, lo, rotation)
@@ -1783,7 +1966,7 @@ def _load_ivfpq_index(folder, device=0, row_range=None, devices=None, embeddings
             ix.pq_threshold_scan = True
         return ix
 
-    if cent.shape != (man["nlist"], man["d"]) or codes.shape != (shi - slo, M) or lists.shape[0] != shi - slo:
+    if cent.shape != (man["nlist"], read_ivfpq_out_dim(folder, man)) or codes.shape != (shi - slo, M) or lists.shape[0] != shi - slo:
         raise ValueError(f"{folder}: the IVF-PQ files disagree with the manifest")
     if devices is not None:
         if row_range is not None:

@@ -175,7 +175,7 @@ int knnx_ivfpq_m(const knnx_index* ix); /* 0: not an IVF-PQ index */
 /* every row of a built index, in arena order (list by list): ids [ntotal], lists [ntotal], codes [ntotal][M] (host) */
 int knnx_ivfpq_get_codes(knnx_index* ix, int64_t* ids, int32_t* lists, uint8_t* codes);
 int knnx_ivfpq_get_codebooks(knnx_index* ix, float* codebooks);
-/* ---- OPQ rotation in front of IVF-PQ: faiss IndexPreTransform(OPQMatrix(d, M), IndexIVFPQ(...)), d_out = d_in = d ------------------
+/* ---- OPQ rotation in front of IVF-PQ: faiss IndexPreTransform(OPQMatrix(d, M), IndexIVFPQ(...)), d_out = d_in = d (d_out > d_in: below)
  * (what autofaiss puts in front of every IVF-PQ index it builds, and what ivf_metadata_ordering.py:23-24 applies to a query before it
  * asks the coarse quantiser).  A: f32 [d][d] row-major, y = A x, owned by the index.  Everything of the block above -- centroids, lists,
  * residuals, codebooks, codes, LUT, the ADC scan -- lives in the rotated space; an index without a rotation is exactly that block.
@@ -197,6 +197,30 @@ int knnx_ivfpq_get_codebooks(knnx_index* ix, float* codebooks);
  * all carry the same rotation (bit for bit) or none, and refuses a mix. */
 int knnx_ivfpq_set_rotation(knnx_index* ix, const float* A);
 int knnx_ivfpq_get_rotation(knnx_index* ix, float* A);
+/* ---- d_out > d_in: faiss IndexPreTransform(OPQMatrix(d_in, M, d_out), IndexIVFPQ(..., d_out, ...)) ("OPQ256_768,...,PQ256x8" on 512-d rows) --
+ * The index has two widths.  d (= d_in, knnx_dim) is what the user sees: queries, the rows entering the build, the refine store and its
+ * re-scoring, knnx_reconstruct, the R of search / search_dedup and the dedup vectors.  d_out is the quantiser space: centroids fp16
+ * [nlist][d_out], the coarse scan, residuals, codebooks f32 [M][256][d_out / M], LUT, codes, the decode scratch.  A: f32 [d_out][d]
+ * row-major with orthonormal COLUMNS (A^T A = I_d), y = A x; <A q, A x> = <q, x>, so the scores still estimate the inner product; the back
+ * transform is A^T y.  The arithmetic contracts of the OPQ block above (rows / queries / decoding) hold word for word with "columns"
+ * meaning the d columns of A: a row's component j sums the d columns of row j of A, a query's likewise, and decoding sums j over the
+ * d_out rows of A.  Supported: both widths multiples of 256, 256 <= d < d_out <= 1024.  An index nobody gave a d_out is exactly the
+ * blocks above and below, byte for byte.
+ * knnx_ivfpq_set_out_dim: on an empty index BEFORE knnx_ivfpq_set_quantizer; KNNX_E_STATE afterwards or on an index that has rows or
+ * lists; KNNX_E_ARG for a width outside the rule (the message names both widths); d_out == d is accepted and changes nothing.
+ * knnx_ivfpq_out_dim: d_out, or d when none was set; 0 on a null or non-PQ index.  With a d_out != d:
+ *   quantizer  knnx_ivfpq_set_quantizer applies its M rule to d_out and takes codebooks [M][256][d_out / M] (knnx_ivfpq_get_codebooks too).
+ *   rotation   knnx_ivfpq_set_rotation / knnx_ivfpq_get_rotation take and give [d_out][d]; refused (KNNX_E_ARG) unless
+ *              max |A^T A - I_d| <= 1e-3 in float64 (a square matrix keeps the A A^T test above).  The rotation is MANDATORY:
+ *              knnx_ivf_begin without one answers KNNX_E_STATE and says why.
+ *   build      knnx_ivf_begin takes centroids fp16 [nlist][d_out]; knnx_ivf_add_assigned[_device] take UN-ROTATED rows [n][d], the
+ *              list ids being those of the rotated rows as above; knnx_ivfpq_add_codes is unchanged.
+ *   refine     the row arena is tiles x 32 x d x 2 bytes (memory rule: M + 2 d_in bytes per padded row), which is what
+ *              knnx_ivfpq_arena_bytes reports; re-scoring uses the original d-wide query.
+ *   shards     knnx_shards_adopt takes shards with the same d_out and the same rotation bit for bit and refuses a mix (the message names
+ *              the widths); queries travel to the shards d wide. */
+int knnx_ivfpq_set_out_dim(knnx_index* ix, int d_out);
+int knnx_ivfpq_out_dim(const knnx_index* ix); /* d when no d_out was set; 0: null or not an IVF-PQ index */
 /* ---- Refine store on IVF-PQ: faiss IndexRefineFlat(IndexIVFPQ(...)) ("...,PQ64,RFlat"), with or without the OPQ rotation ------------
  * The index keeps, next to the codes, the fp16 rows exactly as they entered the build (original, UN-ROTATED space), in the
  * list-sorted, tile-padded arena order of the codes: tiles x 32 x d x 2 bytes more HBM (memory rule: M + 2 d bytes per padded row;
@@ -255,6 +279,9 @@ int knnx_ivfpq_threshold_stats(knnx_index* ix, int64_t* queries, int64_t* launch
  * fmaf chain over the rows in ascending order -- the product whose SVD is the Procrustes step of OPQ training.  `stream`: hipStream_t
  * or NULL; both synchronous. */
 int knnx_rotate_f16_device(int device, const float* A_host, const void* rows_dev_f16, int64_t n, int d, void* out_dev_f16, void* stream);
+/* The same for A_host f32 [d_out][d_in], d_in <= d_out, both in {256, 512, 768, 1024}: rows_dev fp16 [n][d_in], out_dev fp16 [n][d_out]. */
+int knnx_rotate_rect_f16_device(int device, const float* A_host, const void* rows_dev_f16, int64_t n, int d_in, int d_out,
+                                void* out_dev_f16, void* stream);
 int knnx_xty_device(int device, const void* x_dev_f16, const float* y_dev_f32, int64_t n, int d, float* g_dev, void* stream);
 /* Codebook training on the device (faiss trains the M sub-quantisers on the residuals of a sample; default 256 x 256 rows):
  * the builder keeps the sample rows (fp16 [n][d]) with their list ids and the coarse centroids resident.  knnx_pqb_lloyd = one

@@ -11,6 +11,10 @@ at a size where both fit).  Prints ONE JSON line.
                                                                 # also prints the partial-sum slab and the sub-groups of a 256-query pass
   python tools/ivfpq_bench.py --opq                             # + the same index behind an OPQ rotation: rotate_s, recall, times
   python tools/ivfpq_bench.py --opq --kind 2                    # ... on the dominant-column corpus (knnx_synth_rows_device kind 2)
+  python tools/ivfpq_bench.py --rows 4000000 --d 512 --nlist 4096 --M 256 --opq --opq-dim 768
+                                                                # OPQ256_768 on 512-d rows: ONLY the rectangular index (rotation [768, 512]) and
+                                                                # its yardstick, the square d = 768 index over the same rows zero-padded, both
+                                                                # with a refine store, built and timed alternately in this process
   python tools/ivfpq_bench.py --rows 16000000 --nlist 16384 --nprobes 64 --refine [--k-factor 1,4,8]
                                                                 # + the same index with a refine store and IVF-Flat on the same rows, all three
                                                                 # resident, timed alternately; recall@40 of each
@@ -43,6 +47,9 @@ def main():
     ap.add_argument("--recall-queries", type=int, default=64)
     ap.add_argument("--flat-ab", action="store_true")
     ap.add_argument("--opq", action="store_true", help="also build the index behind a trained OPQ rotation and compare: same corpus, queries, process")
+    ap.add_argument("--opq-dim", type=int, default=0, help="with --opq: d_out > d.  Builds the index behind a trained rotation [d_out, d] and the "
+                    "square d_out index over the zero-padded rows (both with a refine store), reports rotate_s, build seconds, arena bytes "
+                    "and B x nprobe 64 timed alternately, and nothing else")
     ap.add_argument("--refine", action="store_true", help="also build the index with a refine store (same centroids and codebooks) and IVF-Flat "
                     "on the same rows; all three stay resident and are timed alternately at nprobe 64, k = 40")
     ap.add_argument("--k-factor", default="1,4,8", help="k_factor values of --refine")
@@ -63,6 +70,12 @@ def main():
             return
         # kind 2 is generated with stride 1 only; its rows are i.i.d., so a contiguous block is as good a sample as a strided one
         synth_rows_device(dst, row0, count, d, a.seed, kind=2)
+
+    if a.opq_dim:
+        if not a.opq:
+            ap.error("--opq-dim needs --opq")
+        print(json.dumps(rect_ab(a, fill_rows)))
+        return
 
     free0 = torch.cuda.mem_get_info()[0]
     index, st = build_ivfpq_index_device(fill_rows, n, d, a.nlist, a.M, nprobe=16, niter=6, pq_niter=8, seed=0)
@@ -246,6 +259,73 @@ def main():
     else:
         index.close()
     print(json.dumps(out))
+
+
+def rect_ab(a, fill_rows):
+    """--opq --opq-dim N: the index with two widths (rows d, quantiser d_out = N) against the route it replaces -- every row and query
+    zero-padded to N in front of a square N rotation.  Same rows, same seeds (the two rotations are trained by the same recipe on the
+    same padded sample), both with a refine store; searches alternate between the two, three rounds, the median of the rounds' medians."""
+    import torch
+
+    from clip_retrieval_amd.knn import build_ivfpq_index_device, opq_embedding, rotate_rows_device, synth_rows_device
+
+    n, d, dq, k = a.rows, a.d, a.opq_dim, 40
+    E = opq_embedding(d, dq)
+
+    def fill_padded(dst, row0, count, stride):  # the same rows, N wide: generated d wide, then scattered into zeros (exact)
+        tmp = torch.empty((count, d), dtype=torch.float16, device="cuda")
+        fill_rows(tmp.data_ptr(), row0, count, stride)
+        torch.cuda.synchronize()
+        rotate_rows_device(E, tmp.data_ptr(), count, dst, 0)
+
+    out = {"rows": n, "d": d, "d_out": dq, "nlist": a.nlist, "M": a.M}
+    built = {}
+    for name, fill, width, kw in (("rect", fill_rows, d, {"opq_dim": dq}), ("padded_square", fill_padded, dq, {})):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ix, st = build_ivfpq_index_device(fill, n, width, a.nlist, a.M, nprobe=64, niter=6, pq_niter=8, seed=0, opq=True, refine=True, **kw)
+        torch.cuda.synchronize()
+        built[name] = ix
+        out[name] = {"build_s": round(time.perf_counter() - t0, 2), "opq_s": round(st["opq_s"], 2), "train_s": round(st["train_s"], 2),
+                     "assign_s": round(st["assign_s"], 2), "rotate_s": round(st["rotate_s"], 3), "encode_s": round(st["encode_s"], 2),
+                     "code_arena_bytes": st["code_arena_bytes"], "row_arena_bytes": st["row_arena_bytes"]}
+    qrows = torch.empty((256, d), dtype=torch.float16, device="cuda")
+    synth_rows_device(qrows.data_ptr(), n + 12345, 256, d, a.seed, kind=a.kind, n_clusters=a.clusters if a.kind == 1 else 0)
+    q = qrows.float().cpu().numpy()
+    q += 0.05 * np.random.default_rng(1).standard_normal(q.shape).astype(np.float32) / np.sqrt(d)
+    q /= np.linalg.norm(q, axis=1, keepdims=True)
+    qs = {"rect": torch.from_numpy(np.ascontiguousarray(q, dtype=np.float32)).cuda(),
+          "padded_square": torch.from_numpy(np.ascontiguousarray(np.pad(q, ((0, 0), (0, dq - d))), dtype=np.float32)).cuda()}
+    Dd = torch.empty((256, 64), dtype=torch.float32, device="cuda")
+    Id = torch.empty((256, 64), dtype=torch.int64, device="cuda")
+
+    def timed(name, B):
+        ix, qd = built[name], qs[name]
+        ix.search_device(qd.data_ptr(), B, k, Dd.data_ptr(), Id.data_ptr())
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            ix.search_device(qd.data_ptr(), B, k, Dd.data_ptr(), Id.data_ptr())
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+        return float(np.median(ts))
+
+    ids = {}
+    for name, ix in built.items():
+        ix.nprobe = 64
+        ids[name] = ix.search(qs[name].cpu().numpy(), k)[1]
+    out["same_ids_share"] = round(float((ids["rect"] == ids["padded_square"]).mean()), 4)
+    for B in [int(v) for v in a.batches.split(",")]:
+        ts = {name: [] for name in built}
+        for _ in range(3):
+            for name in built:
+                ts[name].append(timed(name, B))
+        for name, v in ts.items():
+            out[name][f"B{B}_np64_ms"] = round(float(np.median(v)) * 1e3, 4)
+    for ix in built.values():
+        ix.close()
+    return out
 
 
 if __name__ == "__main__":

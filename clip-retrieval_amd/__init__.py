@@ -8,3 +8,16 @@ Nothing here computes on the CPU: every product entry point goes through `lib/li
 __version__ = "0.1.0"
 
 from ._lib import HipLibraryError, ResidualStreamOverflow, load_library, library_path  # noqa: F401
+
+# the list-ordered ids of an IVF index under the reference's names (ivf_metadata_ordering.py, clip_back.py:629-640), resolved on first
+# use so that importing the package stays as light as it was
+_LAZY = {"get_old_to_new_mapping": "knn", "search_to_new_ids": "knn", "load_ivf_old_to_new_mapping": "service",
+         "reorder_arrow_metadata": "service"}
+
+
+def __getattr__(name):
+    if name in _LAZY:
+        import importlib  # pylint: disable=import-outside-toplevel
+
+        return getattr(importlib.import_module("clip_retrieval_amd." + _LAZY[name]), name)
+    raise AttributeError(f"module 'clip_retrieval_amd' has no attribute {name!r}")

@@ -62,6 +62,8 @@ SIGNATURES = {
     "knnx_ivf_nprobe": (C.c_int, [_P]),
     "knnx_ivf_last_scan_tiles": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "knnx_ivf_last_scan_union_tiles": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "knnx_ivf_id_order": (C.c_int, [_P, _P, _P]),
+    "knnx_ivf_map_ids": (C.c_int, [_P, _P, C.c_int64, _P]),
     "knnx_ivfb_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "knnx_ivfb_destroy": (None, [_P]),
     "knnx_ivfb_set_centroids": (C.c_int, [_P, _P]),
@@ -126,6 +128,8 @@ SIGNATURES = {
     "knnx_shards_search": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
     "knnx_shards_reconstruct": (C.c_int, [_P, _P, C.c_int64, _P]),
     "knnx_shards_range_search": (C.c_int, [_P, _P, C.c_int, C.c_float, _P, _P, _P]),
+    "knnx_shards_id_order": (C.c_int, [_P, _P, _P]),
+    "knnx_shards_map_ids": (C.c_int, [_P, _P, C.c_int64, _P]),
     "knnx_set_coalesce": (C.c_int, [_P, C.c_int]),
     "knnx_coalesce_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "knnx_i8_served": (C.c_int64, [_P]),

@@ -102,6 +102,13 @@ size_t synth_mix_table_bytes(int d);
 hipError_t launch_copy_rows(const _Float16* src, int d, const int64_t* src_rows, const int32_t* dst_rows, int64_t n, _Float16* dst,
                             hipStream_t st);
 hipError_t launch_ivf_hist(const int32_t* lists, int64_t n, int nlist, unsigned long long* hist, hipStream_t st);
+// list-ordered ids (knn_idorder_kernels.hip; dense0 [nlist + 1] = exclusive prefix sum of the list sizes, knnx_id_order.h):
+// out[t] = idmap[arena row of ordinal o0 + t], t < n -- a slice of new_to_old (prow: rows of the padded arena)
+hipError_t launch_ivf_new_to_old(const int64_t* idmap, int64_t prow, const unsigned* tile0, const int64_t* dense0, int nlist, int64_t o0,
+                                 int64_t n, int64_t* out, hipStream_t st);
+// out[t] = id_base + ordinal of the row with id ids[t] (-1 -> -1; out may be ids); ids == null: the ids id_base + i0 + t, a slice of old_to_new
+hipError_t launch_ivf_map_ids(const uint32_t* inv, int64_t id_base, int64_t ntotal, const unsigned* tile0, const int64_t* dense0, int nlist,
+                              const int64_t* ids_or_null, int64_t i0, int64_t n, int64_t* out, hipStream_t st);
 
 // ---- register-stationary-queries (RQ) scan, knn_rq_kernels.hip: up to rq_queries_per_pass(d) queries per pass over HBM
 constexpr int KNN_RQ_MAX = 256;        // queries of one RQ pass at d <= 768 (128 at d = 1024)

@@ -102,6 +102,10 @@ extern "C" void knnx_destroy(knnx_index* ix) {
   if (!ix) return;
   hipSetDevice(ix->device);
   if (ix->stream) hipStreamSynchronize(ix->stream);
+  {  // a translation of ids still running on its own stream (knnx_ivf_map_ids) finishes first
+    std::lock_guard<std::mutex> lk(ix->ido.mu);
+    if (ix->ido.stream) hipStreamSynchronize(ix->ido.stream);
+  }
   if (ix->cent) knnx_destroy(ix->cent);
   hipSetDevice(ix->device);
   delete ix;

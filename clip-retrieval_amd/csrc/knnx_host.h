@@ -463,6 +463,21 @@ struct PqScratch {
   }
 };
 
+// list-ordered ids (knnx_ivf.hip: knnx_ivf_id_order / knnx_ivf_map_ids; include/knnx.h "List-ordered ids").  Empty until the first call.
+// The layout it reads (ivf.tile0 / size / idmap / inv) does not change once the index is built, so this group has a mutex and a stream
+// of its own: a translation on the request path never queues behind the scans that hold knnx_index::mu.
+struct IdOrder {
+  Stream stream;                  // (first: destroyed after the buffers below)
+  std::mutex mu;
+  bool ready = false;             // dense0 is built
+  std::vector<int64_t> dense0_h;  // [nlist + 1] exclusive prefix sum of the list sizes
+  DevBuf<int64_t> dense0;         // the same on the device
+  // staging of knnx_ivf_map_ids, grown on demand up to one chunk (KNNX_ID_ORDER_CHUNK): a request's ids go in, their answers come back
+  PinBuf pin;
+  DevBuf<int64_t> dev;
+  int64_t cap = 0;                // ids pin / dev hold
+};
+
 // hit pools of the range scans, grown on demand (knnx_range.hip: range_pool_alloc)
 struct RangePools {
   DevBuf<float> s;
@@ -559,6 +574,7 @@ struct knnx_index {
   IvfBuild ivfb;
   PqData pq;
   PqScratch pqs;
+  IdOrder ido;
 
   // a proof-based scan that skipped its fallback (see WideScratch) says so here: 1 = rq.need / rq.gate, 2 = wide.need / wide.gate
   bool defer_fb = false;

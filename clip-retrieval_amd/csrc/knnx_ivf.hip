@@ -1,7 +1,9 @@
 // knnx_ivf.hip -- IVF-Flat on the host side: the list layout, the single- and the multi-block scan, the device build
-// (knnx_ivfb_*) and the streaming build knnx_ivf_begin / add_assigned / end (see knnx_host.h).
+// (knnx_ivfb_*), the streaming build knnx_ivf_begin / add_assigned / end (see knnx_host.h) and the list-ordered ids of a built
+// index (knnx_ivf_id_order / knnx_ivf_map_ids).
 
 #include "knnx_host.h"
+#include "knnx_id_order.h"
 
 // IVF: the work list (ix->ivf1.work / ivf_nwork) of <= KNN_NQ queries already in HBM
 int ivf_build_worklist(knnx_index* ix, const float* q_dev, int nq, hipStream_t st, const unsigned* gate) {
@@ -738,4 +740,116 @@ extern "C" int knnx_ivf_last_scan_union_tiles(knnx_index* ix, int64_t* tiles) {
     }
   }
   return knnx_ivf_last_scan_tiles(ix, tiles);
+}
+
+// ---------------------------------------------------------------------------------------------
+// List-ordered ids (include/knnx.h; the reference's reorder_metadata_by_ivf_index: ivf_metadata_ordering.py:46-64 builds the mapping
+// with a Python loop over the lists and keeps ntotal x 8 bytes of it on the host, clip_back.py:350-369 applies it with np.take).
+// Here the mapping is a function of the layout the index owns: ordinal = dense0[list] + position.  Neither entry point takes
+// knnx_index::mu -- the layout is immutable once the index is built -- so a translation never waits for a scan; they serialise among
+// themselves on IdOrder::mu and run on IdOrder::stream.  What they read without the lock (ivf_nlist, ivfb.nlist, ntotal, id_base) is
+// settled by knnx_ivf_end / knnx_ivf_set_lists.
+// ---------------------------------------------------------------------------------------------
+static int ido_refuse(const knnx_index* ix, const char* who) {
+  if (ix->ivfb.nlist)
+    return fail(KNNX_E_STATE, std::string(who) + ": the index is between knnx_ivf_begin and knnx_ivf_end: its lists are not complete (call knnx_ivf_end first)");
+  if (!ix->ivf_nlist) return fail(KNNX_E_STATE, std::string(who) + ": a flat index has no inverted lists to order its ids by");
+  if (ix->ntotal <= 0) return fail(KNNX_E_STATE, std::string(who) + ": the index is empty");
+  return 0;
+}
+
+// dense0 on the host and the device, the stream; caller holds ido.mu and has set the device.  Once per index.
+static int ido_prepare(knnx_index* ix) {
+  IdOrder& S = ix->ido;
+  if (S.ready) return 0;
+  if (!S.stream) HIPCHK(S.stream.create());
+  const int nlist = ix->ivf_nlist;
+  HIPCHK(hipStreamSynchronize(ix->stream));  // (this once: whatever laid the layout down has finished)
+  std::vector<unsigned> size((size_t)nlist);
+  HIPCHK(hipMemcpyAsync(size.data(), ix->ivf.size, (size_t)nlist * sizeof(unsigned), hipMemcpyDeviceToHost, S.stream));
+  HIPCHK(hipStreamSynchronize(S.stream));
+  ido_dense0(size.data(), nlist, S.dense0_h);
+  if (S.dense0_h[(size_t)nlist] != ix->ntotal) return fail(KNNX_E_STATE, "internal: the list sizes do not add up to ntotal");
+  HIPCHK(S.dense0.alloc((size_t)nlist + 1));
+  hipError_t e = hipMemcpyAsync(S.dense0, S.dense0_h.data(), ((size_t)nlist + 1) * sizeof(int64_t), hipMemcpyHostToDevice, S.stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(S.stream);
+  if (e != hipSuccess) {
+    S.dense0.reset();
+    return fail(KNNX_E_HIP, std::string("id order: ") + hipGetErrorString(e));
+  }
+  S.ready = true;
+  return 0;
+}
+
+extern "C" int knnx_ivf_id_order(knnx_index* ix, int64_t* old_to_new, int64_t* new_to_old) {
+  if (!ix) return fail(KNNX_E_ARG, "index is null");
+  if (!old_to_new && !new_to_old) return fail(KNNX_E_ARG, "knnx_ivf_id_order: old_to_new and new_to_old are both null");
+  int r = ido_refuse(ix, "knnx_ivf_id_order");
+  if (r) return r;
+  IdOrder& S = ix->ido;
+  std::lock_guard<std::mutex> lk(S.mu);
+  if (set_dev(ix)) return KNNX_E_HIP;
+  if ((r = ido_prepare(ix))) return r;
+  // consecutive ranges of ordinals (new_to_old) / ids (old_to_new) through ONE staging buffer of a chunk: nothing here is proportional
+  // to ntotal on the device.  old_to_new comes from inv by the kernel of knnx_ivf_map_ids (thread per id), so both arrays leave the
+  // device as contiguous slices and the host only copies.
+  const IdoChunks plan(ix->ntotal, ido_chunk_from_env(getenv("KNNX_ID_ORDER_CHUNK")));
+  DevBuf<int64_t> stage;
+  PinBuf pin;
+  HIPCHK(stage.alloc((size_t)plan.staging()));
+  HIPCHK(pin.ensure((size_t)plan.staging() * sizeof(int64_t)));
+  for (int64_t c = 0; c < plan.count(); ++c) {
+    const int64_t o0 = plan.first(c), m = plan.len(c);
+    if (new_to_old) {
+      HIPCHK(launch_ivf_new_to_old(ix->ivf.idmap, ix->capacity, ix->ivf.tile0, S.dense0, ix->ivf_nlist, o0, m, stage, S.stream));
+      HIPCHK(hipMemcpyAsync(pin.p, stage, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, S.stream));
+      HIPCHK(hipStreamSynchronize(S.stream));
+      memcpy(new_to_old + o0, pin.p, (size_t)m * sizeof(int64_t));
+    }
+    if (old_to_new) {
+      HIPCHK(launch_ivf_map_ids(ix->ivf.inv, ix->id_base, ix->ntotal, ix->ivf.tile0, S.dense0, ix->ivf_nlist, nullptr, o0, m, stage, S.stream));
+      HIPCHK(hipMemcpyAsync(pin.p, stage, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, S.stream));
+      HIPCHK(hipStreamSynchronize(S.stream));
+      memcpy(old_to_new + o0, pin.p, (size_t)m * sizeof(int64_t));
+    }
+  }
+  return KNNX_OK;
+}
+
+extern "C" int knnx_ivf_map_ids(knnx_index* ix, const int64_t* ids, int64_t n, int64_t* out) {
+  if (!ix) return fail(KNNX_E_ARG, "index is null");
+  if (n < 0 || (n > 0 && (!ids || !out))) return fail(KNNX_E_ARG, "bad ivf_map_ids arguments");
+  int r = ido_refuse(ix, "knnx_ivf_map_ids");
+  if (r) return r;
+  if (n == 0) return KNNX_OK;
+  // the whole request is checked on the host before anything is launched: a refusal leaves `out` as it was
+  const int64_t bad = ido_first_bad(ids, n, ix->id_base, ix->ntotal);
+  if (bad >= 0)
+    return fail(KNNX_E_ARG, "knnx_ivf_map_ids: id " + std::to_string(ids[bad]) + " at position " + std::to_string(bad) +
+                                " is neither -1 nor in [" + std::to_string(ix->id_base) + ", " + std::to_string(ix->id_base + ix->ntotal) + ")");
+  IdOrder& S = ix->ido;
+  std::lock_guard<std::mutex> lk(S.mu);
+  if (set_dev(ix)) return KNNX_E_HIP;
+  if ((r = ido_prepare(ix))) return r;
+  const int64_t chunk = ido_chunk_from_env(getenv("KNNX_ID_ORDER_CHUNK"));
+  if (S.cap < std::min(n, chunk)) {  // grow the staging: a power of two >= 1024 ids, one chunk at the most
+    int64_t want = 1024;
+    while (want < std::min(n, chunk)) want *= 2;
+    want = std::min(want, chunk);
+    S.cap = 0;
+    HIPCHK(S.pin.ensure((size_t)want * sizeof(int64_t)));
+    HIPCHK(S.dev.alloc((size_t)want));
+    S.cap = want;
+  }
+  const int64_t step = std::min(S.cap, chunk);
+  for (int64_t o = 0; o < n; o += step) {
+    const int64_t m = std::min(step, n - o);
+    memcpy(S.pin.p, ids + o, (size_t)m * sizeof(int64_t));
+    HIPCHK(hipMemcpyAsync(S.dev, S.pin.p, (size_t)m * sizeof(int64_t), hipMemcpyHostToDevice, S.stream));
+    HIPCHK(launch_ivf_map_ids(ix->ivf.inv, ix->id_base, ix->ntotal, ix->ivf.tile0, S.dense0, ix->ivf_nlist, S.dev, 0, m, S.dev, S.stream));
+    HIPCHK(hipMemcpyAsync(S.pin.p, S.dev, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, S.stream));
+    HIPCHK(hipStreamSynchronize(S.stream));
+    memcpy(out + o, S.pin.p, (size_t)m * sizeof(int64_t));
+  }
+  return KNNX_OK;
 }

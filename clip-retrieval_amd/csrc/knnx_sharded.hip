@@ -20,12 +20,15 @@
 //     which is why it is opt-in, and why an exchange that returns an error hands the batch (and the index, from then on) to the peer
 //     copies instead of failing the search.
 //   * reconstruct: ids are routed to the owning shard by row range.
+//   * list-ordered ids (knnx_shards_id_order / knnx_shards_map_ids): the concatenation of the shards' own mappings; ids are routed by
+//     row range, every shard translates its own (knnx_ivf_map_ids: its own mutex and stream, not the handle's lock).
 // Built on the public entry points of include/knnx.h only.  No CPU arithmetic: the host routes ids and pointers.
 
 #include <dlfcn.h>
 #include <stdlib.h>
 
 #include "knnx_host.h"  // the error helpers and the owning types only: the index is used through include/knnx.h
+#include "knnx_id_order.h"
 
 namespace {
 
@@ -493,5 +496,60 @@ extern "C" int knnx_shards_range_search(knnx_shards* s, const float* q, int n, f
       fill[i] += c;
     }
   }
+  return KNNX_OK;
+}
+
+// ---- list-ordered ids over the shards (include/knnx.h, "List-ordered ids"): shard g owns the ids [lo_g, lo_g + ntotal_g) with id_base =
+// lo_g, so its old_to_new values are global new ids already and the global arrays are the shards' arrays one after the other.  Neither
+// call takes s->mu: the shards' layouts do not change once they are built, and every shard serialises its own translations.
+static int shards_ido_refuse(knnx_shards* s, const char* who) {
+  for (size_t g = 0; g < s->sh.size(); ++g)
+    if (knnx_ivf_nlist(s->sh[g].ix) <= 0)
+      return fail(KNNX_E_STATE, std::string(who) + ": shard " + std::to_string(g) + " is not a built IVF index: it has no inverted lists to order its ids by");
+  return 0;
+}
+
+extern "C" int knnx_shards_id_order(knnx_shards* s, int64_t* old_to_new, int64_t* new_to_old) {
+  if (!s) return fail(KNNX_E_ARG, "shards handle is null");
+  if (!old_to_new && !new_to_old) return fail(KNNX_E_ARG, "knnx_shards_id_order: old_to_new and new_to_old are both null");
+  int r = shards_ido_refuse(s, "knnx_shards_id_order");
+  if (r) return r;
+  int64_t off = 0;
+  for (auto& h : s->sh) {
+    if (knnx_ntotal(h.ix) == 0) continue;  // (a shard without rows adds nothing to the concatenation)
+    r = knnx_ivf_id_order(h.ix, old_to_new ? old_to_new + off : nullptr, new_to_old ? new_to_old + off : nullptr);
+    if (r) return r;
+    off += knnx_ntotal(h.ix);
+  }
+  return KNNX_OK;
+}
+
+extern "C" int knnx_shards_map_ids(knnx_shards* s, const int64_t* ids, int64_t n, int64_t* out) {
+  if (!s) return fail(KNNX_E_ARG, "shards handle is null");
+  if (n < 0 || (n > 0 && (!ids || !out))) return fail(KNNX_E_ARG, "bad shards_map_ids arguments");
+  int r = shards_ido_refuse(s, "knnx_shards_map_ids");
+  if (r) return r;
+  if (n == 0) return KNNX_OK;
+  const int P = (int)s->sh.size();
+  std::vector<int64_t> lo((size_t)P), hi((size_t)P);
+  for (int g = 0; g < P; ++g) lo[(size_t)g] = s->sh[g].lo, hi[(size_t)g] = s->sh[g].lo + knnx_ntotal(s->sh[g].ix);
+  IdoRoute route;
+  const int64_t bad = ido_route(ids, n, lo.data(), hi.data(), P, route);
+  if (bad >= 0)
+    return fail(KNNX_E_ARG, "knnx_shards_map_ids: id " + std::to_string(ids[bad]) + " at position " + std::to_string(bad) +
+                                " is neither -1 nor in the row range of a shard");
+  // every shard answers into its own buffer first: a shard that fails leaves `out` as it was
+  std::vector<std::vector<int64_t>> mapped((size_t)P);
+  for (int g = 0; g < P; ++g) {
+    const std::vector<int64_t>& sub = route.ids[(size_t)g];
+    if (sub.empty()) continue;
+    mapped[(size_t)g].resize(sub.size());
+    r = knnx_ivf_map_ids(s->sh[g].ix, sub.data(), (int64_t)sub.size(), mapped[(size_t)g].data());
+    if (r) return r;
+  }
+  for (int64_t i = 0; i < n; ++i)
+    if (ids[i] == -1) out[i] = -1;  // (out may be ids: -1 stays -1, and every other position is overwritten below)
+  for (int g = 0; g < P; ++g)
+    if (!mapped[(size_t)g].empty()) ido_scatter_back(route, g, mapped[(size_t)g].data(), out);
   return KNNX_OK;
 }

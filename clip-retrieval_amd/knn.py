@@ -37,6 +37,14 @@ def _as_queries(x, d):
     return np.ascontiguousarray(x)
 
 
+def _map_ids_call(lib, fn, handle, ids):
+    """ids of any shape (int64) through knnx_ivf_map_ids / knnx_shards_map_ids -> a new int64 array of the same shape."""
+    ids = np.ascontiguousarray(ids, dtype=np.int64)
+    out = np.empty_like(ids)
+    check(lib, fn(handle, ids.ctypes.data, ids.size, out.ctypes.data), "knnx")
+    return out
+
+
 class _FaissShaped:
     """The part of the faiss Index surface clip_back / clip_filter exercise, on top of `_search_raw`,
     `reconstruct_batch`, `range_search` and `ntotal` of the concrete index (one GPU or row-sharded)."""
@@ -335,6 +343,26 @@ class Mi355xIndex(_FaissShaped):
         order = np.argsort(ids, kind="stable")
         return np.ascontiguousarray(codes[order]), np.ascontiguousarray(lists[order])
 
+    # ------------------------------------------------------------------ list-ordered ids (reorder_metadata_by_ivf_index)
+    def ivf_old_to_new(self):
+        """int64 [ntotal]: old_to_new[i] = id_base + the list-ordered ordinal of the row with id id_base + i (include/knnx.h,
+        "List-ordered ids"); with id_base = 0 the array of the reference's get_old_to_new_mapping (ivf_metadata_ordering.py:46-64)."""
+        out = np.empty(self.ntotal, dtype=np.int64)
+        check(self._lib, self._lib.knnx_ivf_id_order(self._h, out.ctypes.data, None), "knnx")
+        return out
+
+    def ivf_new_to_old(self):
+        """int64 [ntotal]: the ids of the lists one after the other, list 0 first -- row o of a list-ordered metadata store is the
+        source row new_to_old[o] - id_base."""
+        out = np.empty(self.ntotal, dtype=np.int64)
+        check(self._lib, self._lib.knnx_ivf_id_order(self._h, None, out.ctypes.data), "knnx")
+        return out
+
+    def map_ids(self, ids):
+        """Result ids (any shape, int64) -> their list-ordered ids, -1 kept: np.take(ivf_old_to_new(), ids - id_base) without the
+        table, by a gather kernel over the layout the index holds.  Safe to call from request threads while others search."""
+        return _map_ids_call(self._lib, self._lib.knnx_ivf_map_ids, self._h, ids)
+
     # ------------------------------------------------------------------ searching
     def _search_raw(self, q, k, want_r):
         n = q.shape[0]
@@ -597,6 +625,23 @@ class ShardedMi355xIndex(_FaissShaped):
                                                                 D.ctypes.data, I.ctypes.data), "knnx")
         return lims, D, I
 
+    def ivf_old_to_new(self):
+        """int64 [ntotal]: the concatenation of the shards' old_to_new arrays (each list-sorted inside its own row range): a
+        permutation of [0, ntotal) (Mi355xIndex.ivf_old_to_new)."""
+        out = np.empty(self.ntotal, dtype=np.int64)
+        check(self._lib, self._lib.knnx_shards_id_order(self._h, out.ctypes.data, None), "knnx")
+        return out
+
+    def ivf_new_to_old(self):
+        """int64 [ntotal]: the concatenation of the shards' new_to_old arrays (Mi355xIndex.ivf_new_to_old)."""
+        out = np.empty(self.ntotal, dtype=np.int64)
+        check(self._lib, self._lib.knnx_shards_id_order(self._h, None, out.ctypes.data), "knnx")
+        return out
+
+    def map_ids(self, ids):
+        """Result ids (any shape, int64) -> their list-ordered ids, -1 kept; every id is translated by the shard that owns it."""
+        return _map_ids_call(self._lib, self._lib.knnx_shards_map_ids, self._h, ids)
+
     def shard_stats(self):
         """Per-shard (proof-served queries, proof failures)."""
         out = []
@@ -605,6 +650,20 @@ class ShardedMi355xIndex(_FaissShaped):
             check(self._lib, self._lib.knnx_get_stats(C.c_void_p(self._lib.knnx_shards_get(self._h, g)), C.byref(a), C.byref(b)), "knnx")
             out.append((int(a.value), int(b.value)))
         return out
+
+
+def get_old_to_new_mapping(index):
+    """The reference's get_old_to_new_mapping(index) (ivf_metadata_ordering.py:46-64) for an IVF index of this package: int64
+    [ntotal], entry i = the position of id i in a metadata store ordered by inverted list.  One pass over the id map on the device
+    instead of a Python loop over the lists."""
+    return index.ivf_old_to_new()
+
+
+def search_to_new_ids(index, query, k):
+    """The reference's search_to_new_ids(index, query, k) (ivf_metadata_ordering.py:17-43): (distances [n, k], the list-ordered ids
+    of the FIRST query's results [k], -1 kept).  The search is the plain search; only its ids are translated (Mi355xIndex.map_ids)."""
+    distances, indices = index.search(query, k)
+    return distances, index.map_ids(indices[0])
 
 
 def embedding_files(folder):

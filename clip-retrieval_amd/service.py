@@ -153,6 +153,82 @@ class ArrowMetadataProvider:
         return out
 
 
+IVF_MAPPING_FILE = "ivf_old_to_new_mapping.npy"
+
+
+def load_ivf_old_to_new_mapping(indice_folder, image_index):
+    """The reference's file protocol for the id mapping of a metadata store ordered by inverted list (clip_back.py:629-640):
+    `<indice_folder>/ivf_old_to_new_mapping.npy` is, despite its name, a RAW int64 memmap without an npy header.  It is written once
+    when absent -- from `image_index.ivf_old_to_new()`, one pass on the device -- and memory-mapped read-only from then on; a file the
+    reference wrote loads here and the reverse.  The result goes into `clip_resource.ivf_old_to_new_mapping`; a service may also leave
+    that None and let KnnHotPath translate through `image_index.map_ids` without any per-row table on the host."""
+    path = os.path.join(indice_folder, IVF_MAPPING_FILE)
+    if not os.path.exists(path):
+        mapping = np.ascontiguousarray(image_index.ivf_old_to_new(), dtype=np.int64)
+        tmp = path + ".tmp"  # (never a half-written file under the final name)
+        out = np.memmap(tmp, dtype="int64", mode="w+", shape=mapping.shape)
+        out[:] = mapping
+        out.flush()
+        del out
+        os.replace(tmp, path)
+    return np.memmap(path, dtype="int64", mode="r")
+
+
+def reorder_arrow_metadata(index, src_folder, dst_folder, columns=None, rows_per_file=1 << 20):
+    """Write the Arrow IPC metadata of `src_folder` (what ArrowMetadataProvider reads: row i = id i) into `dst_folder` ordered by the
+    inverted lists of `index`: row o of the result is source row new_to_old[o], so that
+    `ArrowMetadataProvider(dst_folder).get(index.map_ids(ids)) == ArrowMetadataProvider(src_folder).get(ids)` and the results of one
+    probed list are one contiguous run.  Streams: every output file (`rows_per_file` rows, one record batch) is gathered from the
+    memory-mapped source batches it touches and written before the next one is looked at; the table is never materialised.  `columns`
+    keeps a subset (unknown names are ignored, like the provider's filter).  Returns the files written.  (The reference's HDF5 sink --
+    ivf_metadata_ordering.py:87-131 -- is out of scope: DESIGN section 7.)"""
+    from pathlib import Path  # pylint: disable=import-outside-toplevel
+
+    import pyarrow as pa  # pylint: disable=import-outside-toplevel
+
+    files = [str(a) for a in sorted(Path(src_folder).glob("**/*")) if a.is_file()]
+    if not files:
+        raise ValueError(f"no Arrow files under {src_folder}")
+    readers = [pa.ipc.RecordBatchFileReader(pa.memory_map(f, "r")) for f in files]
+    where = [(r, b) for r in readers for b in range(r.num_record_batches)]  # global batch number -> (reader, batch in it)
+    schema = readers[0].schema
+    names = schema.names if columns is None else [c for c in schema.names if c in set(columns)]
+    out_schema = pa.schema([schema.field(c) for c in names])
+    starts = np.cumsum([0] + [r.get_batch(b).num_rows for r, b in where])
+    new_to_old = np.asarray(index.ivf_new_to_old(), dtype=np.int64)
+    if int(starts[-1]) != new_to_old.shape[0]:
+        raise ValueError(f"{src_folder} holds {int(starts[-1])} rows, the index {new_to_old.shape[0]}")
+    id_base = int(new_to_old.min()) if new_to_old.size else 0
+    if id_base != 0:
+        raise ValueError(f"the index's ids start at {id_base}: metadata rows are addressed by ids from 0 (map a sharded index as a whole)")
+    rows_per_file = max(int(rows_per_file), 1)
+    os.makedirs(dst_folder, exist_ok=True)
+    written = []
+    for part, lo in enumerate(range(0, new_to_old.shape[0], rows_per_file)):
+        src = new_to_old[lo:lo + rows_per_file]
+        which = np.searchsorted(starts, src, side="right") - 1
+        order = np.argsort(which, kind="stable")
+        sorted_which = which[order]
+        pieces, pos = [], 0
+        while pos < len(order):  # one take per source batch this file touches (ArrowMetadataProvider.get does the same per request)
+            b = int(sorted_which[pos])
+            end = int(np.searchsorted(sorted_which, b, side="right"))
+            r, bi = where[b]
+            pieces.append(r.get_batch(bi).select(names).take(pa.array(src[order[pos:end]] - starts[b])))
+            pos = end
+        back = np.empty(len(order), dtype=np.int64)
+        back[order] = np.arange(len(order))  # the pieces are in `order`; put the rows back into list order
+        table = pa.Table.from_batches(pieces, schema=out_schema).take(pa.array(back)).combine_chunks()
+        if part > 99999:  # (the provider reads the files in name order: five digits keep that the part order)
+            raise ValueError("more than 100 000 output files: raise rows_per_file")
+        path = os.path.join(dst_folder, f"{part:05d}.arrow")
+        with pa.OSFile(path, "wb") as sink, pa.ipc.new_file(sink, out_schema) as writer:
+            for batch in table.to_batches():
+                writer.write_batch(batch)
+        written.append(path)
+    return written
+
+
 class _ResidentIndexPool:
     """Small flat GPU indexes that live as long as the service (allocating one per request would cost more than the search),
     a few per embedding width so that concurrent request threads (clip_back.py:1018) do not queue behind ONE dedup index:
@@ -201,7 +277,8 @@ class _ResidentIndexPool:
 class KnnHotPath:
     """The arithmetic of one /knn-service request.  `clip_resource` is the reference's ClipResource-shaped object:
     .model / .tokenizer / .preprocess (encoder.load_clip), .image_index / .text_index (knn.Mi355xIndex or
-    knn.ShardedMi355xIndex), .safety_model, .violence_detector, .aesthetic_embeddings, .metadata_is_ordered_by_ivf = False."""
+    knn.ShardedMi355xIndex), .safety_model, .violence_detector, .aesthetic_embeddings, .metadata_is_ordered_by_ivf and
+    .ivf_old_to_new_mapping (None: the image index translates the ids itself)."""
 
     def __init__(self, dedup_device=0):
         self._scratch = _ResidentIndexPool(dedup_device)   # dedup: the request's own result vectors
@@ -333,14 +410,13 @@ class KnnHotPath:
     # ------------------------------------------------------------------ clip_back.py:343-399
     def knn_search(self, query, modality, num_result_ids, clip_resource, deduplicate, use_safety_model, use_violence_detector):
         """(distances, indices): the index's answer cut at the first -1, minus the post filter's picks, each id once, best
-        first.  (metadata_is_ordered_by_ivf needs faiss' IVF id mapping: serve with reorder_metadata_by_ivf_index=False, as the
-        LAION-5B recipes do, docs/laion5B_back.md:22.)
+        first.  With `clip_resource.metadata_is_ordered_by_ivf` the surviving ids are translated into the ids of the list-ordered
+        metadata store as the last step (_ivf_id_mapper).
         An IVF-PQ index serves num_result_ids <= 64 as it stands; the Python default of 100, the front end's 3 000 and the >= 100 000
         requests of the probe-widening branch below need its threshold scan switched on (Mi355xIndex.pq_threshold_scan, or
         threshold_scan=True at build time; saved with the index) -- without it the index answers them with KNNX_E_UNSUPPORTED, which
         is raised, never papered over.  No branch of this function depends on the switch."""
-        if getattr(clip_resource, "metadata_is_ordered_by_ivf", False):
-            raise NotImplementedError("metadata_is_ordered_by_ivf needs faiss' IVF id mapping; serve with reorder_metadata_by_ivf_index=False")
+        to_new = self._ivf_id_mapper(clip_resource)
         index = clip_resource.image_index if modality == "image" else clip_resource.text_index
         # clip_back.py:356-369: a request for >= 100 000 results widens the IVF probe to ceil(k / 3000) lists for the duration of the
         # search (nprobe lists hold ~nprobe * N / nlist rows: fewer than k otherwise) and puts the old value back.  The reference does
@@ -383,7 +459,8 @@ class KnnHotPath:
         ids, dist = ids[:n], D[0][:n]
         if (ids_l is not None and not need_vectors and (not deduplicate or (links is not None and len(links) == 0))
                 and len(set(ids_l[:n])) == n):
-            return list(dist), list(ids)  # nothing to drop, every id once: the answer as it is (numpy scalars, like the reference's lists)
+            # nothing to drop, every id once: the answer as it is (numpy scalars, like the reference's lists)
+            return list(dist), list(ids if to_new is None else to_new(ids))
         keep = np.ones(n, dtype=bool)
         drop = set()
         emb = normalized(R[0][:n]) if R is not None else None
@@ -401,7 +478,23 @@ class KnnHotPath:
         once = np.zeros(n, dtype=bool)
         once[first] = True
         sel = np.flatnonzero(keep & once)
-        return list(dist[sel]), list(ids[sel])
+        return list(dist[sel]), list(ids[sel] if to_new is None else to_new(ids[sel]))
+
+    @staticmethod
+    def _ivf_id_mapper(clip_resource):
+        """None, or -- with `metadata_is_ordered_by_ivf` -- the translation of result ids into the ids of a metadata store ordered by
+        inverted list (clip_back.py:350-364).  The search runs exactly as without it; the ids that survive the cut at -1 and the post
+        filter are translated last, so the fewest ids travel and -1 never reaches the mapping.  The mapping is ALWAYS the image
+        index's, whichever index was searched: the metadata is ordered by the image index's lists, and the reference maps text
+        results through the same array.  `clip_resource.ivf_old_to_new_mapping` (the reference's array; works with any index object)
+        wins when it is not None, otherwise `image_index.map_ids` translates on the device without a per-row table on the host."""
+        if not getattr(clip_resource, "metadata_is_ordered_by_ivf", False):
+            return None
+        table = getattr(clip_resource, "ivf_old_to_new_mapping", None)
+        if table is not None:
+            return lambda ids: np.take(table, ids)
+        mapper = clip_resource.image_index.map_ids
+        return lambda ids: mapper(np.ascontiguousarray(ids, dtype=np.int64))
 
     # ------------------------------------------------------------------ clip_back.py:401-417
     @staticmethod

@@ -300,6 +300,34 @@ int knnx_pqb_set_codebooks(knnx_pq_builder* b, const float* codebooks);
 int knnx_pqb_get_codebooks(knnx_pq_builder* b, float* codebooks);
 int knnx_pqb_lloyd(knnx_pq_builder* b, uint8_t* codes_out, int64_t* sizes_out);
 
+/* ---- List-ordered ids: the reference's reorder_metadata_by_ivf_index (ivf_metadata_ordering.py:17-64, clip_back.py:350-369, 629-640) ----
+ * A metadata store re-ordered so that the ids of one inverted list are one contiguous run turns the k random rows of a request into
+ * nprobe runs.  The mapping is a function of the layout a built IVF index (IVF-Flat or IVF-PQ; with or without rotation, d_out, refine
+ * store, threshold scan) already owns.  size[l] = rows of list l; dense0[l] = the exclusive prefix sum of size in int64.  The row at
+ * position j of list l (arena row 32 * tile0[l] + j) has the ORDINAL dense0[l] + j; the ordinals are a permutation of [0, ntotal); pad
+ * rows have none.
+ *   new_to_old[o] = the id of the row with ordinal o: the lists' ids one after the other, list 0 first, in arena order (what faiss'
+ *                   il.get_ids(l) yields list by list).
+ *   old_to_new[i] = id_base + the ordinal of the row whose id is id_base + i, i in [0, ntotal).  With id_base = 0 exactly the array
+ *                   get_old_to_new_mapping returns.
+ * knnx_ivf_id_order: host arrays of ntotal int64 each; one may be NULL, both NULL: KNNX_E_ARG.  The export walks consecutive ranges of
+ * KNNX_ID_ORDER_CHUNK ordinals (read from the environment at call time; default 2^22, minimum 64) through one staging buffer of that
+ * size: no device allocation proportional to ntotal.
+ * knnx_ivf_map_ids: out[i] = the old_to_new value of ids[i] (host, n entries); -1 -> -1; out may alias ids.  An id that is neither -1
+ * nor in [id_base, id_base + ntotal) answers KNNX_E_ARG naming the id and its position; the range is checked on the host before
+ * anything is launched and out is left untouched.  n == 0 is a success that launches nothing.  It is meant for the request path: it
+ * does not take the lock the searches hold (the layout is immutable once the index is built) but a mutex, a stream and a grow-on-demand
+ * staging of its own, walked in chunks of KNNX_ID_ORDER_CHUNK when n exceeds it; knnx_destroy waits for it.
+ * Both answer KNNX_E_STATE, with a message that says why, on a flat index, on an IVF index between knnx_ivf_begin and knnx_ivf_end, and
+ * on an empty index.  An index nobody asks for a mapping allocates and launches nothing of this: dense0 is built by the first call, from
+ * the list sizes, and kept.  Nothing of it is saved with an index: it follows from the layout.
+ * Shards: shard g holds the global ids [row_lo[g], row_hi[g)) with id_base = row_lo[g], so the global mapping is the concatenation of
+ * the shards' mappings -- a permutation of [0, N), list-sorted inside each shard's range.  knnx_shards_map_ids routes every id to its
+ * shard by row range, maps per shard and puts the answers back in request order; an id outside every range answers KNNX_E_ARG as above;
+ * shards that are not IVF answer KNNX_E_STATE. */
+int knnx_ivf_id_order(knnx_index* ix, int64_t* old_to_new, int64_t* new_to_old);
+int knnx_ivf_map_ids(knnx_index* ix, const int64_t* ids, int64_t n, int64_t* out);
+
 /* Merge P per-shard results ([P, n, k] each, already global ids) into the top-k [n, k];
  * the step after the RCCL all-gather of a row-sharded index.  Device buffers.  k <= 64: any order within a list;
  * k > 64: every list sorted as knnx_search returns it (score descending, -1 padding at the tail), P <= 64. */
@@ -338,6 +366,9 @@ knnx_index* knnx_shards_get(knnx_shards* s, int g); /* borrowed: profiling, npro
 int knnx_shards_search(knnx_shards* s, const float* q, int n, int k, float* D, int64_t* I, float* R);
 int knnx_shards_reconstruct(knnx_shards* s, const int64_t* ids, int64_t n, float* out);
 int knnx_shards_range_search(knnx_shards* s, const float* q, int n, float thresh, int64_t* lims, float* D, int64_t* I);
+/* List-ordered ids over all shards (the block "List-ordered ids" above): host arrays of knnx_shards_ntotal entries / n entries. */
+int knnx_shards_id_order(knnx_shards* s, int64_t* old_to_new, int64_t* new_to_old);
+int knnx_shards_map_ids(knnx_shards* s, const int64_t* ids, int64_t n, int64_t* out);
 
 /* Counters of the proof-based scans (64-query wide scan, 256-query RQ scan): queries they served and queries whose
  * exactness proof failed and were re-run by the exact 32-query scan (each failure costs one more pass over HBM). */

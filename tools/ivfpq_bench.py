@@ -55,6 +55,9 @@ def main():
     ap.add_argument("--k-factor", default="1,4,8", help="k_factor values of --refine")
     ap.add_argument("--large-k", default="", help="with --refine: k values above 64 (e.g. 100,3000) timed at B = 1, nprobe 64 on the plain index, "
                     "the refine index (the first --k-factor) and IVF-Flat -- the yardstick -- alternately")
+    ap.add_argument("--id-order", action="store_true", help="build the index, time the export of its list-ordered ids (Mi355xIndex.ivf_old_to_new / "
+                    "ivf_new_to_old: one pass on the device) against the numpy restatement on this box (np.concatenate of the per-list ids, "
+                    "inverse by np.put), print one JSON line and stop")
     ap.add_argument("--kind", type=int, default=1, choices=(1, 2), help="corpus: 1 = the mixture of config 5, 2 = isotropic with three dominant columns")
     a = ap.parse_args()
 
@@ -80,6 +83,9 @@ def main():
     free0 = torch.cuda.mem_get_info()[0]
     index, st = build_ivfpq_index_device(fill_rows, n, d, a.nlist, a.M, nprobe=16, niter=6, pq_niter=8, seed=0)
     torch.cuda.synchronize()
+    if a.id_order:
+        print(json.dumps(id_order_ab(a, index, st)))
+        return
     used = free0 - torch.cuda.mem_get_info()[0]
     out = {"rows": n, "d": d, "nlist": a.nlist, "M": a.M, "train_s": round(st["train_s"], 2), "assign_s": round(st["assign_s"], 2),
            "encode_s": round(st["encode_s"], 2), "bytes_per_row_model": a.M + 12, "hbm_bytes_index": int(used),
@@ -259,6 +265,42 @@ def main():
     else:
         index.close()
     print(json.dumps(out))
+
+
+def id_order_ab(a, index, st):
+    """The export of the list-ordered ids against the numpy restatement of ivf_metadata_ordering.py:46-64 (the reference's own loop needs
+    faiss): per-list id arrays -> np.concatenate, inverse by np.put.  The per-list arrays are views of the exported new_to_old, cut at
+    the list sizes, so the yardstick starts from what il.get_ids(l) would hand it."""
+    def best(fn, reps):
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            r = fn()
+            ts.append(time.perf_counter() - t0)
+        return r, float(np.min(ts)), float(np.median(ts))
+
+    index.ivf_old_to_new()  # (first call: dense0 is built, the runtime has loaded the kernels)
+    o2n, o2n_min, o2n_med = best(index.ivf_old_to_new, a.reps)
+    n2o, n2o_min, n2o_med = best(index.ivf_new_to_old, a.reps)
+    sizes = np.asarray(st["list_sizes"], dtype=np.int64)
+    per_list = np.split(n2o, np.cumsum(sizes)[:-1])
+
+    def restated():
+        flat = np.concatenate(per_list)
+        d_ = np.ones((flat.shape[0],), "int64")
+        d_.put(flat, np.arange(flat.shape[0], dtype=np.int64))
+        return flat, d_
+
+    (flat, inv), np_min, np_med = best(restated, a.reps)
+    ids = np.random.default_rng(0).integers(0, a.rows, 40).astype(np.int64)
+    index.map_ids(ids)
+    _, map_min, map_med = best(lambda: index.map_ids(ids), 200)
+    return {"rows": a.rows, "d": a.d, "nlist": a.nlist, "M": a.M, "equal_to_numpy": bool(np.array_equal(flat, n2o) and np.array_equal(inv, o2n)),
+            "empty_lists": int((sizes == 0).sum()), "largest_list": int(sizes.max()),
+            "old_to_new_s": {"min": round(o2n_min, 4), "median": round(o2n_med, 4)},
+            "new_to_old_s": {"min": round(n2o_min, 4), "median": round(n2o_med, 4)},
+            "numpy_concatenate_put_s": {"min": round(np_min, 4), "median": round(np_med, 4)},
+            "map_ids_40_us": {"min": round(map_min * 1e6, 1), "median": round(map_med * 1e6, 1)}}
 
 
 def rect_ab(a, fill_rows):

@@ -10,6 +10,13 @@ vocabulary file exists offline -- the arithmetic per request is the same); index
 in HBM (BASELINE config 3); metadata: an Arrow IPC table of --meta-rows rows (url, caption), memory-mapped, through the
 reference's per-id slicing (clip_back.py:608-615 restated) and through service.ArrowMetadataProvider's batched take.
 Prints a table like README.md:429-437 and one JSON line (prefix "REQUEST ").
+
+    python tools/request_bench.py --serve-threads 64 [--ordered-by-ivf] [--ivf-rows 16777216 --nlist 16384 --requests 200]
+
+The serving side alone: --serve-threads request threads, each sending one-query requests (knn_search at k = 40 + map_to_metadata) to ONE
+IVF-PQ index built on the device, as clip_back's werkzeug threads do.  --ordered-by-ivf serves the same request stream with
+metadata_is_ordered_by_ivf=True: the ids are translated by the image index (Mi355xIndex.map_ids) and the metadata comes from a folder
+re-ordered by its lists.  Prints one JSON line (prefix "SERVE ").
 """
 import argparse
 import base64
@@ -60,13 +67,103 @@ class ReferenceStyleProvider:
         return t.select(cols).to_pandas().to_dict("records")
 
 
+def serve(a):
+    """--serve-threads: requests per second of the search + metadata half under concurrent one-query callers."""
+    import threading
+    from types import SimpleNamespace
+
+    import numpy as np
+    import pyarrow as pa
+    import pyarrow.compute as pc
+    import torch
+
+    from clip_retrieval_amd.knn import build_ivfpq_index_device, synth_rows_device
+    from clip_retrieval_amd.service import ArrowMetadataProvider, KnnHotPath, reorder_arrow_metadata
+
+    n, d, k = a.ivf_rows, 1024, 40
+
+    def fill_rows(dst, row0, count, stride):
+        synth_rows_device(dst, row0, count, d, 5, kind=1, n_clusters=4096, row_stride=stride)
+
+    ix, _ = build_ivfpq_index_device(fill_rows, n, d, a.nlist, 64, nprobe=16, niter=4, pq_niter=4, seed=0)
+    qrows = torch.empty((256, d), dtype=torch.float16, device="cuda")
+    synth_rows_device(qrows.data_ptr(), n + 12345, 256, d, 5, kind=1, n_clusters=4096)
+    q = qrows.float().cpu().numpy()
+    q = np.ascontiguousarray(q / np.linalg.norm(q, axis=1, keepdims=True), dtype=np.float32)
+    tmp = tempfile.mkdtemp(prefix="reqserve")
+    ids = pa.array(np.arange(n, dtype=np.int64))
+    table = pa.table({"url": pc.binary_join_element_wise(pa.scalar("https://example.org/images/"), pc.cast(ids, pa.string()), pa.scalar(".jpg"), pa.scalar("")),
+                      "row": ids})
+    mdir = os.path.join(tmp, "meta")
+    os.makedirs(mdir)
+    with pa.OSFile(os.path.join(mdir, "0.arrow"), "wb") as sink, pa.ipc.new_file(sink, table.schema) as w:
+        w.write_table(table, max_chunksize=1 << 20)
+    del table
+    reorder_s = None
+    if a.ordered_by_ivf:
+        t0 = time.perf_counter()
+        mdir2 = os.path.join(tmp, "meta_by_list")
+        reorder_arrow_metadata(ix, mdir, mdir2)
+        reorder_s = time.perf_counter() - t0
+        mdir = mdir2
+    provider = ArrowMetadataProvider(mdir)
+    res = SimpleNamespace(image_index=ix, text_index=ix, metadata_is_ordered_by_ivf=bool(a.ordered_by_ivf), ivf_old_to_new_mapping=None,
+                          safety_model=None, violence_detector=None, aesthetic_embeddings=None)
+    hp = KnnHotPath()
+    T, R = a.serve_threads, a.requests
+    lat = [[] for _ in range(T)]
+    rows_seen = [None] * T
+    go = threading.Barrier(T + 1)
+
+    def worker(t):
+        go.wait()
+        for r in range(R):
+            t0 = time.perf_counter()
+            j = (t * R + r) % 256
+            dist, ind = hp.knn_search(q[j:j + 1], "image", k, res, False, False, False)
+            meta = hp.map_to_metadata(ind, dist, len(ind), provider, ["url", "row"])
+            lat[t].append(time.perf_counter() - t0)
+            if r == 0:
+                rows_seen[t] = [m["row"] for m in meta]
+        go.wait()
+
+    hp.knn_search(q[:1], "image", k, res, False, False, False)  # (first call: kernels loaded, scratch allocated)
+    threads = [threading.Thread(target=worker, args=(t,)) for t in range(T)]
+    for th in threads:
+        th.start()
+    go.wait()
+    t0 = time.perf_counter()
+    go.wait()
+    wall = time.perf_counter() - t0
+    for th in threads:
+        th.join()
+    # the same records either way: the `row` column carries the original id
+    check = all(rows_seen[t] == [int(v) for v in ix.search(q[(t * R) % 256:(t * R) % 256 + 1], k)[1][0] if v >= 0] for t in range(min(T, 4)))
+    all_lat = np.sort(np.concatenate([np.asarray(x) for x in lat]))
+    print("SERVE " + json.dumps({"rows": n, "nlist": a.nlist, "threads": T, "requests": T * R, "k": k, "ordered_by_ivf": bool(a.ordered_by_ivf),
+                                 "requests_per_s": round(T * R / wall, 1), "p50_ms": round(float(all_lat[len(all_lat) // 2]) * 1e3, 3),
+                                 "p99_ms": round(float(all_lat[int(len(all_lat) * 0.99)]) * 1e3, 3), "records_are_the_original_rows": bool(check),
+                                 "reorder_metadata_s": None if reorder_s is None else round(reorder_s, 2),
+                                 "coalesce": ix.coalesce_stats()}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--serve-threads", type=int, default=0, help="measure the serving side alone from this many request threads (see the module text)")
+    ap.add_argument("--ordered-by-ivf", action="store_true", help="with --serve-threads: serve with metadata_is_ordered_by_ivf=True")
+    ap.add_argument("--ivf-rows", type=int, default=16_777_216)
+    ap.add_argument("--nlist", type=int, default=16384)
+    ap.add_argument("--requests", type=int, default=200, help="with --serve-threads: requests per thread")
     ap.add_argument("--rows", type=int, default=100_000_000)
     ap.add_argument("--meta-rows", type=int, default=10_000_000)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--model", default="ViT-L/14")
     a = ap.parse_args()
+    if a.ordered_by_ivf and not a.serve_threads:
+        ap.error("--ordered-by-ivf needs --serve-threads")
+    if a.serve_threads:
+        serve(a)
+        return
 
     import numpy as np
     import pyarrow as pa

@@ -162,6 +162,7 @@ SIGNATURES = {
     "clipx_get_option": (C.c_int, [_P, C.c_int]),
     "clipx_max_batch": (C.c_int, [_P]),
     "clipx_graphs_cached": (C.c_int, [_P]),
+    "clipx_last_text_rows": (C.c_int, [_P]),
     "clipx_embed_dim": (C.c_int, [_P]),
     "clipx_gemm_bf16_device": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "clipx_gemm_bf16_ex_device": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
@@ -171,8 +172,10 @@ SIGNATURES = {
     "clipx_attention_dh_device": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "clipx_layernorm_device": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
     "clipx_rowstats_device": (C.c_int, [C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_float, _P]),
+    "clipx_tail_device": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P]),
     "clipx_profile_enable": (C.c_int, [_P, C.c_int]),
     "clipx_profile_get": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "clipx_profile_events": (C.c_int, [_P]),
     "clipx_last_error": (C.c_char_p, []),
 }
 

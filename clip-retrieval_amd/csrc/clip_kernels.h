@@ -1,6 +1,7 @@
 // clip_kernels.h -- launchers of the gfx950 CLIP encoder kernels (internal; public ABI: include/clipx.h)
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <stdint.h>
 
 namespace clipx {
@@ -20,6 +21,27 @@ enum GemmEpilogue {
                             // (round 4): q and k feed the softmax logits, where the bf16 rounding of EPI 0 was the largest single
                             // error of the encoder on weights with large LayerNorm gains (tools/emulate_fp16_stream.py)
 };
+
+// Per-dispatch timing (the GEMM brackets of clipx_profile_enable, clipx_api.hip ProfScope): start / stop event pairs that the
+// kernels of one launch_gemm call take, one pair per kernel, attached to the kernel's own dispatch packet instead of being
+// recorded as marker packets in front of and behind it -- nothing sits between back-to-back dispatches.
+struct LaunchEvents {
+  hipEvent_t* ev;  // ev[2 i] / ev[2 i + 1]: start / stop of the i-th kernel launched
+  int cap, used;   // pairs available / handed out so far
+  int untimed;     // kernels launched after the pairs ran out (their time is missing from the scope: clipx_profile_get reports it)
+};
+
+// hipLaunchKernelGGL, with the next event pair of `le` on the dispatch when there is one (le may be null)
+template <class K, class... Args>
+inline void launch_with_events(LaunchEvents* le, K kern, const dim3& grid, const dim3& block, size_t smem, hipStream_t st, Args... args) {
+  if (le && le->used < le->cap) {
+    hipEvent_t* p = le->ev + 2 * le->used++;
+    hipExtLaunchKernelGGL(kern, grid, block, (uint32_t)smem, st, p[0], p[1], 0, args...);
+  } else {
+    if (le) ++le->untimed;
+    hipLaunchKernelGGL(kern, grid, block, smem, st, args...);
+  }
+}
 
 struct GemmArgs {
   const bf16* A;      // activations [M, K] row-major
@@ -49,10 +71,15 @@ struct GemmArgs {
                           // compute it (launch_gemm runs launch_rowstats on those rows); the rows the 4-wave 256x256 kernel takes get
                           // their statistics from the A fragments inside its K loop instead (gemm256w4.hip, STATS) and are not written
   int* range_flag;        // (stats_eps > 0) raised when a row of A holds inf / NaN (launch_rowstats)
+  LaunchEvents* events;   // null, or the source of one start / stop event pair for every kernel this GEMM launches
 };
 
 // number of 256-row m-tiles variant 3 hands to the 256x256 kernel for an [M, N] output
 int gemm256_bulk_mtiles(int M, int N, int n_cu);
+// the same count under launch_gemm's whole dispatch rule: 0 when every row goes to the 128x128 kernel in one launch
+int gemm256_dispatch_mtiles(int M, int N, int K, int variant, int n_cu);
+// M rounded up to whole 256-row m-tiles where that saves launch_gemm the leftover-row launch, else M (ragged_prepare pads to it)
+int gemm256_whole_tile_rows(int M, int N, int K, int variant, int n_cu);
 // blocks of 32 columns per workgroup when ONE ragged m-tile of 256 rows rides in the persistent launch (0: not possible)
 int gemm256_tail_blocks(int N, int K, int n_cu);
 
@@ -70,7 +97,7 @@ hipError_t launch_layernorm(const float* x, const float* gamma, const float* bet
 // absorbs beta: clipx_api.hip fold_layernorm), whose epilogue multiplies by rstd[m].  One wave per row.
 // canonical != 0 (fp16 rows): the one-pass form of a GEMM that owns its statistics (GemmArgs.stats_eps)
 hipError_t launch_rowstats(const void* x16, float* rstd, int M, int d, float eps, hipStream_t st, int f16 = 0, int* range_flag = nullptr,
-                           int canonical = 0);
+                           int canonical = 0, LaunchEvents* events = nullptr);
 
 // LayerNorm-folded weights: Wf[n, k] = r16(W[n,k] gamma[k] - mean_k(W[n,:] gamma)), cf[n] = bias[n] + sum_k beta[k] W[n,k];
 // r16 = bf16 rounding, or IEEE fp16 when f16 != 0
@@ -98,12 +125,17 @@ hipError_t launch_text_embed(const int32_t* ids, const float* tok_emb, const flo
 // pooled row (CLS, or argmax(ids) for text) -> LayerNorm -> @ proj^T [E, d] -> / L2 norm -> fp16 [B, E]
 // x: the residual stream, f32 [B*T, d] or (x_f16 != 0) IEEE fp16
 // scratch: B * E floats of device memory (the un-normalised projection between the two kernels)
+// sb: samples per workgroup of the projection kernel -- -1: chosen by B (per-sample kernel for small batches, batched above),
+// 0: the per-sample kernel, 8 / 16: the batched kernel.  Every choice writes the same bytes.
 // pooled rows (token 0, or the EOT token of `ids`) of att [B*T, d] bf16 and x16 [B*T, d] fp16 -> attc / xc [B, d]
 hipError_t launch_gather_pooled(const bf16* att, const void* x16, const int32_t* ids_or_null, bf16* attc, void* xc, int B, int T,
                                 int d, hipStream_t st, const int* rows_or_null = nullptr);
+// (an `sb` the batched kernel cannot serve -- not 0 / 8 / 16, or more LDS than a workgroup may have -- is hipErrorInvalidValue,
+// never a silent fall-back to the per-sample kernel; tail_batched_rows tells what -1 picks)
+int tail_batched_rows(int B, int d, int E);
 hipError_t launch_tail(const void* x, const int32_t* ids_or_null, const float* gamma, const float* beta,
                        const bf16* proj, uint16_t* out_f16, float* out_f32_or_null, float* scratch, int B, int T, int d,
-                       int E, float eps, hipStream_t st, int x_f16 = 0, int* range_flag = nullptr);
+                       int E, float eps, hipStream_t st, int x_f16 = 0, int* range_flag = nullptr, int sb = -1);
 
 hipError_t launch_f32_to_bf16(const float* in, bf16* out, int64_t n, hipStream_t st);
 // conv weight [width, 3*P*P] f32 -> bf16 [width, Kp] zero padded

@@ -57,8 +57,17 @@ struct Tower {
   bf16* proj = nullptr;                            // [embed, width]
 };
 
+constexpr int RG_PAD_MAX = 255;  // most rows ragged_prepare appends to a text batch (whole 256-row m-tiles)
+
+constexpr int PROF_MAX_PAIRS = 4;  // kernels one launch_gemm call issues at most (row statistics, bulk, leftover rows / the split-K pair)
+
+// One bracketed launch scope.  Marker form: ev[0] / ev[1] are recorded on the stream in front of and behind the scope's launches
+// (pairs = 1).  Dispatch form (GEMMs): every kernel of the scope carries its own start / stop pair on its dispatch, and the
+// scope's time is the sum of its kernels' own elapsed times -- never an interval between events of different commands.
 struct ProfEvent {
-  hipEvent_t a, b;
+  hipEvent_t ev[2 * PROF_MAX_PAIRS];
+  int pairs;
+  int untimed;  // kernels of the scope that found no pair left (PROF_MAX_PAIRS too small: clipx_profile_get fails)
   int kind;
   double flops;
 };
@@ -147,10 +156,14 @@ struct clipx_handle {
   hipEvent_t rg_ev[RG_SLOTS] = {nullptr, nullptr, nullptr, nullptr};
   bool rg_used[RG_SLOTS] = {false, false, false, false};
   int rg_next = 0;
+  int last_text_rows = 0;  // rows the latest text chunk ran its layers on (clipx_last_text_rows)
   int32_t* rg_ids_host = nullptr;          // device-pointer calls: the ids come back through this page-locked buffer
   const int32_t* text_ids_host = nullptr;  // host-pointer calls: the caller's ids of the chunk in flight (set by slot_submit)
   int prof = 0;  // bit k set: launches of kind k (0 gemm, 1 attention, 2 layernorm, 3 other) are bracketed by hipEvents
+  bool prof_markers = false;  // CLIPX_OPT_PROF_MARKERS: the marker form for the GEMMs as well (default: events on the dispatches)
   std::vector<ProfEvent> prof_events;
+  std::vector<hipEvent_t> prof_pool;  // events free for reuse: clipx_profile_get hands back what it has read
+  int prof_created = 0;               // events created so far (clipx_profile_events)
 };
 
 static int dev_alloc(clipx_handle* h, void** p, size_t bytes) {
@@ -276,7 +289,8 @@ static int create_impl(clipx_handle* h, const float* blob, size_t blob_floats) {
 
   // ---- workspace
   const size_t Bm = h->max_batch;
-  const size_t rowsV = Bm * V.T, rowsX = Bm * X.T;
+  // text rows: a ragged batch is padded to whole 256-row m-tiles (ragged_prepare), at most 255 rows past a full rectangular one
+  const size_t rowsV = Bm * V.T, rowsX = Bm * X.T + RG_PAD_MAX;
   const size_t nx = std::max(rowsV * V.width, rowsX * X.width);
   const size_t nqkv = std::max(rowsV * 3 * V.width, rowsX * 3 * X.width);
   const size_t nh = std::max(rowsV * V.mlp, rowsX * X.mlp);
@@ -287,6 +301,8 @@ static int create_impl(clipx_handle* h, const float* blob, size_t blob_floats) {
   if ((r = dev_alloc(h, (void**)&h->att, nx * sizeof(bf16)))) return r;
   if ((r = dev_alloc(h, (void**)&h->hbuf, nh * sizeof(bf16)))) return r;
   if ((r = dev_alloc(h, (void**)&h->patches, rowsV * h->Kp * sizeof(bf16)))) return r;
+  if (nx < rowsX * X.width || nqkv < rowsX * 3 * X.width || nh < rowsX * X.mlp || std::max(rowsV, rowsX) < Bm * X.T + RG_PAD_MAX)
+    return fail(CLIPX_E_ARG, "internal: the activation workspace does not hold the padded text rows");
   h->splitk_ws_bytes = (size_t)32 << 20;
   if ((r = dev_alloc(h, (void**)&h->splitk_ws, h->splitk_ws_bytes))) return r;
 
@@ -309,7 +325,8 @@ static int create_impl(clipx_handle* h, const float* blob, size_t blob_floats) {
   memset(h->range_host, 0, (clipx_handle::NSLOT + 1) * sizeof(int));
   h->cur_flag = h->range_flags + clipx_handle::NSLOT;
   {
-    const size_t rg_ints = (size_t)Bm * (X.T + 3);
+    // lens / offsets of B samples + the pseudo-samples of the pad rows (one row each at worst), pooled rows, row map
+    const size_t rg_ints = (size_t)Bm * (X.T + 3) + 3 * RG_PAD_MAX;
     for (int i = 0; i < clipx_handle::RG_SLOTS; ++i) {
       HIPCHK(hipHostMalloc((void**)&h->rg_host[i], rg_ints * sizeof(int), hipHostMallocDefault));
       if ((r = dev_alloc(h, (void**)&h->rg_dev[i], rg_ints * sizeof(int)))) return r;
@@ -369,10 +386,9 @@ extern "C" void clipx_destroy(clipx_handle* h) {
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
-  for (auto& e : h->prof_events) {
-    (void)hipEventDestroy(e.a);
-    (void)hipEventDestroy(e.b);
-  }
+  for (auto& e : h->prof_events)
+    for (int i = 0; i < 2 * e.pairs; ++i) (void)hipEventDestroy(e.ev[i]);
+  for (hipEvent_t e : h->prof_pool) (void)hipEventDestroy(e);
   for (auto& g : h->graphs) (void)hipGraphExecDestroy(g.second);
   for (void* p : h->owned) (void)hipFree(p);
   if (h->blob_dev) (void)hipFree(h->blob_dev);
@@ -400,6 +416,7 @@ extern "C" int clipx_set_option(clipx_handle* h, int option, int value) {
   switch (option) {
     case CLIPX_OPT_RAGGED_TEXT: h->ragged_text = value != 0; return CLIPX_OK;
     case CLIPX_OPT_POOL_LAST_BLOCK: h->pool_last_block = value != 0; return CLIPX_OK;
+    case CLIPX_OPT_PROF_MARKERS: h->prof_markers = value != 0; return CLIPX_OK;
     default: return fail(CLIPX_E_ARG, "unknown option");
   }
 }
@@ -408,40 +425,79 @@ extern "C" int clipx_get_option(const clipx_handle* h, int option) {
   switch (option) {
     case CLIPX_OPT_RAGGED_TEXT: return h->ragged_text ? 1 : 0;
     case CLIPX_OPT_POOL_LAST_BLOCK: return h->pool_last_block ? 1 : 0;
+    case CLIPX_OPT_PROF_MARKERS: return h->prof_markers ? 1 : 0;
     default: return -1;
   }
 }
 extern "C" int clipx_max_batch(const clipx_handle* h) { return h ? h->max_batch : 0; }
 extern "C" int clipx_graphs_cached(const clipx_handle* h) { return h ? (int)h->graphs.size() : 0; }
+extern "C" int clipx_profile_events(const clipx_handle* h) { return h ? h->prof_created : 0; }
+extern "C" int clipx_last_text_rows(const clipx_handle* h) { return h ? h->last_text_rows : 0; }
 extern "C" int clipx_embed_dim(const clipx_handle* h) { return h ? h->desc.embed_dim : 0; }
 
 // ---------------------------------------------------------------------------------------------
 // launch helpers with optional event bracketing
 // ---------------------------------------------------------------------------------------------
+static bool stream_is_capturing(hipStream_t st);
+
+// Timing events live in a pool on the handle: a scope takes what it needs, clipx_profile_get returns what it has read.
+static hipEvent_t prof_take(clipx_handle* h) {
+  if (!h->prof_pool.empty()) {
+    hipEvent_t e = h->prof_pool.back();
+    h->prof_pool.pop_back();
+    return e;
+  }
+  hipEvent_t e = nullptr;
+  if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+  ++h->prof_created;
+  return e;
+}
+
+// Brackets the launches of one scope when its kind is being profiled.  GEMMs (kind 0) get the dispatch form: events() is handed
+// to launch_gemm through GemmArgs and every kernel takes a pair on its own dispatch -- two marker packets around each of the ~136
+// GEMM launches of a step kept back-to-back dispatches apart and cost 1.1 ms of a 43.7 ms ViT-L/14 step.  The other
+// kinds, CLIPX_OPT_PROF_MARKERS, and a stream that is being captured keep the marker form.
 struct ProfScope {
   clipx_handle* h;
   hipStream_t st;
-  hipEvent_t a = nullptr, b = nullptr;
-  int kind;
-  double flops;
-  ProfScope(clipx_handle* h_, hipStream_t st_, int kind_, double flops_) : h(h_), st(st_), kind(kind_), flops(flops_) {
-    if (h->prof & (1 << kind)) {
-      (void)hipEventCreate(&a);
-      (void)hipEventCreate(&b);
-      (void)hipEventRecord(a, st);
+  ProfEvent e{};
+  LaunchEvents le{};
+  bool on = false, dispatch = false;
+  ProfScope(clipx_handle* h_, hipStream_t st_, int kind, double flops) : h(h_), st(st_) {
+    if (!(h->prof & (1 << kind))) return;
+    e.kind = kind;
+    e.flops = flops;
+    dispatch = kind == 0 && !h->prof_markers && !stream_is_capturing(st);
+    const int n = dispatch ? 2 * PROF_MAX_PAIRS : 2;
+    for (int i = 0; i < n; ++i) {
+      e.ev[i] = prof_take(h);
+      if (!e.ev[i]) {  // no event to be had: this scope goes untimed
+        while (i > 0) h->prof_pool.push_back(e.ev[--i]);
+        return;
+      }
     }
+    on = true;
+    if (dispatch) le = LaunchEvents{e.ev, PROF_MAX_PAIRS, 0, 0};
+    else (void)hipEventRecord(e.ev[0], st);
   }
+  LaunchEvents* events() { return on && dispatch ? &le : nullptr; }
   ~ProfScope() {
-    if (a && b) {
-      (void)hipEventRecord(b, st);
-      h->prof_events.push_back({a, b, kind, flops});
+    if (!on) return;
+    if (dispatch) {
+      e.pairs = le.used;
+      e.untimed = le.untimed;
+      for (int i = 2 * le.used; i < 2 * PROF_MAX_PAIRS; ++i) h->prof_pool.push_back(e.ev[i]);
+    } else {
+      (void)hipEventRecord(e.ev[1], st);
+      e.pairs = 1;
     }
+    h->prof_events.push_back(e);
   }
 };
 
 static int run_gemm(clipx_handle* h, hipStream_t st, const bf16* A, const bf16* W, const float* bias, void* out,
                     const float* table, int T, int M, int N, int K, int epi, const float* rowscale = nullptr, bool f16 = false,
-                    float stats_eps = 0.f) {
+                    float stats_eps = 0.f, int pad_rows = 0) {
   GemmArgs g{};
   g.A = A; g.W = W; g.bias = bias; g.out = out; g.table = table; g.T = T;
   g.M = M; g.N = N; g.K = K; g.epi = epi; g.variant = h->gemm_variant; g.n_cu = h->n_cu; g.row0 = 0;
@@ -453,7 +509,8 @@ static int run_gemm(clipx_handle* h, hipStream_t st, const bf16* A, const bf16* 
   // by the unsplit kernels, whose rows do not depend on the batch they travel in (bitwise); a B = 1 row differs from the same
   // sample inside a batch by f32 summation order only
   if (h->single_query) { g.splitk_ws = h->splitk_ws; g.splitk_ws_bytes = h->splitk_ws_bytes; }
-  ProfScope ps(h, st, 0, 2.0 * M * (double)N * K);
+  ProfScope ps(h, st, 0, 2.0 * (M - pad_rows) * (double)N * K);  // (pad rows of a ragged text batch are not work the model asks for)
+  g.events = ps.events();
   HIPCHK(launch_gemm(g, st));
   return 0;
 }
@@ -464,9 +521,11 @@ static const void* pooled_rows(const clipx_handle* h, int B, int width) {
 }
 
 struct Ragged {  // device arrays of one ragged text batch (see clipx_handle::ragged_text)
-  int M;                // rows in all: sum of the lengths
-  const int* offs;      // [B] first row of sample b
-  const int* lens;      // [B] rows of sample b (EOT position + 1)
+  int M;                // rows in all: sum of the lengths, pad rows included (ragged_prepare)
+  int rows;             // the real rows among them (what the profile's flop counts are taken from)
+  int S;                // samples the attention sees: B + the pseudo-samples that own the pad rows
+  const int* offs;      // [S] first row of sample b
+  const int* lens;      // [S] rows of sample b (EOT position + 1)
   const int* rowmap;    // [M] compact row -> b * ctx_len + t
   const int* poolrows;  // [B] compact row of the EOT token
   double att_flops;     // 4 heads dh sum(len^2)
@@ -477,6 +536,7 @@ struct Ragged {  // device arrays of one ragged text batch (see clipx_handle::ra
 static int run_layers(clipx_handle* h, hipStream_t st, const Tower& t, int B, int causal, const int32_t* ids, bool* pooled,
                       const Ragged* rg = nullptr) {
   const int M = rg ? rg->M : B * t.T, w = t.width;
+  const int pad = rg ? rg->M - rg->rows : 0;
   const float eps = h->desc.ln_eps;
   const int act = h->desc.act == CLIPX_ACT_QUICK_GELU ? EPI_BIAS_QGELU_BF16 : EPI_BIAS_GELU_BF16;
   // On entry h->xn holds the residual stream x in fp16 (written by ln_pre / the text embedding).  Per block:
@@ -491,13 +551,13 @@ static int run_layers(clipx_handle* h, hipStream_t st, const Tower& t, int B, in
     int r;
     // (LayerNorm statistics: the separate pass of rounds 2 - 5, or with CLIPX_LN_FUSED=1 inside the GEMM -- run_gemm's stats_eps)
     if (!h->ln_fused) { ProfScope ps(h, st, 2, 0); HIPCHK(launch_rowstats(h->xn, h->rstd, M, w, eps, st, 1, h->cur_flag)); }
-    if ((r = run_gemm(h, st, h->xn, L.qkv_w, L.qkv_c, h->qkv, nullptr, 1, M, 3 * w, w, EPI_BIAS_F16, h->rstd, true, h->ln_fused ? eps : 0.f))) return r;
+    if ((r = run_gemm(h, st, h->xn, L.qkv_w, L.qkv_c, h->qkv, nullptr, 1, M, 3 * w, w, EPI_BIAS_F16, h->rstd, true, h->ln_fused ? eps : 0.f, pad))) return r;
     // last block of the image tower: only token 0's attention row is read afterwards -> query block 0 only (same arithmetic)
     const bool pool_here = l == t.layers - 1 && h->pool_last_block && t.T > 1;
     const int q_blocks = pool_here && !ids ? 1 : 0;
     const double att_rows = q_blocks ? std::min(32, t.T) : t.T;
     { ProfScope ps(h, st, 1, rg ? rg->att_flops * t.heads * (w / t.heads) : 4.0 * B * t.heads * att_rows * t.T * (w / t.heads));
-      HIPCHK(launch_attention(h->qkv, h->att, B, t.T, t.heads, w / t.heads, causal, st, q_blocks, rg ? rg->offs : nullptr, rg ? rg->lens : nullptr)); }
+      HIPCHK(launch_attention(h->qkv, h->att, rg ? rg->S : B, t.T, t.heads, w / t.heads, causal, st, q_blocks, rg ? rg->offs : nullptr, rg ? rg->lens : nullptr)); }
     if (pool_here) {
       // The embedding reads ONE row of this block's output per sample (token 0 / the EOT token: launch_tail), and past the
       // attention every operation of a block is row-wise: out-proj, both residual adds, LayerNorm 2 and the MLP run on those B
@@ -513,10 +573,10 @@ static int run_layers(clipx_handle* h, hipStream_t st, const Tower& t, int B, in
       *pooled = true;
       return 0;
     }
-    if ((r = run_gemm(h, st, h->att, L.out_w, L.out_b, h->xn, nullptr, 1, M, w, w, EPI_BIAS_RESID_H16))) return r;
+    if ((r = run_gemm(h, st, h->att, L.out_w, L.out_b, h->xn, nullptr, 1, M, w, w, EPI_BIAS_RESID_H16, nullptr, false, 0.f, pad))) return r;
     if (!h->ln_fused) { ProfScope ps(h, st, 2, 0); HIPCHK(launch_rowstats(h->xn, h->rstd, M, w, eps, st, 1, h->cur_flag)); }
-    if ((r = run_gemm(h, st, h->xn, L.fc1_w, L.fc1_c, h->hbuf, nullptr, 1, M, t.mlp, w, act, h->rstd, true, h->ln_fused ? eps : 0.f))) return r;
-    if ((r = run_gemm(h, st, h->hbuf, L.fc2_w, L.fc2_b, h->xn, nullptr, 1, M, w, t.mlp, EPI_BIAS_RESID_H16))) return r;
+    if ((r = run_gemm(h, st, h->xn, L.fc1_w, L.fc1_c, h->hbuf, nullptr, 1, M, t.mlp, w, act, h->rstd, true, h->ln_fused ? eps : 0.f, pad))) return r;
+    if ((r = run_gemm(h, st, h->hbuf, L.fc2_w, L.fc2_b, h->xn, nullptr, 1, M, w, t.mlp, EPI_BIAS_RESID_H16, nullptr, false, 0.f, pad))) return r;
   }
   *pooled = false;
   return 0;
@@ -563,7 +623,6 @@ static int run_graphed(clipx_handle* h, hipStream_t st, const clipx_handle::Grap
 static int vision_chunk_body(clipx_handle* h, hipStream_t st, const void* pix_dev, int B, int fmt, uint16_t* out_f16,
                              float* out_f32);
 static int text_chunk_body(clipx_handle* h, hipStream_t st, const int32_t* ids_dev, int B, uint16_t* out_f16, float* out_f32);
-static bool stream_is_capturing(hipStream_t st);
 
 // one chunk (B <= max_batch), everything on the device, asynchronous on `st`
 static int vision_chunk(clipx_handle* h, hipStream_t st, const void* pix_dev, int B, int fmt, uint16_t* out_f16,
@@ -595,14 +654,25 @@ static int vision_chunk_body(clipx_handle* h, hipStream_t st, const void* pix_de
 
 // Builds the ragged description of a text batch from its ids (host) and uploads it.  The pooling rule is launch_tail's /
 // gather_pooled's: the highest id, first occurrence (torch.argmax of the reference model).
+//
+// Whole m-tiles: where the folded GEMMs (QKV, fc1) of the batch run in the 256x256 kernel, the row count is rounded up to a
+// multiple of 256 (gemm256_whole_tile_rows: launch_gemm's own rule), so that no GEMM of the tower needs a second launch for a
+// handful of leftover rows.  The P extra rows are duplicates of real rows: pseudo-samples that are prefixes of the longest
+// caption b* (row map entries b* T + t), ceil(P / len[b*]) of them, the last one shortened so that the lengths sum to P.  The
+// tower is causal and everything else is row-wise, so a prefix of a real caption goes through exactly the arithmetic of its
+// real rows: every pad row holds the bytes of a real row (nothing a GEMM reads is uninitialised, and the fp16 range flag
+// cannot fire where the unpadded batch would not), and no real row changes, because a row does not depend on the rows it
+// travels with.  Only the attention (one more "sample" each) and the row-wise kernels see the pseudo-samples; the pooled
+// rows, gather_pooled and the tail keep B entries.
 static int ragged_prepare(clipx_handle* h, hipStream_t st, const int32_t* ids_host, int B, Ragged* rg) {
-  const int T = h->txt.T;
+  const int T = h->txt.T, w = h->txt.width;
   const int s = h->rg_next;
   h->rg_next = (s + 1) % clipx_handle::RG_SLOTS;
   if (h->rg_used[s]) HIPCHK(hipEventSynchronize(h->rg_ev[s]));  // the upload that last read this slot's host buffer is done
   int* host = h->rg_host[s];
-  int* offs = host, *lens = host + B, *pool = host + 2 * B, *rowmap = host + 3 * B;
-  int M = 0;
+  // layout: pool [B], lens [S], offs [S], rowmap [M]   (S is known once every length is)
+  int* pool = host, *lens = host + B;
+  int M = 0, longest = 0;
   double f = 0.0;
   for (int b = 0; b < B; ++b) {
     const int32_t* row = ids_host + (size_t)b * T;
@@ -610,22 +680,34 @@ static int ragged_prepare(clipx_handle* h, hipStream_t st, const int32_t* ids_ho
     for (int t = 1; t < T; ++t)
       if (row[t] > bv) { bv = row[t]; best = t; }
     const int len = best + 1;
-    offs[b] = M;
     lens[b] = len;
     pool[b] = M + best;
-    for (int t = 0; t < len; ++t) rowmap[M + t] = b * T + t;
+    if (len > lens[longest]) longest = b;
     M += len;
     f += 4.0 * (double)len * len;
   }
+  const int Mp = gemm256_whole_tile_rows(M, 3 * w, w, h->gemm_variant, h->n_cu);
+  const int lmax = lens[longest];
+  const int S = B + (Mp - M + lmax - 1) / lmax;
+  for (int b = B, left = Mp - M; b < S; ++b, left -= lmax) lens[b] = std::min(lmax, left);
+  int* offs = lens + S, *rowmap = offs + S;
+  for (int b = 0, m = 0; b < S; ++b) {
+    const int src = b < B ? b : longest;
+    offs[b] = m;
+    for (int t = 0; t < lens[b]; ++t) rowmap[m + t] = src * T + t;
+    m += lens[b];
+  }
   int* dev = h->rg_dev[s];
-  HIPCHK(hipMemcpyAsync(dev, host, ((size_t)3 * B + M) * sizeof(int), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(dev, host, ((size_t)B + 2 * S + Mp) * sizeof(int), hipMemcpyHostToDevice, st));
   HIPCHK(hipEventRecord(h->rg_ev[s], st));
   h->rg_used[s] = true;
-  rg->M = M;
-  rg->offs = dev;
+  rg->M = Mp;
+  rg->rows = M;
+  rg->S = S;
+  rg->poolrows = dev;
   rg->lens = dev + B;
-  rg->poolrows = dev + 2 * B;
-  rg->rowmap = dev + 3 * B;
+  rg->offs = dev + B + S;
+  rg->rowmap = dev + B + 2 * S;
   rg->att_flops = f;
   return 0;
 }
@@ -651,6 +733,7 @@ static int text_chunk_body(clipx_handle* h, hipStream_t st, const int32_t* ids_d
     if (rr) return rr;
     rg = &rgv;
   }
+  h->last_text_rows = rg ? rg->M : B * X.T;
   { ProfScope ps(h, st, 3, 0); HIPCHK(launch_text_embed(ids_dev, h->tok_emb, h->txt_pos, nullptr, B, X.T, X.width, d.vocab, st, h->xn, 1, rg ? rg->rowmap : nullptr, rg ? rg->M : 0)); }
   bool pooled = false;
   int r = run_layers(h, st, X, B, 1, ids_dev, &pooled, rg);
@@ -1025,6 +1108,20 @@ extern "C" int clipx_rowstats_device(int device, const void* x16, int is_f16, fl
   return CLIPX_OK;
 }
 
+extern "C" int clipx_tail_device(int device, const void* x_f16, const float* gamma, const float* beta, const void* proj_bf16,
+                                 uint16_t* out_f16, float* out_f32_or_null, float* scratch, int B, int d, int E, float eps,
+                                 int rows_per_workgroup, void* stream) {
+  if (!x_f16 || !gamma || !beta || !proj_bf16 || !out_f16 || !scratch || B <= 0 || E <= 0) return fail(CLIPX_E_ARG, "bad tail arguments");
+  if (d % 32 || d <= 0) return fail(CLIPX_E_UNSUPPORTED, "d must be a multiple of 32");
+  HIPCHK(hipSetDevice(device));
+  if (rows_per_workgroup < 0) return tail_batched_rows(B, d, E);  // a query: what the encoder's own call picks for this shape
+  hipError_t e = launch_tail(x_f16, nullptr, gamma, beta, (const bf16*)proj_bf16, out_f16, out_f32_or_null, scratch, B, 1, d, E, eps,
+                             (hipStream_t)stream, 1, nullptr, rows_per_workgroup);
+  if (e == hipErrorInvalidValue) return fail(CLIPX_E_UNSUPPORTED, "no projection kernel with this many rows per workgroup for this d");
+  HIPCHK(e);
+  return CLIPX_OK;
+}
+
 extern "C" int clipx_profile_enable(clipx_handle* h, int on) {
   if (!h) return fail(CLIPX_E_ARG, "handle is null");
   std::lock_guard<std::mutex> lk(h->mu);
@@ -1039,21 +1136,31 @@ extern "C" int clipx_profile_get(clipx_handle* h, int kind, int64_t* launches, d
   int64_t n = 0;
   double t = 0.0, f = 0.0;
   std::vector<ProfEvent> keep;
+  hipError_t err = hipSuccess;  // the first failure; the loop still consumes every scope, so that no event is handed back twice
+  int untimed = 0;
   for (auto& e : h->prof_events) {
     if (e.kind != kind) {
       keep.push_back(e);
       continue;
     }
-    HIPCHK(hipEventSynchronize(e.b));
-    float dt = 0.f;
-    HIPCHK(hipEventElapsedTime(&dt, e.a, e.b));
-    t += dt;
+    for (int i = 0; i < e.pairs; ++i) {
+      float dt = 0.f;
+      hipError_t r = hipEventSynchronize(e.ev[2 * i + 1]);
+      if (r == hipSuccess) r = hipEventElapsedTime(&dt, e.ev[2 * i], e.ev[2 * i + 1]);
+      if (r != hipSuccess && err == hipSuccess) err = r;
+      t += dt;
+    }
     f += e.flops;
     ++n;
-    (void)hipEventDestroy(e.a);
-    (void)hipEventDestroy(e.b);
+    untimed += e.untimed;
+    for (int i = 0; i < 2 * e.pairs; ++i) h->prof_pool.push_back(e.ev[i]);
   }
   h->prof_events.swap(keep);
+  if (err != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(CLIPX_E_HIP, std::string("clipx_profile_get: ") + hipGetErrorString(err));
+  }
+  if (untimed) return fail(CLIPX_E_STATE, "internal: a GEMM launched more kernels than it had timing events for (PROF_MAX_PAIRS)");
   if (launches) *launches = n;
   if (ms) *ms = t;
   if (flops) *flops = f;

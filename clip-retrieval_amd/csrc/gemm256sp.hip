@@ -822,7 +822,7 @@ static hipError_t launch_sp_epi(const GemmArgs& g, int grid, hipStream_t st) {
   auto kern = gemm256sp_kernel<EPI, DBG, F16>;
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), smem, st, g.A, g.W, g.bias, g.out, g.table, g.T, g.N, g.K, g.M / 256,
+  launch_with_events(g.events, kern, dim3(grid), dim3(512), smem, st, g.A, g.W, g.bias, g.out, g.table, g.T, g.N, g.K, g.M / 256,
                      g.N / 256, g.rowscale, g.out16, raster, g.tail_m0, g.tail_nb);
   return hipGetLastError();
 }

@@ -690,7 +690,7 @@ static hipError_t launch_w4_epi(const GemmArgs& g, int grid, hipStream_t st) {
   auto kern = gemm256w4_kernel<EPI, F16, DBG, STATS>;
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, st, g.A, g.W, g.bias, g.out, g.N, g.K, g.M / 256, g.N / 256, g.rowscale, g.tail_m0, g.tail_nb, w4_stagger(),
+  launch_with_events(g.events, kern, dim3(grid), dim3(256), smem, st, g.A, g.W, g.bias, g.out, g.N, g.K, g.M / 256, g.N / 256, g.rowscale, g.tail_m0, g.tail_nb, w4_stagger(),
                      g.stats_eps, g.range_flag);
   return hipGetLastError();
 }

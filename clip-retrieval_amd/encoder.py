@@ -371,7 +371,7 @@ class ClipEncoder:
         of them since the last check (include/clipx.h: clipx_range_check).  The host-buffer calls and tickets check by themselves."""
         check(self._lib, self._lib.clipx_range_check(self._h, C.c_void_p(int(stream)) if stream else None), "clipx")
 
-    OPT_RAGGED_TEXT, OPT_POOL_LAST_BLOCK = 1, 2
+    OPT_RAGGED_TEXT, OPT_POOL_LAST_BLOCK, OPT_PROF_MARKERS = 1, 2, 3
 
     def set_option(self, option, value):
         check(self._lib, self._lib.clipx_set_option(self._h, int(option), int(value)), "clipx")
@@ -382,6 +382,14 @@ class ClipEncoder:
     def graphs_cached(self):
         """Small-batch launch sequences captured as hipGraphs so far (include/clipx.h: clipx_graphs_cached)."""
         return int(self._lib.clipx_graphs_cached(self._h))
+
+    def profile_events(self):
+        """hipEvents the profiling brackets have created so far; profile_get() returns them to a pool (clipx_profile_events)."""
+        return int(self._lib.clipx_profile_events(self._h))
+
+    def last_text_rows(self):
+        """Rows the latest text chunk ran its layers on (include/clipx.h: clipx_last_text_rows)."""
+        return int(self._lib.clipx_last_text_rows(self._h))
 
     def profile(self, on):
         """on: False/0 off, True/1 every kind, or a mask with bit (kind + 1): 2 gemm, 4 attention, 8 layernorm, 16 other."""

@@ -149,9 +149,12 @@ int clipx_range_check(clipx_handle* h, void* stream);
  * values).  Both change which rows are computed, never the bytes of the embeddings (tests/test_clip_gpu.py).
  *   CLIPX_OPT_RAGGED_TEXT [1]      text batches > 8 run every layer on the rows up to each caption's EOT only
  *   CLIPX_OPT_POOL_LAST_BLOCK [1]  the last block runs past its attention on the pooled rows only
+ *   CLIPX_OPT_PROF_MARKERS [0]     clipx_profile_enable brackets the GEMMs with marker events around each launch, as it does the
+ *                                  other kinds, instead of start / stop events on the GEMM kernels' own dispatches (A/B of the two)
  * clipx_get_option returns the value or -1. */
 #define CLIPX_OPT_RAGGED_TEXT 1
 #define CLIPX_OPT_POOL_LAST_BLOCK 2
+#define CLIPX_OPT_PROF_MARKERS 3
 int clipx_set_option(clipx_handle* h, int option, int value);
 int clipx_get_option(const clipx_handle* h, int option);
 
@@ -162,6 +165,10 @@ int clipx_max_batch(const clipx_handle* h);
  * query encode of KnnService.compute_query, clip_back.py:207-255 -- are replayed from a graph per (tower, B, buffers, stream));
  * introspection for tests and service dashboards. */
 int clipx_graphs_cached(const clipx_handle* h);
+/* Rows the text tower ran its layers on in the latest text chunk of this handle: B * ctx_len for a rectangular batch, the
+ * sum of the caption lengths for a ragged one -- rounded up to a multiple of 256 where the batch is large enough for the
+ * 256-row GEMM tiles (the extra rows repeat real rows and are never read); introspection for tests. */
+int clipx_last_text_rows(const clipx_handle* h);
 int clipx_embed_dim(const clipx_handle* h);
 
 /* Raw bf16 GEMM of this library (out[m,n] = sum_k A[m,k] W[n,k] + bias[n]), device pointers;
@@ -206,11 +213,23 @@ int clipx_layernorm_device(int device, const float* x, const float* gamma, const
  * one-pass canonical form that clipx_gemm_f16_ln_device uses for the rows its 4-wave kernel does not take). */
 int clipx_rowstats_device(int device, const void* x16, int is_f16, float* rstd, int M, int d, float eps, void* stream);
 
+/* The embedding tail in isolation (per-kernel parity test): pooled rows x IEEE fp16 [B, d] -> LayerNorm(gamma, beta) -> @ proj^T
+ * (bf16 [E, d]) -> / L2 norm -> out_f16 [B, E] (+ the f32 rows); scratch: B * E floats.  rows_per_workgroup selects the projection
+ * kernel: 0 the per-sample one (small batches, queries), 8 or 16 the batched one -- every choice writes the same bytes;
+ * CLIPX_E_UNSUPPORTED where the batched kernel cannot hold that many rows of d floats.  rows_per_workgroup < 0 launches nothing
+ * and RETURNS the value the encoder itself uses for a batch of this (B, d, E): 0 or 8. */
+int clipx_tail_device(int device, const void* x_f16, const float* gamma, const float* beta, const void* proj_bf16, uint16_t* out_f16,
+                      float* out_f32_or_null, float* scratch, int B, int d, int E, float eps, int rows_per_workgroup, void* stream);
+
 /* Live per-kernel timing for bench.py: launches of the enabled kinds are bracketed by hipEvents on
  * their stream.  kind: 0 gemm, 1 attention, 2 layernorm, 3 other.  on: 0 off, 1 all kinds, else a bit
  * mask with bit (kind + 1): 2 = GEMMs only, 4 | 8 | 16 = everything but the GEMMs.  get() sums and resets. */
 int clipx_profile_enable(clipx_handle* h, int on);
 int clipx_profile_get(clipx_handle* h, int kind, int64_t* launches, double* ms, double* flops);
+/* The GEMMs (kind 0) carry their events on the kernels' own dispatch packets: a GEMM launch counts once, with the summed run time
+ * of the kernels it consists of (CLIPX_OPT_PROF_MARKERS = 1: events recorded around the launch, like the other kinds).  The
+ * events come from a pool on the handle that clipx_profile_get refills; clipx_profile_events = events created so far. */
+int clipx_profile_events(const clipx_handle* h);
 
 const char* clipx_last_error(void);
 

@@ -19,6 +19,7 @@
 
 #include "../../include/clipx.h"
 #include "clip_kernels.h"
+#include "clipx_attn_plan.h"
 
 using namespace clipx;
 
@@ -195,7 +196,12 @@ static int check_desc(const clipx_model_desc* d) {
     return fail(CLIPX_E_UNSUPPORTED, "this build has attention kernels for head dimensions 64 and 80 only");
   if (d->v_mlp % 128 || d->t_mlp % 128) return fail(CLIPX_E_UNSUPPORTED, "mlp widths must be multiples of 128");
   const int g = d->image_size / d->patch_size;
-  if (g * g + 1 > 288 || d->ctx_len > 288) return fail(CLIPX_E_UNSUPPORTED, "sequence longer than 288 tokens");
+  // the image tower may be long where the long-sequence attention kernel exists (head dimension 64, not causal: clipx_attn_plan.h)
+  if (d->ctx_len > clipx::ATTN_SHORT_MAX_T) return fail(CLIPX_E_UNSUPPORTED, "text context longer than 288 tokens");
+  // (head dimension 80 at 97 .. 256 tokens has no kernel either, and is left to fail at its first launch as it always has)
+  if (g * g + 1 > clipx::ATTN_LONG_MAX_T) return fail(CLIPX_E_UNSUPPORTED, "image sequence longer than 608 tokens");
+  if (g * g + 1 > clipx::ATTN_SHORT_MAX_T && vdh != 64)
+    return fail(CLIPX_E_UNSUPPORTED, "image sequence longer than 288 tokens at a head dimension other than 64");
   if (d->embed_dim <= 0 || d->embed_dim % 8) return fail(CLIPX_E_ARG, "embed_dim must be a multiple of 8");
   if (d->act != CLIPX_ACT_QUICK_GELU && d->act != CLIPX_ACT_GELU) return fail(CLIPX_E_ARG, "unknown activation");
   if (d->v_layers <= 0 || d->t_layers <= 0 || d->vocab <= 0 || d->ctx_len <= 0) return fail(CLIPX_E_ARG, "bad layer/vocab/context size");
@@ -1070,10 +1076,18 @@ extern "C" int clipx_gemm_f16_ln_device(int device, const void* A_f16, const voi
   return gemm_hook(device, A_f16, W_f16, bias, out_16bit, M, N, K, epi, rstd_buf, nullptr, stream, 1, eps);
 }
 
+// the T limits of the attention entry points (clipx_attn_plan.h): nullptr when T is within them, else the message; nothing is launched
+static const char* attention_limit(int T, int dh, int causal) {
+  if (T > clipx::ATTN_LONG_MAX_T) return "sequence longer than 608 tokens";
+  if (T > clipx::ATTN_SHORT_MAX_T && causal) return "causal sequence longer than 288 tokens";
+  if (T > clipx::ATTN_SHORT_MAX_T && dh != 64) return "sequence longer than 288 tokens at a head dimension other than 64";
+  return nullptr;
+}
+
 extern "C" int clipx_attention_device(int device, const void* qkv_bf16, void* out_bf16, int B, int T, int H, int causal,
                                       void* stream) {
   if (!qkv_bf16 || !out_bf16 || B <= 0 || T <= 0 || H <= 0) return fail(CLIPX_E_ARG, "bad attention arguments");
-  if (T > 288) return fail(CLIPX_E_UNSUPPORTED, "sequence longer than 288 tokens");
+  if (const char* why = attention_limit(T, 64, causal)) return fail(CLIPX_E_UNSUPPORTED, why);
   HIPCHK(hipSetDevice(device));
   HIPCHK(launch_attention((const bf16*)qkv_bf16, (bf16*)out_bf16, B, T, H, 64, causal, (hipStream_t)stream));
   return CLIPX_OK;
@@ -1082,8 +1096,8 @@ extern "C" int clipx_attention_device(int device, const void* qkv_bf16, void* ou
 extern "C" int clipx_attention_dh_device(int device, const void* qkv_bf16, void* out_bf16, int B, int T, int H, int dh,
                                          int causal, void* stream) {
   if (!qkv_bf16 || !out_bf16 || B <= 0 || T <= 0 || H <= 0) return fail(CLIPX_E_ARG, "bad attention arguments");
-  if (T > 288) return fail(CLIPX_E_UNSUPPORTED, "sequence longer than 288 tokens");
   if (dh != 64 && dh != 80) return fail(CLIPX_E_UNSUPPORTED, "head dimension must be 64 or 80");
+  if (const char* why = attention_limit(T, dh, causal)) return fail(CLIPX_E_UNSUPPORTED, why);
   HIPCHK(hipSetDevice(device));
   hipError_t e = launch_attention((const bf16*)qkv_bf16, (bf16*)out_bf16, B, T, H, dh, causal, (hipStream_t)stream);
   if (e == hipErrorInvalidValue) return fail(CLIPX_E_UNSUPPORTED, "no attention kernel for this (T, head dimension)");

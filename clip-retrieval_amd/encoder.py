@@ -64,6 +64,8 @@ ARCHS = {
     "ViT-B/16": ClipArch(patch_size=16, v_width=768, v_layers=12, v_heads=12, v_mlp=3072, t_width=512, t_heads=8,
                          t_mlp=2048, embed_dim=512),
     "ViT-L/14": ClipArch(),
+    # OpenAI's 336-pixel fine-tune of ViT-L/14: 24 x 24 patches + class token = 577 tokens (the long-sequence attention kernel)
+    "ViT-L/14@336px": ClipArch(image_size=336),
     "open_clip:ViT-B-32": ClipArch(patch_size=32, v_width=768, v_layers=12, v_heads=12, v_mlp=3072, t_width=512,
                                    t_heads=8, t_mlp=2048, embed_dim=512, act="gelu"),
     "open_clip:ViT-L-14": ClipArch(act="gelu"),
@@ -431,7 +433,10 @@ def register_encoder(name: str, encoder: ClipEncoder):
 
 # `clip_model` strings of the reference (all_clip: "ViT-L/14", "open_clip:ViT-H-14/laion2b_s32b_b79k", "hf_clip:openai/clip-vit-large-patch14", ...)
 _HF_NAMES = {"openai/clip-vit-base-patch32": "ViT-B/32", "openai/clip-vit-base-patch16": "ViT-B/16",
-             "openai/clip-vit-large-patch14": "ViT-L/14"}
+             "openai/clip-vit-large-patch14": "ViT-L/14", "openai/clip-vit-large-patch14-336": "ViT-L/14@336px"}
+# open_clip spells the 336-pixel model "ViT-L-14-336" and has OpenAI's weights only for it.  These three names (and the HF one above)
+# are recalled from memory of the third-party packages, not read from them: SURVEY marks such things.
+_OPEN_CLIP_NAMES = {"ViT-L-14-336": "ViT-L/14@336px"}
 
 
 def resolve_arch_name(clip_model: str) -> str:
@@ -445,6 +450,8 @@ def resolve_arch_name(clip_model: str) -> str:
     if clip_model.startswith("open_clip:"):
         arch = clip_model[len("open_clip:"):].split("/")[0]  # "ViT-H-14/laion2b_s32b_b79k" -> "ViT-H-14"
         pretrained = clip_model.split("/", 1)[1] if "/" in clip_model else ""
+        if arch in _OPEN_CLIP_NAMES and pretrained in ("", "openai"):
+            return _OPEN_CLIP_NAMES[arch]
         if pretrained == "openai" and "/".join(arch.rsplit("-", 1)) in ARCHS:
             return "/".join(arch.rsplit("-", 1))  # open_clip:ViT-L-14/openai = the OpenAI (quick_gelu) weights
         if "open_clip:" + arch in ARCHS:
@@ -491,6 +498,8 @@ def get_encoder(clip_model: str, clip_cache_path=None, device: int = 0) -> ClipE
             if os.path.isfile(clip_cache_path):
                 cands.append(clip_cache_path)
             cands += [os.path.join(clip_cache_path, stem + ext) for ext in (".pt", ".safetensors", ".bin", ".npy")]
+            if "@" in stem:  # "ViT-L-14@336px": OpenAI's own file name has a dash there
+                cands += [os.path.join(clip_cache_path, stem.replace("@", "-") + ext) for ext in (".pt", ".safetensors", ".bin", ".npy")]
         path = next((c for c in cands if os.path.isfile(c)), None)
         if path is None:
             raise FileNotFoundError(

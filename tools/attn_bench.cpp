@@ -1,6 +1,9 @@
 // attn_bench.cpp -- times the library's attention kernel (clipx_attention_dh_device, include/clipx.h) without Python and
 // checks a few (batch, head) pairs against an fp32 CPU softmax(QK^T/sqrt(dh))V of the same IEEE fp16 inputs (round 4: q, k, v are fp16; the output is bf16).
-//   hipcc -O2 -o tools/attn_bench tools/attn_bench.cpp -ldl ;  tools/attn_bench [B T H dh causal]
+//   hipcc -O2 -o tools/attn_bench tools/attn_bench.cpp -ldl ;  tools/attn_bench [B T H dh causal [ab_cfg]]
+// ab_cfg (tools library, CLIPX_LIB=libclipx_ablate.so): alternates the default dispatch and CLIPX_ATTN_CFG=ab_cfg in one process on the
+// same buffers -- rounds of 20 timed launches each, A B A B ... -- and prints the median and the spread of the round medians of both,
+// and the largest difference of their outputs.  ab_cfg = 19 at T = 577 .. 608: the long-sequence kernel against the RECOMP yardstick.
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -71,6 +74,46 @@ int main(int argc, char** argv) {
   const double fl = 4.0 * B * H * (double)T * T * dh * (causal ? 0.5 : 1.0);
   printf("attention B=%d T=%d H=%d dh=%d causal=%d cfg=%s: median %.1f us (%.1f TFLOP/s), min %.1f us; max |err| vs fp32 CPU on 3 heads %.4g\n", B, T, H, dh,
          causal, getenv("CLIPX_ATTN_CFG") ? getenv("CLIPX_ATTN_CFG") : "-", ts[ts.size() / 2] * 1e3, fl / (ts[ts.size() / 2] * 1e-3) / 1e12, ts[0] * 1e3, maxerr);
+  const int ab_cfg = argc > 6 ? atoi(argv[6]) : 0;
+  if (ab_cfg == 19 && ((T + 31) / 32 != 19 || dh != 64 || causal)) {
+    // the yardstick is instantiated at 19 key blocks only: anywhere else the library would run the default kernel under both names
+    fprintf(stderr, "ab_cfg 19 (the RECOMP yardstick) exists for T = 577 .. 608, dh 64, not causal only: no A/B at T = %d dh = %d causal = %d\n", T, dh, causal);
+    return 2;
+  }
+  if (ab_cfg > 0 && !(getenv("CLIPX_LIB") && strstr(getenv("CLIPX_LIB"), "ablate"))) {
+    fprintf(stderr, "ab_cfg needs the tools library (CLIPX_LIB=libclipx_ablate.so): the product library has no A/B configurations\n");
+    return 2;
+  }
+  if (ab_cfg > 0) {
+    const int rounds = 9, per = 20;
+    std::vector<float> med[2];
+    std::vector<uint16_t> o2[2] = {std::vector<uint16_t>(no), std::vector<uint16_t>(no)};
+    const std::string cfgs = std::to_string(ab_cfg);
+    for (int r = 0; r < rounds; ++r)
+      for (int c = 0; c < 2; ++c) {
+        if (c) setenv("CLIPX_ATTN_CFG", cfgs.c_str(), 1); else unsetenv("CLIPX_ATTN_CFG");
+        for (int i = 0; i < 3; ++i) if (attn(0, dq, dout, B, T, H, dh, causal, st)) { fprintf(stderr, "attention call failed (cfg %d)\n", c ? ab_cfg : 0); return 2; }
+        std::vector<float> t;
+        for (int i = 0; i < per; ++i) {
+          CK(hipEventRecord(e0, st)); attn(0, dq, dout, B, T, H, dh, causal, st); CK(hipEventRecord(e1, st)); CK(hipEventSynchronize(e1));
+          float ms; CK(hipEventElapsedTime(&ms, e0, e1)); t.push_back(ms);
+        }
+        std::sort(t.begin(), t.end());
+        med[c].push_back(t[t.size() / 2]);
+        if (r == 0) CK(hipMemcpy(o2[c].data(), dout, no * 2, hipMemcpyDeviceToHost));
+      }
+    unsetenv("CLIPX_ATTN_CFG");
+    double dmax = 0; size_t ndiff = 0;
+    for (size_t i = 0; i < no; ++i) { const double d = fabs(bf2f(o2[0][i]) - bf2f(o2[1][i])); dmax = std::max(dmax, d); ndiff += o2[0][i] != o2[1][i]; }
+    for (int c = 0; c < 2; ++c) {
+      std::sort(med[c].begin(), med[c].end());
+      const double m = med[c][med[c].size() / 2];
+      printf("  A/B %s: median of %d round medians %.1f us (%.1f TFLOP/s), spread %.1f .. %.1f us\n", c ? ("cfg " + cfgs).c_str() : "default",
+             rounds, m * 1e3, fl / (m * 1e-3) / 1e12, med[c].front() * 1e3, med[c].back() * 1e3);
+    }
+    printf("  A/B outputs: max |default - cfg %d| = %.4g, %zu of %zu bf16 values differ\n", ab_cfg, dmax, ndiff, no);
+    if (dmax > 0.02) return 1;
+  }
   typedef int (*dbg_fn)(long long*, int);
   dbg_fn dbgf = (dbg_fn)dlsym(h, "clipx_dbg_attn_phase");
   if (dbgf && getenv("CLIPX_ATTN_CFG") && atoi(getenv("CLIPX_ATTN_CFG")) == 9) {

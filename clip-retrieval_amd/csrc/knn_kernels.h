@@ -247,4 +247,39 @@ hipError_t launch_pq_scatter_codes(const uint8_t* src, int64_t n, int M, const i
                                    const unsigned* tile0, int64_t id_lo, int64_t n_ids, uint8_t* codes, int64_t* idmap, uint32_t* inv,
                                    hipStream_t st);
 
+// ---- IVF-SQ8 (knn_sq_kernels.hip): faiss IndexIVFScalarQuantizer(IndexFlatIP(d), d, nlist, QT_8bit), inner product, not residual.
+// One code byte per column in the list-sorted, tile-padded arena; vmin / scale / step: device f32 [d] (include/knnx.h: "IVF-SQ8").
+constexpr int SQ_BURST = 8;  // dwordx4 loads a lane of the list scan keeps in flight per burst (256 columns)
+// u [nq][d] = q * step scaled by a power of two per query, in the scan's column order (input of launch_prep_blocks); bq [nq] = <q, vmin
+// + step / 2>; inv [nq] = the inverse of the power
+hipError_t launch_sq_prep(const float* q_dev, int nq, int d, const float* vmin, const float* step, float* u, float* bq, float* inv,
+                          hipStream_t st);
+// the list scan of one multi-block pass: the IVF mode-0 fields of ScanArgs with the code arena in place of the rows
+struct SqScanArgs {
+  const uint8_t* codes;
+  int d;
+  const _Float16* qfrag;  // [nblk][d * 64] fragment images of u
+  const float* bq;        // [32 nblk]
+  const float* inv;       // [32 nblk]
+  int nq, k, cap, grid;
+  int* thr_g;
+  float* part_s;
+  uint32_t* part_i;
+  int* part_n;
+  const uint4* work;
+  const unsigned* nwork;
+  int nblk;
+  unsigned work_stride;
+};
+hipError_t launch_sq_scan(const SqScanArgs& a, hipStream_t st);
+// encode n fp16 rows into their arena slots (tile0 == null: slot = i; idmap == null: codes only), laying down idmap / inv like launch_ivf_scatter
+hipError_t launch_sq_encode(const _Float16* src, int64_t n, int d, const int32_t* lists, const int32_t* pos, const int64_t* ids,
+                            int64_t id0, const unsigned* tile0, int64_t id_lo, int64_t n_ids, const float* vmin, const float* scale,
+                            uint8_t* codes, int64_t* idmap, uint32_t* inv, hipStream_t st);
+// out [n][d] = the decoded rows of n ids through inv; an id outside the index (-1) -> 0xFF bytes
+hipError_t launch_sq_decode(const uint8_t* codes, int d, const float* vmin, const float* step, int64_t id_lo, int64_t n_ids,
+                            const uint32_t* inv, const int64_t* ids, int64_t n, float* out, hipStream_t st);
+// per-column min / max of n fp16 rows (d <= 1024) -> vmin_dev / vmax_dev f32 [d]; enc: 2 d ints of device scratch
+hipError_t launch_sq_colminmax(const _Float16* X, int64_t n, int d, int* enc, float* vmin_dev, float* vmax_dev, hipStream_t st);
+
 }  // namespace knnx

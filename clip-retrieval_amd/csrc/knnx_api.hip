@@ -120,6 +120,7 @@ extern "C" int knnx_reset(knnx_index* ix) {
   if (!ix) return fail(KNNX_E_ARG, "index is null");
   std::lock_guard<std::mutex> lk(ix->mu);
   if (ix->pq.m) return fail(KNNX_E_STATE, "reset of an IVF-PQ index is not supported (destroy it instead)");
+  if (ix->sq.on) return fail(KNNX_E_STATE, "reset of an IVF-SQ8 index is not supported (destroy it instead)");
   if (ix->ivf_nlist || ix->ivfb.nlist) return fail(KNNX_E_STATE, "reset of an IVF index is not supported (destroy it instead)");
   if (set_dev(ix)) return KNNX_E_HIP;
   HIPCHK(hipStreamSynchronize(ix->stream));
@@ -164,6 +165,7 @@ extern "C" int knnx_reserve(knnx_index* ix, int64_t n_rows) {
   std::lock_guard<std::mutex> lk(ix->mu);
   if (set_dev(ix)) return KNNX_E_HIP;
   if (ix->pq.m) return fail(KNNX_E_STATE, "reserve on an IVF-PQ index (its arena is sized by knnx_ivf_begin)");
+  if (ix->sq.on) return fail(KNNX_E_STATE, "reserve on an IVF-SQ8 index (its arena is sized by knnx_ivf_begin)");
   return grow(ix, n_rows);
 }
 
@@ -174,6 +176,7 @@ static int add_common(knnx_index* ix, const void* rows, int64_t n, bool is_f32) 
   if (set_dev(ix)) return KNNX_E_HIP;
   if (ix->rows.borrowed) return fail(KNNX_E_STATE, "add() on an index that borrows device rows");
   if (ix->pq.m) return fail(KNNX_E_STATE, "add() on an IVF-PQ index (rows are encoded by knnx_ivf_begin / knnx_ivf_add_assigned / knnx_ivf_end)");
+  if (ix->sq.on) return fail(KNNX_E_STATE, "add() on an IVF-SQ8 index (rows are encoded by knnx_ivf_begin / knnx_ivf_add_assigned / knnx_ivf_end)");
   if (ix->ivf_nlist) return fail(KNNX_E_STATE, "add() after knnx_ivf_set_lists (rebuild the index instead)");
   if (ix->ntotal + n > ix->capacity) {
     int64_t want = std::max<int64_t>(ix->ntotal + n, ix->capacity + ix->capacity / 2);
@@ -214,6 +217,7 @@ extern "C" int knnx_attach_device_f16(knnx_index* ix, const void* dev_rows, int6
   if (!ix || !dev_rows || n < 0) return fail(KNNX_E_ARG, "bad attach arguments");
   std::lock_guard<std::mutex> lk(ix->mu);
   if (ix->pq.m) return fail(KNNX_E_STATE, "attach on an IVF-PQ index");
+  if (ix->sq.on) return fail(KNNX_E_STATE, "attach on an IVF-SQ8 index");
   if (ix->rows && !ix->rows.borrowed) return fail(KNNX_E_STATE, "index already owns rows");
   if (n > (int64_t)0xffffffffll) return fail(KNNX_E_UNSUPPORTED, "more than 2^32 rows per device");
   ix->rows.borrow(dev_rows);
@@ -233,6 +237,7 @@ extern "C" int knnx_synth_fill(knnx_index* ix, int64_t n, uint64_t seed) {
   std::lock_guard<std::mutex> lk(ix->mu);
   if (set_dev(ix)) return KNNX_E_HIP;
   if (ix->pq.m) return fail(KNNX_E_STATE, "synth_fill on an IVF-PQ index");
+  if (ix->sq.on) return fail(KNNX_E_STATE, "synth_fill on an IVF-SQ8 index");
   if (!ix->rows.borrowed) {
     int r = grow(ix, n);
     if (r) return r;
@@ -652,7 +657,7 @@ static int scan_topk_i8(knnx_index* ix, const float* q_dev, int nq, int k, float
 
 // ---- the dispatch policy: which scan serves the next step of `remaining` queries, and how many of them it takes.  The ONE place
 // that decides; step_queries (how many queries the host entry point stages) and scan_step (what runs) both ask here.
-enum class Scan { PQ, IVF_MULTI, I8, RQ, WIDE, EXACT };
+enum class Scan { PQ, SQ, IVF_MULTI, I8, RQ, WIDE, EXACT };
 struct Step {
   Scan kind;
   int nq;
@@ -660,6 +665,8 @@ struct Step {
 };
 static Step choose_step(const knnx_index* ix, int remaining, int k) {
   if (ix->pq.m) return {Scan::PQ, std::min(PQ_PASS, remaining), false};  // IVF-PQ: its own pass, dispatched beside the fp16 scans
+  // IVF-SQ8: always its multi-block pass (one block for <= 32 queries; a block needs a workgroup of its own: KNNX_GRID can set few)
+  if (ix->sq.on) return {Scan::SQ, std::min(KNN_NQ * std::max(1, std::min(IVFM_BLK, ix->n_cu)), remaining), false};
   if (ivfm_usable(ix, remaining, k)) return {Scan::IVF_MULTI, std::min(IVFM_BLK * KNN_NQ, remaining), false};
   const bool i8 = i8_usable(ix, remaining, k);
   // (two planes: four waves x 32 = 128 queries per int8 pass -- a batch of more goes to the fp16 register-stationary pass, 36 ms for
@@ -689,6 +696,7 @@ static int scan_step(knnx_index* ix, const float* q_dev, int remaining, int k, f
     *taken = s.nq;
     switch (s.kind) {
       case Scan::PQ: return scan_topk_pq(ix, q_dev, s.nq, k, D_out, I_out, st);
+      case Scan::SQ: return scan_topk_sq(ix, q_dev, s.nq, k, D_out, I_out, st);
       case Scan::IVF_MULTI: return scan_topk_ivf_multi(ix, q_dev, s.nq, k, D_out, I_out, st);
       case Scan::I8: return scan_topk_i8(ix, q_dev, s.nq, k, D_out, I_out, st);
       case Scan::RQ: return scan_topk_rq(ix, q_dev, s.nq, k, D_out, I_out, st);
@@ -729,7 +737,8 @@ extern "C" int knnx_i8_dominant(knnx_index* ix, int* cols4) {
 extern "C" int knnx_search_device(knnx_index* ix, const float* q_dev, int n, int k, float* D_dev, int64_t* I_dev,
                                   void* stream) {
   if (!ix || !q_dev || !D_dev || !I_dev || n < 0 || k <= 0) return fail(KNNX_E_ARG, "bad search arguments");
-  if (k > KNNX_MAX_K_FAST) return fail(KNNX_E_UNSUPPORTED, "device-buffer search supports k <= 64");
+  if (k > KNNX_MAX_K_FAST)
+    return fail(KNNX_E_UNSUPPORTED, ix->sq.on ? "k > 64 is not supported on an IVF-SQ8 index" : "device-buffer search supports k <= 64");
   std::lock_guard<std::mutex> lk(ix->mu);
   if (set_dev(ix)) return KNNX_E_HIP;
   hipStream_t st = stream ? (hipStream_t)stream : ix->stream;
@@ -866,7 +875,8 @@ static int co_run_batch_locked(knnx_index* ix, std::vector<CoReq*>& b) {
     HIPCHK(hipMemcpyAsync(ids_dev, ix->pin.p, (size_t)nrow * sizeof(int64_t), hipMemcpyHostToDevice, st));
     HIPCHK(hipStreamSynchronize(st));  // the pinned buffer is reused below
     if (ix->pq.m && (r = pq_decode_rows(ix, ids_dev, nrow, rows_dev, st))) return r;
-    hipError_t e = ix->pq.m ? hipSuccess
+    if (ix->sq.on && (r = sq_decode_rows(ix, ids_dev, nrow, rows_dev, st))) return r;
+    hipError_t e = (ix->pq.m || ix->sq.on) ? hipSuccess
                    : ix->ivf_nlist ? launch_gather_inv(ix->rows, d, ix->id_base, ix->ntotal, ix->ivf.inv, ids_dev, nrow, rows_dev, st)
                                    : launch_gather(ix->rows, ix->ntotal, d, ix->id_base, ids_dev, nrow, rows_dev, st);
     if (e != hipSuccess) return fail(KNNX_E_HIP, std::string("coalesced gather: ") + hipGetErrorString(e));
@@ -997,6 +1007,7 @@ extern "C" int knnx_search(knnx_index* ix, const float* q, int n, int k, float* 
     std::lock_guard<std::mutex> lk(ix->mu);
     if (!ix->pq.threshold_scan) return fail(KNNX_E_UNSUPPORTED, "k > 64 is not supported on an IVF-PQ index");
   }
+  if (ix->sq.on && k > KNNX_MAX_K_FAST) return fail(KNNX_E_UNSUPPORTED, "k > 64 is not supported on an IVF-SQ8 index");
   if (n == 0) return KNNX_OK;
   if (n == 1 && k <= KNNX_MAX_K_FAST && ix->co.on) {  // concurrent single-query callers share one scan
     CoReq me{q, k, D, I, R, false, 0.f, nullptr, 0, nullptr};
@@ -1036,8 +1047,9 @@ extern "C" int knnx_reconstruct(knnx_index* ix, const int64_t* ids, int64_t n, f
     memcpy(ids_pin, ids + o, (size_t)m * sizeof(int64_t));
     e = hipMemcpyAsync(ids_dev, ids_pin, (size_t)m * sizeof(int64_t), hipMemcpyHostToDevice, ix->stream);
     if (e == hipSuccess && ix->pq.m && (r = pq_decode_rows(ix, ids_dev, m, out_dev, ix->stream))) return r;
+    if (e == hipSuccess && ix->sq.on && (r = sq_decode_rows(ix, ids_dev, m, out_dev, ix->stream))) return r;
     if (e == hipSuccess)
-      e = ix->pq.m ? hipSuccess
+      e = (ix->pq.m || ix->sq.on) ? hipSuccess
           : ix->ivf_nlist ? launch_gather_inv(ix->rows, ix->d, ix->id_base, ix->ntotal, ix->ivf.inv, ids_dev, m, out_dev, ix->stream)
                           : launch_gather(ix->rows, ix->ntotal, ix->d, ix->id_base, ids_dev, m, out_dev, ix->stream);
     if (e == hipSuccess)

@@ -1,5 +1,5 @@
 // knnx_host.h -- shared by the HOST translation units of the search half (knnx_api / knnx_range / knnx_ivf / knnx_ivfpq /
-// knnx_sharded .hip): the error helpers, the owners of device memory, pinned memory, streams and events, the index object
+// knnx_ivfsq / knnx_sharded .hip): the error helpers, the owners of device memory, pinned memory, streams and events, the index object
 // with its state grouped by the scan that uses it, and the handful of functions one file calls in another.  The kernel
 // files include knn_kernels.h only.
 //
@@ -463,6 +463,32 @@ struct PqScratch {
   }
 };
 
+// IVF-SQ8 (knnx_ivfsq_set_quantizer before knnx_ivf_begin; knn_sq_kernels.hip, knnx_ivfsq.hip): the arena holds d code bytes per row,
+// list-sorted and tile-padded like the IVF-Flat rows (`rows` stays null); layout, coarse quantiser and probe rule are the IVF ones
+struct SqData {
+  bool on = false;
+  std::vector<float> vmin_h, vdiff_h;    // the quantiser as it was given (knnx_ivfsq_get_quantizer, knnx_shards_adopt)
+  DevBuf<float> vmin, scale, step;       // [d]; scale = 255 / vdiff and step = vdiff / 255 from the host, 0 where vdiff == 0
+  DevBuf<uint8_t> codes;                 // [capacity][d]
+  std::vector<unsigned> tile0_h, size_h; // host copy of the layout (knnx_ivfsq_get_codes)
+};
+// one IVF-SQ8 pass of up to IVFM_BLK x 32 queries (next to IvfMultiScratch, which serves its coarse half); allocated on first use
+struct SqScratch {
+  DevBuf<float> u;         // [256][d] q * step, scaled, in the scan's column order
+  DevBuf<_Float16> qfrag;  // [IVFM_BLK][d * 64] its fragment images
+  DevBuf<float> bq, inv;   // [256] bias and inverse scale of every query
+  hipError_t alloc(int d) {
+    if (u) return hipSuccess;
+    hipError_t e = hipSuccess;
+    dev_alloc(e, u, (size_t)IVFM_BLK * KNN_NQ * d);
+    dev_alloc(e, qfrag, (size_t)IVFM_BLK * d * 64);
+    dev_alloc(e, bq, (size_t)IVFM_BLK * KNN_NQ);
+    dev_alloc(e, inv, (size_t)IVFM_BLK * KNN_NQ);
+    if (e != hipSuccess) *this = SqScratch();
+    return e;
+  }
+};
+
 // list-ordered ids (knnx_ivf.hip: knnx_ivf_id_order / knnx_ivf_map_ids; include/knnx.h "List-ordered ids").  Empty until the first call.
 // The layout it reads (ivf.tile0 / size / idmap / inv) does not change once the index is built, so this group has a mutex and a stream
 // of its own: a translation on the request path never queues behind the scans that hold knnx_index::mu.
@@ -574,6 +600,8 @@ struct knnx_index {
   IvfBuild ivfb;
   PqData pq;
   PqScratch pqs;
+  SqData sq;
+  SqScratch sqs;
   IdOrder ido;
 
   // a proof-based scan that skipped its fallback (see WideScratch) says so here: 1 = rq.need / rq.gate, 2 = wide.need / wide.gate
@@ -607,6 +635,7 @@ int search_large_k_pq_locked(knnx_index* ix, const float* q, int n, int k, float
 int ivf_build_worklist(knnx_index* ix, const float* q_dev, int nq, hipStream_t st, const unsigned* gate);
 bool ivfm_usable(const knnx_index* ix, int nq, int k);
 int ivfm_alloc(knnx_index* ix);
+int ivfm_coarse_worklists(knnx_index* ix, const float* q_dev, int nq, int nblk, int grid, int* thr_f_or_null, hipStream_t st);
 int scan_topk_ivf_multi(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out, int64_t* I_out, hipStream_t st);
 bool ivfb_claim_all(knnx_index* ix, const int32_t* lists, const int32_t* pos, int64_t n);
 // knnx_ivfpq.hip
@@ -619,6 +648,11 @@ int pq_pass_threshold_scan(knnx_index* ix, int nq, int np, const float* thr_h, u
 // decoded rows of n ids (device) -> out f32 [n][d] in the ORIGINAL space (back-rotated when the index has a rotation; scratch slot 5);
 // on an index with a refine store: the stored rows themselves
 int pq_decode_rows(knnx_index* ix, const int64_t* ids_dev, int64_t n, float* out_dev, hipStream_t st);
+
+// knnx_ivfsq.hip
+int scan_topk_sq(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out, int64_t* I_out, hipStream_t st);
+// decoded rows of n ids (device) -> out f32 [n][d]; -1 -> 0xFF bytes
+int sq_decode_rows(knnx_index* ix, const int64_t* ids_dev, int64_t n, float* out_dev, hipStream_t st);
 
 // the int8 copy is an accelerator, not data: whoever needs device memory and cannot get it takes the copy's back and tries once more
 // (the lazily built copy must not starve the range pools / large-k scratch that fitted before it existed)

@@ -68,15 +68,12 @@ int ivfm_alloc(knnx_index* ix) {
   return 1;
 }
 
-// one pass of 1 .. 32 IVFM_BLK queries already in HBM
-int scan_topk_ivf_multi(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out, int64_t* I_out, hipStream_t st) {
-  const int cap = scan_cap(ix->d, k);
-  const int nblk = (nq + KNN_NQ - 1) / KNN_NQ;
-  const int grid = std::max(1, ix->n_cu / nblk) * nblk;  // (part_* hold n_cu x 64 lists: grid <= n_cu whenever n_cu >= nblk)
-  if (cap < 0 || nblk > IVFM_BLK || grid > std::max(ix->n_cu, nblk)) return fail(KNNX_E_STATE, "internal: multi-block IVF pass misuse");
+// the coarse half of a multi-block pass (IVF-Flat below, IVF-SQ8 in knnx_ivfsq.hip): fragments of nq queries in nblk blocks (thr_c and,
+// when given, thr_f reset), the centroid scores, the nprobe best lists of every query, the blocks' work lists in ix->ivfm
+int ivfm_coarse_worklists(knnx_index* ix, const float* q_dev, int nq, int nblk, int grid, int* thr_f_or_null, hipStream_t st) {
   knnx_index* c = ix->cent;
   const int np = std::min(ix->ivf_nprobe, ix->ivf_nlist);
-  HIPCHK(launch_prep_blocks(q_dev, nq, ix->d, ix->ivfm.qfrag, ix->ivfm.thr_c, ix->ivfm.thr_f, st));
+  HIPCHK(launch_prep_blocks(q_dev, nq, ix->d, ix->ivfm.qfrag, ix->ivfm.thr_c, thr_f_or_null, st));
   // coarse quantiser: ONE scan over the centroid rows dumps every block's scores (mode 2: no queues -- a top-nprobe queue scan of
   // 65 536 centroids spends its time pruning cold queues: 245 us for two blocks, profiles/r06k_*), a radix select marks the nprobe
   // best lists of every query (knn_kernels.hip: ivf_select_mark_kernel), whatever nprobe is
@@ -99,6 +96,17 @@ int scan_topk_ivf_multi(knnx_index* ix, const float* q_dev, int nq, int k, float
                                          ix->ivf.size, ix->ivfm.off, ix->ivfm.work, ix->ivfm.nwork, st, ix->ivfm.stride));
   if (ix->prof.on)  // tiles of the union of the blocks' lists (what one pass over shared lists would read): knnx_ivf_last_scan_tiles
     HIPCHK(launch_ivf_union_tiles(ix->ivfm.masks, nblk, ix->ivf_nlist, ix->ivf.ntile, ix->ivfm.nwork + IVFM_BLK, st));
+  return 0;
+}
+
+// one pass of 1 .. 32 IVFM_BLK queries already in HBM
+int scan_topk_ivf_multi(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out, int64_t* I_out, hipStream_t st) {
+  const int cap = scan_cap(ix->d, k);
+  const int nblk = (nq + KNN_NQ - 1) / KNN_NQ;
+  const int grid = std::max(1, ix->n_cu / nblk) * nblk;  // (part_* hold n_cu x 64 lists: grid <= n_cu whenever n_cu >= nblk)
+  if (cap < 0 || nblk > IVFM_BLK || grid > std::max(ix->n_cu, nblk)) return fail(KNNX_E_STATE, "internal: multi-block IVF pass misuse");
+  int r = ivfm_coarse_worklists(ix, q_dev, nq, nblk, grid, ix->ivfm.thr_f, st);
+  if (r) return r;
   ScanArgs a{};
   a.X = ix->rows;
   a.N = ix->capacity;
@@ -186,6 +194,7 @@ extern "C" int knnx_ivf_set_lists(knnx_index* ix, int nlist, const uint16_t* cen
   if (set_dev(ix)) return KNNX_E_HIP;
   if (ix->rows.borrowed) return fail(KNNX_E_STATE, "IVF needs an index that owns its rows");
   if (ix->pq.m) return fail(KNNX_E_STATE, "an IVF-PQ index is built through knnx_ivf_begin / knnx_ivf_add_assigned / knnx_ivf_end");
+  if (ix->sq.on) return fail(KNNX_E_STATE, "an IVF-SQ8 index is built through knnx_ivf_begin / knnx_ivf_add_assigned / knnx_ivf_end");
   if (ix->ivf_nlist) return fail(KNNX_E_STATE, "lists are already set");
   TileLayout t;
   int r = ivf_tile_layout(nlist, list_sizes, t);
@@ -479,6 +488,9 @@ extern "C" int knnx_ivf_begin(knnx_index* ix, int nlist, const uint16_t* centroi
       if (e == hipSuccess) e = malloc_or_reclaim(ix, ix->rows, (size_t)prow * ix->d);
       if (e == hipSuccess) e = hipMemsetAsync(ix->rows, 0, (size_t)prow * ix->d * sizeof(_Float16), ix->stream);
     }
+  } else if (ix->sq.on) {  // IVF-SQ8: d code bytes per arena row (pad rows are zero)
+    dev_alloc(e, ix->sq.codes, (size_t)prow * ix->d);
+    if (e == hipSuccess) e = hipMemsetAsync(ix->sq.codes, 0, (size_t)prow * ix->d, ix->stream);
   } else {
     dev_alloc(e, ix->rows, (size_t)prow * ix->d);
     if (e == hipSuccess) e = hipMemsetAsync(ix->rows, 0, (size_t)prow * ix->d * sizeof(_Float16), ix->stream);  // pad rows are zero
@@ -498,6 +510,7 @@ extern "C" int knnx_ivf_begin(knnx_index* ix, int nlist, const uint16_t* centroi
     ix->rows.reset();
     ix->pq.codes.reset();
     ix->pq.bcent.reset();
+    ix->sq.codes.reset();
     return fail(e == hipErrorOutOfMemory ? KNNX_E_NOMEM : KNNX_E_HIP, std::string("ivf_begin: ") + hipGetErrorString(e));
   }
   ix->capacity = prow;
@@ -576,6 +589,9 @@ extern "C" int knnx_ivf_add_assigned(knnx_index* ix, const uint16_t* rows_f16, i
       HIPCHK(launch_pq_encode(ix->pq.rot ? ix->ivfb.rot.p : ix->ivfb.rows.p, m, pq_dq(ix), ix->pq.m, ix->ivfb.lists, ix->pq.bcent, ix->pq.cb,
                               ix->ivf.tile0, ix->ivfb.pos, ix->ivfb.ids, 0, ix->id_base, ix->ivfb.total,
                               ix->pq.codes, ix->ivf.idmap, ix->ivf.inv, ix->stream));
+    } else if (ix->sq.on) {  // IVF-SQ8: the rows are encoded into their slots
+      HIPCHK(launch_sq_encode(ix->ivfb.rows, m, ix->d, ix->ivfb.lists, ix->ivfb.pos, ix->ivfb.ids, 0, ix->ivf.tile0, ix->id_base,
+                              ix->ivfb.total, ix->sq.vmin, ix->sq.scale, ix->sq.codes, ix->ivf.idmap, ix->ivf.inv, ix->stream));
     } else {
       HIPCHK(launch_ivf_scatter(ix->ivfb.rows, m, ix->d, ix->ivfb.lists, ix->ivfb.pos,
                                 ix->ivfb.ids, 0, ix->ivf.tile0, ix->id_base, ix->ivfb.total, ix->rows, ix->ivf.idmap,
@@ -641,6 +657,9 @@ extern "C" int knnx_ivf_add_assigned_device(knnx_index* ix, const void* rows_dev
       if (ix->pq.rot) HIPCHK(launch_rotate_f16(ix->pq.rot_w, ix->d, pq_dq(ix), src, m, ix->ivfb.rot, ix->stream));
       HIPCHK(launch_pq_encode(ix->pq.rot ? ix->ivfb.rot.p : src, m, pq_dq(ix), ix->pq.m, lists_dev + o, ix->pq.bcent, ix->pq.cb, ix->ivf.tile0, ix->ivfb.pos,
                               nullptr, id0 + o, ix->id_base, ix->ivfb.total, ix->pq.codes, ix->ivf.idmap, ix->ivf.inv, ix->stream));
+    } else if (ix->sq.on) {
+      HIPCHK(launch_sq_encode(src, m, ix->d, lists_dev + o, ix->ivfb.pos, nullptr, id0 + o, ix->ivf.tile0, ix->id_base, ix->ivfb.total,
+                              ix->sq.vmin, ix->sq.scale, ix->sq.codes, ix->ivf.idmap, ix->ivf.inv, ix->stream));
     } else {
       HIPCHK(launch_ivf_scatter(src, m, ix->d, lists_dev + o, ix->ivfb.pos, nullptr, id0 + o, ix->ivf.tile0, ix->id_base,
                                 ix->ivfb.total, ix->rows, ix->ivf.idmap, ix->ivf.inv, ix->stream));
@@ -669,6 +688,10 @@ extern "C" int knnx_ivf_end(knnx_index* ix) {
       ix->pq.slab_np = 0;  // (M = 256: the slab width is recomputed from these sizes)
       ix->pq.bcent.reset();
       ix->pq.rot_w.reset();
+    }
+    if (ix->sq.on) {
+      ix->sq.tile0_h.assign(ix->ivfb.tile0.begin(), ix->ivfb.tile0.end());
+      ix->sq.size_h.assign(ix->ivfb.size.begin(), ix->ivfb.size.end());
     }
     std::vector<uint32_t>().swap(ix->ivfb.size);
     std::vector<uint32_t>().swap(ix->ivfb.fill);

@@ -288,6 +288,7 @@ extern "C" int knnx_ivfpq_set_quantizer(knnx_index* ix, int M, const float* code
   if (!pq_supported(dq, M)) return fail(KNNX_E_ARG, PQ_M_RULE);
   std::lock_guard<std::mutex> lk(ix->mu);
   if (set_dev(ix)) return KNNX_E_HIP;
+  if (ix->sq.on) return fail(KNNX_E_STATE, "the PQ quantizer cannot be set on an IVF-SQ8 index");
   if (ix->rows.borrowed || ix->ntotal != 0 || ix->ivf_nlist || ix->ivfb.nlist || ix->pq.m)
     return fail(KNNX_E_STATE, "the PQ quantizer is set once, on an empty index, before knnx_ivf_begin");
   const size_t bytes = (size_t)256 * dq * sizeof(float);

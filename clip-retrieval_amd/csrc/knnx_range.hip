@@ -219,8 +219,9 @@ static int range_scan_pq(knnx_index* ix, const float* q_host, int nq, float thr,
   }
 }
 
-// what an IVF-PQ index answers to a range_search it does not serve (0: it serves it, or is no IVF-PQ index).  Caller holds ix->mu.
+// what an IVF-PQ or IVF-SQ8 index answers to a range_search it does not serve (0: it serves it, or is neither).  Caller holds ix->mu.
 static int pq_range_refusal(const knnx_index* ix) {
+  if (ix->sq.on) return fail(KNNX_E_UNSUPPORTED, "range_search is not supported on an IVF-SQ8 index");
   if (!ix->pq.m) return 0;
   if (!ix->pq.threshold_scan) return fail(KNNX_E_UNSUPPORTED, "range_search is not supported on an IVF-PQ index");
   if (ix->pq.refine)

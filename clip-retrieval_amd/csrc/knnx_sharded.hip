@@ -213,6 +213,14 @@ extern "C" int knnx_shards_adopt(int n_shards, knnx_index* const* shards, const 
   for (int g = 1; g < n_shards; ++g)
     if (shards[g]->pq.refine != shards[0]->pq.refine)
       return fail(KNNX_E_ARG, "IVF-PQ shards with and without a refine store cannot be mixed");
+  // IVF-SQ8 shards decode with one quantiser (bit for bit), and an IVF-SQ8 shard does not mix with any other kind
+  for (int g = 1; g < n_shards; ++g) {
+    if (shards[g]->sq.on != shards[0]->sq.on) return fail(KNNX_E_ARG, "IVF-SQ8 shards cannot be mixed with shards of another kind");
+    if (shards[0]->sq.on &&
+        (memcmp(shards[g]->sq.vmin_h.data(), shards[0]->sq.vmin_h.data(), (size_t)d * sizeof(float)) != 0 ||
+         memcmp(shards[g]->sq.vdiff_h.data(), shards[0]->sq.vdiff_h.data(), (size_t)d * sizeof(float)) != 0))
+      return fail(KNNX_E_ARG, "IVF-SQ8 shards carry different quantisers (vmin / vdiff must agree bit for bit)");
+  }
   knnx_shards* s = new knnx_shards();
   s->d = d;
   s->sh.resize(n_shards);

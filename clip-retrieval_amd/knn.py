@@ -343,6 +343,40 @@ class Mi355xIndex(_FaissShaped):
         order = np.argsort(ids, kind="stable")
         return np.ascontiguousarray(codes[order]), np.ascontiguousarray(lists[order])
 
+    # ------------------------------------------------------------------ IVF-SQ8
+    def set_sq_quantizer(self, vmin, vdiff):
+        """Make this EMPTY index an IVF-SQ8 one (faiss IndexIVFScalarQuantizer(IndexFlatIP(d), d, nlist, QT_8bit), not residual):
+        vmin, vdiff f32 [d] (train_sq_ranges), one code byte per dimension.  The rows then go in through knnx_ivf_begin / add_assigned
+        / end (build_ivfsq_index*), which encode them (include/knnx.h: "IVF-SQ8").  Padding columns get vmin = vdiff = 0."""
+        vmin = np.asarray(vmin, dtype=np.float32).reshape(-1)
+        vdiff = np.asarray(vdiff, dtype=np.float32).reshape(-1)
+        if vmin.shape != (self.d,) or vdiff.shape != (self.d,):
+            raise AssertionError(f"vmin and vdiff must be [{self.d}], got {vmin.shape} and {vdiff.shape}")
+        a, b = np.zeros(self._dpad, dtype=np.float32), np.zeros(self._dpad, dtype=np.float32)
+        a[: self.d], b[: self.d] = vmin, vdiff
+        check(self._lib, self._lib.knnx_ivfsq_set_quantizer(self._h, a.ctypes.data, b.ctypes.data), "knnx")
+
+    @property
+    def is_sq(self):
+        """True on an IVF-SQ8 index."""
+        return bool(self._lib.knnx_ivfsq(self._h)) if self._h else False
+
+    def sq_quantizer(self):
+        """(vmin, vdiff) f32 [d] as they were given."""
+        a, b = np.empty(self._dpad, dtype=np.float32), np.empty(self._dpad, dtype=np.float32)
+        check(self._lib, self._lib.knnx_ivfsq_get_quantizer(self._h, a.ctypes.data, b.ctypes.data), "knnx")
+        return np.ascontiguousarray(a[: self.d]), np.ascontiguousarray(b[: self.d])
+
+    def sq_codes(self):
+        """(codes u8 [ntotal, d], lists int32 [ntotal]) in id order: row i belongs to id id_base + i."""
+        n = self.ntotal
+        ids = np.empty(n, dtype=np.int64)
+        lists = np.empty(n, dtype=np.int32)
+        codes = np.empty((n, self._dpad), dtype=np.uint8)
+        check(self._lib, self._lib.knnx_ivfsq_get_codes(self._h, ids.ctypes.data, lists.ctypes.data, codes.ctypes.data), "knnx")
+        order = np.argsort(ids, kind="stable")
+        return np.ascontiguousarray(codes[order][:, : self.d]), np.ascontiguousarray(lists[order])
+
     # ------------------------------------------------------------------ list-ordered ids (reorder_metadata_by_ivf_index)
     def ivf_old_to_new(self):
         """int64 [ntotal]: old_to_new[i] = id_base + the list-ordered ordinal of the row with id id_base + i (include/knnx.h,
@@ -679,7 +713,8 @@ def embedding_files(folder):
 
 def load_index(path, device=0, row_range=None, enable_faiss_memory_mapping=False, devices=None, embeddings_folder=None):  # pylint: disable=unused-argument
     """Build an HBM-resident flat index from a folder of fp16 `.npy` partitions -- or, when `path` is a folder written by
-    `save_index()` (it holds ivf_manifest.json), re-create that IVF-Flat index without training or assigning anything.
+    `save_index()` (it holds ivf_manifest.json), re-create that IVF-Flat index without training or assigning anything; a folder
+    with ivf_pq_manifest.json / ivf_sq_manifest.json is read as that IVF-PQ / IVF-SQ8 index, straight from its saved codes.
 
     Takes the place of clip_back.py:589-596 (`faiss.read_index`) for this index type; ids are the global
     row order of the concatenated partitions = the metadata row order (clip_back.py:401-417).
@@ -690,6 +725,8 @@ def load_index(path, device=0, row_range=None, enable_faiss_memory_mapping=False
     """
     if os.path.isfile(os.path.join(path, IVFPQ_MANIFEST)):  # a saved IVF-PQ index: self-contained unless it has a refine store
         return _load_ivfpq_index(path, device=device, row_range=row_range, devices=devices, embeddings_folder=embeddings_folder)
+    if os.path.isfile(os.path.join(path, IVFSQ_MANIFEST)):  # a saved IVF-SQ8 index: self-contained (codes, not rows)
+        return _load_ivfsq_index(path, device=device, row_range=row_range, devices=devices)
     if os.path.isfile(os.path.join(path, IVF_MANIFEST)):  # a built IVF-Flat index saved by save_index(): no k-means, no assignment
         return _load_ivf_index(path, device=device, row_range=row_range, devices=devices)
     src = FolderRows(path)
@@ -1165,6 +1202,8 @@ def save_index(index, folder, embeddings_folder=None):
 
     if getattr(index, "pq_m", 0):
         return _save_ivfpq_index(index, folder, embeddings_folder)
+    if getattr(index, "is_sq", False):
+        return _save_ivfsq_index(index, folder)
     lists, cent = getattr(index, "ivf_lists", None), getattr(index, "ivf_centroids", None)
     src = getattr(index, "ivf_source", None)
     if lists is None or cent is None:
@@ -2041,3 +2080,268 @@ def _load_ivfpq_index(folder, device=0, row_range=None, devices=None, embeddings
     if not slo <= lo <= hi <= shi:
         raise ValueError(f"row_range {row_range} is outside the saved shard's rows [{slo}, {shi})")
     return make(codes[lo - slo:hi - slo], np.asarray(lists[lo - slo:hi - slo]), lo, device)
+
+
+# ------------------------------------------------------------------------------------------------------------
+# IVF-SQ8 (faiss IndexIVFScalarQuantizer(IndexFlatIP(d), d, nlist, QT_8bit, METRIC_INNER_PRODUCT), not residual; the factory string
+# "IVF{nlist},SQ8"): one code byte per dimension (csrc/knn_sq_kernels.hip) -- d + 12 bytes per padded row against IVF-Flat's 2 d + 12,
+# with a ranking that is practically IVF-Flat's.  The coarse quantiser and the list layout are the IVF-Flat ones; the builders mirror
+# the IVF-PQ ones.
+# ------------------------------------------------------------------------------------------------------------
+IVFSQ_MANIFEST = "ivf_sq_manifest.json"
+IVFSQ_FORMAT = "clip-retrieval_amd ivf-sq8 v1"
+
+
+def train_sq_ranges(x, n=None, d=None, device=0, chunk=1 << 20):
+    """The SQ8 quantiser of a training set (faiss ScalarQuantizer RS_minmax with argument 0): per-column (vmin, vdiff = vmax - vmin),
+    f32 [d], by the column min / max kernel (knnx_colminmax_device).  `x`: fp16 rows [n, d] on the host (uploaded chunk by chunk), or
+    the device address of n fp16 rows of width d (then name n and d).  Min and max do not depend on the order of the rows, so the
+    result is that of x.astype(float32).min(0) / .max(0), bit for bit."""
+    lib = load_library()
+    if isinstance(x, (int, np.integer)):
+        n, d = int(n), int(d)
+        vmin, vmax = np.empty(d, dtype=np.float32), np.empty(d, dtype=np.float32)
+        check(lib, lib.knnx_colminmax_device(int(device), C.c_void_p(int(x)), n, d, vmin.ctypes.data, vmax.ctypes.data, None), "knnx")
+        return vmin, vmax - vmin
+    import torch  # pylint: disable=import-outside-toplevel
+
+    x = np.asarray(x)
+    if x.ndim != 2 or x.shape[0] == 0:
+        raise ValueError(f"train_sq_ranges takes rows [n, d] with n > 0, got {x.shape}")
+    d = x.shape[1]
+    vmin, vmax = np.full(d, np.inf, dtype=np.float32), np.full(d, -np.inf, dtype=np.float32)
+    a, b = np.empty(d, dtype=np.float32), np.empty(d, dtype=np.float32)
+    for o in range(0, x.shape[0], chunk):
+        t = torch.from_numpy(np.ascontiguousarray(x[o:o + chunk], dtype=np.float16)).to(f"cuda:{device}")
+        torch.cuda.synchronize(device)
+        check(lib, lib.knnx_colminmax_device(int(device), C.c_void_p(t.data_ptr()), t.shape[0], d, a.ctypes.data, b.ctypes.data, None), "knnx")
+        vmin, vmax = np.minimum(vmin, a), np.maximum(vmax, b)
+        del t
+    return vmin, vmax - vmin
+
+
+def ivfsq_params_from_index_key(key):
+    """The faiss index-factory string "IVF{nlist}[_HNSW32],SQ8" -> {"nlist": nlist}, the keyword argument of build_ivfsq_index*.  The
+    _HNSW32 suffix is accepted and ignored (the coarse quantiser here is flat).  Whatever cannot be served -- another bit width (SQ4,
+    SQ6, SQfp16), a pre-transform, a refine stage -- raises ValueError naming the part.  It parses; it does not choose an index."""
+    import re  # pylint: disable=import-outside-toplevel
+
+    parts = [p.strip() for p in str(key).split(",")]
+    m = re.fullmatch(r"IVF(\d+)(_HNSW\d+)?", parts[0]) if parts else None
+    if not m or int(m.group(1)) < 1:
+        raise ValueError(f"index key part {parts[0] if parts else ''!r}: expected IVF{{nlist}} or IVF{{nlist}}_HNSW32")
+    if len(parts) < 2 or parts[1] != "SQ8":
+        raise ValueError(f"index key part {parts[1] if len(parts) > 1 else ''!r}: expected SQ8 (the 8-bit scalar quantiser is the only one served)")
+    if len(parts) > 2:
+        raise ValueError(f"index key part {parts[2]!r}: not served (IVF and SQ8 parts only)")
+    return {"nlist": int(m.group(1))}
+
+
+def ivfsq_manifest(d, nlist, nprobe, row_range):
+    """The manifest of a saved IVF-SQ8 folder (kind "ivfsq")."""
+    return {"format": IVFSQ_FORMAT, "kind": "ivfsq", "d": int(d), "nlist": int(nlist), "nprobe": int(nprobe),
+            "row_range": [int(row_range[0]), int(row_range[1])]}
+
+
+def check_ivfsq_manifest(man, where=""):
+    """A manifest read back: the format and the kind must be this one's, the numbers consistent.  Returns it."""
+    if man.get("format") != IVFSQ_FORMAT or man.get("kind") != "ivfsq":
+        raise ValueError(f"{where}: unknown index format {man.get('format')!r} / kind {man.get('kind')!r}")
+    lo, hi = man["row_range"]
+    if not (int(man["d"]) > 0 and int(man["nlist"]) > 0 and 0 <= int(lo) <= int(hi) and int(man["nprobe"]) >= 1):
+        raise ValueError(f"{where}: inconsistent IVF-SQ8 manifest {man}")
+    return man
+
+
+def _ivfsq_begin(d, nlist, centroids, ranges, sizes, device, id_base):
+    index = Mi355xIndex(d, device=device, id_base=id_base)
+    index.set_sq_quantizer(*ranges)
+    cpad = np.ascontiguousarray(index._pad(np.asarray(centroids, dtype=np.float16)))  # pylint: disable=protected-access
+    check(index._lib, index._lib.knnx_ivf_begin(index._h, nlist, cpad.ctypes.data, np.ascontiguousarray(sizes, dtype=np.int64).ctypes.data), "knnx")  # pylint: disable=protected-access
+    return index
+
+
+def _ivfsq_end(index, nlist, nprobe, centroids, id_base, n, lists=None):
+    check(index._lib, index._lib.knnx_ivf_end(index._h), "knnx")  # pylint: disable=protected-access
+    index.nprobe = min(int(nprobe), nlist)
+    index.ivf_centroids, index.ivf_row_range = np.asarray(centroids, dtype=np.float16), (int(id_base), int(id_base) + int(n))
+    if lists is not None:
+        index.ivf_lists = lists
+    return index
+
+
+def _ivfsq_encode_chunks(chunks, n, d, nlist, centroids, ranges, lists, nprobe, device, id_base):
+    """Rows (an iterator of (offset, fp16 rows)) -> IVF-SQ8 index: every row is encoded into the next free slot of its list."""
+    sizes = np.bincount(lists, minlength=nlist).astype(np.int64)
+    if sizes.shape[0] != nlist:
+        raise ValueError("a list id is outside [0, nlist)")
+    index = _ivfsq_begin(d, nlist, centroids, ranges, sizes, device, id_base)
+    lib = index._lib  # pylint: disable=protected-access
+    cursor = np.zeros(nlist, dtype=np.int64)
+    for o, x in chunks:
+        rows = np.ascontiguousarray(index._pad(np.asarray(x, dtype=np.float16)))  # pylint: disable=protected-access
+        ls = np.ascontiguousarray(lists[o:o + rows.shape[0]], dtype=np.int32)
+        pos = _positions_in_lists(ls, cursor)
+        ids = np.arange(o, o + rows.shape[0], dtype=np.int64) + id_base
+        check(lib, lib.knnx_ivf_add_assigned(index._h, rows.ctypes.data, rows.shape[0], ids.ctypes.data, ls.ctypes.data, pos.ctypes.data), "knnx")  # pylint: disable=protected-access
+    return _ivfsq_end(index, nlist, nprobe, centroids, id_base, n, lists)
+
+
+def build_ivfsq_index(x_f16, nlist, nprobe=16, niter=8, seed=0, device=0, id_base=0, centroids=None, ranges=None, chunk=1 << 20):
+    """fp16 rows [N, d] -> HBM-resident IVF-SQ8 index (ids = id_base + row number).  `centroids` (fp16 [nlist, d]) and `ranges`
+    ((vmin, vdiff), f32 [d]) can be given; by default both are trained on the rows (train_ivf_centroids, train_sq_ranges).  Lists by
+    the MFMA assignment kernel, codes by the device encoder.  Shards of one index MUST share centroids and ranges."""
+    n, d = x_f16.shape
+    if centroids is None:
+        centroids = train_ivf_centroids(x_f16, nlist, niter=niter, seed=seed, device=device)
+    if ranges is None:
+        ranges = train_sq_ranges(x_f16, device=device, chunk=chunk)
+    centroids = np.asarray(centroids).astype(np.float16)
+    lists, _ = _assign_chunks(((o, x_f16[o:o + chunk]) for o in range(0, n, chunk)), n, d, nlist, centroids, device, None)
+    return _ivfsq_encode_chunks(((o, x_f16[o:o + chunk]) for o in range(0, n, chunk)), n, d, nlist, centroids, ranges, lists, nprobe, device,
+                                id_base)
+
+
+def build_ivfsq_index_from_folder(path, nlist, nprobe=16, niter=8, seed=0, device=0, centroids=None, ranges=None,
+                                  max_points_per_centroid=256, chunk=1 << 20):
+    """`clip inference` output folder (img_emb_*.npy) -> IVF-SQ8 index, streaming the partitions: training on a strided sample of the
+    whole folder (centroids and ranges, unless given), then one assignment pass and one encoding pass.  The result can be
+    save_index()ed: the folder is self-contained (codes, not rows)."""
+    src = path if isinstance(path, FolderRows) else FolderRows(path)
+    if centroids is None or ranges is None:
+        take = min(src.n, int(nlist) * int(max_points_per_centroid))
+        sample = src.take(np.unique(np.linspace(0, src.n - 1, take).astype(np.int64)))
+        if centroids is None:
+            centroids = train_ivf_centroids(sample, nlist, niter=niter, seed=seed, device=device, max_points_per_centroid=max_points_per_centroid)
+        if ranges is None:
+            ranges = train_sq_ranges(sample, device=device, chunk=chunk)
+    centroids = np.asarray(centroids).astype(np.float16)
+    lists, _ = _assign_chunks(src.chunks(0, src.n, chunk), src.n, src.d, nlist, centroids, device, None)
+    return _ivfsq_encode_chunks(src.chunks(0, src.n, chunk), src.n, src.d, nlist, centroids, ranges, lists, nprobe, device, 0)
+
+
+def build_ivfsq_index_device(fill_rows, n, d, nlist, nprobe=16, niter=8, seed=0, device=0, id_base=0, centroids=None, ranges=None,
+                             chunk=1 << 20, alloc=None, points_per_centroid=64, keep_lists=False):
+    """IVF-SQ8 index over n rows PRODUCED ON THE GPU (`fill_rows(dst_ptr, row0, count, stride)` as in build_ivf_index_device, which
+    must have COMPLETED when it returns): the fp16 corpus never exists whole -- a training sample (centroids and ranges, unless
+    given), then per chunk one assignment pass and one encoding pass; the index keeps d bytes per row.  Returns (index, stats dict)."""
+    import time  # pylint: disable=import-outside-toplevel
+
+    assert d % 256 == 0, "device builds take padded rows (d % 256 == 0)"
+    lib = load_library()
+    if alloc is None:
+        def alloc(nbytes):
+            import torch  # pylint: disable=import-outside-toplevel
+
+            t = torch.empty(int(nbytes), dtype=torch.uint8, device=f"cuda:{device}")
+            return t.data_ptr(), t
+    t0 = time.perf_counter()
+    b = IvfBuilder(d, nlist, device)
+    if centroids is None or ranges is None:
+        n_sample = int(min(n, nlist * points_per_centroid))
+        sample_ptr, sample_keep = alloc(n_sample * d * 2)
+        fill_rows(sample_ptr, 0, n_sample, max(1, n // n_sample))
+        if ranges is None:
+            ranges = train_sq_ranges(sample_ptr, n_sample, d, device=device)
+        if centroids is None:
+            train_ivf_centroids_device(b, sample_ptr, n_sample, niter=niter, seed=seed)
+            centroids = np.ascontiguousarray(b.centroids())
+        del sample_keep
+    centroids = np.asarray(centroids).astype(np.float16)
+    b.set_centroids(centroids)
+    _release_cached_device_memory()
+    t1 = time.perf_counter()
+    lists_ptr, lists_keep = alloc(n * 4)
+    rows_ptr, rows_keep = alloc(min(chunk, n) * d * 2)
+    b.list_sizes(reset=True)
+    for o in range(0, n, chunk):
+        m = min(chunk, n - o)
+        fill_rows(rows_ptr, o, m, 1)
+        b.assign_device(rows_ptr, m, lists_ptr + 4 * o)
+    sizes = b.list_sizes()
+    b.close()
+    _release_cached_device_memory()
+    t2 = time.perf_counter()
+    index = _ivfsq_begin(d, nlist, centroids, ranges, sizes, device, id_base)
+    for o in range(0, n, chunk):
+        m = min(chunk, n - o)
+        fill_rows(rows_ptr, o, m, 1)
+        check(lib, lib.knnx_ivf_add_assigned_device(index._h, C.c_void_p(rows_ptr), m, id_base + o, C.c_void_p(lists_ptr + 4 * o)), "knnx")  # pylint: disable=protected-access
+    index = _ivfsq_end(index, nlist, nprobe, centroids, id_base, n, _download_i32(lists_ptr, n, device) if keep_lists else None)
+    del rows_keep, lists_keep
+    _release_cached_device_memory()
+    t3 = time.perf_counter()
+    padded = int(((sizes + 31) // 32 * 32).sum())
+    stats = {"train_s": t1 - t0, "assign_s": t2 - t1, "encode_s": t3 - t2, "list_sizes": sizes, "bytes_per_row": d + 12,
+             "arena_bytes": max(padded, 32) * (d + 12)}
+    return index, stats
+
+
+def _save_ivfsq_index(index, folder):
+    """The self-contained IVF-SQ8 folder: ivf_sq_centroids.npy (fp16 [nlist, d]), ivf_sq_vmin.npy / ivf_sq_vdiff.npy (f32 [d]),
+    ivf_sq_codes.npy (u8 [n, d] in id order), ivf_sq_lists.npy (int32 [n]) and ivf_sq_manifest.json (kind "ivfsq", written last)."""
+    import json  # pylint: disable=import-outside-toplevel
+
+    cent = getattr(index, "ivf_centroids", None)
+    if cent is None:
+        raise ValueError("save_index takes an IVF-SQ8 index built by build_ivfsq_index* / load_index")
+    codes, lists = index.sq_codes()
+    vmin, vdiff = index.sq_quantizer()
+    lo, hi = getattr(index, "ivf_row_range", (0, codes.shape[0]))
+    os.makedirs(folder, exist_ok=True)
+    np.save(os.path.join(folder, "ivf_sq_centroids.npy"), np.asarray(cent, dtype=np.float16))
+    np.save(os.path.join(folder, "ivf_sq_vmin.npy"), vmin)
+    np.save(os.path.join(folder, "ivf_sq_vdiff.npy"), vdiff)
+    np.save(os.path.join(folder, "ivf_sq_codes.npy"), codes)
+    np.save(os.path.join(folder, "ivf_sq_lists.npy"), lists)
+    man = ivfsq_manifest(index.d, cent.shape[0], index.nprobe, (lo, hi))
+    tmp = os.path.join(folder, IVFSQ_MANIFEST + ".part")
+    with open(tmp, "w", encoding="utf-8") as f:
+        json.dump(man, f, indent=1)
+    os.replace(tmp, os.path.join(folder, IVFSQ_MANIFEST))
+    return man
+
+
+def _ivfsq_from_codes(codes, lists, lo, cent, ranges, nprobe, device, chunk=1 << 20):
+    nlist, d = cent.shape
+    n = codes.shape[0]
+    sizes = np.bincount(lists, minlength=nlist).astype(np.int64)
+    index = _ivfsq_begin(d, nlist, cent, ranges, sizes, device, lo)
+    lib = index._lib  # pylint: disable=protected-access
+    cursor = np.zeros(nlist, dtype=np.int64)
+    for o in range(0, n, chunk):
+        c = np.ascontiguousarray(index._pad(np.asarray(codes[o:o + chunk], dtype=np.uint8)))  # pylint: disable=protected-access
+        ls = np.ascontiguousarray(lists[o:o + chunk], dtype=np.int32)
+        pos = _positions_in_lists(ls, cursor)
+        ids = np.arange(lo + o, lo + o + c.shape[0], dtype=np.int64)
+        check(lib, lib.knnx_ivfsq_add_codes(index._h, c.ctypes.data, c.shape[0], ids.ctypes.data, ls.ctypes.data, pos.ctypes.data), "knnx")  # pylint: disable=protected-access
+    return _ivfsq_end(index, nlist, nprobe, cent, lo, n, np.asarray(lists, dtype=np.int32))
+
+
+def _load_ivfsq_index(folder, device=0, row_range=None, devices=None):
+    import json  # pylint: disable=import-outside-toplevel
+
+    with open(os.path.join(folder, IVFSQ_MANIFEST), encoding="utf-8") as f:
+        man = check_ivfsq_manifest(json.load(f), folder)
+    cent = np.load(os.path.join(folder, "ivf_sq_centroids.npy"))
+    ranges = (np.load(os.path.join(folder, "ivf_sq_vmin.npy")), np.load(os.path.join(folder, "ivf_sq_vdiff.npy")))
+    codes = np.load(os.path.join(folder, "ivf_sq_codes.npy"), mmap_mode="r")
+    lists = np.load(os.path.join(folder, "ivf_sq_lists.npy"), mmap_mode="r")
+    slo, shi = man["row_range"]
+    d = int(man["d"])
+    if cent.shape != (man["nlist"], d) or codes.shape != (shi - slo, d) or lists.shape[0] != shi - slo or ranges[0].shape != (d,) or ranges[1].shape != (d,):
+        raise ValueError(f"{folder}: the IVF-SQ8 files disagree with the manifest")
+    if devices is not None:
+        if row_range is not None:
+            raise ValueError("row_range and devices are mutually exclusive")
+        G = len(devices)
+        cuts = [slo + (shi - slo) * g // G for g in range(G + 1)]
+        shards = [_ivfsq_from_codes(codes[cuts[g] - slo:cuts[g + 1] - slo], np.asarray(lists[cuts[g] - slo:cuts[g + 1] - slo]), cuts[g], cent,
+                                    ranges, man["nprobe"], devices[g]) for g in range(G)]
+        sharded = ShardedMi355xIndex.from_shards(shards, cuts[:-1])
+        sharded.nprobe = man["nprobe"]
+        return sharded
+    lo, hi = (slo, shi) if row_range is None else (int(row_range[0]), int(row_range[1]))
+    if not slo <= lo <= hi <= shi:
+        raise ValueError(f"row_range {row_range} is outside the saved shard's rows [{slo}, {shi})")
+    return _ivfsq_from_codes(codes[lo - slo:hi - slo], np.asarray(lists[lo - slo:hi - slo]), lo, cent, ranges, man["nprobe"], device)

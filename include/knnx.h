@@ -300,9 +300,51 @@ int knnx_pqb_set_codebooks(knnx_pq_builder* b, const float* codebooks);
 int knnx_pqb_get_codebooks(knnx_pq_builder* b, float* codebooks);
 int knnx_pqb_lloyd(knnx_pq_builder* b, uint8_t* codes_out, int64_t* sizes_out);
 
+/* ---- IVF-SQ8: faiss IndexIVFScalarQuantizer(IndexFlatIP(d), d, nlist, QT_8bit, METRIC_INNER_PRODUCT), by_residual = false -------------
+ * (the "IVF65536,SQ8" factory string: the point between IVF-Flat's 2 d + 12 and IVF-PQ's M + 12 bytes per row).  The arena holds ONE
+ * byte per dimension: d + 12 bytes per padded row with the id maps; pad rows of a tile are zero bytes and are never admitted.  The
+ * quantiser is NOT residual: two fp32 vectors vmin [d], vdiff [d] (faiss' `trained` of QT_8bit).  The library derives, on the HOST in
+ * fp32 with IEEE division (numpy float32 gives the same bits): scale_j = 255.f / vdiff_j, step_j = vdiff_j / 255.f, and scale_j = 0
+ * where vdiff_j == 0 (a constant column; zero-padded columns are such).
+ *   encode    t = (f32(x_f16_j) - vmin_j) * scale_j, ONE fp32 subtract then ONE fp32 multiply (no fused contraction); code_j = 0 if
+ *             t < 0 or t is NaN, 255 if t >= 255, (int)t otherwise -- faiss' (int)(255 * x) on the clamped, normalised component;
+ *             equal to np.clip(np.floor((x.astype(f32) - vmin) * scale), 0, 255) bit for bit.
+ *   decode    dec_j = vmin_j + (f32(code_j) + 0.5f) * step_j, the multiply and the add rounded separately.  knnx_reconstruct, the R
+ *             of search / search_dedup and the vectors the dedup links are computed from are these rows, bit-equal to the numpy
+ *             float32 restatement.
+ *   score     <q, dec(row)>, evaluated as b_q + sum_j u_j code_j with u = q * step and b_q = <q, vmin + step / 2>: the codes enter the
+ *             MFMA as fp16 values (0 .. 255 are exact), u -- scaled by a power of two per query so that it sits in the fp16 normal
+ *             range, which is undone exactly -- is split hi / lo into two fp16 operands as the fp16 scans split q, accumulation is
+ *             fp32, b_q is added once per score.  Not a bit-level contract: within 1e-5 of the float64 value, like the fp16 and ADC
+ *             scans.  A (query, row) score does not depend on the batch the query arrives in.
+ *   the rest  coarse quantiser, probe rule (knnx_ivf_set_nprobe), result order (score descending, ties by ascending id) and the
+ *             -1 / -FLT_MAX padding are IVF-Flat's, word for word.
+ * Build: knnx_ivfsq_set_quantizer on an EMPTY index before knnx_ivf_begin (KNNX_E_ARG for a non-finite entry or a negative vdiff;
+ * KNNX_E_STATE on an index that has rows or lists, that already has a quantiser, or that is IVF-PQ -- and knnx_ivfpq_set_quantizer
+ * answers KNNX_E_STATE on an IVF-SQ8 index).  Afterwards knnx_ivf_begin / knnx_ivf_add_assigned[_device] / knnx_ivf_end ENCODE the
+ * rows under the same list / position rules, or knnx_ivfsq_add_codes loads precomputed codes [n][d] in their place (the scatter
+ * alone).  knnx_ivfsq_get_quantizer: vmin / vdiff as they were given.  knnx_ivfsq_get_codes: every row of a built index in arena
+ * order (list by list): ids [ntotal], lists [ntotal], codes [ntotal][d] (host).  knnx_ivfsq: 1 on an IVF-SQ8 index, 0 otherwise.
+ * Served: knnx_search (with and without R), knnx_search_device, knnx_search_dedup, the coalescer, knnx_reconstruct,
+ * knnx_ivf_set_nprobe, knnx_ivf_id_order / knnx_ivf_map_ids, knnx_ivf_last_scan_tiles (bytes read = tiles * 32 * d), and
+ * knnx_shards_adopt of IVF-SQ8 shards that carry the same quantiser bit for bit (a different one, or a mix with another index kind,
+ * is refused with a message) -- all with k <= 64 and any n: every batch is ONE multi-block pass per 256 queries (1 .. 32 queries are
+ * one block), so the ids do not depend on the batch size.  Refused: k > 64 and knnx_range_search* answer KNNX_E_UNSUPPORTED; add /
+ * attach / synth_fill / reset / reserve / knnx_ivf_set_lists answer KNNX_E_STATE; every such message says "IVF-SQ8".  An index nobody
+ * gave an SQ8 quantiser is exactly the blocks above and below, byte for byte: it allocates and launches nothing of this. */
+int knnx_ivfsq_set_quantizer(knnx_index* ix, const float* vmin, const float* vdiff);
+int knnx_ivfsq_get_quantizer(knnx_index* ix, float* vmin, float* vdiff);
+int knnx_ivfsq(const knnx_index* ix); /* 0 / 1 */
+int knnx_ivfsq_add_codes(knnx_index* ix, const uint8_t* codes, int64_t n, const int64_t* ids, const int32_t* lists, const int32_t* pos);
+int knnx_ivfsq_get_codes(knnx_index* ix, int64_t* ids, int32_t* lists, uint8_t* codes);
+/* The training kernel (faiss RS_minmax with argument 0): per-column min and max of n fp16 rows [n][d] in HBM, 0 < d <= 1024, n > 0 ->
+ * host f32 vmin_out [d], vmax_out [d].  Min and max do not depend on the order of the rows: bit-equal to numpy's
+ * x.astype(float32).min(0) / .max(0).  `stream`: hipStream_t or NULL; synchronous. */
+int knnx_colminmax_device(int device, const void* rows_dev_f16, int64_t n, int d, float* vmin_out, float* vmax_out, void* stream);
+
 /* ---- List-ordered ids: the reference's reorder_metadata_by_ivf_index (ivf_metadata_ordering.py:17-64, clip_back.py:350-369, 629-640) ----
  * A metadata store re-ordered so that the ids of one inverted list are one contiguous run turns the k random rows of a request into
- * nprobe runs.  The mapping is a function of the layout a built IVF index (IVF-Flat or IVF-PQ; with or without rotation, d_out, refine
+ * nprobe runs.  The mapping is a function of the layout a built IVF index (IVF-Flat, IVF-SQ8 or IVF-PQ; with or without rotation, d_out, refine
  * store, threshold scan) already owns.  size[l] = rows of list l; dense0[l] = the exclusive prefix sum of size in int64.  The row at
  * position j of list l (arena row 32 * tile0[l] + j) has the ORDINAL dense0[l] + j; the ordinals are a permutation of [0, ntotal); pad
  * rows have none.

@@ -926,7 +926,10 @@ __device__ long long g_attn_phase[8192 * 4];
 #ifdef CLIPX_ABLATE
 __device__ int g_attn_pk_timer = 0;  // set by launch_attention_pk9 from CLIPX_ATTN_PK_TIMER (tools build)
 #endif
-template <int DH, int NKB, int NW, int QPW, bool CAUSAL, bool RECOMP, bool TIMER = false>
+// RAGGED (not causal, offs / lens given): a sample shorter than the launch's NKB - 1 blocks has padding keys in EVERY block from
+// its own last one on, so the key < T mask runs in all of them -- the plain form masks the last block only, and the zeroed K rows
+// of the blocks in between would sit in the softmax at logit 0.  (The causal form masks every block as it is.)
+template <int DH, int NKB, int NW, int QPW, bool CAUSAL, bool RECOMP, bool TIMER = false, bool RAGGED = false>
 // two workgroups per CU up to 9 key blocks; beyond that (tools build: the 19-block yardstick) the LDS holds one
 __global__ __launch_bounds__(NW * 64, NKB > 9 ? (NW + 3) / 4 : (2 * NW + 3) / 4) void attention_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ out, int Tin,
                                                               int H, float scale_log2e, int dbg, int q_blocks,
@@ -1057,7 +1060,7 @@ __global__ __launch_bounds__(NW * 64, NKB > 9 ? (NW + 3) / 4 : (2 * NW + 3) / 4)
         }
       }
       // masking is needed only in the last key block (padding past T) and, for causal, on/after the diagonal
-      if (kb == NKB - 1 || CAUSAL) {
+      if (kb == NKB - 1 || CAUSAL || RAGGED) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int key = kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hb;
@@ -2037,6 +2040,17 @@ static hipError_t launch_attention_cfg(const bf16* qkv, bf16* out, int B, int T,
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, grid, block, smem, st, qkv, out, T, H, scale_log2e, dbg, q_blocks, offs, lens);
+  } else if (lens) {
+    // a ragged batch that is not causal: the form that masks the padding keys of every block (the rows launch_attention gives
+    // offs / lens to; the encoder's own ragged batches are the causal text tower's)
+    if constexpr (DH == 64 && NKB <= 4 && !RECOMP) {
+      auto kern = attention_kernel<DH, NKB, NW, QPW, false, RECOMP, false, true>;
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL(kern, grid, block, smem, st, qkv, out, T, H, scale_log2e, dbg, q_blocks, offs, lens);
+    } else {
+      return hipErrorInvalidValue;
+    }
   } else {
     auto kern = attention_kernel<DH, NKB, NW, QPW, false, RECOMP>;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);

@@ -1105,6 +1105,25 @@ extern "C" int clipx_attention_dh_device(int device, const void* qkv_bf16, void*
   return CLIPX_OK;
 }
 
+// launch_attention with the encoder's own two extras (run_layers): the pooled last block's q_blocks and the ragged batches' offs /
+// lens.  Every refusal is made here, before the device is touched, so launch_attention is never asked for a kernel it has not
+extern "C" int clipx_attention_ex_device(int device, const void* qkv_f16, void* out_bf16, int B, int T, int H, int dh, int causal,
+                                         int q_blocks, const int32_t* offs, const int32_t* lens, void* stream) {
+  if (!qkv_f16 || !out_bf16 || B <= 0 || T <= 0 || H <= 0 || q_blocks < 0) return fail(CLIPX_E_ARG, "bad attention arguments");
+  if (dh != 64 && dh != 80) return fail(CLIPX_E_UNSUPPORTED, "head dimension must be 64 or 80");
+  if (const char* why = attention_limit(T, dh, causal)) return fail(CLIPX_E_UNSUPPORTED, why);
+  if ((offs != nullptr) != (lens != nullptr)) return fail(CLIPX_E_ARG, "offs and lens go together: both or neither");
+  if (offs && (dh != 64 || T > 128))
+    return fail(CLIPX_E_UNSUPPORTED, "ragged batches (offs / lens) need head dimension 64 and at most 128 tokens");
+  if (clipx::attn_plan(T, dh, causal).kernel == clipx::ATTN_NONE)
+    return fail(CLIPX_E_UNSUPPORTED, "no attention kernel for head dimension 80 at 97 .. 256 tokens");
+  HIPCHK(hipSetDevice(device));
+  hipError_t e = launch_attention((const bf16*)qkv_f16, (bf16*)out_bf16, B, T, H, dh, causal, (hipStream_t)stream, q_blocks, offs, lens);
+  if (e == hipErrorInvalidValue) return fail(CLIPX_E_UNSUPPORTED, "no attention kernel for this (T, head dimension)");
+  HIPCHK(e);
+  return CLIPX_OK;
+}
+
 extern "C" int clipx_layernorm_device(int device, const float* x, const float* gamma, const float* beta, void* y,
                                       int out_bf16, int M, int d, float eps, void* stream) {
   if (!x || !gamma || !beta || !y || M <= 0) return fail(CLIPX_E_ARG, "bad layernorm arguments");

@@ -206,6 +206,16 @@ int clipx_attention_device(int device, const void* qkv_f16, void* out_bf16, int 
 /* Same for head dimension dh = 64 or 80 (ViT-H/14 image tower: 1280 / 16): qkv [B*T, 3*H*dh] -> out [B*T, H*dh]. */
 int clipx_attention_dh_device(int device, const void* qkv_f16, void* out_bf16, int B, int T, int H, int dh,
                               int causal, void* stream);
+/* The same kernels with the two arguments the encoder itself passes them, for per-kernel tests of those forms.
+ *   q_blocks  0: every row.  n > 0: only the rows of the n leading blocks of 32 queries of every sample are computed (the pooled
+ *             last block asks for 1); those rows hold the bits of the full launch, the OTHER ROWS OF out ARE UNSPECIFIED.
+ *   offs_dev_or_null, lens_dev_or_null  device int32 [B], both or neither (CLIPX_E_ARG otherwise): a ragged batch, sample b owns
+ *             the lens[b] >= 1 packed rows from row offs[b] on, so qkv and out hold sum(lens) rows and T is the longest length.
+ *             Head dimension 64 and T <= 128 only (CLIPX_E_UNSUPPORTED otherwise).
+ * The limits of T are those of the two entry points above, and dh = 80 has no kernel at T = 97 .. 256 (CLIPX_E_UNSUPPORTED);
+ * a refused call launches nothing. */
+int clipx_attention_ex_device(int device, const void* qkv_f16, void* out_bf16, int B, int T, int H, int dh, int causal,
+                              int q_blocks, const int32_t* offs_dev_or_null, const int32_t* lens_dev_or_null, void* stream);
 int clipx_layernorm_device(int device, const float* x, const float* gamma, const float* beta, void* y, int out_bf16,
                            int M, int d, float eps, void* stream);
 /* LayerNorm statistics of the residual stream as the LayerNorm-folded GEMMs consume them (per-kernel parity test):

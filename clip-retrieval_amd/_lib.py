@@ -103,6 +103,9 @@ SIGNATURES = {
     "knnx_ivfsq": (C.c_int, [_P]),
     "knnx_ivfsq_add_codes": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P]),
     "knnx_ivfsq_get_codes": (C.c_int, [_P, _P, _P, _P]),
+    "knnx_ivfsq_set_threshold_scan": (C.c_int, [_P, C.c_int]),
+    "knnx_ivfsq_threshold_scan": (C.c_int, [_P]),
+    "knnx_ivfsq_threshold_stats": (C.c_int, [_P, _P, _P, _P, _P]),
     "knnx_colminmax_device": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int, _P, _P, _P]),
     "knnx_rotate_f16_device": (C.c_int, [C.c_int, _P, _P, C.c_int64, C.c_int, _P, _P]),
     "knnx_rotate_rect_f16_device": (C.c_int, [C.c_int, _P, _P, C.c_int64, C.c_int, C.c_int, _P, _P]),

@@ -270,8 +270,19 @@ struct SqScanArgs {
   const unsigned* nwork;
   int nblk;
   unsigned work_stride;
+  // threshold mode (launch_sq_range_scan; k, cap, thr_g and part_* are not read there)
+  const float* rthr;      // [32 nblk] thresholds, strict; +INFINITY: the query is finished
+  unsigned* rcnt;         // [32 nblk] hits per query, exact even past rcap
+  unsigned rcap;          // hits a query's slice holds
+  float* hit_s;           // [nq][rcap] scores
+  uint32_t* hit_i;        // [nq][rcap] arena rows
 };
 hipError_t launch_sq_scan(const SqScanArgs& a, hipStream_t st);
+// Threshold mode of the list scan: every valid row of the work lists whose score is > rthr[q] is appended to query q's slice as (score,
+// arena row); rcnt is cleared first.  The scores are those of launch_sq_scan, bit for bit.
+hipError_t launch_sq_range_scan(const SqScanArgs& a, hipStream_t st);
+// out [nq] = rows in the lists whose mask (masks [ceil(nq / 32)][nlist], bit q % 32) names query q
+hipError_t launch_sq_probed_rows(const unsigned* masks, const unsigned* size, int nlist, int nq, unsigned long long* out, hipStream_t st);
 // encode n fp16 rows into their arena slots (tile0 == null: slot = i; idmap == null: codes only), laying down idmap / inv like launch_ivf_scatter
 hipError_t launch_sq_encode(const _Float16* src, int64_t n, int d, const int32_t* lists, const int32_t* pos, const int64_t* ids,
                             int64_t id0, const unsigned* tile0, int64_t id_lo, int64_t n_ids, const float* vmin, const float* scale,

@@ -105,18 +105,29 @@ __device__ __forceinline__ half8 sq_codes_half8(uint32_t w0, uint32_t w1) {
 }
 
 // D = row width in bytes (= columns); LD = dwordx4 loads of one burst (32 LD columns); D / (32 LD) bursts per tile
-template <int D, int LD>
-__global__ __launch_bounds__(KNN_WG, 2) void knn_sq_scan_kernel(
-    const uint8_t* __restrict__ X, const _Float16* __restrict__ qfrag, const float* __restrict__ bq_g,
+//
+// RANGE = true is the threshold mode (range_search and k > 64 on an index with the threshold-scan switch on): the same work lists,
+// operand path, bursts, MFMA order and score arithmetic -- a (query, row) score is the same fp32 value in both modes -- but no
+// candidate queues, no prune, no partial lists: the LDS holds the u fragments only (128 D bytes) and the tile loop has no barrier.
+// Query NQ blk + q of the pass has the threshold rthr[NQ blk + q]; a valid row of a tile whose mask has the query's bit is a hit when
+// score > threshold (strict).  A lane owns 16 rows of ONE query: it counts its hits, takes that many slots of the query's slice
+// [rcap] of hit_s / hit_i with ONE atomicAdd on rcnt[NQ blk + q] and writes (score, arena row) while below rcap -- the counter stays
+// exact when the slice overflows (the host regrows the pools and scans again).  A threshold of +INFINITY marks a finished query; a
+// workgroup whose block has only finished queries returns before it stages the fragments.
+template <int D, int LD, bool RANGE>
+__device__ __forceinline__ void sq_scan_body(
+    unsigned char* smem_raw, const uint8_t* __restrict__ X, const _Float16* __restrict__ qfrag, const float* __restrict__ bq_g,
     const float* __restrict__ inv_g, int nq, int k, int cap, int* __restrict__ thr_g, float* __restrict__ part_s,
     uint32_t* __restrict__ part_i, int* __restrict__ part_n, const uint4* __restrict__ work,
-    const unsigned* __restrict__ nwork_ptr, int nblk, unsigned work_stride) {
+    const unsigned* __restrict__ nwork_ptr, int nblk, unsigned work_stride, const float* __restrict__ rthr,
+    unsigned* __restrict__ rcnt, unsigned rcap, float* __restrict__ hit_s, uint32_t* __restrict__ hit_i) {
   constexpr int NQ = 32;
   constexpr int KS = D / 16;
   constexpr int NB = D / (32 * LD);  // bursts per tile
   static_assert(D % (32 * LD) == 0, "whole bursts");
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  const ScanSmem sm = carve(smem_raw, D, cap, NQ);
+  ScanSmem sm{};
+  if constexpr (RANGE) sm.qf = reinterpret_cast<half8*>(smem_raw);
+  else sm = carve(smem_raw, D, cap, NQ);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, w = tid >> 6;
@@ -136,20 +147,32 @@ __global__ __launch_bounds__(KNN_WG, 2) void knn_sq_scan_kernel(
     if (bgrid == 0) return;
     qfrag += (size_t)blk * D * 64;
     nq = nq - NQ * blk < NQ ? nq - NQ * blk : NQ;
-    thr_g += NQ * blk;
+    if constexpr (!RANGE) thr_g += NQ * blk;
     work += (size_t)blk * work_stride;
     nwork_ptr += blk;
   }
   // this lane's query: the inverse of its power-of-two scale and its bias (unused where q >= nq)
   const float inv_q = q < nq ? inv_g[NQ * blk + q] : 0.f;
   const float b_q = q < nq ? bq_g[NQ * blk + q] : 0.f;
+  // threshold mode: this lane's threshold (queries past nq never hit) and the first entry of its slice of the pools (the launcher
+  // checks that the pools' queries x rcap entries are indexed by 32 bits)
+  float thr_q = INFINITY;
+  unsigned slice_q = 0;
+  if constexpr (RANGE) {
+    if (q < nq) thr_q = rthr[NQ * blk + q];
+    slice_q = (unsigned)(NQ * blk + q) * rcap;
+    // (every wave holds all 32 queries of the block: the vote is the same in all 8, so the whole workgroup leaves or stays)
+    if (__ballot(thr_q < INFINITY) == 0ull) return;
+  }
 
   {
     const uint4* src = reinterpret_cast<const uint4*>(qfrag);
     uint4* dst = reinterpret_cast<uint4*>(sm.qf);
     for (int i = tid; i < KS * 2 * 64; i += KNN_WG) dst[i] = src[i];
-    if (tid < NQ) { sm.cnt[tid] = 0; sm.thr[tid] = enc_f(-INFINITY); }
-    if (tid < 4) sm.flag[tid] = 0;
+    if constexpr (!RANGE) {
+      if (tid < NQ) { sm.cnt[tid] = 0; sm.thr[tid] = enc_f(-INFINITY); }
+      if (tid < 4) sm.flag[tid] = 0;
+    }
   }
   __syncthreads();
 
@@ -214,6 +237,32 @@ __global__ __launch_bounds__(KNN_WG, 2) void knn_sq_scan_kernel(
     const int64_t row_lim = (int64_t)it_cur.x * 32 + (int64_t)it_cur.z;
     const bool q_ok = q < nq && ((it_cur.y >> q) & 1u);
     float sc[16];
+    if constexpr (RANGE) {
+      unsigned hit = 0;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float v = sq_mul_add(sq_mul_add(acc_l[r], KNN_LO_INV, acc_h[r]), inv_q, b_q);
+        sc[r] = v;
+        const int64_t row = row0 + (r & 3) + 8 * (r >> 2);
+        if (v > thr_q && row < row_lim && q_ok) hit |= 1u << r;
+      }
+      if (hit) {
+        unsigned at = atomicAdd(&rcnt[NQ * blk + q], (unsigned)__popc(hit));  // (hit != 0 implies q < nq: a query of the pass)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          if (hit & (1u << r)) {
+            if (at < rcap) {
+              hit_s[slice_q + at] = sc[r];
+              hit_i[slice_q + at] = (uint32_t)(row0 + (r & 3) + 8 * (r >> 2));
+            }
+            ++at;
+          }
+        }
+      }
+      grp = gnext;
+      ++rnd;
+      return;
+    }
     unsigned pend = 0;
     const float thr = dec_f(sm.thr[q]);
 #pragma unroll
@@ -268,6 +317,7 @@ __global__ __launch_bounds__(KNN_WG, 2) void knn_sq_scan_kernel(
       group(a1, a0);
     }
   }
+  if constexpr (RANGE) return;
 
   __syncthreads();
   for (int qq = w; qq < NQ; qq += KNN_WAVES) prune_query(sm, qq, cap, k, lane, thr_g);
@@ -282,6 +332,31 @@ __global__ __launch_bounds__(KNN_WG, 2) void knn_sq_scan_kernel(
     }
   }
   if (tid < NQ) part_n[slot * NQ + tid] = sm.cnt[tid];
+}
+
+// the two kernels over the one body: top-k (candidate queues, partial lists) and threshold mode
+template <int D, int LD>
+__global__ __launch_bounds__(KNN_WG, 2) void knn_sq_scan_kernel(
+    const uint8_t* __restrict__ X, const _Float16* __restrict__ qfrag, const float* __restrict__ bq_g,
+    const float* __restrict__ inv_g, int nq, int k, int cap, int* __restrict__ thr_g, float* __restrict__ part_s,
+    uint32_t* __restrict__ part_i, int* __restrict__ part_n, const uint4* __restrict__ work,
+    const unsigned* __restrict__ nwork_ptr, int nblk, unsigned work_stride) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  sq_scan_body<D, LD, false>(smem_raw, X, qfrag, bq_g, inv_g, nq, k, cap, thr_g, part_s, part_i, part_n, work, nwork_ptr, nblk, work_stride,
+                             nullptr, nullptr, 0u, nullptr, nullptr);
+}
+// (d = 768 runs bursts of 6 loads, four per tile: with 8 -- three per tile, the tile body unrolled twice -- the compiler takes 222
+// VGPRs, more than the 210 of the top-k form; the k-steps, and so the scores, come in the same order whatever the burst length)
+constexpr int sq_range_burst(int d) { return d == 768 ? 6 : SQ_BURST; }
+template <int D, int LD>
+__global__ __launch_bounds__(KNN_WG, 2) void knn_sq_range_scan_kernel(
+    const uint8_t* __restrict__ X, const _Float16* __restrict__ qfrag, const float* __restrict__ bq_g,
+    const float* __restrict__ inv_g, int nq, const uint4* __restrict__ work, const unsigned* __restrict__ nwork_ptr, int nblk,
+    unsigned work_stride, const float* __restrict__ rthr, unsigned* __restrict__ rcnt, unsigned rcap, float* __restrict__ hit_s,
+    uint32_t* __restrict__ hit_i) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  sq_scan_body<D, LD, true>(smem_raw, X, qfrag, bq_g, inv_g, nq, 0, 0, nullptr, nullptr, nullptr, nullptr, work, nwork_ptr, nblk, work_stride,
+                            rthr, rcnt, rcap, hit_s, hit_i);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -379,6 +454,22 @@ __global__ void sq_minmax_decode_kernel(int d, const int* __restrict__ omin, con
   if (c < d) { vmin[c] = dec_f(omin[c]); vmax[c] = dec_f(omax[c]); }
 }
 
+// rows in the probed lists of every query of a multi-block pass: out[n] = sum of size[l] over the lists l whose mask
+// masks[n / 32][l] has bit n % 32 (the descent of a large-k search wants it; the masks stay on the device).  One workgroup per query.
+__global__ __launch_bounds__(256) void sq_probed_rows_kernel(const unsigned* __restrict__ masks, const unsigned* __restrict__ size,
+                                                            int nlist, unsigned long long* __restrict__ out) {
+  __shared__ unsigned long long s_sum[4];
+  const int n = blockIdx.x, tid = threadIdx.x;
+  const unsigned* mk = masks + (size_t)(n >> 5) * nlist;
+  unsigned long long sum = 0;
+  for (int l = tid; l < nlist; l += 256)
+    if ((mk[l] >> (n & 31)) & 1u) sum += size[l];
+  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+  if ((tid & 63) == 0) s_sum[tid >> 6] = sum;
+  __syncthreads();
+  if (tid == 0) out[n] = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
+}
+
 // ---------------------------------------------------------------------------------------------
 // launchers (declared in knn_kernels.h)
 // ---------------------------------------------------------------------------------------------
@@ -409,6 +500,38 @@ hipError_t launch_sq_scan(const SqScanArgs& a, hipStream_t st) {
     default: return hipErrorInvalidValue;
   }
 #undef SQ_LAUNCH
+}
+
+// threshold mode over the work lists of the pass: rcnt [32 nblk] is cleared here
+hipError_t launch_sq_range_scan(const SqScanArgs& a, hipStream_t st) {
+  if (a.nblk < 1 || a.grid < a.nblk || !a.work || !a.nwork || !a.rthr || !a.rcnt || !a.hit_s || !a.hit_i) return hipErrorInvalidValue;
+  if (a.nq < 1 || (uint64_t)a.nq * a.rcap > 0xffffffffull) return hipErrorInvalidValue;  // (the kernel indexes the pools with 32 bits)
+  const size_t smem = (size_t)a.d * 128;
+  hipError_t e = hipMemsetAsync(a.rcnt, 0, (size_t)a.nblk * 32 * sizeof(unsigned), st);
+  if (e != hipSuccess) return e;
+#define SQ_LAUNCH(DD)                                                                                                          \
+  {                                                                                                                            \
+    auto kern = knn_sq_range_scan_kernel<DD, sq_range_burst(DD)>;                                                              \
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);       \
+    if (e != hipSuccess) return e;                                                                                             \
+    hipLaunchKernelGGL(kern, dim3(a.grid), dim3(KNN_WG), smem, st, a.codes, a.qfrag, a.bq, a.inv, a.nq, a.work, a.nwork,        \
+                       a.nblk, a.work_stride, a.rthr, a.rcnt, a.rcap, a.hit_s, a.hit_i);                                       \
+    return hipGetLastError();                                                                                                  \
+  }
+  switch (a.d) {
+    case 256: SQ_LAUNCH(256)
+    case 512: SQ_LAUNCH(512)
+    case 768: SQ_LAUNCH(768)
+    case 1024: SQ_LAUNCH(1024)
+    default: return hipErrorInvalidValue;
+  }
+#undef SQ_LAUNCH
+}
+
+hipError_t launch_sq_probed_rows(const unsigned* masks, const unsigned* size, int nlist, int nq, unsigned long long* out, hipStream_t st) {
+  if (nq <= 0) return hipSuccess;
+  hipLaunchKernelGGL(sq_probed_rows_kernel, dim3(nq), dim3(256), 0, st, masks, size, nlist, out);
+  return hipGetLastError();
 }
 
 hipError_t launch_sq_encode(const _Float16* src, int64_t n, int d, const int32_t* lists, const int32_t* pos, const int64_t* ids,

@@ -1007,7 +1007,10 @@ extern "C" int knnx_search(knnx_index* ix, const float* q, int n, int k, float* 
     std::lock_guard<std::mutex> lk(ix->mu);
     if (!ix->pq.threshold_scan) return fail(KNNX_E_UNSUPPORTED, "k > 64 is not supported on an IVF-PQ index");
   }
-  if (ix->sq.on && k > KNNX_MAX_K_FAST) return fail(KNNX_E_UNSUPPORTED, "k > 64 is not supported on an IVF-SQ8 index");
+  if (ix->sq.on && k > KNNX_MAX_K_FAST) {  // likewise, through the threshold mode of the code scan
+    std::lock_guard<std::mutex> lk(ix->mu);
+    if (!ix->sq.threshold_scan) return fail(KNNX_E_UNSUPPORTED, "k > 64 is not supported on an IVF-SQ8 index");
+  }
   if (n == 0) return KNNX_OK;
   if (n == 1 && k <= KNNX_MAX_K_FAST && ix->co.on) {  // concurrent single-query callers share one scan
     CoReq me{q, k, D, I, R, false, 0.f, nullptr, 0, nullptr};
@@ -1019,6 +1022,8 @@ extern "C" int knnx_search(knnx_index* ix, const float* q, int n, int k, float* 
     int r = (k <= KNNX_MAX_K_FAST) ? search_fast_locked(ix, q, n, k, D, I)
             : ix->pq.m               ? (ix->pq.threshold_scan ? search_large_k_pq_locked(ix, q, n, k, D, I)
                                                               : fail(KNNX_E_UNSUPPORTED, "k > 64 is not supported on an IVF-PQ index"))
+            : ix->sq.on              ? (ix->sq.threshold_scan ? search_large_k_sq_locked(ix, q, n, k, D, I)
+                                                              : fail(KNNX_E_UNSUPPORTED, "k > 64 is not supported on an IVF-SQ8 index"))
                                      : search_large_k_locked(ix, q, n, k, D, I);
     if (r) return r;
   }

@@ -471,12 +471,30 @@ struct SqData {
   DevBuf<float> vmin, scale, step;       // [d]; scale = 255 / vdiff and step = vdiff / 255 from the host, 0 where vdiff == 0
   DevBuf<uint8_t> codes;                 // [capacity][d]
   std::vector<unsigned> tile0_h, size_h; // host copy of the layout (knnx_ivfsq_get_codes)
+  // threshold mode of the list scan (knnx_ivfsq_set_threshold_scan): k > 64 and range_search are served; off: they are refused
+  bool threshold_scan = false;
+  int64_t thr_queries = 0, thr_scans = 0, thr_query_scans = 0, thr_hits = 0;  // knnx_ivfsq_threshold_stats
 };
 // one IVF-SQ8 pass of up to IVFM_BLK x 32 queries (next to IvfMultiScratch, which serves its coarse half); allocated on first use
 struct SqScratch {
   DevBuf<float> u;         // [256][d] q * step, scaled, in the scan's column order
   DevBuf<_Float16> qfrag;  // [IVFM_BLK][d * 64] its fragment images
   DevBuf<float> bq, inv;   // [256] bias and inverse scale of every query
+  // threshold passes (allocated by the first one): the per-query thresholds and hit counters of one scan, the counters of a fetch, the
+  // rows in every query's probed lists
+  DevBuf<float> tthr;                 // [256]
+  DevBuf<unsigned> tcnt, tfetch;      // [256]
+  DevBuf<unsigned long long> trows;   // [256]
+  hipError_t alloc_threshold() {
+    if (tthr) return hipSuccess;
+    hipError_t e = hipSuccess;
+    dev_alloc(e, tthr, (size_t)IVFM_BLK * KNN_NQ);
+    dev_alloc(e, tcnt, (size_t)IVFM_BLK * KNN_NQ);
+    dev_alloc(e, tfetch, (size_t)IVFM_BLK * KNN_NQ);
+    dev_alloc(e, trows, (size_t)IVFM_BLK * KNN_NQ);
+    if (e != hipSuccess) tthr.reset(), tcnt.reset(), tfetch.reset(), trows.reset();
+    return e;
+  }
   hipError_t alloc(int d) {
     if (u) return hipSuccess;
     hipError_t e = hipSuccess;
@@ -631,6 +649,7 @@ int search_fast_locked(knnx_index* ix, const float* q, int n, int k, float* D, i
 // knnx_range.hip
 int search_large_k_locked(knnx_index* ix, const float* q, int n, int k, float* D, int64_t* I);
 int search_large_k_pq_locked(knnx_index* ix, const float* q, int n, int k, float* D, int64_t* I);
+int search_large_k_sq_locked(knnx_index* ix, const float* q, int n, int k, float* D, int64_t* I);
 // knnx_ivf.hip
 int ivf_build_worklist(knnx_index* ix, const float* q_dev, int nq, hipStream_t st, const unsigned* gate);
 bool ivfm_usable(const knnx_index* ix, int nq, int k);
@@ -651,6 +670,13 @@ int pq_decode_rows(knnx_index* ix, const int64_t* ids_dev, int64_t n, float* out
 
 // knnx_ivfsq.hip
 int scan_topk_sq(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out, int64_t* I_out, hipStream_t st);
+// queries of one IVF-SQ8 pass: IVFM_BLK blocks of 32, fewer where KNNX_GRID leaves fewer workgroups than blocks
+inline int sq_pass_max(const knnx_index* ix) { return KNN_NQ * std::max(1, std::min(IVFM_BLK, ix->n_cu)); }
+// threshold passes (one front half, then any number of threshold launches over its work lists; knnx_range.hip drives them)
+int sq_front(knnx_index* ix, const float* q_dev, int nq, hipStream_t st);
+int sq_pass_top64(knnx_index* ix, int nq, float* D64, hipStream_t st);
+int sq_pass_probed_rows(knnx_index* ix, int nq, std::vector<int64_t>& total, hipStream_t st);
+int sq_pass_threshold_scan(knnx_index* ix, int nq, const float* thr_h, unsigned cap, std::vector<unsigned>& counts, hipStream_t st);
 // decoded rows of n ids (device) -> out f32 [n][d]; -1 -> 0xFF bytes
 int sq_decode_rows(knnx_index* ix, const int64_t* ids_dev, int64_t n, float* out_dev, hipStream_t st);
 

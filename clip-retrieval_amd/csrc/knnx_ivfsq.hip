@@ -11,11 +11,17 @@
 // radix select of the nprobe best lists, the per-block work lists.  The list scan then runs over the code arena with the fragments of u = q *
 // step (knn_sq_kernels.hip) and the merge is the IVF one.  Every batch size takes this path -- 1 .. 32 queries are one block --
 // so a query's ids and scores do not depend on the batch it arrives in.
-int scan_topk_sq(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out, int64_t* I_out, hipStream_t st) {
-  const int cap = scan_cap(ix->d, k);
-  const int nblk = (nq + KNN_NQ - 1) / KNN_NQ;
-  if (cap < 0 || nblk > IVFM_BLK || nblk > ix->n_cu) return fail(KNNX_E_STATE, "internal: IVF-SQ8 pass misuse");
-  const int grid = std::max(1, ix->n_cu / nblk) * nblk;  // (part_* hold n_cu x 64 lists: grid <= n_cu)
+//
+// The pass comes in two halves.  The front half (sq_front) leaves the work lists of the blocks in ix->ivfm and the u fragments, biases
+// and inverse scales in ix->sqs; the top-k pass follows it with the list scan and the merge, a threshold pass (the switch
+// knnx_ivfsq_set_threshold_scan) with any number of threshold launches over the same work lists.
+static int sq_blocks(int nq) { return (nq + KNN_NQ - 1) / KNN_NQ; }
+static int sq_grid(const knnx_index* ix, int nblk) { return std::max(1, ix->n_cu / nblk) * nblk; }  // (part_* hold n_cu x 64 lists: grid <= n_cu)
+
+int sq_front(knnx_index* ix, const float* q_dev, int nq, hipStream_t st) {
+  const int nblk = sq_blocks(nq);
+  if (nq < 1 || nblk > IVFM_BLK || nblk > ix->n_cu) return fail(KNNX_E_STATE, "internal: IVF-SQ8 pass misuse");
+  const int grid = sq_grid(ix, nblk);
   hipError_t e = ix->ivfm.alloc(ix->d, (size_t)ix->ivf_nlist, ix->capacity);
   if (e == hipSuccess) e = ix->sqs.alloc(ix->d);
   if (e != hipSuccess) {
@@ -26,6 +32,11 @@ int scan_topk_sq(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out
   if (r) return r;
   HIPCHK(launch_sq_prep(q_dev, nq, ix->d, ix->sq.vmin, ix->sq.step, ix->sqs.u, ix->sqs.bq, ix->sqs.inv, st));
   HIPCHK(launch_prep_blocks(ix->sqs.u, nq, ix->d, ix->sqs.qfrag, ix->ivfm.thr_f, nullptr, st));  // (resets the list scan's thresholds)
+  return 0;
+}
+
+// what both modes of the list scan read of the pass whose front half is in ix->ivfm / ix->sqs
+static SqScanArgs sq_scan_args(const knnx_index* ix, int nq) {
   SqScanArgs a{};
   a.codes = ix->sq.codes;
   a.d = ix->d;
@@ -33,17 +44,26 @@ int scan_topk_sq(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out
   a.bq = ix->sqs.bq;
   a.inv = ix->sqs.inv;
   a.nq = nq;
+  a.nblk = sq_blocks(nq);
+  a.grid = sq_grid(ix, a.nblk);
+  a.work = ix->ivfm.work;
+  a.nwork = ix->ivfm.nwork;
+  a.work_stride = ix->ivfm.stride;
+  return a;
+}
+
+// the top-k list scan over the work lists of the front half, and the merge of its partial lists
+static int sq_topk_scan_merge(knnx_index* ix, int nq, int k, float* D_out, int64_t* I_out, hipStream_t st) {
+  const int cap = scan_cap(ix->d, k);
+  if (cap < 0) return fail(KNNX_E_STATE, "internal: IVF-SQ8 pass misuse");
+  SqScanArgs a = sq_scan_args(ix, nq);
+  const int nblk = a.nblk, grid = a.grid;
   a.k = k;
   a.cap = cap;
-  a.grid = grid;
   a.thr_g = ix->ivfm.thr_f;
   a.part_s = ix->flat.part_s;
   a.part_i = ix->flat.part_i;
   a.part_n = ix->flat.part_n;
-  a.work = ix->ivfm.work;
-  a.nwork = ix->ivfm.nwork;
-  a.nblk = nblk;
-  a.work_stride = ix->ivfm.stride;
   HIPCHK(ix->prof.begin(ix->prof.on, st));
   HIPCHK(launch_sq_scan(a, st));
   HIPCHK(ix->prof.end(ix->prof.on, st));
@@ -52,6 +72,79 @@ int scan_topk_sq(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out
   ix->ivfm_last_blk = nblk;
   ix->ivfm_union_valid = ix->prof.on;
   return 0;
+}
+
+int scan_topk_sq(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out, int64_t* I_out, hipStream_t st) {
+  if (scan_cap(ix->d, k) < 0) return fail(KNNX_E_STATE, "internal: IVF-SQ8 pass misuse");
+  int r = sq_front(ix, q_dev, nq, st);
+  if (r) return r;
+  return sq_topk_scan_merge(ix, nq, k, D_out, I_out, st);
+}
+
+// ---- threshold passes (the switch knnx_ivfsq_set_threshold_scan; knnx_range.hip drives them) ---------------------------------------
+// the top-64 scores of the pass whose front half is in place -> D64 host [nq][64], -FLT_MAX padded.  Synchronises.
+int sq_pass_top64(knnx_index* ix, int nq, float* D64, hipStream_t st) {
+  const int k = KNNX_MAX_K_FAST;
+  int r = sq_topk_scan_merge(ix, nq, k, ix->flat.D_dev, ix->flat.I_dev, st);
+  if (r) return r;
+  HIPCHK(hipMemcpyAsync(D64, ix->flat.D_dev, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return 0;
+}
+
+// rows in the probed lists of every query of the pass -> total [nq], summed on the device from the blocks' list masks.  Synchronises.
+int sq_pass_probed_rows(knnx_index* ix, int nq, std::vector<int64_t>& total, hipStream_t st) {
+  HIPCHK(ix->sqs.alloc_threshold());
+  HIPCHK(launch_sq_probed_rows(ix->ivfm.masks, ix->ivf.size, ix->ivf_nlist, nq, ix->sqs.trows, st));
+  std::vector<unsigned long long> t((size_t)nq);
+  HIPCHK(hipMemcpyAsync(t.data(), ix->sqs.trows, t.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  total.assign(t.begin(), t.end());
+  return 0;
+}
+
+// one threshold launch of the pass: thr_h [nq] (host; +INFINITY: a finished query) -> counts [nq] (exact), hits in ix->range at q * cap;
+// the device counters stay in ix->sqs.tcnt.  Synchronises.
+int sq_pass_threshold_scan(knnx_index* ix, int nq, const float* thr_h, unsigned cap, std::vector<unsigned>& counts, hipStream_t st) {
+  SqScratch& S = ix->sqs;
+  HIPCHK(S.alloc_threshold());
+  HIPCHK(hipMemcpyAsync(S.tthr, thr_h, (size_t)nq * sizeof(float), hipMemcpyHostToDevice, st));
+  SqScanArgs a = sq_scan_args(ix, nq);
+  a.rthr = S.tthr;
+  a.rcnt = S.tcnt;
+  a.rcap = cap;
+  a.hit_s = ix->range.s;
+  a.hit_i = ix->range.i;
+  HIPCHK(ix->prof.begin(ix->prof.on, st));
+  HIPCHK(launch_sq_range_scan(a, st));
+  HIPCHK(ix->prof.end(ix->prof.on, st));
+  counts.assign((size_t)nq, 0u);
+  HIPCHK(hipMemcpyAsync(counts.data(), S.tcnt, (size_t)nq * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  ++ix->sq.thr_scans;
+  return 0;
+}
+
+extern "C" int knnx_ivfsq_set_threshold_scan(knnx_index* ix, int on) {
+  if (!ix) return fail(KNNX_E_ARG, "index is null");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  if (!ix->sq.on) return fail(KNNX_E_STATE, "not an IVF-SQ8 index");
+  ix->sq.threshold_scan = on != 0;
+  return KNNX_OK;
+}
+extern "C" int knnx_ivfsq_threshold_scan(const knnx_index* ix) { return ix && ix->sq.on && ix->sq.threshold_scan ? 1 : 0; }
+
+// counters of the threshold passes since the index was created: queries served with k > 64, threshold launches (one serves a whole
+// group), launches summed over the queries that took part in them, hits fetched to the host
+extern "C" int knnx_ivfsq_threshold_stats(knnx_index* ix, int64_t* queries, int64_t* launches, int64_t* query_scans, int64_t* hits) {
+  if (!ix) return fail(KNNX_E_ARG, "index is null");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  if (!ix->sq.on) return fail(KNNX_E_STATE, "not an IVF-SQ8 index");
+  if (queries) *queries = ix->sq.thr_queries;
+  if (launches) *launches = ix->sq.thr_scans;
+  if (query_scans) *query_scans = ix->sq.thr_query_scans;
+  if (hits) *hits = ix->sq.thr_hits;
+  return KNNX_OK;
 }
 
 int sq_decode_rows(knnx_index* ix, const int64_t* ids_dev, int64_t n, float* out_dev, hipStream_t st) {

@@ -219,9 +219,45 @@ static int range_scan_pq(knnx_index* ix, const float* q_host, int nq, float thr,
   }
 }
 
+// ---- IVF-SQ8 with the threshold-scan switch on (knnx_ivfsq_set_threshold_scan): the list scan in threshold mode feeds the same pools ----
+// stage a group of <= sq_pass_max queries and run the front half of their pass (knnx_ivfsq.hip: sq_front)
+static int sq_pass_begin(knnx_index* ix, const float* q_host, int nq) {
+  hipStream_t st = ix->stream;
+  int r = ensure_pin(ix, (size_t)sq_pass_max(ix) * ix->d * sizeof(float));
+  if (r) return r;
+  if (scratch_acquire(ix, st)) return KNNX_E_HIP;
+  memcpy(ix->pin.p, q_host, (size_t)nq * ix->d * sizeof(float));
+  HIPCHK(hipMemcpyAsync(ix->flat.q_dev, ix->pin.p, (size_t)nq * ix->d * sizeof(float), hipMemcpyHostToDevice, st));
+  return sq_front(ix, ix->flat.q_dev, nq, st);
+}
+
+// range scan of <= sq_pass_max queries of an IVF-SQ8 index: the rows of the probed lists whose score is > thr.  Counts and hits as
+// range_scan leaves them, the device counters in ix->sqs.tcnt.
+static int range_scan_sq(knnx_index* ix, const float* q_host, int nq, float thr, std::vector<unsigned>& counts, unsigned* cap_out) {
+  int r = sq_pass_begin(ix, q_host, nq);
+  if (r) return r;
+  const std::vector<float> th((size_t)nq, thr);
+  for (;;) {
+    if (ix->range.pool == 0 && (r = range_pool_alloc(ix, (size_t)1 << 21))) return r;
+    const unsigned cap = (unsigned)std::min<size_t>(ix->range.pool / (size_t)nq, 0xffffffffu);
+    if ((r = sq_pass_threshold_scan(ix, nq, th.data(), cap, counts, ix->stream))) return r;
+    unsigned mx = 0;
+    for (int i = 0; i < nq; ++i) mx = std::max(mx, counts[i]);
+    if (mx <= cap) {
+      *cap_out = cap;
+      return 0;
+    }
+    // overflow: regrow and rescan over the same front half (the counts are exact even when the slices overflowed)
+    size_t want = ix->range.pool;
+    while (want / (size_t)nq < (size_t)mx) want <<= 1;
+    if (want > RANGE_POOL_MAX) return fail(KNNX_E_NOMEM, "range_search result exceeds the 512 Mi-hit scratch limit");
+    if ((r = range_pool_alloc(ix, want))) return r;
+  }
+}
+
 // what an IVF-PQ or IVF-SQ8 index answers to a range_search it does not serve (0: it serves it, or is neither).  Caller holds ix->mu.
 static int pq_range_refusal(const knnx_index* ix) {
-  if (ix->sq.on) return fail(KNNX_E_UNSUPPORTED, "range_search is not supported on an IVF-SQ8 index");
+  if (ix->sq.on) return ix->sq.threshold_scan ? 0 : fail(KNNX_E_UNSUPPORTED, "range_search is not supported on an IVF-SQ8 index");
   if (!ix->pq.m) return 0;
   if (!ix->pq.threshold_scan) return fail(KNNX_E_UNSUPPORTED, "range_search is not supported on an IVF-PQ index");
   if (ix->pq.refine)
@@ -237,15 +273,16 @@ extern "C" int knnx_range_search(knnx_index* ix, const float* q, int n, float th
   if (pq_range_refusal(ix)) return KNNX_E_UNSUPPORTED;
   if (set_dev(ix)) return KNNX_E_HIP;
   const bool fill = D != nullptr;
-  const bool pq = ix->pq.m != 0;
-  const int step = pq ? PQ_PASS : KNN_NQ;
+  const bool pq = ix->pq.m != 0, sq = ix->sq.on;
+  const int step = pq ? PQ_PASS : sq ? sq_pass_max(ix) : KNN_NQ;
   int64_t run = 0;
   std::vector<unsigned> counts;
   if (!fill) lims[0] = 0;
   for (int o = 0; o < n; o += step) {
     const int nq = std::min(step, n - o);
     unsigned cap = 0;
-    int r = pq ? range_scan_pq(ix, q + (size_t)o * ix->d, nq, thresh, counts, &cap) : range_scan(ix, q + (size_t)o * ix->d, nq, thresh, counts, &cap);
+    const float* qo = q + (size_t)o * ix->d;
+    int r = pq ? range_scan_pq(ix, qo, nq, thresh, counts, &cap) : sq ? range_scan_sq(ix, qo, nq, thresh, counts, &cap) : range_scan(ix, qo, nq, thresh, counts, &cap);
     if (r) return r;
     if (!fill) {
       for (int i = 0; i < nq; ++i) {
@@ -258,7 +295,7 @@ extern "C" int knnx_range_search(knnx_index* ix, const float* q, int n, float th
     for (int i = 0; i < nq; ++i)
       if (lims[o + i + 1] - lims[o + i] != (int64_t)counts[i])
         return fail(KNNX_E_STATE, "lims do not match this query/threshold (index changed between the two calls?)");
-    r = range_fetch(ix, nq, counts, cap, D + lims[o], I + lims[o], pq ? ix->pqs.tcnt.p : nullptr);
+    r = range_fetch(ix, nq, counts, cap, D + lims[o], I + lims[o], pq ? ix->pqs.tcnt.p : sq ? ix->sqs.tcnt.p : nullptr);
     if (r) return r;
   }
   return KNNX_OK;
@@ -274,8 +311,8 @@ extern "C" int knnx_range_search_once(knnx_index* ix, const float* q, int n, flo
   std::lock_guard<std::mutex> lk(ix->mu);
   if (pq_range_refusal(ix)) return KNNX_E_UNSUPPORTED;
   if (set_dev(ix)) return KNNX_E_HIP;
-  const bool pq = ix->pq.m != 0;
-  const int step = pq ? PQ_PASS : KNN_NQ;
+  const bool pq = ix->pq.m != 0, sq = ix->sq.on;
+  const int step = pq ? PQ_PASS : sq ? sq_pass_max(ix) : KNN_NQ;
   int64_t run = 0;
   bool fits = true;
   std::vector<unsigned> counts;
@@ -296,7 +333,8 @@ extern "C" int knnx_range_search_once(knnx_index* ix, const float* q, int n, flo
   for (int o = 0; o < n; o += step) {
     const int nq = std::min(step, n - o);
     unsigned cap = 0;
-    int r = pq ? range_scan_pq(ix, q + (size_t)o * ix->d, nq, thresh, counts, &cap) : range_scan(ix, q + (size_t)o * ix->d, nq, thresh, counts, &cap);
+    const float* qo = q + (size_t)o * ix->d;
+    int r = pq ? range_scan_pq(ix, qo, nq, thresh, counts, &cap) : sq ? range_scan_sq(ix, qo, nq, thresh, counts, &cap) : range_scan(ix, qo, nq, thresh, counts, &cap);
     if (r) return r;
     const int64_t first = run;
     for (int i = 0; i < nq; ++i) {
@@ -305,7 +343,7 @@ extern "C" int knnx_range_search_once(knnx_index* ix, const float* q, int n, flo
     }
     if (run > capacity) fits = false;
     if (fits) {
-      r = range_fetch(ix, nq, counts, cap, D + first, I + first, pq ? ix->pqs.tcnt.p : nullptr);
+      r = range_fetch(ix, nq, counts, cap, D + first, I + first, pq ? ix->pqs.tcnt.p : sq ? ix->sqs.tcnt.p : nullptr);
       if (r) return r;
     }
   }
@@ -606,6 +644,98 @@ int search_large_k_pq_locked(knnx_index* ix, const float* q, int n, int k, float
             Iq[j] = j < (int)h.size() ? h[j].second : -1;
           }
         }
+      }
+    }
+    o += gq;
+  }
+  return KNNX_OK;
+}
+
+// k > 64 on an IVF-SQ8 index with the threshold-scan switch on: search_large_k_pq_locked without the refine branch.  A group of queries
+// (up to sq_pass_max; fewer when group x 16 k hits would not fit the pools) runs the front half of the pass ONCE; the k = 64 pass over it
+// gives every query its 32nd and 64th score; then all queries descend together (knnx_descent.h), one threshold launch and one
+// synchronisation per step for the whole group, a finished query riding along with thr = +INFINITY.  A query whose probed lists hold
+// <= 2 k rows takes them all in the first scan.  The hits are ranked on the host: (score descending, id ascending).  Caller holds ix->mu.
+int search_large_k_sq_locked(knnx_index* ix, const float* q, int n, int k, float* D, int64_t* I) {
+  typedef std::pair<float, int64_t> Hit;
+  hipStream_t st = ix->stream;
+  const int K64 = KNNX_MAX_K_FAST;
+  const int gmax = (int)std::max<size_t>(1, std::min<size_t>((size_t)sq_pass_max(ix), RANGE_POOL_MAX / ((size_t)16 * (size_t)k)));
+  auto better = [](const Hit& a, const Hit& b) { return a.first > b.first || (a.first == b.first && a.second < b.second); };
+  std::vector<float> d64, thr, hd;
+  std::vector<int64_t> total, hi;
+  std::vector<unsigned> counts, sel;
+  for (int o = 0; o < n;) {
+    const int gq = std::min(gmax, n - o);
+    int r = sq_pass_begin(ix, q + (size_t)o * ix->d, gq);
+    if (r) return r;
+    d64.resize((size_t)gq * K64);
+    if ((r = sq_pass_top64(ix, gq, d64.data(), st))) return r;
+    if ((r = sq_pass_probed_rows(ix, gq, total, st))) return r;
+    std::vector<PqDescent> ds((size_t)gq);
+    std::vector<int> state((size_t)gq, 0);  // 0: descending, 1: its threshold is final, the hits did not fit yet, 2: fetched
+    std::vector<std::vector<Hit>> hits((size_t)gq);
+    for (int i = 0; i < gq; ++i) ds[i].start(d64[(size_t)i * K64 + K64 / 2 - 1], d64[(size_t)i * K64 + K64 - 1], k, total[i]);
+    thr.assign((size_t)gq, 0.f);
+    for (int left = gq; left > 0;) {
+      if (ix->range.pool == 0 && (r = range_pool_alloc(ix, (size_t)1 << 21))) return r;
+      const unsigned cap = (unsigned)std::min<size_t>(ix->range.pool / (size_t)gq, 0xffffffffu);
+      for (int i = 0; i < gq; ++i) thr[i] = state[i] == 2 ? INFINITY : ds[i].thr;
+      if ((r = sq_pass_threshold_scan(ix, gq, thr.data(), cap, counts, st))) return r;
+      sel.assign((size_t)gq, 0u);
+      unsigned grow = 0;
+      int64_t nsel = 0;
+      for (int i = 0; i < gq; ++i) {
+        if (state[i] == 2) continue;
+        ++ix->sq.thr_query_scans;
+        if (state[i] == 0) {
+          if (ds[i].next((int64_t)counts[i]) == PqDescent::SCAN) continue;
+          state[i] = 1;
+        }
+        if (counts[i] <= cap) {
+          sel[i] = counts[i];
+          nsel += counts[i];
+        } else {
+          grow = std::max(grow, counts[i]);
+        }
+      }
+      if (nsel > 0) {
+        HIPCHK(hipMemcpyAsync(ix->sqs.tfetch, sel.data(), (size_t)gq * sizeof(unsigned), hipMemcpyHostToDevice, st));
+        hd.resize((size_t)nsel);
+        hi.resize((size_t)nsel);
+        if ((r = range_fetch(ix, gq, sel, cap, hd.data(), hi.data(), ix->sqs.tfetch))) return r;
+        ix->sq.thr_hits += nsel;
+      }
+      int64_t at = 0;
+      for (int i = 0; i < gq; ++i) {
+        if (state[i] != 1 || counts[i] > cap) continue;
+        std::vector<Hit>& h = hits[i];
+        h.resize((size_t)sel[i]);
+        for (unsigned j = 0; j < sel[i]; ++j) h[j] = Hit(hd[(size_t)at + j], hi[(size_t)at + j]);
+        at += sel[i];
+        if ((int64_t)h.size() > (int64_t)k) {
+          std::nth_element(h.begin(), h.begin() + k, h.end(), better);
+          h.resize((size_t)k);
+        }
+        std::sort(h.begin(), h.end(), better);
+        state[i] = 2;
+        --left;
+      }
+      if (grow) {  // a final threshold whose hits overflowed its slice: regrow, scan it again
+        size_t want = ix->range.pool;
+        while (want / (size_t)gq < (size_t)grow) want <<= 1;
+        if (want > RANGE_POOL_MAX) return fail(KNNX_E_NOMEM, "large-k search result exceeds the 512 Mi-hit scratch limit");
+        if ((r = range_pool_alloc(ix, want))) return r;
+      }
+    }
+    ix->sq.thr_queries += gq;
+    for (int i = 0; i < gq; ++i) {
+      float* Dq = D + (size_t)(o + i) * k;
+      int64_t* Iq = I + (size_t)(o + i) * k;
+      const std::vector<Hit>& h = hits[i];
+      for (int j = 0; j < k; ++j) {
+        Dq[j] = j < (int)h.size() ? h[j].first : -FLT_MAX;
+        Iq[j] = j < (int)h.size() ? h[j].second : -1;
       }
     }
     o += gq;

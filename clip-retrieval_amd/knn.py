@@ -377,6 +377,24 @@ class Mi355xIndex(_FaissShaped):
         order = np.argsort(ids, kind="stable")
         return np.ascontiguousarray(codes[order][:, : self.d]), np.ascontiguousarray(lists[order])
 
+    @property
+    def sq_threshold_scan(self):
+        """The threshold mode of the code scan (include/knnx.h: knnx_ivfsq_set_threshold_scan): with it on, an IVF-SQ8 index serves
+        k > 64 (up to 131 072) and range_search; off -- the default -- it refuses both as it always has.  False on an index that is
+        not IVF-SQ8; setting it there is an error."""
+        return bool(self._lib.knnx_ivfsq_threshold_scan(self._h)) if self._h else False
+
+    @sq_threshold_scan.setter
+    def sq_threshold_scan(self, on):
+        check(self._lib, self._lib.knnx_ivfsq_set_threshold_scan(self._h, 1 if on else 0), "knnx")
+
+    def sq_threshold_stats(self):
+        """(queries served with k > 64, threshold-scan launches, launches summed over the queries that took part, hits fetched) since
+        the index was created (include/knnx.h: knnx_ivfsq_threshold_stats)."""
+        v = [C.c_int64(0) for _ in range(4)]
+        check(self._lib, self._lib.knnx_ivfsq_threshold_stats(self._h, *[C.byref(x) for x in v]), "knnx")
+        return tuple(int(x.value) for x in v)
+
     # ------------------------------------------------------------------ list-ordered ids (reorder_metadata_by_ivf_index)
     def ivf_old_to_new(self):
         """int64 [ntotal]: old_to_new[i] = id_base + the list-ordered ordinal of the row with id id_base + i (include/knnx.h,
@@ -596,6 +614,16 @@ class ShardedMi355xIndex(_FaissShaped):
     def pq_threshold_scan(self, on):
         for g in range(self.nshards):
             check(self._lib, self._lib.knnx_ivfpq_set_threshold_scan(C.c_void_p(self._lib.knnx_shards_get(self._h, g)), 1 if on else 0), "knnx")
+
+    @property
+    def sq_threshold_scan(self):
+        """The IVF-SQ8 threshold-scan switch as carried by the first shard (Mi355xIndex.sq_threshold_scan); the setter sets every shard."""
+        return bool(self._lib.knnx_ivfsq_threshold_scan(C.c_void_p(self._lib.knnx_shards_get(self._h, 0)))) if self.nshards else False
+
+    @sq_threshold_scan.setter
+    def sq_threshold_scan(self, on):
+        for g in range(self.nshards):
+            check(self._lib, self._lib.knnx_ivfsq_set_threshold_scan(C.c_void_p(self._lib.knnx_shards_get(self._h, g)), 1 if on else 0), "knnx")
 
     @property
     def nshards(self):
@@ -2153,9 +2181,25 @@ def check_ivfsq_manifest(man, where=""):
     return man
 
 
-def _ivfsq_begin(d, nlist, centroids, ranges, sizes, device, id_base):
+def ivfsq_threshold_scan_entry(on):
+    """What a saved IVF-SQ8 manifest says about the threshold-scan switch: {"threshold_scan": true} when it is on, nothing otherwise."""
+    return {"threshold_scan": True} if on else {}
+
+
+def read_ivfsq_threshold_scan(folder, man):
+    """The threshold-scan switch of a saved IVF-SQ8 folder: False where the manifest has no such key (folders saved before the switch
+    existed, and every folder saved with it off)."""
+    v = man.get("threshold_scan", False)
+    if not isinstance(v, bool):
+        raise ValueError(f"{folder}: \"threshold_scan\" must be true or false, got {v!r}")
+    return v
+
+
+def _ivfsq_begin(d, nlist, centroids, ranges, sizes, device, id_base, threshold_scan=False):
     index = Mi355xIndex(d, device=device, id_base=id_base)
     index.set_sq_quantizer(*ranges)
+    if threshold_scan:  # (off is the state of a new index: nothing is called for it)
+        index.sq_threshold_scan = True
     cpad = np.ascontiguousarray(index._pad(np.asarray(centroids, dtype=np.float16)))  # pylint: disable=protected-access
     check(index._lib, index._lib.knnx_ivf_begin(index._h, nlist, cpad.ctypes.data, np.ascontiguousarray(sizes, dtype=np.int64).ctypes.data), "knnx")  # pylint: disable=protected-access
     return index
@@ -2170,12 +2214,12 @@ def _ivfsq_end(index, nlist, nprobe, centroids, id_base, n, lists=None):
     return index
 
 
-def _ivfsq_encode_chunks(chunks, n, d, nlist, centroids, ranges, lists, nprobe, device, id_base):
+def _ivfsq_encode_chunks(chunks, n, d, nlist, centroids, ranges, lists, nprobe, device, id_base, threshold_scan=False):
     """Rows (an iterator of (offset, fp16 rows)) -> IVF-SQ8 index: every row is encoded into the next free slot of its list."""
     sizes = np.bincount(lists, minlength=nlist).astype(np.int64)
     if sizes.shape[0] != nlist:
         raise ValueError("a list id is outside [0, nlist)")
-    index = _ivfsq_begin(d, nlist, centroids, ranges, sizes, device, id_base)
+    index = _ivfsq_begin(d, nlist, centroids, ranges, sizes, device, id_base, threshold_scan)
     lib = index._lib  # pylint: disable=protected-access
     cursor = np.zeros(nlist, dtype=np.int64)
     for o, x in chunks:
@@ -2187,10 +2231,12 @@ def _ivfsq_encode_chunks(chunks, n, d, nlist, centroids, ranges, lists, nprobe, 
     return _ivfsq_end(index, nlist, nprobe, centroids, id_base, n, lists)
 
 
-def build_ivfsq_index(x_f16, nlist, nprobe=16, niter=8, seed=0, device=0, id_base=0, centroids=None, ranges=None, chunk=1 << 20):
+def build_ivfsq_index(x_f16, nlist, nprobe=16, niter=8, seed=0, device=0, id_base=0, centroids=None, ranges=None, chunk=1 << 20,
+                      threshold_scan=False):
     """fp16 rows [N, d] -> HBM-resident IVF-SQ8 index (ids = id_base + row number).  `centroids` (fp16 [nlist, d]) and `ranges`
     ((vmin, vdiff), f32 [d]) can be given; by default both are trained on the rows (train_ivf_centroids, train_sq_ranges).  Lists by
-    the MFMA assignment kernel, codes by the device encoder.  Shards of one index MUST share centroids and ranges."""
+    the MFMA assignment kernel, codes by the device encoder.  Shards of one index MUST share centroids and ranges.
+    threshold_scan=True switches on k > 64 and range_search (Mi355xIndex.sq_threshold_scan; off by default)."""
     n, d = x_f16.shape
     if centroids is None:
         centroids = train_ivf_centroids(x_f16, nlist, niter=niter, seed=seed, device=device)
@@ -2199,14 +2245,14 @@ def build_ivfsq_index(x_f16, nlist, nprobe=16, niter=8, seed=0, device=0, id_bas
     centroids = np.asarray(centroids).astype(np.float16)
     lists, _ = _assign_chunks(((o, x_f16[o:o + chunk]) for o in range(0, n, chunk)), n, d, nlist, centroids, device, None)
     return _ivfsq_encode_chunks(((o, x_f16[o:o + chunk]) for o in range(0, n, chunk)), n, d, nlist, centroids, ranges, lists, nprobe, device,
-                                id_base)
+                                id_base, threshold_scan)
 
 
 def build_ivfsq_index_from_folder(path, nlist, nprobe=16, niter=8, seed=0, device=0, centroids=None, ranges=None,
-                                  max_points_per_centroid=256, chunk=1 << 20):
+                                  max_points_per_centroid=256, chunk=1 << 20, threshold_scan=False):
     """`clip inference` output folder (img_emb_*.npy) -> IVF-SQ8 index, streaming the partitions: training on a strided sample of the
     whole folder (centroids and ranges, unless given), then one assignment pass and one encoding pass.  The result can be
-    save_index()ed: the folder is self-contained (codes, not rows)."""
+    save_index()ed: the folder is self-contained (codes, not rows).  threshold_scan as in build_ivfsq_index."""
     src = path if isinstance(path, FolderRows) else FolderRows(path)
     if centroids is None or ranges is None:
         take = min(src.n, int(nlist) * int(max_points_per_centroid))
@@ -2217,14 +2263,15 @@ def build_ivfsq_index_from_folder(path, nlist, nprobe=16, niter=8, seed=0, devic
             ranges = train_sq_ranges(sample, device=device, chunk=chunk)
     centroids = np.asarray(centroids).astype(np.float16)
     lists, _ = _assign_chunks(src.chunks(0, src.n, chunk), src.n, src.d, nlist, centroids, device, None)
-    return _ivfsq_encode_chunks(src.chunks(0, src.n, chunk), src.n, src.d, nlist, centroids, ranges, lists, nprobe, device, 0)
+    return _ivfsq_encode_chunks(src.chunks(0, src.n, chunk), src.n, src.d, nlist, centroids, ranges, lists, nprobe, device, 0, threshold_scan)
 
 
 def build_ivfsq_index_device(fill_rows, n, d, nlist, nprobe=16, niter=8, seed=0, device=0, id_base=0, centroids=None, ranges=None,
-                             chunk=1 << 20, alloc=None, points_per_centroid=64, keep_lists=False):
+                             chunk=1 << 20, alloc=None, points_per_centroid=64, keep_lists=False, threshold_scan=False):
     """IVF-SQ8 index over n rows PRODUCED ON THE GPU (`fill_rows(dst_ptr, row0, count, stride)` as in build_ivf_index_device, which
     must have COMPLETED when it returns): the fp16 corpus never exists whole -- a training sample (centroids and ranges, unless
-    given), then per chunk one assignment pass and one encoding pass; the index keeps d bytes per row.  Returns (index, stats dict)."""
+    given), then per chunk one assignment pass and one encoding pass; the index keeps d bytes per row.  threshold_scan as in
+    build_ivfsq_index.  Returns (index, stats dict)."""
     import time  # pylint: disable=import-outside-toplevel
 
     assert d % 256 == 0, "device builds take padded rows (d % 256 == 0)"
@@ -2262,7 +2309,7 @@ def build_ivfsq_index_device(fill_rows, n, d, nlist, nprobe=16, niter=8, seed=0,
     b.close()
     _release_cached_device_memory()
     t2 = time.perf_counter()
-    index = _ivfsq_begin(d, nlist, centroids, ranges, sizes, device, id_base)
+    index = _ivfsq_begin(d, nlist, centroids, ranges, sizes, device, id_base, threshold_scan)
     for o in range(0, n, chunk):
         m = min(chunk, n - o)
         fill_rows(rows_ptr, o, m, 1)
@@ -2279,7 +2326,8 @@ def build_ivfsq_index_device(fill_rows, n, d, nlist, nprobe=16, niter=8, seed=0,
 
 def _save_ivfsq_index(index, folder):
     """The self-contained IVF-SQ8 folder: ivf_sq_centroids.npy (fp16 [nlist, d]), ivf_sq_vmin.npy / ivf_sq_vdiff.npy (f32 [d]),
-    ivf_sq_codes.npy (u8 [n, d] in id order), ivf_sq_lists.npy (int32 [n]) and ivf_sq_manifest.json (kind "ivfsq", written last)."""
+    ivf_sq_codes.npy (u8 [n, d] in id order), ivf_sq_lists.npy (int32 [n]) and ivf_sq_manifest.json (kind "ivfsq", written last).  An
+    index with the threshold scan switched on adds "threshold_scan": true (only then: other folders are byte-identical to before)."""
     import json  # pylint: disable=import-outside-toplevel
 
     cent = getattr(index, "ivf_centroids", None)
@@ -2295,6 +2343,7 @@ def _save_ivfsq_index(index, folder):
     np.save(os.path.join(folder, "ivf_sq_codes.npy"), codes)
     np.save(os.path.join(folder, "ivf_sq_lists.npy"), lists)
     man = ivfsq_manifest(index.d, cent.shape[0], index.nprobe, (lo, hi))
+    man.update(ivfsq_threshold_scan_entry(index.sq_threshold_scan))
     tmp = os.path.join(folder, IVFSQ_MANIFEST + ".part")
     with open(tmp, "w", encoding="utf-8") as f:
         json.dump(man, f, indent=1)
@@ -2302,11 +2351,11 @@ def _save_ivfsq_index(index, folder):
     return man
 
 
-def _ivfsq_from_codes(codes, lists, lo, cent, ranges, nprobe, device, chunk=1 << 20):
+def _ivfsq_from_codes(codes, lists, lo, cent, ranges, nprobe, device, chunk=1 << 20, threshold_scan=False):
     nlist, d = cent.shape
     n = codes.shape[0]
     sizes = np.bincount(lists, minlength=nlist).astype(np.int64)
-    index = _ivfsq_begin(d, nlist, cent, ranges, sizes, device, lo)
+    index = _ivfsq_begin(d, nlist, cent, ranges, sizes, device, lo, threshold_scan)
     lib = index._lib  # pylint: disable=protected-access
     cursor = np.zeros(nlist, dtype=np.int64)
     for o in range(0, n, chunk):
@@ -2323,6 +2372,7 @@ def _load_ivfsq_index(folder, device=0, row_range=None, devices=None):
 
     with open(os.path.join(folder, IVFSQ_MANIFEST), encoding="utf-8") as f:
         man = check_ivfsq_manifest(json.load(f), folder)
+    thr_scan = read_ivfsq_threshold_scan(folder, man)
     cent = np.load(os.path.join(folder, "ivf_sq_centroids.npy"))
     ranges = (np.load(os.path.join(folder, "ivf_sq_vmin.npy")), np.load(os.path.join(folder, "ivf_sq_vdiff.npy")))
     codes = np.load(os.path.join(folder, "ivf_sq_codes.npy"), mmap_mode="r")
@@ -2337,11 +2387,12 @@ def _load_ivfsq_index(folder, device=0, row_range=None, devices=None):
         G = len(devices)
         cuts = [slo + (shi - slo) * g // G for g in range(G + 1)]
         shards = [_ivfsq_from_codes(codes[cuts[g] - slo:cuts[g + 1] - slo], np.asarray(lists[cuts[g] - slo:cuts[g + 1] - slo]), cuts[g], cent,
-                                    ranges, man["nprobe"], devices[g]) for g in range(G)]
+                                    ranges, man["nprobe"], devices[g], threshold_scan=thr_scan) for g in range(G)]
         sharded = ShardedMi355xIndex.from_shards(shards, cuts[:-1])
         sharded.nprobe = man["nprobe"]
         return sharded
     lo, hi = (slo, shi) if row_range is None else (int(row_range[0]), int(row_range[1]))
     if not slo <= lo <= hi <= shi:
         raise ValueError(f"row_range {row_range} is outside the saved shard's rows [{slo}, {shi})")
-    return _ivfsq_from_codes(codes[lo - slo:hi - slo], np.asarray(lists[lo - slo:hi - slo]), lo, cent, ranges, man["nprobe"], device)
+    return _ivfsq_from_codes(codes[lo - slo:hi - slo], np.asarray(lists[lo - slo:hi - slo]), lo, cent, ranges, man["nprobe"], device,
+                             threshold_scan=thr_scan)

@@ -415,7 +415,8 @@ class KnnHotPath:
         An IVF-PQ index serves num_result_ids <= 64 as it stands; the Python default of 100, the front end's 3 000 and the >= 100 000
         requests of the probe-widening branch below need its threshold scan switched on (Mi355xIndex.pq_threshold_scan, or
         threshold_scan=True at build time; saved with the index) -- without it the index answers them with KNNX_E_UNSUPPORTED, which
-        is raised, never papered over.  No branch of this function depends on the switch."""
+        is raised, never papered over.  An IVF-SQ8 index has the same rule and its own switch (Mi355xIndex.sq_threshold_scan).  No
+        branch of this function depends on either switch."""
         to_new = self._ivf_id_mapper(clip_resource)
         index = clip_resource.image_index if modality == "image" else clip_resource.text_index
         # clip_back.py:356-369: a request for >= 100 000 results widens the IVF probe to ceil(k / 3000) lists for the duration of the

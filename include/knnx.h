@@ -329,7 +329,8 @@ int knnx_pqb_lloyd(knnx_pq_builder* b, uint8_t* codes_out, int64_t* sizes_out);
  * knnx_ivf_set_nprobe, knnx_ivf_id_order / knnx_ivf_map_ids, knnx_ivf_last_scan_tiles (bytes read = tiles * 32 * d), and
  * knnx_shards_adopt of IVF-SQ8 shards that carry the same quantiser bit for bit (a different one, or a mix with another index kind,
  * is refused with a message) -- all with k <= 64 and any n: every batch is ONE multi-block pass per 256 queries (1 .. 32 queries are
- * one block), so the ids do not depend on the batch size.  Refused: k > 64 and knnx_range_search* answer KNNX_E_UNSUPPORTED; add /
+ * one block), so the ids do not depend on the batch size.  Refused: k > 64 and knnx_range_search* answer KNNX_E_UNSUPPORTED unless the
+ * threshold scan is switched on (next block); add /
  * attach / synth_fill / reset / reserve / knnx_ivf_set_lists answer KNNX_E_STATE; every such message says "IVF-SQ8".  An index nobody
  * gave an SQ8 quantiser is exactly the blocks above and below, byte for byte: it allocates and launches nothing of this. */
 int knnx_ivfsq_set_quantizer(knnx_index* ix, const float* vmin, const float* vdiff);
@@ -337,6 +338,27 @@ int knnx_ivfsq_get_quantizer(knnx_index* ix, float* vmin, float* vdiff);
 int knnx_ivfsq(const knnx_index* ix); /* 0 / 1 */
 int knnx_ivfsq_add_codes(knnx_index* ix, const uint8_t* codes, int64_t n, const int64_t* ids, const int32_t* lists, const int32_t* pos);
 int knnx_ivfsq_get_codes(knnx_index* ix, int64_t* ids, int32_t* lists, uint8_t* codes);
+/* ---- Threshold scan on IVF-SQ8: k > 64 and range_search (clip_back.py:356-369 asks for up to 1e5 results; clip_filter.py:52) --------
+ * A switch per index, OFF by default: an index nobody switched on is exactly the block above, refusals included (the two messages
+ * byte for byte), and allocates and launches nothing of this.
+ * knnx_ivfsq_set_threshold_scan: any IVF-SQ8 index, any time; KNNX_E_STATE on any other index (the message says "IVF-SQ8").
+ * knnx_ivfsq_threshold_scan: 0 / 1; 0 on a non-SQ8 or null index.  With the switch ON:
+ *   search    64 < k <= 131072: the top k rows of the probed lists by (score descending, id ascending), padded with -1 / -FLT_MAX -- the
+ *             contract of the IVF-SQ8 block for k <= 64, extended.  The scores are the SAME fp32 values (same operands, same MFMA order,
+ *             same two roundings around inv_q and b_q), so the first 64 results of a k > 64 search equal the k = 64 search bit for bit,
+ *             D and I, and a query gets the same ids alone and in a batch.  R comes from knnx_reconstruct: the decoded rows.  How: the
+ *             code scan in threshold mode (every valid row of the probed lists scoring > t is a hit) with t walked down from the
+ *             query's 64th score until at least k rows pass; queries run in groups of up to 256 over ONE coarse half and ONE set of work
+ *             lists, one launch and one synchronisation per step; the hits are ranked on the host.
+ *   range     knnx_range_search / knnx_range_search_once: all rows of the probed lists whose score is > thresh (strict), ids ascending
+ *             inside each query; two-call protocol, the _once return value 1 and KNNX_E_STATE on mismatching lims as for IVF-Flat.
+ * knnx_search_device, knnx_search_dedup and the coalescer stay at k <= 64 and keep their messages; builds and knnx_ivfsq_add_codes are
+ * unchanged.  Shards: every shard answers for itself (a shard with the switch off gives its own refusal).
+ * knnx_ivfsq_threshold_stats: counters since the index was created -- queries served with k > 64, threshold-scan launches (one serves
+ * a whole group of queries), launches summed over the queries that took part in them, hits fetched to the host; any pointer may be null. */
+int knnx_ivfsq_set_threshold_scan(knnx_index* ix, int on);
+int knnx_ivfsq_threshold_scan(const knnx_index* ix);   /* 0 / 1; 0 on a non-SQ8 or null index */
+int knnx_ivfsq_threshold_stats(knnx_index* ix, int64_t* queries, int64_t* launches, int64_t* query_scans, int64_t* hits);
 /* The training kernel (faiss RS_minmax with argument 0): per-column min and max of n fp16 rows [n][d] in HBM, 0 < d <= 1024, n > 0 ->
  * host f32 vmin_out [d], vmax_out [d].  Min and max do not depend on the order of the rows: bit-equal to numpy's
  * x.astype(float32).min(0) / .max(0).  `stream`: hipStream_t or NULL; synchronous. */

@@ -6,6 +6,12 @@ streamed over the same corpus.  Prints ONE JSON line.
 
   python tools/ivfsq_bench.py                                     # 16 M x 1024, nlist 16 384, nprobe 16 / 64 / 256, B = 1 / 32 / 256
   python tools/ivfsq_bench.py --rows 4000000 --d 768 --nlist 4096
+  python tools/ivfsq_bench.py --nprobes 64 --large-k 100,3000      # and k > 64 through the threshold scan, against IVF-Flat's large-k path
+
+--large-k K1,K2: the IVF-SQ8 index is built with its threshold scan switched on (Mi355xIndex.sq_threshold_scan; the k <= 64 paths do not
+depend on it); at nprobe 64, for k = 64 and every listed k, one query and a 32-query batch through Mi355xIndex.search (host buffers) on
+both indexes alternately, --reps repeats, the median; with the threshold scans per query and the hits fetched per query from
+sq_threshold_stats().
 """
 import argparse
 import json
@@ -29,6 +35,7 @@ def main():
     ap.add_argument("--nprobes", default="16,64,256")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--recall-queries", type=int, default=64)
+    ap.add_argument("--large-k", default="", help="comma-separated k > 64: time them at nprobe 64 against IVF-Flat (see the module text)")
     a = ap.parse_args()
 
     import torch
@@ -48,7 +55,9 @@ def main():
         torch.cuda.synchronize()
         return ix, st, time.perf_counter() - t0, free0 - torch.cuda.mem_get_info()[0]
 
-    sq, ss, sq_s, sq_used = built(lambda: build_ivfsq_index_device(fill_rows, n, d, a.nlist, nprobe=16, niter=6, seed=0))
+    large_ks = [int(v) for v in a.large_k.split(",") if v]
+    sq, ss, sq_s, sq_used = built(lambda: build_ivfsq_index_device(fill_rows, n, d, a.nlist, nprobe=16, niter=6, seed=0,
+                                                                   threshold_scan=bool(large_ks)))
     flat, sf, flat_s, flat_used = built(lambda: build_ivf_index_device(fill_rows, n, d, a.nlist, nprobe=16, niter=6, seed=0))
     padded = int(((np.asarray(ss["list_sizes"]) + 31) // 32 * 32).sum())
     out = {"rows": n, "d": d, "nlist": a.nlist, "padded_rows": padded,
@@ -131,6 +140,37 @@ def main():
                           "scan_TBps_ivf_flat": round(tiles_fl * 32 * d * 2 / (ms_fl * 1e-3) / 1e12, 2) if ms_fl else None}
         grid[f"np{npb}"] = e
     out["search"] = grid
+
+    if large_ks:
+        sq.nprobe = flat.nprobe = 64
+        lk = {"nprobe": 64, "reps": a.reps}
+        for kk in [64] + large_ks:
+            e = {}
+            for B in (1, 32):
+                qq = q[:B]
+                sq.search(qq, kk)  # warm-up: pools, pinned staging
+                flat.search(qq, kk)
+                s0 = sq.sq_threshold_stats()
+                ts, tf = [], []
+                for _ in range(a.reps):  # the two indexes alternately
+                    t0 = time.perf_counter()
+                    sq.search(qq, kk)
+                    ts.append(time.perf_counter() - t0)
+                    t0 = time.perf_counter()
+                    flat.search(qq, kk)
+                    tf.append(time.perf_counter() - t0)
+                s1 = sq.sq_threshold_stats()
+                t_sq, t_fl = float(np.median(ts)), float(np.median(tf))
+                served = max(1, s1[0] - s0[0])
+                e[f"B{B}"] = {"ms_sq8": round(t_sq * 1e3, 3), "ms_ivf_flat": round(t_fl * 1e3, 3), "speedup": round(t_fl / t_sq, 3),
+                              "threshold_launches": s1[1] - s0[1],
+                              "threshold_scans_per_query": round((s1[2] - s0[2]) / served, 2) if kk > 64 else 0,
+                              "hits_fetched_per_query": round((s1[3] - s0[3]) / served, 1) if kk > 64 else 0}
+            lk[f"k{kk}"] = e
+        for kk in large_ks:
+            for B in (1, 32):
+                lk[f"k{kk}"][f"B{B}"]["ms_sq8_over_k64"] = round(lk[f"k{kk}"][f"B{B}"]["ms_sq8"] / lk["k64"][f"B{B}"]["ms_sq8"], 2)
+        out["large_k"] = lk
     sq.close()
     flat.close()
     print(json.dumps(out))

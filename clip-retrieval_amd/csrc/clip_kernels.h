@@ -86,7 +86,7 @@ int gemm256_tail_blocks(int N, int K, int n_cu);
 hipError_t launch_gemm(const GemmArgs& g, hipStream_t st);
 
 // x f32 [M, d] -> y [M, d]; out_kind 0: f32, 1: bf16, 2: IEEE fp16 (ln_pre of the vision tower writes the fp16 residual
-// stream); one wave per row; d % 256 == 0, d <= 2048.  y16 (f32 output only, may be null): also the bf16 rounding of y
+// stream); one wave per row; d % 128 == 0, d <= 2048.  y16 (f32 output only, may be null): also the bf16 rounding of y
 hipError_t launch_layernorm(const float* x, const float* gamma, const float* beta, void* y, int out_kind, int M,
                             int d, float eps, hipStream_t st, bf16* y16 = nullptr);
 
@@ -110,7 +110,7 @@ hipError_t launch_fill_f32(float* p, float v, int64_t n, hipStream_t st);
 hipError_t launch_im2col(const void* pixels, int fmt, int B, int S, int P, int Kp, const float* mean,
                          const float* stdv, bf16* out, hipStream_t st);
 
-// qkv bf16 [B*T, 3*H*dh] -> out bf16 [B*T, H*dh]; softmax(q k^T / sqrt(dh) [+ causal]) v, head dim dh = 64 or 80
+// qkv bf16 [B*T, 3*H*dh] -> out bf16 [B*T, H*dh]; softmax(q k^T / sqrt(dh) [+ causal]) v, head dim dh = 64, 80, 88 or 104 (88 / 104: not causal, T <= 96 or 257 .. 288)
 // q_blocks > 0: only the first q_blocks 32-row query blocks are computed (rows past them are left untouched); 0 = all
 // offs / lens (both or neither; head dim 64, T <= 128): ragged batch -- sample b owns rows offs[b] .. offs[b] + lens[b] - 1
 hipError_t launch_attention(const bf16* qkv, bf16* out, int B, int T, int H, int dh, int causal, hipStream_t st, int q_blocks = 0,

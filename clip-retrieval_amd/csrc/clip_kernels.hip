@@ -615,11 +615,14 @@ hipError_t launch_gemm(const GemmArgs& g0, hipStream_t st) {
 // =============================================================================================
 // LayerNorm: one wave per row, fp32 statistics (two-pass in registers)
 // =============================================================================================
-template <int NV, int OUT>  // d = NV * 256; OUT 0: f32 (+ optional bf16 copy), 1: bf16, 2: IEEE fp16
+// Widths are multiples of 128 (D128 = d / 128).  A lane takes 4 consecutive values per step and a wave 256, so an odd D128 (1408 and
+// 1664: the ViT-g/14 and ViT-bigG/14 image towers) ends in a half step that only lanes 0 .. 31 take part in (the `D128 % 2 != 0 &&`
+// tests below).  For an even D128 the test is the constant false, and the kernels compile to the code they always have.
+template <int D128, int OUT>  // d = D128 * 128; OUT 0: f32 (+ optional bf16 copy), 1: bf16, 2: IEEE fp16
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                        const float* __restrict__ beta, void* __restrict__ y, int M,
                                                        float eps, bf16* __restrict__ y16) {
-  constexpr int d = NV * 256;
+  constexpr int d = D128 * 128, NV = (D128 + 1) / 2;
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= M) return;
@@ -628,6 +631,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
   float s = 0.f;
 #pragma unroll
   for (int e = 0; e < NV; ++e) {
+    if (D128 % 2 != 0 && e == D128 / 2 && lane >= 32) continue;  // the half step of an odd D128
     v[e] = xr[lane + 64 * e];
     s += (v[e].x + v[e].y) + (v[e].z + v[e].w);
   }
@@ -636,6 +640,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
   float q = 0.f;
 #pragma unroll
   for (int e = 0; e < NV; ++e) {
+    if (D128 % 2 != 0 && e == D128 / 2 && lane >= 32) continue;  // the half step of an odd D128
     const float a = v[e].x - mean, b = v[e].y - mean, c = v[e].z - mean, dd = v[e].w - mean;
     q += (a * a + b * b) + (c * c + dd * dd);
   }
@@ -643,6 +648,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
   const float rstd = 1.f / sqrtf(q * (1.f / d) + eps);
 #pragma unroll
   for (int e = 0; e < NV; ++e) {
+    if (D128 % 2 != 0 && e == D128 / 2 && lane >= 32) continue;  // the half step of an odd D128
     const int c4 = lane + 64 * e;
     const float4 g4 = reinterpret_cast<const float4*>(gamma)[c4];
     const float4 b4 = reinterpret_cast<const float4*>(beta)[c4];
@@ -670,11 +676,12 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
   }
 }
 
-// rstd of the bf16 shadow rows (see clip_kernels.h: launch_rowstats); d = NV * 512: a lane holds NV x 8 consecutive values
-template <int NV2, bool F16>  // d = NV2 * 256 (NV2 x 4 values per lane); F16: rows are IEEE fp16, else bf16
+// rstd of the 16-bit shadow rows (see clip_kernels.h: launch_rowstats), two passes in registers: a lane holds 4 consecutive values
+// per step of 256, the last step of an odd D128 in lanes 0 .. 31 only
+template <int D128, bool F16>  // d = D128 * 128; F16: rows are IEEE fp16, else bf16
 __global__ __launch_bounds__(256) void rowstats_kernel(const void* __restrict__ x16, float* __restrict__ rstd, int M, float eps,
                                                        int* __restrict__ range_flag) {
-  constexpr int d = NV2 * 256;
+  constexpr int d = D128 * 128, NV2 = (D128 + 1) / 2;
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= M) return;
@@ -683,6 +690,7 @@ __global__ __launch_bounds__(256) void rowstats_kernel(const void* __restrict__ 
   float s = 0.f;
 #pragma unroll
   for (int e = 0; e < NV2; ++e) {
+    if (D128 % 2 != 0 && e == D128 / 2 && lane >= 32) continue;  // the half step of an odd D128
     const uint2 raw = xr[lane + 64 * e];
     if (F16) {
       const f16x4 h = __builtin_bit_cast(f16x4, raw);
@@ -705,6 +713,7 @@ __global__ __launch_bounds__(256) void rowstats_kernel(const void* __restrict__ 
   float q = 0.f;
 #pragma unroll
   for (int e = 0; e < NV2; ++e) {
+    if (D128 % 2 != 0 && e == D128 / 2 && lane >= 32) continue;  // the half step of an odd D128
     const float a = v[e][0] - mean, b = v[e][1] - mean, c = v[e][2] - mean, dd = v[e][3] - mean;
     q += (a * a + b * b) + (c * c + dd * dd);
   }
@@ -714,17 +723,19 @@ __global__ __launch_bounds__(256) void rowstats_kernel(const void* __restrict__ 
 
 // The fp16 stream: ONE pass in the canonical order (gemm_common.h: ln_rstd_onepass) -- four lanes per row (lane = r16 + 16 q4, the
 // fragment layout of the 4-wave GEMM kernel, which computes the same sums for the rows it multiplies), lane part q4 takes the 16-B
-// chunks q4, q4 + 4, ..; a wave covers 16 rows, a workgroup 64.
-template <int NV2>  // d = NV2 * 256
+// chunks q4, q4 + 4, ..; a wave covers 16 rows, a workgroup 64.  Widths that are odd multiples of 128 (1408, 1664: 44 and 52 chunks
+// per lane part) keep 4 chunks in flight instead of 8; the sums are one chain per lane part in ascending chunk order whatever the
+// number in flight, which is the order of the GEMM's K loop at any K that is a multiple of 128: the same bits at the new widths too.
+template <int D128>  // d = D128 * 128
 __global__ __launch_bounds__(256) void rowstats_f16_kernel(const void* __restrict__ x16, float* __restrict__ rstd, int M, float eps,
                                                            int* __restrict__ range_flag) {
-  constexpr int d = NV2 * 256, NCH = d / 8;
+  constexpr int d = D128 * 128, NCH = d / 8;
   const int lane = threadIdx.x & 63, q4 = lane >> 4, r16 = lane & 15;
   const int row = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 16 + r16;
   const uint4* xr = reinterpret_cast<const uint4*>(reinterpret_cast<const uint16_t*>(x16) + (size_t)(row < M ? row : M - 1) * d);
   const unsigned ones2 = __builtin_amdgcn_readfirstlane(0x3c003c00u);
   float s1 = 0.f, s2 = 0.f;
-  constexpr int U = 8;  // chunks in flight per lane
+  constexpr int U = D128 % 2 == 0 ? 8 : 4;  // chunks in flight per lane
   static_assert((NCH / 4) % U == 0, "row length");
   for (int j0 = 0; j0 < NCH / 4; j0 += U) {
     uint4 c[U];
@@ -751,25 +762,27 @@ hipError_t launch_rowstats(const void* x16, float* rstd, int M, int d, float eps
   if (M <= 0) return hipSuccess;
   if (f16 && canonical) {
     const dim3 grid((M + 63) / 64), block(256);
-#define RSH_CASE(NV)                                                                                           \
-  case NV * 256:                                                                                               \
-    launch_with_events(events, rowstats_f16_kernel<NV>, grid, block, 0, st, x16, rstd, M, eps, range_flag);   \
+#define RSH_CASE(D128)                                                                                         \
+  case D128 * 128:                                                                                             \
+    launch_with_events(events, rowstats_f16_kernel<D128>, grid, block, 0, st, x16, rstd, M, eps, range_flag); \
     break;
     switch (d) {
-      RSH_CASE(1) RSH_CASE(2) RSH_CASE(3) RSH_CASE(4) RSH_CASE(5) RSH_CASE(6) RSH_CASE(7) RSH_CASE(8)
+      RSH_CASE(2) RSH_CASE(4) RSH_CASE(6) RSH_CASE(8) RSH_CASE(10) RSH_CASE(12) RSH_CASE(14) RSH_CASE(16)
+      RSH_CASE(1) RSH_CASE(3) RSH_CASE(5) RSH_CASE(7) RSH_CASE(9) RSH_CASE(11) RSH_CASE(13) RSH_CASE(15)
       default: return hipErrorInvalidValue;
     }
 #undef RSH_CASE
     return hipGetLastError();
   }
   const dim3 grid((M + 3) / 4), block(256);
-#define RS_CASE(NV)                                                                                        \
-  case NV * 256:                                                                                           \
-    if (f16) launch_with_events(events, rowstats_kernel<NV, true>, grid, block, 0, st, x16, rstd, M, eps, range_flag);   \
-    else launch_with_events(events, rowstats_kernel<NV, false>, grid, block, 0, st, x16, rstd, M, eps, range_flag);      \
+#define RS_CASE(D128)                                                                                      \
+  case D128 * 128:                                                                                         \
+    if (f16) launch_with_events(events, rowstats_kernel<D128, true>, grid, block, 0, st, x16, rstd, M, eps, range_flag); \
+    else launch_with_events(events, rowstats_kernel<D128, false>, grid, block, 0, st, x16, rstd, M, eps, range_flag);    \
     break;
   switch (d) {
-    RS_CASE(1) RS_CASE(2) RS_CASE(3) RS_CASE(4) RS_CASE(5) RS_CASE(6) RS_CASE(7) RS_CASE(8)
+    RS_CASE(2) RS_CASE(4) RS_CASE(6) RS_CASE(8) RS_CASE(10) RS_CASE(12) RS_CASE(14) RS_CASE(16)
+    RS_CASE(1) RS_CASE(3) RS_CASE(5) RS_CASE(7) RS_CASE(9) RS_CASE(11) RS_CASE(13) RS_CASE(15)
     default: return hipErrorInvalidValue;
   }
 #undef RS_CASE
@@ -817,14 +830,15 @@ hipError_t launch_layernorm(const float* x, const float* gamma, const float* bet
                             float eps, hipStream_t st, bf16* y16) {
   if (M <= 0) return hipSuccess;
   const dim3 grid((M + 3) / 4), block(256);
-#define LN_CASE(NV)                                                                                           \
-  case NV * 256:                                                                                              \
-    if (out_kind == 1) hipLaunchKernelGGL((layernorm_kernel<NV, 1>), grid, block, 0, st, x, gamma, beta, y, M, eps, (bf16*)nullptr); \
-    else if (out_kind == 2) hipLaunchKernelGGL((layernorm_kernel<NV, 2>), grid, block, 0, st, x, gamma, beta, y, M, eps, (bf16*)nullptr); \
-    else hipLaunchKernelGGL((layernorm_kernel<NV, 0>), grid, block, 0, st, x, gamma, beta, y, M, eps, y16);    \
+#define LN_CASE(D128)                                                                                         \
+  case D128 * 128:                                                                                            \
+    if (out_kind == 1) hipLaunchKernelGGL((layernorm_kernel<D128, 1>), grid, block, 0, st, x, gamma, beta, y, M, eps, (bf16*)nullptr); \
+    else if (out_kind == 2) hipLaunchKernelGGL((layernorm_kernel<D128, 2>), grid, block, 0, st, x, gamma, beta, y, M, eps, (bf16*)nullptr); \
+    else hipLaunchKernelGGL((layernorm_kernel<D128, 0>), grid, block, 0, st, x, gamma, beta, y, M, eps, y16);  \
     break;
   switch (d) {
-    LN_CASE(1) LN_CASE(2) LN_CASE(3) LN_CASE(4) LN_CASE(5) LN_CASE(6) LN_CASE(7) LN_CASE(8)
+    LN_CASE(2) LN_CASE(4) LN_CASE(6) LN_CASE(8) LN_CASE(10) LN_CASE(12) LN_CASE(14) LN_CASE(16)
+    LN_CASE(1) LN_CASE(3) LN_CASE(5) LN_CASE(7) LN_CASE(9) LN_CASE(11) LN_CASE(13) LN_CASE(15)
     default: return hipErrorInvalidValue;
   }
 #undef LN_CASE
@@ -894,7 +908,7 @@ hipError_t launch_im2col(const void* pixels, int fmt, int B, int S, int P, int K
 }
 
 // =============================================================================================
-// Attention (head dim DH = 64 or 80): one workgroup per (batch, head); K (row-major) and V^T in LDS.
+// Attention (head dim DH = 64, 80, 88 or 104): one workgroup per (batch, head); K (row-major) and V^T in LDS.
 //   S^T = K Q^T   (MFMA A = K rows, B = Q rows): a lane holds 16 keys x NKB blocks of ONE query column
 //   softmax over the lane's registers + one exchange with lane^32; P stays in registers as the B operand
 //   O^T = V^T P^T (MFMA A = V^T rows from LDS, B = P): a lane ends with 4 consecutive d of its query -> 8-B stores
@@ -929,16 +943,32 @@ __device__ int g_attn_pk_timer = 0;  // set by launch_attention_pk9 from CLIPX_A
 // RAGGED (not causal, offs / lens given): a sample shorter than the launch's NKB - 1 blocks has padding keys in EVERY block from
 // its own last one on, so the key < T mask runs in all of them -- the plain form masks the last block only, and the zeroed K rows
 // of the blocks in between would sit in the softmax at logit 0.  (The causal form masks every block as it is.)
+// Waves per SIMD the register budget is sized for: two workgroups per CU up to 9 key blocks; beyond that (tools build: the 19-block
+// yardstick) the LDS holds one.  The wide heads (88, 104) say what their LDS allows: at 9 key blocks their images take 113 and
+// 141 KiB, one workgroup per CU, and a budget for two would be a budget for an occupancy that cannot happen.
+template <int DH, int NKB, int NW>
+constexpr int attn_waves_per_simd() {
+  return (NKB > 9 || (attn_wide_head(DH) && 2 * attn_image_bytes(DH, NKB) > ATTN_LDS_LIMIT)) ? (NW + 3) / 4 : (2 * NW + 3) / 4;
+}
+// Head dimensions 88 and 104 (DH % 16 == 8; ViT-g/14, ViT-bigG/14): QK^T takes KS = ceil(DH / 16) k-steps and the last is a HALF
+// step -- lane half hb = 0 holds the real columns DH - 8 .. DH - 1, hb = 1 would hold columns DH .. DH + 7, which belong to the next
+// head (or lie past the row).  Both operands are exactly zero there: the Q fragment is replaced by zeros (and its load redirected
+// to the head's own column 0, so nothing outside the head is ever read), the K rows carry one more 16-B chunk that the staging
+// fills with zeros (an unwritten chunk could hold a NaN pattern, and 0 x NaN is NaN).  CH = DH / 8 is whole, so K / V staging
+// moves whole chunks; V^T has DV = 96 / 128 rows, rows DH .. DV - 1 zero, and the store is masked to d < DH.
 template <int DH, int NKB, int NW, int QPW, bool CAUSAL, bool RECOMP, bool TIMER = false, bool RAGGED = false>
-// two workgroups per CU up to 9 key blocks; beyond that (tools build: the 19-block yardstick) the LDS holds one
-__global__ __launch_bounds__(NW * 64, NKB > 9 ? (NW + 3) / 4 : (2 * NW + 3) / 4) void attention_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ out, int Tin,
+__global__ __launch_bounds__(NW * 64, (attn_waves_per_simd<DH, NKB, NW>())) void attention_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ out, int Tin,
                                                               int H, float scale_log2e, int dbg, int q_blocks,
                                                               const int* __restrict__ offs, const int* __restrict__ lens) {
   constexpr int TP = NKB * 32;
   constexpr int CH = DH / 8;                      // 16-B chunks per key row
-  constexpr int KS = DH / 16;                     // MFMA k-steps of the QK^T product
-  constexpr int KROW = DH == 64 ? 128 : 176;      // bytes per K row in LDS
-  constexpr int DV = (DH + 31) / 32 * 32, NB = DV / 32;
+  constexpr int KS = (DH + 15) / 16;              // MFMA k-steps of the QK^T product (DH 88 / 104: the last one is a half step)
+  constexpr bool HALF = DH % 16 != 0;             // the last k-step has real columns in lane half hb = 0 only
+  static_assert(DH % 8 == 0 && (!HALF || attn_wide_head(DH)), "head dimension");
+  static_assert(!HALF || (!CAUSAL && !RAGGED), "head dimensions 88 and 104: not causal, not ragged");
+  constexpr int KROW = (int)attn_krow_bytes(DH);  // bytes per K row in LDS (clipx_attn_plan.h)
+  static_assert(KROW >= 2 * KS * 16, "every chunk a k-step reads lies inside the row");
+  constexpr int DV = (int)attn_dv(DH), NB = DV / 32;
   constexpr int VT_STRIDE = TP * 2 + 8;  // bytes per V^T row: odd multiple of 8 -> conflict-free ds_read_b64
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* sK = smem;                 // [TP][KROW]
@@ -967,8 +997,16 @@ __global__ __launch_bounds__(NW * 64, NKB > 9 ? (NW + 3) / 4 : (2 * NW + 3) / 4)
     const int qrow = qpos < T ? qpos : T - 1;  // padded query rows compute on a valid row and are never stored
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
-      const uint4 v = *reinterpret_cast<const uint4*>(qbase + (size_t)qrow * ld + 16 * s + 8 * hb);
-      qf_all[qi][s] = *reinterpret_cast<const bf16x8*>(&v);
+      if constexpr (HALF) {
+        // the half step: columns 16 s + 8 hb .. + 8 exist for hb = 0 only -- hb = 1 reads the head's own column 0 and holds zeros
+        const bool real = s < KS - 1 || hb == 0;
+        uint4 v = *reinterpret_cast<const uint4*>(qbase + (size_t)qrow * ld + (real ? 16 * s + 8 * hb : 0));
+        if (!real) v = make_uint4(0u, 0u, 0u, 0u);
+        qf_all[qi][s] = *reinterpret_cast<const bf16x8*>(&v);
+      } else {
+        const uint4 v = *reinterpret_cast<const uint4*>(qbase + (size_t)qrow * ld + 16 * s + 8 * hb);
+        qf_all[qi][s] = *reinterpret_cast<const bf16x8*>(&v);
+      }
     }
   }
 
@@ -994,6 +1032,9 @@ __global__ __launch_bounds__(NW * 64, NKB > 9 ? (NW + 3) / 4 : (2 * NW + 3) / 4)
         const uint4 v = key < T ? kv[it] : make_uint4(0u, 0u, 0u, 0u);
         *reinterpret_cast<uint4*>(sK + key * KROW + (kchunk(key, c) << 4)) = v;
       }
+    }
+    if constexpr (HALF) {  // chunk CH of every row: the hb = 1 half of the last k-step
+      for (int key = tid; key < TP; key += NW * 64) *reinterpret_cast<uint4*>(sK + key * KROW + (CH << 4)) = make_uint4(0u, 0u, 0u, 0u);
     }
   }
   // ---- stage V transposed: a thread takes keys (2kp, 2kp+1) x 8 d and writes 8 packed key-pairs
@@ -2021,8 +2062,7 @@ template <int DH, int NKB, int NW, int QPW, bool RECOMP = false>
 static hipError_t launch_attention_cfg(const bf16* qkv, bf16* out, int B, int T, int H, int causal, hipStream_t st, int q_blocks,
                                        const int* offs = nullptr, const int* lens = nullptr, const clipx::AttnPlan* plan = nullptr) {
   q_blocks = q_blocks > 0 && q_blocks < NKB ? q_blocks : NKB;
-  constexpr int KROW = DH == 64 ? 128 : 176, DV = (DH + 31) / 32 * 32;
-  const size_t smem = (size_t)NKB * 32 * KROW + (size_t)DV * (NKB * 64 + 8);
+  const size_t smem = attn_image_bytes(DH, NKB);
   // the rows of the product's dispatch pass the plan (clipx_attn_plan.h): the instantiation launched must be the one it names, so
   // the table the CPU check walks cannot drift from this switch unnoticed (the A/B configurations of the tools build pass none)
   if (plan && (plan->kernel != clipx::ATTN_BLOCK || plan->nkb != NKB || plan->nw != NW || plan->qpw != QPW || plan->recomp != RECOMP ||
@@ -2036,10 +2076,14 @@ static hipError_t launch_attention_cfg(const bf16* qkv, bf16* out, int B, int T,
   constexpr int dbg = 0;
 #endif
   if (causal) {
-    auto kern = attention_kernel<DH, NKB, NW, QPW, true, RECOMP>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, grid, block, smem, st, qkv, out, T, H, scale_log2e, dbg, q_blocks, offs, lens);
+    if constexpr (!attn_wide_head(DH)) {
+      auto kern = attention_kernel<DH, NKB, NW, QPW, true, RECOMP>;
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL(kern, grid, block, smem, st, qkv, out, T, H, scale_log2e, dbg, q_blocks, offs, lens);
+    } else {
+      return hipErrorInvalidValue;  // head dimensions 88 and 104 have no causal form
+    }
   } else if (lens) {
     // a ragged batch that is not causal: the form that masks the padding keys of every block (the rows launch_attention gives
     // offs / lens to; the encoder's own ragged batches are the causal text tower's)
@@ -2058,6 +2102,20 @@ static hipError_t launch_attention_cfg(const bf16* qkv, bf16* out, int B, int T,
     hipLaunchKernelGGL(kern, grid, block, smem, st, qkv, out, T, H, scale_log2e, dbg, q_blocks, offs, lens);
   }
   return hipGetLastError();
+}
+
+// the rows of the head dimensions other than 64 (80, 88, 104): up to three key blocks one wave each, nine key blocks on nine waves
+// with S^T computed twice
+template <int DH>
+static hipError_t launch_attention_odd(const bf16* qkv, bf16* out, int B, int T, int H, int causal, hipStream_t st, int q_blocks,
+                                       const clipx::AttnPlan& plan) {
+  switch (plan.nkb) {
+    case 1: return launch_attention_cfg<DH, 1, 1, 1>(qkv, out, B, T, H, causal, st, q_blocks, nullptr, nullptr, &plan);
+    case 2: return launch_attention_cfg<DH, 2, 2, 1>(qkv, out, B, T, H, causal, st, q_blocks, nullptr, nullptr, &plan);
+    case 3: return launch_attention_cfg<DH, 3, 3, 1>(qkv, out, B, T, H, causal, st, q_blocks, nullptr, nullptr, &plan);
+    case 9: return launch_attention_cfg<DH, 9, 9, 1, true>(qkv, out, B, T, H, causal, st, q_blocks, nullptr, nullptr, &plan);
+    default: return hipErrorInvalidValue;
+  }
 }
 
 hipError_t launch_attention(const bf16* qkv, bf16* out, int B, int T, int H, int dh, int causal, hipStream_t st, int q_blocks,
@@ -2081,15 +2139,9 @@ hipError_t launch_attention(const bf16* qkv, bf16* out, int B, int T, int H, int
 #endif
     return launch_attention_long(qkv, out, B, T, H, st, q_blocks, plan);
   }
-  if (dh == 80) {  // ViT-H/14 image tower (T = 257), ViT-bigG is dh 104: not built
-    switch (nkb) {
-      case 1: return launch_attention_cfg<80, 1, 1, 1>(qkv, out, B, T, H, causal, st, q_blocks, nullptr, nullptr, &plan);
-      case 2: return launch_attention_cfg<80, 2, 2, 1>(qkv, out, B, T, H, causal, st, q_blocks, nullptr, nullptr, &plan);
-      case 3: return launch_attention_cfg<80, 3, 3, 1>(qkv, out, B, T, H, causal, st, q_blocks, nullptr, nullptr, &plan);
-      case 9: return launch_attention_cfg<80, 9, 9, 1, true>(qkv, out, B, T, H, causal, st, q_blocks, nullptr, nullptr, &plan);
-      default: return hipErrorInvalidValue;
-    }
-  }
+  if (dh == 80) return launch_attention_odd<80>(qkv, out, B, T, H, causal, st, q_blocks, plan);    // ViT-H/14 image tower (T = 257)
+  if (dh == 88) return launch_attention_odd<88>(qkv, out, B, T, H, causal, st, q_blocks, plan);    // ViT-g/14 image tower
+  if (dh == 104) return launch_attention_odd<104>(qkv, out, B, T, H, causal, st, q_blocks, plan);  // ViT-bigG/14 image tower
   if (dh != 64) return hipErrorInvalidValue;
   switch (nkb) {
     case 1: return launch_attention_cfg<64, 1, 1, 1>(qkv, out, B, T, H, causal, st, q_blocks, offs, lens, &plan);

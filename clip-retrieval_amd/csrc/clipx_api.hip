@@ -189,11 +189,13 @@ extern "C" size_t clipx_blob_floats(const clipx_model_desc* d) {
 
 static int check_desc(const clipx_model_desc* d) {
   if (d->image_size <= 0 || d->patch_size <= 0 || d->image_size % d->patch_size) return fail(CLIPX_E_ARG, "image_size must be a multiple of patch_size");
-  if (d->v_width % 256 || d->t_width % 256) return fail(CLIPX_E_UNSUPPORTED, "tower widths must be multiples of 256");
+  if (d->v_width % 128 || d->t_width % 128 || d->v_width > 2048 || d->t_width > 2048)
+    return fail(CLIPX_E_UNSUPPORTED, "tower widths must be multiples of 128, at most 2048");
   if (d->v_width % d->v_heads || d->t_width % d->t_heads) return fail(CLIPX_E_ARG, "width must be a multiple of heads");
   const int vdh = d->v_width / d->v_heads, tdh = d->t_width / d->t_heads;
-  if ((vdh != 64 && vdh != 80) || (tdh != 64 && tdh != 80))
-    return fail(CLIPX_E_UNSUPPORTED, "this build has attention kernels for head dimensions 64 and 80 only");
+  if (tdh != 64 && tdh != 80) return fail(CLIPX_E_UNSUPPORTED, "this build has text-tower attention kernels for head dimensions 64 and 80 only");
+  if (vdh != 64 && vdh != 80 && !clipx::attn_wide_head(vdh))
+    return fail(CLIPX_E_UNSUPPORTED, "this build has image-tower attention kernels for head dimensions 64, 80, 88 and 104 only");
   if (d->v_mlp % 128 || d->t_mlp % 128) return fail(CLIPX_E_UNSUPPORTED, "mlp widths must be multiples of 128");
   const int g = d->image_size / d->patch_size;
   // the image tower may be long where the long-sequence attention kernel exists (head dimension 64, not causal: clipx_attn_plan.h)
@@ -202,6 +204,9 @@ static int check_desc(const clipx_model_desc* d) {
   if (g * g + 1 > clipx::ATTN_LONG_MAX_T) return fail(CLIPX_E_UNSUPPORTED, "image sequence longer than 608 tokens");
   if (g * g + 1 > clipx::ATTN_SHORT_MAX_T && vdh != 64)
     return fail(CLIPX_E_UNSUPPORTED, "image sequence longer than 288 tokens at a head dimension other than 64");
+  // head dimensions 88 and 104 (ViT-g/14, ViT-bigG/14) have the key-block counts 1 .. 3 and 9 only: refused here, not at the first launch
+  if (clipx::attn_wide_head(vdh) && clipx::attn_plan(g * g + 1, vdh, 0).kernel == clipx::ATTN_NONE)
+    return fail(CLIPX_E_UNSUPPORTED, "image-tower head dimensions 88 and 104 need at most 96 image tokens, or 257 .. 288");
   if (d->embed_dim <= 0 || d->embed_dim % 8) return fail(CLIPX_E_ARG, "embed_dim must be a multiple of 8");
   if (d->act != CLIPX_ACT_QUICK_GELU && d->act != CLIPX_ACT_GELU) return fail(CLIPX_E_ARG, "unknown activation");
   if (d->v_layers <= 0 || d->t_layers <= 0 || d->vocab <= 0 || d->ctx_len <= 0) return fail(CLIPX_E_ARG, "bad layer/vocab/context size");
@@ -1081,8 +1086,12 @@ static const char* attention_limit(int T, int dh, int causal) {
   if (T > clipx::ATTN_LONG_MAX_T) return "sequence longer than 608 tokens";
   if (T > clipx::ATTN_SHORT_MAX_T && causal) return "causal sequence longer than 288 tokens";
   if (T > clipx::ATTN_SHORT_MAX_T && dh != 64) return "sequence longer than 288 tokens at a head dimension other than 64";
+  if (clipx::attn_wide_head(dh) && causal) return "head dimensions 88 and 104 have no causal attention kernel";
+  if (dh != 64 && clipx::attn_plan(T, dh, causal).kernel == clipx::ATTN_NONE)
+    return "no attention kernel for head dimensions 80, 88 and 104 at 97 .. 256 tokens";
   return nullptr;
 }
+static bool attention_dh_known(int dh) { return dh == 64 || dh == 80 || clipx::attn_wide_head(dh); }
 
 extern "C" int clipx_attention_device(int device, const void* qkv_bf16, void* out_bf16, int B, int T, int H, int causal,
                                       void* stream) {
@@ -1096,7 +1105,7 @@ extern "C" int clipx_attention_device(int device, const void* qkv_bf16, void* ou
 extern "C" int clipx_attention_dh_device(int device, const void* qkv_bf16, void* out_bf16, int B, int T, int H, int dh,
                                          int causal, void* stream) {
   if (!qkv_bf16 || !out_bf16 || B <= 0 || T <= 0 || H <= 0) return fail(CLIPX_E_ARG, "bad attention arguments");
-  if (dh != 64 && dh != 80) return fail(CLIPX_E_UNSUPPORTED, "head dimension must be 64 or 80");
+  if (!attention_dh_known(dh)) return fail(CLIPX_E_UNSUPPORTED, "head dimension must be 64, 80, 88 or 104");
   if (const char* why = attention_limit(T, dh, causal)) return fail(CLIPX_E_UNSUPPORTED, why);
   HIPCHK(hipSetDevice(device));
   hipError_t e = launch_attention((const bf16*)qkv_bf16, (bf16*)out_bf16, B, T, H, dh, causal, (hipStream_t)stream);
@@ -1110,13 +1119,11 @@ extern "C" int clipx_attention_dh_device(int device, const void* qkv_bf16, void*
 extern "C" int clipx_attention_ex_device(int device, const void* qkv_f16, void* out_bf16, int B, int T, int H, int dh, int causal,
                                          int q_blocks, const int32_t* offs, const int32_t* lens, void* stream) {
   if (!qkv_f16 || !out_bf16 || B <= 0 || T <= 0 || H <= 0 || q_blocks < 0) return fail(CLIPX_E_ARG, "bad attention arguments");
-  if (dh != 64 && dh != 80) return fail(CLIPX_E_UNSUPPORTED, "head dimension must be 64 or 80");
+  if (!attention_dh_known(dh)) return fail(CLIPX_E_UNSUPPORTED, "head dimension must be 64, 80, 88 or 104");
   if (const char* why = attention_limit(T, dh, causal)) return fail(CLIPX_E_UNSUPPORTED, why);
   if ((offs != nullptr) != (lens != nullptr)) return fail(CLIPX_E_ARG, "offs and lens go together: both or neither");
   if (offs && (dh != 64 || T > 128))
     return fail(CLIPX_E_UNSUPPORTED, "ragged batches (offs / lens) need head dimension 64 and at most 128 tokens");
-  if (clipx::attn_plan(T, dh, causal).kernel == clipx::ATTN_NONE)
-    return fail(CLIPX_E_UNSUPPORTED, "no attention kernel for head dimension 80 at 97 .. 256 tokens");
   HIPCHK(hipSetDevice(device));
   hipError_t e = launch_attention((const bf16*)qkv_f16, (bf16*)out_bf16, B, T, H, dh, causal, (hipStream_t)stream, q_blocks, offs, lens);
   if (e == hipErrorInvalidValue) return fail(CLIPX_E_UNSUPPORTED, "no attention kernel for this (T, head dimension)");
@@ -1127,7 +1134,7 @@ extern "C" int clipx_attention_ex_device(int device, const void* qkv_f16, void* 
 extern "C" int clipx_layernorm_device(int device, const float* x, const float* gamma, const float* beta, void* y,
                                       int out_bf16, int M, int d, float eps, void* stream) {
   if (!x || !gamma || !beta || !y || M <= 0) return fail(CLIPX_E_ARG, "bad layernorm arguments");
-  if (d % 256 || d > 2048) return fail(CLIPX_E_UNSUPPORTED, "d must be a multiple of 256, <= 2048");
+  if (d <= 0 || d % 128 || d > 2048) return fail(CLIPX_E_UNSUPPORTED, "d must be a multiple of 128, <= 2048");
   HIPCHK(hipSetDevice(device));
   HIPCHK(launch_layernorm(x, gamma, beta, y, out_bf16, M, d, eps, (hipStream_t)stream));
   return CLIPX_OK;
@@ -1135,7 +1142,7 @@ extern "C" int clipx_layernorm_device(int device, const float* x, const float* g
 
 extern "C" int clipx_rowstats_device(int device, const void* x16, int is_f16, float* rstd, int M, int d, float eps, void* stream) {
   if (!x16 || !rstd || M <= 0) return fail(CLIPX_E_ARG, "bad rowstats arguments");
-  if (d % 256 || d > 2048) return fail(CLIPX_E_UNSUPPORTED, "d must be a multiple of 256, <= 2048");
+  if (d <= 0 || d % 128 || d > 2048) return fail(CLIPX_E_UNSUPPORTED, "d must be a multiple of 128, <= 2048");
   HIPCHK(hipSetDevice(device));
   HIPCHK(launch_rowstats(x16, rstd, M, d, eps, (hipStream_t)stream, is_f16 ? 1 : 0, nullptr, is_f16 == 2 ? 1 : 0));
   return CLIPX_OK;

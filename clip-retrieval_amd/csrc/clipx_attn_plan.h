@@ -9,6 +9,9 @@
 //   NKB 10 .. 19 (T 289 .. 608), dh 64, not causal: attention_long_kernel, K and V^T whole in the LDS, a run-time loop over the
 //                         key blocks with a running softmax, ATTN_LONG_NW waves that own at most ATTN_LONG_QPW query blocks each.
 //   everything else       no kernel: the launch is refused (causal or dh 80 above 288 tokens, anything above 608, dh 80 at NKB 4 .. 8).
+// Head dimensions 88 and 104 (ViT-g/14, ViT-bigG/14 image towers) have the rows of dh 80 -- NKB 1 .. 3 and NKB 9 (nine waves, RECOMP) --
+// and only not causal: 88 and 104 are not multiples of the 16-wide MFMA k-step, so the QK^T product ends in a half step whose upper
+// half is zero in both operands (attn_krow_bytes: the K rows carry a zeroed pad chunk for it).
 // Ragged batches (offs / lens) ride on the dh 64, NKB <= 4 rows only; that restriction stays in launch_attention.
 #pragma once
 
@@ -38,15 +41,23 @@ struct AttnPlan {
   size_t lds_bytes = 0;  // dynamic LDS of the launch
 };
 
-// LDS of the one-head images: K rows of 128 B (dh 64) or 176 B (dh 80), V^T rows of nkb * 64 + 8 bytes, DV = dh rounded up to 32
-inline size_t attn_image_bytes(int dh, int nkb) {
-  const size_t krow = dh == 64 ? 128 : 176, dv = (size_t)(dh + 31) / 32 * 32;
-  return (size_t)nkb * 32 * krow + dv * ((size_t)nkb * 64 + 8);
+constexpr bool attn_wide_head(int dh) { return dh == 88 || dh == 104; }  // the head dimensions that end QK^T in a half k-step
+
+// Bytes of one K row in the LDS -- the ONE expression the kernels, their launchers and tools/attn_plan_check.cpp take it from.
+// dh 64: 128 B, the 16-B chunk position swizzled (XOR).  Every other dh: the 2 ceil(dh / 16) chunks the k-steps read (the last one
+// a zeroed pad chunk when dh is not a multiple of 16), made an ODD number of chunks so that the ds_read_b128 of 32 consecutive keys
+// spreads over the banks without a swizzle: 11 chunks = 176 B (dh 80), 13 = 208 B (dh 88), 15 = 240 B (dh 104).
+constexpr size_t attn_krow_bytes(int dh) { return dh == 64 ? 128 : (size_t)((2 * ((dh + 15) / 16)) | 1) * 16; }
+constexpr size_t attn_dv(int dh) { return (size_t)(dh + 31) / 32 * 32; }  // rows of V^T: dh rounded up to the 32-row output block
+
+// LDS of the one-head images: K rows of attn_krow_bytes, V^T rows of nkb * 64 + 8 bytes, DV = dh rounded up to 32
+constexpr size_t attn_image_bytes(int dh, int nkb) {
+  return (size_t)nkb * 32 * attn_krow_bytes(dh) + attn_dv(dh) * ((size_t)nkb * 64 + 8);
 }
 
 inline AttnPlan attn_plan(int T, int dh, int causal) {
   AttnPlan p;
-  if (T <= 0 || T > ATTN_LONG_MAX_T || (dh != 64 && dh != 80)) return p;
+  if (T <= 0 || T > ATTN_LONG_MAX_T || (dh != 64 && dh != 80 && !attn_wide_head(dh))) return p;
   const int nkb = (T + 31) / 32;
   auto block = [&](int nw, int qpw, bool recomp) {
     p.kernel = ATTN_BLOCK;
@@ -60,7 +71,8 @@ inline AttnPlan attn_plan(int T, int dh, int causal) {
     p.lds_bytes = attn_image_bytes(64, nkb);
     return p;
   }
-  if (dh == 80) {
+  if (attn_wide_head(dh) && causal) return p;
+  if (dh != 64) {  // 80, 88, 104
     if (nkb <= 3) block(nkb, 1, false);
     else if (nkb == 9) block(9, 1, true);
     return p;

@@ -72,6 +72,12 @@ ARCHS = {
     # LAION ViT-H/14 (the 1024-d model of docs/laion5B_h14_back.md; BASELINE config 5): image heads are 80 wide
     "open_clip:ViT-H-14": ClipArch(v_width=1280, v_layers=32, v_heads=16, v_mlp=5120, t_width=1024, t_layers=24,
                                    t_heads=16, t_mlp=4096, embed_dim=1024, act="gelu"),
+    # LAION ViT-g/14 and ViT-bigG/14: image heads are 88 and 104 wide (attention_kernel's half k-step), widths 1408 and 1664 are odd
+    # multiples of 128.  Shapes recalled from memory of open_clip's model configs, not read from the package (as _OPEN_CLIP_NAMES).
+    "open_clip:ViT-g-14": ClipArch(v_width=1408, v_layers=40, v_heads=16, v_mlp=6144, t_width=1024, t_layers=24,
+                                   t_heads=16, t_mlp=4096, embed_dim=1024, act="gelu"),
+    "open_clip:ViT-bigG-14": ClipArch(v_width=1664, v_layers=48, v_heads=16, v_mlp=8192, t_width=1280, t_layers=32,
+                                      t_heads=20, t_mlp=5120, embed_dim=1280, act="gelu"),
 }
 
 
@@ -433,7 +439,10 @@ def register_encoder(name: str, encoder: ClipEncoder):
 
 # `clip_model` strings of the reference (all_clip: "ViT-L/14", "open_clip:ViT-H-14/laion2b_s32b_b79k", "hf_clip:openai/clip-vit-large-patch14", ...)
 _HF_NAMES = {"openai/clip-vit-base-patch32": "ViT-B/32", "openai/clip-vit-base-patch16": "ViT-B/16",
-             "openai/clip-vit-large-patch14": "ViT-L/14", "openai/clip-vit-large-patch14-336": "ViT-L/14@336px"}
+             "openai/clip-vit-large-patch14": "ViT-L/14", "openai/clip-vit-large-patch14-336": "ViT-L/14@336px",
+             # LAION's HF exports of the two largest open_clip towers (ids recalled from memory, like the names below)
+             "laion/CLIP-ViT-g-14-laion2B-s12B-b42K": "open_clip:ViT-g-14",
+             "laion/CLIP-ViT-bigG-14-laion2B-39B-b160k": "open_clip:ViT-bigG-14"}
 # open_clip spells the 336-pixel model "ViT-L-14-336" and has OpenAI's weights only for it.  These three names (and the HF one above)
 # are recalled from memory of the third-party packages, not read from them: SURVEY marks such things.
 _OPEN_CLIP_NAMES = {"ViT-L-14-336": "ViT-L/14@336px"}
@@ -457,7 +466,7 @@ def resolve_arch_name(clip_model: str) -> str:
         if "open_clip:" + arch in ARCHS:
             return "open_clip:" + arch
     raise ValueError(f"unknown clip_model {clip_model!r}; known architectures: {sorted(ARCHS)} "
-                     "(also hf_clip:openai/clip-vit-*, open_clip:<arch>/<pretrained>)")
+                     "(also hf_clip:openai/clip-vit-*, hf_clip:laion/CLIP-ViT-{g,bigG}-14-*, open_clip:<arch>/<pretrained>)")
 
 
 def _strip_prefixes(sd):

@@ -43,7 +43,9 @@ enum {
 #define CLIPX_PIX_U8_NHWC 1  /* u8  [B,S,S,3] raw RGB; /255, mean/std normalised on the device               */
 
 /* Architecture of one CLIP model = what `all_clip.load_clip(clip_model)` resolves a name to
- * (mapper.py:36-41).  Head dimension (width / heads) must be 64 or 80 (ViT-H/14) in this build. */
+ * (mapper.py:36-41).  Tower widths are multiples of 128, at most 2048.  Head dimension (width / heads): 64 or 80 (ViT-H/14) for
+ * either tower; the image tower also 88 (ViT-g/14: 1408 / 16) and 104 (ViT-bigG/14: 1664 / 16), there with at most 96 image tokens
+ * or 257 .. 288 (224 pixels at patch 14 is 257).  CLIPX_E_UNSUPPORTED otherwise. */
 typedef struct clipx_model_desc {
   int image_size;   /* 224 */
   int patch_size;   /* 14 (L/14), 32 (B/32), 16 (B/16) */
@@ -203,7 +205,8 @@ int clipx_gemm_f16_ln_device(int device, const void* A_f16, const void* W_f16, c
  * rounded to fp16) -> out bf16 [B*T, H*64];  x f32 [M, d] -> y (bf16 if out_bf16 else f32). */
 int clipx_attention_device(int device, const void* qkv_f16, void* out_bf16, int B, int T, int H, int causal,
                            void* stream);
-/* Same for head dimension dh = 64 or 80 (ViT-H/14 image tower: 1280 / 16): qkv [B*T, 3*H*dh] -> out [B*T, H*dh]. */
+/* Same for head dimension dh = 64, 80 (ViT-H/14 image tower: 1280 / 16), 88 (ViT-g/14: 1408 / 16) or 104 (ViT-bigG/14: 1664 / 16):
+ * qkv [B*T, 3*H*dh] -> out [B*T, H*dh].  dh = 88 and 104: not causal, T <= 96 or 257 .. 288 (CLIPX_E_UNSUPPORTED otherwise). */
 int clipx_attention_dh_device(int device, const void* qkv_f16, void* out_bf16, int B, int T, int H, int dh,
                               int causal, void* stream);
 /* The same kernels with the two arguments the encoder itself passes them, for per-kernel tests of those forms.
@@ -212,10 +215,12 @@ int clipx_attention_dh_device(int device, const void* qkv_f16, void* out_bf16, i
  *   offs_dev_or_null, lens_dev_or_null  device int32 [B], both or neither (CLIPX_E_ARG otherwise): a ragged batch, sample b owns
  *             the lens[b] >= 1 packed rows from row offs[b] on, so qkv and out hold sum(lens) rows and T is the longest length.
  *             Head dimension 64 and T <= 128 only (CLIPX_E_UNSUPPORTED otherwise).
- * The limits of T are those of the two entry points above, and dh = 80 has no kernel at T = 97 .. 256 (CLIPX_E_UNSUPPORTED);
+ * The limits of T are those of the two entry points above; dh = 80, 88 and 104 have no kernel at T = 97 .. 256, dh = 88 and 104 none
+ * that is causal or ragged (CLIPX_E_UNSUPPORTED);
  * a refused call launches nothing. */
 int clipx_attention_ex_device(int device, const void* qkv_f16, void* out_bf16, int B, int T, int H, int dh, int causal,
                               int q_blocks, const int32_t* offs_dev_or_null, const int32_t* lens_dev_or_null, void* stream);
+/* d: a multiple of 128, at most 2048 (here and in clipx_rowstats_device); out_bf16 = 2: IEEE fp16 rows */
 int clipx_layernorm_device(int device, const float* x, const float* gamma, const float* beta, void* y, int out_bf16,
                            int M, int d, float eps, void* stream);
 /* LayerNorm statistics of the residual stream as the LayerNorm-folded GEMMs consume them (per-kernel parity test):

@@ -4,6 +4,11 @@
 // ab_cfg (tools library, CLIPX_LIB=libclipx_ablate.so): alternates the default dispatch and CLIPX_ATTN_CFG=ab_cfg in one process on the
 // same buffers -- rounds of 20 timed launches each, A B A B ... -- and prints the median and the spread of the round medians of both,
 // and the largest difference of their outputs.  ab_cfg = 19 at T = 577 .. 608: the long-sequence kernel against the RECOMP yardstick.
+//   tools/attn_bench B T H 80,88,104   -- a comma list of head dimensions (not causal): the kernels of the list alternate in one
+// process, rounds of 20 timed launches each (80 88 104 80 88 104 ...), buffers of their own; per head dimension the median of the
+// round medians, the spread, TFLOP/s counted on the real dh, the k-steps + PV steps the kernel issues per key block
+// (ceil(dh / 16) + 2 DV / 32) and the time relative to the first of the list per such step.  One (batch, head) pair of each is
+// checked against the fp32 CPU softmax first.
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -19,6 +24,91 @@ typedef int (*attn_fn)(int, const void*, void*, int, int, int, int, int, void*);
 static float bf2f(uint16_t b) { uint32_t u = (uint32_t)b << 16; float f; memcpy(&f, &u, 4); return f; }
 static float h2f(uint16_t b) { _Float16 h; memcpy(&h, &b, 2); return (float)h; }
 static uint16_t f2h(float f) { _Float16 h = (_Float16)f; uint16_t b; memcpy(&b, &h, 2); return b; }
+// max |out - fp32 CPU| over the (batch, head) pairs given
+static double cpu_check(const std::vector<uint16_t>& hq, const std::vector<uint16_t>& ho, int T, int H, int dh, int causal, const int (*pairs)[2], int npairs) {
+  const size_t ld = (size_t)3 * H * dh;
+  double maxerr = 0;
+  std::vector<float> s(T);
+  for (int p = 0; p < npairs; ++p) {
+    const int b = pairs[p][0], hh = pairs[p][1];
+    for (int q = 0; q < T; ++q) {
+      const uint16_t* qp = &hq[((size_t)b * T + q) * ld + hh * dh];
+      float mx = -1e30f;
+      const int kend = causal ? q + 1 : T;
+      for (int k = 0; k < kend; ++k) {
+        const uint16_t* kp = &hq[((size_t)b * T + k) * ld + H * dh + hh * dh];
+        float a = 0;
+        for (int d = 0; d < dh; ++d) a += h2f(qp[d]) * h2f(kp[d]);
+        s[k] = a / sqrtf((float)dh);
+        mx = std::max(mx, s[k]);
+      }
+      double sum = 0;
+      for (int k = 0; k < kend; ++k) { s[k] = expf(s[k] - mx); sum += s[k]; }
+      for (int d = 0; d < dh; ++d) {
+        double o = 0;
+        for (int k = 0; k < kend; ++k) o += s[k] * h2f(hq[((size_t)b * T + k) * ld + 2 * H * dh + hh * dh + d]);
+        o /= sum;
+        maxerr = std::max(maxerr, fabs(o - bf2f(ho[((size_t)b * T + q) * (H * dh) + hh * dh + d])));
+      }
+    }
+  }
+  return maxerr;
+}
+
+// the comma-list mode: several head dimensions alternating in one process
+static int compare_dhs(attn_fn attn, int B, int T, int H, const std::vector<int>& dhs) {
+  const int n = (int)dhs.size(), rounds = 9, per = 20;
+  std::vector<void*> dq(n), dout(n);
+  hipStream_t st; CK(hipStreamCreate(&st));
+  hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+  int bad = 0;
+  for (int i = 0; i < n; ++i) {
+    const int dh = dhs[i];
+    const size_t nq = (size_t)B * T * 3 * H * dh, no = (size_t)B * T * H * dh;
+    std::vector<uint16_t> hq(nq), ho(no);
+    unsigned r = 777u + (unsigned)dh;
+    for (auto& v : hq) { r = r * 1664525u + 1013904223u; v = f2h((((int)(r >> 9) & 0xffff) / 32768.f - 1.f) * 1.5f); }
+    CK(hipMalloc(&dq[i], nq * 2)); CK(hipMalloc(&dout[i], no * 2));
+    CK(hipMemcpy(dq[i], hq.data(), nq * 2, hipMemcpyHostToDevice));
+    if (attn(0, dq[i], dout[i], B, T, H, dh, 0, st)) { fprintf(stderr, "attention call failed at dh %d\n", dh); return 2; }
+    CK(hipStreamSynchronize(st));
+    CK(hipMemcpy(ho.data(), dout[i], no * 2, hipMemcpyDeviceToHost));
+    const int pairs[1][2] = {{B - 1, H - 1}};  // the last head of the last sample: its fragments end where the buffer ends
+    const double err = cpu_check(hq, ho, T, H, dh, 0, pairs, 1);
+    printf("dh %d: max |err| vs fp32 CPU on the last (batch, head) pair %.4g\n", dh, err);
+    bad |= !(err < 0.02);
+  }
+  if (bad) return 1;
+  std::vector<std::vector<float>> med(n);
+  for (int r = 0; r < rounds; ++r)
+    for (int i = 0; i < n; ++i) {
+      int rc = 0;  // a refused launch would be timed as a very fast kernel: every return code of the round counts
+      for (int k = 0; k < 3; ++k) rc |= attn(0, dq[i], dout[i], B, T, H, dhs[i], 0, st);
+      std::vector<float> t;
+      for (int k = 0; k < per; ++k) {
+        CK(hipEventRecord(e0, st)); rc |= attn(0, dq[i], dout[i], B, T, H, dhs[i], 0, st); CK(hipEventRecord(e1, st)); CK(hipEventSynchronize(e1));
+        float ms; CK(hipEventElapsedTime(&ms, e0, e1)); t.push_back(ms);
+      }
+      if (rc) { fprintf(stderr, "attention call failed at dh %d in round %d\n", dhs[i], r); return 2; }
+      std::sort(t.begin(), t.end());
+      med[i].push_back(t[t.size() / 2]);
+    }
+  double base = 0;
+  for (int i = 0; i < n; ++i) {
+    std::sort(med[i].begin(), med[i].end());
+    const double m = med[i][med[i].size() / 2];
+    const int dh = dhs[i], steps = (dh + 15) / 16 + 2 * ((dh + 31) / 32);
+    const double fl = 4.0 * B * H * (double)T * T * dh;
+    if (i == 0) base = m / steps;
+    printf("attention B=%d T=%d H=%d dh=%d: median of %d round medians %.1f us (%.1f TFLOP/s on dh %d), spread %.1f .. %.1f us; %d MFMA steps per key block, "
+           "time per step %.2f x dh %d's\n", B, T, H, dh, rounds, m * 1e3, fl / (m * 1e-3) / 1e12, dh, med[i].front() * 1e3, med[i].back() * 1e3, steps,
+           m / steps / base, dhs[0]);
+  }
+  for (int i = 0; i < n; ++i) { CK(hipFree(dq[i])); CK(hipFree(dout[i])); }
+  CK(hipEventDestroy(e0)); CK(hipEventDestroy(e1)); CK(hipStreamDestroy(st));
+  return 0;
+}
+
 int main(int argc, char** argv) {
   std::string self = argv[0];
   std::string dir = self.substr(0, self.find_last_of('/') == std::string::npos ? 0 : self.find_last_of('/'));
@@ -26,6 +116,17 @@ int main(int argc, char** argv) {
   if (!h) { fprintf(stderr, "dlopen: %s\n", dlerror()); return 2; }
   attn_fn attn = (attn_fn)dlsym(h, "clipx_attention_dh_device");
   const int B = argc > 1 ? atoi(argv[1]) : 256, T = argc > 2 ? atoi(argv[2]) : 257, H = argc > 3 ? atoi(argv[3]) : 16;
+  if (argc > 4 && strchr(argv[4], ',')) {
+    std::vector<int> dhs;
+    for (const char* p = argv[4]; p && *p;) {
+      char* end;
+      const long dh = strtol(p, &end, 10);
+      if (end == p || (*end != ',' && *end != 0) || dh <= 0 || dh > 256) { fprintf(stderr, "bad head dimension list '%s'\n", argv[4]); return 2; }
+      dhs.push_back((int)dh);
+      p = *end ? end + 1 : nullptr;
+    }
+    return compare_dhs(attn, B, T, H, dhs);
+  }
   const int dh = argc > 4 ? atoi(argv[4]) : 64, causal = argc > 5 ? atoi(argv[5]) : 0;
   const size_t ld = (size_t)3 * H * dh, nq = (size_t)B * T * ld, no = (size_t)B * T * H * dh;
   std::vector<uint16_t> hq(nq), ho(no);

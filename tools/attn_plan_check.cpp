@@ -66,6 +66,7 @@ int main() {
             CHECK(p.nkb == nkb && p.nw == o.nw && p.qpw == o.qpw && p.recomp == o.recomp);
             // the bytes launch_attention_cfg / launch_attention_pk9 have always asked for
             const size_t krow = dh == 64 ? 128 : 176, dv = dh == 64 ? 64 : 96;
+            CHECK(krow == attn_krow_bytes(dh) && dv == attn_dv(dh));  // the one expression every launcher takes them from
             const size_t want = o.kernel == ATTN_PK9 ? (size_t)2 * (288 * 128 + 2 * 288 * 64) : (size_t)nkb * 32 * krow + dv * ((size_t)nkb * 64 + 8);
             CHECK(p.lds_bytes == want);
             ++n_old;
@@ -110,7 +111,7 @@ int main() {
   {
     const int T = 0, dh = 64, causal = 0;
     CHECK(attn_plan(0, 64, 0).kernel == ATTN_NONE && attn_plan(-5, 64, 0).kernel == ATTN_NONE);
-    CHECK(attn_plan(257, 88, 0).kernel == ATTN_NONE && attn_plan(257, 104, 0).kernel == ATTN_NONE);
+    CHECK(attn_plan(257, 72, 0).kernel == ATTN_NONE && attn_plan(257, 96, 0).kernel == ATTN_NONE);  // (88 and 104: tools/attn_wide_plan_check.cpp)
     CHECK(attn_plan(577, 64, 0).nkb == 19 && attn_plan(577, 64, 0).lds_bytes == 156160);
   }
   if (failures) {

@@ -1005,11 +1005,11 @@ extern "C" int knnx_search(knnx_index* ix, const float* q, int n, int k, float* 
   if (k > KNNX_MAX_K) return fail(KNNX_E_UNSUPPORTED, "k > 131072 is not implemented");
   if (ix->pq.m && k > KNNX_MAX_K_FAST) {  // served through the threshold mode of the ADC scan where the index has it switched on
     std::lock_guard<std::mutex> lk(ix->mu);
-    if (!ix->pq.threshold_scan) return fail(KNNX_E_UNSUPPORTED, "k > 64 is not supported on an IVF-PQ index");
+    if (!ix->pq.thr.on) return fail(KNNX_E_UNSUPPORTED, "k > 64 is not supported on an IVF-PQ index");
   }
   if (ix->sq.on && k > KNNX_MAX_K_FAST) {  // likewise, through the threshold mode of the code scan
     std::lock_guard<std::mutex> lk(ix->mu);
-    if (!ix->sq.threshold_scan) return fail(KNNX_E_UNSUPPORTED, "k > 64 is not supported on an IVF-SQ8 index");
+    if (!ix->sq.thr.on) return fail(KNNX_E_UNSUPPORTED, "k > 64 is not supported on an IVF-SQ8 index");
   }
   if (n == 0) return KNNX_OK;
   if (n == 1 && k <= KNNX_MAX_K_FAST && ix->co.on) {  // concurrent single-query callers share one scan
@@ -1020,9 +1020,9 @@ extern "C" int knnx_search(knnx_index* ix, const float* q, int n, int k, float* 
     std::lock_guard<std::mutex> lk(ix->mu);
     if (set_dev(ix)) return KNNX_E_HIP;
     int r = (k <= KNNX_MAX_K_FAST) ? search_fast_locked(ix, q, n, k, D, I)
-            : ix->pq.m               ? (ix->pq.threshold_scan ? search_large_k_pq_locked(ix, q, n, k, D, I)
+            : ix->pq.m               ? (ix->pq.thr.on ? search_large_k_thr_locked(ix, pq_thr_pass(), q, n, k, D, I)
                                                               : fail(KNNX_E_UNSUPPORTED, "k > 64 is not supported on an IVF-PQ index"))
-            : ix->sq.on              ? (ix->sq.threshold_scan ? search_large_k_sq_locked(ix, q, n, k, D, I)
+            : ix->sq.on              ? (ix->sq.thr.on ? search_large_k_thr_locked(ix, sq_thr_pass(), q, n, k, D, I)
                                                               : fail(KNNX_E_UNSUPPORTED, "k > 64 is not supported on an IVF-SQ8 index"))
                                      : search_large_k_locked(ix, q, n, k, D, I);
     if (r) return r;

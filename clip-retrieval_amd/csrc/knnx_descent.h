@@ -1,5 +1,6 @@
-// knnx_descent.h -- the per-query threshold descent of a large-k search on an IVF-PQ index (knnx_ivfpq.hip).  No HIP in here: a
-// struct and next(count) -> {threshold | fetch}, so that a host-only program can drive it (tools/descent_check.cpp).
+// knnx_descent.h -- the per-query threshold descent of a large-k search on an IVF-PQ or IVF-SQ8 index (knnx_thr_group.h runs one per
+// query of a group).  No HIP in here: a struct and next(count) -> {threshold | fetch}, so that a host-only program can drive it
+// (tools/descent_check.cpp).
 //
 // A threshold scan returns every row of the probed lists whose score is > thr (strict) and counts them exactly.  The descent looks
 // for a threshold that lets at least `want` rows through and not absurdly many more, with the rule search_large_k_locked uses for

@@ -357,6 +357,27 @@ struct IvfBuild {
   std::vector<uint64_t> taken;  // one bit per padded arena row
 };
 
+// threshold mode of a compressed index's list scan (IVF-PQ: the ADC scan, IVF-SQ8: the code scan): the switch, the counters of
+// knnx_ivf{pq,sq}_threshold_stats, and the device scratch of one threshold pass (allocated by the first one).  One per family.
+struct ThrState {
+  bool on = false;  // knnx_ivf{pq,sq}_set_threshold_scan: k > 64 and range_search are served; off: they are refused
+  // since the index was created: queries served with k > 64, threshold scans launched (one launch serves a whole group), scans summed
+  // over the queries that took part in them, hits fetched to the host
+  int64_t queries = 0, scans = 0, query_scans = 0, hits = 0;
+  DevBuf<float> tthr;       // [256] the per-query thresholds of one scan
+  DevBuf<unsigned> tcnt;    // [256] its hit counters
+  DevBuf<unsigned> tfetch;  // [256] tcnt with the queries that are not fetched set to 0 (range_fetch reads its counts on the device)
+  hipError_t alloc() {
+    if (tthr) return hipSuccess;
+    hipError_t e = hipSuccess;
+    dev_alloc(e, tthr, PQ_PASS);
+    dev_alloc(e, tcnt, PQ_PASS);
+    dev_alloc(e, tfetch, PQ_PASS);
+    if (e != hipSuccess) tthr.reset(), tcnt.reset(), tfetch.reset();
+    return e;
+  }
+};
+
 // IVF-PQ (knnx_ivfpq_set_quantizer before knnx_ivf_begin; knn_pq_kernels.hip): the arena holds M code bytes per row, list-sorted
 // and tile-padded like the IVF-Flat rows (`rows` stays null); the coarse quantiser is the IVF one
 struct PqData {
@@ -377,9 +398,7 @@ struct PqData {
   // They live in knnx_index::rows ([capacity][d], allocated by knnx_ivf_begin); ivf.idmap / ivf.inv serve codes and rows alike.
   bool refine = false;
   int k_factor = 1;                      // candidates per result of a refine search (knnx_ivfpq_set_k_factor)
-  // threshold mode of the ADC scan (knnx_ivfpq_set_threshold_scan): k > 64 and range_search are served; off: they are refused
-  bool threshold_scan = false;
-  int64_t thr_queries = 0, thr_scans = 0, thr_query_scans = 0, thr_hits = 0;  // knnx_ivfpq_threshold_stats
+  ThrState thr;                          // threshold mode of the ADC scan
   // M = 256 (the two-half ADC scan, knnx_pq_plan.h): the budget of the partial-sum buffer (KNNX_PQ_PARTIAL_MAX_BYTES, read by
   // knnx_ivfpq_set_quantizer) and the slab width S of slab_np probed lists (host arithmetic on size_h, no device round trip: by the
   // first pass after the index is finished, and again by the first pass after nprobe changed; slab_np = 0: not computed)
@@ -396,6 +415,7 @@ struct PqScratch {
   DevBuf<int> probe;        // [256][np_cap] probed lists
   DevBuf<float> pscore;     // [256][np_cap] their coarse scores
   int np_cap = 0;
+  int np = 0;               // lists probed per query by the pass whose front half is in here (pq_front)
   DevBuf<float> lut;        // [256][M][256]
   DevBuf<float> part_s;     // [PQ_SLOTS][64] per-workgroup top-k of the ADC scan
   DevBuf<uint32_t> part_i;
@@ -408,10 +428,6 @@ struct PqScratch {
   DevBuf<float> rpart_s;    // [PQ_SLOTS][PQ_REFINE_MAX]
   DevBuf<uint32_t> rpart_r;
   DevBuf<float> rdc;        // [256][64]
-  // threshold passes (allocated by the first one): the per-query thresholds and hit counters of one scan, the counters of a fetch
-  DevBuf<float> tthr;       // [256]
-  DevBuf<unsigned> tcnt;    // [256]
-  DevBuf<unsigned> tfetch;  // [256] tcnt with the queries that are not fetched set to 0 (range_fetch reads its counts on the device)
   // M = 256 only (the two-half ADC scan): the row offset of every probe in its query's slab, written by pq_front; the partial sums
   // of the sub-group being scored, allocated on first use (knnx_ivfpq.hip: pq_half_buffer).  half_nq = n > 0: the buffer holds the
   // sums of all n queries of the pass whose front half is in here (one sub-group) -- cleared by pq_front, so they never outlive it.
@@ -419,15 +435,6 @@ struct PqScratch {
   DevBuf<float> half;       // [g][S]
   uint64_t half_cap = 0;    // floats in half
   int half_nq = 0;
-  hipError_t alloc_threshold() {
-    if (tthr) return hipSuccess;
-    hipError_t e = hipSuccess;
-    dev_alloc(e, tthr, PQ_PASS);
-    dev_alloc(e, tcnt, PQ_PASS);
-    dev_alloc(e, tfetch, PQ_PASS);
-    if (e != hipSuccess) tthr.reset(), tcnt.reset(), tfetch.reset();
-    return e;
-  }
   hipError_t alloc_refine() {
     if (rcand) return hipSuccess;
     hipError_t e = hipSuccess;
@@ -471,30 +478,14 @@ struct SqData {
   DevBuf<float> vmin, scale, step;       // [d]; scale = 255 / vdiff and step = vdiff / 255 from the host, 0 where vdiff == 0
   DevBuf<uint8_t> codes;                 // [capacity][d]
   std::vector<unsigned> tile0_h, size_h; // host copy of the layout (knnx_ivfsq_get_codes)
-  // threshold mode of the list scan (knnx_ivfsq_set_threshold_scan): k > 64 and range_search are served; off: they are refused
-  bool threshold_scan = false;
-  int64_t thr_queries = 0, thr_scans = 0, thr_query_scans = 0, thr_hits = 0;  // knnx_ivfsq_threshold_stats
+  ThrState thr;                          // threshold mode of the list scan
 };
 // one IVF-SQ8 pass of up to IVFM_BLK x 32 queries (next to IvfMultiScratch, which serves its coarse half); allocated on first use
 struct SqScratch {
   DevBuf<float> u;         // [256][d] q * step, scaled, in the scan's column order
   DevBuf<_Float16> qfrag;  // [IVFM_BLK][d * 64] its fragment images
   DevBuf<float> bq, inv;   // [256] bias and inverse scale of every query
-  // threshold passes (allocated by the first one): the per-query thresholds and hit counters of one scan, the counters of a fetch, the
-  // rows in every query's probed lists
-  DevBuf<float> tthr;                 // [256]
-  DevBuf<unsigned> tcnt, tfetch;      // [256]
-  DevBuf<unsigned long long> trows;   // [256]
-  hipError_t alloc_threshold() {
-    if (tthr) return hipSuccess;
-    hipError_t e = hipSuccess;
-    dev_alloc(e, tthr, (size_t)IVFM_BLK * KNN_NQ);
-    dev_alloc(e, tcnt, (size_t)IVFM_BLK * KNN_NQ);
-    dev_alloc(e, tfetch, (size_t)IVFM_BLK * KNN_NQ);
-    dev_alloc(e, trows, (size_t)IVFM_BLK * KNN_NQ);
-    if (e != hipSuccess) tthr.reset(), tcnt.reset(), tfetch.reset(), trows.reset();
-    return e;
-  }
+  DevBuf<unsigned long long> trows;   // [256] rows in every query's probed lists (threshold passes; allocated by the first one)
   hipError_t alloc(int d) {
     if (u) return hipSuccess;
     hipError_t e = hipSuccess;
@@ -635,6 +626,24 @@ struct knnx_index {
 // the width of the quantiser space of an IVF-PQ index: d unless knnx_ivfpq_set_out_dim gave another
 inline int pq_dq(const knnx_index* ix) { return ix->pq.dq ? ix->pq.dq : ix->d; }
 
+// What the threshold passes of the two compressed families differ in (pq_thr_pass(): knnx_ivfpq.hip, sq_thr_pass(): knnx_ivfsq.hip);
+// knnx_range.hip drives either through this table.  A pass is one front half over <= pass_max queries already in HBM, then the
+// k = 64 scan, the probed-row totals and any number of threshold scans over what the front half left in the family's scratch.
+struct ThrPass {
+  const char* family;                        // "IVF-PQ" / "IVF-SQ8", for the messages
+  bool (*is)(const knnx_index* ix);          // the index belongs to the family
+  ThrState& (*thr)(knnx_index* ix);          // its threshold state
+  int (*pass_max)(const knnx_index* ix);     // queries of one pass at most
+  int (*front)(knnx_index* ix, const float* q_dev, int nq, hipStream_t st);
+  // the top-64 scores of the pass -> D64 host [nq][64], -FLT_MAX padded.  Synchronises.
+  int (*top64)(knnx_index* ix, int nq, float* D64, hipStream_t st);
+  // rows in the probed lists of every query of the pass -> total [nq].  Synchronises.
+  int (*probed_rows)(knnx_index* ix, int nq, std::vector<int64_t>& total, hipStream_t st);
+  // the threshold kernel(s) alone: thresholds thr.tthr [nq] (+INFINITY: a finished query) -> exact counts in thr.tcnt, hits in
+  // ix->range at q * cap
+  int (*launch_threshold)(knnx_index* ix, int nq, unsigned cap, hipStream_t st);
+};
+
 // ---- what one host file calls in another ---------------------------------------------------------
 // knnx_api.hip
 int set_dev(const knnx_index* ix);
@@ -648,22 +657,23 @@ int scan_topk(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out, i
 int search_fast_locked(knnx_index* ix, const float* q, int n, int k, float* D, int64_t* I);
 // knnx_range.hip
 int search_large_k_locked(knnx_index* ix, const float* q, int n, int k, float* D, int64_t* I);
-int search_large_k_pq_locked(knnx_index* ix, const float* q, int n, int k, float* D, int64_t* I);
-int search_large_k_sq_locked(knnx_index* ix, const float* q, int n, int k, float* D, int64_t* I);
+int search_large_k_thr_locked(knnx_index* ix, const ThrPass& P, const float* q, int n, int k, float* D, int64_t* I);
+int thr_set_switch(knnx_index* ix, const ThrPass& P, int on);
+int thr_switch(const knnx_index* ix, const ThrPass& P);
+int thr_stats(knnx_index* ix, const ThrPass& P, int64_t* queries, int64_t* launches, int64_t* query_scans, int64_t* hits);
 // knnx_ivf.hip
 int ivf_build_worklist(knnx_index* ix, const float* q_dev, int nq, hipStream_t st, const unsigned* gate);
 bool ivfm_usable(const knnx_index* ix, int nq, int k);
 int ivfm_alloc(knnx_index* ix);
 int ivfm_coarse_worklists(knnx_index* ix, const float* q_dev, int nq, int nblk, int grid, int* thr_f_or_null, hipStream_t st);
 int scan_topk_ivf_multi(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out, int64_t* I_out, hipStream_t st);
-bool ivfb_claim_all(knnx_index* ix, const int32_t* lists, const int32_t* pos, int64_t n);
+int ivf_import_codes_locked(knnx_index* ix, uint8_t* arena, int width, const uint8_t* codes, int64_t n, const int64_t* ids, const int32_t* lists,
+                            const int32_t* pos);
+int ivf_export_codes_locked(knnx_index* ix, const uint8_t* arena, int width, const std::vector<unsigned>& tile0_h,
+                            const std::vector<unsigned>& size_h, const char* family, int64_t* ids, int32_t* lists, uint8_t* codes);
 // knnx_ivfpq.hip
 int scan_topk_pq(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out, int64_t* I_out, hipStream_t st);
-// threshold passes (one front half, then any number of threshold scans over its probe lists and lookup tables)
-int pq_front(knnx_index* ix, const float* q_dev, int nq, hipStream_t st, const float** q_used, int* np_out);
-int pq_pass_top64(knnx_index* ix, int nq, int np, float* D64, hipStream_t st);
-int pq_pass_probed_rows(knnx_index* ix, int nq, int np, std::vector<int64_t>& total, hipStream_t st);
-int pq_pass_threshold_scan(knnx_index* ix, int nq, int np, const float* thr_h, unsigned cap, std::vector<unsigned>& counts, hipStream_t st);
+const ThrPass& pq_thr_pass();
 // decoded rows of n ids (device) -> out f32 [n][d] in the ORIGINAL space (back-rotated when the index has a rotation; scratch slot 5);
 // on an index with a refine store: the stored rows themselves
 int pq_decode_rows(knnx_index* ix, const int64_t* ids_dev, int64_t n, float* out_dev, hipStream_t st);
@@ -672,11 +682,7 @@ int pq_decode_rows(knnx_index* ix, const int64_t* ids_dev, int64_t n, float* out
 int scan_topk_sq(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out, int64_t* I_out, hipStream_t st);
 // queries of one IVF-SQ8 pass: IVFM_BLK blocks of 32, fewer where KNNX_GRID leaves fewer workgroups than blocks
 inline int sq_pass_max(const knnx_index* ix) { return KNN_NQ * std::max(1, std::min(IVFM_BLK, ix->n_cu)); }
-// threshold passes (one front half, then any number of threshold launches over its work lists; knnx_range.hip drives them)
-int sq_front(knnx_index* ix, const float* q_dev, int nq, hipStream_t st);
-int sq_pass_top64(knnx_index* ix, int nq, float* D64, hipStream_t st);
-int sq_pass_probed_rows(knnx_index* ix, int nq, std::vector<int64_t>& total, hipStream_t st);
-int sq_pass_threshold_scan(knnx_index* ix, int nq, const float* thr_h, unsigned cap, std::vector<unsigned>& counts, hipStream_t st);
+const ThrPass& sq_thr_pass();
 // decoded rows of n ids (device) -> out f32 [n][d]; -1 -> 0xFF bytes
 int sq_decode_rows(knnx_index* ix, const int64_t* ids_dev, int64_t n, float* out_dev, hipStream_t st);
 

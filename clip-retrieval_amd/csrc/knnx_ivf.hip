@@ -539,7 +539,7 @@ static bool ivfb_claim(knnx_index* ix, int32_t list, int64_t pos) {
 }
 
 // claim (lists[i], pos[i]) for all n rows of a call, or none of them: a refused call leaves the build as it was
-bool ivfb_claim_all(knnx_index* ix, const int32_t* lists, const int32_t* pos, int64_t n) {
+static bool ivfb_claim_all(knnx_index* ix, const int32_t* lists, const int32_t* pos, int64_t n) {
   for (int64_t i = 0; i < n; ++i)
     if (!ivfb_claim(ix, lists[i], pos[i])) {
       for (int64_t j = 0; j < i; ++j) {
@@ -550,6 +550,52 @@ bool ivfb_claim_all(knnx_index* ix, const int32_t* lists, const int32_t* pos, in
       return false;
     }
   return true;
+}
+
+// ---- codes in and out of a compressed index (knnx_ivfpq_add_codes / knnx_ivfsq_add_codes, ..._get_codes): `width` code bytes per row in
+// `arena`.  The callers hold ix->mu and have checked their arguments and the state of their family.
+// precomputed codes [n][width] (host) into an index between knnx_ivf_begin and knnx_ivf_end: the (list, position) rules of
+// knnx_ivf_add_assigned, the scatter alone
+int ivf_import_codes_locked(knnx_index* ix, uint8_t* arena, int width, const uint8_t* codes, int64_t n, const int64_t* ids, const int32_t* lists,
+                            const int32_t* pos) {
+  if (ix->ivfb.added + n > ix->ivfb.total) return fail(KNNX_E_ARG, "more rows than the list sizes announced");
+  for (int64_t i = 0; i < n; ++i)
+    if (ids[i] < ix->id_base || ids[i] - ix->id_base >= ix->ivfb.total) return fail(KNNX_E_ARG, "ids must lie in [id_base, id_base + total rows)");
+  if (!ivfb_claim_all(ix, lists, pos, n)) return KNNX_E_ARG;
+  // (ivfb.rows holds IVFB_CHUNK x d x 2 bytes: room for IVFB_CHUNK rows of `width` <= 2 d code bytes)
+  for (int64_t o = 0; o < n; o += IVFB_CHUNK) {
+    const int64_t m = std::min(IVFB_CHUNK, n - o);
+    HIPCHK(hipMemcpy(ix->ivfb.rows, codes + (size_t)o * width, (size_t)m * width, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ix->ivfb.ids, ids + o, (size_t)m * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ix->ivfb.lists, lists + o, (size_t)m * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ix->ivfb.pos, pos + o, (size_t)m * 4, hipMemcpyHostToDevice));
+    HIPCHK(launch_pq_scatter_codes((const uint8_t*)ix->ivfb.rows.p, m, width, ix->ivfb.lists, ix->ivfb.pos, ix->ivfb.ids, ix->ivf.tile0,
+                                   ix->id_base, ix->ivfb.total, arena, ix->ivf.idmap, ix->ivf.inv, ix->stream));
+    HIPCHK(hipStreamSynchronize(ix->stream));
+  }
+  ix->ivfb.added += n;
+  return KNNX_OK;
+}
+
+// every row of a built index in arena order: ids [ntotal], lists [ntotal], codes [ntotal][width].  tile0_h / size_h: the host copy of
+// the layout.  A list's rows are contiguous in the arena: one copy per list, straight into place.
+int ivf_export_codes_locked(knnx_index* ix, const uint8_t* arena, int width, const std::vector<unsigned>& tile0_h,
+                            const std::vector<unsigned>& size_h, const char* family, int64_t* ids, int32_t* lists, uint8_t* codes) {
+  if (set_dev(ix)) return KNNX_E_HIP;
+  HIPCHK(hipStreamSynchronize(ix->stream));
+  const size_t w = (size_t)width;
+  std::vector<int64_t> idmap((size_t)ix->capacity);
+  HIPCHK(hipMemcpy(idmap.data(), ix->ivf.idmap, idmap.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+  int64_t o = 0;
+  for (int l = 0; l < ix->ivf_nlist; ++l) {
+    const size_t r0 = (size_t)tile0_h[l] * 32, n = size_h[l];
+    if (n) HIPCHK(hipMemcpy(codes + (size_t)o * w, arena + r0 * w, n * w, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i, ++o) {
+      ids[o] = idmap[r0 + i];
+      lists[o] = l;
+    }
+  }
+  return o == ix->ntotal ? KNNX_OK : fail(KNNX_E_STATE, std::string("internal: ") + family + " layout does not add up to ntotal");
 }
 
 extern "C" int knnx_ivf_add_assigned(knnx_index* ix, const uint16_t* rows_f16, int64_t n, const int64_t* ids, const int32_t* lists,

@@ -12,9 +12,9 @@
 // ---------------------------------------------------------------------------------------------
 //
 // The front half of a pass, shared by the top-k pass and the threshold passes: rotation, query prep, coarse dump, select / mark,
-// probe lists and lookup tables.  Leaves probe / pscore / pcnt / lut of the nq queries in ix->pqs; *q_used = the queries the ADC
-// stage scores (the rotated ones behind an OPQ rotation), *np_out = lists probed per query.
-int pq_front(knnx_index* ix, const float* q_dev, int nq, hipStream_t st, const float** q_used, int* np_out) {
+// probe lists and lookup tables.  Leaves probe / pscore / pcnt / lut of the nq queries in ix->pqs, and in ix->pqs.np the lists probed
+// per query.
+static int pq_front(knnx_index* ix, const float* q_dev, int nq, hipStream_t st) {
   const int np = std::min(ix->ivf_nprobe, ix->ivf_nlist);
   const int dq = pq_dq(ix);  // everything behind the rotation is dq wide (= d unless the index was given a d_out)
   HIPCHK(ix->pqs.alloc(dq, (size_t)ix->ivf_nlist, ix->pq.m, np));
@@ -48,8 +48,7 @@ int pq_front(knnx_index* ix, const float* q_dev, int nq, hipStream_t st, const f
     ix->pqs.half_nq = 0;  // the sums of an earlier front half are not these queries'
   }
   HIPCHK(launch_pq_lut(q_dev, nq, dq, ix->pq.m, ix->pq.cb, ix->pqs.lut, st));
-  *q_used = q_dev;
-  *np_out = np;
+  ix->pqs.np = np;
   return 0;
 }
 
@@ -159,9 +158,9 @@ int scan_topk_pq(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out
     return fail(KNNX_E_ARG, "k x k_factor = " + std::to_string(k) + " x " + std::to_string(ix->pq.k_factor) + " exceeds " +
                                 std::to_string(PQ_REFINE_MAX) + " candidates per query");
   const float* q_orig = q_dev;
-  int np = 0;
-  int r = pq_front(ix, q_orig, nq, st, &q_dev, &np);
+  int r = pq_front(ix, q_orig, nq, st);
   if (r) return r;
+  const int np = ix->pqs.np;
   if (ix->pq.refine) HIPCHK(ix->pqs.alloc_refine());
   int nsplit = pq_nsplit(np, nq);
   if (ix->pq.refine) {
@@ -200,9 +199,9 @@ int scan_topk_pq(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out
 // ---------------------------------------------------------------------------------------------
 // the plain ADC top-64 scores of the pass whose front half is in ix->pqs (no refine stage) -> D64 host [nq][64], -FLT_MAX padded.
 // Synchronises.
-int pq_pass_top64(knnx_index* ix, int nq, int np, float* D64, hipStream_t st) {
+static int pq_pass_top64(knnx_index* ix, int nq, float* D64, hipStream_t st) {
   PqScratch& S = ix->pqs;
-  const int nsplit = pq_nsplit(np, nq), k = KNNX_MAX_K_FAST;
+  const int np = S.np, nsplit = pq_nsplit(np, nq), k = KNNX_MAX_K_FAST;
   int r = pq_stage_topk(ix, nq, np, nsplit, k, S.part_s, S.part_i, st);
   if (r) return r;
   HIPCHK(launch_merge_u32(S.part_s, S.part_i, S.part_n, nsplit, nq, k, nq, k, ix->id_base, ix->ivf.idmap, ix->flat.D_dev, ix->flat.I_dev,
@@ -213,7 +212,8 @@ int pq_pass_top64(knnx_index* ix, int nq, int np, float* D64, hipStream_t st) {
 }
 
 // rows in the probed lists of every query of the pass -> total [nq].  Synchronises.
-int pq_pass_probed_rows(knnx_index* ix, int nq, int np, std::vector<int64_t>& total, hipStream_t st) {
+static int pq_pass_probed_rows(knnx_index* ix, int nq, std::vector<int64_t>& total, hipStream_t st) {
+  const int np = ix->pqs.np;
   std::vector<unsigned> pc((size_t)nq);
   std::vector<int> pr((size_t)nq * np);
   HIPCHK(hipMemcpyAsync(pc.data(), ix->pqs.pcnt, pc.size() * sizeof(unsigned), hipMemcpyDeviceToHost, st));
@@ -229,50 +229,40 @@ int pq_pass_probed_rows(knnx_index* ix, int nq, int np, std::vector<int64_t>& to
   return 0;
 }
 
-// one threshold scan of the pass: thr_h [nq] (host; +INFINITY skips a query) -> counts [nq] (exact), hits in ix->range at q * cap.
-// Synchronises.
-int pq_pass_threshold_scan(knnx_index* ix, int nq, int np, const float* thr_h, unsigned cap, std::vector<unsigned>& counts, hipStream_t st) {
+// the threshold ADC scan of the pass (ThrPass::launch_threshold); +INFINITY skips a query
+static int pq_pass_launch_threshold(knnx_index* ix, int nq, unsigned cap, hipStream_t st) {
   PqScratch& S = ix->pqs;
-  HIPCHK(S.alloc_threshold());
-  HIPCHK(hipMemcpyAsync(S.tthr, thr_h, (size_t)nq * sizeof(float), hipMemcpyHostToDevice, st));
-  HIPCHK(ix->prof.begin(ix->prof.on, st));
+  ThrState& T = ix->pq.thr;
+  const int np = S.np;
   if (ix->pq.m == 256) {
     PqStage a;
-    a.kind = PqStage::RANGE, a.thr = S.tthr, a.cnt = S.tcnt, a.cap = cap, a.hit_s = ix->range.s, a.hit_r = ix->range.i;
-    int r = pq_two_half_stage(ix, nq, np, pq_nsplit(np, nq), a, st);
-    if (r) return r;
-  } else {
-    HIPCHK(launch_pq_range_scan(ix->pq.codes, ix->pq.m, S.lut, S.probe, S.pscore, S.pcnt, np, pq_nsplit(np, nq), ix->ivf.tile0, ix->ivf.size,
-                                S.tthr, S.tcnt, cap, ix->range.s, ix->range.i, nq, st));
+    a.kind = PqStage::RANGE, a.thr = T.tthr, a.cnt = T.tcnt, a.cap = cap, a.hit_s = ix->range.s, a.hit_r = ix->range.i;
+    return pq_two_half_stage(ix, nq, np, pq_nsplit(np, nq), a, st);
   }
-  HIPCHK(ix->prof.end(ix->prof.on, st));
-  counts.assign((size_t)nq, 0u);
-  HIPCHK(hipMemcpyAsync(counts.data(), S.tcnt, (size_t)nq * sizeof(unsigned), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  ++ix->pq.thr_scans;
+  HIPCHK(launch_pq_range_scan(ix->pq.codes, ix->pq.m, S.lut, S.probe, S.pscore, S.pcnt, np, pq_nsplit(np, nq), ix->ivf.tile0, ix->ivf.size,
+                              T.tthr, T.tcnt, cap, ix->range.s, ix->range.i, nq, st));
   return 0;
 }
 
-extern "C" int knnx_ivfpq_set_threshold_scan(knnx_index* ix, int on) {
-  if (!ix) return fail(KNNX_E_ARG, "index is null");
-  std::lock_guard<std::mutex> lk(ix->mu);
-  if (!ix->pq.m) return fail(KNNX_E_STATE, "not an IVF-PQ index");
-  ix->pq.threshold_scan = on != 0;
-  return KNNX_OK;
+// (a function-local table: a namespace-scope constant would be emitted for the device too, where the host functions it names do not exist)
+const ThrPass& pq_thr_pass() {
+  static const ThrPass P = {
+    "IVF-PQ",
+    [](const knnx_index* ix) { return ix->pq.m != 0; },
+    [](knnx_index* ix) -> ThrState& { return ix->pq.thr; },
+    [](const knnx_index*) { return PQ_PASS; },
+    pq_front,
+    pq_pass_top64,
+    pq_pass_probed_rows,
+    pq_pass_launch_threshold,
+  };
+  return P;
 }
-extern "C" int knnx_ivfpq_threshold_scan(const knnx_index* ix) { return ix && ix->pq.m && ix->pq.threshold_scan ? 1 : 0; }
 
-// counters of the threshold passes since the index was created: queries served with k > 64, threshold scans launched (one launch
-// serves a whole group), scans summed over the queries that took part in them, hits fetched to the host
+extern "C" int knnx_ivfpq_set_threshold_scan(knnx_index* ix, int on) { return thr_set_switch(ix, pq_thr_pass(), on); }
+extern "C" int knnx_ivfpq_threshold_scan(const knnx_index* ix) { return thr_switch(ix, pq_thr_pass()); }
 extern "C" int knnx_ivfpq_threshold_stats(knnx_index* ix, int64_t* queries, int64_t* launches, int64_t* query_scans, int64_t* hits) {
-  if (!ix) return fail(KNNX_E_ARG, "index is null");
-  std::lock_guard<std::mutex> lk(ix->mu);
-  if (!ix->pq.m) return fail(KNNX_E_STATE, "not an IVF-PQ index");
-  if (queries) *queries = ix->pq.thr_queries;
-  if (launches) *launches = ix->pq.thr_scans;
-  if (query_scans) *query_scans = ix->pq.thr_query_scans;
-  if (hits) *hits = ix->pq.thr_hits;
-  return KNNX_OK;
+  return thr_stats(ix, pq_thr_pass(), queries, launches, query_scans, hits);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -474,27 +464,10 @@ extern "C" int knnx_ivfpq_get_codes(knnx_index* ix, int64_t* ids, int32_t* lists
   if (!ix || !ids || !lists || !codes) return fail(KNNX_E_ARG, "bad ivfpq_get_codes arguments");
   std::lock_guard<std::mutex> lk(ix->mu);
   if (!ix->pq.m || !ix->ivf_nlist) return fail(KNNX_E_STATE, "not a built IVF-PQ index (knnx_ivf_end first)");
-  if (set_dev(ix)) return KNNX_E_HIP;
-  HIPCHK(hipStreamSynchronize(ix->stream));
-  const int M = ix->pq.m;
-  std::vector<int64_t> idmap((size_t)ix->capacity);
-  std::vector<uint8_t> all((size_t)ix->capacity * M);
-  HIPCHK(hipMemcpy(idmap.data(), ix->ivf.idmap, idmap.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(all.data(), ix->pq.codes, all.size(), hipMemcpyDeviceToHost));
-  int64_t o = 0;
-  for (int l = 0; l < ix->ivf_nlist; ++l) {
-    const size_t r0 = (size_t)ix->pq.tile0_h[l] * 32;
-    for (unsigned i = 0; i < ix->pq.size_h[l]; ++i, ++o) {
-      ids[o] = idmap[r0 + i];
-      lists[o] = l;
-      memcpy(codes + (size_t)o * M, all.data() + (r0 + i) * M, M);
-    }
-  }
-  return o == ix->ntotal ? KNNX_OK : fail(KNNX_E_STATE, "internal: IVF-PQ layout does not add up to ntotal");
+  return ivf_export_codes_locked(ix, ix->pq.codes, ix->pq.m, ix->pq.tile0_h, ix->pq.size_h, "IVF-PQ", ids, lists, codes);
 }
 
-// precomputed codes [n][M] (host) into an index between knnx_ivf_begin and knnx_ivf_end: the same (list, position) rules as
-// knnx_ivf_add_assigned; no encoding (an index loaded from its saved codes)
+// precomputed codes [n][M] (host) into an index between knnx_ivf_begin and knnx_ivf_end (an index loaded from its saved codes)
 extern "C" int knnx_ivfpq_add_codes(knnx_index* ix, const uint8_t* codes, int64_t n, const int64_t* ids, const int32_t* lists,
                                     const int32_t* pos) {
   if (!ix || (n > 0 && (!codes || !ids || !lists || !pos)) || n < 0) return fail(KNNX_E_ARG, "bad ivfpq_add_codes arguments");
@@ -503,25 +476,7 @@ extern "C" int knnx_ivfpq_add_codes(knnx_index* ix, const uint8_t* codes, int64_
   if (set_dev(ix)) return KNNX_E_HIP;
   if (!ix->pq.m || !ix->ivfb.nlist) return fail(KNNX_E_STATE, "set the PQ quantizer and call knnx_ivf_begin first");
   if (ix->pq.refine) return fail(KNNX_E_STATE, "an index with a refine store takes rows (knnx_ivf_add_assigned), not codes: it has no rows to store");
-  if (ix->ivfb.added + n > ix->ivfb.total) return fail(KNNX_E_ARG, "more rows than the list sizes announced");
-  for (int64_t i = 0; i < n; ++i)
-    if (ids[i] < ix->id_base || ids[i] - ix->id_base >= ix->ivfb.total) return fail(KNNX_E_ARG, "ids must lie in [id_base, id_base + total rows)");
-  if (!ivfb_claim_all(ix, lists, pos, n)) return KNNX_E_ARG;
-  const int M = ix->pq.m;
-  // (ivfb_rows holds IVFB_CHUNK x d x 2 >= IVFB_CHUNK x M bytes)
-  for (int64_t o = 0; o < n; o += IVFB_CHUNK) {
-    const int64_t m = std::min(IVFB_CHUNK, n - o);
-    HIPCHK(hipMemcpy(ix->ivfb.rows, codes + (size_t)o * M, (size_t)m * M, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(ix->ivfb.ids, ids + o, (size_t)m * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(ix->ivfb.lists, lists + o, (size_t)m * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(ix->ivfb.pos, pos + o, (size_t)m * 4, hipMemcpyHostToDevice));
-    HIPCHK(launch_pq_scatter_codes((const uint8_t*)ix->ivfb.rows.p, m, M, ix->ivfb.lists, ix->ivfb.pos,
-                                   ix->ivfb.ids, ix->ivf.tile0, ix->id_base, ix->ivfb.total, ix->pq.codes, ix->ivf.idmap,
-                                   ix->ivf.inv, ix->stream));
-    HIPCHK(hipStreamSynchronize(ix->stream));
-  }
-  ix->ivfb.added += n;
-  return KNNX_OK;
+  return ivf_import_codes_locked(ix, ix->pq.codes, ix->pq.m, codes, n, ids, lists, pos);
 }
 
 // ---- codebook training (faiss ProductQuantizer::train on the residuals of a sample; one L2 k-means of 256 per sub-quantiser) ----

@@ -18,7 +18,7 @@
 static int sq_blocks(int nq) { return (nq + KNN_NQ - 1) / KNN_NQ; }
 static int sq_grid(const knnx_index* ix, int nblk) { return std::max(1, ix->n_cu / nblk) * nblk; }  // (part_* hold n_cu x 64 lists: grid <= n_cu)
 
-int sq_front(knnx_index* ix, const float* q_dev, int nq, hipStream_t st) {
+static int sq_front(knnx_index* ix, const float* q_dev, int nq, hipStream_t st) {
   const int nblk = sq_blocks(nq);
   if (nq < 1 || nblk > IVFM_BLK || nblk > ix->n_cu) return fail(KNNX_E_STATE, "internal: IVF-SQ8 pass misuse");
   const int grid = sq_grid(ix, nblk);
@@ -83,7 +83,7 @@ int scan_topk_sq(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out
 
 // ---- threshold passes (the switch knnx_ivfsq_set_threshold_scan; knnx_range.hip drives them) ---------------------------------------
 // the top-64 scores of the pass whose front half is in place -> D64 host [nq][64], -FLT_MAX padded.  Synchronises.
-int sq_pass_top64(knnx_index* ix, int nq, float* D64, hipStream_t st) {
+static int sq_pass_top64(knnx_index* ix, int nq, float* D64, hipStream_t st) {
   const int k = KNNX_MAX_K_FAST;
   int r = sq_topk_scan_merge(ix, nq, k, ix->flat.D_dev, ix->flat.I_dev, st);
   if (r) return r;
@@ -93,8 +93,8 @@ int sq_pass_top64(knnx_index* ix, int nq, float* D64, hipStream_t st) {
 }
 
 // rows in the probed lists of every query of the pass -> total [nq], summed on the device from the blocks' list masks.  Synchronises.
-int sq_pass_probed_rows(knnx_index* ix, int nq, std::vector<int64_t>& total, hipStream_t st) {
-  HIPCHK(ix->sqs.alloc_threshold());
+static int sq_pass_probed_rows(knnx_index* ix, int nq, std::vector<int64_t>& total, hipStream_t st) {
+  if (!ix->sqs.trows) HIPCHK(ix->sqs.trows.alloc((size_t)IVFM_BLK * KNN_NQ));
   HIPCHK(launch_sq_probed_rows(ix->ivfm.masks, ix->ivf.size, ix->ivf_nlist, nq, ix->sqs.trows, st));
   std::vector<unsigned long long> t((size_t)nq);
   HIPCHK(hipMemcpyAsync(t.data(), ix->sqs.trows, t.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
@@ -103,48 +103,36 @@ int sq_pass_probed_rows(knnx_index* ix, int nq, std::vector<int64_t>& total, hip
   return 0;
 }
 
-// one threshold launch of the pass: thr_h [nq] (host; +INFINITY: a finished query) -> counts [nq] (exact), hits in ix->range at q * cap;
-// the device counters stay in ix->sqs.tcnt.  Synchronises.
-int sq_pass_threshold_scan(knnx_index* ix, int nq, const float* thr_h, unsigned cap, std::vector<unsigned>& counts, hipStream_t st) {
-  SqScratch& S = ix->sqs;
-  HIPCHK(S.alloc_threshold());
-  HIPCHK(hipMemcpyAsync(S.tthr, thr_h, (size_t)nq * sizeof(float), hipMemcpyHostToDevice, st));
+// the threshold launch of the pass (ThrPass::launch_threshold)
+static int sq_pass_launch_threshold(knnx_index* ix, int nq, unsigned cap, hipStream_t st) {
   SqScanArgs a = sq_scan_args(ix, nq);
-  a.rthr = S.tthr;
-  a.rcnt = S.tcnt;
+  a.rthr = ix->sq.thr.tthr;
+  a.rcnt = ix->sq.thr.tcnt;
   a.rcap = cap;
   a.hit_s = ix->range.s;
   a.hit_i = ix->range.i;
-  HIPCHK(ix->prof.begin(ix->prof.on, st));
   HIPCHK(launch_sq_range_scan(a, st));
-  HIPCHK(ix->prof.end(ix->prof.on, st));
-  counts.assign((size_t)nq, 0u);
-  HIPCHK(hipMemcpyAsync(counts.data(), S.tcnt, (size_t)nq * sizeof(unsigned), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  ++ix->sq.thr_scans;
   return 0;
 }
 
-extern "C" int knnx_ivfsq_set_threshold_scan(knnx_index* ix, int on) {
-  if (!ix) return fail(KNNX_E_ARG, "index is null");
-  std::lock_guard<std::mutex> lk(ix->mu);
-  if (!ix->sq.on) return fail(KNNX_E_STATE, "not an IVF-SQ8 index");
-  ix->sq.threshold_scan = on != 0;
-  return KNNX_OK;
+const ThrPass& sq_thr_pass() {
+  static const ThrPass P = {
+    "IVF-SQ8",
+    [](const knnx_index* ix) { return ix->sq.on; },
+    [](knnx_index* ix) -> ThrState& { return ix->sq.thr; },
+    sq_pass_max,
+    sq_front,
+    sq_pass_top64,
+    sq_pass_probed_rows,
+    sq_pass_launch_threshold,
+  };
+  return P;
 }
-extern "C" int knnx_ivfsq_threshold_scan(const knnx_index* ix) { return ix && ix->sq.on && ix->sq.threshold_scan ? 1 : 0; }
 
-// counters of the threshold passes since the index was created: queries served with k > 64, threshold launches (one serves a whole
-// group), launches summed over the queries that took part in them, hits fetched to the host
+extern "C" int knnx_ivfsq_set_threshold_scan(knnx_index* ix, int on) { return thr_set_switch(ix, sq_thr_pass(), on); }
+extern "C" int knnx_ivfsq_threshold_scan(const knnx_index* ix) { return thr_switch(ix, sq_thr_pass()); }
 extern "C" int knnx_ivfsq_threshold_stats(knnx_index* ix, int64_t* queries, int64_t* launches, int64_t* query_scans, int64_t* hits) {
-  if (!ix) return fail(KNNX_E_ARG, "index is null");
-  std::lock_guard<std::mutex> lk(ix->mu);
-  if (!ix->sq.on) return fail(KNNX_E_STATE, "not an IVF-SQ8 index");
-  if (queries) *queries = ix->sq.thr_queries;
-  if (launches) *launches = ix->sq.thr_scans;
-  if (query_scans) *query_scans = ix->sq.thr_query_scans;
-  if (hits) *hits = ix->sq.thr_hits;
-  return KNNX_OK;
+  return thr_stats(ix, sq_thr_pass(), queries, launches, query_scans, hits);
 }
 
 int sq_decode_rows(knnx_index* ix, const int64_t* ids_dev, int64_t n, float* out_dev, hipStream_t st) {
@@ -206,25 +194,10 @@ extern "C" int knnx_ivfsq_get_codes(knnx_index* ix, int64_t* ids, int32_t* lists
   if (!ix || !ids || !lists || !codes) return fail(KNNX_E_ARG, "bad ivfsq_get_codes arguments");
   std::lock_guard<std::mutex> lk(ix->mu);
   if (!ix->sq.on || !ix->ivf_nlist) return fail(KNNX_E_STATE, "not a built IVF-SQ8 index (knnx_ivf_end first)");
-  if (set_dev(ix)) return KNNX_E_HIP;
-  HIPCHK(hipStreamSynchronize(ix->stream));
-  const size_t d = (size_t)ix->d;
-  std::vector<int64_t> idmap((size_t)ix->capacity);
-  HIPCHK(hipMemcpy(idmap.data(), ix->ivf.idmap, idmap.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
-  int64_t o = 0;
-  for (int l = 0; l < ix->ivf_nlist; ++l) {  // a list's rows are contiguous in the arena: one copy per list, straight into place
-    const size_t r0 = (size_t)ix->sq.tile0_h[l] * 32, n = ix->sq.size_h[l];
-    if (n) HIPCHK(hipMemcpy(codes + (size_t)o * d, ix->sq.codes + r0 * d, n * d, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < n; ++i, ++o) {
-      ids[o] = idmap[r0 + i];
-      lists[o] = l;
-    }
-  }
-  return o == ix->ntotal ? KNNX_OK : fail(KNNX_E_STATE, "internal: IVF-SQ8 layout does not add up to ntotal");
+  return ivf_export_codes_locked(ix, ix->sq.codes, ix->d, ix->sq.tile0_h, ix->sq.size_h, "IVF-SQ8", ids, lists, codes);
 }
 
-// precomputed codes [n][d] (host) into an index between knnx_ivf_begin and knnx_ivf_end: the (list, position) rules of
-// knnx_ivf_add_assigned, the scatter alone (an index loaded from its saved codes)
+// precomputed codes [n][d] (host) into an index between knnx_ivf_begin and knnx_ivf_end (an index loaded from its saved codes)
 extern "C" int knnx_ivfsq_add_codes(knnx_index* ix, const uint8_t* codes, int64_t n, const int64_t* ids, const int32_t* lists,
                                     const int32_t* pos) {
   if (!ix || (n > 0 && (!codes || !ids || !lists || !pos)) || n < 0) return fail(KNNX_E_ARG, "bad ivfsq_add_codes arguments");
@@ -232,24 +205,7 @@ extern "C" int knnx_ivfsq_add_codes(knnx_index* ix, const uint8_t* codes, int64_
   std::lock_guard<std::mutex> lk(ix->mu);
   if (set_dev(ix)) return KNNX_E_HIP;
   if (!ix->sq.on || !ix->ivfb.nlist) return fail(KNNX_E_STATE, "set the IVF-SQ8 quantizer and call knnx_ivf_begin first");
-  if (ix->ivfb.added + n > ix->ivfb.total) return fail(KNNX_E_ARG, "more rows than the list sizes announced");
-  for (int64_t i = 0; i < n; ++i)
-    if (ids[i] < ix->id_base || ids[i] - ix->id_base >= ix->ivfb.total) return fail(KNNX_E_ARG, "ids must lie in [id_base, id_base + total rows)");
-  if (!ivfb_claim_all(ix, lists, pos, n)) return KNNX_E_ARG;
-  const int d = ix->d;
-  // (ivfb.rows holds IVFB_CHUNK x d x 2 bytes: room for IVFB_CHUNK rows of d code bytes)
-  for (int64_t o = 0; o < n; o += IVFB_CHUNK) {
-    const int64_t m = std::min(IVFB_CHUNK, n - o);
-    HIPCHK(hipMemcpy(ix->ivfb.rows, codes + (size_t)o * d, (size_t)m * d, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(ix->ivfb.ids, ids + o, (size_t)m * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(ix->ivfb.lists, lists + o, (size_t)m * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(ix->ivfb.pos, pos + o, (size_t)m * 4, hipMemcpyHostToDevice));
-    HIPCHK(launch_pq_scatter_codes((const uint8_t*)ix->ivfb.rows.p, m, d, ix->ivfb.lists, ix->ivfb.pos, ix->ivfb.ids, ix->ivf.tile0,
-                                   ix->id_base, ix->ivfb.total, ix->sq.codes, ix->ivf.idmap, ix->ivf.inv, ix->stream));
-    HIPCHK(hipStreamSynchronize(ix->stream));
-  }
-  ix->ivfb.added += n;
-  return KNNX_OK;
+  return ivf_import_codes_locked(ix, ix->sq.codes, ix->d, codes, n, ids, lists, pos);
 }
 
 // ---- training: per-column min and max of fp16 rows in HBM (faiss RS_minmax with argument 0) ---------------------------------------

@@ -1,10 +1,8 @@
 // knnx_range.hip -- range scans and the large-k search built on them (host side; see knnx_host.h).
 
 #include "knnx_host.h"
-#include "knnx_descent.h"
+#include "knnx_thr_group.h"
 
-// range scan of <= KNN_NQ queries; leaves per-query counts in `counts` and the hits on the device
-// (query i's hits at range_s/range_i[i*cap .. i*cap+counts[i]), cap = range_pool / nq)
 static const size_t RANGE_POOL_MAX = (size_t)1 << 29;  // 512 Mi hits = 4 GiB of scratch
 constexpr int64_t RANGE_BATCH_MAX_ROWS = 1 << 16;  // range_scan_batched: indexes up to this many rows (a scan is launch-bound there)
 
@@ -19,6 +17,24 @@ static int range_pool_alloc(knnx_index* ix, size_t want) {
   return 0;
 }
 
+// *cap = the entries each of `slices` queries has in the pools (allocated here when there are none yet)
+static int range_pool_slice(knnx_index* ix, size_t slices, unsigned* cap) {
+  int r;
+  if (ix->range.pool == 0 && (r = range_pool_alloc(ix, (size_t)1 << 21))) return r;
+  *cap = (unsigned)std::min<size_t>(ix->range.pool / slices, 0xffffffffu);
+  return 0;
+}
+
+// a scan counted mx hits for one of its `slices` queries and its slice overflowed: grow the pools until mx fit (the caller scans
+// again: the counts are exact even when the slices overflowed).  what: "range_search" / "large-k search", for the message
+static int range_pool_fit(knnx_index* ix, size_t slices, size_t mx, const char* what) {
+  const size_t want = pool_want(ix->range.pool, slices, mx);
+  if (want > RANGE_POOL_MAX) return fail(KNNX_E_NOMEM, std::string(what) + " result exceeds the 512 Mi-hit scratch limit");
+  return range_pool_alloc(ix, want);
+}
+
+// range scan of <= KNN_NQ queries; leaves per-query counts in `counts` and the hits on the device
+// (query i's hits at range_s/range_i[i*cap .. i*cap+counts[i]), cap = range_pool / nq)
 static int range_scan(knnx_index* ix, const float* q_host, int nq, float thr, std::vector<unsigned>& counts,
                       unsigned* cap_out) {
   hipStream_t st = ix->stream;
@@ -28,8 +44,8 @@ static int range_scan(knnx_index* ix, const float* q_host, int nq, float thr, st
   memcpy(ix->pin.p, q_host, (size_t)nq * ix->d * sizeof(float));
   HIPCHK(hipMemcpyAsync(ix->flat.q_dev, ix->pin.p, (size_t)nq * ix->d * sizeof(float), hipMemcpyHostToDevice, st));
   for (;;) {
-    if (ix->range.pool == 0 && (r = range_pool_alloc(ix, (size_t)1 << 21))) return r;
-    const unsigned cap = (unsigned)std::min<size_t>(ix->range.pool / (size_t)nq, 0xffffffffu);
+    unsigned cap = 0;
+    if ((r = range_pool_slice(ix, (size_t)nq, &cap))) return r;
     if (ix->ivf_nlist) {  // IVF: the range is taken over the rows of the nprobe best lists of each query (faiss IndexIVF semantics)
       r = ivf_build_worklist(ix, ix->flat.q_dev, nq, st, nullptr);
       if (r) return r;
@@ -63,11 +79,7 @@ static int range_scan(knnx_index* ix, const float* q_host, int nq, float thr, st
       *cap_out = cap;
       return 0;
     }
-    // overflow: regrow and rescan (the counts are exact even when the buffers overflowed)
-    size_t want = ix->range.pool;
-    while (want / (size_t)nq < (size_t)mx) want <<= 1;
-    if (want > RANGE_POOL_MAX) return fail(KNNX_E_NOMEM, "range_search result exceeds the 512 Mi-hit scratch limit");
-    if ((r = range_pool_alloc(ix, want))) return r;
+    if ((r = range_pool_fit(ix, (size_t)nq, mx, "range_search"))) return r;
   }
 }
 
@@ -89,8 +101,8 @@ static int range_scan_batched(knnx_index* ix, const float* q_host, int n, float 
   if (scratch_acquire(ix, st)) return KNNX_E_HIP;
   HIPCHK(hipMemcpyAsync(q_all, q_host, (size_t)n * ix->d * sizeof(float), hipMemcpyHostToDevice, st));
   for (;;) {
-    if (ix->range.pool == 0 && (r = range_pool_alloc(ix, (size_t)1 << 21))) return r;
-    const unsigned cap = (unsigned)std::min<size_t>(ix->range.pool / nr, 0xffffffffu);
+    unsigned cap = 0;
+    if ((r = range_pool_slice(ix, nr, &cap))) return r;
     unsigned mx = 0;
     if (cap > 0) {
       for (int g = 0; g < ngroups; ++g) {
@@ -126,11 +138,7 @@ static int range_scan_batched(knnx_index* ix, const float* q_host, int n, float 
     } else {
       mx = 1;
     }
-    // overflow: regrow and rescan (the counts are exact even when the buffers overflowed)
-    size_t want = ix->range.pool;
-    while (want / nr < (size_t)mx) want <<= 1;
-    if (want > RANGE_POOL_MAX) return fail(KNNX_E_NOMEM, "range_search result exceeds the 512 Mi-hit scratch limit");
-    if ((r = range_pool_alloc(ix, want))) return r;
+    if ((r = range_pool_fit(ix, nr, mx, "range_search"))) return r;
   }
 }
 
@@ -181,85 +189,73 @@ static int range_fetch(knnx_index* ix, int nq, const std::vector<unsigned>& coun
   return 0;
 }
 
-// ---- IVF-PQ with the threshold-scan switch on (knnx_ivfpq_set_threshold_scan): the ADC scan in threshold mode feeds the same pools ----
-// stage a group of <= PQ_PASS queries and run the front half of their pass (knnx_ivfpq.hip: pq_front)
-static int pq_pass_begin(knnx_index* ix, const float* q_host, int nq, int* np) {
+// ---- IVF-PQ / IVF-SQ8 with the threshold-scan switch on: the family's list scan in threshold mode feeds the same pools.  P says what
+// the two differ in (knnx_host.h: ThrPass) ----
+// stage a group of <= P.pass_max queries and run the front half of their pass
+static int thr_pass_begin(knnx_index* ix, const ThrPass& P, const float* q_host, int nq) {
   hipStream_t st = ix->stream;
-  int r = ensure_pin(ix, (size_t)PQ_PASS * ix->d * sizeof(float));
+  int r = ensure_pin(ix, (size_t)P.pass_max(ix) * ix->d * sizeof(float));
   if (r) return r;
   if (scratch_acquire(ix, st)) return KNNX_E_HIP;
   memcpy(ix->pin.p, q_host, (size_t)nq * ix->d * sizeof(float));
   HIPCHK(hipMemcpyAsync(ix->flat.q_dev, ix->pin.p, (size_t)nq * ix->d * sizeof(float), hipMemcpyHostToDevice, st));
-  const float* used = nullptr;
-  return pq_front(ix, ix->flat.q_dev, nq, st, &used, np);
+  return P.front(ix, ix->flat.q_dev, nq, st);
 }
 
-// range scan of <= PQ_PASS queries of an IVF-PQ index: the rows of the probed lists whose ADC score is > thr.  Counts and hits as
-// range_scan leaves them, the device counters in ix->pqs.tcnt.
-static int range_scan_pq(knnx_index* ix, const float* q_host, int nq, float thr, std::vector<unsigned>& counts, unsigned* cap_out) {
-  int np = 0;
-  int r = pq_pass_begin(ix, q_host, nq, &np);
+// one threshold scan of the pass: thr_h [nq] (host; +INFINITY: a finished query) -> counts [nq] (exact), hits in ix->range at q * cap;
+// the device counters stay in the family's tcnt.  Synchronises.
+static int thr_pass_scan(knnx_index* ix, const ThrPass& P, int nq, const float* thr_h, unsigned cap, std::vector<unsigned>& counts) {
+  hipStream_t st = ix->stream;
+  ThrState& T = P.thr(ix);
+  HIPCHK(T.alloc());
+  HIPCHK(hipMemcpyAsync(T.tthr, thr_h, (size_t)nq * sizeof(float), hipMemcpyHostToDevice, st));
+  HIPCHK(ix->prof.begin(ix->prof.on, st));
+  int r = P.launch_threshold(ix, nq, cap, st);
+  if (r) return r;
+  HIPCHK(ix->prof.end(ix->prof.on, st));
+  counts.assign((size_t)nq, 0u);
+  HIPCHK(hipMemcpyAsync(counts.data(), T.tcnt, (size_t)nq * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  ++T.scans;
+  return 0;
+}
+
+// range scan of <= P.pass_max queries of a compressed index: the rows of the probed lists whose score is > thr.  Counts and hits as
+// range_scan leaves them, the device counters in the family's tcnt.
+static int range_scan_thr(knnx_index* ix, const ThrPass& P, const float* q_host, int nq, float thr, std::vector<unsigned>& counts,
+                          unsigned* cap_out) {
+  int r = thr_pass_begin(ix, P, q_host, nq);
   if (r) return r;
   const std::vector<float> th((size_t)nq, thr);
   for (;;) {
-    if (ix->range.pool == 0 && (r = range_pool_alloc(ix, (size_t)1 << 21))) return r;
-    const unsigned cap = (unsigned)std::min<size_t>(ix->range.pool / (size_t)nq, 0xffffffffu);
-    if ((r = pq_pass_threshold_scan(ix, nq, np, th.data(), cap, counts, ix->stream))) return r;
+    unsigned cap = 0;
+    if ((r = range_pool_slice(ix, (size_t)nq, &cap))) return r;
+    if ((r = thr_pass_scan(ix, P, nq, th.data(), cap, counts))) return r;
     unsigned mx = 0;
     for (int i = 0; i < nq; ++i) mx = std::max(mx, counts[i]);
     if (mx <= cap) {
       *cap_out = cap;
       return 0;
     }
-    // overflow: regrow and rescan over the same front half (the counts are exact even when the slices overflowed)
-    size_t want = ix->range.pool;
-    while (want / (size_t)nq < (size_t)mx) want <<= 1;
-    if (want > RANGE_POOL_MAX) return fail(KNNX_E_NOMEM, "range_search result exceeds the 512 Mi-hit scratch limit");
-    if ((r = range_pool_alloc(ix, want))) return r;
+    if ((r = range_pool_fit(ix, (size_t)nq, mx, "range_search"))) return r;  // (the rescan runs over the same front half)
   }
 }
 
-// ---- IVF-SQ8 with the threshold-scan switch on (knnx_ivfsq_set_threshold_scan): the list scan in threshold mode feeds the same pools ----
-// stage a group of <= sq_pass_max queries and run the front half of their pass (knnx_ivfsq.hip: sq_front)
-static int sq_pass_begin(knnx_index* ix, const float* q_host, int nq) {
-  hipStream_t st = ix->stream;
-  int r = ensure_pin(ix, (size_t)sq_pass_max(ix) * ix->d * sizeof(float));
-  if (r) return r;
-  if (scratch_acquire(ix, st)) return KNNX_E_HIP;
-  memcpy(ix->pin.p, q_host, (size_t)nq * ix->d * sizeof(float));
-  HIPCHK(hipMemcpyAsync(ix->flat.q_dev, ix->pin.p, (size_t)nq * ix->d * sizeof(float), hipMemcpyHostToDevice, st));
-  return sq_front(ix, ix->flat.q_dev, nq, st);
-}
+// the pass table of a compressed index, null for a flat or IVF-Flat one
+static const ThrPass* thr_pass_of(const knnx_index* ix) { return ix->pq.m ? &pq_thr_pass() : ix->sq.on ? &sq_thr_pass() : nullptr; }
 
-// range scan of <= sq_pass_max queries of an IVF-SQ8 index: the rows of the probed lists whose score is > thr.  Counts and hits as
-// range_scan leaves them, the device counters in ix->sqs.tcnt.
-static int range_scan_sq(knnx_index* ix, const float* q_host, int nq, float thr, std::vector<unsigned>& counts, unsigned* cap_out) {
-  int r = sq_pass_begin(ix, q_host, nq);
-  if (r) return r;
-  const std::vector<float> th((size_t)nq, thr);
-  for (;;) {
-    if (ix->range.pool == 0 && (r = range_pool_alloc(ix, (size_t)1 << 21))) return r;
-    const unsigned cap = (unsigned)std::min<size_t>(ix->range.pool / (size_t)nq, 0xffffffffu);
-    if ((r = sq_pass_threshold_scan(ix, nq, th.data(), cap, counts, ix->stream))) return r;
-    unsigned mx = 0;
-    for (int i = 0; i < nq; ++i) mx = std::max(mx, counts[i]);
-    if (mx <= cap) {
-      *cap_out = cap;
-      return 0;
-    }
-    // overflow: regrow and rescan over the same front half (the counts are exact even when the slices overflowed)
-    size_t want = ix->range.pool;
-    while (want / (size_t)nq < (size_t)mx) want <<= 1;
-    if (want > RANGE_POOL_MAX) return fail(KNNX_E_NOMEM, "range_search result exceeds the 512 Mi-hit scratch limit");
-    if ((r = range_pool_alloc(ix, want))) return r;
-  }
+// the range scan of one step of knnx_range_search[_once]: <= range_step(ix) queries
+static int range_step(const knnx_index* ix, const ThrPass* P) { return P ? P->pass_max(ix) : KNN_NQ; }
+static int range_scan_any(knnx_index* ix, const ThrPass* P, const float* q_host, int nq, float thr, std::vector<unsigned>& counts,
+                          unsigned* cap_out) {
+  return P ? range_scan_thr(ix, *P, q_host, nq, thr, counts, cap_out) : range_scan(ix, q_host, nq, thr, counts, cap_out);
 }
 
 // what an IVF-PQ or IVF-SQ8 index answers to a range_search it does not serve (0: it serves it, or is neither).  Caller holds ix->mu.
 static int pq_range_refusal(const knnx_index* ix) {
-  if (ix->sq.on) return ix->sq.threshold_scan ? 0 : fail(KNNX_E_UNSUPPORTED, "range_search is not supported on an IVF-SQ8 index");
+  if (ix->sq.on) return ix->sq.thr.on ? 0 : fail(KNNX_E_UNSUPPORTED, "range_search is not supported on an IVF-SQ8 index");
   if (!ix->pq.m) return 0;
-  if (!ix->pq.threshold_scan) return fail(KNNX_E_UNSUPPORTED, "range_search is not supported on an IVF-PQ index");
+  if (!ix->pq.thr.on) return fail(KNNX_E_UNSUPPORTED, "range_search is not supported on an IVF-PQ index");
   if (ix->pq.refine)
     return fail(KNNX_E_UNSUPPORTED, "range_search is not supported on an IVF-PQ index with a refine store (it would need the exact score of every probed row)");
   return 0;
@@ -273,8 +269,8 @@ extern "C" int knnx_range_search(knnx_index* ix, const float* q, int n, float th
   if (pq_range_refusal(ix)) return KNNX_E_UNSUPPORTED;
   if (set_dev(ix)) return KNNX_E_HIP;
   const bool fill = D != nullptr;
-  const bool pq = ix->pq.m != 0, sq = ix->sq.on;
-  const int step = pq ? PQ_PASS : sq ? sq_pass_max(ix) : KNN_NQ;
+  const ThrPass* P = thr_pass_of(ix);
+  const int step = range_step(ix, P);
   int64_t run = 0;
   std::vector<unsigned> counts;
   if (!fill) lims[0] = 0;
@@ -282,7 +278,7 @@ extern "C" int knnx_range_search(knnx_index* ix, const float* q, int n, float th
     const int nq = std::min(step, n - o);
     unsigned cap = 0;
     const float* qo = q + (size_t)o * ix->d;
-    int r = pq ? range_scan_pq(ix, qo, nq, thresh, counts, &cap) : sq ? range_scan_sq(ix, qo, nq, thresh, counts, &cap) : range_scan(ix, qo, nq, thresh, counts, &cap);
+    int r = range_scan_any(ix, P, qo, nq, thresh, counts, &cap);
     if (r) return r;
     if (!fill) {
       for (int i = 0; i < nq; ++i) {
@@ -295,7 +291,7 @@ extern "C" int knnx_range_search(knnx_index* ix, const float* q, int n, float th
     for (int i = 0; i < nq; ++i)
       if (lims[o + i + 1] - lims[o + i] != (int64_t)counts[i])
         return fail(KNNX_E_STATE, "lims do not match this query/threshold (index changed between the two calls?)");
-    r = range_fetch(ix, nq, counts, cap, D + lims[o], I + lims[o], pq ? ix->pqs.tcnt.p : sq ? ix->sqs.tcnt.p : nullptr);
+    r = range_fetch(ix, nq, counts, cap, D + lims[o], I + lims[o], P ? P->thr(ix).tcnt.p : nullptr);
     if (r) return r;
   }
   return KNNX_OK;
@@ -311,8 +307,8 @@ extern "C" int knnx_range_search_once(knnx_index* ix, const float* q, int n, flo
   std::lock_guard<std::mutex> lk(ix->mu);
   if (pq_range_refusal(ix)) return KNNX_E_UNSUPPORTED;
   if (set_dev(ix)) return KNNX_E_HIP;
-  const bool pq = ix->pq.m != 0, sq = ix->sq.on;
-  const int step = pq ? PQ_PASS : sq ? sq_pass_max(ix) : KNN_NQ;
+  const ThrPass* P = thr_pass_of(ix);
+  const int step = range_step(ix, P);
   int64_t run = 0;
   bool fits = true;
   std::vector<unsigned> counts;
@@ -334,7 +330,7 @@ extern "C" int knnx_range_search_once(knnx_index* ix, const float* q, int n, flo
     const int nq = std::min(step, n - o);
     unsigned cap = 0;
     const float* qo = q + (size_t)o * ix->d;
-    int r = pq ? range_scan_pq(ix, qo, nq, thresh, counts, &cap) : sq ? range_scan_sq(ix, qo, nq, thresh, counts, &cap) : range_scan(ix, qo, nq, thresh, counts, &cap);
+    int r = range_scan_any(ix, P, qo, nq, thresh, counts, &cap);
     if (r) return r;
     const int64_t first = run;
     for (int i = 0; i < nq; ++i) {
@@ -343,7 +339,7 @@ extern "C" int knnx_range_search_once(knnx_index* ix, const float* q, int n, flo
     }
     if (run > capacity) fits = false;
     if (fits) {
-      r = range_fetch(ix, nq, counts, cap, D + first, I + first, pq ? ix->pqs.tcnt.p : sq ? ix->sqs.tcnt.p : nullptr);
+      r = range_fetch(ix, nq, counts, cap, D + first, I + first, P ? P->thr(ix).tcnt.p : nullptr);
       if (r) return r;
     }
   }
@@ -408,7 +404,7 @@ int search_large_k_locked(knnx_index* ix, const float* q, int n, int k, float* D
     const float* qq = q + (size_t)qi * ix->d;
     float* Dq = D + (size_t)qi * k;
     int64_t* Iq = I + (size_t)qi * k;
-    std::vector<std::pair<float, int64_t>> hits;
+    std::vector<Hit> hits;
     std::vector<unsigned> counts;
     unsigned cap = 0;
     int r;
@@ -492,253 +488,125 @@ int search_large_k_locked(knnx_index* ix, const float* q, int n, int k, float* D
         }
       }
     }
-    // rank the hits: score descending, ties by ascending id.  Only the first k are reported, so only they are sorted (a range
-    // scan hands back 1.5 .. 16 x k hits: O(hits) selection + k log k, 10 ms at k = 100 000 instead of a full sort)
-    auto better = [](const std::pair<float, int64_t>& a, const std::pair<float, int64_t>& b) {
-      return a.first > b.first || (a.first == b.first && a.second < b.second);
-    };
-    if ((int64_t)hits.size() > (int64_t)k) {
-      std::nth_element(hits.begin(), hits.begin() + k, hits.end(), better);
-      hits.resize((size_t)k);
-    }
-    std::sort(hits.begin(), hits.end(), better);
-    for (int j = 0; j < k; ++j) {
-      if (j < (int)hits.size()) {
-        Dq[j] = hits[j].first;
-        Iq[j] = hits[j].second;
-      } else {
-        Dq[j] = -FLT_MAX;
-        Iq[j] = -1;
-      }
-    }
+    rank_hits(hits, k);  // score descending, ties by ascending id; only the first k are reported
+    write_topk(hits, k, Dq, Iq);
   }
   return KNNX_OK;
 }
 
-// k > 64 on an IVF-PQ index with the threshold-scan switch on.  A group of queries (up to PQ_PASS; fewer when group x 16 kc hits would
-// not fit the pools) runs the front half of the pass ONCE; the k = 64 ADC pass gives every query its 32nd and 64th score; then all
-// queries descend together (knnx_descent.h), one threshold scan and one synchronisation per step for the whole group, a finished
-// query riding along with thr = +INFINITY.  A query whose probed lists hold <= 2 kc rows takes them all in the first scan.  The hits
-// (score, id) are ranked on the host: (ADC score descending, id ascending), the first kc = k (k x k_factor with a refine store) kept;
-// with a refine store these candidates are re-scored from the stored rows (pq_rescore_kernel) and ranked again by (exact score
-// descending, id ascending).  Caller holds ix->mu.
-int search_large_k_pq_locked(knnx_index* ix, const float* q, int n, int k, float* D, int64_t* I) {
-  typedef std::pair<float, int64_t> Hit;
+// with a refine store: the kc candidates of every query of the group, re-scored against the ORIGINAL query (still in flat.q_dev, a
+// few queries per launch: pq_rescore_kernel), ranked again by (exact score descending, id ascending) and written to rows o .. of D / I
+static int pq_refine_group(knnx_index* ix, ThrGroup& g, int o, int k, float* D, int64_t* I) {
+  hipStream_t st = ix->stream;
+  const int gq = g.gq;
+  const int64_t kc = g.kc;
+  const int qc = (int)std::max<int64_t>(1, std::min<int64_t>(gq, ((int64_t)1 << 22) / kc));
+  int64_t* cand_dev = nullptr;
+  float* es_dev = nullptr;
+  int r;
+  if ((r = ensure_scratch(ix, 3, (size_t)qc * kc * sizeof(int64_t), (void**)&cand_dev))) return r;
+  if ((r = ensure_scratch(ix, 4, (size_t)qc * kc * sizeof(float), (void**)&es_dev))) return r;
+  std::vector<int64_t> cand;
+  std::vector<float> es;
+  for (int c0 = 0; c0 < gq; c0 += qc) {
+    const int m = std::min(qc, gq - c0);
+    cand.assign((size_t)m * kc, -1);
+    for (int i = 0; i < m; ++i)
+      for (size_t j = 0; j < g.hits[c0 + i].size(); ++j) cand[(size_t)i * kc + j] = g.hits[c0 + i][j].second;
+    es.resize((size_t)m * kc);
+    HIPCHK(hipMemcpyAsync(cand_dev, cand.data(), cand.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    HIPCHK(launch_pq_rescore(ix->rows, ix->d, ix->flat.q_dev + (size_t)c0 * ix->d, m, ix->id_base, ix->ntotal, ix->ivf.inv, cand_dev, (int)kc,
+                             es_dev, st));
+    HIPCHK(hipMemcpyAsync(es.data(), es_dev, es.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int i = 0; i < m; ++i) {
+      std::vector<Hit>& h = g.hits[c0 + i];
+      for (size_t j = 0; j < h.size(); ++j) h[j].first = es[(size_t)i * kc + j];
+      rank_hits(h, k);
+      write_topk(h, k, D + (size_t)(o + c0 + i) * k, I + (size_t)(o + c0 + i) * k);
+    }
+  }
+  return 0;
+}
+
+// k > 64 on an IVF-PQ or IVF-SQ8 index with the threshold-scan switch on (P: the family's pass table).  A group of queries (up to
+// P.pass_max; fewer when group x 16 kc hits would not fit the pools) runs the front half of the pass ONCE; the k = 64 pass over it gives
+// every query its 32nd and 64th score; then all queries descend together (knnx_thr_group.h drives knnx_descent.h), one threshold scan
+// and one synchronisation per step for the whole group, a finished query riding along with thr = +INFINITY.  A query whose probed
+// lists hold <= 2 kc rows takes them all in the first scan.  The hits (score, id) are ranked on the host: (score descending, id
+// ascending), the first kc = k kept.  IVF-PQ with a refine store keeps kc = k x k_factor and re-scores them (pq_refine_group).
+// Caller holds ix->mu.
+int search_large_k_thr_locked(knnx_index* ix, const ThrPass& P, const float* q, int n, int k, float* D, int64_t* I) {
   const bool refine = ix->pq.refine;
   const int64_t kc = refine ? (int64_t)k * ix->pq.k_factor : (int64_t)k;
   if (kc > KNNX_MAX_K)
     return fail(KNNX_E_ARG, "k x k_factor = " + std::to_string(k) + " x " + std::to_string(ix->pq.k_factor) + " exceeds " +
                                 std::to_string(KNNX_MAX_K) + " candidates per query");
   hipStream_t st = ix->stream;
+  ThrState& T = P.thr(ix);
   const int K64 = KNNX_MAX_K_FAST;
-  const int gmax = (int)std::max<size_t>(1, std::min<size_t>((size_t)PQ_PASS, RANGE_POOL_MAX / ((size_t)16 * (size_t)kc)));
-  auto better = [](const Hit& a, const Hit& b) { return a.first > b.first || (a.first == b.first && a.second < b.second); };
-  std::vector<float> d64, thr, hd, es;
-  std::vector<int64_t> total, hi, cand;
-  std::vector<unsigned> counts, sel;
+  const int gmax = (int)std::max<size_t>(1, std::min<size_t>((size_t)P.pass_max(ix), RANGE_POOL_MAX / ((size_t)16 * (size_t)kc)));
+  std::vector<float> d64, thr, hd;
+  std::vector<int64_t> total, hi;
+  std::vector<unsigned> counts;
+  ThrGroup g;
   for (int o = 0; o < n;) {
     const int gq = std::min(gmax, n - o);
-    int np = 0;
-    int r = pq_pass_begin(ix, q + (size_t)o * ix->d, gq, &np);
+    int r = thr_pass_begin(ix, P, q + (size_t)o * ix->d, gq);
     if (r) return r;
     d64.resize((size_t)gq * K64);
-    if ((r = pq_pass_top64(ix, gq, np, d64.data(), st))) return r;
-    if ((r = pq_pass_probed_rows(ix, gq, np, total, st))) return r;
-    std::vector<PqDescent> ds((size_t)gq);
-    std::vector<int> state((size_t)gq, 0);  // 0: descending, 1: its threshold is final, the hits did not fit yet, 2: fetched
-    std::vector<std::vector<Hit>> hits((size_t)gq);
-    for (int i = 0; i < gq; ++i) ds[i].start(d64[(size_t)i * K64 + K64 / 2 - 1], d64[(size_t)i * K64 + K64 - 1], kc, total[i]);
+    if ((r = P.top64(ix, gq, d64.data(), st))) return r;
+    if ((r = P.probed_rows(ix, gq, total, st))) return r;
+    g.start(gq, kc, d64.data(), K64, total.data());
     thr.assign((size_t)gq, 0.f);
-    for (int left = gq; left > 0;) {
-      if (ix->range.pool == 0 && (r = range_pool_alloc(ix, (size_t)1 << 21))) return r;
-      const unsigned cap = (unsigned)std::min<size_t>(ix->range.pool / (size_t)gq, 0xffffffffu);
-      for (int i = 0; i < gq; ++i) thr[i] = state[i] == 2 ? INFINITY : ds[i].thr;
-      if ((r = pq_pass_threshold_scan(ix, gq, np, thr.data(), cap, counts, st))) return r;
-      sel.assign((size_t)gq, 0u);
-      unsigned grow = 0;
-      int64_t nsel = 0;
-      for (int i = 0; i < gq; ++i) {
-        if (state[i] == 2) continue;
-        ++ix->pq.thr_query_scans;
-        if (state[i] == 0) {
-          if (ds[i].next((int64_t)counts[i]) == PqDescent::SCAN) continue;
-          state[i] = 1;
-        }
-        if (counts[i] <= cap) {
-          sel[i] = counts[i];
-          nsel += counts[i];
-        } else {
-          grow = std::max(grow, counts[i]);
-        }
+    while (g.left > 0) {
+      unsigned cap = 0;
+      if ((r = range_pool_slice(ix, (size_t)gq, &cap))) return r;
+      g.thresholds(thr.data());
+      if ((r = thr_pass_scan(ix, P, gq, thr.data(), cap, counts))) return r;
+      const ThrGroup::Step s = g.absorb(counts.data(), cap);
+      T.query_scans += s.query_scans;
+      if (s.nsel > 0) {
+        HIPCHK(hipMemcpyAsync(T.tfetch, g.sel.data(), (size_t)gq * sizeof(unsigned), hipMemcpyHostToDevice, st));
+        hd.resize((size_t)s.nsel);
+        hi.resize((size_t)s.nsel);
+        if ((r = range_fetch(ix, gq, g.sel, cap, hd.data(), hi.data(), T.tfetch))) return r;
+        T.hits += s.nsel;
       }
-      if (nsel > 0) {
-        HIPCHK(hipMemcpyAsync(ix->pqs.tfetch, sel.data(), (size_t)gq * sizeof(unsigned), hipMemcpyHostToDevice, st));
-        hd.resize((size_t)nsel);
-        hi.resize((size_t)nsel);
-        if ((r = range_fetch(ix, gq, sel, cap, hd.data(), hi.data(), ix->pqs.tfetch))) return r;
-        ix->pq.thr_hits += nsel;
-      }
-      int64_t at = 0;
-      for (int i = 0; i < gq; ++i) {
-        if (state[i] != 1 || counts[i] > cap) continue;
-        std::vector<Hit>& h = hits[i];
-        h.resize((size_t)sel[i]);
-        for (unsigned j = 0; j < sel[i]; ++j) h[j] = Hit(hd[(size_t)at + j], hi[(size_t)at + j]);
-        at += sel[i];
-        if ((int64_t)h.size() > kc) {
-          std::nth_element(h.begin(), h.begin() + kc, h.end(), better);
-          h.resize((size_t)kc);
-        }
-        std::sort(h.begin(), h.end(), better);
-        state[i] = 2;
-        --left;
-      }
-      if (grow) {  // a final threshold whose hits overflowed its slice: regrow, scan it again
-        size_t want = ix->range.pool;
-        while (want / (size_t)gq < (size_t)grow) want <<= 1;
-        if (want > RANGE_POOL_MAX) return fail(KNNX_E_NOMEM, "large-k search result exceeds the 512 Mi-hit scratch limit");
-        if ((r = range_pool_alloc(ix, want))) return r;
-      }
+      g.take(hd.data(), hi.data());
+      // a final threshold whose hits overflowed its slice: regrow, scan it again
+      if (s.grow && (r = range_pool_fit(ix, (size_t)gq, s.grow, "large-k search"))) return r;
     }
-    ix->pq.thr_queries += gq;
-    if (!refine) {
-      for (int i = 0; i < gq; ++i) {
-        float* Dq = D + (size_t)(o + i) * k;
-        int64_t* Iq = I + (size_t)(o + i) * k;
-        const std::vector<Hit>& h = hits[i];
-        for (int j = 0; j < k; ++j) {
-          Dq[j] = j < (int)h.size() ? h[j].first : -FLT_MAX;
-          Iq[j] = j < (int)h.size() ? h[j].second : -1;
-        }
-      }
+    T.queries += gq;
+    if (refine) {
+      if ((r = pq_refine_group(ix, g, o, k, D, I))) return r;
     } else {
-      // the kc candidates of every query, re-scored against the ORIGINAL query (still in flat.q_dev), a few queries per launch
-      const int qc = (int)std::max<int64_t>(1, std::min<int64_t>(gq, ((int64_t)1 << 22) / kc));
-      int64_t* cand_dev = nullptr;
-      float* es_dev = nullptr;
-      if ((r = ensure_scratch(ix, 3, (size_t)qc * kc * sizeof(int64_t), (void**)&cand_dev))) return r;
-      if ((r = ensure_scratch(ix, 4, (size_t)qc * kc * sizeof(float), (void**)&es_dev))) return r;
-      for (int c0 = 0; c0 < gq; c0 += qc) {
-        const int m = std::min(qc, gq - c0);
-        cand.assign((size_t)m * kc, -1);
-        for (int i = 0; i < m; ++i)
-          for (size_t j = 0; j < hits[c0 + i].size(); ++j) cand[(size_t)i * kc + j] = hits[c0 + i][j].second;
-        es.resize((size_t)m * kc);
-        HIPCHK(hipMemcpyAsync(cand_dev, cand.data(), cand.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        HIPCHK(launch_pq_rescore(ix->rows, ix->d, ix->flat.q_dev + (size_t)c0 * ix->d, m, ix->id_base, ix->ntotal, ix->ivf.inv, cand_dev, (int)kc,
-                                 es_dev, st));
-        HIPCHK(hipMemcpyAsync(es.data(), es_dev, es.size() * sizeof(float), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (int i = 0; i < m; ++i) {
-          std::vector<Hit>& h = hits[c0 + i];
-          for (size_t j = 0; j < h.size(); ++j) h[j].first = es[(size_t)i * kc + j];
-          if ((int64_t)h.size() > (int64_t)k) {
-            std::nth_element(h.begin(), h.begin() + k, h.end(), better);
-            h.resize((size_t)k);
-          }
-          std::sort(h.begin(), h.end(), better);
-          float* Dq = D + (size_t)(o + c0 + i) * k;
-          int64_t* Iq = I + (size_t)(o + c0 + i) * k;
-          for (int j = 0; j < k; ++j) {
-            Dq[j] = j < (int)h.size() ? h[j].first : -FLT_MAX;
-            Iq[j] = j < (int)h.size() ? h[j].second : -1;
-          }
-        }
-      }
+      for (int i = 0; i < gq; ++i) write_topk(g.hits[i], k, D + (size_t)(o + i) * k, I + (size_t)(o + i) * k);
     }
     o += gq;
   }
   return KNNX_OK;
 }
 
-// k > 64 on an IVF-SQ8 index with the threshold-scan switch on: search_large_k_pq_locked without the refine branch.  A group of queries
-// (up to sq_pass_max; fewer when group x 16 k hits would not fit the pools) runs the front half of the pass ONCE; the k = 64 pass over it
-// gives every query its 32nd and 64th score; then all queries descend together (knnx_descent.h), one threshold launch and one
-// synchronisation per step for the whole group, a finished query riding along with thr = +INFINITY.  A query whose probed lists hold
-// <= 2 k rows takes them all in the first scan.  The hits are ranked on the host: (score descending, id ascending).  Caller holds ix->mu.
-int search_large_k_sq_locked(knnx_index* ix, const float* q, int n, int k, float* D, int64_t* I) {
-  typedef std::pair<float, int64_t> Hit;
-  hipStream_t st = ix->stream;
-  const int K64 = KNNX_MAX_K_FAST;
-  const int gmax = (int)std::max<size_t>(1, std::min<size_t>((size_t)sq_pass_max(ix), RANGE_POOL_MAX / ((size_t)16 * (size_t)k)));
-  auto better = [](const Hit& a, const Hit& b) { return a.first > b.first || (a.first == b.first && a.second < b.second); };
-  std::vector<float> d64, thr, hd;
-  std::vector<int64_t> total, hi;
-  std::vector<unsigned> counts, sel;
-  for (int o = 0; o < n;) {
-    const int gq = std::min(gmax, n - o);
-    int r = sq_pass_begin(ix, q + (size_t)o * ix->d, gq);
-    if (r) return r;
-    d64.resize((size_t)gq * K64);
-    if ((r = sq_pass_top64(ix, gq, d64.data(), st))) return r;
-    if ((r = sq_pass_probed_rows(ix, gq, total, st))) return r;
-    std::vector<PqDescent> ds((size_t)gq);
-    std::vector<int> state((size_t)gq, 0);  // 0: descending, 1: its threshold is final, the hits did not fit yet, 2: fetched
-    std::vector<std::vector<Hit>> hits((size_t)gq);
-    for (int i = 0; i < gq; ++i) ds[i].start(d64[(size_t)i * K64 + K64 / 2 - 1], d64[(size_t)i * K64 + K64 - 1], k, total[i]);
-    thr.assign((size_t)gq, 0.f);
-    for (int left = gq; left > 0;) {
-      if (ix->range.pool == 0 && (r = range_pool_alloc(ix, (size_t)1 << 21))) return r;
-      const unsigned cap = (unsigned)std::min<size_t>(ix->range.pool / (size_t)gq, 0xffffffffu);
-      for (int i = 0; i < gq; ++i) thr[i] = state[i] == 2 ? INFINITY : ds[i].thr;
-      if ((r = sq_pass_threshold_scan(ix, gq, thr.data(), cap, counts, st))) return r;
-      sel.assign((size_t)gq, 0u);
-      unsigned grow = 0;
-      int64_t nsel = 0;
-      for (int i = 0; i < gq; ++i) {
-        if (state[i] == 2) continue;
-        ++ix->sq.thr_query_scans;
-        if (state[i] == 0) {
-          if (ds[i].next((int64_t)counts[i]) == PqDescent::SCAN) continue;
-          state[i] = 1;
-        }
-        if (counts[i] <= cap) {
-          sel[i] = counts[i];
-          nsel += counts[i];
-        } else {
-          grow = std::max(grow, counts[i]);
-        }
-      }
-      if (nsel > 0) {
-        HIPCHK(hipMemcpyAsync(ix->sqs.tfetch, sel.data(), (size_t)gq * sizeof(unsigned), hipMemcpyHostToDevice, st));
-        hd.resize((size_t)nsel);
-        hi.resize((size_t)nsel);
-        if ((r = range_fetch(ix, gq, sel, cap, hd.data(), hi.data(), ix->sqs.tfetch))) return r;
-        ix->sq.thr_hits += nsel;
-      }
-      int64_t at = 0;
-      for (int i = 0; i < gq; ++i) {
-        if (state[i] != 1 || counts[i] > cap) continue;
-        std::vector<Hit>& h = hits[i];
-        h.resize((size_t)sel[i]);
-        for (unsigned j = 0; j < sel[i]; ++j) h[j] = Hit(hd[(size_t)at + j], hi[(size_t)at + j]);
-        at += sel[i];
-        if ((int64_t)h.size() > (int64_t)k) {
-          std::nth_element(h.begin(), h.begin() + k, h.end(), better);
-          h.resize((size_t)k);
-        }
-        std::sort(h.begin(), h.end(), better);
-        state[i] = 2;
-        --left;
-      }
-      if (grow) {  // a final threshold whose hits overflowed its slice: regrow, scan it again
-        size_t want = ix->range.pool;
-        while (want / (size_t)gq < (size_t)grow) want <<= 1;
-        if (want > RANGE_POOL_MAX) return fail(KNNX_E_NOMEM, "large-k search result exceeds the 512 Mi-hit scratch limit");
-        if ((r = range_pool_alloc(ix, want))) return r;
-      }
-    }
-    ix->sq.thr_queries += gq;
-    for (int i = 0; i < gq; ++i) {
-      float* Dq = D + (size_t)(o + i) * k;
-      int64_t* Iq = I + (size_t)(o + i) * k;
-      const std::vector<Hit>& h = hits[i];
-      for (int j = 0; j < k; ++j) {
-        Dq[j] = j < (int)h.size() ? h[j].first : -FLT_MAX;
-        Iq[j] = j < (int)h.size() ? h[j].second : -1;
-      }
-    }
-    o += gq;
-  }
+// ---- the switch and the counters behind knnx_ivf{pq,sq}_set_threshold_scan / _threshold_scan / _threshold_stats ----
+int thr_set_switch(knnx_index* ix, const ThrPass& P, int on) {
+  if (!ix) return fail(KNNX_E_ARG, "index is null");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  if (!P.is(ix)) return fail(KNNX_E_STATE, std::string("not an ") + P.family + " index");
+  P.thr(ix).on = on != 0;
+  return KNNX_OK;
+}
+
+int thr_switch(const knnx_index* ix, const ThrPass& P) { return ix && P.is(ix) && P.thr(const_cast<knnx_index*>(ix)).on ? 1 : 0; }
+
+int thr_stats(knnx_index* ix, const ThrPass& P, int64_t* queries, int64_t* launches, int64_t* query_scans, int64_t* hits) {
+  if (!ix) return fail(KNNX_E_ARG, "index is null");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  if (!P.is(ix)) return fail(KNNX_E_STATE, std::string("not an ") + P.family + " index");
+  const ThrState& T = P.thr(ix);
+  if (queries) *queries = T.queries;
+  if (launches) *launches = T.scans;
+  if (query_scans) *query_scans = T.query_scans;
+  if (hits) *hits = T.hits;
   return KNNX_OK;
 }

@@ -45,6 +45,34 @@ def _map_ids_call(lib, fn, handle, ids):
     return out
 
 
+def _threshold_scan_property(family, handles, doc):
+    """The property {pq,sq}_threshold_scan of an index class over knnx_{family}_threshold_scan / knnx_{family}_set_threshold_scan.
+    handles(self) iterates over the native handles: the first is read, all are set."""
+    def get(self):
+        h = next(handles(self), None)
+        return bool(getattr(self._lib, f"knnx_{family}_threshold_scan")(h)) if h else False  # pylint: disable=protected-access
+
+    def put(self, on):
+        for h in handles(self):
+            check(self._lib, getattr(self._lib, f"knnx_{family}_set_threshold_scan")(h, 1 if on else 0), "knnx")  # pylint: disable=protected-access
+
+    return property(get, put, doc=doc)
+
+
+def _threshold_stats(index, family):
+    v = [C.c_int64(0) for _ in range(4)]
+    check(index._lib, getattr(index._lib, f"knnx_{family}_threshold_stats")(index._h, *[C.byref(x) for x in v]), "knnx")  # pylint: disable=protected-access
+    return tuple(int(x.value) for x in v)
+
+
+def _own_handle(index):
+    return iter((index._h,))  # pylint: disable=protected-access
+
+
+def _shard_handles(index):
+    return (C.c_void_p(index._lib.knnx_shards_get(index._h, g)) for g in range(index.nshards))  # pylint: disable=protected-access
+
+
 class _FaissShaped:
     """The part of the faiss Index surface clip_back / clip_filter exercise, on top of `_search_raw`,
     `reconstruct_batch`, `range_search` and `ntotal` of the concrete index (one GPU or row-sharded)."""
@@ -309,23 +337,14 @@ class Mi355xIndex(_FaissShaped):
     def k_factor(self, v):
         check(self._lib, self._lib.knnx_ivfpq_set_k_factor(self._h, int(v)), "knnx")
 
-    @property
-    def pq_threshold_scan(self):
-        """The threshold mode of the ADC scan (include/knnx.h: knnx_ivfpq_set_threshold_scan): with it on, an IVF-PQ index serves
-        k > 64 (up to 131 072) and range_search; off -- the default -- it refuses both as it always has.  False on an index that is
-        not IVF-PQ; setting it there is an error."""
-        return bool(self._lib.knnx_ivfpq_threshold_scan(self._h)) if self._h else False
-
-    @pq_threshold_scan.setter
-    def pq_threshold_scan(self, on):
-        check(self._lib, self._lib.knnx_ivfpq_set_threshold_scan(self._h, 1 if on else 0), "knnx")
+    pq_threshold_scan = _threshold_scan_property("ivfpq", _own_handle, """The threshold mode of the ADC scan (include/knnx.h:
+        knnx_ivfpq_set_threshold_scan): with it on, an IVF-PQ index serves k > 64 (up to 131 072) and range_search; off -- the
+        default -- it refuses both as it always has.  False on an index that is not IVF-PQ; setting it there is an error.""")
 
     def pq_threshold_stats(self):
         """(queries served with k > 64, threshold-scan launches, scans summed over the queries that took part, hits fetched) since the
         index was created (include/knnx.h: knnx_ivfpq_threshold_stats)."""
-        v = [C.c_int64(0) for _ in range(4)]
-        check(self._lib, self._lib.knnx_ivfpq_threshold_stats(self._h, *[C.byref(x) for x in v]), "knnx")
-        return tuple(int(x.value) for x in v)
+        return _threshold_stats(self, "ivfpq")
 
     def pq_arena_bytes(self):
         """(bytes of the code arena, bytes of the row arena -- 0 without a refine store) of an IVF-PQ index."""
@@ -377,23 +396,14 @@ class Mi355xIndex(_FaissShaped):
         order = np.argsort(ids, kind="stable")
         return np.ascontiguousarray(codes[order][:, : self.d]), np.ascontiguousarray(lists[order])
 
-    @property
-    def sq_threshold_scan(self):
-        """The threshold mode of the code scan (include/knnx.h: knnx_ivfsq_set_threshold_scan): with it on, an IVF-SQ8 index serves
-        k > 64 (up to 131 072) and range_search; off -- the default -- it refuses both as it always has.  False on an index that is
-        not IVF-SQ8; setting it there is an error."""
-        return bool(self._lib.knnx_ivfsq_threshold_scan(self._h)) if self._h else False
-
-    @sq_threshold_scan.setter
-    def sq_threshold_scan(self, on):
-        check(self._lib, self._lib.knnx_ivfsq_set_threshold_scan(self._h, 1 if on else 0), "knnx")
+    sq_threshold_scan = _threshold_scan_property("ivfsq", _own_handle, """The threshold mode of the code scan (include/knnx.h:
+        knnx_ivfsq_set_threshold_scan): with it on, an IVF-SQ8 index serves k > 64 (up to 131 072) and range_search; off -- the
+        default -- it refuses both as it always has.  False on an index that is not IVF-SQ8; setting it there is an error.""")
 
     def sq_threshold_stats(self):
         """(queries served with k > 64, threshold-scan launches, launches summed over the queries that took part, hits fetched) since
         the index was created (include/knnx.h: knnx_ivfsq_threshold_stats)."""
-        v = [C.c_int64(0) for _ in range(4)]
-        check(self._lib, self._lib.knnx_ivfsq_threshold_stats(self._h, *[C.byref(x) for x in v]), "knnx")
-        return tuple(int(x.value) for x in v)
+        return _threshold_stats(self, "ivfsq")
 
     # ------------------------------------------------------------------ list-ordered ids (reorder_metadata_by_ivf_index)
     def ivf_old_to_new(self):
@@ -605,25 +615,10 @@ class ShardedMi355xIndex(_FaissShaped):
         for g in range(self.nshards):
             check(self._lib, self._lib.knnx_ivfpq_set_k_factor(C.c_void_p(self._lib.knnx_shards_get(self._h, g)), int(v)), "knnx")
 
-    @property
-    def pq_threshold_scan(self):
-        """The threshold-scan switch as carried by the first shard (Mi355xIndex.pq_threshold_scan); the setter sets every shard."""
-        return bool(self._lib.knnx_ivfpq_threshold_scan(C.c_void_p(self._lib.knnx_shards_get(self._h, 0)))) if self.nshards else False
-
-    @pq_threshold_scan.setter
-    def pq_threshold_scan(self, on):
-        for g in range(self.nshards):
-            check(self._lib, self._lib.knnx_ivfpq_set_threshold_scan(C.c_void_p(self._lib.knnx_shards_get(self._h, g)), 1 if on else 0), "knnx")
-
-    @property
-    def sq_threshold_scan(self):
-        """The IVF-SQ8 threshold-scan switch as carried by the first shard (Mi355xIndex.sq_threshold_scan); the setter sets every shard."""
-        return bool(self._lib.knnx_ivfsq_threshold_scan(C.c_void_p(self._lib.knnx_shards_get(self._h, 0)))) if self.nshards else False
-
-    @sq_threshold_scan.setter
-    def sq_threshold_scan(self, on):
-        for g in range(self.nshards):
-            check(self._lib, self._lib.knnx_ivfsq_set_threshold_scan(C.c_void_p(self._lib.knnx_shards_get(self._h, g)), 1 if on else 0), "knnx")
+    pq_threshold_scan = _threshold_scan_property("ivfpq", _shard_handles, """The threshold-scan switch as carried by the first shard
+        (Mi355xIndex.pq_threshold_scan); the setter sets every shard.""")
+    sq_threshold_scan = _threshold_scan_property("ivfsq", _shard_handles, """The IVF-SQ8 threshold-scan switch as carried by the first
+        shard (Mi355xIndex.sq_threshold_scan); the setter sets every shard.""")
 
     @property
     def nshards(self):
@@ -1073,6 +1068,102 @@ def _positions_in_lists(lists, cursor):
     return pos.astype(np.int32)
 
 
+def _list_sizes(lists, nlist):
+    sizes = np.bincount(lists, minlength=nlist).astype(np.int64)
+    if sizes.shape[0] != nlist:
+        raise ValueError("a list id is outside [0, nlist)")
+    return sizes
+
+
+def _ivf_begin(index, nlist, centroids, sizes):
+    """knnx_ivf_begin on an index whose quantiser, if it has one, is set -> the padded centroids it was given."""
+    cpad = np.ascontiguousarray(index._pad(np.asarray(centroids, dtype=np.float16)))  # pylint: disable=protected-access
+    check(index._lib, index._lib.knnx_ivf_begin(index._h, nlist, cpad.ctypes.data, np.ascontiguousarray(sizes, dtype=np.int64).ctypes.data), "knnx")  # pylint: disable=protected-access
+    return index
+
+
+def _add_assigned_chunks(index, chunks, lists, nlist, id_base):
+    """Rows (an iterator of (offset, fp16 rows)) into an index between knnx_ivf_begin and knnx_ivf_end: row offset + j gets id
+    id_base + offset + j and the next free slot of list lists[offset + j] (an IVF-PQ / IVF-SQ8 index encodes it there)."""
+    lib = index._lib  # pylint: disable=protected-access
+    cursor = np.zeros(nlist, dtype=np.int64)
+    for o, x in chunks:
+        rows = np.ascontiguousarray(index._pad(np.asarray(x, dtype=np.float16)))  # pylint: disable=protected-access
+        ls = np.ascontiguousarray(lists[o:o + rows.shape[0]], dtype=np.int32)
+        pos = _positions_in_lists(ls, cursor)
+        ids = np.arange(o, o + rows.shape[0], dtype=np.int64) + id_base
+        check(lib, lib.knnx_ivf_add_assigned(index._h, rows.ctypes.data, rows.shape[0], ids.ctypes.data, ls.ctypes.data, pos.ctypes.data), "knnx")  # pylint: disable=protected-access
+
+
+def _add_code_chunks(index, add_codes, codes, lists, lo, nlist, chunk, prepare=lambda c: c):
+    """Saved codes (u8 [n, width], ids lo + row number) into an index between knnx_ivf_begin and knnx_ivf_end through the library's
+    add_codes (knnx_ivfpq_add_codes / knnx_ivfsq_add_codes), `chunk` rows at a time."""
+    lib = index._lib  # pylint: disable=protected-access
+    cursor = np.zeros(nlist, dtype=np.int64)
+    for o in range(0, codes.shape[0], chunk):
+        c = np.ascontiguousarray(prepare(np.asarray(codes[o:o + chunk], dtype=np.uint8)))
+        ls = np.ascontiguousarray(lists[o:o + chunk], dtype=np.int32)
+        pos = _positions_in_lists(ls, cursor)
+        ids = np.arange(lo + o, lo + o + c.shape[0], dtype=np.int64)
+        check(lib, add_codes(index._h, c.ctypes.data, c.shape[0], ids.ctypes.data, ls.ctypes.data, pos.ctypes.data), "knnx")  # pylint: disable=protected-access
+
+
+def _ivf_end(index, nlist, nprobe, centroids, id_base, n, lists=None):
+    """knnx_ivf_end, then what every built IVF index carries: nprobe, its centroids and row range, the lists where they are known."""
+    check(index._lib, index._lib.knnx_ivf_end(index._h), "knnx")  # pylint: disable=protected-access
+    index.nprobe = min(int(nprobe), nlist)
+    index.ivf_centroids, index.ivf_row_range = np.asarray(centroids, dtype=np.float16), (int(id_base), int(id_base) + int(n))
+    if lists is not None:
+        index.ivf_lists = lists
+    return index
+
+
+def _encode_chunks(begin, chunks, n, nlist, centroids, lists, nprobe, id_base):
+    """Rows (an iterator of (offset, fp16 rows)) -> a compressed IVF index: begin(list sizes) makes the index and opens the build."""
+    index = begin(_list_sizes(lists, nlist))
+    _add_assigned_chunks(index, chunks, lists, nlist, id_base)
+    return _ivf_end(index, nlist, nprobe, centroids, id_base, n, lists)
+
+
+def _split_saved_rows(make, codes, lists, saved_range, nprobe, device, row_range, devices):
+    """What load_index does with the saved rows [slo, shi) of a compressed index: all of them or `row_range` on one device, or an
+    even split over `devices`.  make(codes, lists, first id, device) builds one index."""
+    slo, shi = saved_range
+    if devices is not None:
+        if row_range is not None:
+            raise ValueError("row_range and devices are mutually exclusive")
+        G = len(devices)
+        cuts = [slo + (shi - slo) * g // G for g in range(G + 1)]
+        shards = [make(codes[cuts[g] - slo:cuts[g + 1] - slo], np.asarray(lists[cuts[g] - slo:cuts[g + 1] - slo]), cuts[g], devices[g])
+                  for g in range(G)]
+        sharded = ShardedMi355xIndex.from_shards(shards, cuts[:-1])
+        sharded.nprobe = nprobe
+        return sharded
+    lo, hi = (slo, shi) if row_range is None else (int(row_range[0]), int(row_range[1]))
+    if not slo <= lo <= hi <= shi:
+        raise ValueError(f"row_range {row_range} is outside the saved shard's rows [{slo}, {shi})")
+    return make(codes[lo - slo:hi - slo], np.asarray(lists[lo - slo:hi - slo]), lo, device)
+
+
+def threshold_scan_entry(on):
+    """What a saved IVF-PQ or IVF-SQ8 manifest says about the threshold-scan switch: {"threshold_scan": true} when it is on, nothing
+    otherwise."""
+    return {"threshold_scan": True} if on else {}
+
+
+def read_threshold_scan(folder, man):
+    """The threshold-scan switch of a saved IVF-PQ or IVF-SQ8 manifest: False for a manifest without the key (every folder written
+    before the switch existed, and every index saved with it off), else the boolean it carries; anything but a boolean is refused."""
+    v = man.get("threshold_scan", False)
+    if not isinstance(v, bool):
+        raise ValueError(f"{folder}: \"threshold_scan\" must be true or false, got {v!r}")
+    return v
+
+
+ivfpq_threshold_scan_entry = ivfsq_threshold_scan_entry = threshold_scan_entry
+read_ivfpq_threshold_scan = read_ivfsq_threshold_scan = read_threshold_scan
+
+
 def build_ivf_index(x_f16, nlist, nprobe=16, niter=8, seed=0, device=0, id_base=0, centroids=None, chunk=1 << 20):
     """fp16 rows [N, d] -> HBM-resident IVF-Flat index (ids = id_base + row number, like the flat index).  `x_f16` may be a
     numpy memmap: rows are streamed twice in chunks (assignment, then scatter into the list-sorted arena)."""
@@ -1086,23 +1177,10 @@ def build_ivf_index(x_f16, nlist, nprobe=16, niter=8, seed=0, device=0, id_base=
     for o in range(0, n, chunk):
         lists[o:o + chunk] = b.assign(x_f16[o:o + chunk])
     b.close()
-    sizes = np.bincount(lists, minlength=nlist).astype(np.int64)
-    index = Mi355xIndex(d, device=device, id_base=id_base)
-    lib = index._lib  # pylint: disable=protected-access
-    cpad = np.ascontiguousarray(index._pad(centroids))  # pylint: disable=protected-access
-    check(lib, lib.knnx_ivf_begin(index._h, nlist, cpad.ctypes.data, sizes.ctypes.data), "knnx")  # pylint: disable=protected-access
-    cursor = np.zeros(nlist, dtype=np.int64)
-    for o in range(0, n, chunk):
-        rows = np.ascontiguousarray(index._pad(np.asarray(x_f16[o:o + chunk], dtype=np.float16)))  # pylint: disable=protected-access
-        ls = np.ascontiguousarray(lists[o:o + chunk])
-        pos = _positions_in_lists(ls, cursor)
-        ids = np.arange(o, o + rows.shape[0], dtype=np.int64) + id_base
-        check(lib, lib.knnx_ivf_add_assigned(index._h, rows.ctypes.data, rows.shape[0], ids.ctypes.data, ls.ctypes.data, pos.ctypes.data), "knnx")  # pylint: disable=protected-access
-    check(lib, lib.knnx_ivf_end(index._h), "knnx")  # pylint: disable=protected-access
-    index.nprobe = min(nprobe, nlist)
-    index.ivf_lists = lists  # kept for tests / recall measurement, and for save_index(index, folder, embeddings_folder=...)
-    index.ivf_centroids, index.ivf_row_range = centroids, (int(id_base), int(id_base) + int(n))
-    return index
+    index = _ivf_begin(Mi355xIndex(d, device=device, id_base=id_base), nlist, centroids, np.bincount(lists, minlength=nlist))
+    _add_assigned_chunks(index, ((o, x_f16[o:o + chunk]) for o in range(0, n, chunk)), lists, nlist, id_base)
+    # (the lists are kept for tests / recall measurement, and for save_index(index, folder, embeddings_folder=...))
+    return _ivf_end(index, nlist, nprobe, centroids, id_base, n, lists)
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -1174,23 +1252,10 @@ def _scatter_into_ivf(src, lo, hi, centroids, lists, nprobe, device, chunk):
     """The second pass of an IVF build: rows [lo, hi) of `src` into a list-sorted arena on `device` (ids = global row numbers),
     given every row's list id.  Streams the rows once; no training, no assignment."""
     nlist, d = centroids.shape
-    sizes = np.bincount(lists, minlength=nlist).astype(np.int64)
-    if sizes.shape[0] != nlist:
-        raise ValueError("a list id is outside [0, nlist)")
-    index = Mi355xIndex(d, device=device, id_base=lo)
-    lib = index._lib  # pylint: disable=protected-access
-    cpad = np.ascontiguousarray(index._pad(np.asarray(centroids, dtype=np.float16)))  # pylint: disable=protected-access
-    check(lib, lib.knnx_ivf_begin(index._h, nlist, cpad.ctypes.data, sizes.ctypes.data), "knnx")  # pylint: disable=protected-access
-    cursor = np.zeros(nlist, dtype=np.int64)
-    for o, x in src.chunks(lo, hi, chunk):
-        rows = np.ascontiguousarray(index._pad(x))  # pylint: disable=protected-access
-        ls = np.ascontiguousarray(lists[o - lo:o - lo + rows.shape[0]], dtype=np.int32)
-        pos = _positions_in_lists(ls, cursor)
-        ids = np.arange(o, o + rows.shape[0], dtype=np.int64)
-        check(lib, lib.knnx_ivf_add_assigned(index._h, rows.ctypes.data, rows.shape[0], ids.ctypes.data, ls.ctypes.data, pos.ctypes.data), "knnx")  # pylint: disable=protected-access
-    check(lib, lib.knnx_ivf_end(index._h), "knnx")  # pylint: disable=protected-access
-    index.nprobe = min(int(nprobe), nlist)
-    index.ivf_lists, index.ivf_centroids, index.ivf_source, index.ivf_row_range = lists, np.asarray(centroids, dtype=np.float16), src, (int(lo), int(hi))
+    index = _ivf_begin(Mi355xIndex(d, device=device, id_base=lo), nlist, centroids, _list_sizes(lists, nlist))
+    _add_assigned_chunks(index, ((o - lo, x) for o, x in src.chunks(lo, hi, chunk)), lists, nlist, lo)
+    index = _ivf_end(index, nlist, nprobe, centroids, lo, hi - lo, lists)
+    index.ivf_source = src
     return index
 
 
@@ -1683,39 +1748,19 @@ def _ivfpq_begin(d, nlist, M, centroids, codebooks, sizes, device, id_base, rota
     index.k_factor = k_factor
     if threshold_scan:  # (off is the state of a new index: nothing is called for it)
         index.pq_threshold_scan = True
-    cpad = np.ascontiguousarray(index._pad(np.asarray(centroids, dtype=np.float16)))  # pylint: disable=protected-access
-    if dq != d and cpad.shape != (nlist, dq):
-        raise ValueError(f"centroids must be [{nlist}, {dq}] behind a rotation {rotation.shape}, got {cpad.shape}")
-    check(index._lib, index._lib.knnx_ivf_begin(index._h, nlist, cpad.ctypes.data, np.ascontiguousarray(sizes, dtype=np.int64).ctypes.data), "knnx")  # pylint: disable=protected-access
-    return index
-
-
-def _ivfpq_end(index, nlist, nprobe, centroids, id_base, n):
-    check(index._lib, index._lib.knnx_ivf_end(index._h), "knnx")  # pylint: disable=protected-access
-    index.nprobe = min(int(nprobe), nlist)
-    index.ivf_centroids, index.ivf_row_range = np.asarray(centroids, dtype=np.float16), (int(id_base), int(id_base) + int(n))
-    return index
+    if dq != d:
+        cshape = index._pad(np.asarray(centroids, dtype=np.float16)).shape  # pylint: disable=protected-access
+        if cshape != (nlist, dq):
+            raise ValueError(f"centroids must be [{nlist}, {dq}] behind a rotation {rotation.shape}, got {cshape}")
+    return _ivf_begin(index, nlist, centroids, sizes)
 
 
 def _ivfpq_encode_chunks(chunks, n, d, nlist, M, centroids, codebooks, lists, nprobe, device, id_base, rotation=None, refine=False,
                          k_factor=1, threshold_scan=False):
     """Rows (an iterator of (offset, fp16 rows)) -> IVF-PQ index: every row is encoded into the next free slot of its list.  With a
     rotation the rows are the UN-ROTATED ones (the index rotates each chunk) and `lists` are those of the rotated rows."""
-    sizes = np.bincount(lists, minlength=nlist).astype(np.int64)
-    if sizes.shape[0] != nlist:
-        raise ValueError("a list id is outside [0, nlist)")
-    index = _ivfpq_begin(d, nlist, M, centroids, codebooks, sizes, device, id_base, rotation, refine, k_factor, threshold_scan)
-    lib = index._lib  # pylint: disable=protected-access
-    cursor = np.zeros(nlist, dtype=np.int64)
-    for o, x in chunks:
-        rows = np.ascontiguousarray(index._pad(np.asarray(x, dtype=np.float16)))  # pylint: disable=protected-access
-        ls = np.ascontiguousarray(lists[o:o + rows.shape[0]], dtype=np.int32)
-        pos = _positions_in_lists(ls, cursor)
-        ids = np.arange(o, o + rows.shape[0], dtype=np.int64) + id_base
-        check(lib, lib.knnx_ivf_add_assigned(index._h, rows.ctypes.data, rows.shape[0], ids.ctypes.data, ls.ctypes.data, pos.ctypes.data), "knnx")  # pylint: disable=protected-access
-    index = _ivfpq_end(index, nlist, nprobe, centroids, id_base, n)
-    index.ivf_lists = lists
-    return index
+    return _encode_chunks(lambda sizes: _ivfpq_begin(d, nlist, M, centroids, codebooks, sizes, device, id_base, rotation, refine, k_factor,
+                                                     threshold_scan), chunks, n, nlist, centroids, lists, nprobe, id_base)
 
 
 def _assign_chunks(chunks, n, d, nlist, centroids, device, A):
@@ -1889,7 +1934,7 @@ def build_ivfpq_index_device(fill_rows, n, d, nlist, M, nprobe=16, niter=8, pq_n
         m = min(chunk, n - o)
         fill_rows(rows_ptr, o, m, 1)
         check(lib, lib.knnx_ivf_add_assigned_device(index._h, C.c_void_p(rows_ptr), m, id_base + o, C.c_void_p(lists_ptr + 4 * o)), "knnx")  # pylint: disable=protected-access
-    index = _ivfpq_end(index, nlist, nprobe, centroids, id_base, n)
+    index = _ivf_end(index, nlist, nprobe, centroids, id_base, n)
     del rows_keep, lists_keep
     _release_cached_device_memory()
     t3 = time.perf_counter()
@@ -1943,20 +1988,6 @@ def _save_ivfpq_index(index, folder, embeddings_folder=None):
         json.dump(man, f, indent=1)
     os.replace(tmp, os.path.join(folder, IVFPQ_MANIFEST))
     return man
-
-
-def ivfpq_threshold_scan_entry(on):
-    """What a saved IVF-PQ manifest says about the threshold-scan switch: {"threshold_scan": true} when it is on, nothing otherwise."""
-    return {"threshold_scan": True} if on else {}
-
-
-def read_ivfpq_threshold_scan(folder, man):
-    """The threshold-scan switch of a saved IVF-PQ manifest: False for a manifest without the key (every folder written before the
-    switch existed, and every index saved with it off), else the boolean it carries; anything but a boolean is refused."""
-    v = man.get("threshold_scan", False)
-    if not isinstance(v, bool):
-        raise ValueError(f"{folder}: \"threshold_scan\" must be true or false, got {v!r}")
-    return v
 
 
 def ivfpq_out_dim_entry(d, d_out):
@@ -2050,20 +2081,9 @@ def _ivfpq_from_codes(codes, lists, lo, cent, cb, M, nprobe, device, chunk=1 << 
     nlist, d = cent.shape
     if rotation is not None:  # (behind a rectangular rotation the centroids are d_out wide; the index is as wide as the rotation's input)
         d = rotation.shape[1]
-    n = codes.shape[0]
-    sizes = np.bincount(lists, minlength=nlist).astype(np.int64)
-    index = _ivfpq_begin(d, nlist, M, cent, cb, sizes, device, lo, rotation)
-    lib = index._lib  # pylint: disable=protected-access
-    cursor = np.zeros(nlist, dtype=np.int64)
-    for o in range(0, n, chunk):
-        c = np.ascontiguousarray(codes[o:o + chunk], dtype=np.uint8)
-        ls = np.ascontiguousarray(lists[o:o + chunk], dtype=np.int32)
-        pos = _positions_in_lists(ls, cursor)
-        ids = np.arange(lo + o, lo + o + c.shape[0], dtype=np.int64)
-        check(lib, lib.knnx_ivfpq_add_codes(index._h, c.ctypes.data, c.shape[0], ids.ctypes.data, ls.ctypes.data, pos.ctypes.data), "knnx")  # pylint: disable=protected-access
-    index = _ivfpq_end(index, nlist, nprobe, cent, lo, n)
-    index.ivf_lists = np.asarray(lists, dtype=np.int32)
-    return index
+    index = _ivfpq_begin(d, nlist, M, cent, cb, np.bincount(lists, minlength=nlist).astype(np.int64), device, lo, rotation)
+    _add_code_chunks(index, index._lib.knnx_ivfpq_add_codes, codes, lists, lo, nlist, chunk)  # pylint: disable=protected-access
+    return _ivf_end(index, nlist, nprobe, cent, lo, codes.shape[0], np.asarray(lists, dtype=np.int32))
 
 
 def _load_ivfpq_index(folder, device=0, row_range=None, devices=None, embeddings_folder=None):
@@ -2094,20 +2114,7 @@ def _load_ivfpq_index(folder, device=0, row_range=None, devices=None, embeddings
 
     if cent.shape != (man["nlist"], read_ivfpq_out_dim(folder, man)) or codes.shape != (shi - slo, M) or lists.shape[0] != shi - slo:
         raise ValueError(f"{folder}: the IVF-PQ files disagree with the manifest")
-    if devices is not None:
-        if row_range is not None:
-            raise ValueError("row_range and devices are mutually exclusive")
-        G = len(devices)
-        cuts = [slo + (shi - slo) * g // G for g in range(G + 1)]
-        shards = [make(codes[cuts[g] - slo:cuts[g + 1] - slo], np.asarray(lists[cuts[g] - slo:cuts[g + 1] - slo]), cuts[g], devices[g])
-                  for g in range(G)]
-        sharded = ShardedMi355xIndex.from_shards(shards, cuts[:-1])
-        sharded.nprobe = man["nprobe"]
-        return sharded
-    lo, hi = (slo, shi) if row_range is None else (int(row_range[0]), int(row_range[1]))
-    if not slo <= lo <= hi <= shi:
-        raise ValueError(f"row_range {row_range} is outside the saved shard's rows [{slo}, {shi})")
-    return make(codes[lo - slo:hi - slo], np.asarray(lists[lo - slo:hi - slo]), lo, device)
+    return _split_saved_rows(make, codes, lists, (slo, shi), man["nprobe"], device, row_range, devices)
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -2181,54 +2188,18 @@ def check_ivfsq_manifest(man, where=""):
     return man
 
 
-def ivfsq_threshold_scan_entry(on):
-    """What a saved IVF-SQ8 manifest says about the threshold-scan switch: {"threshold_scan": true} when it is on, nothing otherwise."""
-    return {"threshold_scan": True} if on else {}
-
-
-def read_ivfsq_threshold_scan(folder, man):
-    """The threshold-scan switch of a saved IVF-SQ8 folder: False where the manifest has no such key (folders saved before the switch
-    existed, and every folder saved with it off)."""
-    v = man.get("threshold_scan", False)
-    if not isinstance(v, bool):
-        raise ValueError(f"{folder}: \"threshold_scan\" must be true or false, got {v!r}")
-    return v
-
-
 def _ivfsq_begin(d, nlist, centroids, ranges, sizes, device, id_base, threshold_scan=False):
     index = Mi355xIndex(d, device=device, id_base=id_base)
     index.set_sq_quantizer(*ranges)
     if threshold_scan:  # (off is the state of a new index: nothing is called for it)
         index.sq_threshold_scan = True
-    cpad = np.ascontiguousarray(index._pad(np.asarray(centroids, dtype=np.float16)))  # pylint: disable=protected-access
-    check(index._lib, index._lib.knnx_ivf_begin(index._h, nlist, cpad.ctypes.data, np.ascontiguousarray(sizes, dtype=np.int64).ctypes.data), "knnx")  # pylint: disable=protected-access
-    return index
-
-
-def _ivfsq_end(index, nlist, nprobe, centroids, id_base, n, lists=None):
-    check(index._lib, index._lib.knnx_ivf_end(index._h), "knnx")  # pylint: disable=protected-access
-    index.nprobe = min(int(nprobe), nlist)
-    index.ivf_centroids, index.ivf_row_range = np.asarray(centroids, dtype=np.float16), (int(id_base), int(id_base) + int(n))
-    if lists is not None:
-        index.ivf_lists = lists
-    return index
+    return _ivf_begin(index, nlist, centroids, sizes)
 
 
 def _ivfsq_encode_chunks(chunks, n, d, nlist, centroids, ranges, lists, nprobe, device, id_base, threshold_scan=False):
     """Rows (an iterator of (offset, fp16 rows)) -> IVF-SQ8 index: every row is encoded into the next free slot of its list."""
-    sizes = np.bincount(lists, minlength=nlist).astype(np.int64)
-    if sizes.shape[0] != nlist:
-        raise ValueError("a list id is outside [0, nlist)")
-    index = _ivfsq_begin(d, nlist, centroids, ranges, sizes, device, id_base, threshold_scan)
-    lib = index._lib  # pylint: disable=protected-access
-    cursor = np.zeros(nlist, dtype=np.int64)
-    for o, x in chunks:
-        rows = np.ascontiguousarray(index._pad(np.asarray(x, dtype=np.float16)))  # pylint: disable=protected-access
-        ls = np.ascontiguousarray(lists[o:o + rows.shape[0]], dtype=np.int32)
-        pos = _positions_in_lists(ls, cursor)
-        ids = np.arange(o, o + rows.shape[0], dtype=np.int64) + id_base
-        check(lib, lib.knnx_ivf_add_assigned(index._h, rows.ctypes.data, rows.shape[0], ids.ctypes.data, ls.ctypes.data, pos.ctypes.data), "knnx")  # pylint: disable=protected-access
-    return _ivfsq_end(index, nlist, nprobe, centroids, id_base, n, lists)
+    return _encode_chunks(lambda sizes: _ivfsq_begin(d, nlist, centroids, ranges, sizes, device, id_base, threshold_scan), chunks, n, nlist,
+                          centroids, lists, nprobe, id_base)
 
 
 def build_ivfsq_index(x_f16, nlist, nprobe=16, niter=8, seed=0, device=0, id_base=0, centroids=None, ranges=None, chunk=1 << 20,
@@ -2314,7 +2285,7 @@ def build_ivfsq_index_device(fill_rows, n, d, nlist, nprobe=16, niter=8, seed=0,
         m = min(chunk, n - o)
         fill_rows(rows_ptr, o, m, 1)
         check(lib, lib.knnx_ivf_add_assigned_device(index._h, C.c_void_p(rows_ptr), m, id_base + o, C.c_void_p(lists_ptr + 4 * o)), "knnx")  # pylint: disable=protected-access
-    index = _ivfsq_end(index, nlist, nprobe, centroids, id_base, n, _download_i32(lists_ptr, n, device) if keep_lists else None)
+    index = _ivf_end(index, nlist, nprobe, centroids, id_base, n, _download_i32(lists_ptr, n, device) if keep_lists else None)
     del rows_keep, lists_keep
     _release_cached_device_memory()
     t3 = time.perf_counter()
@@ -2353,18 +2324,9 @@ def _save_ivfsq_index(index, folder):
 
 def _ivfsq_from_codes(codes, lists, lo, cent, ranges, nprobe, device, chunk=1 << 20, threshold_scan=False):
     nlist, d = cent.shape
-    n = codes.shape[0]
-    sizes = np.bincount(lists, minlength=nlist).astype(np.int64)
-    index = _ivfsq_begin(d, nlist, cent, ranges, sizes, device, lo, threshold_scan)
-    lib = index._lib  # pylint: disable=protected-access
-    cursor = np.zeros(nlist, dtype=np.int64)
-    for o in range(0, n, chunk):
-        c = np.ascontiguousarray(index._pad(np.asarray(codes[o:o + chunk], dtype=np.uint8)))  # pylint: disable=protected-access
-        ls = np.ascontiguousarray(lists[o:o + chunk], dtype=np.int32)
-        pos = _positions_in_lists(ls, cursor)
-        ids = np.arange(lo + o, lo + o + c.shape[0], dtype=np.int64)
-        check(lib, lib.knnx_ivfsq_add_codes(index._h, c.ctypes.data, c.shape[0], ids.ctypes.data, ls.ctypes.data, pos.ctypes.data), "knnx")  # pylint: disable=protected-access
-    return _ivfsq_end(index, nlist, nprobe, cent, lo, n, np.asarray(lists, dtype=np.int32))
+    index = _ivfsq_begin(d, nlist, cent, ranges, np.bincount(lists, minlength=nlist).astype(np.int64), device, lo, threshold_scan)
+    _add_code_chunks(index, index._lib.knnx_ivfsq_add_codes, codes, lists, lo, nlist, chunk, index._pad)  # pylint: disable=protected-access
+    return _ivf_end(index, nlist, nprobe, cent, lo, codes.shape[0], np.asarray(lists, dtype=np.int32))
 
 
 def _load_ivfsq_index(folder, device=0, row_range=None, devices=None):
@@ -2381,18 +2343,5 @@ def _load_ivfsq_index(folder, device=0, row_range=None, devices=None):
     d = int(man["d"])
     if cent.shape != (man["nlist"], d) or codes.shape != (shi - slo, d) or lists.shape[0] != shi - slo or ranges[0].shape != (d,) or ranges[1].shape != (d,):
         raise ValueError(f"{folder}: the IVF-SQ8 files disagree with the manifest")
-    if devices is not None:
-        if row_range is not None:
-            raise ValueError("row_range and devices are mutually exclusive")
-        G = len(devices)
-        cuts = [slo + (shi - slo) * g // G for g in range(G + 1)]
-        shards = [_ivfsq_from_codes(codes[cuts[g] - slo:cuts[g + 1] - slo], np.asarray(lists[cuts[g] - slo:cuts[g + 1] - slo]), cuts[g], cent,
-                                    ranges, man["nprobe"], devices[g], threshold_scan=thr_scan) for g in range(G)]
-        sharded = ShardedMi355xIndex.from_shards(shards, cuts[:-1])
-        sharded.nprobe = man["nprobe"]
-        return sharded
-    lo, hi = (slo, shi) if row_range is None else (int(row_range[0]), int(row_range[1]))
-    if not slo <= lo <= hi <= shi:
-        raise ValueError(f"row_range {row_range} is outside the saved shard's rows [{slo}, {shi})")
-    return _ivfsq_from_codes(codes[lo - slo:hi - slo], np.asarray(lists[lo - slo:hi - slo]), lo, cent, ranges, man["nprobe"], device,
-                             threshold_scan=thr_scan)
+    return _split_saved_rows(lambda c, ls, lo, dev: _ivfsq_from_codes(c, ls, lo, cent, ranges, man["nprobe"], dev, threshold_scan=thr_scan),
+                             codes, lists, (slo, shi), man["nprobe"], device, row_range, devices)

@@ -94,16 +94,14 @@ def test_restatement_agrees_with_np_adc_search():
 
 
 # ------------------------------------------------------------------------------------------------ the descent state machine
-def test_descent_state_machine_under_sanitizers(tmp_path):
-    """tools/descent_check.cpp (its own main, only knnx_descent.h) built with -fsanitize=address,undefined and run as a child: the
-    descent terminates within its scan budget on uniform / bell / one-close-neighbour / all-equal / T < k / T = 0 score arrays, fetches
-    at least min(k, T) rows, and never fetches more than 16 k once a scan within [min(k, T), 16 k] was seen."""
+def _run_sanitized_check(tmp_path, name):
+    """tools/<name>.cpp built with -fsanitize=address,undefined against csrc/ and run as a child process -> its standard output."""
     cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
     if cxx is None:
         pytest.skip("no host C++ compiler")
-    exe = str(tmp_path / "descent_check")
+    exe = str(tmp_path / name)
     base = [cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I",
-            os.path.join(ROOT, "clip-retrieval_amd", "csrc"), os.path.join(ROOT, "tools", "descent_check.cpp"), "-o", exe]
+            os.path.join(ROOT, "clip-retrieval_amd", "csrc"), os.path.join(ROOT, "tools", name + ".cpp"), "-o", exe]
     # the sanitizer runtimes linked into the program where the toolchain has them as archives (nothing then depends on the order in
     # which shared libraries are loaded); the toolchain's default otherwise
     build = subprocess.run(base + ["-static-libasan", "-static-libubsan"], capture_output=True, text=True)
@@ -112,8 +110,16 @@ def test_descent_state_machine_under_sanitizers(tmp_path):
     assert build.returncode == 0, build.stdout + build.stderr
     run = subprocess.run([exe], capture_output=True, text=True)
     assert run.returncode == 0, run.stdout[-4000:] + run.stderr[-4000:]
-    assert run.stdout.rstrip().endswith("descent ok") and "FAILED" not in run.stdout
-    lines = [ln for ln in run.stdout.splitlines() if " scans " in ln]
+    return run.stdout
+
+
+def test_descent_state_machine_under_sanitizers(tmp_path):
+    """tools/descent_check.cpp (its own main, only knnx_descent.h) built with -fsanitize=address,undefined and run as a child: the
+    descent terminates within its scan budget on uniform / bell / one-close-neighbour / all-equal / T < k / T = 0 score arrays, fetches
+    at least min(k, T) rows, and never fetches more than 16 k once a scan within [min(k, T), 16 k] was seen."""
+    out = _run_sanitized_check(tmp_path, "descent_check")
+    assert out.rstrip().endswith("descent ok") and "FAILED" not in out
+    lines = [ln for ln in out.splitlines() if " scans " in ln]
     assert len(lines) >= 50
     assert any("bisections 0" not in ln for ln in lines), "no case exercised the bisection"
 
@@ -122,6 +128,30 @@ def test_descent_header_has_no_hip():
     text = open(os.path.join(ROOT, "clip-retrieval_amd", "csrc", "knnx_descent.h"), encoding="utf-8").read()
     includes = [ln.split()[1] for ln in text.splitlines() if ln.startswith("#include")]
     assert includes and all(inc.startswith("<") and "hip" not in inc for inc in includes), includes  # system headers only, none of HIP's
+    assert "__global__" not in text and "__device__" not in text and "hipStream" not in text
+
+
+def test_threshold_group_driver_under_sanitizers(tmp_path):
+    """tools/thr_group_check.cpp (its own main, only knnx_thr_group.h) built with -fsanitize=address,undefined and run as a child: it
+    plays the device for mixed groups of queries (bell / uniform / all-equal / tied scores, totals <= 2 kc, < kc and 0, kc = 65 and
+    3000, pools so small that a regrow falls among fetched queries, a full pass of 256) and asserts that every query ends fetched
+    with exactly the brute-force top min(kc, total), that a fetched query only ever sees +INFINITY again, that the participations
+    reported are the scans a query was not yet fetched in, and that pool_want is the smallest doubling that fits."""
+    out = _run_sanitized_check(tmp_path, "thr_group_check")
+    assert out.rstrip().endswith("thr group ok") and "FAILED" not in out
+    lines = [ln for ln in out.splitlines() if " scans " in ln]
+    assert len(lines) >= 16
+    assert any(" gq 256 " in ln for ln in lines), "no group of a full pass"
+    assert any("regrows 0" not in ln for ln in lines), "no case made the pool grow"
+    assert any("mixed steps 0" not in ln for ln in lines), "no step had a final query next to a descending one"
+
+
+def test_threshold_group_header_has_no_hip():
+    text = open(os.path.join(ROOT, "clip-retrieval_amd", "csrc", "knnx_thr_group.h"), encoding="utf-8").read()
+    includes = [ln.split()[1] for ln in text.splitlines() if ln.startswith("#include")]
+    # system headers and the descent (itself checked above), none of HIP's
+    assert includes and all((inc.startswith("<") and "hip" not in inc) or inc == '"knnx_descent.h"' for inc in includes), includes
+    assert '"knnx_descent.h"' in includes
     assert "__global__" not in text and "__device__" not in text and "hipStream" not in text
 
 

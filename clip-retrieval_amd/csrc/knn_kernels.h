@@ -109,6 +109,12 @@ hipError_t launch_ivf_new_to_old(const int64_t* idmap, int64_t prow, const unsig
 // out[t] = id_base + ordinal of the row with id ids[t] (-1 -> -1; out may be ids); ids == null: the ids id_base + i0 + t, a slice of old_to_new
 hipError_t launch_ivf_map_ids(const uint32_t* inv, int64_t id_base, int64_t ntotal, const unsigned* tile0, const int64_t* dense0, int nlist,
                               const int64_t* ids_or_null, int64_t i0, int64_t n, int64_t* out, hipStream_t st);
+// the arena move of a growing index (knn_grow_kernels.hip; src_tile [tiles]: the old tile of every new tile or GROW_NO_TILE, knnx_grow_plan.h):
+// dst tile t = src tile src_tile[t], or zeros; `width` bytes per arena row (a multiple of 16), tiles of 32 rows; src and dst distinct
+hipError_t launch_ivf_grow_move(const void* src, void* dst, int width, const uint32_t* src_tile, int64_t tiles, int n_cu, hipStream_t st);
+// ... and its ids: idmap [prow] = the old id of every moved row, -1 elsewhere; inv[id - id_lo] = the new arena row of every moved id
+hipError_t launch_ivf_grow_ids(const int64_t* idmap_old, const uint32_t* src_tile, int64_t prow, int64_t id_lo, int64_t n_ids, int64_t* idmap,
+                               uint32_t* inv, hipStream_t st);
 
 // ---- register-stationary-queries (RQ) scan, knn_rq_kernels.hip: up to rq_queries_per_pass(d) queries per pass over HBM
 constexpr int KNN_RQ_MAX = 256;        // queries of one RQ pass at d <= 768 (128 at d = 1024)

@@ -513,6 +513,14 @@ struct IdOrder {
   int64_t cap = 0;                // ids pin / dev hold
 };
 
+// what the most recent knnx_ivf_append* / knnx_ivf_merge_from that succeeded spent (knnx_grow.hip; knnx_ivf_grow_stats)
+struct GrowStats {
+  double assign_ms = 0, move_ms = 0, ids_ms = 0, fill_ms = 0;  // host time of the assignment pass; device time of the arena move, of its
+                                                                // idmap / inv pass (part of move_ms), of the scatter / encode
+  int64_t moved_bytes = 0;                          // payload bytes the move copied (occupied tiles of every arena)
+  int64_t calls = 0;
+};
+
 // hit pools of the range scans, grown on demand (knnx_range.hip: range_pool_alloc)
 struct RangePools {
   DevBuf<float> s;
@@ -612,6 +620,7 @@ struct knnx_index {
   SqData sq;
   SqScratch sqs;
   IdOrder ido;
+  GrowStats grow;
 
   // a proof-based scan that skipped its fallback (see WideScratch) says so here: 1 = rq.need / rq.gate, 2 = wide.need / wide.gate
   bool defer_fb = false;

@@ -166,6 +166,7 @@ class Mi355xIndex(_FaissShaped):
         self._h = h
         self.metric_type = METRIC_INNER_PRODUCT
         self.is_trained = True
+        self._id_base = int(id_base)
         if id_base:
             check(self._lib, self._lib.knnx_set_id_base(self._h, int(id_base)), "knnx")
         # concurrent single-query callers are coalesced INSIDE the library (knnx.h: knnx_set_coalesce; round 4 -- round 3 did it
@@ -424,6 +425,82 @@ class Mi355xIndex(_FaissShaped):
         """Result ids (any shape, int64) -> their list-ordered ids, -1 kept: np.take(ivf_old_to_new(), ids - id_base) without the
         table, by a gather kernel over the layout the index holds.  Safe to call from request threads while others search."""
         return _map_ids_call(self._lib, self._lib.knnx_ivf_map_ids, self._h, ids)
+
+    # ------------------------------------------------------------------ growing a built IVF index (include/knnx.h)
+    def _grown(self, n_before, lists):
+        """After rows were appended: the ids they got; ivf_lists / ivf_row_range follow where the index carries them (save_index).
+        lists None: they are not known, and an index that carried them no longer does."""
+        n = self.ntotal - n_before
+        rng = getattr(self, "ivf_row_range", None)
+        base = rng[0] if rng is not None else self._id_base
+        if rng is not None:
+            self.ivf_row_range = (rng[0], rng[1] + n)
+        if getattr(self, "ivf_lists", None) is not None:
+            if lists is None:
+                del self.ivf_lists
+            else:
+                self.ivf_lists = np.concatenate([np.asarray(self.ivf_lists, dtype=np.int32), np.asarray(lists, dtype=np.int32)])
+        return np.arange(base + n_before, base + n_before + n, dtype=np.int64)
+
+    def ivf_append(self, x, lists=None, chunk=1 << 22):
+        """faiss index.add on a BUILT IVF index of any kind (add() keeps refusing it): float16 or float32 rows [n, d] go behind the rows
+        of their lists and get the next ids -> int64 [n], the new ids (id_base + ntotal before + i).  `lists` (int32 [n]) names every
+        row's list -- in the quantiser space for an index with a rotation, as at build time; None: the library assigns with the index's
+        own centroids (what IvfBuilder.assign answers).  The result is bit for bit the index a fresh build over all rows gives.  Every
+        call moves the arena once (peak memory: old + new arena), so rows are best appended in large batches; inputs above `chunk` rows
+        are converted and appended `chunk` rows at a time.  Concurrent searches see the index before or after a call.  A list-ordered
+        metadata store (ivf_old_to_new) must be exported again afterwards."""
+        x = np.asarray(x)
+        if x.ndim != 2 or x.shape[1] != self.d:
+            raise ValueError(f"ivf_append expects [n, {self.d}], got {x.shape}")
+        if x.dtype not in (np.float16, np.float32):
+            raise TypeError(f"ivf_append expects float32 or float16 rows, got {x.dtype}")
+        if lists is not None:
+            lists = np.ascontiguousarray(lists, dtype=np.int32).reshape(-1)
+            if lists.shape[0] != x.shape[0]:
+                raise ValueError(f"lists must name one list per row: {lists.shape[0]} for {x.shape[0]} rows")
+        n_before, got = self.ntotal, []
+        for o in range(0, x.shape[0], int(chunk)):
+            rows = np.ascontiguousarray(self._pad(np.asarray(x[o:o + chunk], dtype=np.float16)))
+            if lists is not None:
+                ls = np.ascontiguousarray(lists[o:o + chunk])
+                check(self._lib, self._lib.knnx_ivf_append_assigned(self._h, rows.ctypes.data, rows.shape[0], ls.ctypes.data), "knnx")
+            else:
+                ls = np.empty(rows.shape[0], dtype=np.int32)
+                check(self._lib, self._lib.knnx_ivf_append(self._h, rows.ctypes.data, rows.shape[0], ls.ctypes.data), "knnx")
+            got.append(ls)
+        if x.shape[0] == 0:  # (still refused on an index that cannot grow)
+            check(self._lib, self._lib.knnx_ivf_append(self._h, None, 0, None), "knnx")
+        return self._grown(n_before, np.concatenate(got) if got else np.zeros(0, np.int32))
+
+    def ivf_append_device(self, ptr, n):
+        """ivf_append for n fp16 rows [n, d] already in HBM on the index's device (a torch tensor's data_ptr(); d % 256 == 0): the
+        library assigns them, the rows never visit the host -> the new ids."""
+        if self._dpad != self.d:
+            raise HipLibraryError("device rows must already be padded to a multiple of 256 columns")
+        n_before = self.ntotal
+        ls = np.empty(int(n), dtype=np.int32)
+        check(self._lib, self._lib.knnx_ivf_append_device(self._h, C.c_void_p(int(ptr)), int(n), ls.ctypes.data), "knnx")
+        return self._grown(n_before, ls)
+
+    def merge_from(self, other):
+        """faiss merge_from / merge_ondisk (clip_back_prepro/index_combiner.py): every row of `other`, a built IVF index of the same
+        kind with bit-equal centroids and quantiser, goes into this one -> the new ids; other's id j becomes id_base + ntotal before +
+        (j - other's id_base).  Codes and rows are copied through host memory, never encoded again, so `other` may live on another
+        device.  Unlike faiss, `other` is left untouched (close it when it is no longer needed)."""
+        if not isinstance(other, Mi355xIndex):
+            raise TypeError("merge_from takes a Mi355xIndex")
+        n_before = self.ntotal
+        check(self._lib, self._lib.knnx_ivf_merge_from(self._h, other._h), "knnx")  # pylint: disable=protected-access
+        lists = getattr(other, "ivf_lists", None)
+        if lists is None and other.pq_m:
+            lists = other.pq_codes()[1]
+        elif lists is None and other.is_sq:
+            lists = other.sq_codes()[1]
+        for name in ("ivf_source", "embeddings_folder", "ivf_folder", "ivf_folder_files"):  # the rows no longer come from one folder
+            if hasattr(self, name):
+                delattr(self, name)
+        return self._grown(n_before, lists)
 
     # ------------------------------------------------------------------ searching
     def _search_raw(self, q, k, want_r):
@@ -1256,7 +1333,43 @@ def _scatter_into_ivf(src, lo, hi, centroids, lists, nprobe, device, chunk):
     _add_assigned_chunks(index, ((o - lo, x) for o, x in src.chunks(lo, hi, chunk)), lists, nlist, lo)
     index = _ivf_end(index, nlist, nprobe, centroids, lo, hi - lo, lists)
     index.ivf_source = src
+    return _remember_folder(index, src)
+
+
+def _remember_folder(index, src):
+    """What append_new_folder_rows needs of the folder an index was built from: where it is, and the name and row count of every
+    partition file it held then."""
+    index.ivf_folder, index.ivf_folder_files = src.folder, src.manifest()["files"]
     return index
+
+
+def append_new_folder_rows(index, folder=None, chunk=1 << 22):
+    """The reference keeps writing img_emb_N.npy partitions into the embeddings folder (`clip inference`): append the rows the folder
+    gained since `index` was built from it (build_*_from_folder, or load_index of a folder that names its embeddings) -> their ids, the
+    global row numbers.  The files the index was built from must still be a PREFIX of the folder's files, with the same names and row
+    counts, and the index must reach the end of them (a shard that stops earlier cannot grow without renumbering); otherwise
+    ValueError, before anything is touched.  The library assigns the rows (Mi355xIndex.ivf_append), so a following save_index +
+    load_index gives the index a fresh build over the enlarged folder with the same centroids and quantiser gives.  `folder`: where the
+    embeddings are now, if they moved.  The new rows go in `chunk` rows per call, and every call moves the arena once."""
+    files = getattr(index, "ivf_folder_files", None)
+    folder = folder or getattr(index, "ivf_folder", None)
+    if files is None or folder is None:
+        raise ValueError("append_new_folder_rows takes an index built from an embeddings folder (build_*_from_folder / load_index)")
+    src = folder if isinstance(folder, FolderRows) else FolderRows(folder)
+    now = src.manifest()["files"]
+    files = [list(f) for f in files]
+    if now[:len(files)] != files or src.d != index.d:
+        raise ValueError(f"{src.folder}: the embedding files the index was built from changed (names / row counts / dimension): they must "
+                         "still be the first files of the folder")
+    old_n = sum(int(rows) for _, rows in files)
+    lo, hi = getattr(index, "ivf_row_range", (0, old_n))
+    if hi != old_n:
+        raise ValueError(f"the index holds rows [{lo}, {hi}) of a folder that had {old_n}: only an index that reaches the end of its folder can grow")
+    ids = [index.ivf_append(x) for _, x in src.chunks(old_n, src.n, chunk)]
+    _remember_folder(index, src)
+    if hasattr(index, "ivf_source"):
+        index.ivf_source = src
+    return np.concatenate(ids) if ids else np.zeros(0, dtype=np.int64)
 
 
 def build_ivf_index_from_folder(path, nlist, nprobe=16, niter=8, seed=0, device=0, row_range=None, centroids=None,
@@ -1830,7 +1943,7 @@ def build_ivfpq_index_from_folder(path, nlist, M, nprobe=16, niter=8, pq_niter=1
                                  refine, k_factor, threshold_scan)
     index.rotate_s = rotate_s
     index.embeddings_folder = src.folder if hasattr(src, "folder") else None
-    return index
+    return _remember_folder(index, src)
 
 
 def build_ivfpq_index_device(fill_rows, n, d, nlist, M, nprobe=16, niter=8, pq_niter=10, seed=0, device=0, id_base=0, centroids=None,
@@ -2074,7 +2187,7 @@ def _ivfpq_refine_from_rows(src, codes, lists, lo, cent, cb, M, nprobe, device, 
         index.close()
         raise ValueError(f"{bad} of {n} rows of {src.folder} do not encode to the saved ivf_pq_codes.npy: the embeddings or the codes changed")
     index.embeddings_folder = src.folder
-    return index
+    return _remember_folder(index, src)
 
 
 def _ivfpq_from_codes(codes, lists, lo, cent, cb, M, nprobe, device, chunk=1 << 20, rotation=None):
@@ -2234,7 +2347,8 @@ def build_ivfsq_index_from_folder(path, nlist, nprobe=16, niter=8, seed=0, devic
             ranges = train_sq_ranges(sample, device=device, chunk=chunk)
     centroids = np.asarray(centroids).astype(np.float16)
     lists, _ = _assign_chunks(src.chunks(0, src.n, chunk), src.n, src.d, nlist, centroids, device, None)
-    return _ivfsq_encode_chunks(src.chunks(0, src.n, chunk), src.n, src.d, nlist, centroids, ranges, lists, nprobe, device, 0, threshold_scan)
+    return _remember_folder(_ivfsq_encode_chunks(src.chunks(0, src.n, chunk), src.n, src.d, nlist, centroids, ranges, lists, nprobe, device, 0,
+                                                 threshold_scan), src)
 
 
 def build_ivfsq_index_device(fill_rows, n, d, nlist, nprobe=16, niter=8, seed=0, device=0, id_base=0, centroids=None, ranges=None,

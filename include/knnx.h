@@ -392,6 +392,46 @@ int knnx_colminmax_device(int device, const void* rows_dev_f16, int64_t n, int d
 int knnx_ivf_id_order(knnx_index* ix, int64_t* old_to_new, int64_t* new_to_old);
 int knnx_ivf_map_ids(knnx_index* ix, const int64_t* ids, int64_t n, int64_t* out);
 
+/* ---- Growing a built index: faiss index.add on a trained IVF index (autofaiss fills an index batch by batch) and merge_from / merge_ondisk
+ * (clip_back_prepro/index_combiner.py joins index parts that share a quantiser) ----
+ * For every BUILT IVF index -- IVF-Flat, IVF-PQ (rotation, d_out, refine store, M = 256, threshold scan) and IVF-SQ8; knnx_ivf_end or
+ * knnx_ivf_set_lists has run -- that owns its rows.  knnx_add_* keeps refusing such an index; these are the calls that grow it.
+ * Ids stay faiss' sequential ids: row i of a call gets id id_base + ntotal_before + i.  Inside its list a row goes behind the rows already
+ * there, in call order -- position = old list size + its stable rank among the rows of the call in the same list.  The result is, bit for
+ * bit (arena, id maps, search results, exported codes), the index knnx_ivf_begin / knnx_ivf_add_assigned / knnx_ivf_end build from the
+ * concatenated rows with the same centroids, quantiser and lists.
+ *   knnx_ivf_append_assigned  rows_f16 host fp16 [n][d]; lists host int32 [n] names the list of every row (in the quantiser space for an
+ *                             index with a rotation, as at build time).
+ *   knnx_ivf_append           the library assigns: the assignment kernel of knnx_ivfb_assign over the index's own coarse centroids, after
+ *                             the rotation where the index has one.  lists_out (host int32 [n], may be NULL) receives the lists.
+ *   knnx_ivf_append_device    the same for rows already in HBM on the index's device (fp16 [n][d]); the rows never visit the host.
+ *   knnx_ivf_merge_from       every row of `other` into ix.  Both built and of the same kind; d, d_out, nlist, M equal; centroids,
+ *                             codebooks, rotation and SQ8 ranges bit-equal; a refine store in both or in neither -- otherwise KNNX_E_ARG
+ *                             naming what differs.  other's row with id j gets id id_base + ntotal_before + (j - other's id_base); inside
+ *                             a list the rows keep other's order, behind the rows already there.  Codes and rows are copied, never
+ *                             encoded again; they are staged through host memory (all of other at once), so the two may live on
+ *                             different devices.  `other` is left UNTOUCHED (faiss' merge_from empties it).  ix == other: KNNX_E_ARG.
+ * How: the arena is dense and tile-padded (tile0 = prefix sum of ceil(size / 32)), so a list that grows moves every list behind it.  A
+ * call lays the grown index down OUT OF PLACE -- new arena(s), idmap and inv; the occupied tiles copied by a tile-granular move kernel,
+ * the new rows scattered / encoded by the kernels of the build -- and swaps it in at the end: peak memory is old + new arena.  Calls are
+ * all or nothing and atomic for searchers (they run under the lock the searches hold): a search from another thread sees the index
+ * before or after the call.  Argument errors -- a NULL pointer, a list id outside [0, nlist), a flat index, an index between
+ * knnx_ivf_begin and knnx_ivf_end, borrowed rows -- answer KNNX_E_ARG before anything is touched; an allocation that fails answers
+ * KNNX_E_NOMEM, more than 2^32 padded rows KNNX_E_UNSUPPORTED; in every case nothing was added and the index stays searchable.
+ * nprobe, k_factor, the refine and threshold-scan switches and the counters are kept.  The list-ordered ids (above) change with every
+ * call -- every old_to_new entry may shift -- so a list-ordered metadata store must be exported again.  Per-list slack, in-place moves,
+ * removal of ids and a sharded form are not provided. */
+int knnx_ivf_append_assigned(knnx_index* ix, const uint16_t* rows_f16, int64_t n, const int32_t* lists);
+int knnx_ivf_append(knnx_index* ix, const uint16_t* rows_f16, int64_t n, int32_t* lists_out);
+int knnx_ivf_append_device(knnx_index* ix, const void* rows_dev_f16, int64_t n, int32_t* lists_out);
+int knnx_ivf_merge_from(knnx_index* ix, knnx_index* other);
+/* What the most recent of the four calls above that succeeded spent, for tools/ivf_append_bench.py: assign_ms = host time of the
+ * assignment pass (0 where the caller named the lists), move_ms = device time of the arena move (payload copy, zero fill, idmap / inv), ids_ms = the idmap / inv pass alone (part of move_ms),
+ * fill_ms = device time from the end of the move to the last scatter / encode kernel (for host rows it includes their upload),
+ * moved_bytes = payload bytes the move copied (the occupied tiles of every arena; idmap / inv not counted).  Any pointer may be NULL.
+ * KNNX_E_STATE before the first such call. */
+int knnx_ivf_grow_stats(knnx_index* ix, double* assign_ms, double* move_ms, double* ids_ms, double* fill_ms, int64_t* moved_bytes);
+
 /* Merge P per-shard results ([P, n, k] each, already global ids) into the top-k [n, k];
  * the step after the RCCL all-gather of a row-sharded index.  Device buffers.  k <= 64: any order within a list;
  * k > 64: every list sorted as knnx_search returns it (score descending, -1 padding at the tail), P <= 64. */

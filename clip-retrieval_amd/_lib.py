@@ -69,6 +69,9 @@ SIGNATURES = {
     "knnx_ivf_append_device": (C.c_int, [_P, _P, C.c_int64, _P]),
     "knnx_ivf_merge_from": (C.c_int, [_P, _P]),
     "knnx_ivf_grow_stats": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    "knnx_ivf_remove_ids": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "knnx_ivf_remove_stats": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64),
+                                        C.POINTER(C.c_int64)]),
     "knnx_ivfb_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "knnx_ivfb_destroy": (None, [_P]),
     "knnx_ivfb_set_centroids": (C.c_int, [_P, _P]),

@@ -115,6 +115,27 @@ hipError_t launch_ivf_grow_move(const void* src, void* dst, int width, const uin
 // ... and its ids: idmap [prow] = the old id of every moved row, -1 elsewhere; inv[id - id_lo] = the new arena row of every moved id
 hipError_t launch_ivf_grow_ids(const int64_t* idmap_old, const uint32_t* src_tile, int64_t prow, int64_t id_lo, int64_t n_ids, int64_t* idmap,
                                uint32_t* inv, hipStream_t st);
+// removing ids from a built index (knn_shrink_kernels.hip; the arithmetic is knnx_shrink_plan.h), in the order of a call.  dead and rank
+// are allocated in whole blocks of SHRINK_BLOCK ids (dead zeroed), tmask / tpos have one entry per tile of the OLD arena.
+hipError_t launch_ivf_shrink_mark(const int64_t* ids, int64_t m, int64_t id_lo, int64_t n, uint8_t* dead, hipStream_t st);
+hipError_t launch_ivf_shrink_rank_sum(const uint8_t* dead, int64_t n, uint32_t* blocksum, hipStream_t st);
+hipError_t launch_ivf_shrink_rank_apply(const uint8_t* dead, int64_t n, const uint32_t* blockoff, uint32_t* rank, hipStream_t st);
+hipError_t launch_ivf_shrink_mask(const int64_t* idmap, int64_t prow, int64_t id_lo, int64_t n, const uint8_t* dead, uint32_t* tmask,
+                                  hipStream_t st);
+hipError_t launch_ivf_shrink_list_scan(const unsigned* tile0, const unsigned* ntile, int nlist, const uint32_t* tmask, uint32_t* tpos,
+                                       unsigned* size_new, hipStream_t st);
+// tpos -> dst0 in place, once the new layout is on the device
+hipError_t launch_ivf_shrink_dst0(const unsigned* tile0_old, const unsigned* ntile_old, const unsigned* tile0_new, int nlist, uint32_t* tpos,
+                                  hipStream_t st);
+// the survivors of source tile t -> the run of `width`-byte rows at destination row dst0[t]; src and dst distinct
+hipError_t launch_ivf_shrink_move(const void* src, void* dst, int width, const uint32_t* tmask, const uint32_t* dst0, int64_t tiles, int n_cu,
+                                  hipStream_t st);
+// zeros over the pad rows of every list of the NEW layout
+hipError_t launch_ivf_shrink_pads(void* dst, int width, const unsigned* tile0, const unsigned* ntile, const unsigned* size, int nlist,
+                                  hipStream_t st);
+// idmap (already all -1) and inv of the new arena
+hipError_t launch_ivf_shrink_ids(const int64_t* idmap_old, int64_t prow_old, int64_t id_lo, int64_t n, const uint32_t* tmask,
+                                 const uint32_t* dst0, const uint32_t* rank, int64_t* idmap, uint32_t* inv, hipStream_t st);
 
 // ---- register-stationary-queries (RQ) scan, knn_rq_kernels.hip: up to rq_queries_per_pass(d) queries per pass over HBM
 constexpr int KNN_RQ_MAX = 256;        // queries of one RQ pass at d <= 768 (128 at d = 1024)

@@ -6,7 +6,7 @@
 // occupied tiles moved by launch_ivf_grow_move, the new rows scattered / encoded by the kernels of the build -- and only when all of that
 // has succeeded does grow_commit() swap them into the index, under knnx_index::mu and IdOrder::mu.  A search from another thread sees the
 // index before or after the call; a failure (an allocation above all) leaves it exactly as it was.  Whatever caches the layout is
-// refreshed or dropped by grow_commit(), in one place.
+// refreshed or dropped by ivf_swap_in(), in one place, which grow_commit() and the removal of ids (knnx_shrink.hip) both call.
 
 #include <chrono>
 
@@ -109,9 +109,8 @@ int grow_open(knnx_index* ix, const char* who, const std::vector<unsigned>& size
   return 0;
 }
 
-// the grown state becomes the index.  Everything that caches the layout is refreshed or dropped HERE; nprobe, k_factor, the refine and
-// threshold-scan switches and every counter stay.  The caller holds ix->mu and has synchronised ix->stream; the old buffers leave in G
-// (hipFree waits for the device, so a search_device still queued on a caller's stream finishes on the arena it was launched on).
+// the grown state becomes the index (ivf_swap_in, below the namespace), and the call's timings its grow stats.  The caller holds ix->mu
+// and has synchronised ix->stream.
 int grow_commit(knnx_index* ix, Grown& G) {
   float ms = 0;
   HIPCHK(hipEventRecord(G.ev_fill, ix->stream));
@@ -123,40 +122,8 @@ int grow_commit(knnx_index* ix, Grown& G) {
   HIPCHK(hipEventElapsedTime(&ms, G.ev_move1, G.ev_fill));
   G.stats.fill_ms = ms;
   G.stats.calls = ix->grow.calls + 1;
-  IdOrder& S = ix->ido;
-  std::lock_guard<std::mutex> lk(S.mu);  // a translation of ids (knnx_ivf_map_ids) reads the layout without ix->mu
-  if (S.stream) HIPCHK(hipStreamSynchronize(S.stream));
-  std::swap(ix->ivf, G.L);
-  std::swap(ix->ivf1.work, G.work);
-  if (G.pq_codes) std::swap(ix->pq.codes, G.pq_codes);
-  if (G.sq_codes) std::swap(ix->sq.codes, G.sq_codes);
-  if (G.rows) std::swap(ix->rows, G.rows);
-  ix->capacity = G.plan.prow;
-  ix->ntotal = G.ntotal;
-  // the multi-block scratch is sized by the tiles of the arena and allocated once: drop it, the next pass allocates it for the new size
-  ix->ivfm = IvfMultiScratch();
-  ix->ivfm_last_blk = 0;
-  ix->ivfm_union_valid = false;
-  if (ix->pq.m) {
-    ix->pq.tile0_h.assign(G.plan.tile0.begin(), G.plan.tile0.end());
-    ix->pq.size_h.assign(G.plan.size.begin(), G.plan.size.end());
-    ix->pq.slab_np = 0;  // (M = 256: the slab width follows the list sizes)
-    ix->pq.slab = 0;
-    ix->pq.thr.tthr.reset(), ix->pq.thr.tcnt.reset(), ix->pq.thr.tfetch.reset();
-  }
-  if (ix->sq.on) {
-    ix->sq.tile0_h.assign(G.plan.tile0.begin(), G.plan.tile0.end());
-    ix->sq.size_h.assign(G.plan.size.begin(), G.plan.size.end());
-    ix->sq.thr.tthr.reset(), ix->sq.thr.tcnt.reset(), ix->sq.thr.tfetch.reset();
-  }
-  // per-pass scratch of the compressed scans (probe offsets and partial sums of a pass over the old layout) and the hit pools
-  ix->pqs = PqScratch();
-  ix->sqs = SqScratch();
-  ix->range = RangePools();
-  // the list-order cache: dense0 is rebuilt by the next translation
-  S.ready = false;
-  S.dense0.reset();
-  S.dense0_h.clear();
+  int r = ivf_swap_in(ix, G.L, G.work, G.pq_codes, G.sq_codes, G.rows, G.plan.tile0, G.plan.size, G.plan.prow, G.ntotal);
+  if (r) return r;
   ix->grow = G.stats;
   return 0;
 }
@@ -323,6 +290,49 @@ bool bits_equal(const std::vector<T>& a, const std::vector<T>& b) {
 }
 
 }  // namespace
+
+// A layout built next to the index -- by a call that grew it (above) or shrank it (knnx_shrink.hip) -- becomes the index.  Everything
+// that caches the layout is refreshed or dropped HERE; nprobe, k_factor, the refine and threshold-scan switches and every counter stay.
+// The caller holds ix->mu and has synchronised ix->stream; the old buffers leave in the arguments (hipFree waits for the device, so a
+// search_device still queued on a caller's stream finishes on the arena it was launched on).  A payload the index does not have is null.
+int ivf_swap_in(knnx_index* ix, IvfLayout& L, DevBuf<uint4>& work, DevBuf<uint8_t>& pq_codes, DevBuf<uint8_t>& sq_codes, DevBuf<_Float16>& rows,
+                const std::vector<unsigned>& tile0_h, const std::vector<unsigned>& size_h, int64_t prow, int64_t ntotal) {
+  IdOrder& S = ix->ido;
+  std::lock_guard<std::mutex> lk(S.mu);  // a translation of ids (knnx_ivf_map_ids) reads the layout without ix->mu
+  if (S.stream) HIPCHK(hipStreamSynchronize(S.stream));
+  std::swap(ix->ivf, L);
+  std::swap(ix->ivf1.work, work);
+  if (pq_codes) std::swap(ix->pq.codes, pq_codes);
+  if (sq_codes) std::swap(ix->sq.codes, sq_codes);
+  if (rows) std::swap(ix->rows, rows);
+  ix->capacity = prow;
+  ix->ntotal = ntotal;
+  // the multi-block scratch is sized by the tiles of the arena and allocated once: drop it, the next pass allocates it for the new size
+  ix->ivfm = IvfMultiScratch();
+  ix->ivfm_last_blk = 0;
+  ix->ivfm_union_valid = false;
+  if (ix->pq.m) {
+    ix->pq.tile0_h.assign(tile0_h.begin(), tile0_h.end());
+    ix->pq.size_h.assign(size_h.begin(), size_h.end());
+    ix->pq.slab_np = 0;  // (M = 256: the slab width follows the list sizes)
+    ix->pq.slab = 0;
+    ix->pq.thr.tthr.reset(), ix->pq.thr.tcnt.reset(), ix->pq.thr.tfetch.reset();
+  }
+  if (ix->sq.on) {
+    ix->sq.tile0_h.assign(tile0_h.begin(), tile0_h.end());
+    ix->sq.size_h.assign(size_h.begin(), size_h.end());
+    ix->sq.thr.tthr.reset(), ix->sq.thr.tcnt.reset(), ix->sq.thr.tfetch.reset();
+  }
+  // per-pass scratch of the compressed scans (probe offsets and partial sums of a pass over the old layout) and the hit pools
+  ix->pqs = PqScratch();
+  ix->sqs = SqScratch();
+  ix->range = RangePools();
+  // the list-order cache: dense0 is rebuilt by the next translation
+  S.ready = false;
+  S.dense0.reset();
+  S.dense0_h.clear();
+  return 0;
+}
 
 extern "C" int knnx_ivf_append_assigned(knnx_index* ix, const uint16_t* rows_f16, int64_t n, const int32_t* lists) {
   if (ix && n > 0 && !lists) return fail(KNNX_E_ARG, "knnx_ivf_append_assigned: lists is null (nothing was added)");

@@ -1,5 +1,5 @@
 // knnx_host.h -- shared by the HOST translation units of the search half (knnx_api / knnx_range / knnx_ivf / knnx_ivfpq /
-// knnx_ivfsq / knnx_sharded .hip): the error helpers, the owners of device memory, pinned memory, streams and events, the index object
+// knnx_ivfsq / knnx_grow / knnx_shrink / knnx_sharded .hip): the error helpers, the owners of device memory, pinned memory, streams and events, the index object
 // with its state grouped by the scan that uses it, and the handful of functions one file calls in another.  The kernel
 // files include knn_kernels.h only.
 //
@@ -521,6 +521,15 @@ struct GrowStats {
   int64_t calls = 0;
 };
 
+// what the most recent knnx_ivf_remove_ids that succeeded spent (knnx_shrink.hip; knnx_ivf_remove_stats); a call that found nothing to
+// remove counts, with zeros
+struct ShrinkStats {
+  double mark_ms = 0, plan_ms = 0, move_ms = 0, ids_ms = 0;  // device time of the phases (plan includes its host round trips)
+  int64_t moved_bytes = 0;                                   // payload bytes of the survivors, every arena
+  int64_t n_removed = 0;
+  int64_t calls = 0;
+};
+
 // hit pools of the range scans, grown on demand (knnx_range.hip: range_pool_alloc)
 struct RangePools {
   DevBuf<float> s;
@@ -621,6 +630,7 @@ struct knnx_index {
   SqScratch sqs;
   IdOrder ido;
   GrowStats grow;
+  ShrinkStats shrink;
 
   // a proof-based scan that skipped its fallback (see WideScratch) says so here: 1 = rq.need / rq.gate, 2 = wide.need / wide.gate
   bool defer_fb = false;
@@ -680,6 +690,9 @@ int ivf_import_codes_locked(knnx_index* ix, uint8_t* arena, int width, const uin
                             const int32_t* pos);
 int ivf_export_codes_locked(knnx_index* ix, const uint8_t* arena, int width, const std::vector<unsigned>& tile0_h,
                             const std::vector<unsigned>& size_h, const char* family, int64_t* ids, int32_t* lists, uint8_t* codes);
+// knnx_grow.hip: the one place where a layout built next to the index is swapped in and every cache of the old one dropped
+int ivf_swap_in(knnx_index* ix, IvfLayout& L, DevBuf<uint4>& work, DevBuf<uint8_t>& pq_codes, DevBuf<uint8_t>& sq_codes, DevBuf<_Float16>& rows,
+                const std::vector<unsigned>& tile0_h, const std::vector<unsigned>& size_h, int64_t prow, int64_t ntotal);
 // knnx_ivfpq.hip
 int scan_topk_pq(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out, int64_t* I_out, hipStream_t st);
 const ThrPass& pq_thr_pass();

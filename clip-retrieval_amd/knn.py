@@ -502,6 +502,61 @@ class Mi355xIndex(_FaissShaped):
                 delattr(self, name)
         return self._grown(n_before, lists)
 
+    # ------------------------------------------------------------------ shrinking a built IVF index (include/knnx.h)
+    def _shrunk(self, kept, base):
+        """After rows were removed (kept: the old ids of the survivors in new-id order): ivf_lists / ivf_row_range follow where the index
+        carries them, and what bound the index to the folder it was built from is dropped -- the folder's rows no longer are its rows."""
+        if getattr(self, "ivf_lists", None) is not None:
+            self.ivf_lists = np.ascontiguousarray(np.asarray(self.ivf_lists, dtype=np.int32)[kept - base])
+        if getattr(self, "ivf_row_range", None) is not None:
+            self.ivf_row_range = (self.ivf_row_range[0], self.ivf_row_range[0] + len(kept))
+        for name in ("ivf_source", "embeddings_folder", "ivf_folder", "ivf_folder_files"):
+            if hasattr(self, name):
+                delattr(self, name)
+
+    def ivf_remove(self, ids):
+        """Remove rows from a BUILT IVF index of any kind: `ids` (integers, any shape) names them; entries that name no row (-1, outside
+        [id_base, id_base + ntotal)) are ignored and duplicates count once.  Ids are positional, so the survivors are RENUMBERED densely
+        in id order, as faiss' IndexFlat.remove_ids does -> kept, int64 [ntotal after]: the OLD ids of the survivors in new-id order --
+        new id id_base + i was old id kept[i].  The caller filters its embeddings and its metadata store with kept - id_base.  The
+        result is bit for bit the index a fresh build over the surviving rows gives; concurrent searches see the index before or after
+        the call; peak memory is old + new arena.  A list-ordered metadata store (ivf_old_to_new) must be exported again afterwards.
+        The index no longer belongs to the folder it was built from: save_index of an IVF-Flat or refine index then needs
+        embeddings_folder= naming a folder that holds the surviving rows.  A sharded index has no removal (the shards' row ranges would
+        shift), and an index handed to ShardedMi355xIndex must not be shrunk afterwards."""
+        ids = np.asarray(ids)
+        if ids.dtype.kind not in "iu":
+            raise TypeError(f"ivf_remove expects integer ids, got {ids.dtype}")
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        n_before = self.ntotal
+        rng = getattr(self, "ivf_row_range", None)
+        base = rng[0] if rng is not None else self._id_base
+        removed = C.c_int64(0)
+        # (an empty array still goes to the library: an index that cannot shrink refuses)
+        check(self._lib, self._lib.knnx_ivf_remove_ids(self._h, ids.ctypes.data if ids.size else None, int(ids.size), C.byref(removed)), "knnx")
+        alive = np.ones(n_before, dtype=bool)
+        o = ids - base
+        alive[o[(o >= 0) & (o < n_before)]] = False
+        kept = base + np.flatnonzero(alive).astype(np.int64)
+        if n_before - len(kept) != removed.value or len(kept) != self.ntotal:
+            raise HipLibraryError(f"ivf_remove: the library removed {removed.value} rows and holds {self.ntotal}, the ids name {n_before - len(kept)} of {n_before}")
+        if removed.value:
+            self._shrunk(kept, base)
+        return kept
+
+    def remove_ids(self, ids):
+        """faiss Index.remove_ids: ivf_remove(ids) -> the number of rows removed.  Mind that the survivors are renumbered (ivf_remove)."""
+        n_before = self.ntotal
+        return n_before - len(self.ivf_remove(ids))
+
+    def ivf_remove_stats(self):
+        """What the most recent removal spent (include/knnx.h: knnx_ivf_remove_stats): dict of mark_ms, plan_ms, move_ms, ids_ms,
+        moved_bytes, n_removed."""
+        ms = [C.c_double() for _ in range(4)]
+        mb, nr = C.c_int64(), C.c_int64()
+        check(self._lib, self._lib.knnx_ivf_remove_stats(self._h, *[C.byref(m) for m in ms], C.byref(mb), C.byref(nr)), "knnx")
+        return dict(mark_ms=ms[0].value, plan_ms=ms[1].value, move_ms=ms[2].value, ids_ms=ms[3].value, moved_bytes=mb.value, n_removed=nr.value)
+
     # ------------------------------------------------------------------ searching
     def _search_raw(self, q, k, want_r):
         n = q.shape[0]

@@ -419,8 +419,8 @@ int knnx_ivf_map_ids(knnx_index* ix, const int64_t* ids, int64_t n, int64_t* out
  * knnx_ivf_begin and knnx_ivf_end, borrowed rows -- answer KNNX_E_ARG before anything is touched; an allocation that fails answers
  * KNNX_E_NOMEM, more than 2^32 padded rows KNNX_E_UNSUPPORTED; in every case nothing was added and the index stays searchable.
  * nprobe, k_factor, the refine and threshold-scan switches and the counters are kept.  The list-ordered ids (above) change with every
- * call -- every old_to_new entry may shift -- so a list-ordered metadata store must be exported again.  Per-list slack, in-place moves,
- * removal of ids and a sharded form are not provided. */
+ * call -- every old_to_new entry may shift -- so a list-ordered metadata store must be exported again.  Per-list slack, in-place moves
+ * and a sharded form are not provided; ids are removed by the block "Shrinking a built index" below. */
 int knnx_ivf_append_assigned(knnx_index* ix, const uint16_t* rows_f16, int64_t n, const int32_t* lists);
 int knnx_ivf_append(knnx_index* ix, const uint16_t* rows_f16, int64_t n, int32_t* lists_out);
 int knnx_ivf_append_device(knnx_index* ix, const void* rows_dev_f16, int64_t n, int32_t* lists_out);
@@ -431,6 +431,45 @@ int knnx_ivf_merge_from(knnx_index* ix, knnx_index* other);
  * moved_bytes = payload bytes the move copied (the occupied tiles of every arena; idmap / inv not counted).  Any pointer may be NULL.
  * KNNX_E_STATE before the first such call. */
 int knnx_ivf_grow_stats(knnx_index* ix, double* assign_ms, double* move_ms, double* ids_ms, double* fill_ms, int64_t* moved_bytes);
+
+/* ---- Shrinking a built index: faiss remove_ids (rows a safety filter flags, near-duplicate groups, take-down requests -- what
+ * clip_back.py:326-341 filters per request because it treats the index file as frozen) ----
+ * For the same indexes as the block above: every BUILT IVF index of any kind that owns its rows.  Ids here are POSITIONAL -- inv is a dense
+ * table indexed by id - id_base, the list-ordered ids are a permutation of [0, ntotal), saved codes are kept in id order, metadata is
+ * addressed by row number -- and a removal keeps all of that true: the survivors are renumbered densely in id order, as faiss'
+ * IndexFlat.remove_ids does (faiss' IVF classes keep the old ids; on this point we differ on purpose).  After the call a surviving row with
+ * old id o has id id_base + rank(o), rank(o) = the surviving ids below o.  Inside a list the survivors keep their order.  The layout is the
+ * rule of knnx_ivf_begin applied to the new list sizes; pad rows are zero bytes in every payload and have idmap -1.  The result is, bit
+ * for bit (arena, id maps, search results, exported codes, reconstructed rows, list-ordered ids), the index knnx_ivf_begin /
+ * knnx_ivf_add_assigned / knnx_ivf_end build from the surviving rows in their original order with the same centroids, quantiser,
+ * rotation, ranges and lists; of an IVF-Flat index the bound on the row norms is taken again over the survivors.
+ *   knnx_ivf_remove_ids    ids host int64 [n], any order.  Entries that name no row -- -1, below id_base, at or above id_base + ntotal -- are
+ *                          ignored (faiss' IDSelectorBatch), duplicates count once.  n_removed (may be NULL) receives the rows removed.
+ *                          n == 0, or a call in which no id names a row, is a success that moves nothing, allocates nothing on the device
+ *                          and leaves every cache as it was.  Removing every row is legal: it leaves ntotal == 0 and the one-tile arena of
+ *                          an empty built index, every search answers with full padding, and knnx_ivf_append* works on it.  ids are
+ *                          read in chunks of 2^20 through one staging buffer.
+ * How: a flag per id is set (plain byte stores), a reduce-then-scan over the id space gives every survivor its new id (block sums scanned
+ * on the host in int64), a ballot gives every source tile its 32-bit survivor mask, one wave per list turns the masks into the new list
+ * sizes and into the destination row of every tile's first survivor, and a row-granular move copies the survivors of a source tile to
+ * ONE contiguous run of the new arena; only the pad rows are zeroed.  The phases are separate launches: no kernel waits for another
+ * workgroup.  The new sizes must add up to the survivors the id scan counted -- two independent device computations -- or the call answers
+ * KNNX_E_STATE "internal: ..." before anything is swapped.  Like a growing call it is OUT OF PLACE, all or nothing and atomic for searchers:
+ * new arena(s), idmap and inv next to the old ones (peak memory: old + new arena, plus 5 bytes per id and 8 per tile), swapped in at the
+ * end under the lock the searches hold.  A flat index, an index between knnx_ivf_begin and knnx_ivf_end, borrowed rows, ids == NULL with
+ * n > 0 and n < 0 answer KNNX_E_ARG with a message that ends in "nothing was removed", before anything is touched; an allocation that
+ * fails answers KNNX_E_NOMEM with the index as it was.  nprobe, k_factor, the refine and threshold-scan switches, the counters, centroids
+ * and quantiser are kept, and knnx_ivf_grow_stats keeps its answer.  The list-ordered ids change with every call that removes a row, so a
+ * list-ordered metadata store must be exported again -- and the caller's embeddings and metadata rows must be filtered the same way, since
+ * every id above the first removed one shifts.  An index handed to knnx_shards_adopt must not be shrunk afterwards (the shards' row ranges
+ * would shift); a sharded removal is not provided. */
+int knnx_ivf_remove_ids(knnx_index* ix, const int64_t* ids, int64_t n, int64_t* n_removed /* may be NULL */);
+/* What the most recent knnx_ivf_remove_ids that succeeded spent, for tools/ivf_remove_bench.py: device time of the mark, plan (rank scan,
+ * masks, list scan, layout; includes its host round trips), move (payload copy and pad rows) and ids (idmap / inv) phases; moved_bytes =
+ * payload bytes of the survivors over every arena; n_removed.  A call that found nothing to remove reports zeros.  Any pointer may be
+ * NULL.  KNNX_E_STATE before the first call. */
+int knnx_ivf_remove_stats(knnx_index* ix, double* mark_ms, double* plan_ms, double* move_ms, double* ids_ms, int64_t* moved_bytes,
+                          int64_t* n_removed);
 
 /* Merge P per-shard results ([P, n, k] each, already global ids) into the top-k [n, k];
  * the step after the RCCL all-gather of a row-sharded index.  Device buffers.  k <= 64: any order within a list;

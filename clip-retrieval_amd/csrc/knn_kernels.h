@@ -320,4 +320,18 @@ hipError_t launch_sq_decode(const uint8_t* codes, int d, const float* vmin, cons
 // per-column min / max of n fp16 rows (d <= 1024) -> vmin_dev / vmax_dev f32 [d]; enc: 2 d ints of device scratch
 hipError_t launch_sq_colminmax(const _Float16* X, int64_t n, int d, int* enc, float* vmin_dev, float* vmax_dev, hipStream_t st);
 
+// ---- post filter of one request on the device (knn_filter_kernels.hip; the shared arithmetic: knnx_filter_plan.h) ----
+// R f32 [n][d] -> unit rows in place over the columns [0, d_user) (one fmaf chain per row, a zero row stays zero); columns [d_user, d) <- 0.
+// d % 4 == 0, d <= 4096
+hipError_t launch_filter_normalise(float* R, int n, int d, int d_user, hipStream_t st);
+// every pair i < j < n of the unit rows E with e_i . e_j > thr (exact f32, columns ascending) -> links (i << 16 | j) in no particular
+// order; counters[FILTER_C_LINKS] (cleared by the caller) counts them all, only the first `cap` are kept.  n <= FILTER_MAX_K
+hipError_t launch_filter_links(const float* E, int n, int d, int d_user, float thr, uint32_t* links, int cap, int* counters, hipStream_t st);
+// drop[i] = KNNX_DROP_VIOLENT if the first maximum of vs[i][0..P) is entry 1 | KNNX_DROP_UNSAFE if ss[i][0] > sthr, for i < n;
+// drop[n..k) = 0.  vs / ss may be null (no such filter)
+hipError_t launch_filter_bits(const float* vs, int P, const float* ss, int S, float sthr, int n, int k, uint8_t* drop, hipStream_t st);
+// drop[i] |= KNNX_DROP_DUPLICATE for every i < n that is not the smallest member of its component under the kept links; does nothing
+// when counters[FILTER_C_LINKS] is 0 or above cap.  Writes counters[FILTER_C_ROUNDS] and counters[FILTER_C_BOUND].  One workgroup.
+hipError_t launch_filter_cc(const uint32_t* links, int cap, int* counters, int n, uint8_t* drop, hipStream_t st);
+
 }  // namespace knnx

@@ -1000,6 +1000,16 @@ extern "C" int knnx_search_dedup(knnx_index* ix, const float* q, int k, float* D
   return co_run_batch(ix, one);
 }
 
+// every kind of index, any k <= KNNX_MAX_K, host buffers; caller holds ix->mu and has set the device (knnx_search, knnx_search_filtered)
+int search_locked(knnx_index* ix, const float* q, int n, int k, float* D, int64_t* I) {
+  return (k <= KNNX_MAX_K_FAST) ? search_fast_locked(ix, q, n, k, D, I)
+         : ix->pq.m             ? (ix->pq.thr.on ? search_large_k_thr_locked(ix, pq_thr_pass(), q, n, k, D, I)
+                                                 : fail(KNNX_E_UNSUPPORTED, "k > 64 is not supported on an IVF-PQ index"))
+         : ix->sq.on            ? (ix->sq.thr.on ? search_large_k_thr_locked(ix, sq_thr_pass(), q, n, k, D, I)
+                                                 : fail(KNNX_E_UNSUPPORTED, "k > 64 is not supported on an IVF-SQ8 index"))
+                                : search_large_k_locked(ix, q, n, k, D, I);
+}
+
 extern "C" int knnx_search(knnx_index* ix, const float* q, int n, int k, float* D, int64_t* I, float* R) {
   if (!ix || (n > 0 && (!q || !D || !I)) || n < 0 || k <= 0) return fail(KNNX_E_ARG, "bad search arguments");
   if (k > KNNX_MAX_K) return fail(KNNX_E_UNSUPPORTED, "k > 131072 is not implemented");
@@ -1019,12 +1029,7 @@ extern "C" int knnx_search(knnx_index* ix, const float* q, int n, int k, float* 
   {
     std::lock_guard<std::mutex> lk(ix->mu);
     if (set_dev(ix)) return KNNX_E_HIP;
-    int r = (k <= KNNX_MAX_K_FAST) ? search_fast_locked(ix, q, n, k, D, I)
-            : ix->pq.m               ? (ix->pq.thr.on ? search_large_k_thr_locked(ix, pq_thr_pass(), q, n, k, D, I)
-                                                              : fail(KNNX_E_UNSUPPORTED, "k > 64 is not supported on an IVF-PQ index"))
-            : ix->sq.on              ? (ix->sq.thr.on ? search_large_k_thr_locked(ix, sq_thr_pass(), q, n, k, D, I)
-                                                              : fail(KNNX_E_UNSUPPORTED, "k > 64 is not supported on an IVF-SQ8 index"))
-                                     : search_large_k_locked(ix, q, n, k, D, I);
+    int r = search_locked(ix, q, n, k, D, I);
     if (r) return r;
   }
   if (R) return knnx_reconstruct(ix, I, (int64_t)n * k, R);

@@ -1,5 +1,5 @@
 // knnx_host.h -- shared by the HOST translation units of the search half (knnx_api / knnx_range / knnx_ivf / knnx_ivfpq /
-// knnx_ivfsq / knnx_grow / knnx_shrink / knnx_sharded .hip): the error helpers, the owners of device memory, pinned memory, streams and events, the index object
+// knnx_ivfsq / knnx_grow / knnx_shrink / knnx_filter / knnx_sharded .hip): the error helpers, the owners of device memory, pinned memory, streams and events, the index object
 // with its state grouped by the scan that uses it, and the handful of functions one file calls in another.  The kernel
 // files include knn_kernels.h only.
 //
@@ -24,6 +24,7 @@
 
 #include "../../include/knnx.h"
 #include "knn_kernels.h"
+#include "knnx_filter_plan.h"
 
 using namespace knnx;  // (the launchers and constants of knn_kernels.h)
 
@@ -530,6 +531,21 @@ struct ShrinkStats {
   int64_t calls = 0;
 };
 
+// device post filter of one request (knnx_filter.hip: knnx_search_filtered; sizes: filter_sizes() of knnx_filter_plan.h).  Grow-only:
+// alloc() keeps what it has when that is large enough, otherwise it replaces the WHOLE group by one sized for the request -- taking the
+// int8 copy back (malloc_or_reclaim) before it gives up -- and leaves the group EMPTY when even that fails.  Used under knnx_index::mu.
+struct FilterScratch {
+  DevBuf<float> rows;         // [k_cap][d] the gathered result rows, normalised in place
+  DevBuf<int64_t> ids;        // [k_cap]
+  DevBuf<uint32_t> links;     // [FILTER_LINK_CAP] i << 16 | j
+  DevBuf<int> counters;       // [FILTER_COUNTERS]
+  DevBuf<float> vscores;      // [k_cap][v_cap] violence scores
+  DevBuf<float> sscores;      // [k_cap][s_cap] safety scores
+  DevBuf<uint8_t> drop;       // [k_cap]
+  int k_cap = 0, v_cap = 0, s_cap = 0;
+  hipError_t alloc(struct knnx_index* ix, int k, int v_out, int s_out);  // (defined below malloc_or_reclaim)
+};
+
 // hit pools of the range scans, grown on demand (knnx_range.hip: range_pool_alloc)
 struct RangePools {
   DevBuf<float> s;
@@ -603,6 +619,7 @@ struct knnx_index {
   I8Copy i8;
   I8Scratch i8q;
   RangePools range;
+  FilterScratch filter;
   Profile prof;
   Coalescer co;
 
@@ -721,5 +738,30 @@ inline hipError_t malloc_or_reclaim(knnx_index* ix, DevBuf<T>& b, size_t n) {
   }
   return e;
 }
+
+inline hipError_t FilterScratch::alloc(knnx_index* ix, int k, int v_out, int s_out) {
+  if (rows && k <= k_cap && v_out <= v_cap && s_out <= s_cap) return hipSuccess;
+  const int kc = std::max(k, k_cap), vc = std::max(v_out, v_cap), sc = std::max(s_out, s_cap);
+  const FilterSizes z = filter_sizes(kc, ix->d, vc, sc);
+  *this = FilterScratch();  // (the old buffers go first: the new group need not fit next to them)
+  hipError_t e = malloc_or_reclaim(ix, rows, z.rows);
+  if (e == hipSuccess) e = malloc_or_reclaim(ix, ids, z.ids);
+  if (e == hipSuccess) e = malloc_or_reclaim(ix, links, z.links);
+  if (e == hipSuccess) e = malloc_or_reclaim(ix, counters, z.counters);
+  if (e == hipSuccess) e = malloc_or_reclaim(ix, vscores, z.vscores);
+  if (e == hipSuccess) e = malloc_or_reclaim(ix, sscores, z.sscores);
+  if (e == hipSuccess) e = malloc_or_reclaim(ix, drop, z.drop);
+  if (e != hipSuccess) {
+    *this = FilterScratch();
+    return e;
+  }
+  k_cap = kc, v_cap = vc, s_cap = sc;
+  return hipSuccess;
+}
+
+// postfilter.hip (the MLP handle is its own object with its own mutex; these two are what the filter asks of it)
+void knnx_mlp_shape(const knnx_mlp* m, int* d_in, int* d_out, int* n_layers, int* has_bias);
+// knnx_api.hip: the dispatch of knnx_search for host buffers with ix->mu held (no coalescing, no reconstruct)
+int search_locked(knnx_index* ix, const float* q, int n, int k, float* D, int64_t* I);
 
 #pragma GCC visibility pop

@@ -24,10 +24,10 @@ namespace {
 
 constexpr int TM = 64, TN = 64, TK = 16;
 
-// Y[n, N] = act(X[n, K] @ W[N, K]^T + b);  W row-major like torch.nn.Linear.weight
+// Y[n, N] = act(X[n, K] @ W[N, K]^T + b);  W row-major like torch.nn.Linear.weight; row r of X starts at X + r * ldx
 __global__ __launch_bounds__(256) void linear_f32_kernel(const float* __restrict__ X, const float* __restrict__ W,
                                                         const float* __restrict__ b, float* __restrict__ Y, int n, int N, int K,
-                                                        int relu) {
+                                                        int relu, int64_t ldx) {
   __shared__ float sX[TK][TM + 4];  // [k][row]: a thread reads 4 consecutive rows
   __shared__ float sW[TK][TN + 4];  // [k][col]
   const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(256) void linear_f32_kernel(const float* __restrict
       // unconditional loads from clamped coordinates, masked afterwards: behind per-element tests hipcc waits for every load
       // on its own (the pattern found in the hit re-scoring kernel)
       float xv[4], wv[4];
-      const size_t xr = (size_t)(gr < n ? gr : n - 1) * K, wr = (size_t)(gc < N ? gc : N - 1) * K;
+      const size_t xr = (size_t)(gr < n ? gr : n - 1) * (size_t)ldx, wr = (size_t)(gc < N ? gc : N - 1) * K;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int k = k0 + kq + e, kc = k < K ? k : K - 1;
@@ -173,33 +173,77 @@ extern "C" int knnx_mlp_create(int device, int n_layers, const int32_t* dims, co
   return KNNX_OK;
 }
 
+// the ping-pong activations hold n rows; caller holds m->mu and has set the device
+static int mlp_ensure_rows(knnx_mlp* m, int n) {
+  if ((size_t)n <= m->cap_rows) return KNNX_OK;
+  (void)hipFree(m->act[0]);
+  (void)hipFree(m->act[1]);
+  m->act[0] = m->act[1] = nullptr;
+  m->cap_rows = 0;
+  const size_t rows = std::max<size_t>((size_t)n, 4096);
+  MLPCHK(hipMalloc(&m->act[0], rows * m->max_dim * sizeof(float)));
+  MLPCHK(hipMalloc(&m->act[1], rows * m->max_dim * sizeof(float)));
+  m->cap_rows = rows;
+  return KNNX_OK;
+}
+
+// the layers over n rows at x (row stride ldx) on stream st; the last layer writes y_or_null [n, dims[n_layers]] when given, else
+// the activation buffer *last points at afterwards.  Caller holds m->mu.
+static int mlp_layers(knnx_mlp* m, const float* x, int64_t ldx, int n, float* y_or_null, hipStream_t st, float** last) {
+  const float* in = x;
+  int cur = 1;  // layer 0 writes act[1] (knnx_mlp_forward stages its input in act[0])
+  for (int l = 0; l < m->n_layers; ++l) {
+    const int K = m->dims[l], N = m->dims[l + 1];
+    float* out = (l + 1 == m->n_layers && y_or_null) ? y_or_null : m->act[cur];
+    hipLaunchKernelGGL(linear_f32_kernel, dim3((N + TN - 1) / TN, (n + TM - 1) / TM), dim3(256), 0, st, in, m->w[l], m->b[l], out, n, N, K,
+                       (int)m->relu[l], l == 0 ? ldx : (int64_t)K);
+    MLPCHK(hipGetLastError());
+    in = out;
+    cur ^= 1;
+    if (last) *last = out;
+  }
+  return KNNX_OK;
+}
+
 extern "C" int knnx_mlp_forward(knnx_mlp* m, const float* x_host, int n, float* y_host) {
   if (!m || n < 0 || (n > 0 && (!x_host || !y_host))) return fail(KNNX_E_ARG, "bad mlp_forward arguments");
   if (n == 0) return KNNX_OK;
   std::lock_guard<std::mutex> lk(m->mu);
   MLPCHK(hipSetDevice(m->device));
-  if ((size_t)n > m->cap_rows) {
-    (void)hipFree(m->act[0]);
-    (void)hipFree(m->act[1]);
-    m->act[0] = m->act[1] = nullptr;
-    m->cap_rows = 0;
-    const size_t rows = std::max<size_t>((size_t)n, 4096);
-    MLPCHK(hipMalloc(&m->act[0], rows * m->max_dim * sizeof(float)));
-    MLPCHK(hipMalloc(&m->act[1], rows * m->max_dim * sizeof(float)));
-    m->cap_rows = rows;
-  }
+  int r = mlp_ensure_rows(m, n);
+  if (r) return r;
   MLPCHK(hipMemcpyAsync(m->act[0], x_host, (size_t)n * m->dims[0] * sizeof(float), hipMemcpyHostToDevice, m->stream));
-  int cur = 0;
-  for (int l = 0; l < m->n_layers; ++l) {
-    const int K = m->dims[l], N = m->dims[l + 1];
-    hipLaunchKernelGGL(linear_f32_kernel, dim3((N + TN - 1) / TN, (n + TM - 1) / TM), dim3(256), 0, m->stream, m->act[cur], m->w[l],
-                       m->b[l], m->act[cur ^ 1], n, N, K, (int)m->relu[l]);
-    MLPCHK(hipGetLastError());
-    cur ^= 1;
-  }
-  MLPCHK(hipMemcpyAsync(y_host, m->act[cur], (size_t)n * m->dims[m->n_layers] * sizeof(float), hipMemcpyDeviceToHost, m->stream));
+  float* last = nullptr;
+  if ((r = mlp_layers(m, m->act[0], m->dims[0], n, nullptr, m->stream, &last))) return r;
+  MLPCHK(hipMemcpyAsync(y_host, last, (size_t)n * m->dims[m->n_layers] * sizeof(float), hipMemcpyDeviceToHost, m->stream));
   MLPCHK(hipStreamSynchronize(m->stream));
   return KNNX_OK;
+}
+
+extern "C" int knnx_mlp_forward_device(knnx_mlp* m, const float* x_dev, int64_t ld, int n, float* y_dev, void* stream) {
+  if (!m || n < 0 || (n > 0 && (!x_dev || !y_dev))) return fail(KNNX_E_ARG, "bad mlp_forward_device arguments");
+  if (ld < m->dims[0])
+    return fail(KNNX_E_ARG, "mlp_forward_device: row stride " + std::to_string(ld) + " is below the input width " + std::to_string(m->dims[0]));
+  if (n == 0) return KNNX_OK;
+  std::lock_guard<std::mutex> lk(m->mu);
+  MLPCHK(hipSetDevice(m->device));
+  hipStream_t st = stream ? (hipStream_t)stream : m->stream;
+  int r = mlp_ensure_rows(m, n);
+  if (r) return r;
+  if ((r = mlp_layers(m, x_dev, ld, n, y_dev, st, nullptr))) return r;
+  MLPCHK(hipStreamSynchronize(st));  // the activation buffers are the handle's: nobody else may start before these kernels are done
+  return KNNX_OK;
+}
+
+extern "C" int knnx_mlp_device(const knnx_mlp* m) { return m ? m->device : -1; }
+
+// (host layer, not ABI: knnx_filter.hip checks a handle's shape against the request before it launches anything)
+__attribute__((visibility("hidden"))) void knnx_mlp_shape(const knnx_mlp* m, int* d_in, int* d_out, int* n_layers, int* has_bias) {
+  *d_in = m->dims[0];
+  *d_out = m->dims[m->n_layers];
+  *n_layers = m->n_layers;
+  *has_bias = 0;
+  for (float* b : m->b) *has_bias |= b ? 1 : 0;
 }
 
 

@@ -598,6 +598,32 @@ class Mi355xIndex(_FaissShaped):
             R = np.ascontiguousarray(R[:, :, : self.d])
         return D, I, R, (pairs[: n.value].copy() if n.value <= self.DEDUP_PAIR_CAP else None)
 
+    FILTER_MAX_K = 8192
+    DROP_DUPLICATE, DROP_VIOLENT, DROP_UNSAFE = 1, 2, 4
+
+    def search_filtered(self, x, k, dedup_thr=None, violence=None, safety=None, safety_thr=0.5):
+        """One request of KnnService.knn_search with its whole post filter on the device (knnx.h: knnx_search_filtered;
+        clip_back.py:343-399): x float32 [1, d], k <= 8192 -> (D [1, k], I [1, k], drop uint8 [k], stats).  D, I are what search(x, k)
+        returns; drop[i] carries DROP_DUPLICATE (rank i is not the best-ranked member of its group of near-duplicates: normalised stored
+        rows with inner product > dedup_thr, transitively; None: no dedup), DROP_VIOLENT (`violence`: a bias-free one-layer device head
+        [P, d] over the prompt embeddings; the best-matching prompt is prompt 1) and DROP_UNSAFE (`safety`: a device head whose output 0
+        is > safety_thr).  The heads are objects with `._h` (a knnx_mlp handle) on this index's device, e.g. service.Mi355xSafetyHead.
+        stats: dict(n_valid, n_links, links_overflowed, cc_rounds); with links_overflowed the request had more than 2^20 links, NO
+        duplicate bit is set and dedup is the caller's (reconstruct_batch + a range search).  Only D, I and the k bytes travel."""
+        q = np.ascontiguousarray(self._pad(_as_queries(x, self.d)))
+        if q.shape[0] != 1:
+            raise AssertionError("search_filtered serves one query")
+        k = int(k)
+        D = np.empty((1, max(k, 1)), dtype=np.float32)
+        I = np.empty((1, max(k, 1)), dtype=np.int64)
+        drop = np.zeros(max(k, 1), dtype=np.uint8)
+        stats = (C.c_int32 * 4)()
+        check(self._lib, self._lib.knnx_search_filtered(
+            self._h, q.ctypes.data, k, self.d, 0 if dedup_thr is None else 1, C.c_float(0.0 if dedup_thr is None else dedup_thr),
+            violence._h if violence is not None else None, safety._h if safety is not None else None,  # pylint: disable=protected-access
+            C.c_float(safety_thr), D.ctypes.data, I.ctypes.data, drop.ctypes.data, C.cast(stats, C.c_void_p)), "knnx")
+        return D, I, drop, dict(n_valid=int(stats[0]), n_links=int(stats[1]), links_overflowed=int(stats[2]), cc_rounds=int(stats[3]))
+
     def i8_served(self):
         """Queries answered through the int8 first stage of the flat scans (include/knnx.h: knnx_i8_served); results are exact
         either way."""

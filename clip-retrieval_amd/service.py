@@ -67,6 +67,7 @@ class Mi355xSafetyHead:
         self.relu = [bool(r) for r in relu]
         self.dims = [self._w[0].shape[1]] + [w.shape[0] for w in self._w]
         self.input_size = self.dims[0]
+        self.device = int(device)  # where the layers live: Mi355xIndex.search_filtered runs them only beside an index of that device
         self._lib = load_library()
         n = len(pos)
         dims = (C.c_int32 * (n + 1))(*self.dims)
@@ -280,7 +281,11 @@ class KnnHotPath:
     knn.ShardedMi355xIndex), .safety_model, .violence_detector, .aesthetic_embeddings, .metadata_is_ordered_by_ivf and
     .ivf_old_to_new_mapping (None: the image index translates the ids itself)."""
 
-    def __init__(self, dedup_device=0):
+    def __init__(self, dedup_device=0, device_filter=False):
+        # device_filter: large-k requests (and small ones with a safety / violence filter) run their whole post filter beside the index
+        # (Mi355xIndex.search_filtered) when the index offers it and every active model is a device head there; off: knn_search is
+        # the general path below, line for line
+        self._device_filter = bool(device_filter)
         self._scratch = _ResidentIndexPool(dedup_device)   # dedup: the request's own result vectors
         self._prompts = {}                             # (shape, content hash) -> (the prompt array, its resident fp32 Linear layer)
         self._prompts_lock = threading.Lock()
@@ -385,6 +390,11 @@ class KnnHotPath:
         embeddings = np.ascontiguousarray(embeddings, dtype=np.float32)
         if embeddings.shape[0] == 0:
             return np.zeros(0, dtype=np.int64)
+        scores = self._prompt_head(safety_prompts).predict(embeddings, batch_size=embeddings.shape[0])
+        return np.flatnonzero(np.argmax(scores, axis=1) == 1)
+
+    def _prompt_head(self, safety_prompts):
+        """The resident bias-free Linear layer over the violence prompts (cached by content; see get_violent_items)."""
         prompts = np.ascontiguousarray(safety_prompts, dtype=np.float32)
         key = (prompts.shape, hash(prompts.tobytes()))
         with self._prompts_lock:
@@ -393,8 +403,7 @@ class KnnHotPath:
                 if len(self._prompts) >= 8:  # a service has one detector; do not grow without bound if a caller keeps swapping it
                     self._prompts.clear()
                 hit = self._prompts[key] = (prompts, Mi355xSafetyHead({"layers.0.weight": prompts}, device=self._device, relu=[False]))
-        scores = hit[1].predict(embeddings, batch_size=embeddings.shape[0])
-        return np.flatnonzero(np.argmax(scores, axis=1) == 1)
+        return hit[1]
 
     def post_filter(self, safety_model, embeddings, deduplicate, use_safety_model, use_violence_detector, violence_detector):
         """Local indices to drop: duplicates | violent | unsafe."""
@@ -429,6 +438,12 @@ class KnnHotPath:
         need_vectors = (use_safety_model and safety_model is not None) or (use_violence_detector and violence_detector is not None)
         query = np.asarray(query)
         links = None
+        if getattr(self, "_device_filter", False) and not wide:  # (getattr: a hot path made without __init__ has no switch, so it is off)
+            answer = self._knn_search_device_filter(index, query, num_result_ids, to_new, deduplicate,
+                                                    safety_model if use_safety_model else None,
+                                                    violence_detector if use_violence_detector else None)
+            if answer is not None:
+                return answer
         if wide:
             import math  # pylint: disable=import-outside-toplevel
 
@@ -473,6 +488,40 @@ class KnnHotPath:
                 drop.update(self.get_non_uniques(emb))
         if need_vectors:
             drop.update(self.post_filter(safety_model, emb, False, use_safety_model, use_violence_detector, violence_detector))
+        if drop:
+            keep &= ~np.isin(ids, ids[np.fromiter(drop, dtype=np.int64)])  # an id the filter dropped goes everywhere it occurs
+        _, first = np.unique(ids, return_index=True)                       # an id is reported once, at its best rank
+        once = np.zeros(n, dtype=bool)
+        once[first] = True
+        sel = np.flatnonzero(keep & once)
+        return list(dist[sel]), list(ids[sel] if to_new is None else to_new(ids[sel]))
+
+    def _knn_search_device_filter(self, index, query, k, to_new, deduplicate, safety_model, violence_detector):
+        """knn_search through Mi355xIndex.search_filtered, or None where the request is the general path's: nothing to filter at k <= 64
+        (the fused dedup serves that), k above the device filter's limit, an index without the method (ShardedMi355xIndex), or an
+        active model that is not a device head on the index's device.  Behind the drop bytes the assembly is the general path's: cut at
+        -1, an id the filter dropped goes everywhere it occurs, each id once, to_new.  A request with more links than the device keeps
+        re-runs dedup alone through reconstruct_batch + get_non_uniques."""
+        need_vectors = safety_model is not None or violence_detector is not None
+        if not (deduplicate or need_vectors) or not (k > 64 or need_vectors) or k > 8192 or query.shape[0] != 1:
+            return None
+        if not hasattr(index, "search_filtered"):
+            return None
+        if safety_model is not None and not (isinstance(safety_model, Mi355xSafetyHead) and safety_model.device == index.device):
+            return None
+        violence = None
+        if violence_detector is not None:
+            violence = self._prompt_head(violence_detector)
+            if violence.device != index.device:
+                return None
+        D, I, bits, stats = index.search_filtered(query, k, 0.94 if deduplicate else None, violence, safety_model, 0.5)
+        ids = I[0]
+        n = int(np.argmax(ids == -1)) if (ids == -1).any() else len(ids)
+        ids, dist = ids[:n], D[0][:n]
+        drop = set(np.flatnonzero(bits[:n]).tolist())
+        if deduplicate and stats["links_overflowed"]:
+            drop.update(self.get_non_uniques(normalized(index.reconstruct_batch(ids))))
+        keep = np.ones(n, dtype=bool)
         if drop:
             keep &= ~np.isin(ids, ids[np.fromiter(drop, dtype=np.int64)])  # an id the filter dropped goes everywhere it occurs
         _, first = np.unique(ids, return_index=True)                       # an id is reported once, at its best rank

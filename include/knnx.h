@@ -595,17 +595,61 @@ int knnx_i8_dominant(knnx_index* ix, int* cols4);
 int knnx_search_dedup(knnx_index* ix, const float* q, int k, float* D, int64_t* I, float* R_or_null, float dedup_thr,
                       int32_t* pairs, int pairs_cap, int* n_pairs);
 
+/* ---- Post filter on the device: one request of any k <= 8192 with its dedup, violence and safety filters where the rows are ---------
+ * KnnService.knn_search asks for 3 000 results with all three filters (clip_back.py:343-399).  knnx_search_filtered answers ONE query:
+ * the search, one gather of the result rows into device scratch, and the three filters there; D, I and one byte per result come back.
+ *
+ * Search:    D, I are exactly what knnx_search(ix, q, 1, k, D, I, NULL) returns for this index -- flat, IVF-Flat, IVF-PQ in all its
+ *            variants, IVF-SQ8; the compressed families keep their k > 64 rule and answer as knnx_search does while their threshold
+ *            scan is off.  n = the number of leading results with id >= 0; drop[n .. k-1] = 0.
+ * Rows:      r_i = the f32 row knnx_reconstruct returns for I[i], the same bits (IVF-PQ: decoded and back-rotated, or the refine
+ *            store's row where there is one; IVF-SQ8: decoded).
+ * Normalise: as normalized() does (clip_back.py:194-197): s_i = one fmaf chain over the columns 0 .. d_user-1 in ascending order from
+ *            +0, e_i[c] = r_i[c] / sqrtf(s_i); a row with s_i == 0 stays 0.  Columns d_user .. d-1 of an index row are the zero padding
+ *            the Python layer adds and take no part.  d_user <= d, and every MLP's input width must equal d_user: KNNX_E_ARG otherwise,
+ *            the message names both numbers.
+ * Dedup      (dedup_on != 0; clip_back.py:290-309): sim(i, j) = one fmaf chain over c ascending of e_i[c] * e_j[c] from +0 (what
+ *            v_mfma_f32_32x32x2_f32 computes).  Ranks i < j are linked iff sim > dedup_thr (strict); every rank that is not the
+ *            smallest member of its connected component gets KNNX_DROP_DUPLICATE.  The links are counted (stats->n_links), never
+ *            returned; the device keeps 2^20 of them: a request with more sets stats->links_overflowed = 1, sets NO duplicate bit at
+ *            all and still fills the other two -- the caller then takes the general path for dedup (knnx_reconstruct +
+ *            knnx_range_search_once).  Call with stats when dedup is on.
+ * Violence   (violence_or_null; clip_back.py:326-331): a bias-free one-layer knnx_mlp [P, d_user] holding the prompt embeddings;
+ *            KNNX_DROP_VIOLENT iff the FIRST maximum of the P scores of e_i is prompt 1.
+ * Safety     (safety_or_null; clip_back.py:315-325): KNNX_DROP_UNSAFE iff output 0 of the MLP on e_i is > safety_thr.
+ * Refused before anything is launched: k > KNNX_FILTER_MAX_K (KNNX_E_UNSUPPORTED, names the limit); an MLP that lives on another
+ * device than the index (KNNX_E_ARG); no filter asked for (KNNX_E_ARG: knnx_search is the call for that).
+ * The call takes the index once for search, gather and filter, on the index's stream; it is not coalesced with other requests.
+ * Deterministic: the same drop bytes for the same index and query, alone or beside other threads.  stats->cc_rounds: rounds of the
+ * connected-components kernel (0: it had nothing to do); more than n of them cannot happen and would answer KNNX_E_STATE. */
+#define KNNX_FILTER_MAX_K 8192
+#define KNNX_DROP_DUPLICATE 1
+#define KNNX_DROP_VIOLENT 2
+#define KNNX_DROP_UNSAFE 4
+typedef struct {
+  int32_t n_valid, n_links, links_overflowed, cc_rounds;
+} knnx_filter_stats;
+typedef struct knnx_mlp knnx_mlp; /* the resident fp32 MLP of the block below */
+int knnx_search_filtered(knnx_index* ix, const float* q, int k, int d_user, int dedup_on, float dedup_thr,
+                         knnx_mlp* violence_or_null, knnx_mlp* safety_or_null, float safety_thr, float* D, int64_t* I,
+                         uint8_t* drop, knnx_filter_stats* stats_or_null);
+
 /* ---- post filter: the safety head on the GPU --------------------------------------------------------
  * Replaces `safety_model.predict(embeddings, batch_size)` of clip_retrieval/clip_back.py:315-325 for a model that is a stack
  * of fp32 Linear layers with ReLU between them -- the H14 detector of clip_retrieval/h14_nsfw_model.py:16-34
  * (1024 -> 1024 -> 2048 -> 1024 -> 256 -> 128 -> 16 -> 1, Dropout = identity in eval mode).  dims: n_layers + 1 widths;
  * weights[l]: f32 [dims[l+1], dims[l]] row-major (torch.nn.Linear.weight), biases[l]: f32 [dims[l+1]] or NULL;
  * relu[l] != 0: ReLU after layer l (NULL: after every layer but the last).  fp32 FMA, f32 accumulate in k order. */
-typedef struct knnx_mlp knnx_mlp;
 int knnx_mlp_create(int device, int n_layers, const int32_t* dims, const float* const* weights, const float* const* biases,
                     const uint8_t* relu, knnx_mlp** out);
 /* x: host f32 [n, dims[0]] -> y: host f32 [n, dims[n_layers]]; synchronous; calls on one handle are serialised. */
 int knnx_mlp_forward(knnx_mlp* m, const float* x_host, int n, float* y_host);
+/* The same layers applied to n rows that are already on the handle's device: x_dev f32, row r at x_dev + r * ld (ld >= dims[0]) ->
+ * y_dev f32 [n, dims[n_layers]], left on the device.  The bits equal those of knnx_mlp_forward on the same inputs (the same kernel,
+ * a k-ordered fmaf chain from 0 plus the bias).  stream: a hipStream_t of that device, NULL: the handle's own.  Holds the handle's
+ * mutex until its kernels have completed on `stream` (the layers share the handle's activation buffers), so it is synchronous too. */
+int knnx_mlp_forward_device(knnx_mlp* m, const float* x_dev, int64_t ld, int n, float* y_dev, void* stream);
+int knnx_mlp_device(const knnx_mlp* m); /* the device the handle lives on, -1: null */
 int knnx_mlp_destroy(knnx_mlp* m);
 
 const char* knnx_last_error(void);

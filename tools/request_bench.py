@@ -17,6 +17,17 @@ The serving side alone: --serve-threads request threads, each sending one-query 
 IVF-PQ index built on the device, as clip_back's werkzeug threads do.  --ordered-by-ivf serves the same request stream with
 metadata_is_ordered_by_ivf=True: the ids are translated by the image index (Mi355xIndex.map_ids) and the metadata comes from a folder
 re-ordered by its lists.  Prints one JSON line (prefix "SERVE ").
+
+    python tools/request_bench.py --device-filter [--filter-index flat|ivfsq --rows N --ivf-rows N --nlist L --nprobe P --rounds 5 --reps 10]
+                                  [--serve-threads 64 --requests 20]
+
+The post filter of knn_search where the rows are (KnnHotPath(device_filter=True) -> Mi355xIndex.search_filtered) against the general path
+(the switch off: search_and_reconstruct + host normalisation + scratch-index dedup + the heads over host rows), in ONE process on ONE
+index: a flat --rows x 768 index or an IVF-SQ8 --ivf-rows x 1024 index with its threshold scan on, safety (H14-shaped, random weights)
+and violence models in the clip_resource.  k = 40 and 3 000, dedup alone and all three filters; --rounds rounds, the two switch
+positions alternating inside each round, --reps requests per position; per position the median request of every round, then the median
+and the spread (min .. max) of the round medians.  With --serve-threads T a further leg, labelled as such: T threads x --requests
+requests at k = 3 000 with all three filters, switch off then on.  Prints one JSON line per leg (prefix "FILTER ").
 """
 import argparse
 import base64
@@ -147,8 +158,112 @@ def serve(a):
                                  "coalesce": ix.coalesce_stats()}), flush=True)
 
 
+def device_filter(a):
+    """--device-filter: request time of knn_search with the post filter on the device against the general path (see the module text)."""
+    import threading
+    from types import SimpleNamespace
+
+    import numpy as np
+    import torch
+
+    from clip_retrieval_amd.knn import Mi355xIndex, build_ivfsq_index_device, synth_rows_device
+    from clip_retrieval_amd.service import KnnHotPath, Mi355xSafetyHead
+    from clip_retrieval_amd.synth import perturbed_queries
+
+    rng = np.random.default_rng(0)
+    if a.filter_index == "flat":
+        d = 768
+        ix = Mi355xIndex(d)
+        rows = int(min(a.rows, (torch.cuda.mem_get_info()[0] - (8 << 30)) // (d * 2)))
+        ix.synth_fill(rows, 3)
+        q = perturbed_queries(ix.reconstruct_batch(np.sort(rng.choice(rows, 64, replace=False))))
+        what = {"index": "flat", "rows": rows, "d": d}
+    else:
+        d, rows = 1024, a.ivf_rows
+
+        def fill_rows(dst, row0, count, stride):
+            synth_rows_device(dst, row0, count, d, 5, kind=1, n_clusters=4096, row_stride=stride)
+
+        ix = build_ivfsq_index_device(fill_rows, rows, d, a.nlist, nprobe=a.nprobe, niter=4, seed=0, threshold_scan=True)[0]
+        qrows = torch.empty((64, d), dtype=torch.float16, device="cuda")
+        synth_rows_device(qrows.data_ptr(), rows + 12345, 64, d, 5, kind=1, n_clusters=4096)
+        q = qrows.float().cpu().numpy()
+        q = np.ascontiguousarray(q / np.linalg.norm(q, axis=1, keepdims=True), dtype=np.float32)
+        what = {"index": "ivfsq", "rows": rows, "d": d, "nlist": a.nlist, "nprobe": a.nprobe}
+    widths, positions = [d, 1024, 2048, 1024, 256, 128, 16, 1], [0, 3, 6, 9, 12, 15, 16]
+    sd = {}
+    for j, p_ in enumerate(positions):
+        sd[f"layers.{p_}.weight"] = (rng.uniform(-1, 1, (widths[j + 1], widths[j])) * np.sqrt(3.0 / widths[j])).astype(np.float32)
+        sd[f"layers.{p_}.bias"] = (rng.uniform(-1, 1, widths[j + 1]) * 0.1).astype(np.float32)
+    prompts = rng.standard_normal((2, d)).astype(np.float32)
+    prompts /= np.linalg.norm(prompts, axis=1, keepdims=True)
+    res = SimpleNamespace(image_index=ix, text_index=ix, metadata_is_ordered_by_ivf=False, safety_model=Mi355xSafetyHead(sd, device=0),
+                          violence_detector=prompts, aesthetic_embeddings=None)
+    hp = {False: KnnHotPath(device_filter=False), True: KnnHotPath(device_filter=True)}
+    print(f"index: {what}", flush=True)
+
+    if a.serve_threads:
+        T, R, k = a.serve_threads, a.requests, 3000
+        for on in (False, True):
+            hp[on].knn_search(q[:1], "image", k, res, True, True, True)
+            lat = [[] for _ in range(T)]
+            go = threading.Barrier(T + 1)
+
+            def worker(t, on=on, lat=lat, go=go):
+                go.wait()
+                for r in range(R):
+                    t0 = time.perf_counter()
+                    hp[on].knn_search(q[(t * R + r) % 64:(t * R + r) % 64 + 1], "image", k, res, True, True, True)
+                    lat[t].append(time.perf_counter() - t0)
+                go.wait()
+
+            threads = [threading.Thread(target=worker, args=(t,)) for t in range(T)]
+            for th in threads:
+                th.start()
+            go.wait()
+            t0 = time.perf_counter()
+            go.wait()
+            wall = time.perf_counter() - t0
+            for th in threads:
+                th.join()
+            all_lat = np.sort(np.concatenate([np.asarray(x) for x in lat]))
+            print("FILTER " + json.dumps({**what, "leg": f"--serve-threads {T}", "k": k, "filters": "dedup+violence+safety", "device_filter": on,
+                                          "requests": T * R, "requests_per_s": round(T * R / wall, 1),
+                                          "p50_ms": round(float(all_lat[len(all_lat) // 2]) * 1e3, 3),
+                                          "p99_ms": round(float(all_lat[int(len(all_lat) * 0.99)]) * 1e3, 3)}), flush=True)
+        return
+
+    for k in (40, 3000):
+        for name, flags in (("dedup", (True, False, False)), ("dedup+violence+safety", (True, True, True))):
+            same = True
+            for on in (False, True):  # (first calls: kernels loaded, scratch allocated, prompt heads cached)
+                hp[on].knn_search(q[:1], "image", k, res, *flags)
+            med = {False: [], True: []}
+            for rnd in range(a.rounds):
+                for on in ((False, True) if rnd % 2 == 0 else (True, False)):
+                    ts = []
+                    for r in range(a.reps):
+                        j = (rnd * a.reps + r) % 64
+                        t0 = time.perf_counter()
+                        got = hp[on].knn_search(q[j:j + 1], "image", k, res, *flags)
+                        ts.append(time.perf_counter() - t0)
+                        if r == 0 and on:
+                            ref = hp[False].knn_search(q[j:j + 1], "image", k, res, *flags)
+                            same = same and [int(i) for i in ref[1]] == [int(i) for i in got[1]]
+                    med[on].append(float(np.median(ts)) * 1e3)
+            line = {**what, "k": k, "filters": name, "rounds": a.rounds, "reps": a.reps, "same_ids_as_the_general_path": bool(same)}
+            for on, key in ((False, "general_path_ms"), (True, "device_filter_ms")):
+                m = np.asarray(med[on])
+                line[key] = {"median": round(float(np.median(m)), 3), "min": round(float(m.min()), 3), "max": round(float(m.max()), 3)}
+            print("FILTER " + json.dumps(line), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--device-filter", action="store_true", help="measure knn_search with the post filter on the device against the general path")
+    ap.add_argument("--filter-index", choices=("flat", "ivfsq"), default="flat", help="with --device-filter: the index served")
+    ap.add_argument("--nprobe", type=int, default=64, help="with --device-filter --filter-index ivfsq")
+    ap.add_argument("--rounds", type=int, default=5, help="with --device-filter: rounds (both switch positions in each)")
     ap.add_argument("--serve-threads", type=int, default=0, help="measure the serving side alone from this many request threads (see the module text)")
     ap.add_argument("--ordered-by-ivf", action="store_true", help="with --serve-threads: serve with metadata_is_ordered_by_ivf=True")
     ap.add_argument("--ivf-rows", type=int, default=16_777_216)
@@ -161,6 +276,9 @@ def main():
     a = ap.parse_args()
     if a.ordered_by_ivf and not a.serve_threads:
         ap.error("--ordered-by-ivf needs --serve-threads")
+    if a.device_filter:
+        device_filter(a)
+        return
     if a.serve_threads:
         serve(a)
         return

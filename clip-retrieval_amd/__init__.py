@@ -12,7 +12,10 @@ from ._lib import HipLibraryError, ResidualStreamOverflow, load_library, library
 # the list-ordered ids of an IVF index under the reference's names (ivf_metadata_ordering.py, clip_back.py:629-640), resolved on first
 # use so that importing the package stays as light as it was
 _LAZY = {"get_old_to_new_mapping": "knn", "search_to_new_ids": "knn", "load_ivf_old_to_new_mapping": "service",
-         "reorder_arrow_metadata": "service"}
+         "reorder_arrow_metadata": "service",
+         # the multilingual text towers of `use_mclip` (mclip.py)
+         "BertArch": "mclip", "BertTextEncoder": "mclip", "WordPieceTokenizer": "mclip", "blob_from_distilbert_state_dict": "mclip",
+         "blob_from_xlmr_state_dict": "mclip", "random_bert_blob": "mclip", "load_sentence_transformer": "mclip", "load_mclip": "mclip"}
 
 
 def __getattr__(name):

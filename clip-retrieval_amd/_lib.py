@@ -37,6 +37,14 @@ class ClipxModelDesc(C.Structure):
     ]
 
 
+class ClipxBertDesc(C.Structure):
+    _fields_ = [
+        ("vocab", C.c_int), ("max_pos", C.c_int), ("pos_offset", C.c_int), ("width", C.c_int), ("layers", C.c_int),
+        ("heads", C.c_int), ("mlp", C.c_int), ("out_dim", C.c_int), ("dense_bias", C.c_int), ("max_len", C.c_int),
+        ("ln_eps", C.c_float),
+    ]
+
+
 # name -> (restype, argtypes): every symbol include/*.h declares
 _P = C.c_void_p
 SIGNATURES = {
@@ -194,6 +202,17 @@ SIGNATURES = {
     "clipx_layernorm_device": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
     "clipx_rowstats_device": (C.c_int, [C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_float, _P]),
     "clipx_tail_device": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P]),
+    "clipx_bert_blob_floats": (C.c_size_t, [C.POINTER(ClipxBertDesc)]),
+    "clipx_bert_create": (C.c_int, [C.POINTER(ClipxBertDesc), _P, C.c_size_t, C.c_int, C.POINTER(_P)]),
+    "clipx_bert_destroy": (None, [_P]),
+    "clipx_bert_out_dim": (C.c_int, [_P]),
+    "clipx_bert_encode": (C.c_int, [_P, _P, _P, C.c_int, _P, _P]),
+    "clipx_bert_encode_device": (C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P]),
+    "clipx_bert_range_check": (C.c_int, [_P, _P]),
+    "clipx_bert_embed_device": (C.c_int, [C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P,
+                                          C.c_int, C.c_int, C.c_float, _P]),
+    "clipx_postln_f16_device": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_float, _P]),
+    "clipx_bert_pool_device": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "clipx_profile_enable": (C.c_int, [_P, C.c_int]),
     "clipx_profile_get": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "clipx_profile_events": (C.c_int, [_P]),

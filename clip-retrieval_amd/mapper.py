@@ -40,10 +40,7 @@ class ClipMapper:
         clip_cache_path=None,
         device=0,
     ):
-        del use_jit, mclip_model  # no TorchScript on this path; mclip is refused below
-        if use_mclip:
-            raise NotImplementedError("use_mclip needs sentence-transformers' multilingual text tower; "
-                                      "only the CLIP towers are accelerated (SURVEY 2.2: out of scope)")
+        del use_jit  # no TorchScript on this path
         self.enable_image = enable_image
         self.enable_text = enable_text
         self.enable_metadata = enable_metadata
@@ -59,6 +56,14 @@ class ClipMapper:
                 ids[:, 0], ids[:, 1] = arch.vocab - 2, arch.vocab - 1
                 self._enc.encode_text(ids)
             self._enc._warm = True  # pylint: disable=protected-access
+        # use_mclip (mapper.py:44-47): the text side is the multilingual tower's `.encode(item["text"])`, float32, normalised in numpy
+        # (mapper.py:62-63); the image side is unchanged.  `mclip_model`: a local sentence-transformers folder, or its name under
+        # clip_cache_path (mclip.load_sentence_transformer; nothing is fetched)
+        self._mclip = None
+        if use_mclip and enable_text:
+            from .mclip import load_sentence_transformer  # pylint: disable=import-outside-toplevel
+
+            self._mclip = load_sentence_transformer(mclip_model, clip_cache_path, device)
 
     def _encode_images(self, item):
         """`image_tensor` (the reference's batch: f32 NCHW, or uint8 NHWC crops) or `image_raw` (decoded sources of any size:
@@ -66,6 +71,11 @@ class ClipMapper:
         if "image_raw" in item:
             return self._enc.encode_image_raw(item["image_raw"])
         return self._enc.encode_image(item["image_tensor"])
+
+    def _encode_texts(self, item):
+        if self.use_mclip:
+            return normalized(self._mclip.encode(item["text"]))  # float32, as SentenceTransformer.encode + mapper.py:63 leave it
+        return self._enc.encode_text(item["text_tokens"])
 
     def submit(self, item):
         """Stage the batch and enqueue its upload + kernels (clipx_encode_*_async); returns a handle for collect().
@@ -75,7 +85,7 @@ class ClipMapper:
         try:
             if self.enable_image and "image_raw" not in item and len(item["image_tensor"]) <= self._enc.max_batch:
                 h["img"] = self._enc.submit_image(item["image_tensor"])  # (decoded sources: resized + encoded in collect())
-            if self.enable_text and len(item["text_tokens"]) <= self._enc.max_batch:
+            if self.enable_text and not self.use_mclip and len(item["text_tokens"]) <= self._enc.max_batch:
                 h["txt"] = self._enc.submit_text(item["text_tokens"])
         except BaseException:
             self.discard(h)  # a half-submitted batch must not keep a staging slot of the (cached, long-lived) encoder
@@ -100,7 +110,7 @@ class ClipMapper:
             image_embs = self._enc.collect(h["img"]) if h["img"] is not None else self._encode_images(item)
             image_filename = item["image_filename"]
         if self.enable_text:
-            text_embs = self._enc.collect(h["txt"]) if h["txt"] is not None else self._enc.encode_text(item["text_tokens"])
+            text_embs = self._enc.collect(h["txt"]) if h["txt"] is not None else self._encode_texts(item)
             text = item["text"]
         if self.enable_metadata:
             metadata = item["metadata"]
@@ -118,7 +128,7 @@ class ClipMapper:
             image_embs = self._encode_images(item)
             image_filename = item["image_filename"]
         if self.enable_text:
-            text_embs = self._enc.encode_text(item["text_tokens"])
+            text_embs = self._encode_texts(item)
             text = item["text"]
         if self.enable_metadata:
             metadata = item["metadata"]

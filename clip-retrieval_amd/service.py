@@ -296,10 +296,14 @@ class KnnHotPath:
     def compute_query(self, clip_resource, text_input, image_input, image_url_input, embedding_input, use_mclip=False,
                       aesthetic_score=None, aesthetic_weight=None):
         """fp32 [1, d] query.  Exactly one of the inputs is used, in the reference's order of precedence."""
-        if use_mclip:
-            raise NotImplementedError("mclip (sentence-transformers) is not part of the accelerated path")
-        feats = None
-        if text_input:
+        feats = query = None
+        if text_input and use_mclip:
+            # clip_back.py:222-224: the multilingual tower's own callable (mclip.load_mclip), normalised in numpy, float32
+            fn = getattr(clip_resource, "model_txt_mclip", None)
+            if fn is None:
+                raise NotImplementedError("use_mclip was requested but the clip resource has no model_txt_mclip (mclip.load_mclip)")
+            query = np.asarray(normalized(np.asarray(fn(text_input), dtype=np.float32)), dtype=np.float32).reshape(1, -1)
+        elif text_input:
             feats = clip_resource.model.encode_text(clip_resource.tokenizer([text_input]))
         elif image_input is not None:
             import base64  # pylint: disable=import-outside-toplevel
@@ -314,9 +318,9 @@ class KnnHotPath:
         if feats is not None:
             # the encoder already returns unit-norm fp32 rows; dividing again keeps the reference's exact contract for any model
             query = (feats / feats.norm(dim=-1, keepdim=True)).cpu().float().numpy()
-        elif embedding_input is not None:
+        elif query is None and embedding_input is not None:
             query = np.asarray(embedding_input, dtype=np.float32)[None, :]
-        else:
+        elif query is None:
             return None
         aest = getattr(clip_resource, "aesthetic_embeddings", None)
         if aest is not None and aesthetic_score is not None:

@@ -236,6 +236,72 @@ int clipx_rowstats_device(int device, const void* x16, int is_f16, float* rstd, 
 int clipx_tail_device(int device, const void* x_f16, const float* gamma, const float* beta, const void* proj_bf16, uint16_t* out_f16,
                       float* out_f32_or_null, float* scratch, int B, int d, int E, float eps, int rows_per_workgroup, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Multilingual text towers (the reference's `use_mclip`: clip_inference/mapper.py:44-47, 62-63 and clip_back.py:222-224, 837-859).
+ * One family: a post-LN, bidirectional, padding-masked BERT encoder -> masked mean pooling -> one dense layer -> unit L2 norm.
+ *   x = LN_emb(word[id] + pos[pos_offset + t]);  per layer: x = LN_att(x + out_proj(attention(qkv(x)))), x = LN_out(x + fc2(gelu(fc1(x))))
+ *   y = dense(mean over the sample's tokens of x) (+ bias);  out = y / |y|
+ * DistilBERT multilingual (sentence-transformers/clip-ViT-B-32-multilingual-v1): 6 layers, width 768, 12 heads, mlp 3072, vocab
+ * 119 547, 512 positions, eps 1e-12, dense 768 -> 512 without bias.  XLM-R large (M-CLIP XLM-Roberta-Large-Vit-L-14 / -Vit-B-32): 24
+ * layers, width 1024, 16 heads, mlp 4096, vocab 250 002, 514 positions from 2 on, eps 1e-5, dense 1024 -> 768 or 512 with bias.
+ * (Shapes recalled from memory of the published configurations; a loader takes the true values from the checkpoint's config.json.)
+ * Arithmetic: the residual stream is IEEE fp16 and every LayerNorm rewrites it in place from fp32 statistics; QKV and fc1 read it as
+ * fp16 MFMA operands, out_proj and fc2 run on bf16 operands and add into it in fp32 (epilogue 6); the pooled mean, the dense layer
+ * (f32 weights) and the norm are fp32.  erf-GELU.  Head dimension 64 and at most 128 tokens per text (the ragged attention kernels). */
+typedef struct clipx_bert clipx_bert;
+typedef struct clipx_bert_desc {
+  int vocab;      /* 119547 | 250002 */
+  int max_pos;    /* rows of the position table: 512 | 514 */
+  int pos_offset; /* position row of token 0: 0 | 2 (XLM-R: padding_idx + 1) */
+  int width;      /* 768 | 1024: a multiple of 128, at most 2048 */
+  int layers;     /* 6 | 24 */
+  int heads;      /* 12 | 16: width / heads must be 64 */
+  int mlp;        /* 3072 | 4096: a multiple of 128 */
+  int out_dim;    /* 512 | 768: rows of the dense layer */
+  int dense_bias; /* 0 | 1 */
+  int max_len;    /* tokens per text, at most 128; pos_offset + max_len <= max_pos */
+  float ln_eps;   /* 1e-12 | 1e-5 */
+} clipx_bert_desc;
+
+/* Number of floats in the weight blob for `desc`.  Blob order, all row-major, torch `nn.Linear` [out, in] weights:
+ *   word embeddings [vocab, width]; position table [max_pos, width] (XLM-R: its single token-type row already added to every row);
+ *   embedding LN {w, b}; per layer { in_proj [3 width, width] (q | k | v), its bias [3 width]; out_proj {w [width, width], b};
+ *   attention LN {w, b}; fc1 {w [mlp, width], b}; fc2 {w [width, mlp], b}; output LN {w, b} }; dense weight [out_dim, width];
+ *   dense bias [out_dim] when dense_bias. */
+size_t clipx_bert_blob_floats(const clipx_bert_desc* desc);
+/* CLIPX_E_UNSUPPORTED: head dimension other than 64, max_len > 128, a width that is not a multiple of 128 or above 2048, an mlp width
+ * that is not a multiple of 128.  The blob is consumed during the call. */
+int clipx_bert_create(const clipx_bert_desc* desc, const float* blob, size_t blob_floats, int device, clipx_bert** out);
+void clipx_bert_destroy(clipx_bert* h);
+int clipx_bert_out_dim(const clipx_bert* h);
+
+/* ids: host int32 [B, max_len], left-aligned; only the first lens[b] ids of row b are read (the attention mask of the reference's
+ * tokenizers is 1 on a prefix).  lens: host int32 [B], each in 1 .. max_len (CLIPX_E_ARG otherwise: nothing is launched).
+ * out_f32: host [B, out_dim] unit-norm rows; out_f16_or_null: their IEEE fp16 rounding.  Any B >= 1 (chunked internally).
+ * CLIPX_E_RANGE when the fp16 residual stream overflowed (the outputs of the call must be discarded).  Calls on one handle serialise. */
+int clipx_bert_encode(clipx_bert* h, const int32_t* ids, const int32_t* lens, int B, float* out_f32, uint16_t* out_f16_or_null);
+/* The same with ids and outputs resident in HBM, asynchronous on `stream` (NULL = the handle's stream); lens_host as above, read
+ * during the call.  clipx_bert_range_check synchronises `stream` and reports / clears the range flag of the calls since the last check. */
+int clipx_bert_encode_device(clipx_bert* h, const int32_t* ids_dev, const int32_t* lens_host, int B, float* out_f32_dev,
+                             uint16_t* out_f16_dev_or_null, void* stream);
+int clipx_bert_range_check(clipx_bert* h, void* stream);
+
+/* The three kernels of the family in isolation (device pointers), for per-kernel parity tests.
+ * embed: ids int32, offs / lens int32 [B] (sample b owns the packed rows offs[b] .. offs[b] + lens[b] - 1 of out, IEEE fp16
+ *   [rows, d]); ids_stride > 0: ids is [B, ids_stride] and only the first lens[b] of a row are read; 0: ids is packed like the rows.
+ *   T = the longest length; row offs[b] + t = LN(word[id] + pos[pos_offset + t]) gamma + beta; an id outside [0, vocab) is clamped.
+ *   CLIPX_E_ARG unless 1 <= T, pos_offset + T <= max_pos.  d: a multiple of 128, at most 2048 (here and in postln).
+ * postln: x16 IEEE fp16 [M, d] in place, fp32 two-pass statistics; a row of equal elements gives exactly fp16(beta).
+ * pool: x16 IEEE fp16 packed rows; y_raw f32 [B, E] receives W mean(rows) (+ bias) (W f32 [E, d], fp32 accumulation), out_f32 [B, E]
+ *   = y / |y| (|y| = 0 -> 1), out_f16_or_null its fp16 rounding.  d: a multiple of 32, at most 2048. */
+int clipx_bert_embed_device(int device, const int32_t* ids, int ids_stride, const int32_t* offs, const int32_t* lens, int B, int T,
+                            int rows, const float* word, const float* pos, int pos_offset, int max_pos, const float* gamma,
+                            const float* beta, void* out_f16, int d, int vocab, float eps, void* stream);
+int clipx_postln_f16_device(int device, void* x16, const float* gamma, const float* beta, int M, int d, float eps, void* stream);
+int clipx_bert_pool_device(int device, const void* x16, const int32_t* offs, const int32_t* lens, const float* W,
+                           const float* bias_or_null, float* y_raw, float* out_f32, uint16_t* out_f16_or_null, int B, int d, int E,
+                           void* stream);
+
 /* Live per-kernel timing for bench.py: launches of the enabled kinds are bracketed by hipEvents on
  * their stream.  kind: 0 gemm, 1 attention, 2 layernorm, 3 other.  on: 0 off, 1 all kinds, else a bit
  * mask with bit (kind + 1): 2 = GEMMs only, 4 | 8 | 16 = everything but the GEMMs.  get() sums and resets. */

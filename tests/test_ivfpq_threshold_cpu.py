@@ -186,7 +186,7 @@ class _StubLib:
 
 
 def _begin_with_stub(monkeypatch, **kw):
-    from clip_retrieval_amd import knn
+    from clip_retrieval_amd import knn, knn_build
 
     lib = _StubLib()
 
@@ -203,7 +203,7 @@ def _begin_with_stub(monkeypatch, **kw):
         k_factor = 1
         pq_threshold_scan = knn.Mi355xIndex.pq_threshold_scan
 
-    monkeypatch.setattr(knn, "Mi355xIndex", StubIndex)
+    monkeypatch.setattr(knn_build, "Mi355xIndex", StubIndex)  # (where _ivfpq_begin looks the class up)
     cent = np.zeros((4, 64), np.float16)
     knn._ivfpq_begin(64, 4, 16, cent, np.zeros((16, 256, 4), np.float32), np.ones(4, np.int64), 0, 0, **kw)  # pylint: disable=protected-access
     return [c for c in lib.calls if c[0] == "knnx_ivfpq_set_threshold_scan"], [c[0] for c in lib.calls]

@@ -48,7 +48,7 @@ def test_build_functions_take_threshold_scan():
 
 def test_ivfsq_begin_passes_the_switch(monkeypatch):
     """_ivfsq_begin switches a new index on when asked and calls nothing for it otherwise."""
-    from clip_retrieval_amd import knn
+    from clip_retrieval_amd import knn, knn_build
 
     calls = []
 
@@ -66,8 +66,8 @@ def test_ivfsq_begin_passes_the_switch(monkeypatch):
 
         sq_threshold_scan = property(lambda self: False, lambda self, v: calls.append(v))
 
-    monkeypatch.setattr(knn, "Mi355xIndex", Fake)
-    monkeypatch.setattr(knn, "check", lambda lib, rc, which: None)
+    monkeypatch.setattr(knn_build, "Mi355xIndex", Fake)  # (where _ivfsq_begin and _ivf_begin look the names up)
+    monkeypatch.setattr(knn_build, "check", lambda lib, rc, which: None)
     cent, sizes = np.zeros((2, 256), np.float16), np.array([1, 2])
     knn._ivfsq_begin(256, 2, cent, (np.zeros(256), np.zeros(256)), sizes, 0, 0)  # pylint: disable=protected-access
     assert calls == []

@@ -223,6 +223,41 @@ def blob_from_checkpoint(path: str, arch: ClipArch) -> np.ndarray:
 # ----------------------------------------------------------------------------------------------
 # the encoder object
 # ----------------------------------------------------------------------------------------------
+def resize_crop_device(lib, device, S, raw, stream=None, jpeg=None):
+    """The device half of a reader built on DecodeRgbU8, without a model: `raw` ({"pixels", "offsets", "hw"}: reader._collate) ->
+    uint8 [B, S, S, 3] torch tensor on GPU `device`, bit-identical to Pillow's bicubic resize + centre crop.  With `jpeg` (the batch's
+    `image_jpeg`: {"coefs", "descs", "slots"}) the images of `slots` are first decoded from their DCT coefficients into the bytes
+    `raw` reserves for them (clipx_jpeg_pixels_device, bit-identical to Pillow's decode), on the same stream.  A batch that holds
+    coefficients only uploads no pixel at all."""
+    import torch  # pylint: disable=import-outside-toplevel
+
+    dev = torch.device("cuda", device)
+    B = int(raw["hw"].shape[0])
+    offsets = np.ascontiguousarray(raw["offsets"], dtype=np.int64)
+    hw = np.ascontiguousarray(raw["hw"], dtype=np.int32)
+    st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    coefs = None
+    if jpeg is not None and len(jpeg["slots"]):
+        from .jpeg import pixels_device  # pylint: disable=import-outside-toplevel
+
+        slots = np.asarray(jpeg["slots"], dtype=np.int64)
+        if not np.array_equal(hw[slots], np.stack([jpeg["descs"]["height"], jpeg["descs"]["width"]], 1)):
+            raise ValueError("image_jpeg descriptors do not match the sizes image_raw reserves for their slots")
+        if len(slots) == B:
+            src = torch.empty(raw["pixels"].numel(), dtype=torch.uint8, device=dev)
+        else:
+            src = raw["pixels"].to(dev, non_blocking=True)
+        coefs = jpeg["coefs"].to(dev, non_blocking=True)
+        pixels_device(device, coefs, jpeg["descs"], src, offsets[slots], st, lib)
+    else:
+        src = raw["pixels"].to(dev, non_blocking=True)
+    out = torch.empty((B, S, S, 3), dtype=torch.uint8, device=dev)
+    check(lib, lib.clipx_resize_crop_u8_device(device, C.c_void_p(src.data_ptr()), offsets.ctypes.data, hw.ctypes.data,
+                                               B, S, C.c_void_p(out.data_ptr()), C.c_void_p(st) if st else None), "clipx")
+    out._clipx_src = (src, coefs)  # the kernels read these asynchronously: keep them alive as long as the result
+    return out
+
+
 class ClipEncoder:
     """One CLIP model resident on one GPU.  `encode_*` return fresh fp16 numpy arrays (unit L2 norm)."""
 
@@ -292,25 +327,14 @@ class ClipEncoder:
         return out
 
     # ---- decoded sources of any size: resize + centre crop on the GPU (csrc/preprocess.hip), then the image tower
-    def resize_crop_device(self, raw, stream=None):
+    def resize_crop_device(self, raw, stream=None, jpeg=None):
         """`raw` = {"pixels": uint8 1-D torch tensor (page-locked or not) with the packed RGB sources, "offsets": int64 [B],
         "hw": int32 [B, 2]} (reader._collate) -> uint8 [B, S, S, 3] torch tensor on this encoder's GPU, bit-identical to
-        Pillow's bicubic resize + centre crop (the reference's image_transform, reader.py:83,87)."""
-        import torch  # pylint: disable=import-outside-toplevel
+        Pillow's bicubic resize + centre crop (the reference's image_transform, reader.py:83,87).  `jpeg` (the batch's
+        `image_jpeg`, or None): images that travel as DCT coefficients are decoded into their slots of `raw` on the GPU first."""
+        return resize_crop_device(self._lib, self.device, self.arch.image_size, raw, stream, jpeg)
 
-        dev = torch.device("cuda", self.device)
-        B, S = int(raw["hw"].shape[0]), self.arch.image_size
-        src = raw["pixels"].to(dev, non_blocking=True)
-        offsets = np.ascontiguousarray(raw["offsets"], dtype=np.int64)
-        hw = np.ascontiguousarray(raw["hw"], dtype=np.int32)
-        out = torch.empty((B, S, S, 3), dtype=torch.uint8, device=dev)
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        check(self._lib, self._lib.clipx_resize_crop_u8_device(self.device, C.c_void_p(src.data_ptr()), offsets.ctypes.data, hw.ctypes.data,
-                                                               B, S, C.c_void_p(out.data_ptr()), C.c_void_p(st) if st else None), "clipx")
-        out._clipx_src = src  # the kernel reads `src` asynchronously: keep it alive as long as the result
-        return out
-
-    def encode_image_raw(self, raw) -> np.ndarray:
+    def encode_image_raw(self, raw, jpeg=None) -> np.ndarray:
         """fp16 [B, E] unit-norm rows from decoded sources (see resize_crop_device): upload once, resize / crop / normalise and
         encode on the GPU.  Everything is ordered on one side stream of this encoder (a NULL stream handle would make the
         library fall back to its own stream and lose the ordering against the resize kernel)."""
@@ -321,7 +345,7 @@ class ClipEncoder:
             self._raw_stream = torch.cuda.Stream(dev)
         s = self._raw_stream
         with torch.cuda.stream(s):
-            u8 = self.resize_crop_device(raw, s.cuda_stream)
+            u8 = self.resize_crop_device(raw, s.cuda_stream, jpeg)
             out = torch.empty((u8.shape[0], self.embed_dim), dtype=torch.float16, device=dev)
             self.encode_image_device(u8.data_ptr(), u8.shape[0], PIX_U8_NHWC, out.data_ptr(), None, s.cuda_stream)
             host = torch.empty(out.shape, dtype=torch.float16, pin_memory=True)

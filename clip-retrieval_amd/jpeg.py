@@ -1,0 +1,104 @@
+"""Baseline JPEG decode in two stages: the host half of the binding.
+
+`entropy()` runs the entropy stage of lib/libclipx.so (csrc/jpegx_entropy.h: markers + Huffman -> int16 DCT coefficients) on one
+file's bytes.  It makes no HIP call, so the readers' decode processes use it without a GPU.  A file outside the accepted class --
+or one that does not parse cleanly -- is DEFERRED (`None`): the caller decodes it with Pillow as before.  `pixels_device()` is the
+device half: records -> packed RGB, bit-identical to Pillow (csrc/jpeg_kernels.hip).
+"""
+
+import ctypes as C
+
+import numpy as np
+
+from ._lib import check, load_library
+
+# clipx_jpeg_desc of include/clipx.h, 64 bytes
+JPEG_DESC = np.dtype([("width", "<i4"), ("height", "<i4"), ("ncomp", "<i4"), ("hs", "<i4"), ("vs", "<i4"), ("bw", "<i4", (3,)),
+                      ("bh", "<i4", (3,)), ("blocks", "<i4"), ("restart", "<i4"), ("pad", "<i4"), ("coef_off", "<i8")])
+assert JPEG_DESC.itemsize == 64
+TABLE_BYTES = 3 * 64 * 2  # the three quantisation tables at the head of a record
+DEFERRED, TAKEN = 0, 1
+
+
+def record_bytes(desc):
+    return TABLE_BYTES + int(desc["blocks"]) * 128
+
+
+def probe(data, max_side=8192, lib=None):
+    """(descriptor, record bytes) of a file of the accepted class, from its markers up to the SOF; None = deferred."""
+    lib = lib or load_library()
+    desc = np.zeros(1, dtype=JPEG_DESC)
+    need = C.c_size_t(0)
+    buf = bytes(data)
+    rc = lib.clipx_jpeg_probe_host(buf, len(buf), int(max_side), desc.ctypes.data, C.byref(need))
+    if rc < 0:
+        check(lib, rc, "clipx")
+    return (desc, need.value) if rc == TAKEN else None
+
+
+def entropy_packed(data, max_side=8192, lib=None):
+    """One uint8 array [64 bytes of descriptor | record] of a file of the accepted class -- the form in which a sample travels from
+    a decode process to the batch (`image_jpeg` of reader._decode_sample) -- or None = deferred."""
+    lib = lib or load_library()
+    buf = bytes(data)
+    got = probe(buf, max_side, lib)
+    if got is None:
+        return None
+    need = got[1]
+    packed = np.empty(JPEG_DESC.itemsize + need, dtype=np.uint8)
+    rc = lib.clipx_jpeg_entropy_host(buf, len(buf), int(max_side), packed.ctypes.data, packed.ctypes.data + JPEG_DESC.itemsize, need)
+    if rc < 0:
+        check(lib, rc, "clipx")
+    return packed if rc == TAKEN else None
+
+
+def unpack(packed):
+    """(descriptor [1] of JPEG_DESC, record) views of an entropy_packed() array."""
+    return packed[:JPEG_DESC.itemsize].view(JPEG_DESC), packed[JPEG_DESC.itemsize:]
+
+
+def entropy(data, max_side=8192, lib=None):
+    """(descriptor [1] of JPEG_DESC, record uint8 [record_bytes]) of a file of the accepted class; None = deferred."""
+    packed = entropy_packed(data, max_side, lib)
+    return None if packed is None else unpack(packed)
+
+
+def pack_records(packed, pin=False):
+    """The entropy_packed() arrays of a batch in ONE (page-locked) byte buffer, each on a 16-byte boundary -> (torch uint8 buffer,
+    descriptors [n] with coef_off pointing at each record)."""
+    import torch  # pylint: disable=import-outside-toplevel
+
+    sizes = np.asarray([(r.size + 15) & ~15 for r in packed], dtype=np.int64)
+    starts = np.zeros(len(packed), dtype=np.int64)
+    np.cumsum(sizes[:-1], out=starts[1:])
+    buf = torch.empty(int(sizes.sum()), dtype=torch.uint8, pin_memory=bool(pin))
+    flat = buf.numpy()
+    for r, o in zip(packed, starts):
+        flat[o:o + r.size] = r
+    descs = np.stack([r[:JPEG_DESC.itemsize] for r in packed]).view(JPEG_DESC).reshape(-1)
+    descs["coef_off"] = starts + JPEG_DESC.itemsize
+    return buf, descs
+
+
+def pixels_device(device, coefs_dev, descs, pixels_dev, offsets, stream=None, lib=None):
+    """Run the pixel stage: image i of `descs` (its record at descs[i].coef_off of the device tensor `coefs_dev`) becomes packed RGB
+    at byte offsets[i] of the device tensor `pixels_dev`.  Asynchronous on `stream` (a hipStream_t value; None: torch's current).
+    Both tensors' extents are checked here: the C entry point takes bare pointers."""
+    import torch  # pylint: disable=import-outside-toplevel
+
+    lib = lib or load_library()
+    descs = np.ascontiguousarray(descs, dtype=JPEG_DESC)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    if offsets.shape != (descs.shape[0],):
+        raise ValueError("one pixel offset per descriptor")
+    if coefs_dev.dtype != torch.uint8 or pixels_dev.dtype != torch.uint8:
+        raise ValueError("coefficient and pixel buffers are uint8 tensors")
+    rec_end = descs["coef_off"] + TABLE_BYTES + descs["blocks"].astype(np.int64) * 128
+    if descs.size and (descs["coef_off"].min() < 0 or descs["blocks"].min() < 0 or rec_end.max() > coefs_dev.numel()):
+        raise ValueError("a JPEG record lies outside the coefficient buffer")
+    pix_end = offsets + descs["height"].astype(np.int64) * descs["width"] * 3
+    if descs.size and (offsets.min() < 0 or min(descs["height"].min(), descs["width"].min()) < 1 or pix_end.max() > pixels_dev.numel()):
+        raise ValueError("a decoded image lies outside the pixel buffer")
+    st = stream if stream is not None else torch.cuda.current_stream(torch.device("cuda", device)).cuda_stream
+    check(lib, lib.clipx_jpeg_pixels_device(device, C.c_void_p(coefs_dev.data_ptr()), descs.ctypes.data, descs.shape[0],
+                                            C.c_void_p(pixels_dev.data_ptr()), offsets.ctypes.data, C.c_void_p(st) if st else None), "clipx")

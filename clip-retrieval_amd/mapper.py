@@ -67,9 +67,10 @@ class ClipMapper:
 
     def _encode_images(self, item):
         """`image_tensor` (the reference's batch: f32 NCHW, or uint8 NHWC crops) or `image_raw` (decoded sources of any size:
-        resize + centre crop on the GPU too, reader.decode_rgb_u8)."""
+        resize + centre crop on the GPU too, reader.decode_rgb_u8; with `image_jpeg` beside it, some of them still as DCT
+        coefficients: reader.DecodeRgbU8(gpu_jpeg=True))."""
         if "image_raw" in item:
-            return self._enc.encode_image_raw(item["image_raw"])
+            return self._enc.encode_image_raw(item["image_raw"], item.get("image_jpeg"))
         return self._enc.encode_image(item["image_tensor"])
 
     def _encode_texts(self, item):

@@ -75,13 +75,33 @@ class DecodeRgbU8:
     clip_preprocess_u8) resizes in the image's own mode and converts afterwards (CLIP's `_transform`: Resize, CenterCrop,
     `_convert_image_to_rgb`).  Those images, and sources beyond what the kernel takes (a down-scale above ~30 x or a row that does
     not fit its LDS staging: CLIPX_E_UNSUPPORTED would otherwise abort the whole partition), go through the host transform here
-    and travel as a ready size x size crop, which the GPU resample passes through unchanged."""
+    and travel as a ready size x size crop, which the GPU resample passes through unchanged.
+
+    gpu_jpeg (off by default): baseline JPEGs are not decoded to pixels here either.  The decode process runs only the entropy stage
+    (markers + Huffman, csrc/jpegx_entropy.h) and the sample travels as `image_jpeg`, its DCT coefficients; inverse DCT, chroma
+    upsampling and colour conversion run on the GPU (csrc/jpeg_kernels.hip), bit-identical to Pillow, into the image's slot of the
+    `image_raw` buffer.  Every file outside that class (progressive, CMYK, other formats, anything that does not parse cleanly) is
+    deferred to the Pillow branch above, error handling included."""
 
     raw_images = True  # readers: collate as `image_raw`, not as a stacked `image_tensor`
     GPU_MODES = ("RGB", "L")
+    gpu_jpeg = False  # (class default: instances pickled before the switch existed stay off)
 
-    def __init__(self, size=224, max_side=8192, max_downscale=16):
+    def __init__(self, size=224, max_side=8192, max_downscale=16, gpu_jpeg=False):
         self.size, self.max_side, self.max_downscale = size, max_side, max_downscale
+        self.gpu_jpeg = bool(gpu_jpeg)
+
+    def entropy(self, data):
+        """[descriptor | record] (jpeg.entropy_packed) of a file the GPU decodes, None for one that stays with Pillow -- deferred by
+        the entropy stage, or a source `__call__` would hand to the host transform."""
+        from . import jpeg  # pylint: disable=import-outside-toplevel
+
+        if not isinstance(data, (bytes, bytearray, memoryview)):
+            return None
+        got = jpeg.probe(data, self.max_side)
+        if got is None or min(int(got[0][0]["width"]), int(got[0][0]["height"])) > self.max_downscale * self.size:
+            return None
+        return jpeg.entropy_packed(data, self.max_side)
 
     def __call__(self, image):
         w, h = image.size
@@ -183,18 +203,35 @@ def _collate(samples, enable_image, enable_text, enable_metadata, pin):
     import torch  # pylint: disable=import-outside-toplevel
 
     batch = {}
-    if enable_image and "image_raw" in samples[0]:
+    slots = [i for i, s in enumerate(samples) if "image_jpeg" in s] if enable_image else []  # (DecodeRgbU8(gpu_jpeg=True) only)
+    if enable_image and ("image_raw" in samples[0] or slots):
         # decoded sources of different sizes: ONE packed (page-locked) byte buffer + host-side offsets and (h, w) per image --
         # the layout clipx_resize_crop_u8_device takes
-        sizes = np.asarray([s["image_raw"].shape[:2] for s in samples], dtype=np.int32)
+        if slots:
+            from . import jpeg  # pylint: disable=import-outside-toplevel
+
+            coefs, descs = jpeg.pack_records([samples[i]["image_jpeg"] for i in slots], pin)
+            sizes = np.zeros((len(samples), 2), dtype=np.int32)
+            for i, s in enumerate(samples):
+                if "image_raw" in s:
+                    sizes[i] = s["image_raw"].shape[:2]
+            sizes[slots, 0], sizes[slots, 1] = descs["height"], descs["width"]
+        else:
+            sizes = np.asarray([s["image_raw"].shape[:2] for s in samples], dtype=np.int32)
         nbytes = sizes[:, 0].astype(np.int64) * sizes[:, 1] * 3
         offsets = np.zeros(len(samples), dtype=np.int64)
         np.cumsum(nbytes[:-1], out=offsets[1:])
-        packed = torch.empty(int(nbytes.sum()), dtype=torch.uint8, pin_memory=bool(pin))
+        # (a batch of coefficients only has no pixel to upload: its buffer is the layout alone, never touched and not page-locked)
+        packed = torch.empty(int(nbytes.sum()), dtype=torch.uint8, pin_memory=bool(pin) and len(slots) < len(samples))
         flat = packed.numpy()
         for s, o, n in zip(samples, offsets, nbytes):
-            flat[o:o + n] = s["image_raw"].reshape(-1)
+            if "image_raw" in s:
+                flat[o:o + n] = s["image_raw"].reshape(-1)
         batch["image_raw"] = {"pixels": packed, "offsets": offsets, "hw": sizes}
+        if slots:
+            # coefficients of the images the GPU decodes: one page-locked buffer of records + descriptors + each image's slot of the
+            # batch, whose h * w * 3 bytes above are reserved and left unwritten (clipx_jpeg_pixels_device fills them on the device)
+            batch["image_jpeg"] = {"coefs": coefs, "descs": descs, "slots": np.asarray(slots, dtype=np.int64)}
         batch["image_filename"] = [s["image_filename"] for s in samples]
     elif enable_image:
         first = samples[0]["image_tensor"]
@@ -307,7 +344,11 @@ def _decode_sample(raw, preprocess, tokenizer, enable_image, enable_text, enable
     except (OSError, UnicodeDecodeError) as e:
         print(f"Failed to read sample {raw['key']}. Error: {e}. Skipping.")
         return None
-    if enable_image:
+    taken = preprocess.entropy(raw["image"]) if enable_image and getattr(preprocess, "gpu_jpeg", False) else None
+    if taken is not None:  # a baseline JPEG: its coefficients travel, the pixel stage runs on the GPU
+        out["image_jpeg"] = taken  # uint8 [64-byte descriptor | quantisation tables | int16 coefficients]
+        out["image_filename"] = raw["key"]
+    elif enable_image:
         try:
             img = preprocess(Image.open(io.BytesIO(raw["image"])))
         except (UnidentifiedImageError, OSError, ValueError) as e:
@@ -386,7 +427,7 @@ class _DecodeWorker:
             for sample in out:  # copy the pixels out before this worker's next chunk overwrites the arena
                 if sample is None:
                     continue
-                for k in ("image_tensor", "image_raw"):
+                for k in ("image_tensor", "image_raw", "image_jpeg"):
                     v = sample.get(k)
                     if isinstance(v, tuple) and v and v[0] == "@arena":
                         _, off, shape, dtype = v

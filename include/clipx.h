@@ -137,6 +137,42 @@ int clipx_encode_text_device_ids(clipx_handle* h, const int32_t* ids_dev, const 
 int clipx_resize_crop_u8_device(int device, const void* src_dev, const int64_t* offsets, const int32_t* hw, int B, int S, void* out_dev,
                                 void* stream);
 
+/* Baseline JPEG decode in two stages, for ONE class of files -- SOF0, 8-bit, one interleaved scan (DRI / RSTn allowed),
+ * grayscale or JFIF YCbCr 4:4:4 / 4:2:2 / 4:2:0, both sides <= max_side -- and bit-identical to Pillow's (libjpeg's default)
+ * decode of them.  Every other file, and every file that does not parse cleanly to its EOI, is DEFERRED: not an error, the
+ * caller decodes it as it did before.
+ *
+ * Entropy stage, HOST only (no HIP call: usable in a process without a GPU).  clipx_jpeg_probe_host parses up to the SOF and
+ * returns the class, the descriptor and the size of the record; clipx_jpeg_entropy_host decodes the file into `record`
+ * (record_bytes >= the probed size; never written past it):
+ *   uint16 qt[3][64]         each component's quantisation table
+ *   int16  coef[blocks][64]  component 0's blocks, then 1's, then 2's; a component's blocks in raster order of its plane padded
+ *                            to whole MCUs (bw[c] x bh[c]), DC prediction undone
+ * both in NATURAL order (index = 8 * row + column).  Return: CLIPX_JPEG_TAKEN, CLIPX_JPEG_DEFERRED (nothing was written: neither
+ * the descriptor nor the record), or CLIPX_E_ARG. */
+#define CLIPX_JPEG_DEFERRED 0
+#define CLIPX_JPEG_TAKEN 1
+typedef struct {
+  int32_t width, height;
+  int32_t ncomp;        /* 1 = grayscale, 3 = YCbCr */
+  int32_t hs, vs;       /* luma sampling factors, 1 or 2 (chroma is 1 x 1) */
+  int32_t bw[3], bh[3]; /* blocks per row / column of each component's padded plane */
+  int32_t blocks;       /* of all components */
+  int32_t restart;      /* MCUs per restart interval (informative) */
+  int32_t pad;
+  int64_t coef_off;     /* byte offset of the image's record in the buffer handed to clipx_jpeg_pixels_device: set by the
+                           caller that packs the records, a multiple of 16 */
+} clipx_jpeg_desc;
+int clipx_jpeg_probe_host(const void* data, size_t n, int max_side, clipx_jpeg_desc* desc, size_t* record_bytes);
+int clipx_jpeg_entropy_host(const void* data, size_t n, int max_side, clipx_jpeg_desc* desc, void* record, size_t record_bytes);
+
+/* Pixel stage: dequantisation, libjpeg's slow-integer inverse DCT, fancy chroma upsampling and JFIF colour conversion on the GPU
+ * (csrc/jpeg_kernels.hip).  coefs_dev holds the B records at descs[i].coef_off (16-byte aligned buffer); image i is written as packed
+ * RGB uint8 [height, width, 3] at byte offset offsets[i] of pixels_dev -- the layout clipx_resize_crop_u8_device reads -- and not a byte
+ * outside it.  descs / offsets are HOST arrays; asynchronous on `stream`. */
+int clipx_jpeg_pixels_device(int device, const void* coefs_dev, const clipx_jpeg_desc* descs, int B, void* pixels_dev,
+                             const int64_t* offsets, void* stream);
+
 /* Range guard.  The encoder keeps the residual stream of both towers in IEEE fp16: exact for every checkpoint that is
  * trained or served in fp16 (the reference's CUDA path runs the whole model in fp16, mapper.py:35-41), but a model whose
  * activations exceed 65 504 (possible for bf16-trained checkpoints) would overflow to inf, and LayerNorm turns a row holding inf

@@ -22,7 +22,7 @@ enum GemmEpilogue {
                             // error of the encoder on weights with large LayerNorm gains (tools/emulate_fp16_stream.py)
 };
 
-// Per-dispatch timing (the GEMM brackets of clipx_profile_enable, clipx_api.hip ProfScope): start / stop event pairs that the
+// Per-dispatch timing (the GEMM brackets of clipx_profile_enable, clipx_encode.hip ProfScope): start / stop event pairs that the
 // kernels of one launch_gemm call take, one pair per kernel, attached to the kernel's own dispatch packet instead of being
 // recorded as marker packets in front of and behind it -- nothing sits between back-to-back dispatches.
 struct LaunchEvents {
@@ -78,7 +78,7 @@ struct GemmArgs {
 int gemm256_bulk_mtiles(int M, int N, int n_cu);
 // the same count under launch_gemm's whole dispatch rule: 0 when every row goes to the 128x128 kernel in one launch
 int gemm256_dispatch_mtiles(int M, int N, int K, int variant, int n_cu);
-// M rounded up to whole 256-row m-tiles where that saves launch_gemm the leftover-row launch, else M (ragged_prepare pads to it)
+// M rounded up to whole 256-row m-tiles where that saves launch_gemm the leftover-row launch, else M (the ragged text batches are padded to it: clipx_ragged_plan.h)
 int gemm256_whole_tile_rows(int M, int N, int K, int variant, int n_cu);
 // blocks of 32 columns per workgroup when ONE ragged m-tile of 256 rows rides in the persistent launch (0: not possible)
 int gemm256_tail_blocks(int N, int K, int n_cu);
@@ -94,7 +94,7 @@ hipError_t launch_layernorm(const float* x, const float* gamma, const float* bet
 // (two-pass, fp32; or, for fp16 rows on request, ONE pass in the canonical order of gemm_common.h ln_rstd_onepass -- the order the
 // 4-wave GEMM kernel accumulates the same sums in from its A fragments, so that a row's rstd does not depend on which of the two
 // computed it: the CLIPX_LN_FUSED=1 experiment of round 6).  The LayerNorm itself is folded into the GEMM that follows (weights scaled by gamma and row-centred, bias
-// absorbs beta: clipx_api.hip fold_layernorm), whose epilogue multiplies by rstd[m].  One wave per row.
+// absorbs beta: clipx_api.hip carve_layers), whose epilogue multiplies by rstd[m].  One wave per row.
 // canonical != 0 (fp16 rows): the one-pass form of a GEMM that owns its statistics (GemmArgs.stats_eps)
 hipError_t launch_rowstats(const void* x16, float* rstd, int M, int d, float eps, hipStream_t st, int f16 = 0, int* range_flag = nullptr,
                            int canonical = 0, LaunchEvents* events = nullptr);

@@ -408,7 +408,7 @@ static hipError_t launch_gemm_epi(const GemmArgs& g, hipStream_t st) {
 // else on the CU: fc2 (K = 4096) 36 us, out-proj 13 us.  Splitting K over S workgroup columns fills the chip; the S partial
 // products (raw f32 accumulators) are summed in FIXED order 0 .. S-1 by a second kernel that applies the very epilogue code of
 // the unsplit kernels (gemm_store_quad).  The result is deterministic but not bitwise equal to
-// the unsplit sum, so the caller (clipx_api.hip) hands a scratch buffer only to the GEMMs of a single-sample API call: every
+// the unsplit sum, so the caller (clipx_encode.hip run_gemm) hands a scratch buffer only to the GEMMs of a single-sample API call: every
 // call with >= 2 samples keeps the invariant "a row does not depend on the batch (or chunk) it travels in".
 template <int EPI>
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ part, int S, int M, int N,

@@ -103,7 +103,7 @@ __device__ __forceinline__ float gelu_erf(float v) {
 // One accumulator quad of the transposed-product layout both kernels use (MFMA A operand = weight rows, B operand
 // = activation rows): the lane owns output row m and four consecutive columns n..n+3.
 // bf16-output epilogues: out = act(acc * rowscale[m] + bias[n]) -- rowscale is the row's LayerNorm 1/std when the GEMM
-// consumes the raw residual stream with the LayerNorm folded into its weights (clipx_api.hip: fold_layernorm), 1 otherwise.
+// consumes the raw residual stream with the LayerNorm folded into its weights (clipx_api.hip: carve_layers), 1 otherwise.
 // The multiply-add is ONE fma in both kernels, so a row's result does not depend on which kernel produced it.
 // f32 residual epilogue: x += acc + bias, and (out16 != null) the bf16 copy of the new x row that the next folded GEMM reads.
 // fp16 residual epilogue (EPI_BIAS_RESID_H16): x16 = fp16(f32(x16) + (acc + bias)), in place -- the same association.

@@ -21,9 +21,9 @@
 #include <vector>
 
 #include "../../include/clipx.h"
+#include "clipx_host.h"
 #include "jpegx_entropy.h"
 
-extern "C" int clipx_set_error(int code, const char* msg);
 
 static_assert(sizeof(clipx_jpeg_desc) == sizeof(jpegx::Desc), "clipx_jpeg_desc is jpegx::Desc");
 
@@ -235,15 +235,9 @@ struct Ring {
 std::mutex g_mu;
 Ring g_ring[64];
 
-int fail(int code, const std::string& m) { return clipx_set_error(code, m.c_str()); }
-
 }  // namespace
 
-#define JCHK(expr)                                                                                                 \
-  do {                                                                                                             \
-    hipError_t _e = (expr);                                                                                        \
-    if (_e != hipSuccess) return fail(_e == hipErrorOutOfMemory ? CLIPX_E_NOMEM : CLIPX_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
+using clipx::fail;
 
 extern "C" int clipx_jpeg_probe_host(const void* data, size_t n, int max_side, clipx_jpeg_desc* desc, size_t* record_bytes) {
   if (!desc || !record_bytes || max_side <= 0) return fail(CLIPX_E_ARG, "bad jpeg_probe arguments");
@@ -305,22 +299,22 @@ extern "C" int clipx_jpeg_pixels_device(int device, const void* coefs_dev, const
   }
   const size_t tab_bytes = tab.size() * sizeof(JImg);
 
-  JCHK(hipSetDevice(device));
+  HIPCHK(hipSetDevice(device));
   hipStream_t st = (hipStream_t)stream;
   std::lock_guard<std::mutex> lk(g_mu);
   Ring& r = g_ring[device];
   Slot* sl = &r.slot[r.next];
   r.next = (r.next + 1) & 3;
-  if (sl->used) JCHK(hipEventSynchronize(sl->ev));  // the launch that last used this slot has finished
-  if (!sl->ev) JCHK(hipEventCreateWithFlags(&sl->ev, hipEventDisableTiming));
+  if (sl->used) HIPCHK(hipEventSynchronize(sl->ev));  // the launch that last used this slot has finished
+  if (!sl->ev) HIPCHK(hipEventCreateWithFlags(&sl->ev, hipEventDisableTiming));
   if (sl->tab_bytes < tab_bytes) {
     if (sl->tab_dev) (void)hipFree(sl->tab_dev);
     if (sl->tab_host) (void)hipHostFree(sl->tab_host);
     sl->tab_dev = sl->tab_host = nullptr;
     sl->tab_bytes = 0;
     const size_t want = std::max(tab_bytes, (size_t)64 << 10);
-    JCHK(hipMalloc(&sl->tab_dev, want));
-    JCHK(hipHostMalloc(&sl->tab_host, want, hipHostMallocDefault));
+    HIPCHK(hipMalloc(&sl->tab_dev, want));
+    HIPCHK(hipHostMalloc(&sl->tab_host, want, hipHostMallocDefault));
     sl->tab_bytes = want;
   }
   if (sl->plane_bytes < (size_t)plane_bytes) {
@@ -328,18 +322,18 @@ extern "C" int clipx_jpeg_pixels_device(int device, const void* coefs_dev, const
     sl->planes = nullptr;
     sl->plane_bytes = 0;
     const size_t want = std::max((size_t)plane_bytes + (size_t)plane_bytes / 4, (size_t)8 << 20);
-    JCHK(hipMalloc(&sl->planes, want));
+    HIPCHK(hipMalloc(&sl->planes, want));
     sl->plane_bytes = want;
   }
   memcpy(sl->tab_host, tab.data(), tab_bytes);
-  JCHK(hipMemcpyAsync(sl->tab_dev, sl->tab_host, tab_bytes, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(sl->tab_dev, sl->tab_host, tab_bytes, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(idct_kernel, dim3((max_blocks + 31) / 32, B), dim3(256), 0, st, (const unsigned char*)coefs_dev,
                      (const JImg*)sl->tab_dev, (unsigned char*)sl->planes);
-  JCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(rgb_kernel, dim3((unsigned)((max_items + 255) / 256), B), dim3(256), 0, st, (const unsigned char*)sl->planes,
                      (const JImg*)sl->tab_dev, (unsigned char*)pixels_dev);
-  JCHK(hipGetLastError());
-  JCHK(hipEventRecord(sl->ev, st));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(sl->ev, st));
   sl->used = true;
   return CLIPX_OK;
 }

@@ -1,5 +1,5 @@
 // knnx_host.h -- shared by the HOST translation units of the search half (knnx_api / knnx_range / knnx_ivf / knnx_ivfpq /
-// knnx_ivfsq / knnx_grow / knnx_shrink / knnx_filter / knnx_sharded .hip): the error helpers, the owners of device memory, pinned memory, streams and events, the index object
+// knnx_ivfsq / knnx_grow / knnx_shrink / knnx_filter / knnx_sharded .hip): the error helpers, the owners of device memory, pinned memory, streams and events (hip_owners.h), the index object
 // with its state grouped by the scan that uses it, and the handful of functions one file calls in another.  The kernel
 // files include knn_kernels.h only.
 //
@@ -24,6 +24,7 @@
 
 #include "../../include/knnx.h"
 #include "knn_kernels.h"
+#include "hip_owners.h"
 #include "knnx_filter_plan.h"
 
 using namespace knnx;  // (the launchers and constants of knn_kernels.h)
@@ -42,109 +43,6 @@ inline int fail(int code, const std::string& msg) {
       return fail(_e == hipErrorOutOfMemory ? KNNX_E_NOMEM : KNNX_E_HIP,                         \
                   std::string(#expr) + ": " + hipGetErrorString(_e));                             \
   } while (0)
-
-// ---- owners -------------------------------------------------------------------------------------
-// One device allocation of n T (bytes for T = void).  Move-only; converts to T* so that it is passed to launchers and
-// copies like the pointer it holds.  borrow() points it at memory somebody else owns (attached rows, a device-resident
-// training sample): reset() and the destructor then leave that memory alone.
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  bool borrowed = false;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  DevBuf(DevBuf&& o) noexcept : p(o.p), borrowed(o.borrowed) { o.p = nullptr, o.borrowed = false; }
-  DevBuf& operator=(DevBuf&& o) noexcept {
-    if (this != &o) {
-      reset();
-      std::swap(p, o.p);
-      std::swap(borrowed, o.borrowed);
-    }
-    return *this;
-  }
-  ~DevBuf() { reset(); }
-  hipError_t alloc(size_t n) {
-    reset();
-    hipError_t e = hipMalloc((void**)&p, n * sizeof(std::conditional_t<std::is_void<T>::value, char, T>));
-    if (e != hipSuccess) p = nullptr;
-    return e;
-  }
-  void borrow(const void* q) {
-    reset();
-    p = (T*)q;
-    borrowed = true;
-  }
-  void reset() {
-    if (p && !borrowed) (void)hipFree(p);
-    p = nullptr;
-    borrowed = false;
-  }
-  operator T*() const { return p; }
-};
-// `e` carries the first failure of a chain of allocations; the ones after it are skipped
-template <class T>
-inline void dev_alloc(hipError_t& e, DevBuf<T>& b, size_t n) {
-  if (e == hipSuccess) e = b.alloc(n);
-}
-
-// grow-only pinned staging buffer
-struct PinBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  PinBuf() = default;
-  PinBuf(const PinBuf&) = delete;
-  PinBuf& operator=(const PinBuf&) = delete;
-  ~PinBuf() { reset(); }
-  hipError_t ensure(size_t want) {
-    if (bytes >= want) return hipSuccess;
-    reset();
-    hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
-    if (e != hipSuccess) p = nullptr;
-    else bytes = want;
-    return e;
-  }
-  void reset() {
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    bytes = 0;
-  }
-  operator void*() const { return p; }
-};
-
-struct Stream {
-  hipStream_t s = nullptr;
-  Stream() = default;
-  Stream(const Stream&) = delete;
-  Stream& operator=(const Stream&) = delete;
-  Stream(Stream&& o) noexcept : s(o.s) { o.s = nullptr; }
-  Stream& operator=(Stream&& o) noexcept {
-    std::swap(s, o.s);
-    return *this;
-  }
-  ~Stream() {
-    if (s) (void)hipStreamDestroy(s);
-  }
-  hipError_t create() { return hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
-  operator hipStream_t() const { return s; }
-};
-
-struct Event {
-  hipEvent_t e = nullptr;
-  Event() = default;
-  Event(const Event&) = delete;
-  Event& operator=(const Event&) = delete;
-  Event(Event&& o) noexcept : e(o.e) { o.e = nullptr; }
-  Event& operator=(Event&& o) noexcept {
-    std::swap(e, o.e);
-    return *this;
-  }
-  ~Event() {
-    if (e) (void)hipEventDestroy(e);
-  }
-  hipError_t create(unsigned flags = hipEventDefault) { return hipEventCreateWithFlags(&e, flags); }
-  operator hipEvent_t() const { return e; }
-};
 
 // ---- the index: state grouped by the scan that uses it --------------------------------------------
 constexpr int IVFM_BLK = 8;                       // 32-query blocks of one multi-block IVF pass (knnx_ivf.hip)

@@ -27,10 +27,9 @@
 #include <vector>
 
 #include "../../include/clipx.h"
+#include "clipx_host.h"
 
 extern "C" const char* clipx_last_error(void);
-// (sets the thread-local message of clipx_api.hip)
-extern "C" int clipx_set_error(int code, const char* msg);
 
 namespace {
 
@@ -282,15 +281,9 @@ struct CoefRing {
 std::mutex g_mu;
 CoefRing g_ring[64];
 
-int fail(int code, const std::string& m) { return clipx_set_error(code, m.c_str()); }
-
 }  // namespace
 
-#define PPCHK(expr)                                                                                                \
-  do {                                                                                                             \
-    hipError_t _e = (expr);                                                                                        \
-    if (_e != hipSuccess) return fail(_e == hipErrorOutOfMemory ? CLIPX_E_NOMEM : CLIPX_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
+using clipx::fail;
 
 extern "C" int clipx_resize_crop_u8_device(int device, const void* src_dev, const int64_t* offsets, const int32_t* hw, int B, int S,
                                            void* out_dev, void* stream) {
@@ -369,7 +362,7 @@ extern "C" int clipx_resize_crop_u8_device(int device, const void* src_dev, cons
   memcpy(cb.data(), descs.data(), (size_t)B * sizeof(ImgDesc));
   const size_t bytes = cb.size() * sizeof(int);
 
-  PPCHK(hipSetDevice(device));
+  HIPCHK(hipSetDevice(device));
   hipStream_t st = (hipStream_t)stream;
   CoefSlot* sl;
   {
@@ -377,26 +370,26 @@ extern "C" int clipx_resize_crop_u8_device(int device, const void* src_dev, cons
     CoefRing& r = g_ring[device];
     sl = &r.slot[r.next];
     r.next = (r.next + 1) & 3;
-    if (sl->used) PPCHK(hipEventSynchronize(sl->ev));  // the launch that last read this slot has finished
-    if (!sl->ev) PPCHK(hipEventCreateWithFlags(&sl->ev, hipEventDisableTiming));
+    if (sl->used) HIPCHK(hipEventSynchronize(sl->ev));  // the launch that last read this slot has finished
+    if (!sl->ev) HIPCHK(hipEventCreateWithFlags(&sl->ev, hipEventDisableTiming));
     if (sl->bytes < bytes) {
       if (sl->dev) (void)hipFree(sl->dev);
       if (sl->host) (void)hipHostFree(sl->host);
       sl->dev = sl->host = nullptr;
       sl->bytes = 0;
       const size_t want = std::max(bytes, (size_t)1 << 20);
-      PPCHK(hipMalloc(&sl->dev, want));
-      PPCHK(hipHostMalloc(&sl->host, want, hipHostMallocDefault));
+      HIPCHK(hipMalloc(&sl->dev, want));
+      HIPCHK(hipHostMalloc(&sl->host, want, hipHostMallocDefault));
       sl->bytes = want;
     }
     memcpy(sl->host, cb.data(), bytes);
-    PPCHK(hipMemcpyAsync(sl->dev, sl->host, bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(sl->dev, sl->host, bytes, hipMemcpyHostToDevice, st));
     const size_t smem = max_lds;  // what the largest band of this batch needs (small for mild down-scales: more workgroups per CU)
-    PPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(resize_crop_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(resize_crop_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     hipLaunchKernelGGL(resize_crop_kernel, dim3(max_bands, B), dim3(256), smem, st, (const unsigned char*)src_dev, src_bytes,
                        (const int*)sl->dev, (const ImgDesc*)sl->dev, S, (unsigned char*)out_dev);
-    PPCHK(hipGetLastError());
-    PPCHK(hipEventRecord(sl->ev, st));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(sl->ev, st));
     sl->used = true;
   }
   return CLIPX_OK;

@@ -76,7 +76,7 @@ def emu(tmp_path_factory):
     device = (device.replace("__global__ __launch_bounds__(256) ", "").replace("__device__ __forceinline__", "static inline")
               .replace("extern __shared__ __attribute__((aligned(16))) unsigned char lds[];", "unsigned char* lds = g_lds;")
               .replace('asm volatile("" : "+v"(v));', ""))
-    host = s[s.index("  // ---- geometry + weights of every image"):s.index("  PPCHK(hipSetDevice(device));")]
+    host = s[s.index("  // ---- geometry + weights of every image"):s.index("  HIPCHK(hipSetDevice(device));")]
     d = tmp_path_factory.mktemp("emu")
     (d / "emu.cpp").write_text(SHIM % {"device": device, "host": host})
     subprocess.run(["g++", "-O1", "-std=c++17", "-shared", "-fPIC", "-o", str(d / "emu.so"), str(d / "emu.cpp"), "-lpthread"], check=True)

@@ -1,4 +1,4 @@
-"""Ragged text batches in whole 256-row m-tiles (clipx_api.hip: ragged_prepare).
+"""Ragged text batches in whole 256-row m-tiles (clipx_encode.hip: ragged_prepare, by the planner of clipx_ragged_plan.h).
 
 Where the folded GEMMs of a ragged text batch run in the 256x256 kernel, its row count is rounded up to a multiple of 256 with
 duplicates of real rows (pseudo-samples that are prefixes of the longest caption), so that no GEMM needs a second launch for a

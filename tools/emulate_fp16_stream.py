@@ -1,5 +1,5 @@
 """CPU emulation of the HIP encoder's NUMERICS (not its kernels): fp16 residual stream, LayerNorm folded into fp16 weights,
-bf16 operands everywhere else, f32 accumulation / softmax / statistics (clipx_api.hip run_layers).  Used to predict,
+bf16 operands everywhere else, f32 accumulation / softmax / statistics (clipx_encode.hip run_layers).  Used to predict,
 without a GPU, what outlier magnitudes do to the parity cosine and whether the stream leaves fp16's range.
 usage: python tools/emulate_fp16_stream.py tiny-L/14 [--outliers 300,-300] [--gain 30] [--batch 2]"""
 import argparse

@@ -1,5 +1,5 @@
 // bert_kernels.hip -- gfx950 kernels of the multilingual text towers (use_mclip: DistilBERT multilingual, XLM-R): what a post-LN,
-// padding-masked BERT encoder needs beyond the CLIP encoder's GEMMs and ragged attention (clip_kernels.hip):
+// padding-masked BERT encoder needs beyond the CLIP encoder's GEMMs and ragged attention (gemm_launch.hip, attn_block.hip):
 //
 //   bert_embed_ln_kernel   ids -> LN(word[id] + pos[pos_offset + t]) -> the fp16 residual stream (packed rows of a ragged batch)
 //   postln_f16_kernel      the LayerNorm BEHIND a residual add, in place over the fp16 stream.  It cannot be folded into the next GEMM

@@ -174,7 +174,7 @@ static int bert_gemm(clipx_bert* h, hipStream_t st, const bf16* A, const bf16* W
                      bool f16) {
   GemmArgs g{};
   g.A = A; g.W = W; g.bias = bias; g.out = out; g.T = 1;
-  g.M = M; g.N = N; g.K = K; g.epi = epi; g.variant = 6; g.n_cu = h->n_cu;
+  g.M = M; g.N = N; g.K = K; g.epi = epi; g.variant = clipx::GEMM_V_DEFAULT; g.n_cu = h->n_cu;
   g.rowscale = f16 ? h->ws.ones.p : nullptr;
   g.f16 = f16 ? 1 : 0;
   HIPCHK(launch_gemm(g, st));
@@ -191,7 +191,7 @@ static int bert_chunk(clipx_bert* h, hipStream_t st, int s, const int32_t* ids_d
   const int w = d.width;
   int M = 0;
   for (int b = 0; b < nb; ++b) M += lens_host[b];
-  const int Mp = gemm256_whole_tile_rows(M, 3 * w, w, 6, h->n_cu);
+  const int Mp = gemm256_whole_tile_rows(M, 3 * w, w, clipx::GEMM_V_DEFAULT, h->n_cu);
   int* slot = h->ring.ints(s);
   const RaggedPlan p = ragged_complete(slot, lens_host, nb, d.max_len, Mp, false);
   if (!p.S) return fail(CLIPX_E_ARG, "internal: the activation workspace does not hold the padded rows");

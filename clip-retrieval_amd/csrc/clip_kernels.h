@@ -3,24 +3,11 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
+#include "clipx_gemm_plan.h"  // GemmEpilogue, GemmVariant, the gemm256_* planner functions
 
 namespace clipx {
 
 typedef __bf16 bf16;
-
-enum GemmEpilogue {
-  EPI_BIAS_BF16 = 0,        // out bf16 [M,N] = acc + bias                       (QKV projection)
-  EPI_BIAS_QGELU_BF16 = 1,  // out bf16 = quick_gelu(acc + bias)                 (fc1, OpenAI CLIP)
-  EPI_BIAS_GELU_BF16 = 2,   // out bf16 = gelu_erf(acc + bias)                   (fc1, open_clip LAION)
-  EPI_BIAS_RESID_F32 = 3,   // out f32 [M,N] += acc + bias   (in place residual) (out_proj, fc2)
-  EPI_TABLE_F32 = 4,        // out f32 = acc + table[m % T][n]                   (patch embed + cls/pos)
-  EPI_RAW_F32 = 5,          // internal (split-K): out f32 [M,N] = acc, no bias; the reduction kernel applies the epilogue
-  EPI_BIAS_RESID_H16 = 6,   // out fp16 [M,N] = fp16(f32(out) + (acc + bias)): the encoder's residual stream lives in IEEE fp16
-                            // (out_proj, fc2): a third of the bytes of the f32 read-modify-write + bf16 shadow of EPI 3
-  EPI_BIAS_F16 = 7          // out IEEE fp16 [M,N] = acc * rowscale + bias: EPI 0 with three more mantissa bits.  The QKV projection
-                            // (round 4): q and k feed the softmax logits, where the bf16 rounding of EPI 0 was the largest single
-                            // error of the encoder on weights with large LayerNorm gains (tools/emulate_fp16_stream.py)
-};
 
 // Per-dispatch timing (the GEMM brackets of clipx_profile_enable, clipx_encode.hip ProfScope): start / stop event pairs that the
 // kernels of one launch_gemm call take, one pair per kernel, attached to the kernel's own dispatch packet instead of being
@@ -52,17 +39,16 @@ struct GemmArgs {
   int T;
   int M, N, K;        // N % 128 == 0, K % 64 == 0
   int epi;
-  int variant;        // 0 = 128x128 register-staged LDS fill, 1 = 128x128 global_load_lds, >= 2 (3 by convention, the
-                      // default) = persistent 256x256 kernel (gemm256sp.hip) for the whole 256-row m-tiles, 128x128
-                      // (variant 1) for the rest
-  int n_cu;           // compute units of the device (variant 3 launches one workgroup per CU); 0 = 256
+  int variant;        // GemmVariant (clipx_gemm_plan.h): GEMM_V_DEFAULT = whole 256-row m-tiles in the 4-wave 256x256 kernel where it
+                      // has the form, the 8-wave one elsewhere, the 128x128 kernel for the rest; 0 / 1 / 3: the forms the tests compare
+  int n_cu;           // compute units of the device (the persistent kernels launch one workgroup per CU); 0 = 256
   int row0;           // EPI_TABLE_F32: table row = (row0 + m) % T (set by the launcher when it splits M)
   const float* rowscale;  // bf16-output epilogues: out = act(acc * rowscale[m] + bias[n]); [M] f32, never null (the LayerNorm
                           // 1/std of the row when the LayerNorm is folded into W, launch_rowstats; ones otherwise)
   bf16* out16;            // EPI_BIAS_RESID_F32: also store the new x row as bf16 here (null: do not)
   float* splitk_ws;       // device scratch for split-K partial products (null: never split), splitk_ws_bytes of it
   size_t splitk_ws_bytes;
-  int tail_m0, tail_nb;   // set by launch_gemm for the persistent kernel: rows [tail_m0, tail_m0 + 256) beyond the whole
+  int tail_m0, tail_nb;   // set by launch_gemm (from its GemmPlan) for the persistent kernel: rows [tail_m0, tail_m0 + 256) beyond the whole
                           // m-tiles are computed inside the same launch, 32 x (tail_nb x 32) per workgroup (0: none)
   int f16;                // A and W hold IEEE fp16 instead of bf16 (v_mfma_f32_32x32x16_f16, same rate): the LayerNorm-folded
                           // GEMMs, whose A operand is the fp16 residual stream itself.  bf16-output epilogues (0..2) and RAW only.
@@ -73,15 +59,6 @@ struct GemmArgs {
   int* range_flag;        // (stats_eps > 0) raised when a row of A holds inf / NaN (launch_rowstats)
   LaunchEvents* events;   // null, or the source of one start / stop event pair for every kernel this GEMM launches
 };
-
-// number of 256-row m-tiles variant 3 hands to the 256x256 kernel for an [M, N] output
-int gemm256_bulk_mtiles(int M, int N, int n_cu);
-// the same count under launch_gemm's whole dispatch rule: 0 when every row goes to the 128x128 kernel in one launch
-int gemm256_dispatch_mtiles(int M, int N, int K, int variant, int n_cu);
-// M rounded up to whole 256-row m-tiles where that saves launch_gemm the leftover-row launch, else M (the ragged text batches are padded to it: clipx_ragged_plan.h)
-int gemm256_whole_tile_rows(int M, int N, int K, int variant, int n_cu);
-// blocks of 32 columns per workgroup when ONE ragged m-tile of 256 rows rides in the persistent launch (0: not possible)
-int gemm256_tail_blocks(int N, int K, int n_cu);
 
 hipError_t launch_gemm(const GemmArgs& g, hipStream_t st);
 

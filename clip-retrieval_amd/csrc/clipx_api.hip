@@ -164,7 +164,7 @@ extern "C" int clipx_create(const clipx_model_desc* desc, const float* blob, siz
   h->max_batch = env_positive("CLIPX_MAX_BATCH", h->max_batch);
   h->host_chunk = std::min(env_positive("CLIPX_HOST_CHUNK", h->host_chunk), h->max_batch);
   const char* gv = getenv("CLIPX_GEMM_VARIANT");
-  if (gv) h->gemm_variant = std::min(6, std::max(0, atoi(gv)));  // 5: tools build only (falls back to 3 in the product)
+  if (gv) h->gemm_variant = std::min((int)clipx::GEMM_V_MAX, std::max(0, atoi(gv)));  // 5: tools build only (falls back to 3 in the product)
   const char* lf = getenv("CLIPX_LN_FUSED");
   if (lf) h->ln_fused = lf[0] == '1';
   const char* rgt = getenv("CLIPX_RAGGED_TEXT");

@@ -1,4 +1,4 @@
-// clipx_attn_plan.h -- which attention kernel runs for a (T, head dimension, causal) and with what geometry (clip_kernels.hip,
+// clipx_attn_plan.h -- which attention kernel runs for a (T, head dimension, causal) and with what geometry (attn_block.hip,
 // launch_attention).  No device code in here: plain integer arithmetic, so that a host-only program can drive it
 // (tools/attn_plan_check.cpp).
 //

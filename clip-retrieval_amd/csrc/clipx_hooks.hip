@@ -42,7 +42,7 @@ static int gemm_hook(int device, const void* A_bf16, const void* W_bf16, const f
     g.rowscale = ones[device];
   }
   const char* gv = getenv("CLIPX_GEMM_VARIANT");
-  g.variant = gv ? std::min(6, std::max(0, atoi(gv))) : 6;
+  g.variant = gv ? std::min((int)clipx::GEMM_V_MAX, std::max(0, atoi(gv))) : (int)clipx::GEMM_V_DEFAULT;
   int ncu = 0;
   HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
   g.n_cu = ncu;

@@ -211,7 +211,7 @@ struct Workspace {
   // an f32 stream + bf16 shadow (673 MB -> 269 MB moved per residual GEMM at ViT-L/14 bs 256; same accuracy: the stream has
   // 3 mantissa bits more than the bf16 operands it used to be rounded to).
   DevBuf<bf16> xn, qkv, att, hbuf, patches;
-  DevBuf<float> splitk;  // partial products of the small-M split-K GEMMs (clip_kernels.hip)
+  DevBuf<float> splitk;  // partial products of the small-M split-K GEMMs (gemm128.hip)
   size_t splitk_bytes = 0;
   // text rows: a ragged batch is padded to whole 256-row m-tiles (clipx_ragged_plan.h), at most 255 rows past a full rectangular one
   hipError_t alloc(size_t Bm, const Tower& V, const Tower& X, int Kp) {
@@ -305,7 +305,7 @@ struct clipx_handle {
   int host_chunk = 256;  // chunk of the host-buffer pipeline (H2D of chunk i+1 overlaps the kernels of chunk i); measured
                          // at B=256: chunks of 32/64/128/256 -> 92/65/58/56.5 ms, small chunks lose more GEMM efficiency than
                          // the overlap wins
-  int gemm_variant = 6;  // 6: the 4-wave 256x256 kernel (gemm256w4.hip) where it has the form, the 8-wave one (variant 3) elsewhere
+  int gemm_variant = clipx::GEMM_V_DEFAULT;  // 6: the 4-wave 256x256 kernel (gemm256w4.hip) where it has the form, the 8-wave one (variant 3) elsewhere
   int n_cu = 256;
   bool pool_last_block = true;  // last block past the attention on the pooled rows only (CLIPX_FULL_LAST_BLOCK=1: all rows)
   // LayerNorm statistics of the folded GEMMs inside the 4-wave GEMM kernel instead of a pass of their own: CLIPX_LN_FUSED=1, OFF by

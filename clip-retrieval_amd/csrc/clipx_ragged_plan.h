@@ -2,7 +2,7 @@
 // the multilingual towers (bertx_api.hip).  System headers only, no HIP: tools/ragged_plan_check.cpp runs it under the sanitizers.
 //
 // Sample b owns lens[b] packed rows.  Where the folded GEMMs of the batch run in the 256x256 kernel the row count M is rounded up
-// to Mp, a multiple of 256 (gemm256_whole_tile_rows, clip_kernels.hip: launch_gemm's own rule), so that no GEMM of the tower needs
+// to Mp, a multiple of 256 (gemm256_whole_tile_rows, clipx_gemm_plan.h: launch_gemm's own rule), so that no GEMM of the tower needs
 // a second launch for a handful of leftover rows.  The P = Mp - M extra rows are duplicates of real rows: pseudo-samples that are
 // prefixes of the longest sample b* (the first of equal maxima), ceil(P / lens[b*]) of them, the last one shortened so that the
 // lengths sum to Mp.  Attention stays inside a sample and everything else is row-wise, so a prefix of a real sample goes through

@@ -32,21 +32,12 @@ __device__ __forceinline__ void gemm256_tail(const bf16* __restrict__ A, const b
   if (strip >= 8 * ncg) return;   // (uniform per workgroup; the host makes sure every strip has a workgroup)
   const int rb = strip & 7, cg = strip >> 3;
   const int tm = tail_m0 + rb * 32, tn = cg * NB * 32;
-  const int l31 = lane & 31, hb = lane >> 5;
-#if CLIPX_MFMA16
-  // 16x16x32 form: a stage (128 k) is 4 slabs x 2 row halves = 8 pieces of 1 KiB per 32-row operand; piece p = 2 * slab + half is a
+  // A stage (128 k) is 4 slabs x 2 row halves = 8 pieces of 1 KiB per 32-row operand; piece p = 2 * slab + half is a
   // fragment as the MFMA wants it: lane (l15, q4) holds row 16 * half + l15, k = 32 * slab + 8 * q4 .. + 8.  Wave w fetches piece w.
   const unsigned voff = (unsigned)(((lane & 15) * K + 8 * (lane >> 4)) * 2);
   const char* baseA = reinterpret_cast<const char*>(A) + (size_t)tm * K * 2;  // + piece: (16 * (p & 1)) rows, (p >> 1) * 64 bytes
   const char* baseW = reinterpret_cast<const char*>(W) + (size_t)tn * K * 2;
 #define T_PIECE(p) ((size_t)(16 * ((p) & 1)) * K * 2 + ((p) >> 1) * 64)
-  (void)l31; (void)hb;
-#else
-  const unsigned voff = (unsigned)((l31 * K + 8 * hb) * 2);  // row l31 of the operand, 16 B of the k-step
-  const char* baseA = reinterpret_cast<const char*>(A) + (size_t)tm * K * 2;  // + piece * 32: the piece's k-step in a stage
-  const char* baseW = reinterpret_cast<const char*>(W) + (size_t)tn * K * 2;
-#define T_PIECE(p) ((size_t)(p) * 32)
-#endif
   constexpr int PPW = 8 / NW;  // pieces per wave, operand and stage
   const int nch = K >> 7;
 #define T_DMA(off, base, dst) \
@@ -65,17 +56,10 @@ __device__ __forceinline__ void gemm256_tail(const bf16* __restrict__ A, const b
   };
 #pragma unroll
   for (int c = 0; c < R - 1; ++c) issue(c, c);
-#if CLIPX_MFMA16
   f32x4 acc[4];  // the four 16 x 16 quads of the wave's 32 x 32 block
 #pragma unroll
   for (int g = 0; g < 4; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
 #define T_ACC(g, e) acc[g][e]
-#else
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#define T_ACC(g, e) acc[4 * (g) + (e)]
-#endif
   int slot = 0;
   for (int c = 0; c < nch; ++c) {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"((R - 2) * NOP * PPW) : "memory");  // this wave's share of stage c has landed
@@ -85,7 +69,6 @@ __device__ __forceinline__ void gemm256_tail(const bf16* __restrict__ A, const b
     issue(c + R - 1, slot == 0 ? R - 1 : slot - 1);
     if (w < NB) {
       const unsigned char* st = smem + slot * SB + lane * 16;
-#if CLIPX_MFMA16
 #pragma unroll
       for (int sl = 0; sl < 4; ++sl) {
         const frag_t af0 = *reinterpret_cast<const frag_t*>(st + (2 * sl) * 1024);
@@ -94,14 +77,6 @@ __device__ __forceinline__ void gemm256_tail(const bf16* __restrict__ A, const b
         const frag_t wf1 = *reinterpret_cast<const frag_t*>(st + (1 + w) * 8192 + (2 * sl + 1) * 1024);
         mfma_block16<F16>(acc, wf0, wf1, af0, af1);
       }
-#else
-#pragma unroll
-      for (int ks = 0; ks < 8; ++ks) {
-        const frag_t af = *reinterpret_cast<const frag_t*>(st + ks * 1024);
-        const frag_t wf = *reinterpret_cast<const frag_t*>(st + (1 + w) * 8192 + ks * 1024);
-        acc = mfma_32x32x16<F16>(wf, af, acc);
-      }
-#endif
     }
     slot = slot + 1 == R ? 0 : slot + 1;
   }
@@ -120,6 +95,5 @@ __device__ __forceinline__ void gemm256_tail(const bf16* __restrict__ A, const b
   }
 #undef T_ACC
 }
-
 
 }  // namespace clipx

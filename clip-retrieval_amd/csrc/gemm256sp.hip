@@ -1,5 +1,5 @@
-// gemm256sp.hip -- persistent 256x256x64 software-pipelined bf16 GEMM for gfx950, 8 waves (GemmArgs.variant == 3; since round 6 the default,
-// variant 6, sends the forms gemm256w4.hip has to that 4-wave kernel and everything else here).
+// gemm256sp.hip -- persistent 256x256x64 software-pipelined bf16 GEMM for gfx950, 8 waves (GEMM_V_256_W8; since round 6 the default,
+// GEMM_V_256_W4, sends the forms gemm256w4.hip has to that 4-wave kernel and everything else here).
 //
 //   out[m, n] = epilogue( sum_k A[m, k] * W[n, k] )        A bf16 [M, K] activations, W bf16 [N, K] (torch Linear)
 //
@@ -7,12 +7,12 @@
 //
 //   * one 512-thread workgroup per CU, persistent over output tiles as one continuous K-tile stream.
 //   * 8 waves = 2 (M) x 4 (N), wave tile 128 x 64 = 8 x 4 blocks of v_mfma_f32_16x16x32_{bf16,f16} (128 accumulator VGPRs;
-//     CLIPX_MFMA16 = 1 since round 4 -- the 32x32x16 form is kept behind CLIPX_MFMA16 = 0 for A/B only).
+//     the shape of every GEMM kernel since round 4: gemm_common.h).
 //   * LDS: 2 K-tile buffers x (M operand 256 rows + N operand 256 rows) x 128 B = 128 KiB, filled by LDS-DMA
 //     (global_load_lds_dwordx4, 8 per wave per K-tile, SGPR base + one of four per-lane offsets, M0 = one s_add),
 //     chunk-XOR swizzled through the source address; + 32 KiB of per-wave scratch for the epilogue transposition.
 //   * per K-tile each wave runs 8 units of {2 or 6 ds_read_b128 for the NEXT unit, 8 MFMA of this unit} from two
-//     register sets (32x32x16 form: 4 k-steps of 6 reads + 8 MFMA); the single s_barrier of the K-tile sits BEFORE the last
+//     register sets; the single s_barrier of the K-tile sits BEFORE the last
 //     unit's MFMAs:
 //         step 3:  lgkmcnt(0); vmcnt(1)  [K-tile g+1 landed; the L2 prefetch may stay in flight]; s_barrier;
 //                  ds_read step 0 of K-tile g+1; 8 MFMA; stage K-tile g+2 into the buffer just released;
@@ -26,7 +26,7 @@
 //     tile drain under the next tile's first K-tiles).  Measured with the phase timer (DBG 16): an earlier version whose
 //     address registers spilled paid an `s_waitcnt vmcnt(0)` per store = 17.7 k cycles per tile; now ~4 k.
 //
-// Requirements: M % 256 == 0, N % 256 == 0, K % 128 == 0 (the launcher in clip_kernels.hip peels ragged rows).
+// Requirements: M % 256 == 0, N % 256 == 0, K % 128 == 0 (gemm_plan peels ragged rows).
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -86,7 +86,6 @@ __global__ __launch_bounds__(512, 2) void gemm256sp_kernel(const bf16* __restric
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = w >> 2, wc = w & 3;  // waves w and w+4 share a SIMD (measured placement); rows differ, harmless here
-  const int hb = lane >> 5, l31 = lane & 31;
   const int ntiles = ntm * ntn;
 
   // ---- tile list of this block, XCD-aware: the 32 workgroups of an XCD (blockIdx % 8) walk 8 m-tiles x all n-tiles of a
@@ -179,20 +178,11 @@ __global__ __launch_bounds__(512, 2) void gemm256sp_kernel(const bf16* __restric
   if (PFD) asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %0, off" ::"v"(ptr), "s"(pf_m0) : "memory"); \
   S_FENCE();
 
-  // ---- fragment read addresses (LDS byte addresses): one per (operand, k-step); buffer and fragment index are
+  // ---- fragment read addresses (LDS byte addresses): one per (operand, 32-deep slab); buffer and fragment index are
   // immediates.  The reads are inline asm so that THIS file places the lgkmcnt waits (hipcc's own placement waits
   // lgkmcnt(0) right after issuing the next step's reads, which serialises LDS latency with the MFMAs).
-  const int sw = (l31 >> 1) & 7;
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
-  unsigned fM[4], fN[4];
-#pragma unroll
-  for (int kk = 0; kk < 4; ++kk) {
-    const int xk = ((2 * kk + hb) ^ sw) << 4;
-    fM[kk] = lds0 + (wr * 128 + l31) * 128 + xk;            // + buf*S_OPB + mi*4096
-    fN[kk] = lds0 + S_NBASE + (wc * 64 + l31) * 128 + xk;   // + buf*S_OPB + ni*4096
-  }
-
-  // 16x16x32 form (CLIPX_MFMA16): row l15 of a 16-row half-block (+ 2 KiB per half, + 4 KiB per 32-row block), k-chunk 4 sl + q4 of
+  // row l15 of a 16-row half-block (+ 2 KiB per half, + 4 KiB per 32-row block), k-chunk 4 sl + q4 of
   // the 32-deep slab sl; (row >> 1) & 7 of the swizzle only depends on l15 (the block bases are multiples of 16 rows)
   const int l15 = lane & 15, q4 = lane >> 4;
   unsigned fM16[2], fN16[2];
@@ -203,27 +193,15 @@ __global__ __launch_bounds__(512, 2) void gemm256sp_kernel(const bf16* __restric
     fN16[sl] = lds0 + S_NBASE + (wc * 64 + l15) * 128 + xk;   // + buf*S_OPB + ni*4096 + j2*2048
   }
   // accumulators of the wave's 128 x 64 tile: 32 x 32 blocks (mt, nt), quad g of a block, element e of a quad (gemm_common.h)
-#if CLIPX_MFMA16
   f32x4 acc[8][4];  // [2 mt + m-half][2 nt + n-half]: one 16 x 16 MFMA block each
 #define ACC(mt, nt, g, e) acc[2 * (mt) + ((g) >> 1)][2 * (nt) + ((g) & 1)][e]
 #pragma unroll
   for (int i = 0; i < 8; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#else
-  f32x16 acc[4][2];
-#define ACC(mt, nt, g, e) acc[mt][nt][4 * (g) + (e)]
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-#endif
 
   typedef int i32x4 __attribute__((ext_vector_type(4)));
 #define S_DSREAD(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(off))
-#if CLIPX_MFMA16
   // A 64-deep K-tile is eight units u = 4 * slab + mi: unit (sl, mi) multiplies the slab's four weight fragments Nd[sl][2 ni + j2]
   // (16 rows x 32 k each) with the two activation fragments Md[u & 1][h2] of the 32-row block mi: 8 v_mfma_f32_16x16x32 = 128
   // matrix-pipe cycles.  The fragments of unit u + 1 are read while unit u multiplies: 2 reads (the next block's activations), or
@@ -278,45 +256,6 @@ __global__ __launch_bounds__(512, 2) void gemm256sp_kernel(const bf16* __restric
   S_FENCE();
 #define S_READ_FIRST(buf) S_READ_U(0, buf)
 #define S_MFMA_LAST() S_MFMA_U(7)
-#else
-  // [0..3] M fragments (mi), [4..5] N fragments (ni) of one k-step; held as 4 x b32 so that hipcc keeps each
-  // fragment one 128-bit register tuple across the loop back-edge (as 8 x bf16 it re-packs them with v_perm_b32)
-  i32x4 F0[6], F1[6];
-  if (DBG_NO_READ) {
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-      F0[i] = F1[i] = i32x4{0, 0, 0, 0};
-      asm volatile("" : "+v"(F0[i]), "+v"(F1[i]));
-    }
-  }
-#define S_READ(F, buf, kk)                                                                 \
-  if (!DBG_NO_READ) {                                                                      \
-    S_DSREAD(F[4], fN[kk], (buf) * S_OPB);                                                 \
-    S_DSREAD(F[5], fN[kk], (buf) * S_OPB + 4096);                                          \
-    S_DSREAD(F[0], fM[kk], (buf) * S_OPB);                                                 \
-    S_DSREAD(F[1], fM[kk], (buf) * S_OPB + 4096);                                          \
-    S_DSREAD(F[2], fM[kk], (buf) * S_OPB + 8192);                                          \
-    S_DSREAD(F[3], fM[kk], (buf) * S_OPB + 12288);                                         \
-  }                                                                                        \
-  S_FENCE();
-// the fragment set read one step earlier has landed when at most the 6 reads issued since are outstanding
-#define S_WAIT_PREV() asm volatile("s_waitcnt lgkmcnt(6)" ::: "memory"); S_FENCE();
-#define S_MFMA(F)                                                                                                  \
-  _Pragma("unroll") for (int mi = 0; mi < 4; ++mi) _Pragma("unroll") for (int ni = 0; ni < 2; ++ni) acc[mi][ni] =  \
-      mfma_32x32x16<F16>(F[4 + ni], F[mi], acc[mi][ni]);                                                            \
-  S_FENCE();
-
-  // One K-tile = S_KT_HEAD (k-steps 0..2 and the LDS drain), a vmcnt wait + barrier, the stage of a later K-tile into
-  // the buffer just released, then S_KT_TAIL (pre-read of the next K-tile's first fragments + k-step 3's MFMAs).
-#define S_KT_HEAD(buf)                                       \
-  S_READ(F1, buf, 1) S_WAIT_PREV() S_MFMA(F0)                \
-  S_READ(F0, buf, 2) S_WAIT_PREV() S_MFMA(F1)                \
-  S_READ(F1, buf, 3) S_WAIT_PREV() S_MFMA(F0)                \
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");         \
-  S_FENCE();
-#define S_READ_FIRST(buf) S_READ(F0, buf, 0)
-#define S_MFMA_LAST() S_MFMA(F1)
-#endif
 #define S_KT_SYNC(vm)                                        \
   asm volatile("s_waitcnt vmcnt(%0)" ::"i"(vm) : "memory");  \
   S_FENCE();                                                 \
@@ -462,19 +401,11 @@ __global__ __launch_bounds__(512, 2) void gemm256sp_kernel(const bf16* __restric
     S_FENCE();
     // Where quad g (four consecutive columns of one row, gemm_common.h) of the 32 x 32 block (mt, nt) sits in the wave's transposition
     // scratch -- rows of 128 B, one 32-row pass at a time -- and which bias / row-scale entries it needs, for both MFMA forms:
-#if CLIPX_MFMA16
 #define Q_ROW(g) (16 * ((g) >> 1) + l15)                        // row inside the 32-row pass
 #define Q_CH16(nt, g) (4 * (nt) + 2 * ((g) & 1) + (q4 >> 1))    // 16-B chunk of eight 16-bit outputs (64 columns = 8 chunks)
 #define Q_HALF(g) (q4 & 1)                                      // 8-B half of that chunk
 #define Q_CH32(g) (4 * ((g) & 1) + q4)                          // 16-B chunk of four f32 outputs inside the 32-column block
 #define Q_NCOL(nt, g) ((nt) * 32 + 16 * ((g) & 1) + 4 * q4)     // first column of the quad inside the wave's 64 columns
-#else
-#define Q_ROW(g) l31
-#define Q_CH16(nt, g) (4 * (nt) + (g))
-#define Q_HALF(g) hb
-#define Q_CH32(g) (2 * (g) + hb)
-#define Q_NCOL(nt, g) ((nt) * 32 + 8 * (g) + 4 * hb)
-#endif
 #define Q_POS16(nt, g) (Q_ROW(g) * 128 + ((Q_CH16(nt, g) ^ (Q_ROW(g) & 7)) << 4) + Q_HALF(g) * 8)
 #define Q_POS32(g) (Q_ROW(g) * 128 + ((Q_CH32(g) ^ (Q_ROW(g) & 7)) << 4))
     if (DBG != 5) {
@@ -827,10 +758,10 @@ static hipError_t launch_sp_epi(const GemmArgs& g, int grid, hipStream_t st) {
   return hipGetLastError();
 }
 
-hipError_t launch_gemm256sp(const GemmArgs& g, int n_cu, hipStream_t st) {
+hipError_t launch_gemm256sp(const GemmArgs& g, const GemmPlan& plan, hipStream_t st) {
   if (g.M <= 0 || g.M % 256 != 0 || g.N % 256 != 0 || g.K % 128 != 0 || g.K <= 0) return hipErrorInvalidValue;
-  int grid = (n_cu > 0 ? n_cu : 256) & ~7;  // one workgroup per CU; multiple of the 8 XCDs
-  if (grid < 8) grid = 8;
+  if (!plan.valid || plan.kernel256 != GEMM256_W8 || g.M != plan.rows256 || g.tail_nb != plan.tail_nb) return hipErrorInvalidValue;
+  const int grid = plan.grid256;  // one workgroup per CU; multiple of the 8 XCDs
 #ifdef CLIPX_ABLATE
   // Ablation / phase-timer instantiations exist only in the tools build (make ablate -> lib/libclipx_ablate.so); the
   // product library has no environment switch that changes what the hot path computes.
@@ -869,25 +800,9 @@ hipError_t launch_gemm256sp(const GemmArgs& g, int n_cu, hipStream_t st) {
     }
   }
 #endif
-  if (g.f16) {
-    switch (g.epi) {
-      case EPI_BIAS_BF16: return launch_sp_epi<EPI_BIAS_BF16, 0, true>(g, grid, st);
-      case EPI_BIAS_F16: return launch_sp_epi<EPI_BIAS_F16, 0, true>(g, grid, st);
-      case EPI_BIAS_QGELU_BF16: return launch_sp_epi<EPI_BIAS_QGELU_BF16, 0, true>(g, grid, st);
-      case EPI_BIAS_GELU_BF16: return launch_sp_epi<EPI_BIAS_GELU_BF16, 0, true>(g, grid, st);
-      default: return hipErrorInvalidValue;
-    }
-  }
-  switch (g.epi) {
-    case EPI_BIAS_BF16: return launch_sp_epi<EPI_BIAS_BF16>(g, grid, st);
-    case EPI_BIAS_F16: return launch_sp_epi<EPI_BIAS_F16>(g, grid, st);
-    case EPI_BIAS_QGELU_BF16: return launch_sp_epi<EPI_BIAS_QGELU_BF16>(g, grid, st);
-    case EPI_BIAS_GELU_BF16: return launch_sp_epi<EPI_BIAS_GELU_BF16>(g, grid, st);
-    case EPI_BIAS_RESID_F32: return launch_sp_epi<EPI_BIAS_RESID_F32>(g, grid, st);
-    case EPI_BIAS_RESID_H16: return launch_sp_epi<EPI_BIAS_RESID_H16>(g, grid, st);
-    case EPI_TABLE_F32: return launch_sp_epi<EPI_TABLE_F32>(g, grid, st);
-    default: return hipErrorInvalidValue;
-  }
+  if (g.f16) return with_out16_epilogue(g.epi, [&](auto E) { return launch_sp_epi<decltype(E)::value, 0, true>(g, grid, st); });
+  return with_epilogue<EPI_BIAS_BF16, EPI_BIAS_F16, EPI_BIAS_QGELU_BF16, EPI_BIAS_GELU_BF16, EPI_BIAS_RESID_F32, EPI_BIAS_RESID_H16, EPI_TABLE_F32>(
+      g.epi, [&](auto E) { return launch_sp_epi<decltype(E)::value>(g, grid, st); });
 }
 
 }  // namespace clipx

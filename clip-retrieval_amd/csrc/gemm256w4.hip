@@ -695,23 +695,15 @@ static hipError_t launch_w4_epi(const GemmArgs& g, int grid, hipStream_t st) {
   return hipGetLastError();
 }
 
-// true when the 4-wave kernel computes the LayerNorm row scales of this GEMM itself (GemmArgs.stats_eps > 0)
-bool gemm256w4_fuses_stats(const GemmArgs& g) {
-  return g.stats_eps > 0.f && g.f16 && gemm256w4_supports(g) &&
-         (g.epi == EPI_BIAS_BF16 || g.epi == EPI_BIAS_F16 || g.epi == EPI_BIAS_QGELU_BF16 || g.epi == EPI_BIAS_GELU_BF16);
-}
-
-// true when the 4-wave kernel has this (epilogue, operand type, shape)
-bool gemm256w4_supports(const GemmArgs& g) {
-  if (g.M <= 0 || g.M % 256 != 0 || g.N % 256 != 0 || g.K % 128 != 0 || g.K < 256) return false;
-  if (g.f16) return g.epi == EPI_BIAS_BF16 || g.epi == EPI_BIAS_F16 || g.epi == EPI_BIAS_QGELU_BF16 || g.epi == EPI_BIAS_GELU_BF16;
-  return g.epi == EPI_BIAS_BF16 || g.epi == EPI_BIAS_F16 || g.epi == EPI_BIAS_QGELU_BF16 || g.epi == EPI_BIAS_GELU_BF16 || g.epi == EPI_BIAS_RESID_H16;
-}
-
-hipError_t launch_gemm256w4(const GemmArgs& g, int n_cu, hipStream_t st) {
-  if (!gemm256w4_supports(g)) return hipErrorInvalidValue;
-  int grid = (n_cu > 0 ? n_cu : 256) & ~7;
-  if (grid < 8) grid = 8;
+// (which shapes, epilogues and operand types this kernel has, and when it takes the statistics: gemm256w4_supports /
+// gemm256w4_fuses_stats, clipx_gemm_plan.h)
+hipError_t launch_gemm256w4(const GemmArgs& g, const GemmPlan& plan, hipStream_t st) {
+  if (!gemm256w4_supports(g.M, g.N, g.K, g.epi, g.f16 != 0)) return hipErrorInvalidValue;
+  const bool stats = plan.fused_rows > 0;
+  if (!plan.valid || plan.kernel256 != GEMM256_W4 || g.M != plan.rows256 || g.tail_nb != plan.tail_nb ||
+      stats != (g.stats_eps > 0.f) || (stats && (plan.fused_rows != g.M || !gemm256w4_fuses_stats(g.M, g.N, g.K, g.epi, g.f16 != 0))))
+    return hipErrorInvalidValue;
+  const int grid = plan.grid256;
 #ifdef CLIPX_ABLATE
   {
     const char* dbg = getenv("CLIPX_GEMM_DBG");
@@ -732,32 +724,10 @@ hipError_t launch_gemm256w4(const GemmArgs& g, int n_cu, hipStream_t st) {
     }
   }
 #endif
-  if (gemm256w4_fuses_stats(g)) {
-    switch (g.epi) {
-      case EPI_BIAS_BF16: return launch_w4_epi<EPI_BIAS_BF16, true, 0, true>(g, grid, st);
-      case EPI_BIAS_F16: return launch_w4_epi<EPI_BIAS_F16, true, 0, true>(g, grid, st);
-      case EPI_BIAS_QGELU_BF16: return launch_w4_epi<EPI_BIAS_QGELU_BF16, true, 0, true>(g, grid, st);
-      case EPI_BIAS_GELU_BF16: return launch_w4_epi<EPI_BIAS_GELU_BF16, true, 0, true>(g, grid, st);
-      default: return hipErrorInvalidValue;
-    }
-  }
-  if (g.f16) {
-    switch (g.epi) {
-      case EPI_BIAS_BF16: return launch_w4_epi<EPI_BIAS_BF16, true>(g, grid, st);
-      case EPI_BIAS_F16: return launch_w4_epi<EPI_BIAS_F16, true>(g, grid, st);
-      case EPI_BIAS_QGELU_BF16: return launch_w4_epi<EPI_BIAS_QGELU_BF16, true>(g, grid, st);
-      case EPI_BIAS_GELU_BF16: return launch_w4_epi<EPI_BIAS_GELU_BF16, true>(g, grid, st);
-      default: return hipErrorInvalidValue;
-    }
-  }
-  switch (g.epi) {
-    case EPI_BIAS_BF16: return launch_w4_epi<EPI_BIAS_BF16, false>(g, grid, st);
-    case EPI_BIAS_F16: return launch_w4_epi<EPI_BIAS_F16, false>(g, grid, st);
-    case EPI_BIAS_QGELU_BF16: return launch_w4_epi<EPI_BIAS_QGELU_BF16, false>(g, grid, st);
-    case EPI_BIAS_GELU_BF16: return launch_w4_epi<EPI_BIAS_GELU_BF16, false>(g, grid, st);
-    case EPI_BIAS_RESID_H16: return launch_w4_epi<EPI_BIAS_RESID_H16, false>(g, grid, st);
-    default: return hipErrorInvalidValue;
-  }
+  if (stats) return with_out16_epilogue(g.epi, [&](auto E) { return launch_w4_epi<decltype(E)::value, true, 0, true>(g, grid, st); });
+  if (g.f16) return with_out16_epilogue(g.epi, [&](auto E) { return launch_w4_epi<decltype(E)::value, true>(g, grid, st); });
+  return with_epilogue<EPI_BIAS_BF16, EPI_BIAS_F16, EPI_BIAS_QGELU_BF16, EPI_BIAS_GELU_BF16, EPI_BIAS_RESID_H16>(
+      g.epi, [&](auto E) { return launch_w4_epi<decltype(E)::value, false>(g, grid, st); });
 }
 
 }  // namespace clipx

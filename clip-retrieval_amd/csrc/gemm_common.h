@@ -1,8 +1,9 @@
-// gemm_common.h -- device-side pieces shared by the two bf16 GEMM kernels (clip_kernels.hip: 128x128 tile,
-// gemm256sp.hip: persistent 256x256).  Internal.
+// gemm_common.h -- device-side pieces shared by the bf16 / fp16 GEMM kernels (gemm128.hip: 128x128 tile, gemm256sp.hip and
+// gemm256w4.hip: persistent 256x256), and the launchers gemm_launch.hip issues a GemmPlan through.  Internal.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "clip_kernels.h"
 
 namespace clipx {
@@ -15,37 +16,25 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef int frag_t __attribute__((ext_vector_type(4)));  // one MFMA operand fragment: 8 x 16-bit values, type-agnostic
 
-// one v_mfma_f32_32x32x16 on 16-bit operand fragments: bf16 (F16 = false) or IEEE fp16 (same issue rate)
-template <bool F16>
-__device__ __forceinline__ f32x16 mfma_32x32x16(frag_t a, frag_t b, f32x16 c) {
-  if constexpr (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-// ---- MFMA shape (round 4).  CLIPX_MFMA16 = 1: every GEMM kernel of this library multiplies with v_mfma_f32_16x16x32 (16 x 16
-// output blocks, 32-deep k-slabs) instead of v_mfma_f32_32x32x16.  Same flops per matrix-pipe cycle, same LDS bytes per flop -- but on
+// ---- MFMA shape (round 4).  Every GEMM kernel of this library multiplies with v_mfma_f32_16x16x32 (16 x 16 output blocks, 32-deep
+// k-slabs), not v_mfma_f32_32x32x16.  Same flops per matrix-pipe cycle, same LDS bytes per flop -- but on
 // this power-managed part the 16x16x32 form sustains ~10 % more TFLOP/s: +13 % on register-only loops, +9 % on this library's GEMM
 // skeleton (fragment reads + LDS-DMA + barrier; tools/mfma_power_probe.hip, tools/mfma_probe2.hip, profiles/r04i_*, r04j_*): a quarter
 // of the accumulator registers are read and written per instruction for half the flops.  It is also the instruction the vendor's
-// assembly kernel uses.  All kernels switch together: an output element is the sum of its k-slabs in ascending order of
+// assembly kernel uses (profiles/r04m_gemm_mfma16_vs_mfma32.log holds the A/B, after which the 32x32x16 forms were
+// deleted).  All kernels share the shape: an output element is the sum of its k-slabs in ascending order of
 // 32, whichever kernel computes it, so rows stay bit-identical across kernels, batch chunkings and the ragged tail.
 //
 // Accumulator layout.  A 32 x 32 output block (32 weight rows n x 32 activation rows m, the weights being the MFMA A operand) is 16
-// registers per lane in both forms (one f32x16, or four f32x4 quads):
-//   32x32x16  lane (l31 = lane & 31, hb = lane >> 5):  quad g = 0..3 -> m = l31,           n = 8 g + 4 hb + e
-//   16x16x32  lane (l15 = lane & 15, q4 = lane >> 4):  quad g = 0..3 -> m = 16 (g >> 1) + l15, n = 16 (g & 1) + 4 q4 + e     (e = 0..3)
-// i.e. quad g of the 16x16x32 form is the 16 x 16 sub-block (m-half g >> 1, n-half g & 1).  Fragments: one 16-B LDS read per lane in
-// both forms -- 32x32x16: row l31, k-chunk 2 kk + hb of the 16-deep step kk; 16x16x32: row l15 (+ 16 per half), k-chunk 4 s + q4 of
-// the 32-deep slab s.
-#ifndef CLIPX_MFMA16
-#define CLIPX_MFMA16 1
-#endif
-
+// registers per lane, four f32x4 quads: lane (l15 = lane & 15, q4 = lane >> 4), quad g = 0..3 -> m = 16 (g >> 1) + l15,
+// n = 16 (g & 1) + 4 q4 + e (e = 0..3), i.e. quad g is the 16 x 16 sub-block (m-half g >> 1, n-half g & 1).  Fragments: one 16-B LDS
+// read per lane -- row l15 (+ 16 per half), k-chunk 4 s + q4 of the 32-deep slab s.
 template <bool F16>
 __device__ __forceinline__ f32x4 mfma_16x16x32(frag_t a, frag_t b, f32x4 c) {
   if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
   else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
-// In the 16x16x32 form the four quads of a 32 x 32 block are four separate f32x4 variables (each MFMA then accumulates in place;
+// The four quads of a 32 x 32 block are four separate f32x4 variables (each MFMA then accumulates in place;
 // packed into one f32x16 with shuffles the register allocator let the accumulators wander and spilled around tile boundaries).
 // one 32 x 32 block over one 32-deep k-slab: wf[j2] = weight rows 16 j2 .. + 16, af[h2] = activation rows 16 h2 .. + 16
 template <bool F16>
@@ -56,8 +45,8 @@ __device__ __forceinline__ void mfma_block16(f32x4 (&q)[4], frag_t wf0, frag_t w
   q[3] = mfma_16x16x32<F16>(wf1, af1, q[3]);
 }
 // the (m, n) of quad g inside its 32 x 32 block for this lane (n = first of four consecutive columns)
-__device__ __forceinline__ int quad_m(int g, int lane) { return CLIPX_MFMA16 ? 16 * (g >> 1) + (lane & 15) : (lane & 31); }
-__device__ __forceinline__ int quad_n(int g, int lane) { return CLIPX_MFMA16 ? 16 * (g & 1) + 4 * (lane >> 4) : 8 * g + 4 * (lane >> 5); }
+__device__ __forceinline__ int quad_m(int g, int lane) { return 16 * (g >> 1) + (lane & 15); }
+__device__ __forceinline__ int quad_n(int g, int lane) { return 16 * (g & 1) + 4 * (lane >> 4); }
 
 // ---- LayerNorm statistics of an fp16 row, one pass, in ONE canonical order (round 6).  The folded GEMMs (QKV, fc1) multiply their
 // accumulators by the row's 1 / sqrt(var + eps).  The 4-wave 256x256 kernel takes the two sums it needs from the A fragments it
@@ -165,11 +154,26 @@ __device__ __forceinline__ void gemm_store_quad(float4 v, int m, int n, int N, c
   }
 }
 
-// bulk-tile launcher of gemm256sp.hip: rows [0, g.M) must be a multiple of 256, N % 256 == 0, K % 128 == 0
-hipError_t launch_gemm256sp(const GemmArgs& g, int n_cu, hipStream_t st);
-// the 4-wave form of the same tile (gemm256w4.hip): 16-bit-output epilogues and the fp16 in-place residual, K >= 256
-bool gemm256w4_supports(const GemmArgs& g);
-bool gemm256w4_fuses_stats(const GemmArgs& g);  // GemmArgs.stats_eps > 0 and the form has the STATS kernel
-hipError_t launch_gemm256w4(const GemmArgs& g, int n_cu, hipStream_t st);
+// ---- the epilogue number as a compile-time constant, written once: calls f(std::integral_constant<int, EPI>) for the one of
+// ALLOWED that epi is, hipErrorInvalidValue for any other (the kernel family has no such form)
+template <int... ALLOWED, class F>
+inline hipError_t with_epilogue(int epi, F&& f) {
+  hipError_t r = hipErrorInvalidValue;
+  (void)((epi == ALLOWED ? (r = f(std::integral_constant<int, ALLOWED>{}), true) : false) || ...);
+  return r;
+}
+template <class F>  // the 16-bit-output epilogues: every form with fp16 operands
+inline hipError_t with_out16_epilogue(int epi, F&& f) {
+  return with_epilogue<EPI_BIAS_BF16, EPI_BIAS_F16, EPI_BIAS_QGELU_BF16, EPI_BIAS_GELU_BF16>(epi, f);
+}
+
+// ---- the launchers of one GemmPlan (clipx_gemm_plan.h), called by launch_gemm with the rows the plan gave each.  Every one refuses
+// (hipErrorInvalidValue) a launch that is not the one the plan names.
+// gemm128.hip: g.M = plan.rows128 rows, LDS fill and split-K factor as planned
+hipError_t launch_gemm128(const GemmArgs& g, const GemmPlan& plan, hipStream_t st);
+// gemm256sp.hip (GEMM256_W8) / gemm256w4.hip (GEMM256_W4): g.M = plan.rows256, g.tail_nb = plan.tail_nb, plan.grid256 workgroups;
+// the 4-wave kernel takes the LayerNorm statistics of its rows itself when plan.fused_rows > 0 (g.stats_eps)
+hipError_t launch_gemm256sp(const GemmArgs& g, const GemmPlan& plan, hipStream_t st);
+hipError_t launch_gemm256w4(const GemmArgs& g, const GemmPlan& plan, hipStream_t st);
 
 }  // namespace clipx

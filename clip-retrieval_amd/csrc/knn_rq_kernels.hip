@@ -40,20 +40,11 @@
 
 namespace knnx {
 
-// KNNX_MFMA16 (default 1, round 4): the scan and the assignment kernel multiply with v_mfma_f32_16x16x32_f16 instead of
-// v_mfma_f32_32x32x16_f16 -- on this power-managed part the 16 x 16 x 32 shape sustains more TFLOP/s (the same switch as
-// the encoder's GEMMs, CLIPX_MFMA16; -DCLIPX_MFMA16=0 / -DKNNX_MFMA16=0 builds the previous kernels for the A/B).  What changes is
-// the fragment shape, nothing else: a 1-KiB LDS piece is (16 rows x 32 columns) -- lane (r = l & 15, q4 = l >> 4) holds row r,
-// columns 8 q4 .. + 8 of the 32-column slab -- instead of (32 rows x 16 columns); a 32-row tile is still d / 16 pieces, piece
-// p = 2 * slab + (row half); a wave's queries are blocks of 16 (lane: query l & 15, the same columns); a 16 x 16 result block gives
-// lane (query l & 15) the rows 4 q4 .. + 4 of its half.
-#ifndef KNNX_MFMA16
-#ifdef CLIPX_MFMA16
-#define KNNX_MFMA16 CLIPX_MFMA16
-#else
-#define KNNX_MFMA16 1
-#endif
-#endif
+// MFMA shape (round 4): the scan and the assignment kernel multiply with v_mfma_f32_16x16x32_f16, not v_mfma_f32_32x32x16_f16 -- on
+// this power-managed part the 16 x 16 x 32 shape sustains more TFLOP/s (as in the encoder's GEMMs: gemm_common.h).
+// Fragment shape: a 1-KiB LDS piece is (16 rows x 32 columns) -- lane (r = l & 15, q4 = l >> 4) holds row r, columns 8 q4 .. + 8 of
+// the 32-column slab; a 32-row tile is d / 16 pieces, piece p = 2 * slab + (row half); a wave's queries are blocks of 16 (lane:
+// query l & 15, the same columns); a 16 x 16 result block gives lane (query l & 15) the rows 4 q4 .. + 4 of its half.
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef float float16v __attribute__((ext_vector_type(16)));
@@ -68,23 +59,17 @@ __device__ __forceinline__ float rq_dec_f(int e) { return __int_as_float(e >= 0 
 
 // ---------------------------------------------------------------------------------------------
 // prep: f32 queries -> fp16-hi B fragments in wave-block order; thresholds from the sample pass; counters reset
-//   qfrag [nblk][KS][64 lanes][8 halves]: block b = queries 32b .. 32b+31; lane (n = l & 31, h = l >> 5) holds
-//   q_n[16 s + 8 h + j].  thr[q] = J-th best sample score (samp [nq, kw] descending, -FLT_MAX padded; fewer than J sample
+//   qfrag [nblk][d / 32][64 lanes][8 halves]: block b = queries 16b .. 16b+15; lane (n = l & 15, q4 = l >> 4) holds
+//   q_n[32 s + 8 q4 + j].  thr[q] = J-th best sample score (samp [nq, kw] descending, -FLT_MAX padded; fewer than J sample
 //   rows -> -inf: every row is a hit, which only happens on indexes far too small for this path); unused columns +inf.
 // ---------------------------------------------------------------------------------------------
 __global__ void knn_rq_prep_kernel(const float* __restrict__ q, int nq, int d, int nblk, _Float16* __restrict__ qfrag,
                                    const float* __restrict__ samp, int kw, int J, float slack, float* __restrict__ thr,
                                    unsigned* __restrict__ cnt, unsigned* __restrict__ lost) {
-  const int s = blockIdx.x, b = blockIdx.y;  // k-step (KNNX_MFMA16: 32-column slab), query block (KNNX_MFMA16: of 16)
+  const int s = blockIdx.x, b = blockIdx.y;  // 32-column slab, query block of 16
   const int lane = threadIdx.x;
-#if KNNX_MFMA16
-  // qfrag [nblk16][d / 32][64 lanes][8 halves]: lane (n = l & 15, q4 = l >> 4) holds q_n[32 s + 8 q4 + j]
   const int n = 16 * b + (lane & 15), h = lane >> 4;
   constexpr int QB = 16, KW = 32;
-#else
-  const int n = 32 * b + (lane & 31), h = lane >> 5;
-  constexpr int QB = 32, KW = 16;
-#endif
   half8 hi;
 #pragma unroll
   for (int j = 0; j < 8; ++j) hi[j] = (n < nq) ? (_Float16)q[(size_t)n * d + KW * s + 8 * h + j] : (_Float16)0.f;
@@ -93,9 +78,9 @@ __global__ void knn_rq_prep_kernel(const float* __restrict__ q, int nq, int d, i
     float t = INFINITY;
     if (n < nq) {
       const float v = samp[(size_t)n * kw + (J - 1)];
-      // (KNNX_MFMA16: the sample scan accumulates 16 products per MFMA, this scan 32 -- the same exact products in another f32
+      // (the sample scan accumulates 16 products per MFMA, this scan 32 -- the same exact products in another f32
       // summation order; a relative 1e-5 keeps the sample rows themselves above their own threshold)
-      t = v > -FLT_MAX ? v - slack - (KNNX_MFMA16 ? 1e-5f * fabsf(v) : 0.f) : -INFINITY;
+      t = v > -FLT_MAX ? v - slack - 1e-5f * fabsf(v) : -INFINITY;
     }
     thr[n] = t;
     cnt[n] = 0u;
@@ -118,27 +103,20 @@ struct RqTile {
   const char* base;  // tile + this wave's offset
   unsigned m0b;      // LDS address of the slot + this wave's offset
   unsigned vo;       // per-lane byte offset (row, half)
-  unsigned vo1;      // KNNX_MFMA16: the same for the pieces of the tile's second row half (rows 16 .. 31)
+  unsigned vo1;      // the same for the pieces of the tile's second row half (rows 16 .. 31)
 };
 // per-lane source offsets of a fragment-shaped DMA: [0] ordinary tiles, [1] the (possibly ragged) last tile, whose rows >= N re-read
-// row N - 1 (never admitted by the filter).  32x32x16: lane (row = l & 31, h = l >> 5) fetches 16 B of row `row` at column 8 h of
-// the k-step.  KNNX_MFMA16: lane (r = l & 15, q4 = l >> 4) fetches 16 B of row 16 * half + r at column 8 q4 of the slab.
+// row N - 1 (never admitted by the filter).  Lane (r = l & 15, q4 = l >> 4) fetches 16 B of row 16 * half + r at column 8 q4 of the slab.
 struct RqLaneOff {
   unsigned v[2], v1[2];
 };
 __device__ __forceinline__ RqLaneOff rq_lane_offsets(int lane, int D, int lrow /* last valid row inside the last tile */) {
   RqLaneOff o;
-#if KNNX_MFMA16
   const int r = lane & 15, q4 = lane >> 4;
   o.v[0] = (unsigned)(r * D * 2 + q4 * 16);
   o.v1[0] = (unsigned)((16 + r) * D * 2 + q4 * 16);
   o.v[1] = (unsigned)((r < lrow ? r : lrow) * D * 2 + q4 * 16);
   o.v1[1] = (unsigned)((16 + r < lrow ? 16 + r : lrow) * D * 2 + q4 * 16);
-#else
-  const int row = lane & 31, hb = lane >> 5;
-  o.v[0] = o.v1[0] = (unsigned)(row * D * 2 + hb * 16);
-  o.v[1] = o.v1[1] = (unsigned)((row < lrow ? row : lrow) * D * 2 + hb * 16);
-#endif
   return o;
 }
 template <int KS, int NW>
@@ -149,7 +127,7 @@ __device__ __forceinline__ RqTile rq_tile(const _Float16* __restrict__ X, int64_
   RqTile r;
   r.vo = tt == last ? lo.v[1] : lo.v[0];
   r.vo1 = tt == last ? lo.v1[1] : lo.v1[0];
-  // the wave's DPW pieces: 32x32x16 -- k-steps w DPW .. (32 B each); KNNX_MFMA16 -- slabs w DPW / 2 .. (64 B each), both halves
+  // the wave's DPW pieces: slabs w DPW / 2 .. (64 B each), both halves
   r.base = reinterpret_cast<const char*>(X) + (size_t)tt * TILE_BYTES + w * (DPW * 32);
   r.m0b = lds_base + slot * TILE_BYTES + w * (DPW * 1024);
   return r;
@@ -157,17 +135,10 @@ __device__ __forceinline__ RqTile rq_tile(const _Float16* __restrict__ X, int64_
 #define RQ_TILE(t_, slot_) rq_tile<KS, NW>(X, (t_), ntile, last, lane_off, lds_base, (slot_), w)
 template <int NW, int IDX>
 __device__ __forceinline__ void rq_issue_one(const RqTile& r) {
-#if KNNX_MFMA16
   const char* p = r.base + (IDX >> 1) * 64;  // piece IDX of the wave = slab IDX >> 1, row half IDX & 1
   asm volatile("s_add_u32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"((IDX & 1) ? r.vo1 : r.vo), "s"(p), "s"(r.m0b),
                "n"(IDX * 1024)
                : "memory", "scc");
-#else
-  constexpr int KOFF = IDX;  // k-step minus the wave's first one
-  const char* p = r.base + KOFF * 32;
-  asm volatile("s_add_u32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(r.vo), "s"(p), "s"(r.m0b), "n"(KOFF * 1024)
-               : "memory", "scc");
-#endif
 }
 template <int NW, int DPW, int IDX = 0>
 __device__ __forceinline__ void rq_issue_all(const RqTile& r) {
@@ -189,16 +160,10 @@ template <int N>
 __device__ __forceinline__ void rq_wait_lgkm() {
   asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
 }
-#if KNNX_MFMA16
 // piece S = 2 * slab + half: one LDS read feeds the 2 * QBW MFMAs of the wave's 16-query blocks against that half of the slab
 #define RQ_NQB(QBW) (2 * (QBW))
 #define RQ_NSL(KS) ((KS) / 2)
 typedef float4v rq_acc_t[2];  // [row half] of one 16-query block
-#else
-#define RQ_NQB(QBW) (QBW)
-#define RQ_NSL(KS) (KS)
-typedef float16v rq_acc_t;
-#endif
 template <int KS, int QBW, int NW, int DPW, int S>
 __device__ __forceinline__ void rq_ksteps(unsigned xa, i32x4 (&A)[4], rq_acc_t (&acc)[RQ_NQB(QBW)],
                                           const half8 (&Q)[RQ_NQB(QBW)][RQ_NSL(KS)], const RqTile& refill) {
@@ -206,15 +171,9 @@ __device__ __forceinline__ void rq_ksteps(unsigned xa, i32x4 (&A)[4], rq_acc_t (
     if constexpr (S + 3 < KS) rq_dsread<(S + 3) * 1024>(A[(S + 3) & 3], xa);
     rq_wait_lgkm<(KS - 1 - S < 3 ? KS - 1 - S : 3)>();  // reads issued after the one this step needs may stay in flight
     __builtin_amdgcn_sched_barrier(0);
-#if KNNX_MFMA16
 #pragma unroll
     for (int b = 0; b < 2 * QBW; ++b)
       acc[b][S & 1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, A[S & 3]), Q[b][S >> 1], acc[b][S & 1], 0, 0, 0);
-#else
-#pragma unroll
-    for (int b = 0; b < QBW; ++b)
-      acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8, A[S & 3]), Q[b][S], acc[b], 0, 0, 0);
-#endif
     __builtin_amdgcn_sched_barrier(0);
     // DMA piece S / (KS / DPW) of the refill behind this step's MFMAs: the DPW pieces are spread over the tile so that
     // their issue time overlaps with MFMAs already queued instead of holding all waves at the top of the tile
@@ -244,8 +203,8 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void knn_rq_scan_kernel(
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   // query blocks of QBS queries, NQB per wave, NSL fragments each; lane = (query column qcol, hb) -- hb is the row-group index of
-  // the lane inside a result block: 32x32x16: rows 4 hb + 8 i + e (hb < 2), KNNX_MFMA16: rows 4 hb + e of a 16-row half (hb < 4)
-  constexpr int NQB = RQ_NQB(QBW), NSL = RQ_NSL(KS), QBS = KNNX_MFMA16 ? 16 : 32;
+  // the lane inside a result block: rows 4 hb + e of a 16-row half (hb < 4)
+  constexpr int NQB = RQ_NQB(QBW), NSL = RQ_NSL(KS), QBS = 16;
   const int qcol = lane & (QBS - 1), hb = lane / QBS;
   float* st_s = reinterpret_cast<float*>(stage + w * RQ_STAGE * 12);
   uint32_t* st_r = reinterpret_cast<uint32_t*>(st_s + RQ_STAGE);
@@ -304,16 +263,8 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void knn_rq_scan_kernel(
     const RqTile refill = RQ_TILE(t + (int64_t)(NSLOT - 1) * gstride, slot == 0 ? NSLOT - 1 : slot - 1);
 
     rq_acc_t acc[NQB];
-#if KNNX_MFMA16
 #pragma unroll
     for (int b = 0; b < NQB; ++b) acc[b][0] = acc[b][1] = float4v{0.f, 0.f, 0.f, 0.f};
-#else
-#pragma unroll
-    for (int b = 0; b < QBW; ++b) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
-    }
-#endif
     // the k-loop: rq_ksteps<...> above (A fragments through a 4-deep register ring, the refill DMAs spread over the steps)
     const unsigned xa = lds_base + slot * TILE_BYTES + lane * 16;
     i32x4 A[4];
@@ -329,7 +280,6 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void knn_rq_scan_kernel(
     // runs with the matrix pipe idle.  (hipcc keeps the accumulators in AGPRs -- forcing them into VGPRs only adds copies --
     // so every value still costs one v_accvgpr_read.)
     bool any = false;
-#if KNNX_MFMA16
     // RQ_SCORE(b, r): the lane's r-th score of block b, r = 4 * half + e -> row row0 + 16 * half + e
 #define RQ_SCORE(b, r) acc[b][(r) >> 2][(r) & 3]
 #define RQ_ROWOFF(r) (16 * ((r) >> 2) + ((r) & 3))
@@ -341,22 +291,6 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void knn_rq_scan_kernel(
       const float m2 = __builtin_fmaxf(acc[b][1][2], acc[b][1][3]);
       any |= __builtin_fmaxf(__builtin_fmaxf(m0, m1), m2) >= tq[b];
     }
-#else
-#define RQ_SCORE(b, r) acc[b][r]
-#define RQ_ROWOFF(r) (((r) & 3) + 8 * ((r) >> 2))
-    constexpr int NSC = 16;
-#pragma unroll
-    for (int b = 0; b < QBW; ++b) {
-      float m0 = __builtin_fmaxf(__builtin_fmaxf(acc[b][0], acc[b][1]), acc[b][2]);
-      float m1 = __builtin_fmaxf(__builtin_fmaxf(acc[b][3], acc[b][4]), acc[b][5]);
-      float m2 = __builtin_fmaxf(__builtin_fmaxf(acc[b][6], acc[b][7]), acc[b][8]);
-      float m3 = __builtin_fmaxf(__builtin_fmaxf(acc[b][9], acc[b][10]), acc[b][11]);
-      float m4 = __builtin_fmaxf(__builtin_fmaxf(acc[b][12], acc[b][13]), acc[b][14]);
-      m0 = __builtin_fmaxf(__builtin_fmaxf(m0, m1), m2);
-      m3 = __builtin_fmaxf(__builtin_fmaxf(m3, m4), acc[b][15]);
-      any |= __builtin_fmaxf(m0, m3) >= tq[b];
-    }
-#endif
     if (__builtin_amdgcn_ballot_w64(any) != 0ull) {  // a hit somewhere in the wave: ~1 tile step in 8
       bool vmem = false;
 #pragma unroll
@@ -435,7 +369,6 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void knn_rq_scan_kernel(
 // Geometry: an int8 row of d bytes is an fp16 row of d / 2 columns to the tile / DMA helpers above: KS = d / 32 pieces of
 // (16 rows x 64 bytes) per 32-row tile, lane (r = l & 15, q4 = l >> 4) holds bytes 16 q4 .. + 16 of the piece's 64.
 // =============================================================================================
-#if KNNX_MFMA16
 typedef int i32x4v __attribute__((ext_vector_type(4)));
 
 // column maxima: colmax_enc[j] = max_i |x_ij| as the bits of a non-negative float (integer order = float order)
@@ -954,15 +887,13 @@ __global__ __launch_bounds__(256) void knn_i8_proof_kernel(int nq, int k, const 
   }
   if (threadIdx.x == 0 && stats) atomicAdd(&stats[0], (unsigned long long)nq);
 }
-#endif  // KNNX_MFMA16
 
-int i8_supported(int d) { return KNNX_MFMA16 && (d == 512 || d == 768 || d == 1024) ? 1 : 0; }
+int i8_supported(int d) { return d == 512 || d == 768 || d == 1024 ? 1 : 0; }
 
 // quantise rows with the column scales that exist (also used for rows added later: values beyond +-127 c clamp, and A / B -- which
 // are maxima over the rows as stored -- grow with them, so the bound stays a bound)
 hipError_t launch_i8_quant(const _Float16* X, int64_t N, int64_t row_from, int64_t row_to, int d, const float* colscale, const I8Dom& dom,
                            int8_t* X8, int* ab_enc, hipStream_t st) {
-#if KNNX_MFMA16
   // rows [row_from, row_to) of an image that covers rows [0, N) (row_to <= N); whole half tiles are written: rows below row_from that
   // share its half tile are re-quantised to the same bytes, rows at or beyond N become zeros
   const int64_t h0 = row_from >> 4, h1 = (std::max(row_to, row_from) + 15) >> 4;
@@ -972,14 +903,10 @@ hipError_t launch_i8_quant(const _Float16* X, int64_t N, int64_t row_from, int64
   const unsigned grid = (unsigned)std::min<int64_t>((h1p - h0 + 3) / 4, 256 * 16);
   hipLaunchKernelGGL(knn_i8_quant_kernel, dim3(grid), dim3(256), 0, st, X, N, h0, h1p, d, colscale, dom, X8, ab_enc);
   return hipGetLastError();
-#else
-  return hipErrorInvalidValue;
-#endif
 }
 
 // column scales over ALL N rows (the image itself may hold fewer: launch_i8_quant); resets A and B
 hipError_t launch_i8_scales(const _Float16* X, int64_t N, int d, int* colmax_enc, float* colscale, int* ab_enc, hipStream_t st) {
-#if KNNX_MFMA16
   hipError_t e = hipMemsetAsync(colmax_enc, 0, (size_t)d * sizeof(int), st);
   if (e != hipSuccess) return e;
   e = hipMemsetAsync(ab_enc, 0, 2 * sizeof(int), st);
@@ -988,25 +915,17 @@ hipError_t launch_i8_scales(const _Float16* X, int64_t N, int d, int* colmax_enc
   hipLaunchKernelGGL(knn_i8_colmax_kernel, dim3(g1), dim3(256), 0, st, X, N, d, colmax_enc);
   hipLaunchKernelGGL(knn_i8_colscale_kernel, dim3((d + 255) / 256), dim3(256), 0, st, colmax_enc, d, colscale);
   return hipGetLastError();
-#else
-  return hipErrorInvalidValue;
-#endif
 }
 
 hipError_t launch_i8_prep(const float* q_dev, int nq, int d, const float* colscale, const I8Dom& dom, const int* ab_enc, const int* maxnorm,
                           const float* samp, int kw, int J, int planes, int refine, int8_t* qfrag8, int8_t* qdom, int* thr_i, float* thr_lb,
                           float* thr_rest, unsigned* cnt, unsigned* lost, hipStream_t st) {
-#if KNNX_MFMA16
   if (dom.n > 0 && (planes != 1 || !qdom)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(knn_i8_prep_kernel, dim3(256), dim3(64), 0, st, q_dev, nq, d, colscale, dom, ab_enc, maxnorm, samp, kw, J, planes, refine,
                      qfrag8, qdom, thr_i, thr_lb, thr_rest, cnt, lost);
   return hipGetLastError();
-#else
-  return hipErrorInvalidValue;
-#endif
 }
 
-#if KNNX_MFMA16
 template <int KS, int NW, int NSLOT, int PL = 1, bool DOM = false>
 static hipError_t launch_rq8_scan_cfg(const int8_t* X8, int64_t N, const int8_t* qfrag8, const int8_t* qdom, const int* thr_i, unsigned* cnt,
                                       unsigned cap, float* hit_s, uint32_t* hit_r, unsigned* lost, int grid, int tstep, hipStream_t st) {
@@ -1017,9 +936,8 @@ static hipError_t launch_rq8_scan_cfg(const int8_t* X8, int64_t N, const int8_t*
   hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), smem, st, X8, N, qfrag8, qdom, thr_i, cnt, cap, hit_s, hit_r, lost, tstep);
   return hipGetLastError();
 }
-#endif
 
-#if defined(CLIPX_ABLATE) && KNNX_MFMA16
+#ifdef CLIPX_ABLATE
 extern "C" int knnx_dbg_rq8_phases(long long* host, int n) {
   return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_rq8_phase), (size_t)n * sizeof(long long));
 }
@@ -1028,14 +946,13 @@ hipError_t launch_rq8_scan(const int8_t* X8, int64_t N, int d, int nq, int plane
                            unsigned* cnt, unsigned cap, float* hit_s, uint32_t* hit_r, unsigned* lost, int grid, int tstep, hipStream_t st) {
   // qdom != nullptr: the index has dominant columns (one plane; I8Dom)
   if (tstep < 1 || (qdom && planes != 1)) return hipErrorInvalidValue;
-#if defined(CLIPX_ABLATE) && KNNX_MFMA16
+#ifdef CLIPX_ABLATE
   {
     static const int tm = getenv("KNNX_RQ8_TIMER") ? atoi(getenv("KNNX_RQ8_TIMER")) : 0;
     static bool set = false;
     if (!set) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_rq8_timer), &tm, sizeof(int)); set = true; }
   }
 #endif
-#if KNNX_MFMA16
 #define RQ8_ARGS X8, N, qfrag8, qdom, thr_i, cnt, cap, hit_s, hit_r, lost, grid, tstep, st
   if (planes == 2) {  // two query planes: 4 waves x 32 queries (twice the fragments per query: 192 registers at d = 768)
     if (nq > 128) return hipErrorInvalidValue;
@@ -1063,19 +980,12 @@ hipError_t launch_rq8_scan(const int8_t* X8, int64_t N, int d, int nq, int plane
     default: return hipErrorInvalidValue;
   }
 #undef RQ8_ARGS
-#else
-  return hipErrorInvalidValue;
-#endif
 }
 
 hipError_t launch_i8_proof(int nq, int k, const float* D, const float* thr_lb, const unsigned* cnt, unsigned cap, const unsigned* lost,
                            unsigned* need, unsigned* gate, unsigned long long* stats, hipStream_t st) {
-#if KNNX_MFMA16
   hipLaunchKernelGGL(knn_i8_proof_kernel, dim3(1), dim3(256), 0, st, nq, k, D, thr_lb, cnt, cap, lost, need, gate, stats);
   return hipGetLastError();
-#else
-  return hipErrorInvalidValue;
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1097,13 +1007,13 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void knn_assign_kernel(const _Floa
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  constexpr int NQB = RQ_NQB(1), NSL = RQ_NSL(KS), QBS = KNNX_MFMA16 ? 16 : 32;
+  constexpr int NQB = RQ_NQB(1), NSL = RQ_NSL(KS), QBS = 16;
   const int qcol = lane & (QBS - 1), hb = lane / QBS;
   const _Float16* X = C;  // the streamed operand (RQ_TILE below)
   const int64_t N = nlist;
 
   // this wave's 32 points as B fragments: lane (qcol, hb) holds point[16 s + 8 hb .. + 8] of every k-step s
-  // (KNNX_MFMA16: two blocks of 16 points, point[32 s + 8 hb .. + 8] of every slab s)
+  // (two blocks of 16 points, point[32 s + 8 hb .. + 8] of every slab s)
   int64_t pidx[NQB];
   half8 Q[NQB][NSL];
 #pragma unroll
@@ -1112,7 +1022,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void knn_assign_kernel(const _Floa
     const int64_t prow = pidx[b] < n ? pidx[b] : n - 1;
     const half8* src = reinterpret_cast<const half8*>(P + (size_t)prow * D) + hb;
 #pragma unroll
-    for (int s = 0; s < NSL; ++s) Q[b][s] = src[(KNNX_MFMA16 ? 4 : 2) * s];
+    for (int s = 0; s < NSL; ++s) Q[b][s] = src[4 * s];
   }
 #pragma unroll
   for (int b = 0; b < NQB; ++b)
@@ -1141,13 +1051,8 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void knn_assign_kernel(const _Floa
     __builtin_amdgcn_sched_barrier(0);
     const RqTile refill = RQ_TILE(t + (NSLOT - 1), slot == 0 ? NSLOT - 1 : slot - 1);
     rq_acc_t acc[NQB];
-#if KNNX_MFMA16
 #pragma unroll
     for (int b = 0; b < NQB; ++b) acc[b][0] = acc[b][1] = float4v{0.f, 0.f, 0.f, 0.f};
-#else
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[0][r] = 0.f;
-#endif
     const unsigned xa = lds_base + slot * TILE_BYTES + lane * 16;
     i32x4 A[4];
     rq_dsread<0>(A[0], xa);
@@ -1162,7 +1067,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void knn_assign_kernel(const _Floa
 #pragma unroll
     for (int b = 0; b < NQB; ++b) {
 #pragma unroll
-      for (int r = 0; r < (KNNX_MFMA16 ? 8 : 16); ++r) {
+      for (int r = 0; r < 8; ++r) {
         const int row = row0 + RQ_ROWOFF(r);
         const float sc = RQ_SCORE(b, r);
         const bool take = sc > best[b] && (!ragged || row < (int)N);
@@ -1173,7 +1078,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void knn_assign_kernel(const _Floa
     slot = slot + 1 == NSLOT ? 0 : slot + 1;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // tail reloads still in flight
-  // the lane groups of a point (2 half-waves; KNNX_MFMA16: 4 quarter-waves) saw different rows of every tile
+  // the lane groups of a point (4 quarter-waves) saw different rows of every tile
 #pragma unroll
   for (int b = 0; b < NQB; ++b) {
 #pragma unroll
@@ -1212,8 +1117,8 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void knn_rotate_kernel(const _Floa
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  constexpr int NQB = RQ_NQB(1), NSL = RQ_NSL(KS), QBS = KNNX_MFMA16 ? 16 : 32;
-  constexpr int NSC = KNNX_MFMA16 ? 8 : 16, NG = NSC / 4;
+  constexpr int NQB = RQ_NQB(1), NSL = RQ_NSL(KS), QBS = 16;
+  constexpr int NSC = 8, NG = NSC / 4;
   const int qcol = lane & (QBS - 1), hb = lane / QBS;
   const _Float16* X = W;  // the streamed operand (RQ_TILE below)
   constexpr int64_t N = 2 * DO;
@@ -1226,7 +1131,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void knn_rotate_kernel(const _Floa
     const int64_t prow = pidx[b] < n ? pidx[b] : n - 1;
     const half8* src = reinterpret_cast<const half8*>(P + (size_t)prow * D) + hb;
 #pragma unroll
-    for (int s = 0; s < NSL; ++s) Q[b][s] = src[(KNNX_MFMA16 ? 4 : 2) * s];
+    for (int s = 0; s < NSL; ++s) Q[b][s] = src[4 * s];
   }
 #pragma unroll
   for (int b = 0; b < NQB; ++b)
@@ -1258,13 +1163,8 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void knn_rotate_kernel(const _Floa
           for (int g = 0; g < NG; ++g)
             if (pidx[b] < n) *reinterpret_cast<half4*>(Y + (size_t)pidx[b] * DO + col0 + RQ_ROWOFF(4 * g)) = pend[b][g];
       }
-#if KNNX_MFMA16
 #pragma unroll
       for (int b = 0; b < NQB; ++b) acc[b][0] = acc[b][1] = float4v{0.f, 0.f, 0.f, 0.f};
-#else
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[0][r] = 0.f;
-#endif
     } else {
 #pragma unroll
       for (int b = 0; b < NQB; ++b)
@@ -1467,8 +1367,8 @@ int rq_queries_per_pass(int d) { return d == 1024 ? 128 : (d == 512 || d == 768 
 
 hipError_t launch_rq_prep(const float* q_dev, int nq, int d, _Float16* qfrag, const float* samp, int kw, int J, float slack,
                           float* thr, unsigned* cnt, unsigned* lost, hipStream_t st) {
-  const int nblk = rq_queries_per_pass(d) / (KNNX_MFMA16 ? 16 : 32);
-  hipLaunchKernelGGL(knn_rq_prep_kernel, dim3(d / (KNNX_MFMA16 ? 32 : 16), nblk), dim3(64), 0, st, q_dev, nq, d, nblk, qfrag, samp, kw, J, slack, thr, cnt, lost);
+  const int nblk = rq_queries_per_pass(d) / 16;
+  hipLaunchKernelGGL(knn_rq_prep_kernel, dim3(d / 32, nblk), dim3(64), 0, st, q_dev, nq, d, nblk, qfrag, samp, kw, J, slack, thr, cnt, lost);
   return hipGetLastError();
 }
 

@@ -97,5 +97,5 @@ def test_inline_asm_vmem_hazards():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     csrc = os.path.join(root, "clip-retrieval_amd", "csrc")
     r = subprocess.run([sys.executable, os.path.join(root, "tools", "check_isa.py"), os.path.join(csrc, "gemm256sp.hip"),
-                        os.path.join(csrc, "clip_kernels.hip")], capture_output=True, text=True)
+                        os.path.join(csrc, "gemm128.hip"), os.path.join(csrc, "gemm256w4.hip")], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr

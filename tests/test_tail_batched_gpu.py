@@ -1,4 +1,4 @@
-"""The batched projection tail (clip_kernels.hip: tail_proj_batched_kernel) against the per-sample one (tail_proj_kernel).
+"""The batched projection tail (tail_kernels.hip: tail_proj_batched_kernel) against the per-sample one (tail_proj_kernel).
 
 launch_tail runs the batched kernel (8 samples per workgroup) from B * d * E >= 2^26 multiply-adds on and the per-sample kernel
 below.  Both must write the same bytes: the embeddings of one batch are compared, bitwise, with the same samples encoded in

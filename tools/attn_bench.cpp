@@ -226,6 +226,7 @@ int main(int argc, char** argv) {
       printf("  phases, shader cycles per wave (3 query blocks): staging %.0f | S + max %.0f | exp + PV %.0f | store %.0f\n", s4[0], s4[1], s4[2], s4[3]);
     }
   }
+  dbgf = (dbg_fn)dlsym(h, "clipx_dbg_attn_pk_phase");  // each kernel file owns its phase array (no relocatable device code)
   if (dbgf && getenv("CLIPX_ATTN_PK_TIMER") && atoi(getenv("CLIPX_ATTN_PK_TIMER"))) {
     // persistent kernel (attention_pk_kernel): per wave index, averaged over the workgroups, shader cycles of the LAST launch
     const int nwg = std::min(B * H, 256);

@@ -219,6 +219,7 @@ SIGNATURES = {
     "clipx_profile_enable": (C.c_int, [_P, C.c_int]),
     "clipx_profile_get": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "clipx_profile_events": (C.c_int, [_P]),
+    "clipx_profile_gemm_device": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "clipx_last_error": (C.c_char_p, []),
 }
 

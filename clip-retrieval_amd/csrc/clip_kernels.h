@@ -1,33 +1,28 @@
 // clip_kernels.h -- launchers of the gfx950 CLIP encoder kernels (internal; public ABI: include/clipx.h)
 #pragma once
 #include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
 #include <stdint.h>
 #include "clipx_gemm_plan.h"  // GemmEpilogue, GemmVariant, the gemm256_* planner functions
+#include "clipx_stamp_slots.h"
 
 namespace clipx {
 
 typedef __bf16 bf16;
 
-// Per-dispatch timing (the GEMM brackets of clipx_profile_enable, clipx_encode.hip ProfScope): start / stop event pairs that the
-// kernels of one launch_gemm call take, one pair per kernel, attached to the kernel's own dispatch packet instead of being
-// recorded as marker packets in front of and behind it -- nothing sits between back-to-back dispatches.
+// In-kernel timing (the GEMM brackets of clipx_profile_enable, clipx_encode.hip ProfScope): every kernel launch_gemm can issue takes
+// a StampSlot* as its last argument (clipx_stamp_slots.h; null = not profiled, the kernel does nothing more than test it) and
+// writes its own first start and last end into it.  The dispatch carries nothing: no event, no completion signal, no marker.
+// LaunchEvents is where the slots of one launch_gemm call come from, one per kernel.
 struct LaunchEvents {
-  hipEvent_t* ev;  // ev[2 i] / ev[2 i + 1]: start / stop of the i-th kernel launched
-  int cap, used;   // pairs available / handed out so far
-  int untimed;     // kernels launched after the pairs ran out (their time is missing from the scope: clipx_profile_get reports it)
+  void* ctx;
+  StampSlot* (*next)(void* ctx);  // a filled slot on the device, or null when none is to be had (the kernel then runs unstamped)
 };
 
-// hipLaunchKernelGGL, with the next event pair of `le` on the dispatch when there is one (le may be null)
+// hipLaunchKernelGGL with the next slot of `le` (null when le is) appended to the arguments
 template <class K, class... Args>
 inline void launch_with_events(LaunchEvents* le, K kern, const dim3& grid, const dim3& block, size_t smem, hipStream_t st, Args... args) {
-  if (le && le->used < le->cap) {
-    hipEvent_t* p = le->ev + 2 * le->used++;
-    hipExtLaunchKernelGGL(kern, grid, block, (uint32_t)smem, st, p[0], p[1], 0, args...);
-  } else {
-    if (le) ++le->untimed;
-    hipLaunchKernelGGL(kern, grid, block, smem, st, args...);
-  }
+  StampSlot* slot = le ? le->next(le->ctx) : nullptr;
+  hipLaunchKernelGGL(kern, grid, block, smem, st, args..., slot);
 }
 
 struct GemmArgs {
@@ -57,7 +52,7 @@ struct GemmArgs {
                           // compute it (launch_gemm runs launch_rowstats on those rows); the rows the 4-wave 256x256 kernel takes get
                           // their statistics from the A fragments inside its K loop instead (gemm256w4.hip, STATS) and are not written
   int* range_flag;        // (stats_eps > 0) raised when a row of A holds inf / NaN (launch_rowstats)
-  LaunchEvents* events;   // null, or the source of one start / stop event pair for every kernel this GEMM launches
+  LaunchEvents* events;   // null, or the source of one stamp slot for every kernel this GEMM launches
 };
 
 hipError_t launch_gemm(const GemmArgs& g, hipStream_t st);
@@ -81,6 +76,8 @@ hipError_t launch_rowstats(const void* x16, float* rstd, int M, int d, float eps
 hipError_t launch_fold_layernorm(const float* W, const float* gamma, const float* beta, const float* bias, bf16* Wf, float* cf,
                                  int N, int K, hipStream_t st, int f16 = 0);
 hipError_t launch_fill_f32(float* p, float v, int64_t n, hipStream_t st);
+// every entry of n stamp slots <- {~0, 0} (clipx_stamp_slots.h: a slot is handed out filled)
+hipError_t launch_fill_stamps(StampSlot* slots, int64_t n, hipStream_t st);
 
 // pixels -> bf16 patch matrix [B*T, Kp] (row b*T is the all-zero class-token row; k = c*P*P + iy*P + ix)
 // fmt 0: f32 NCHW already normalised (the reference's `image_tensor`); fmt 1: u8 NHWC, normalised here

@@ -21,23 +21,31 @@ static hipEvent_t prof_take(Profiler& p) {
   return p.created.back();
 }
 
-// Brackets the launches of one scope when its kind is being profiled.  GEMMs (kind 0) get the dispatch form: events() is handed
-// to launch_gemm through GemmArgs and every kernel takes a pair on its own dispatch -- two marker packets around each of the ~136
-// GEMM launches of a step kept back-to-back dispatches apart and cost 1.1 ms of a 43.7 ms ViT-L/14 step.  The other
-// kinds, CLIPX_OPT_PROF_MARKERS, and a stream that is being captured keep the marker form.
+// Brackets the launches of one scope when its kind is being profiled.  GEMMs (kind 0) get the stamp form: events() is handed to
+// launch_gemm through GemmArgs, every kernel it launches takes the next free slot of the profiler as an argument and writes its own
+// first start and last end into it (gemm_common.h stamp_start / stamp_end) -- the dispatches are plain launches that carry nothing,
+// and nothing is recorded on the stream.  (Two marker packets around each of the ~136 GEMM launches of a step kept back-to-back
+// dispatches apart and cost 1.1 ms of a 43.7 ms ViT-L/14 step; a completion signal with timestamps on each dispatch 0.5 ms of 42.0:
+// DESIGN 5.)  The other kinds, CLIPX_OPT_PROF_MARKERS, and a stream that is being captured keep the marker form.
 struct ProfScope {
   Profiler& p;
   hipStream_t st;
   ProfEvent e{};
   LaunchEvents le{};
-  bool on = false, dispatch = false;
+  bool on = false;
   ProfScope(clipx_handle* h, hipStream_t st_, int kind, double flops) : p(h->prof), st(st_) {
     if (!(p.mask & (1 << kind))) return;
     e.kind = kind;
     e.flops = flops;
-    dispatch = kind == 0 && !p.markers && !stream_is_capturing(st);
-    const int n = dispatch ? 2 * PROF_MAX_PAIRS : 2;
-    for (int i = 0; i < n; ++i) {
+    e.st = st;
+    e.stamps = kind == 0 && !p.markers && !stream_is_capturing(st);
+    if (e.stamps) {
+      e.slot0 = p.book.in_use();
+      le = LaunchEvents{this, &ProfScope::next_slot};
+      on = true;
+      return;
+    }
+    for (int i = 0; i < 2; ++i) {
       e.ev[i] = prof_take(p);
       if (!e.ev[i]) {  // no event to be had: this scope goes untimed
         while (i > 0) p.unused.push_back(e.ev[--i]);
@@ -45,23 +53,39 @@ struct ProfScope {
       }
     }
     on = true;
-    if (dispatch) le = LaunchEvents{e.ev, PROF_MAX_PAIRS, 0, 0};
-    else (void)hipEventRecord(e.ev[0], st);
+    (void)hipEventRecord(e.ev[0], st);
   }
-  LaunchEvents* events() { return on && dispatch ? &le : nullptr; }
+  // The next kernel's slot.  Only when the chunks have run out is anything allocated here: one more chunk, filled and synchronised
+  // (add_chunk) before any of its slots is handed out.
+  static StampSlot* next_slot(void* self) {
+    ProfScope& s = *static_cast<ProfScope*>(self);
+    int id = s.p.book.take();
+    if (id < 0) {
+      if (s.p.add_chunk(s.st) != hipSuccess) {
+        (void)hipGetLastError();
+        s.p.starved = true;
+        return nullptr;
+      }
+      id = s.p.book.take();
+    }
+    ++s.e.nslots;
+    return s.p.slot(id);
+  }
+  LaunchEvents* events() { return on && e.stamps ? &le : nullptr; }
   ~ProfScope() {
     if (!on) return;
-    if (dispatch) {
-      e.pairs = le.used;
-      e.untimed = le.untimed;
-      for (int i = 2 * le.used; i < 2 * PROF_MAX_PAIRS; ++i) p.unused.push_back(e.ev[i]);
-    } else {
-      (void)hipEventRecord(e.ev[1], st);
-      e.pairs = 1;
-    }
+    if (!e.stamps) (void)hipEventRecord(e.ev[1], st);
     p.scopes.push_back(e);
   }
 };
+
+// launch_gemm as one profiled scope of `flops` (run_gemm below; the test entry clipx_profile_gemm_device, clipx_hooks.hip)
+int clipx::profiled_gemm(clipx_handle* h, GemmArgs& g, hipStream_t st, double flops) {
+  ProfScope ps(h, st, 0, flops);
+  g.events = ps.events();
+  HIPCHK(launch_gemm(g, st));
+  return 0;
+}
 
 static int run_gemm(clipx_handle* h, const Call& c, const bf16* A, const bf16* W, const float* bias, void* out,
                     const float* table, int T, int M, int N, int K, int epi, const float* rowscale = nullptr, bool f16 = false,
@@ -77,10 +101,7 @@ static int run_gemm(clipx_handle* h, const Call& c, const bf16* A, const bf16* W
   // by the unsplit kernels, whose rows do not depend on the batch they travel in (bitwise); a B = 1 row differs from the same
   // sample inside a batch by f32 summation order only
   if (c.single_query) { g.splitk_ws = h->ws.splitk; g.splitk_ws_bytes = h->ws.splitk_bytes; }
-  ProfScope ps(h, c.st, 0, 2.0 * (M - pad_rows) * (double)N * K);  // (pad rows of a ragged text batch are not work the model asks for)
-  g.events = ps.events();
-  HIPCHK(launch_gemm(g, c.st));
-  return 0;
+  return profiled_gemm(h, g, c.st, 2.0 * (M - pad_rows) * (double)N * K);  // (pad rows of a ragged text batch are not work the model asks for)
 }
 
 // where run_layers leaves the pooled rows (fp16 [B, width]) when it pools the last block: behind the gathered attention rows
@@ -289,7 +310,16 @@ int clipx::text_chunk(clipx_handle* h, const Call& c, const int32_t* ids_dev, in
 extern "C" int clipx_profile_enable(clipx_handle* h, int on) {
   if (!h) return fail(CLIPX_E_ARG, "handle is null");
   std::lock_guard<std::mutex> lk(h->mu);
-  h->prof.mask = on == 1 ? 15 : ((on >> 1) & 15);  // 1 = every kind; otherwise bit (kind + 1) selects a kind
+  Profiler& p = h->prof;
+  const int mask = on == 1 ? 15 : ((on >> 1) & 15);  // 1 = every kind; otherwise bit (kind + 1) selects a kind
+  if ((mask & 1) && p.chunks.empty()) {
+    // the GEMMs' stamp slots: the first chunk is made and filled here, so that no scope has to (ProfScope::next_slot)
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipDeviceGetAttribute(&p.clock_khz, hipDeviceAttributeWallClockRate, h->device));
+    if (p.clock_khz <= 0) return fail(CLIPX_E_HIP, "hipDeviceAttributeWallClockRate is not positive");
+    HIPCHK(p.add_chunk(h->stream));
+  }
+  p.mask = mask;
   return CLIPX_OK;
 }
 
@@ -303,31 +333,70 @@ extern "C" int clipx_profile_get(clipx_handle* h, int kind, int64_t* launches, d
   int64_t n = 0;
   double t = 0.0, f = 0.0;
   std::vector<ProfEvent> keep;
-  hipError_t err = hipSuccess;  // the first failure; the loop still consumes every scope, so that no event is handed back twice
-  int untimed = 0;
+  hipError_t err = hipSuccess;  // the first failure; everything below still consumes every scope and every slot, so that nothing is handed out twice
+  // ---- stamp form (all of it is kind 0): wait for the streams the scopes ran on, bring the slots back in one copy per run of ids
+  std::vector<std::pair<int, int>> runs;
+  if (kind == 0 && p.book.in_use() > 0) {
+    std::vector<hipStream_t> streams;
+    for (auto& e : p.scopes)
+      if (e.stamps && std::find(streams.begin(), streams.end(), e.st) == streams.end()) streams.push_back(e.st);
+    for (hipStream_t s : streams) {
+      hipError_t r = hipStreamSynchronize(s);
+      if (r != hipSuccess && err == hipSuccess) err = r;
+    }
+    runs = p.book.runs();
+    p.host.resize(p.book.capacity());
+    for (auto& r : runs) {
+      hipError_t c = hipMemcpy(&p.host[r.first], p.slot(r.first), (size_t)r.second * sizeof(StampSlot), hipMemcpyDeviceToHost);
+      if (c != hipSuccess && err == hipSuccess) err = c;
+    }
+  }
+  int starved = 0;  // stamp scopes with a slot that still holds its fill value, or with no slot at all: some kernel did not run
   for (auto& e : p.scopes) {
     if (e.kind != kind) {
       keep.push_back(e);
       continue;
     }
-    for (int i = 0; i < e.pairs; ++i) {
+    if (e.stamps) {
+      unsigned long long ticks = 0;
+      bool ok = e.nslots > 0;
+      for (int i = 0; i < e.nslots && err == hipSuccess; ++i) {
+        unsigned long long t0 = 0, t1 = 0;
+        if (stamp_reduce(p.host[e.slot0 + i], &t0, &t1)) ticks += t1 - t0;
+        else ok = false;
+      }
+      if (!ok) ++starved;
+      t += (double)ticks / (double)p.clock_khz;  // ticks / kHz = ms
+    } else {
       float dt = 0.f;
-      hipError_t r = hipEventSynchronize(e.ev[2 * i + 1]);
-      if (r == hipSuccess) r = hipEventElapsedTime(&dt, e.ev[2 * i], e.ev[2 * i + 1]);
+      hipError_t r = hipEventSynchronize(e.ev[1]);
+      if (r == hipSuccess) r = hipEventElapsedTime(&dt, e.ev[0], e.ev[1]);
       if (r != hipSuccess && err == hipSuccess) err = r;
       t += dt;
+      for (int i = 0; i < 2; ++i) p.unused.push_back(e.ev[i]);
     }
     f += e.flops;
     ++n;
-    untimed += e.untimed;
-    for (int i = 0; i < 2 * e.pairs; ++i) p.unused.push_back(e.ev[i]);
   }
   p.scopes.swap(keep);
+  if (kind == 0 && p.book.in_use() > 0) {  // the slots that were read go back filled
+    for (auto& r : runs) {
+      hipError_t c = launch_fill_stamps(p.slot(r.first), r.second, h->stream);
+      if (c != hipSuccess && err == hipSuccess) err = c;
+    }
+    hipError_t c = hipStreamSynchronize(h->stream);
+    if (c != hipSuccess && err == hipSuccess) err = c;
+    p.book.reset();
+  }
+  const bool out_of_slots = kind == 0 && p.starved;
+  if (kind == 0) p.starved = false;
   if (err != hipSuccess) {
     (void)hipGetLastError();
     return fail(CLIPX_E_HIP, std::string("clipx_profile_get: ") + hipGetErrorString(err));
   }
-  if (untimed) return fail(CLIPX_E_STATE, "internal: a GEMM launched more kernels than it had timing events for (PROF_MAX_PAIRS)");
+  if (out_of_slots) return fail(CLIPX_E_NOMEM, "clipx_profile_get: the stamp slots ran out and no further chunk could be allocated; some GEMM kernels ran untimed");
+  if (starved)
+    return fail(CLIPX_E_STATE, "clipx_profile_get: " + std::to_string(starved) + " profiled GEMM scope(s) hold a stamp slot no kernel wrote, or launched no kernel at all (the launch was refused)");
   if (launches) *launches = n;
   if (ms) *ms = t;
   if (flops) *flops = f;

@@ -71,6 +71,26 @@ extern "C" int clipx_gemm_f16_ln_device(int device, const void* A_f16, const voi
   return gemm_hook(device, A_f16, W_f16, bias, out_16bit, M, N, K, epi, rstd_buf, nullptr, stream, 1, eps);
 }
 
+// One GEMM through a handle's profiler, exactly as the encoder issues its own (clipx_encode.hip run_gemm: one scope, the handle's
+// variant and compute units, 2 M N K flops) -- for the tests of the GEMM brackets, which need every kernel family on a shape of
+// their choosing.  Only what a kernel would dereference is validated here (the operands, the bias or the table); which shapes,
+// epilogues and operand types have a plan is launch_gemm's business, and what it refuses comes back as CLIPX_E_HIP with the scope
+// recorded (that is one of the things tested).
+extern "C" int clipx_profile_gemm_device(clipx_handle* h, const void* A, const void* W, const float* bias_or_null, void* out,
+                                         const float* table_or_null, int T, int M, int N, int K, int epi, int f16,
+                                         const float* rowscale_or_null, void* stream) {
+  if (!h || !A || !W || !out || M <= 0 || N <= 0 || K <= 0) return fail(CLIPX_E_ARG, "bad gemm arguments");
+  if (epi == EPI_TABLE_F32 ? (!table_or_null || T <= 0) : !bias_or_null)
+    return fail(CLIPX_E_ARG, "epilogue 4 needs its table and T > 0, every other epilogue its bias");
+  std::lock_guard<std::mutex> lk(h->mu);
+  HIPCHK(hipSetDevice(h->device));
+  GemmArgs g{};
+  g.A = (const bf16*)A; g.W = (const bf16*)W; g.bias = bias_or_null; g.out = out; g.table = table_or_null; g.T = T;
+  g.M = M; g.N = N; g.K = K; g.epi = epi; g.variant = h->gemm_variant; g.n_cu = h->n_cu;
+  g.rowscale = rowscale_or_null; g.f16 = f16 ? 1 : 0;
+  return profiled_gemm(h, g, (hipStream_t)stream, 2.0 * M * (double)N * K);
+}
+
 // the T limits of the attention entry points (clipx_attn_plan.h): nullptr when T is within them, else the message; nothing is launched
 static const char* attention_limit(int T, int dh, int causal) {
   if (T > clipx::ATTN_LONG_MAX_T) return "sequence longer than 608 tokens";

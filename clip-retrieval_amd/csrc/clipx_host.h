@@ -275,25 +275,45 @@ struct GraphCache {
   bool on = true;
 };
 
-constexpr int PROF_MAX_PAIRS = 4;  // kernels one launch_gemm call issues at most (row statistics, bulk, leftover rows / the split-K pair)
-
-// One bracketed launch scope.  Marker form: ev[0] / ev[1] are recorded on the stream in front of and behind the scope's launches
-// (pairs = 1).  Dispatch form (GEMMs): every kernel of the scope carries its own start / stop pair on its dispatch, and the
-// scope's time is the sum of its kernels' own elapsed times -- never an interval between events of different commands.
+// One bracketed launch scope.  Marker form: ev[0] / ev[1] are recorded on the stream in front of and behind the scope's launches.
+// Stamp form (GEMMs): every kernel of the scope was given a slot of its own and wrote its first start and last end into it; the
+// scope's time is the sum over its kernels of last_end - first_start -- never an interval across kernels.
 struct ProfEvent {
-  hipEvent_t ev[2 * PROF_MAX_PAIRS];
-  int pairs;
-  int untimed;  // kernels of the scope that found no pair left (PROF_MAX_PAIRS too small: clipx_profile_get fails)
+  hipEvent_t ev[2];   // marker form
+  bool stamps;        // stamp form: the scope's slots are the ids slot0 .. slot0 + nslots - 1 (scopes do not interleave: h->mu)
+  int slot0, nslots;
+  hipStream_t st;     // the stream the scope's launches went to
   int kind;
   double flops;
 };
 
+constexpr int PROF_CHUNK_SLOTS = 8192;  // slots per device chunk (8 MiB): 55 ViT-L/14 steps of 147 GEMM kernels between two clipx_profile_get
+
 struct Profiler {
-  int mask = 0;          // bit k set: launches of kind k (0 gemm, 1 attention, 2 layernorm, 3 other) are bracketed by hipEvents
-  bool markers = false;  // CLIPX_OPT_PROF_MARKERS: the marker form for the GEMMs as well (default: events on the dispatches)
+  int mask = 0;          // bit k set: launches of kind k (0 gemm, 1 attention, 2 layernorm, 3 other) are bracketed
+  bool markers = false;  // CLIPX_OPT_PROF_MARKERS: the marker form for the GEMMs as well (default: the kernels' own clock stamps)
   std::vector<Event> created;      // every timing event made so far (clipx_profile_events); the two below borrow from it
   std::vector<hipEvent_t> unused;  // free for reuse: clipx_profile_get hands back what it has read
   std::vector<ProfEvent> scopes;
+  // stamp form: the slots live in device chunks of PROF_CHUNK_SLOTS; `book` counts the ids handed out since the last read
+  StampBook book{PROF_CHUNK_SLOTS};
+  std::vector<DevBuf<StampSlot>> chunks;
+  std::vector<StampSlot> host;  // where clipx_profile_get reads the slots back to, indexed by slot id
+  int clock_khz = 0;            // hipDeviceAttributeWallClockRate, read once
+  bool starved = false;         // the slots ran out and no further chunk could be allocated: some kernel ran without a slot
+  StampSlot* slot(int id) const { return chunks[id / PROF_CHUNK_SLOTS].p + id % PROF_CHUNK_SLOTS; }
+  // one more chunk, filled on `st` and synchronised before its ids exist: whichever stream a later scope launches on, the fill
+  // has run (a scope that runs out of slots pays that wait once per 8 192 kernels; clipx_profile_enable pays it for the first chunk)
+  hipError_t add_chunk(hipStream_t st) {
+    DevBuf<StampSlot> c;
+    hipError_t e = c.alloc(PROF_CHUNK_SLOTS);
+    if (e == hipSuccess) e = launch_fill_stamps(c, PROF_CHUNK_SLOTS, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return e;
+    chunks.push_back(std::move(c));
+    book.add_chunk();
+    return hipSuccess;
+  }
 };
 
 }  // namespace clipx
@@ -355,6 +375,8 @@ inline size_t pix_bytes_per_image(const clipx_model_desc& d, int fmt) {
 // clipx_encode.hip: one chunk (B <= max_batch), everything on the device, asynchronous on c.st
 int vision_chunk(clipx_handle* h, const Call& c, const void* pix_dev, int B, int fmt, uint16_t* out_f16, float* out_f32);
 int text_chunk(clipx_handle* h, const Call& c, const int32_t* ids_dev, int B, uint16_t* out_f16, float* out_f32);
+// launch_gemm(g) on st as ONE profiled scope of `flops` (g.events is set here); the caller holds h->mu
+int profiled_gemm(clipx_handle* h, GemmArgs& g, hipStream_t st, double flops);
 
 }  // namespace clipx
 

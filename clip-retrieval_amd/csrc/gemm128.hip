@@ -34,7 +34,8 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const bf16* __restric
                                                           const float* __restrict__ bias, void* __restrict__ outp,
                                                           const float* __restrict__ table, int T, int M, int N,
                                                           int K, int row0, const float* __restrict__ rowscale,
-                                                          bf16* __restrict__ out16, int kz) {
+                                                          bf16* __restrict__ out16, int kz, StampSlot* stamp) {
+  stamp_start(stamp, blockIdx.x + blockIdx.y * gridDim.x);
   // kz > 0 (EPI_RAW_F32, DEEP only): split-K -- workgroup column blockIdx.y multiplies K-tiles [y * kz, (y + 1) * kz) and
   // writes its raw accumulators to outp + y * M * N
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -309,6 +310,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const bf16* __restric
       }
     }
   }
+  stamp_end(stamp, blockIdx.x + blockIdx.y * gridDim.x);
 }
 
 template <int EPI, bool F16 = false>
@@ -333,9 +335,8 @@ static hipError_t launch_gemm_epi(const GemmArgs& g, int fill, hipStream_t st) {
 // the unsplit sum, so the caller (clipx_encode.hip run_gemm) hands a scratch buffer only to the GEMMs of a single-sample API call: every
 // call with >= 2 samples keeps the invariant "a row does not depend on the batch (or chunk) it travels in".
 template <int EPI>
-__global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ part, int S, int M, int N,
-                                                           const float* __restrict__ bias, void* __restrict__ outp,
-                                                           const float* __restrict__ rowscale, bf16* __restrict__ out16) {
+__device__ __forceinline__ void splitk_reduce_quad(const float* __restrict__ part, int S, int M, int N, const float* __restrict__ bias,
+                                                   void* __restrict__ outp, const float* __restrict__ rowscale, bf16* __restrict__ out16) {
   const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;  // quad index
   const int nq4 = N >> 2;
   if (q >= (int64_t)M * nq4) return;
@@ -346,6 +347,14 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
     v.x += p.x; v.y += p.y; v.z += p.z; v.w += p.w;
   }
   gemm_store_quad<EPI>(v, m, n, N, bias, outp, nullptr, 1, 0, rowscale, out16);
+}
+template <int EPI>
+__global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ part, int S, int M, int N,
+                                                           const float* __restrict__ bias, void* __restrict__ outp,
+                                                           const float* __restrict__ rowscale, bf16* __restrict__ out16, StampSlot* stamp) {
+  stamp_start(stamp, blockIdx.x);
+  splitk_reduce_quad<EPI>(part, S, M, N, bias, outp, rowscale, out16);  // (threads past the last quad return from it early)
+  stamp_end(stamp, blockIdx.x);
 }
 
 // (how many splits: gemm_splitk_factor, clipx_gemm_plan.h)

@@ -73,7 +73,7 @@ __global__ __launch_bounds__(512, 2) void gemm256sp_kernel(const bf16* __restric
                                                           const float* __restrict__ bias, void* __restrict__ outp,
                                                           const float* __restrict__ table, int T, int N, int K, int ntm,
                                                           int ntn, const float* __restrict__ rowscale, bf16* __restrict__ out16,
-                                                          int raster, int tail_m0, int tail_nb) {
+                                                          int raster, int tail_m0, int tail_nb, StampSlot* stamp) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr bool DBG_TIMER = DBG == 16 || DBG == 19 || DBG == 20 || DBG == 21 || DBG == 22;
   constexpr bool DBG_L2HOT = DBG == 21;
@@ -127,7 +127,8 @@ __global__ __launch_bounds__(512, 2) void gemm256sp_kernel(const bf16* __restric
     return true;
   };
   int m0, n0, shA0, shW0;
-  if (!tile_of(0, m0, n0, shA0, shW0)) return;  // before any barrier
+  if (!tile_of(0, m0, n0, shA0, shW0)) return;  // before any barrier (and any stamp: a workgroup without a tile stores nothing)
+  stamp_start(stamp, blockIdx.x);
 
   // ---- staging: wave w fills rows [32w, 32w+32) of both operands, 8 rows (1 KiB) per instruction (piece 4w + j =
   // rows 32w + 8j .. +8).  Source chunk = LDS chunk position ^ ((row>>1)&7).  One per-lane byte offset per piece
@@ -734,6 +735,7 @@ __global__ __launch_bounds__(512, 2) void gemm256sp_kernel(const bf16* __restric
 #pragma unroll
     for (int i = 0; i < 8; ++i) g_sp_phase[blockIdx.x * 8 + i] = ph[i];
   }
+  stamp_end(stamp, blockIdx.x);
 }
 
 #ifdef CLIPX_ABLATE

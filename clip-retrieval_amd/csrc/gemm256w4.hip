@@ -59,7 +59,7 @@ template <int EPI, bool F16, int DBG, bool STATS = false>
 __global__ __launch_bounds__(256, 1) void gemm256w4_kernel(const bf16* __restrict__ A, const bf16* __restrict__ W,
                                                           const float* __restrict__ bias, void* __restrict__ outp, int N, int K,
                                                           int ntm, int ntn, const float* __restrict__ rowscale, int tail_m0, int tail_nb, int stagger,
-                                                          float stats_eps, int* __restrict__ range_flag) {
+                                                          float stats_eps, int* __restrict__ range_flag, StampSlot* stamp) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   // DBG (tools build only): 16 = phase timer, results correct.  19 .. 23 = the timer + an ABLATION of the K loop (results are garbage,
   // the timings say what each ingredient costs): 19 no operand DMAs, 20 no fragment reads, 21 neither, 22 no s_barrier, 23 no L2 prefetch
@@ -102,7 +102,8 @@ __global__ __launch_bounds__(256, 1) void gemm256w4_kernel(const bf16* __restric
     return true;
   };
   int m0, n0, shA0, shW0;
-  if (!tile_of(0, m0, n0, shA0, shW0)) return;  // before any barrier
+  if (!tile_of(0, m0, n0, shA0, shW0)) return;  // before any barrier (and any stamp: a workgroup without a tile stores nothing)
+  stamp_start(stamp, blockIdx.x);
   // ---- de-phase the XCDs.  Every workgroup runs the same tile lengths, so all 256 CUs reach their epilogues in the same few hundred
   // cycles and their output bursts meet at the fabric: 256 CUs storing at once get 14.5 B/clk each, 128 get 28.7, 64 or fewer the
   // CU's own 33 B/clk (tools/store_probe, profiles/r06e_store_probe_grid.log) -- the 128 KiB of a tile cost ~9 k cycles in step and
@@ -668,6 +669,7 @@ __global__ __launch_bounds__(256, 1) void gemm256w4_kernel(const bf16* __restric
 #pragma unroll
     for (int i = 0; i < 8; ++i) g_w4_phase[blockIdx.x * 8 + i] = ph[i];
   }
+  stamp_end(stamp, blockIdx.x);  // behind the trickled stores of the last tile and the ragged m-tile
 }
 
 #ifdef CLIPX_ABLATE
@@ -691,7 +693,7 @@ static hipError_t launch_w4_epi(const GemmArgs& g, int grid, hipStream_t st) {
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   if (e != hipSuccess) return e;
   launch_with_events(g.events, kern, dim3(grid), dim3(256), smem, st, g.A, g.W, g.bias, g.out, g.N, g.K, g.M / 256, g.N / 256, g.rowscale, g.tail_m0, g.tail_nb, w4_stagger(),
-                     g.stats_eps, g.range_flag);
+                     g.stats_eps, g.range_flag);  // (+ the stamp slot)
   return hipGetLastError();
 }
 

@@ -16,6 +16,25 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef int frag_t __attribute__((ext_vector_type(4)));  // one MFMA operand fragment: 8 x 16-bit values, type-agnostic
 
+// ---- clock stamps of a profiled launch (clipx_stamp_slots.h).  `slot` is a kernel argument, null when the launch is not
+// profiled: both functions are then one scalar compare and a branch, uniform over the workgroup.  Every kernel launch_gemm issues
+// calls stamp_start first and stamp_end last, on every path out of the kernel that has stored anything (all threads of the
+// workgroup: stamp_end holds a barrier), with its workgroup's number in the grid (blockIdx.x where the grid is one-dimensional: a
+// kernel that never reads blockIdx.y is not given it, and the persistent kernels are short of scalar registers).  One lane per
+// workgroup reads the constant-rate counter and sends a no-return 64-bit atomic to entry wg % STAMP_WAYS of the slot; the end stamp
+// is taken when every wave's global stores have been acknowledged (vmcnt(0) of each wave, then the barrier).  A workgroup of a
+// persistent kernel that owns no tile returns in front of both: it stores nothing.
+__device__ __forceinline__ void stamp_start(StampSlot* slot, unsigned wg) {
+  if (slot && threadIdx.x == 0) atomicMin(&slot->way[wg & (STAMP_WAYS - 1)].first_start, (unsigned long long)wall_clock64());
+}
+__device__ __forceinline__ void stamp_end(StampSlot* slot, unsigned wg) {
+  if (slot) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) atomicMax(&slot->way[wg & (STAMP_WAYS - 1)].last_end, (unsigned long long)wall_clock64());
+  }
+}
+
 // ---- MFMA shape (round 4).  Every GEMM kernel of this library multiplies with v_mfma_f32_16x16x32 (16 x 16 output blocks, 32-deep
 // k-slabs), not v_mfma_f32_32x32x16.  Same flops per matrix-pipe cycle, same LDS bytes per flop -- but on
 // this power-managed part the 16x16x32 form sustains ~10 % more TFLOP/s: +13 % on register-only loops, +9 % on this library's GEMM

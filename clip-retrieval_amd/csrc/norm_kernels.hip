@@ -76,8 +76,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
 // rstd of the 16-bit shadow rows (see clip_kernels.h: launch_rowstats), two passes in registers: a lane holds 4 consecutive values
 // per step of 256, the last step of an odd D128 in lanes 0 .. 31 only
 template <int D128, bool F16>  // d = D128 * 128; F16: rows are IEEE fp16, else bf16
-__global__ __launch_bounds__(256) void rowstats_kernel(const void* __restrict__ x16, float* __restrict__ rstd, int M, float eps,
-                                                       int* __restrict__ range_flag) {
+__device__ __forceinline__ void rowstats_row(const void* __restrict__ x16, float* __restrict__ rstd, int M, float eps,
+                                             int* __restrict__ range_flag) {
   constexpr int d = D128 * 128, NV2 = (D128 + 1) / 2;
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -117,6 +117,15 @@ __global__ __launch_bounds__(256) void rowstats_kernel(const void* __restrict__ 
   for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
   if (lane == 0) rstd[row] = 1.f / sqrtf(q * (1.f / d) + eps);
 }
+// (stamp: the launch belongs to a profiled GEMM that owns its statistics, gemm_common.h stamp_start; null otherwise.  The waves
+// past the last row return from rowstats_row early and still reach stamp_end's barrier)
+template <int D128, bool F16>
+__global__ __launch_bounds__(256) void rowstats_kernel(const void* __restrict__ x16, float* __restrict__ rstd, int M, float eps,
+                                                       int* __restrict__ range_flag, StampSlot* stamp) {
+  stamp_start(stamp, blockIdx.x);
+  rowstats_row<D128, F16>(x16, rstd, M, eps, range_flag);
+  stamp_end(stamp, blockIdx.x);
+}
 
 // The fp16 stream: ONE pass in the canonical order (gemm_common.h: ln_rstd_onepass) -- four lanes per row (lane = r16 + 16 q4, the
 // fragment layout of the 4-wave GEMM kernel, which computes the same sums for the rows it multiplies), lane part q4 takes the 16-B
@@ -124,8 +133,8 @@ __global__ __launch_bounds__(256) void rowstats_kernel(const void* __restrict__ 
 // per lane part) keep 4 chunks in flight instead of 8; the sums are one chain per lane part in ascending chunk order whatever the
 // number in flight, which is the order of the GEMM's K loop at any K that is a multiple of 128: the same bits at the new widths too.
 template <int D128>  // d = D128 * 128
-__global__ __launch_bounds__(256) void rowstats_f16_kernel(const void* __restrict__ x16, float* __restrict__ rstd, int M, float eps,
-                                                           int* __restrict__ range_flag) {
+__device__ __forceinline__ void rowstats_f16_rows(const void* __restrict__ x16, float* __restrict__ rstd, int M, float eps,
+                                                  int* __restrict__ range_flag) {
   constexpr int d = D128 * 128, NCH = d / 8;
   const int lane = threadIdx.x & 63, q4 = lane >> 4, r16 = lane & 15;
   const int row = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 16 + r16;
@@ -152,6 +161,13 @@ __global__ __launch_bounds__(256) void rowstats_f16_kernel(const void* __restric
   // range guard of the fp16 residual stream (see rowstats_kernel): a row holding inf / NaN has a non-finite sum
   if (range_flag && !(fabsf(s1) <= 3.0e38f)) atomicOr(range_flag, 1);
   rstd[row] = ln_rstd_onepass(s1, s2, 1.f / (float)d, eps);
+}
+template <int D128>
+__global__ __launch_bounds__(256) void rowstats_f16_kernel(const void* __restrict__ x16, float* __restrict__ rstd, int M, float eps,
+                                                           int* __restrict__ range_flag, StampSlot* stamp) {
+  stamp_start(stamp, blockIdx.x);
+  rowstats_f16_rows<D128>(x16, rstd, M, eps, range_flag);
+  stamp_end(stamp, blockIdx.x);
 }
 
 hipError_t launch_rowstats(const void* x16, float* rstd, int M, int d, float eps, hipStream_t st, int f16, int* range_flag, int canonical,
@@ -220,6 +236,15 @@ __global__ void fill_f32_kernel(float* __restrict__ p, float v, int64_t n) {
 hipError_t launch_fill_f32(float* p, float v, int64_t n, hipStream_t st) {
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(fill_f32_kernel, dim3(256), dim3(256), 0, st, p, v, n);
+  return hipGetLastError();
+}
+__global__ void fill_stamps_kernel(StampEntry* __restrict__ p, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    p[i] = StampEntry{STAMP_FILL_START, STAMP_FILL_END};
+}
+hipError_t launch_fill_stamps(StampSlot* slots, int64_t n, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(fill_stamps_kernel, dim3(256), dim3(256), 0, st, slots->way, n * STAMP_WAYS);
   return hipGetLastError();
 }
 

@@ -427,6 +427,13 @@ class ClipEncoder:
         """on: False/0 off, True/1 every kind, or a mask with bit (kind + 1): 2 gemm, 4 attention, 8 layernorm, 16 other."""
         check(self._lib, self._lib.clipx_profile_enable(self._h, int(on)), "clipx")
 
+    def profile_gemm(self, A, W, bias, out, M, N, K, epi, f16=False, rowscale=None, table=None, T=1, stream=None):
+        """Test entry (clipx_profile_gemm_device): one GEMM on device pointers through this handle's profiler, as the encoder
+        issues its own.  Pointers are integers (0 / None = null)."""
+        p = lambda v: C.c_void_p(int(v)) if v else None  # noqa: E731
+        check(self._lib, self._lib.clipx_profile_gemm_device(self._h, p(A), p(W), p(bias), p(out), p(table), int(T), int(M), int(N), int(K),
+                                                             int(epi), int(bool(f16)), p(rowscale), p(stream)), "clipx")
+
     def profile_get(self, kind):
         n, ms, fl = C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
         check(self._lib, self._lib.clipx_profile_get(self._h, int(kind), C.byref(n), C.byref(ms), C.byref(fl)), "clipx")

@@ -188,7 +188,7 @@ int clipx_range_check(clipx_handle* h, void* stream);
  *   CLIPX_OPT_RAGGED_TEXT [1]      text batches > 8 run every layer on the rows up to each caption's EOT only
  *   CLIPX_OPT_POOL_LAST_BLOCK [1]  the last block runs past its attention on the pooled rows only
  *   CLIPX_OPT_PROF_MARKERS [0]     clipx_profile_enable brackets the GEMMs with marker events around each launch, as it does the
- *                                  other kinds, instead of start / stop events on the GEMM kernels' own dispatches (A/B of the two)
+ *                                  other kinds, instead of the clock stamps the GEMM kernels write themselves (A/B of the two)
  * clipx_get_option returns the value or -1. */
 #define CLIPX_OPT_RAGGED_TEXT 1
 #define CLIPX_OPT_POOL_LAST_BLOCK 2
@@ -343,10 +343,21 @@ int clipx_bert_pool_device(int device, const void* x16, const int32_t* offs, con
  * mask with bit (kind + 1): 2 = GEMMs only, 4 | 8 | 16 = everything but the GEMMs.  get() sums and resets. */
 int clipx_profile_enable(clipx_handle* h, int on);
 int clipx_profile_get(clipx_handle* h, int kind, int64_t* launches, double* ms, double* flops);
-/* The GEMMs (kind 0) carry their events on the kernels' own dispatch packets: a GEMM launch counts once, with the summed run time
- * of the kernels it consists of (CLIPX_OPT_PROF_MARKERS = 1: events recorded around the launch, like the other kinds).  The
- * events come from a pool on the handle that clipx_profile_get refills; clipx_profile_events = events created so far. */
+/* The GEMMs (kind 0) are timed by the kernels themselves: every kernel of a GEMM launch stamps its first start and its last end
+ * (constant-rate device counter) into a slot of device memory the handle owns, and a GEMM launch counts once, with the sum over
+ * its kernels of last end - first start (CLIPX_OPT_PROF_MARKERS = 1: events recorded around the launch, like the other kinds).
+ * The slots are allocated in chunks, the first one by clipx_profile_enable; clipx_profile_get synchronises the streams the GEMMs
+ * ran on, reads the slots once and hands them back; CLIPX_E_STATE when a profiled GEMM launched no kernel or left a slot unwritten.
+ * The events of the marker form come from a pool on the handle that clipx_profile_get refills; clipx_profile_events = events
+ * created so far (the stamp form creates none). */
 int clipx_profile_events(const clipx_handle* h);
+/* Test entry: one GEMM on the caller's device buffers through the handle's profiler, the way the encoder issues its own (one scope
+ * of 2 M N K flops; epi / f16 / rowscale as in clipx_gemm_*_device, table [T, N] for epilogue 4).  CLIPX_E_ARG for a null operand,
+ * a null table or T <= 0 with epilogue 4, a null bias with any other.  What the GEMM launcher refuses returns CLIPX_E_HIP and
+ * leaves a scope without kernels behind. */
+int clipx_profile_gemm_device(clipx_handle* h, const void* A, const void* W, const float* bias_or_null, void* out,
+                              const float* table_or_null, int T, int M, int N, int K, int epi, int f16,
+                              const float* rowscale_or_null, void* stream);
 
 const char* clipx_last_error(void);
 

@@ -11,12 +11,21 @@ Only what depends on a kernel's position in its file is normalised: the function
   --rename 'OLD=NEW'   a demangled-name substring that changed on purpose (template arguments), applied to the parent's names;
                        may be given more than once
   --symbol 'KERNEL:OLD=NEW'  a device symbol that kernels whose demangled name contains KERNEL refer to under a new (mangled) name
+  --ignore-signature   match kernels by their name and template arguments only (a parameter was added to or taken from a kernel)
+  --hunks              for a kernel whose code differs, list every differing stretch (difflib opcodes: where, how many lines each
+                       side) instead of the first differing line only
+  --vector-view        compare what the vector units, the LDS and the memory pipes are given, in order: scalar ALU / scalar memory
+                       instructions, branches, lane spills of scalar registers (v_writelane / v_readlane) and labels are
+                       dropped (s_waitcnt, s_barrier, s_nop, s_setprio, s_sleep stay) and scalar register numbers are blanked.
+                       For a change that costs a kernel scalar registers on purpose (one more kernel argument): the scalar
+                       numbering moves everywhere, the question is whether anything else did
   --cache DIR          keep the .s files there and reuse one when it is newer than every source of its directory
   -j N                 compilers in parallel (default 8)
 Exit status 0: every common kernel identical.  1: some kernel differs.
 """
 import argparse
 import concurrent.futures
+import difflib
 import os
 import re
 import subprocess
@@ -82,6 +91,20 @@ def cut(path):
     return kernels, objects
 
 
+SREG = re.compile(r"\bs(\d+|\[\d+:\d+\])")
+KEPT_SCALAR = ("s_waitcnt", "s_barrier", "s_nop", "s_setprio", "s_sleep")
+
+
+def vector_view(code):
+    out = []
+    for ln in code:
+        m = ln.split()[0]
+        if ln.strip().endswith(":") or m in ("v_writelane_b32", "v_readlane_b32") or (m.startswith("s_") and m not in KEPT_SCALAR):
+            continue
+        out.append(SREG.sub("s#", ln.strip()))
+    return out
+
+
 def collect(asm):
     kernels, objects, where = {}, [], {}
     for f, s in asm.items():
@@ -100,6 +123,9 @@ def main():
     ap.add_argument("-D", dest="defines", action="append", default=[])
     ap.add_argument("--rename", action="append", default=[])
     ap.add_argument("--symbol", action="append", default=[])
+    ap.add_argument("--ignore-signature", action="store_true")
+    ap.add_argument("--hunks", action="store_true")
+    ap.add_argument("--vector-view", action="store_true")
     ap.add_argument("--cache")
     ap.add_argument("-j", type=int, default=8)
     a = ap.parse_args()
@@ -111,6 +137,8 @@ def main():
         asm = compile_dir(src, os.path.join(tmp, side + "_" + tag), defines, a.j)
         k, o, w = collect(asm)
         d = demangle(list(k))
+        if a.ignore_signature:
+            d = {s: (n[:n.index("(")] if "(" in n else n) for s, n in d.items()}
         sides.append(({d[s]: (v, w[s]) for s, v in k.items()}, sorted(demangle(o).values())))
     (pk, po), (nk, no) = sides
     renamed = []
@@ -134,12 +162,19 @@ def main():
     for name in sorted(pk.keys() & nk.keys()):
         (pc, pd), pf = pk[name]
         (nc, nd), nf = nk[name]
+        if a.vector_view:
+            pc, nc = vector_view(pc), vector_view(nc)
         if pc == nc and pd == nd:
             continue
         differ += 1
         what = " and ".join(w for w, bad in (("code", pc != nc), ("descriptor", pd != nd)) if bad)
         print(f"DIFFERS ({what}): {name}   [{pf} -> {nf}]")
-        if pc != nc:
+        if pc != nc and a.hunks:
+            print(f"    {len(pc)} -> {len(nc)} lines")
+            for tag, i1, i2, j1, j2 in difflib.SequenceMatcher(None, pc, nc, autojunk=False).get_opcodes():
+                if tag != "equal":
+                    print(f"    {tag}: parent lines {i1}..{i2} ({i2 - i1}) -> new lines {j1}..{j2} ({j2 - j1})")
+        elif pc != nc:
             at = next((i for i, (x, y) in enumerate(zip(pc, nc)) if x != y), min(len(pc), len(nc)))
             print(f"    {len(pc)} -> {len(nc)} lines, first difference at line {at}:")
             print(f"    - {pc[at] if at < len(pc) else '<end>'}\n    + {nc[at] if at < len(nc) else '<end>'}")

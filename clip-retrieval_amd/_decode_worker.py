@@ -60,7 +60,7 @@ def main():
                 for o in outs:
                     if o is None:
                         continue
-                    for k in ("image_tensor", "image_raw", "image_jpeg"):
+                    for k in ("image_tensor", "image_raw", "image_jpeg", "image_jpeg_scan"):
                         a = o.get(k)
                         if a is None or not hasattr(a, "nbytes") or off + a.nbytes > arena_np.size:
                             continue

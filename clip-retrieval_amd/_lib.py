@@ -188,6 +188,9 @@ SIGNATURES = {
     "clipx_jpeg_probe_host": (C.c_int, [_P, C.c_size_t, C.c_int, _P, C.POINTER(C.c_size_t)]),
     "clipx_jpeg_entropy_host": (C.c_int, [_P, C.c_size_t, C.c_int, _P, _P, C.c_size_t]),
     "clipx_jpeg_pixels_device": (C.c_int, [C.c_int, _P, _P, C.c_int, _P, _P, _P]),
+    "clipx_jpeg_scan_probe_host": (C.c_int, [_P, C.c_size_t, C.c_int, _P, C.POINTER(C.c_size_t)]),
+    "clipx_jpeg_scan_host": (C.c_int, [_P, C.c_size_t, C.c_int, _P, _P, C.c_size_t]),
+    "clipx_jpeg_entropy_device": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, _P, _P, _P]),
     "clipx_range_check": (C.c_int, [_P, _P]),
     "clipx_set_option": (C.c_int, [_P, C.c_int, C.c_int]),
     "clipx_get_option": (C.c_int, [_P, C.c_int]),

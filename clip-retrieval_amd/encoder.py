@@ -223,12 +223,20 @@ def blob_from_checkpoint(path: str, arch: ClipArch) -> np.ndarray:
 # ----------------------------------------------------------------------------------------------
 # the encoder object
 # ----------------------------------------------------------------------------------------------
-def resize_crop_device(lib, device, S, raw, stream=None, jpeg=None):
+def resize_crop_device(lib, device, S, raw, stream=None, jpeg=None, preprocess=None):
     """The device half of a reader built on DecodeRgbU8, without a model: `raw` ({"pixels", "offsets", "hw"}: reader._collate) ->
     uint8 [B, S, S, 3] torch tensor on GPU `device`, bit-identical to Pillow's bicubic resize + centre crop.  With `jpeg` (the batch's
     `image_jpeg`: {"coefs", "descs", "slots"}) the images of `slots` are first decoded from their DCT coefficients into the bytes
     `raw` reserves for them (clipx_jpeg_pixels_device, bit-identical to Pillow's decode), on the same stream.  A batch that holds
-    coefficients only uploads no pixel at all."""
+    coefficients only uploads no pixel at all.
+
+    The scan form: `jpeg` is the batch's `image_jpeg_scan` ({"scans", "descs", "offs", "coef_bytes", "slots", "names"}).  The scan
+    records are uploaded and Huffman-decoded on the device (clipx_jpeg_entropy_device); the statuses come back and are WAITED for; an
+    image with a non-zero status -- one the host entropy stage would have deferred -- is decoded late, here, by Pillow, through
+    `preprocess` (default: reader.DecodeRgbU8(S)) exactly as the deferred branch of reader._decode_sample decodes, and its pixels are
+    uploaded into its slot; where that fails too, the ROW IS DROPPED with that branch's skip line.  The result then has fewer rows
+    than the batch and its `_clipx_kept` holds the indices of the rows it does have (None: all of them).  `stream`, when given, must
+    be torch's current stream: the copies here are torch's."""
     import torch  # pylint: disable=import-outside-toplevel
 
     dev = torch.device("cuda", device)
@@ -236,25 +244,54 @@ def resize_crop_device(lib, device, S, raw, stream=None, jpeg=None):
     offsets = np.ascontiguousarray(raw["offsets"], dtype=np.int64)
     hw = np.ascontiguousarray(raw["hw"], dtype=np.int32)
     st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-    coefs = None
+    coefs = scans = kept = None
     if jpeg is not None and len(jpeg["slots"]):
-        from .jpeg import pixels_device  # pylint: disable=import-outside-toplevel
+        from .jpeg import entropy_device, pixels_device, scan_file  # pylint: disable=import-outside-toplevel
 
         slots = np.asarray(jpeg["slots"], dtype=np.int64)
-        if not np.array_equal(hw[slots], np.stack([jpeg["descs"]["height"], jpeg["descs"]["width"]], 1)):
+        descs = jpeg["descs"]
+        if not np.array_equal(hw[slots], np.stack([descs["height"], descs["width"]], 1)):
             raise ValueError("image_jpeg descriptors do not match the sizes image_raw reserves for their slots")
         if len(slots) == B:
             src = torch.empty(raw["pixels"].numel(), dtype=torch.uint8, device=dev)
         else:
             src = raw["pixels"].to(dev, non_blocking=True)
-        coefs = jpeg["coefs"].to(dev, non_blocking=True)
-        pixels_device(device, coefs, jpeg["descs"], src, offsets[slots], st, lib)
+        if "scans" in jpeg:
+            from .reader import DecodeRgbU8, late_decode  # pylint: disable=import-outside-toplevel
+
+            scans = jpeg["scans"].to(dev, non_blocking=True)
+            coefs = torch.empty(int(jpeg["coef_bytes"]), dtype=torch.uint8, device=dev)
+            status = torch.empty(len(slots), dtype=torch.int32, device=dev)
+            entropy_device(device, scans, descs, jpeg["offs"], coefs, status, st, lib)
+            unclean = np.flatnonzero(status.cpu().numpy())  # (waits for the Huffman kernel)
+            dropped = []
+            for j in unclean:
+                o, (h, w) = int(jpeg["offs"][j]), (int(x) for x in hw[slots[j]])
+                px = late_decode(jpeg["names"][j], scan_file(jpeg["scans"].numpy()[o:int(jpeg["offs"][j + 1])]),
+                                 preprocess or DecodeRgbU8(S), h, w)
+                if px is None:
+                    dropped.append(int(slots[j]))
+                else:
+                    at = int(offsets[slots[j]])
+                    src[at:at + px.size].copy_(torch.from_numpy(px.reshape(-1)))
+            clean = np.ones(len(slots), dtype=bool)
+            clean[unclean] = False
+            if clean.any():
+                pixels_device(device, coefs, descs[clean], src, offsets[slots[clean]], st, lib)
+            if dropped:
+                kept = np.setdiff1d(np.arange(B), np.asarray(dropped))
+                offsets, hw, B = np.ascontiguousarray(offsets[kept]), np.ascontiguousarray(hw[kept]), int(kept.size)
+        else:
+            coefs = jpeg["coefs"].to(dev, non_blocking=True)
+            pixels_device(device, coefs, descs, src, offsets[slots], st, lib)
     else:
         src = raw["pixels"].to(dev, non_blocking=True)
     out = torch.empty((B, S, S, 3), dtype=torch.uint8, device=dev)
-    check(lib, lib.clipx_resize_crop_u8_device(device, C.c_void_p(src.data_ptr()), offsets.ctypes.data, hw.ctypes.data,
-                                               B, S, C.c_void_p(out.data_ptr()), C.c_void_p(st) if st else None), "clipx")
-    out._clipx_src = (src, coefs)  # the kernels read these asynchronously: keep them alive as long as the result
+    if B:
+        check(lib, lib.clipx_resize_crop_u8_device(device, C.c_void_p(src.data_ptr()), offsets.ctypes.data, hw.ctypes.data,
+                                                   B, S, C.c_void_p(out.data_ptr()), C.c_void_p(st) if st else None), "clipx")
+    out._clipx_src = (src, coefs, scans)  # the kernels read these asynchronously: keep them alive as long as the result
+    out._clipx_kept = kept
     return out
 
 
@@ -327,17 +364,20 @@ class ClipEncoder:
         return out
 
     # ---- decoded sources of any size: resize + centre crop on the GPU (csrc/preprocess.hip), then the image tower
-    def resize_crop_device(self, raw, stream=None, jpeg=None):
+    def resize_crop_device(self, raw, stream=None, jpeg=None, preprocess=None):
         """`raw` = {"pixels": uint8 1-D torch tensor (page-locked or not) with the packed RGB sources, "offsets": int64 [B],
         "hw": int32 [B, 2]} (reader._collate) -> uint8 [B, S, S, 3] torch tensor on this encoder's GPU, bit-identical to
         Pillow's bicubic resize + centre crop (the reference's image_transform, reader.py:83,87).  `jpeg` (the batch's
-        `image_jpeg`, or None): images that travel as DCT coefficients are decoded into their slots of `raw` on the GPU first."""
-        return resize_crop_device(self._lib, self.device, self.arch.image_size, raw, stream, jpeg)
+        `image_jpeg` or `image_jpeg_scan`, or None): images that travel as DCT coefficients or as scans are decoded into their slots
+        of `raw` on the GPU first; the scan form may drop rows (see the module-level function)."""
+        return resize_crop_device(self._lib, self.device, self.arch.image_size, raw, stream, jpeg, preprocess)
 
-    def encode_image_raw(self, raw, jpeg=None) -> np.ndarray:
+    def encode_image_raw(self, raw, jpeg=None, return_kept=False):
         """fp16 [B, E] unit-norm rows from decoded sources (see resize_crop_device): upload once, resize / crop / normalise and
         encode on the GPU.  Everything is ordered on one side stream of this encoder (a NULL stream handle would make the
-        library fall back to its own stream and lose the ordering against the resize kernel)."""
+        library fall back to its own stream and lose the ordering against the resize kernel).  return_kept: (rows, kept) where `kept`
+        is None or the indices of the batch's rows that have an embedding -- the scan form drops the rows of files that neither the
+        device nor Pillow decode."""
         import torch  # pylint: disable=import-outside-toplevel
 
         dev = torch.device("cuda", self.device)
@@ -346,6 +386,11 @@ class ClipEncoder:
         s = self._raw_stream
         with torch.cuda.stream(s):
             u8 = self.resize_crop_device(raw, s.cuda_stream, jpeg)
+            kept = u8._clipx_kept  # pylint: disable=protected-access
+            if u8.shape[0] == 0:
+                s.synchronize()
+                rows = np.empty((0, self.embed_dim), dtype=np.float16)
+                return (rows, kept) if return_kept else rows
             out = torch.empty((u8.shape[0], self.embed_dim), dtype=torch.float16, device=dev)
             self.encode_image_device(u8.data_ptr(), u8.shape[0], PIX_U8_NHWC, out.data_ptr(), None, s.cuda_stream)
             host = torch.empty(out.shape, dtype=torch.float16, pin_memory=True)
@@ -353,7 +398,7 @@ class ClipEncoder:
         # synchronises the stream AND raises ResidualStreamOverflow if a row of this call left the fp16 range (include/clipx.h: "reported,
         # never hidden" -- the *_device entry points only set the flag; ADVICE r4: a plain synchronize here wrote finite-looking wrong rows)
         self.check_range(s.cuda_stream)
-        return host.numpy()
+        return (host.numpy(), kept) if return_kept else host.numpy()
 
     # ---- asynchronous tickets (clipx_encode_*_async / clipx_wait): submit now, collect later
     def submit_image(self, pixels):

@@ -4,6 +4,10 @@
 file's bytes.  It makes no HIP call, so the readers' decode processes use it without a GPU.  A file outside the accepted class --
 or one that does not parse cleanly -- is DEFERRED (`None`): the caller decodes it with Pillow as before.  `pixels_device()` is the
 device half: records -> packed RGB, bit-identical to Pillow (csrc/jpeg_kernels.hip).
+
+With the Huffman stage on the device (`gpu_huffman`): `scan_packed()` only parses markers (csrc/jpegx_scan.h, no HIP call either) and
+`entropy_device()` turns the scan records of a batch into the same records on the GPU (csrc/jpeg_huff_kernels.hip), with a status
+per image that is non-zero exactly where `entropy()` would have deferred the file.
 """
 
 import ctypes as C
@@ -78,6 +82,90 @@ def pack_records(packed, pin=False):
     descs = np.stack([r[:JPEG_DESC.itemsize] for r in packed]).view(JPEG_DESC).reshape(-1)
     descs["coef_off"] = starts + JPEG_DESC.itemsize
     return buf, descs
+
+
+def scan_packed(data, max_side=8192, lib=None):
+    """One uint8 array [64 bytes of descriptor | scan record] of a file of the accepted class whose entropy-coded bytes end in the
+    markers they should -- the form in which a sample travels when the Huffman stage runs on the device (`image_jpeg_scan` of
+    reader._decode_sample; csrc/jpegx_scan.h) -- or None = deferred.  No Huffman decoding happens here."""
+    lib = lib or load_library()
+    buf = bytes(data)
+    desc = np.zeros(1, dtype=JPEG_DESC)
+    need = C.c_size_t(0)
+    rc = lib.clipx_jpeg_scan_probe_host(buf, len(buf), int(max_side), desc.ctypes.data, C.byref(need))
+    if rc < 0:
+        check(lib, rc, "clipx")
+    if rc != TAKEN:
+        return None
+    packed = np.empty(JPEG_DESC.itemsize + need.value, dtype=np.uint8)
+    rc = lib.clipx_jpeg_scan_host(buf, len(buf), int(max_side), packed.ctypes.data, packed.ctypes.data + JPEG_DESC.itemsize, need.value)
+    if rc < 0:
+        check(lib, rc, "clipx")
+    return packed if rc == TAKEN else None
+
+
+SCAN_HEADER = np.dtype([("magic", "<u4"), ("total_bytes", "<u4"), ("file_bytes", "<u4"), ("nintervals", "<i4"), ("ntables", "<i4"),
+                        ("dc_tab", "<i4", (3,)), ("ac_tab", "<i4", (3,)), ("pad", "<i4", (5,))])  # ScanHeader of csrc/jpegx_scan.h
+assert SCAN_HEADER.itemsize == 64
+HUFF_BYTES, INTERVAL_BYTES = 2448, 16
+
+
+def scan_file(record):
+    """The file's own bytes out of a scan record (a scan_packed() array behind its descriptor, or a record of pack_scans()'s
+    buffer): what a late Pillow decode reads."""
+    record = np.asarray(record, dtype=np.uint8)
+    h = record[:SCAN_HEADER.itemsize].view(SCAN_HEADER)[0]
+    at = SCAN_HEADER.itemsize + TABLE_BYTES + int(h["ntables"]) * HUFF_BYTES + int(h["nintervals"]) * INTERVAL_BYTES
+    return record[at:at + int(h["file_bytes"])].tobytes()
+
+
+def pack_scans(packed, pin=False):
+    """The scan_packed() arrays of a batch in ONE (page-locked) byte buffer -> (torch uint8 buffer of the scan records, descriptors
+    [n] with coef_off laid out for the records the device stage will WRITE, scan offsets int64 [n + 1], bytes of that coefficient
+    buffer).  Record i of the scans lies in [offs[i], offs[i + 1]), each on a 16-byte boundary."""
+    import torch  # pylint: disable=import-outside-toplevel
+
+    sizes = np.asarray([(r.size - JPEG_DESC.itemsize + 15) & ~15 for r in packed], dtype=np.int64)
+    offs = np.zeros(len(packed) + 1, dtype=np.int64)
+    np.cumsum(sizes, out=offs[1:])
+    buf = torch.empty(int(offs[-1]), dtype=torch.uint8, pin_memory=bool(pin))
+    flat = buf.numpy()
+    for r, o in zip(packed, offs):
+        flat[o:o + r.size - JPEG_DESC.itemsize] = r[JPEG_DESC.itemsize:]
+    descs = np.stack([r[:JPEG_DESC.itemsize] for r in packed]).view(JPEG_DESC).reshape(-1) if len(packed) else np.zeros(0, JPEG_DESC)
+    rec = (TABLE_BYTES + descs["blocks"].astype(np.int64) * 128 + 15) & ~15
+    descs["coef_off"] = np.cumsum(rec) - rec
+    return buf, descs, offs, int(rec.sum())
+
+
+def entropy_device(device, scans_dev, descs, scan_offs, coefs_dev, status_dev, stream=None, lib=None):
+    """Run the Huffman stage on the device: scan record i (bytes [scan_offs[i], scan_offs[i + 1]) of the device tensor `scans_dev`)
+    becomes the record pixels_device reads at descs[i].coef_off of `coefs_dev`; status_dev (device int32 [>= n]) gets 0 per clean
+    image and a reason code per image the host stage would have deferred.  Asynchronous on `stream` (a hipStream_t value; None:
+    torch's current).  The tensors' extents are checked here: the C entry point takes bare pointers."""
+    import torch  # pylint: disable=import-outside-toplevel
+
+    lib = lib or load_library()
+    descs = np.ascontiguousarray(descs, dtype=JPEG_DESC)
+    scan_offs = np.ascontiguousarray(scan_offs, dtype=np.int64)
+    n = descs.shape[0]
+    if scan_offs.shape != (n + 1,):
+        raise ValueError("n + 1 scan offsets for n descriptors")
+    if scans_dev.dtype != torch.uint8 or coefs_dev.dtype != torch.uint8 or status_dev.dtype != torch.int32:
+        raise ValueError("scan and coefficient buffers are uint8 tensors, the status array is int32")
+    if not (scans_dev.is_contiguous() and coefs_dev.is_contiguous() and status_dev.is_contiguous()):
+        raise ValueError("contiguous tensors only")
+    if n and (scan_offs[0] < 0 or (np.diff(scan_offs) < 0).any() or scan_offs[-1] > scans_dev.numel()):
+        raise ValueError("a scan record lies outside the scan buffer")
+    rec_end = descs["coef_off"] + TABLE_BYTES + descs["blocks"].astype(np.int64) * 128
+    if n and (descs["coef_off"].min() < 0 or descs["blocks"].min() < 0 or rec_end.max() > coefs_dev.numel()):
+        raise ValueError("a JPEG record lies outside the coefficient buffer")
+    if status_dev.numel() < n:
+        raise ValueError("one status word per image")
+    st = stream if stream is not None else torch.cuda.current_stream(torch.device("cuda", device)).cuda_stream
+    check(lib, lib.clipx_jpeg_entropy_device(device, C.c_void_p(scans_dev.data_ptr()), descs.ctypes.data, scan_offs.ctypes.data, n,
+                                             C.c_void_p(coefs_dev.data_ptr()), C.c_void_p(status_dev.data_ptr()),
+                                             C.c_void_p(st) if st else None), "clipx")
 
 
 def pixels_device(device, coefs_dev, descs, pixels_dev, offsets, stream=None, lib=None):

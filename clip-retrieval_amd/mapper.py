@@ -68,10 +68,21 @@ class ClipMapper:
     def _encode_images(self, item):
         """`image_tensor` (the reference's batch: f32 NCHW, or uint8 NHWC crops) or `image_raw` (decoded sources of any size:
         resize + centre crop on the GPU too, reader.decode_rgb_u8; with `image_jpeg` beside it, some of them still as DCT
-        coefficients: reader.DecodeRgbU8(gpu_jpeg=True))."""
+        coefficients: reader.DecodeRgbU8(gpu_jpeg=True); with `image_jpeg_scan`, as undecoded scans: gpu_huffman=True).
+        -> (rows, kept): `kept` is None, or the indices of the batch's rows that have an embedding where the scan form dropped a
+        file that neither the device nor Pillow decode."""
         if "image_raw" in item:
-            return self._enc.encode_image_raw(item["image_raw"], item.get("image_jpeg"))
-        return self._enc.encode_image(item["image_tensor"])
+            if "image_jpeg_scan" in item:
+                return self._enc.encode_image_raw(item["image_raw"], item["image_jpeg_scan"], return_kept=True)
+            return self._enc.encode_image_raw(item["image_raw"], item.get("image_jpeg")), None
+        return self._enc.encode_image(item["image_tensor"]), None
+
+    @staticmethod
+    def _keep(kept, values):
+        """The per-sample entry `values` without the rows the image side dropped."""
+        if kept is None or values is None:
+            return values
+        return values[kept] if isinstance(values, np.ndarray) else [values[i] for i in kept]
 
     def _encode_texts(self, item):
         if self.use_mclip:
@@ -106,15 +117,15 @@ class ClipMapper:
 
     def collect(self, h):
         item = h["item"]
-        image_embs = text_embs = image_filename = text = metadata = None
+        image_embs = text_embs = image_filename = text = metadata = kept = None
         if self.enable_image:
-            image_embs = self._enc.collect(h["img"]) if h["img"] is not None else self._encode_images(item)
-            image_filename = item["image_filename"]
+            image_embs, kept = (self._enc.collect(h["img"]), None) if h["img"] is not None else self._encode_images(item)
+            image_filename = self._keep(kept, item["image_filename"])
         if self.enable_text:
-            text_embs = self._enc.collect(h["txt"]) if h["txt"] is not None else self._encode_texts(item)
-            text = item["text"]
+            text_embs = self._keep(kept, self._enc.collect(h["txt"]) if h["txt"] is not None else self._encode_texts(item))
+            text = self._keep(kept, item["text"])
         if self.enable_metadata:
-            metadata = item["metadata"]
+            metadata = self._keep(kept, item["metadata"])
         return {
             "image_embs": image_embs,
             "text_embs": text_embs,
@@ -124,15 +135,15 @@ class ClipMapper:
         }
 
     def __call__(self, item):
-        image_embs = text_embs = image_filename = text = metadata = None
+        image_embs = text_embs = image_filename = text = metadata = kept = None
         if self.enable_image:
-            image_embs = self._encode_images(item)
-            image_filename = item["image_filename"]
+            image_embs, kept = self._encode_images(item)
+            image_filename = self._keep(kept, item["image_filename"])
         if self.enable_text:
-            text_embs = self._encode_texts(item)
-            text = item["text"]
+            text_embs = self._keep(kept, self._encode_texts(item))
+            text = self._keep(kept, item["text"])
         if self.enable_metadata:
-            metadata = item["metadata"]
+            metadata = self._keep(kept, item["metadata"])
         return {
             "image_embs": image_embs,
             "text_embs": text_embs,

@@ -81,15 +81,23 @@ class DecodeRgbU8:
     (markers + Huffman, csrc/jpegx_entropy.h) and the sample travels as `image_jpeg`, its DCT coefficients; inverse DCT, chroma
     upsampling and colour conversion run on the GPU (csrc/jpeg_kernels.hip), bit-identical to Pillow, into the image's slot of the
     `image_raw` buffer.  Every file outside that class (progressive, CMYK, other formats, anything that does not parse cleanly) is
-    deferred to the Pillow branch above, error handling included."""
+    deferred to the Pillow branch above, error handling included.
+
+    gpu_huffman (off by default; implies gpu_jpeg): the Huffman stage runs on the GPU as well (csrc/jpeg_huff_kernels.hip).  The decode
+    process only parses the markers of a baseline JPEG (`scan`, csrc/jpegx_scan.h) and the sample travels as `image_jpeg_scan`: the
+    file's own bytes with its tables and restart intervals laid out for the device.  A file the device stage then finds malformed is
+    decoded late, by Pillow, in the process that runs the GPU (encoder.resize_crop_device), and dropped there if Pillow fails too.  An
+    instance emits coefficients or scans, never both."""
 
     raw_images = True  # readers: collate as `image_raw`, not as a stacked `image_tensor`
     GPU_MODES = ("RGB", "L")
     gpu_jpeg = False  # (class default: instances pickled before the switch existed stay off)
+    gpu_huffman = False
 
-    def __init__(self, size=224, max_side=8192, max_downscale=16, gpu_jpeg=False):
+    def __init__(self, size=224, max_side=8192, max_downscale=16, gpu_jpeg=False, gpu_huffman=False):
         self.size, self.max_side, self.max_downscale = size, max_side, max_downscale
-        self.gpu_jpeg = bool(gpu_jpeg)
+        self.gpu_huffman = bool(gpu_huffman)
+        self.gpu_jpeg = bool(gpu_jpeg) or self.gpu_huffman
 
     def entropy(self, data):
         """[descriptor | record] (jpeg.entropy_packed) of a file the GPU decodes, None for one that stays with Pillow -- deferred by
@@ -102,6 +110,18 @@ class DecodeRgbU8:
         if got is None or min(int(got[0][0]["width"]), int(got[0][0]["height"])) > self.max_downscale * self.size:
             return None
         return jpeg.entropy_packed(data, self.max_side)
+
+    def scan(self, data):
+        """[descriptor | scan record] (jpeg.scan_packed) of a file whose Huffman stage the GPU runs, None for one that stays with
+        Pillow -- deferred by the marker walk, or a source `__call__` would hand to the host transform."""
+        from . import jpeg  # pylint: disable=import-outside-toplevel
+
+        if not isinstance(data, (bytes, bytearray, memoryview)):
+            return None
+        got = jpeg.probe(data, self.max_side)
+        if got is None or min(int(got[0][0]["width"]), int(got[0][0]["height"])) > self.max_downscale * self.size:
+            return None
+        return jpeg.scan_packed(data, self.max_side)
 
     def __call__(self, image):
         w, h = image.size
@@ -204,13 +224,20 @@ def _collate(samples, enable_image, enable_text, enable_metadata, pin):
 
     batch = {}
     slots = [i for i, s in enumerate(samples) if "image_jpeg" in s] if enable_image else []  # (DecodeRgbU8(gpu_jpeg=True) only)
+    scans = [i for i, s in enumerate(samples) if "image_jpeg_scan" in s] if enable_image else []  # (gpu_huffman=True only)
+    if scans and slots:
+        raise ValueError("a batch holds JPEG coefficients or JPEG scans, never both")
+    slots = slots or scans
     if enable_image and ("image_raw" in samples[0] or slots):
         # decoded sources of different sizes: ONE packed (page-locked) byte buffer + host-side offsets and (h, w) per image --
         # the layout clipx_resize_crop_u8_device takes
         if slots:
             from . import jpeg  # pylint: disable=import-outside-toplevel
 
-            coefs, descs = jpeg.pack_records([samples[i]["image_jpeg"] for i in slots], pin)
+            if scans:
+                scan_buf, descs, scan_offs, coef_bytes = jpeg.pack_scans([samples[i]["image_jpeg_scan"] for i in scans], pin)
+            else:
+                coefs, descs = jpeg.pack_records([samples[i]["image_jpeg"] for i in slots], pin)
             sizes = np.zeros((len(samples), 2), dtype=np.int32)
             for i, s in enumerate(samples):
                 if "image_raw" in s:
@@ -228,7 +255,13 @@ def _collate(samples, enable_image, enable_text, enable_metadata, pin):
             if "image_raw" in s:
                 flat[o:o + n] = s["image_raw"].reshape(-1)
         batch["image_raw"] = {"pixels": packed, "offsets": offsets, "hw": sizes}
-        if slots:
+        if scans:
+            # the files whose whole decode runs on the GPU: one page-locked buffer of scan records, their extents, descriptors laid
+            # out for the coefficient buffer the device stage fills (`coef_bytes` long), each image's slot -- reserved as below --
+            # and its name, for the skip line of a file that the device and then Pillow refuse (encoder.resize_crop_device)
+            batch["image_jpeg_scan"] = {"scans": scan_buf, "descs": descs, "offs": scan_offs, "coef_bytes": coef_bytes,
+                                        "slots": np.asarray(slots, dtype=np.int64), "names": [samples[i]["image_filename"] for i in scans]}
+        elif slots:
             # coefficients of the images the GPU decodes: one page-locked buffer of records + descriptors + each image's slot of the
             # batch, whose h * w * 3 bytes above are reserved and left unwritten (clipx_jpeg_pixels_device fills them on the device)
             batch["image_jpeg"] = {"coefs": coefs, "descs": descs, "slots": np.asarray(slots, dtype=np.int64)}
@@ -344,8 +377,13 @@ def _decode_sample(raw, preprocess, tokenizer, enable_image, enable_text, enable
     except (OSError, UnicodeDecodeError) as e:
         print(f"Failed to read sample {raw['key']}. Error: {e}. Skipping.")
         return None
-    taken = preprocess.entropy(raw["image"]) if enable_image and getattr(preprocess, "gpu_jpeg", False) else None
-    if taken is not None:  # a baseline JPEG: its coefficients travel, the pixel stage runs on the GPU
+    huffman = enable_image and getattr(preprocess, "gpu_huffman", False)  # (an instance emits scans or coefficients, never both)
+    scan = preprocess.scan(raw["image"]) if huffman else None
+    taken = preprocess.entropy(raw["image"]) if enable_image and not huffman and getattr(preprocess, "gpu_jpeg", False) else None
+    if scan is not None:  # a baseline JPEG: the file travels with its tables and intervals, the whole decode runs on the GPU
+        out["image_jpeg_scan"] = scan  # uint8 [64-byte descriptor | scan record]
+        out["image_filename"] = raw["key"]
+    elif taken is not None:  # a baseline JPEG: its coefficients travel, the pixel stage runs on the GPU
         out["image_jpeg"] = taken  # uint8 [64-byte descriptor | quantisation tables | int16 coefficients]
         out["image_filename"] = raw["key"]
     elif enable_image:
@@ -367,6 +405,22 @@ def _decode_sample(raw, preprocess, tokenizer, enable_image, enable_text, enable
     if enable_metadata:
         out["metadata"] = raw["metadata"]
     return out
+
+
+def late_decode(key, data, preprocess, h, w):
+    """A file the device's Huffman stage refused (encoder.resize_crop_device), decoded as the deferred branch of `_decode_sample`
+    decodes: uint8 [h, w, 3], or None -- with that branch's skip line -- when Pillow fails or gives anything but the reserved size."""
+    from PIL import Image, UnidentifiedImageError  # pylint: disable=import-outside-toplevel
+
+    try:
+        img = preprocess(Image.open(io.BytesIO(data)))
+        img = img.numpy() if hasattr(img, "numpy") else np.asarray(img)
+        if img.dtype != np.uint8 or img.shape != (h, w, 3):
+            raise ValueError(f"decoded to {img.dtype} {img.shape}, not to the {h} x {w} x 3 bytes its batch reserves")
+    except (UnidentifiedImageError, OSError, ValueError) as e:
+        print(f"Failed to load image {key}. Error: {e}. Skipping.")
+        return None
+    return np.array(img)  # (a copy: Pillow's array is read-only, and the caller hands it to torch)
 
 
 class _DecodeWorker:
@@ -427,7 +481,7 @@ class _DecodeWorker:
             for sample in out:  # copy the pixels out before this worker's next chunk overwrites the arena
                 if sample is None:
                     continue
-                for k in ("image_tensor", "image_raw", "image_jpeg"):
+                for k in ("image_tensor", "image_raw", "image_jpeg", "image_jpeg_scan"):
                     v = sample.get(k)
                     if isinstance(v, tuple) and v and v[0] == "@arena":
                         _, off, shape, dtype = v

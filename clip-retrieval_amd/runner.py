@@ -104,6 +104,17 @@ def _batch_rows(batch):
     return batch["text_tokens"].shape[0]
 
 
+def _rows_written(embeddings, batch_rows):
+    """Rows the mapper handed on for the writer: the batch's, unless the mapper dropped some (ClipMapper does where a reader with
+    gpu_huffman let a file through that neither the device nor Pillow decode)."""
+    if isinstance(embeddings, dict):
+        for k in ("image_embs", "text_embs"):
+            v = embeddings.get(k)
+            if v is not None and hasattr(v, "shape"):
+                return int(v.shape[0])
+    return batch_rows
+
+
 class Runner:
     """Runs one output partition end to end.
 
@@ -171,7 +182,7 @@ class Runner:
                     last_end = wall1
                     logger({"start_time": start, "end_time": wall1, "read_duration": read_d,
                             "inference_duration": sub_d + (t4 - t3), "write_duration": t5 - t4,
-                            "total_duration": wall1 - start, "sample_count": count})
+                            "total_duration": wall1 - start, "sample_count": _rows_written(embeddings, count)})
                 else:
                     if batch is None:
                         break
@@ -182,7 +193,7 @@ class Runner:
                     wall1 = time.time()
                     logger({"start_time": wall0, "end_time": wall1, "read_duration": t1 - t0,
                             "inference_duration": t3 - t1, "write_duration": t4 - t3,
-                            "total_duration": wall1 - wall0, "sample_count": _batch_rows(batch)})
+                            "total_duration": wall1 - wall0, "sample_count": _rows_written(embeddings, _batch_rows(batch))})
         except BaseException:
             # A submitted ticket owns one of the encoder's staging slots (and keeps its pinned input referenced) until it is
             # collected; the encoder outlives this partition (cached per model and device), so a ticket leaked here would

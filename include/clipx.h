@@ -173,6 +173,26 @@ int clipx_jpeg_entropy_host(const void* data, size_t n, int max_side, clipx_jpeg
 int clipx_jpeg_pixels_device(int device, const void* coefs_dev, const clipx_jpeg_desc* descs, int B, void* pixels_dev,
                              const int64_t* offsets, void* stream);
 
+/* Huffman stage on the device (`gpu_huffman`; csrc/jpegx_scan.h, csrc/jpeg_huff_kernels.hip), same class of files, same verdicts.
+ *
+ * Host preparation (no HIP call).  clipx_jpeg_scan_probe_host parses up to the SOS and returns the descriptor and the size of the
+ * file's SCAN RECORD; clipx_jpeg_scan_host walks the entropy-coded bytes for markers only (no Huffman decoding) and writes the
+ * record into `scan` (scan_bytes >= the probed size; never written past it): a header, the quantisation tables, the Huffman tables
+ * the scan selects, the table of restart intervals and the file's bytes.  Return as above: TAKEN, DEFERRED (nothing was written --
+ * also where the probe took the file and the marker walk does not), or CLIPX_E_ARG.
+ *
+ * clipx_jpeg_entropy_device decodes B scan records, one wave per restart interval.  scans_dev holds record i in
+ * [scan_offs[i], scan_offs[i + 1]) -- scan_offs is a HOST array of B + 1 multiples of 16 -- and image i's output, exactly the record
+ * clipx_jpeg_pixels_device reads (uint16 qt[3][64] | int16 coef[blocks][64]), is written at descs[i].coef_off of coefs_dev (HOST
+ * descriptors, as the preparation wrote them, coef_off set by the caller).  status_dev[i] (device int32 [B]) becomes 0 when every
+ * interval of image i decoded cleanly -- its record then equals clipx_jpeg_entropy_host's byte for byte -- and a reason code > 0
+ * otherwise: clipx_jpeg_entropy_host defers exactly those files, their records hold no meaning, and the caller decodes them as it
+ * did before.  Nothing outside the B records and the status array is written.  Asynchronous on `stream`; B = 0 is a no-op. */
+int clipx_jpeg_scan_probe_host(const void* data, size_t n, int max_side, clipx_jpeg_desc* desc, size_t* scan_bytes);
+int clipx_jpeg_scan_host(const void* data, size_t n, int max_side, clipx_jpeg_desc* desc, void* scan, size_t scan_bytes);
+int clipx_jpeg_entropy_device(int device, const void* scans_dev, const clipx_jpeg_desc* descs, const int64_t* scan_offs, int B,
+                              void* coefs_dev, int32_t* status_dev, void* stream);
+
 /* Range guard.  The encoder keeps the residual stream of both towers in IEEE fp16: exact for every checkpoint that is
  * trained or served in fp16 (the reference's CUDA path runs the whole model in fp16, mapper.py:35-41), but a model whose
  * activations exceed 65 504 (possible for bf16-trained checkpoints) would overflow to inf, and LayerNorm turns a row holding inf

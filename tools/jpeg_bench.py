@@ -9,10 +9,17 @@
                      against on, for ViT-B/32 and ViT-L/14.
 Legs 1 and 3 run off / on alternating, several passes each after an untimed pass of both, and print every pass and the medians.
 
+With --legs huffman (or all), the Huffman stage on the device (`gpu_huffman`) beside the two:
+  4. Huffman stage   clipx_jpeg_entropy_device alone on a 256-image batch, events around the launch, for files without restart
+                     markers (one wave per image) and with one interval per MCU row; the single-core host entropy rate of the
+                     same files beside it; the bytes that travel in each form;
+  5. reader rate     leg 1 with 4 and 16 decode processes, off / host entropy / device entropy alternating;
+  6. pipeline        leg 3 in the same three settings.
+
 The workload: 256 x 256, quality 95, 4:2:0 JPEGs of the project's synthetic images (synth.synth_pixels_u8).  The "off" leg of the
 same run is the yardstick.
 
-    python tools/jpeg_bench.py [--workers 16] [--samples 32768] [--rounds 3] [--models ViT-B/32,ViT-L/14]
+    python tools/jpeg_bench.py [--workers 16] [--samples 32768] [--rounds 3] [--models ViT-B/32,ViT-L/14] [--legs jpeg|huffman|all]
 """
 import argparse
 import glob
@@ -136,6 +143,121 @@ def pipeline(paths, tmp, model, workers, gpu_jpeg, tag):
     return rows / dt, out
 
 
+MODES = {"off": {}, "host entropy": {"gpu_jpeg": True}, "device entropy": {"gpu_huffman": True}}
+
+
+def huffman_stage(restart):
+    """clipx_jpeg_entropy_device alone: 256 images, `restart` MCUs per interval (0: none, one wave per image)."""
+    import torch
+    from PIL import Image
+
+    from clip_retrieval_amd import jpeg
+    from clip_retrieval_amd.synth import synth_pixels_u8
+
+    files = []
+    for im in synth_pixels_u8(64, 256):
+        buf = io.BytesIO()
+        Image.fromarray(im).save(buf, format="JPEG", quality=95, subsampling=2, restart_marker_blocks=restart)
+        files.append(buf.getvalue())
+    files = [files[i % 64] for i in range(256)]
+    t0 = time.perf_counter()
+    host = [jpeg.entropy_packed(f) for f in files]
+    t1 = time.perf_counter()
+    packed = [jpeg.scan_packed(f) for f in files]
+    t2 = time.perf_counter()
+    scans, descs, offs, coef_bytes = jpeg.pack_scans(packed, True)
+    dev = scans.cuda()
+    coefs = torch.empty(coef_bytes, dtype=torch.uint8, device="cuda")
+    status = torch.empty(256, dtype=torch.int32, device="cuda")
+    for _ in range(3):
+        jpeg.entropy_device(0, dev, descs, offs, coefs, status)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    reps = 10
+    e0.record()
+    for _ in range(reps):
+        jpeg.entropy_device(0, dev, descs, offs, coefs, status)
+    e1.record()
+    torch.cuda.synchronize()
+    ms = e0.elapsed_time(e1) / reps
+    assert int(status.abs().sum()) == 0
+    got, want = coefs.cpu().numpy(), jpeg.unpack(host[0])[1]
+    assert np.array_equal(got[int(descs["coef_off"][0]):int(descs["coef_off"][0]) + want.size], want)
+    intervals = int(packed[0][64:128].view(jpeg.SCAN_HEADER)[0]["nintervals"])
+    print(f"Huffman stage alone, 256 images, {intervals} interval(s) per image: {ms:.2f} ms per batch = {256 / ms * 1e3:.0f} images/s "
+          f"(events around the launch, mean of {reps}); one host core: entropy stage {256 / (t1 - t0):.0f} images/s, scan preparation "
+          f"{256 / (t2 - t1):.0f} images/s; per image {np.mean([len(f) for f in files]) / 1024:.1f} KiB of file, {scans.numel() / 256 / 1024:.1f} KiB "
+          f"of scan record, {np.mean([h.size for h in host]) / 1024:.1f} KiB of coefficient record", flush=True)
+
+
+def reader_rate3(paths, workers, mode):
+    """reader_rate in one of MODES."""
+    import torch
+
+    from clip_retrieval_amd import load_library
+    from clip_retrieval_amd.encoder import resize_crop_device
+    from clip_retrieval_amd.reader import DecodeRgbU8, WebdatasetReader
+    from clip_retrieval_amd.runner import Sampler
+
+    lib = load_library()
+    r = WebdatasetReader(Sampler(0, 1), DecodeRgbU8(224, **MODES[mode]), None, paths, 256, workers, enable_text=False)
+    t0 = time.perf_counter()
+    n = taken = 0
+    for b in r:
+        jp = b.get("image_jpeg_scan") or b.get("image_jpeg")
+        out = resize_crop_device(lib, 0, 224, b["image_raw"], None, jp)
+        assert out.shape[0] == b["image_raw"]["hw"].shape[0]
+        n += out.shape[0]
+        taken += 0 if jp is None else len(jp["slots"])
+    torch.cuda.synchronize()
+    assert taken == (0 if mode == "off" else n)
+    return n / (time.perf_counter() - t0)
+
+
+def pipeline3(paths, tmp, model, workers, mode, tag):
+    from clip_retrieval_amd.worker import worker
+
+    out = os.path.join(tmp, f"out3-{model.replace('/', '_')}-{mode.replace(' ', '_')}-{tag}")
+    t0 = time.perf_counter()
+    worker([0], input_dataset=paths, output_folder=out, output_partition_count=1, input_format="webdataset", batch_size=256,
+           num_prepro_workers=workers, enable_text=False, enable_image=True, clip_model="random:" + model, gpu_resize=True, **MODES[mode])
+    dt = time.perf_counter() - t0
+    rows = sum(np.load(f, mmap_mode="r").shape[0] for f in glob.glob(out + "/img_emb/*.npy"))
+    return rows / dt, out
+
+
+def alternate3(name, run, rounds):
+    """The three MODES alternating, `rounds` times after one untimed pass of each."""
+    for mode in MODES:
+        run(mode, "warm")
+    rates = {mode: [] for mode in MODES}
+    for i in range(rounds):
+        for mode in MODES:
+            rates[mode].append(run(mode, str(i)))
+    for mode, v in rates.items():
+        print(f"{name}, {mode}: median {np.median(v):.0f} samples/s of {rounds} alternating passes ({', '.join(f'{x:.0f}' for x in v)})", flush=True)
+    off = np.median(rates["off"])
+    print(f"{name}: host entropy / off = {np.median(rates['host entropy']) / off:.3f}, device entropy / off = {np.median(rates['device entropy']) / off:.3f}", flush=True)
+
+
+def huffman_legs(a, paths, tmp):
+    for restart in (0, 16):  # 256 x 256 at 4:2:0 is 16 x 16 MCUs: 16 per interval is one interval per MCU row
+        huffman_stage(restart)
+    for w in sorted({a.few_workers, a.workers}):
+        alternate3(f"reader + upload + GPU resize, {w} decode processes", lambda mode, tag, w=w: reader_rate3(paths, w, mode), a.rounds)
+    for model in [m for m in a.models.split(",") if m]:
+        outs = {}
+
+        def run(mode, tag, model=model, outs=outs):
+            rate, outs[mode] = pipeline3(paths, tmp, model, a.workers, mode, tag)
+            return rate
+
+        alternate3(f"pipeline worker() {model} images, {a.workers} decode processes, gpu_resize", run, a.rounds)
+        embs = {mode: [np.load(f) for f in sorted(glob.glob(outs[mode] + "/img_emb/*.npy"))] for mode in MODES}
+        same = all(len(embs[m]) == len(embs["off"]) and all(np.array_equal(x, y) for x, y in zip(embs[m], embs["off"])) for m in MODES)
+        print(f"    {model}: embeddings of the three settings {'equal' if same else 'DIFFER'}", flush=True)
+
+
 def alternate(name, run, rounds):
     """off / on alternating, `rounds` times after one untimed pass of each (start-up of the decode processes, warm-up)."""
     run(False, "warm"), run(True, "warm")
@@ -156,6 +278,7 @@ def main():
     ap.add_argument("--few-workers", type=int, default=4, help="a second reader leg with this many decode processes")
     ap.add_argument("--rounds", type=int, default=3, help="alternating off / on passes per leg")
     ap.add_argument("--models", default="ViT-B/32,ViT-L/14")
+    ap.add_argument("--legs", default="jpeg", choices=("jpeg", "huffman", "all"), help="jpeg: legs 1 - 3; huffman: legs 4 - 6")
     a = ap.parse_args()
     tmp = tempfile.mkdtemp()
     paths, jpegs = make_shards(tmp, 8, a.samples // 8)
@@ -166,6 +289,11 @@ def main():
         with gzip.open(os.environ["CLIP_BPE_PATH"], "wt", encoding="utf-8") as f:
             f.write("#version: 0.2\nt h\nth e</w>\no f</w>\np h\n")
     print(f"host cores visible: {os.cpu_count()}; decode processes: {a.workers}", flush=True)
+    if a.legs in ("huffman", "all"):
+        huffman_legs(a, paths, tmp)
+    if a.legs == "huffman":
+        shutil.rmtree(tmp, ignore_errors=True)
+        return
     entropy_rate(jpegs)
     pixel_stage(jpegs)
     for w in sorted({a.few_workers, a.workers}):  # few processes: the decode is the bound; many: the parent process is

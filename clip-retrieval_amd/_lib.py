@@ -191,6 +191,8 @@ SIGNATURES = {
     "clipx_jpeg_scan_probe_host": (C.c_int, [_P, C.c_size_t, C.c_int, _P, C.POINTER(C.c_size_t)]),
     "clipx_jpeg_scan_host": (C.c_int, [_P, C.c_size_t, C.c_int, _P, _P, C.c_size_t]),
     "clipx_jpeg_entropy_device": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, _P, _P, _P]),
+    "clipx_jpeg_entropy_split_device": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
+    "clipx_jpeg_entropy_split_host": (C.c_int, [_P, C.c_size_t, _P, _P, _P, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "clipx_range_check": (C.c_int, [_P, _P]),
     "clipx_set_option": (C.c_int, [_P, C.c_int, C.c_int]),
     "clipx_get_option": (C.c_int, [_P, C.c_int]),

@@ -26,71 +26,14 @@
 #include "../../include/clipx.h"
 #include "clipx_host.h"
 #include "jpegx_scan.h"
+#include "jpegx_split.h"
+#include "jpeg_huff_dev.h"  // HImg, WaveBytes, LaneSink: shared with jpeg_split_kernels.hip
 
 static_assert(sizeof(clipx_jpeg_desc) == sizeof(jpegx::Desc), "clipx_jpeg_desc is jpegx::Desc");
 
 namespace {
 
-namespace S = jpegx::scan;
-
-struct HImg {            // one per image, in the table buffer
-  long long scan_off;    // byte offset of the scan record in the scan buffer
-  long long scan_avail;  // bytes the caller gave for it
-  long long coef_off;    // byte offset of the output record in the coefficient buffer
-  long long first[3];    // first block of each component's plane
-  int ncomp, hs, vs, mx;
-  int bw[3];
-  int nint;              // restart intervals
-  int mcus, per;         // MCUs of the image, MCUs per interval
-};
-static_assert(sizeof(HImg) % 8 == 0, "descriptors are read as an array");
-
-// zig-zag position of natural index i: the inverse of jpegx::detail::NATURAL
-__device__ const unsigned char ZIGZAG_OF[64] = {0,  1,  5,  6,  14, 15, 27, 28, 2,  4,  7,  13, 16, 26, 29, 42, 3,  8,  12, 17, 25, 30,
-                                                41, 43, 9,  11, 18, 24, 31, 40, 44, 53, 10, 19, 23, 32, 39, 45, 52, 54, 20, 22, 33, 38,
-                                                46, 51, 55, 60, 21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63};
-
-// The file's bytes as a wave reads them: a 256-byte window, one dword per lane, refilled when a position leaves it.  `padded` is the
-// file's length rounded up to 16 -- still inside the record -- and nothing is loaded past it.
-struct WaveBytes {
-  const unsigned char* file;  // 16-byte aligned
-  unsigned padded;
-  unsigned lo;  // first byte of the window (a multiple of 256); ~0: none yet
-  unsigned w;   // this lane's dword
-  __device__ __forceinline__ unsigned byte(unsigned pos) {
-    if ((pos & ~255u) != lo) {
-      lo = pos & ~255u;
-      const unsigned at = lo + 4u * threadIdx.x;
-      w = at + 4u <= padded ? *reinterpret_cast<const unsigned*>(file + at) : 0u;
-    }
-    const unsigned d = (unsigned)__builtin_amdgcn_readlane((int)w, (int)((pos & 255u) >> 2));
-    return (d >> (8u * (pos & 3u))) & 255u;
-  }
-};
-
-// The block under construction, one coefficient per lane.
-struct LaneSink {
-  short* coef;  // the image's coefficient area
-  long long first1, first2;
-  int zz;       // zig-zag position of this lane's coefficient
-  int q0, q1, q2;
-  int val, q;
-  short* row;
-  __device__ __forceinline__ void begin(int c, long long blk) {
-    val = 0;
-    q = c == 0 ? q0 : (c == 1 ? q1 : q2);
-    row = coef + ((c == 0 ? 0 : (c == 1 ? first1 : first2)) + blk) * 64;
-  }
-  __device__ __forceinline__ bool put(int k, int v) {
-    val = zz == k ? v : val;
-    return true;
-  }
-  __device__ __forceinline__ bool end() {
-    row[threadIdx.x] = (short)val;
-    const int t = val * q;
-    return __ballot(t > jpegx::MAX_ABS_DEQUANT || t < -jpegx::MAX_ABS_DEQUANT) == 0ull;
-  }
-};
+namespace P = jpegx::scan::split;
 
 // grid (most intervals of an image, B), 64 threads
 __global__ __launch_bounds__(64) void huff_kernel(const unsigned char* __restrict__ scans, const HImg* __restrict__ imgs,
@@ -186,35 +129,46 @@ extern "C" int clipx_jpeg_scan_host(const void* data, size_t n, int max_side, cl
   return CLIPX_JPEG_TAKEN;
 }
 
-extern "C" int clipx_jpeg_entropy_device(int device, const void* scans_dev, const clipx_jpeg_desc* descs, const int64_t* scan_offs, int B,
-                                         void* coefs_dev, int32_t* status_dev, void* stream) {
+// the descriptor is what the host preparation wrote; anything else must not reach a decoder that indexes with it
+static bool descriptor_ok(const clipx_jpeg_desc& s, long long* mcus_out) {
+  const bool gray = s.ncomp == 1;
+  bool ok = s.width >= 1 && s.height >= 1 && s.width <= 65535 && s.height <= 65535 && (gray || s.ncomp == 3) &&
+            ((s.hs == 1 && s.vs == 1) || (!gray && s.hs == 2 && (s.vs == 1 || s.vs == 2))) && s.coef_off >= 0 && (s.coef_off & 15) == 0 &&
+            s.restart >= 0;
+  if (ok) {
+    const int mx = (s.width + 8 * s.hs - 1) / (8 * s.hs), my = (s.height + 8 * s.vs - 1) / (8 * s.vs);
+    const long long mcus = (long long)mx * my;
+    long long blocks = mcus * s.hs * s.vs;
+    ok = s.bw[0] == mx * s.hs && s.bh[0] == my * s.vs;
+    for (int c = 1; c < s.ncomp; ++c) {
+      ok = ok && s.bw[c] == mx && s.bh[c] == my;
+      blocks += mcus;
+    }
+    ok = ok && blocks == s.blocks;
+    *mcus_out = mcus;
+  }
+  return ok;
+}
+
+// split_bytes 0: huff_kernel over the whole batch, as ever.  Otherwise the batch is cut into runs of consecutive images: a run of
+// images whose record extent leaves no room for an interval of 2 x split_bytes goes to huff_kernel; every other run gets two
+// launches on the same grid, huff_unsplit_kernel for the intervals the cut leaves whole (the host cannot see an interval's length:
+// it lies in the device record) and huff_split_kernel for the others.  They write disjoint rows.
+static int entropy_launch(int device, const void* scans_dev, const clipx_jpeg_desc* descs, const int64_t* scan_offs, int B, void* coefs_dev,
+                          int32_t* status_dev, unsigned split_bytes, int max_rounds, int32_t* rounds_dev, void* stream) {
   if (!scans_dev || !descs || !scan_offs || !coefs_dev || !status_dev || B < 0) return fail(CLIPX_E_ARG, "bad jpeg_entropy_device arguments");
   if (B == 0) return CLIPX_OK;
   if (device < 0 || device >= 64 || B > 65535) return fail(CLIPX_E_ARG, "bad device or more than 65535 images");
   if ((reinterpret_cast<uintptr_t>(scans_dev) & 15) || (reinterpret_cast<uintptr_t>(coefs_dev) & 15))
     return fail(CLIPX_E_ARG, "the scan and coefficient buffers must be 16-byte aligned");
   std::vector<HImg> tab((size_t)B);
-  long long max_int = 1;
+  std::vector<char> may_split((size_t)B, 0);
   for (int i = 0; i < B; ++i) {
     const clipx_jpeg_desc& s = descs[i];
     HImg& d = tab[i];
     const bool gray = s.ncomp == 1;
-    // the descriptor is what the host preparation wrote; anything else must not reach a kernel that indexes with it
-    bool ok = s.width >= 1 && s.height >= 1 && s.width <= 65535 && s.height <= 65535 && (gray || s.ncomp == 3) &&
-              ((s.hs == 1 && s.vs == 1) || (!gray && s.hs == 2 && (s.vs == 1 || s.vs == 2))) && s.coef_off >= 0 && (s.coef_off & 15) == 0 &&
-              s.restart >= 0;
     long long mcus = 0;
-    if (ok) {
-      const int mx = (s.width + 8 * s.hs - 1) / (8 * s.hs), my = (s.height + 8 * s.vs - 1) / (8 * s.vs);
-      mcus = (long long)mx * my;
-      long long blocks = mcus * s.hs * s.vs;
-      ok = s.bw[0] == mx * s.hs && s.bh[0] == my * s.vs;
-      for (int c = 1; c < s.ncomp; ++c) {
-        ok = ok && s.bw[c] == mx && s.bh[c] == my;
-        blocks += mcus;
-      }
-      ok = ok && blocks == s.blocks;
-    }
+    const bool ok = descriptor_ok(s, &mcus);
     if (!ok) return fail(CLIPX_E_ARG, "jpeg descriptor " + std::to_string(i) + " is not one the scan preparation writes");
     const long long per = s.restart > 0 ? std::min<long long>(s.restart, mcus) : mcus;
     const long long nint = (mcus + per - 1) / per;
@@ -234,7 +188,9 @@ extern "C" int clipx_jpeg_entropy_device(int device, const void* scans_dev, cons
     d.nint = (int)nint;
     d.mcus = (int)mcus;
     d.per = (int)per;
-    max_int = std::max(max_int, nint);
+    // (the record holds header, at least a DC and an AC table, intervals and the file: an interval cannot be longer than what is
+    // left for the file)
+    may_split[i] = split_bytes && avail - (long long)S::total_bytes(2, nint, 0) >= 2ll * split_bytes;
   }
   const size_t tab_bytes = tab.size() * sizeof(HImg);
 
@@ -259,15 +215,60 @@ extern "C" int clipx_jpeg_entropy_device(int device, const void* scans_dev, cons
   memcpy(sl->tab_host, tab.data(), tab_bytes);
   HIPCHK(hipMemcpyAsync(sl->tab_dev, sl->tab_host, tab_bytes, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemsetAsync(status_dev, 0, (size_t)B * sizeof(int32_t), st));
-  // (images per launch: a batch of files with a restart marker behind every MCU must not outgrow a grid)
-  const int step = (int)std::max<long long>(1, std::min<long long>(B, MAX_WAVES / max_int));
-  for (int b0 = 0; b0 < B; b0 += step) {
-    const int nb = std::min(step, B - b0);
-    hipLaunchKernelGGL(huff_kernel, dim3((unsigned)max_int, (unsigned)nb), dim3(64), 0, st, (const unsigned char*)scans_dev,
-                       (const HImg*)sl->tab_dev + b0, (unsigned char*)coefs_dev, (int*)status_dev + b0);
-    HIPCHK(hipGetLastError());
+  if (rounds_dev) HIPCHK(hipMemsetAsync(rounds_dev, 0, (size_t)B * sizeof(int32_t), st));
+  for (int r0 = 0; r0 < B;) {
+    int r1 = r0 + 1;
+    long long max_int = tab[r0].nint;
+    while (r1 < B && may_split[r1] == may_split[r0]) max_int = std::max<long long>(max_int, tab[r1++].nint);
+    // (images per launch: a batch of files with a restart marker behind every MCU must not outgrow a grid)
+    const int step = (int)std::max<long long>(1, std::min<long long>(r1 - r0, MAX_WAVES / max_int));
+    for (int b0 = r0; b0 < r1; b0 += step) {
+      const int nb = std::min(step, r1 - b0);
+      if (may_split[r0]) {
+        HIPCHK(clipx_jpeg_launch_split((unsigned)max_int, (unsigned)nb, st, (const unsigned char*)scans_dev, (const HImg*)sl->tab_dev + b0,
+                                       (unsigned char*)coefs_dev, (int*)status_dev + b0, rounds_dev ? (int*)rounds_dev + b0 : (int*)nullptr,
+                                       split_bytes, max_rounds));
+      } else {
+        hipLaunchKernelGGL(huff_kernel, dim3((unsigned)max_int, (unsigned)nb), dim3(64), 0, st, (const unsigned char*)scans_dev,
+                           (const HImg*)sl->tab_dev + b0, (unsigned char*)coefs_dev, (int*)status_dev + b0);
+      }
+      HIPCHK(hipGetLastError());
+    }
+    r0 = r1;
   }
   HIPCHK(hipEventRecord(sl->ev, st));
   sl->used = true;
+  return CLIPX_OK;
+}
+
+extern "C" int clipx_jpeg_entropy_device(int device, const void* scans_dev, const clipx_jpeg_desc* descs, const int64_t* scan_offs, int B,
+                                         void* coefs_dev, int32_t* status_dev, void* stream) {
+  return entropy_launch(device, scans_dev, descs, scan_offs, B, coefs_dev, status_dev, 0, 0, nullptr, stream);
+}
+
+static bool split_ok(const clipx_jpeg_split* split) {
+  return split && P::valid_split_bytes(split->split_bytes) && split->max_rounds >= 0 && split->reserved[0] == 0 && split->reserved[1] == 0;
+}
+
+extern "C" int clipx_jpeg_entropy_split_device(int device, const void* scans_dev, const clipx_jpeg_desc* descs, const int64_t* scan_offs,
+                                               int B, void* coefs_dev, int32_t* status_dev, const clipx_jpeg_split* split,
+                                               int32_t* rounds_dev, void* stream) {
+  if (!split_ok(split)) return fail(CLIPX_E_ARG, "jpeg split: split_bytes must be 0 or a power of two 32 .. 1024, max_rounds >= 0, reserved 0");
+  return entropy_launch(device, scans_dev, descs, scan_offs, B, coefs_dev, status_dev, (unsigned)split->split_bytes,
+                        split->max_rounds ? split->max_rounds : P::DEFAULT_MAX_ROUNDS, rounds_dev, stream);
+}
+
+extern "C" int clipx_jpeg_entropy_split_host(const void* scan, size_t scan_bytes, const clipx_jpeg_desc* desc, const clipx_jpeg_split* split,
+                                             void* record, size_t record_bytes, int32_t* status, int32_t* rounds) {
+  if (!scan || !desc || !record || !status || !rounds) return fail(CLIPX_E_ARG, "bad jpeg_entropy_split_host arguments");
+  if (!split_ok(split)) return fail(CLIPX_E_ARG, "jpeg split: split_bytes must be 0 or a power of two 32 .. 1024, max_rounds >= 0, reserved 0");
+  jpegx::Desc d;
+  memcpy(&d, desc, sizeof(d));
+  long long mcus = 0;
+  if (!descriptor_ok(*desc, &mcus) || S::intervals_of(d) > MAX_INTERVALS) return fail(CLIPX_E_ARG, "the jpeg descriptor is not one the scan preparation writes");
+  if (record_bytes < jpegx::record_bytes(d)) return fail(CLIPX_E_ARG, "the record buffer is smaller than the descriptor's record");
+  if ((reinterpret_cast<uintptr_t>(scan) & 15) || scan_bytes < S::total_bytes(1, S::intervals_of(d), 0)) return fail(CLIPX_E_ARG, "the scan record is not 16-byte aligned or shorter than its fixed part");
+  P::decode_record_host(static_cast<const uint8_t*>(scan), scan_bytes, d, (uint32_t)split->split_bytes,
+                        split->max_rounds ? split->max_rounds : P::DEFAULT_MAX_ROUNDS, static_cast<uint8_t*>(record), status, rounds);
   return CLIPX_OK;
 }

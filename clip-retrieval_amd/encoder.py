@@ -231,7 +231,8 @@ def resize_crop_device(lib, device, S, raw, stream=None, jpeg=None, preprocess=N
     coefficients only uploads no pixel at all.
 
     The scan form: `jpeg` is the batch's `image_jpeg_scan` ({"scans", "descs", "offs", "coef_bytes", "slots", "names"}).  The scan
-    records are uploaded and Huffman-decoded on the device (clipx_jpeg_entropy_device); the statuses come back and are WAITED for; an
+    records are uploaded and Huffman-decoded on the device (clipx_jpeg_entropy_device, or clipx_jpeg_entropy_split_device when the
+    entry carries a non-zero "split_bytes"); the statuses come back and are WAITED for; an
     image with a non-zero status -- one the host entropy stage would have deferred -- is decoded late, here, by Pillow, through
     `preprocess` (default: reader.DecodeRgbU8(S)) exactly as the deferred branch of reader._decode_sample decodes, and its pixels are
     uploaded into its slot; where that fails too, the ROW IS DROPPED with that branch's skip line.  The result then has fewer rows
@@ -262,7 +263,7 @@ def resize_crop_device(lib, device, S, raw, stream=None, jpeg=None, preprocess=N
             scans = jpeg["scans"].to(dev, non_blocking=True)
             coefs = torch.empty(int(jpeg["coef_bytes"]), dtype=torch.uint8, device=dev)
             status = torch.empty(len(slots), dtype=torch.int32, device=dev)
-            entropy_device(device, scans, descs, jpeg["offs"], coefs, status, st, lib)
+            entropy_device(device, scans, descs, jpeg["offs"], coefs, status, st, lib, split_bytes=int(jpeg.get("split_bytes", 0)))
             unclean = np.flatnonzero(status.cpu().numpy())  # (waits for the Huffman kernel)
             dropped = []
             for j in unclean:

@@ -138,7 +138,39 @@ def pack_scans(packed, pin=False):
     return buf, descs, offs, int(rec.sum())
 
 
-def entropy_device(device, scans_dev, descs, scan_offs, coefs_dev, status_dev, stream=None, lib=None):
+JPEG_SPLIT = np.dtype([("split_bytes", "<i4"), ("max_rounds", "<i4"), ("reserved", "<i4", (2,))])  # clipx_jpeg_split of include/clipx.h
+SPLIT_SIZES = (0, 32, 64, 128, 256, 512, 1024)
+SPLIT_DEFAULT_ROUNDS = 16  # DEFAULT_MAX_ROUNDS of csrc/jpegx_split.h: what max_rounds=0 stands for
+
+
+def _split_arg(split_bytes, max_rounds):
+    if int(split_bytes) not in SPLIT_SIZES or int(max_rounds) < 0:
+        raise ValueError("split_bytes is 0 or a power of two 32 .. 1024, max_rounds is 0 (the default) or >= 1")
+    arg = np.zeros(1, dtype=JPEG_SPLIT)
+    arg["split_bytes"], arg["max_rounds"] = int(split_bytes), int(max_rounds)
+    return arg
+
+
+def entropy_split_host(scan, desc, split_bytes, max_rounds=0, lib=None):
+    """The split Huffman decode of csrc/jpegx_split.h on the host, lanes as a loop (no GPU): `scan` is ONE scan record (a
+    scan_packed() array behind its 64-byte descriptor), `desc` its descriptor -> (status, record uint8 [record_bytes], rounds), what
+    the device entry writes for that image (rounds: 0 not split, r >= 2 rounds taken, -r gave up after r rounds and decoded serially)."""
+    lib = lib or load_library()
+    desc = np.ascontiguousarray(desc, dtype=JPEG_DESC).reshape(-1)[:1].copy()
+    aligned = np.empty(np.asarray(scan).size + 16, dtype=np.uint8)
+    at = (-aligned.ctypes.data) & 15
+    rec = aligned[at:at + np.asarray(scan).size]
+    rec[:] = np.asarray(scan, dtype=np.uint8)
+    out = np.empty(record_bytes(desc[0]), dtype=np.uint8)
+    arg = _split_arg(split_bytes, max_rounds)
+    status, rounds = C.c_int32(-1), C.c_int32(0)
+    check(lib, lib.clipx_jpeg_entropy_split_host(rec.ctypes.data, rec.size, desc.ctypes.data, arg.ctypes.data, out.ctypes.data, out.size,
+                                                 C.byref(status), C.byref(rounds)), "clipx")
+    return status.value, out, rounds.value
+
+
+def entropy_device(device, scans_dev, descs, scan_offs, coefs_dev, status_dev, stream=None, lib=None, split_bytes=0, max_rounds=0,
+                   rounds_dev=None):
     """Run the Huffman stage on the device: scan record i (bytes [scan_offs[i], scan_offs[i + 1]) of the device tensor `scans_dev`)
     becomes the record pixels_device reads at descs[i].coef_off of `coefs_dev`; status_dev (device int32 [>= n]) gets 0 per clean
     image and a reason code per image the host stage would have deferred.  Asynchronous on `stream` (a hipStream_t value; None:
@@ -163,6 +195,15 @@ def entropy_device(device, scans_dev, descs, scan_offs, coefs_dev, status_dev, s
     if status_dev.numel() < n:
         raise ValueError("one status word per image")
     st = stream if stream is not None else torch.cuda.current_stream(torch.device("cuda", device)).cuda_stream
+    if split_bytes or max_rounds or rounds_dev is not None:  # the split decode inside an interval
+        arg = _split_arg(split_bytes, max_rounds)
+        if rounds_dev is not None and (rounds_dev.dtype != torch.int32 or not rounds_dev.is_contiguous() or rounds_dev.numel() < n):
+            raise ValueError("rounds_dev is a contiguous int32 tensor with one word per image")
+        check(lib, lib.clipx_jpeg_entropy_split_device(device, C.c_void_p(scans_dev.data_ptr()), descs.ctypes.data, scan_offs.ctypes.data, n,
+                                                       C.c_void_p(coefs_dev.data_ptr()), C.c_void_p(status_dev.data_ptr()), arg.ctypes.data,
+                                                       C.c_void_p(rounds_dev.data_ptr()) if rounds_dev is not None else None,
+                                                       C.c_void_p(st) if st else None), "clipx")
+        return
     check(lib, lib.clipx_jpeg_entropy_device(device, C.c_void_p(scans_dev.data_ptr()), descs.ctypes.data, scan_offs.ctypes.data, n,
                                              C.c_void_p(coefs_dev.data_ptr()), C.c_void_p(status_dev.data_ptr()),
                                              C.c_void_p(st) if st else None), "clipx")

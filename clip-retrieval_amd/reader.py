@@ -87,16 +87,27 @@ class DecodeRgbU8:
     process only parses the markers of a baseline JPEG (`scan`, csrc/jpegx_scan.h) and the sample travels as `image_jpeg_scan`: the
     file's own bytes with its tables and restart intervals laid out for the device.  A file the device stage then finds malformed is
     decoded late, by Pillow, in the process that runs the GPU (encoder.resize_crop_device), and dropped there if Pillow fails too.  An
-    instance emits coefficients or scans, never both."""
+    instance emits coefficients or scans, never both.
+
+    huffman_split (0 = off, the default; needs gpu_huffman): the device stage cuts every restart interval of at least twice that many
+    bytes into sub-sequences of that size and decodes them concurrently (csrc/jpegx_split.h) -- the parallelism a file
+    without restart markers otherwise lacks.  The samples are the same; the batch carries the size as `split_bytes` of its
+    `image_jpeg_scan` entry, and the records, statuses and late decodes are those of huffman_split=0."""
 
     raw_images = True  # readers: collate as `image_raw`, not as a stacked `image_tensor`
     GPU_MODES = ("RGB", "L")
     gpu_jpeg = False  # (class default: instances pickled before the switch existed stay off)
     gpu_huffman = False
+    huffman_split = 0
 
-    def __init__(self, size=224, max_side=8192, max_downscale=16, gpu_jpeg=False, gpu_huffman=False):
+    def __init__(self, size=224, max_side=8192, max_downscale=16, gpu_jpeg=False, gpu_huffman=False, huffman_split=0):
         self.size, self.max_side, self.max_downscale = size, max_side, max_downscale
         self.gpu_huffman = bool(gpu_huffman)
+        self.huffman_split = int(huffman_split)
+        if self.huffman_split and not self.gpu_huffman:
+            raise ValueError("huffman_split needs gpu_huffman: it is a setting of the Huffman stage on the device")
+        if self.huffman_split not in (0, 32, 64, 128, 256, 512, 1024):
+            raise ValueError("huffman_split is 0 or a power of two 32 .. 1024")
         self.gpu_jpeg = bool(gpu_jpeg) or self.gpu_huffman
 
     def entropy(self, data):
@@ -219,7 +230,7 @@ def folder_to_keys(folder, enable_text=True, enable_image=True, enable_metadata=
     return keys, remap(text_files), remap(image_files), remap(metadata_files)
 
 
-def _collate(samples, enable_image, enable_text, enable_metadata, pin):
+def _collate(samples, enable_image, enable_text, enable_metadata, pin, split_bytes=0):
     import torch  # pylint: disable=import-outside-toplevel
 
     batch = {}
@@ -261,6 +272,8 @@ def _collate(samples, enable_image, enable_text, enable_metadata, pin):
             # and its name, for the skip line of a file that the device and then Pillow refuse (encoder.resize_crop_device)
             batch["image_jpeg_scan"] = {"scans": scan_buf, "descs": descs, "offs": scan_offs, "coef_bytes": coef_bytes,
                                         "slots": np.asarray(slots, dtype=np.int64), "names": [samples[i]["image_filename"] for i in scans]}
+            if split_bytes:  # (DecodeRgbU8(huffman_split=...): the device stage splits long restart intervals)
+                batch["image_jpeg_scan"]["split_bytes"] = int(split_bytes)
         elif slots:
             # coefficients of the images the GPU decodes: one page-locked buffer of records + descriptors + each image's slot of the
             # batch, whose h * w * 3 bytes above are reserved and left unwritten (clipx_jpeg_pixels_device fills them on the device)
@@ -683,10 +696,12 @@ class _BatchingReader:
             full = taken == self.batch_size if self.batch_before_filter else len(pending) == self.batch_size
             if full:
                 if pending:
-                    yield _collate(pending, self.enable_image, self.enable_text, self.enable_metadata, self.pin)
+                    yield _collate(pending, self.enable_image, self.enable_text, self.enable_metadata, self.pin,
+                               getattr(self.preprocess, "huffman_split", 0))
                 pending, taken = [], 0
         if pending:
-            yield _collate(pending, self.enable_image, self.enable_text, self.enable_metadata, self.pin)
+            yield _collate(pending, self.enable_image, self.enable_text, self.enable_metadata, self.pin,
+                               getattr(self.preprocess, "huffman_split", 0))
 
     def __iter__(self):
         return self._batches(self._decoded())

@@ -67,6 +67,7 @@ def worker(
     gpu_resize=False,
     gpu_jpeg=False,
     gpu_huffman=False,
+    gpu_huffman_split=0,
 ):
     """Start a worker.  gpu_normalise (not in the reference): the readers resize / crop on the host and hand uint8 pixels to
     the mapper, which normalises on the GPU; False reproduces the reference's float32 `image_tensor` batches.  gpu_resize (not in
@@ -75,8 +76,11 @@ def worker(
     upsampling and colour conversion run on the GPU, bit-identical to Pillow (csrc/jpeg_kernels.hip); other files go through Pillow.
     gpu_huffman (not in the reference; implies gpu_jpeg): the decode processes only parse the markers of baseline JPEGs; Huffman
     decoding runs on the GPU too (csrc/jpeg_huff_kernels.hip); a file the device finds malformed is decoded late by Pillow in this
-    process, and skipped if Pillow fails as well."""
+    process, and skipped if Pillow fails as well.  gpu_huffman_split (0 = off; needs gpu_huffman): the device cuts restart intervals
+    of at least twice that many bytes into sub-sequences of that size (a power of two 32 .. 1024) and decodes them concurrently."""
     print("Starting the worker", flush=True)
+    if gpu_huffman_split and not gpu_huffman:
+        raise ValueError("gpu_huffman_split needs gpu_huffman")
     if input_format == "webdataset" and not isinstance(input_dataset, list):
         input_dataset = braceexpand(input_dataset)
     print(f"dataset is {len(input_dataset)}", flush=True)
@@ -85,7 +89,8 @@ def worker(
         model, preprocess, tokenizer = load_clip(clip_model=clip_model, use_jit=use_jit, warmup_batch_size=0,
                                                  clip_cache_path=clip_cache_path, device=device)
         if gpu_resize or gpu_jpeg or gpu_huffman:  # decode only; geometry and normalisation on the GPU (non-RGB modes and oversized sources: host crop)
-            preprocess = DecodeRgbU8(model._enc.arch.image_size, gpu_jpeg=gpu_jpeg, gpu_huffman=gpu_huffman)  # pylint: disable=protected-access
+            preprocess = DecodeRgbU8(model._enc.arch.image_size, gpu_jpeg=gpu_jpeg, gpu_huffman=gpu_huffman,
+                                     huffman_split=gpu_huffman_split)  # pylint: disable=protected-access
         elif gpu_normalise:
             size = model._enc.arch.image_size  # pylint: disable=protected-access
             preprocess = functools.partial(clip_preprocess_u8, size=size)  # picklable: travels to the decode processes
@@ -176,6 +181,7 @@ def _main(argv=None):
     ap.add_argument("--gpu_resize", type=truth, help="decode only on the host; resize + centre crop on the GPU too, bit-identical to Pillow (default false)")
     ap.add_argument("--gpu_jpeg", type=truth, help="baseline JPEGs: Huffman decoding on the host, the rest of the decode on the GPU, bit-identical to Pillow (default false)")
     ap.add_argument("--gpu_huffman", type=truth, help="baseline JPEGs: only the markers are parsed on the host, Huffman decoding and the rest of the decode run on the GPU, bit-identical to Pillow (default false)")
+    ap.add_argument("--gpu_huffman_split", type=int, help="with --gpu_huffman: split restart intervals into sub-sequences of this many bytes (a power of two 32 .. 1024) and decode them concurrently on the GPU (default 0: off)")
     gpu_worker(**vars(ap.parse_args(argv)))
 
 

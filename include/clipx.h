@@ -193,6 +193,29 @@ int clipx_jpeg_scan_host(const void* data, size_t n, int max_side, clipx_jpeg_de
 int clipx_jpeg_entropy_device(int device, const void* scans_dev, const clipx_jpeg_desc* descs, const int64_t* scan_offs, int B,
                               void* coefs_dev, int32_t* status_dev, void* stream);
 
+/* Split decode inside a restart interval (`huffman_split`; csrc/jpegx_split.h, csrc/jpeg_split_kernels.hip).  A file
+ * without restart markers is ONE interval, which clipx_jpeg_entropy_device gives one wave.  With split_bytes != 0 an interval of at
+ * least 2 x split_bytes entropy-coded bytes is cut into sub-sequences of split_bytes (doubled until there are at most 512), which
+ * one workgroup decodes concurrently: each starts from a guessed state and is decoded again from its predecessor's exit state until
+ * a round changes nothing (self-synchronisation), then one more pass writes the coefficients.  Records, statuses and verdicts are
+ * those of clipx_jpeg_entropy_device, byte for byte and code for code.  An interval that has not reached the fixed point after
+ * max_rounds rounds (periodic content never does before its last sub-sequence) is decoded serially, with the same result.
+ *   split_bytes  0 (no interval is split: exactly clipx_jpeg_entropy_device) or a power of two 32 .. 1024
+ *   max_rounds   0 = the library's default (16), else >= 1
+ *   reserved     must be 0
+ * rounds_dev (device int32 [B], or NULL) / *rounds: 0 -- no interval of the image was split; r >= 2 -- the most rounds a split
+ * interval of the image took, the round in which nothing decodes counted; -r -- at least one interval gave up after r = max_rounds
+ * rounds and was decoded serially.  Nothing outside the B records, the status array and rounds_dev is written.
+ * clipx_jpeg_entropy_split_host runs the same decoder on the host with the lanes as a loop, on ONE scan record (16-byte aligned, as
+ * clipx_jpeg_scan_host wrote it, with its descriptor): no HIP call, usable without a GPU.  `record` (record_bytes >= the
+ * descriptor's record) receives [tables | coefficients], *status and *rounds what the device entry writes for that image. */
+typedef struct { int32_t split_bytes; int32_t max_rounds; int32_t reserved[2]; } clipx_jpeg_split;
+int clipx_jpeg_entropy_split_device(int device, const void* scans_dev, const clipx_jpeg_desc* descs, const int64_t* scan_offs,
+                                    int B, void* coefs_dev, int32_t* status_dev, const clipx_jpeg_split* split,
+                                    int32_t* rounds_dev /* [B] or NULL */, void* stream);
+int clipx_jpeg_entropy_split_host(const void* scan, size_t scan_bytes, const clipx_jpeg_desc* desc, const clipx_jpeg_split* split,
+                                  void* record, size_t record_bytes, int32_t* status, int32_t* rounds);
+
 /* Range guard.  The encoder keeps the residual stream of both towers in IEEE fp16: exact for every checkpoint that is
  * trained or served in fp16 (the reference's CUDA path runs the whole model in fp16, mapper.py:35-41), but a model whose
  * activations exceed 65 504 (possible for bf16-trained checkpoints) would overflow to inf, and LayerNorm turns a row holding inf

@@ -12,9 +12,12 @@ Legs 1 and 3 run off / on alternating, several passes each after an untimed pass
 With --legs huffman (or all), the Huffman stage on the device (`gpu_huffman`) beside the two:
   4. Huffman stage   clipx_jpeg_entropy_device alone on a 256-image batch, events around the launch, for files without restart
                      markers (one wave per image) and with one interval per MCU row; the single-core host entropy rate of the
-                     same files beside it; the bytes that travel in each form;
-  5. reader rate     leg 1 with 4 and 16 decode processes, off / host entropy / device entropy alternating;
-  6. pipeline        leg 3 in the same three settings.
+                     same files beside it; the bytes that travel in each form; for the files without restart markers also the
+                     split decode inside an interval at 128 / 256 / 512 bytes, alternating with the serial form in
+                     the same run, and the distribution of `rounds` over the files;
+  5. reader rate     leg 1 with 4 and 16 decode processes, off / host entropy / device entropy / device split 128 / 256 / 512
+                     alternating;
+  6. pipeline        leg 3 in the same six settings.
 
 The workload: 256 x 256, quality 95, 4:2:0 JPEGs of the project's synthetic images (synth.synth_pixels_u8).  The "off" leg of the
 same run is the yardstick.
@@ -143,7 +146,47 @@ def pipeline(paths, tmp, model, workers, gpu_jpeg, tag):
     return rows / dt, out
 
 
-MODES = {"off": {}, "host entropy": {"gpu_jpeg": True}, "device entropy": {"gpu_huffman": True}}
+SPLITS = (128, 256, 512)  # split_bytes of the split decode inside an interval
+MODES = {"off": {}, "host entropy": {"gpu_jpeg": True}, "device entropy": {"gpu_huffman": True},
+         **{f"device split {n}": {"gpu_huffman": True, "huffman_split": n} for n in SPLITS}}
+
+
+def split_stage(files, dev, descs, offs, coefs, status, want):
+    """The device stage on the batch without restart markers: serial (one wave per image) and every split size alternating in ONE
+    run, each launch between its own events, medians; then the distribution of `rounds` over the distinct files."""
+    import torch
+
+    from clip_retrieval_amd import jpeg
+
+    settings = (0,) + SPLITS
+    rounds = torch.zeros(256, dtype=torch.int32, device="cuda")
+    ms = {n: [] for n in settings}
+    for rep in range(13):  # (the first pass of each setting is the warm-up)
+        for n in settings:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            jpeg.entropy_device(0, dev, descs, offs, coefs, status, split_bytes=n)
+            e1.record()
+            torch.cuda.synchronize()
+            if rep:
+                ms[n].append(e0.elapsed_time(e1))
+            assert int(status.abs().sum()) == 0
+            got = coefs.cpu().numpy()[int(descs["coef_off"][0]):int(descs["coef_off"][0]) + want.size] if rep == 0 else want
+            assert np.array_equal(got, want)
+    base = np.median(ms[0])
+    for n in settings:
+        v = ms[n]
+        print(f"Huffman stage alone, 256 images without restart markers, {'serial (one wave per image)' if n == 0 else f'split {n}'}: median "
+              f"{np.median(v):.2f} ms per batch of 12 alternating launches (min {min(v):.2f}, max {max(v):.2f}) = {base / np.median(v):.2f} x serial",
+              flush=True)
+    for n in SPLITS:
+        jpeg.entropy_device(0, dev, descs, offs, coefs, status, split_bytes=n, max_rounds=4096, rounds_dev=rounds)
+        r = rounds.cpu().numpy()[:64]  # (the batch repeats 64 distinct files)
+        hist = ", ".join(f"{k}: {c}" for k, c in sorted(zip(*np.unique(r, return_counts=True))))
+        over = int((r > jpeg.SPLIT_DEFAULT_ROUNDS).sum())
+        print(f"rounds to the fixed point at split {n}, 64 files, max_rounds 4096: min {r.min()}, median {int(np.median(r))}, p99 "
+              f"{int(np.percentile(r, 99))}, max {r.max()}; above the default cap of {jpeg.SPLIT_DEFAULT_ROUNDS}: {over} of 64 "
+              f"({100 * over / 64:.1f} % would fall back); histogram {{{hist}}}", flush=True)
 
 
 def huffman_stage(restart):
@@ -188,6 +231,8 @@ def huffman_stage(restart):
           f"(events around the launch, mean of {reps}); one host core: entropy stage {256 / (t1 - t0):.0f} images/s, scan preparation "
           f"{256 / (t2 - t1):.0f} images/s; per image {np.mean([len(f) for f in files]) / 1024:.1f} KiB of file, {scans.numel() / 256 / 1024:.1f} KiB "
           f"of scan record, {np.mean([h.size for h in host]) / 1024:.1f} KiB of coefficient record", flush=True)
+    if intervals == 1:
+        split_stage(files, dev, descs, offs, coefs, status, want)
 
 
 def reader_rate3(paths, workers, mode):
@@ -219,15 +264,16 @@ def pipeline3(paths, tmp, model, workers, mode, tag):
 
     out = os.path.join(tmp, f"out3-{model.replace('/', '_')}-{mode.replace(' ', '_')}-{tag}")
     t0 = time.perf_counter()
+    switches = {("gpu_huffman_split" if k == "huffman_split" else k): v for k, v in MODES[mode].items()}
     worker([0], input_dataset=paths, output_folder=out, output_partition_count=1, input_format="webdataset", batch_size=256,
-           num_prepro_workers=workers, enable_text=False, enable_image=True, clip_model="random:" + model, gpu_resize=True, **MODES[mode])
+           num_prepro_workers=workers, enable_text=False, enable_image=True, clip_model="random:" + model, gpu_resize=True, **switches)
     dt = time.perf_counter() - t0
     rows = sum(np.load(f, mmap_mode="r").shape[0] for f in glob.glob(out + "/img_emb/*.npy"))
     return rows / dt, out
 
 
 def alternate3(name, run, rounds):
-    """The three MODES alternating, `rounds` times after one untimed pass of each."""
+    """The MODES alternating, `rounds` times after one untimed pass of each."""
     for mode in MODES:
         run(mode, "warm")
     rates = {mode: [] for mode in MODES}
@@ -237,7 +283,7 @@ def alternate3(name, run, rounds):
     for mode, v in rates.items():
         print(f"{name}, {mode}: median {np.median(v):.0f} samples/s of {rounds} alternating passes ({', '.join(f'{x:.0f}' for x in v)})", flush=True)
     off = np.median(rates["off"])
-    print(f"{name}: host entropy / off = {np.median(rates['host entropy']) / off:.3f}, device entropy / off = {np.median(rates['device entropy']) / off:.3f}", flush=True)
+    print(f"{name}: " + ", ".join(f"{mode} / off = {np.median(v) / off:.3f}" for mode, v in rates.items() if mode != "off"), flush=True)
 
 
 def huffman_legs(a, paths, tmp):
@@ -255,7 +301,7 @@ def huffman_legs(a, paths, tmp):
         alternate3(f"pipeline worker() {model} images, {a.workers} decode processes, gpu_resize", run, a.rounds)
         embs = {mode: [np.load(f) for f in sorted(glob.glob(outs[mode] + "/img_emb/*.npy"))] for mode in MODES}
         same = all(len(embs[m]) == len(embs["off"]) and all(np.array_equal(x, y) for x, y in zip(embs[m], embs["off"])) for m in MODES)
-        print(f"    {model}: embeddings of the three settings {'equal' if same else 'DIFFER'}", flush=True)
+        print(f"    {model}: embeddings of the {len(MODES)} settings {'equal' if same else 'DIFFER'}", flush=True)
 
 
 def alternate(name, run, rounds):

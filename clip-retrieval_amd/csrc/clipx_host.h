@@ -1,5 +1,5 @@
 // clipx_host.h -- shared by the HOST translation units of the encode half (clipx_api / clipx_encode / clipx_host_path /
-// clipx_hooks / bertx_api / preprocess / jpeg_kernels .hip): the one error channel of clipx_last_error(), the device-open helper,
+// clipx_hooks / bertx_api / preprocess / jpeg_kernels / jpeg_huff_kernels .hip): the one error channel of clipx_last_error(), the device-open helper,
 // the pieces both encoder handles are built from (int-slot ring, range guard, workspace gate), the CLIP handle with its state
 // grouped by concern, the per-call state, and the handful of functions one file calls in another.
 //

@@ -1,6 +1,7 @@
 // hip_owners.h -- the owners of device memory, pinned memory, streams, events and graph execs that both host layers build their
-// handles from (knnx_host.h, clipx_host.h).  Move-only; each converts to the raw handle it holds, so it is passed to launchers
-// and copies like that handle.  The HIP runtime only: no error codes of either ABI, nothing else of the project.
+// handles from (knnx_host.h, clipx_host.h), as do the image front end's upload ring (clipx_upload_ring.h) and postfilter.hip.
+// Move-only; each converts to the raw handle it holds, so it is passed to launchers and copies like that handle.  The HIP runtime
+// only: no error codes of either ABI, nothing else of the project.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -76,6 +77,24 @@ struct PinBuf {
     bytes = 0;
   }
   operator void*() const { return p; }
+};
+
+// grow-only device buffer of bytes, PinBuf's device twin (a DevBuf keeps no capacity); empty again after a failed ensure()
+struct DevGrow {
+  DevBuf<void> buf;
+  size_t bytes = 0;
+  hipError_t ensure(size_t want) {
+    if (bytes >= want) return hipSuccess;
+    bytes = 0;
+    hipError_t e = buf.alloc(want);
+    if (e == hipSuccess) bytes = want;
+    return e;
+  }
+  void reset() {
+    buf.reset();
+    bytes = 0;
+  }
+  operator void*() const { return buf.p; }
 };
 
 struct Stream {

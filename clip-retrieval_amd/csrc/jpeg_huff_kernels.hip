@@ -25,6 +25,7 @@
 
 #include "../../include/clipx.h"
 #include "clipx_host.h"
+#include "clipx_upload_ring.h"
 #include "jpegx_scan.h"
 #include "jpegx_split.h"
 #include "jpeg_huff_dev.h"  // HImg, WaveBytes, LaneSink: shared with jpeg_split_kernels.hip
@@ -89,20 +90,11 @@ __global__ __launch_bounds__(64) void huff_kernel(const unsigned char* __restric
   if (code && lane == 0) atomicMax(status + blockIdx.y, code);
 }
 
-// per device: a small ring of image tables, each slot guarded by the event of the launch that last used it
-struct Slot {
-  void* tab_dev = nullptr;
-  void* tab_host = nullptr;  // page-locked: the upload is a true asynchronous copy
-  size_t tab_bytes = 0;
-  hipEvent_t ev = nullptr;
-  bool used = false;
-};
-struct Ring {
-  Slot slot[4];
-  int next = 0;
-};
-std::mutex g_mu;
-Ring g_ring[64];
+// image tables of at least 64 KiB; made once and never deleted (clipx_upload_ring.h)
+clipx::UploadRing& table_ring() {
+  static clipx::UploadRing* const ring = new clipx::UploadRing((size_t)64 << 10);
+  return *ring;
+}
 
 constexpr long long MAX_INTERVALS = 1ll << 22;  // of one image (8192 x 8192 at 4:4:4 with a restart marker behind every MCU has 2^20)
 constexpr long long MAX_WAVES = 1ll << 24;      // of one launch
@@ -129,27 +121,6 @@ extern "C" int clipx_jpeg_scan_host(const void* data, size_t n, int max_side, cl
   return CLIPX_JPEG_TAKEN;
 }
 
-// the descriptor is what the host preparation wrote; anything else must not reach a decoder that indexes with it
-static bool descriptor_ok(const clipx_jpeg_desc& s, long long* mcus_out) {
-  const bool gray = s.ncomp == 1;
-  bool ok = s.width >= 1 && s.height >= 1 && s.width <= 65535 && s.height <= 65535 && (gray || s.ncomp == 3) &&
-            ((s.hs == 1 && s.vs == 1) || (!gray && s.hs == 2 && (s.vs == 1 || s.vs == 2))) && s.coef_off >= 0 && (s.coef_off & 15) == 0 &&
-            s.restart >= 0;
-  if (ok) {
-    const int mx = (s.width + 8 * s.hs - 1) / (8 * s.hs), my = (s.height + 8 * s.vs - 1) / (8 * s.vs);
-    const long long mcus = (long long)mx * my;
-    long long blocks = mcus * s.hs * s.vs;
-    ok = s.bw[0] == mx * s.hs && s.bh[0] == my * s.vs;
-    for (int c = 1; c < s.ncomp; ++c) {
-      ok = ok && s.bw[c] == mx && s.bh[c] == my;
-      blocks += mcus;
-    }
-    ok = ok && blocks == s.blocks;
-    *mcus_out = mcus;
-  }
-  return ok;
-}
-
 // split_bytes 0: huff_kernel over the whole batch, as ever.  Otherwise the batch is cut into runs of consecutive images: a run of
 // images whose record extent leaves no room for an interval of 2 x split_bytes goes to huff_kernel; every other run gets two
 // launches on the same grid, huff_unsplit_kernel for the intervals the cut leaves whole (the host cannot see an interval's length:
@@ -167,9 +138,12 @@ static int entropy_launch(int device, const void* scans_dev, const clipx_jpeg_de
     const clipx_jpeg_desc& s = descs[i];
     HImg& d = tab[i];
     const bool gray = s.ncomp == 1;
+    // the descriptor is what the host preparation wrote; anything else must not reach a decoder that indexes with it
+    jpegx::Desc jd;
+    memcpy(&jd, &s, sizeof(jd));
     long long mcus = 0;
-    const bool ok = descriptor_ok(s, &mcus);
-    if (!ok) return fail(CLIPX_E_ARG, "jpeg descriptor " + std::to_string(i) + " is not one the scan preparation writes");
+    if (!jpegx::desc_consistent(jd, &mcus) || s.restart < 0)
+      return fail(CLIPX_E_ARG, "jpeg descriptor " + std::to_string(i) + " is not one the scan preparation writes");
     const long long per = s.restart > 0 ? std::min<long long>(s.restart, mcus) : mcus;
     const long long nint = (mcus + per - 1) / per;
     if (nint > MAX_INTERVALS) return fail(CLIPX_E_UNSUPPORTED, "image " + std::to_string(i) + " has more than 2^22 restart intervals");
@@ -196,24 +170,12 @@ static int entropy_launch(int device, const void* scans_dev, const clipx_jpeg_de
 
   HIPCHK(hipSetDevice(device));
   hipStream_t st = (hipStream_t)stream;
-  std::lock_guard<std::mutex> lk(g_mu);
-  Ring& r = g_ring[device];
-  Slot* sl = &r.slot[r.next];
-  r.next = (r.next + 1) & 3;
-  if (sl->used) HIPCHK(hipEventSynchronize(sl->ev));  // the launch that last used this slot has finished
-  if (!sl->ev) HIPCHK(hipEventCreateWithFlags(&sl->ev, hipEventDisableTiming));
-  if (sl->tab_bytes < tab_bytes) {
-    if (sl->tab_dev) (void)hipFree(sl->tab_dev);
-    if (sl->tab_host) (void)hipHostFree(sl->tab_host);
-    sl->tab_dev = sl->tab_host = nullptr;
-    sl->tab_bytes = 0;
-    const size_t want = std::max(tab_bytes, (size_t)64 << 10);
-    HIPCHK(hipMalloc(&sl->tab_dev, want));
-    HIPCHK(hipHostMalloc(&sl->tab_host, want, hipHostMallocDefault));
-    sl->tab_bytes = want;
-  }
-  memcpy(sl->tab_host, tab.data(), tab_bytes);
-  HIPCHK(hipMemcpyAsync(sl->tab_dev, sl->tab_host, tab_bytes, hipMemcpyHostToDevice, st));
+  clipx::UploadRing& ring = table_ring();
+  std::lock_guard<std::mutex> lk(ring.mu);
+  clipx::UploadSlot* sl;
+  if (int r = ring.take(device, tab_bytes, &sl)) return r;
+  if (int r = ring.upload(sl, tab.data(), tab_bytes, st)) return r;
+  const HImg* tab_dev = static_cast<const HImg*>((void*)sl->dev);
   HIPCHK(hipMemsetAsync(status_dev, 0, (size_t)B * sizeof(int32_t), st));
   if (rounds_dev) HIPCHK(hipMemsetAsync(rounds_dev, 0, (size_t)B * sizeof(int32_t), st));
   for (int r0 = 0; r0 < B;) {
@@ -225,20 +187,18 @@ static int entropy_launch(int device, const void* scans_dev, const clipx_jpeg_de
     for (int b0 = r0; b0 < r1; b0 += step) {
       const int nb = std::min(step, r1 - b0);
       if (may_split[r0]) {
-        HIPCHK(clipx_jpeg_launch_split((unsigned)max_int, (unsigned)nb, st, (const unsigned char*)scans_dev, (const HImg*)sl->tab_dev + b0,
+        HIPCHK(clipx_jpeg_launch_split((unsigned)max_int, (unsigned)nb, st, (const unsigned char*)scans_dev, tab_dev + b0,
                                        (unsigned char*)coefs_dev, (int*)status_dev + b0, rounds_dev ? (int*)rounds_dev + b0 : (int*)nullptr,
                                        split_bytes, max_rounds));
       } else {
         hipLaunchKernelGGL(huff_kernel, dim3((unsigned)max_int, (unsigned)nb), dim3(64), 0, st, (const unsigned char*)scans_dev,
-                           (const HImg*)sl->tab_dev + b0, (unsigned char*)coefs_dev, (int*)status_dev + b0);
+                           tab_dev + b0, (unsigned char*)coefs_dev, (int*)status_dev + b0);
       }
       HIPCHK(hipGetLastError());
     }
     r0 = r1;
   }
-  HIPCHK(hipEventRecord(sl->ev, st));
-  sl->used = true;
-  return CLIPX_OK;
+  return ring.commit(sl, st);
 }
 
 extern "C" int clipx_jpeg_entropy_device(int device, const void* scans_dev, const clipx_jpeg_desc* descs, const int64_t* scan_offs, int B,
@@ -265,7 +225,7 @@ extern "C" int clipx_jpeg_entropy_split_host(const void* scan, size_t scan_bytes
   jpegx::Desc d;
   memcpy(&d, desc, sizeof(d));
   long long mcus = 0;
-  if (!descriptor_ok(*desc, &mcus) || S::intervals_of(d) > MAX_INTERVALS) return fail(CLIPX_E_ARG, "the jpeg descriptor is not one the scan preparation writes");
+  if (!jpegx::desc_consistent(d, &mcus) || d.restart < 0 || S::intervals_of(d) > MAX_INTERVALS) return fail(CLIPX_E_ARG, "the jpeg descriptor is not one the scan preparation writes");
   if (record_bytes < jpegx::record_bytes(d)) return fail(CLIPX_E_ARG, "the record buffer is smaller than the descriptor's record");
   if ((reinterpret_cast<uintptr_t>(scan) & 15) || scan_bytes < S::total_bytes(1, S::intervals_of(d), 0)) return fail(CLIPX_E_ARG, "the scan record is not 16-byte aligned or shorter than its fixed part");
   P::decode_record_host(static_cast<const uint8_t*>(scan), scan_bytes, d, (uint32_t)split->split_bytes,

@@ -22,8 +22,8 @@
 
 #include "../../include/clipx.h"
 #include "clipx_host.h"
+#include "clipx_upload_ring.h"
 #include "jpegx_entropy.h"
-
 
 static_assert(sizeof(clipx_jpeg_desc) == sizeof(jpegx::Desc), "clipx_jpeg_desc is jpegx::Desc");
 
@@ -218,22 +218,11 @@ __global__ __launch_bounds__(256) void rgb_kernel(const unsigned char* __restric
   }
 }
 
-// per device: a small ring of (image table, plane scratch), each slot guarded by the event of the launch that last used it
-struct Slot {
-  void* tab_dev = nullptr;
-  void* tab_host = nullptr;  // page-locked: the upload is a true asynchronous copy
-  size_t tab_bytes = 0;
-  void* planes = nullptr;
-  size_t plane_bytes = 0;
-  hipEvent_t ev = nullptr;
-  bool used = false;
-};
-struct Ring {
-  Slot slot[4];
-  int next = 0;
-};
-std::mutex g_mu;
-Ring g_ring[64];
+// image tables of at least 64 KiB, the plane scratch in the slot beside them; made once and never deleted (clipx_upload_ring.h)
+clipx::UploadRing& table_ring() {
+  static clipx::UploadRing* const ring = new clipx::UploadRing((size_t)64 << 10);
+  return *ring;
+}
 
 }  // namespace
 
@@ -268,22 +257,12 @@ extern "C" int clipx_jpeg_pixels_device(int device, const void* coefs_dev, const
   for (int i = 0; i < B; ++i) {
     const clipx_jpeg_desc& s = descs[i];
     JImg& d = tab[i];
-    const bool gray = s.ncomp == 1;
     // the descriptor is what the entropy stage wrote; anything else must not reach a kernel that indexes with it
-    bool ok = s.width >= 1 && s.height >= 1 && s.width <= 65535 && s.height <= 65535 && (gray || s.ncomp == 3) &&
-              ((s.hs == 1 && s.vs == 1) || (!gray && s.hs == 2 && (s.vs == 1 || s.vs == 2))) && s.coef_off >= 0 && (s.coef_off & 15) == 0 &&
-              offsets[i] >= 0;
-    if (ok) {
-      const int mx = (s.width + 8 * s.hs - 1) / (8 * s.hs), my = (s.height + 8 * s.vs - 1) / (8 * s.vs);
-      long long blocks = (long long)mx * s.hs * my * s.vs;
-      ok = s.bw[0] == mx * s.hs && s.bh[0] == my * s.vs;
-      for (int c = 1; c < s.ncomp; ++c) {
-        ok = ok && s.bw[c] == mx && s.bh[c] == my;
-        blocks += (long long)mx * my;
-      }
-      ok = ok && blocks == s.blocks;
-    }
-    if (!ok) return fail(CLIPX_E_ARG, "jpeg descriptor " + std::to_string(i) + " is not one the entropy stage writes");
+    jpegx::Desc jd;
+    memcpy(&jd, &s, sizeof(jd));
+    long long mcus = 0;
+    if (!jpegx::desc_consistent(jd, &mcus) || offsets[i] < 0)
+      return fail(CLIPX_E_ARG, "jpeg descriptor " + std::to_string(i) + " is not one the entropy stage writes");
     d.coef_off = s.coef_off;
     d.plane_off = plane_bytes;
     d.pix_off = offsets[i];
@@ -301,39 +280,20 @@ extern "C" int clipx_jpeg_pixels_device(int device, const void* coefs_dev, const
 
   HIPCHK(hipSetDevice(device));
   hipStream_t st = (hipStream_t)stream;
-  std::lock_guard<std::mutex> lk(g_mu);
-  Ring& r = g_ring[device];
-  Slot* sl = &r.slot[r.next];
-  r.next = (r.next + 1) & 3;
-  if (sl->used) HIPCHK(hipEventSynchronize(sl->ev));  // the launch that last used this slot has finished
-  if (!sl->ev) HIPCHK(hipEventCreateWithFlags(&sl->ev, hipEventDisableTiming));
-  if (sl->tab_bytes < tab_bytes) {
-    if (sl->tab_dev) (void)hipFree(sl->tab_dev);
-    if (sl->tab_host) (void)hipHostFree(sl->tab_host);
-    sl->tab_dev = sl->tab_host = nullptr;
-    sl->tab_bytes = 0;
-    const size_t want = std::max(tab_bytes, (size_t)64 << 10);
-    HIPCHK(hipMalloc(&sl->tab_dev, want));
-    HIPCHK(hipHostMalloc(&sl->tab_host, want, hipHostMallocDefault));
-    sl->tab_bytes = want;
-  }
-  if (sl->plane_bytes < (size_t)plane_bytes) {
-    if (sl->planes) (void)hipFree(sl->planes);
-    sl->planes = nullptr;
-    sl->plane_bytes = 0;
-    const size_t want = std::max((size_t)plane_bytes + (size_t)plane_bytes / 4, (size_t)8 << 20);
-    HIPCHK(hipMalloc(&sl->planes, want));
-    sl->plane_bytes = want;
-  }
-  memcpy(sl->tab_host, tab.data(), tab_bytes);
-  HIPCHK(hipMemcpyAsync(sl->tab_dev, sl->tab_host, tab_bytes, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(idct_kernel, dim3((max_blocks + 31) / 32, B), dim3(256), 0, st, (const unsigned char*)coefs_dev,
-                     (const JImg*)sl->tab_dev, (unsigned char*)sl->planes);
+  clipx::UploadRing& ring = table_ring();
+  std::lock_guard<std::mutex> lk(ring.mu);
+  clipx::UploadSlot* sl;
+  if (int r = ring.take(device, tab_bytes, &sl)) return r;
+  // the planes: at least 8 MiB, a growth takes a quarter more than was asked for
+  if (sl->scratch.bytes < (size_t)plane_bytes)
+    HIPCHK(sl->scratch.ensure(std::max((size_t)plane_bytes + (size_t)plane_bytes / 4, (size_t)8 << 20)));
+  if (int r = ring.upload(sl, tab.data(), tab_bytes, st)) return r;
+  const JImg* tab_dev = static_cast<const JImg*>((void*)sl->dev);
+  unsigned char* planes = static_cast<unsigned char*>((void*)sl->scratch);
+  hipLaunchKernelGGL(idct_kernel, dim3((max_blocks + 31) / 32, B), dim3(256), 0, st, (const unsigned char*)coefs_dev, tab_dev, planes);
   HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(rgb_kernel, dim3((unsigned)((max_items + 255) / 256), B), dim3(256), 0, st, (const unsigned char*)sl->planes,
-                     (const JImg*)sl->tab_dev, (unsigned char*)pixels_dev);
+  hipLaunchKernelGGL(rgb_kernel, dim3((unsigned)((max_items + 255) / 256), B), dim3(256), 0, st, (const unsigned char*)planes, tab_dev,
+                     (unsigned char*)pixels_dev);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(sl->ev, st));
-  sl->used = true;
-  return CLIPX_OK;
+  return ring.commit(sl, st);
 }

@@ -45,6 +45,23 @@ constexpr int MAX_ABS_DEQUANT = 2047;
 
 inline size_t record_bytes(const Desc& d) { return TABLE_BYTES + (size_t)d.blocks * 64 * sizeof(int16_t); }
 
+// Is `s` a descriptor the host stages write (probe / decode here, the scan preparation of jpegx_scan.h), with a coef_off a packer may
+// have set?  The device stages index memory with these fields: anything else must not reach them.  True: *mcus = the image's MCUs.
+// What only one stage reads (`restart`, the pixel offsets) is checked by that stage.
+inline bool desc_consistent(const Desc& s, long long* mcus) {
+  const bool gray = s.ncomp == 1;
+  if (!(s.width >= 1 && s.height >= 1 && s.width <= 65535 && s.height <= 65535 && (gray || s.ncomp == 3) &&
+        ((s.hs == 1 && s.vs == 1) || (!gray && s.hs == 2 && (s.vs == 1 || s.vs == 2))) && s.coef_off >= 0 && (s.coef_off & 15) == 0))
+    return false;
+  const int mx = (s.width + 8 * s.hs - 1) / (8 * s.hs), my = (s.height + 8 * s.vs - 1) / (8 * s.vs);
+  const long long n = (long long)mx * my;
+  bool ok = s.bw[0] == mx * s.hs && s.bh[0] == my * s.vs;
+  for (int c = 1; c < s.ncomp; ++c) ok = ok && s.bw[c] == mx && s.bh[c] == my;
+  if (!ok || n * (s.hs * s.vs + s.ncomp - 1) != s.blocks) return false;
+  *mcus = n;
+  return true;
+}
+
 namespace detail {
 
 // natural (row-major) index of zig-zag position k

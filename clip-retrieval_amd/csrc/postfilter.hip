@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/knnx.h"
+#include "hip_owners.h"
 
 extern "C" int knnx_set_error(int code, const char* msg);
 
@@ -102,13 +103,14 @@ struct knnx_mlp {
   int device = 0;
   int n_layers = 0;
   std::vector<int> dims;           // n_layers + 1
-  std::vector<float*> w, b;        // device
   std::vector<unsigned char> relu;
-  float* act[2] = {nullptr, nullptr};  // ping-pong activations [cap, max_dim]
   size_t cap_rows = 0;
   int max_dim = 0;
-  hipStream_t stream = nullptr;
   std::mutex mu;
+  // (destroyed bottom-up: the buffers go before the stream they were used on)
+  Stream stream;
+  std::vector<DevBuf<float>> w, b;  // per layer; b[l] empty: no bias
+  DevBuf<float> act[2];             // ping-pong activations [cap_rows, max_dim]
 };
 
 #define MLPCHK(expr)                                                                                                              \
@@ -120,32 +122,22 @@ struct knnx_mlp {
 extern "C" int knnx_mlp_destroy(knnx_mlp* m) {
   if (!m) return KNNX_OK;
   (void)hipSetDevice(m->device);
-  for (float* p : m->w) (void)hipFree(p);
-  for (float* p : m->b) (void)hipFree(p);
-  (void)hipFree(m->act[0]);
-  (void)hipFree(m->act[1]);
-  if (m->stream) (void)hipStreamDestroy(m->stream);
   delete m;
   return KNNX_OK;
 }
 
 static int mlp_create_impl(knnx_mlp* m, const float* const* weights, const float* const* biases) {
   MLPCHK(hipSetDevice(m->device));
-  MLPCHK(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
+  MLPCHK(m->stream.create());
+  m->w.resize(m->n_layers);
+  m->b.resize(m->n_layers);
   for (int l = 0; l < m->n_layers; ++l) {
-    const size_t nw = (size_t)m->dims[l + 1] * m->dims[l];
-    float* dw = nullptr;
-    MLPCHK(hipMalloc(&dw, nw * sizeof(float)));
-    m->w.push_back(dw);
-    MLPCHK(hipMemcpy(dw, weights[l], nw * sizeof(float), hipMemcpyHostToDevice));
-    float* db = nullptr;
-    if (biases && biases[l]) {
-      MLPCHK(hipMalloc(&db, (size_t)m->dims[l + 1] * sizeof(float)));
-      m->b.push_back(db);
-      MLPCHK(hipMemcpy(db, biases[l], (size_t)m->dims[l + 1] * sizeof(float), hipMemcpyHostToDevice));
-    } else {
-      m->b.push_back(nullptr);
-    }
+    const size_t nw = (size_t)m->dims[l + 1] * m->dims[l], nb = (size_t)m->dims[l + 1];
+    MLPCHK(m->w[l].alloc(nw));
+    MLPCHK(hipMemcpy(m->w[l], weights[l], nw * sizeof(float), hipMemcpyHostToDevice));
+    if (!(biases && biases[l])) continue;
+    MLPCHK(m->b[l].alloc(nb));
+    MLPCHK(hipMemcpy(m->b[l], biases[l], nb * sizeof(float), hipMemcpyHostToDevice));
   }
   return KNNX_OK;
 }
@@ -176,13 +168,10 @@ extern "C" int knnx_mlp_create(int device, int n_layers, const int32_t* dims, co
 // the ping-pong activations hold n rows; caller holds m->mu and has set the device
 static int mlp_ensure_rows(knnx_mlp* m, int n) {
   if ((size_t)n <= m->cap_rows) return KNNX_OK;
-  (void)hipFree(m->act[0]);
-  (void)hipFree(m->act[1]);
-  m->act[0] = m->act[1] = nullptr;
   m->cap_rows = 0;
   const size_t rows = std::max<size_t>((size_t)n, 4096);
-  MLPCHK(hipMalloc(&m->act[0], rows * m->max_dim * sizeof(float)));
-  MLPCHK(hipMalloc(&m->act[1], rows * m->max_dim * sizeof(float)));
+  MLPCHK(m->act[0].alloc(rows * m->max_dim));
+  MLPCHK(m->act[1].alloc(rows * m->max_dim));
   m->cap_rows = rows;
   return KNNX_OK;
 }
@@ -194,8 +183,8 @@ static int mlp_layers(knnx_mlp* m, const float* x, int64_t ldx, int n, float* y_
   int cur = 1;  // layer 0 writes act[1] (knnx_mlp_forward stages its input in act[0])
   for (int l = 0; l < m->n_layers; ++l) {
     const int K = m->dims[l], N = m->dims[l + 1];
-    float* out = (l + 1 == m->n_layers && y_or_null) ? y_or_null : m->act[cur];
-    hipLaunchKernelGGL(linear_f32_kernel, dim3((N + TN - 1) / TN, (n + TM - 1) / TM), dim3(256), 0, st, in, m->w[l], m->b[l], out, n, N, K,
+    float* out = (l + 1 == m->n_layers && y_or_null) ? y_or_null : m->act[cur].p;
+    hipLaunchKernelGGL(linear_f32_kernel, dim3((N + TN - 1) / TN, (n + TM - 1) / TM), dim3(256), 0, st, in, m->w[l].p, m->b[l].p, out, n, N, K,
                        (int)m->relu[l], l == 0 ? ldx : (int64_t)K);
     MLPCHK(hipGetLastError());
     in = out;
@@ -227,7 +216,7 @@ extern "C" int knnx_mlp_forward_device(knnx_mlp* m, const float* x_dev, int64_t 
   if (n == 0) return KNNX_OK;
   std::lock_guard<std::mutex> lk(m->mu);
   MLPCHK(hipSetDevice(m->device));
-  hipStream_t st = stream ? (hipStream_t)stream : m->stream;
+  hipStream_t st = stream ? (hipStream_t)stream : m->stream.s;
   int r = mlp_ensure_rows(m, n);
   if (r) return r;
   if ((r = mlp_layers(m, x_dev, ld, n, y_dev, st, nullptr))) return r;
@@ -243,7 +232,7 @@ __attribute__((visibility("hidden"))) void knnx_mlp_shape(const knnx_mlp* m, int
   *d_out = m->dims[m->n_layers];
   *n_layers = m->n_layers;
   *has_bias = 0;
-  for (float* b : m->b) *has_bias |= b ? 1 : 0;
+  for (const DevBuf<float>& b : m->b) *has_bias |= b.p ? 1 : 0;
 }
 
 

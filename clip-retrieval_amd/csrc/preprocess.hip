@@ -28,6 +28,7 @@
 
 #include "../../include/clipx.h"
 #include "clipx_host.h"
+#include "clipx_upload_ring.h"
 
 extern "C" const char* clipx_last_error(void);
 
@@ -266,20 +267,11 @@ std::shared_ptr<const AxisCoeffs> axis_coeffs_cached(int in_size, int out_size, 
   return c;
 }
 
-// device-side coefficient buffers: a small ring per device, each slot guarded by the event of the launch that last read it
-struct CoefSlot {
-  void* dev = nullptr;
-  void* host = nullptr;  // page-locked staging of the same size: the upload is a true asynchronous copy
-  size_t bytes = 0;
-  hipEvent_t ev = nullptr;
-  bool used = false;
-};
-struct CoefRing {
-  CoefSlot slot[4];
-  int next = 0;
-};
-std::mutex g_mu;
-CoefRing g_ring[64];
+// device-side coefficient buffers, at least 1 MiB each; made once and never deleted (clipx_upload_ring.h)
+clipx::UploadRing& coef_ring() {
+  static clipx::UploadRing* const ring = new clipx::UploadRing((size_t)1 << 20);
+  return *ring;
+}
 
 }  // namespace
 
@@ -364,33 +356,16 @@ extern "C" int clipx_resize_crop_u8_device(int device, const void* src_dev, cons
 
   HIPCHK(hipSetDevice(device));
   hipStream_t st = (hipStream_t)stream;
-  CoefSlot* sl;
-  {
-    std::lock_guard<std::mutex> lk(g_mu);
-    CoefRing& r = g_ring[device];
-    sl = &r.slot[r.next];
-    r.next = (r.next + 1) & 3;
-    if (sl->used) HIPCHK(hipEventSynchronize(sl->ev));  // the launch that last read this slot has finished
-    if (!sl->ev) HIPCHK(hipEventCreateWithFlags(&sl->ev, hipEventDisableTiming));
-    if (sl->bytes < bytes) {
-      if (sl->dev) (void)hipFree(sl->dev);
-      if (sl->host) (void)hipHostFree(sl->host);
-      sl->dev = sl->host = nullptr;
-      sl->bytes = 0;
-      const size_t want = std::max(bytes, (size_t)1 << 20);
-      HIPCHK(hipMalloc(&sl->dev, want));
-      HIPCHK(hipHostMalloc(&sl->host, want, hipHostMallocDefault));
-      sl->bytes = want;
-    }
-    memcpy(sl->host, cb.data(), bytes);
-    HIPCHK(hipMemcpyAsync(sl->dev, sl->host, bytes, hipMemcpyHostToDevice, st));
-    const size_t smem = max_lds;  // what the largest band of this batch needs (small for mild down-scales: more workgroups per CU)
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(resize_crop_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    hipLaunchKernelGGL(resize_crop_kernel, dim3(max_bands, B), dim3(256), smem, st, (const unsigned char*)src_dev, src_bytes,
-                       (const int*)sl->dev, (const ImgDesc*)sl->dev, S, (unsigned char*)out_dev);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(sl->ev, st));
-    sl->used = true;
-  }
-  return CLIPX_OK;
+  clipx::UploadRing& ring = coef_ring();
+  std::lock_guard<std::mutex> lk(ring.mu);
+  clipx::UploadSlot* sl;
+  if (int r = ring.take(device, bytes, &sl)) return r;
+  if (int r = ring.upload(sl, cb.data(), bytes, st)) return r;
+  const void* cb_dev = sl->dev;
+  const size_t smem = max_lds;  // what the largest band of this batch needs (small for mild down-scales: more workgroups per CU)
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(resize_crop_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+  hipLaunchKernelGGL(resize_crop_kernel, dim3(max_bands, B), dim3(256), smem, st, (const unsigned char*)src_dev, src_bytes,
+                     (const int*)cb_dev, (const ImgDesc*)cb_dev, S, (unsigned char*)out_dev);
+  HIPCHK(hipGetLastError());
+  return ring.commit(sl, st);
 }

@@ -420,6 +420,31 @@ def test_mlp_forward_device_equals_mlp_forward_bit_for_bit(lib, width):
         head.close()
 
 
+def test_mlp_handles_come_and_go_and_the_activations_regrow():
+    """Twenty heads created and destroyed in a row; then on one handle knnx_mlp_forward at n = 1, at n = 5 000 -- past the 4 096 rows
+    the activation buffers start with, so both are replaced -- and at n = 1 again.  Unit rows through the small stack: each result
+    within 1e-3 of the float64 restatement (the margin every expectation of this file keeps, 100 x the fp32 chain's error bound), the
+    two single rows the same bits."""
+    from clip_retrieval_amd.service import Mi355xSafetyHead
+
+    d = 256
+    sd = _small_stack(d, 91)
+    for _ in range(20):
+        Mi355xSafetyHead(sd).close()
+    x = _unit64(np.random.default_rng(92).standard_normal((5000, d))).astype(np.float32)
+    want = _stack64(sd, x)
+    head = Mi355xSafetyHead(sd)
+    try:
+        first, grown, again = head.predict(x[:1]), head.predict(x), head.predict(x[:1])
+    finally:
+        head.close()
+    for got, n in ((first, 1), (grown, 5000), (again, 1)):
+        assert got.shape == (n, 1)
+        err = np.abs(got[:, 0].astype(np.float64) - want[:n]).max()
+        assert err <= 1e-3, f"n = {n}: {err} from the float64 restatement"
+    assert np.array_equal(first.view(np.uint32), again.view(np.uint32))
+
+
 # ---- refusals and concurrency -----------------------------------------------------------------------------------------------------
 def test_refusals_launch_nothing(edge_index):
     """k = 8193, a head of the wrong width, no filter, and (where the machine has a second GPU) a head on another device: each is refused,

@@ -1,6 +1,7 @@
 """The pixel stage of the JPEG decoder on the GPU (csrc/jpeg_kernels.hip, clipx_jpeg_pixels_device) against Pillow: every
 byte of every file of the accepted class, not a byte outside the images, the hand-over to the GPU resize, and the reader end to end
 with the switch on and off."""
+import functools
 import io
 import os
 import tarfile
@@ -166,3 +167,44 @@ def test_two_streams_decode_at_once(lib):
         pending.append((items, _decode_batch(lib, items, gap=7, stream=streams[k % 2])))
     for items, collect in pending:
         _assert_equal_pillow(items, collect())
+
+
+@functools.lru_cache(maxsize=None)
+def _ring_calls():
+    """The calls of the two tests below, built once: B = 1 and B = 768 images of 8 x 8 in turn, nine calls, so that the ring of four
+    table slots wraps twice and a slot that held the 64 KiB floor meets a table of 768 x 88 bytes = 66 KiB and grows; then one
+    2048 x 2048 4:4:4 image, whose planes (256 x 256 blocks x 3 components x 64 bytes = 12.6 MB) pass the 8 MiB floor of the plane
+    scratch; then the B = 1 call again.  -> [(items, Pillow's RGB of each)]"""
+    from PIL import Image
+
+    def want(items):
+        return [np.asarray(Image.open(io.BytesIO(d)).convert("RGB")) for _, d in items]
+
+    tiny = [(f"8x8-{i}", J.encode(J.content(J.CONTENTS[i % 3], 8, 8, 300 + i), J.SAMPLINGS[i % 4], J.QUALITIES[(i // 4) % 4], False, 0))
+            for i in range(768)]
+    one, many = (tiny[:1], want(tiny[:1])), (tiny, want(tiny))
+    big = [("2048x2048-s0", J.encode(J.content("gradient", 2048, 2048, 1), 0, 90, False, 0))]
+    return [one if k % 2 == 0 else many for k in range(9)] + [(big, want(big)), one]
+
+
+def _run_ring_calls(lib, streams):
+    calls = _ring_calls()
+    assert [len(items) for items, _ in calls] == [1, 768, 1, 768, 1, 768, 1, 768, 1, 1, 1]
+    pending = [_decode_batch(lib, items, gap=3, stream=streams[k % len(streams)]) for k, (items, _) in enumerate(calls)]
+    for k, ((items, want), collect) in enumerate(zip(calls, pending)):
+        got = collect()  # (the sentinel bytes around the images: checked inside)
+        assert len(got) == len(want)
+        for (name, _), w, g in zip(items, want, got):
+            assert g.shape == w.shape and np.array_equal(g, w), f"call {k}, {name}: differs from Pillow's decode"
+
+
+def test_table_and_plane_regrowth_across_ring_wraps(lib):
+    """Eleven calls in a row on one stream (see _ring_calls): every image equals Pillow's decode, nothing outside them is written."""
+    _run_ring_calls(lib, [None])
+
+
+def test_table_and_plane_regrowth_on_two_streams(lib):
+    """The same calls dealt to two streams in turn, all launched before the first is collected."""
+    import torch
+
+    _run_ring_calls(lib, [torch.cuda.Stream(), torch.cuda.Stream()])

@@ -19,8 +19,9 @@ SENTINEL = 0x5A
 STATUS_SENTINEL = 0x5A5A5A5A
 
 
-def _entropy_batch(lib, files, gap=48, stream=None):
-    """files: [jpeg bytes] that pass the host preparation -> ONE clipx_jpeg_entropy_device call.  The output records lie `gap` bytes
+def _entropy_batch(lib, files, gap=48, stream=None, split_bytes=0):
+    """files: [jpeg bytes] that pass the host preparation -> ONE clipx_jpeg_entropy_device call (split_bytes > 0: one
+    clipx_jpeg_entropy_split_device call with that cut).  The output records lie `gap` bytes
     (a multiple of 16) apart in a buffer pre-filled with a sentinel, the status array has sentinel words behind it; collect() returns
     (statuses, [record bytes], descs, device coefficient buffer) after checking that every byte outside them still holds it."""
     import torch
@@ -41,7 +42,7 @@ def _entropy_batch(lib, files, gap=48, stream=None):
         stream.wait_stream(torch.cuda.current_stream())  # (the sentinel fills ran on the current stream)
     with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
         dev = scans.cuda() if n else torch.zeros(16, dtype=torch.uint8, device="cuda")
-        jpeg.entropy_device(0, dev, descs, offs, coefs, status, stream.cuda_stream if stream is not None else None, lib)
+        jpeg.entropy_device(0, dev, descs, offs, coefs, status, stream.cuda_stream if stream is not None else None, lib, split_bytes=split_bytes)
 
     def collect():
         (stream or torch.cuda.current_stream()).synchronize()
@@ -173,6 +174,21 @@ def test_two_streams_decode_at_once(lib):
         pending.append((items, streams[k % 2], _entropy_batch(lib, [d for _, d in items], gap=80, stream=streams[k % 2])))
     for items, stream, collect in pending:
         _assert_equal_pillow(items, _pixels_after(lib, items, collect, stream))
+
+
+@pytest.mark.parametrize("split_bytes", [0, 128])
+def test_table_regrowth_across_ring_wraps(lib, split_bytes):
+    """B = 1 and B = 768 images of 8 x 8 in turn, nine calls, through clipx_jpeg_entropy_device and through the split entry at 128
+    bytes: the ring of four table slots wraps twice, and a slot that held the 64 KiB floor meets a table of 768 x 88 bytes = 66 KiB and
+    grows.  All launched before the first is collected; every status 0, every record the host stage's, no byte outside them written
+    (checked in collect())."""
+    files = [J.encode(J.content(J.CONTENTS[i % 3], 8, 8, 300 + i), J.SAMPLINGS[i % 4], J.QUALITIES[(i // 4) % 4], False, 0) for i in range(768)]
+    calls = [files[:1] if k % 2 == 0 else files for k in range(9)]
+    pending = [_entropy_batch(lib, batch, gap=16, split_bytes=split_bytes) for batch in calls]
+    for k, (batch, collect) in enumerate(zip(calls, pending)):
+        statuses, records, _, _ = collect()
+        assert statuses.shape == (len(batch),) and (statuses == 0).all(), f"call {k}: statuses {np.unique(statuses)}"
+        _assert_records_equal_host(lib, batch, statuses, records, [f"call {k}, image {i}" for i in range(len(batch))])
 
 
 @pytest.fixture(scope="module")

@@ -83,6 +83,22 @@ def test_batches_and_repeat_calls_are_independent(lib):
     assert np.array_equal(_resize_crop(lib, imgs[::-1], 224)[::-1], whole)
 
 
+def test_a_coefficient_block_above_the_slot_floor_then_a_small_one(lib):
+    """One call whose coefficient block is twice the 1 MiB floor of a slot, so the slot grows, then a small call, which takes the
+    next slot at its floor.  The arithmetic (csrc/preprocess.hip, axis_coeffs): an axis of `in` > 448 source pixels resampled to 224
+    has scale > 2, support > 4, so ksize = 2 ceil(support) + 1 >= 11 taps, and its tables are 224 x 2 bounds + 224 x ksize weights
+    >= 2 912 int32 = 11 648 bytes.  Image i is (452 + 2 i) x (453 + 2 i): the heights are even, the widths odd, so no two axes of
+    the batch share a table and each image brings two: 92 images x 23 296 bytes = 2 143 232 >= 2 x 2^20 = 2 097 152 bytes, the 64-byte
+    descriptors not counted.  Every crop equals the numpy restatement of Pillow."""
+    from oracle.resample_oracle import clip_resize_crop_u8
+
+    imgs = [_synthetic(452 + 2 * i, 453 + 2 * i, i) for i in range(92)]
+    for im, g in zip(imgs, _resize_crop(lib, imgs, 224)):
+        assert np.array_equal(g, clip_resize_crop_u8(im, 224)), im.shape
+    small = _synthetic(97, 131, 5)
+    assert np.array_equal(_resize_crop(lib, [small], 224)[0], clip_resize_crop_u8(small, 224))
+
+
 def test_unaligned_source_and_repeated_sizes(lib):
     """A packed source that does not start on a 16-byte boundary takes the byte-wise staging path; images of one size share
     one copy of the weight tables (host cache + per-call placement).  Same bytes as Pillow either way."""

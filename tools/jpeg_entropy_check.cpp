@@ -2,6 +2,8 @@
 // -fsanitize=address,undefined (tests/test_jpeg_cpu.py does).  Each file is probed, then decoded twice: into a heap buffer of
 // EXACTLY the probed size (a write past it is the sanitizer's to report) and into a buffer with guard bytes behind the probed size
 // (checked here).  A file is "taken" or "deferred", never anything else; a deferral must leave descriptor and record untouched.
+// Every descriptor a file is taken with passes jpegx::desc_consistent -- the bounds check in front of the device stages -- with the
+// right MCU count, and fails it once a field the kernels index with is off by one.
 // Prints, per first letter of the file names, "prefix <letter> <taken>/<files>", then "jpeg entropy ok".
 #include <dirent.h>
 #include <stdio.h>
@@ -33,6 +35,35 @@ static std::vector<uint8_t> slurp(const std::string& path) {
   while ((n = fread(buf, 1, sizeof(buf), f)) > 0) out.insert(out.end(), buf, buf + n);
   fclose(f);
   return out;
+}
+
+// `d` as probe() / decode() wrote it: consistent, and no longer so with one field bumped
+static void check_descriptor(const char* name, const char* who, const jpegx::Desc& d) {
+  long long mcus = -1;
+  const bool ok = jpegx::desc_consistent(d, &mcus);
+  // the MCU grid from the image size alone, not from the block counts the check compares it with
+  const long long want = (long long)((d.width + 8 * d.hs - 1) / (8 * d.hs)) * ((d.height + 8 * d.vs - 1) / (8 * d.vs));
+  CHECK(ok && mcus == want, "%s: %s's descriptor is not consistent, or %lld MCUs for %lld", name, who, mcus, want);
+  long long unused;
+  jpegx::Desc b = d;
+  // width + 1 is another image of the same geometry unless it opens a new MCU column: the check must tell exactly that ...
+  b.width += 1;
+  CHECK(jpegx::desc_consistent(b, &unused) == (d.width % (8 * d.hs) != 0), "%s: %s's width + 1 judged wrongly", name, who);
+  // ... and the first width of the next MCU column never passes
+  b.width = d.bw[0] * 8 + 1;
+  CHECK(!jpegx::desc_consistent(b, &unused), "%s: %s's width in the next MCU column was accepted", name, who);
+  b = d, b.hs += 1;
+  CHECK(!jpegx::desc_consistent(b, &unused), "%s: %s's hs + 1 was accepted", name, who);
+  b = d, b.bw[0] += 1;
+  CHECK(!jpegx::desc_consistent(b, &unused), "%s: %s's bw[0] + 1 was accepted", name, who);
+  if (d.ncomp == 3) {  // (a grayscale image has no second plane: no stage reads bh[1] of it)
+    b = d, b.bh[1] += 1;
+    CHECK(!jpegx::desc_consistent(b, &unused), "%s: %s's bh[1] + 1 was accepted", name, who);
+  }
+  b = d, b.blocks += 1;
+  CHECK(!jpegx::desc_consistent(b, &unused), "%s: %s's blocks + 1 was accepted", name, who);
+  b = d, b.coef_off += 1;
+  CHECK(!jpegx::desc_consistent(b, &unused), "%s: %s's coef_off + 1 was accepted", name, who);
 }
 
 int main(int argc, char** argv) {
@@ -68,6 +99,7 @@ int main(int argc, char** argv) {
     if (p == jpegx::TAKEN)
       CHECK(probed.blocks > 0 && probed.width >= 1 && probed.width <= MAX_SIDE && probed.height >= 1 && probed.height <= MAX_SIDE,
             "%s: descriptor out of range", name.c_str());
+    if (p == jpegx::TAKEN) check_descriptor(name.c_str(), "probe", probed);
     // 1: exactly the probed size
     uint8_t* exact = static_cast<uint8_t*>(malloc(size));
     memset(exact, 0xA5, size);
@@ -82,6 +114,7 @@ int main(int argc, char** argv) {
     } else {
       CHECK(jpegx::record_bytes(d) == size && d.blocks == probed.blocks && d.width == probed.width && d.height == probed.height,
             "%s: decode and probe disagree", name.c_str());
+      check_descriptor(name.c_str(), "decode", d);
     }
     // 2: guard bytes behind the probed size; a buffer one byte short must be refused
     uint8_t* guarded = static_cast<uint8_t*>(malloc(size + GUARD));

@@ -14,6 +14,16 @@ constexpr int KNN_WG = KNN_WAVES * 64;
 constexpr float KNN_LO_SCALE = 2048.f;
 constexpr float KNN_LO_INV = 1.f / 2048.f;
 constexpr int KNN_LDS_BYTES = 160 * 1024;
+constexpr int KNN_D_MAX = 1280;  // widest index (ViT-bigG/14 embeddings)
+// The stationary operand of a 32-query scan is d / 16 k-steps of a hi and a lo fragment, 1 KiB each.  Up to d = 1024 both live in
+// the LDS (d * 128 B).  At d = 1280 that is the whole LDS, so only the hi fragments of all 80 k-steps and the lo fragments of the first
+// KNN_KS_LO_LDS_1280 stay there; every wave keeps the lo fragments of the other k-steps in registers (4 VGPRs per k-step) for the
+// whole kernel.  58: 138 KiB of fragments, queues of 86 entries (scan_cap(1280, 64) >= 80), 88 stationary VGPRs, no scratch (at 56
+// the list scan spills one fragment inside its tile loop; above 59 the queues fall below the 80 entries the k <= 64 path needs).
+// This is the ONE statement of the layout: carve, scan_smem_bytes, scan_cap, wide_cap and the kernel all read it.
+constexpr int KNN_KS_LO_LDS_1280 = 58;
+__host__ __device__ constexpr int scan_lo_lds_ksteps(int d) { return d <= 1024 ? d / 16 : KNN_KS_LO_LDS_1280; }
+__host__ __device__ constexpr size_t scan_frag_lds_bytes(int d) { return (size_t)(d / 16 + scan_lo_lds_ksteps(d)) * 1024; }
 
 struct ScanArgs {
   const _Float16* X;

@@ -89,8 +89,13 @@ __global__ void knn_prep_queries_kernel(const float* __restrict__ q, int nq, int
 // by at most |q - fp16(q)| * |x|.  The caller asks for the best kw > k rows by that approximate score, re-scores them
 // exactly (knn_rescore_kernel) and PROVES the top-k exact from the gap between the kw-th approximate and the k-th exact
 // score, falling back to the QB = 1 scan for a query whose gap is too small.  `gate`: run only if *gate != 0.
+// NCH = 10 (d = 1280): the hi / lo fragment image would be the whole LDS, so the lo fragments of the last KS_REG k-steps are held by
+// every wave in registers (loaded once from qfrag; they are the same for every row tile) and the LDS keeps slots (2 s, 2 s + 1) = (hi,
+// lo) of k-step s < KS_LO followed by one hi slot per k-step s >= KS_LO (slot KS_LO + s).  The MFMA order of a k-step (hi, then lo, k
+// ascending, one accumulator pair) is that of the other widths, so a score has the same bits.  The full LDS admits one workgroup
+// per CU, which the launch bounds of this instantiation say.
 template <int NCH, int MODE, bool NT, bool IVF, int QB>  // NCH = d/128 (even); MODE 0 = top-k, 1 = range; NT = nontemporal loads
-__global__ __launch_bounds__(KNN_WG, 2) void knn_scan_kernel(
+__global__ __launch_bounds__(KNN_WG, NCH > 8 ? 1 : 2) void knn_scan_kernel(
     const _Float16* __restrict__ X, int64_t N, const _Float16* __restrict__ qfrag, int nq, int k, int cap,
     int* __restrict__ thr_g, float* __restrict__ part_s, uint32_t* __restrict__ part_i, int* __restrict__ part_n,
     float range_thr, unsigned* __restrict__ range_cnt, unsigned range_cap, float* __restrict__ range_s,
@@ -99,7 +104,10 @@ __global__ __launch_bounds__(KNN_WG, 2) void knn_scan_kernel(
   constexpr int D = NCH * 128;
   constexpr int KS = D / 16;
   constexpr int NQ = 32 * QB;  // queries (= queues, thresholds) of this scan
+  constexpr int KS_LO = scan_lo_lds_ksteps(D);  // k-steps whose lo fragment sits in the LDS
+  constexpr int KS_REG = KS - KS_LO;            // ... and in this wave's registers
   static_assert(QB == 1 || (MODE == 0 && !IVF), "the wide scan exists for the flat top-k mode only");
+  static_assert(KS_REG == 0 || QB == 1, "the register-held lo fragments belong to the exact 32-query scan");
   if (gate && *gate == 0) return;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const ScanSmem sm = carve(smem_raw, D, cap, NQ);
@@ -148,7 +156,14 @@ __global__ __launch_bounds__(KNN_WG, 2) void knn_scan_kernel(
   {
     const uint4* src = reinterpret_cast<const uint4*>(qfrag);
     uint4* dst = reinterpret_cast<uint4*>(sm.qf);
-    for (int i = tid; i < KS * 2 * 64; i += KNN_WG) dst[i] = src[i];
+    if constexpr (KS_REG == 0) {
+      for (int i = tid; i < KS * 2 * 64; i += KNN_WG) dst[i] = src[i];
+    } else {
+      for (int i = tid; i < (KS + KS_LO) * 64; i += KNN_WG) {
+        const int sl = i >> 6;  // LDS slot -> slot of the image in HBM: the hi slots of the k-steps >= KS_LO lie 2 apart there
+        dst[i] = src[(sl < 2 * KS_LO ? sl : 2 * (sl - KS_LO)) * 64 + (i & 63)];
+      }
+    }
     if (tid < NQ) { sm.cnt[tid] = 0; sm.thr[tid] = enc_f(-INFINITY); }
     if (tid < 4) sm.flag[tid] = 0;
   }
@@ -158,6 +173,15 @@ __global__ __launch_bounds__(KNN_WG, 2) void knn_scan_kernel(
   // the register-stationary scan (knn_rq_kernels.hip) takes its per-query thresholds
   const int64_t ntile = IVF ? (int64_t)*nwork_ptr : (((N + 31) >> 5) + tstride - 1) / tstride;  // IVF: number of work items
   const int64_t ngroup = (ntile + KNN_WAVES - 1) / KNN_WAVES;
+
+  half8 blo[KS_REG > 0 ? KS_REG : 1];  // lo fragments of the k-steps KS_LO .. KS - 1
+  if constexpr (KS_REG > 0) {
+    const half8* src = reinterpret_cast<const half8*>(qfrag);
+#pragma unroll
+    for (int j = 0; j < KS_REG; ++j) blo[j] = src[((KS_LO + j) * 2 + 1) * 64 + lane];
+#pragma unroll
+    for (int j = 0; j < KS_REG; ++j) asm volatile("" : "+v"(blo[j]));  // loaded here, once: never re-fetched inside the tile loop
+  }
 
   half8 a0[8], a1[8];
   auto item_of = [&](int64_t grp) -> uint4 {  // IVF work item of this wave in group `grp` (wave-uniform address)
@@ -211,8 +235,17 @@ __global__ __launch_bounds__(KNN_WG, 2) void knn_scan_kernel(
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const int s = c * 8 + j;
-        const half8 bh = sm.qf[(s * 2 + 0) * 64 + lane];
-        const half8 bl = sm.qf[(s * 2 + 1) * 64 + lane];
+        half8 bh, bl;
+        if constexpr (KS_REG == 0) {
+          bh = sm.qf[(s * 2 + 0) * 64 + lane];
+          bl = sm.qf[(s * 2 + 1) * 64 + lane];
+        } else if (s < KS_LO) {
+          bh = sm.qf[(s * 2 + 0) * 64 + lane];
+          bl = sm.qf[(s * 2 + 1) * 64 + lane];
+        } else {
+          bh = sm.qf[(KS_LO + s) * 64 + lane];
+          bl = blo[s >= KS_LO ? s - KS_LO : 0];
+        }
         acc_h = __builtin_amdgcn_mfma_f32_32x32x16_f16(cur[j], bh, acc_h, 0, 0, 0);
         acc_l = __builtin_amdgcn_mfma_f32_32x32x16_f16(cur[j], bl, acc_l, 0, 0, 0);
       }
@@ -1182,10 +1215,11 @@ __global__ __launch_bounds__(256) void kmeans_update_kernel(const _Float16* __re
   const int l = blockIdx.x;
   const int64_t a = off[l], b = off[l + 1];
   if (b <= a) return;  // empty list: the caller re-seeds it
-  float m[4] = {0.f, 0.f, 0.f, 0.f};  // d <= 1024: up to 4 columns per thread
+  constexpr int MAXC = KNN_D_MAX / 256;  // columns per thread
+  float m[MAXC] = {};
   float ss = 0.f;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
+  for (int e = 0; e < MAXC; ++e) {
     const int c = threadIdx.x + 256 * e;
     if (c < d) {
       float s = 0.f;
@@ -1200,14 +1234,14 @@ __global__ __launch_bounds__(256) void kmeans_update_kernel(const _Float16* __re
   const float nrm = sqrtf(red[0] + red[1] + red[2] + red[3]);
   const float inv = nrm > 0.f ? 1.f / nrm : 0.f;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
+  for (int e = 0; e < MAXC; ++e) {
     const int c = threadIdx.x + 256 * e;
     if (c < d) cent[(size_t)l * d + c] = (_Float16)(m[e] * inv);
   }
 }
 hipError_t launch_kmeans_update(const _Float16* X, int d, const int64_t* order, const int64_t* off, int nlist, _Float16* cent,
                                 hipStream_t st) {
-  if (d > 1024) return hipErrorInvalidValue;
+  if (d > KNN_D_MAX) return hipErrorInvalidValue;
   hipLaunchKernelGGL(kmeans_update_kernel, dim3(nlist), dim3(256), 0, st, X, d, order, off, cent);
   return hipGetLastError();
 }
@@ -1340,7 +1374,7 @@ hipError_t launch_gather_inv(const _Float16* X, int d, int64_t id_lo, int64_t n_
 // ---------------------------------------------------------------------------------------------
 // host-side launchers (declared in knn_kernels.h)
 // ---------------------------------------------------------------------------------------------
-size_t scan_smem_bytes(int d, int cap, int nqs) { return (size_t)d * 128 + (size_t)nqs * cap * 8 + nqs * 8 + 16; }
+size_t scan_smem_bytes(int d, int cap, int nqs) { return scan_frag_lds_bytes(d) + (size_t)nqs * cap * 8 + nqs * 8 + 16; }
 
 hipError_t launch_prep(const float* q_dev, int nq, int d, _Float16* qfrag, int* thr_g, unsigned* range_cnt, int wide,
                        const unsigned* gate, hipStream_t st) {
@@ -1378,6 +1412,7 @@ hipError_t launch_select(const unsigned* need, int q0, int nq, int k, const floa
 template <int MODE, bool NT, bool IVF = false, int QB = 1>
 static hipError_t launch_scan_mode(const ScanArgs& a, hipStream_t st) {
   const size_t smem = scan_smem_bytes(a.d, a.cap, 32 * QB);
+  if (smem > (size_t)KNN_LDS_BYTES) return hipErrorInvalidValue;
 #define KNN_LAUNCH(NCH)                                                                                         \
   {                                                                                                             \
     auto kern = knn_scan_kernel<NCH, MODE, NT, IVF, QB>;                                                                   \
@@ -1395,6 +1430,9 @@ static hipError_t launch_scan_mode(const ScanArgs& a, hipStream_t st) {
     case 512: KNN_LAUNCH(4)
     case 768: KNN_LAUNCH(6)
     case 1024: KNN_LAUNCH(8)
+    case 1280:  // (the 32-query scans only: wide_cap(1280) < 0)
+      if constexpr (QB == 1) KNN_LAUNCH(10)
+      return hipErrorInvalidValue;
     default: return hipErrorInvalidValue;
   }
 #undef KNN_LAUNCH
@@ -1494,6 +1532,7 @@ hipError_t launch_range_sort(const float* rs, const uint32_t* ri, const unsigned
 }
 hipError_t launch_synth(_Float16* X, int64_t row_begin, int64_t n, int d, uint64_t seed, hipStream_t st, int dominant) {
   if (n == 0) return hipSuccess;
+  if (d > 1024) return hipErrorInvalidValue;  // (knn_synth_kernel: 16 columns per lane)
   const int64_t chunk = 1 << 22;  // rows per launch (grid.x limit)
   for (int64_t o = 0; o < n; o += chunk) {
     const int64_t m = (n - o) < chunk ? (n - o) : chunk;

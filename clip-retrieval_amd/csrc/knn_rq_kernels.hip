@@ -154,7 +154,11 @@ __device__ __forceinline__ void rq_issue_all(const RqTile& r) {
 // waits lgkmcnt(0) right behind each read, which puts the LDS latency of every k-step in front of its MFMAs).
 template <int OFF>
 __device__ __forceinline__ void rq_dsread(i32x4& dst, unsigned addr) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
+  if constexpr (OFF < 65536) {
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
+  } else {  // (the 80 KiB tiles of d = 1280: the instruction's offset field holds 16 bits)
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr + 65536u), "n"(OFF - 65536));
+  }
 }
 template <int N>
 __device__ __forceinline__ void rq_wait_lgkm() {
@@ -1219,6 +1223,8 @@ hipError_t launch_assign(const _Float16* C, int64_t nlist, int d, const _Float16
     case 512: return launch_assign_cfg<32, 8, 3>(C, nlist, P, n, out, st);
     case 768: return launch_assign_cfg<48, 8, 3>(C, nlist, P, n, out, st);
     case 1024: return launch_assign_cfg<64, 4, 2>(C, nlist, P, n, out, st);
+    // d = 1280: two ring slots of 80 KiB are the whole LDS; a wave's 32 stationary points take 320 of its 512 registers
+    case 1280: return launch_assign_cfg<80, 4, 2>(C, nlist, P, n, out, st);
     default: return hipErrorInvalidValue;
   }
 }

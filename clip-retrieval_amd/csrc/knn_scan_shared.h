@@ -27,7 +27,7 @@ __device__ __forceinline__ bool better(float sa, uint32_t ia, float sb, uint32_t
 
 struct ScanSmem {
   // carved from dynamic LDS in this order (all offsets multiples of 16 B)
-  half8* qf;         // [KS*2*64]
+  half8* qf;         // [KS*2*64] (d = 1280: [(KS + KS_LO)*64], knn_kernels.h: scan_frag_lds_bytes)
   float* cand_s;     // [NQ*cap]
   uint32_t* cand_i;  // [NQ*cap]
   int* cnt;          // [NQ]
@@ -39,7 +39,7 @@ __device__ __forceinline__ ScanSmem carve(unsigned char* base, int d, int cap, i
   ScanSmem s;
   size_t off = 0;
   s.qf = reinterpret_cast<half8*>(base + off);
-  off += (size_t)d * 128;  // (d/16) * 2 * 64 * 16 B
+  off += scan_frag_lds_bytes(d);  // d <= 1024: (d/16) * 2 * 64 * 16 B
   s.cand_s = reinterpret_cast<float*>(base + off);
   off += (size_t)nqs * cap * 4;
   s.cand_i = reinterpret_cast<uint32_t*>(base + off);

@@ -33,7 +33,7 @@ int ensure_scratch(knnx_index* ix, int slot, size_t bytes, void** out) {
 }
 
 int scan_cap(int d, int k) {
-  long avail = (long)KNN_LDS_BYTES - (long)d * 128 - KNN_NQ * 8 - 16;
+  long avail = (long)KNN_LDS_BYTES - (long)scan_frag_lds_bytes(d) - KNN_NQ * 8 - 16;
   int cap = (int)(avail / (KNN_NQ * 8));
   cap = std::min(cap, 128);
   cap &= ~1;
@@ -55,8 +55,8 @@ extern "C" int knnx_create(int device, int d, int metric, knnx_index** out) {
   if (!out) return fail(KNNX_E_ARG, "out is null");
   *out = nullptr;
   if (metric != KNNX_METRIC_INNER_PRODUCT) return fail(KNNX_E_UNSUPPORTED, "only inner product is implemented");
-  if (d <= 0 || d % 256 != 0 || d > 1024)
-    return fail(KNNX_E_UNSUPPORTED, "d must be a multiple of 256 and <= 1024 (pad rows with zeros otherwise)");
+  if (d <= 0 || d % 256 != 0 || d > KNN_D_MAX)
+    return fail(KNNX_E_UNSUPPORTED, "d must be a multiple of 256 and <= 1280 (pad rows with zeros otherwise)");
   int ndev = 0;
   HIPCHK(hipGetDeviceCount(&ndev));
   if (device < 0 || device >= ndev) return fail(KNNX_E_ARG, "no such HIP device");
@@ -238,6 +238,7 @@ extern "C" int knnx_synth_fill(knnx_index* ix, int64_t n, uint64_t seed) {
   if (set_dev(ix)) return KNNX_E_HIP;
   if (ix->pq.m) return fail(KNNX_E_STATE, "synth_fill on an IVF-PQ index");
   if (ix->sq.on) return fail(KNNX_E_STATE, "synth_fill on an IVF-SQ8 index");
+  if (ix->d > 1024) return fail(KNNX_E_UNSUPPORTED, "synth_fill takes d <= 1024");
   if (!ix->rows.borrowed) {
     int r = grow(ix, n);
     if (r) return r;
@@ -312,7 +313,7 @@ static int fallback_groups(knnx_index* ix, const float* q_dev, int nq, int k, fl
 
 // LDS capacity of the 64-queue wide scan at this d
 static int wide_cap(int d) {
-  long avail = (long)KNN_LDS_BYTES - (long)d * 128 - KNN_NQ_MAX * 8 - 16;
+  long avail = (long)KNN_LDS_BYTES - (long)scan_frag_lds_bytes(d) - KNN_NQ_MAX * 8 - 16;
   int cap = (int)(avail / (KNN_NQ_MAX * 8));
   cap = std::min(cap, 128) & ~1;
   return cap >= KNN_WIDE_KW + 16 ? cap : -1;

@@ -268,7 +268,7 @@ extern "C" void knnx_ivfb_destroy(knnx_ivf_builder* b) {
 extern "C" int knnx_ivfb_create(int device, int d, int nlist, knnx_ivf_builder** out) {
   if (!out || nlist <= 0) return fail(KNNX_E_ARG, "bad ivfb_create arguments");
   *out = nullptr;
-  if (d <= 0 || d % 256 != 0 || d > 1024) return fail(KNNX_E_UNSUPPORTED, "d must be a multiple of 256 and <= 1024");
+  if (d <= 0 || d % 256 != 0 || d > KNN_D_MAX) return fail(KNNX_E_UNSUPPORTED, "d must be a multiple of 256 and <= 1280");
   HIPCHK(hipSetDevice(device));
   knnx_ivf_builder* b = new knnx_ivf_builder();
   b->device = device;

@@ -144,6 +144,7 @@ int sq_decode_rows(knnx_index* ix, const int64_t* ids_dev, int64_t n, float* out
 extern "C" int knnx_ivfsq_set_quantizer(knnx_index* ix, const float* vmin, const float* vdiff) {
   if (!ix || !vmin || !vdiff) return fail(KNNX_E_ARG, "bad ivfsq_set_quantizer arguments");
   const int d = ix->d;
+  if (d > 1024) return fail(KNNX_E_UNSUPPORTED, "IVF-SQ8 takes d <= 1024");
   for (int j = 0; j < d; ++j)
     if (!isfinite(vmin[j]) || !isfinite(vdiff[j]) || vdiff[j] < 0.f)
       return fail(KNNX_E_ARG, "IVF-SQ8 needs finite vmin and finite vdiff >= 0 (column " + std::to_string(j) + ")");

@@ -39,7 +39,10 @@ enum {
                                      * host (the reference advertises K = 100 000: README.md:301, clip_back.py:358)        */
 
 /* faiss.IndexFlatIP(d) / faiss.read_index(...) (clip_back.py:589-596).  `device` is the HIP
- * ordinal.  d must be a multiple of 256 and <= 1024 (CLIP embedding widths 512/768/1024). */
+ * ordinal.  d must be a multiple of 256 and <= 1280 (CLIP embedding widths 512/768/1024/1280); wider: KNNX_E_UNSUPPORTED.
+ * d = 1280 (ViT-bigG/14) serves flat and IVF-Flat indexes through the exact 32-query scans only: the 64-query wide scan, the
+ * register-stationary scan and the int8 first stage are off at that width, and IVF-PQ, IVF-SQ8, OPQ and synth_fill stay at
+ * d <= 1024. */
 int knnx_create(int device, int d, int metric, knnx_index** out);
 void knnx_destroy(knnx_index* ix);
 

@@ -327,7 +327,7 @@ hipError_t launch_sq_encode(const _Float16* src, int64_t n, int d, const int32_t
 // out [n][d] = the decoded rows of n ids through inv; an id outside the index (-1) -> 0xFF bytes
 hipError_t launch_sq_decode(const uint8_t* codes, int d, const float* vmin, const float* step, int64_t id_lo, int64_t n_ids,
                             const uint32_t* inv, const int64_t* ids, int64_t n, float* out, hipStream_t st);
-// per-column min / max of n fp16 rows (d <= 1024) -> vmin_dev / vmax_dev f32 [d]; enc: 2 d ints of device scratch
+// per-column min / max of n fp16 rows (d <= KNN_D_MAX) -> vmin_dev / vmax_dev f32 [d]; enc: 2 d ints of device scratch
 hipError_t launch_sq_colminmax(const _Float16* X, int64_t n, int d, int* enc, float* vmin_dev, float* vmax_dev, hipStream_t st);
 
 // ---- post filter of one request on the device (knn_filter_kernels.hip; the shared arithmetic: knnx_filter_plan.h) ----

@@ -125,12 +125,16 @@ __device__ __forceinline__ void sq_scan_body(
   constexpr int KS = D / 16;
   constexpr int NB = D / (32 * LD);  // bursts per tile
   static_assert(D % (32 * LD) == 0, "whole bursts");
+  constexpr int KS_LO = scan_lo_lds_ksteps(D);  // k-steps whose lo fragment sits in the LDS (knn_kernels.h) ...
+  constexpr int KS_REG = KS - KS_LO;            // ... and in this wave's registers (D = 1280: 22)
   ScanSmem sm{};
   if constexpr (RANGE) sm.qf = reinterpret_cast<half8*>(smem_raw);
   else sm = carve(smem_raw, D, cap, NQ);
 
   const int tid = threadIdx.x;
-  const int lane = tid & 63, w = tid >> 6;
+  // (D = 1280: the wave number is made scalar, so the three work items in flight and the tile addresses made from them sit in
+  // scalar registers -- the 12 VGPRs they take at the other widths are what the top-k mode lacks beside the stationary fragments)
+  const int lane = tid & 63, w = KS_REG > 0 ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
   const int q = lane & 31, hb = lane >> 5;
 
   // which query block this workgroup serves, and as which of that block's workgroups (knn_scan_kernel, IVF && MODE 0)
@@ -168,7 +172,14 @@ __device__ __forceinline__ void sq_scan_body(
   {
     const uint4* src = reinterpret_cast<const uint4*>(qfrag);
     uint4* dst = reinterpret_cast<uint4*>(sm.qf);
-    for (int i = tid; i < KS * 2 * 64; i += KNN_WG) dst[i] = src[i];
+    if constexpr (KS_REG == 0) {
+      for (int i = tid; i < KS * 2 * 64; i += KNN_WG) dst[i] = src[i];
+    } else {
+      for (int i = tid; i < (KS + KS_LO) * 64; i += KNN_WG) {
+        const int sl = i >> 6;  // LDS slot -> slot of the image in HBM (knn_scan_kernel: the hi slots of the k-steps >= KS_LO lie 2 apart)
+        dst[i] = src[(sl < 2 * KS_LO ? sl : 2 * (sl - KS_LO)) * 64 + (i & 63)];
+      }
+    }
     if constexpr (!RANGE) {
       if (tid < NQ) { sm.cnt[tid] = 0; sm.thr[tid] = enc_f(-INFINITY); }
       if (tid < 4) sm.flag[tid] = 0;
@@ -178,6 +189,20 @@ __device__ __forceinline__ void sq_scan_body(
 
   const int64_t ntile = (int64_t)*nwork_ptr;
   const int64_t ngroup = (ntile + KNN_WAVES - 1) / KNN_WAVES;
+
+  // D = 1280: the lo fragments of the k-steps KS_LO .. KS - 1, loaded once -- they are the same for every tile (88 of the wave's 256
+  // registers; see the head of the D = 1280 kernels below for what that leaves the bursts)
+  half8 blo[KS_REG > 0 ? KS_REG : 1];
+  if constexpr (KS_REG > 0) {
+    const half8* src = reinterpret_cast<const half8*>(qfrag);
+#pragma unroll
+    for (int j = 0; j < KS_REG; ++j) blo[j] = src[((KS_LO + j) * 2 + 1) * 64 + lane];
+#pragma unroll
+    for (int j = 0; j < KS_REG; ++j) asm volatile("" : "+v"(blo[j]));  // loaded here, once: never re-fetched inside the tile loop
+  }
+  // the B operands of k-step ks in the split layout (ks is a constant of the unrolled loop)
+  auto frag_hi = [&](int ks) -> half8 { return sm.qf[(ks < KS_LO ? 2 * ks : KS_LO + ks) * 64 + lane]; };
+  auto frag_lo = [&](int ks) -> half8 { return ks < KS_LO ? sm.qf[(2 * ks + 1) * 64 + lane] : blo[ks >= KS_LO ? ks - KS_LO : 0]; };
 
   uint4 a0[LD], a1[LD];
   auto item_of = [&](int64_t grp) -> uint4 {
@@ -224,10 +249,17 @@ __device__ __forceinline__ void sq_scan_body(
         const int s = 2 * (c * LD + j);
         const half8 x0 = sq_codes_half8(cur[j].x, cur[j].y);
         const half8 x1 = sq_codes_half8(cur[j].z, cur[j].w);
-        acc_h = __builtin_amdgcn_mfma_f32_32x32x16_f16(x0, sm.qf[(s * 2 + 0) * 64 + lane], acc_h, 0, 0, 0);
-        acc_l = __builtin_amdgcn_mfma_f32_32x32x16_f16(x0, sm.qf[(s * 2 + 1) * 64 + lane], acc_l, 0, 0, 0);
-        acc_h = __builtin_amdgcn_mfma_f32_32x32x16_f16(x1, sm.qf[(s * 2 + 2) * 64 + lane], acc_h, 0, 0, 0);
-        acc_l = __builtin_amdgcn_mfma_f32_32x32x16_f16(x1, sm.qf[(s * 2 + 3) * 64 + lane], acc_l, 0, 0, 0);
+        if constexpr (KS_REG == 0) {
+          acc_h = __builtin_amdgcn_mfma_f32_32x32x16_f16(x0, sm.qf[(s * 2 + 0) * 64 + lane], acc_h, 0, 0, 0);
+          acc_l = __builtin_amdgcn_mfma_f32_32x32x16_f16(x0, sm.qf[(s * 2 + 1) * 64 + lane], acc_l, 0, 0, 0);
+          acc_h = __builtin_amdgcn_mfma_f32_32x32x16_f16(x1, sm.qf[(s * 2 + 2) * 64 + lane], acc_h, 0, 0, 0);
+          acc_l = __builtin_amdgcn_mfma_f32_32x32x16_f16(x1, sm.qf[(s * 2 + 3) * 64 + lane], acc_l, 0, 0, 0);
+        } else {
+          acc_h = __builtin_amdgcn_mfma_f32_32x32x16_f16(x0, frag_hi(s), acc_h, 0, 0, 0);
+          acc_l = __builtin_amdgcn_mfma_f32_32x32x16_f16(x0, frag_lo(s), acc_l, 0, 0, 0);
+          acc_h = __builtin_amdgcn_mfma_f32_32x32x16_f16(x1, frag_hi(s + 1), acc_h, 0, 0, 0);
+          acc_l = __builtin_amdgcn_mfma_f32_32x32x16_f16(x1, frag_lo(s + 1), acc_l, 0, 0, 0);
+        }
       }
     }
     xp = xnext;
@@ -347,7 +379,9 @@ __global__ __launch_bounds__(KNN_WG, 2) void knn_sq_scan_kernel(
 }
 // (d = 768 runs bursts of 6 loads, four per tile: with 8 -- three per tile, the tile body unrolled twice -- the compiler takes 222
 // VGPRs, more than the 210 of the top-k form; the k-steps, and so the scores, come in the same order whatever the burst length)
-constexpr int sq_range_burst(int d) { return d == 768 ? 6 : SQ_BURST; }
+constexpr int SQ_BURST_1280 = 5;  // (see the D = 1280 kernels below)
+constexpr int sq_scan_burst(int d) { return d > 1024 ? SQ_BURST_1280 : SQ_BURST; }
+constexpr int sq_range_burst(int d) { return d == 768 ? 6 : sq_scan_burst(d); }
 template <int D, int LD>
 __global__ __launch_bounds__(KNN_WG, 2) void knn_sq_range_scan_kernel(
     const uint8_t* __restrict__ X, const _Float16* __restrict__ qfrag, const float* __restrict__ bq_g,
@@ -358,6 +392,39 @@ __global__ __launch_bounds__(KNN_WG, 2) void knn_sq_range_scan_kernel(
   sq_scan_body<D, LD, true>(smem_raw, X, qfrag, bq_g, inv_g, nq, 0, 0, nullptr, nullptr, nullptr, nullptr, work, nwork_ptr, nblk, work_stride,
                             rthr, rcnt, rcap, hit_s, hit_i);
 }
+
+// D = 1280 (ViT-bigG/14).  The fragment image of u is 128 D = 160 KiB, the whole LDS, so both modes use the split of the fp16 scan
+// (knn_kernels.h: scan_lo_lds_ksteps / scan_frag_lds_bytes; knn_kernels.hip: knn_scan_kernel, NCH = 10): the LDS keeps the hi
+// fragments of all 80 k-steps and the lo fragments of k-steps 0 .. 57 (138 KiB, queues of 86 entries beside them in the top-k mode),
+// every wave holds the lo fragments of k-steps 58 .. 79 in 88 registers, and the k-step order -- hi, then lo, k ascending -- is that
+// of the other widths, so a score has the same bits in both modes.  138 KiB admit one workgroup per CU: 8 waves on 4 SIMDs are 2 waves
+// per SIMD, 256 of a SIMD's 512 unified registers each, accumulation registers included -- there is no second half of the file to
+// put the stationary fragments into.  Beside the 88 the wave keeps 32 accumulators, 16 scores, two bursts of LD x 4 and the
+// converted operands: with bursts of 8 loads the top-k mode spills (52 B of scratch, 12 B with the scalar work items), with bursts
+// of 5 -- eight per tile, 160 columns each, still 10 dwordx4 loads in flight across a burst boundary -- neither mode does.
+// These two are compiled without packed fp32 arithmetic (the score's multiply and add stay one instruction per row).
+#define SQ_1280_ATTRS __attribute__((target("no-packed-fp32-ops"))) __launch_bounds__(KNN_WG, 1)
+template <>
+__global__ SQ_1280_ATTRS void knn_sq_scan_kernel<1280, SQ_BURST_1280>(
+    const uint8_t* __restrict__ X, const _Float16* __restrict__ qfrag, const float* __restrict__ bq_g,
+    const float* __restrict__ inv_g, int nq, int k, int cap, int* __restrict__ thr_g, float* __restrict__ part_s,
+    uint32_t* __restrict__ part_i, int* __restrict__ part_n, const uint4* __restrict__ work,
+    const unsigned* __restrict__ nwork_ptr, int nblk, unsigned work_stride) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  sq_scan_body<1280, SQ_BURST_1280, false>(smem_raw, X, qfrag, bq_g, inv_g, nq, k, cap, thr_g, part_s, part_i, part_n, work, nwork_ptr, nblk,
+                                           work_stride, nullptr, nullptr, 0u, nullptr, nullptr);
+}
+template <>
+__global__ SQ_1280_ATTRS void knn_sq_range_scan_kernel<1280, SQ_BURST_1280>(
+    const uint8_t* __restrict__ X, const _Float16* __restrict__ qfrag, const float* __restrict__ bq_g,
+    const float* __restrict__ inv_g, int nq, const uint4* __restrict__ work, const unsigned* __restrict__ nwork_ptr, int nblk,
+    unsigned work_stride, const float* __restrict__ rthr, unsigned* __restrict__ rcnt, unsigned rcap, float* __restrict__ hit_s,
+    uint32_t* __restrict__ hit_i) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  sq_scan_body<1280, SQ_BURST_1280, true>(smem_raw, X, qfrag, bq_g, inv_g, nq, 0, 0, nullptr, nullptr, nullptr, nullptr, work, nwork_ptr, nblk,
+                                          work_stride, rthr, rcnt, rcap, hit_s, hit_i);
+}
+#undef SQ_1280_ATTRS
 
 // ---------------------------------------------------------------------------------------------
 // encode + scatter, decode-gather, column min / max
@@ -444,6 +511,36 @@ __global__ __launch_bounds__(256) void sq_colminmax_kernel(const _Float16* __res
     }
   }
 }
+// ... and d <= 1280: five columns per thread.  (A kernel of its own: the four-column one keeps its code.)
+__global__ __launch_bounds__(256) void sq_colminmax5_kernel(const _Float16* __restrict__ X, int64_t n, int d, int* __restrict__ omin,
+                                                           int* __restrict__ omax) {
+  constexpr int NE = KNN_D_MAX / 256;
+  float mn[NE], mx[NE];
+#pragma unroll
+  for (int e = 0; e < NE; ++e) { mn[e] = INFINITY; mx[e] = -INFINITY; }
+  for (int64_t r0 = (int64_t)blockIdx.x * 64; r0 < n; r0 += (int64_t)gridDim.x * 64) {
+    const int64_t r1 = r0 + 64 < n ? r0 + 64 : n;
+    for (int64_t r = r0; r < r1; ++r) {
+#pragma unroll
+      for (int e = 0; e < NE; ++e) {
+        const int c = threadIdx.x + 256 * e;
+        if (c < d) {
+          const float v = (float)X[(size_t)r * d + c];
+          mn[e] = fminf(mn[e], v);
+          mx[e] = fmaxf(mx[e], v);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < NE; ++e) {
+    const int c = threadIdx.x + 256 * e;
+    if (c < d) {
+      atomicMin(&omin[c], enc_f(mn[e]));
+      atomicMax(&omax[c], enc_f(mx[e]));
+    }
+  }
+}
 __global__ void sq_minmax_init_kernel(int d, int* __restrict__ omin, int* __restrict__ omax) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c < d) { omin[c] = enc_f(INFINITY); omax[c] = enc_f(-INFINITY); }
@@ -485,7 +582,7 @@ hipError_t launch_sq_scan(const SqScanArgs& a, hipStream_t st) {
   const size_t smem = scan_smem_bytes(a.d, a.cap, 32);
 #define SQ_LAUNCH(DD)                                                                                                          \
   {                                                                                                                            \
-    auto kern = knn_sq_scan_kernel<DD, SQ_BURST>;                                                                              \
+    auto kern = knn_sq_scan_kernel<DD, sq_scan_burst(DD)>;                                                                              \
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
     if (e != hipSuccess) return e;                                                                                             \
     hipLaunchKernelGGL(kern, dim3(a.grid), dim3(KNN_WG), smem, st, a.codes, a.qfrag, a.bq, a.inv, a.nq, a.k, a.cap, a.thr_g,    \
@@ -497,6 +594,7 @@ hipError_t launch_sq_scan(const SqScanArgs& a, hipStream_t st) {
     case 512: SQ_LAUNCH(512)
     case 768: SQ_LAUNCH(768)
     case 1024: SQ_LAUNCH(1024)
+    case 1280: SQ_LAUNCH(1280)
     default: return hipErrorInvalidValue;
   }
 #undef SQ_LAUNCH
@@ -506,7 +604,7 @@ hipError_t launch_sq_scan(const SqScanArgs& a, hipStream_t st) {
 hipError_t launch_sq_range_scan(const SqScanArgs& a, hipStream_t st) {
   if (a.nblk < 1 || a.grid < a.nblk || !a.work || !a.nwork || !a.rthr || !a.rcnt || !a.hit_s || !a.hit_i) return hipErrorInvalidValue;
   if (a.nq < 1 || (uint64_t)a.nq * a.rcap > 0xffffffffull) return hipErrorInvalidValue;  // (the kernel indexes the pools with 32 bits)
-  const size_t smem = (size_t)a.d * 128;
+  const size_t smem = scan_frag_lds_bytes(a.d);  // (d <= 1024: 128 d; d = 1280: the split layout of the top-k mode)
   hipError_t e = hipMemsetAsync(a.rcnt, 0, (size_t)a.nblk * 32 * sizeof(unsigned), st);
   if (e != hipSuccess) return e;
 #define SQ_LAUNCH(DD)                                                                                                          \
@@ -523,6 +621,7 @@ hipError_t launch_sq_range_scan(const SqScanArgs& a, hipStream_t st) {
     case 512: SQ_LAUNCH(512)
     case 768: SQ_LAUNCH(768)
     case 1024: SQ_LAUNCH(1024)
+    case 1280: SQ_LAUNCH(1280)
     default: return hipErrorInvalidValue;
   }
 #undef SQ_LAUNCH
@@ -553,10 +652,10 @@ hipError_t launch_sq_decode(const uint8_t* codes, int d, const float* vmin, cons
 
 // vmin_dev / vmax_dev: device f32 [d]; enc: device scratch of 2 d ints
 hipError_t launch_sq_colminmax(const _Float16* X, int64_t n, int d, int* enc, float* vmin_dev, float* vmax_dev, hipStream_t st) {
-  if (d <= 0 || d > 1024 || n <= 0) return hipErrorInvalidValue;
+  if (d <= 0 || d > KNN_D_MAX || n <= 0) return hipErrorInvalidValue;
   hipLaunchKernelGGL(sq_minmax_init_kernel, dim3((d + 255) / 256), dim3(256), 0, st, d, enc, enc + d);
   const int64_t blocks = std::min<int64_t>((n + 63) / 64, 2048);
-  hipLaunchKernelGGL(sq_colminmax_kernel, dim3((unsigned)blocks), dim3(256), 0, st, X, n, d, enc, enc + d);
+  hipLaunchKernelGGL(d <= 1024 ? sq_colminmax_kernel : sq_colminmax5_kernel, dim3((unsigned)blocks), dim3(256), 0, st, X, n, d, enc, enc + d);
   hipLaunchKernelGGL(sq_minmax_decode_kernel, dim3((d + 255) / 256), dim3(256), 0, st, d, enc, enc + d, vmin_dev, vmax_dev);
   return hipGetLastError();
 }

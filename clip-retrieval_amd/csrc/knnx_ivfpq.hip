@@ -275,6 +275,7 @@ static const char* const PQ_M_RULE = "IVF-PQ needs M in {16, 32, 64, 128} dividi
 extern "C" int knnx_ivfpq_set_quantizer(knnx_index* ix, int M, const float* codebooks) {
   if (!ix || !codebooks) return fail(KNNX_E_ARG, "bad ivfpq_set_quantizer arguments");
   const int dq = pq_dq(ix);  // (the rule speaks of the quantiser width: d_out where knnx_ivfpq_set_out_dim gave one)
+  if (dq > 1024) return fail(KNNX_E_UNSUPPORTED, "IVF-PQ takes d <= 1024");  // (no M makes a 1280-wide index an IVF-PQ one)
   if (!pq_supported(dq, M)) return fail(KNNX_E_ARG, PQ_M_RULE);
   std::lock_guard<std::mutex> lk(ix->mu);
   if (set_dev(ix)) return KNNX_E_HIP;

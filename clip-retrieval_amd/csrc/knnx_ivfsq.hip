@@ -144,7 +144,6 @@ int sq_decode_rows(knnx_index* ix, const int64_t* ids_dev, int64_t n, float* out
 extern "C" int knnx_ivfsq_set_quantizer(knnx_index* ix, const float* vmin, const float* vdiff) {
   if (!ix || !vmin || !vdiff) return fail(KNNX_E_ARG, "bad ivfsq_set_quantizer arguments");
   const int d = ix->d;
-  if (d > 1024) return fail(KNNX_E_UNSUPPORTED, "IVF-SQ8 takes d <= 1024");
   for (int j = 0; j < d; ++j)
     if (!isfinite(vmin[j]) || !isfinite(vdiff[j]) || vdiff[j] < 0.f)
       return fail(KNNX_E_ARG, "IVF-SQ8 needs finite vmin and finite vdiff >= 0 (column " + std::to_string(j) + ")");
@@ -212,7 +211,7 @@ extern "C" int knnx_ivfsq_add_codes(knnx_index* ix, const uint8_t* codes, int64_
 // ---- training: per-column min and max of fp16 rows in HBM (faiss RS_minmax with argument 0) ---------------------------------------
 extern "C" int knnx_colminmax_device(int device, const void* rows_dev_f16, int64_t n, int d, float* vmin_out, float* vmax_out,
                                      void* stream) {
-  if (!rows_dev_f16 || n <= 0 || d <= 0 || d > 1024 || !vmin_out || !vmax_out) return fail(KNNX_E_ARG, "bad colminmax arguments (n > 0, 0 < d <= 1024)");
+  if (!rows_dev_f16 || n <= 0 || d <= 0 || d > KNN_D_MAX || !vmin_out || !vmax_out) return fail(KNNX_E_ARG, "bad colminmax arguments (n > 0, 0 < d <= 1280)");
   HIPCHK(hipSetDevice(device));
   hipStream_t st = (hipStream_t)stream;
   DevBuf<int> enc;

@@ -40,9 +40,9 @@ enum {
 
 /* faiss.IndexFlatIP(d) / faiss.read_index(...) (clip_back.py:589-596).  `device` is the HIP
  * ordinal.  d must be a multiple of 256 and <= 1280 (CLIP embedding widths 512/768/1024/1280); wider: KNNX_E_UNSUPPORTED.
- * d = 1280 (ViT-bigG/14) serves flat and IVF-Flat indexes through the exact 32-query scans only: the 64-query wide scan, the
- * register-stationary scan and the int8 first stage are off at that width, and IVF-PQ, IVF-SQ8, OPQ and synth_fill stay at
- * d <= 1024. */
+ * d = 1280 (ViT-bigG/14) serves flat, IVF-Flat and IVF-SQ8 indexes; the flat and IVF-Flat ones through the exact 32-query scans
+ * only: the 64-query wide scan, the register-stationary scan and the int8 first stage are off at that width.  IVF-PQ
+ * (knnx_ivfpq_set_quantizer: KNNX_E_UNSUPPORTED), OPQ and synth_fill stay at d <= 1024. */
 int knnx_create(int device, int d, int metric, knnx_index** out);
 void knnx_destroy(knnx_index* ix);
 
@@ -322,6 +322,8 @@ int knnx_pqb_lloyd(knnx_pq_builder* b, uint8_t* codes_out, int64_t* sizes_out);
  *             scans.  A (query, row) score does not depend on the batch the query arrives in.
  *   the rest  coarse quantiser, probe rule (knnx_ivf_set_nprobe), result order (score descending, ties by ascending id) and the
  *             -1 / -FLT_MAX padding are IVF-Flat's, word for word.
+ * Widths: every d an index takes, d <= 1280 (at 1280 the scan keeps part of u in registers; same contract, same score bits in the
+ * top-k and the threshold mode).
  * Build: knnx_ivfsq_set_quantizer on an EMPTY index before knnx_ivf_begin (KNNX_E_ARG for a non-finite entry or a negative vdiff;
  * KNNX_E_STATE on an index that has rows or lists, that already has a quantiser, or that is IVF-PQ -- and knnx_ivfpq_set_quantizer
  * answers KNNX_E_STATE on an IVF-SQ8 index).  Afterwards knnx_ivf_begin / knnx_ivf_add_assigned[_device] / knnx_ivf_end ENCODE the
@@ -362,7 +364,7 @@ int knnx_ivfsq_get_codes(knnx_index* ix, int64_t* ids, int32_t* lists, uint8_t* 
 int knnx_ivfsq_set_threshold_scan(knnx_index* ix, int on);
 int knnx_ivfsq_threshold_scan(const knnx_index* ix);   /* 0 / 1; 0 on a non-SQ8 or null index */
 int knnx_ivfsq_threshold_stats(knnx_index* ix, int64_t* queries, int64_t* launches, int64_t* query_scans, int64_t* hits);
-/* The training kernel (faiss RS_minmax with argument 0): per-column min and max of n fp16 rows [n][d] in HBM, 0 < d <= 1024, n > 0 ->
+/* The training kernel (faiss RS_minmax with argument 0): per-column min and max of n fp16 rows [n][d] in HBM, 0 < d <= 1280, n > 0 ->
  * host f32 vmin_out [d], vmax_out [d].  Min and max do not depend on the order of the rows: bit-equal to numpy's
  * x.astype(float32).min(0) / .max(0).  `stream`: hipStream_t or NULL; synchronous. */
 int knnx_colminmax_device(int device, const void* rows_dev_f16, int64_t n, int d, float* vmin_out, float* vmax_out, void* stream);

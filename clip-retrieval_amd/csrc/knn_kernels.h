@@ -148,7 +148,7 @@ hipError_t launch_ivf_shrink_ids(const int64_t* idmap_old, int64_t prow_old, int
                                  const uint32_t* dst0, const uint32_t* rank, int64_t* idmap, uint32_t* inv, hipStream_t st);
 
 // ---- register-stationary-queries (RQ) scan, knn_rq_kernels.hip: up to rq_queries_per_pass(d) queries per pass over HBM
-constexpr int KNN_RQ_MAX = 256;        // queries of one RQ pass at d <= 768 (128 at d = 1024)
+constexpr int KNN_RQ_MAX = 256;        // queries of one RQ pass at d <= 768 (128 at d = 1024 and d = 1280); of one int8 pass at every width
 // The sample pass visits every S-th 32-row tile, S = min(1024, tiles / 4096) (>= 4096 tiles = 131 k rows sampled); the
 // threshold is the J-th best sample score with J = k + 8 up to S = 128 and J = (k + 8) * 128 / S (>= 6) beyond, i.e. ~6 k
 // expected hits per query whatever the index size.  The number of index rows above the J-th best of a 1/S sample is
@@ -159,7 +159,7 @@ constexpr int KNN_RQ_STRIDE = 1024;
 constexpr int KNN_RQ_MARGIN = 8;
 constexpr unsigned KNN_RQ_CAP = 32768; // hit list entries per query
 constexpr int64_t KNN_RQ_MIN_ROWS = (int64_t)1 << 21;  // below this the 64-query scan is used
-int rq_queries_per_pass(int d);  // 0: no RQ kernel for this d
+int rq_queries_per_pass(int d);  // 0: no RQ kernel for this d (512 / 768: 256; 1024: 128; 1280: 128 through the ring of 16-row half tiles)
 hipError_t launch_rq_prep(const float* q_dev, int nq, int d, _Float16* qfrag, const float* samp, int kw, int J, float slack,
                           float* thr, unsigned* cnt, unsigned* lost, hipStream_t st);
 hipError_t launch_rq_scan(const _Float16* X, int64_t N, int d, int nq, const _Float16* qfrag, const float* thr, unsigned* cnt,

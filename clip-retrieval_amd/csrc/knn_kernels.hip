@@ -1430,7 +1430,7 @@ static hipError_t launch_scan_mode(const ScanArgs& a, hipStream_t st) {
     case 512: KNN_LAUNCH(4)
     case 768: KNN_LAUNCH(6)
     case 1024: KNN_LAUNCH(8)
-    case 1280:  // (the 32-query scans only: wide_cap(1280) < 0)
+    case 1280:  // (no 64-query wide scan: wide_cap(1280) < 0; batches of a large flat index go to knn_rq_kernels.hip)
       if constexpr (QB == 1) KNN_LAUNCH(10)
       return hipErrorInvalidValue;
     default: return hipErrorInvalidValue;

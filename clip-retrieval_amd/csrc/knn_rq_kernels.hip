@@ -352,6 +352,201 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void knn_rq_scan_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// d = 1280 (KS = 80): the same scan with a ring of 16-ROW HALF TILES.  A 32-row tile is 80 KiB here: two slots are the whole LDS, nothing
+// is left for the staging lists, and the DMA cannot run two units ahead of the MFMAs.  So the ring unit is one 16-row half tile = 40 KiB =
+// KS / 2 lane-linear 1-KiB pieces, one per 32-column slab (piece s: lane (r = l & 15, q4 = l >> 4) holds row r, columns 32 s + 8 q4 .. + 8);
+// three slots + staging = 126 KiB.  The index is walked in units of 16 rows, ceil(N / 16) of them; one s_barrier, one k-loop of KS / 2
+// steps and one filter over 4 scores per lane and 16-query block per unit.  (The alternative, a K-half of a 32-row tile per unit, keeps
+// the 32-row filter but carries 16 accumulators over two units and halves the DMA request to 16 rows x 32 B: DESIGN 4.3.)
+// Four waves, one per SIMD with all 512 registers, 32 queries each: the B fragments are 2 blocks x 40 slabs x 4 = 320 registers, more
+// than the 256 architectural VGPRs, so block 0 is pinned in VGPRs and block 1 in AGPRs ("+a": MFMA reads B from either file).  One
+// ds_read_b128 feeds both blocks' v_mfma_f32_16x16x32_f16; the A fragments go through the 4-deep register ring of rq_ksteps.
+// DMA: wave w fetches the DPW = KS / 2 / NW slabs w DPW .. of a unit, 16 rows x 64 B each, fragment-shaped from the row-major rows;
+// one instruction every (KS / 2) / DPW k-steps.  Past the end of the index the last unit is re-loaded (uniform vmcnt arithmetic); the
+// rows of the last unit at or beyond N re-read row N - 1 and are never admitted.
+// ---------------------------------------------------------------------------------------------
+struct Rq16Unit {
+  const char* base;  // unit + this wave's first slab
+  unsigned m0b;      // LDS address of the slot + this wave's first piece
+  unsigned vo;       // per-lane byte offset (row, 16-B quarter of the slab's 64 B)
+};
+template <int KS, int NW>
+__device__ __forceinline__ Rq16Unit rq16_unit(const _Float16* __restrict__ X, int64_t u, int64_t nunit, unsigned vo_full, unsigned vo_last,
+                                              unsigned lds_base, int slot, int w) {
+  constexpr int UNIT_BYTES = KS * 512, DPW = KS / 2 / NW;
+  const int64_t last = nunit - 1;
+  const int64_t uu = u < nunit ? u : last;
+  Rq16Unit r;
+  r.vo = uu == last ? vo_last : vo_full;
+  r.base = reinterpret_cast<const char*>(X) + (size_t)uu * UNIT_BYTES + w * (DPW * 64);
+  r.m0b = lds_base + slot * UNIT_BYTES + w * (DPW * 1024);
+  return r;
+}
+#define RQ16_UNIT(u_, slot_) rq16_unit<KS, NW>(X, (u_), nunit, vo_full, vo_last, lds_base, (slot_), w)
+template <int IDX>
+__device__ __forceinline__ void rq16_issue_one(const Rq16Unit& r) {
+  const char* p = r.base + IDX * 64;  // slab IDX of the wave
+  asm volatile("s_add_u32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(r.vo), "s"(p), "s"(r.m0b), "n"(IDX * 1024)
+               : "memory", "scc");
+}
+template <int DPW, int IDX = 0>
+__device__ __forceinline__ void rq16_issue_all(const Rq16Unit& r) {
+  if constexpr (IDX < DPW) {
+    rq16_issue_one<IDX>(r);
+    rq16_issue_all<DPW, IDX + 1>(r);
+  }
+}
+// k-step S = slab S of the unit: one LDS read, one MFMA per 16-query block (Q[0]: VGPRs, Q[1]: AGPRs)
+template <int NSL, int DPW, int S>
+__device__ __forceinline__ void rq16_ksteps(unsigned xa, i32x4 (&A)[4], float4v (&acc)[2], const half8 (&Q)[2][NSL], const Rq16Unit& refill) {
+  if constexpr (S < NSL) {
+    if constexpr (S + 3 < NSL) rq_dsread<(S + 3) * 1024>(A[(S + 3) & 3], xa);
+    rq_wait_lgkm<(NSL - 1 - S < 3 ? NSL - 1 - S : 3)>();
+    __builtin_amdgcn_sched_barrier(0);
+    acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, A[S & 3]), Q[0][S], acc[0], 0, 0, 0);
+    acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, A[S & 3]), Q[1][S], acc[1], 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (S % (NSL / DPW) == 1) {
+      rq16_issue_one<S / (NSL / DPW)>(refill);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    rq16_ksteps<NSL, DPW, S + 1>(xa, A, acc, Q, refill);
+  }
+}
+
+// KS = d / 16; NW waves x 32 queries, one wave per SIMD; NSLOT ring slots of one 16-row unit each.  Arguments as knn_rq_scan_kernel.
+template <int KS, int NW, int NSLOT>
+__global__ __launch_bounds__(NW * 64, 1) void knn_rq16_scan_kernel(
+    const _Float16* __restrict__ X, int64_t N, const _Float16* __restrict__ qfrag, const float* __restrict__ thr,
+    unsigned* __restrict__ g_cnt, unsigned cap, float* __restrict__ hit_s, uint32_t* __restrict__ hit_r,
+    unsigned* __restrict__ g_lost, const unsigned* __restrict__ gate, uint32_t row_off) {
+  constexpr int D = KS * 16, NSL = KS / 2, QBS = 16;
+  constexpr int UNIT_BYTES = KS * 512;  // 16 rows x D x 2 B, stored as NSL lane-linear 1 KiB pieces
+  constexpr int DPW = NSL / NW;         // DMA instructions per wave per unit
+  static_assert(NSL % NW == 0 && NSL % DPW == 0 && NSL / DPW >= 2, "slabs must divide evenly among the waves and the k-steps");
+  static_assert(NSLOT * UNIT_BYTES + NW * RQ_STAGE * 12 <= KNN_LDS_BYTES, "ring + staging must fit the LDS");
+  if (N <= 0 || (gate && *gate == 0)) return;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  unsigned char* stage = smem + NSLOT * UNIT_BYTES;
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int qcol = lane & (QBS - 1), hb = lane / QBS;  // lane = (query column, row group): rows 4 hb + e of the unit
+  float* st_s = reinterpret_cast<float*>(stage + w * RQ_STAGE * 12);
+  uint32_t* st_r = reinterpret_cast<uint32_t*>(st_s + RQ_STAGE);
+  uint32_t* st_q = st_r + RQ_STAGE;
+
+  half8 Q[2][NSL];
+  float tq[2];
+#pragma unroll
+  for (int b = 0; b < 2; ++b) {
+    const int blk = w * 2 + b;
+    const half8* src = reinterpret_cast<const half8*>(qfrag) + (size_t)blk * NSL * 64 + lane;
+#pragma unroll
+    for (int s = 0; s < NSL; ++s) Q[b][s] = src[s * 64];
+    tq[b] = thr[blk * QBS + qcol];
+  }
+  // all landed before the DMA ring starts, each block in its register file for good (see knn_rq_scan_kernel)
+#pragma unroll
+  for (int s = 0; s < NSL; ++s) {
+    asm volatile("" : "+v"(Q[0][s]));
+    asm volatile("" : "+a"(Q[1][s]));
+  }
+  asm volatile("" : "+v"(tq[0]), "+v"(tq[1]));
+
+  const int64_t nunit = (N + 15) >> 4;
+  const int lrow = (int)(N - 1 - (nunit - 1) * 16);  // last valid row inside the last unit
+  const unsigned vo_full = (unsigned)(qcol * D * 2 + hb * 16);  // DMA lane (r = l & 15, q4 = l >> 4): the same split of the lane index
+  const unsigned vo_last = (unsigned)((qcol < lrow ? qcol : lrow) * D * 2 + hb * 16);
+  const unsigned lds_base = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem);
+
+  int64_t t = blockIdx.x;
+  const int64_t gstride = gridDim.x;
+#pragma unroll
+  for (int i = 0; i < NSLOT - 1; ++i) rq16_issue_all<DPW>(RQ16_UNIT(t + (int64_t)i * gstride, i));
+
+  int nst = 0;  // entries in this wave's staging list (wave-uniform)
+  int slot = 0;
+  for (; t < nunit; t += gstride) {
+    // unit t has landed (this wave's share: all but the DPW * (NSLOT - 2) youngest DMAs are done), then everyone's
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DPW * (NSLOT - 2)) : "memory");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+    // refill of the slot that unit t - 1 (of this workgroup's sequence) occupied -- every wave is past it
+    const Rq16Unit refill = RQ16_UNIT(t + (int64_t)(NSLOT - 1) * gstride, slot == 0 ? NSLOT - 1 : slot - 1);
+
+    float4v acc[2] = {float4v{0.f, 0.f, 0.f, 0.f}, float4v{0.f, 0.f, 0.f, 0.f}};
+    const unsigned xa = lds_base + slot * UNIT_BYTES + lane * 16;
+    i32x4 A[4];
+    rq_dsread<0>(A[0], xa);
+    rq_dsread<1024>(A[1], xa);
+    rq_dsread<2048>(A[2], xa);
+    __builtin_amdgcn_sched_barrier(0);
+    rq16_ksteps<NSL, DPW, 0>(xa, A, acc, Q, refill);
+
+    // ---- filter: lane (qcol, hb) owns rows row0 + e, e < 4, of its query column in each block
+    const int64_t row0 = t * 16 + 4 * hb;
+    bool any = false;
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+      any |= __builtin_fmaxf(__builtin_fmaxf(acc[b][0], acc[b][1]), __builtin_fmaxf(acc[b][2], acc[b][3])) >= tq[b];
+    if (__builtin_amdgcn_ballot_w64(any) != 0ull) {
+      bool vmem = false;
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int64_t row = row0 + e;
+          const bool hit = acc[b][e] >= tq[b] && row < N;
+          const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
+          if (m != 0ull) {
+            const int pos = nst + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+            const unsigned qq = (unsigned)((w * 2 + b) * QBS + qcol);
+            if (hit) {
+              if (pos < RQ_STAGE) {
+                st_s[pos] = acc[b][e];
+                st_r[pos] = (uint32_t)row + row_off;
+                st_q[pos] = qq;
+              } else {
+                g_lost[qq] = 1u;  // staging overflow (flood of hits in one unit): the query falls back
+                vmem = true;
+              }
+            }
+            nst += __builtin_popcountll(m);
+          }
+        }
+      }
+      if (nst > RQ_STAGE) nst = RQ_STAGE;
+      if (nst >= RQ_FLUSH_AT) {
+        vmem = true;
+        for (int i = lane; i < nst; i += 64) {
+          const unsigned qq = st_q[i];
+          const unsigned pos = atomicAdd(&g_cnt[qq], 1u);
+          if (pos < cap) {
+            hit_s[(size_t)qq * cap + pos] = st_s[i];
+            hit_r[(size_t)qq * cap + pos] = st_r[i];
+          }
+        }
+        nst = 0;
+      }
+      // VMEM operations that hipcc counts itself: drain, so that the DMA arithmetic at the loop top holds (see knn_rq_scan_kernel)
+      if (__builtin_amdgcn_ballot_w64(vmem) != 0ull) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    slot = slot + 1 == NSLOT ? 0 : slot + 1;
+  }
+  // drain the DMAs still in flight (tail reloads) before the LDS is released, then the last staged hits
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  for (int i = lane; i < nst; i += 64) {
+    const unsigned qq = st_q[i];
+    const unsigned pos = atomicAdd(&g_cnt[qq], 1u);
+    if (pos < cap) {
+      hit_s[(size_t)qq * cap + pos] = st_s[i];
+      hit_r[(size_t)qq * cap + pos] = st_r[i];
+    }
+  }
+}
+
 // =============================================================================================
 // int8 first stage (round 4).  The flat index keeps, next to its fp16 rows, an int8 copy x8 = rint(x / c) with one scale per
 // COLUMN (c_j = max_i |x_ij| / 127), and the scan of a query batch reads THAT: half the bytes of a pass over HBM, and
@@ -377,10 +572,10 @@ typedef int i32x4v __attribute__((ext_vector_type(4)));
 
 // column maxima: colmax_enc[j] = max_i |x_ij| as the bits of a non-negative float (integer order = float order)
 __global__ __launch_bounds__(256) void knn_i8_colmax_kernel(const _Float16* __restrict__ X, int64_t N, int d, int* __restrict__ colmax_enc) {
-  // a block walks rows blockIdx.x, + gridDim.x, ...; thread t owns columns 4 t .. 4 t + 3 (one 8-byte load per row; d <= 1024)
-  float m[4] = {0.f, 0.f, 0.f, 0.f};
-  const int c = 4 * threadIdx.x;
-  if (c < d) {
+  // a block walks rows blockIdx.x, + gridDim.x, ...; thread t owns columns 4 t .. 4 t + 3 (one 8-byte load per row) and, beyond d = 1024,
+  // columns 1024 + 4 t .. in a second walk over the same rows
+  for (int c = 4 * threadIdx.x; c < d; c += 4 * 256) {
+    float m[4] = {0.f, 0.f, 0.f, 0.f};
     for (int64_t r = blockIdx.x; r < N; r += gridDim.x) {
       const uint2 raw = *reinterpret_cast<const uint2*>(X + (size_t)r * d + c);
       const _Float16* h = reinterpret_cast<const _Float16*>(&raw);
@@ -485,6 +680,8 @@ __global__ __launch_bounds__(256) void knn_i8_quant_kernel(const _Float16* __res
 // queries: one wave per query slot (grid = queries per pass).  Writes the int8 B fragments (qfrag8 [nblk16][d / 64][64 lanes][16 B]:
 // lane (n = l & 15, q4 = l >> 4) holds u8_n[64 s + 16 q4 .. + 16]), the integer admission threshold thr_i and the exact-score
 // lower bound thr_lb (= T) of the proof; resets the hit counters.  Unused slots: zero fragments, thr_i = INT_MAX.
+// NE = columns per lane (lane + 64 e): 16 up to d = 1024, 20 at d = 1280
+template <int NE>
 __global__ __launch_bounds__(64) void knn_i8_prep_kernel(const float* __restrict__ q, int nq, int d, const float* __restrict__ colscale,
                                                         const I8Dom dom, const int* __restrict__ ab_enc, const int* __restrict__ maxnorm,
                                                         const float* __restrict__ samp, int kw, int J, int planes, int refine,
@@ -512,10 +709,10 @@ __global__ __launch_bounds__(64) void knn_i8_prep_kernel(const float* __restrict
   const int nsl = d / 64;
   int8_t* dst = qfrag8 + ((size_t)(n >> 4) * nsl * 64 + (n & 15)) * 16;  // + (s * 64 + q4 * 16) * 16 + byte
   int8_t* dst2 = dst + (size_t)256 * d;
-  float u[16];  // columns lane + 64 e
+  float u[NE];  // columns lane + 64 e
   float mu = 0.f, mud = 0.f, e2 = 0.f, n2 = 0.f;  // mud: the largest dominant component
 #pragma unroll
-  for (int e = 0; e < 16; ++e) {
+  for (int e = 0; e < NE; ++e) {
     const int c = lane + 64 * e;
     u[e] = 0.f;
     if (c < d && n < nq) {
@@ -533,7 +730,7 @@ __global__ __launch_bounds__(64) void knn_i8_prep_kernel(const float* __restrict
   }
   float nu2 = 0.f;
 #pragma unroll
-  for (int e = 0; e < 16; ++e) nu2 += u[e] * u[e];
+  for (int e = 0; e < NE; ++e) nu2 += u[e] * u[e];
   for (int o = 32; o > 0; o >>= 1) {
     mu = fmaxf(mu, __shfl_xor(mu, o));
     mud = fmaxf(mud, __shfl_xor(mud, o));
@@ -545,8 +742,9 @@ __global__ __launch_bounds__(64) void knn_i8_prep_kernel(const float* __restrict
   // round to zero, eps8 would admit every row and the query would fall back to the exact scan
   const float su = mu > 0.f ? mu / 127.f : (mud > 0.f ? mud / 16256.f : 1.f);
   float er2 = 0.f;
+  float i2 = 0.f, i2b = 0.f;  // (NE > 16, two planes) squared norms of the planes' integers: the int32 range check below
 #pragma unroll
-  for (int e = 0; e < 16; ++e) {
+  for (int e = 0; e < NE; ++e) {
     const int c = lane + 64 * e;
     if (c < d) {
       float v = rintf(u[e] / su);
@@ -571,11 +769,28 @@ __global__ __launch_bounds__(64) void knn_i8_prep_kernel(const float* __restrict
         v2 = fminf(fmaxf(v2, -127.f), 127.f);
         res -= su2 * v2;
         dst2[fo] = (int8_t)(int)v2;
+        if constexpr (NE > 16) {
+          i2 += v * v;
+          i2b += v2 * v2;
+        }
       }
       er2 += res * res;
     }
   }
   for (int o = 32; o > 0; o >>= 1) er2 += __shfl_xor(er2, o);
+  // Two planes: the scan compares 128 * sum(u8 x8) + sum(u8b x8) in int32.  Up to d = 1024 that cannot overflow (128 * 127 * 127 * d <
+  // 2^31); at d = 1280 the worst case can.  |sum(a x8)| <= |a| B for every stored row (Cauchy-Schwarz; B = max |x8_i|), so a query whose
+  // bound reaches 2^31 is marked lost here and takes the exact scan; every other query's integer scores are exact.
+  bool wide_sum = false;
+  if constexpr (NE > 16) {
+    if (planes == 2) {
+      for (int o = 32; o > 0; o >>= 1) {
+        i2 += __shfl_xor(i2, o);
+        i2b += __shfl_xor(i2b, o);
+      }
+      wide_sum = (128.f * sqrtf(i2) + sqrtf(i2b)) * __int_as_float(ab_enc[1]) * 1.001f >= 2.0e9f;
+    }
+  }
   if (qdom && lane < 4 && (lane >= dom.n || n >= nq)) qdom[n * 4 + lane] = qdom[1024 + n * 4 + lane] = 0;
   if (lane == 0) {
     int ti = 0x7fffffff;
@@ -588,7 +803,7 @@ __global__ __launch_bounds__(64) void knn_i8_prep_kernel(const float* __restrict
       } else if (v > -FLT_MAX) {
         // eps_hi: the sample scores are fp16-hi approximations of the exact scores (cf. knn_rq_proof_kernel)
         // Every norm below is an fp32 sum of up to d non-negative terms followed by a square root: relative error <= (d + 2) 2^-24
-        // < 6.2e-5 at d = 1024, and the products / sums of the bound add a few ulp.  The factor 1 + 1e-3 covers all of it with an
+        // < 7.7e-5 at d = 1280 (the widest index), and the products / sums of the bound add a few ulp.  The factor 1 + 1e-3 covers all of it with an
         // order of magnitude to spare (it widens the admission band by 0.1 %); the same factor is in oracle.knn_oracle.Int8FirstStage.
         const float eps_q = (sqrtf(e2) + (float)d * 1.2e-7f * sqrtf(n2)) * rq_dec_f(*maxnorm) * 1.001f;
         const float eps_hi = refine ? 0.f : eps_q;
@@ -613,7 +828,7 @@ __global__ __launch_bounds__(64) void knn_i8_prep_kernel(const float* __restrict
       thr_lb[n] = lb;
     }
     cnt[n] = 0u;
-    lost[n] = 0u;
+    lost[n] = wide_sum ? 1u : 0u;
   }
 }
 
@@ -727,7 +942,12 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void knn_rq8_scan_kernel(const int
 #pragma unroll
     for (int p = 0; p < PL; ++p)
 #pragma unroll
-      for (int s = 0; s < NSL; ++s) asm volatile("" : "+v"(Q[p][b][s]));  // all landed before the DMA ring starts (see knn_rq_scan_kernel)
+      for (int s = 0; s < NSL; ++s) {  // all landed before the DMA ring starts (see knn_rq_scan_kernel)
+        // (two planes at d = 1280: 320 fragment registers -- the second plane lives in AGPRs for good, as the second query block of
+        // knn_rq16_scan_kernel does; the narrower widths keep the code they had)
+        if (PL == 2 && KS > 32 && p == 1) asm volatile("" : "+a"(Q[p][b][s]));
+        else asm volatile("" : "+v"(Q[p][b][s]));
+      }
     asm volatile("" : "+v"(tq[b]));
     if constexpr (DOM) asm volatile("" : "+v"(dlo[b]), "+v"(dhi[b]));
   }
@@ -789,7 +1009,8 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void knn_rq8_scan_kernel(const int
 
     // ---- filter: lane (qcol, hb) owns rows row0 + 16 half + e of its query column in each block; integer compares
     const int64_t row0 = t * tstep * 32 + 4 * hb;
-    // (two planes: |128 * plane 0| <= 128 * 127 * 127 * d < 2^31 at d <= 1024, plane 1 adds at most 127 * 127 * d)
+    // (two planes: |128 * plane 0| <= 128 * 127 * 127 * d < 2^31 at d <= 1024, plane 1 adds at most 127 * 127 * d; at d = 1280
+    // knn_i8_prep_kernel<20> sends a query whose sums could leave the int32 range to the exact scan)
 #define RQ8_SC(b, r) (PL == 2 ? acc[0][b][(r) >> 2][(r) & 3] * 128 + acc[PL - 1][b][(r) >> 2][(r) & 3] : acc[0][b][(r) >> 2][(r) & 3])
     bool any = false;
 #pragma unroll
@@ -892,7 +1113,7 @@ __global__ __launch_bounds__(256) void knn_i8_proof_kernel(int nq, int k, const 
   if (threadIdx.x == 0 && stats) atomicAdd(&stats[0], (unsigned long long)nq);
 }
 
-int i8_supported(int d) { return d == 512 || d == 768 || d == 1024 ? 1 : 0; }
+int i8_supported(int d) { return d == 512 || d == 768 || d == 1024 || d == 1280 ? 1 : 0; }
 
 // quantise rows with the column scales that exist (also used for rows added later: values beyond +-127 c clamp, and A / B -- which
 // are maxima over the rows as stored -- grow with them, so the bound stays a bound)
@@ -925,8 +1146,12 @@ hipError_t launch_i8_prep(const float* q_dev, int nq, int d, const float* colsca
                           const float* samp, int kw, int J, int planes, int refine, int8_t* qfrag8, int8_t* qdom, int* thr_i, float* thr_lb,
                           float* thr_rest, unsigned* cnt, unsigned* lost, hipStream_t st) {
   if (dom.n > 0 && (planes != 1 || !qdom)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(knn_i8_prep_kernel, dim3(256), dim3(64), 0, st, q_dev, nq, d, colscale, dom, ab_enc, maxnorm, samp, kw, J, planes, refine,
-                     qfrag8, qdom, thr_i, thr_lb, thr_rest, cnt, lost);
+  if (d > 1024)
+    hipLaunchKernelGGL(knn_i8_prep_kernel<20>, dim3(256), dim3(64), 0, st, q_dev, nq, d, colscale, dom, ab_enc, maxnorm, samp, kw, J, planes,
+                       refine, qfrag8, qdom, thr_i, thr_lb, thr_rest, cnt, lost);
+  else
+    hipLaunchKernelGGL(knn_i8_prep_kernel<16>, dim3(256), dim3(64), 0, st, q_dev, nq, d, colscale, dom, ab_enc, maxnorm, samp, kw, J, planes,
+                       refine, qfrag8, qdom, thr_i, thr_lb, thr_rest, cnt, lost);
   return hipGetLastError();
 }
 
@@ -964,6 +1189,7 @@ hipError_t launch_rq8_scan(const int8_t* X8, int64_t N, int d, int nq, int plane
       case 512: return launch_rq8_scan_cfg<16, 4, 4, 2>(RQ8_ARGS);
       case 768: return launch_rq8_scan_cfg<24, 4, 4, 2>(RQ8_ARGS);
       case 1024: return launch_rq8_scan_cfg<32, 4, 4, 2>(RQ8_ARGS);
+      case 1280: return launch_rq8_scan_cfg<40, 4, 3, 2>(RQ8_ARGS);  // (a 40 KiB tile: three ring slots + staging = 126 KiB)
       default: return hipErrorInvalidValue;
     }
   }
@@ -974,6 +1200,7 @@ hipError_t launch_rq8_scan(const int8_t* X8, int64_t N, int d, int nq, int plane
       case 512: return qdom ? launch_rq8_scan_cfg<16, 4, 4, 1, true>(RQ8_ARGS) : launch_rq8_scan_cfg<16, 4, 4>(RQ8_ARGS);
       case 768: return qdom ? launch_rq8_scan_cfg<24, 4, 4, 1, true>(RQ8_ARGS) : launch_rq8_scan_cfg<24, 4, 4>(RQ8_ARGS);
       case 1024: return qdom ? launch_rq8_scan_cfg<32, 4, 4, 1, true>(RQ8_ARGS) : launch_rq8_scan_cfg<32, 4, 4>(RQ8_ARGS);
+      case 1280: return qdom ? launch_rq8_scan_cfg<40, 4, 3, 1, true>(RQ8_ARGS) : launch_rq8_scan_cfg<40, 4, 3>(RQ8_ARGS);
       default: return hipErrorInvalidValue;
     }
   }
@@ -981,6 +1208,7 @@ hipError_t launch_rq8_scan(const int8_t* X8, int64_t N, int d, int nq, int plane
     case 512: return qdom ? launch_rq8_scan_cfg<16, 8, 4, 1, true>(RQ8_ARGS) : launch_rq8_scan_cfg<16, 8, 4>(RQ8_ARGS);
     case 768: return qdom ? launch_rq8_scan_cfg<24, 8, 4, 1, true>(RQ8_ARGS) : launch_rq8_scan_cfg<24, 8, 4>(RQ8_ARGS);
     case 1024: return qdom ? launch_rq8_scan_cfg<32, 8, 4, 1, true>(RQ8_ARGS) : launch_rq8_scan_cfg<32, 8, 4>(RQ8_ARGS);
+    case 1280: return qdom ? launch_rq8_scan_cfg<40, 8, 3, 1, true>(RQ8_ARGS) : launch_rq8_scan_cfg<40, 8, 3>(RQ8_ARGS);  // 132 KiB
     default: return hipErrorInvalidValue;
   }
 #undef RQ8_ARGS
@@ -1369,7 +1597,7 @@ __global__ __launch_bounds__(256) void knn_rq_proof_kernel(const float* __restri
 // ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
-int rq_queries_per_pass(int d) { return d == 1024 ? 128 : (d == 512 || d == 768 ? 256 : 0); }
+int rq_queries_per_pass(int d) { return d == 1024 || d == 1280 ? 128 : (d == 512 || d == 768 ? 256 : 0); }
 
 hipError_t launch_rq_prep(const float* q_dev, int nq, int d, _Float16* qfrag, const float* samp, int kw, int J, float slack,
                           float* thr, unsigned* cnt, unsigned* lost, hipStream_t st) {
@@ -1384,6 +1612,19 @@ static hipError_t launch_rq_scan_cfg(const _Float16* X, int64_t N, const _Float1
                                      hipStream_t st, uint32_t row_off) {
   const size_t smem = (size_t)NSLOT * KS * 1024 + (size_t)NW * RQ_STAGE * 12;
   auto kern = knn_rq_scan_kernel<KS, QBW, NW, NSLOT>;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), smem, st, X, N, qfrag, thr, cnt, cap, hit_s, hit_r, lost, gate, row_off);
+  return hipGetLastError();
+}
+
+// d = 1280: the ring of 16-row half tiles (knn_rq16_scan_kernel)
+template <int KS, int NW, int NSLOT>
+static hipError_t launch_rq16_scan_cfg(const _Float16* X, int64_t N, const _Float16* qfrag, const float* thr, unsigned* cnt,
+                                       unsigned cap, float* hit_s, uint32_t* hit_r, unsigned* lost, const unsigned* gate, int grid,
+                                       hipStream_t st, uint32_t row_off) {
+  const size_t smem = (size_t)NSLOT * KS * 512 + (size_t)NW * RQ_STAGE * 12;
+  auto kern = knn_rq16_scan_kernel<KS, NW, NSLOT>;
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), smem, st, X, N, qfrag, thr, cnt, cap, hit_s, hit_r, lost, gate, row_off);
@@ -1412,6 +1653,8 @@ hipError_t launch_rq_scan(const _Float16* X, int64_t N, int d, int nq, const _Fl
     // (round 2 counter run; the file is no longer kept under profiles/).
     case 768: return launch_rq_scan_cfg<48, 1, 8, 3>(X, N, qfrag, thr, cnt, cap, hit_s, hit_r, lost, gate, grid, st, row_off);
     case 1024: return launch_rq_scan_cfg<64, 1, 4, 2>(X, N, qfrag, thr, cnt, cap, hit_s, hit_r, lost, gate, grid, st, row_off);
+    // d = 1280: 4 waves x 32 queries over three 40 KiB slots of 16 rows (a 32-row tile is 80 KiB: two slots and no staging)
+    case 1280: return launch_rq16_scan_cfg<80, 4, 3>(X, N, qfrag, thr, cnt, cap, hit_s, hit_r, lost, gate, grid, st, row_off);
     default: return hipErrorInvalidValue;
   }
 }
@@ -1422,6 +1665,7 @@ hipError_t launch_rq_rescore(const _Float16* X, int d, const float* q, int nq, c
     case 512: hipLaunchKernelGGL(knn_rq_rescore_kernel<8>, dim3(32, nq), dim3(256), 0, st, X, q, cnt, cap, hit_s, hit_r, cntc); break;
     case 768: hipLaunchKernelGGL(knn_rq_rescore_kernel<12>, dim3(32, nq), dim3(256), 0, st, X, q, cnt, cap, hit_s, hit_r, cntc); break;
     case 1024: hipLaunchKernelGGL(knn_rq_rescore_kernel<16>, dim3(32, nq), dim3(256), 0, st, X, q, cnt, cap, hit_s, hit_r, cntc); break;
+    case 1280: hipLaunchKernelGGL(knn_rq_rescore_kernel<20>, dim3(32, nq), dim3(256), 0, st, X, q, cnt, cap, hit_s, hit_r, cntc); break;
     default: return hipErrorInvalidValue;  // rq_queries_per_pass(d) == 0 for every other d: the RQ path is never taken
   }
   return hipGetLastError();

@@ -381,7 +381,7 @@ static int rq_sample_pass(knnx_index* ix, const float* q_dev, int nq, int k, int
   const int d = ix->d;
   const int64_t ntiles = (ix->ntotal + 31) / 32;
   const int tstride = (int)std::max<int64_t>(1, std::min<int64_t>(stride_cap, ntiles / 4096));
-  // (the 64-query wide scan where its LDS queues fit, d <= 768; at d = 1024 the exact 32-query scan, whose scores are exact
+  // (the 64-query wide scan where its LDS queues fit, d <= 768; at d = 1024 and 1280 the exact 32-query scan, whose scores are exact
   // rather than fp16-hi: the threshold then gets a slack of a few eps so that the sample rows themselves still reach it)
   const bool wide_samp = wide_cap(d) > 0;
   const int gsz = wide_samp ? KNN_NQ_MAX : KNN_NQ;
@@ -670,9 +670,13 @@ static Step choose_step(const knnx_index* ix, int remaining, int k) {
   if (ix->sq.on) return {Scan::SQ, std::min(KNN_NQ * std::max(1, std::min(IVFM_BLK, ix->n_cu)), remaining), false};
   if (ivfm_usable(ix, remaining, k)) return {Scan::IVF_MULTI, std::min(IVFM_BLK * KNN_NQ, remaining), false};
   const bool i8 = i8_usable(ix, remaining, k);
+  // d = 1280, measured (DESIGN 4.3 "Width 1280", tools/knn_d1280_batch.py): a step of 25 .. 32 queries is no faster through the int8
+  // stage than through ONE exact 32-query scan (B = 32: 2.33 ms against 2.15 over 4 M rows; B = 24: 2.05 against 2.08), so the exact
+  // scan keeps those steps; every other step size takes the dispatch of the other widths
+  const bool i8_step = i8 && !(ix->d == 1280 && remaining > 24 && remaining <= KNN_NQ);
   // (two planes: four waves x 32 = 128 queries per int8 pass -- a batch of more goes to the fp16 register-stationary pass, 36 ms for
   // 256 against 2 x 19.6)
-  if (i8 && !(ix->i8.planes == 2 && remaining > 128 && rq_usable(ix, remaining, k)))
+  if (i8_step && !(ix->i8.planes == 2 && remaining > 128 && rq_usable(ix, remaining, k)))
     return {Scan::I8, std::min(ix->i8.planes == 2 ? 128 : KNN_RQ_MAX, remaining), i8};
   if (rq_usable(ix, remaining, k)) return {Scan::RQ, std::min(rq_queries_per_pass(ix->d), remaining), i8};
   if (wide_usable(ix, remaining, k)) return {Scan::WIDE, std::min(KNN_NQ_MAX, remaining), i8};

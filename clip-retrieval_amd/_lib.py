@@ -108,6 +108,9 @@ SIGNATURES = {
     "knnx_ivfpq_out_dim": (C.c_int, [_P]),
     "knnx_ivfpq_set_refine": (C.c_int, [_P, C.c_int]),
     "knnx_ivfpq_refine": (C.c_int, [_P]),
+    "knnx_ivfpq_set_refine_sq8": (C.c_int, [_P, _P, _P]),
+    "knnx_ivfpq_refine_kind": (C.c_int, [_P]),
+    "knnx_ivfpq_get_refine_ranges": (C.c_int, [_P, _P, _P]),
     "knnx_ivfpq_set_k_factor": (C.c_int, [_P, C.c_int]),
     "knnx_ivfpq_k_factor": (C.c_int, [_P]),
     "knnx_ivfpq_set_threshold_scan": (C.c_int, [_P, C.c_int]),

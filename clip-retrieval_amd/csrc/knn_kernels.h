@@ -244,6 +244,16 @@ hipError_t launch_pq_refine(const _Float16* X, int d, const float* q, int nq, in
 // the exact scores alone for any kc (the large-k refine search): es [nq][kc], -FLT_MAX where cand holds no id of the index
 hipError_t launch_pq_rescore(const _Float16* X, int d, const float* q, int nq, int64_t id_lo, int64_t n_ids, const uint32_t* inv,
                              const int64_t* cand, int kc, float* es, hipStream_t st);
+// the ranking stage of launch_pq_refine alone: D / I = the top k of es [nq][kc] by (score descending, id ascending), padded
+hipError_t launch_pq_refine_topk(const float* es, const int64_t* cand, int nq, int kc, int k, float* D, int64_t* I, hipStream_t st);
+// Refine store in SQ8 (faiss IndexRefine(IndexIVFPQ, IndexScalarQuantizer(QT_8bit)); knn_pqsq_kernels.hip): the candidates are re-scored
+// from one code byte per column, <q, dec(code)> = b_q + sum_c u_c code_c with the SQ8 contract's u = q * step, b_q = <q, vmin + step / 2>.
+// launch_pqsq_prep: u [nq][d] in plain column order (no scaling) and bq [nq] of the ORIGINAL queries q f32 [nq][d].
+hipError_t launch_pqsq_prep(const float* q, int nq, int d, const float* vmin, const float* step, float* u, float* bq, hipStream_t st);
+// es[q][c] = bq[q] + sum over the code bytes of arena row inv[cand[q][c] - id_lo] (fixed summation order: knnx.h), -FLT_MAX where cand
+// holds no id of the index; any kc >= 1, d in {256, 512, 768, 1024}
+hipError_t launch_pqsq_rescore(const uint8_t* codes, int d, const float* u, const float* bq, int nq, int64_t id_lo, int64_t n_ids,
+                               const uint32_t* inv, const int64_t* cand, int kc, float* es, hipStream_t st);
 // Threshold mode of the ADC scan (pq_range_scan_kernel): every row of the probed lists with score > thr[q] (strict; +INFINITY: the
 // query is skipped) is appended to hit_s / hit_r [q * cap ..] as (score, arena row); cnt[q] (cleared by the launcher) counts the hits
 // exactly even when more than cap of them exist.  Scores are those of launch_pq_adc_scan, bit for bit.

@@ -1183,6 +1183,13 @@ hipError_t launch_pq_refine(const _Float16* X, int d, const float* q, int nq, in
   if (kc < 1 || kc > PQ_REFINE_MAX || k < 1 || k > kc) return hipErrorInvalidValue;
   hipError_t e = launch_pq_rescore(X, d, q, nq, id_lo, n_ids, inv, cand, kc, es, st);
   if (e != hipSuccess) return e;
+  return launch_pq_refine_topk(es, cand, nq, kc, k, D, I, st);
+}
+
+// the ranking stage alone (the SQ8 refine store scores its candidates with kernels of its own: knn_pqsq_kernels.hip)
+hipError_t launch_pq_refine_topk(const float* es, const int64_t* cand, int nq, int kc, int k, float* D, int64_t* I, hipStream_t st) {
+  if (nq <= 0) return hipSuccess;
+  if (kc < 1 || kc > PQ_REFINE_MAX || k < 1 || k > kc) return hipErrorInvalidValue;
   hipLaunchKernelGGL(pq_refine_topk_kernel, dim3((unsigned)nq), dim3(256), 0, st, es, cand, kc, k, D, I);
   return hipGetLastError();
 }

@@ -27,27 +27,13 @@
 #include <algorithm>
 #include "knn_kernels.h"
 #include "knn_scan_shared.h"
+#include "knn_sq_arith.h"
 
 namespace knnx {
 
 typedef uint32_t uint4v __attribute__((ext_vector_type(4)));
 
-// The contract fixes where every rounding falls (encode: subtract, then multiply; decode and score: multiply, then add).  hipcc
-// contracts a * b + c into one fma by default, so these pin the two-rounding forms.
-__device__ __forceinline__ float sq_mul(float a, float b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
-__device__ __forceinline__ float sq_mul_add(float a, float b, float c) {  // c + round(a * b)
-#pragma clang fp contract(off)
-  const float p = a * b;
-  return c + p;
-}
-__device__ __forceinline__ float sq_sub_mul(float a, float b, float c) {  // round(a - b) * c
-#pragma clang fp contract(off)
-  const float t = a - b;
-  return t * c;
-}
+// (sq_mul, sq_mul_add, sq_sub_mul -- the two-rounding forms the contract fixes: knn_sq_arith.h)
 
 // ---------------------------------------------------------------------------------------------
 // query preparation: u = q * step in the scan's column order, scaled; b_q; 1 / scale

@@ -46,6 +46,7 @@ int hip_fail(const char* who, hipError_t e) {
 
 // an index that can grow: built, IVF, owning its rows
 int grow_refuse(const knnx_index* ix, const char* who) {
+  if (const int r = pq_refine_sq8_refuse(ix, who)) return r;
   if (ix->ivfb.nlist)
     return fail(KNNX_E_ARG, std::string(who) + ": the index is between knnx_ivf_begin and knnx_ivf_end (finish the build first; nothing was added)");
   if (!ix->ivf_nlist || !ix->cent) return fail(KNNX_E_ARG, std::string(who) + ": not a built IVF index (nothing was added)");
@@ -351,6 +352,9 @@ extern "C" int knnx_ivf_merge_from(knnx_index* ix, knnx_index* other) {
   const char* who = "knnx_ivf_merge_from";
   if (!ix || !other) return fail(KNNX_E_ARG, std::string(who) + ": index is null");
   if (ix == other) return fail(KNNX_E_ARG, std::string(who) + ": an index cannot be merged into itself (nothing was added)");
+  // (either side with the sq8 refine store: refused here, before a byte of `other` is staged; the flag is settled before the build)
+  if (const int r0 = pq_refine_sq8_refuse(ix, who)) return r0;
+  if (const int r0 = pq_refine_sq8_refuse(other, std::string(who) + " (other)")) return r0;
   MergeSrc M;
   int r;
   {  // ---- other, under its own lock: its description and every row in arena order, staged on the host.  It is left untouched.

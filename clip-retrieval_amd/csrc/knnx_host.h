@@ -296,6 +296,14 @@ struct PqData {
   // refine store (knnx_ivfpq_set_refine): the fp16 rows as they entered the build, un-rotated, in the arena order of the codes.
   // They live in knnx_index::rows ([capacity][d], allocated by knnx_ivf_begin); ivf.idmap / ivf.inv serve codes and rows alike.
   bool refine = false;
+  // refine store in SQ8 (knnx_ivfpq_set_refine_sq8; exclusive with `refine`): ONE byte per column of the un-rotated row in an arena of
+  // its own, [capacity][d] in the arena order of the codes, encoded / decoded by the IVF-SQ8 contract (`rows` stays null)
+  struct RefineSq8 {
+    bool on = false;
+    std::vector<float> vmin_h, vdiff_h;  // the ranges as they were given (knnx_ivfpq_get_refine_ranges)
+    DevBuf<float> vmin, scale, step;     // [d]; scale = 255 / vdiff and step = vdiff / 255 from the host, 0 where vdiff == 0
+    DevBuf<uint8_t> codes;               // [capacity][d]
+  } rsq;
   int k_factor = 1;                      // candidates per result of a refine search (knnx_ivfpq_set_k_factor)
   ThrState thr;                          // threshold mode of the ADC scan
   // M = 256 (the two-half ADC scan, knnx_pq_plan.h): the budget of the partial-sum buffer (KNNX_PQ_PARTIAL_MAX_BYTES, read by
@@ -327,6 +335,17 @@ struct PqScratch {
   DevBuf<float> rpart_s;    // [PQ_SLOTS][PQ_REFINE_MAX]
   DevBuf<uint32_t> rpart_r;
   DevBuf<float> rdc;        // [256][64]
+  // SQ8 refine store only (allocated by its first search): u = q * step of the pass's ORIGINAL queries and their b_q
+  DevBuf<float> ru;         // [256][d]
+  DevBuf<float> rbq;        // [256]
+  hipError_t alloc_refine_sq8(int d) {
+    if (ru) return hipSuccess;
+    hipError_t e = hipSuccess;
+    dev_alloc(e, ru, (size_t)PQ_PASS * d);
+    dev_alloc(e, rbq, (size_t)PQ_PASS);
+    if (e != hipSuccess) ru.reset(), rbq.reset();
+    return e;
+  }
   // M = 256 only (the two-half ADC scan): the row offset of every probe in its query's slab, written by pq_front; the partial sums
   // of the sub-group being scored, allocated on first use (knnx_ivfpq.hip: pq_half_buffer).  half_nq = n > 0: the buffer holds the
   // sums of all n queries of the pass whose front half is in here (one sub-group) -- cleared by pq_front, so they never outlive it.
@@ -612,8 +631,11 @@ int ivf_swap_in(knnx_index* ix, IvfLayout& L, DevBuf<uint4>& work, DevBuf<uint8_
 int scan_topk_pq(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out, int64_t* I_out, hipStream_t st);
 const ThrPass& pq_thr_pass();
 // decoded rows of n ids (device) -> out f32 [n][d] in the ORIGINAL space (back-rotated when the index has a rotation; scratch slot 5);
-// on an index with a refine store: the stored rows themselves
+// on an index with a refine store: the stored rows themselves (fp16 store), the decoded SQ8 rows (sq8 store)
 int pq_decode_rows(knnx_index* ix, const int64_t* ids_dev, int64_t n, float* out_dev, hipStream_t st);
+// what the sq8 refine store does not serve yet (append, merge, remove, shards, threshold mode, search_filtered): 0, or
+// KNNX_E_UNSUPPORTED with a message that names the store.  Host only: called before any HIP call of `who`.
+int pq_refine_sq8_refuse(const knnx_index* ix, const std::string& who);
 
 // knnx_ivfsq.hip
 int scan_topk_sq(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out, int64_t* I_out, hipStream_t st);

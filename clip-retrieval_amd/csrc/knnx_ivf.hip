@@ -488,6 +488,10 @@ extern "C" int knnx_ivf_begin(knnx_index* ix, int nlist, const uint16_t* centroi
       if (e == hipSuccess) e = malloc_or_reclaim(ix, ix->rows, (size_t)prow * ix->d);
       if (e == hipSuccess) e = hipMemsetAsync(ix->rows, 0, (size_t)prow * ix->d * sizeof(_Float16), ix->stream);
     }
+    if (ix->pq.rsq.on) {  // ... or its sq8 form: d code bytes per arena row (pad rows are zero)
+      if (e == hipSuccess) e = malloc_or_reclaim(ix, ix->pq.rsq.codes, (size_t)prow * ix->d);  // (the route of the fp16 store's arena)
+      if (e == hipSuccess) e = hipMemsetAsync(ix->pq.rsq.codes, 0, (size_t)prow * ix->d, ix->stream);
+    }
   } else if (ix->sq.on) {  // IVF-SQ8: d code bytes per arena row (pad rows are zero)
     dev_alloc(e, ix->sq.codes, (size_t)prow * ix->d);
     if (e == hipSuccess) e = hipMemsetAsync(ix->sq.codes, 0, (size_t)prow * ix->d, ix->stream);
@@ -510,6 +514,7 @@ extern "C" int knnx_ivf_begin(knnx_index* ix, int nlist, const uint16_t* centroi
     ix->rows.reset();
     ix->pq.codes.reset();
     ix->pq.bcent.reset();
+    ix->pq.rsq.codes.reset();
     ix->sq.codes.reset();
     return fail(e == hipErrorOutOfMemory ? KNNX_E_NOMEM : KNNX_E_HIP, std::string("ivf_begin: ") + hipGetErrorString(e));
   }
@@ -631,6 +636,9 @@ extern "C" int knnx_ivf_add_assigned(knnx_index* ix, const uint16_t* rows_f16, i
       if (ix->pq.refine)
         HIPCHK(launch_ivf_scatter(ix->ivfb.rows, m, ix->d, ix->ivfb.lists, ix->ivfb.pos, ix->ivfb.ids, 0, ix->ivf.tile0, ix->id_base,
                                   ix->ivfb.total, ix->rows, ix->ivf.idmap, ix->ivf.inv, ix->stream));
+      if (ix->pq.rsq.on)  // the sq8 store: the un-rotated rows encoded into the same slots (idmap / inv are laid down by the PQ encoder)
+        HIPCHK(launch_sq_encode(ix->ivfb.rows, m, ix->d, ix->ivfb.lists, ix->ivfb.pos, ix->ivfb.ids, 0, ix->ivf.tile0, ix->id_base,
+                                ix->ivfb.total, ix->pq.rsq.vmin, ix->pq.rsq.scale, ix->pq.rsq.codes, nullptr, nullptr, ix->stream));
       if (ix->pq.rot) HIPCHK(launch_rotate_f16(ix->pq.rot_w, ix->d, pq_dq(ix), ix->ivfb.rows, m, ix->ivfb.rot, ix->stream));
       HIPCHK(launch_pq_encode(ix->pq.rot ? ix->ivfb.rot.p : ix->ivfb.rows.p, m, pq_dq(ix), ix->pq.m, ix->ivfb.lists, ix->pq.bcent, ix->pq.cb,
                               ix->ivf.tile0, ix->ivfb.pos, ix->ivfb.ids, 0, ix->id_base, ix->ivfb.total,
@@ -700,6 +708,9 @@ extern "C" int knnx_ivf_add_assigned_device(knnx_index* ix, const void* rows_dev
       if (ix->pq.refine)
         HIPCHK(launch_ivf_scatter(src, m, ix->d, lists_dev + o, ix->ivfb.pos, nullptr, id0 + o, ix->ivf.tile0, ix->id_base, ix->ivfb.total,
                                   ix->rows, ix->ivf.idmap, ix->ivf.inv, ix->stream));
+      if (ix->pq.rsq.on)
+        HIPCHK(launch_sq_encode(src, m, ix->d, lists_dev + o, ix->ivfb.pos, nullptr, id0 + o, ix->ivf.tile0, ix->id_base, ix->ivfb.total,
+                                ix->pq.rsq.vmin, ix->pq.rsq.scale, ix->pq.rsq.codes, nullptr, nullptr, ix->stream));
       if (ix->pq.rot) HIPCHK(launch_rotate_f16(ix->pq.rot_w, ix->d, pq_dq(ix), src, m, ix->ivfb.rot, ix->stream));
       HIPCHK(launch_pq_encode(ix->pq.rot ? ix->ivfb.rot.p : src, m, pq_dq(ix), ix->pq.m, lists_dev + o, ix->pq.bcent, ix->pq.cb, ix->ivf.tile0, ix->ivfb.pos,
                               nullptr, id0 + o, ix->id_base, ix->ivfb.total, ix->pq.codes, ix->ivf.idmap, ix->ivf.inv, ix->stream));

@@ -5,6 +5,8 @@
 #include "knnx_pq_plan.h"
 #include "knnx_rot_shape.h"
 
+#include <math.h>
+
 // ---------------------------------------------------------------------------------------------
 // IVF-PQ pass of 1 .. 256 queries already in HBM (csrc/knn_pq_kernels.hip): the coarse quantiser of the multi-block IVF pass
 // (one score dump over the centroids + the radix select of ivf_select_mark_kernel: the nprobe largest <q, c>, ties to the lower
@@ -149,11 +151,14 @@ static int pq_stage_topk(knnx_index* ix, int nq, int np, int nsplit, int k, floa
 // Refine store (knnx_ivfpq_set_refine): the ADC stage keeps kc = k x k_factor candidates instead of k -- for kc <= 64 the scan and
 // merge above, for more the workgroup-queue scan and the LDS selection (pq_cand_scan_kernel, pq_cand_select_kernel) with the
 // shares capped so that shares x kc <= PQ_SEL_MAX -- and the candidates are re-scored from the fp16 rows with the ORIGINAL query
-// (pq_rescore_kernel) and ranked (pq_refine_topk_kernel).
+// (pq_rescore_kernel) and ranked (pq_refine_topk_kernel).  The sq8 store (knnx_ivfpq_set_refine_sq8) shares the candidate stage and the
+// ranking; in between its candidates are re-scored from their code bytes (knn_pqsq_kernels.hip: pqsq_prep_kernel of the ORIGINAL queries,
+// pqsq_rescore_kernel).
 int scan_topk_pq(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out, int64_t* I_out, hipStream_t st) {
   if (nq < 1 || nq > PQ_PASS || k < 1 || k > KNNX_MAX_K_FAST || !ix->cent || !ix->ivf_nlist)
     return fail(KNNX_E_STATE, "internal: IVF-PQ pass misuse");
-  const int kc = ix->pq.refine ? k * ix->pq.k_factor : k;
+  const bool sq8 = ix->pq.rsq.on, refine = ix->pq.refine || sq8;
+  const int kc = refine ? k * ix->pq.k_factor : k;
   if (kc > PQ_REFINE_MAX)
     return fail(KNNX_E_ARG, "k x k_factor = " + std::to_string(k) + " x " + std::to_string(ix->pq.k_factor) + " exceeds " +
                                 std::to_string(PQ_REFINE_MAX) + " candidates per query");
@@ -161,9 +166,10 @@ int scan_topk_pq(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out
   int r = pq_front(ix, q_orig, nq, st);
   if (r) return r;
   const int np = ix->pqs.np;
-  if (ix->pq.refine) HIPCHK(ix->pqs.alloc_refine());
+  if (refine) HIPCHK(ix->pqs.alloc_refine());
+  if (sq8) HIPCHK(ix->pqs.alloc_refine_sq8(ix->d));
   int nsplit = pq_nsplit(np, nq);
-  if (ix->pq.refine) {
+  if (refine) {
     PqScratch& S = ix->pqs;
     HIPCHK(ix->prof.begin(ix->prof.on, st));
     if (kc <= PQ_MAX_K) {
@@ -181,7 +187,14 @@ int scan_topk_pq(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out
       }
       HIPCHK(launch_pq_cand_select(S.rpart_s, S.rpart_r, S.part_n, nsplit, nq, kc, ix->ivf.idmap, S.rcand, st));
     }
-    HIPCHK(launch_pq_refine(ix->rows, ix->d, q_orig, nq, ix->id_base, ix->ntotal, ix->ivf.inv, S.rcand, kc, k, S.rscore, D_out, I_out, st));
+    if (sq8) {
+      const PqData::RefineSq8& R = ix->pq.rsq;
+      HIPCHK(launch_pqsq_prep(q_orig, nq, ix->d, R.vmin, R.step, S.ru, S.rbq, st));
+      HIPCHK(launch_pqsq_rescore(R.codes, ix->d, S.ru, S.rbq, nq, ix->id_base, ix->ntotal, ix->ivf.inv, S.rcand, kc, S.rscore, st));
+      HIPCHK(launch_pq_refine_topk(S.rscore, S.rcand, nq, kc, k, D_out, I_out, st));
+    } else {
+      HIPCHK(launch_pq_refine(ix->rows, ix->d, q_orig, nq, ix->id_base, ix->ntotal, ix->ivf.inv, S.rcand, kc, k, S.rscore, D_out, I_out, st));
+    }
     HIPCHK(ix->prof.end(ix->prof.on, st));
     return 0;
   }
@@ -259,7 +272,13 @@ const ThrPass& pq_thr_pass() {
   return P;
 }
 
-extern "C" int knnx_ivfpq_set_threshold_scan(knnx_index* ix, int on) { return thr_set_switch(ix, pq_thr_pass(), on); }
+extern "C" int knnx_ivfpq_set_threshold_scan(knnx_index* ix, int on) {
+  if (ix && on) {  // (off is what such an index has anyway)
+    const int r = pq_refine_sq8_refuse(ix, "the threshold scan (k > 64, range_search)");
+    if (r) return r;
+  }
+  return thr_set_switch(ix, pq_thr_pass(), on);
+}
 extern "C" int knnx_ivfpq_threshold_scan(const knnx_index* ix) { return thr_switch(ix, pq_thr_pass()); }
 extern "C" int knnx_ivfpq_threshold_stats(knnx_index* ix, int64_t* queries, int64_t* launches, int64_t* query_scans, int64_t* hits) {
   return thr_stats(ix, pq_thr_pass(), queries, launches, query_scans, hits);
@@ -316,10 +335,69 @@ extern "C" int knnx_ivfpq_set_refine(knnx_index* ix, int on) {
   std::lock_guard<std::mutex> lk(ix->mu);
   if (!ix->pq.m || ix->ntotal != 0 || ix->ivf_nlist || ix->ivfb.nlist)
     return fail(KNNX_E_STATE, "the refine store is chosen on an IVF-PQ index after knnx_ivfpq_set_quantizer and before knnx_ivf_begin");
+  if (on && ix->pq.rsq.on) return fail(KNNX_E_STATE, "the index already has the sq8 refine store (knnx_ivfpq_set_refine_sq8): an index keeps one kind");
   ix->pq.refine = on != 0;
   return KNNX_OK;
 }
 extern "C" int knnx_ivfpq_refine(const knnx_index* ix) { return ix && ix->pq.refine ? 1 : 0; }
+
+// ---- refine store in SQ8 (faiss IndexRefine(IndexIVFPQ, IndexScalarQuantizer(QT_8bit)), ",Refine(SQ8)"): one code byte per column of the
+// un-rotated row next to the M code bytes.  The ranges are those of the ORIGINAL rows; scale and step as knnx_ivfsq_set_quantizer derives them.
+int pq_refine_sq8_refuse(const knnx_index* ix, const std::string& who) {
+  if (!ix->pq.rsq.on) return 0;
+  return fail(KNNX_E_UNSUPPORTED, who + " is not supported on an IVF-PQ index with the sq8 refine store (knnx_ivfpq_set_refine_sq8)");
+}
+
+extern "C" int knnx_ivfpq_set_refine_sq8(knnx_index* ix, const float* vmin, const float* vdiff) {
+  if (!ix || !vmin || !vdiff) return fail(KNNX_E_ARG, "bad ivfpq_set_refine_sq8 arguments");
+  const int d = ix->d;
+  for (int j = 0; j < d; ++j)
+    if (!isfinite(vmin[j]) || !isfinite(vdiff[j]) || vdiff[j] < 0.f)
+      return fail(KNNX_E_ARG, "the sq8 refine store needs finite vmin and finite vdiff >= 0 (column " + std::to_string(j) + ")");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  if (!ix->pq.m || ix->ntotal != 0 || ix->ivf_nlist || ix->ivfb.nlist)
+    return fail(KNNX_E_STATE, "the sq8 refine store is chosen on an IVF-PQ index after knnx_ivfpq_set_quantizer and before knnx_ivf_begin");
+  if (ix->pq.refine) return fail(KNNX_E_STATE, "the sq8 refine store cannot join the fp16 refine store (knnx_ivfpq_set_refine): an index keeps one kind");
+  if (ix->pq.rsq.on) return fail(KNNX_E_STATE, "the sq8 refine store is set once");
+  if (ix->pq.thr.on)
+    return fail(KNNX_E_UNSUPPORTED, "the sq8 refine store is not supported on an IVF-PQ index with the threshold scan switched on");
+  if (set_dev(ix)) return KNNX_E_HIP;
+  // scale and step in fp32 with IEEE division, here on the host: what numpy float32 computes, bit for bit
+  std::vector<float> scale((size_t)d), step((size_t)d);
+  for (int j = 0; j < d; ++j) {
+    const float vd = vdiff[j];
+    scale[j] = vd == 0.f ? 0.f : 255.f / vd;
+    step[j] = vd / 255.f;
+  }
+  PqData::RefineSq8& R = ix->pq.rsq;
+  hipError_t e = hipSuccess;
+  dev_alloc(e, R.vmin, (size_t)d);
+  dev_alloc(e, R.scale, (size_t)d);
+  dev_alloc(e, R.step, (size_t)d);
+  if (e == hipSuccess) e = hipMemcpy(R.vmin, vmin, (size_t)d * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(R.scale, scale.data(), (size_t)d * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(R.step, step.data(), (size_t)d * sizeof(float), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    R = PqData::RefineSq8();
+    return fail(e == hipErrorOutOfMemory ? KNNX_E_NOMEM : KNNX_E_HIP, std::string("ivfpq_set_refine_sq8: ") + hipGetErrorString(e));
+  }
+  R.vmin_h.assign(vmin, vmin + d);
+  R.vdiff_h.assign(vdiff, vdiff + d);
+  R.on = true;
+  return KNNX_OK;
+}
+
+extern "C" int knnx_ivfpq_refine_kind(const knnx_index* ix) { return !ix ? 0 : ix->pq.rsq.on ? 2 : ix->pq.refine ? 1 : 0; }
+
+extern "C" int knnx_ivfpq_get_refine_ranges(knnx_index* ix, float* vmin, float* vdiff) {
+  if (!ix || !vmin || !vdiff) return fail(KNNX_E_ARG, "bad ivfpq_get_refine_ranges arguments");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  if (!ix->pq.rsq.on) return fail(KNNX_E_STATE, "not an IVF-PQ index with the sq8 refine store");
+  memcpy(vmin, ix->pq.rsq.vmin_h.data(), (size_t)ix->d * sizeof(float));
+  memcpy(vdiff, ix->pq.rsq.vdiff_h.data(), (size_t)ix->d * sizeof(float));
+  return KNNX_OK;
+}
 
 extern "C" int knnx_ivfpq_set_k_factor(knnx_index* ix, int k_factor) {
   if (!ix) return fail(KNNX_E_ARG, "index is null");
@@ -338,6 +416,7 @@ extern "C" int knnx_ivfpq_arena_bytes(knnx_index* ix, int64_t* code_bytes, int64
   if (!ix->pq.m) return fail(KNNX_E_STATE, "not an IVF-PQ index");
   *code_bytes = ix->pq.codes ? ix->capacity * (int64_t)ix->pq.m : 0;
   *row_bytes = ix->pq.refine && ix->rows ? ix->capacity * (int64_t)ix->d * 2 : 0;
+  if (ix->pq.rsq.on && ix->pq.rsq.codes) *row_bytes = ix->capacity * (int64_t)ix->d;  // the sq8 store: one byte per column
   return KNNX_OK;
 }
 
@@ -439,6 +518,11 @@ int pq_decode_rows(knnx_index* ix, const int64_t* ids_dev, int64_t n, float* out
     HIPCHK(launch_gather_inv(ix->rows, ix->d, ix->id_base, ix->ntotal, ix->ivf.inv, ids_dev, n, out_dev, st));
     return KNNX_OK;
   }
+  if (ix->pq.rsq.on) {  // the sq8 store asked the same way: its decoded rows, in the original space
+    const PqData::RefineSq8& R = ix->pq.rsq;
+    HIPCHK(launch_sq_decode(R.codes, ix->d, R.vmin, R.step, ix->id_base, ix->ntotal, ix->ivf.inv, ids_dev, n, out_dev, st));
+    return KNNX_OK;
+  }
   const int dq = pq_dq(ix);  // the decode is dq wide; A^T brings it back to d (without a rotation dq = d: knnx_ivf_begin saw to it)
   float* dec = out_dev;
   if (ix->pq.rot) {
@@ -476,7 +560,7 @@ extern "C" int knnx_ivfpq_add_codes(knnx_index* ix, const uint8_t* codes, int64_
   std::lock_guard<std::mutex> lk(ix->mu);
   if (set_dev(ix)) return KNNX_E_HIP;
   if (!ix->pq.m || !ix->ivfb.nlist) return fail(KNNX_E_STATE, "set the PQ quantizer and call knnx_ivf_begin first");
-  if (ix->pq.refine) return fail(KNNX_E_STATE, "an index with a refine store takes rows (knnx_ivf_add_assigned), not codes: it has no rows to store");
+  if (ix->pq.refine || ix->pq.rsq.on) return fail(KNNX_E_STATE, "an index with a refine store takes rows (knnx_ivf_add_assigned), not codes: it has no rows to store");
   return ivf_import_codes_locked(ix, ix->pq.codes, ix->pq.m, codes, n, ids, lists, pos);
 }
 

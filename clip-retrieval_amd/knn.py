@@ -20,11 +20,11 @@ from .knn_build import (FolderRows, _add_assigned_chunks, _assign_chunks, _downl
 from .knn_index import (_SCAN_QUERIES, METRIC_INNER_PRODUCT, Mi355xIndex, ShardedMi355xIndex, _as_queries, _FaissShaped, _map_ids_call,
                         _own_handle, _pad_rotation, _shard_handles, _threshold_scan_property, _threshold_stats, get_old_to_new_mapping,
                         search_to_new_ids)
-from .knn_store import (IVF_FORMAT, IVF_MANIFEST, IVFPQ_FORMAT, IVFPQ_MANIFEST, IVFPQ_ROTATION, IVFSQ_FORMAT, IVFSQ_MANIFEST,
+from .knn_store import (IVF_FORMAT, IVF_MANIFEST, IVFPQ_FORMAT, IVFPQ_MANIFEST, IVFPQ_REFINE_RANGES, IVFPQ_ROTATION, IVFSQ_FORMAT, IVFSQ_MANIFEST,
                         _add_code_chunks, _ivfpq_from_codes, _ivfpq_refine_from_rows, _ivfsq_from_codes, _load_ivf_index, _load_ivfpq_index,
                         _load_ivfsq_index, _save_ivfpq_index, _save_ivfsq_index, _split_saved_rows, check_ivfsq_manifest, ivfpq_out_dim_entry,
                         ivfpq_threshold_scan_entry, ivfsq_manifest, ivfsq_threshold_scan_entry, load_index, read_ivf_manifest,
-                        read_ivfpq_out_dim, read_ivfpq_refine, read_ivfpq_rotation, read_ivfpq_threshold_scan, read_ivfsq_threshold_scan,
+                        read_ivfpq_out_dim, read_ivfpq_refine, read_ivfpq_refine_kind, read_ivfpq_rotation, read_ivfpq_threshold_scan, read_ivfsq_threshold_scan,
                         read_threshold_scan, save_index, threshold_scan_entry)
 from .knn_train import (OPQ_SAMPLE_ROWS, PQ_SAMPLE_ROWS, IvfBuilder, PqBuilder, _check_opq_dim, _f16_padded, _resolve_rotation,
                         _rotation_out_dim, ivfpq_params_from_index_key, ivfsq_params_from_index_key, opq_embedding, opq_initial_rotation,

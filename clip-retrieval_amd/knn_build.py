@@ -365,6 +365,19 @@ def build_ivf_index_from_folder(path, nlist, nprobe=16, niter=8, seed=0, device=
     return _scatter_into_ivf(src, lo, hi, np.asarray(centroids).astype(np.float16), None, nprobe, device, chunk)
 
 
+def _refine_arg(refine, refine_ranges, train_ranges):
+    """refine= / refine_ranges= of build_ivfpq_index* -> what _ivfpq_begin takes: False, True (the fp16 store) or ("sq8", (vmin, vdiff))
+    for the SQ8 store (faiss ",Refine(SQ8)"), whose ranges -- over the ORIGINAL rows -- come from train_ranges() unless they are given."""
+    if isinstance(refine, str):
+        if refine != "sq8":
+            raise ValueError(f"refine must be False, True (the fp16 store) or \"sq8\", got {refine!r}")
+        vmin, vdiff = train_ranges() if refine_ranges is None else refine_ranges
+        return "sq8", (np.asarray(vmin, dtype=np.float32), np.asarray(vdiff, dtype=np.float32))
+    if refine_ranges is not None:
+        raise ValueError("refine_ranges belongs to refine=\"sq8\"")
+    return bool(refine)
+
+
 def _ivfpq_begin(d, nlist, M, centroids, codebooks, sizes, device, id_base, rotation=None, refine=False, k_factor=1, threshold_scan=False):
     index = Mi355xIndex(d, device=device, id_base=id_base)
     dq = _rotation_out_dim(rotation, d)
@@ -373,7 +386,9 @@ def _ivfpq_begin(d, nlist, M, centroids, codebooks, sizes, device, id_base, rota
     index.set_pq_quantizer(M, codebooks)
     if rotation is not None:
         index.set_pq_rotation(rotation)
-    if refine:
+    if isinstance(refine, tuple):  # ("sq8", (vmin, vdiff)): _refine_arg
+        index.set_pq_refine_sq8(*refine[1])
+    elif refine:
         index.set_pq_refine()
     index.k_factor = k_factor
     if threshold_scan:  # (off is the state of a new index: nothing is called for it)
@@ -405,16 +420,20 @@ def _ivfpq_from_chunks(chunks, n, d, nlist, M, centroids, codebooks, nprobe, dev
 
 
 def build_ivfpq_index(x_f16, nlist, M, nprobe=16, niter=8, pq_niter=10, seed=0, device=0, id_base=0, centroids=None, codebooks=None,
-                      chunk=1 << 20, opq=False, rotation=None, refine=False, k_factor=1, threshold_scan=False, opq_dim=None):
+                      chunk=1 << 20, opq=False, rotation=None, refine=False, k_factor=1, threshold_scan=False, opq_dim=None,
+                      refine_ranges=None):
     """fp16 rows [N, d] -> HBM-resident IVF-PQ index (ids = id_base + row number).  Trains (train_ivfpq) unless both `centroids` and
     `codebooks` are given; lists by the MFMA assignment kernel; codes by the device encoder.
     opq=True trains an OPQ rotation first (train_opq), rotation=A uses that one; centroids / codebooks, given or trained, are those of
     the rotated space.  The index keeps the rotation: it is searched with, and reconstructs, un-rotated vectors.
     refine=True keeps the fp16 rows next to the codes (Mi355xIndex.set_pq_refine) and re-scores k x k_factor candidates exactly.
+    refine="sq8" keeps one SQ8 code byte per column instead (Mi355xIndex.set_pq_refine_sq8: M + d bytes per row, not M + 2 d) and
+    re-scores from those; refine_ranges=(vmin, vdiff), f32 [d] over the un-rotated rows, are trained on the rows (train_sq_ranges) unless given.
     threshold_scan=True switches on k > 64 and range_search (Mi355xIndex.pq_threshold_scan; off by default).
     opq_dim=d_out with opq=True, or a rotation [d_out, d]: the rotation leads into a WIDER space (faiss OPQ{M}_{d_out}; d and d_out
     multiples of 256, d < d_out <= 1024) where centroids, codebooks and codes live; queries, reconstruct and the refine store stay d wide."""
     n, d = x_f16.shape
+    refine = _refine_arg(refine, refine_ranges, lambda: train_sq_ranges(x_f16, device=device, chunk=chunk))
     A, _ = _resolve_rotation(x_f16, M, opq, rotation, seed, device, opq_dim)
     if centroids is None or codebooks is None:
         centroids, codebooks = train_ivfpq(x_f16, nlist, M, niter=niter, pq_niter=pq_niter, seed=seed, device=device, centroids=centroids,
@@ -425,18 +444,27 @@ def build_ivfpq_index(x_f16, nlist, M, nprobe=16, niter=8, pq_niter=10, seed=0, 
 
 def build_ivfpq_index_from_folder(path, nlist, M, nprobe=16, niter=8, pq_niter=10, seed=0, device=0, centroids=None, codebooks=None,
                                   max_points_per_centroid=256, chunk=1 << 20, opq=False, rotation=None, refine=False, k_factor=1,
-                                  threshold_scan=False, opq_dim=None):
+                                  threshold_scan=False, opq_dim=None, refine_ranges=None):
     """`clip inference` output folder (img_emb_*.npy) -> IVF-PQ index, streaming the partitions: training on a strided sample of the
     whole folder, then one assignment pass and one encoding pass.  The result can be save_index()ed (self-contained).  opq / rotation
-    as in build_ivfpq_index (the rotation is trained on the same strided sample).  refine / k_factor as in build_ivfpq_index; a saved
+    as in build_ivfpq_index (the rotation is trained on the same strided sample).  refine / k_factor / refine_ranges as in
+    build_ivfpq_index (the ranges of refine="sq8" are trained on a strided sample of the folder); a saved
     refine index is loaded from its folder PLUS these embeddings (save_index(index, folder, embeddings_folder=...)).  threshold_scan as
     in build_ivfpq_index; save_index records it.  opq_dim as in build_ivfpq_index."""
     src = path if isinstance(path, FolderRows) else FolderRows(path)
+    taken = []
+
+    def sample_rows():  # the strided training sample of the folder, read once for whoever trains on it
+        if not taken:
+            taken.append(_folder_sample(src, min(src.n, max(int(nlist) * int(max_points_per_centroid), PQ_SAMPLE_ROWS))))
+        return taken[0]
+
+    refine = _refine_arg(refine, refine_ranges, lambda: train_sq_ranges(sample_rows(), device=device, chunk=chunk))
     A = None if rotation is None else _resolve_rotation(None, M, opq, rotation, seed, device, opq_dim)[0]
     if opq_dim is not None and A is None and not opq:
         raise ValueError("opq_dim needs opq=True or rotation=")
     if centroids is None or codebooks is None or (opq and A is None):
-        sample = _folder_sample(src, min(src.n, max(int(nlist) * int(max_points_per_centroid), PQ_SAMPLE_ROWS)))
+        sample = sample_rows()
         A, _ = _resolve_rotation(sample, M, opq, A, seed, device, opq_dim)
         if centroids is None or codebooks is None:
             centroids, codebooks = train_ivfpq(sample, nlist, M, niter=niter, pq_niter=pq_niter, seed=seed, device=device,
@@ -449,7 +477,8 @@ def build_ivfpq_index_from_folder(path, nlist, M, nprobe=16, niter=8, pq_niter=1
 
 def build_ivfpq_index_device(fill_rows, n, d, nlist, M, nprobe=16, niter=8, pq_niter=10, seed=0, device=0, id_base=0, centroids=None,
                              codebooks=None, chunk=1 << 20, alloc=None, points_per_centroid=64, pq_sample_rows=PQ_SAMPLE_ROWS, opq=False,
-                             rotation=None, opq_sample_rows=OPQ_SAMPLE_ROWS, refine=False, k_factor=1, threshold_scan=False, opq_dim=None):
+                             rotation=None, opq_sample_rows=OPQ_SAMPLE_ROWS, refine=False, k_factor=1, threshold_scan=False, opq_dim=None,
+                             refine_ranges=None):
     """IVF-PQ index over n rows PRODUCED ON THE GPU (`fill_rows(dst_ptr, row0, count, stride)` as in build_ivf_index_device): the
     fp16 corpus never exists whole -- training samples, then per chunk one assignment pass and one encoding pass; the index keeps
     M bytes per row.  Returns (index, stats dict).
@@ -458,13 +487,22 @@ def build_ivfpq_index_device(fill_rows, n, d, nlist, M, nprobe=16, niter=8, pq_n
     un-rotated chunks (it rotates them itself).  stats["rotate_s"]: the rotations of the assignment pass (those of the encoding pass
     are part of encode_s), stats["opq_s"]: training the rotation (part of train_s).
     refine / k_factor as in build_ivfpq_index: the index stores each generated chunk as it encodes it (the chunk is handed over once
-    and never held a second time); stats["code_arena_bytes"] / stats["row_arena_bytes"]: what the index keeps in HBM.
+    and never held a second time; the ranges of refine="sq8" are trained on the centroid sample's rows unless refine_ranges gives them);
+    stats["code_arena_bytes"] / stats["row_arena_bytes"]: what the index keeps in HBM.
     opq_dim=d_out / a rotation [d_out, d]: as in build_ivfpq_index; a chunk is still held once per width -- the generated rows d wide,
     their rotation d_out wide."""
     opq_s = [0.0]
 
+    def sq8_ranges(alloc):
+        n_sample = int(min(n, nlist * points_per_centroid))
+        sample_ptr, sample_keep = _device_sample(alloc, fill_rows, n, n_sample, d)
+        out = train_sq_ranges(sample_ptr, n_sample, d, device=device)
+        del sample_keep
+        return out
+
     def train(alloc):
         t0 = time.perf_counter()
+        rf = _refine_arg(refine, refine_ranges, lambda: sq8_ranges(alloc))
         A = None if rotation is None else _resolve_rotation(None, M, opq, rotation, seed, device, opq_dim)[0]
         if A is not None and A.shape[0] == A.shape[1]:
             A = _pad_rotation(A, d)
@@ -516,13 +554,13 @@ def build_ivfpq_index_device(fill_rows, n, d, nlist, M, nprobe=16, niter=8, pq_n
             cb = train_pq_codebooks(pb, niter=pq_niter, seed=seed)
             pb.close()
             del ps_keep, ps_rot_keep, pl_keep
-        return b, A, cent, lambda sizes: _ivfpq_begin(d, nlist, M, cent, cb, sizes, device, id_base, A, refine, k_factor, threshold_scan)
+        return b, A, cent, lambda sizes: _ivfpq_begin(d, nlist, M, cent, cb, sizes, device, id_base, A, rf, k_factor, threshold_scan)
 
     # (release_after_assign=False: this builder has never emptied the allocator's cache between the rotated chunk and the arena)
     index, sizes, clock = _build_on_device(train, fill_rows, n, d, nlist, nprobe, device, id_base, chunk, alloc, release_after_assign=False)
     code_bytes, row_bytes = index.pq_arena_bytes()
     return index, {"train_s": clock[0], "assign_s": clock[1], "encode_s": clock[2], "list_sizes": sizes,
-                   "bytes_per_row": M + 12 + (2 * d if refine else 0), "rotate_s": clock[3], "opq_s": opq_s[0],
+                   "bytes_per_row": M + 12 + (d if refine == "sq8" else 2 * d if refine else 0), "rotate_s": clock[3], "opq_s": opq_s[0],
                    "code_arena_bytes": code_bytes, "row_arena_bytes": row_bytes}
 
 

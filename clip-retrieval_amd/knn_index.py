@@ -376,6 +376,31 @@ class Mi355xIndex(_FaissShaped):
         """True when this IVF-PQ index has a refine store."""
         return bool(self._lib.knnx_ivfpq_refine(self._h)) if self._h else False
 
+    def set_pq_refine_sq8(self, vmin, vdiff):
+        """Refine store in SQ8 (faiss IndexRefine(IndexIVFPQ, IndexScalarQuantizer(QT_8bit)), ",Refine(SQ8)"): the index keeps one code byte
+        per column of the un-rotated row next to the PQ codes (d bytes more per row) and re-scores the k x k_factor best rows by ADC score
+        from them; reconstruct and the R of a search return the decoded SQ8 rows.  vmin, vdiff f32 [d]: the ranges of the ORIGINAL rows
+        (train_sq_ranges).  After set_pq_quantizer, before the rows go in; exclusive with set_pq_refine (include/knnx.h:
+        knnx_ivfpq_set_refine_sq8).  Padding columns get vmin = vdiff = 0."""
+        vmin = np.asarray(vmin, dtype=np.float32).reshape(-1)
+        vdiff = np.asarray(vdiff, dtype=np.float32).reshape(-1)
+        if vmin.shape != (self.d,) or vdiff.shape != (self.d,):
+            raise AssertionError(f"vmin and vdiff must be [{self.d}], got {vmin.shape} and {vdiff.shape}")
+        a, b = np.zeros(self._dpad, dtype=np.float32), np.zeros(self._dpad, dtype=np.float32)
+        a[: self.d], b[: self.d] = vmin, vdiff
+        check(self._lib, self._lib.knnx_ivfpq_set_refine_sq8(self._h, a.ctypes.data, b.ctypes.data), "knnx")
+
+    @property
+    def pq_refine_kind(self):
+        """The refine store of this IVF-PQ index: None, "fp16" (set_pq_refine) or "sq8" (set_pq_refine_sq8)."""
+        return (None, "fp16", "sq8")[int(self._lib.knnx_ivfpq_refine_kind(self._h))] if self._h else None
+
+    def pq_refine_ranges(self):
+        """(vmin, vdiff) f32 [d] of the sq8 refine store, as they were given."""
+        a, b = np.empty(self._dpad, dtype=np.float32), np.empty(self._dpad, dtype=np.float32)
+        check(self._lib, self._lib.knnx_ivfpq_get_refine_ranges(self._h, a.ctypes.data, b.ctypes.data), "knnx")
+        return np.ascontiguousarray(a[: self.d]), np.ascontiguousarray(b[: self.d])
+
     @property
     def k_factor(self):
         """Candidates per result of a refine search (faiss IndexRefine.k_factor; 1 .. 512, k x k_factor <= 512)."""

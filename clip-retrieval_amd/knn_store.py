@@ -20,6 +20,7 @@ IVF_MANIFEST = "ivf_manifest.json"
 IVF_FORMAT = "clip-retrieval_amd ivf-flat v1"
 IVFPQ_MANIFEST = "ivf_pq_manifest.json"
 IVFPQ_ROTATION = "ivf_pq_rotation.npy"
+IVFPQ_REFINE_RANGES = "ivf_pq_refine_ranges.npy"  # f32 [2, d]: vmin, vdiff of an sq8 refine store
 IVFPQ_FORMAT = "clip-retrieval_amd ivf-pq v1"
 IVFSQ_MANIFEST = "ivf_sq_manifest.json"
 IVFSQ_FORMAT = "clip-retrieval_amd ivf-sq8 v1"
@@ -199,13 +200,15 @@ def _save_ivfpq_index(index, folder, embeddings_folder=None):
     OPQ rotation adds ivf_pq_rotation.npy (f32 [d, d]) and "opq": true in the manifest; one whose quantiser space is wider than its
     rows also "d_out" (only then), and its rotation file is f32 [d_out, d], its centroids [nlist, d_out].  An index with a refine store adds "refine": true,
     "k_factor" and the embeddings folder (as save_index does for IVF-Flat) to the manifest: the rows are not written a second time, the
-    folder is loaded together with the embeddings.  An index with the threshold scan switched on adds "threshold_scan": true (only
+    folder is loaded together with the embeddings.  The sq8 refine store adds "refine_kind": "sq8" next to "refine": true and its ranges
+    as ivf_pq_refine_ranges.npy (f32 [2, d]: vmin, vdiff); loading encodes the store again from the embeddings.  An index with the threshold scan switched on adds "threshold_scan": true (only
     then: every other folder is what it always was)."""
     cent = getattr(index, "ivf_centroids", None)
     if cent is None:
         raise ValueError("save_index takes an IVF-PQ index built by build_ivfpq_index* / load_index")
     src = None
-    if index.pq_refine:
+    kind = index.pq_refine_kind
+    if kind:
         src = embeddings_folder or getattr(index, "embeddings_folder", None)
         if src is None:
             raise ValueError("this IVF-PQ index has a refine store: name the embeddings folder its rows can be re-read from")
@@ -228,6 +231,9 @@ def _save_ivfpq_index(index, folder, embeddings_folder=None):
         if src.n < hi or src.d != index.d:
             raise ValueError(f"{src.folder}: {src.n} rows of width {src.d} cannot hold rows [{lo}, {hi}) of width {index.d}")
         man.update({"refine": True, "k_factor": int(index.k_factor), **_embeddings_entries(src, folder)})
+        if kind == "sq8":  # (only then: the folder of an fp16 store is what it always was)
+            np.save(os.path.join(folder, IVFPQ_REFINE_RANGES), np.stack(index.pq_refine_ranges()).astype(np.float32))
+            man["refine_kind"] = "sq8"
     man.update(ivfpq_threshold_scan_entry(index.pq_threshold_scan))
     return _write_manifest(folder, IVFPQ_MANIFEST, man)
 
@@ -304,12 +310,35 @@ def read_ivfpq_refine(folder, man, embeddings_folder=None):
     return True, kf, src
 
 
-def _ivfpq_refine_from_rows(src, codes, lists, lo, cent, cb, M, nprobe, device, k_factor, chunk=1 << 20, rotation=None):
-    """A saved refine index: rows [lo, lo + n) of the embeddings are stored AND re-encoded with the saved centroids, codebooks,
-    rotation and lists; the codes that come out must be the saved ones."""
+def read_ivfpq_refine_kind(folder, man):
+    """The kind of refine store a saved IVF-PQ manifest names -> what _ivfpq_begin takes: False (no "refine"), True (the fp16 store:
+    "refine": true without "refine_kind" -- every refine folder written before the key existed -- or with "refine_kind": "fp16"), or
+    ("sq8", (vmin, vdiff)) with the ranges of the sidecar ivf_pq_refine_ranges.npy (f32 [2, d]).  The key without "refine": true, any
+    other value, and the key and the sidecar without each other are refused.  Touches no device."""
+    path = os.path.join(folder, IVFPQ_REFINE_RANGES)
+    kind = man.get("refine_kind")
+    if kind is not None and not man.get("refine", False):
+        raise ValueError(f"{folder}: the manifest carries \"refine_kind\" but does not say \"refine\": true")
+    if kind not in (None, "fp16", "sq8"):
+        raise ValueError(f"{folder}: \"refine_kind\" must be \"fp16\" or \"sq8\", got {kind!r}")
+    if kind != "sq8":
+        if os.path.exists(path):
+            raise ValueError(f"{folder}: {IVFPQ_REFINE_RANGES} is present but the manifest does not say \"refine_kind\": \"sq8\"")
+        return bool(man.get("refine", False))
+    if not os.path.isfile(path):
+        raise ValueError(f"{folder}: the manifest says \"refine_kind\": \"sq8\" but {IVFPQ_REFINE_RANGES} is missing")
+    rng = np.load(path)
+    if rng.shape != (2, int(man["d"])) or rng.dtype != np.float32:
+        raise ValueError(f"{folder}: {IVFPQ_REFINE_RANGES} must be float32 [2, {man['d']}], got {rng.dtype} {rng.shape}")
+    return "sq8", (np.ascontiguousarray(rng[0]), np.ascontiguousarray(rng[1]))
+
+
+def _ivfpq_refine_from_rows(src, codes, lists, lo, cent, cb, M, nprobe, device, k_factor, chunk=1 << 20, rotation=None, refine=True):
+    """A saved refine index: rows [lo, lo + n) of the embeddings are stored (refine=True: as fp16 rows; ("sq8", ranges): encoded with
+    the saved ranges) AND re-encoded with the saved centroids, codebooks, rotation and lists; the codes that come out must be the saved ones."""
     n = codes.shape[0]
     index = _ivfpq_encode_chunks(((o - lo, x) for o, x in src.chunks(lo, lo + n, chunk)), n, src.d, cent.shape[0], M, cent, cb,
-                                 np.asarray(lists, dtype=np.int32), nprobe, device, lo, rotation, True, k_factor)
+                                 np.asarray(lists, dtype=np.int32), nprobe, device, lo, rotation, refine, k_factor)
     got = index.pq_codes()[0]
     if not np.array_equal(got, np.asarray(codes)):
         bad = int((got != np.asarray(codes)).any(axis=1).sum())
@@ -338,6 +367,7 @@ def _load_ivfpq_index(folder, device=0, row_range=None, devices=None, embeddings
     lists = np.load(os.path.join(folder, "ivf_pq_lists.npy"), mmap_mode="r")
     rot = read_ivfpq_rotation(folder, man)
     refine, kf, src = read_ivfpq_refine(folder, man, embeddings_folder)
+    refine_kind = read_ivfpq_refine_kind(folder, man)
     thr_scan = read_ivfpq_threshold_scan(folder, man)
     slo, shi = man["row_range"]
     M = int(man["M"])
@@ -345,7 +375,7 @@ def _load_ivfpq_index(folder, device=0, row_range=None, devices=None, embeddings
     def make(lo, hi, dev):
         c, ls = codes[lo - slo:hi - slo], np.asarray(lists[lo - slo:hi - slo])
         if refine:
-            ix = _ivfpq_refine_from_rows(src, c, ls, lo, cent, cb, M, man["nprobe"], dev, kf, rotation=rot)
+            ix = _ivfpq_refine_from_rows(src, c, ls, lo, cent, cb, M, man["nprobe"], dev, kf, rotation=rot, refine=refine_kind)
         else:
             ix = _ivfpq_from_codes(c, ls, lo, cent, cb, M, man["nprobe"], dev, rotation=rot)
         if thr_scan:

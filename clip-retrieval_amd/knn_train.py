@@ -515,9 +515,9 @@ def train_ivfpq(x_f16, nlist, M, niter=8, pq_niter=10, seed=0, device=0, sample_
 
 
 def ivfpq_params_from_index_key(key, d):
-    """A faiss index-factory string of the family autofaiss builds -- `OPQ{M}_{d_out},IVF{nlist}[_HNSW32],PQ{M}x8[,RFlat]`, the OPQ
+    """A faiss index-factory string of the family autofaiss builds -- `OPQ{M}_{d_out},IVF{nlist}[_HNSW32],PQ{M}x8[,RFlat | ,Refine(SQ8)]`, the OPQ
     part optional -- for rows of width d -> the keyword arguments of build_ivfpq_index*: {"nlist", "M", "opq", "opq_dim", "refine"}
-    (opq_dim is None when d_out == d).  The _HNSW32 suffix is accepted and ignored: the coarse quantiser here is flat.  Whatever
+    (opq_dim is None when d_out == d; refine is False, True for RFlat -- the fp16 store -- or "sq8" for Refine(SQ8)).  The _HNSW32 suffix is accepted and ignored: the coarse quantiser here is flat.  Whatever
     cannot be served raises ValueError naming the part.  It parses; it does not choose an index."""
     import re  # pylint: disable=import-outside-toplevel
 
@@ -560,8 +560,11 @@ def ivfpq_params_from_index_key(key, d):
     if i < len(parts) and parts[i] == "RFlat":
         out["refine"] = True
         i += 1
+    elif i < len(parts) and parts[i] == "Refine(SQ8)":  # faiss IndexRefine(.., IndexScalarQuantizer(QT_8bit)): the sq8 refine store
+        out["refine"] = "sq8"
+        i += 1
     if i < len(parts):
-        raise ValueError(f"index key part {parts[i]!r}: not served (OPQ, IVF, PQ and RFlat parts only)")
+        raise ValueError(f"index key part {parts[i]!r}: not served (OPQ, IVF, PQ and RFlat / Refine(SQ8) parts only)")
     return out
 
 

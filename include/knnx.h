@@ -252,6 +252,33 @@ int knnx_ivfpq_refine(const knnx_index* ix); /* 1: the index has (or will be bui
 int knnx_ivfpq_set_k_factor(knnx_index* ix, int k_factor);
 int knnx_ivfpq_k_factor(const knnx_index* ix);
 int knnx_ivfpq_arena_bytes(knnx_index* ix, int64_t* code_bytes, int64_t* row_bytes);
+/* ---- Refine store in SQ8: faiss IndexRefine(IndexIVFPQ(...), IndexScalarQuantizer(d, QT_8bit)) ("...,PQ64,Refine(SQ8)") ------------
+ * The second kind of refine store: next to the M code bytes the index keeps ONE BYTE per column of the row as it entered the build
+ * (original, un-rotated space), in the arena order of the codes: tiles x 32 x d bytes more HBM (memory rule: M + d bytes per padded
+ * row, against M + 2 d of the fp16 store).  Encode and decode are those of the IVF-SQ8 block below, with ranges vmin / vdiff [d] over
+ * the ORIGINAL rows; scale = 255 / vdiff and step = vdiff / 255 are derived on the host as knnx_ivfsq_set_quantizer derives them.
+ *   search    k <= 64, kc = k x k_factor <= 512.  1. Candidates: exactly those of the fp16 store (the block above).  2. Re-score with
+ *             the ORIGINAL query: s = <q, dec(code)> = b_q + sum_c u_c code_c, where u_c = q_c * step_c is one fp32 product (rounded
+ *             once) and b_q = <q, vmin + step / 2> is accumulated in double and rounded once.  Summation order: a row is d / 16 lanes
+ *             of 16 bytes; lane l owns columns 16 l .. 16 l + 15 and runs ONE fmaf chain from 0.f over them in ascending order of
+ *             u_c * (float)code_c; the lane sums of a candidate's group of G = 16 / 32 / 64 / 64 lanes (d = 256 / 512 / 768 / 1024; at
+ *             768 lanes 48 .. 63 hold 0) are added pairwise in a butterfly over lane distance G / 2, .., 2, 1; then s = b_q + sum,
+ *             rounded once.  It depends on nothing else: not on the batch, the shares of the ADC pass or the candidate's position.
+ *             A candidate id outside the index scores -FLT_MAX.  3. Result: as for the fp16 store.
+ *   rows      reconstruct and the R of search are the DECODED SQ8 rows (vmin + (code + 0.5) * step, two roundings), in the original
+ *             space with no back-rotation (faiss IndexRefine::reconstruct asks the refine index); an id outside the index -> 0xFF bytes.
+ * knnx_ivfpq_set_refine_sq8: after knnx_ivfpq_set_quantizer and before knnx_ivf_begin, once; KNNX_E_STATE otherwise, on an index that is
+ * not IVF-PQ and on one that already has the fp16 store (knnx_ivfpq_set_refine(ix, 1) after it answers KNNX_E_STATE as well); KNNX_E_ARG
+ * for ranges that are not finite or a negative vdiff.  knnx_ivf_add_assigned[_device] encode every un-rotated chunk into the store AND
+ * into the PQ codes; knnx_ivfpq_add_codes answers KNNX_E_STATE.  knnx_ivfpq_refine_kind: 0 none, 1 fp16, 2 sq8 (knnx_ivfpq_refine stays
+ * 1 for the fp16 store only).  knnx_ivfpq_get_refine_ranges: the ranges as given; KNNX_E_STATE without the sq8 store.
+ * knnx_ivfpq_arena_bytes reports capacity x d row bytes.  k_factor and the k x k_factor <= 512 rule are those of the block above.
+ * Not served yet, each KNNX_E_UNSUPPORTED with a message that names the sq8 refine store, before any device work: knnx_ivf_append*,
+ * knnx_ivf_merge_from (either side), knnx_ivf_remove_ids, knnx_shards_adopt, knnx_search_filtered, and switching the threshold scan on
+ * (so k > 64 and range_search keep the plain index's refusals). */
+int knnx_ivfpq_set_refine_sq8(knnx_index* ix, const float* vmin, const float* vdiff);
+int knnx_ivfpq_refine_kind(const knnx_index* ix);
+int knnx_ivfpq_get_refine_ranges(knnx_index* ix, float* vmin, float* vdiff);
 /* ---- Threshold scan on IVF-PQ: k > 64 and range_search (clip_back.py:356-369 asks for up to 1e5 results; clip_filter.py:52) ---------
  * A switch per index, OFF by default: an index nobody switched on is exactly the three blocks above, refusals included.
  * knnx_ivfpq_set_threshold_scan: any IVF-PQ index, any time (like knnx_ivfpq_set_k_factor); KNNX_E_STATE on an index that is not IVF-PQ.

@@ -19,6 +19,8 @@ at a size where both fit).  Prints ONE JSON line.
                                                                 # + the same index with a refine store and IVF-Flat on the same rows, all three
                                                                 # resident, timed alternately; recall@40 of each
   python tools/ivfpq_bench.py --rows 16000000 --nlist 16384 --nprobes 64 --refine --large-k 100,3000
+  python tools/ivfpq_bench.py --rows 16000000 --nlist 16384 --nprobes 64 --refine sq8 [--k-factor 1,4,8]
+                                                                # the sq8 refine store against the fp16 store and IVF-SQ8, alternately
                                                                 # + one query at nprobe 64 for every k on those three indexes (threshold scan
                                                                 # switched on), timed alternately; threshold scans and hits fetched per query
 """
@@ -50,7 +52,9 @@ def main():
     ap.add_argument("--opq-dim", type=int, default=0, help="with --opq: d_out > d.  Builds the index behind a trained rotation [d_out, d] and the "
                     "square d_out index over the zero-padded rows (both with a refine store), reports rotate_s, build seconds, arena bytes "
                     "and B x nprobe 64 timed alternately, and nothing else")
-    ap.add_argument("--refine", action="store_true", help="also build the index with a refine store (same centroids and codebooks) and IVF-Flat "
+    ap.add_argument("--refine", nargs="?", const="fp16", default="", choices=("fp16", "sq8"), help="sq8: build the index with the sq8 refine store, "
+                    "with the fp16 store and as IVF-SQ8 (same centroids) and report bytes, recall@40 per --k-factor and alternating times at "
+                    "nprobe 64.  Without a value (fp16): also build the index with a refine store (same centroids and codebooks) and IVF-Flat "
                     "on the same rows; all three stay resident and are timed alternately at nprobe 64, k = 40")
     ap.add_argument("--k-factor", default="1,4,8", help="k_factor values of --refine")
     ap.add_argument("--large-k", default="", help="with --refine: k values above 64 (e.g. 100,3000) timed at B = 1, nprobe 64 on the plain index, "
@@ -63,7 +67,7 @@ def main():
 
     import torch
 
-    from clip_retrieval_amd.knn import Mi355xIndex, build_ivf_index_device, build_ivfpq_index_device, synth_rows_device
+    from clip_retrieval_amd.knn import Mi355xIndex, build_ivf_index_device, build_ivfpq_index_device, build_ivfsq_index_device, synth_rows_device
 
     n, d = a.rows, a.d
 
@@ -181,7 +185,40 @@ def main():
         out["opq"] = cmp_
         rot.close()
 
-    if a.refine:
+    if a.refine == "sq8":
+        # the sq8 refine store against the fp16 store (same centroids, codebooks: the same candidates) and against IVF-SQ8 (same centroids)
+        # at equal nprobe.  One process, the indexes timed alternately, three rounds, the median of the rounds' medians.
+        kw = {"nprobe": 64, "seed": 0, "centroids": index.ivf_centroids}
+        sq8, s8 = build_ivfpq_index_device(fill_rows, n, d, a.nlist, a.M, codebooks=index.pq_codebooks(), refine="sq8", **kw)
+        f16, s16 = build_ivfpq_index_device(fill_rows, n, d, a.nlist, a.M, codebooks=index.pq_codebooks(), refine=True, **kw)
+        isq, _ = build_ivfsq_index_device(fill_rows, n, d, a.nlist, ranges=sq8.pq_refine_ranges(), **kw)
+        index.nprobe = sq8.nprobe = f16.nprobe = isq.nprobe = 64
+        kfs = [int(v) for v in a.k_factor.split(",")]
+
+        def rec(I):
+            return round(float(np.mean([len(set(x) & set(y)) / k for x, y in zip(I, best_I)])), 4)
+
+        r = {"row_arena_bytes_sq8": s8["row_arena_bytes"], "row_arena_bytes_fp16": s16["row_arena_bytes"], "code_arena_bytes": s8["code_arena_bytes"],
+             "bytes_per_row_sq8": s8["bytes_per_row"], "bytes_per_row_fp16": s16["bytes_per_row"], "encode_s_sq8": round(s8["encode_s"], 2),
+             "encode_s_fp16": round(s16["encode_s"], 2), "recall40_plain": rec(index.search(q[:nr], k)[1]), "recall40_ivfsq": rec(isq.search(q[:nr], k)[1])}
+        for kf in kfs:
+            sq8.k_factor = f16.k_factor = kf
+            r[f"recall40_sq8_kf{kf}"], r[f"recall40_fp16_kf{kf}"] = rec(sq8.search(q[:nr], k)[1]), rec(f16.search(q[:nr], k)[1])
+        for B in [int(v) for v in a.batches.split(",")]:
+            ts = {"plain": [], "ivfsq": [], **{f"{s}_kf{kf}": [] for kf in kfs for s in ("sq8", "fp16")}}
+            for _ in range(3):
+                ts["plain"].append(timed(index, B))
+                for kf in kfs:
+                    sq8.k_factor = f16.k_factor = kf
+                    ts[f"sq8_kf{kf}"].append(timed(sq8, B))
+                    ts[f"fp16_kf{kf}"].append(timed(f16, B))
+                ts["ivfsq"].append(timed(isq, B))
+            for name, v in ts.items():
+                r[f"B{B}_np64_ms_{name}"] = round(float(np.median(v)) * 1e3, 4)
+        out["refine_sq8"] = r
+        sq8.close(), f16.close(), isq.close()
+
+    if a.refine == "fp16":
         # the same centroids and codebooks (so the candidates are the plain index's), the fp16 rows next to the codes; IVF-Flat with the
         # same k-means seed on the same rows.  One process, the indexes timed alternately, three rounds, the median of the rounds' medians.
         torch.cuda.synchronize()

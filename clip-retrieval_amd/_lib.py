@@ -126,6 +126,12 @@ SIGNATURES = {
     "knnx_ivfsq_threshold_scan": (C.c_int, [_P]),
     "knnx_ivfsq_threshold_stats": (C.c_int, [_P, _P, _P, _P, _P]),
     "knnx_colminmax_device": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int, _P, _P, _P]),
+    "knnx_sq8_set_quantizer": (C.c_int, [_P, _P, _P]),
+    "knnx_sq8_get_quantizer": (C.c_int, [_P, _P, _P]),
+    "knnx_sq8": (C.c_int, [_P]),
+    "knnx_sq8_add_codes": (C.c_int, [_P, _P, C.c_int64]),
+    "knnx_sq8_add_device_f16": (C.c_int, [_P, _P, C.c_int64]),
+    "knnx_sq8_get_codes": (C.c_int, [_P, _P]),
     "knnx_rotate_f16_device": (C.c_int, [C.c_int, _P, _P, C.c_int64, C.c_int, _P, _P]),
     "knnx_rotate_rect_f16_device": (C.c_int, [C.c_int, _P, _P, C.c_int64, C.c_int, C.c_int, _P, _P]),
     "knnx_xty_device": (C.c_int, [C.c_int, _P, _P, C.c_int64, C.c_int, _P, _P]),

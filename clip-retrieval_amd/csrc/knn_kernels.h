@@ -339,6 +339,19 @@ hipError_t launch_sq_decode(const uint8_t* codes, int d, const float* vmin, cons
                             const uint32_t* inv, const int64_t* ids, int64_t n, float* out, hipStream_t st);
 // per-column min / max of n fp16 rows (d <= KNN_D_MAX) -> vmin_dev / vmax_dev f32 [d]; enc: 2 d ints of device scratch
 hipError_t launch_sq_colminmax(const _Float16* X, int64_t n, int d, int* enc, float* vmin_dev, float* vmax_dev, hipStream_t st);
+// ---- Flat SQ8 (knn_sq_kernels.hip, "Flat SQ8"): the code arena [capacity][d] in id order, tile-padded, no lists
+// queries of one register-stationary pass over the codes: 128 at d <= 768, 64 at d = 1024 / 1280 (0: no kernel for this d)
+int sq_rq_queries_per_pass(int d);
+// ONE pass over rows [0, n) for nq <= sq_rq_queries_per_pass(d) queries: qfrag / bq / inv as launch_sq_prep + launch_prep_blocks leave
+// them, thr_g [128] reset; partial list (g, q) of the grid's workgroups at part_s / part_i [(g * NQP + q) * k], part_n [g * NQP + q],
+// NQP = sq_rq_queries_per_pass(d); k <= 64.  Merge: launch_merge_u32(.., P = grid, nq_stride = NQP, kin = k, ..) without an id map.
+hipError_t launch_sq_rq_scan(const uint8_t* codes, int64_t n, int d, const _Float16* qfrag, const float* bq, const float* inv, int nq, int k,
+                             int* thr_g, float* part_s, uint32_t* part_i, int* part_n, int grid, hipStream_t st);
+// the work list launch_sq_scan walks over a flat arena of n rows: work [ceil(n / 32)] = {tile, all queries, valid rows}, *nwork = tiles
+hipError_t launch_sq_flat_worklist(int64_t n, uint4* work, unsigned* nwork, hipStream_t st);
+// launch_sq_decode with identity addressing: arena row = id - id_lo
+hipError_t launch_sq_decode_flat(const uint8_t* codes, int d, const float* vmin, const float* step, int64_t id_lo, int64_t n_ids,
+                                 const int64_t* ids, int64_t n, float* out, hipStream_t st);
 
 // ---- post filter of one request on the device (knn_filter_kernels.hip; the shared arithmetic: knnx_filter_plan.h) ----
 // R f32 [n][d] -> unit rows in place over the columns [0, d_user) (one fmaf chain per row, a zero row stays zero); columns [d_user, d) <- 0.

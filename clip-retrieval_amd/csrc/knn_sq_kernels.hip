@@ -646,4 +646,288 @@ hipError_t launch_sq_colminmax(const _Float16* X, int64_t n, int d, int* enc, fl
   return hipGetLastError();
 }
 
+// =============================================================================================
+// Flat SQ8 (include/knnx.h, "Flat SQ8"; DESIGN 4.8 "Flat SQ8"): the code arena in id order, no lists, no idmap.
+//
+// knn_sq_rq_scan_kernel: ONE pass over the code bytes for a whole step of queries.  The list scan above keeps the u fragments of 32
+// queries in the LDS and every wave streams its own tile HBM -> VGPR: a 128-query step would read the arena four times.  Here the roles
+// are those of the register-stationary fp16 passes (knn_rq_kernels.hip):
+//   * four waves, one per SIMD with the whole 512-register file (launch bound 256 threads, one workgroup per CU).  A wave keeps the hi
+//     AND the lo fragment of its 32 queries for its k-steps in registers for the whole pass, 8 registers per k-step: the lo fragments
+//     pinned in the accumulation file, the hi ones in the architectural file (the MFMA reads B from either).
+//       KSPLIT = 1 (d <= 512): wave w holds query block w, all KS k-steps (d = 512: 256 registers) -- 128 queries per pass;
+//       KSPLIT = 2 (d = 768, 1024, 1280): 8 KS registers per wave would be 384 / 512 / 640 -- at 768 the compiler spills 52 B beside
+//         the accumulators, scores and staging registers, the others are the whole file and more -- so the k-steps are split: wave w
+//         holds query block w & 1 and the k-steps of column half w >> 1 (192 / 256 / 320 registers) -- 64 queries per pass.  The wave
+//         of the upper half hands its 16 partial sums per lane to the lower-half wave through 4 KiB of LDS per block and one barrier.
+//     Nothing of u lives in the LDS: 128 queries x d x 4 B of fragments are 256 KiB at d = 512, against 160 KiB of LDS.
+//   * code tiles (32 rows x d bytes, contiguous in the arena) go HBM -> VGPR -> LDS with plain 16-byte loads, all 256 threads taking
+//     consecutive 16-byte chunks, into a ring of two tiles.  The LDS image is fragment-shaped: chunk c of row r sits at piece c >> 1
+//     (32 columns, 1 KiB), lane slot 32 (c & 1) + r, so a wave's ds_read_b128 at piece * 1024 + 16 lane is lane-linear and hands lane
+//     (row, half) exactly the two dwords per k-step that sq_codes_half8 unpacks -- the 8-byte alignment v_perm_b32 wants comes for
+//     free from the 16-byte chunk, where an LDS-DMA of the row-major bytes would need a second pass to reshape.  The loads of tile
+//     t + 1 are issued before the MFMAs of tile t in two halves (half the staging registers), and stored behind them; the barrier of
+//     the candidate filter publishes the stores.  Every code byte is read from HBM once per pass and used by all four waves.
+//   * scores: hi and lo products in two fp32 accumulators, the k-step order of the list scan within a wave's columns; score =
+//     (lo / 2048 + hi) * 2^-sh + b_q, added once before the threshold compare.  No approximation, no re-score.
+//   * top-k: the LDS candidate queues and prune_query of knn_scan_shared.h for all queries of the pass (SQRQ_CAP entries each), thresholds
+//     shared across workgroups through thr_g, one partial list per workgroup and query, merged by launch_merge_u32.
+// HBM bytes per pass: ceil(N / 32) * 32 * d code bytes + the fragments (512 d per workgroup, from L2 after the first) + the partial lists.
+constexpr int SQRQ_CAP = 96;  // queue entries per query (>= k + 16, <= 128: prune_query)
+constexpr int sqrq_ksplit(int d) { return d <= 512 ? 1 : 2; }
+constexpr size_t sqrq_smem_bytes(int d) {
+  const int nqp = 128 / sqrq_ksplit(d);
+  return (size_t)2 * 32 * d + (sqrq_ksplit(d) == 2 ? (size_t)2 * 64 * 16 * 4 : 0) + (size_t)nqp * SQRQ_CAP * 8 + (size_t)nqp * 8 + 16;
+}
+
+template <int D, int KSPLIT>
+__global__ __launch_bounds__(256, 1) void knn_sq_rq_scan_kernel(
+    const uint8_t* __restrict__ X, int64_t N, const _Float16* __restrict__ qfrag, const float* __restrict__ bq_g,
+    const float* __restrict__ inv_g, int nq, int k, int* __restrict__ thr_g, float* __restrict__ part_s,
+    uint32_t* __restrict__ part_i, int* __restrict__ part_n) {
+  constexpr int KS = D / 16, KW = KS / KSPLIT;     // k-steps of a row; of this wave
+  constexpr int NQB = 4 / KSPLIT, NQP = 32 * NQB;  // query blocks, queries of the pass
+  constexpr int TILE = 32 * D;                     // bytes of one code tile
+  constexpr int CPR = D / 16;                      // 16-byte chunks of a row
+  constexpr int LPT = D / 128, LPH = LPT / 2;      // chunks a thread stages per tile; per half
+  constexpr int NW = 4, CAP = SQRQ_CAP;
+  static_assert(KW % 2 == 0 && LPT % 2 == 0, "whole 32-column pieces, two staging halves");
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  unsigned char* ring = smem_raw;
+  float* xch = reinterpret_cast<float*>(smem_raw + 2 * TILE);  // [NQB][16][64] (KSPLIT = 2 only)
+  ScanSmem sm{};
+  {
+    unsigned char* p = smem_raw + 2 * TILE + (KSPLIT == 2 ? NQB * 64 * 16 * 4 : 0);
+    sm.cand_s = reinterpret_cast<float*>(p);
+    sm.cand_i = reinterpret_cast<uint32_t*>(p + (size_t)NQP * CAP * 4);
+    sm.cnt = reinterpret_cast<int*>(p + (size_t)NQP * CAP * 8);
+    sm.thr = sm.cnt + NQP;
+    sm.flag = sm.thr + NQP;
+  }
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int qb = w & (NQB - 1), kh = w / NQB;  // query block and column half of this wave
+  const int q = lane & 31, hb = lane >> 5;
+  const int qq = 32 * qb + q;                  // this lane's query of the pass
+  const bool owner = kh == 0;                  // the wave that filters its block's scores
+  const float inv_q = qq < nq ? inv_g[qq] : 0.f;
+  const float b_q = qq < nq ? bq_g[qq] : 0.f;
+
+  // the stationary operand: hi and lo fragments of block qb, k-steps kh KW .. + KW - 1, loaded once
+  half8 Qh[KW], Ql[KW];
+  {
+    const half8* src = reinterpret_cast<const half8*>(qfrag) + (size_t)qb * KS * 2 * 64 + lane;
+#pragma unroll
+    for (int j = 0; j < KW; ++j) {
+      Qh[j] = src[((kh * KW + j) * 2 + 0) * 64];
+      Ql[j] = src[((kh * KW + j) * 2 + 1) * 64];
+    }
+#pragma unroll
+    for (int j = 0; j < KW; ++j) {
+      asm volatile("" : "+v"(Qh[j]));
+      asm volatile("" : "+a"(Ql[j]));
+    }
+  }
+  for (int i = tid; i < NQP; i += 256) { sm.cnt[i] = 0; sm.thr[i] = enc_f(-INFINITY); }
+  if (tid < 4) sm.flag[tid] = 0;
+
+  const int64_t ntile = (N + 31) >> 5;  // (the arena is padded to whole tiles: every tile below ntile is inside it)
+  const int64_t G = gridDim.x;
+  int64_t t = blockIdx.x;
+
+  // staging: chunk g = 256 i + tid of the tile, i < LPT -- row g / CPR, chunk g % CPR of the row; half H of the chunks at a time
+  uint4v pf[LPH];
+#define SQRQ_GLOAD(tt_, H_)                                                                  \
+  {                                                                                          \
+    const uint4v* src_ = reinterpret_cast<const uint4v*>(X + (size_t)(tt_) * TILE);           \
+    _Pragma("unroll") for (int i = 0; i < LPH; ++i) pf[i] = src_[256 * ((H_) * LPH + i) + tid]; \
+  }
+#define SQRQ_LSTORE(slot_, H_)                                                                               \
+  {                                                                                                          \
+    _Pragma("unroll") for (int i = 0; i < LPH; ++i) {                                                        \
+      const int g_ = 256 * ((H_) * LPH + i) + tid;                                                           \
+      const int r_ = g_ / CPR, c_ = g_ - r_ * CPR;                                                           \
+      *reinterpret_cast<uint4v*>(ring + (slot_) * TILE + (c_ >> 1) * 1024 + (32 * (c_ & 1) + r_) * 16) = pf[i]; \
+    }                                                                                                        \
+  }
+#define SQRQ_KSTEPS(J0_, J1_)                                                               \
+  _Pragma("unroll") for (int j = (J0_); j < (J1_); ++j) {                                   \
+    const uint4v a = *reinterpret_cast<const uint4v*>(xs + j * 1024);                       \
+    const half8 x0 = sq_codes_half8(a[0], a[1]);                                             \
+    const half8 x1 = sq_codes_half8(a[2], a[3]);                                             \
+    acc_h = __builtin_amdgcn_mfma_f32_32x32x16_f16(x0, Qh[2 * j], acc_h, 0, 0, 0);          \
+    acc_l = __builtin_amdgcn_mfma_f32_32x32x16_f16(x0, Ql[2 * j], acc_l, 0, 0, 0);          \
+    acc_h = __builtin_amdgcn_mfma_f32_32x32x16_f16(x1, Qh[2 * j + 1], acc_h, 0, 0, 0);      \
+    acc_l = __builtin_amdgcn_mfma_f32_32x32x16_f16(x1, Ql[2 * j + 1], acc_l, 0, 0, 0);      \
+  }
+  if (t < ntile) {
+    SQRQ_GLOAD(t, 0)
+    SQRQ_LSTORE(0, 0)
+    SQRQ_GLOAD(t, 1)
+    SQRQ_LSTORE(0, 1)
+  }
+  __syncthreads();
+
+  int slot = 0, rnd = 0;
+  for (; t < ntile; t += G) {
+    const int64_t tn = t + G;
+    const bool more = tn < ntile;  // (the same in every wave of the workgroup)
+    if (more) SQRQ_GLOAD(tn, 0)
+    float16v acc_h, acc_l;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { acc_h[r] = 0.f; acc_l[r] = 0.f; }
+    const unsigned char* xs = ring + slot * TILE + (kh * (KW / 2)) * 1024 + lane * 16;
+    SQRQ_KSTEPS(0, KW / 4)
+    // the other slot was last read before the barrier of the previous tile's filter: every wave is past it
+    if (more) {
+      SQRQ_LSTORE(slot ^ 1, 0)
+      SQRQ_GLOAD(tn, 1)
+    }
+    SQRQ_KSTEPS(KW / 4, KW / 2)
+    if (more) SQRQ_LSTORE(slot ^ 1, 1)
+#undef SQRQ_GLOAD
+#undef SQRQ_LSTORE
+#undef SQRQ_KSTEPS
+
+    // ---- the column halves meet: lane (q, hb) of the upper-half wave holds the same (row, query) entries as the owner's lane
+    float sc[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) sc[r] = sq_mul_add(acc_l[r], KNN_LO_INV, acc_h[r]);
+    if constexpr (KSPLIT == 2) {
+      float* xq = xch + qb * (16 * 64) + lane;
+      if (!owner) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) xq[64 * r] = sc[r];
+      }
+      __syncthreads();  // (the filter's barrier (A) below separates these reads from the next tile's writes)
+      if (owner) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sc[r] += xq[64 * r];
+      }
+    }
+
+    // ---- filter (the list scan's): lane (q, hb) owns rows row0 + (r & 3) + 8 (r >> 2) of query qq
+    const int64_t row0 = t * 32 + 4 * hb;
+    const bool q_ok = owner && qq < nq;
+    unsigned pend = 0;
+    const float thr = dec_f(sm.thr[qq]);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float v = sq_mul_add(sc[r], inv_q, b_q);
+      sc[r] = v;
+      const int64_t row = row0 + (r & 3) + 8 * (r >> 2);
+      if (v >= thr && row < N && q_ok) pend |= 1u << r;
+    }
+    const int par = rnd & 1;
+    for (;;) {
+      bool ovf = false;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        if (pend & (1u << r)) {
+          const int pos = atomicAdd(&sm.cnt[qq], 1);
+          if (pos < CAP) {
+            sm.cand_s[(size_t)qq * CAP + pos] = sc[r];
+            sm.cand_i[(size_t)qq * CAP + pos] = (uint32_t)(row0 + (r & 3) + 8 * (r >> 2));
+            pend &= ~(1u << r);
+          } else {
+            ovf = true;
+          }
+        }
+      }
+      if (ovf) sm.flag[par] = 1;
+      __syncthreads();  // (A) every append of this attempt and every store of the next tile has landed
+      if (sm.flag[par] == 0) break;
+      for (int x = w; x < NQP; x += NW) prune_query(sm, x, CAP, k, lane, thr_g);
+      __syncthreads();  // (B) queues pruned, everyone has read flag[par]
+      if (tid == 0) sm.flag[par] = 0;
+      __syncthreads();  // (C) flag cleared before anyone appends again
+      const float thr2 = dec_f(sm.thr[qq]);
+      unsigned keep = 0;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) keep |= sc[r] >= thr2 ? 1u << r : 0u;
+      pend &= keep;
+    }
+    if ((rnd & 3) == 3 && tid < NQP) {
+      const int g = __hip_atomic_load(&thr_g[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      atomicMax(&sm.thr[tid], g);
+    }
+    slot ^= 1;
+    ++rnd;
+  }
+
+  __syncthreads();
+  for (int x = w; x < NQP; x += NW) prune_query(sm, x, CAP, k, lane, thr_g);
+  __syncthreads();
+  const size_t wg = blockIdx.x;
+  for (int i = tid; i < NQP * k; i += 256) {
+    const int x = i / k, j = i - x * k;
+    if (j < sm.cnt[x]) {
+      const size_t o = (wg * NQP + x) * k + j;
+      part_s[o] = sm.cand_s[(size_t)x * CAP + j];
+      part_i[o] = sm.cand_i[(size_t)x * CAP + j];
+    }
+  }
+  if (tid < NQP) part_n[wg * NQP + tid] = sm.cnt[tid];
+}
+
+// work list of the list scan over a flat arena: one item {tile, every query, valid rows} per tile, *nwork = tiles
+__global__ void sq_flat_worklist_kernel(int64_t n, uint4* __restrict__ work, unsigned* __restrict__ nwork) {
+  const int64_t ntile = (n + 31) >> 5;
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < ntile) work[t] = make_uint4((unsigned)t, 0xffffffffu, (unsigned)(n - 32 * t < 32 ? n - 32 * t : 32), 0u);
+  if (t == 0) *nwork = (unsigned)ntile;
+}
+
+// out[i, :] = decode(codes[ids[i] - id_lo, :]); an id outside [id_lo, id_lo + n_ids) (-1 among them) -> 0xFF bytes
+__global__ __launch_bounds__(256) void sq_decode_flat_kernel(const uint8_t* __restrict__ codes, int d, const float* __restrict__ vmin,
+                                                            const float* __restrict__ step, int64_t id_lo, int64_t n_ids,
+                                                            const int64_t* __restrict__ ids, int64_t n, float* __restrict__ out) {
+  const int64_t i = blockIdx.x;
+  if (i >= n) return;
+  const int64_t id = ids[i];
+  const bool ok = id >= id_lo && id - id_lo < n_ids;
+  const size_t r = ok ? (size_t)(id - id_lo) : 0;
+  for (int c = threadIdx.x; c < d; c += 256)
+    out[(size_t)i * d + c] = ok ? sq_mul_add((float)codes[r * d + c] + 0.5f, step[c], vmin[c]) : __int_as_float(-1);
+}
+
+int sq_rq_queries_per_pass(int d) { return (d == 256 || d == 512) ? 128 : (d == 768 || d == 1024 || d == 1280) ? 64 : 0; }
+
+hipError_t launch_sq_rq_scan(const uint8_t* codes, int64_t n, int d, const _Float16* qfrag, const float* bq, const float* inv, int nq, int k,
+                             int* thr_g, float* part_s, uint32_t* part_i, int* part_n, int grid, hipStream_t st) {
+  if (n <= 0 || nq < 1 || nq > sq_rq_queries_per_pass(d) || k < 1 || k + 16 > SQRQ_CAP || grid < 1) return hipErrorInvalidValue;
+#define SQRQ_LAUNCH(DD)                                                                                                        \
+  {                                                                                                                            \
+    auto kern = knn_sq_rq_scan_kernel<DD, sqrq_ksplit(DD)>;                                                                    \
+    constexpr size_t smem = sqrq_smem_bytes(DD);                                                                               \
+    static_assert(smem <= KNN_LDS_BYTES, "ring + queues must fit the LDS");                                                    \
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
+    if (e != hipSuccess) return e;                                                                                             \
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, st, codes, n, qfrag, bq, inv, nq, k, thr_g, part_s, part_i, part_n); \
+    return hipGetLastError();                                                                                                  \
+  }
+  switch (d) {
+    case 256: SQRQ_LAUNCH(256)
+    case 512: SQRQ_LAUNCH(512)
+    case 768: SQRQ_LAUNCH(768)
+    case 1024: SQRQ_LAUNCH(1024)
+    case 1280: SQRQ_LAUNCH(1280)
+    default: return hipErrorInvalidValue;
+  }
+#undef SQRQ_LAUNCH
+}
+
+hipError_t launch_sq_flat_worklist(int64_t n, uint4* work, unsigned* nwork, hipStream_t st) {
+  const int64_t ntile = std::max<int64_t>(1, (n + 31) >> 5);
+  hipLaunchKernelGGL(sq_flat_worklist_kernel, dim3((unsigned)((ntile + 255) / 256)), dim3(256), 0, st, n, work, nwork);
+  return hipGetLastError();
+}
+
+hipError_t launch_sq_decode_flat(const uint8_t* codes, int d, const float* vmin, const float* step, int64_t id_lo, int64_t n_ids,
+                                 const int64_t* ids, int64_t n, float* out, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(sq_decode_flat_kernel, dim3((unsigned)n), dim3(256), 0, st, codes, d, vmin, step, id_lo, n_ids, ids, n, out);
+  return hipGetLastError();
+}
+
 }  // namespace knnx

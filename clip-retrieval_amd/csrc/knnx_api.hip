@@ -125,9 +125,10 @@ extern "C" int knnx_reset(knnx_index* ix) {
   if (set_dev(ix)) return KNNX_E_HIP;
   HIPCHK(hipStreamSynchronize(ix->stream));
   ix->ntotal = 0;
+  ix->fsq.work_rows = -1;
   ix->i8.valid = false;
   ix->i8.nrows = 0;
-  ix->i8_ok = ix->i8_env_ok;  // a copy that was given up for lack of memory may be tried again for the new rows; KNNX_I8=0 still rules
+  ix->i8_ok = ix->fsq.on ? 0 : ix->i8_env_ok;  // a copy that was given up for lack of memory may be tried again for the new rows; KNNX_I8=0 still rules
   HIPCHK(hipMemsetAsync(ix->flat.maxnorm, 0, sizeof(int), ix->stream));
   return KNNX_OK;
 }
@@ -166,6 +167,7 @@ extern "C" int knnx_reserve(knnx_index* ix, int64_t n_rows) {
   if (set_dev(ix)) return KNNX_E_HIP;
   if (ix->pq.m) return fail(KNNX_E_STATE, "reserve on an IVF-PQ index (its arena is sized by knnx_ivf_begin)");
   if (ix->sq.on) return fail(KNNX_E_STATE, "reserve on an IVF-SQ8 index (its arena is sized by knnx_ivf_begin)");
+  if (ix->fsq.on) return sq8_reserve_locked(ix, n_rows);
   return grow(ix, n_rows);
 }
 
@@ -178,6 +180,7 @@ static int add_common(knnx_index* ix, const void* rows, int64_t n, bool is_f32) 
   if (ix->pq.m) return fail(KNNX_E_STATE, "add() on an IVF-PQ index (rows are encoded by knnx_ivf_begin / knnx_ivf_add_assigned / knnx_ivf_end)");
   if (ix->sq.on) return fail(KNNX_E_STATE, "add() on an IVF-SQ8 index (rows are encoded by knnx_ivf_begin / knnx_ivf_add_assigned / knnx_ivf_end)");
   if (ix->ivf_nlist) return fail(KNNX_E_STATE, "add() after knnx_ivf_set_lists (rebuild the index instead)");
+  if (ix->fsq.on) return sq8_add_locked(ix, rows, n, is_f32);  // flat SQ8: the chunks are encoded, no fp16 row is kept
   if (ix->ntotal + n > ix->capacity) {
     int64_t want = std::max<int64_t>(ix->ntotal + n, ix->capacity + ix->capacity / 2);
     int r = grow(ix, want);
@@ -215,6 +218,7 @@ extern "C" int knnx_add_f32(knnx_index* ix, const float* rows, int64_t n) { retu
 
 extern "C" int knnx_attach_device_f16(knnx_index* ix, const void* dev_rows, int64_t n) {
   if (!ix || !dev_rows || n < 0) return fail(KNNX_E_ARG, "bad attach arguments");
+  if (const int r0 = sq8_refuse(ix, "knnx_attach_device_f16")) return r0;
   std::lock_guard<std::mutex> lk(ix->mu);
   if (ix->pq.m) return fail(KNNX_E_STATE, "attach on an IVF-PQ index");
   if (ix->sq.on) return fail(KNNX_E_STATE, "attach on an IVF-SQ8 index");
@@ -234,6 +238,7 @@ extern "C" int knnx_attach_device_f16(knnx_index* ix, const void* dev_rows, int6
 
 extern "C" int knnx_synth_fill(knnx_index* ix, int64_t n, uint64_t seed) {
   if (!ix || n < 0) return fail(KNNX_E_ARG, "bad synth arguments");
+  if (const int r0 = sq8_refuse(ix, "knnx_synth_fill")) return r0;
   std::lock_guard<std::mutex> lk(ix->mu);
   if (set_dev(ix)) return KNNX_E_HIP;
   if (ix->pq.m) return fail(KNNX_E_STATE, "synth_fill on an IVF-PQ index");
@@ -658,7 +663,7 @@ static int scan_topk_i8(knnx_index* ix, const float* q_dev, int nq, int k, float
 
 // ---- the dispatch policy: which scan serves the next step of `remaining` queries, and how many of them it takes.  The ONE place
 // that decides; step_queries (how many queries the host entry point stages) and scan_step (what runs) both ask here.
-enum class Scan { PQ, SQ, IVF_MULTI, I8, RQ, WIDE, EXACT };
+enum class Scan { PQ, SQ, SQ8, IVF_MULTI, I8, RQ, WIDE, EXACT };
 struct Step {
   Scan kind;
   int nq;
@@ -668,6 +673,8 @@ static Step choose_step(const knnx_index* ix, int remaining, int k) {
   if (ix->pq.m) return {Scan::PQ, std::min(PQ_PASS, remaining), false};  // IVF-PQ: its own pass, dispatched beside the fp16 scans
   // IVF-SQ8: always its multi-block pass (one block for <= 32 queries; a block needs a workgroup of its own: KNNX_GRID can set few)
   if (ix->sq.on) return {Scan::SQ, std::min(KNN_NQ * std::max(1, std::min(IVFM_BLK, ix->n_cu)), remaining), false};
+  // flat SQ8: the list scan for <= 32 queries, the one-pass batch scan of the codes above that (knnx_sq8.hip)
+  if (ix->fsq.on) return {Scan::SQ8, sq8_step_queries(ix, remaining), false};
   if (ivfm_usable(ix, remaining, k)) return {Scan::IVF_MULTI, std::min(IVFM_BLK * KNN_NQ, remaining), false};
   const bool i8 = i8_usable(ix, remaining, k);
   // d = 1280, measured (DESIGN 4.3 "Width 1280", tools/knn_d1280_batch.py): a step of 25 .. 32 queries is no faster through the int8
@@ -702,6 +709,7 @@ static int scan_step(knnx_index* ix, const float* q_dev, int remaining, int k, f
     switch (s.kind) {
       case Scan::PQ: return scan_topk_pq(ix, q_dev, s.nq, k, D_out, I_out, st);
       case Scan::SQ: return scan_topk_sq(ix, q_dev, s.nq, k, D_out, I_out, st);
+      case Scan::SQ8: return scan_topk_sq8(ix, q_dev, s.nq, k, D_out, I_out, st);
       case Scan::IVF_MULTI: return scan_topk_ivf_multi(ix, q_dev, s.nq, k, D_out, I_out, st);
       case Scan::I8: return scan_topk_i8(ix, q_dev, s.nq, k, D_out, I_out, st);
       case Scan::RQ: return scan_topk_rq(ix, q_dev, s.nq, k, D_out, I_out, st);
@@ -743,7 +751,9 @@ extern "C" int knnx_search_device(knnx_index* ix, const float* q_dev, int n, int
                                   void* stream) {
   if (!ix || !q_dev || !D_dev || !I_dev || n < 0 || k <= 0) return fail(KNNX_E_ARG, "bad search arguments");
   if (k > KNNX_MAX_K_FAST)
-    return fail(KNNX_E_UNSUPPORTED, ix->sq.on ? "k > 64 is not supported on an IVF-SQ8 index" : "device-buffer search supports k <= 64");
+    return fail(KNNX_E_UNSUPPORTED, ix->sq.on    ? "k > 64 is not supported on an IVF-SQ8 index"
+                                    : ix->fsq.on ? "k > 64 is not supported on a flat SQ8 index"
+                                                 : "device-buffer search supports k <= 64");
   std::lock_guard<std::mutex> lk(ix->mu);
   if (set_dev(ix)) return KNNX_E_HIP;
   hipStream_t st = stream ? (hipStream_t)stream : ix->stream;
@@ -881,7 +891,8 @@ static int co_run_batch_locked(knnx_index* ix, std::vector<CoReq*>& b) {
     HIPCHK(hipStreamSynchronize(st));  // the pinned buffer is reused below
     if (ix->pq.m && (r = pq_decode_rows(ix, ids_dev, nrow, rows_dev, st))) return r;
     if (ix->sq.on && (r = sq_decode_rows(ix, ids_dev, nrow, rows_dev, st))) return r;
-    hipError_t e = (ix->pq.m || ix->sq.on) ? hipSuccess
+    if (ix->fsq.on && (r = sq8_decode_rows(ix, ids_dev, nrow, rows_dev, st))) return r;
+    hipError_t e = (ix->pq.m || ix->sq.on || ix->fsq.on) ? hipSuccess
                    : ix->ivf_nlist ? launch_gather_inv(ix->rows, d, ix->id_base, ix->ntotal, ix->ivf.inv, ids_dev, nrow, rows_dev, st)
                                    : launch_gather(ix->rows, ix->ntotal, d, ix->id_base, ids_dev, nrow, rows_dev, st);
     if (e != hipSuccess) return fail(KNNX_E_HIP, std::string("coalesced gather: ") + hipGetErrorString(e));
@@ -998,6 +1009,7 @@ extern "C" int knnx_search_dedup(knnx_index* ix, const float* q, int k, float* D
                                  int32_t* pairs, int pairs_cap, int* n_pairs) {
   if (!ix || !q || !D || !I || k <= 0 || !pairs || pairs_cap < 0 || !n_pairs) return fail(KNNX_E_ARG, "bad search_dedup arguments");
   if (k > KNNX_MAX_K_FAST) return fail(KNNX_E_UNSUPPORTED, "search_dedup serves k <= 64 (larger answers: knnx_search + knnx_range_search_once)");
+  if (const int r0 = sq8_refuse(ix, "knnx_search_dedup")) return r0;
   CoReq me{q, k, D, I, R_or_null, true, dedup_thr, pairs, pairs_cap, n_pairs};
   *n_pairs = 0;
   if (ix->co.on) return co_submit(ix, me);
@@ -1012,6 +1024,7 @@ int search_locked(knnx_index* ix, const float* q, int n, int k, float* D, int64_
                                                  : fail(KNNX_E_UNSUPPORTED, "k > 64 is not supported on an IVF-PQ index"))
          : ix->sq.on            ? (ix->sq.thr.on ? search_large_k_thr_locked(ix, sq_thr_pass(), q, n, k, D, I)
                                                  : fail(KNNX_E_UNSUPPORTED, "k > 64 is not supported on an IVF-SQ8 index"))
+         : ix->fsq.on           ? fail(KNNX_E_UNSUPPORTED, "k > 64 is not supported on a flat SQ8 index")
                                 : search_large_k_locked(ix, q, n, k, D, I);
 }
 
@@ -1026,6 +1039,8 @@ extern "C" int knnx_search(knnx_index* ix, const float* q, int n, int k, float* 
     std::lock_guard<std::mutex> lk(ix->mu);
     if (!ix->sq.thr.on) return fail(KNNX_E_UNSUPPORTED, "k > 64 is not supported on an IVF-SQ8 index");
   }
+  if (k > KNNX_MAX_K_FAST)
+    if (const int r0 = sq8_refuse(ix, "k > 64")) return r0;
   if (n == 0) return KNNX_OK;
   if (n == 1 && k <= KNNX_MAX_K_FAST && ix->co.on) {  // concurrent single-query callers share one scan
     CoReq me{q, k, D, I, R, false, 0.f, nullptr, 0, nullptr};
@@ -1063,8 +1078,9 @@ extern "C" int knnx_reconstruct(knnx_index* ix, const int64_t* ids, int64_t n, f
     e = hipMemcpyAsync(ids_dev, ids_pin, (size_t)m * sizeof(int64_t), hipMemcpyHostToDevice, ix->stream);
     if (e == hipSuccess && ix->pq.m && (r = pq_decode_rows(ix, ids_dev, m, out_dev, ix->stream))) return r;
     if (e == hipSuccess && ix->sq.on && (r = sq_decode_rows(ix, ids_dev, m, out_dev, ix->stream))) return r;
+    if (e == hipSuccess && ix->fsq.on && (r = sq8_decode_rows(ix, ids_dev, m, out_dev, ix->stream))) return r;
     if (e == hipSuccess)
-      e = (ix->pq.m || ix->sq.on) ? hipSuccess
+      e = (ix->pq.m || ix->sq.on || ix->fsq.on) ? hipSuccess
           : ix->ivf_nlist ? launch_gather_inv(ix->rows, ix->d, ix->id_base, ix->ntotal, ix->ivf.inv, ids_dev, m, out_dev, ix->stream)
                           : launch_gather(ix->rows, ix->ntotal, ix->d, ix->id_base, ids_dev, m, out_dev, ix->stream);
     if (e == hipSuccess)

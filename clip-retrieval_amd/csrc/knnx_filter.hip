@@ -26,6 +26,7 @@ extern "C" int knnx_search_filtered(knnx_index* ix, const float* q, int k, int d
                                         std::to_string(k));
   if (!ix || !q || !D || !I || !drop || k <= 0) return fail(KNNX_E_ARG, "bad search_filtered arguments");
   if (const int r0 = pq_refine_sq8_refuse(ix, "search_filtered")) return r0;
+  if (const int r0 = sq8_refuse(ix, "knnx_search_filtered")) return r0;
   if (!dedup_on && !violence && !safety) return fail(KNNX_E_ARG, "search_filtered: no filter asked for (knnx_search is the call for that)");
   if (d_user <= 0 || d_user > ix->d)
     return fail(KNNX_E_ARG, "search_filtered: d_user = " + std::to_string(d_user) + " must be in [1, d = " + std::to_string(ix->d) + "]");

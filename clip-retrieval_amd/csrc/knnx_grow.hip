@@ -47,6 +47,7 @@ int hip_fail(const char* who, hipError_t e) {
 // an index that can grow: built, IVF, owning its rows
 int grow_refuse(const knnx_index* ix, const char* who) {
   if (const int r = pq_refine_sq8_refuse(ix, who)) return r;
+  if (const int r = sq8_refuse(ix, who)) return r;
   if (ix->ivfb.nlist)
     return fail(KNNX_E_ARG, std::string(who) + ": the index is between knnx_ivf_begin and knnx_ivf_end (finish the build first; nothing was added)");
   if (!ix->ivf_nlist || !ix->cent) return fail(KNNX_E_ARG, std::string(who) + ": not a built IVF index (nothing was added)");
@@ -355,6 +356,8 @@ extern "C" int knnx_ivf_merge_from(knnx_index* ix, knnx_index* other) {
   // (either side with the sq8 refine store: refused here, before a byte of `other` is staged; the flag is settled before the build)
   if (const int r0 = pq_refine_sq8_refuse(ix, who)) return r0;
   if (const int r0 = pq_refine_sq8_refuse(other, std::string(who) + " (other)")) return r0;
+  if (const int r0 = sq8_refuse(ix, who)) return r0;
+  if (const int r0 = sq8_refuse(other, std::string(who) + " (other)")) return r0;
   MergeSrc M;
   int r;
   {  // ---- other, under its own lock: its description and every row in arena order, staged on the host.  It is left untouched.

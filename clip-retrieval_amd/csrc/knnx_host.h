@@ -416,6 +416,42 @@ struct SqScratch {
   }
 };
 
+// Flat SQ8 (knnx_sq8_set_quantizer on an empty non-IVF index; knnx_sq8.hip, knn_sq_kernels.hip "Flat SQ8"): the arena holds d code bytes
+// per row in ID order, tile-padded to 32 rows (`rows` stays null; knnx_index::capacity counts its rows); no lists, no idmap, no inv
+struct Sq8Flat {
+  bool on = false;
+  std::vector<float> vmin_h, vdiff_h;  // the quantiser as it was given (knnx_sq8_get_quantizer)
+  DevBuf<float> vmin, scale, step;     // [d]; scale = 255 / vdiff and step = vdiff / 255 from the host, 0 where vdiff == 0
+  DevBuf<uint8_t> codes;               // [capacity][d]
+  // the list scan's view of the arena (steps of <= 32 queries): one work item per tile; rebuilt when ntotal changed
+  DevBuf<uint4> work;                  // [capacity / 32]
+  DevBuf<unsigned> nwork;              // [1]
+  int64_t work_rows = -1;              // ntotal the work list describes
+  // scratch of one step, allocated by the first search: u, fragments, biases, inverse scales, thresholds; the partial lists of the
+  // one-pass batch scan ([n_cu][128][64])
+  DevBuf<float> u, bq, inv;
+  DevBuf<_Float16> qfrag;
+  DevBuf<int> thr;
+  DevBuf<float> part_s;
+  DevBuf<uint32_t> part_i;
+  DevBuf<int> part_n;
+  hipError_t alloc_scratch(int d, size_t G) {
+    if (u) return hipSuccess;
+    const size_t Q = 128;
+    hipError_t e = hipSuccess;
+    dev_alloc(e, u, Q * d);
+    dev_alloc(e, qfrag, (Q / 32) * (size_t)d * 64);
+    dev_alloc(e, bq, Q);
+    dev_alloc(e, inv, Q);
+    dev_alloc(e, thr, Q);
+    dev_alloc(e, part_s, G * Q * KNNX_MAX_K_FAST);
+    dev_alloc(e, part_i, G * Q * KNNX_MAX_K_FAST);
+    dev_alloc(e, part_n, G * Q);
+    if (e != hipSuccess) u.reset(), qfrag.reset(), bq.reset(), inv.reset(), thr.reset(), part_s.reset(), part_i.reset(), part_n.reset();
+    return e;
+  }
+};
+
 // list-ordered ids (knnx_ivf.hip: knnx_ivf_id_order / knnx_ivf_map_ids; include/knnx.h "List-ordered ids").  Empty until the first call.
 // The layout it reads (ivf.tile0 / size / idmap / inv) does not change once the index is built, so this group has a mutex and a stream
 // of its own: a translation on the request path never queues behind the scans that hold knnx_index::mu.
@@ -562,6 +598,7 @@ struct knnx_index {
   PqScratch pqs;
   SqData sq;
   SqScratch sqs;
+  Sq8Flat fsq;
   IdOrder ido;
   GrowStats grow;
   ShrinkStats shrink;
@@ -644,6 +681,18 @@ inline int sq_pass_max(const knnx_index* ix) { return KNN_NQ * std::max(1, std::
 const ThrPass& sq_thr_pass();
 // decoded rows of n ids (device) -> out f32 [n][d]; -1 -> 0xFF bytes
 int sq_decode_rows(knnx_index* ix, const int64_t* ids_dev, int64_t n, float* out_dev, hipStream_t st);
+
+// knnx_sq8.hip (flat SQ8)
+// one step over the code arena: <= 32 queries through the list scan, more (an index of at least rq_min_rows rows) through the one-pass
+// batch scan; sq8_step_queries says how many of `remaining` the step takes
+int sq8_step_queries(const knnx_index* ix, int remaining);
+int scan_topk_sq8(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out, int64_t* I_out, hipStream_t st);
+int sq8_decode_rows(knnx_index* ix, const int64_t* ids_dev, int64_t n, float* out_dev, hipStream_t st);
+int sq8_reserve_locked(knnx_index* ix, int64_t n_rows);
+int sq8_add_locked(knnx_index* ix, const void* rows, int64_t n, bool is_f32);
+// what a flat SQ8 index does not serve (range_search, k > 64, search_dedup, search_filtered, attach, the IVF build protocol, grow /
+// shrink, shards): 0, or KNNX_E_UNSUPPORTED with a message that names the mode.  Host only: called before any HIP call of `who`.
+int sq8_refuse(const knnx_index* ix, const std::string& who);
 
 // the int8 copy is an accelerator, not data: whoever needs device memory and cannot get it takes the copy's back and tries once more
 // (the lazily built copy must not starve the range pools / large-k scratch that fitted before it existed)

@@ -195,6 +195,7 @@ extern "C" int knnx_ivf_set_lists(knnx_index* ix, int nlist, const uint16_t* cen
   if (ix->rows.borrowed) return fail(KNNX_E_STATE, "IVF needs an index that owns its rows");
   if (ix->pq.m) return fail(KNNX_E_STATE, "an IVF-PQ index is built through knnx_ivf_begin / knnx_ivf_add_assigned / knnx_ivf_end");
   if (ix->sq.on) return fail(KNNX_E_STATE, "an IVF-SQ8 index is built through knnx_ivf_begin / knnx_ivf_add_assigned / knnx_ivf_end");
+  if (const int r0 = sq8_refuse(ix, "knnx_ivf_set_lists (the IVF build)")) return r0;
   if (ix->ivf_nlist) return fail(KNNX_E_STATE, "lists are already set");
   TileLayout t;
   int r = ivf_tile_layout(nlist, list_sizes, t);
@@ -462,6 +463,7 @@ extern "C" int knnx_ivfb_list_sizes(knnx_ivf_builder* b, int64_t* sizes_out, int
 extern "C" int knnx_ivf_begin(knnx_index* ix, int nlist, const uint16_t* centroids_f16, const int64_t* list_sizes) {
   if (!ix || nlist <= 0 || !centroids_f16 || !list_sizes) return fail(KNNX_E_ARG, "bad ivf_begin arguments");
   std::lock_guard<std::mutex> lk(ix->mu);
+  if (const int r0 = sq8_refuse(ix, "knnx_ivf_begin (the IVF build)")) return r0;
   if (set_dev(ix)) return KNNX_E_HIP;
   if (ix->rows.borrowed || ix->ntotal != 0 || ix->ivf_nlist || ix->ivfb.nlist) return fail(KNNX_E_STATE, "ivf_begin needs an empty index that owns its rows");
   // the centroids, and with them the encoder, live in the quantiser space: dq = d unless the index was given a d_out

@@ -150,6 +150,7 @@ extern "C" int knnx_ivfsq_set_quantizer(knnx_index* ix, const float* vmin, const
   std::lock_guard<std::mutex> lk(ix->mu);
   if (set_dev(ix)) return KNNX_E_HIP;
   if (ix->pq.m) return fail(KNNX_E_STATE, "the IVF-SQ8 quantizer cannot be set on an IVF-PQ index");
+  if (ix->fsq.on) return fail(KNNX_E_STATE, "the IVF-SQ8 quantizer cannot be set on a flat SQ8 index");
   if (ix->rows.borrowed || ix->rows || ix->ntotal != 0 || ix->ivf_nlist || ix->ivfb.nlist || ix->sq.on)
     return fail(KNNX_E_STATE, "the IVF-SQ8 quantizer is set once, on an empty index, before knnx_ivf_begin");
   // scale and step in fp32 with IEEE division, here on the host: what numpy float32 computes, bit for bit

@@ -267,6 +267,7 @@ extern "C" int knnx_range_search(knnx_index* ix, const float* q, int n, float th
   if ((D == nullptr) != (I == nullptr)) return fail(KNNX_E_ARG, "D and I must both be null or both be set");
   std::lock_guard<std::mutex> lk(ix->mu);
   if (pq_range_refusal(ix)) return KNNX_E_UNSUPPORTED;
+  if (const int r0 = sq8_refuse(ix, "range_search")) return r0;
   if (set_dev(ix)) return KNNX_E_HIP;
   const bool fill = D != nullptr;
   const ThrPass* P = thr_pass_of(ix);
@@ -306,6 +307,7 @@ extern "C" int knnx_range_search_once(knnx_index* ix, const float* q, int n, flo
   if (!ix || !lims || (n > 0 && !q) || n < 0 || capacity < 0 || (capacity > 0 && (!D || !I))) return fail(KNNX_E_ARG, "bad range_search_once arguments");
   std::lock_guard<std::mutex> lk(ix->mu);
   if (pq_range_refusal(ix)) return KNNX_E_UNSUPPORTED;
+  if (const int r0 = sq8_refuse(ix, "range_search")) return r0;
   if (set_dev(ix)) return KNNX_E_HIP;
   const ThrPass* P = thr_pass_of(ix);
   const int step = range_step(ix, P);

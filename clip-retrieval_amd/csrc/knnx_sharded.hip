@@ -202,6 +202,8 @@ extern "C" int knnx_shards_adopt(int n_shards, knnx_index* const* shards, const 
     if (!shards[g] || knnx_dim(shards[g]) != d) return fail(KNNX_E_ARG, "shards disagree on the dimension");
   for (int g = 0; g < n_shards; ++g)
     if (const int r = pq_refine_sq8_refuse(shards[g], "knnx_shards_adopt (the sharded index)")) return r;
+  for (int g = 0; g < n_shards; ++g)
+    if (const int r = sq8_refuse(shards[g], "knnx_shards_adopt (the sharded index)")) return r;
   // IVF-PQ shards answer in one space only if they quantise the same width behind the same rotation (bit for bit), or none
   for (int g = 1; g < n_shards; ++g)
     if (pq_dq(shards[g]) != pq_dq(shards[0]))

@@ -38,6 +38,7 @@ int hip_fail(const char* who, hipError_t e) {
 // an index that can shrink: built, IVF, owning its rows
 int shrink_refuse(const knnx_index* ix, const char* who) {
   if (const int r = pq_refine_sq8_refuse(ix, who)) return r;
+  if (const int r = sq8_refuse(ix, who)) return r;
   if (ix->ivfb.nlist)
     return fail(KNNX_E_ARG, std::string(who) + ": the index is between knnx_ivf_begin and knnx_ivf_end (finish the build first; nothing was removed)");
   if (!ix->ivf_nlist || !ix->cent) return fail(KNNX_E_ARG, std::string(who) + ": not a built IVF index (nothing was removed)");

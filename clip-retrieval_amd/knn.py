@@ -16,11 +16,13 @@ from .knn_build import (FolderRows, _add_assigned_chunks, _assign_chunks, _downl
                         _release_cached_device_memory, _remember_folder, _scatter_into_ivf, append_new_folder_rows, build_ivf_index,
                         build_ivf_index_device, build_ivf_index_from_folder, build_ivfpq_index, build_ivfpq_index_device,
                         build_ivfpq_index_from_folder, build_ivfsq_index, build_ivfsq_index_device, build_ivfsq_index_from_folder,
-                        embedding_files)
+                        build_sq8_index, build_sq8_index_device, embedding_files)
 from .knn_index import (_SCAN_QUERIES, METRIC_INNER_PRODUCT, Mi355xIndex, ShardedMi355xIndex, _as_queries, _FaissShaped, _map_ids_call,
                         _own_handle, _pad_rotation, _shard_handles, _threshold_scan_property, _threshold_stats, get_old_to_new_mapping,
                         search_to_new_ids)
-from .knn_store import (IVF_FORMAT, IVF_MANIFEST, IVFPQ_FORMAT, IVFPQ_MANIFEST, IVFPQ_REFINE_RANGES, IVFPQ_ROTATION, IVFSQ_FORMAT, IVFSQ_MANIFEST,
+from .knn_store import (FLAT_SQ8_FORMAT, FLAT_SQ8_MANIFEST, _load_flat_sq8_index, _save_flat_sq8_index, check_flat_sq8_files,
+                        check_flat_sq8_manifest, flat_sq8_manifest,
+                        IVF_FORMAT, IVF_MANIFEST, IVFPQ_FORMAT, IVFPQ_MANIFEST, IVFPQ_REFINE_RANGES, IVFPQ_ROTATION, IVFSQ_FORMAT, IVFSQ_MANIFEST,
                         _add_code_chunks, _ivfpq_from_codes, _ivfpq_refine_from_rows, _ivfsq_from_codes, _load_ivf_index, _load_ivfpq_index,
                         _load_ivfsq_index, _save_ivfpq_index, _save_ivfsq_index, _split_saved_rows, check_ivfsq_manifest, ivfpq_out_dim_entry,
                         ivfpq_threshold_scan_entry, ivfsq_manifest, ivfsq_threshold_scan_entry, load_index, read_ivf_manifest,

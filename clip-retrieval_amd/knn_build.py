@@ -564,6 +564,57 @@ def build_ivfpq_index_device(fill_rows, n, d, nlist, M, nprobe=16, niter=8, pq_n
                    "code_arena_bytes": code_bytes, "row_arena_bytes": row_bytes}
 
 
+def _sq8_from_chunks(chunks, d, ranges, device, id_base, reserve):
+    index = Mi355xIndex(d, device=device, id_base=id_base)
+    index.set_sq8_quantizer(*ranges)
+    index.reserve(reserve)
+    for _, rows in chunks:
+        index.add(np.ascontiguousarray(rows, dtype=np.float16))
+    return index
+
+
+def build_sq8_index(rows_or_folder, device=0, id_base=0, ranges=None, chunk=1 << 20, sample_rows=1 << 20):
+    """fp16 rows [N, d], or a `clip inference` output folder (img_emb_*.npy), -> HBM-resident flat SQ8 index (faiss "SQ8": one code
+    byte per dimension, exhaustive search; ids = id_base + row number).  `ranges` ((vmin, vdiff), f32 [d]) are trained on the rows
+    (an array) or on a strided sample of the folder by train_sq_ranges unless given; the rows are then encoded chunk by chunk and
+    not kept.  Shards of one index MUST share the ranges.  The result can be save_index()ed (codes, not rows)."""
+    if isinstance(rows_or_folder, (str, os.PathLike, FolderRows)):
+        src = rows_or_folder if isinstance(rows_or_folder, FolderRows) else FolderRows(rows_or_folder)
+        if ranges is None:
+            ranges = train_sq_ranges(_folder_sample(src, min(src.n, int(sample_rows))), device=device, chunk=chunk)
+        return _remember_folder(_sq8_from_chunks(src.chunks(0, src.n, chunk), src.d, ranges, device, 0, src.n), src)
+    x = rows_or_folder
+    if ranges is None:
+        ranges = train_sq_ranges(x, device=device, chunk=chunk)
+    return _sq8_from_chunks(_array_chunks(x, chunk)(), x.shape[1], ranges, device, id_base, x.shape[0])
+
+
+def build_sq8_index_device(fill_rows, n, d, device=0, id_base=0, ranges=None, chunk=1 << 20, alloc=None, sample_rows=1 << 20):
+    """Flat SQ8 index over n rows PRODUCED ON THE GPU (`fill_rows(dst_ptr, row0, count, stride)` as in build_ivf_index_device, which
+    must have COMPLETED when it returns; d % 256 == 0): the fp16 corpus never exists whole -- a strided training sample for the ranges
+    (knnx_colminmax_device, unless given), then one chunk at a time is produced, encoded (knnx_sq8_add_device_f16) and dropped.
+    Returns (index, stats dict)."""
+    alloc = alloc or _torch_alloc(device)
+    t0 = time.time()
+    if ranges is None:
+        n_sample = int(min(n, sample_rows))
+        sample_ptr, sample_keep = _device_sample(alloc, fill_rows, n, n_sample, d)
+        ranges = train_sq_ranges(sample_ptr, n_sample, d, device=device)
+        del sample_keep
+    t1 = time.time()
+    index = Mi355xIndex(d, device=device, id_base=id_base)
+    index.set_sq8_quantizer(*ranges)
+    index.reserve(n)
+    rows = min(int(chunk), int(n))
+    ptr, keep = alloc(rows * d * 2)
+    for o in range(0, n, rows):
+        m = min(rows, n - o)
+        fill_rows(ptr, o, m, 1)
+        index.add_sq8_device_rows(ptr, m)
+    del keep
+    return index, {"train_s": t1 - t0, "encode_s": time.time() - t1, "bytes_per_row": d, "arena_bytes": (n + 31) // 32 * 32 * d}
+
+
 def _ivfsq_begin(d, nlist, centroids, ranges, sizes, device, id_base, threshold_scan=False):
     index = Mi355xIndex(d, device=device, id_base=id_base)
     index.set_sq_quantizer(*ranges)

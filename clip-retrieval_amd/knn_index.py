@@ -478,6 +478,48 @@ class Mi355xIndex(_FaissShaped):
         the index was created (include/knnx.h: knnx_ivfsq_threshold_stats)."""
         return _threshold_stats(self, "ivfsq")
 
+    # ------------------------------------------------------------------ flat SQ8
+    def set_sq8_quantizer(self, vmin, vdiff):
+        """Make this EMPTY flat index a flat SQ8 one (faiss IndexScalarQuantizer(d, QT_8bit), the "SQ8" factory string): vmin, vdiff
+        f32 [d] (train_sq_ranges), one code byte per dimension and nothing else per row.  add() then encodes the rows it is given
+        (include/knnx.h: "Flat SQ8").  Padding columns get vmin = vdiff = 0."""
+        vmin = np.asarray(vmin, dtype=np.float32).reshape(-1)
+        vdiff = np.asarray(vdiff, dtype=np.float32).reshape(-1)
+        if vmin.shape != (self.d,) or vdiff.shape != (self.d,):
+            raise AssertionError(f"vmin and vdiff must be [{self.d}], got {vmin.shape} and {vdiff.shape}")
+        a, b = np.zeros(self._dpad, dtype=np.float32), np.zeros(self._dpad, dtype=np.float32)
+        a[: self.d], b[: self.d] = vmin, vdiff
+        check(self._lib, self._lib.knnx_sq8_set_quantizer(self._h, a.ctypes.data, b.ctypes.data), "knnx")
+
+    @property
+    def is_sq8(self):
+        """True on a flat SQ8 index."""
+        return bool(self._lib.knnx_sq8(self._h)) if self._h else False
+
+    def sq8_quantizer(self):
+        """(vmin, vdiff) f32 [d] as they were given."""
+        a, b = np.empty(self._dpad, dtype=np.float32), np.empty(self._dpad, dtype=np.float32)
+        check(self._lib, self._lib.knnx_sq8_get_quantizer(self._h, a.ctypes.data, b.ctypes.data), "knnx")
+        return np.ascontiguousarray(a[: self.d]), np.ascontiguousarray(b[: self.d])
+
+    def sq8_codes(self):
+        """codes u8 [ntotal, d] in id order: row i belongs to id id_base + i."""
+        codes = np.empty((self.ntotal, self._dpad), dtype=np.uint8)
+        check(self._lib, self._lib.knnx_sq8_get_codes(self._h, codes.ctypes.data), "knnx")
+        return np.ascontiguousarray(codes[:, : self.d])
+
+    def add_sq8_codes(self, codes):
+        """Append saved codes u8 [n, d] (id order) to a flat SQ8 index."""
+        codes = np.asarray(codes, dtype=np.uint8)
+        if codes.ndim != 2 or codes.shape[1] != self.d:
+            raise AssertionError(f"add_sq8_codes expects [n, {self.d}], got {codes.shape}")
+        c = np.ascontiguousarray(self._pad(codes))
+        check(self._lib, self._lib.knnx_sq8_add_codes(self._h, c.ctypes.data, c.shape[0]), "knnx")
+
+    def add_sq8_device_rows(self, dev_ptr, n_rows):
+        """Encode n fp16 rows already in HBM (width d_padded) into a flat SQ8 index; the rows are not kept."""
+        check(self._lib, self._lib.knnx_sq8_add_device_f16(self._h, C.c_void_p(int(dev_ptr)), int(n_rows)), "knnx")
+
     # ------------------------------------------------------------------ list-ordered ids (reorder_metadata_by_ivf_index)
     def map_ids(self, ids):
         """Result ids (any shape, int64) -> their list-ordered ids, -1 kept: np.take(ivf_old_to_new(), ids - id_base) without the

@@ -24,6 +24,8 @@ IVFPQ_REFINE_RANGES = "ivf_pq_refine_ranges.npy"  # f32 [2, d]: vmin, vdiff of a
 IVFPQ_FORMAT = "clip-retrieval_amd ivf-pq v1"
 IVFSQ_MANIFEST = "ivf_sq_manifest.json"
 IVFSQ_FORMAT = "clip-retrieval_amd ivf-sq8 v1"
+FLAT_SQ8_MANIFEST = "flat_sq8_manifest.json"
+FLAT_SQ8_FORMAT = "clip-retrieval_amd flat-sq8 v1"
 
 
 def _write_manifest(folder, name, man):
@@ -108,6 +110,8 @@ def load_index(path, device=0, row_range=None, enable_faiss_memory_mapping=False
         return _load_ivfsq_index(path, device=device, row_range=row_range, devices=devices)
     if os.path.isfile(os.path.join(path, IVF_MANIFEST)):  # a built IVF-Flat index saved by save_index(): no k-means, no assignment
         return _load_ivf_index(path, device=device, row_range=row_range, devices=devices)
+    if os.path.isfile(os.path.join(path, FLAT_SQ8_MANIFEST)):  # a saved flat SQ8 index: ranges and codes
+        return _load_flat_sq8_index(path, device=device, row_range=row_range, devices=devices)
     src = FolderRows(path)
     files, shapes, d, total = src.files, src.shapes, src.d, src.n
     lo, hi = (0, total) if row_range is None else row_range
@@ -140,6 +144,8 @@ def save_index(index, folder, embeddings_folder=None):
         return _save_ivfpq_index(index, folder, embeddings_folder)
     if getattr(index, "is_sq", False):
         return _save_ivfsq_index(index, folder)
+    if getattr(index, "is_sq8", False):
+        return _save_flat_sq8_index(index, folder)
     lists, cent = getattr(index, "ivf_lists", None), getattr(index, "ivf_centroids", None)
     src = getattr(index, "ivf_source", None)
     if lists is None or cent is None:
@@ -401,6 +407,65 @@ def check_ivfsq_manifest(man, where=""):
     if not (int(man["d"]) > 0 and int(man["nlist"]) > 0 and 0 <= int(lo) <= int(hi) and int(man["nprobe"]) >= 1):
         raise ValueError(f"{where}: inconsistent IVF-SQ8 manifest {man}")
     return man
+
+
+def flat_sq8_manifest(d, row_range):
+    """The manifest of a saved flat SQ8 folder (kind "flat_sq8")."""
+    return {"format": FLAT_SQ8_FORMAT, "kind": "flat_sq8", "d": int(d), "row_range": [int(row_range[0]), int(row_range[1])]}
+
+
+def check_flat_sq8_manifest(man, where=""):
+    """A manifest read back: the format and the kind must be this one's, the numbers consistent.  Returns it."""
+    if not isinstance(man, dict) or man.get("format") != FLAT_SQ8_FORMAT or man.get("kind") != "flat_sq8":
+        raise ValueError(f"{where}: not a flat SQ8 manifest (format {man.get('format')!r}, kind {man.get('kind')!r})" if isinstance(man, dict)
+                         else f"{where}: not a flat SQ8 manifest")
+    d, rr = man.get("d"), man.get("row_range")
+    ints = lambda v: isinstance(v, int) and not isinstance(v, bool)  # noqa: E731
+    if not ints(d) or d <= 0 or not isinstance(rr, list) or len(rr) != 2 or not all(ints(v) for v in rr) or not 0 <= rr[0] <= rr[1]:
+        raise ValueError(f"{where}: inconsistent flat SQ8 manifest {man}")
+    return man
+
+
+def check_flat_sq8_files(man, vmin, vdiff, codes, where=""):
+    """The arrays of a flat SQ8 folder against its manifest: shapes and types."""
+    d, (lo, hi) = man["d"], man["row_range"]
+    if vmin.shape != (d,) or vdiff.shape != (d,) or vmin.dtype != np.float32 or vdiff.dtype != np.float32:
+        raise ValueError(f"{where}: the flat SQ8 ranges disagree with the manifest (d = {d})")
+    if codes.dtype != np.uint8 or codes.shape != (hi - lo, d):
+        raise ValueError(f"{where}: the flat SQ8 codes {codes.shape} {codes.dtype} disagree with the manifest ({hi - lo} rows of {d} bytes)")
+
+
+def _save_flat_sq8_index(index, folder):
+    """The self-contained flat SQ8 folder: flat_sq8_vmin.npy / flat_sq8_vdiff.npy (f32 [d]), flat_sq8_codes.npy (u8 [n, d] in id
+    order) and flat_sq8_manifest.json (kind "flat_sq8", written last)."""
+    codes = index.sq8_codes()
+    vmin, vdiff = index.sq8_quantizer()
+    lo = int(getattr(index, "_id_base", 0))
+    os.makedirs(folder, exist_ok=True)
+    np.save(os.path.join(folder, "flat_sq8_vmin.npy"), vmin)
+    np.save(os.path.join(folder, "flat_sq8_vdiff.npy"), vdiff)
+    np.save(os.path.join(folder, "flat_sq8_codes.npy"), codes)
+    return _write_manifest(folder, FLAT_SQ8_MANIFEST, flat_sq8_manifest(index.d, (lo, lo + codes.shape[0])))
+
+
+def _load_flat_sq8_index(folder, device=0, row_range=None, devices=None, chunk=1 << 20):
+    if devices is not None:
+        raise ValueError("a flat SQ8 index is not sharded over devices yet (load one row_range per process)")
+    man = check_flat_sq8_manifest(_read_manifest(folder, FLAT_SQ8_MANIFEST), folder)
+    vmin = np.load(os.path.join(folder, "flat_sq8_vmin.npy"))
+    vdiff = np.load(os.path.join(folder, "flat_sq8_vdiff.npy"))
+    codes = np.load(os.path.join(folder, "flat_sq8_codes.npy"), mmap_mode="r")
+    check_flat_sq8_files(man, vmin, vdiff, codes, folder)
+    slo, shi = man["row_range"]
+    lo, hi = (slo, shi) if row_range is None else (int(row_range[0]), int(row_range[1]))
+    if not slo <= lo <= hi <= shi:
+        raise ValueError(f"row_range {row_range} is outside the saved shard's rows [{slo}, {shi})")
+    index = Mi355xIndex(man["d"], device=device, id_base=lo)
+    index.set_sq8_quantizer(vmin, vdiff)
+    index.reserve(hi - lo)
+    for o in range(lo - slo, hi - slo, chunk):
+        index.add_sq8_codes(np.asarray(codes[o:min(o + chunk, hi - slo)]))
+    return index
 
 
 def _save_ivfsq_index(index, folder):

@@ -391,6 +391,32 @@ int knnx_ivfsq_get_codes(knnx_index* ix, int64_t* ids, int32_t* lists, uint8_t* 
 int knnx_ivfsq_set_threshold_scan(knnx_index* ix, int on);
 int knnx_ivfsq_threshold_scan(const knnx_index* ix);   /* 0 / 1; 0 on a non-SQ8 or null index */
 int knnx_ivfsq_threshold_stats(knnx_index* ix, int64_t* queries, int64_t* launches, int64_t* query_scans, int64_t* hits);
+
+/* ---- Flat SQ8: faiss IndexScalarQuantizer(d, QT_8bit, METRIC_INNER_PRODUCT), the "SQ8" factory string ---------------------------------
+ * Exhaustive search over ONE code byte per dimension and nothing else per row: d bytes against the 2 d of the flat fp16 index.  The arena
+ * is u8 [capacity][d] in id order, tile-padded to 32 rows, growing as the flat arena grows; ids are positions (id_base + i), there is
+ * no idmap.  No fp16 row is kept.
+ * Contract: that of the IVF-SQ8 block above, word for word -- vmin / vdiff [d], scale = 255 / vdiff and step = vdiff / 255 derived on
+ * the host in fp32 (0 where vdiff == 0); the same encode and decode (the same bytes, the same floats); score(q, row) = b_q + sum_j u_j
+ * code_j with u = q * step (scaled by a power of two per query) and b_q = <q, vmin + step / 2>, hi and lo fp16 parts of u both
+ * accumulated in fp32; results by score descending, then id ascending, padded with -1 / -FLT_MAX.  A step of 1 .. 32 queries runs the
+ * IVF-SQ8 list scan over the whole arena; a larger step on an index of at least KNNX_RQ_MIN_ROWS rows runs the one-pass batch scan,
+ * which reads every code byte ONCE for up to 128 queries (d <= 512; 64 at d = 768, 1024 and 1280) and scores with the same operands in
+ * another fp32 summation order.  Widths: 256, 512, 768, 1024, 1280 (pad columns: vdiff = 0, code 0).  k <= 64.
+ * knnx_sq8_set_quantizer: on an EMPTY index that is not an IVF index and has no quantiser (anything else: KNNX_E_STATE; KNNX_E_ARG
+ * for a null pointer, a non-finite entry or a negative vdiff).  Afterwards knnx_add_f16 / knnx_add_f32 ENCODE the rows they are
+ * given, knnx_sq8_add_device_f16 encodes n fp16 rows already in HBM (and does not keep them), knnx_sq8_add_codes appends host codes
+ * [n][d] in id order; knnx_reserve, knnx_reset, knnx_search, knnx_search_device, knnx_reconstruct (decoded rows, as the R of
+ * knnx_search), knnx_ntotal, knnx_dim and knnx_set_id_base serve the index.  knnx_sq8_get_quantizer: vmin / vdiff as given;
+ * knnx_sq8_get_codes: codes [ntotal][d] (host); knnx_sq8: 1 on a flat SQ8 index, 0 otherwise.
+ * Not served (KNNX_E_UNSUPPORTED, the message says "flat SQ8"): knnx_range_search*, k > 64, knnx_search_dedup, knnx_search_filtered,
+ * knnx_attach_device_f16, knnx_synth_fill, the IVF build protocol, the append / merge / remove calls, knnx_shards_adopt. */
+int knnx_sq8_set_quantizer(knnx_index* ix, const float* vmin, const float* vdiff);
+int knnx_sq8_get_quantizer(knnx_index* ix, float* vmin, float* vdiff);
+int knnx_sq8(const knnx_index* ix); /* 0 / 1 */
+int knnx_sq8_add_codes(knnx_index* ix, const uint8_t* codes, int64_t n);
+int knnx_sq8_add_device_f16(knnx_index* ix, const void* rows_dev_f16, int64_t n);
+int knnx_sq8_get_codes(knnx_index* ix, uint8_t* codes);
 /* The training kernel (faiss RS_minmax with argument 0): per-column min and max of n fp16 rows [n][d] in HBM, 0 < d <= 1280, n > 0 ->
  * host f32 vmin_out [d], vmax_out [d].  Min and max do not depend on the order of the rows: bit-equal to numpy's
  * x.astype(float32).min(0) / .max(0).  `stream`: hipStream_t or NULL; synchronous. */

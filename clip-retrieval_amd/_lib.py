@@ -132,6 +132,9 @@ SIGNATURES = {
     "knnx_sq8_add_codes": (C.c_int, [_P, _P, C.c_int64]),
     "knnx_sq8_add_device_f16": (C.c_int, [_P, _P, C.c_int64]),
     "knnx_sq8_get_codes": (C.c_int, [_P, _P]),
+    "knnx_sq8_set_threshold_scan": (C.c_int, [_P, C.c_int]),
+    "knnx_sq8_threshold_scan": (C.c_int, [_P]),
+    "knnx_sq8_threshold_stats": (C.c_int, [_P, _P, _P, _P, _P]),
     "knnx_rotate_f16_device": (C.c_int, [C.c_int, _P, _P, C.c_int64, C.c_int, _P, _P]),
     "knnx_rotate_rect_f16_device": (C.c_int, [C.c_int, _P, _P, C.c_int64, C.c_int, C.c_int, _P, _P]),
     "knnx_xty_device": (C.c_int, [C.c_int, _P, _P, C.c_int64, C.c_int, _P, _P]),

@@ -347,6 +347,12 @@ int sq_rq_queries_per_pass(int d);
 // NQP = sq_rq_queries_per_pass(d); k <= 64.  Merge: launch_merge_u32(.., P = grid, nq_stride = NQP, kin = k, ..) without an id map.
 hipError_t launch_sq_rq_scan(const uint8_t* codes, int64_t n, int d, const _Float16* qfrag, const float* bq, const float* inv, int nq, int k,
                              int* thr_g, float* part_s, uint32_t* part_i, int* part_n, int grid, hipStream_t st);
+// Threshold mode of that pass (knn_sq_rq_range_scan_kernel): every row r < n whose score is > rthr[q] (strict; +INFINITY: the query is
+// finished and never hits) is appended to query q's slice hit_s / hit_i [q * rcap ..] as (score, arena row); rcnt [nq] (cleared here)
+// counts the hits and stays exact when a slice overflows.  The scores are those of launch_sq_rq_scan, bit for bit.  nq * rcap must be
+// indexable by 32 bits.
+hipError_t launch_sq_rq_range_scan(const uint8_t* codes, int64_t n, int d, const _Float16* qfrag, const float* bq, const float* inv, int nq,
+                                   const float* rthr, unsigned* rcnt, unsigned rcap, float* hit_s, uint32_t* hit_i, int grid, hipStream_t st);
 // the work list launch_sq_scan walks over a flat arena of n rows: work [ceil(n / 32)] = {tile, all queries, valid rows}, *nwork = tiles
 hipError_t launch_sq_flat_worklist(int64_t n, uint4* work, unsigned* nwork, hipStream_t st);
 // launch_sq_decode with identity addressing: arena row = id - id_lo

@@ -680,6 +680,60 @@ constexpr size_t sqrq_smem_bytes(int d) {
   return (size_t)2 * 32 * d + (sqrq_ksplit(d) == 2 ? (size_t)2 * 64 * 16 * 4 : 0) + (size_t)nqp * SQRQ_CAP * 8 + (size_t)nqp * 8 + 16;
 }
 
+// The pass has two kernels, top-k (knn_sq_rq_scan_kernel) and threshold mode (knn_sq_rq_range_scan_kernel, below it).  What makes a
+// (query, row) score -- the stationary fragments, the staging of a tile, the k-steps, the hand-over of the column halves -- is ONE text,
+// the macros here, expanded in both: the same operands in the same order, so a score is the same fp32 value in both modes.  (A shared
+// __forceinline__ body templated on the mode, as the list scan has, was tried first: it changes the register allocation and the
+// schedule of all five top-k instantiations.  Macros leave the top-k kernel the token sequence it had.)  They use the kernels' locals.
+#define SQRQ_FRAGMENTS                                                                                 \
+  {                                                                                                    \
+    const half8* src = reinterpret_cast<const half8*>(qfrag) + (size_t)qb * KS * 2 * 64 + lane;       \
+    _Pragma("unroll") for (int j = 0; j < KW; ++j) {                                                   \
+      Qh[j] = src[((kh * KW + j) * 2 + 0) * 64];                                                       \
+      Ql[j] = src[((kh * KW + j) * 2 + 1) * 64];                                                       \
+    }                                                                                                  \
+    _Pragma("unroll") for (int j = 0; j < KW; ++j) {                                                   \
+      asm volatile("" : "+v"(Qh[j]));                                                                  \
+      asm volatile("" : "+a"(Ql[j]));                                                                  \
+    }                                                                                                  \
+  }
+#define SQRQ_GLOAD(tt_, H_)                                                                  \
+  {                                                                                          \
+    const uint4v* src_ = reinterpret_cast<const uint4v*>(X + (size_t)(tt_) * TILE);           \
+    _Pragma("unroll") for (int i = 0; i < LPH; ++i) pf[i] = src_[256 * ((H_) * LPH + i) + tid]; \
+  }
+#define SQRQ_LSTORE(slot_, H_)                                                                               \
+  {                                                                                                          \
+    _Pragma("unroll") for (int i = 0; i < LPH; ++i) {                                                        \
+      const int g_ = 256 * ((H_) * LPH + i) + tid;                                                           \
+      const int r_ = g_ / CPR, c_ = g_ - r_ * CPR;                                                           \
+      *reinterpret_cast<uint4v*>(ring + (slot_) * TILE + (c_ >> 1) * 1024 + (32 * (c_ & 1) + r_) * 16) = pf[i]; \
+    }                                                                                                        \
+  }
+#define SQRQ_KSTEPS(J0_, J1_)                                                               \
+  _Pragma("unroll") for (int j = (J0_); j < (J1_); ++j) {                                   \
+    const uint4v a = *reinterpret_cast<const uint4v*>(xs + j * 1024);                       \
+    const half8 x0 = sq_codes_half8(a[0], a[1]);                                             \
+    const half8 x1 = sq_codes_half8(a[2], a[3]);                                             \
+    acc_h = __builtin_amdgcn_mfma_f32_32x32x16_f16(x0, Qh[2 * j], acc_h, 0, 0, 0);          \
+    acc_l = __builtin_amdgcn_mfma_f32_32x32x16_f16(x0, Ql[2 * j], acc_l, 0, 0, 0);          \
+    acc_h = __builtin_amdgcn_mfma_f32_32x32x16_f16(x1, Qh[2 * j + 1], acc_h, 0, 0, 0);      \
+    acc_l = __builtin_amdgcn_mfma_f32_32x32x16_f16(x1, Ql[2 * j + 1], acc_l, 0, 0, 0);      \
+  }
+// sc[r] = lo / 2048 + hi of this wave's columns; KSPLIT = 2: the upper-half wave hands its 16 sums to the owner through xch and ONE barrier
+#define SQRQ_HALVES_MEET                                                                    \
+  _Pragma("unroll") for (int r = 0; r < 16; ++r) sc[r] = sq_mul_add(acc_l[r], KNN_LO_INV, acc_h[r]); \
+  if constexpr (KSPLIT == 2) {                                                              \
+    float* xq = xch + qb * (16 * 64) + lane;                                                \
+    if (!owner) {                                                                           \
+      _Pragma("unroll") for (int r = 0; r < 16; ++r) xq[64 * r] = sc[r];                    \
+    }                                                                                       \
+    __syncthreads();                                                                        \
+    if (owner) {                                                                            \
+      _Pragma("unroll") for (int r = 0; r < 16; ++r) sc[r] += xq[64 * r];                   \
+    }                                                                                       \
+  }
+
 template <int D, int KSPLIT>
 __global__ __launch_bounds__(256, 1) void knn_sq_rq_scan_kernel(
     const uint8_t* __restrict__ X, int64_t N, const _Float16* __restrict__ qfrag, const float* __restrict__ bq_g,
@@ -715,19 +769,7 @@ __global__ __launch_bounds__(256, 1) void knn_sq_rq_scan_kernel(
 
   // the stationary operand: hi and lo fragments of block qb, k-steps kh KW .. + KW - 1, loaded once
   half8 Qh[KW], Ql[KW];
-  {
-    const half8* src = reinterpret_cast<const half8*>(qfrag) + (size_t)qb * KS * 2 * 64 + lane;
-#pragma unroll
-    for (int j = 0; j < KW; ++j) {
-      Qh[j] = src[((kh * KW + j) * 2 + 0) * 64];
-      Ql[j] = src[((kh * KW + j) * 2 + 1) * 64];
-    }
-#pragma unroll
-    for (int j = 0; j < KW; ++j) {
-      asm volatile("" : "+v"(Qh[j]));
-      asm volatile("" : "+a"(Ql[j]));
-    }
-  }
+  SQRQ_FRAGMENTS
   for (int i = tid; i < NQP; i += 256) { sm.cnt[i] = 0; sm.thr[i] = enc_f(-INFINITY); }
   if (tid < 4) sm.flag[tid] = 0;
 
@@ -737,29 +779,6 @@ __global__ __launch_bounds__(256, 1) void knn_sq_rq_scan_kernel(
 
   // staging: chunk g = 256 i + tid of the tile, i < LPT -- row g / CPR, chunk g % CPR of the row; half H of the chunks at a time
   uint4v pf[LPH];
-#define SQRQ_GLOAD(tt_, H_)                                                                  \
-  {                                                                                          \
-    const uint4v* src_ = reinterpret_cast<const uint4v*>(X + (size_t)(tt_) * TILE);           \
-    _Pragma("unroll") for (int i = 0; i < LPH; ++i) pf[i] = src_[256 * ((H_) * LPH + i) + tid]; \
-  }
-#define SQRQ_LSTORE(slot_, H_)                                                                               \
-  {                                                                                                          \
-    _Pragma("unroll") for (int i = 0; i < LPH; ++i) {                                                        \
-      const int g_ = 256 * ((H_) * LPH + i) + tid;                                                           \
-      const int r_ = g_ / CPR, c_ = g_ - r_ * CPR;                                                           \
-      *reinterpret_cast<uint4v*>(ring + (slot_) * TILE + (c_ >> 1) * 1024 + (32 * (c_ & 1) + r_) * 16) = pf[i]; \
-    }                                                                                                        \
-  }
-#define SQRQ_KSTEPS(J0_, J1_)                                                               \
-  _Pragma("unroll") for (int j = (J0_); j < (J1_); ++j) {                                   \
-    const uint4v a = *reinterpret_cast<const uint4v*>(xs + j * 1024);                       \
-    const half8 x0 = sq_codes_half8(a[0], a[1]);                                             \
-    const half8 x1 = sq_codes_half8(a[2], a[3]);                                             \
-    acc_h = __builtin_amdgcn_mfma_f32_32x32x16_f16(x0, Qh[2 * j], acc_h, 0, 0, 0);          \
-    acc_l = __builtin_amdgcn_mfma_f32_32x32x16_f16(x0, Ql[2 * j], acc_l, 0, 0, 0);          \
-    acc_h = __builtin_amdgcn_mfma_f32_32x32x16_f16(x1, Qh[2 * j + 1], acc_h, 0, 0, 0);      \
-    acc_l = __builtin_amdgcn_mfma_f32_32x32x16_f16(x1, Ql[2 * j + 1], acc_l, 0, 0, 0);      \
-  }
   if (t < ntile) {
     SQRQ_GLOAD(t, 0)
     SQRQ_LSTORE(0, 0)
@@ -785,26 +804,10 @@ __global__ __launch_bounds__(256, 1) void knn_sq_rq_scan_kernel(
     }
     SQRQ_KSTEPS(KW / 4, KW / 2)
     if (more) SQRQ_LSTORE(slot ^ 1, 1)
-#undef SQRQ_GLOAD
-#undef SQRQ_LSTORE
-#undef SQRQ_KSTEPS
 
     // ---- the column halves meet: lane (q, hb) of the upper-half wave holds the same (row, query) entries as the owner's lane
     float sc[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) sc[r] = sq_mul_add(acc_l[r], KNN_LO_INV, acc_h[r]);
-    if constexpr (KSPLIT == 2) {
-      float* xq = xch + qb * (16 * 64) + lane;
-      if (!owner) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) xq[64 * r] = sc[r];
-      }
-      __syncthreads();  // (the filter's barrier (A) below separates these reads from the next tile's writes)
-      if (owner) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sc[r] += xq[64 * r];
-      }
-    }
+    SQRQ_HALVES_MEET  // (the filter's barrier (A) below separates the owner's reads from the next tile's writes)
 
     // ---- filter (the list scan's): lane (q, hb) owns rows row0 + (r & 3) + 8 (r >> 2) of query qq
     const int64_t row0 = t * 32 + 4 * hb;
@@ -870,6 +873,116 @@ __global__ __launch_bounds__(256, 1) void knn_sq_rq_scan_kernel(
   if (tid < NQP) part_n[wg * NQP + tid] = sm.cnt[tid];
 }
 
+// Threshold mode of the pass (k > 64 and range_search on an index with the threshold-scan switch on, groups of more than 32 queries):
+// the same four waves, stationary fragments (hi in the architectural file, lo in the accumulation file), ring, staging halves, k-step
+// order and hand-over -- the macros above -- and the same two roundings around inv_q and b_q, but no candidate queues, no prune, no
+// shared thresholds, no partial lists: the LDS holds the ring and the exchange buffer only (64 d bytes, + 8 KiB at KSPLIT = 2).
+//   * every lane reads its query's threshold rthr[qq] ONCE into a register; +INFINITY (a finished query; also what a lane past nq
+//     holds) never hits;
+//   * an owner lane holds 16 rows of ONE query: it marks the rows r < N with score > threshold (strict, as the list scan's threshold
+//     mode), takes popc(marks) entries of the query's slice [rcap] of hit_s / hit_i with ONE atomicAdd on rcnt[qq] and writes (score,
+//     arena row) while below rcap -- the counter goes on past rcap, so it is exact when the slice overflows (the host regrows the pools
+//     and scans again).  A lane without a mark issues nothing: at the hit rates of a descent (k of N rows) most tiles pass with the
+//     compare alone;
+//   * nothing is appended to the LDS, so the filter's barriers (A) (B) (C) shrink to ONE per tile: it publishes the next tile's LDS
+//     stores and lets the slot just read -- and, KSPLIT = 2, the exchange buffer the owners just read -- be written again.
+constexpr size_t sqrq_range_smem_bytes(int d) { return (size_t)2 * 32 * d + (sqrq_ksplit(d) == 2 ? (size_t)2 * 64 * 16 * 4 : 0); }
+
+template <int D, int KSPLIT>
+__global__ __launch_bounds__(256, 1) void knn_sq_rq_range_scan_kernel(
+    const uint8_t* __restrict__ X, int64_t N, const _Float16* __restrict__ qfrag, const float* __restrict__ bq_g,
+    const float* __restrict__ inv_g, int nq, const float* __restrict__ rthr, unsigned* __restrict__ rcnt, unsigned rcap,
+    float* __restrict__ hit_s, uint32_t* __restrict__ hit_i) {
+  constexpr int KS = D / 16, KW = KS / KSPLIT;  // (the shape constants of knn_sq_rq_scan_kernel)
+  constexpr int NQB = 4 / KSPLIT;
+  constexpr int TILE = 32 * D;
+  constexpr int CPR = D / 16;
+  constexpr int LPT = D / 128, LPH = LPT / 2;
+  static_assert(KW % 2 == 0 && LPT % 2 == 0, "whole 32-column pieces, two staging halves");
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  unsigned char* ring = smem_raw;
+  float* xch = reinterpret_cast<float*>(smem_raw + 2 * TILE);  // [NQB][16][64] (KSPLIT = 2 only)
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int qb = w & (NQB - 1), kh = w / NQB;
+  const int q = lane & 31, hb = lane >> 5;
+  const int qq = 32 * qb + q;
+  const bool owner = kh == 0;
+  const bool q_ok = owner && qq < nq;
+  const float inv_q = qq < nq ? inv_g[qq] : 0.f;
+  const float b_q = qq < nq ? bq_g[qq] : 0.f;
+  const float thr_q = qq < nq ? rthr[qq] : INFINITY;
+  const unsigned slice_q = (unsigned)qq * rcap;  // (the launcher checks that nq x rcap entries are indexed by 32 bits)
+
+  half8 Qh[KW], Ql[KW];
+  SQRQ_FRAGMENTS
+
+  const int64_t ntile = (N + 31) >> 5;
+  const int64_t G = gridDim.x;
+  int64_t t = blockIdx.x;
+  uint4v pf[LPH];
+  if (t < ntile) {
+    SQRQ_GLOAD(t, 0)
+    SQRQ_LSTORE(0, 0)
+    SQRQ_GLOAD(t, 1)
+    SQRQ_LSTORE(0, 1)
+  }
+  __syncthreads();
+
+  int slot = 0;
+  for (; t < ntile; t += G) {
+    const int64_t tn = t + G;
+    const bool more = tn < ntile;  // (the same in every wave of the workgroup)
+    if (more) SQRQ_GLOAD(tn, 0)
+    float16v acc_h, acc_l;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { acc_h[r] = 0.f; acc_l[r] = 0.f; }
+    const unsigned char* xs = ring + slot * TILE + (kh * (KW / 2)) * 1024 + lane * 16;
+    SQRQ_KSTEPS(0, KW / 4)
+    // the other slot was last read before the previous tile's barrier: every wave is past it
+    if (more) {
+      SQRQ_LSTORE(slot ^ 1, 0)
+      SQRQ_GLOAD(tn, 1)
+    }
+    SQRQ_KSTEPS(KW / 4, KW / 2)
+    if (more) SQRQ_LSTORE(slot ^ 1, 1)
+
+    float sc[16];
+    SQRQ_HALVES_MEET
+
+    // ---- compare and write out: lane (q, hb) of an owner wave holds rows row0 + (r & 3) + 8 (r >> 2) of query qq
+    const int64_t row0 = t * 32 + 4 * hb;
+    unsigned hit = 0;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float v = sq_mul_add(sc[r], inv_q, b_q);
+      sc[r] = v;
+      const int64_t row = row0 + (r & 3) + 8 * (r >> 2);
+      if (v > thr_q && row < N && q_ok) hit |= 1u << r;
+    }
+    if (hit) {
+      unsigned at = atomicAdd(&rcnt[qq], (unsigned)__popc(hit));  // (hit != 0 implies an owner lane with qq < nq)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        if (hit & (1u << r)) {
+          if (at < rcap) {
+            hit_s[slice_q + at] = sc[r];
+            hit_i[slice_q + at] = (uint32_t)(row0 + (r & 3) + 8 * (r >> 2));
+          }
+          ++at;
+        }
+      }
+    }
+    __syncthreads();  // the one barrier of the tile (see the head)
+    slot ^= 1;
+  }
+}
+#undef SQRQ_FRAGMENTS
+#undef SQRQ_GLOAD
+#undef SQRQ_LSTORE
+#undef SQRQ_KSTEPS
+#undef SQRQ_HALVES_MEET
+
 // work list of the list scan over a flat arena: one item {tile, every query, valid rows} per tile, *nwork = tiles
 __global__ void sq_flat_worklist_kernel(int64_t n, uint4* __restrict__ work, unsigned* __restrict__ nwork) {
   const int64_t ntile = (n + 31) >> 5;
@@ -904,6 +1017,34 @@ hipError_t launch_sq_rq_scan(const uint8_t* codes, int64_t n, int d, const _Floa
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
     if (e != hipSuccess) return e;                                                                                             \
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, st, codes, n, qfrag, bq, inv, nq, k, thr_g, part_s, part_i, part_n); \
+    return hipGetLastError();                                                                                                  \
+  }
+  switch (d) {
+    case 256: SQRQ_LAUNCH(256)
+    case 512: SQRQ_LAUNCH(512)
+    case 768: SQRQ_LAUNCH(768)
+    case 1024: SQRQ_LAUNCH(1024)
+    case 1280: SQRQ_LAUNCH(1280)
+    default: return hipErrorInvalidValue;
+  }
+#undef SQRQ_LAUNCH
+}
+
+// threshold mode of the pass: rcnt [nq] is cleared here
+hipError_t launch_sq_rq_range_scan(const uint8_t* codes, int64_t n, int d, const _Float16* qfrag, const float* bq, const float* inv, int nq,
+                                   const float* rthr, unsigned* rcnt, unsigned rcap, float* hit_s, uint32_t* hit_i, int grid, hipStream_t st) {
+  if (n <= 0 || nq < 1 || nq > sq_rq_queries_per_pass(d) || grid < 1 || !rthr || !rcnt || !hit_s || !hit_i) return hipErrorInvalidValue;
+  if ((uint64_t)nq * rcap > 0xffffffffull) return hipErrorInvalidValue;  // (the kernel indexes the pools with 32 bits)
+  hipError_t e = hipMemsetAsync(rcnt, 0, (size_t)nq * sizeof(unsigned), st);
+  if (e != hipSuccess) return e;
+#define SQRQ_LAUNCH(DD)                                                                                                        \
+  {                                                                                                                            \
+    auto kern = knn_sq_rq_range_scan_kernel<DD, sqrq_ksplit(DD)>;                                                              \
+    constexpr size_t smem = sqrq_range_smem_bytes(DD); /* the ring and the exchange buffer: no queues */                       \
+    static_assert(smem <= KNN_LDS_BYTES, "the ring must fit the LDS");                                                         \
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);       \
+    if (e != hipSuccess) return e;                                                                                             \
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, st, codes, n, qfrag, bq, inv, nq, rthr, rcnt, rcap, hit_s, hit_i);   \
     return hipGetLastError();                                                                                                  \
   }
   switch (d) {

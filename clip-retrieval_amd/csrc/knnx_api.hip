@@ -1024,7 +1024,8 @@ int search_locked(knnx_index* ix, const float* q, int n, int k, float* D, int64_
                                                  : fail(KNNX_E_UNSUPPORTED, "k > 64 is not supported on an IVF-PQ index"))
          : ix->sq.on            ? (ix->sq.thr.on ? search_large_k_thr_locked(ix, sq_thr_pass(), q, n, k, D, I)
                                                  : fail(KNNX_E_UNSUPPORTED, "k > 64 is not supported on an IVF-SQ8 index"))
-         : ix->fsq.on           ? fail(KNNX_E_UNSUPPORTED, "k > 64 is not supported on a flat SQ8 index")
+         : ix->fsq.on           ? (ix->fsq.thr_scan.on ? search_large_k_thr_locked(ix, sq8_thr_pass(), q, n, k, D, I)
+                                                       : fail(KNNX_E_UNSUPPORTED, "k > 64 is not supported on a flat SQ8 index"))
                                 : search_large_k_locked(ix, q, n, k, D, I);
 }
 
@@ -1039,8 +1040,10 @@ extern "C" int knnx_search(knnx_index* ix, const float* q, int n, int k, float* 
     std::lock_guard<std::mutex> lk(ix->mu);
     if (!ix->sq.thr.on) return fail(KNNX_E_UNSUPPORTED, "k > 64 is not supported on an IVF-SQ8 index");
   }
-  if (k > KNNX_MAX_K_FAST)
-    if (const int r0 = sq8_refuse(ix, "k > 64")) return r0;
+  if (ix->fsq.on && k > KNNX_MAX_K_FAST) {  // likewise, through the threshold mode of the flat SQ8 scans
+    std::lock_guard<std::mutex> lk(ix->mu);
+    if (const int r0 = sq8_refuse_unless_thr(ix, "k > 64")) return r0;
+  }
   if (n == 0) return KNNX_OK;
   if (n == 1 && k <= KNNX_MAX_K_FAST && ix->co.on) {  // concurrent single-query callers share one scan
     CoReq me{q, k, D, I, R, false, 0.f, nullptr, 0, nullptr};

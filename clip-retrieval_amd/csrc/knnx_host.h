@@ -256,8 +256,9 @@ struct IvfBuild {
   std::vector<uint64_t> taken;  // one bit per padded arena row
 };
 
-// threshold mode of a compressed index's list scan (IVF-PQ: the ADC scan, IVF-SQ8: the code scan): the switch, the counters of
-// knnx_ivf{pq,sq}_threshold_stats, and the device scratch of one threshold pass (allocated by the first one).  One per family.
+// threshold mode of a compressed index's scan (IVF-PQ: the ADC scan, IVF-SQ8: the code scan, flat SQ8: the list scan over the arena and
+// the one-pass batch scan): the switch, the counters of knnx_{ivfpq,ivfsq,sq8}_threshold_stats, and the device scratch of one threshold
+// pass (allocated by the first one).  One per family.
 struct ThrState {
   bool on = false;  // knnx_ivf{pq,sq}_set_threshold_scan: k > 64 and range_search are served; off: they are refused
   // since the index was created: queries served with k > 64, threshold scans launched (one launch serves a whole group), scans summed
@@ -435,6 +436,7 @@ struct Sq8Flat {
   DevBuf<float> part_s;
   DevBuf<uint32_t> part_i;
   DevBuf<int> part_n;
+  ThrState thr_scan;                   // threshold mode of the two scans (knnx_sq8_set_threshold_scan)
   hipError_t alloc_scratch(int d, size_t G) {
     if (u) return hipSuccess;
     const size_t Q = 128;
@@ -616,11 +618,12 @@ struct knnx_index {
 // the width of the quantiser space of an IVF-PQ index: d unless knnx_ivfpq_set_out_dim gave another
 inline int pq_dq(const knnx_index* ix) { return ix->pq.dq ? ix->pq.dq : ix->d; }
 
-// What the threshold passes of the two compressed families differ in (pq_thr_pass(): knnx_ivfpq.hip, sq_thr_pass(): knnx_ivfsq.hip);
-// knnx_range.hip drives either through this table.  A pass is one front half over <= pass_max queries already in HBM, then the
-// k = 64 scan, the probed-row totals and any number of threshold scans over what the front half left in the family's scratch.
+// What the threshold passes of the compressed families differ in (pq_thr_pass(): knnx_ivfpq.hip, sq_thr_pass(): knnx_ivfsq.hip,
+// sq8_thr_pass(): knnx_sq8.hip); knnx_range.hip drives any of them through this table.  A pass is one front half over <= pass_max queries
+// already in HBM, then the k = 64 scan, the probed-row totals and any number of threshold scans over what the front half left in the
+// family's scratch.  (Flat SQ8 has no lists: every row is "probed".)
 struct ThrPass {
-  const char* family;                        // "IVF-PQ" / "IVF-SQ8", for the messages
+  const char* family;                        // "IVF-PQ" / "IVF-SQ8" / "flat SQ8", for the messages
   bool (*is)(const knnx_index* ix);          // the index belongs to the family
   ThrState& (*thr)(knnx_index* ix);          // its threshold state
   int (*pass_max)(const knnx_index* ix);     // queries of one pass at most
@@ -690,9 +693,13 @@ int scan_topk_sq8(knnx_index* ix, const float* q_dev, int nq, int k, float* D_ou
 int sq8_decode_rows(knnx_index* ix, const int64_t* ids_dev, int64_t n, float* out_dev, hipStream_t st);
 int sq8_reserve_locked(knnx_index* ix, int64_t n_rows);
 int sq8_add_locked(knnx_index* ix, const void* rows, int64_t n, bool is_f32);
-// what a flat SQ8 index does not serve (range_search, k > 64, search_dedup, search_filtered, attach, the IVF build protocol, grow /
-// shrink, shards): 0, or KNNX_E_UNSUPPORTED with a message that names the mode.  Host only: called before any HIP call of `who`.
+// what a flat SQ8 index does not serve (search_dedup, search_filtered, attach, the IVF build protocol, grow / shrink, shards; range_search
+// and k > 64 while the threshold-scan switch is off): 0, or KNNX_E_UNSUPPORTED with a message that names the mode.  Host only: called
+// before any HIP call of `who`.
 int sq8_refuse(const knnx_index* ix, const std::string& who);
+// range_search and k > 64 (who): refused unless the index has the threshold scan switched on.  Caller holds ix->mu.
+int sq8_refuse_unless_thr(const knnx_index* ix, const std::string& who);
+const ThrPass& sq8_thr_pass();
 
 // the int8 copy is an accelerator, not data: whoever needs device memory and cannot get it takes the copy's back and tries once more
 // (the lazily built copy must not starve the range pools / large-k scratch that fitted before it existed)

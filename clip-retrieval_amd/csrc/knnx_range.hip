@@ -241,8 +241,10 @@ static int range_scan_thr(knnx_index* ix, const ThrPass& P, const float* q_host,
   }
 }
 
-// the pass table of a compressed index, null for a flat or IVF-Flat one
-static const ThrPass* thr_pass_of(const knnx_index* ix) { return ix->pq.m ? &pq_thr_pass() : ix->sq.on ? &sq_thr_pass() : nullptr; }
+// the pass table of a compressed index, null for a flat fp16 or IVF-Flat one
+static const ThrPass* thr_pass_of(const knnx_index* ix) {
+  return ix->pq.m ? &pq_thr_pass() : ix->sq.on ? &sq_thr_pass() : ix->fsq.on ? &sq8_thr_pass() : nullptr;
+}
 
 // the range scan of one step of knnx_range_search[_once]: <= range_step(ix) queries
 static int range_step(const knnx_index* ix, const ThrPass* P) { return P ? P->pass_max(ix) : KNN_NQ; }
@@ -267,7 +269,7 @@ extern "C" int knnx_range_search(knnx_index* ix, const float* q, int n, float th
   if ((D == nullptr) != (I == nullptr)) return fail(KNNX_E_ARG, "D and I must both be null or both be set");
   std::lock_guard<std::mutex> lk(ix->mu);
   if (pq_range_refusal(ix)) return KNNX_E_UNSUPPORTED;
-  if (const int r0 = sq8_refuse(ix, "range_search")) return r0;
+  if (const int r0 = sq8_refuse_unless_thr(ix, "range_search")) return r0;
   if (set_dev(ix)) return KNNX_E_HIP;
   const bool fill = D != nullptr;
   const ThrPass* P = thr_pass_of(ix);
@@ -307,7 +309,7 @@ extern "C" int knnx_range_search_once(knnx_index* ix, const float* q, int n, flo
   if (!ix || !lims || (n > 0 && !q) || n < 0 || capacity < 0 || (capacity > 0 && (!D || !I))) return fail(KNNX_E_ARG, "bad range_search_once arguments");
   std::lock_guard<std::mutex> lk(ix->mu);
   if (pq_range_refusal(ix)) return KNNX_E_UNSUPPORTED;
-  if (const int r0 = sq8_refuse(ix, "range_search")) return r0;
+  if (const int r0 = sq8_refuse_unless_thr(ix, "range_search")) return r0;
   if (set_dev(ix)) return KNNX_E_HIP;
   const ThrPass* P = thr_pass_of(ix);
   const int step = range_step(ix, P);
@@ -315,7 +317,7 @@ extern "C" int knnx_range_search_once(knnx_index* ix, const float* q, int n, flo
   bool fits = true;
   std::vector<unsigned> counts;
   lims[0] = 0;
-  if (!ix->ivf_nlist && n > KNN_NQ && ix->ntotal <= RANGE_BATCH_MAX_ROWS) {  // small flat index, many queries: one synchronisation
+  if (!P && !ix->ivf_nlist && n > KNN_NQ && ix->ntotal <= RANGE_BATCH_MAX_ROWS) {  // small flat fp16 index, many queries: one synchronisation
     unsigned cap = 0;
     unsigned* cnt_dev = nullptr;
     int r = range_scan_batched(ix, q, n, thresh, counts, &cap, &cnt_dev);
@@ -594,7 +596,7 @@ int search_large_k_thr_locked(knnx_index* ix, const ThrPass& P, const float* q, 
 int thr_set_switch(knnx_index* ix, const ThrPass& P, int on) {
   if (!ix) return fail(KNNX_E_ARG, "index is null");
   std::lock_guard<std::mutex> lk(ix->mu);
-  if (!P.is(ix)) return fail(KNNX_E_STATE, std::string("not an ") + P.family + " index");
+  if (!P.is(ix)) return fail(KNNX_E_STATE, std::string(P.family[0] == 'I' ? "not an " : "not a ") + P.family + " index");
   P.thr(ix).on = on != 0;
   return KNNX_OK;
 }
@@ -604,7 +606,7 @@ int thr_switch(const knnx_index* ix, const ThrPass& P) { return ix && P.is(ix) &
 int thr_stats(knnx_index* ix, const ThrPass& P, int64_t* queries, int64_t* launches, int64_t* query_scans, int64_t* hits) {
   if (!ix) return fail(KNNX_E_ARG, "index is null");
   std::lock_guard<std::mutex> lk(ix->mu);
-  if (!P.is(ix)) return fail(KNNX_E_STATE, std::string("not an ") + P.family + " index");
+  if (!P.is(ix)) return fail(KNNX_E_STATE, std::string(P.family[0] == 'I' ? "not an " : "not a ") + P.family + " index");
   const ThrState& T = P.thr(ix);
   if (queries) *queries = T.queries;
   if (launches) *launches = T.scans;

@@ -99,11 +99,13 @@ int sq8_step_queries(const knnx_index* ix, int remaining) {
   return std::min(remaining, sq8_batch_usable(ix, remaining) ? sq_rq_queries_per_pass(ix->d) : KNN_NQ);
 }
 
-int scan_topk_sq8(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out, int64_t* I_out, hipStream_t st) {
+// A step comes in two halves, like an IVF-SQ8 pass.  The front half (sq8_front) leaves u, its fragments, the biases and inverse scales
+// of the step's queries in ix->fsq and, for a step of <= 32 queries, the flat work list; the top-k step follows it with the scan of its
+// route and the merge, a threshold pass (the switch knnx_sq8_set_threshold_scan) with any number of threshold launches of that route.
+static int sq8_front(knnx_index* ix, const float* q_dev, int nq, hipStream_t st) {
   Sq8Flat& f = ix->fsq;
   const int d = ix->d;
-  const int cap = scan_cap(d, k);
-  if (nq < 1 || nq > 128 || k > KNNX_MAX_K_FAST || cap < 0) return fail(KNNX_E_STATE, "internal: flat SQ8 step misuse");
+  if (nq < 1 || nq > (nq > KNN_NQ ? sq_rq_queries_per_pass(d) : KNN_NQ)) return fail(KNNX_E_STATE, "internal: flat SQ8 step misuse");
   hipError_t e = f.alloc_scratch(d, (size_t)ix->n_cu);
   if (e == hipSuccess && !f.nwork) e = f.nwork.alloc(1);
   if (e != hipSuccess) {
@@ -112,6 +114,41 @@ int scan_topk_sq8(knnx_index* ix, const float* q_dev, int nq, int k, float* D_ou
   }
   HIPCHK(launch_sq_prep(q_dev, nq, d, f.vmin, f.step, f.u, f.bq, f.inv, st));
   HIPCHK(launch_prep_blocks(f.u, nq, d, f.qfrag, f.thr, nullptr, st));  // (resets the thresholds of the blocks it prepares)
+  // <= 32 queries: the list scan of IVF-SQ8 walks the arena as one run of tiles
+  if (nq <= KNN_NQ && ix->ntotal > 0 && f.work_rows != ix->ntotal) {
+    HIPCHK(launch_sq_flat_worklist(ix->ntotal, f.work, f.nwork, st));
+    f.work_rows = ix->ntotal;
+  }
+  return 0;
+}
+
+// workgroups of the one-pass batch scan
+static int sq8_rq_grid(const knnx_index* ix) { return (int)std::min<int64_t>(ix->n_cu, (ix->ntotal + 31) / 32); }
+
+// what both modes of the list scan read of the step whose front half is in ix->fsq (nq <= 32)
+static SqScanArgs sq8_list_args(const knnx_index* ix, int nq) {
+  const Sq8Flat& f = ix->fsq;
+  SqScanArgs a{};
+  a.codes = f.codes;
+  a.d = ix->d;
+  a.qfrag = f.qfrag;
+  a.bq = f.bq;
+  a.inv = f.inv;
+  a.nq = nq;
+  a.grid = ix->n_cu;
+  a.work = f.work;
+  a.nwork = f.nwork;
+  a.nblk = 1;
+  a.work_stride = (unsigned)(ix->capacity / 32);
+  return a;
+}
+
+// the top-k scan of the step's route over what the front half left, and the merge of its partial lists
+static int sq8_topk_scan_merge(knnx_index* ix, int nq, int k, float* D_out, int64_t* I_out, hipStream_t st) {
+  Sq8Flat& f = ix->fsq;
+  const int d = ix->d;
+  const int cap = scan_cap(d, k);
+  if (k > KNNX_MAX_K_FAST || cap < 0) return fail(KNNX_E_STATE, "internal: flat SQ8 step misuse");
   if (ix->ntotal == 0) {  // nothing to scan: every partial list empty
     HIPCHK(hipMemsetAsync(f.part_n, 0, (size_t)KNN_NQ * sizeof(int), st));
     HIPCHK(launch_merge_u32(f.part_s, f.part_i, f.part_n, 1, KNN_NQ, k, nq, k, ix->id_base, nullptr, D_out, I_out, nullptr, st));
@@ -120,43 +157,98 @@ int scan_topk_sq8(knnx_index* ix, const float* q_dev, int nq, int k, float* D_ou
   if (nq > KNN_NQ) {
     // the one-pass batch scan: every code byte once for the whole step
     const int nqp = sq_rq_queries_per_pass(d);
-    const int grid = (int)std::min<int64_t>(ix->n_cu, (ix->ntotal + 31) / 32);
-    if (nq > nqp) return fail(KNNX_E_STATE, "internal: flat SQ8 step misuse");
+    const int grid = sq8_rq_grid(ix);
     HIPCHK(ix->prof.begin(ix->prof.on, st));
     HIPCHK(launch_sq_rq_scan(f.codes, ix->ntotal, d, f.qfrag, f.bq, f.inv, nq, k, f.thr, f.part_s, f.part_i, f.part_n, grid, st));
     HIPCHK(ix->prof.end(ix->prof.on, st));
     HIPCHK(launch_merge_u32(f.part_s, f.part_i, f.part_n, grid, nqp, k, nq, k, ix->id_base, nullptr, D_out, I_out, nullptr, st));
     return 0;
   }
-  // <= 32 queries: the list scan of IVF-SQ8 over the arena as one run of tiles
-  if (f.work_rows != ix->ntotal) {
-    HIPCHK(launch_sq_flat_worklist(ix->ntotal, f.work, f.nwork, st));
-    f.work_rows = ix->ntotal;
-  }
-  SqScanArgs a{};
-  a.codes = f.codes;
-  a.d = d;
-  a.qfrag = f.qfrag;
-  a.bq = f.bq;
-  a.inv = f.inv;
-  a.nq = nq;
+  SqScanArgs a = sq8_list_args(ix, nq);
   a.k = k;
   a.cap = cap;
-  a.grid = ix->n_cu;
   a.thr_g = f.thr;
   a.part_s = ix->flat.part_s;
   a.part_i = ix->flat.part_i;
   a.part_n = ix->flat.part_n;
-  a.work = f.work;
-  a.nwork = f.nwork;
-  a.nblk = 1;
-  a.work_stride = (unsigned)(ix->capacity / 32);
   HIPCHK(ix->prof.begin(ix->prof.on, st));
   HIPCHK(launch_sq_scan(a, st));
   HIPCHK(ix->prof.end(ix->prof.on, st));
   HIPCHK(launch_merge_u32(ix->flat.part_s, ix->flat.part_i, ix->flat.part_n, ix->n_cu, KNN_NQ, k, nq, k, ix->id_base, nullptr, D_out, I_out,
                           nullptr, st));
   return 0;
+}
+
+int scan_topk_sq8(knnx_index* ix, const float* q_dev, int nq, int k, float* D_out, int64_t* I_out, hipStream_t st) {
+  if (k > KNNX_MAX_K_FAST || scan_cap(ix->d, k) < 0) return fail(KNNX_E_STATE, "internal: flat SQ8 step misuse");
+  int r = sq8_front(ix, q_dev, nq, st);
+  if (r) return r;
+  return sq8_topk_scan_merge(ix, nq, k, D_out, I_out, st);
+}
+
+// ---- threshold passes (the switch knnx_sq8_set_threshold_scan; knnx_range.hip drives them) ------------------------------------------
+// A group takes the route a step of its size takes at k <= 64 (sq8_step_queries): <= 32 queries the list scan over the flat work list,
+// more the one-pass batch scan -- so pass_max is the batch scan's queries per pass where that route is usable, 32 otherwise.
+static int sq8_pass_max(const knnx_index* ix) { return sq8_step_queries(ix, std::max(sq_rq_queries_per_pass(ix->d), KNN_NQ)); }
+
+// the top-64 scores of the pass whose front half is in place -> D64 host [nq][64], -FLT_MAX padded.  Synchronises.
+static int sq8_pass_top64(knnx_index* ix, int nq, float* D64, hipStream_t st) {
+  const int k = KNNX_MAX_K_FAST;
+  int r = sq8_topk_scan_merge(ix, nq, k, ix->flat.D_dev, ix->flat.I_dev, st);
+  if (r) return r;
+  HIPCHK(hipMemcpyAsync(D64, ix->flat.D_dev, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return 0;
+}
+
+// no lists: every query reaches every row
+static int sq8_pass_probed_rows(knnx_index* ix, int nq, std::vector<int64_t>& total, hipStream_t) {
+  total.assign((size_t)nq, ix->ntotal);
+  return 0;
+}
+
+// the threshold launch of the pass (ThrPass::launch_threshold); an empty index has no hits
+static int sq8_pass_launch_threshold(knnx_index* ix, int nq, unsigned cap, hipStream_t st) {
+  Sq8Flat& f = ix->fsq;
+  if (ix->ntotal == 0) {
+    HIPCHK(hipMemsetAsync(f.thr_scan.tcnt, 0, (size_t)nq * sizeof(unsigned), st));
+    return 0;
+  }
+  if (nq > KNN_NQ) {
+    HIPCHK(launch_sq_rq_range_scan(f.codes, ix->ntotal, ix->d, f.qfrag, f.bq, f.inv, nq, f.thr_scan.tthr, f.thr_scan.tcnt, cap, ix->range.s,
+                                   ix->range.i, sq8_rq_grid(ix), st));
+    return 0;
+  }
+  SqScanArgs a = sq8_list_args(ix, nq);
+  a.rthr = f.thr_scan.tthr;
+  a.rcnt = f.thr_scan.tcnt;
+  a.rcap = cap;
+  a.hit_s = ix->range.s;
+  a.hit_i = ix->range.i;
+  HIPCHK(launch_sq_range_scan(a, st));
+  return 0;
+}
+
+const ThrPass& sq8_thr_pass() {
+  static const ThrPass P = {
+    "flat SQ8",
+    [](const knnx_index* ix) { return ix->fsq.on; },
+    [](knnx_index* ix) -> ThrState& { return ix->fsq.thr_scan; },
+    sq8_pass_max,
+    sq8_front,
+    sq8_pass_top64,
+    sq8_pass_probed_rows,
+    sq8_pass_launch_threshold,
+  };
+  return P;
+}
+
+int sq8_refuse_unless_thr(const knnx_index* ix, const std::string& who) { return ix && ix->fsq.on && ix->fsq.thr_scan.on ? 0 : sq8_refuse(ix, who); }
+
+extern "C" int knnx_sq8_set_threshold_scan(knnx_index* ix, int on) { return thr_set_switch(ix, sq8_thr_pass(), on); }
+extern "C" int knnx_sq8_threshold_scan(const knnx_index* ix) { return thr_switch(ix, sq8_thr_pass()); }
+extern "C" int knnx_sq8_threshold_stats(knnx_index* ix, int64_t* queries, int64_t* launches, int64_t* query_scans, int64_t* hits) {
+  return thr_stats(ix, sq8_thr_pass(), queries, launches, query_scans, hits);
 }
 
 int sq8_decode_rows(knnx_index* ix, const int64_t* ids_dev, int64_t n, float* out_dev, hipStream_t st) {

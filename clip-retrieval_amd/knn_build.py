@@ -564,36 +564,45 @@ def build_ivfpq_index_device(fill_rows, n, d, nlist, M, nprobe=16, niter=8, pq_n
                    "code_arena_bytes": code_bytes, "row_arena_bytes": row_bytes}
 
 
-def _sq8_from_chunks(chunks, d, ranges, device, id_base, reserve):
+def _sq8_begin(d, ranges, device, id_base, reserve, threshold_scan=False):
     index = Mi355xIndex(d, device=device, id_base=id_base)
     index.set_sq8_quantizer(*ranges)
+    if threshold_scan:  # (off is the state of a new index: nothing is called for it)
+        index.sq8_threshold_scan = True
     index.reserve(reserve)
+    return index
+
+
+def _sq8_from_chunks(chunks, d, ranges, device, id_base, reserve, threshold_scan=False):
+    index = _sq8_begin(d, ranges, device, id_base, reserve, threshold_scan)
     for _, rows in chunks:
         index.add(np.ascontiguousarray(rows, dtype=np.float16))
     return index
 
 
-def build_sq8_index(rows_or_folder, device=0, id_base=0, ranges=None, chunk=1 << 20, sample_rows=1 << 20):
+def build_sq8_index(rows_or_folder, device=0, id_base=0, ranges=None, chunk=1 << 20, sample_rows=1 << 20, threshold_scan=False):
     """fp16 rows [N, d], or a `clip inference` output folder (img_emb_*.npy), -> HBM-resident flat SQ8 index (faiss "SQ8": one code
     byte per dimension, exhaustive search; ids = id_base + row number).  `ranges` ((vmin, vdiff), f32 [d]) are trained on the rows
     (an array) or on a strided sample of the folder by train_sq_ranges unless given; the rows are then encoded chunk by chunk and
-    not kept.  Shards of one index MUST share the ranges.  The result can be save_index()ed (codes, not rows)."""
+    not kept.  Shards of one index MUST share the ranges.  The result can be save_index()ed (codes, not rows).
+    threshold_scan=True switches on k > 64 and range_search (Mi355xIndex.sq8_threshold_scan; off by default)."""
     if isinstance(rows_or_folder, (str, os.PathLike, FolderRows)):
         src = rows_or_folder if isinstance(rows_or_folder, FolderRows) else FolderRows(rows_or_folder)
         if ranges is None:
             ranges = train_sq_ranges(_folder_sample(src, min(src.n, int(sample_rows))), device=device, chunk=chunk)
-        return _remember_folder(_sq8_from_chunks(src.chunks(0, src.n, chunk), src.d, ranges, device, 0, src.n), src)
+        return _remember_folder(_sq8_from_chunks(src.chunks(0, src.n, chunk), src.d, ranges, device, 0, src.n, threshold_scan), src)
     x = rows_or_folder
     if ranges is None:
         ranges = train_sq_ranges(x, device=device, chunk=chunk)
-    return _sq8_from_chunks(_array_chunks(x, chunk)(), x.shape[1], ranges, device, id_base, x.shape[0])
+    return _sq8_from_chunks(_array_chunks(x, chunk)(), x.shape[1], ranges, device, id_base, x.shape[0], threshold_scan)
 
 
-def build_sq8_index_device(fill_rows, n, d, device=0, id_base=0, ranges=None, chunk=1 << 20, alloc=None, sample_rows=1 << 20):
+def build_sq8_index_device(fill_rows, n, d, device=0, id_base=0, ranges=None, chunk=1 << 20, alloc=None, sample_rows=1 << 20,
+                           threshold_scan=False):
     """Flat SQ8 index over n rows PRODUCED ON THE GPU (`fill_rows(dst_ptr, row0, count, stride)` as in build_ivf_index_device, which
     must have COMPLETED when it returns; d % 256 == 0): the fp16 corpus never exists whole -- a strided training sample for the ranges
     (knnx_colminmax_device, unless given), then one chunk at a time is produced, encoded (knnx_sq8_add_device_f16) and dropped.
-    Returns (index, stats dict)."""
+    threshold_scan as in build_sq8_index.  Returns (index, stats dict)."""
     alloc = alloc or _torch_alloc(device)
     t0 = time.time()
     if ranges is None:
@@ -602,9 +611,7 @@ def build_sq8_index_device(fill_rows, n, d, device=0, id_base=0, ranges=None, ch
         ranges = train_sq_ranges(sample_ptr, n_sample, d, device=device)
         del sample_keep
     t1 = time.time()
-    index = Mi355xIndex(d, device=device, id_base=id_base)
-    index.set_sq8_quantizer(*ranges)
-    index.reserve(n)
+    index = _sq8_begin(d, ranges, device, id_base, n, threshold_scan)
     rows = min(int(chunk), int(n))
     ptr, keep = alloc(rows * d * 2)
     for o in range(0, n, rows):

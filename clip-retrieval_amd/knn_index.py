@@ -520,6 +520,15 @@ class Mi355xIndex(_FaissShaped):
         """Encode n fp16 rows already in HBM (width d_padded) into a flat SQ8 index; the rows are not kept."""
         check(self._lib, self._lib.knnx_sq8_add_device_f16(self._h, C.c_void_p(int(dev_ptr)), int(n_rows)), "knnx")
 
+    sq8_threshold_scan = _threshold_scan_property("sq8", _own_handle, """The threshold mode of the flat SQ8 scans (include/knnx.h:
+        knnx_sq8_set_threshold_scan): with it on, a flat SQ8 index serves k > 64 (up to 131 072) and range_search; off -- the
+        default -- it refuses both as it always has.  False on an index that is not flat SQ8; setting it there is an error.""")
+
+    def sq8_threshold_stats(self):
+        """(queries served with k > 64, threshold-scan launches, launches summed over the queries that took part, hits fetched) since
+        the index was created (include/knnx.h: knnx_sq8_threshold_stats)."""
+        return _threshold_stats(self, "sq8")
+
     # ------------------------------------------------------------------ list-ordered ids (reorder_metadata_by_ivf_index)
     def map_ids(self, ids):
         """Result ids (any shape, int64) -> their list-ordered ids, -1 kept: np.take(ivf_old_to_new(), ids - id_base) without the

@@ -43,8 +43,8 @@ def _read_manifest(folder, name):
 
 
 def threshold_scan_entry(on):
-    """What a saved IVF-PQ or IVF-SQ8 manifest says about the threshold-scan switch: {"threshold_scan": true} when it is on, nothing
-    otherwise."""
+    """What a saved IVF-PQ, IVF-SQ8 or flat SQ8 manifest says about the threshold-scan switch: {"threshold_scan": true} when it is on,
+    nothing otherwise."""
     return {"threshold_scan": True} if on else {}
 
 
@@ -423,6 +423,7 @@ def check_flat_sq8_manifest(man, where=""):
     ints = lambda v: isinstance(v, int) and not isinstance(v, bool)  # noqa: E731
     if not ints(d) or d <= 0 or not isinstance(rr, list) or len(rr) != 2 or not all(ints(v) for v in rr) or not 0 <= rr[0] <= rr[1]:
         raise ValueError(f"{where}: inconsistent flat SQ8 manifest {man}")
+    read_threshold_scan(where, man)  # (the optional key, when present, must be a bool)
     return man
 
 
@@ -437,7 +438,8 @@ def check_flat_sq8_files(man, vmin, vdiff, codes, where=""):
 
 def _save_flat_sq8_index(index, folder):
     """The self-contained flat SQ8 folder: flat_sq8_vmin.npy / flat_sq8_vdiff.npy (f32 [d]), flat_sq8_codes.npy (u8 [n, d] in id
-    order) and flat_sq8_manifest.json (kind "flat_sq8", written last)."""
+    order) and flat_sq8_manifest.json (kind "flat_sq8", written last).  An index with the threshold scan switched on adds
+    "threshold_scan": true (only then: other folders are byte-identical to before)."""
     codes = index.sq8_codes()
     vmin, vdiff = index.sq8_quantizer()
     lo = int(getattr(index, "_id_base", 0))
@@ -445,7 +447,9 @@ def _save_flat_sq8_index(index, folder):
     np.save(os.path.join(folder, "flat_sq8_vmin.npy"), vmin)
     np.save(os.path.join(folder, "flat_sq8_vdiff.npy"), vdiff)
     np.save(os.path.join(folder, "flat_sq8_codes.npy"), codes)
-    return _write_manifest(folder, FLAT_SQ8_MANIFEST, flat_sq8_manifest(index.d, (lo, lo + codes.shape[0])))
+    man = flat_sq8_manifest(index.d, (lo, lo + codes.shape[0]))
+    man.update(threshold_scan_entry(index.sq8_threshold_scan))
+    return _write_manifest(folder, FLAT_SQ8_MANIFEST, man)
 
 
 def _load_flat_sq8_index(folder, device=0, row_range=None, devices=None, chunk=1 << 20):
@@ -462,6 +466,8 @@ def _load_flat_sq8_index(folder, device=0, row_range=None, devices=None, chunk=1
         raise ValueError(f"row_range {row_range} is outside the saved shard's rows [{slo}, {shi})")
     index = Mi355xIndex(man["d"], device=device, id_base=lo)
     index.set_sq8_quantizer(vmin, vdiff)
+    if read_threshold_scan(folder, man):
+        index.sq8_threshold_scan = True
     index.reserve(hi - lo)
     for o in range(lo - slo, hi - slo, chunk):
         index.add_sq8_codes(np.asarray(codes[o:min(o + chunk, hi - slo)]))

@@ -409,14 +409,33 @@ int knnx_ivfsq_threshold_stats(knnx_index* ix, int64_t* queries, int64_t* launch
  * [n][d] in id order; knnx_reserve, knnx_reset, knnx_search, knnx_search_device, knnx_reconstruct (decoded rows, as the R of
  * knnx_search), knnx_ntotal, knnx_dim and knnx_set_id_base serve the index.  knnx_sq8_get_quantizer: vmin / vdiff as given;
  * knnx_sq8_get_codes: codes [ntotal][d] (host); knnx_sq8: 1 on a flat SQ8 index, 0 otherwise.
- * Not served (KNNX_E_UNSUPPORTED, the message says "flat SQ8"): knnx_range_search*, k > 64, knnx_search_dedup, knnx_search_filtered,
- * knnx_attach_device_f16, knnx_synth_fill, the IVF build protocol, the append / merge / remove calls, knnx_shards_adopt. */
+ * Not served (KNNX_E_UNSUPPORTED, the message says "flat SQ8"): knnx_range_search* and k > 64 (unless switched on, below),
+ * knnx_search_dedup, knnx_search_filtered, knnx_attach_device_f16, knnx_synth_fill, the IVF build protocol, the append / merge / remove
+ * calls, knnx_shards_adopt.
+ * Threshold scan: k > 64 and range_search.  A switch per index, OFF by default: an index nobody switched on is exactly the block
+ * above, refusals included, and allocates and launches nothing of this.
+ * knnx_sq8_set_threshold_scan: any flat SQ8 index, any time; KNNX_E_STATE on any other index (the message says "flat SQ8").
+ * knnx_sq8_threshold_scan: 0 / 1; 0 on any other or a null index.  With the switch ON:
+ *   search    64 < k <= 131072 through knnx_search: the top k rows by (score descending, id ascending), padded with -1 / -FLT_MAX.  A
+ *             group of queries takes the route its size takes at k <= 64 (1 .. 32: the list scan; more: the one-pass batch scan) with
+ *             the same operands in the same order, so the first 64 results of a k > 64 search equal the k = 64 search of the same
+ *             batch bit for bit, D and I.  How: the route's scan in threshold mode (every row scoring > t is a hit) with t walked
+ *             down from the query's 64th score until at least k rows pass, one launch and one synchronisation per step for the whole
+ *             group -- the batch route still reads every code byte ONCE per step; the hits are ranked on the host.
+ *   range     knnx_range_search / knnx_range_search_once: all rows whose score is > thresh (strict), ids ascending inside each
+ *             query; two-call protocol, the _once return value 1 and KNNX_E_STATE on mismatching lims as for the flat fp16 index.
+ * knnx_search_device, knnx_search_dedup, knnx_search_filtered and the coalescer stay as above and keep their messages.
+ * knnx_sq8_threshold_stats: counters since the index was created -- queries served with k > 64, threshold-scan launches (one serves
+ * a whole group of queries), launches summed over the queries that took part in them, hits fetched to the host; any pointer may be null. */
 int knnx_sq8_set_quantizer(knnx_index* ix, const float* vmin, const float* vdiff);
 int knnx_sq8_get_quantizer(knnx_index* ix, float* vmin, float* vdiff);
 int knnx_sq8(const knnx_index* ix); /* 0 / 1 */
 int knnx_sq8_add_codes(knnx_index* ix, const uint8_t* codes, int64_t n);
 int knnx_sq8_add_device_f16(knnx_index* ix, const void* rows_dev_f16, int64_t n);
 int knnx_sq8_get_codes(knnx_index* ix, uint8_t* codes);
+int knnx_sq8_set_threshold_scan(knnx_index* ix, int on);
+int knnx_sq8_threshold_scan(const knnx_index* ix);   /* 0 / 1; 0 on any other or a null index */
+int knnx_sq8_threshold_stats(knnx_index* ix, int64_t* queries, int64_t* launches, int64_t* query_scans, int64_t* hits);
 /* The training kernel (faiss RS_minmax with argument 0): per-column min and max of n fp16 rows [n][d] in HBM, 0 < d <= 1280, n > 0 ->
  * host f32 vmin_out [d], vmax_out [d].  Min and max do not depend on the order of the rows: bit-equal to numpy's
  * x.astype(float32).min(0) / .max(0).  `stream`: hipStream_t or NULL; synchronous. */
